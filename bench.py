@@ -3,17 +3,23 @@
 bench.py -- throughput of the F2CNN hot path on MI355X, in audio-seconds per second.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg3|cfg5|cfg5r|cfg2|cfg4] [--batch B]
+                    [--dump-outputs DIR] [--full]
 
 One "step" = one pass of the hot path over synthetic utterances that are already resident in HBM (int16 waves in,
-float64 envelopes out, device pointers through the C ABI). Workloads (BASELINE.json configs):
+float64 envelopes out, device pointers through the C ABI). A plain run sets up, warms up, times the K steps and prints the
+headline line (value, ms_per_step, config); `--full` adds what takes measurements of its own or events in the timed
+region: per-kernel times and the roofline, the routing pass, the CPU baselines and, for the default workload, the side
+blocks below. `--dump-outputs DIR` writes a fixed, seeded sample of the last timed step's outputs (envelopes, filterbank
+or CNN scores and labels) as .npy files; the inputs are seeded, so two builds can be compared output for output.
+Workloads (BASELINE.json configs):
   cfg3   fused filterbank + Hilbert envelope + 50 Hz LPF, 1000 x 1 s utterances per GPU, 128 channels   (weak scaling)
   cfg5   the 10 000-utterance corpus (utterance u = seed 2029+u), rank r owns utterances r::G, processed in
          HBM-sized batches through the same fused call; a step = one pass over the rank's shard            (strong scaling)
   cfg5r  the same corpus with lengths U[16000, 64000] samples (SURVEY 8d secondary run)
   cfg2   128-channel filterbank only, 256 utterances
   cfg4   `cnn eval` end to end (filterbank, envelope, every-sample windows, CNN), 8 utterances
-Default workload: cfg3 at --gpus 1 (plus side blocks: float64-FFT timing, cfg4, cfg5, end-to-end files), cfg5 at
---gpus N > 1.
+Default workload: cfg3 at --gpus 1 (with --full plus side blocks: float64-FFT timing, cfg4, cfg5, end-to-end files), cfg5
+at --gpus N > 1.
 
 Multi-GPU: one process per GPU, no data-path collective (utterances are independent; reference analogue: the
 Pool(cpu_count()) over files at scripts/processing/GammatoneFiltering.py:121-125). `python bench.py --gpus N` starts
@@ -381,23 +387,80 @@ class DspJob:
         self.ctx.free(self.d_out)
 
 
-def timed(ctx, ranks, step, steps, warmup):
-    """W untimed steps, barrier + device sync, K timed steps, device sync. Returns (elapsed_s, prof): the library brackets every
-    kernel group with HIP events inside the timed region (what `roofline.achieved` is made of; measured on cfg4, 34 event pairs
-    per step: a pass without them is no faster)."""
+def timed(ctx, ranks, step, steps, warmup, prof=True):
+    """W untimed steps, barrier + device sync, K timed steps, device sync. Returns (elapsed_s, prof): with `prof` the library
+    brackets every kernel group with HIP events inside the timed region (what `roofline.achieved` is made of; measured on cfg4,
+    34 event pairs per step: a pass without them is no faster); without it `prof` is {}."""
     for _ in range(warmup):
         step()
     ctx.synchronize()
     ranks.barrier()
-    ctx.prof_enable(True)
+    if prof:
+        ctx.prof_enable(True)
     t0 = time.perf_counter()
     for _ in range(steps):
         step()
     ctx.synchronize()
     elapsed = time.perf_counter() - t0
+    if not prof:
+        return elapsed, {}
     prof = ctx.prof_get()
     ctx.prof_enable(False)
     return elapsed, prof
+
+
+# ------------------------------------------------------------------------------------------------
+# --dump-outputs: what the timed path computed in its last step, as .npy files (float32 / float64 only)
+# ------------------------------------------------------------------------------------------------
+DUMP_BUDGET_BYTES = 48 << 20     # all files of one run together (ranks share it)
+DUMP_MAX_ROWS = 256
+DUMP_SEED = 20261016
+
+
+def dump_dsp(job, out_dir, name, suffix, budget):
+    """A fixed, seeded sample of whole output rows (utterance, channel) of the job's last step, float64 as the library writes
+    them: <name>.npy (rows, samples) - or, for ragged utterances, the rows concatenated plus <name>_lengths.npy -, and
+    <name>_index.npy = (utterance of the rank's shard, channel) per row. When the batches share one output region only
+    the last batch's outputs are still there, so only its rows are sampled."""
+    C = job.C
+    keep = range(len(job.batches)) if job.resident else [len(job.batches) - 1]
+    first = np.concatenate([[0], np.cumsum([nb for _, _, nb in job.batches])])
+    base, lens, utt = [], [], []
+    for i in keep:
+        _, off, nb = job.batches[i]
+        base.append(job.out_ptr[i] + 8 * C * off[:-1])
+        lens.append(np.diff(off))
+        utt.append(first[i] + np.arange(nb))
+    base, lens, utt = np.concatenate(base), np.concatenate(lens), np.concatenate(utt)
+    k = int(min(DUMP_MAX_ROWS, budget // (8 * max(int(lens.max()), 1)), len(lens) * C))
+    rows = np.sort(np.random.default_rng(DUMP_SEED).choice(len(lens) * C, size=k, replace=False))
+    u, c = rows // C, rows % C
+    parts = []
+    for ui, ci in zip(u, c):
+        row = np.empty(int(lens[ui]), np.float64)
+        job.ctx.d2h(row, int(base[ui] + 8 * ci * lens[ui]))
+        parts.append(row)
+    if len(set(lens[u].tolist())) <= 1:
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), np.stack(parts) if parts else np.zeros((0, 0)))
+    else:
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), np.concatenate(parts))
+        np.save(os.path.join(out_dir, f"{name}_lengths{suffix}.npy"), lens[u].astype(np.float64))
+    np.save(os.path.join(out_dir, f"{name}_index{suffix}.npy"), np.stack([utt[u], c], axis=1).astype(np.float64))
+
+
+def dump_cnn(ctx, d_scores, d_labels, n, out_dir, suffix, budget):
+    """scores (windows, 2) float32 and labels (windows,) as float32 of the last cfg4 step; above the budget a fixed, seeded
+    sample of windows, whose indices go to cnn_index.npy."""
+    scores = np.empty((n, 2), np.float32)
+    labels = np.empty(n, np.uint8)
+    ctx.d2h(scores, d_scores)
+    ctx.d2h(labels, d_labels)
+    if 12 * n > budget:
+        pick = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=budget // 12, replace=False))
+        scores, labels = scores[pick], labels[pick]
+        np.save(os.path.join(out_dir, f"cnn_index{suffix}.npy"), pick.astype(np.float64))
+    np.save(os.path.join(out_dir, f"cnn_scores{suffix}.npy"), scores)
+    np.save(os.path.join(out_dir, f"cnn_labels{suffix}.npy"), labels.astype(np.float32))
 
 
 def dsp_kernel_report(prof, steps, C, samples_per_step, mode, handoff_bytes, routed=0, flagged=0):
@@ -435,8 +498,10 @@ def dsp_kernel_report(prof, steps, C, samples_per_step, mode, handoff_bytes, rou
     return rep
 
 
-def dsp_run(ctx, ranks, coefs, C, N, workload, fft, steps, warmup, batch, corpus):
-    """One DSP workload on every rank; rank 0 gets the merged result (host-side merge, no collective on the data path)."""
+def dsp_run(ctx, ranks, coefs, C, N, workload, fft, steps, warmup, batch, corpus, full=True, dump=None):
+    """One DSP workload on every rank; rank 0 gets the merged result (host-side merge, no collective on the data path).
+    Without `full` only the headline figures: no per-kernel events in the timed region, no routing pass, no roofline.
+    `dump` = (directory, file-name suffix, byte budget) for the outputs of the last timed step."""
     rank, world = ranks.rank, ranks.world
     seed = SEEDS[workload]
     mode = "filterbank" if workload == "cfg2" else "both"
@@ -478,16 +543,34 @@ def dsp_run(ctx, ranks, coefs, C, N, workload, fft, steps, warmup, batch, corpus
     precision = _lib.FFT_F32 if fft == "f32" else _lib.FFT_F64
     job = DspJob(ctx, coefs, C, waves, lens, batch, mode, lpf, precision)
     del waves
-    elapsed, prof = timed(ctx, ranks, job.step, steps, warmup)
+    elapsed, prof = timed(ctx, ranks, job.step, steps, warmup, prof=full)
     flagged = int(ctx.get_option("spectral_flagged")) if mode == "both" else 0
     samples = job.total_samples
+    if dump:
+        dump_dsp(job, dump[0], "filterbank" if mode == "filterbank" else "envelopes", dump[1], dump[2])
+    config = {"workload": label, "channels": C, "sample_rate": FS, "lpf_hz": lpf, "utterances_per_step": utts,
+              "launch_batch": batch, "launches_per_step_per_gpu": len(job.batches), "outputs_resident_in_hbm": job.resident,
+              "route": ("k_spectral_envelope (one kernel per row class; k_utterance_spectrum + k_tail_state once per "
+                        "utterance) where it appears in `kernels`, else k_erb_filterbank -> k_envelope"),
+              "parallelism": f"utterance-sharded x{world}, no collective"}
+    if not full:
+        job.free()
+        res = ranks.gather({"elapsed": elapsed, "samples_per_step": samples, "flagged": flagged})
+        if rank != 0:
+            return None
+        elapsed = max(r["elapsed"] for r in res)
+        total_samples = sum(r["samples_per_step"] for r in res)
+        config["utterances_sent_back_by_the_accuracy_guard"] = sum(r["flagged"] for r in res)
+        return {"value": round(total_samples / FS * steps / elapsed, 1), "ms_per_step": round(elapsed / steps * 1e3, 4),
+                "steps": steps, "scaling": scaling, "lpf": lpf, "mode": mode, "config": config,
+                "per_rank": [{"elapsed_s": round(r["elapsed"], 4), "audio_s_per_step": round(r["samples_per_step"] / FS, 1)}
+                             for r in res]}
     routed_s, flagged_s = job.routing()
     # hand-off bytes per sample-channel, as f2_plan_handoff decides: float32 when the FFT is float32, else float64
     handoff = 4 if fft == "f32" else 8
     mine = {"elapsed": elapsed, "samples_per_step": samples,
             "kernels": dsp_kernel_report(prof, steps, C, samples, mode, handoff, routed_s, flagged_s), "flagged": flagged,
             "routed_samples": routed_s, "flagged_samples": flagged_s}
-    resident, nlaunch = job.resident, len(job.batches)
     job.free()
     res = ranks.gather(mine)
     if rank != 0:
@@ -517,13 +600,8 @@ def dsp_run(ctx, ranks, coefs, C, N, workload, fft, steps, warmup, batch, corpus
         roof["traffic_over_algorithmic"] = round(sum(traffic.values()) / (need_step / world), 3)
     return {"value": round(total_samples / FS * steps / elapsed, 1), "ms_per_step": round(step_s * 1e3, 4), "steps": steps,
             "scaling": scaling, "lpf": lpf, "mode": mode, "roofline": roof, "kernels": kern,
-            "config": {"workload": label, "channels": C, "sample_rate": FS, "lpf_hz": lpf, "utterances_per_step": utts,
-                       "launch_batch": batch, "launches_per_step_per_gpu": nlaunch, "outputs_resident_in_hbm": resident,
-                       "route": ("k_spectral_envelope (one kernel per row class; k_utterance_spectrum + k_tail_state once per "
-                                 "utterance) where it appears in `kernels`, else k_erb_filterbank -> k_envelope"),
-                       "utterances_sent_back_by_the_accuracy_guard": sum(r.get("flagged", 0) for r in res),
-                       "fraction_of_samples_through_the_spectral_kernel": round(samples_via_spectral / max(total_samples, 1), 4),
-                       "parallelism": f"utterance-sharded x{world}, no collective"},
+            "config": {**config, "utterances_sent_back_by_the_accuracy_guard": sum(r.get("flagged", 0) for r in res),
+                       "fraction_of_samples_through_the_spectral_kernel": round(samples_via_spectral / max(total_samples, 1), 4)},
             "per_rank": [{"elapsed_s": round(r["elapsed"], 4), "audio_s_per_step": round(r["samples_per_step"] / FS, 1)}
                          for r in res]}
 
@@ -531,7 +609,9 @@ def dsp_run(ctx, ranks, coefs, C, N, workload, fft, steps, warmup, batch, corpus
 # ------------------------------------------------------------------------------------------------
 # side blocks of the default single-GPU run
 # ------------------------------------------------------------------------------------------------
-def block_cfg4(ctx, coefs, precision, B, N, steps, warmup, ranks, with_cpu):
+def block_cfg4(ctx, coefs, precision, B, N, steps, warmup, ranks, with_cpu, full=True, dump=None):
+    """cfg4 on one rank: (block, prof, elapsed_s, flop). Without `full` no per-kernel events and no CNN accounting: the block
+    holds the workload, value and ms_per_step only. `dump` as in dsp_run."""
     from f2cnn_amd import _lib
     from f2cnn_amd.model import F2CNNModel
     model = F2CNNModel.glorot(7)
@@ -546,18 +626,22 @@ def block_cfg4(ctx, coefs, precision, B, N, steps, warmup, ranks, with_cpu):
     def step():
         ctx.eval_batch(hcnn, d_wave, _lib.WAVE_I16, offsets, coefs, B, 128, False, 0.0, precision, 5, 160, d_scores,
                        d_labels, _lib.MEM_DEVICE)
-    elapsed, prof = timed(ctx, ranks, step, steps, warmup)
+    elapsed, prof = timed(ctx, ranks, step, steps, warmup, prof=full)
+    if dump:
+        dump_cnn(ctx, d_scores, d_labels, nb * B, *dump)
     for p in (d_wave, d_scores, d_labels):
         ctx.free(p)
-    cnn_s = prof["k_cnn_forward"][1] / 1e3
     flop = CNN_FLOP_PER_WINDOW * nb * B * steps
     out = {"workload": f"cfg4: cnn eval end to end (filterbank, envelope, every-sample 11x128 windows, normalise, CNN), "
                        f"{B} x {N / FS:g} s utterances per GPU = {B * nb} windows, Glorot weights seed 7",
            "value": round(B * N / FS * steps / elapsed, 2), "unit": "audio-seconds/s", "steps": steps,
-           "ms_per_step": round(elapsed / steps * 1e3, 3),
-           "cnn": {"launch_groups": prof["k_cnn_forward"][0], "ms_per_step": round(cnn_s / steps * 1e3, 3),
-                   **cnn_accounting(ctx, flop, cnn_s, nb * B * steps)},
-           "kernels_ms_per_step": {k: round(ms / steps, 3) for k, (n, ms) in prof.items()}}
+           "ms_per_step": round(elapsed / steps * 1e3, 3)}
+    if not full:
+        return out, prof, elapsed, flop
+    cnn_s = prof["k_cnn_forward"][1] / 1e3
+    out.update({"cnn": {"launch_groups": prof["k_cnn_forward"][0], "ms_per_step": round(cnn_s / steps * 1e3, 3),
+                        **cnn_accounting(ctx, flop, cnn_s, nb * B * steps)},
+                "kernels_ms_per_step": {k: round(ms / steps, 3) for k, (n, ms) in prof.items()}})
     if with_cpu:
         out["cpu_baseline"] = cpu_baseline_cnn(SEEDS["cfg4"], N)
         out["gpu_over_cpu"] = round(out["value"] / out["cpu_baseline"]["value"], 1)
@@ -727,8 +811,8 @@ def block_end_to_end(n_files, cpu_files, with_cpu, local=0):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--steps", type=int, default=None, help="timed steps (default: 20; 3 for cfg4 and cfg5r)")
+    ap.add_argument("--warmup", type=int, default=None, help="untimed steps before them (default: 3; 1 for cfg4 and cfg5r)")
     ap.add_argument("--workload", default=None, choices=["cfg2", "cfg3", "cfg4", "cfg5", "cfg5r"])
     ap.add_argument("--batch", type=int, default=None, help="utterances per launch (default: the config's)")
     ap.add_argument("--corpus", type=int, default=CORPUS, help="utterances in the cfg5 corpus")
@@ -741,6 +825,12 @@ def main():
     ap.add_argument("--e2e-files", type=int, default=256)
     ap.add_argument("--dry-run", action="store_true",
                     help="no GPU: ranks only shard + generate the corpus and meet for the merge (CPU test of the N > 1 path)")
+    ap.add_argument("--full", action="store_true",
+                    help="also what the headline does not need: per-kernel events and roofline, the routing pass, CPU "
+                         "baselines and (default workload) the side blocks")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step to DIR/<name>.npy (a fixed, seeded sample, "
+                         f"at most {DUMP_BUDGET_BYTES >> 20} MiB in all)")
     args = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -757,6 +847,11 @@ def main():
         local = 0
     args.gpus = world
     workload = args.workload or ("cfg3" if world == 1 else "cfg5")
+    short = workload in ("cfg4", "cfg5r")
+    args.steps = (3 if short else 20) if args.steps is None else args.steps
+    args.warmup = (1 if short else 3) if args.warmup is None else args.warmup
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
 
     if args.dry_run:
         ranks = Ranks(rank, world)
@@ -778,29 +873,32 @@ def main():
     coefs = filters.make_erb_filters(FS, filters.centre_freqs(FS, C, 100))
     precision = _lib.FFT_F32 if args.fft == "f32" else _lib.FFT_F64
     seed = SEEDS[workload]
-    with_cpu = not args.no_cpu_baseline
+    with_cpu = args.full and not args.no_cpu_baseline
+    dump = None
+    if args.dump_outputs:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        dump = (args.dump_outputs, f"_rank{rank}" if world > 1 else "", DUMP_BUDGET_BYTES // world)
     out = None
 
     if workload == "cfg4":
         if C != 128:
             raise SystemExit("cfg4 uses the 11 x 128 network")
-        if args.steps == 20 and args.warmup == 3:
-            args.steps, args.warmup = 3, 1
         B = args.batch or 8
         blk, prof, elapsed, flop = block_cfg4(ctx, coefs, precision, B, N, args.steps, args.warmup, ranks,
-                                              with_cpu and rank == 0)
+                                              with_cpu and rank == 0, full=args.full, dump=dump)
         res = ranks.gather({"elapsed": elapsed, "audio_s": B * N / FS * args.steps})
         if rank == 0:
             elapsed = max(r["elapsed"] for r in res)
-            cnn_s = prof["k_cnn_forward"][1] / 1e3
             out = {"metric": "audio-seconds/sec through filterbank+envelope+CNN (HIP, 1 MI355X per rank)",
                    "value": round(sum(r["audio_s"] for r in res) / elapsed, 2), "unit": "audio-seconds/s",
                    "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
                    "ms_per_step": round(elapsed / args.steps * 1e3, 4), "higher_is_better": True, "scaling": "weak",
                    "vs_baseline": None, "dtype": f"f64 IIR + {args.fft} FFT + f32 CNN (conv2-conv4, dense1 products as 3 split-fp16 MFMAs, f32 accumulate)", "data": "synthetic",
                    "config": {"workload": blk["workload"], "batch_per_gpu": B, "channels": C, "samples_per_utterance": N,
-                              "sample_rate": FS, "lpf_hz": 0, "parallelism": f"utterance-sharded x{world}, no collective"},
-                   "roofline": {"bound": "mfma", "kernel": "k_cnn_forward",
+                              "sample_rate": FS, "lpf_hz": 0, "parallelism": f"utterance-sharded x{world}, no collective"}}
+        if rank == 0 and args.full:
+            cnn_s = prof["k_cnn_forward"][1] / 1e3
+            out.update({"roofline": {"bound": "mfma", "kernel": "k_cnn_forward",
                                 "achieved": round(blk["cnn"].get("issued_TFLOPps", blk["cnn"]["TFLOPps"]) * 1e3, 1),
                                 "peak": blk["cnn"]["peak_TFLOPps"] * 1e3, "unit": "GFLOP/s",
                                 "frac": blk["cnn"]["frac"], "traffic": None, "arithmetic": blk["cnn"]["arithmetic"],
@@ -808,14 +906,13 @@ def main():
                                 "algorithmic_flop_per_launch": flop // prof["k_cnn_forward"][0],
                                 "avg_launch_ms": round(cnn_s * 1e3 / prof["k_cnn_forward"][0], 4),
                                 "launches_timed": prof["k_cnn_forward"][0]},
-                   "kernels": blk["kernels_ms_per_step"], "cpu_baseline": blk.get("cpu_baseline")}
+                   "kernels": blk["kernels_ms_per_step"], "cpu_baseline": blk.get("cpu_baseline")})
             if out["cpu_baseline"]:
                 out["gpu_over_cpu"] = round(out["value"] / out["cpu_baseline"]["value"], 1)
                 out["gpu_over_cpu_all_cores_est"] = all_cores_estimate(out["value"], out["cpu_baseline"])
     else:
-        if args.steps == 20 and args.warmup == 3 and workload == "cfg5r":
-            args.steps, args.warmup = 3, 1
-        run = dsp_run(ctx, ranks, coefs, C, N, workload, args.fft, args.steps, args.warmup, args.batch, args.corpus)
+        run = dsp_run(ctx, ranks, coefs, C, N, workload, args.fft, args.steps, args.warmup, args.batch, args.corpus,
+                      full=args.full, dump=dump)
         if rank == 0:
             out = {"metric": "audio-seconds/sec through filterbank" + ("" if workload == "cfg2" else "+envelope")
                              + " (HIP, 1 MI355X per rank); the +CNN figure of BASELINE's metric is value_with_cnn / blocks.cfg4",
@@ -823,17 +920,19 @@ def main():
                    "warmup": args.warmup, "ms_per_step": run["ms_per_step"], "higher_is_better": True,
                    "scaling": run["scaling"], "vs_baseline": None,
                    "dtype": "f64" if workload == "cfg2" else f"f64 filter state + f64 utterance FFT + {args.fft} row FFT", "data": "synthetic",
-                   "config": run["config"], "roofline": run["roofline"], "kernels": run["kernels"],
-                   "per_rank": run["per_rank"]}
+                   "config": run["config"]}
+            if args.full:
+                out.update({"roofline": run["roofline"], "kernels": run["kernels"]})
+            out["per_rank"] = run["per_rank"]
             if with_cpu:
                 n_cpu = N if workload != "cfg5r" else 40000
                 out["cpu_baseline"] = cpu_baseline(seed, n_cpu, C, run["lpf"], run["mode"], args.cpu_sample)
                 out["gpu_over_cpu"] = round(out["value"] / out["cpu_baseline"]["value"], 1)
                 out["gpu_over_cpu_all_cores_est"] = all_cores_estimate(out["value"], out["cpu_baseline"])
 
-    # side blocks: the other configurations in the same line (default runs only)
+    # side blocks: the other configurations in the same line (default --full runs only)
     blocks = {}
-    if args.workload is None and not args.no_blocks:
+    if args.full and args.workload is None and not args.no_blocks:
         def brief(r):
             return {"workload": r["config"]["workload"], "value": r["value"], "unit": "audio-seconds/s",
                     "steps": r["steps"], "ms_per_step": r["ms_per_step"], "scaling": r["scaling"],

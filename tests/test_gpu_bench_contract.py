@@ -4,7 +4,10 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
+
+from conftest import chan_relerr
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -20,7 +23,8 @@ def run_bench(*args):
 
 
 def test_default_workload_line():
-    d = run_bench("--steps", "3", "--warmup", "1", "--batch", "96", "--corpus", "150", "--e2e-files", "8", "--cpu-sample", "8")
+    d = run_bench("--full", "--steps", "3", "--warmup", "1", "--batch", "96", "--corpus", "150", "--e2e-files", "8",
+                  "--cpu-sample", "8")
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
               "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"):
         assert k in d, k
@@ -73,10 +77,43 @@ def test_two_ranks_on_one_device():
     assert d["ms_per_step"] / 1e3 * d["steps"] <= max(p["elapsed_s"] for p in d["per_rank"]) + 1e-4
 
 
-def test_cnn_workload_line():
-    d = run_bench("--workload", "cfg4", "--steps", "1", "--warmup", "1", "--batch", "2", "--no-cpu-baseline")
+def test_cnn_workload_line(tmp_path):
+    d = run_bench("--full", "--workload", "cfg4", "--steps", "1", "--warmup", "1", "--batch", "2", "--no-cpu-baseline",
+                  "--dump-outputs", str(tmp_path))
     assert d["roofline"]["bound"] == "mfma" and d["roofline"]["kernel"] == "k_cnn_forward"
-    assert 0 < d["roofline"]["frac"] < 1 and d["value"] > 0
+    assert 0 < d["roofline"]["frac"] < 1 and d["value"] > 0 and d["steps"] == 1
+    # the last step's outputs: softmax scores of every window of the two utterances, labels = argmax (ties -> 0)
+    s, lab = np.load(tmp_path / "cnn_scores.npy"), np.load(tmp_path / "cnn_labels.npy")
+    assert s.dtype == lab.dtype == np.float32 and s.shape == (2 * (16000 - 11 * 160), 2) and lab.shape == (s.shape[0],)
+    assert np.allclose(s.sum(axis=1), 1.0, atol=1e-5) and np.array_equal(lab, (s[:, 1] > s[:, 0]).astype(np.float32))
+
+
+def test_plain_line_is_the_headline_only_and_dumps_the_last_step(tmp_path):
+    """A plain run times exactly --steps steps and prints the headline fields without what --full measures on top;
+    --dump-outputs writes a seeded sample of whole (utterance, channel) envelope rows of the last step, float64, and those
+    rows are the oracle's envelopes of the seeded utterances."""
+    import f2cnn_oracle as orc
+    B, N = 16, 16000
+    d = run_bench("--steps", "4", "--warmup", "2", "--batch", str(B), "--dump-outputs", str(tmp_path))
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+              "vs_baseline", "dtype", "data", "config"):
+        assert k in d, k
+    assert d["steps"] == 4 and d["warmup"] == 2 and d["unit"] == "audio-seconds/s" and d["higher_is_better"] is True
+    assert not {"cpu_baseline", "blocks", "roofline", "kernels", "value_with_cnn"} & set(d)
+    assert abs(d["value"] - B / (d["ms_per_step"] / 1e3)) / d["value"] < 0.02
+    files = sorted(tmp_path.iterdir())
+    assert [f.name for f in files] == ["envelopes.npy", "envelopes_index.npy"]
+    assert sum(f.stat().st_size for f in files) <= 64 << 20
+    env, idx = np.load(tmp_path / "envelopes.npy"), np.load(tmp_path / "envelopes_index.npy")
+    assert env.dtype == idx.dtype == np.float64 and env.shape == (256, N) and idx.shape == (256, 2)
+    assert len(np.unique(idx, axis=0)) == 256 and idx[:, 0].max() < B and idx[:, 1].max() < 128
+    import bench
+    from f2cnn_amd.gammatone import filters
+    coefs = filters.make_erb_filters(16000, filters.centre_freqs(16000, 128, 100))
+    for u in np.unique(idx[:, 0])[:3].astype(int):              # cfg3: utterance u of rank 0 = default_rng(2027 + u)
+        ref = orc.filter_and_envelope(bench.synth_utterance(2027 + u, N), coefs, True, 50)
+        rows = np.flatnonzero(idx[:, 0] == u)
+        assert chan_relerr(env[rows], ref[idx[rows, 1].astype(int)]) <= 1e-5, u
 
 
 def test_an_eighth_of_the_corpus_runs_at_the_full_batch_rate():

@@ -6,7 +6,7 @@ mkdir -p $(dirname $out)
 for round in 1 2; do
 for v in tree "$@"; do
   if [ $v = tree ]; then
-    python bench.py --workload cfg3 --steps 20 --warmup 3 > /tmp/ksv.json 2>/dev/null
+    python bench.py --full --workload cfg3 --steps 20 --warmup 3 > /tmp/ksv.json 2>/dev/null
   else
     python tools/bench_with_lib.py tools/libf2cnn_hip_$v.so --workload cfg3 --steps 20 --warmup 3 > /tmp/ksv.json 2>/dev/null
   fi

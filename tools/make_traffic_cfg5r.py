@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """profiles/rNN_x_traffic_cfg5r.json from two rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE) of
-`bench.py --workload cfg5r --corpus N --steps 1 --warmup 1 --no-cpu-baseline`: HBM-side bytes per launch of every kernel of the
+`bench.py --full --workload cfg5r --corpus N --steps 1 --warmup 1 --no-cpu-baseline`: HBM-side bytes per launch of every kernel of the
 ragged pass, and per ROW for the kernels that own rows (gfx950: FETCH_SIZE doubled, MI355X_MICROARCH.md HBM section).
 usage: make_traffic_cfg5r.py <fetch dir> <write dir> <out.json> <corpus>"""
 import collections, csv, glob, json, os, sys
