@@ -311,7 +311,8 @@ class Context:
         return h
 
     def cnn_info(self, handle, key):
-        """f2_cnn_get_info: 'ws_ok', 'ws_dense_ok', 'ws_check_diff', 'ws_dense_check_diff', 'flat'"""
+        """f2_cnn_get_info: 'ws_ok', 'ws_dense_ok', 'ws_check_diff', 'ws_dense_check_diff', 'flat', 'f16x3_ok',
+        'f16x3_check_diff', 'last_input_bound'"""
         v = _d()
         self.check(self.lib.f2_cnn_get_info(self.handle, handle, key.encode(), C.byref(v)))
         return v.value

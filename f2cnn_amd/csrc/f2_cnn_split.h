@@ -12,13 +12,17 @@
 // fewer bits), so every layer's operands are scaled by powers of two first - exact, and taken out of the accumulator again in the
 // layer's epilogue, together with the next layer's scale:
 //   activations entering layer L (conv2, conv3, conv4, dense1) are stored as a * sa_L, sa_L = the largest power of two that keeps
-//     an UPPER BOUND of the layer's input (L1 norms of the weights of the layers before it, network inputs in [0, 1] as
-//     normalizeInput leaves them - Training.py:13-28) at or below 2^14: inputs up to 4 cannot overflow, larger ones give inf / NaN
-//     scores (the float32 kernels, option cnn_f16x3 = 0, take any range);
+//     an UPPER BOUND of the layer's input (L1 norms of the weights of the layers before it, network inputs bounded by B) at or
+//     below 2^14. B = 1 covers the windows normalizeInput leaves in [0, 1] (Training.py:13-28); f2_cnn_forward measures its
+//     input (k_cnn_input_range) and takes the set of B = 2^ceil(log2 max|x|) when that exceeds 1 (f2_cnn.hip: one set per B,
+//     built on first use; inputs for which a scale would leave the clamp [2^-20, 2^20], or inf / NaN, run on the float32 kernels);
 //   weights of layer L are stored as w * sb_L, sb_L = the power of two that puts max |w| into [2^10, 2^11);
 //   the accumulator holds sa_L sb_L (w . a): the epilogue forms relu(acc * c_L + b_L * so_L) with c_L = so_L / (sa_L sb_L) and
 //     so_L = the next layer's sa (1 after dense1) - one fma where there was an addition.
-// conv1 (Cin = 1) has its weights scaled by sa_2 directly, so its outputs are conv2's scaled inputs.
+// conv1 (Cin = 1) has its weights scaled by sa_2 directly, so its outputs are conv2's scaled inputs; where conv1 runs on the
+// matrix cores (k_conv12_ws) its input is split too: x sin (exact), its taps times sw1 = sa_2 / sin, its bias times sa_2, with
+// sin = 1 for B = 1 and 2^14 / B above - |x sin| <= 2^14, so that the inputs of a window far below the batch's maximum (a spike
+// elsewhere) stay in fp16's normal range rather than losing their low bits as subnormal pieces of x / B would.
 #ifndef F2_CNN_SPLIT_H
 #define F2_CNN_SPLIT_H
 
@@ -27,12 +31,14 @@ typedef _Float16 h16x4 __attribute__((ext_vector_type(4)));
 
 #define MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_f16((a), (b), (c), 0, 0, 0)
 
-// powers of two, computed once per network by f2_cnn_create (struct f2_cnn: sc)
+// powers of two, one set per network and input bound B (f2_internal.h: f2_scale_set)
 struct f2_split_scales {
     float sa2;              // scale of conv1's weights and bias = scale of conv2's input
     float c2, c3, c4, cd;   // epilogue multipliers of conv2, conv3, conv4, dense1
     float sin_d;            // what the per-tile dense1 kernel multiplies its input by: 1 when conv4 left it scaled, sa_dense1 when
                             // it comes in true units (window shapes whose conv3 / conv4 run on the float32 kernels)
+    float sin;              // what k_conv12_ws multiplies the network input by before splitting it: 1 (B = 1), 2^14 / B (B > 1)
+    float sw1;              // sa2 / sin: the scale of k_conv12_ws's conv1 taps (its bias takes sa2)
 };
 
 __device__ __forceinline__ void split_h16(float v, _Float16& hi, _Float16& lo) {

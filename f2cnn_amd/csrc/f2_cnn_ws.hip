@@ -201,7 +201,7 @@ constexpr int XR = P12_ROWS + 2, XW = PW + 2;      // raw input region of a task
 constexpr int XIN = XR * XW;                       // 432 floats
 static_assert((XIN + 63) / 64 == 7, "LDS-DMA pieces of the raw input: waves 4-7 take piece w - 4, waves 4-6 also piece w");
 constexpr int XIN_BYTES = ((XIN * 4 + 255) / 256) * 256;
-constexpr int CTAB = 2 * XW + 2;                   // floats: 1, 0, 0, ... - what the upper lane half reads in place of taps 1 .. 7,
+constexpr int CTAB = 2 * XW + 2;                   // floats: 1 / sin, 0, 0, ... (x the input scale sin: 1) - what the upper lane half reads in place of taps 1 .. 7,
 constexpr int CTAB_BYTES = ((CTAB * 4 + 255) / 256) * 256;   // one copy behind EACH raw-input buffer (same offset from either base)
 constexpr int XIN_STRIDE = XIN_BYTES + CTAB_BYTES;
 constexpr int W1_BYTES = 2 * 64 * 16;               // conv1's A operand (W1^T, bias row), hi and lo piece, 16 bytes per lane
@@ -244,7 +244,8 @@ __global__ __launch_bounds__(512) void k_conv12_ws(const float* __restrict__ x, 
 
     if (threadIdx.x < 2 * CTAB) {
         const int b = threadIdx.x >= CTAB ? 1 : 0, e = threadIdx.x - b * CTAB;
-        reinterpret_cast<float*>(lds + b * XIN_STRIDE + XIN_BYTES)[e] = e == 0 ? 1.f : 0.f;
+        // (table[0] carries conv1's bias: 1 / sin, which the input scale sin below brings back to exactly 1)
+        reinterpret_cast<float*>(lds + b * XIN_STRIDE + XIN_BYTES)[e] = e == 0 ? 1.f / S.sin : 0.f;
     }
 
     // conv2 weights of every wave: B operand, [piece][tap][kb][h][cout]
@@ -271,7 +272,8 @@ __global__ __launch_bounds__(512) void k_conv12_ws(const float* __restrict__ x, 
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
         const int tap = 8 * h + j;
-        const float v = (tap < 9 ? w1[(tap < 9 ? tap : 0) * C1 + i] : tap == 9 ? b1[i] : 0.f) * S.sa2;   // conv1 writes conv2's scaled inputs
+        // conv1 writes conv2's scaled inputs: taps x sa_2 / sin for the input x sin, bias x sa_2 (f2_cnn_split.h)
+        const float v = tap < 9 ? w1[(tap < 9 ? tap : 0) * C1 + i] * S.sw1 : tap == 9 ? b1[i] * S.sa2 : 0.f;
         const _Float16 vh = (_Float16)v;
         w1h[j] = vh;
         w1l[j] = (_Float16)(v - (float)vh);
@@ -346,6 +348,10 @@ __global__ __launch_bounds__(512) void k_conv12_ws(const float* __restrict__ x, 
             xv[0] = x0p[0];
 #pragma unroll
             for (int j = 1; j < 8; ++j) xv[j] = x1p[(j / 3) * XW + (j % 3)];
+            if (S.sin != 1.f) {                // (uniform: B = 1, every normalised window, skips the multiplies)
+#pragma unroll
+                for (int j = 0; j < 8; ++j) xv[j] *= S.sin;   // |x sin| <= 2^14: exact (a power of two)
+            }
         } else if (c == 1) {
             w1h = *reinterpret_cast<const h16x8*>(ldsW1);
             w1l = *reinterpret_cast<const h16x8*>(ldsW1 + 64 * 16);
@@ -991,7 +997,7 @@ static void ws_stamp_report(f2_ctx* ctx, const char* name, unsigned long long* d
 }
 #endif
 
-int f2_launch_cnn_ws(f2_ctx* ctx, const f2_cnn* cnn, const float* d_x, int64_t n, void* a2s, float* a4) {
+int f2_launch_cnn_ws(f2_ctx* ctx, const f2_cnn* cnn, const f2_scale_set* S, const float* d_x, int64_t n, void* a2s, float* a4) {
 #ifdef F2_WS_STAMPS
     static unsigned long long* d_stamps = nullptr;
     if (!d_stamps) F2_HIP(ctx, hipMalloc((void**)&d_stamps, sizeof(unsigned long long) * 8 * 8 * 32 * 8));
@@ -1013,8 +1019,8 @@ int f2_launch_cnn_ws(f2_ctx* ctx, const f2_cnn* cnn, const float* d_x, int64_t n
         F2_HIP(ctx, hipFuncSetAttribute((const void*)k_conv12_ws, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS12));
         const unsigned grid = (unsigned)(ntask < grid_max ? ntask : grid_max);
         hipLaunchKernelGGL(k_conv12_ws, dim3(grid), dim3(512), LDS12, ctx->stream, d_x, cnn->t(0), cnn->t(1),
-                           (const h16x8*)(cnn->blob16 + cnn->off16[0]), cnn->sbias + F2_SB_B2, (_Float16*)a2s, (const float*)cnn->zeros, H1, W1,
-                           Wa, xt, (unsigned)ntask, cnn->sc WS_STAMP_PASS);
+                           (const h16x8*)(cnn->blob16 + cnn->off16[0]), S->sbias + F2_SB_B2, (_Float16*)a2s, (const float*)cnn->zeros, H1, W1,
+                           Wa, xt, (unsigned)ntask, S->sc WS_STAMP_PASS);
         F2_HIP(ctx, hipGetLastError());
 #ifdef F2_WS_STAMPS
         ws_stamp_report(ctx, "k_conv12_ws (slot4 / slot5 = VALU phase of waves 4-7 / 0-3 done)", d_stamps);
@@ -1029,8 +1035,8 @@ int f2_launch_cnn_ws(f2_ctx* ctx, const f2_cnn* cnn, const float* d_x, int64_t n
         F2_HIP(ctx, hipFuncSetAttribute((const void*)k_conv34_ws, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS34));
         const unsigned grid = (unsigned)(ntile < grid_max ? ntile : grid_max);
         hipLaunchKernelGGL(k_conv34_ws, dim3(grid), dim3(512), LDS34, ctx->stream, (const uint4*)a2s,
-                           (const h16x8*)(cnn->blob16 + cnn->off16[1]), cnn->sbias + F2_SB_B3I, (const h16x8*)(cnn->blob16 + cnn->off16[2]),
-                           cnn->sbias + F2_SB_B4, a4, (const uint4*)cnn->zeros, Wp1, Wa, xt, (unsigned)ntile, cnn->sc WS_STAMP_PASS);
+                           (const h16x8*)(cnn->blob16 + cnn->off16[1]), S->sbias + F2_SB_B3I, (const h16x8*)(cnn->blob16 + cnn->off16[2]),
+                           S->sbias + F2_SB_B4, a4, (const uint4*)cnn->zeros, Wp1, Wa, xt, (unsigned)ntile, S->sc WS_STAMP_PASS);
         F2_HIP(ctx, hipGetLastError());
 #ifdef F2_WS_STAMPS
         ws_stamp_report(ctx, "k_conv34_ws (waves 0-3 conv3; 4-7 conv4: slot4 = K halves combined + stored, slot5 = LDS-DMA issued)", d_stamps);
@@ -1040,7 +1046,7 @@ int f2_launch_cnn_ws(f2_ctx* ctx, const f2_cnn* cnn, const float* d_x, int64_t n
 }
 
 // dense1 of n windows: a4 (n, K) float32 -> a5 (n, 516) float32
-int f2_launch_dense1_ws(f2_ctx* ctx, const f2_cnn* cnn, const float* a4, int64_t n, int K, float* a5) {
+int f2_launch_dense1_ws(f2_ctx* ctx, const f2_cnn* cnn, const f2_scale_set* S, const float* a4, int64_t n, int K, float* a5) {
     F2_CHECK(ctx, K % D1W_KC == 0 && K >= 2 * D1W_KC && n * (int64_t)K * 4 < (int64_t(1) << 32), F2_ERR_UNSUPPORTED,
              "dense1: %lld windows x %d inputs", (long long)n, K);
 #ifndef F2_D1W_MT
@@ -1061,7 +1067,7 @@ int f2_launch_dense1_ws(f2_ctx* ctx, const f2_cnn* cnn, const float* a4, int64_t
     F2_HIP(ctx, hipMemsetAsync(d_stamps, 0, sizeof(unsigned long long) * 8 * 8 * 32 * 8, ctx->stream));
 #endif
     hipLaunchKernelGGL(k_dense1_ws<MT>, grid, dim3(D1W_THREADS), LDSB, ctx->stream, a4,
-                       (const h16x8*)(cnn->blob16 + cnn->off16[3]), cnn->t(9), a5, K, n, cnn->sc WS_STAMP_PASS);
+                       (const h16x8*)(cnn->blob16 + cnn->off16[3]), cnn->t(9), a5, K, n, S->sc WS_STAMP_PASS);
     F2_HIP(ctx, hipGetLastError());
 #ifdef F2_WS_STAMPS
     ws_stamp_report(ctx, "k_dense1_ws (waves 0-7 of 12; chunk = iteration: +matrix loop = wait for the first weight fragment, +epilogue = four steps issued, slot4 = split + stores done, +barrier = through the barrier)", d_stamps);

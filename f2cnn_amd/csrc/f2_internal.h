@@ -6,6 +6,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <mutex>
 #include <string>
 #include <utility>
 #include <vector>
@@ -118,9 +119,26 @@ struct f2_ctx {
 };
 
 #include "f2_cnn_split.h"
-// offsets (floats) into f2_cnn::sbias: conv2's biases x sa_3; conv3's x sa_3 sb_3 (accumulator-initial form) and x sa_4 (epilogue
-// form); conv4's x sa_dense1
+// offsets (floats) into f2_scale_set::sbias: conv2's biases x sa_3; conv3's x sa_3 sb_3 (accumulator-initial form) and x sa_4
+// (epilogue form); conv4's x sa_dense1
 enum { F2_SB_B2 = 0, F2_SB_B3I = 64, F2_SB_B3F = 128, F2_SB_B4 = 192, F2_SB_FLOATS = 256 };
+
+// One set of the split path's power-of-two scales (f2_cnn_split.h), for network inputs bounded by |x| <= B = 2^e
+struct f2_scale_set {
+    f2_split_scales sc = {1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f};
+    float c2_true = 1.f, sa_d1 = 1.f;   // 1 / (sa_2 sb_2): conv2's epilogue multiplier for outputs in true units; dense1's input scale
+    float* sbias = nullptr;             // biases in the scaled units the split kernels' epilogues use (F2_SB_* offsets), device
+    bool ok = false;                    // every scale inside the clamp [2^-20, 2^20] (always true for B = 1: the inputs the
+                                        // scales were first designed for, kept as they were whatever the weights)
+};
+#define F2_BOUND_EXP_MAX 128            // finite float32 inputs: |x| < 2^128
+
+// What f2_cnn_create keeps of the weights to run the L1 cascade of the scales for any input bound (f2_cnn.hip)
+struct f2_cnn_cascade {
+    std::vector<double> l1[5], absb[5];   // conv1 .. conv4, dense1: per output column, L1 norm of its weights and |bias|
+    double sb[4] = {1.0, 1.0, 1.0, 1.0};  // weight scales of conv2 .. conv4, dense1 (independent of the input bound)
+    std::vector<float> b2, b3, b4;        // biases of conv2 .. conv4 (the sbias forms)
+};
 
 struct f2_cnn {
     int rows = 0, channels = 0, flat = 0;
@@ -129,17 +147,27 @@ struct f2_cnn {
     size_t off[12] = {0};        // element offsets of the 12 tensors in `blob`
     const float* t(int i) const { return blob + off[i]; }
     uint16_t* blob16 = nullptr;  // conv2 .. conv4 and dense1 kernels, scaled and split into two fp16 pieces (f2_cnn_split.h, k_*_h16x3)
-    f2_split_scales sc = {1.f, 1.f, 1.f, 1.f, 1.f, 1.f};   // the power-of-two scales that go with them
-    float c2_true = 1.f, sa_d1 = 1.f;   // 1 / (sa_2 sb_2): conv2's epilogue multiplier for outputs in true units; dense1's input scale
-    float* sbias = nullptr;      // biases in the scaled units the split kernels' epilogues use (F2_SB_* offsets)
     size_t off16[4] = {0};       // element offsets of the four layers in `blob16`
     const void* zeros = nullptr; // 256 zero bytes behind them (source of the padding pixels of f2_cnn_ws.hip's LDS-DMA loads)
+    f2_cnn_cascade cascade;
+    // scale sets by input-bound exponent e (B = 2^e): [0] built by f2_cnn_create, the others on first use by f2_cnn_forward
+    // (f2_cnn_scale_set); each owns its sbias buffer, freed by f2_cnn_destroy
+    mutable std::mutex sets_mu;
+    mutable f2_scale_set* sets[F2_BOUND_EXP_MAX + 1] = {nullptr};
+    mutable double last_input_bound = 0.0;   // B of the last f2_cnn_forward, -1: the float32 kernels ran, 0: none yet
     // f2_cnn_create's self-check of the weight-stationary kernels (hand-placed s_waitcnt around inline-asm loads: correct only
     // while the register allocator of the hipcc that built the library leaves those registers alone) against the per-tile
     // split-bf16 kernels on a fixed batch; a kernel that disagrees is not used with this network
     bool ws_ok = true, ws_dense_ok = true;
     float ws_check_diff = -1.f, ws_dense_check_diff = -1.f;   // max |score difference| measured (-1: not applicable)
+    // ... and of the split path as a whole against the float32 kernels, at B = 1 and B = 2^10: off for this network if it disagrees
+    bool f16x3_ok = true;
+    float f16x3_check_diff = -1.f;
 };
+
+// The scale set for inputs bounded by 2^e, built (and its biases uploaded) on first use. *out = NULL: the split path cannot take
+// such inputs (a scale would leave the clamp) or is off for this network - run the float32 kernels.
+int f2_cnn_scale_set(f2_ctx* ctx, const f2_cnn* cnn, int e, const f2_scale_set** out);
 
 // activation workspace (floats) the CNN needs per window
 size_t f2_cnn_workspace_floats(const f2_cnn* cnn);
@@ -255,13 +283,19 @@ int f2_launch_gather(f2_ctx* ctx, const double* d_env, int C, int64_t N, const i
                      int64_t first_center, int64_t n_windows, int radius, int step, int normalize, float* d_out, int* d_flag);
 // weight-stationary split-bf16 convolutions (f2_cnn_ws.hip): windows whose pooled conv2 output has four rows
 bool f2_cnn_ws_supported(int rows, int channels);
-int f2_launch_dense1_ws(f2_ctx* ctx, const f2_cnn* cnn, const float* a4, int64_t n, int K, float* a5);
-int f2_launch_cnn_ws(f2_ctx* ctx, const f2_cnn* cnn, const float* d_x, int64_t n, void* a2s, float* a4);
-// runs the network on n windows (n <= chunk the workspace was sized for); d_ws: n * workspace floats
-int f2_launch_cnn(f2_ctx* ctx, const f2_cnn* cnn, const float* d_x, int64_t n, float* d_ws, float* d_scores,
+int f2_launch_dense1_ws(f2_ctx* ctx, const f2_cnn* cnn, const f2_scale_set* S, const float* a4, int64_t n, int K, float* a5);
+int f2_launch_cnn_ws(f2_ctx* ctx, const f2_cnn* cnn, const f2_scale_set* S, const float* d_x, int64_t n, void* a2s, float* a4);
+// runs the network on n windows (n <= chunk the workspace was sized for); d_ws: n * workspace floats. S: the scale set of the
+// split path for inputs of this bound (f2_cnn_scale_set), NULL = the float32 kernels
+int f2_launch_cnn(f2_ctx* ctx, const f2_cnn* cnn, const f2_scale_set* S, const float* d_x, int64_t n, float* d_ws, float* d_scores,
                   uint8_t* d_labels);
 // the two halves of f2_launch_cnn (f2_cnn.hip): convolutions per chunk of windows, dense layers over several chunks at once
-int f2_launch_cnn_convs(f2_ctx* ctx, const f2_cnn* cnn, const float* d_x, int64_t n, float* d_ws, float* a4);
-int f2_launch_cnn_dense(f2_ctx* ctx, const f2_cnn* cnn, const float* a4, int64_t n, float* a5, float* d_scores, uint8_t* d_labels);
+int f2_launch_cnn_convs(f2_ctx* ctx, const f2_cnn* cnn, const f2_scale_set* S, const float* d_x, int64_t n, float* d_ws, float* a4);
+int f2_launch_cnn_dense(f2_ctx* ctx, const f2_cnn* cnn, const f2_scale_set* S, const float* a4, int64_t n, float* a5, float* d_scores,
+                        uint8_t* d_labels);
+// k_cnn_input_range (f2_cnn_range.hip) over nwin windows of S floats at d_x: atomicMax of the bit pattern of max |x| over the finite
+// values into d_words[0], of the complement of the quietest window's max |x| into d_words[2], and 1 into d_words[1] if a value is
+// inf / NaN. The caller zeroes the three words first.
+int f2_launch_cnn_input_range(f2_ctx* ctx, const float* d_x, int64_t nwin, int S, unsigned* d_words);
 size_t f2_cnn_flat_floats(const f2_cnn* cnn);    // floats per window of the conv4 output
 size_t f2_cnn_dense_floats(const f2_cnn* cnn);   // ... plus dense1's output

@@ -2,6 +2,8 @@
 // (scripts/CNN/Evaluating.py:42-87): host/device pointer handling, chunking, error flags. Host code only.
 #include "f2_internal.h"
 
+#include <cmath>
+
 namespace {
 
 constexpr int64_t CNN_CHUNK = 16384;  // windows per CNN launch group (activation workspace 1.75 GB, windows 92 MB)
@@ -20,14 +22,60 @@ int read_flag(f2_ctx* ctx, int* value) {
     return F2_OK;
 }
 
-int cnn_forward_device(f2_ctx* ctx, const f2_cnn* cnn, const float* d_x, int64_t n, float* d_scores, uint8_t* d_labels) {
+// Input range of f2_cnn_forward: ctx->flags words RANGE_WORD .. + 2 = bit pattern of max |x| over the finite values, inf / NaN
+// seen, complement of the quietest window's max |x| (word 0 is the gather's flag)
+constexpr int RANGE_WORD = 4;
+// A window whose max |x| lies more than this many binades below the call's bound B loses the low bits of its activations' second
+// fp16 pieces (they fall below fp16's normal range: the scales are the call's, set by its loudest window). Calls with B above
+// 2^QUIET_BINADES and such a window (a spike among normalised windows) take the float32 kernels; up to there no window is
+// served worse than a window whose max is 2^-QUIET_BINADES is at B = 1.
+constexpr int QUIET_BINADES = 4;
+
+int run_input_range(f2_ctx* ctx, const float* d_x, int64_t nwin, int S) {
+    unsigned* words = (unsigned*)ctx->flags.ptr + RANGE_WORD;
+    F2_HIP(ctx, hipMemsetAsync(words, 0, 3 * sizeof(unsigned), ctx->stream));
+    F2_TRY(f2_prof_begin(ctx, F2_K_CNN));
+    F2_TRY(f2_launch_cnn_input_range(ctx, d_x, nwin, S, words));
+    F2_TRY(f2_prof_end(ctx, F2_K_CNN));
+    return F2_OK;
+}
+
+// waits for the stream. The scale set for what run_input_range saw - B = 1 for max |x| <= 1, else B = 2^ceil(log2 max |x|) -
+// and *bound = B; *S = NULL and *bound = -1 (the float32 kernels) after inf / NaN, for a B whose scales leave the clamp, or when
+// B > 2^QUIET_BINADES and a window's max |x| lies below B / 2^QUIET_BINADES
+int pick_scale_set(f2_ctx* ctx, const f2_cnn* cnn, const f2_scale_set** S, double* bound) {
+    F2_HIP(ctx, hipMemcpyAsync(ctx->host_flags + RANGE_WORD, (unsigned*)ctx->flags.ptr + RANGE_WORD, 3 * sizeof(unsigned),
+                               hipMemcpyDeviceToHost, ctx->stream));
+    F2_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    const unsigned mbits = (unsigned)ctx->host_flags[RANGE_WORD], bad = (unsigned)ctx->host_flags[RANGE_WORD + 1];
+    const unsigned qbits = ~(unsigned)ctx->host_flags[RANGE_WORD + 2];
+    *S = nullptr;
+    *bound = -1.0;
+    if (bad) return F2_OK;
+    float m, quiet;
+    memcpy(&m, &mbits, sizeof(m));
+    memcpy(&quiet, &qbits, sizeof(quiet));
+    int e = 0;
+    if (m > 1.f) {
+        int ex;
+        const float f = std::frexp(m, &ex);   // m = f 2^ex, f in [0.5, 1)
+        e = f == 0.5f ? ex - 1 : ex;
+        if (e > QUIET_BINADES && (double)quiet < std::ldexp(1.0, e - QUIET_BINADES)) return F2_OK;
+    }
+    F2_TRY(f2_cnn_scale_set(ctx, cnn, e, S));
+    if (*S) *bound = std::ldexp(1.0, e);
+    return F2_OK;
+}
+
+int cnn_forward_device(f2_ctx* ctx, const f2_cnn* cnn, const f2_scale_set* S, const float* d_x, int64_t n, float* d_scores,
+                       uint8_t* d_labels) {
     const size_t per = f2_cnn_workspace_floats(cnn);
     const int64_t chunk = n < CNN_CHUNK ? n : CNN_CHUNK;
     F2_TRY(f2_reserve(ctx, ctx->work, sizeof(float) * per * (size_t)chunk));
     const size_t xs = (size_t)cnn->rows * cnn->channels;
     for (int64_t s = 0; s < n; s += chunk) {
         const int64_t m = n - s < chunk ? n - s : chunk;
-        F2_TRY(f2_launch_cnn(ctx, cnn, d_x + (size_t)s * xs, m, (float*)ctx->work.ptr, d_scores ? d_scores + 2 * s : nullptr,
+        F2_TRY(f2_launch_cnn(ctx, cnn, S, d_x + (size_t)s * xs, m, (float*)ctx->work.ptr, d_scores ? d_scores + 2 * s : nullptr,
                              d_labels ? d_labels + s : nullptr));
     }
     return F2_OK;
@@ -96,23 +144,46 @@ int f2_cnn_forward(f2_ctx* ctx, const f2_cnn* cnn, const float* x, int64_t n, fl
     F2_CHECK(ctx, n >= 0, F2_ERR_INVALID, "negative window count");
     if (n == 0) return F2_OK;
     F2_CHECK(ctx, x, F2_ERR_INVALID, "x is NULL");
-    if (mem_space == F2_MEM_DEVICE) return cnn_forward_device(ctx, cnn, x, n, scores, labels);
     const size_t xs = (size_t)cnn->rows * cnn->channels;
+    // the split path's scales follow the input (f2_cnn_split.h): a range pass, then the set of its bound
+    const f2_scale_set* S1 = nullptr;
+    F2_TRY(f2_cnn_scale_set(ctx, cnn, 0, &S1));
+    const bool measure = S1 && ctx->opt_cnn_bf16x3;   // (else the float32 kernels run whatever the input)
+    if (mem_space == F2_MEM_DEVICE) {
+        const f2_scale_set* S = nullptr;
+        double bound = -1.0;
+        if (measure) {
+            F2_TRY(run_input_range(ctx, x, n, (int)xs));
+            F2_TRY(pick_scale_set(ctx, cnn, &S, &bound));
+        }
+        F2_TRY(cnn_forward_device(ctx, cnn, S, x, n, scores, labels));
+        cnn->last_input_bound = bound;
+        return F2_OK;
+    }
     const int64_t chunk = n < CNN_CHUNK ? n : CNN_CHUNK;
     F2_TRY(f2_reserve(ctx, ctx->stage_in, sizeof(float) * xs * (size_t)chunk));
     F2_TRY(f2_reserve(ctx, ctx->stage_aux, (sizeof(float) * 2 + 1) * (size_t)chunk + 64));
     float* d_scores = (float*)ctx->stage_aux.ptr;
     uint8_t* d_labels = (uint8_t*)(d_scores + 2 * chunk);
+    double bound = 0.0;   // largest B of the chunks, -1 once one of them ran on the float32 kernels
     for (int64_t s = 0; s < n; s += chunk) {
         const int64_t m = n - s < chunk ? n - s : chunk;
         F2_HIP(ctx, hipMemcpyAsync(ctx->stage_in.ptr, x + (size_t)s * xs, sizeof(float) * xs * (size_t)m,
                                    hipMemcpyHostToDevice, ctx->stream));
-        F2_TRY(cnn_forward_device(ctx, cnn, (const float*)ctx->stage_in.ptr, m, d_scores, d_labels));
+        const f2_scale_set* S = nullptr;
+        double b = -1.0;
+        if (measure) {
+            F2_TRY(run_input_range(ctx, (const float*)ctx->stage_in.ptr, m, (int)xs));
+            F2_TRY(pick_scale_set(ctx, cnn, &S, &b));
+        }
+        bound = b < 0 || bound < 0 ? -1.0 : b > bound ? b : bound;
+        F2_TRY(cnn_forward_device(ctx, cnn, S, (const float*)ctx->stage_in.ptr, m, d_scores, d_labels));
         if (scores)
             F2_HIP(ctx, hipMemcpyAsync(scores + 2 * s, d_scores, sizeof(float) * 2 * (size_t)m, hipMemcpyDeviceToHost, ctx->stream));
         if (labels) F2_HIP(ctx, hipMemcpyAsync(labels + s, d_labels, (size_t)m, hipMemcpyDeviceToHost, ctx->stream));
         F2_HIP(ctx, hipStreamSynchronize(ctx->stream));
     }
+    cnn->last_input_bound = bound;
     return F2_OK;
 }
 
@@ -176,13 +247,15 @@ int f2_eval_utterance(f2_ctx* ctx, const f2_cnn* cnn, const void* wave, int wave
         d_scores = (float*)ctx->stage_aux.ptr;
         d_labels = (uint8_t*)(d_scores + 2 * nb);
     }
+    const f2_scale_set* S1 = nullptr;
+    F2_TRY(f2_cnn_scale_set(ctx, cnn, 0, &S1));   // K3's normalised windows lie in [0, 1] by construction: no range pass
     F2_TRY(reset_flag(ctx));
     const int64_t reach = (int64_t)radius * step;
     for (int64_t s = 0; s < nb; s += chunk) {
         const int64_t m = nb - s < chunk ? nb - s : chunk;
         F2_TRY(f2_launch_gather(ctx, d_env, C, N, nullptr, reach + s, m, radius, step, 1, (float*)ctx->xbuf.ptr,
                                 (int*)ctx->flags.ptr));
-        F2_TRY(f2_launch_cnn(ctx, cnn, (const float*)ctx->xbuf.ptr, m, (float*)ctx->work.ptr,
+        F2_TRY(f2_launch_cnn(ctx, cnn, S1, (const float*)ctx->xbuf.ptr, m, (float*)ctx->work.ptr,
                              d_scores ? d_scores + 2 * s : nullptr, d_labels ? d_labels + s : nullptr));
     }
     if (mem_space == F2_MEM_HOST) {
@@ -268,12 +341,14 @@ int f2_eval_batch(f2_ctx* ctx, const f2_cnn* cnn, const void* wave, int wave_dty
         d_scores = (float*)ctx->stage_aux.ptr;
         d_labels = (uint8_t*)(d_scores + 2 * nb_total);
     }
+    const f2_scale_set* S1 = nullptr;
+    F2_TRY(f2_cnn_scale_set(ctx, cnn, 0, &S1));   // K3's normalised windows lie in [0, 1] by construction: no range pass
     F2_TRY(reset_flag(ctx));
     const int64_t reach = (int64_t)radius * step;
     int64_t done = 0, g0 = 0, gn = 0;      // windows finished before this utterance; first window and size of the open dense group
     auto flush = [&]() -> int {
         if (gn > 0)
-            F2_TRY(f2_launch_cnn_dense(ctx, cnn, d_a4, gn, d_a5, d_scores ? d_scores + 2 * g0 : nullptr, d_labels ? d_labels + g0 : nullptr));
+            F2_TRY(f2_launch_cnn_dense(ctx, cnn, S1, d_a4, gn, d_a5, d_scores ? d_scores + 2 * g0 : nullptr, d_labels ? d_labels + g0 : nullptr));
         g0 += gn;
         gn = 0;
         return F2_OK;
@@ -288,7 +363,7 @@ int f2_eval_batch(f2_ctx* ctx, const f2_cnn* cnn, const void* wave, int wave_dty
             if (gn + m > group_cap) F2_TRY(flush());
             F2_TRY(f2_launch_gather(ctx, env_b, C, N, nullptr, reach + s, m, radius, step, 1, (float*)ctx->xbuf.ptr,
                                     (int*)ctx->flags.ptr));
-            F2_TRY(f2_launch_cnn_convs(ctx, cnn, (const float*)ctx->xbuf.ptr, m, (float*)ctx->work.ptr, d_a4 + flat * (size_t)gn));
+            F2_TRY(f2_launch_cnn_convs(ctx, cnn, S1, (const float*)ctx->xbuf.ptr, m, (float*)ctx->work.ptr, d_a4 + flat * (size_t)gn));
             gn += m;
         }
         done += nb;

@@ -147,7 +147,9 @@ class F2CNNModel:
         return h[1]
 
     def predict(self, x, ctx=None):
-        """Softmax scores (n,2) float32 for x (n, rows, channels[,1]); like keras model.predict."""
+        """Softmax scores (n,2) float32 for x (n, rows, channels[,1]); like keras model.predict, any finite input. The default
+        split-fp16 path scales its operands for the range it measures in x (per chunk of 16384 windows); inputs it cannot take
+        (inf / NaN, or a spike far above the other windows) run on the float32 kernels (include/f2cnn_hip.h: f2_cnn_forward)."""
         ctx = ctx or _lib.default_context()
         x = np.asarray(x)
         if x.ndim == 4 and x.shape[-1] == 1:

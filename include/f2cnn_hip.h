@@ -60,7 +60,9 @@ enum { F2_WAVE_I16 = 0, F2_WAVE_F64 = 1 };
 enum { F2_FFT_F32 = 0, F2_FFT_F64 = 1 };
 
 /* ---- library / context -------------------------------------------------------------------- */
-int f2_version(void);   /* 100 * major + minor; 101 added f2_eval_batch, 102 f2_host_alloc + F2_MEM_HOST_ASYNC, 103 f2_ctx_set_option, 105 f2_spectral_guard_read + f2_cnn_get_info */
+int f2_version(void);   /* 100 * major + minor; 101 added f2_eval_batch, 102 f2_host_alloc + F2_MEM_HOST_ASYNC, 103 f2_ctx_set_option, 105 f2_spectral_guard_read + f2_cnn_get_info,
+                           106 f2_cnn_forward accepts any finite input on the split path (scales from the input's range; the
+                           f2_cnn_get_info keys "f16x3_ok", "f16x3_check_diff", "last_input_bound") */
 int f2_device_count(int* count);
 int f2_ctx_create(int device, f2_ctx** ctx);
 int f2_ctx_destroy(f2_ctx* ctx);
@@ -87,9 +89,11 @@ const char* f2_last_error(f2_ctx* ctx);
  *   "k1_qwaves"      0 / n             waves of the queue launch (0 = from the batch)
  *   "env_pair"       1 / 0             on-chip envelope kernel for rows of 32769..65536 samples
  *   "env_plan4"      0 / 1             four-pass transform plan for every 8193..16384-sample row
- *   "cnn_bf16x3"     1 (default) / 0   conv2..conv4 of f2_cnn_* / f2_eval_* on the bf16 matrix cores with both operands
- *                                      split in two bf16 pieces (three MFMAs per product, float32 accumulation: scores within
- *                                      1e-6 of the float32 matrix path, 2.2 x its speed); 0 = v_mfma_f32_32x32x2_f32 throughout
+ *   "cnn_bf16x3"     1 (default) / 0   (alias "cnn_f16x3") conv2..conv4 + dense1 of f2_cnn_* / f2_eval_* on the fp16 matrix
+ *                                      cores with both operands split in two fp16 pieces, each layer's operands scaled by powers
+ *                                      of two (three MFMAs per product, float32 accumulation: scores at the float32 rounding
+ *                                      level, within 1e-6 of the float32 matrix path, several times its speed; the scales follow
+ *                                      the input's range, see f2_cnn_forward); 0 = v_mfma_f32_32x32x2_f32 throughout
  *   "cnn_ws"         1 (default) / 0   with "cnn_bf16x3", windows of 10 / 11 rows (the reference's 11 x C): persistent weight-
  *                                      stationary kernels (each wave keeps the weights of its role in registers, conv1 on the
  *                                      matrix cores too, one barrier per tile); 0 = one workgroup per tile, weights re-read
@@ -195,6 +199,12 @@ int f2_gather_windows(f2_ctx* ctx, const double* env, int C, int64_t N, const in
  *   conv4 (3,3,64,64),(64) | dense1 (F,516),(516) | dense2 (516,2),(2),  F = flatten size for (rows, channels)
  * f2_cnn_forward: x (n, rows, channels) float32 -> scores (n,2) softmax float32 and
  * labels[i] = scores[i][1] > scores[i][0] (ties -> 0). scores or labels may be NULL.
+ * Any finite input is accepted, as keras model.predict accepts it. With option "cnn_bf16x3" (the default) a pass over x
+ * finds max |x|; the split path then runs with the scales of the input bound B = 1 when max |x| <= 1 (the scales of every
+ * normalised window: f2_eval_* use them without the pass) and B = 2^ceil(log2 max |x|) above that. An input holding inf /
+ * NaN, or one whose B would need a scale outside [2^-20, 2^20], runs on the float32 kernels (option "cnn_bf16x3" = 0), and
+ * its scores are what those give. x in device memory: the call synchronises the stream once (to read the range back);
+ * x in host memory: per chunk of 16384 windows, as before.
  */
 int f2_cnn_create(f2_ctx* ctx, const float* const* tensors, int rows, int channels, f2_cnn** cnn);
 int f2_cnn_destroy(f2_ctx* ctx, f2_cnn* cnn);
@@ -203,7 +213,12 @@ int f2_cnn_destroy(f2_ctx* ctx, f2_cnn* cnn);
  * network: its shape qualifies AND they reproduced the per-tile kernels' scores on f2_cnn_create's self-check batch (their
  * hand-placed memory waits are only valid for the register allocation of the compiler they were validated with; a library
  * built by another hipcc that fails the check falls back to the per-tile kernels and says so on stderr);
- * "ws_check_diff" / "ws_dense_check_diff" = the score differences measured (-1: not applicable). */
+ * "ws_check_diff" / "ws_dense_check_diff" = the score differences measured (-1: not applicable);
+ * "f16x3_ok" = 1 if the split-fp16 path serves this network: f2_cnn_create held it against the float32 kernels on its
+ * self-check batch (inputs in [0, 1), and the same x 2^10 with the scales of B = 2^10) and it agreed to 5e-6, else 0 (the
+ * network runs on the float32 kernels, said on stderr); "f16x3_check_diff" = the larger of the two score differences
+ * measured (-1: no split path); "last_input_bound" = B of the last f2_cnn_forward on this network (a host call of several
+ * chunks: the largest), -1 if the float32 kernels ran, 0 before the first call. */
 int f2_cnn_get_info(f2_ctx* ctx, const f2_cnn* cnn, const char* key, double* value);
 int f2_cnn_forward(f2_ctx* ctx, const f2_cnn* cnn, const float* x, int64_t n, float* scores,
                    uint8_t* labels, int mem_space);
