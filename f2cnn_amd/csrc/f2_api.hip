@@ -32,6 +32,47 @@ int f2_reserve(f2_ctx* ctx, f2_scratch& s, size_t bytes) {
     return F2_OK;
 }
 
+#ifdef F2_STAMPS
+// (sized once for the most rows and phases any launcher stamps: the buffer never moves while a launch that uses it is queued)
+constexpr size_t F2_STAMP_ROWS_MAX = (size_t)128 * 2048, F2_STAMP_PHASES_MAX = 10;
+
+int f2_stamps_buffer(f2_ctx* ctx, size_t rows, int phases, unsigned long long** out) {
+    *out = nullptr;
+    F2_CHECK(ctx, phases >= 1 && (size_t)phases <= F2_STAMP_PHASES_MAX, F2_ERR_INVALID, "%d stamps per workgroup", phases);
+    if (rows > F2_STAMP_ROWS_MAX) return F2_OK;
+    F2_TRY(f2_reserve(ctx, ctx->stamps, sizeof(unsigned long long) * F2_STAMP_ROWS_MAX * F2_STAMP_PHASES_MAX));
+    F2_HIP(ctx, hipMemsetAsync(ctx->stamps.ptr, 0, sizeof(unsigned long long) * rows * phases, ctx->stream));
+    *out = (unsigned long long*)ctx->stamps.ptr;
+    return F2_OK;
+}
+
+int f2_stamps_report(f2_ctx* ctx, const unsigned long long* d_stamps, size_t rows, int phases, const char* const* names,
+                     const char* tag, const char* what, bool residency) {
+    if (!d_stamps) return F2_OK;
+    F2_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    std::vector<unsigned long long> h(rows * phases);
+    F2_HIP(ctx, hipMemcpy(h.data(), d_stamps, sizeof(unsigned long long) * h.size(), hipMemcpyDeviceToHost));
+    std::vector<double> acc(phases, 0.0);
+    unsigned long long t0 = ~0ull, t1 = 0;
+    double life = 0;
+    for (size_t r = 0; r < rows; ++r) {
+        const unsigned long long* st = &h[r * phases];
+        for (int k = 1; k < phases; ++k) acc[k] += (double)(st[k] - st[k - 1]);
+        t0 = std::min(t0, st[0]);
+        t1 = std::max(t1, st[phases - 1]);
+        life += (double)(st[phases - 1] - st[0]);
+    }
+    fprintf(stderr, "%s %s", tag, what);
+    for (int k = 1; k < phases; ++k) fprintf(stderr, " %s=%.0f", names[k], acc[k] / rows);
+    fprintf(stderr, "\n");
+    // residency: sum of workgroup lifetimes / kernel span = workgroups alive at once (chip-wide)
+    if (residency)
+        fprintf(stderr, "%s mean workgroup lifetime %.1f ticks, kernel span %.0f ticks, workgroups alive at once %.1f\n", tag,
+                life / rows, (double)(t1 - t0), life / (double)(t1 - t0));
+    return F2_OK;
+}
+#endif
+
 int f2_upload_async(f2_ctx* ctx, void* d_dst, const void* src, size_t bytes) {
     if (bytes == 0) return F2_OK;
     constexpr size_t RING = size_t(8) << 20, ALIGN = 256;
@@ -217,7 +258,8 @@ int f2_ctx_destroy(f2_ctx* ctx) {
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
     f2_scratch* all[] = {&ctx->coefs, &ctx->offsets, &ctx->stage_in, &ctx->stage_out, &ctx->stage_aux,
-                         &ctx->work,  &ctx->work2,   &ctx->xbuf,      &ctx->flags,    &ctx->gather_log, &ctx->dense_in};
+                         &ctx->work,  &ctx->work2,   &ctx->xbuf,      &ctx->flags,    &ctx->gather_log, &ctx->dense_in,
+                         &ctx->stamps};
     for (f2_scratch* s : all)
         if (s->ptr) (void)hipFree(s->ptr);
     for (auto& v : ctx->prof)
@@ -308,8 +350,8 @@ const opt_entry kOptions[] = {
     {"k1_qwaves", &f2_ctx::opt_k1_qwaves, nullptr, 0, 1 << 20},
     {"env_pair", &f2_ctx::opt_env_pair, nullptr, 0, 1},
     {"env_plan4", &f2_ctx::opt_env_plan4, nullptr, 0, 1},
-    {"cnn_f16x3", &f2_ctx::opt_cnn_bf16x3, nullptr, 0, 1},
-    {"cnn_bf16x3", &f2_ctx::opt_cnn_bf16x3, nullptr, 0, 1},   // the option's name in rounds 3-4 (bf16 pieces then): same switch
+    {"cnn_f16x3", &f2_ctx::opt_cnn_f16x3, nullptr, 0, 1},
+    {"cnn_bf16x3", &f2_ctx::opt_cnn_f16x3, nullptr, 0, 1},   // the option's name in rounds 3-4 (bf16 pieces then): same switch
     {"cnn_ws", &f2_ctx::opt_cnn_ws, nullptr, 0, 1},
     {"cnn_ws_dense", &f2_ctx::opt_cnn_ws_dense, nullptr, 0, 1},
     {"gather_blocked", &f2_ctx::opt_gather_blocked, nullptr, 0, 1},

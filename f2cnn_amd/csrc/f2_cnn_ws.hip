@@ -440,15 +440,10 @@ __global__ __launch_bounds__(512) void k_conv12_ws(const float* __restrict__ x, 
                     else if (f < 16) conv1_stage(k, 1, f - 9);
                 });
             } else {
-#ifndef F2_B_PRIO_STEPS
-#define F2_B_PRIO_STEPS 0
-#endif
-                if (F2_B_PRIO_STEPS > 0) __builtin_amdgcn_s_setprio(1);
                 conv2(k, [&](int f) {
                     if (f < 2) dma_piece(k, f);
                     else if (f < 16 && (f & 1) == 0) conv1_stage(k, 0, (f - 2) >> 1);
                     else if ((f == 3 || f == 5) && pending) store_pooled(k - 1, f - 3);
-                    if (F2_B_PRIO_STEPS > 0 && f == F2_B_PRIO_STEPS - 1) __builtin_amdgcn_s_setprio(0);
                 });
             }
         } else {
@@ -741,10 +736,7 @@ __global__ __launch_bounds__(512) void k_conv34_ws(const uint4* __restrict__ in,
 // 2 KB of LDS reads per 3 MT MFMAs and wave, 22 us with everything else knocked out - and the launch's fixed costs.
 constexpr int D1W_WAVES = 6, D1W_KC = 64, D1W_TILES = 17, D1W_NPAD = D1W_TILES * 32, D1W_N = 516;
 constexpr int D1W_GROUPS = (D1W_TILES + D1W_WAVES - 1) / D1W_WAVES;
-#ifndef F2_D1W_HALVES
-#define F2_D1W_HALVES 2
-#endif
-constexpr int D1W_HALVES = F2_D1W_HALVES;      // row halves of a workgroup: 6 x 2 = 12 waves, three on every SIMD
+constexpr int D1W_HALVES = 2;      // row halves of a workgroup: 6 x 2 = 12 waves, three on every SIMD
 constexpr int D1W_THREADS = D1W_WAVES * D1W_HALVES * 64;
 template <int MT>
 __global__ __launch_bounds__(D1W_THREADS, 3) void k_dense1_ws(const float* __restrict__ a, const h16x8* __restrict__ ws,
@@ -793,9 +785,6 @@ __global__ __launch_bounds__(D1W_THREADS, 3) void k_dense1_ws(const float* __res
     u32x4 ar[2 * PERT];
     auto gload = [](u32x4& dst, const void* p) { asm volatile("global_load_dwordx4 %0, %1, off" : "=&v"(dst) : "v"(p) : "memory"); };
     auto load_a = [&](int kc) {
-#ifdef F2_D1W_KO_A      // timing knock-out: the activations of chunk 0 again (cache hits)
-        kc = 0;
-#endif
 #pragma unroll
         for (int m = 0; m < PERT; ++m) {
             const unsigned char* p = reinterpret_cast<const unsigned char*>(a) + srcoff[m] + kc * (D1W_KC * 4);
@@ -829,9 +818,6 @@ __global__ __launch_bounds__(D1W_THREADS, 3) void k_dense1_ws(const float* __res
     // weight fragments: a ring of four K steps (slot = ks, compile-time)
     u32x4 bh[4], bl[4];
     auto load_b = [&](int step, int slot) {
-#ifdef F2_D1W_KO_W      // timing knock-out (tools/build_variant.sh): every step re-reads the fragment of step `slot` (L1 hits)
-        step = slot;
-#endif
         gload(bh[slot], wh + (int64_t)step * 2 * D1W_NPAD);
         gload(bl[slot], wl + (int64_t)step * 2 * D1W_NPAD);
     };
@@ -844,13 +830,8 @@ __global__ __launch_bounds__(D1W_THREADS, 3) void k_dense1_ws(const float* __res
     auto fetch = [&](const unsigned char* pa, int ks, int set) {
 #pragma unroll
         for (int t = 0; t < MT; ++t) {
-#ifdef F2_D1W_KO_LDSR   // timing knock-out: no LDS reads in the loop
-            fal[set][t] = __builtin_bit_cast(h16x8, bh[t]);
-            fah[set][t] = __builtin_bit_cast(h16x8, bl[t]);
-#else
             fal[set][t] = *reinterpret_cast<const h16x8*>(pa + aoff[ks] + t * 4096 + PIECE);
             fah[set][t] = *reinterpret_cast<const h16x8*>(pa + aoff[ks] + t * 4096);
-#endif
         }
         __builtin_amdgcn_sched_barrier(0);
     };
@@ -911,13 +892,9 @@ __global__ __launch_bounds__(D1W_THREADS, 3) void k_dense1_ws(const float* __res
         for (int m = 0; m < 2 * PERT; ++m) asm volatile("" : "+v"(ar[m]));
         step_mfmas(3, 1);
         WS_STAMP(kc, 2);
-#ifndef F2_D1W_KO_STORE  // timing knock-out: no split, no LDS stores
         store_a((kc + 1) & 1);                                       // (that buffer was read in chunk kc - 1: behind that chunk's barrier)
-#endif
         WS_STAMP(kc, 4);
-#ifndef F2_D1W_KO_BAR    // timing knock-out: no barrier
         __syncthreads();
-#endif
         WS_STAMP(kc, 3);
     }
     {
@@ -1049,15 +1026,8 @@ int f2_launch_cnn_ws(f2_ctx* ctx, const f2_cnn* cnn, const f2_scale_set* S, cons
 int f2_launch_dense1_ws(f2_ctx* ctx, const f2_cnn* cnn, const f2_scale_set* S, const float* a4, int64_t n, int K, float* a5) {
     F2_CHECK(ctx, K % D1W_KC == 0 && K >= 2 * D1W_KC && n * (int64_t)K * 4 < (int64_t(1) << 32), F2_ERR_UNSUPPORTED,
              "dense1: %lld windows x %d inputs", (long long)n, K);
-#ifndef F2_D1W_MT
-#define F2_D1W_MT 3
-#endif
-    constexpr int MT = F2_D1W_MT;
-#ifdef F2_D1W_ONE_WG     // timing experiment: one workgroup per CU
-    constexpr int LDSB = 100 * 1024;
-#else
+    constexpr int MT = 3;   // M tiles of 32 windows per wave: 96 windows per weight fragment
     constexpr int LDSB = 2 * 2 * 32 * MT * D1W_HALVES * 128;
-#endif
     F2_HIP(ctx, hipFuncSetAttribute((const void*)k_dense1_ws<MT>, hipFuncAttributeMaxDynamicSharedMemorySize, LDSB));
     const int64_t nrb = (n + 32 * MT * D1W_HALVES - 1) / (32 * MT * D1W_HALVES);
     const dim3 grid((unsigned)((nrb + 7) / 8 * 8 * D1W_GROUPS));

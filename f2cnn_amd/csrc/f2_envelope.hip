@@ -41,20 +41,6 @@ using namespace f2fft;
 
 namespace {
 
-// Diagnostic build only (-DF2_STAMPS): wave 0 of every workgroup records s_memrealtime (100 MHz) at the phase boundaries.
-#ifdef F2_STAMPS
-#define F2_STAMP(k)                                          \
-    do {                                                     \
-        __builtin_amdgcn_sched_barrier(0);                   \
-        st[k] = __builtin_amdgcn_s_memrealtime();              \
-        __builtin_amdgcn_sched_barrier(0);                   \
-    } while (0)
-#else
-#define F2_STAMP(k) \
-    do {            \
-    } while (0)
-#endif
-
 
 // (f2_envelope_flagged.hip compiles this file once more with F2_ENVELOPE_FLAGGED_TU: the body below then becomes the
 // device function envelope_row(P, tw, u, c) that its looping kernel calls; this translation unit's kernel is unchanged)
@@ -97,17 +83,11 @@ __global__ __launch_bounds__((threads_for<F, LOG2H>()), (min_waves_for<F, LOG2H>
     const int64_t off = P.offsets[b];
     const int n = (int)(P.offsets[b + 1] - off);
     const size_t row = (size_t)P.C * (size_t)off + (size_t)c * (size_t)n;
-#ifdef F2_KO_LOAD   // knock-out (timing only): every row reads the first row, so the input comes from cache
-    const double* __restrict__ x = P.gfb;
-#else
     const double* __restrict__ x = P.gfb + row;
-#endif
     double* __restrict__ y = P.env + row;
 
-#ifdef F2_STAMPS
-    unsigned long long st[10] = {0};
-#endif
-    F2_STAMP(0);
+    F2_STAMP_ARRAY(st, 10);   // (-DF2_STAMPS: phase boundaries, tools/k2_stamps.py)
+    F2_STAMP(st, 0);
     // (visible to every wave after the first pass's barrier; pass 0 never reads it)
     for (int i = tid; i < TWL; i += NT) twl[i] = tw[plan_tw_offset(LOG2H, 1) + i];
     // 1. load: point (i, j) of this thread is m = tid + i*NT + j*NB0
@@ -154,30 +134,11 @@ __global__ __launch_bounds__((threads_for<F, LOG2H>()), (min_waves_for<F, LOG2H>
         if ((n & 1) == 0) load_row(x, std::false_type{});
         else load_row(x, std::true_type{});
     }
-    F2_STAMP(1);
-#ifdef F2_FUSE_PROBE
-    // Timing probe (results wrong by ~1e-30): the float64 work a row-parallel filterbank inside this workgroup would
-    // add - F2_FUSE_PROBE FMAs per thread in eight independent chains - to see how it co-schedules with the
-    // transforms of the other workgroup on the CU. Use with -DF2_KO_LOAD.
-    {
-        double acc[8];
-#pragma unroll
-        for (int q = 0; q < 8; ++q) acc[q] = (double)v[q].re;
-        const double ca = 0.999999 + 1e-9 * tid, cb = 1e-7;
-        for (int it = 0; it < F2_FUSE_PROBE / 8; ++it) {
-#pragma unroll
-            for (int q = 0; q < 8; ++q) acc[q] = fma(acc[q], ca, cb);
-        }
-        double sum = 0;
-#pragma unroll
-        for (int q = 0; q < 8; ++q) sum += acc[q];
-        v[0].re += (F)(sum * 1e-30);
-    }
-#endif
+    F2_STAMP(st, 1);
     // 2. forward transform (first pass straight from the registers)
     constexpr bool T0R = derive_tw0<F, LOG2H>();
     fft_all<F, LOG2H, false, PT, NT, T0R>(lds, tw, twl, tid, v);
-    F2_STAMP(2);
+    F2_STAMP(st, 2);
     // 3. packed spectrum of the Hilbert transform, conjugated and scaled by 1/H for step 4:
     //    W[k] = i sin(t_k) Z[k] + cos(t_k) conj(Z[H-k]), W[0] = 0. Either folded into the first pass of
     //    step 4 (fuse_hilbert) or one sweep over the pairs (k, H-k) here, all loads issued up front.
@@ -212,12 +173,12 @@ __global__ __launch_bounds__((threads_for<F, LOG2H>()), (min_waves_for<F, LOG2H>
         }
         __syncthreads();
     }
-    F2_STAMP(3);
+    F2_STAMP(st, 3);
     // 4. inverse transform (forward transform of the conjugate); outputs stay in v
     fft_all<F, LOG2H, true, PT, NT, T0R>(lds, tw, twl, tid, v);
     if constexpr (LOG2H == 0) v[0] = {F(0), F(0)};   // H = 1: W[0] = 0, the envelope is |x|
 
-    F2_STAMP(4);
+    F2_STAMP(st, 4);
     // 5. magnitude (in F: the FFT already limits the accuracy to F). The last pass left point j of
     //    butterfly i in v[i*R0 + brev(j)]; the envelope pair replaces it there.
 #pragma unroll
@@ -257,7 +218,7 @@ __global__ __launch_bounds__((threads_for<F, LOG2H>()), (min_waves_for<F, LOG2H>
         }
         return;
     }
-    F2_STAMP(5);
+    F2_STAMP(st, 5);
     if constexpr (FULL0) {
         // block jj = i + ITER0*j of this thread's envelope pairs sits in v[i*R0 + brev(j)]
         constexpr int NBLK = ITER0 * R0;
@@ -271,12 +232,11 @@ __global__ __launch_bounds__((threads_for<F, LOG2H>()), (min_waves_for<F, LOG2H>
                 ei[i + ITER0 * j] = v[i * R0 + brev<R0>(j)].im;
             }
         lowpass_pairs_store<F, NT, NBLK>(er, ei, P.a1, P.b0, smem, y, n, tid);
+        F2_STAMP(st, 6);
 #ifdef F2_STAMPS
-        F2_STAMP(6);
         st[7] = st[8] = st[9] = st[6];
-        if (tid == 0 && P.stamps)
-            for (int k = 0; k < 10; ++k) P.stamps[(size_t)blockIdx.x * 10 + k] = st[k];
 #endif
+        F2_STAMP_STORE(st, 10, P.stamps);
         return;
     }
     // With the low-pass the envelope goes to LDS, TRANSPOSED: thread t will own the contiguous samples
@@ -297,7 +257,7 @@ __global__ __launch_bounds__((threads_for<F, LOG2H>()), (min_waves_for<F, LOG2H>
     }
     __syncthreads();
 
-    F2_STAMP(6);
+    F2_STAMP(st, 6);
     // low-pass: chunked recurrence + multiplicative scan over the chunks. Each thread runs its chunk once
     // from zero state (float64 accumulator, float32 input term) keeping the zero-state responses; the true
     // output is that plus carry * (-a1)^(j+1), one float FMA per sample with the powers from an LDS table.
@@ -362,7 +322,7 @@ __global__ __launch_bounds__((threads_for<F, LOG2H>()), (min_waves_for<F, LOG2H>
         gd *= gd;
     }
     // gd == g^64 now
-    F2_STAMP(7);
+    F2_STAMP(st, 7);
     if (lane == 63) wave_tot[wv] = sc;
     // g^(lane+1) (data independent; placed before the barrier to overlap with the other waves' scans)
     double gl = 1.0, gp = g;
@@ -388,14 +348,11 @@ __global__ __launch_bounds__((threads_for<F, LOG2H>()), (min_waves_for<F, LOG2H>
         }
     }
     __syncthreads();
-    F2_STAMP(8);
+    F2_STAMP(st, 8);
 #pragma unroll 4
     for (int i = 2 * tid; i < n; i += 2 * NT) store_row_pair(y, n, i, (double)rl[tpos(i)], (double)rl[tpos(min(i + 1, n - 1))]);
-#ifdef F2_STAMPS
-    F2_STAMP(9);
-    if (tid == 0 && P.stamps)
-        for (int k = 0; k < 10; ++k) P.stamps[(size_t)blockIdx.x * 10 + k] = st[k];
-#endif
+    F2_STAMP(st, 9);
+    F2_STAMP_STORE(st, 10, P.stamps);
 }
 
 #ifndef F2_ENVELOPE_FLAGGED_TU
@@ -480,12 +437,6 @@ int f2_launch_envelope(f2_ctx* ctx, const double* d_gfb, const int64_t* d_offset
     P.f32_in = f32_in ? 1 : 0;
     P.uflag = d_uflag;
     P.stamps = nullptr;
-#ifdef F2_STAMPS
-    static unsigned long long* d_stamps = nullptr;
-    const size_t nstamp = (size_t)B * C * 10;
-    if (!d_stamps) F2_HIP(ctx, hipMalloc((void**)&d_stamps, sizeof(unsigned long long) * 10 * 128 * 2048));
-    if (nstamp <= (size_t)10 * 128 * 2048) P.stamps = d_stamps;
-#endif
     P.gfb = d_gfb;
     P.env = d_env;
     P.offsets = d_offsets;
@@ -572,14 +523,16 @@ int f2_launch_envelope(f2_ctx* ctx, const double* d_gfb, const int64_t* d_offset
         F2_TRY(f2_upload_async(ctx, ctx->work2.ptr, flat.data(), sizeof(int) * flat.size()));
         d_lists = (int*)ctx->work2.ptr;
     }
+#ifdef F2_STAMPS
+    F2_TRY(f2_stamps_buffer(ctx, (size_t)B * C, 10, &P.stamps));   // (after the pair launcher's report)
+#endif
     size_t pos = 0;
     for (int log2h = 0; log2h < 32; ++log2h) {
         const auto& g = groups[log2h];
         if (g.empty()) continue;
         const int* list = identity ? nullptr : d_lists + pos;
         pos += g.size();
-        const int nthreads = (log2h == 14 && precision == F2_FFT_F32) ? 1024
-                             : (log2h == 13 && precision == F2_FFT_F32) ? F2_THREADS13 : log2h >= 13 ? 512 : 256;   // threads_for<F, LOG2H>()
+        const int nthreads = precision == F2_FFT_F32 ? threads_for<float>(log2h) : threads_for<double>(log2h);
         // one workgroup per row for the utterances ulist[0 .. count)
         auto launch_rows = [&](const int* ulist, size_t count) -> int {
             P.ulist = ulist;
@@ -615,30 +568,10 @@ int f2_launch_envelope(f2_ctx* ctx, const double* d_gfb, const int64_t* d_offset
         F2_TRY(f2_prof_end(ctx, F2_K_ENVELOPE));
     }
 #ifdef F2_STAMPS
-    if (P.stamps) {
-        F2_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        std::vector<unsigned long long> h(nstamp);
-        F2_HIP(ctx, hipMemcpy(h.data(), d_stamps, sizeof(unsigned long long) * nstamp, hipMemcpyDeviceToHost));
-        double acc[10] = {0};
-        const size_t rows = (size_t)B * C;
-        for (size_t r = 0; r < rows; ++r)
-            for (int k = 1; k < 10; ++k) acc[k] += (double)(h[r * 10 + k] - h[r * 10 + k - 1]);
-        static const char* names[10] = {"", "load", "fwd fft", "hilbert pairs", "inv fft", "magnitude", "transposed write",
-                                        "lpf chunk+scan", "lpf carry+apply", "copy out"};
-        fprintf(stderr, "[stamps] mean cycles per workgroup (s_memrealtime, 10 ns ticks):");
-        for (int k = 1; k < 10; ++k) fprintf(stderr, " %s=%.0f", names[k], acc[k] / rows);
-        fprintf(stderr, "\n");
-        // residency: sum of workgroup lifetimes / kernel span = workgroups alive at once (chip-wide)
-        unsigned long long t0 = ~0ull, t1 = 0;
-        double life = 0;
-        for (size_t r = 0; r < rows; ++r) {
-            t0 = std::min(t0, h[r * 10]);
-            t1 = std::max(t1, h[r * 10 + 9]);
-            life += (double)(h[r * 10 + 9] - h[r * 10]);
-        }
-        fprintf(stderr, "[stamps] mean workgroup lifetime %.1f ticks, kernel span %.0f ticks, workgroups alive at once %.1f\n",
-                life / rows, (double)(t1 - t0), life / (double)(t1 - t0));
-    }
+    static const char* names[10] = {"", "load", "fwd fft", "hilbert pairs", "inv fft", "magnitude", "transposed write",
+                                    "lpf chunk+scan", "lpf carry+apply", "copy out"};
+    F2_TRY(f2_stamps_report(ctx, P.stamps, (size_t)B * C, 10, names, "[stamps]",
+                            "mean cycles per workgroup (s_memrealtime, 10 ns ticks):", true));
 #endif
     return F2_OK;
 }

@@ -99,7 +99,7 @@ constexpr int brev(int k) {
 
 // 16-byte store of two consecutive float64 results, non-temporal: the envelopes are written once and not read again by
 // this kernel, and keeping them out of the way of the cache's other lines is worth 4-5 % of K2 (6.14 -> 5.85 ms together
-// with non-temporal loads of the hand-off; -DF2_TEMPORAL restores plain accesses).
+// with non-temporal loads of the hand-off, against plain accesses).
 typedef double f2_d2 __attribute__((ext_vector_type(2)));
 typedef float f2_f2 __attribute__((ext_vector_type(2)));
 // A row of a (C, n) matrix starts on an element boundary, not on a pair boundary (odd n: every other row). Global
@@ -109,25 +109,13 @@ typedef f2_d2 f2_d2u __attribute__((aligned(8)));
 typedef f2_f2 f2_f2u __attribute__((aligned(4)));
 __device__ __forceinline__ void store_pair(double* p, double a, double b) {
     f2_d2u v = {a, b};
-#ifdef F2_TEMPORAL
-    *reinterpret_cast<f2_d2u*>(p) = v;
-#else
     __builtin_nontemporal_store(v, reinterpret_cast<f2_d2u*>(p));
-#endif
 }
 __device__ __forceinline__ f2_d2 load_pair_f64(const double* p) {
-#ifdef F2_TEMPORAL
-    return *reinterpret_cast<const f2_d2u*>(p);
-#else
     return __builtin_nontemporal_load(reinterpret_cast<const f2_d2u*>(p));
-#endif
 }
 __device__ __forceinline__ f2_f2 load_pair_f32(const float* p) {
-#ifdef F2_TEMPORAL
-    return *reinterpret_cast<const f2_f2u*>(p);
-#else
     return __builtin_nontemporal_load(reinterpret_cast<const f2_f2u*>(p));
-#endif
 }
 // Samples i0 and i0 + 1 (i0 even, any value >= 0) of a row of n >= 2 samples, zero beyond its end: one wide load from
 // an address clamped into the row, no divergent loads. ODD = false is the cheaper form for rows of even length (a

@@ -47,18 +47,6 @@ __device__ __forceinline__ void fft13_pass12_merged(cpx<float>* lds, const cpx<f
         cpx<float>& B2 = v[i * 8 + brev<8>(6)];
         cpx<float>& A3 = v[i * 8 + brev<8>(3)];
         cpx<float>& B3 = v[i * 8 + brev<8>(7)];
-#ifdef F2_MERGE_SHFL   // diagnostic: the same exchange through ds_bpermute
-        auto xchg = [&](cpx<float>& A, cpx<float>& B) {
-            const cpx<float> pa = {__shfl_xor(A.re, 32), __shfl_xor(A.im, 32)}, pb = {__shfl_xor(B.re, 32), __shfl_xor(B.im, 32)};
-            const cpx<float> a2 = hl ? pb : A, b2 = hl ? B : pa;
-            A = a2;
-            B = b2;
-        };
-        xchg(A0, B0);
-        xchg(A1, B1);
-        xchg(A2, B2);
-        xchg(A3, B3);
-#else
         asm volatile("s_nop 1\n\t"
                      "v_permlane32_swap_b32 %0, %1\n\t"
                      "v_permlane32_swap_b32 %2, %3\n\t"
@@ -71,7 +59,6 @@ __device__ __forceinline__ void fft13_pass12_merged(cpx<float>* lds, const cpx<f
                      "s_nop 1"
                      : "+v"(A0.re), "+v"(B0.re), "+v"(A0.im), "+v"(B0.im), "+v"(A1.re), "+v"(B1.re), "+v"(A1.im), "+v"(B1.im),
                        "+v"(A2.re), "+v"(B2.re), "+v"(A2.im), "+v"(B2.im), "+v"(A3.re), "+v"(B3.re), "+v"(A3.im), "+v"(B3.im));
-#endif
     }
     const int q = base8 & 15, plo = base8 >> 4;
     const cpx<float>* t2 = twl + OFF2 + plo;
@@ -210,12 +197,8 @@ __device__ __forceinline__ void fft_from_pass0(cpx<float>* lds, const cpx<float>
 template <int PTV, int NT, bool T0REGS>
 __device__ __forceinline__ void fft13_regs_to_regs(cpx<float>* lds, const cpx<float>* __restrict__ tw, const cpx<float>* twl, int tid,
                                                    cpx<float> (&v)[PTV]) {
-#ifdef F2_KS_PLAIN_PASSES   // diagnostic: the four separate passes of f2_fft_lds.h
-    fft_regs_to_regs<float, 13, PTV, NT, T0REGS>(lds, tw, twl, tid, v);
-#else
     fft_pass<float, 13, 0, true, false, PTV, NT, false, T0REGS>(lds, tw, twl, tid, v);
     fft13_pass12_merged<NT, PTV>(lds, twl, tid, v);
     fft_pass<float, 13, 3, false, true, PTV, NT, false, T0REGS>(lds, tw, twl, tid, v);
-#endif
 }
 

@@ -8,31 +8,23 @@
 
 namespace f2fft {
 
-// knock-out (timing only, results wrong): -DF2_KO_BARRIER turns the workgroup barriers of the transforms into nothing
-#ifdef F2_KO_BARRIER
-#define F2_FFT_BARRIER() __builtin_amdgcn_sched_barrier(0)
-#else
-#define F2_FFT_BARRIER() __syncthreads()
-#endif
-
 #ifndef F2_PLAN13_PASSES
 #define F2_PLAN13_PASSES 4
 #endif
-#ifndef F2_THREADS13       // workgroup size of the H = 8192 float transform (diagnostic variants: 256)
-#define F2_THREADS13 512
-#endif
-#ifndef F2_MINWAVES13
-#define F2_MINWAVES13 4
-#endif
-// threads per workgroup: 256, or 512 where 256 threads would need more than 256 registers each
-template <typename F, int LOG2H>
-constexpr int threads_for() {
-    return (LOG2H == 14 && sizeof(F) == 4) ? 1024 : (LOG2H == 13 && sizeof(F) == 4) ? F2_THREADS13 : LOG2H >= 13 ? 512 : 256;
+constexpr int THREADS13 = 512;   // workgroup size of the H = 8192 float transform (256: no faster)
+constexpr int MINWAVES13 = 4;
+// threads per workgroup: 256, or 512 where 256 threads would need more than 256 registers each (the host's launch
+// configuration takes the same function)
+template <typename F>
+constexpr int threads_for(int log2h) {
+    return (log2h == 14 && sizeof(F) == 4) ? 1024 : (log2h == 13 && sizeof(F) == 4) ? THREADS13 : log2h >= 13 ? 512 : 256;
 }
+template <typename F, int LOG2H>
+constexpr int threads_for() { return threads_for<F>(LOG2H); }
 // waves per SIMD the register allocator must leave room for (2 workgroups per CU wherever LDS allows)
 template <typename F, int LOG2H>
 constexpr int min_waves_for() {
-    return (sizeof(F) == 4 && LOG2H == 13) ? F2_MINWAVES13 : (sizeof(F) == 4 && LOG2H == 14) ? 4 : 2;
+    return (sizeof(F) == 4 && LOG2H == 13) ? MINWAVES13 : (sizeof(F) == 4 && LOG2H == 14) ? 4 : 2;
 }
 
 // Whether pass 0 derives its 15 twiddles per butterfly from two loaded ones (radix-16 first pass, float transforms)
@@ -41,11 +33,9 @@ constexpr bool derive_tw0() { return sizeof(F) == 4 && LOG2H >= 11 && LOG2H <= 1
 
 // Whether the Hilbert pair step is folded into the inverse transform's first pass (needs ~3x the pass's points in
 // registers for a moment: only where the register budget allows) or runs as its own sweep over LDS.
-#ifndef F2_FUSE_HILBERT_MAX
-#define F2_FUSE_HILBERT_MAX 12
-#endif
+constexpr int FUSE_HILBERT_MAX = 12;
 template <typename F, int LOG2H>
-constexpr bool fuse_hilbert() { return LOG2H >= 1 && LOG2H <= F2_FUSE_HILBERT_MAX && sizeof(F) == 4; }
+constexpr bool fuse_hilbert() { return LOG2H >= 1 && LOG2H <= FUSE_HILBERT_MAX && sizeof(F) == 4; }
 
 // ---- radix plan: symmetric (first radix == last radix), radices 2..32 ----
 // H = 8192 (the 1 s / 16 kHz row) runs as 16-8-4-16 on 512 threads: 16 points per thread in every pass keeps
@@ -118,20 +108,11 @@ __device__ __forceinline__ void fft_pass(cpx<F>* lds, const cpx<F>* __restrict__
     static_assert(ITER * R <= PTV, "register array too small");
     constexpr bool FULL = NB % NT == 0;   // every thread owns ITER whole butterflies: no guards
     const cpx<F>* __restrict__ twp = tw + plan_tw_offset(LOG2H, PASS);
-#ifdef F2_KO_X12   // knock-out (timing only): no LDS exchange between passes 1 and 2
-    constexpr bool KO_READ = PASS == 2, KO_WRITE = PASS == 1;
-#else
-    constexpr bool KO_READ = false, KO_WRITE = false;
-#endif
-    if constexpr (!SRC_REGS && !KO_READ) {
+    if constexpr (!SRC_REGS) {
 #pragma unroll
         for (int i = 0; i < ITER; ++i) {
             const int bf = tid + i * NT;
-#ifdef F2_KO_LDS
-            if constexpr (false) {
-#else
             if (FULL || bf < NB) {
-#endif
                 // cpad(bf + j*NB) = cpad(bf) + j*(NB + NB/16) when 16 | NB: one base + immediate offsets
                 if constexpr (NB % 16 == 0) {
                     const cpx<F>* src = lds + cpad(bf);
@@ -159,20 +140,14 @@ __device__ __forceinline__ void fft_pass(cpx<F>* lds, const cpx<F>* __restrict__
                 }
             }
         }
-        F2_FFT_BARRIER();
+        __syncthreads();
     }
 #pragma unroll
     for (int i = 0; i < ITER; ++i) {
         const int bf = tid + i * NT;
         if (FULL || bf < NB) {
-#ifndef F2_KO_DFT   // knock-outs: timing experiments only (tools/build_variant.sh), results are wrong
             dft<R>(&v[i * R]);   // X[k] now sits in v[i*R + brev<R>(k)]
-#endif
-#ifdef F2_KO_TW   // bit mask of passes that skip their twiddles
-            if constexpr (!LAST && !((F2_KO_TW >> PASS) & 1)) {
-#else
             if constexpr (!LAST) {
-#endif
                 const cpx<F>* twq = (PASS >= 1 ? twl + (plan_tw_offset(LOG2H, PASS) - plan_tw_offset(LOG2H, 1)) : twp) +
                                     (bf >> LOG2S);
                 if constexpr (PASS == 0 && T0REGS && R == 16) {
@@ -203,11 +178,7 @@ __device__ __forceinline__ void fft_pass(cpx<F>* lds, const cpx<F>* __restrict__
                         v[i * R + brev<R>(k)] = cmul(v[i * R + brev<R>(k)], twq[(k - 1) * (NB / S)]);
                 }
             }
-#ifdef F2_KO_LDS
-            if constexpr (false) {
-#else
-            if constexpr (!DST_REGS && !KO_WRITE) {
-#endif
+            if constexpr (!DST_REGS) {
                 const int q = bf & (S - 1);
                 const int base = q + (bf - q) * R;
                 if constexpr (S % 16 == 0) {
@@ -221,7 +192,7 @@ __device__ __forceinline__ void fft_pass(cpx<F>* lds, const cpx<F>* __restrict__
             }
         }
     }
-    if constexpr (!DST_REGS && !KO_WRITE) F2_FFT_BARRIER();
+    if constexpr (!DST_REGS) __syncthreads();
 }
 
 template <typename F, int LOG2H, bool INVERSE, int PTV, int NT, bool T0REGS = false, int PASS = 0>

@@ -51,15 +51,11 @@ constexpr int SEG_ALIGN = 32;   // host: segment lengths of the time-split path,
 // workgroup barrier); they only share a workgroup so that the dispatcher places them one per SIMD of a CU. With
 // one-wave workgroups the 2000 waves of the benchmark batch land unevenly (some SIMDs run three, others one) and the
 // kernel takes as long as the fullest SIMD.
-#ifndef F2_K1_WAVES_F32
-#define F2_K1_WAVES_F32 4     // float32 hand-off tiles: 4 x 16.9 KB of LDS
-#endif
-#ifndef F2_K1_WAVES_F64
-#define F2_K1_WAVES_F64 2     // float64 output tiles: 2 x 17.4 KB (the store-bound variant gains nothing beyond two)
-#endif
+constexpr int K1_WAVES_F32 = 4;   // float32 hand-off tiles: 4 x 16.9 KB of LDS
+constexpr int K1_WAVES_F64 = 2;   // float64 output tiles: 2 x 17.4 KB (the store-bound variant gains nothing beyond two)
 // (MODE 2 of the time-split path keeps a 32 KB matrix table per wave in LDS: two waves per workgroup)
 template <typename OutT, int MODE = 0>
-constexpr int waves_per_block() { return MODE == 2 ? 2 : sizeof(OutT) == 4 ? F2_K1_WAVES_F32 : F2_K1_WAVES_F64; }
+constexpr int waves_per_block() { return MODE == 2 ? 2 : sizeof(OutT) == 4 ? K1_WAVES_F32 : K1_WAVES_F64; }
 
 // LDS hand-over between lanes of ONE wave: the wave's DS operations execute in order, so only the compiler has to be
 // kept from moving accesses across this point.

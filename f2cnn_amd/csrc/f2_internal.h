@@ -93,7 +93,7 @@ struct f2_ctx {
     int opt_k1_queue = -1;                // unit queue of the filterbank for ragged batches (0 / 1)
     int opt_k1_qwaves = 0;                // waves of the queue launch (0 = from the batch)
     int opt_env_pair = 1;                 // on-chip kernel for rows of 32769..65536 samples
-    int opt_cnn_bf16x3 = 1;               // conv2 .. conv4 + dense1 on the fp16 matrix cores, operands split in two pieces (3 MFMAs per product; "cnn_f16x3")
+    int opt_cnn_f16x3 = 1;               // conv2 .. conv4 + dense1 on the fp16 matrix cores, operands split in two pieces (3 MFMAs per product; "cnn_f16x3")
     int opt_cnn_ws = 1;                   // ... with the weights of each wave's role held in registers (f2_cnn_ws.hip; windows of 10 / 11 rows)
     int opt_cnn_ws_dense = 1;             // ... and dense1 with 96 windows per weight fragment, loads waited for by hand (k_dense1_ws)
     int opt_gather_blocked = 1;           // every-sample windows: logarithm once per sample, blocks of 32 windows (0: one workgroup per window)
@@ -116,6 +116,7 @@ struct f2_ctx {
     std::vector<up_side> up_big;   // grow-only page-locked side buffers of uploads too large for the ring, reused once copied
     f2_scratch flags;      // small device words (error flags)
     int* host_flags = nullptr;  // pinned mirror
+    f2_scratch stamps;     // per-workgroup phase stamps, diagnostic build only (-DF2_STAMPS: f2_stamps_buffer)
 };
 
 #include "f2_cnn_split.h"
@@ -157,7 +158,7 @@ struct f2_cnn {
     mutable double last_input_bound = 0.0;   // B of the last f2_cnn_forward, -1: the float32 kernels ran, 0: none yet
     // f2_cnn_create's self-check of the weight-stationary kernels (hand-placed s_waitcnt around inline-asm loads: correct only
     // while the register allocator of the hipcc that built the library leaves those registers alone) against the per-tile
-    // split-bf16 kernels on a fixed batch; a kernel that disagrees is not used with this network
+    // split-fp16 kernels on a fixed batch; a kernel that disagrees is not used with this network
     bool ws_ok = true, ws_dense_ok = true;
     float ws_check_diff = -1.f, ws_dense_check_diff = -1.f;   // max |score difference| measured (-1: not applicable)
     // ... and of the split path as a whole against the float32 kernels, at B = 1 and B = 2^10: off for this network if it disagrees
@@ -200,6 +201,43 @@ int f2_upload_coefs(f2_ctx* ctx, const double* coefs, int C);
         int rc_ = (expr);         \
         if (rc_ != F2_OK) return rc_; \
     } while (0)
+
+// ---- per-workgroup phase stamps, diagnostic build only (-DF2_STAMPS; tools/k2_stamps.py, tools/pair_stamps.py) ----
+// F2_STAMP_ARRAY(st, N) declares N stamps in registers; F2_STAMP(st, k) records s_memrealtime (100 MHz, 10 ns ticks) into
+// st[k] with nothing scheduled across it; F2_STAMP_STORE(st, N, out) has thread 0 write them to out[blockIdx.x * N + k]
+// (out == NULL: nothing). The default build compiles all three to nothing.
+#ifdef F2_STAMPS
+#define F2_STAMP_ARRAY(st, N) unsigned long long st[N] = {0}
+#define F2_STAMP(st, k)                            \
+    do {                                           \
+        __builtin_amdgcn_sched_barrier(0);         \
+        (st)[k] = __builtin_amdgcn_s_memrealtime(); \
+        __builtin_amdgcn_sched_barrier(0);         \
+    } while (0)
+#define F2_STAMP_STORE(st, N, out)                                                                       \
+    do {                                                                                                 \
+        if (threadIdx.x == 0 && (out))                                                                   \
+            for (int k_ = 0; k_ < (N); ++k_) (out)[(size_t)blockIdx.x * (N) + k_] = (st)[k_];            \
+    } while (0)
+// Host side. f2_stamps_buffer: the device array for `rows` workgroups of `phases` (<= 10) stamps each, zeroed on the
+// stream, or NULL beyond 128 x 2048 rows (one buffer of the context, reused by every launch: take it after the previous
+// report). f2_stamps_report: waits for the stream, reads the
+// stamps back and prints the mean ticks of each phase k >= 1 (stamp k - stamp k-1) as "<tag> <what> <name>=<ticks> ...";
+// with `residency`, also the mean workgroup lifetime (first to last stamp) and how many workgroups were alive at once.
+int f2_stamps_buffer(f2_ctx* ctx, size_t rows, int phases, unsigned long long** out);
+int f2_stamps_report(f2_ctx* ctx, const unsigned long long* d_stamps, size_t rows, int phases, const char* const* names,
+                     const char* tag, const char* what, bool residency);
+#else
+#define F2_STAMP_ARRAY(st, N) \
+    do {                      \
+    } while (0)
+#define F2_STAMP(st, k) \
+    do {                \
+    } while (0)
+#define F2_STAMP_STORE(st, N, out) \
+    do {                           \
+    } while (0)
+#endif
 
 // Profiling bracket: f2_prof_begin before the launch(es) of one kernel id, f2_prof_end after. A span whose launch
 // failed in between is never closed: it is recycled by the next f2_prof_begin / f2_prof_reset and skipped by f2_prof_get.
@@ -281,7 +319,7 @@ int f2_launch_spectral(f2_ctx* ctx, const void* d_wave, int wave_dtype, const in
 // d_centers == NULL: window e is centred at first_center + e
 int f2_launch_gather(f2_ctx* ctx, const double* d_env, int C, int64_t N, const int64_t* d_centers,
                      int64_t first_center, int64_t n_windows, int radius, int step, int normalize, float* d_out, int* d_flag);
-// weight-stationary split-bf16 convolutions (f2_cnn_ws.hip): windows whose pooled conv2 output has four rows
+// weight-stationary split-fp16 convolutions (f2_cnn_ws.hip): windows whose pooled conv2 output has four rows
 bool f2_cnn_ws_supported(int rows, int channels);
 int f2_launch_dense1_ws(f2_ctx* ctx, const f2_cnn* cnn, const f2_scale_set* S, const float* a4, int64_t n, int K, float* a5);
 int f2_launch_cnn_ws(f2_ctx* ctx, const f2_cnn* cnn, const f2_scale_set* S, const float* d_x, int64_t n, void* a2s, float* a4);

@@ -148,7 +148,7 @@ int f2_cnn_forward(f2_ctx* ctx, const f2_cnn* cnn, const float* x, int64_t n, fl
     // the split path's scales follow the input (f2_cnn_split.h): a range pass, then the set of its bound
     const f2_scale_set* S1 = nullptr;
     F2_TRY(f2_cnn_scale_set(ctx, cnn, 0, &S1));
-    const bool measure = S1 && ctx->opt_cnn_bf16x3;   // (else the float32 kernels run whatever the input)
+    const bool measure = S1 && ctx->opt_cnn_f16x3;   // (else the float32 kernels run whatever the input)
     if (mem_space == F2_MEM_DEVICE) {
         const f2_scale_set* S = nullptr;
         double bound = -1.0;

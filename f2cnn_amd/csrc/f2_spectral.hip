@@ -40,6 +40,8 @@
 // spectra (64 KB per utterance, shared by its C rows) and 32 bytes of digits per row come from L2. Bound: f32 VALU +
 // LDS exchanges.
 #define f2fft f2fft_sp   // own copy of the FFT templates (the radix plan of this kernel is chosen independently of K2's)
+#undef F2_PLAN13_PASSES   // (fft13_pass12_merged is the four-pass plan, also in a build that gives K2 the three-pass one)
+#define F2_PLAN13_PASSES 4
 #include <algorithm>
 #include <cmath>
 #include <complex>
@@ -52,38 +54,16 @@ using namespace f2fft;
 namespace {
 
 typedef float f2_f4 __attribute__((ext_vector_type(4)));
-#ifndef F2_SPEC_GB
-#define F2_SPEC_GB 16     // bins per load group of the spectrum phase: all 32 loads of a thread in flight (4, 8: measured slower)
-#endif
-
-// Diagnostic build only (-DF2_STAMPS): wave 0 of every workgroup records s_memrealtime (100 MHz) at the phase boundaries.
-#ifdef F2_STAMPS
-#define F2_SSTAMP(k)                                         \
-    do {                                                     \
-        __builtin_amdgcn_sched_barrier(0);                   \
-        sst[k] = __builtin_amdgcn_s_memrealtime();             \
-        __builtin_amdgcn_sched_barrier(0);                   \
-    } while (0)
-#else
-#define F2_SSTAMP(k) \
-    do {             \
-    } while (0)
-#endif
+constexpr int SPEC_GB = 16;   // bins per load group of the spectrum phase: all 32 loads of a thread in flight (4, 8: measured slower)
 
 // ---- row stores through a buffer descriptor with an explicit cache policy ----
 // The envelopes are written once and never read by this kernel, 128 KB per row. Stored with the default policy (or
 // "nt") the lines stay in the XCD's L2 until evicted and push out the tables every workgroup of the XCD re-reads (2 MB of
 // channel tables per XCD + the utterance spectra against 4 MB of L2: measured, half of the table reads then miss L2 and
 // the spectrum phase waits on the fabric). sc1 = write through and drop the line (MI355X_MICROARCH.md, store flavours).
-#ifndef F2_KS_CGROUP
-#define F2_KS_CGROUP 32
-#endif
-#ifndef F2_KS_CGROUP_LONG
-#define F2_KS_CGROUP_LONG 8     // long rows: one 512 KB channel table per XCD at a time
-#endif
-#ifndef F2_KS_STORE_AUX
-#define F2_KS_STORE_AUX 2    // raw buffer store cache policy bits: 0 default, 1 sc0, 2 nt, 16 sc1 (measured: nt 6.74, sc1 6.87, default 7.10 ms)
-#endif
+constexpr int KS_CGROUP = 32;        // channels per row group (k_spectral_envelope, see there)
+constexpr int KS_CGROUP_LONG = 8;    // long rows: one 512 KB channel table per XCD at a time
+constexpr int KS_STORE_AUX = 2;      // raw buffer store cache policy bits: 0 default, 1 sc0, 2 nt, 16 sc1 (measured: nt 6.74, sc1 6.87, default 7.10 ms)
 typedef unsigned int f2_u4 __attribute__((ext_vector_type(4)));
 typedef unsigned int f2_u2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t row_buffer(double* y, int n) {
@@ -99,15 +79,15 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t row_buffer_uniform(double* y, 
 // envelope samples i0, i0 + 1, both known to lie inside the row
 __device__ __forceinline__ void store_row_pair_inside(__amdgpu_buffer_rsrc_t r, int i0, double a, double b) {
     const f2_d2 v = {a, b};
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(f2_u4, v), r, i0 * 8, 0, F2_KS_STORE_AUX);
+    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(f2_u4, v), r, i0 * 8, 0, KS_STORE_AUX);
 }
 // envelope samples i0, i0 + 1 of a row of n samples
 __device__ __forceinline__ void store_row_pair_buf(__amdgpu_buffer_rsrc_t r, int n, int i0, double a, double b) {
     if (i0 + 1 < n) {
         const f2_d2 v = {a, b};
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(f2_u4, v), r, i0 * 8, 0, F2_KS_STORE_AUX);
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(f2_u4, v), r, i0 * 8, 0, KS_STORE_AUX);
     } else if (i0 < n) {
-        __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(f2_u2, a), r, i0 * 8, 0, F2_KS_STORE_AUX);
+        __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(f2_u2, a), r, i0 * 8, 0, KS_STORE_AUX);
     }
 }
 
@@ -419,7 +399,7 @@ __global__ __launch_bounds__((threads_for<float, LOG2H>()), (min_waves_for<float
     // with CG = 32 against 6.71 ms with the plain (utterance, channel) order.
     int u, c;
     {
-        constexpr int CG = F2_KS_CGROUP;
+        constexpr int CG = KS_CGROUP;
         const int nfull = P.C / CG, per = P.nutt * CG;
         const int cg = min((int)(blockIdx.x / per), nfull);          // the last group may be partial
         const int rr = blockIdx.x - cg * per;
@@ -433,18 +413,11 @@ __global__ __launch_bounds__((threads_for<float, LOG2H>()), (min_waves_for<float
     const int n = (int)(offsets[b + 1] - off);
     double* __restrict__ y = P.env + ((size_t)P.C * (size_t)off + (size_t)c * (size_t)n);
     const float* __restrict__ rho = rho_all + (size_t)row_id * 8;
-#ifdef F2_KS_HOT_TABLES   // knock-out (timing only): every row reads utterance 0's spectrum and channel 0's table
-    const cpx<float>* __restrict__ Xu = Xall;
-    const f2_f4* __restrict__ HUc = HUall;
-#else
     const cpx<float>* __restrict__ Xu = Xall + (size_t)u * P.xpitch;
     const f2_f4* __restrict__ HUc = HUall + (size_t)c * P.tpitch;
-#endif
 
-#ifdef F2_STAMPS
-    unsigned long long sst[8] = {0};
-#endif
-    F2_SSTAMP(0);
+    F2_STAMP_ARRAY(st, 8);   // (-DF2_STAMPS: phase boundaries)
+    F2_STAMP(st, 0);
     for (int i = tid; i < TWL; i += NT) twl[i] = tw[plan_tw_offset(LOG2H, 1) + i];
     if (tid < 4) guard[tid] = 0u;
 
@@ -453,7 +426,7 @@ __global__ __launch_bounds__((threads_for<float, LOG2H>()), (min_waves_for<float
     //    j / 32} (compile-time constants) and w_k^n = w_tid^n (w_NB0^n)^j (wave-uniform factors, scalar loads). The bins
     //    go in groups of GB with the next group's loads in flight - all 32 loads at once would need 96 registers.
     static_assert(ITER0 == 1 && R0 == 16, "one radix-16 butterfly per thread in the first pass");
-    constexpr int GB = F2_SPEC_GB, NG = R0 / GB;
+    constexpr int GB = SPEC_GB, NG = R0 / GB;
     cpx<float> yk[PT], v[PT];
     // rows whose first pass is one radix-16 butterfly per thread (all three length classes served): the two transforms share it
     static_assert(NB0 == NT && plan_npass(LOG2H) >= 3, "fft_pass0_pair + fft_from_pass0");
@@ -469,25 +442,18 @@ __global__ __launch_bounds__((threads_for<float, LOG2H>()), (min_waves_for<float
     // cannot be issued before group g has been computed (the compiler would otherwise hoist all 32 loads and spill)
     //  (unsigned lane offset + wave-uniform row pointers: one offset register serves every load)
     unsigned kb = (unsigned)tid;
-#ifdef F2_KS_KO_LOADS   // knock-out (timing only, results wrong): table values from arithmetic instead of memory
-#define F2_KS_LOADX(ptr, idx) cpx<float>{1.0f + 1e-3f * (float)(idx), 1e-3f * (float)(idx)}
-#define F2_KS_LOADH(ptr, idx) f2_f4{1e-3f, 1e-4f * (float)(idx), 0.5f, 1e-3f * (float)(idx)}
-#else
-#define F2_KS_LOADX(ptr, idx) (ptr)[idx]
-#define F2_KS_LOADH(ptr, idx) (ptr)[idx]
-#endif
 #pragma unroll
     for (int q = 0; q < GB; ++q) {
-        Xl[0][q] = F2_KS_LOADX(Xu + q * NB0, kb);
-        Hl[0][q] = F2_KS_LOADH(HUc + q * NB0, kb);
+        Xl[0][q] = (Xu + q * NB0)[kb];
+        Hl[0][q] = (HUc + q * NB0)[kb];
     }
 #pragma unroll
     for (int g = 0; g < NG; ++g) {
         if (g + 1 < NG) {
 #pragma unroll
             for (int q = 0; q < GB; ++q) {
-                Xl[(g + 1) & 1][q] = F2_KS_LOADX(Xu + ((g + 1) * GB + q) * NB0, kb);
-                Hl[(g + 1) & 1][q] = F2_KS_LOADH(HUc + ((g + 1) * GB + q) * NB0, kb);
+                Xl[(g + 1) & 1][q] = (Xu + ((g + 1) * GB + q) * NB0)[kb];
+                Hl[(g + 1) & 1][q] = (HUc + ((g + 1) * GB + q) * NB0)[kb];
             }
         }
 #pragma unroll
@@ -500,23 +466,17 @@ __global__ __launch_bounds__((threads_for<float, LOG2H>()), (min_waves_for<float
 #ifdef F2_STAMPS
             if (j == 0 || j == 7) {
                 asm volatile("s_nop 0" : "+v"(yk[j].re), "+v"(yk[j].im));
-                sst[j == 0 ? 1 : 2] = __builtin_amdgcn_s_memrealtime();
+                st[j == 0 ? 1 : 2] = __builtin_amdgcn_s_memrealtime();
                 asm volatile("s_nop 0" : "+v"(yk[j].re));
             }
 #endif
         }
         // (w0 / z0 pass through as well: the phase factors of a later group are then not formed ahead of time either)
-        if constexpr (GB == 4) {
-            asm volatile(""
-                         : "+v"(kb), "+v"(w0.re), "+v"(w0.im), "+v"(z0.re), "+v"(z0.im), "+v"(yk[g * GB].re), "+v"(yk[g * GB + 1].re),
-                           "+v"(yk[g * GB + 2].re), "+v"(yk[g * GB + 3].re));
-        } else {
-            asm volatile("" : "+v"(kb), "+v"(w0.re), "+v"(w0.im), "+v"(z0.re), "+v"(z0.im), "+v"(yk[g * GB].re), "+v"(yk[g * GB + GB - 1].re));
-        }
+        asm volatile("" : "+v"(kb), "+v"(w0.re), "+v"(w0.im), "+v"(z0.re), "+v"(z0.im), "+v"(yk[g * GB].re), "+v"(yk[g * GB + GB - 1].re));
     }
 #ifdef F2_STAMPS
     asm volatile("s_nop 0" : "+v"(yk[15].re), "+v"(yk[15].im));
-    sst[3] = __builtin_amdgcn_s_memrealtime();
+    st[3] = __builtin_amdgcn_s_memrealtime();
     asm volatile("s_nop 0" : "+v"(yk[15].re));
 #endif
     // k = 0 carries the Nyquist term: A_e(0) = A(0) + A(H), A_o(0) = A(0) - A(H) (both real); thread 0 keeps
@@ -542,7 +502,7 @@ __global__ __launch_bounds__((threads_for<float, LOG2H>()), (min_waves_for<float
             v[0] = {0.5f * (yk[0].re + yk[0].im), 0.f};
             vo[0] = {0.5f * (yk[0].re - yk[0].im), 0.f};
         }
-        F2_SSTAMP(4);
+        F2_STAMP(st, 4);
         int tid_e = tid;
         asm volatile("" : "+v"(tid_e), "+v"(v[0].re), "+v"(vo[PT - 1].im));
         fft_pass0_pair<LOG2H, NT, PT>(tw, tid_e, v, vo);
@@ -554,7 +514,7 @@ __global__ __launch_bounds__((threads_for<float, LOG2H>()), (min_waves_for<float
             er[j] = fsqrt(a.re * a.re + a.im * a.im);
         }
         fft_from_pass0<LOG2H, PT, NT, T0R>(lds, tw, twl, tid_e, vo);
-        F2_SSTAMP(5);
+        F2_STAMP(st, 5);
         gout = pad_residual<R0, NT, PADLAST>(vo, n, tid, 1, gout);
 #pragma unroll
         for (int j = 0; j < R0; ++j) {
@@ -578,7 +538,7 @@ __global__ __launch_bounds__((threads_for<float, LOG2H>()), (min_waves_for<float
         __hip_atomic_fetch_max(&guard[0], __float_as_uint(gin), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         __hip_atomic_fetch_max(&guard[1], __float_as_uint(gout), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     }
-    F2_SSTAMP(6);
+    F2_STAMP(st, 6);
     // 5. stores (the last pass of the transform ended with a barrier after its LDS reads: smem is free)
     if (!P.lpf) {
         const __amdgpu_buffer_rsrc_t yb = row_buffer(y, n);
@@ -599,11 +559,8 @@ __global__ __launch_bounds__((threads_for<float, LOG2H>()), (min_waves_for<float
         if (__hip_atomic_fetch_add(&guard[3], 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_WORKGROUP) == (unsigned)(NT / 64 - 1))
             guard_decide(P, guard, b, c);
     }
-#ifdef F2_STAMPS
-    F2_SSTAMP(7);
-    if (tid == 0 && P.stamps)
-        for (int k = 0; k < 8; ++k) P.stamps[(size_t)blockIdx.x * 8 + k] = sst[k];
-#endif
+    F2_STAMP(st, 7);
+    F2_STAMP_STORE(st, 8, P.stamps);
 }
 
 // ---- rows of 32769 .. 65472 samples: M = 65536, H = 32768 ----
@@ -623,9 +580,7 @@ __global__ __launch_bounds__((threads_for<float, LOG2H>()), (min_waves_for<float
 // the first / second low-pass sweep - at n and n + 32768; inside a bank one plane per r (a transform's outputs are then
 // stored as whole 256-byte runs per wave instead of one float every 16 bytes), plane sizes summing to the bank's samples.
 // Guard, flags, row order and arguments as k_spectral_envelope; `tw` = the tables of the 16384-point transform.
-#ifndef F2_KSL_PARK_AUX
-#define F2_KSL_PARK_AUX 0    // cache policy of the parked magnitudes (stores and loads)
-#endif
+constexpr int KSL_PARK_AUX = 0;   // cache policy of the parked magnitudes (stores and loads)
 // float index of plane r of bank `bank` (m counted from the bank's first sample)
 __device__ __forceinline__ int park_plane(int n, int bank, int r) {
     constexpr int MB = 8192;                      // m of the first sample of bank 1
@@ -655,7 +610,7 @@ __global__ __launch_bounds__(1024, 4) void k_spectral_envelope_long(
     const int tid = threadIdx.x;
     int u, c;
     {
-        constexpr int CG = F2_KS_CGROUP_LONG;
+        constexpr int CG = KS_CGROUP_LONG;
         const int nfull = P.C / CG, per = P.nutt * CG;
         const int cg = min((int)(blockIdx.x / per), nfull);
         const int rr = blockIdx.x - cg * per;
@@ -685,10 +640,8 @@ __global__ __launch_bounds__(1024, 4) void k_spectral_envelope_long(
     constexpr bool T0R = derive_tw0<float, LOG2Q>();
     float gin = 0.f, gout = 0.f;
     unsigned kb = (unsigned)tid;
-#ifdef F2_STAMPS
-    unsigned long long sst[8] = {0};
-#endif
-    F2_SSTAMP(0);
+    F2_STAMP_ARRAY(st, 8);
+    F2_STAMP(st, 0);
 #pragma unroll 1
     for (int p = 0; p < 2; ++p) {
         cpx<float> v[PT], vo[PT];
@@ -699,10 +652,10 @@ __global__ __launch_bounds__(1024, 4) void k_spectral_envelope_long(
             f2_f4 Hl[2][GB];
 #pragma unroll
             for (int q = 0; q < GB; ++q) {
-                Xl[0][q] = F2_KS_LOADX(Xu + (g * GB + q) * NB0, kb);
-                Hl[0][q] = F2_KS_LOADH(HUc + (g * GB + q) * NB0, kb);
-                Xl[1][q] = F2_KS_LOADX(Xu + Q + (g * GB + q) * NB0, kb);
-                Hl[1][q] = F2_KS_LOADH(HUc + Q + (g * GB + q) * NB0, kb);
+                Xl[0][q] = (Xu + (g * GB + q) * NB0)[kb];
+                Hl[0][q] = (HUc + (g * GB + q) * NB0)[kb];
+                Xl[1][q] = (Xu + Q + (g * GB + q) * NB0)[kb];
+                Hl[1][q] = (HUc + Q + (g * GB + q) * NB0)[kb];
             }
 #pragma unroll
             for (int q = 0; q < GB; ++q) {
@@ -724,10 +677,8 @@ __global__ __launch_bounds__(1024, 4) void k_spectral_envelope_long(
         }
         int tid_e = tid;
         asm volatile("" : "+v"(tid_e), "+v"(v[0].re), "+v"(vo[PT - 1].im));
-#ifdef F2_STAMPS
-        if (p == 0) F2_SSTAMP(1);
-        else F2_SSTAMP(3);
-#endif
+        if (p == 0) F2_STAMP(st, 1);
+        else F2_STAMP(st, 3);
         fft_pass0_pair<LOG2Q, NT, PT>(tw, tid_e, v, vo);
 #pragma unroll
         for (int half = 0; half < 2; ++half) {
@@ -744,19 +695,15 @@ __global__ __launch_bounds__(1024, 4) void k_spectral_envelope_long(
                 const float e = fsqrt(a.re * a.re + a.im * a.im);
                 const bool in = 4 * (tid + NT * j) + r < n;
                 // (no branch per sample: a sample beyond the row goes to an offset the buffer's range check drops)
-#ifndef F2_KSL_KO_PARK   // knock-out (timing only)
                 __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(e), yb, in ? (j < 8 ? pv0 : pv1) : 0x7ffffff0, 4 * NT * (j & 7),
-                                                      F2_KSL_PARK_AUX);
-#endif
+                                                      KSL_PARK_AUX);
                 gin = fmaxf(gin, in ? e : 0.f);
                 // (rows of this class have n > 32768: blocks 0 .. 7 of 4096 samples never hold padding; wave-uniform test for the others)
                 if (j >= 8 && 4 * NT * (j + 1) > n) gout = fmaxf(gout, in ? 0.f : fabsf(a.re));
             }
         }
-#ifdef F2_STAMPS
-        if (p == 0) F2_SSTAMP(2);
-        else F2_SSTAMP(4);
-#endif
+        if (p == 0) F2_STAMP(st, 2);
+        else F2_STAMP(st, 4);
     }
     gin = wave_max63(gin);
     gout = wave_max63(gout);
@@ -771,9 +718,6 @@ __global__ __launch_bounds__(1024, 4) void k_spectral_envelope_long(
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
     // low-pass + stores: two sweeps of 2 NT NBLK = 32768 samples in the pair layout of lowpass_pairs_store_tab
     // (loading the parked inputs of both sweeps up front costs 90 spilled registers next to the low-pass's own 80)
-#ifdef F2_KSL_KO_SWEEP   // knock-out (timing only)
-    if (n < 0)
-#endif
     float glp = 0.f;
 #pragma unroll 1
     for (int sw = 0; sw < 2; ++sw) {
@@ -787,8 +731,8 @@ __global__ __launch_bounds__(1024, 4) void k_spectral_envelope_long(
         for (int jj = 0; jj < NBLK; ++jj) {
             const int i0 = ibase + 2 * (tid + NT * jj);
             // (samples beyond the row: an out-of-range offset, which reads as 0)
-            er[jj] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(yb, i0 < n ? pva : 0x7ffffff0, 2 * NT * jj, F2_KSL_PARK_AUX));
-            ei[jj] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(yb, i0 + 1 < n ? pvb : 0x7ffffff0, 2 * NT * jj, F2_KSL_PARK_AUX));
+            er[jj] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(yb, i0 < n ? pva : 0x7ffffff0, 2 * NT * jj, KSL_PARK_AUX));
+            ei[jj] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(yb, i0 + 1 < n ? pvb : 0x7ffffff0, 2 * NT * jj, KSL_PARK_AUX));
         }
         if (!P.lpf) {
             __syncthreads();   // every load of the sweep before any of its stores
@@ -796,14 +740,12 @@ __global__ __launch_bounds__(1024, 4) void k_spectral_envelope_long(
             for (int jj = 0; jj < NBLK; ++jj) store_row_pair_buf(yb, n, ibase + 2 * (tid + NT * jj), (double)er[jj], (double)ei[jj]);
         } else {
             const float e_in =   // sample 32767: the last of plane 3 of bank 0
-                sw ? __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(yb, 4 * (park_plane(n, 0, 3) + 8191), 0, F2_KSL_PARK_AUX)) : 0.f;
+                sw ? __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(yb, 4 * (park_plane(n, 0, 3) + 8191), 0, KSL_PARK_AUX)) : 0.f;
             glp = fmaxf(glp, lowpass_pairs_store_tab<NT, NBLK, true>(er, ei, P.lp, lptab, smem, y, n, tid, ibase, e_in, &ychain));
         }
         __syncthreads();   // (the second sweep's inputs were parked before the first barrier above; `smem` is free again)
-#ifdef F2_STAMPS
-        if (sw == 0) F2_SSTAMP(5);
-        else F2_SSTAMP(6);
-#endif
+        if (sw == 0) F2_STAMP(st, 5);
+        else F2_STAMP(st, 6);
     }
     // (verdict without a barrier, as in k_spectral_envelope: the wave that counts itself in last decides)
     if (P.lpf) glp = wave_max63(glp);
@@ -812,11 +754,8 @@ __global__ __launch_bounds__(1024, 4) void k_spectral_envelope_long(
         if (__hip_atomic_fetch_add(&guard[3], 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_WORKGROUP) == (unsigned)(NT / 64 - 1))
             guard_decide(P, guard, b, c);
     }
-#ifdef F2_STAMPS
-    F2_SSTAMP(7);
-    if (tid == 0 && P.stamps)
-        for (int k = 0; k < 8; ++k) P.stamps[(size_t)blockIdx.x * 8 + k] = sst[k];
-#endif
+    F2_STAMP(st, 7);
+    F2_STAMP_STORE(st, 8, P.stamps);
 }
 
 // ---- X = DFT_M(x zero-padded), k = 0..H, float64 arithmetic, float32 out ----
@@ -1271,10 +1210,7 @@ static int launch_group(f2_ctx* ctx, const WaveT* d_wave, const int64_t* d_offse
     P.gdump = ctx->opt_spectral_guard_dump ? (float*)ctx->spec_gdump.ptr : nullptr;
     P.stamps = nullptr;
 #ifdef F2_STAMPS
-    static unsigned long long* d_stamps = nullptr;
-    const size_t nstamp = (size_t)nutt * C * 8;
-    if (!d_stamps) F2_HIP(ctx, hipMalloc((void**)&d_stamps, sizeof(unsigned long long) * 8 * 128 * 2048));
-    if (nstamp <= (size_t)8 * 128 * 2048) P.stamps = d_stamps;
+    F2_TRY(f2_stamps_buffer(ctx, (size_t)nutt * C, 8, &P.stamps));
 #endif
     F2_TRY(f2_prof_begin(ctx, F2_K_FUSED));
     if constexpr (LOG2H == 15)
@@ -1292,28 +1228,10 @@ static int launch_group(f2_ctx* ctx, const WaveT* d_wave, const int64_t* d_offse
     F2_HIP(ctx, hipGetLastError());
     F2_TRY(f2_prof_end(ctx, F2_K_FUSED));
 #ifdef F2_STAMPS
-    if (P.stamps) {
-        F2_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        std::vector<unsigned long long> h(nstamp);
-        F2_HIP(ctx, hipMemcpy(h.data(), d_stamps, sizeof(unsigned long long) * nstamp, hipMemcpyDeviceToHost));
-        double acc[8] = {0};
-        const size_t rows = (size_t)nutt * C;
-        unsigned long long t0 = ~0ull, t1 = 0;
-        double life = 0;
-        for (size_t r = 0; r < rows; ++r) {
-            for (int k = 1; k < 8; ++k) acc[k] += (double)(h[r * 8 + k] - h[r * 8 + k - 1]);
-            t0 = std::min(t0, h[r * 8]);
-            t1 = std::max(t1, h[r * 8 + 7]);
-            life += (double)(h[r * 8 + 7] - h[r * 8]);
-        }
-        static const char* names_s[8] = {"", "bin 0 ready", "bin 7 ready", "bin 15 ready", "transform inputs", "both transforms + even magnitudes", "odd magnitudes + guard", "lpf+stores"};
-        static const char* names_l[8] = {"", "spectrum r=0,2", "transforms r=0,2 + parking", "spectrum r=1,3", "transforms r=1,3 + parking", "low-pass sweep 0", "low-pass sweep 1", "flag"};
-        const char* const* names = LOG2H == 15 ? names_l : names_s;
-        fprintf(stderr, "[stamps KS] mean ticks (10 ns) per workgroup:");
-        for (int k = 1; k < 8; ++k) fprintf(stderr, " %s=%.0f", names[k], acc[k] / rows);
-        fprintf(stderr, "\n[stamps KS] mean workgroup lifetime %.1f ticks, kernel span %.0f ticks, workgroups alive at once %.1f\n",
-                life / rows, (double)(t1 - t0), life / (double)(t1 - t0));
-    }
+    static const char* names_s[8] = {"", "bin 0 ready", "bin 7 ready", "bin 15 ready", "transform inputs", "both transforms + even magnitudes", "odd magnitudes + guard", "lpf+stores"};
+    static const char* names_l[8] = {"", "spectrum r=0,2", "transforms r=0,2 + parking", "spectrum r=1,3", "transforms r=1,3 + parking", "low-pass sweep 0", "low-pass sweep 1", "flag"};
+    F2_TRY(f2_stamps_report(ctx, P.stamps, (size_t)nutt * C, 8, LOG2H == 15 ? names_l : names_s, "[stamps KS]",
+                            "mean ticks (10 ns) per workgroup:", true));
 #endif
     return F2_OK;
 }

@@ -89,16 +89,16 @@ const char* f2_last_error(f2_ctx* ctx);
  *   "k1_qwaves"      0 / n             waves of the queue launch (0 = from the batch)
  *   "env_pair"       1 / 0             on-chip envelope kernel for rows of 32769..65536 samples
  *   "env_plan4"      0 / 1             four-pass transform plan for every 8193..16384-sample row
- *   "cnn_bf16x3"     1 (default) / 0   (alias "cnn_f16x3") conv2..conv4 + dense1 of f2_cnn_* / f2_eval_* on the fp16 matrix
+ *   "cnn_f16x3"      1 (default) / 0   (old alias "cnn_bf16x3") conv2..conv4 + dense1 of f2_cnn_* / f2_eval_* on the fp16 matrix
  *                                      cores with both operands split in two fp16 pieces, each layer's operands scaled by powers
  *                                      of two (three MFMAs per product, float32 accumulation: scores at the float32 rounding
  *                                      level, within 1e-6 of the float32 matrix path, several times its speed; the scales follow
  *                                      the input's range, see f2_cnn_forward); 0 = v_mfma_f32_32x32x2_f32 throughout
- *   "cnn_ws"         1 (default) / 0   with "cnn_bf16x3", windows of 10 / 11 rows (the reference's 11 x C): persistent weight-
+ *   "cnn_ws"         1 (default) / 0   with "cnn_f16x3", windows of 10 / 11 rows (the reference's 11 x C): persistent weight-
  *                                      stationary kernels (each wave keeps the weights of its role in registers, conv1 on the
  *                                      matrix cores too, one barrier per tile); 0 = one workgroup per tile, weights re-read
  *   "cnn_ws_dense"   1 (default) / 0   with "cnn_ws": dense1 on 96-window tiles (a weight fragment feeds nine MFMAs), its loads
- *                                      issued and waited for by hand; 0 = the 64-window kernel of "cnn_bf16x3"
+ *                                      issued and waited for by hand; 0 = the 64-window kernel of "cnn_f16x3"
  *   "gather_blocked" 1 (default) / 0   every-sample normalised windows (f2_gather_windows without centres, f2_eval_*): logarithm
  *                                      once per envelope sample and blocks of 32 consecutive windows, bit-identical to 0 = one
  *                                      workgroup per window
@@ -199,10 +199,10 @@ int f2_gather_windows(f2_ctx* ctx, const double* env, int C, int64_t N, const in
  *   conv4 (3,3,64,64),(64) | dense1 (F,516),(516) | dense2 (516,2),(2),  F = flatten size for (rows, channels)
  * f2_cnn_forward: x (n, rows, channels) float32 -> scores (n,2) softmax float32 and
  * labels[i] = scores[i][1] > scores[i][0] (ties -> 0). scores or labels may be NULL.
- * Any finite input is accepted, as keras model.predict accepts it. With option "cnn_bf16x3" (the default) a pass over x
+ * Any finite input is accepted, as keras model.predict accepts it. With option "cnn_f16x3" (the default) a pass over x
  * finds max |x|; the split path then runs with the scales of the input bound B = 1 when max |x| <= 1 (the scales of every
  * normalised window: f2_eval_* use them without the pass) and B = 2^ceil(log2 max |x|) above that. An input holding inf /
- * NaN, or one whose B would need a scale outside [2^-20, 2^20], runs on the float32 kernels (option "cnn_bf16x3" = 0), and
+ * NaN, or one whose B would need a scale outside [2^-20, 2^20], runs on the float32 kernels (option "cnn_f16x3" = 0), and
  * its scores are what those give. x in device memory: the call synchronises the stream once (to read the range back);
  * x in host memory: per chunk of 16384 windows, as before.
  */
