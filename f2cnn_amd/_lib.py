@@ -55,6 +55,7 @@ SIGNATURES = {
     "f2_envelope_batch": (_i, [_vp, _vp, _vp, _i, _i, _i, _d, _i, _vp, _i]),
     "f2_filterbank_envelope_fused": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i, _i, _d, _i, _vp, _vp, _i]),
     "f2_gather_windows": (_i, [_vp, _vp, _i, _i64, _vp, _i64, _i, _i, _i, _vp, _i]),
+    "f2_input_batch": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i, _i, _d, _i, _vp, _vp, _i, _i, _i, _vp, _i]),
     "f2_cnn_create": (_i, [_vp, _P(_vp), _i, _i, _P(_vp)]),
     "f2_cnn_destroy": (_i, [_vp, _vp]),
     "f2_cnn_get_info": (_i, [_vp, _vp, C.c_char_p, _P(_d)]),
@@ -299,6 +300,17 @@ class Context:
     def gather_windows(self, env, Cn, N, centers, n_windows, radius, step, normalize, out, mem_space):
         self.check(self.lib.f2_gather_windows(self.handle, _ptr(env), Cn, N, _ptr(centers), n_windows, radius, step,
                                               int(bool(normalize)), _ptr(out), mem_space))
+
+    def input_batch(self, wave, wave_dtype, offsets, coefs, B, Cn, lpf, cutoff, precision, center_offsets, centers, radius,
+                    step, normalize, windows, mem_space):
+        """Ragged batch of waves -> (center_offsets[B], 2*radius+1, Cn) float32 windows at the given centres (each relative
+        to its own utterance), the envelopes never leaving the device; see f2_input_batch."""
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        center_offsets = np.ascontiguousarray(center_offsets, dtype=np.int64)
+        centers = np.ascontiguousarray(centers, dtype=np.int64)
+        self.check(self.lib.f2_input_batch(self.handle, _ptr(wave), wave_dtype, _ptr(offsets), _ptr(coefs), int(B), Cn,
+                                           int(bool(lpf)), float(cutoff), precision, _ptr(center_offsets), _ptr(centers),
+                                           radius, step, int(bool(normalize)), _ptr(windows), mem_space))
 
     def cnn_create(self, tensors, rows, channels):
         """tensors: 12 contiguous float32 arrays in Keras layouts (see include/f2cnn_hip.h). Returns a handle."""

@@ -5,6 +5,9 @@ package implements:
     python -m f2cnn_amd prepare envelope [--cutoff/-c HZ]
     python -m f2cnn_amd prepare label                       (needs the VTR .FB and TIMIT .PHN side files)
     python -m f2cnn_amd prepare input [--cutoff HZ] [--label/-l CSV] [--input/-i NPY]
+    python -m f2cnn_amd prepare input --from-wav [--cutoff HZ] [--label/-l CSV] [--input/-i NPY] [--metrics FILE]
+                                                            (windows straight from the WAV files: no .GFB.npy / .ENV1.npy
+                                                             on disk; --cutoff low-passes the envelopes; not in the reference)
     python -m f2cnn_amd prepare features [--cutoff HZ]     (filter + envelope in one pass, not in the reference)
     (filter / envelope / features also take --skip-existing to resume and --metrics FILE for a JSON summary; a file that
      cannot be read is reported and skipped, the exit status is then 2)
@@ -36,7 +39,11 @@ def build_parser():
     p.add_argument('--skip-existing', action='store_true',
                    help="filter / envelope / features: leave files whose outputs are already up to date (resume)")
     p.add_argument('--metrics', dest='metrics', nargs='?',
-                   help="filter / envelope / features: write files, audio seconds, wall time and audio-s/s as JSON")
+                   help="filter / envelope / features / input --from-wav: write files, audio seconds, wall time and "
+                        "audio-s/s as JSON")
+    p.add_argument('--from-wav', dest='from_wav', action='store_true',
+                   help="input: build the windows from the WAV files on the device (envelopes low-passed at --cutoff), "
+                        "without .GFB.npy / .ENV1.npy files")
     c = sub.add_parser('cnn', help='CNN commands')
     c.add_argument('--file', '-f', dest='file', nargs='?')
     c.add_argument('--input', '-i', dest='inputFile', nargs='?')
@@ -52,6 +59,9 @@ def build_parser():
 def main(argv=None):
     args = build_parser().parse_args(argv)
     if 'prepare_command' in args:
+        if args.from_wav and args.prepare_command != 'input':
+            print("--from-wav only applies to 'prepare input'")
+            return 1
         kwargs = {}
         if args.prepare_command in ('envelope', 'input', 'features'):      # f2cnn.py:112-114
             kwargs['LPF'] = args.CUTOFF is not None
@@ -72,6 +82,9 @@ def main(argv=None):
             from .scripts.processing.LabelDataGenerator import GenerateLabelData as fn
         elif args.prepare_command == 'features':
             from .scripts.processing.EnvelopeExtraction import FilterAndExtractAll as fn
+        elif args.from_wav:
+            from .scripts.processing.InputGenerator import GenerateInputDataFromWav as fn
+            kwargs['metrics'] = args.metrics
         else:
             from .scripts.processing.InputGenerator import GenerateInputData as fn
         report = fn(**kwargs)

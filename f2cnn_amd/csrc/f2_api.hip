@@ -197,7 +197,7 @@ int f2_prof_end(f2_ctx* ctx, int kernel_id) {
 
 extern "C" {
 
-int f2_version(void) { return 106; }   // 101: f2_eval_batch; 102: f2_host_alloc, F2_MEM_HOST_ASYNC; 103: f2_ctx_set_option; 104: f2_event_query; 105: f2_spectral_guard_read; 106: f2_cnn_forward takes any finite input on the split path
+int f2_version(void) { return 107; }   // 101: f2_eval_batch; 102: f2_host_alloc, F2_MEM_HOST_ASYNC; 103: f2_ctx_set_option; 104: f2_event_query; 105: f2_spectral_guard_read; 106: f2_cnn_forward takes any finite input on the split path; 107: f2_input_batch
 
 int f2_device_count(int* count) {
     if (!count) return f2_fail(nullptr, F2_ERR_INVALID, "count is NULL");
@@ -653,6 +653,81 @@ int f2_plan_handoff(f2_ctx* ctx, const int64_t* h_offsets, int B, int C, int pre
 
 static size_t wave_elem(int wave_dtype) { return wave_dtype == F2_WAVE_I16 ? 2 : 8; }
 
+// The device part of f2_filterbank_envelope_fused, shared with f2_input_batch (f2_pipeline.hip). The caller has uploaded
+// offsets and coefficients (f2_upload_offsets / f2_upload_coefs) and staged the wave.
+int f2_envelopes_device(f2_ctx* ctx, const void* d_wave, int wave_dtype, const int64_t* offsets, int B, int C, int lpf,
+                        double cutoff_hz, int fft_precision, double* d_env, double* d_gfb) {
+    // Spectral path (f2_spectral.hip): utterances it can serve (float FFT, no GFB output wanted, make_erb_filters-shaped
+    // table, 4097..65472 samples with padding to look at) get their envelopes from ONE kernel that never materialises
+    // the filterbank rows. Everything else - and any utterance that kernel's accuracy guard flags on the device - goes
+    // through the filterbank kernel + envelope kernel below, which skip utterances whose flag is 0.
+    const int* d_uflag = nullptr;
+    ctx->spec_last_B = 0;
+    if (ctx->opt_spectral && fft_precision == F2_FFT_F32 && !d_gfb && ctx->spec_coefs_ok < 0)
+        ctx->spec_coefs_ok = f2_spectral_supports_coefs(ctx->coefs_host, C, nullptr, &ctx->spec_min_pad) ? 1 : 0;   // (once per table: ~50 us of logarithms)
+    if (ctx->opt_spectral && fft_precision == F2_FFT_F32 && !d_gfb && ctx->spec_coefs_ok == 1) {
+        std::vector<int> meta((size_t)B, 1);
+        std::vector<int> lists[F2_SPECTRAL_MAX_LOG2H + 1];
+        int nspec = 0;
+        for (int b = 0; b < B; ++b) {
+            const int64_t n = offsets[b + 1] - offsets[b];
+            if (!f2_spectral_supports_len(n, ctx->opt_spectral_min_pad >= 0 ? ctx->opt_spectral_min_pad : ctx->spec_min_pad)) continue;
+            lists[f2_log2_ceil(n) - 1].push_back(b);
+            meta[(size_t)b] = 0;
+            ++nspec;
+        }
+        // a handful of rows cannot hide the serial run of k_tail_state (~0.1 ms for the low channels): small batches
+        // (one file of `cnn eval`, cfg1) keep the time-split filterbank kernel + envelope kernel
+        if ((int64_t)nspec * C < ctx->opt_spectral_min_rows) nspec = 0;
+        if (nspec > 0) {
+            size_t pos[F2_SPECTRAL_MAX_LOG2H + 1];
+            for (int l = F2_SPECTRAL_MIN_LOG2H; l <= F2_SPECTRAL_MAX_LOG2H; ++l) {
+                pos[l] = meta.size();
+                meta.insert(meta.end(), lists[l].begin(), lists[l].end());
+            }
+            if (meta != ctx->spec_meta_host) {   // new batch shape (as f2_upload_offsets: staged, not waited for)
+                ctx->spec_meta_host.clear();
+                F2_TRY(f2_reserve(ctx, ctx->spec_meta, sizeof(int) * meta.size()));
+                F2_TRY(f2_reserve(ctx, ctx->spec_uflag, sizeof(int) * (size_t)B));
+                F2_TRY(f2_upload_async(ctx, ctx->spec_meta.ptr, meta.data(), sizeof(int) * meta.size()));
+                ctx->spec_meta_host = meta;
+            }
+            int* uflag = (int*)ctx->spec_uflag.ptr;
+            F2_HIP(ctx, hipMemcpyAsync(uflag, ctx->spec_meta.ptr, sizeof(int) * (size_t)B, hipMemcpyDeviceToDevice, ctx->stream));
+            ctx->spec_gdump_rows = 0;
+            if (ctx->opt_spectral_guard_dump) {   // diagnostic: rows the spectral kernel does not serve read back as -1
+                const size_t gbytes = sizeof(float) * 4 * (size_t)B * (size_t)C;
+                F2_TRY(f2_reserve(ctx, ctx->spec_gdump, gbytes));
+                F2_HIP(ctx, hipMemsetAsync(ctx->spec_gdump.ptr, 0xff, gbytes, ctx->stream));
+                ctx->spec_gdump_rows = (size_t)B * (size_t)C;
+            }
+            for (int l = F2_SPECTRAL_MIN_LOG2H; l <= F2_SPECTRAL_MAX_LOG2H; ++l) {
+                int64_t min_n = INT64_MAX;
+                for (int b : lists[l]) min_n = std::min(min_n, offsets[b + 1] - offsets[b]);
+                F2_TRY(f2_launch_spectral(ctx, d_wave, wave_dtype, (const int64_t*)ctx->offsets.ptr, (const double*)ctx->coefs.ptr,
+                                          C, (const int*)ctx->spec_meta.ptr + pos[l], (int)lists[l].size(), min_n, l, lpf,
+                                          cutoff_hz, d_env, uflag));
+            }
+            d_uflag = uflag;
+            ctx->spec_last_B = (size_t)B;
+        }
+    }
+    // Filterbank kernel + envelope kernel queued back to back on the context's stream, no third buffer and no host
+    // round trip. When the float64 filterbank output is not wanted and the envelope runs its float32 FFT, the filterbank
+    // hands its rows over as float32 inside the ENV buffer itself (half the bytes written and read back;
+    // the envelope kernel converts to float32 before its FFT anyway, so the result is bit-identical).
+    f2_handoff handoff;
+    F2_TRY(f2_plan_handoff(ctx, offsets, B, C, fft_precision, d_gfb != nullptr, &handoff));
+    double* k1_out = d_gfb ? d_gfb : d_env;
+    F2_TRY(f2_launch_filterbank(ctx, d_wave, wave_dtype, (const int64_t*)ctx->offsets.ptr, offsets,
+                                (const double*)ctx->coefs.ptr, B, C, k1_out, &handoff, d_uflag,
+                                d_uflag && ctx->spec_meta_host.size() >= (size_t)B ? ctx->spec_meta_host.data() : nullptr));
+    F2_TRY(f2_launch_envelope(ctx, k1_out, (const int64_t*)ctx->offsets.ptr, offsets, B, C, lpf, cutoff_hz,
+                              fft_precision, d_env, &handoff, d_uflag,
+                              d_uflag && ctx->spec_meta_host.size() >= (size_t)B ? ctx->spec_meta_host.data() : nullptr));
+    return F2_OK;
+}
+
 extern "C" {
 
 int f2_erb_filterbank_batch(f2_ctx* ctx, const void* wave, int wave_dtype, const int64_t* offsets,
@@ -749,74 +824,7 @@ int f2_filterbank_envelope_fused(f2_ctx* ctx, const void* wave, int wave_dtype, 
         d_env = (double*)ctx->stage_out.ptr;
         d_gfb = gfb_or_null ? (double*)ctx->stage_aux.ptr : nullptr;
     }
-    // Spectral path (f2_spectral.hip): utterances it can serve (float FFT, no GFB output wanted, make_erb_filters-shaped
-    // table, 4097..65472 samples with padding to look at) get their envelopes from ONE kernel that never materialises
-    // the filterbank rows. Everything else - and any utterance that kernel's accuracy guard flags on the device - goes
-    // through the filterbank kernel + envelope kernel below, which skip utterances whose flag is 0.
-    const int* d_uflag = nullptr;
-    ctx->spec_last_B = 0;
-    if (ctx->opt_spectral && fft_precision == F2_FFT_F32 && !d_gfb && ctx->spec_coefs_ok < 0)
-        ctx->spec_coefs_ok = f2_spectral_supports_coefs(ctx->coefs_host, C, nullptr, &ctx->spec_min_pad) ? 1 : 0;   // (once per table: ~50 us of logarithms)
-    if (ctx->opt_spectral && fft_precision == F2_FFT_F32 && !d_gfb && ctx->spec_coefs_ok == 1) {
-        std::vector<int> meta((size_t)B, 1);
-        std::vector<int> lists[F2_SPECTRAL_MAX_LOG2H + 1];
-        int nspec = 0;
-        for (int b = 0; b < B; ++b) {
-            const int64_t n = offsets[b + 1] - offsets[b];
-            if (!f2_spectral_supports_len(n, ctx->opt_spectral_min_pad >= 0 ? ctx->opt_spectral_min_pad : ctx->spec_min_pad)) continue;
-            lists[f2_log2_ceil(n) - 1].push_back(b);
-            meta[(size_t)b] = 0;
-            ++nspec;
-        }
-        // a handful of rows cannot hide the serial run of k_tail_state (~0.1 ms for the low channels): small batches
-        // (one file of `cnn eval`, cfg1) keep the time-split filterbank kernel + envelope kernel
-        if ((int64_t)nspec * C < ctx->opt_spectral_min_rows) nspec = 0;
-        if (nspec > 0) {
-            size_t pos[F2_SPECTRAL_MAX_LOG2H + 1];
-            for (int l = F2_SPECTRAL_MIN_LOG2H; l <= F2_SPECTRAL_MAX_LOG2H; ++l) {
-                pos[l] = meta.size();
-                meta.insert(meta.end(), lists[l].begin(), lists[l].end());
-            }
-            if (meta != ctx->spec_meta_host) {   // new batch shape (as f2_upload_offsets: staged, not waited for)
-                ctx->spec_meta_host.clear();
-                F2_TRY(f2_reserve(ctx, ctx->spec_meta, sizeof(int) * meta.size()));
-                F2_TRY(f2_reserve(ctx, ctx->spec_uflag, sizeof(int) * (size_t)B));
-                F2_TRY(f2_upload_async(ctx, ctx->spec_meta.ptr, meta.data(), sizeof(int) * meta.size()));
-                ctx->spec_meta_host = meta;
-            }
-            int* uflag = (int*)ctx->spec_uflag.ptr;
-            F2_HIP(ctx, hipMemcpyAsync(uflag, ctx->spec_meta.ptr, sizeof(int) * (size_t)B, hipMemcpyDeviceToDevice, ctx->stream));
-            ctx->spec_gdump_rows = 0;
-            if (ctx->opt_spectral_guard_dump) {   // diagnostic: rows the spectral kernel does not serve read back as -1
-                const size_t gbytes = sizeof(float) * 4 * (size_t)B * (size_t)C;
-                F2_TRY(f2_reserve(ctx, ctx->spec_gdump, gbytes));
-                F2_HIP(ctx, hipMemsetAsync(ctx->spec_gdump.ptr, 0xff, gbytes, ctx->stream));
-                ctx->spec_gdump_rows = (size_t)B * (size_t)C;
-            }
-            for (int l = F2_SPECTRAL_MIN_LOG2H; l <= F2_SPECTRAL_MAX_LOG2H; ++l) {
-                int64_t min_n = INT64_MAX;
-                for (int b : lists[l]) min_n = std::min(min_n, offsets[b + 1] - offsets[b]);
-                F2_TRY(f2_launch_spectral(ctx, d_wave, wave_dtype, (const int64_t*)ctx->offsets.ptr, (const double*)ctx->coefs.ptr,
-                                          C, (const int*)ctx->spec_meta.ptr + pos[l], (int)lists[l].size(), min_n, l, lpf,
-                                          cutoff_hz, d_env, uflag));
-            }
-            d_uflag = uflag;
-            ctx->spec_last_B = (size_t)B;
-        }
-    }
-    // Filterbank kernel + envelope kernel queued back to back on the context's stream, no third buffer and no host
-    // round trip. When the float64 filterbank output is not wanted and the envelope runs its float32 FFT, the filterbank
-    // hands its rows over as float32 inside the ENV buffer itself (half the bytes written and read back;
-    // the envelope kernel converts to float32 before its FFT anyway, so the result is bit-identical).
-    f2_handoff handoff;
-    F2_TRY(f2_plan_handoff(ctx, offsets, B, C, fft_precision, d_gfb != nullptr, &handoff));
-    double* k1_out = d_gfb ? d_gfb : d_env;
-    F2_TRY(f2_launch_filterbank(ctx, d_wave, wave_dtype, (const int64_t*)ctx->offsets.ptr, offsets,
-                                (const double*)ctx->coefs.ptr, B, C, k1_out, &handoff, d_uflag,
-                                d_uflag && ctx->spec_meta_host.size() >= (size_t)B ? ctx->spec_meta_host.data() : nullptr));
-    F2_TRY(f2_launch_envelope(ctx, k1_out, (const int64_t*)ctx->offsets.ptr, offsets, B, C, lpf, cutoff_hz,
-                              fft_precision, d_env, &handoff, d_uflag,
-                              d_uflag && ctx->spec_meta_host.size() >= (size_t)B ? ctx->spec_meta_host.data() : nullptr));
+    F2_TRY(f2_envelopes_device(ctx, d_wave, wave_dtype, offsets, B, C, lpf, cutoff_hz, fft_precision, d_env, d_gfb));
     if (staged) {
         F2_HIP(ctx, hipMemcpyAsync(env, d_env, bytes, hipMemcpyDeviceToHost, ctx->stream));
         if (gfb_or_null) F2_HIP(ctx, hipMemcpyAsync(gfb_or_null, d_gfb, bytes, hipMemcpyDeviceToHost, ctx->stream));

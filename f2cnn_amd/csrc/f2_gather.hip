@@ -10,16 +10,23 @@
 // into LDS once, reduced for min/max there, and written out with c fastest, i.e. fully coalesced float32
 // rows. In `cnn eval` mode consecutive windows read consecutive samples of the same envelope rows, so
 // the strided gather is served by L2.
+//
+// RAGGED (f2_input_batch): the windows of a whole ragged batch in one launch. Window e lies in utterance
+// win_utt[e], whose (C, n_b) block starts at env + C * offsets[b]; everything after that is the kernel above,
+// except that without normalisation the values go straight from the envelope to the output (no LDS stage, no
+// barrier). The windows of neighbouring labelled timepoints share most of their tap columns in L2.
 #include "f2_internal.h"
 
 namespace {
 
 constexpr int GT = 256;
 
+template <bool RAGGED>
 __global__ __launch_bounds__(GT) void k_gather_windows(const double* __restrict__ env, int C, int64_t N,
                                                        const int64_t* __restrict__ centers, int64_t first_center,
                                                        int radius, int step, int normalize,
-                                                       float* __restrict__ out, int* __restrict__ flag) {
+                                                       float* __restrict__ out, int* __restrict__ flag,
+                                                       const int64_t* __restrict__ offsets, const int* __restrict__ win_utt) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     double* win = reinterpret_cast<double*>(smem_raw);
     __shared__ double red_min[GT / 64], red_max[GT / 64];
@@ -28,7 +35,20 @@ __global__ __launch_bounds__(GT) void k_gather_windows(const double* __restrict_
     const int64_t e = blockIdx.x;
     const int R = 2 * radius + 1;
     const int total = R * C;
+    if (RAGGED) {
+        const int64_t o0 = offsets[win_utt[e]];
+        env += (size_t)C * (size_t)o0;
+        N = offsets[win_utt[e] + 1] - o0;
+    }
     const int64_t centre = centers ? centers[e] : first_center + e;
+    if (RAGGED && !normalize) {
+        float* o = out + (size_t)e * (size_t)total;
+        for (int idx = tid; idx < total; idx += GT) {
+            const int k = idx / C, c = idx - k * C;
+            o[idx] = (float)env[(size_t)c * (size_t)N + (size_t)(centre + (int64_t)step * (k - radius))];
+        }
+        return;
+    }
 
     double mn = INFINITY, mx = -INFINITY;
     for (int idx = tid; idx < total; idx += GT) {
@@ -250,7 +270,7 @@ int f2_launch_gather(f2_ctx* ctx, const double* d_env, int C, int64_t N, const i
     F2_CHECK(ctx, lds <= 150 * 1024, F2_ERR_UNSUPPORTED, "window of %d x %d values does not fit in LDS", R, C);
     F2_CHECK(ctx, n_windows < (int64_t(1) << 31), F2_ERR_UNSUPPORTED, "too many windows (%lld)", (long long)n_windows);
     if (lds > 64 * 1024)
-        F2_HIP(ctx, hipFuncSetAttribute((const void*)k_gather_windows, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        F2_HIP(ctx, hipFuncSetAttribute((const void*)k_gather_windows<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     F2_TRY(f2_prof_begin(ctx, F2_K_GATHER));
     // every-sample normalised windows (`cnn eval`): the two-pass coalesced form; anything else one workgroup per window
     if (!d_centers && normalize && ctx->opt_gather_blocked && n_windows >= 4 * WB &&
@@ -259,8 +279,26 @@ int f2_launch_gather(f2_ctx* ctx, const double* d_env, int C, int64_t N, const i
         F2_TRY(f2_prof_end(ctx, F2_K_GATHER));
         return F2_OK;
     }
-    hipLaunchKernelGGL(k_gather_windows, dim3((unsigned)n_windows), dim3(GT), lds, ctx->stream, d_env, C, N, d_centers,
-                       first_center, radius, step, normalize, d_out, d_flag);
+    hipLaunchKernelGGL(k_gather_windows<false>, dim3((unsigned)n_windows), dim3(GT), lds, ctx->stream, d_env, C, N, d_centers,
+                       first_center, radius, step, normalize, d_out, d_flag, (const int64_t*)nullptr, (const int*)nullptr);
+    F2_HIP(ctx, hipGetLastError());
+    F2_TRY(f2_prof_end(ctx, F2_K_GATHER));
+    return F2_OK;
+}
+
+int f2_launch_gather_ragged(f2_ctx* ctx, const double* d_env, int C, const int64_t* d_offsets, const int64_t* d_centers,
+                            const int* d_win_utt, int64_t n_windows, int radius, int step, int normalize, float* d_out,
+                            int* d_flag) {
+    if (n_windows <= 0) return F2_OK;
+    const int R = 2 * radius + 1;
+    const size_t lds = normalize ? sizeof(double) * (size_t)R * (size_t)C : 0;
+    F2_CHECK(ctx, lds <= 150 * 1024, F2_ERR_UNSUPPORTED, "window of %d x %d values does not fit in LDS", R, C);
+    F2_CHECK(ctx, n_windows < (int64_t(1) << 31), F2_ERR_UNSUPPORTED, "too many windows (%lld)", (long long)n_windows);
+    if (lds > 64 * 1024)
+        F2_HIP(ctx, hipFuncSetAttribute((const void*)k_gather_windows<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    F2_TRY(f2_prof_begin(ctx, F2_K_GATHER));
+    hipLaunchKernelGGL(k_gather_windows<true>, dim3((unsigned)n_windows), dim3(GT), lds, ctx->stream, d_env, C, (int64_t)0,
+                       d_centers, (int64_t)0, radius, step, normalize, d_out, d_flag, d_offsets, d_win_utt);
     F2_HIP(ctx, hipGetLastError());
     F2_TRY(f2_prof_end(ctx, F2_K_GATHER));
     return F2_OK;

@@ -299,6 +299,11 @@ struct f2_handoff {
     const int64_t* h_x32_off = nullptr;     // the same on the host (owned by the context, valid until the next plan)
 };
 int f2_plan_handoff(f2_ctx* ctx, const int64_t* h_offsets, int B, int C, int precision, bool want_gfb, f2_handoff* plan);
+// Filterbank + envelope of a ragged batch on the device, by the routes of f2_filterbank_envelope_fused (f2_api.hip): spectral
+// kernel with its guard, then filterbank + envelope kernels for the rest. Offsets and coefficients already uploaded
+// (f2_upload_offsets / f2_upload_coefs); h_offsets host, d_wave / d_env / d_gfb (NULL: not wanted) device.
+int f2_envelopes_device(f2_ctx* ctx, const void* d_wave, int wave_dtype, const int64_t* h_offsets, int B, int C, int lpf,
+                        double cutoff_hz, int fft_precision, double* d_env, double* d_gfb);
 // d_uflag (device, B ints) != NULL: only utterances whose flag is non-zero are processed (the rest were served by the
 // spectral kernel); the flags may be written by earlier launches on the stream.
 // h_flag0 (host, B ints, with d_uflag): the flags as they are before the spectral kernel runs - the utterances this launch
@@ -319,6 +324,11 @@ int f2_launch_spectral(f2_ctx* ctx, const void* d_wave, int wave_dtype, const in
 // d_centers == NULL: window e is centred at first_center + e
 int f2_launch_gather(f2_ctx* ctx, const double* d_env, int C, int64_t N, const int64_t* d_centers,
                      int64_t first_center, int64_t n_windows, int radius, int step, int normalize, float* d_out, int* d_flag);
+// the same over a ragged batch in one launch: window e is centred at d_centers[e] (relative to its utterance) in utterance
+// d_win_utt[e], whose (C, n_b) block starts at d_env + C * d_offsets[b]; windows must lie inside their utterance
+int f2_launch_gather_ragged(f2_ctx* ctx, const double* d_env, int C, const int64_t* d_offsets, const int64_t* d_centers,
+                            const int* d_win_utt, int64_t n_windows, int radius, int step, int normalize, float* d_out,
+                            int* d_flag);
 // weight-stationary split-fp16 convolutions (f2_cnn_ws.hip): windows whose pooled conv2 output has four rows
 bool f2_cnn_ws_supported(int rows, int channels);
 int f2_launch_dense1_ws(f2_ctx* ctx, const f2_cnn* cnn, const f2_scale_set* S, const float* a4, int64_t n, int K, float* a5);

@@ -381,4 +381,77 @@ int f2_eval_batch(f2_ctx* ctx, const f2_cnn* cnn, const void* wave, int wave_dty
     return F2_OK;
 }
 
+int f2_input_batch(f2_ctx* ctx, const void* wave, int wave_dtype, const int64_t* offsets, const double* coefs, int B, int C,
+                   int lpf, double cutoff_hz, int fft_precision, const int64_t* center_offsets, const int64_t* centers,
+                   int radius, int step, int normalize, float* windows, int mem_space) {
+    F2_CHECK(nullptr, ctx, F2_ERR_INVALID, "ctx is NULL");
+    F2_HIP(ctx, hipSetDevice(ctx->device));
+    F2_CHECK(ctx, mem_space == F2_MEM_HOST || mem_space == F2_MEM_DEVICE, F2_ERR_INVALID, "bad mem_space %d", mem_space);
+    F2_CHECK(ctx, wave_dtype == F2_WAVE_I16 || wave_dtype == F2_WAVE_F64, F2_ERR_INVALID, "bad wave_dtype %d", wave_dtype);
+    F2_CHECK(ctx, fft_precision == F2_FFT_F32 || fft_precision == F2_FFT_F64, F2_ERR_INVALID, "bad fft_precision %d", fft_precision);
+    F2_CHECK(ctx, !lpf || (cutoff_hz > 0 && cutoff_hz < 8000), F2_ERR_INVALID, "cutoff %g Hz outside (0, 8000)", cutoff_hz);
+    F2_CHECK(ctx, B >= 0 && C > 0 && radius >= 0 && step >= 0, F2_ERR_INVALID, "bad size");
+    if (B == 0) return F2_OK;
+    F2_CHECK(ctx, offsets && center_offsets, F2_ERR_INVALID, "null argument");
+    F2_CHECK(ctx, offsets[0] == 0 && center_offsets[0] == 0, F2_ERR_INVALID, "offsets[0] and center_offsets[0] must be 0");
+    for (int b = 0; b < B; ++b) {
+        F2_CHECK(ctx, offsets[b + 1] >= offsets[b], F2_ERR_INVALID, "offsets must not decrease (utterance %d)", b);
+        F2_CHECK(ctx, center_offsets[b + 1] >= center_offsets[b], F2_ERR_INVALID, "center_offsets must not decrease (utterance %d)", b);
+    }
+    const int64_t n_windows = center_offsets[B];
+    if (n_windows == 0) return F2_OK;
+    F2_CHECK(ctx, wave && coefs && centers && windows, F2_ERR_INVALID, "null data pointer");
+    // InputGenerator.py:73-80 indexes each utterance's own envelope: a window must lie inside it
+    const int64_t reach = (int64_t)radius * step;
+    std::vector<int> win_utt((size_t)n_windows);
+    for (int b = 0; b < B; ++b) {
+        const int64_t nb = offsets[b + 1] - offsets[b];
+        for (int64_t e = center_offsets[b]; e < center_offsets[b + 1]; ++e) {
+            F2_CHECK(ctx, centers[e] - reach >= 0 && centers[e] + reach < nb, F2_ERR_INVALID,
+                     "utterance %d: window %lld (centre %lld, +-%lld) reaches outside its %lld-sample envelope", b,
+                     (long long)(e - center_offsets[b]), (long long)centers[e], (long long)reach, (long long)nb);
+            win_utt[(size_t)e] = b;
+        }
+    }
+    const int64_t total = offsets[B];
+    const int R = 2 * radius + 1;
+
+    // envelopes of the whole batch, by the routes of f2_filterbank_envelope_fused (gfb_or_null = NULL), into a scratch buffer
+    F2_TRY(f2_upload_offsets(ctx, offsets, B));
+    F2_TRY(f2_upload_coefs(ctx, coefs, C));
+    F2_TRY(f2_reserve(ctx, ctx->stage_out, sizeof(double) * (size_t)C * (size_t)total));
+    double* d_env = (double*)ctx->stage_out.ptr;
+    const void* d_wave = wave;
+    if (mem_space == F2_MEM_HOST) {
+        const size_t wb = (wave_dtype == F2_WAVE_I16 ? 2 : 8) * (size_t)total;
+        F2_TRY(f2_reserve(ctx, ctx->stage_in, wb));
+        F2_HIP(ctx, hipMemcpyAsync(ctx->stage_in.ptr, wave, wb, hipMemcpyHostToDevice, ctx->stream));
+        d_wave = ctx->stage_in.ptr;
+    }
+    F2_TRY(f2_envelopes_device(ctx, d_wave, wave_dtype, offsets, B, C, lpf, cutoff_hz, fft_precision, d_env, nullptr));
+
+    // all windows of the batch in one gather launch: centres and the utterance of every window in one upload
+    const size_t cbytes = sizeof(int64_t) * (size_t)n_windows, ubytes = sizeof(int) * (size_t)n_windows;
+    F2_TRY(f2_reserve(ctx, ctx->work2, cbytes + ubytes));
+    F2_TRY(f2_upload_async(ctx, ctx->work2.ptr, centers, cbytes));
+    F2_TRY(f2_upload_async(ctx, (char*)ctx->work2.ptr + cbytes, win_utt.data(), ubytes));
+    const size_t out_bytes = sizeof(float) * (size_t)n_windows * R * (size_t)C;
+    float* d_out = windows;
+    if (mem_space == F2_MEM_HOST) {
+        F2_TRY(f2_reserve(ctx, ctx->xbuf, out_bytes));
+        d_out = (float*)ctx->xbuf.ptr;
+    }
+    F2_TRY(reset_flag(ctx));
+    F2_TRY(f2_launch_gather_ragged(ctx, d_env, C, (const int64_t*)ctx->offsets.ptr, (const int64_t*)ctx->work2.ptr,
+                                   (const int*)((char*)ctx->work2.ptr + cbytes), n_windows, radius, step, normalize, d_out,
+                                   (int*)ctx->flags.ptr));
+    if (mem_space == F2_MEM_HOST) F2_HIP(ctx, hipMemcpyAsync(windows, d_out, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    if (normalize || mem_space == F2_MEM_HOST) {
+        int flag = 0;
+        F2_TRY(read_flag(ctx, &flag));
+        F2_CHECK(ctx, !flag, F2_ERR_NONPOSITIVE, "values must all be positive (normalizeInput)");
+    }
+    return F2_OK;
+}
+
 }  // extern "C"

@@ -15,12 +15,16 @@ from ...runtime import rank_world
 def GetListOfEnvelopeFilesAndTimepoints(labelFilename):
     """dict {"<TEST|TRAIN>/<region>.<speaker>.<sentence>.ENV1.npy": [timepoints in CSV order]} (reference :9-25)."""
     output = dict()
+    keys = dict()     # (a path join per CSV row was most of the parse time of a large label file)
     with open(labelFilename, 'r') as labelFile:
         for row in csv.reader(labelFile):
             if not row:
                 continue
             testOrTrain, region, speaker, sentence, _phoneme, timepoint = row[:6]
-            key = os.path.join(testOrTrain, '.'.join((region, speaker, sentence, 'ENV1.npy')))
+            key = keys.get((testOrTrain, region, speaker, sentence))
+            if key is None:
+                key = keys[testOrTrain, region, speaker, sentence] = os.path.join(
+                    testOrTrain, '.'.join((region, speaker, sentence, 'ENV1.npy')))
             output.setdefault(key, []).append(int(timepoint))
     return output
 
@@ -96,6 +100,117 @@ def GenerateInputData(labelFile=None, inputFile=None, LPF=False, CUTOFF=100):
         _finish_shared_output(target, backup, rank, world)
     print('                Total time:', time.time() - started)
     print('')
+
+
+def wav_for_label_key(key):
+    """Label-CSV key "TRAIN/DR1.FCJF0.SA1.ENV1.npy" -> the audio it was made from, "resources/f2cnn/TRAIN/DR1.FCJF0.SA1.WAV"."""
+    base = key[:-len('.ENV1.npy')] if key.endswith('.ENV1.npy') else os.path.splitext(key)[0]
+    return os.path.join('resources', 'f2cnn', base + '.WAV')
+
+
+def GenerateInputDataFromWav(labelFile=None, inputFile=None, LPF=False, CUTOFF=100, batch_files=64, metrics=None):
+    """`prepare input --from-wav`: what `prepare features` followed by `prepare input` produce, straight from the audio.
+
+    Every labelled file's WAV is read (GetArrayFromWAV), filtered and enveloped on the device with the coefficients of
+    `prepare features` (filterbank_from_config) and its mixed-dtype rule, and only the (2*RADIUS+1, C) windows at the
+    labelled timepoints come back (f2_input_batch): no .GFB.npy or .ENV1.npy is written. Output file, row order (files in
+    sorted key order, timepoints in CSV order) and the multi-rank protocol are those of GenerateInputData.
+
+    LPF / CUTOFF set the envelope's low-pass here (with the two-step path the envelopes were made by `prepare envelope`
+    or `prepare features` and CUTOFF only named the output file). Files run `batch_files` at a time (enough rows for the
+    spectral kernel's grid), the WAV reads of the next batches on reader threads. A label key without its WAV raises
+    FileNotFoundError, a timepoint whose window leaves its file ValueError, both before any device work. Returns the
+    JobReport (`metrics`: its JSON summary)."""
+    from ...iopipe import JobReport, run_batches
+    from ...gammatone import filters
+    from .EnvelopeExtraction import FFT_PRECISION
+    from .GammatoneFiltering import GetArrayFromWAV, filterbank_from_config
+    started = time.time()
+    report = JobReport("prepare input --from-wav", metrics=metrics)
+    if not os.path.isdir("trainingData"):
+        print("LABEL GENERATION SHOULD BE DONE PRIOR TO INPUT...")
+        exit(-1)
+    label_csv = labelFile or os.path.join("trainingData", "label_data.csv")
+    per_file = GetListOfEnvelopeFilesAndTimepoints(label_csv)
+    print("\n###############################\nGenerating Input Data from the audio of the files in '{}'.".format(label_csv))
+    print("Using Low Pass Filtering with a cutoff at {}Hz".format(CUTOFF) if LPF else "Not using Low Pass Filtering")
+    if not per_file:
+        print("NO LABELLED FILES FOUND, PLEASE GENERATE LABELS")
+        exit(-1)
+    order = sorted(per_file)
+    for key in order:
+        if not os.path.isfile(wav_for_label_key(key)):
+            raise FileNotFoundError("{} (label key {}) does not exist".format(wav_for_label_key(key), key))
+    first_row = numpy.concatenate([[0], numpy.cumsum([len(per_file[name]) for name in order])])
+    print(len(order), "files found along with their", int(first_row[-1]), "entry timepoints.")
+    cfg = F2Config()
+    _, coefs = filterbank_from_config(cfg)
+    coefs = numpy.ascontiguousarray(coefs, dtype=numpy.float64)
+    Cn = coefs.shape[0]
+    shape = (int(first_row[-1]), cfg.dots_per_input, Cn)
+    target = inputFile or os.path.join('trainingData',
+                                       'input_data_LPF{}.npy'.format(CUTOFF) if LPF else 'input_data_NOLPF.npy')
+    os.makedirs(os.path.dirname(target) or '.', exist_ok=True)
+    rank, world = rank_world()
+    print("Output shape:", shape)
+    windows = numpy.empty(shape, dtype=numpy.float32) if world == 1 else _shared_output(target, shape, rank, world)
+    reach = cfg.radius * cfg.step
+    ctx = _lib.default_context()
+
+    def load(k):
+        return GetArrayFromWAV(wav_for_label_key(order[k]))
+
+    def compute(loaded):
+        args = []
+        for k, (_rate, samples) in loaded:
+            wave = filters._wave_args(samples)
+            n = wave[0].shape[0]
+            for tp in per_file[order[k]]:
+                if tp - reach < 0 or tp + reach >= n:
+                    raise ValueError("{}: the window at timepoint {} (+-{} samples) reaches outside its {} samples".format(
+                        wav_for_label_key(order[k]), tp, reach, n))
+            args.append(wave)
+        dt = args[0][1] if all(a[1] == args[0][1] for a in args) else _lib.WAVE_F64
+        dtype = numpy.int16 if dt == _lib.WAVE_I16 else numpy.float64
+        offsets = numpy.zeros(len(args) + 1, dtype=numpy.int64)
+        offsets[1:] = numpy.cumsum([a[0].shape[0] for a in args])
+        center_offsets = numpy.zeros(len(args) + 1, dtype=numpy.int64)
+        center_offsets[1:] = numpy.cumsum([len(per_file[order[k]]) for k, _ in loaded])
+        centers = numpy.concatenate([per_file[order[k]] for k, _ in loaded]).astype(numpy.int64)
+        flat = numpy.concatenate([a[0].astype(dtype, copy=False) for a in args])
+        ks = [k for k, _ in loaded]
+        # files of consecutive rows (one rank): the windows come back straight into their place in the output
+        direct = ks == list(range(ks[0], ks[-1] + 1))
+        out = windows[first_row[ks[0]]:first_row[ks[-1] + 1]] if direct else \
+            numpy.empty((int(center_offsets[-1]), cfg.dots_per_input, Cn), numpy.float32)
+        ctx.input_batch(flat, dt, offsets, coefs, len(args), Cn, bool(LPF), CUTOFF if LPF else 0.0, FFT_PRECISION,
+                        center_offsets, centers, cfg.radius, cfg.step, False, out, _lib.MEM_HOST)
+        return [((k, rate, int(offsets[b + 1] - offsets[b])), None if direct else out[center_offsets[b]:center_offsets[b + 1]])
+                for b, (k, (rate, _)) in enumerate(loaded)]
+
+    def save(item, block):
+        k, rate, n = item
+        if block is not None:
+            windows[first_row[k]:first_row[k + 1]] = block
+        print("\t\t{:<50} done !  {}/{} Files".format(wav_for_label_key(order[k]), report.add(n, rate), len(order)))
+
+    run_batches(list(range(len(order)))[rank::world], load, compute, save, batch=batch_files)
+    print('Generated Input Matrix of shape {}.'.format(shape))
+    print("Saving as {}...".format(target))
+    backup = os.path.join('trainingData', 'last_input_data.npy')      # the reference's second copy (:90)
+    if world == 1:
+        # the two copies side by side (with the device work this short, writing them is much of the wall time)
+        paths = [target] + ([backup] if os.path.abspath(backup) != os.path.abspath(target) else [])
+        with ThreadPoolExecutor(len(paths)) as writers:
+            list(writers.map(lambda path: numpy.save(path, windows), paths))
+    else:
+        windows.flush()
+        del windows
+        _finish_shared_output(target, backup, rank, world)
+    print('                Total time:', time.time() - started)
+    print('')
+    report.finish()
+    return report
 
 
 def _run_token():

@@ -62,7 +62,7 @@ enum { F2_FFT_F32 = 0, F2_FFT_F64 = 1 };
 /* ---- library / context -------------------------------------------------------------------- */
 int f2_version(void);   /* 100 * major + minor; 101 added f2_eval_batch, 102 f2_host_alloc + F2_MEM_HOST_ASYNC, 103 f2_ctx_set_option, 105 f2_spectral_guard_read + f2_cnn_get_info,
                            106 f2_cnn_forward accepts any finite input on the split path (scales from the input's range; the
-                           f2_cnn_get_info keys "f16x3_ok", "f16x3_check_diff", "last_input_bound") */
+                           f2_cnn_get_info keys "f16x3_ok", "f16x3_check_diff", "last_input_bound"), 107 f2_input_batch */
 int f2_device_count(int* count);
 int f2_ctx_create(int device, f2_ctx** ctx);
 int f2_ctx_destroy(f2_ctx* ctx);
@@ -190,6 +190,27 @@ int f2_filterbank_envelope_fused(f2_ctx* ctx, const void* wave, int wave_dtype, 
  */
 int f2_gather_windows(f2_ctx* ctx, const double* env, int C, int64_t N, const int64_t* centers,
                       int64_t n_windows, int radius, int step, int normalize, float* out, int mem_space);
+
+/* ---- K1+K2+K3: training windows straight from the waves ------------------------------------------
+ * Replaces scripts/processing/InputGenerator.py:73-83 (windows at the labelled timepoints, cast to float32) together
+ * with the `prepare filter` + `prepare envelope` runs whose .ENV1.npy files it reads: the envelopes of the ragged batch
+ * stay in device scratch memory and only the windows leave it.
+ *   wave, wave_dtype, offsets, coefs, B, C, lpf, cutoff_hz, fft_precision   as for f2_filterbank_envelope_fused; the
+ *                     envelopes are what that call computes for the same batch and options with gfb_or_null = NULL
+ *   center_offsets    host, B+1 entries, center_offsets[0] == 0, non-decreasing: utterance b owns the centres
+ *                     centers[center_offsets[b] .. center_offsets[b+1])
+ *   centers           host, center_offsets[B] timepoints, each relative to the first sample of its own utterance
+ *   windows           out, (center_offsets[B], 2*radius+1, C) float32; window e is what f2_gather_windows gives for
+ *                     centers[e] on its utterance's (C, n_b) envelope (bit for bit), all windows in one launch
+ *   normalize         as for f2_gather_windows (0: `prepare input`; 1: scripts/CNN/Training.py:13-28 normalizeInput)
+ * wave and windows are in mem_space (F2_MEM_HOST or F2_MEM_DEVICE). Returns F2_ERR_INVALID if a window reaches outside
+ * [0, n_b) of its utterance (the message names the utterance, the centre and n_b), F2_ERR_NONPOSITIVE if normalize != 0
+ * and a window holds a value <= 0. B == 0, no centres at all, or utterances without centres (which may be shorter than
+ * a window): F2_OK, nothing written for them.
+ */
+int f2_input_batch(f2_ctx* ctx, const void* wave, int wave_dtype, const int64_t* offsets, const double* coefs, int B,
+                   int C, int lpf, double cutoff_hz, int fft_precision, const int64_t* center_offsets,
+                   const int64_t* centers, int radius, int step, int normalize, float* windows, int mem_space);
 
 /* ---- K4: CNN forward ---------------------------------------------------------------------------
  * Replaces keras model.predict + the label rule of scripts/CNN/Evaluating.py:85-87 for the
