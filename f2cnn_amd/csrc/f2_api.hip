@@ -579,21 +579,70 @@ const char* f2_prof_kernel_name(int kernel_id) {
     return kernel_id >= 0 && kernel_id < F2_K_COUNT ? names[kernel_id] : "";
 }
 
+}  // extern "C" (internal helpers follow)
+
 // ------------------------------------------------------------------------------------------------
-// argument checking shared by the batched DSP entry points
+// argument checks and wave staging shared by the entry points that take caller data, here and in f2_pipeline.hip (f2_internal.h)
 // ------------------------------------------------------------------------------------------------
-static int check_batch(f2_ctx* ctx, const int64_t* offsets, int B, int C, int mem_space) {
-    F2_CHECK(ctx, B >= 0 && C >= 0, F2_ERR_INVALID, "negative batch (B=%d) or channel count (C=%d)", B, C);
-    F2_CHECK(ctx, mem_space == F2_MEM_HOST || mem_space == F2_MEM_DEVICE || mem_space == F2_MEM_HOST_ASYNC, F2_ERR_INVALID,
-             "bad mem_space %d", mem_space);
-    F2_CHECK(ctx, offsets, F2_ERR_INVALID, "offsets is NULL");
-    F2_CHECK(ctx, offsets[0] == 0, F2_ERR_INVALID, "offsets[0] must be 0");
-    for (int b = 0; b < B; ++b)
-        F2_CHECK(ctx, offsets[b + 1] >= offsets[b], F2_ERR_INVALID, "offsets must be non-decreasing (b=%d)", b);
+int f2_check_ctx(f2_ctx* ctx) {
+    F2_CHECK(nullptr, ctx, F2_ERR_INVALID, "ctx is NULL");
+    F2_HIP(ctx, hipSetDevice(ctx->device));
     return F2_OK;
 }
 
-}  // extern "C" (internal helpers follow)
+int f2_check_wave_dtype(f2_ctx* ctx, int wave_dtype) {
+    F2_CHECK(ctx, wave_dtype == F2_WAVE_I16 || wave_dtype == F2_WAVE_F64, F2_ERR_INVALID, "bad wave_dtype %d", wave_dtype);
+    return F2_OK;
+}
+
+int f2_check_envelope_args(f2_ctx* ctx, int lpf, double cutoff_hz, int fft_precision) {
+    F2_CHECK(ctx, fft_precision == F2_FFT_F32 || fft_precision == F2_FFT_F64, F2_ERR_INVALID, "bad fft_precision %d", fft_precision);
+    F2_CHECK(ctx, !lpf || (cutoff_hz > 0 && cutoff_hz < 8000), F2_ERR_INVALID, "cutoff %g Hz outside (0, 8000)", cutoff_hz);
+    return F2_OK;
+}
+
+int f2_check_dsp(f2_ctx* ctx, int wave_dtype, int lpf, double cutoff_hz, int fft_precision) {
+    F2_TRY(f2_check_wave_dtype(ctx, wave_dtype));
+    return f2_check_envelope_args(ctx, lpf, cutoff_hz, fft_precision);
+}
+
+int f2_check_mem_space(f2_ctx* ctx, int mem_space, bool allow_async) {
+    F2_CHECK(ctx, mem_space == F2_MEM_HOST || mem_space == F2_MEM_DEVICE || (allow_async && mem_space == F2_MEM_HOST_ASYNC),
+             F2_ERR_INVALID, "bad mem_space %d", mem_space);
+    return F2_OK;
+}
+
+int f2_check_offsets(f2_ctx* ctx, const int64_t* offsets, int B, const char* name) {
+    F2_CHECK(ctx, offsets, F2_ERR_INVALID, "%s is NULL", name);
+    F2_CHECK(ctx, offsets[0] == 0, F2_ERR_INVALID, "%s[0] must be 0", name);
+    for (int b = 0; b < B; ++b)
+        F2_CHECK(ctx, offsets[b + 1] >= offsets[b], F2_ERR_INVALID, "%s must be non-decreasing (b=%d)", name, b);
+    return F2_OK;
+}
+
+int f2_check_batch(f2_ctx* ctx, const int64_t* offsets, int B, int C, int mem_space, bool pipeline) {
+    F2_CHECK(ctx, B >= 0 && C >= (pipeline ? 1 : 0), F2_ERR_INVALID, "bad batch size (B=%d) or channel count (C=%d)", B, C);
+    F2_TRY(f2_check_mem_space(ctx, mem_space, !pipeline));
+    return f2_check_offsets(ctx, offsets, B, "offsets");
+}
+
+int f2_check_cnn(f2_ctx* ctx, const f2_cnn* cnn, int rows, int C) {
+    F2_CHECK(ctx, cnn, F2_ERR_INVALID, "cnn is NULL");
+    F2_CHECK(ctx, cnn->dev == ctx->device, F2_ERR_INVALID, "cnn weights live on device %d, context on %d", cnn->dev, ctx->device);
+    F2_CHECK(ctx, rows == 0 || (cnn->rows == rows && cnn->channels == C), F2_ERR_INVALID,
+             "network was built for %d x %d windows, asked for %d x %d", cnn->rows, cnn->channels, rows, C);
+    return F2_OK;
+}
+
+int f2_stage_wave(f2_ctx* ctx, const void* wave, int wave_dtype, int64_t total, int mem_space, const void** d_wave) {
+    *d_wave = wave;
+    if (mem_space == F2_MEM_DEVICE) return F2_OK;
+    const size_t bytes = (wave_dtype == F2_WAVE_I16 ? 2 : 8) * (size_t)total;
+    F2_TRY(f2_reserve(ctx, ctx->stage_in, bytes));
+    F2_HIP(ctx, hipMemcpyAsync(ctx->stage_in.ptr, wave, bytes, hipMemcpyHostToDevice, ctx->stream));
+    *d_wave = ctx->stage_in.ptr;
+    return F2_OK;
+}
 
 int f2_upload_offsets(f2_ctx* ctx, const int64_t* offsets, int B) {
     if (ctx->offsets_host.size() == (size_t)(B + 1) &&
@@ -651,21 +700,23 @@ int f2_plan_handoff(f2_ctx* ctx, const int64_t* h_offsets, int B, int C, int pre
     return F2_OK;
 }
 
-static size_t wave_elem(int wave_dtype) { return wave_dtype == F2_WAVE_I16 ? 2 : 8; }
-
-// The device part of f2_filterbank_envelope_fused, shared with f2_input_batch (f2_pipeline.hip). The caller has uploaded
-// offsets and coefficients (f2_upload_offsets / f2_upload_coefs) and staged the wave.
+// Filterbank + envelope of a ragged batch on the device: the part that f2_filterbank_envelope_fused, f2_input_batch
+// (`spectral` = true) and the eval calls (false) share. The caller has uploaded offsets and coefficients
+// (f2_upload_offsets / f2_upload_coefs) and staged the wave.
 int f2_envelopes_device(f2_ctx* ctx, const void* d_wave, int wave_dtype, const int64_t* offsets, int B, int C, int lpf,
-                        double cutoff_hz, int fft_precision, double* d_env, double* d_gfb) {
+                        double cutoff_hz, int fft_precision, double* d_env, double* d_gfb, bool spectral) {
     // Spectral path (f2_spectral.hip): utterances it can serve (float FFT, no GFB output wanted, make_erb_filters-shaped
     // table, 4097..65472 samples with padding to look at) get their envelopes from ONE kernel that never materialises
     // the filterbank rows. Everything else - and any utterance that kernel's accuracy guard flags on the device - goes
-    // through the filterbank kernel + envelope kernel below, which skip utterances whose flag is 0.
+    // through the filterbank kernel + envelope kernel below, which skip utterances whose flag is 0. A caller that passes
+    // `spectral` = false gets the two kernels for every utterance, and what the context remembers of the last spectral
+    // call (spec_last_B, the guard dump) stays as it is.
     const int* d_uflag = nullptr;
-    ctx->spec_last_B = 0;
-    if (ctx->opt_spectral && fft_precision == F2_FFT_F32 && !d_gfb && ctx->spec_coefs_ok < 0)
+    if (spectral) ctx->spec_last_B = 0;
+    spectral = spectral && ctx->opt_spectral && fft_precision == F2_FFT_F32 && !d_gfb;
+    if (spectral && ctx->spec_coefs_ok < 0)
         ctx->spec_coefs_ok = f2_spectral_supports_coefs(ctx->coefs_host, C, nullptr, &ctx->spec_min_pad) ? 1 : 0;   // (once per table: ~50 us of logarithms)
-    if (ctx->opt_spectral && fft_precision == F2_FFT_F32 && !d_gfb && ctx->spec_coefs_ok == 1) {
+    if (spectral && ctx->spec_coefs_ok == 1) {
         std::vector<int> meta((size_t)B, 1);
         std::vector<int> lists[F2_SPECTRAL_MAX_LOG2H + 1];
         int nspec = 0;
@@ -732,27 +783,23 @@ extern "C" {
 
 int f2_erb_filterbank_batch(f2_ctx* ctx, const void* wave, int wave_dtype, const int64_t* offsets,
                             const double* coefs, int B, int C, double* gfb, int mem_space) {
-    F2_CHECK(nullptr, ctx, F2_ERR_INVALID, "ctx is NULL");
-    F2_HIP(ctx, hipSetDevice(ctx->device));
-    F2_CHECK(ctx, wave_dtype == F2_WAVE_I16 || wave_dtype == F2_WAVE_F64, F2_ERR_INVALID, "bad wave_dtype %d", wave_dtype);
-    F2_TRY(check_batch(ctx, offsets, B, C, mem_space));
+    F2_TRY(f2_check_ctx(ctx));
+    F2_TRY(f2_check_wave_dtype(ctx, wave_dtype));
+    F2_TRY(f2_check_batch(ctx, offsets, B, C, mem_space, false));
     const int64_t total = offsets[B];
     if (B == 0 || C == 0 || total == 0) return F2_OK;
     F2_CHECK(ctx, wave && coefs && gfb, F2_ERR_INVALID, "null data pointer");
     F2_TRY(f2_upload_offsets(ctx, offsets, B));
     F2_TRY(f2_upload_coefs(ctx, coefs, C));
-    const void* d_wave = wave;
     double* d_gfb = gfb;
     const size_t out_bytes = sizeof(double) * (size_t)C * (size_t)total;
     const bool staged = mem_space != F2_MEM_DEVICE;
     if (staged) {
-        F2_TRY(f2_reserve(ctx, ctx->stage_in, wave_elem(wave_dtype) * (size_t)total));
         F2_TRY(f2_reserve(ctx, ctx->stage_out, out_bytes));
-        F2_HIP(ctx, hipMemcpyAsync(ctx->stage_in.ptr, wave, wave_elem(wave_dtype) * (size_t)total, hipMemcpyHostToDevice,
-                                   ctx->stream));
-        d_wave = ctx->stage_in.ptr;
         d_gfb = (double*)ctx->stage_out.ptr;
     }
+    const void* d_wave;
+    F2_TRY(f2_stage_wave(ctx, wave, wave_dtype, total, mem_space, &d_wave));
     F2_TRY(f2_launch_filterbank(ctx, d_wave, wave_dtype, (const int64_t*)ctx->offsets.ptr, offsets,
                                 (const double*)ctx->coefs.ptr, B, C, d_gfb));
     if (staged) {
@@ -764,11 +811,9 @@ int f2_erb_filterbank_batch(f2_ctx* ctx, const void* wave, int wave_dtype, const
 
 int f2_envelope_batch(f2_ctx* ctx, const double* gfb, const int64_t* offsets, int B, int C, int lpf,
                       double cutoff_hz, int fft_precision, double* env, int mem_space) {
-    F2_CHECK(nullptr, ctx, F2_ERR_INVALID, "ctx is NULL");
-    F2_HIP(ctx, hipSetDevice(ctx->device));
-    F2_CHECK(ctx, fft_precision == F2_FFT_F32 || fft_precision == F2_FFT_F64, F2_ERR_INVALID, "bad fft_precision %d", fft_precision);
-    F2_CHECK(ctx, !lpf || (cutoff_hz > 0 && cutoff_hz < 8000), F2_ERR_INVALID, "cutoff %g Hz outside (0, 8000)", cutoff_hz);
-    F2_TRY(check_batch(ctx, offsets, B, C, mem_space));
+    F2_TRY(f2_check_ctx(ctx));
+    F2_TRY(f2_check_envelope_args(ctx, lpf, cutoff_hz, fft_precision));
+    F2_TRY(f2_check_batch(ctx, offsets, B, C, mem_space, false));
     const int64_t total = offsets[B];
     if (B == 0 || C == 0 || total == 0) return F2_OK;
     F2_CHECK(ctx, gfb && env, F2_ERR_INVALID, "null data pointer");
@@ -798,33 +843,27 @@ int f2_envelope_batch(f2_ctx* ctx, const double* gfb, const int64_t* offsets, in
 int f2_filterbank_envelope_fused(f2_ctx* ctx, const void* wave, int wave_dtype, const int64_t* offsets,
                                  const double* coefs, int B, int C, int lpf, double cutoff_hz,
                                  int fft_precision, double* env, double* gfb_or_null, int mem_space) {
-    F2_CHECK(nullptr, ctx, F2_ERR_INVALID, "ctx is NULL");
-    F2_HIP(ctx, hipSetDevice(ctx->device));
-    F2_CHECK(ctx, wave_dtype == F2_WAVE_I16 || wave_dtype == F2_WAVE_F64, F2_ERR_INVALID, "bad wave_dtype %d", wave_dtype);
-    F2_CHECK(ctx, fft_precision == F2_FFT_F32 || fft_precision == F2_FFT_F64, F2_ERR_INVALID, "bad fft_precision %d", fft_precision);
-    F2_CHECK(ctx, !lpf || (cutoff_hz > 0 && cutoff_hz < 8000), F2_ERR_INVALID, "cutoff %g Hz outside (0, 8000)", cutoff_hz);
-    F2_TRY(check_batch(ctx, offsets, B, C, mem_space));
+    F2_TRY(f2_check_ctx(ctx));
+    F2_TRY(f2_check_dsp(ctx, wave_dtype, lpf, cutoff_hz, fft_precision));
+    F2_TRY(f2_check_batch(ctx, offsets, B, C, mem_space, false));
     const int64_t total = offsets[B];
     if (B == 0 || C == 0 || total == 0) return F2_OK;
     F2_CHECK(ctx, wave && coefs && env, F2_ERR_INVALID, "null data pointer");
     F2_TRY(f2_upload_offsets(ctx, offsets, B));
     F2_TRY(f2_upload_coefs(ctx, coefs, C));
     const size_t bytes = sizeof(double) * (size_t)C * (size_t)total;
-    const void* d_wave = wave;
     double* d_env = env;
     double* d_gfb = gfb_or_null;
     const bool staged = mem_space != F2_MEM_DEVICE;
     if (staged) {
-        F2_TRY(f2_reserve(ctx, ctx->stage_in, wave_elem(wave_dtype) * (size_t)total));
         F2_TRY(f2_reserve(ctx, ctx->stage_out, bytes));
         if (gfb_or_null) F2_TRY(f2_reserve(ctx, ctx->stage_aux, bytes));
-        F2_HIP(ctx, hipMemcpyAsync(ctx->stage_in.ptr, wave, wave_elem(wave_dtype) * (size_t)total, hipMemcpyHostToDevice,
-                                   ctx->stream));
-        d_wave = ctx->stage_in.ptr;
         d_env = (double*)ctx->stage_out.ptr;
         d_gfb = gfb_or_null ? (double*)ctx->stage_aux.ptr : nullptr;
     }
-    F2_TRY(f2_envelopes_device(ctx, d_wave, wave_dtype, offsets, B, C, lpf, cutoff_hz, fft_precision, d_env, d_gfb));
+    const void* d_wave;
+    F2_TRY(f2_stage_wave(ctx, wave, wave_dtype, total, mem_space, &d_wave));
+    F2_TRY(f2_envelopes_device(ctx, d_wave, wave_dtype, offsets, B, C, lpf, cutoff_hz, fft_precision, d_env, d_gfb, true));
     if (staged) {
         F2_HIP(ctx, hipMemcpyAsync(env, d_env, bytes, hipMemcpyDeviceToHost, ctx->stream));
         if (gfb_or_null) F2_HIP(ctx, hipMemcpyAsync(gfb_or_null, d_gfb, bytes, hipMemcpyDeviceToHost, ctx->stream));

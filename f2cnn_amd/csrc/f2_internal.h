@@ -183,6 +183,23 @@ int f2_upload_async(f2_ctx* ctx, void* d_dst, const void* src, size_t bytes);
 int f2_upload_offsets(f2_ctx* ctx, const int64_t* offsets, int B);
 int f2_upload_coefs(f2_ctx* ctx, const double* coefs, int C);
 
+struct f2_cnn;
+// ---- argument checks of the entry points that take caller data (f2_api.hip): every one of these conditions is tested here
+// and nowhere else; all fail with F2_ERR_INVALID ----
+int f2_check_ctx(f2_ctx* ctx);    // non-NULL, and makes its device current
+int f2_check_wave_dtype(f2_ctx* ctx, int wave_dtype);
+int f2_check_envelope_args(f2_ctx* ctx, int lpf, double cutoff_hz, int fft_precision);
+int f2_check_dsp(f2_ctx* ctx, int wave_dtype, int lpf, double cutoff_hz, int fft_precision);   // the two above
+int f2_check_mem_space(f2_ctx* ctx, int mem_space, bool allow_async);
+int f2_check_offsets(f2_ctx* ctx, const int64_t* offsets, int B, const char* name);   // non-NULL, [0] == 0, non-decreasing
+// B, C, mem_space and offsets of a ragged batch. `pipeline` (the calls of f2_pipeline.hip): C == 0 and F2_MEM_HOST_ASYNC are
+// errors; without it C == 0 is an empty call and the third memory space is accepted
+int f2_check_batch(f2_ctx* ctx, const int64_t* offsets, int B, int C, int mem_space, bool pipeline);
+// non-NULL, weights on the context's device, built for rows x C windows (rows == 0: the call has no window shape of its own)
+int f2_check_cnn(f2_ctx* ctx, const f2_cnn* cnn, int rows, int C);
+// *d_wave = the caller's pointer for F2_MEM_DEVICE, else ctx->stage_in after an asynchronous copy of `total` samples into it
+int f2_stage_wave(f2_ctx* ctx, const void* wave, int wave_dtype, int64_t total, int mem_space, const void** d_wave);
+
 #define F2_HIP(ctx, call)                                                                      \
     do {                                                                                       \
         hipError_t e_ = (call);                                                                \
@@ -299,11 +316,12 @@ struct f2_handoff {
     const int64_t* h_x32_off = nullptr;     // the same on the host (owned by the context, valid until the next plan)
 };
 int f2_plan_handoff(f2_ctx* ctx, const int64_t* h_offsets, int B, int C, int precision, bool want_gfb, f2_handoff* plan);
-// Filterbank + envelope of a ragged batch on the device, by the routes of f2_filterbank_envelope_fused (f2_api.hip): spectral
-// kernel with its guard, then filterbank + envelope kernels for the rest. Offsets and coefficients already uploaded
-// (f2_upload_offsets / f2_upload_coefs); h_offsets host, d_wave / d_env / d_gfb (NULL: not wanted) device.
+// Filterbank + envelope of a ragged batch on the device (f2_api.hip). `spectral`: by the routes of f2_filterbank_envelope_fused -
+// spectral kernel with its guard, then filterbank + envelope kernels for the rest; without it (the eval calls) the two kernels
+// for every utterance. Offsets and coefficients already uploaded (f2_upload_offsets / f2_upload_coefs); h_offsets host,
+// d_wave / d_env / d_gfb (NULL: not wanted) device.
 int f2_envelopes_device(f2_ctx* ctx, const void* d_wave, int wave_dtype, const int64_t* h_offsets, int B, int C, int lpf,
-                        double cutoff_hz, int fft_precision, double* d_env, double* d_gfb);
+                        double cutoff_hz, int fft_precision, double* d_env, double* d_gfb, bool spectral);
 // d_uflag (device, B ints) != NULL: only utterances whose flag is non-zero are processed (the rest were served by the
 // spectral kernel); the flags may be written by earlier launches on the stream.
 // h_flag0 (host, B ints, with d_uflag): the flags as they are before the spectral kernel runs - the utterances this launch

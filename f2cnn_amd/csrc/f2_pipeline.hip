@@ -14,11 +14,11 @@ int reset_flag(f2_ctx* ctx) {
     return F2_OK;
 }
 
-// waits for the stream
-int read_flag(f2_ctx* ctx, int* value) {
+// waits for the stream; the error of a window with a value <= 0 under normalisation (the gather kernels set the flag)
+int finish_positive(f2_ctx* ctx) {
     F2_HIP(ctx, hipMemcpyAsync(ctx->host_flags, ctx->flags.ptr, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     F2_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    *value = ctx->host_flags[0];
+    F2_CHECK(ctx, !ctx->host_flags[0], F2_ERR_NONPOSITIVE, "values must all be positive (normalizeInput)");
     return F2_OK;
 }
 
@@ -87,9 +87,8 @@ extern "C" {
 
 int f2_gather_windows(f2_ctx* ctx, const double* env, int C, int64_t N, const int64_t* centers, int64_t n_windows,
                       int radius, int step, int normalize, float* out, int mem_space) {
-    F2_CHECK(nullptr, ctx, F2_ERR_INVALID, "ctx is NULL");
-    F2_HIP(ctx, hipSetDevice(ctx->device));
-    F2_CHECK(ctx, mem_space == F2_MEM_HOST || mem_space == F2_MEM_DEVICE, F2_ERR_INVALID, "bad mem_space %d", mem_space);
+    F2_TRY(f2_check_ctx(ctx));
+    F2_TRY(f2_check_mem_space(ctx, mem_space, false));
     F2_CHECK(ctx, C >= 0 && N >= 0 && n_windows >= 0 && radius >= 0 && step >= 0, F2_ERR_INVALID, "negative size");
     if (n_windows == 0 || C == 0) return F2_OK;
     F2_CHECK(ctx, env && out, F2_ERR_INVALID, "null data pointer");
@@ -126,21 +125,14 @@ int f2_gather_windows(f2_ctx* ctx, const double* env, int C, int64_t N, const in
                             (int*)ctx->flags.ptr));
     if (mem_space == F2_MEM_HOST)
         F2_HIP(ctx, hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    if (normalize || mem_space == F2_MEM_HOST) {
-        int flag = 0;
-        F2_TRY(read_flag(ctx, &flag));
-        F2_CHECK(ctx, !flag, F2_ERR_NONPOSITIVE, "values must all be positive (normalizeInput)");
-    }
-    return F2_OK;
+    return normalize || mem_space == F2_MEM_HOST ? finish_positive(ctx) : F2_OK;
 }
 
 int f2_cnn_forward(f2_ctx* ctx, const f2_cnn* cnn, const float* x, int64_t n, float* scores, uint8_t* labels,
                    int mem_space) {
-    F2_CHECK(nullptr, ctx, F2_ERR_INVALID, "ctx is NULL");
-    F2_HIP(ctx, hipSetDevice(ctx->device));
-    F2_CHECK(ctx, cnn, F2_ERR_INVALID, "cnn is NULL");
-    F2_CHECK(ctx, cnn->dev == ctx->device, F2_ERR_INVALID, "cnn weights live on device %d, context on %d", cnn->dev, ctx->device);
-    F2_CHECK(ctx, mem_space == F2_MEM_HOST || mem_space == F2_MEM_DEVICE, F2_ERR_INVALID, "bad mem_space %d", mem_space);
+    F2_TRY(f2_check_ctx(ctx));
+    F2_TRY(f2_check_cnn(ctx, cnn, 0, 0));
+    F2_TRY(f2_check_mem_space(ctx, mem_space, false));
     F2_CHECK(ctx, n >= 0, F2_ERR_INVALID, "negative window count");
     if (n == 0) return F2_OK;
     F2_CHECK(ctx, x, F2_ERR_INVALID, "x is NULL");
@@ -187,110 +179,21 @@ int f2_cnn_forward(f2_ctx* ctx, const f2_cnn* cnn, const float* x, int64_t n, fl
     return F2_OK;
 }
 
-int f2_eval_utterance(f2_ctx* ctx, const f2_cnn* cnn, const void* wave, int wave_dtype, int64_t N, const double* coefs,
-                      int C, int lpf, double cutoff_hz, int fft_precision, int radius, int step, double* env_or_null,
-                      float* scores_or_null, uint8_t* labels_or_null, int64_t* n_windows_out, int mem_space) {
-    F2_CHECK(nullptr, ctx, F2_ERR_INVALID, "ctx is NULL");
-    F2_HIP(ctx, hipSetDevice(ctx->device));
-    F2_CHECK(ctx, cnn && wave && coefs, F2_ERR_INVALID, "null argument");
-    F2_CHECK(ctx, cnn->dev == ctx->device, F2_ERR_INVALID, "cnn weights live on device %d, context on %d", cnn->dev, ctx->device);
-    F2_CHECK(ctx, mem_space == F2_MEM_HOST || mem_space == F2_MEM_DEVICE, F2_ERR_INVALID, "bad mem_space %d", mem_space);
-    F2_CHECK(ctx, N >= 0 && C > 0 && radius >= 0 && step >= 0, F2_ERR_INVALID, "bad size");
-    F2_CHECK(ctx, cnn->rows == 2 * radius + 1 && cnn->channels == C, F2_ERR_INVALID,
-             "network was built for %d x %d windows, asked for %d x %d", cnn->rows, cnn->channels, 2 * radius + 1, C);
-    const int R = 2 * radius + 1;
-    const int64_t nb = N - (int64_t)R * step;   // Evaluating.py:73
-    if (n_windows_out) *n_windows_out = nb > 0 ? nb : 0;
-    if (N == 0) return F2_OK;
+}  // extern "C"
 
-    // filterbank + envelope for the one utterance, all on the device
-    const int64_t offsets[2] = {0, N};
-    const size_t env_bytes = sizeof(double) * (size_t)C * (size_t)N;
-    double* d_env;
-    if (mem_space == F2_MEM_DEVICE && env_or_null) {
-        d_env = env_or_null;
-    } else {
-        F2_TRY(f2_reserve(ctx, ctx->stage_out, env_bytes));
-        d_env = (double*)ctx->stage_out.ptr;
-    }
-    F2_TRY(f2_upload_offsets(ctx, offsets, 1));
-    F2_TRY(f2_upload_coefs(ctx, coefs, C));
-    const void* d_wave = wave;
-    if (mem_space == F2_MEM_HOST) {
-        const size_t wb = (wave_dtype == F2_WAVE_I16 ? 2 : 8) * (size_t)N;
-        F2_TRY(f2_reserve(ctx, ctx->stage_in, wb));
-        F2_HIP(ctx, hipMemcpyAsync(ctx->stage_in.ptr, wave, wb, hipMemcpyHostToDevice, ctx->stream));
-        d_wave = ctx->stage_in.ptr;
-    }
-    // same hand-off between the two kernels as f2_eval_batch / f2_filterbank_envelope_fused take for this length, so
-    // that one utterance evaluated alone and inside a batch goes through the same envelope kernel
-    f2_handoff handoff;
-    F2_TRY(f2_plan_handoff(ctx, offsets, 1, C, fft_precision, false, &handoff));
-    F2_TRY(f2_launch_filterbank(ctx, d_wave, wave_dtype, (const int64_t*)ctx->offsets.ptr, offsets,
-                                (const double*)ctx->coefs.ptr, 1, C, d_env, &handoff));
-    F2_TRY(f2_launch_envelope(ctx, d_env, (const int64_t*)ctx->offsets.ptr, offsets, 1, C, lpf, cutoff_hz, fft_precision,
-                              d_env, &handoff));
-    if (mem_space == F2_MEM_HOST && env_or_null)
-        F2_HIP(ctx, hipMemcpyAsync(env_or_null, d_env, env_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    if (nb <= 0) {
-        if (mem_space == F2_MEM_HOST) F2_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        return F2_OK;
-    }
-    // every-sample windows -> normalise -> CNN, chunk by chunk; nothing leaves HBM
-    const int64_t chunk = nb < CNN_CHUNK ? nb : CNN_CHUNK;
-    F2_TRY(f2_reserve(ctx, ctx->xbuf, sizeof(float) * (size_t)chunk * R * (size_t)C));
-    F2_TRY(f2_reserve(ctx, ctx->work, sizeof(float) * f2_cnn_workspace_floats(cnn) * (size_t)chunk));
-    float* d_scores = scores_or_null;
-    uint8_t* d_labels = labels_or_null;
-    if (mem_space == F2_MEM_HOST) {
-        F2_TRY(f2_reserve(ctx, ctx->stage_aux, (sizeof(float) * 2 + 1) * (size_t)nb + 64));
-        d_scores = (float*)ctx->stage_aux.ptr;
-        d_labels = (uint8_t*)(d_scores + 2 * nb);
-    }
-    const f2_scale_set* S1 = nullptr;
-    F2_TRY(f2_cnn_scale_set(ctx, cnn, 0, &S1));   // K3's normalised windows lie in [0, 1] by construction: no range pass
-    F2_TRY(reset_flag(ctx));
-    const int64_t reach = (int64_t)radius * step;
-    for (int64_t s = 0; s < nb; s += chunk) {
-        const int64_t m = nb - s < chunk ? nb - s : chunk;
-        F2_TRY(f2_launch_gather(ctx, d_env, C, N, nullptr, reach + s, m, radius, step, 1, (float*)ctx->xbuf.ptr,
-                                (int*)ctx->flags.ptr));
-        F2_TRY(f2_launch_cnn(ctx, cnn, S1, (const float*)ctx->xbuf.ptr, m, (float*)ctx->work.ptr,
-                             d_scores ? d_scores + 2 * s : nullptr, d_labels ? d_labels + s : nullptr));
-    }
-    if (mem_space == F2_MEM_HOST) {
-        if (scores_or_null)
-            F2_HIP(ctx, hipMemcpyAsync(scores_or_null, d_scores, sizeof(float) * 2 * (size_t)nb, hipMemcpyDeviceToHost, ctx->stream));
-        if (labels_or_null)
-            F2_HIP(ctx, hipMemcpyAsync(labels_or_null, d_labels, (size_t)nb, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    int flag = 0;
-    F2_TRY(read_flag(ctx, &flag));
-    F2_CHECK(ctx, !flag, F2_ERR_NONPOSITIVE, "values must all be positive (normalizeInput)");
-    return F2_OK;
-}
-
-int f2_eval_batch(f2_ctx* ctx, const f2_cnn* cnn, const void* wave, int wave_dtype, const int64_t* offsets,
-                  const double* coefs, int B, int C, int lpf, double cutoff_hz, int fft_precision, int radius, int step,
-                  float* scores_or_null, uint8_t* labels_or_null, int mem_space) {
-    F2_CHECK(nullptr, ctx, F2_ERR_INVALID, "ctx is NULL");
-    F2_HIP(ctx, hipSetDevice(ctx->device));
-    F2_CHECK(ctx, cnn && coefs && offsets, F2_ERR_INVALID, "null argument");
-    F2_CHECK(ctx, cnn->dev == ctx->device, F2_ERR_INVALID, "cnn weights live on device %d, context on %d", cnn->dev, ctx->device);
-    F2_CHECK(ctx, mem_space == F2_MEM_HOST || mem_space == F2_MEM_DEVICE, F2_ERR_INVALID, "bad mem_space %d", mem_space);
-    F2_CHECK(ctx, wave_dtype == F2_WAVE_I16 || wave_dtype == F2_WAVE_F64, F2_ERR_INVALID, "bad wave_dtype %d", wave_dtype);
-    F2_CHECK(ctx, fft_precision == F2_FFT_F32 || fft_precision == F2_FFT_F64, F2_ERR_INVALID, "bad fft_precision %d", fft_precision);
-    F2_CHECK(ctx, !lpf || (cutoff_hz > 0 && cutoff_hz < 8000), F2_ERR_INVALID, "cutoff %g Hz outside (0, 8000)", cutoff_hz);
-    F2_CHECK(ctx, B >= 0 && C > 0 && radius >= 0 && step >= 0, F2_ERR_INVALID, "bad size");
-    F2_CHECK(ctx, cnn->rows == 2 * radius + 1 && cnn->channels == C, F2_ERR_INVALID,
-             "network was built for %d x %d windows, asked for %d x %d", cnn->rows, cnn->channels, 2 * radius + 1, C);
-    F2_CHECK(ctx, offsets[0] == 0, F2_ERR_INVALID, "offsets[0] must be 0");
-    for (int b = 0; b < B; ++b)
-        F2_CHECK(ctx, offsets[b + 1] >= offsets[b], F2_ERR_INVALID, "offsets must not decrease (utterance %d)", b);
-    const int64_t total = B > 0 ? offsets[B] : 0;
-    if (total == 0) return F2_OK;
-    F2_CHECK(ctx, wave, F2_ERR_INVALID, "null wave");
+// `cnn eval` over a ragged batch: f2_eval_batch, and f2_eval_utterance as its B = 1 case with the envelope output
+// (env_or_null, in mem_space) and the window count (n_windows_out)
+static int eval_batch_impl(f2_ctx* ctx, const f2_cnn* cnn, const void* wave, int wave_dtype, const int64_t* offsets,
+                           const double* coefs, int B, int C, int lpf, double cutoff_hz, int fft_precision, int radius, int step,
+                           double* env_or_null, float* scores_or_null, uint8_t* labels_or_null, int64_t* n_windows_out,
+                           int mem_space) {
+    F2_TRY(f2_check_ctx(ctx));
+    F2_TRY(f2_check_dsp(ctx, wave_dtype, lpf, cutoff_hz, fft_precision));
+    F2_TRY(f2_check_batch(ctx, offsets, B, C, mem_space, true));
+    F2_CHECK(ctx, coefs && radius >= 0 && step >= 0, F2_ERR_INVALID, "coefs is NULL, or negative radius or step");
     const int R = 2 * radius + 1;
+    F2_TRY(f2_check_cnn(ctx, cnn, R, C));
+    const bool host = mem_space == F2_MEM_HOST;
     int64_t nb_total = 0, nb_max = 0;
     for (int b = 0; b < B; ++b) {
         const int64_t nb = offsets[b + 1] - offsets[b] - (int64_t)R * step;   // Evaluating.py:73
@@ -299,27 +202,27 @@ int f2_eval_batch(f2_ctx* ctx, const f2_cnn* cnn, const void* wave, int wave_dty
             nb_max = nb > nb_max ? nb : nb_max;
         }
     }
+    if (n_windows_out) *n_windows_out = nb_total;
+    const int64_t total = offsets[B];
+    if (total == 0) return F2_OK;
+    F2_CHECK(ctx, wave, F2_ERR_INVALID, "null wave");
 
-    // filterbank + envelope of the whole batch
+    // filterbank + envelope of the whole batch, always by the two kernels: one utterance evaluated alone and inside a batch
+    // goes through the same envelope kernel. The envelopes stay in stage_out (or the caller's device buffer) for the window loop.
     F2_TRY(f2_upload_offsets(ctx, offsets, B));
     F2_TRY(f2_upload_coefs(ctx, coefs, C));
-    F2_TRY(f2_reserve(ctx, ctx->stage_out, sizeof(double) * (size_t)C * (size_t)total));
-    double* d_env = (double*)ctx->stage_out.ptr;
-    const void* d_wave = wave;
-    if (mem_space == F2_MEM_HOST) {
-        const size_t wb = (wave_dtype == F2_WAVE_I16 ? 2 : 8) * (size_t)total;
-        F2_TRY(f2_reserve(ctx, ctx->stage_in, wb));
-        F2_HIP(ctx, hipMemcpyAsync(ctx->stage_in.ptr, wave, wb, hipMemcpyHostToDevice, ctx->stream));
-        d_wave = ctx->stage_in.ptr;
+    const size_t env_bytes = sizeof(double) * (size_t)C * (size_t)total;
+    double* d_env = env_or_null;
+    if (host || !env_or_null) {
+        F2_TRY(f2_reserve(ctx, ctx->stage_out, env_bytes));
+        d_env = (double*)ctx->stage_out.ptr;
     }
-    f2_handoff handoff;
-    F2_TRY(f2_plan_handoff(ctx, offsets, B, C, fft_precision, false, &handoff));
-    F2_TRY(f2_launch_filterbank(ctx, d_wave, wave_dtype, (const int64_t*)ctx->offsets.ptr, offsets,
-                                (const double*)ctx->coefs.ptr, B, C, d_env, &handoff));
-    F2_TRY(f2_launch_envelope(ctx, d_env, (const int64_t*)ctx->offsets.ptr, offsets, B, C, lpf, cutoff_hz, fft_precision,
-                              d_env, &handoff));
+    const void* d_wave;
+    F2_TRY(f2_stage_wave(ctx, wave, wave_dtype, total, mem_space, &d_wave));
+    F2_TRY(f2_envelopes_device(ctx, d_wave, wave_dtype, offsets, B, C, lpf, cutoff_hz, fft_precision, d_env, nullptr, false));
+    if (host && env_or_null) F2_HIP(ctx, hipMemcpyAsync(env_or_null, d_env, env_bytes, hipMemcpyDeviceToHost, ctx->stream));
     if (nb_total == 0) {
-        if (mem_space == F2_MEM_HOST) F2_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        if (host) F2_HIP(ctx, hipStreamSynchronize(ctx->stream));
         return F2_OK;
     }
 
@@ -336,7 +239,7 @@ int f2_eval_batch(f2_ctx* ctx, const f2_cnn* cnn, const void* wave, int wave_dty
     float* const d_a5 = d_a4 + flat * (size_t)group_cap;
     float* d_scores = scores_or_null;
     uint8_t* d_labels = labels_or_null;
-    if (mem_space == F2_MEM_HOST) {
+    if (host) {
         F2_TRY(f2_reserve(ctx, ctx->stage_aux, (sizeof(float) * 2 + 1) * (size_t)nb_total + 64));
         d_scores = (float*)ctx->stage_aux.ptr;
         d_labels = (uint8_t*)(d_scores + 2 * nb_total);
@@ -345,7 +248,7 @@ int f2_eval_batch(f2_ctx* ctx, const f2_cnn* cnn, const void* wave, int wave_dty
     F2_TRY(f2_cnn_scale_set(ctx, cnn, 0, &S1));   // K3's normalised windows lie in [0, 1] by construction: no range pass
     F2_TRY(reset_flag(ctx));
     const int64_t reach = (int64_t)radius * step;
-    int64_t done = 0, g0 = 0, gn = 0;      // windows finished before this utterance; first window and size of the open dense group
+    int64_t g0 = 0, gn = 0;      // first window and size of the open dense group
     auto flush = [&]() -> int {
         if (gn > 0)
             F2_TRY(f2_launch_cnn_dense(ctx, cnn, S1, d_a4, gn, d_a5, d_scores ? d_scores + 2 * g0 : nullptr, d_labels ? d_labels + g0 : nullptr));
@@ -356,7 +259,6 @@ int f2_eval_batch(f2_ctx* ctx, const f2_cnn* cnn, const void* wave, int wave_dty
     for (int b = 0; b < B; ++b) {
         const int64_t N = offsets[b + 1] - offsets[b];
         const int64_t nb = N - (int64_t)R * step;
-        if (nb <= 0) continue;
         const double* env_b = d_env + (size_t)C * (size_t)offsets[b];
         for (int64_t s = 0; s < nb; s += chunk) {
             const int64_t m = nb - s < chunk ? nb - s : chunk;
@@ -366,38 +268,45 @@ int f2_eval_batch(f2_ctx* ctx, const f2_cnn* cnn, const void* wave, int wave_dty
             F2_TRY(f2_launch_cnn_convs(ctx, cnn, S1, (const float*)ctx->xbuf.ptr, m, (float*)ctx->work.ptr, d_a4 + flat * (size_t)gn));
             gn += m;
         }
-        done += nb;
     }
     F2_TRY(flush());
-    if (mem_space == F2_MEM_HOST) {
+    if (host) {
         if (scores_or_null)
             F2_HIP(ctx, hipMemcpyAsync(scores_or_null, d_scores, sizeof(float) * 2 * (size_t)nb_total, hipMemcpyDeviceToHost, ctx->stream));
         if (labels_or_null)
             F2_HIP(ctx, hipMemcpyAsync(labels_or_null, d_labels, (size_t)nb_total, hipMemcpyDeviceToHost, ctx->stream));
     }
-    int flag = 0;
-    F2_TRY(read_flag(ctx, &flag));
-    F2_CHECK(ctx, !flag, F2_ERR_NONPOSITIVE, "values must all be positive (normalizeInput)");
-    return F2_OK;
+    return finish_positive(ctx);
+}
+
+extern "C" {
+
+int f2_eval_utterance(f2_ctx* ctx, const f2_cnn* cnn, const void* wave, int wave_dtype, int64_t N, const double* coefs,
+                      int C, int lpf, double cutoff_hz, int fft_precision, int radius, int step, double* env_or_null,
+                      float* scores_or_null, uint8_t* labels_or_null, int64_t* n_windows_out, int mem_space) {
+    if (ctx && !wave) return f2_fail(ctx, F2_ERR_INVALID, "null wave");   // (also for N == 0, unlike f2_eval_batch)
+    const int64_t offsets[2] = {0, N};
+    return eval_batch_impl(ctx, cnn, wave, wave_dtype, offsets, coefs, 1, C, lpf, cutoff_hz, fft_precision, radius, step,
+                           env_or_null, scores_or_null, labels_or_null, n_windows_out, mem_space);
+}
+
+int f2_eval_batch(f2_ctx* ctx, const f2_cnn* cnn, const void* wave, int wave_dtype, const int64_t* offsets,
+                  const double* coefs, int B, int C, int lpf, double cutoff_hz, int fft_precision, int radius, int step,
+                  float* scores_or_null, uint8_t* labels_or_null, int mem_space) {
+    return eval_batch_impl(ctx, cnn, wave, wave_dtype, offsets, coefs, B, C, lpf, cutoff_hz, fft_precision, radius, step, nullptr,
+                           scores_or_null, labels_or_null, nullptr, mem_space);
 }
 
 int f2_input_batch(f2_ctx* ctx, const void* wave, int wave_dtype, const int64_t* offsets, const double* coefs, int B, int C,
                    int lpf, double cutoff_hz, int fft_precision, const int64_t* center_offsets, const int64_t* centers,
                    int radius, int step, int normalize, float* windows, int mem_space) {
-    F2_CHECK(nullptr, ctx, F2_ERR_INVALID, "ctx is NULL");
-    F2_HIP(ctx, hipSetDevice(ctx->device));
-    F2_CHECK(ctx, mem_space == F2_MEM_HOST || mem_space == F2_MEM_DEVICE, F2_ERR_INVALID, "bad mem_space %d", mem_space);
-    F2_CHECK(ctx, wave_dtype == F2_WAVE_I16 || wave_dtype == F2_WAVE_F64, F2_ERR_INVALID, "bad wave_dtype %d", wave_dtype);
-    F2_CHECK(ctx, fft_precision == F2_FFT_F32 || fft_precision == F2_FFT_F64, F2_ERR_INVALID, "bad fft_precision %d", fft_precision);
-    F2_CHECK(ctx, !lpf || (cutoff_hz > 0 && cutoff_hz < 8000), F2_ERR_INVALID, "cutoff %g Hz outside (0, 8000)", cutoff_hz);
+    F2_TRY(f2_check_ctx(ctx));
+    F2_TRY(f2_check_mem_space(ctx, mem_space, false));
+    F2_TRY(f2_check_dsp(ctx, wave_dtype, lpf, cutoff_hz, fft_precision));
     F2_CHECK(ctx, B >= 0 && C > 0 && radius >= 0 && step >= 0, F2_ERR_INVALID, "bad size");
-    if (B == 0) return F2_OK;
-    F2_CHECK(ctx, offsets && center_offsets, F2_ERR_INVALID, "null argument");
-    F2_CHECK(ctx, offsets[0] == 0 && center_offsets[0] == 0, F2_ERR_INVALID, "offsets[0] and center_offsets[0] must be 0");
-    for (int b = 0; b < B; ++b) {
-        F2_CHECK(ctx, offsets[b + 1] >= offsets[b], F2_ERR_INVALID, "offsets must not decrease (utterance %d)", b);
-        F2_CHECK(ctx, center_offsets[b + 1] >= center_offsets[b], F2_ERR_INVALID, "center_offsets must not decrease (utterance %d)", b);
-    }
+    if (B == 0) return F2_OK;      // (before the offsets are looked at: they may be NULL then)
+    F2_TRY(f2_check_offsets(ctx, offsets, B, "offsets"));
+    F2_TRY(f2_check_offsets(ctx, center_offsets, B, "center_offsets"));
     const int64_t n_windows = center_offsets[B];
     if (n_windows == 0) return F2_OK;
     F2_CHECK(ctx, wave && coefs && centers && windows, F2_ERR_INVALID, "null data pointer");
@@ -421,14 +330,9 @@ int f2_input_batch(f2_ctx* ctx, const void* wave, int wave_dtype, const int64_t*
     F2_TRY(f2_upload_coefs(ctx, coefs, C));
     F2_TRY(f2_reserve(ctx, ctx->stage_out, sizeof(double) * (size_t)C * (size_t)total));
     double* d_env = (double*)ctx->stage_out.ptr;
-    const void* d_wave = wave;
-    if (mem_space == F2_MEM_HOST) {
-        const size_t wb = (wave_dtype == F2_WAVE_I16 ? 2 : 8) * (size_t)total;
-        F2_TRY(f2_reserve(ctx, ctx->stage_in, wb));
-        F2_HIP(ctx, hipMemcpyAsync(ctx->stage_in.ptr, wave, wb, hipMemcpyHostToDevice, ctx->stream));
-        d_wave = ctx->stage_in.ptr;
-    }
-    F2_TRY(f2_envelopes_device(ctx, d_wave, wave_dtype, offsets, B, C, lpf, cutoff_hz, fft_precision, d_env, nullptr));
+    const void* d_wave;
+    F2_TRY(f2_stage_wave(ctx, wave, wave_dtype, total, mem_space, &d_wave));
+    F2_TRY(f2_envelopes_device(ctx, d_wave, wave_dtype, offsets, B, C, lpf, cutoff_hz, fft_precision, d_env, nullptr, true));
 
     // all windows of the batch in one gather launch: centres and the utterance of every window in one upload
     const size_t cbytes = sizeof(int64_t) * (size_t)n_windows, ubytes = sizeof(int) * (size_t)n_windows;
@@ -446,12 +350,7 @@ int f2_input_batch(f2_ctx* ctx, const void* wave, int wave_dtype, const int64_t*
                                    (const int*)((char*)ctx->work2.ptr + cbytes), n_windows, radius, step, normalize, d_out,
                                    (int*)ctx->flags.ptr));
     if (mem_space == F2_MEM_HOST) F2_HIP(ctx, hipMemcpyAsync(windows, d_out, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    if (normalize || mem_space == F2_MEM_HOST) {
-        int flag = 0;
-        F2_TRY(read_flag(ctx, &flag));
-        F2_CHECK(ctx, !flag, F2_ERR_NONPOSITIVE, "values must all be positive (normalizeInput)");
-    }
-    return F2_OK;
+    return normalize || mem_space == F2_MEM_HOST ? finish_positive(ctx) : F2_OK;
 }
 
 }  // extern "C"

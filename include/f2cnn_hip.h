@@ -247,8 +247,10 @@ int f2_cnn_forward(f2_ctx* ctx, const f2_cnn* cnn, const float* x, int64_t n, fl
 /* ---- `cnn eval` device pipeline -----------------------------------------------------------------
  * scripts/CNN/Evaluating.py:42-87 for one utterance with every intermediate kept in HBM:
  * filterbank -> envelope -> every-sample window gather + normalise -> CNN -> labels.
- * n_windows_out receives N - (2*radius+1)*step (Evaluating.py:73). env_or_null (C,N) float64,
- * scores_or_null (n,2), labels_or_null (n) are optional outputs in `mem_space`.
+ * f2_eval_utterance is f2_eval_batch (below) with the one utterance offsets = {0, N}: the same kernels in the same
+ * order, scores and labels bit-identical, and the same argument errors (see there). On top of it, n_windows_out
+ * receives max(0, N - (2*radius+1)*step) (Evaluating.py:73), env_or_null (C,N) float64 the envelopes (in `mem_space`;
+ * a device buffer serves as the call's envelope buffer itself), and a NULL wave is an error even for N = 0.
  */
 int f2_eval_utterance(f2_ctx* ctx, const f2_cnn* cnn, const void* wave, int wave_dtype, int64_t N,
                       const double* coefs, int C, int lpf, double cutoff_hz, int fft_precision,
@@ -260,6 +262,10 @@ int f2_eval_utterance(f2_ctx* ctx, const f2_cnn* cnn, const void* wave, int wave
  * fills two wavefronts of the filterbank kernel - then windows + CNN utterance by utterance. Utterance b has
  * nb_b = max(0, n_b - (2*radius+1)*step) windows; scores / labels are the concatenation over b in batch order
  * (sum nb_b rows), both optional, in `mem_space`.
+ * F2_ERR_INVALID (nothing is launched): NULL ctx, cnn, coefs or offsets; mem_space other than F2_MEM_HOST / F2_MEM_DEVICE;
+ * wave_dtype or fft_precision not one of the enumerators; lpf with cutoff_hz outside (0, 8000); B < 0, C <= 0, radius < 0,
+ * step < 0; offsets[0] != 0 or decreasing offsets; a network on another device or built for other than (2*radius+1) x C
+ * windows; a NULL wave with offsets[B] > 0. F2_ERR_NONPOSITIVE: a window holds a value <= 0 (normalizeInput).
  */
 int f2_eval_batch(f2_ctx* ctx, const f2_cnn* cnn, const void* wave, int wave_dtype, const int64_t* offsets,
                   const double* coefs, int B, int C, int lpf, double cutoff_hz, int fft_precision, int radius,

@@ -3,6 +3,9 @@
 import os, sys, time
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+if os.environ.get("F2CNN_PROBE_LIB"):   # another build of the library (tools/build_variant.sh, tools/libf2cnn_hip_old.so)
+    from f2cnn_amd import build
+    build.LIB_PATH = os.path.abspath(os.environ["F2CNN_PROBE_LIB"])
 from f2cnn_amd import _lib
 from f2cnn_amd.gammatone import filters
 import bench
