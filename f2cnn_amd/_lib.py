@@ -62,6 +62,7 @@ SIGNATURES = {
     "f2_cnn_forward": (_i, [_vp, _vp, _vp, _i64, _vp, _vp, _i]),
     "f2_eval_utterance": (_i, [_vp, _vp, _vp, _i, _i64, _vp, _i, _i, _d, _i, _i, _i, _vp, _vp, _vp, _P(_i64), _i]),
     "f2_eval_batch": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _d, _i, _i, _i, _vp, _vp, _i]),
+    "f2_eval_batch_strided": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _d, _i, _i, _i, _i, _vp, _vp, _vp, _i]),
 }
 
 _lib = None
@@ -351,6 +352,30 @@ class Context:
         self.check(self.lib.f2_eval_batch(self.handle, handle, _ptr(wave), wave_dtype, _ptr(offsets), _ptr(coefs), int(B),
                                           Cn, int(bool(lpf)), float(cutoff), precision, radius, step, _ptr(scores),
                                           _ptr(labels), mem_space))
+
+    def eval_batch_strided(self, handle, wave, wave_dtype, offsets, coefs, B, Cn, lpf, cutoff, precision, radius, step, hop,
+                           scores, labels, mem_space):
+        """f2_eval_batch with a decision every `hop` samples (see f2_eval_batch_strided): row window_offsets[b] + j is
+        every-sample window j * hop of utterance b. Returns window_offsets (B + 1, int64)."""
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        window_offsets = np.zeros(int(B) + 1, np.int64)
+        self.check(self.lib.f2_eval_batch_strided(self.handle, handle, _ptr(wave), wave_dtype, _ptr(offsets), _ptr(coefs),
+                                                  int(B), Cn, int(bool(lpf)), float(cutoff), precision, radius, step, int(hop),
+                                                  _ptr(scores), _ptr(labels), _ptr(window_offsets), mem_space))
+        return window_offsets
+
+
+def strided_window_count(n, radius, step, hop):
+    """Windows f2_eval_batch_strided evaluates in an utterance of n samples: ceil(max(0, n - (2 radius + 1) step) / hop)."""
+    if hop < 1:
+        raise ValueError("hop must be at least 1 sample")
+    return -(-max(int(n) - (2 * radius + 1) * step, 0) // int(hop))
+
+
+def strided_timepoints(n, radius, step, hop):
+    """Centre sample of each of those windows: radius step + j hop (int64)."""
+    return radius * step + int(hop) * np.arange(strided_window_count(n, radius, step, hop), dtype=np.int64)
+
 
 _default_ctx = {}
 _extra_ctx = {}

@@ -12,9 +12,10 @@ package implements:
     (filter / envelope / features also take --skip-existing to resume and --metrics FILE for a JSON summary; a file that
      cannot be read is reported and skipped, the exit status is then 2)
     python -m f2cnn_amd cnn train [--input/-i NPY] [--label/-l CSV]   (PyTorch-ROCm autograd; weights -> last_trained_model)
-    python -m f2cnn_amd cnn eval --file/-f WAV [--lpf HZ] [--model/-m NPZ]
-    python -m f2cnn_amd cnn evalnoise --file/-f WAV --noise/-n SNRdB [--lpf HZ] [--model/-m NPZ]
-    python -m f2cnn_amd cnn evalrand [--count/-c N] [--lpf HZ] [--model/-m NPZ]
+    python -m f2cnn_amd cnn eval --file/-f WAV [--lpf HZ] [--model/-m NPZ] [--hop N|frame]
+    python -m f2cnn_amd cnn evalnoise --file/-f WAV --noise/-n SNRdB [--lpf HZ] [--model/-m NPZ] [--hop N|frame]
+    python -m f2cnn_amd cnn evalrand [--count/-c N] [--lpf HZ] [--model/-m NPZ] [--hop N|frame]
+    (--hop: a decision every N samples instead of every sample, `frame` = one per STEP of configF2CNN.conf; not in the reference)
     python -m f2cnn_amd --configure            (writes configF2CNN.conf with the reference's defaults)
 
 organize / plot need the licensed TIMIT+VTR corpora or matplotlib and stay with the reference.
@@ -23,6 +24,19 @@ import argparse
 
 PREPARE = ("filter", "envelope", "label", "input", "features")
 CNN = ("train", "eval", "evalnoise", "evalrand")
+
+
+def hop_argument(text):
+    """--hop: a positive number of samples, or 'frame' (resolved to STEP once the configuration is read)"""
+    if text == 'frame':
+        return text
+    try:
+        hop = int(text)
+    except ValueError:
+        hop = 0
+    if hop < 1:
+        raise argparse.ArgumentTypeError("--hop takes a positive number of samples or 'frame', not {!r}".format(text))
+    return hop
 
 
 def build_parser():
@@ -53,6 +67,9 @@ def build_parser():
     c.add_argument('--lpf', action='store', type=int, dest='CUTOFF', help="low pass filter the envelopes")
     c.add_argument('--count', '-c', action='store', type=int, help="number of files to evaluate (evalrand)")
     c.add_argument('--noise', '-n', action='store', type=float, dest='SNRdB', help="SNR in dB (evalnoise)")
+    c.add_argument('--hop', action='store', type=hop_argument, dest='hop',
+                   help="eval / evalnoise / evalrand: evaluate every HOP-th sample ('frame': every STEP samples) instead of "
+                        "every sample")
     return parser
 
 
@@ -111,6 +128,11 @@ def main(argv=None):
             kwargs['CUTOFF'] = args.CUTOFF
         if args.model is not None:
             kwargs['model'] = args.model
+        if args.hop is not None:
+            kwargs['hop'] = args.hop
+            if args.hop == 'frame':
+                from .config import F2Config
+                kwargs['hop'] = F2Config().step
         if args.cnn_command == 'evalrand':                     # needs no --file (unreachable in the reference CLI)
             if args.count is not None:
                 kwargs['count'] = args.count

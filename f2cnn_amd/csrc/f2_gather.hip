@@ -237,6 +237,156 @@ __global__ __launch_bounds__(256) void k_eval_windows(const double* __restrict__
     }
 }
 
+// ---- strided windows of a ragged batch (`cnn eval --hop`, f2_eval_batch_strided), hop | step ----
+// Window j of an utterance has its centre at radius * step + j * hop, so its tap k reads sample hop * (j + k * step / hop): the
+// strided windows are the every-sample windows, with step' = step / hop, of the decimated envelope env'[c][d] = env[c][d * hop].
+// A chunk of windows is cut into segments (consecutive windows of one utterance); segment s owns the columns
+// [col_s, col_s + count_s + 2 * radius * step') of the compact L / pmin / pmax, which hold env' from its first window's first tap
+// on. The three kernels below are k_log_columns, k_window_stats and k_eval_windows with the places they read and write taken
+// from host-built tables - one entry per 64 columns, one per block of up to WB windows of one segment - so that every
+// utterance of the chunk is served by the same three launches. Same float64 operations in the same order: a window's row is
+// bit-identical to the every-sample kernels' and to k_gather_windows' (tests/test_gpu_eval_strided.py).
+constexpr int CBW = 64;     // columns per table entry of k_log_columns_strided: one wavefront
+struct colblock {
+    int64_t src;            // element offset of env_b[0][first sample of the entry] in the batch's envelope buffer
+    int64_t n;              // samples per channel row of that utterance
+    int64_t col;            // first column in L
+    int64_t ncols;          // <= CBW
+};
+struct winblock {
+    int64_t row;            // position of the block's first window in the chunk (its output row and stats slot)
+    int64_t col;            // column of that window's first tap
+    int64_t nw;             // <= WB
+    int64_t pad;
+};
+
+__global__ __launch_bounds__(256) void k_log_columns_strided(const double* __restrict__ env, int C, int hop, int64_t span,
+                                                             const colblock* __restrict__ tab, int nblocks,
+                                                             double* __restrict__ L, double* __restrict__ pmin,
+                                                             double* __restrict__ pmax) {
+    const int blk = blockIdx.x * (256 / CBW) + (threadIdx.x / CBW), lane = threadIdx.x % CBW;
+    if (blk >= nblocks) return;
+    const colblock cb = tab[blk];
+    if (lane >= cb.ncols) return;
+    const size_t j = (size_t)(cb.col + lane), N = (size_t)cb.n;
+    // (neighbouring lanes are hop * 8 bytes apart: from hop = 16 on every load is a 128-byte line of its own)
+    const double* src = env + (size_t)cb.src + (size_t)lane * (size_t)hop;
+    const int c0 = blockIdx.y * LCH, c1 = min(C, c0 + LCH);
+    double mn = INFINITY, mx = -INFINITY;
+    if (c1 - c0 == LCH) {
+        double v[LCH];
+#pragma unroll
+        for (int u = 0; u < LCH; ++u) v[u] = src[(size_t)(c0 + u) * N];
+#pragma unroll
+        for (int u = 0; u < LCH; ++u) {
+            L[(size_t)(c0 + u) * (size_t)span + j] = log(v[u]);
+            mn = fmin(mn, v[u]);
+            mx = fmax(mx, v[u]);
+        }
+    } else {
+        for (int c = c0; c < c1; ++c) {
+            const double v = src[(size_t)c * N];
+            L[(size_t)c * (size_t)span + j] = log(v);
+            mn = fmin(mn, v);
+            mx = fmax(mx, v);
+        }
+    }
+    pmin[(size_t)blockIdx.y * (size_t)span + j] = mn;
+    pmax[(size_t)blockIdx.y * (size_t)span + j] = mx;
+}
+
+// one workgroup per table entry; `step` is step / hop
+__global__ __launch_bounds__(256) void k_window_stats_strided(const double* __restrict__ pmin, const double* __restrict__ pmax,
+                                                              int groups, int64_t span, const winblock* __restrict__ tab,
+                                                              int radius, int step, double* __restrict__ stats,
+                                                              int* __restrict__ flag) {
+    const winblock wb = tab[blockIdx.x];
+    const int w = threadIdx.x & 31, p = threadIdx.x >> 5;
+    const bool live = w < wb.nw;
+    const int R = 2 * radius + 1, pairs = R * groups;
+    double mn = INFINITY, mx = -INFINITY;
+    if (live) {
+#pragma unroll 4
+        for (int pq = p; pq < pairs; pq += 8) {
+            const int k2 = pq / groups, g = pq - k2 * groups;
+            const size_t at = (size_t)g * (size_t)span + (size_t)(wb.col + w + (int64_t)step * k2);
+            mn = fmin(mn, pmin[at]);
+            mx = fmax(mx, pmax[at]);
+        }
+    }
+    __shared__ double smn[8][32], smx[8][32];
+    smn[p][w] = mn;
+    smx[p][w] = mx;
+    __syncthreads();
+    if (p != 0 || !live) return;
+#pragma unroll
+    for (int q = 1; q < 8; ++q) {
+        mn = fmin(mn, smn[q][w]);
+        mx = fmax(mx, smx[q][w]);
+    }
+    double zero = 0.0;
+    if (!(mn > 0.0)) {   // also catches NaN; the reference raises ValueError
+        atomicOr(flag, 1);
+        zero = 1.0;
+    }
+    if (mn == mx) zero = 1.0;
+    const double lmn = log(mn), range = log(mx) - lmn;
+    const int64_t e = wb.row + w;
+    stats[4 * e] = lmn;
+    stats[4 * e + 1] = range;
+    stats[4 * e + 2] = zero;
+    stats[4 * e + 3] = 1.0 / range;
+}
+
+// grid (table entries, taps); `step` is step / hop
+__global__ __launch_bounds__(256) void k_eval_windows_strided(const double* __restrict__ L, const double* __restrict__ stats, int C,
+                                                              int64_t span, const winblock* __restrict__ tab, int radius, int step,
+                                                              float* __restrict__ out) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    float* tile = reinterpret_cast<float*>(smem_raw);            // [WB][C + 1]
+    const winblock wb = tab[blockIdx.x];
+    const int tid = threadIdx.x;
+    const int64_t e0 = wb.row;
+    const int k = blockIdx.y;
+    const int nw = (int)wb.nw;
+    const int R = 2 * radius + 1, CP = C + 1;
+    const int w = tid & (WB - 1), cc = tid / WB;                 // 8 channel lanes x 32 windows
+    const bool live = w < nw;
+    const double* st = stats + 4 * (e0 + (live ? w : 0));
+    const double lmn = st[0], range = st[1], rinv = st[3];
+    const bool zero = st[2] != 0.0;
+    const double* Lk = L + (wb.col + (live ? w : 0) + (int64_t)step * k);
+    // (the quotient as in k_eval_windows: q0 = RN(a rinv), one exact residual, one correction)
+    constexpr int CL = 256 / WB, UN = 8;
+    for (int c0 = cc; c0 < C; c0 += CL * UN) {
+        double v[UN];
+#pragma unroll
+        for (int u = 0; u < UN; ++u) v[u] = (live && c0 + CL * u < C) ? Lk[(size_t)(c0 + CL * u) * (size_t)span] : lmn;
+#pragma unroll
+        for (int u = 0; u < UN; ++u) {
+            const double a = v[u] - lmn, q0 = a * rinv;
+            const float o = (live && !zero) ? (float)fma(fma(-q0, range, a), rinv, q0) : 0.f;
+            if (c0 + CL * u < C) tile[w * CP + c0 + CL * u] = o;
+        }
+    }
+    __syncthreads();
+    float* orow = out + ((size_t)e0 * R + k) * (size_t)C;
+    if ((C & 3) == 0) {
+        // 16 bytes per lane: a window's row of C floats is C / 4 consecutive lanes
+        const int C4 = C >> 2;
+        for (int idx = tid; idx < nw * C4; idx += 256) {
+            const int ww = idx / C4, c = (idx - ww * C4) * 4;
+            const float* t = tile + ww * CP + c;
+            *reinterpret_cast<float4*>(orow + (size_t)ww * R * C + c) = make_float4(t[0], t[1], t[2], t[3]);
+        }
+    } else {
+        for (int idx = tid; idx < nw * C; idx += 256) {
+            const int ww = idx / C, c = idx - ww * C;
+            orow[(size_t)ww * R * C + c] = tile[ww * CP + c];
+        }
+    }
+}
+
 }  // namespace
 
 static int launch_eval_windows(f2_ctx* ctx, const double* d_env, int C, int64_t N, int64_t first_center, int64_t n_windows,
@@ -299,6 +449,90 @@ int f2_launch_gather_ragged(f2_ctx* ctx, const double* d_env, int C, const int64
     F2_TRY(f2_prof_begin(ctx, F2_K_GATHER));
     hipLaunchKernelGGL(k_gather_windows<true>, dim3((unsigned)n_windows), dim3(GT), lds, ctx->stream, d_env, C, (int64_t)0,
                        d_centers, (int64_t)0, radius, step, normalize, d_out, d_flag, d_offsets, d_win_utt);
+    F2_HIP(ctx, hipGetLastError());
+    F2_TRY(f2_prof_end(ctx, F2_K_GATHER));
+    return F2_OK;
+}
+
+bool f2_gather_strided_blocked(const f2_ctx* ctx, int C, int step, int hop) {
+    return ctx->opt_gather_blocked && hop >= 1 && step % hop == 0 && sizeof(float) * WB * ((size_t)C + 1) <= 64 * 1024;
+}
+
+int64_t f2_gather_strided_columns(int64_t count, int radius, int step, int hop) {
+    return count + 2 * (int64_t)radius * (step / hop);
+}
+
+int f2_launch_gather_strided(f2_ctx* ctx, const double* d_env, int C, const int64_t* d_offsets, const int64_t* h_offsets,
+                             const f2_win_seg* segs, int nseg, int radius, int step, int hop, float* d_out, int* d_flag) {
+    int64_t n_windows = 0;
+    for (int s = 0; s < nseg; ++s) n_windows += segs[s].count;
+    if (n_windows <= 0) return F2_OK;
+    const int R = 2 * radius + 1;
+    F2_CHECK(ctx, n_windows < (int64_t(1) << 31), F2_ERR_UNSUPPORTED, "too many windows (%lld)", (long long)n_windows);
+    const int64_t reach = (int64_t)radius * step;
+
+    if (!f2_gather_strided_blocked(ctx, C, step, hop)) {
+        // one workgroup per window at the centres radius * step + j * hop (k_gather_windows<true>)
+        const size_t cbytes = sizeof(int64_t) * (size_t)n_windows, ubytes = sizeof(int) * (size_t)n_windows;
+        std::vector<int64_t> centers((size_t)n_windows);
+        std::vector<int> win_utt((size_t)n_windows);
+        size_t e = 0;
+        for (int s = 0; s < nseg; ++s)
+            for (int64_t j = 0; j < segs[s].count; ++j, ++e) {
+                centers[e] = reach + (segs[s].first + j) * hop;
+                win_utt[e] = segs[s].utt;
+            }
+        F2_TRY(f2_reserve(ctx, ctx->work2, cbytes + ubytes));
+        F2_TRY(f2_upload_async(ctx, ctx->work2.ptr, centers.data(), cbytes));
+        F2_TRY(f2_upload_async(ctx, (char*)ctx->work2.ptr + cbytes, win_utt.data(), ubytes));
+        return f2_launch_gather_ragged(ctx, d_env, C, d_offsets, (const int64_t*)ctx->work2.ptr,
+                                       (const int*)((char*)ctx->work2.ptr + cbytes), n_windows, radius, step, 1, d_out, d_flag);
+    }
+
+    // the tables: per segment its 64-column entries and its blocks of WB windows
+    static_assert(sizeof(colblock) == 32 && sizeof(winblock) == 32, "table entries are four 8-byte words");
+    const int stepd = step / hop;
+    std::vector<colblock> cols;
+    std::vector<winblock> wins;
+    int64_t span = 0, row = 0;
+    for (int s = 0; s < nseg; ++s) {
+        const f2_win_seg& g = segs[s];
+        if (g.count <= 0) continue;
+        const int64_t o0 = h_offsets[g.utt], N = h_offsets[g.utt + 1] - o0;
+        const int64_t ncol = f2_gather_strided_columns(g.count, radius, step, hop);
+        // the segment's last column is sample (first + count - 1) * hop + 2 * reach of its utterance
+        F2_CHECK(ctx, g.first >= 0 && (g.first + g.count - 1) * hop + 2 * reach < N, F2_ERR_INVALID,
+                 "utterance %d: windows %lld .. +%lld at hop %d reach outside its %lld-sample envelope", g.utt, (long long)g.first,
+                 (long long)g.count, hop, (long long)N);
+        for (int64_t c = 0; c < ncol; c += CBW)
+            cols.push_back({(int64_t)C * o0 + (g.first + c) * hop, N, span + c, ncol - c < CBW ? ncol - c : CBW});
+        for (int64_t w = 0; w < g.count; w += WB) wins.push_back({row + w, span + w, g.count - w < WB ? g.count - w : WB, 0});
+        span += ncol;
+        row += g.count;
+    }
+    const int groups = (C + LCH - 1) / LCH;
+    F2_TRY(f2_reserve(ctx, ctx->gather_log, sizeof(double) * ((size_t)span * ((size_t)C + 2 * (size_t)groups) + 4 * (size_t)n_windows)));
+    double* L = (double*)ctx->gather_log.ptr;
+    double* pmin = L + (size_t)span * (size_t)C;
+    double* pmax = pmin + (size_t)span * (size_t)groups;
+    double* stats = pmax + (size_t)span * (size_t)groups;
+    const size_t cbytes = sizeof(colblock) * cols.size(), wbytes = sizeof(winblock) * wins.size();
+    F2_TRY(f2_reserve(ctx, ctx->work2, cbytes + wbytes));
+    F2_TRY(f2_upload_async(ctx, ctx->work2.ptr, cols.data(), cbytes));
+    F2_TRY(f2_upload_async(ctx, (char*)ctx->work2.ptr + cbytes, wins.data(), wbytes));
+    const colblock* d_cols = (const colblock*)ctx->work2.ptr;
+    const winblock* d_wins = (const winblock*)((char*)ctx->work2.ptr + cbytes);
+    const int ncb = (int)cols.size();
+    F2_TRY(f2_prof_begin(ctx, F2_K_GATHER));
+    hipLaunchKernelGGL(k_log_columns_strided, dim3((unsigned)((ncb + 256 / CBW - 1) / (256 / CBW)), (unsigned)groups), dim3(256), 0,
+                       ctx->stream, d_env, C, hop, span, d_cols, ncb, L, pmin, pmax);
+    F2_HIP(ctx, hipGetLastError());
+    hipLaunchKernelGGL(k_window_stats_strided, dim3((unsigned)wins.size()), dim3(256), 0, ctx->stream, (const double*)pmin,
+                       (const double*)pmax, groups, span, d_wins, radius, stepd, stats, d_flag);
+    F2_HIP(ctx, hipGetLastError());
+    const size_t lds = sizeof(float) * WB * ((size_t)C + 1);
+    hipLaunchKernelGGL(k_eval_windows_strided, dim3((unsigned)wins.size(), (unsigned)R), dim3(256), lds, ctx->stream,
+                       (const double*)L, (const double*)stats, C, span, d_wins, radius, stepd, d_out);
     F2_HIP(ctx, hipGetLastError());
     F2_TRY(f2_prof_end(ctx, F2_K_GATHER));
     return F2_OK;

@@ -347,6 +347,19 @@ int f2_launch_gather(f2_ctx* ctx, const double* d_env, int C, int64_t N, const i
 int f2_launch_gather_ragged(f2_ctx* ctx, const double* d_env, int C, const int64_t* d_offsets, const int64_t* d_centers,
                             const int* d_win_utt, int64_t n_windows, int radius, int step, int normalize, float* d_out,
                             int* d_flag);
+// Strided, normalised windows of a ragged batch (f2_eval_batch_strided): segment s is the windows first .. first + count - 1
+// of utterance utt, window j centred at radius * step + j * hop of its utterance; the segments' windows are written to d_out
+// one after the other. hop | step (and option "gather_blocked"): three launches for all segments, on the decimated envelope
+// (f2_gather.hip); any other hop: f2_launch_gather_ragged at those centres. Uses ctx->work2 and ctx->gather_log; h_offsets host.
+struct f2_win_seg {
+    int utt;
+    int64_t first, count;
+};
+int f2_launch_gather_strided(f2_ctx* ctx, const double* d_env, int C, const int64_t* d_offsets, const int64_t* h_offsets,
+                             const f2_win_seg* segs, int nseg, int radius, int step, int hop, float* d_out, int* d_flag);
+bool f2_gather_strided_blocked(const f2_ctx* ctx, int C, int step, int hop);    // the three-launch route serves this call
+// ... and the columns of its scratch a segment of `count` windows takes (float64 values: C + 2 ceil(C / 16) per column)
+int64_t f2_gather_strided_columns(int64_t count, int radius, int step, int hop);
 // weight-stationary split-fp16 convolutions (f2_cnn_ws.hip): windows whose pooled conv2 output has four rows
 bool f2_cnn_ws_supported(int rows, int channels);
 int f2_launch_dense1_ws(f2_ctx* ctx, const f2_cnn* cnn, const f2_scale_set* S, const float* a4, int64_t n, int K, float* a5);

@@ -181,102 +181,217 @@ int f2_cnn_forward(f2_ctx* ctx, const f2_cnn* cnn, const float* x, int64_t n, fl
 
 }  // extern "C"
 
-// `cnn eval` over a ragged batch: f2_eval_batch, and f2_eval_utterance as its B = 1 case with the envelope output
-// (env_or_null, in mem_space) and the window count (n_windows_out)
-static int eval_batch_impl(f2_ctx* ctx, const f2_cnn* cnn, const void* wave, int wave_dtype, const int64_t* offsets,
-                           const double* coefs, int B, int C, int lpf, double cutoff_hz, int fft_precision, int radius, int step,
-                           double* env_or_null, float* scores_or_null, uint8_t* labels_or_null, int64_t* n_windows_out,
-                           int mem_space) {
+// ---- `cnn eval` over a ragged batch: what f2_eval_batch / f2_eval_utterance (every sample) and f2_eval_batch_strided share ----
+namespace {
+
+struct eval_call {
+    bool host = false;
+    int R = 0;
+    int64_t total = 0;           // samples of the batch
+    double* d_env = nullptr;     // envelopes of the batch, (C, n_b) blocks at C * offsets[b]
+    // CNN side (eval_cnn_begin)
+    int64_t n_total = 0, group_cap = 0;
+    size_t flat = 0;
+    float *d_a4 = nullptr, *d_a5 = nullptr, *d_scores = nullptr;
+    uint8_t* d_labels = nullptr;
+    const f2_scale_set* S1 = nullptr;
+    int64_t g0 = 0, gn = 0;      // first window and size of the open dense group
+};
+
+// the argument errors of the eval calls (include/f2cnn_hip.h: f2_eval_batch); nothing is launched before they pass
+int eval_check(f2_ctx* ctx, const f2_cnn* cnn, int wave_dtype, const int64_t* offsets, const double* coefs, int B, int C, int lpf,
+               double cutoff_hz, int fft_precision, int radius, int step, int mem_space, eval_call* E) {
     F2_TRY(f2_check_ctx(ctx));
     F2_TRY(f2_check_dsp(ctx, wave_dtype, lpf, cutoff_hz, fft_precision));
     F2_TRY(f2_check_batch(ctx, offsets, B, C, mem_space, true));
     F2_CHECK(ctx, coefs && radius >= 0 && step >= 0, F2_ERR_INVALID, "coefs is NULL, or negative radius or step");
-    const int R = 2 * radius + 1;
-    F2_TRY(f2_check_cnn(ctx, cnn, R, C));
-    const bool host = mem_space == F2_MEM_HOST;
+    E->R = 2 * radius + 1;
+    F2_TRY(f2_check_cnn(ctx, cnn, E->R, C));
+    E->host = mem_space == F2_MEM_HOST;
+    E->total = offsets[B];
+    return F2_OK;
+}
+
+// filterbank + envelope of the whole batch, always by the two kernels: one utterance evaluated alone and inside a batch
+// goes through the same envelope kernel. The envelopes stay in stage_out (or the caller's device buffer) for the window loop.
+// With no window to evaluate (n_windows == 0) a host call is complete when this returns.
+int eval_envelopes(f2_ctx* ctx, eval_call* E, const void* wave, int wave_dtype, const int64_t* offsets, const double* coefs, int B,
+                   int C, int lpf, double cutoff_hz, int fft_precision, double* env_or_null, int64_t n_windows, int mem_space) {
+    F2_CHECK(ctx, wave, F2_ERR_INVALID, "null wave");
+    F2_TRY(f2_upload_offsets(ctx, offsets, B));
+    F2_TRY(f2_upload_coefs(ctx, coefs, C));
+    const size_t env_bytes = sizeof(double) * (size_t)C * (size_t)E->total;
+    E->d_env = env_or_null;
+    if (E->host || !env_or_null) {
+        F2_TRY(f2_reserve(ctx, ctx->stage_out, env_bytes));
+        E->d_env = (double*)ctx->stage_out.ptr;
+    }
+    const void* d_wave;
+    F2_TRY(f2_stage_wave(ctx, wave, wave_dtype, E->total, mem_space, &d_wave));
+    F2_TRY(f2_envelopes_device(ctx, d_wave, wave_dtype, offsets, B, C, lpf, cutoff_hz, fft_precision, E->d_env, nullptr, false));
+    if (E->host && env_or_null) F2_HIP(ctx, hipMemcpyAsync(env_or_null, E->d_env, env_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    if (n_windows == 0 && E->host) F2_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return F2_OK;
+}
+
+// Buffers of the window loop: xbuf and the convolution workspace for `chunk` windows, conv4 / dense1 outputs of a dense group
+// (the dense layers run over the conv4 outputs of up to DENSE_GROUP windows at once: dense1's grid of 64-window workgroups then
+// fills whole rounds of the device - launched per 14 240-window utterance its second round was one third full), scores and
+// labels of all n_total windows (staged for host calls); nothing leaves HBM. Clears the error flag.
+int eval_cnn_begin(f2_ctx* ctx, const f2_cnn* cnn, eval_call* E, int64_t chunk, int64_t n_total, int C, float* scores_or_null,
+                   uint8_t* labels_or_null) {
+    E->n_total = n_total;
+    E->group_cap = n_total < DENSE_GROUP ? n_total : DENSE_GROUP;
+    const size_t conv_floats = f2_cnn_workspace_floats(cnn) - f2_cnn_dense_floats(cnn);
+    E->flat = f2_cnn_flat_floats(cnn);
+    F2_TRY(f2_reserve(ctx, ctx->xbuf, sizeof(float) * (size_t)chunk * E->R * (size_t)C));
+    F2_TRY(f2_reserve(ctx, ctx->work, sizeof(float) * conv_floats * (size_t)chunk));
+    F2_TRY(f2_reserve(ctx, ctx->dense_in, sizeof(float) * f2_cnn_dense_floats(cnn) * (size_t)E->group_cap));
+    E->d_a4 = (float*)ctx->dense_in.ptr;
+    E->d_a5 = E->d_a4 + E->flat * (size_t)E->group_cap;
+    E->d_scores = scores_or_null;
+    E->d_labels = labels_or_null;
+    if (E->host) {
+        F2_TRY(f2_reserve(ctx, ctx->stage_aux, (sizeof(float) * 2 + 1) * (size_t)n_total + 64));
+        E->d_scores = (float*)ctx->stage_aux.ptr;
+        E->d_labels = (uint8_t*)(E->d_scores + 2 * n_total);
+    }
+    F2_TRY(f2_cnn_scale_set(ctx, cnn, 0, &E->S1));   // K3's normalised windows lie in [0, 1] by construction: no range pass
+    E->g0 = E->gn = 0;
+    return reset_flag(ctx);
+}
+
+int eval_dense_flush(f2_ctx* ctx, const f2_cnn* cnn, eval_call* E) {
+    if (E->gn > 0)
+        F2_TRY(f2_launch_cnn_dense(ctx, cnn, E->S1, E->d_a4, E->gn, E->d_a5, E->d_scores ? E->d_scores + 2 * E->g0 : nullptr,
+                                   E->d_labels ? E->d_labels + E->g0 : nullptr));
+    E->g0 += E->gn;
+    E->gn = 0;
+    return F2_OK;
+}
+
+// before the windows of a chunk of m are written to xbuf: room for them in the open dense group
+int eval_chunk_room(f2_ctx* ctx, const f2_cnn* cnn, eval_call* E, int64_t m) {
+    return E->gn + m > E->group_cap ? eval_dense_flush(ctx, cnn, E) : F2_OK;
+}
+
+// conv1 .. conv4 of the m windows in xbuf, appended to the open dense group
+int eval_chunk_convs(f2_ctx* ctx, const f2_cnn* cnn, eval_call* E, int64_t m) {
+    F2_TRY(f2_launch_cnn_convs(ctx, cnn, E->S1, (const float*)ctx->xbuf.ptr, m, (float*)ctx->work.ptr, E->d_a4 + E->flat * (size_t)E->gn));
+    E->gn += m;
+    return F2_OK;
+}
+
+// the last dense group, scores / labels to a host caller, and the wait for the stream with the windows' error flag
+int eval_cnn_end(f2_ctx* ctx, const f2_cnn* cnn, eval_call* E, float* scores_or_null, uint8_t* labels_or_null) {
+    F2_TRY(eval_dense_flush(ctx, cnn, E));
+    if (E->host) {
+        if (scores_or_null)
+            F2_HIP(ctx, hipMemcpyAsync(scores_or_null, E->d_scores, sizeof(float) * 2 * (size_t)E->n_total, hipMemcpyDeviceToHost, ctx->stream));
+        if (labels_or_null)
+            F2_HIP(ctx, hipMemcpyAsync(labels_or_null, E->d_labels, (size_t)E->n_total, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    return finish_positive(ctx);
+}
+
+}  // namespace
+
+// f2_eval_batch, and f2_eval_utterance as its B = 1 case with the envelope output (env_or_null, in mem_space) and the window
+// count (n_windows_out): every-sample windows -> normalise -> conv1 .. conv4, utterance by utterance, chunk by chunk
+static int eval_batch_impl(f2_ctx* ctx, const f2_cnn* cnn, const void* wave, int wave_dtype, const int64_t* offsets,
+                           const double* coefs, int B, int C, int lpf, double cutoff_hz, int fft_precision, int radius, int step,
+                           double* env_or_null, float* scores_or_null, uint8_t* labels_or_null, int64_t* n_windows_out,
+                           int mem_space) {
+    eval_call E;
+    F2_TRY(eval_check(ctx, cnn, wave_dtype, offsets, coefs, B, C, lpf, cutoff_hz, fft_precision, radius, step, mem_space, &E));
     int64_t nb_total = 0, nb_max = 0;
     for (int b = 0; b < B; ++b) {
-        const int64_t nb = offsets[b + 1] - offsets[b] - (int64_t)R * step;   // Evaluating.py:73
+        const int64_t nb = offsets[b + 1] - offsets[b] - (int64_t)E.R * step;   // Evaluating.py:73
         if (nb > 0) {
             nb_total += nb;
             nb_max = nb > nb_max ? nb : nb_max;
         }
     }
     if (n_windows_out) *n_windows_out = nb_total;
-    const int64_t total = offsets[B];
-    if (total == 0) return F2_OK;
-    F2_CHECK(ctx, wave, F2_ERR_INVALID, "null wave");
-
-    // filterbank + envelope of the whole batch, always by the two kernels: one utterance evaluated alone and inside a batch
-    // goes through the same envelope kernel. The envelopes stay in stage_out (or the caller's device buffer) for the window loop.
-    F2_TRY(f2_upload_offsets(ctx, offsets, B));
-    F2_TRY(f2_upload_coefs(ctx, coefs, C));
-    const size_t env_bytes = sizeof(double) * (size_t)C * (size_t)total;
-    double* d_env = env_or_null;
-    if (host || !env_or_null) {
-        F2_TRY(f2_reserve(ctx, ctx->stage_out, env_bytes));
-        d_env = (double*)ctx->stage_out.ptr;
-    }
-    const void* d_wave;
-    F2_TRY(f2_stage_wave(ctx, wave, wave_dtype, total, mem_space, &d_wave));
-    F2_TRY(f2_envelopes_device(ctx, d_wave, wave_dtype, offsets, B, C, lpf, cutoff_hz, fft_precision, d_env, nullptr, false));
-    if (host && env_or_null) F2_HIP(ctx, hipMemcpyAsync(env_or_null, d_env, env_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    if (nb_total == 0) {
-        if (host) F2_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        return F2_OK;
-    }
-
-    // every-sample windows -> normalise -> conv1 .. conv4, utterance by utterance, chunk by chunk; the dense layers run over the
-    // conv4 outputs of up to DENSE_GROUP windows at once (dense1's grid of 64-window workgroups then fills whole rounds of the
-    // device: launched per 14 240-window utterance its second round was one third full); nothing leaves HBM
+    if (E.total == 0) return F2_OK;
+    F2_TRY(eval_envelopes(ctx, &E, wave, wave_dtype, offsets, coefs, B, C, lpf, cutoff_hz, fft_precision, env_or_null, nb_total,
+                          mem_space));
+    if (nb_total == 0) return F2_OK;
     const int64_t chunk = nb_max < CNN_CHUNK ? nb_max : CNN_CHUNK;
-    const int64_t group_cap = nb_total < DENSE_GROUP ? nb_total : DENSE_GROUP;
-    const size_t conv_floats = f2_cnn_workspace_floats(cnn) - f2_cnn_dense_floats(cnn), flat = f2_cnn_flat_floats(cnn);
-    F2_TRY(f2_reserve(ctx, ctx->xbuf, sizeof(float) * (size_t)chunk * R * (size_t)C));
-    F2_TRY(f2_reserve(ctx, ctx->work, sizeof(float) * conv_floats * (size_t)chunk));
-    F2_TRY(f2_reserve(ctx, ctx->dense_in, sizeof(float) * f2_cnn_dense_floats(cnn) * (size_t)group_cap));
-    float* const d_a4 = (float*)ctx->dense_in.ptr;
-    float* const d_a5 = d_a4 + flat * (size_t)group_cap;
-    float* d_scores = scores_or_null;
-    uint8_t* d_labels = labels_or_null;
-    if (host) {
-        F2_TRY(f2_reserve(ctx, ctx->stage_aux, (sizeof(float) * 2 + 1) * (size_t)nb_total + 64));
-        d_scores = (float*)ctx->stage_aux.ptr;
-        d_labels = (uint8_t*)(d_scores + 2 * nb_total);
-    }
-    const f2_scale_set* S1 = nullptr;
-    F2_TRY(f2_cnn_scale_set(ctx, cnn, 0, &S1));   // K3's normalised windows lie in [0, 1] by construction: no range pass
-    F2_TRY(reset_flag(ctx));
+    F2_TRY(eval_cnn_begin(ctx, cnn, &E, chunk, nb_total, C, scores_or_null, labels_or_null));
     const int64_t reach = (int64_t)radius * step;
-    int64_t g0 = 0, gn = 0;      // first window and size of the open dense group
-    auto flush = [&]() -> int {
-        if (gn > 0)
-            F2_TRY(f2_launch_cnn_dense(ctx, cnn, S1, d_a4, gn, d_a5, d_scores ? d_scores + 2 * g0 : nullptr, d_labels ? d_labels + g0 : nullptr));
-        g0 += gn;
-        gn = 0;
-        return F2_OK;
-    };
     for (int b = 0; b < B; ++b) {
         const int64_t N = offsets[b + 1] - offsets[b];
-        const int64_t nb = N - (int64_t)R * step;
-        const double* env_b = d_env + (size_t)C * (size_t)offsets[b];
+        const int64_t nb = N - (int64_t)E.R * step;
+        const double* env_b = E.d_env + (size_t)C * (size_t)offsets[b];
         for (int64_t s = 0; s < nb; s += chunk) {
             const int64_t m = nb - s < chunk ? nb - s : chunk;
-            if (gn + m > group_cap) F2_TRY(flush());
+            F2_TRY(eval_chunk_room(ctx, cnn, &E, m));
             F2_TRY(f2_launch_gather(ctx, env_b, C, N, nullptr, reach + s, m, radius, step, 1, (float*)ctx->xbuf.ptr,
                                     (int*)ctx->flags.ptr));
-            F2_TRY(f2_launch_cnn_convs(ctx, cnn, S1, (const float*)ctx->xbuf.ptr, m, (float*)ctx->work.ptr, d_a4 + flat * (size_t)gn));
-            gn += m;
+            F2_TRY(eval_chunk_convs(ctx, cnn, &E, m));
         }
     }
-    F2_TRY(flush());
-    if (host) {
-        if (scores_or_null)
-            F2_HIP(ctx, hipMemcpyAsync(scores_or_null, d_scores, sizeof(float) * 2 * (size_t)nb_total, hipMemcpyDeviceToHost, ctx->stream));
-        if (labels_or_null)
-            F2_HIP(ctx, hipMemcpyAsync(labels_or_null, d_labels, (size_t)nb_total, hipMemcpyDeviceToHost, ctx->stream));
+    return eval_cnn_end(ctx, cnn, &E, scores_or_null, labels_or_null);
+}
+
+// f2_eval_batch_strided: window j of utterance b is every-sample window j * hop. A chunk is up to CNN_CHUNK windows taken from
+// as many utterances as it holds (an utterance may continue in the next chunk): one window-stage launch set and one
+// convolution launch set per chunk, whatever B. (On the decimating route a chunk also closes at COLUMN_CAP columns of the
+// window stage's scratch - 2 * radius * step / hop columns per segment on top of its windows: 150 MB for 128 channels - which
+// only batches of very many very short utterances at a small hop reach.)
+static int eval_strided_impl(f2_ctx* ctx, const f2_cnn* cnn, const void* wave, int wave_dtype, const int64_t* offsets,
+                             const double* coefs, int B, int C, int lpf, double cutoff_hz, int fft_precision, int radius, int step,
+                             int hop, float* scores_or_null, uint8_t* labels_or_null, int64_t* window_offsets_or_null,
+                             int mem_space) {
+    constexpr int64_t COLUMN_CAP = 8 * CNN_CHUNK;
+    eval_call E;
+    F2_TRY(eval_check(ctx, cnn, wave_dtype, offsets, coefs, B, C, lpf, cutoff_hz, fft_precision, radius, step, mem_space, &E));
+    F2_CHECK(ctx, hop >= 1, F2_ERR_INVALID, "hop must be at least 1 sample (got %d)", hop);
+    std::vector<int64_t> nbh((size_t)B);
+    int64_t n_total = 0;
+    if (window_offsets_or_null) window_offsets_or_null[0] = 0;
+    for (int b = 0; b < B; ++b) {
+        const int64_t nb = offsets[b + 1] - offsets[b] - (int64_t)E.R * step;
+        nbh[(size_t)b] = nb > 0 ? (nb + hop - 1) / hop : 0;
+        n_total += nbh[(size_t)b];
+        if (window_offsets_or_null) window_offsets_or_null[b + 1] = n_total;
     }
-    return finish_positive(ctx);
+    if (E.total == 0) return F2_OK;
+    F2_TRY(eval_envelopes(ctx, &E, wave, wave_dtype, offsets, coefs, B, C, lpf, cutoff_hz, fft_precision, nullptr, n_total, mem_space));
+    if (n_total == 0) return F2_OK;
+    const int64_t chunk = n_total < CNN_CHUNK ? n_total : CNN_CHUNK;
+    F2_TRY(eval_cnn_begin(ctx, cnn, &E, chunk, n_total, C, scores_or_null, labels_or_null));
+    const bool columns = f2_gather_strided_blocked(ctx, C, step, hop);
+    std::vector<f2_win_seg> segs;
+    int64_t m = 0, cols = 0;     // windows and scratch columns of the open chunk
+    auto close_chunk = [&]() -> int {
+        if (m > 0) {
+            F2_TRY(eval_chunk_room(ctx, cnn, &E, m));
+            F2_TRY(f2_launch_gather_strided(ctx, E.d_env, C, (const int64_t*)ctx->offsets.ptr, offsets, segs.data(), (int)segs.size(),
+                                            radius, step, hop, (float*)ctx->xbuf.ptr, (int*)ctx->flags.ptr));
+            F2_TRY(eval_chunk_convs(ctx, cnn, &E, m));
+        }
+        segs.clear();
+        m = cols = 0;
+        return F2_OK;
+    };
+    for (int b = 0; b < B; ++b)
+        for (int64_t j = 0; j < nbh[(size_t)b];) {
+            int64_t take = nbh[(size_t)b] - j < chunk - m ? nbh[(size_t)b] - j : chunk - m;
+            const int64_t c = columns ? f2_gather_strided_columns(take, radius, step, hop) : 0;
+            if (m > 0 && cols + c > COLUMN_CAP) {
+                F2_TRY(close_chunk());
+                continue;
+            }
+            segs.push_back({b, j, take});
+            j += take;
+            m += take;
+            cols += c;
+            if (m == chunk) F2_TRY(close_chunk());
+        }
+    F2_TRY(close_chunk());
+    return eval_cnn_end(ctx, cnn, &E, scores_or_null, labels_or_null);
 }
 
 extern "C" {
@@ -295,6 +410,13 @@ int f2_eval_batch(f2_ctx* ctx, const f2_cnn* cnn, const void* wave, int wave_dty
                   float* scores_or_null, uint8_t* labels_or_null, int mem_space) {
     return eval_batch_impl(ctx, cnn, wave, wave_dtype, offsets, coefs, B, C, lpf, cutoff_hz, fft_precision, radius, step, nullptr,
                            scores_or_null, labels_or_null, nullptr, mem_space);
+}
+
+int f2_eval_batch_strided(f2_ctx* ctx, const f2_cnn* cnn, const void* wave, int wave_dtype, const int64_t* offsets,
+                          const double* coefs, int B, int C, int lpf, double cutoff_hz, int fft_precision, int radius, int step,
+                          int hop, float* scores_or_null, uint8_t* labels_or_null, int64_t* window_offsets_or_null, int mem_space) {
+    return eval_strided_impl(ctx, cnn, wave, wave_dtype, offsets, coefs, B, C, lpf, cutoff_hz, fft_precision, radius, step, hop,
+                             scores_or_null, labels_or_null, window_offsets_or_null, mem_space);
 }
 
 int f2_input_batch(f2_ctx* ctx, const void* wave, int wave_dtype, const int64_t* offsets, const double* coefs, int B, int C,

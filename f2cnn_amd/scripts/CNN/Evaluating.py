@@ -2,7 +2,11 @@
 envelope -> every-sample 11xC windows -> normalise -> CNN -> rising/falling label per sample
 (``EvaluateOneWavArray`` :42-87, ``EvaluateOneWavFile`` :116-135). Accuracy against VTR labels and the
 plots (:89-113) need the TIMIT/VTR side files and are outside this path; the scores and labels are
-returned and saved next to the WAV instead."""
+returned and saved next to the WAV instead.
+
+``hop=N`` (``cnn eval|evalnoise|evalrand --hop N``; not in the reference) evaluates every N-th of those windows only -
+row j is every-sample row j*N, bit for bit (``f2_eval_batch_strided``) - and the ``.F2CNN.npz`` then also holds ``hop`` and
+``timepoints``, the centre sample of every row. ``hop=None`` is the reference's every-sample loop."""
 import os
 
 import numpy
@@ -15,9 +19,27 @@ from ..processing.EnvelopeExtraction import FFT_PRECISION
 from ..processing.GammatoneFiltering import GetArrayFromWAV
 
 
+def _step(framerate, cfg):
+    return int(framerate * cfg.sampling_period * (1 / 1000000.))
+
+
+def _save(out, scores, labels, hop, N, framerate):
+    """<base>.F2CNN.npz: scores and labels; with a hop also the hop and the centre sample of every row"""
+    if hop is None:
+        numpy.savez(out, scores=scores, labels=labels)
+        return
+    cfg = F2Config()
+    timepoints = _lib.strided_timepoints(N, cfg.radius, _step(framerate, cfg), hop)
+    assert len(timepoints) == len(labels)
+    numpy.savez(out, scores=scores, labels=labels, hop=numpy.int64(hop), timepoints=timepoints)
+
+
 def EvaluateOneWavArray(wavArray, framerate, wavFileName=None, model='last_trained_model', LPF=False, CUTOFF=100,
-                        CENTER_FREQUENCIES=None, FILTERBANK_COEFFICIENTS=None, ctx=None, return_envelopes=False):
-    """Returns (scores (nb,2) float32, labels (nb,) uint8 [, envelopes (C,N) float64]); nb = N - 11*STEP."""
+                        CENTER_FREQUENCIES=None, FILTERBANK_COEFFICIENTS=None, ctx=None, return_envelopes=False, hop=None):
+    """Returns (scores (nb,2) float32, labels (nb,) uint8 [, envelopes (C,N) float64]); nb = N - 11*STEP, or with a hop
+    ceil(nb / hop) rows, row j centred at sample radius*STEP + j*hop."""
+    if hop is not None and return_envelopes:
+        raise ValueError("the strided evaluation (hop) does not return envelopes")
     ctx = ctx or _lib.default_context()
     cfg = F2Config()
     if FILTERBANK_COEFFICIENTS is None:
@@ -34,8 +56,10 @@ def EvaluateOneWavArray(wavArray, framerate, wavFileName=None, model='last_train
         print("Extraction Envelope with {}Hz Low Pass Filter...".format(CUTOFF))
     wave, dt = filters._wave_args(wavArray)
     N = wave.shape[0]
-    STEP = int(framerate * cfg.sampling_period * (1 / 1000000.))
+    STEP = _step(framerate, cfg)
     nb = max(int(N - cfg.dots_per_input * STEP), 0)
+    if hop is not None:
+        nb = _lib.strided_window_count(N, cfg.radius, STEP, hop)
     print("Generating input data for CNN...")
     print("INPUT SHAPE:", (nb, cfg.dots_per_input, Cn))
     scores = numpy.empty((nb, 2), numpy.float32)
@@ -43,8 +67,13 @@ def EvaluateOneWavArray(wavArray, framerate, wavFileName=None, model='last_train
     env = numpy.empty((Cn, N), numpy.float64) if return_envelopes else None
     print("Evaluating the data with the pretrained model...")
     try:
-        got = ctx.eval_utterance(model.handle(ctx), wave, dt, N, coefs, Cn, bool(LPF), CUTOFF if LPF else 0.0,
-                                 FFT_PRECISION, cfg.radius, STEP, env, scores, labels, _lib.MEM_HOST)
+        if hop is not None:
+            got = ctx.eval_batch_strided(model.handle(ctx), wave, dt, numpy.array([0, N], numpy.int64), coefs, 1, Cn, bool(LPF),
+                                         CUTOFF if LPF else 0.0, FFT_PRECISION, cfg.radius, STEP, hop, scores, labels,
+                                         _lib.MEM_HOST)[1]
+        else:
+            got = ctx.eval_utterance(model.handle(ctx), wave, dt, N, coefs, Cn, bool(LPF), CUTOFF if LPF else 0.0,
+                                     FFT_PRECISION, cfg.radius, STEP, env, scores, labels, _lib.MEM_HOST)
     except _lib.F2Error as e:
         if e.code == _lib.F2_ERR_NONPOSITIVE:
             raise ValueError("values must all be positive")
@@ -54,16 +83,17 @@ def EvaluateOneWavArray(wavArray, framerate, wavFileName=None, model='last_train
 
 
 def EvaluateOneWavFile(file, LPF=False, CUTOFF=50, model='last_trained_model', CENTER_FREQUENCIES=None,
-                       FILTERBANK_COEFFICIENTS=None):
-    """`cnn eval --file X.WAV`: writes <base>.F2CNN.npz (scores, labels) and returns (scores, labels)."""
+                       FILTERBANK_COEFFICIENTS=None, hop=None):
+    """`cnn eval --file X.WAV [--hop N]`: writes <base>.F2CNN.npz (scores, labels; with a hop also hop, timepoints) and
+    returns (scores, labels)."""
     print('Using model', model if not isinstance(model, F2CNNModel) else '<in-memory model>')
     print("File:\t\t{}".format(file))
     framerate, wavArray = GetArrayFromWAV(file)
     scores, labels = EvaluateOneWavArray(wavArray, framerate, file, model=model, LPF=LPF, CUTOFF=CUTOFF,
                                          CENTER_FREQUENCIES=CENTER_FREQUENCIES,
-                                         FILTERBANK_COEFFICIENTS=FILTERBANK_COEFFICIENTS)
+                                         FILTERBANK_COEFFICIENTS=FILTERBANK_COEFFICIENTS, hop=hop)
     out = os.path.splitext(file)[0] + '.F2CNN.npz'
-    numpy.savez(out, scores=scores, labels=labels)
+    _save(out, scores, labels, hop, len(wavArray), framerate)
     rising = int(labels.sum())
     print("\t\t{}\tdone ! {} windows: {} rising, {} falling -> {}".format(file, len(labels), rising,
                                                                           len(labels) - rising, out))
@@ -72,9 +102,10 @@ def EvaluateOneWavFile(file, LPF=False, CUTOFF=50, model='last_trained_model', C
 
 # ---- batch / noise evaluation (reference scripts/CNN/Evaluating.py:138-221) -------------
 def EvaluateWavArrays(wavArrays, framerate, model='last_trained_model', LPF=False, CUTOFF=100,
-                      FILTERBANK_COEFFICIENTS=None, ctx=None):
+                      FILTERBANK_COEFFICIENTS=None, ctx=None, hop=None):
     """EvaluateOneWavArray for a list of utterances of one sample type in one device pass (f2_eval_batch): the
-    filterbank and envelope kernels see the whole batch, windows and CNN run utterance by utterance.
+    filterbank and envelope kernels see the whole batch, windows and CNN run utterance by utterance. With a hop
+    (f2_eval_batch_strided) every hop-th window, and the window stage and the CNN see the batch as well.
     Returns a list of (scores (nb,2) float32, labels (nb,) uint8)."""
     ctx = ctx or _lib.default_context()
     cfg = F2Config()
@@ -93,13 +124,21 @@ def EvaluateWavArrays(wavArrays, framerate, model='last_trained_model', LPF=Fals
     offsets = numpy.zeros(len(waves) + 1, numpy.int64)
     offsets[1:] = numpy.cumsum([w.shape[0] for w in waves])
     flat = numpy.concatenate(waves)
-    STEP = int(framerate * cfg.sampling_period * (1 / 1000000.))
+    STEP = _step(framerate, cfg)
     nbs = [max(int(w.shape[0] - cfg.dots_per_input * STEP), 0) for w in waves]
+    if hop is not None:
+        nbs = [_lib.strided_window_count(w.shape[0], cfg.radius, STEP, hop) for w in waves]
     scores = numpy.empty((sum(nbs), 2), numpy.float32)
     labels = numpy.empty(sum(nbs), numpy.uint8)
     try:
-        ctx.eval_batch(model.handle(ctx), flat, dts[0], offsets, coefs, len(waves), Cn, bool(LPF), CUTOFF if LPF else 0.0,
-                       FFT_PRECISION, cfg.radius, STEP, scores, labels, _lib.MEM_HOST)
+        if hop is not None:
+            got = ctx.eval_batch_strided(model.handle(ctx), flat, dts[0], offsets, coefs, len(waves), Cn, bool(LPF),
+                                         CUTOFF if LPF else 0.0, FFT_PRECISION, cfg.radius, STEP, hop, scores, labels,
+                                         _lib.MEM_HOST)
+            assert list(numpy.diff(got)) == nbs
+        else:
+            ctx.eval_batch(model.handle(ctx), flat, dts[0], offsets, coefs, len(waves), Cn, bool(LPF), CUTOFF if LPF else 0.0,
+                           FFT_PRECISION, cfg.radius, STEP, scores, labels, _lib.MEM_HOST)
     except _lib.F2Error as e:
         if e.code == _lib.F2_ERR_NONPOSITIVE:
             raise ValueError("values must all be positive")
@@ -111,10 +150,11 @@ def EvaluateWavArrays(wavArrays, framerate, model='last_trained_model', LPF=Fals
     return out
 
 
-def EvaluateRandom(count=None, LPF=False, CUTOFF=50, model='last_trained_model'):
+def EvaluateRandom(count=None, LPF=False, CUTOFF=50, model='last_trained_model', hop=None):
     """`cnn evalrand`: evaluate the WAV files under resources/f2cnn/*/ in random order (all of them, or `count`
     drawn with replacement like numpy.random.choice in the reference). The filterbank is designed once and the model
-    is uploaded once (the reference reloads the Keras model for every file)."""
+    is uploaded once (the reference reloads the Keras model for every file). With a hop each group of files is one
+    strided call."""
     import glob
     import time
     TotalTime = time.time()
@@ -141,14 +181,15 @@ def EvaluateRandom(count=None, LPF=False, CUTOFF=50, model='last_trained_model')
         rates = {fr for fr, _ in loaded}
         if len(rates) == 1 and len({numpy.asarray(w).dtype for _, w in loaded}) == 1:
             outs = EvaluateWavArrays([w for _, w in loaded], loaded[0][0], model=model, LPF=LPF, CUTOFF=CUTOFF,
-                                     FILTERBANK_COEFFICIENTS=FILTERBANK_COEFFICIENTS)
+                                     FILTERBANK_COEFFICIENTS=FILTERBANK_COEFFICIENTS, hop=hop)
         else:                                     # mixed files: one at a time
             outs = [EvaluateOneWavArray(w, fr, file, model=model, LPF=LPF, CUTOFF=CUTOFF,
-                                        FILTERBANK_COEFFICIENTS=FILTERBANK_COEFFICIENTS if fr == cfg.framerate else None)
+                                        FILTERBANK_COEFFICIENTS=FILTERBANK_COEFFICIENTS if fr == cfg.framerate else None,
+                                        hop=hop)
                     for file, (fr, w) in zip(group, loaded)]
-        for file, (scores, labels) in zip(group, outs):
+        for file, (fr, w), (scores, labels) in zip(group, loaded, outs):
             out = os.path.splitext(file)[0] + '.F2CNN.npz'
-            numpy.savez(out, scores=scores, labels=labels)
+            _save(out, scores, labels, hop, len(w), fr)
             rising = int(labels.sum())
             print("\t\t{}\tdone ! {} windows: {} rising, {} falling -> {}".format(file, len(labels), rising,
                                                                                   len(labels) - rising, out))
@@ -184,7 +225,7 @@ def add_gaussian_noise(wave, SNRdB, rng=None):
 
 
 def EvaluateWithNoise(file, LPF=False, CUTOFF=100, model='last_trained_model', CENTER_FREQUENCIES=None,
-                      FILTERBANK_COEFFICIENTS=None, SNRdB=-3, rng=None):
+                      FILTERBANK_COEFFICIENTS=None, SNRdB=-3, rng=None, hop=None):
     """`cnn evalnoise` (reference: scripts/CNN/Evaluating.py:193-221): the file plus Gaussian noise at the requested level is
     written next to copies of its annotation files under OutputWavFiles/addedNoise/ and the float64 waveform is evaluated by
     the device pipeline. Returns (scores, labels) and also leaves them in <target>.F2CNN.npz; `rng` (a numpy Generator or
@@ -205,7 +246,7 @@ def EvaluateWithNoise(file, LPF=False, CUTOFF=100, model='last_trained_model', C
     print('New noisy WAVE file saved as', target + '.WAV')
     scores, labels = EvaluateOneWavArray(noisy, framerate, target + '.WAV', model=model, LPF=LPF, CUTOFF=CUTOFF,
                                          CENTER_FREQUENCIES=CENTER_FREQUENCIES,
-                                         FILTERBANK_COEFFICIENTS=FILTERBANK_COEFFICIENTS)
-    numpy.savez(target + '.F2CNN.npz', scores=scores, labels=labels)
+                                         FILTERBANK_COEFFICIENTS=FILTERBANK_COEFFICIENTS, hop=hop)
+    _save(target + '.F2CNN.npz', scores, labels, hop, len(noisy), framerate)
     print("\t\t{}\tdone !".format(file))
     return scores, labels

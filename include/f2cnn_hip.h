@@ -62,7 +62,8 @@ enum { F2_FFT_F32 = 0, F2_FFT_F64 = 1 };
 /* ---- library / context -------------------------------------------------------------------- */
 int f2_version(void);   /* 100 * major + minor; 101 added f2_eval_batch, 102 f2_host_alloc + F2_MEM_HOST_ASYNC, 103 f2_ctx_set_option, 105 f2_spectral_guard_read + f2_cnn_get_info,
                            106 f2_cnn_forward accepts any finite input on the split path (scales from the input's range; the
-                           f2_cnn_get_info keys "f16x3_ok", "f16x3_check_diff", "last_input_bound"), 107 f2_input_batch */
+                           f2_cnn_get_info keys "f16x3_ok", "f16x3_check_diff", "last_input_bound"), 107 f2_input_batch,
+                           108 f2_eval_batch_strided */
 int f2_device_count(int* count);
 int f2_ctx_create(int device, f2_ctx** ctx);
 int f2_ctx_destroy(f2_ctx* ctx);
@@ -270,6 +271,27 @@ int f2_eval_utterance(f2_ctx* ctx, const f2_cnn* cnn, const void* wave, int wave
 int f2_eval_batch(f2_ctx* ctx, const f2_cnn* cnn, const void* wave, int wave_dtype, const int64_t* offsets,
                   const double* coefs, int B, int C, int lpf, double cutoff_hz, int fft_precision, int radius,
                   int step, float* scores_or_null, uint8_t* labels_or_null, int mem_space);
+
+/* f2_eval_batch with a decision every `hop` samples instead of every sample (the reference's loop, Evaluating.py:71-87, takes
+ * every sample; the labelled quantity, a slope over 11 frames 10 ms apart, does not change at that rate). Utterance b with
+ * nb_b = max(0, n_b - (2*radius+1)*step) every-sample windows gets nbh_b = ceil(nb_b / hop) windows; window j of this call IS
+ * window j*hop of f2_eval_batch - centre sample radius*step + j*hop, the same envelope (the two-kernel route), the same window
+ * arithmetic, the same network: scores and labels are bit-identical to those rows, and hop = 1 reproduces f2_eval_batch.
+ * scores (sum nbh_b, 2) / labels (sum nbh_b) are the concatenation over b in `mem_space`, both optional;
+ * window_offsets_or_null, always a HOST array of B+1 like `offsets`, receives the prefix sums of nbh_b (also when the call then
+ * has nothing to launch).
+ * The window stage and the convolutions work on chunks of up to 16 384 windows taken across utterance boundaries, so the
+ * number of kernel launches follows the number of windows, not B. When hop divides step the windows are the every-sample
+ * windows of the decimated envelope env[c][j*hop]: one logarithm per sample that an evaluated window uses, for all utterances
+ * of a chunk in three launches; any other hop takes one workgroup per window (f2_input_batch's kernel, normalising).
+ * Errors: those of f2_eval_batch, checked the same way, plus hop < 1 -> F2_ERR_INVALID (nothing is launched).
+ * F2_ERR_NONPOSITIVE is raised only by windows that are evaluated: a sample <= 0 that no evaluated window reads does not fail
+ * the call (the reference raises from normalizeInput of a window, not from the envelope).
+ */
+int f2_eval_batch_strided(f2_ctx* ctx, const f2_cnn* cnn, const void* wave, int wave_dtype, const int64_t* offsets,
+                          const double* coefs, int B, int C, int lpf, double cutoff_hz, int fft_precision, int radius,
+                          int step, int hop, float* scores_or_null, uint8_t* labels_or_null,
+                          int64_t* window_offsets_or_null /* host, B+1 */, int mem_space);
 
 #ifdef __cplusplus
 }
