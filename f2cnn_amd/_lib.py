@@ -63,6 +63,8 @@ SIGNATURES = {
     "f2_eval_utterance": (_i, [_vp, _vp, _vp, _i, _i64, _vp, _i, _i, _d, _i, _i, _i, _vp, _vp, _vp, _P(_i64), _i]),
     "f2_eval_batch": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _d, _i, _i, _i, _vp, _vp, _i]),
     "f2_eval_batch_strided": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _d, _i, _i, _i, _i, _vp, _vp, _vp, _i]),
+    "f2_eval_noise_sweep": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _d, _i, _i, _i, _i, _vp, _i, C.c_uint64, _vp, _vp, _vp,
+                                 _vp, _vp, _vp, _i]),
 }
 
 _lib = None
@@ -363,6 +365,33 @@ class Context:
                                                   int(B), Cn, int(bool(lpf)), float(cutoff), precision, radius, step, int(hop),
                                                   _ptr(scores), _ptr(labels), _ptr(window_offsets), mem_space))
         return window_offsets
+
+    def eval_noise_sweep(self, handle, wave, wave_dtype, offsets, coefs, B, Cn, lpf, cutoff, precision, radius, step, hop,
+                         snr_db, seed, noisy, scores, labels, mem_space, window_offsets=None, sigma=None, stats=None):
+        """The batch at every noise level of snr_db and clean, in one device pass (see f2_eval_noise_sweep): utterance
+        l * B + b of the evaluated batch is utterance b at level l, the clean level last. noisy / scores / labels (numpy
+        arrays or device pointers, by mem_space) may be None. Returns (window_offsets ((K+1)*B + 1, int64), sigma ((K+1)*B,
+        float64), stats ((K+1)*B, 2) int64: rising windows, windows labelled as the clean level labels them), allocating
+        those it is not given."""
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        snr = np.ascontiguousarray(snr_db, dtype=np.float64).reshape(-1)
+        U = (len(snr) + 1) * int(B)
+        if window_offsets is None:
+            window_offsets = np.zeros(U + 1, np.int64)
+        if sigma is None:
+            sigma = np.zeros(U, np.float64)
+        if stats is None:
+            stats = np.zeros((U, 2), np.int64)
+        for a, dt, n in ((window_offsets, np.int64, U + 1), (sigma, np.float64, U), (stats, np.int64, 2 * U)):
+            if a.dtype != dt or a.size != n or not a.flags["C_CONTIGUOUS"]:
+                raise ValueError("window_offsets / sigma / stats must be contiguous int64 (K+1)*B + 1, float64 (K+1)*B, int64 "
+                                 "((K+1)*B, 2)")
+        self.check(self.lib.f2_eval_noise_sweep(self.handle, handle, _ptr(wave), wave_dtype, _ptr(offsets), _ptr(coefs), int(B),
+                                                Cn, int(bool(lpf)), float(cutoff), precision, radius, step, int(hop),
+                                                _ptr(snr) if len(snr) else None, len(snr), int(seed) & (2 ** 64 - 1), _ptr(noisy),
+                                                _ptr(scores), _ptr(labels), _ptr(window_offsets), _ptr(sigma), _ptr(stats),
+                                                mem_space))
+        return window_offsets, sigma, stats
 
 
 def strided_window_count(n, radius, step, hop):

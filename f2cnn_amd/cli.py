@@ -14,6 +14,9 @@ package implements:
     python -m f2cnn_amd cnn train [--input/-i NPY] [--label/-l CSV]   (PyTorch-ROCm autograd; weights -> last_trained_model)
     python -m f2cnn_amd cnn eval --file/-f WAV [--lpf HZ] [--model/-m NPZ] [--hop N|frame]
     python -m f2cnn_amd cnn evalnoise --file/-f WAV --noise/-n SNRdB [--lpf HZ] [--model/-m NPZ] [--hop N|frame]
+    python -m f2cnn_amd cnn noisesweep --file/-f WAV --snrs 20,10,0,-3 [--seed N] [--save-wavs] [--hop N|frame] [--lpf HZ] [--model/-m NPZ]
+                                                            (the file at every level and clean in one device pass, agreement
+                                                             with the clean decisions per level; not in the reference)
     python -m f2cnn_amd cnn evalrand [--count/-c N] [--lpf HZ] [--model/-m NPZ] [--hop N|frame]
     (--hop: a decision every N samples instead of every sample, `frame` = one per STEP of configF2CNN.conf; not in the reference)
     python -m f2cnn_amd --configure            (writes configF2CNN.conf with the reference's defaults)
@@ -23,7 +26,7 @@ organize / plot need the licensed TIMIT+VTR corpora or matplotlib and stay with 
 import argparse
 
 PREPARE = ("filter", "envelope", "label", "input", "features")
-CNN = ("train", "eval", "evalnoise", "evalrand")
+CNN = ("train", "eval", "evalnoise", "evalrand", "noisesweep")
 
 
 def hop_argument(text):
@@ -37,6 +40,18 @@ def hop_argument(text):
     if hop < 1:
         raise argparse.ArgumentTypeError("--hop takes a positive number of samples or 'frame', not {!r}".format(text))
     return hop
+
+
+def snrs_argument(text):
+    """--snrs: a comma-separated list of at least one finite SNR in dB"""
+    import math
+    try:
+        snrs = [float(part) for part in text.split(',')]
+    except ValueError:
+        snrs = []
+    if not snrs or not all(math.isfinite(v) for v in snrs):
+        raise argparse.ArgumentTypeError("--snrs takes a comma-separated list of SNRs in dB, not {!r}".format(text))
+    return snrs
 
 
 def build_parser():
@@ -70,6 +85,11 @@ def build_parser():
     c.add_argument('--hop', action='store', type=hop_argument, dest='hop',
                    help="eval / evalnoise / evalrand: evaluate every HOP-th sample ('frame': every STEP samples) instead of "
                         "every sample")
+    c.add_argument('--snrs', action='store', type=snrs_argument, dest='snrs',
+                   help="noisesweep: comma-separated SNRs in dB, e.g. 20,10,0,-3")
+    c.add_argument('--seed', action='store', type=int, dest='seed', help="noisesweep: seed of the noise (default 0)")
+    c.add_argument('--save-wavs', action='store_true', dest='save_wavs',
+                   help="noisesweep: also write the noisy WAV files, as evalnoise does")
     return parser
 
 
@@ -141,6 +161,12 @@ def main(argv=None):
         if args.file is None:
             print("Please use --file or -f to give input file")
             return 1
+        if args.cnn_command == 'noisesweep':
+            if args.snrs is None:
+                print("Please use --snrs to give the noise levels, e.g. --snrs 20,10,0,-3")
+                return 1
+            Evaluating.EvaluateNoiseSweep([args.file], args.snrs, seed=args.seed or 0, save_wavs=args.save_wavs, **kwargs)
+            return 0
         kwargs['file'] = args.file
         if args.cnn_command == 'evalnoise':
             if args.SNRdB is not None:

@@ -44,6 +44,8 @@ struct f2_ctx {
     f2_scratch work2;
     f2_scratch xbuf;       // window tensor chunk between K3 and K4
     f2_scratch dense_in;   // conv4 outputs (+ dense1 outputs) of the windows of several utterances: one dense launch for all
+    f2_scratch noise_wave; // f2_eval_noise_sweep: the (K+1) x batch float64 waveform when the caller gives no device buffer for it
+    f2_scratch noise_meta; // ... and its small arrays: sigma, 10^(snr / 10) per level, stats, window offsets
     f2_scratch gather_log; // ln of the envelope samples a chunk of every-sample windows touches + column min / max (f2_gather.hip)
     f2_scratch tw[2][16];  // FFT twiddle tables, [precision][log2 H], built on first use
     f2_scratch tw_fl[16];         // twiddle tables of f2_envelope_flagged.hip, by log2 H
@@ -376,5 +378,16 @@ int f2_launch_cnn_dense(f2_ctx* ctx, const f2_cnn* cnn, const f2_scale_set* S, c
 // values into d_words[0], of the complement of the quietest window's max |x| into d_words[2], and 1 into d_words[1] if a value is
 // inf / NaN. The caller zeroes the three words first.
 int f2_launch_cnn_input_range(f2_ctx* ctx, const float* d_x, int64_t nwin, int S, unsigned* d_words);
+// f2_noise.hip, the kernels of f2_eval_noise_sweep. d_offsets: the B + 1 offsets of the clean batch; d_lin: K values
+// 10^(snr_db / 10); d_sigma: (K + 1) * B, level-major, written by the first launch and read by the second, which writes the
+// (K + 1) * total float64 samples of all levels (level K: the clean batch) to d_out.
+int f2_launch_noise_sigma(f2_ctx* ctx, const void* d_wave, int wave_dtype, const int64_t* d_offsets, const double* d_lin, int B,
+                          int K, double* d_sigma);
+int f2_launch_noise_levels(f2_ctx* ctx, const void* d_wave, int wave_dtype, const int64_t* d_offsets, const double* d_sigma, int B,
+                           int K, int64_t total, uint64_t seed, double* d_out);
+// d_stats ((K + 1) * B pairs, zeroed by the caller) += {windows labelled rising, windows labelled as the clean level labels them}
+// per utterance of the (K + 1) * B batch whose window offsets are d_window_offsets; max_windows: the most any utterance has
+int f2_launch_label_tally(f2_ctx* ctx, const uint8_t* d_labels, const int64_t* d_window_offsets, int B, int K, int64_t max_windows,
+                          int64_t* d_stats);
 size_t f2_cnn_flat_floats(const f2_cnn* cnn);    // floats per window of the conv4 output
 size_t f2_cnn_dense_floats(const f2_cnn* cnn);   // ... plus dense1's output

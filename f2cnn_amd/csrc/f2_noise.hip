@@ -1,0 +1,174 @@
+// Kernels of f2_eval_noise_sweep (include/f2cnn_hip.h): the noise levels of a ragged batch and the tally of its labels.
+//   k_noise_sigma  sum of squares of every clean utterance (one workgroup per row, fixed order) -> sigma per (level, utterance)
+//   k_noise_levels the (K+1) x batch float64 waveform: clean + sigma * z, z from Philox4x32-10 per sample; level K is the clean one
+//   k_label_tally  per (level, utterance): windows labelled rising, windows whose label is the clean level's
+// gfx950, wave64. Everything that reaches memory is written by plain C++ stores or vector integer atomics.
+#include "f2_internal.h"
+
+#include <type_traits>
+
+namespace {
+
+constexpr int SIGMA_THREADS = 1024, NOISE_THREADS = 256, TALLY_THREADS = 256;
+
+template <typename T>
+__device__ inline T wave_sum(T v) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v += __shfl_down(v, d, 64);
+    return v;   // lane 0 holds the sum; the tree is the same on every call
+}
+
+// sum over the workgroup, valid in thread 0: lanes by shuffles, waves through LDS in wave order
+template <typename T, int THREADS>
+__device__ inline T block_sum(T v, T* lds) {
+    v = wave_sum(v);
+    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
+    __syncthreads();
+    T total = 0;
+    if (threadIdx.x == 0)
+        for (int w = 0; w < THREADS / 64; ++w) total += lds[w];
+    return total;
+}
+
+// Row b of the clean batch. int16: the squares are summed in int64 (exact, so the order does not matter), then
+// sqrt((double)sum / n). float64: thread t adds samples t, t + THREADS, ... in that order, then the fixed tree of block_sum.
+// sigma[l * B + b] = rms / lin[l] for l < K (lin[l] = 10^(snr_db[l] / 10), from the host) and 0 for the clean level l = K.
+template <typename T>
+__global__ __launch_bounds__(SIGMA_THREADS) void k_noise_sigma(const T* __restrict__ wave, const int64_t* __restrict__ offsets,
+                                                                const double* __restrict__ lin, int B, int K,
+                                                                double* __restrict__ sigma) {
+    using acc_t = typename std::conditional<std::is_same<T, int16_t>::value, long long, double>::type;
+    __shared__ acc_t lds[SIGMA_THREADS / 64];
+    const int b = blockIdx.x;
+    const int64_t n = offsets[b + 1] - offsets[b];
+    const T* x = wave + offsets[b];
+    acc_t acc = 0;
+    for (int64_t i = threadIdx.x; i < n; i += SIGMA_THREADS) {
+        const acc_t v = (acc_t)x[i];
+        acc += v * v;
+    }
+    const acc_t total = block_sum<acc_t, SIGMA_THREADS>(acc, lds);
+    if (threadIdx.x != 0) return;
+    const double rms = n > 0 ? sqrt((double)total / (double)n) : 0.0;
+    for (int l = 0; l < K; ++l) sigma[(size_t)l * B + b] = n > 0 ? rms / lin[l] : 0.0;
+    sigma[(size_t)K * B + b] = 0.0;
+}
+
+struct philox_words {
+    uint32_t w0, w1, w2, w3;
+};
+
+// Philox4x32-10 (Salmon et al., SC'11), the standard constants
+__device__ inline philox_words philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
+        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
+        c1 = (uint32_t)p1;
+        c3 = (uint32_t)p0;
+        c0 = n0;
+        c2 = n2;
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+    return {c0, c1, c2, c3};
+}
+
+// the standard normal deviate of (seed, level, utterance, sample): the cosine branch of Box-Muller on two 53-bit uniforms
+__device__ inline double noise_deviate(uint64_t seed, uint32_t level, uint32_t utt, uint64_t i) {
+    const philox_words w = philox4x32_10((uint32_t)i, (uint32_t)(i >> 32), level, utt, (uint32_t)seed, (uint32_t)(seed >> 32));
+    const double u1 = ((double)(w.w0 >> 5) * 67108864.0 + (double)(w.w1 >> 6) + 1.0) * 0x1p-53;   // (0, 1]
+    const double u2 = ((double)(w.w2 >> 5) * 67108864.0 + (double)(w.w3 >> 6)) * 0x1p-53;         // [0, 1)
+    return sqrt(-2.0 * log(u1)) * cos(6.283185307179586 * u2);
+}
+
+// One thread per sample of one level (blockIdx.y strides over the levels): out[l * total + p] = clean[p] + sigma[l * B + b] * z,
+// product and sum rounded separately; where sigma is 0 (the clean level, an all-zero row) the sample itself, exactly.
+// Consecutive lanes write consecutive float64 values: 512 bytes per wave and store instruction.
+template <typename T>
+__global__ __launch_bounds__(NOISE_THREADS) void k_noise_levels(const T* __restrict__ wave, const int64_t* __restrict__ offsets,
+                                                                 const double* __restrict__ sigma, int B, int levels, int64_t total,
+                                                                 uint64_t seed, double* __restrict__ out) {
+#pragma clang fp contract(off)
+    for (int64_t p = (int64_t)blockIdx.x * NOISE_THREADS + threadIdx.x; p < total; p += (int64_t)gridDim.x * NOISE_THREADS) {
+        // utterance of sample p: the last b with offsets[b] <= p (empty utterances are stepped over)
+        int lo = 0, hi = B;
+        while (hi - lo > 1) {
+            const int mid = (lo + hi) >> 1;
+            if (offsets[mid] <= p) lo = mid; else hi = mid;
+        }
+        const int b = lo;
+        const uint64_t i = (uint64_t)(p - offsets[b]);
+        const double clean = (double)wave[p];
+        for (int l = blockIdx.y; l < levels; l += gridDim.y) {
+            const double s = sigma[(size_t)l * B + b];
+            double v = clean;
+            if (s != 0.0) {
+                const double nz = s * noise_deviate(seed, (uint32_t)l, (uint32_t)b, i);
+                v = clean + nz;
+            }
+            out[(size_t)l * (size_t)total + (size_t)p] = v;
+        }
+    }
+}
+
+// Workgroups (u, blockIdx.y) share the windows of utterance u = l * B + b; window j is held against window j of the clean level's
+// utterance K * B + b (the same count: the levels share their offsets). One pair of 64-bit integer atomics per workgroup that
+// counted something, on a zeroed buffer: integer sums do not depend on the order.
+__global__ __launch_bounds__(TALLY_THREADS) void k_label_tally(const uint8_t* __restrict__ labels, const int64_t* __restrict__ wo,
+                                                               int B, int K, unsigned long long* __restrict__ stats) {
+    __shared__ unsigned lds[TALLY_THREADS / 64];
+    const int u = blockIdx.x, b = u % B;
+    const int64_t first = wo[u], n = wo[u + 1] - first, first_clean = wo[(size_t)K * B + b];
+    unsigned rising = 0, agree = 0;
+    for (int64_t j = (int64_t)blockIdx.y * TALLY_THREADS + threadIdx.x; j < n; j += (int64_t)gridDim.y * TALLY_THREADS) {
+        const uint8_t mine = labels[first + j];
+        rising += mine != 0;
+        agree += mine == labels[first_clean + j];
+    }
+    const unsigned r = block_sum<unsigned, TALLY_THREADS>(rising, lds);
+    __syncthreads();
+    const unsigned a = block_sum<unsigned, TALLY_THREADS>(agree, lds);
+    if (threadIdx.x == 0) {
+        if (r) atomicAdd(&stats[2 * (size_t)u], (unsigned long long)r);
+        if (a) atomicAdd(&stats[2 * (size_t)u + 1], (unsigned long long)a);
+    }
+}
+
+}  // namespace
+
+int f2_launch_noise_sigma(f2_ctx* ctx, const void* d_wave, int wave_dtype, const int64_t* d_offsets, const double* d_lin, int B,
+                          int K, double* d_sigma) {
+    if (B == 0) return F2_OK;
+    if (wave_dtype == F2_WAVE_I16)
+        k_noise_sigma<int16_t><<<dim3(B), dim3(SIGMA_THREADS), 0, ctx->stream>>>((const int16_t*)d_wave, d_offsets, d_lin, B, K, d_sigma);
+    else
+        k_noise_sigma<double><<<dim3(B), dim3(SIGMA_THREADS), 0, ctx->stream>>>((const double*)d_wave, d_offsets, d_lin, B, K, d_sigma);
+    F2_HIP(ctx, hipGetLastError());
+    return F2_OK;
+}
+
+int f2_launch_noise_levels(f2_ctx* ctx, const void* d_wave, int wave_dtype, const int64_t* d_offsets, const double* d_sigma, int B,
+                           int K, int64_t total, uint64_t seed, double* d_out) {
+    if (B == 0 || total == 0) return F2_OK;
+    const int64_t blocks = (total + NOISE_THREADS - 1) / NOISE_THREADS;
+    const dim3 grid((unsigned)(blocks < (1 << 20) ? blocks : (1 << 20)), (unsigned)(K + 1 < 1024 ? K + 1 : 1024));
+    if (wave_dtype == F2_WAVE_I16)
+        k_noise_levels<int16_t><<<grid, dim3(NOISE_THREADS), 0, ctx->stream>>>((const int16_t*)d_wave, d_offsets, d_sigma, B, K + 1, total,
+                                                                              seed, d_out);
+    else
+        k_noise_levels<double><<<grid, dim3(NOISE_THREADS), 0, ctx->stream>>>((const double*)d_wave, d_offsets, d_sigma, B, K + 1, total,
+                                                                             seed, d_out);
+    F2_HIP(ctx, hipGetLastError());
+    return F2_OK;
+}
+
+int f2_launch_label_tally(f2_ctx* ctx, const uint8_t* d_labels, const int64_t* d_window_offsets, int B, int K, int64_t max_windows,
+                          int64_t* d_stats) {
+    if (B == 0 || max_windows == 0) return F2_OK;
+    const int64_t per = (max_windows + TALLY_THREADS - 1) / TALLY_THREADS;
+    const dim3 grid((unsigned)((int64_t)(K + 1) * B), (unsigned)(per < 64 ? per : 64));
+    k_label_tally<<<grid, dim3(TALLY_THREADS), 0, ctx->stream>>>(d_labels, d_window_offsets, B, K, (unsigned long long*)d_stats);
+    F2_HIP(ctx, hipGetLastError());
+    return F2_OK;
+}

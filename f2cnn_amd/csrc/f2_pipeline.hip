@@ -2,6 +2,7 @@
 // (scripts/CNN/Evaluating.py:42-87): host/device pointer handling, chunking, error flags. Host code only.
 #include "f2_internal.h"
 
+#include <algorithm>
 #include <cmath>
 
 namespace {
@@ -335,6 +336,12 @@ static int eval_batch_impl(f2_ctx* ctx, const f2_cnn* cnn, const void* wave, int
     return eval_cnn_end(ctx, cnn, &E, scores_or_null, labels_or_null);
 }
 
+// windows f2_eval_batch_strided evaluates in an utterance of n samples (R = 2 * radius + 1 rows)
+static int64_t strided_windows(int64_t n, int R, int step, int hop) {
+    const int64_t nb = n - (int64_t)R * step;
+    return nb > 0 ? (nb + hop - 1) / hop : 0;
+}
+
 // f2_eval_batch_strided: window j of utterance b is every-sample window j * hop. A chunk is up to CNN_CHUNK windows taken from
 // as many utterances as it holds (an utterance may continue in the next chunk): one window-stage launch set and one
 // convolution launch set per chunk, whatever B. (On the decimating route a chunk also closes at COLUMN_CAP columns of the
@@ -352,8 +359,7 @@ static int eval_strided_impl(f2_ctx* ctx, const f2_cnn* cnn, const void* wave, i
     int64_t n_total = 0;
     if (window_offsets_or_null) window_offsets_or_null[0] = 0;
     for (int b = 0; b < B; ++b) {
-        const int64_t nb = offsets[b + 1] - offsets[b] - (int64_t)E.R * step;
-        nbh[(size_t)b] = nb > 0 ? (nb + hop - 1) / hop : 0;
+        nbh[(size_t)b] = strided_windows(offsets[b + 1] - offsets[b], E.R, step, hop);
         n_total += nbh[(size_t)b];
         if (window_offsets_or_null) window_offsets_or_null[b + 1] = n_total;
     }
@@ -394,6 +400,92 @@ static int eval_strided_impl(f2_ctx* ctx, const f2_cnn* cnn, const void* wave, i
     return eval_cnn_end(ctx, cnn, &E, scores_or_null, labels_or_null);
 }
 
+// f2_eval_noise_sweep: the K noisy levels and the clean one of a ragged batch as ONE (K+1) * B-utterance float64 batch in device
+// memory (f2_noise.hip), through eval_strided_impl as a device call, then the tally of its labels on the device. Only the clean
+// samples go up; sigma, stats and what the caller asked for come back behind one wait.
+static int eval_noise_sweep_impl(f2_ctx* ctx, const f2_cnn* cnn, const void* wave, int wave_dtype, const int64_t* offsets,
+                                 const double* coefs, int B, int C, int lpf, double cutoff_hz, int fft_precision, int radius, int step,
+                                 int hop, const double* snr_db, int K, uint64_t seed, double* noisy_or_null, float* scores_or_null,
+                                 uint8_t* labels_or_null, int64_t* window_offsets_or_null, double* sigma_or_null,
+                                 int64_t* stats_or_null, int mem_space) {
+    eval_call E;
+    F2_TRY(eval_check(ctx, cnn, wave_dtype, offsets, coefs, B, C, lpf, cutoff_hz, fft_precision, radius, step, mem_space, &E));
+    F2_CHECK(ctx, hop >= 1, F2_ERR_INVALID, "hop must be at least 1 sample (got %d)", hop);
+    F2_CHECK(ctx, K >= 1 && snr_db, F2_ERR_INVALID, "a sweep needs at least one noise level (K=%d) and their snr_db", K);
+    for (int k = 0; k < K; ++k) F2_CHECK(ctx, std::isfinite(snr_db[k]), F2_ERR_INVALID, "snr_db[%d] is not finite", k);
+    F2_CHECK(ctx, ((int64_t)K + 1) * (B > 0 ? B : 1) <= INT32_MAX / 2, F2_ERR_UNSUPPORTED, "%d levels of %d utterances", K + 1, B);
+    F2_CHECK(ctx, wave || E.total == 0, F2_ERR_INVALID, "null wave");
+    const int U = (K + 1) * B;
+    const int64_t total = E.total;
+    // the (K+1) * B batch: the clean offsets tiled, its window offsets, 10^(snr / 10) per level
+    std::vector<int64_t> tiled((size_t)U + 1, 0), wo((size_t)U + 1, 0);
+    int64_t max_windows = 0;
+    for (int l = 0; l <= K; ++l)
+        for (int b = 0; b < B; ++b) {
+            const size_t u = (size_t)l * B + b;
+            const int64_t nw = strided_windows(offsets[b + 1] - offsets[b], E.R, step, hop);
+            tiled[u + 1] = (int64_t)l * total + offsets[b + 1];
+            wo[u + 1] = wo[u] + nw;
+            max_windows = nw > max_windows ? nw : max_windows;
+        }
+    const int64_t n_total = wo[(size_t)U];
+    if (window_offsets_or_null) memcpy(window_offsets_or_null, wo.data(), sizeof(int64_t) * ((size_t)U + 1));
+    if (total == 0) {   // nothing to launch: no noise and no window anywhere
+        if (sigma_or_null) std::fill(sigma_or_null, sigma_or_null + U, 0.0);
+        if (stats_or_null) std::fill(stats_or_null, stats_or_null + 2 * (size_t)U, (int64_t)0);
+        return F2_OK;
+    }
+    std::vector<double> lin((size_t)K);
+    for (int k = 0; k < K; ++k) lin[(size_t)k] = std::pow(10.0, snr_db[k] / 10.0);   // Evaluating.py:189 SNRdbToSNRlinear
+
+    // small arrays of the call: [sigma (U) | lin (K) | stats (2 U) | window offsets (U + 1)], all 8-byte words
+    F2_TRY(f2_reserve(ctx, ctx->noise_meta, 8 * ((size_t)U + K + 2 * (size_t)U + U + 1)));
+    double* d_sigma = (double*)ctx->noise_meta.ptr;
+    double* d_lin = d_sigma + U;
+    int64_t* d_stats = (int64_t*)(d_lin + K);
+    int64_t* d_wo = d_stats + 2 * (size_t)U;
+    const size_t noisy_bytes = sizeof(double) * (size_t)(K + 1) * (size_t)total;
+    double* d_noisy = noisy_or_null;
+    if (E.host || !noisy_or_null) {
+        F2_TRY(f2_reserve(ctx, ctx->noise_wave, noisy_bytes));
+        d_noisy = (double*)ctx->noise_wave.ptr;
+    }
+    // scores / labels of the device call below: the caller's device buffers, else staging (the tally always needs the labels)
+    float* d_scores = scores_or_null;
+    uint8_t* d_labels = labels_or_null;
+    if (E.host || !labels_or_null) {
+        const bool stage_scores = E.host && scores_or_null;
+        F2_TRY(f2_reserve(ctx, ctx->stage_aux, (stage_scores ? sizeof(float) * 2 : 0) * (size_t)n_total + (size_t)n_total + 64));
+        if (E.host) d_scores = stage_scores ? (float*)ctx->stage_aux.ptr : nullptr;
+        d_labels = (uint8_t*)ctx->stage_aux.ptr + (stage_scores ? sizeof(float) * 2 * (size_t)n_total : 0);
+    }
+    // the tiled offsets start with the clean ones: one device array serves the noise kernels and the evaluation
+    F2_TRY(f2_upload_offsets(ctx, tiled.data(), U));
+    F2_TRY(f2_upload_async(ctx, d_lin, lin.data(), sizeof(double) * (size_t)K));
+    const void* d_wave;
+    F2_TRY(f2_stage_wave(ctx, wave, wave_dtype, total, mem_space, &d_wave));
+    const int64_t* d_offsets = (const int64_t*)ctx->offsets.ptr;
+    F2_TRY(f2_launch_noise_sigma(ctx, d_wave, wave_dtype, d_offsets, d_lin, B, K, d_sigma));
+    F2_TRY(f2_launch_noise_levels(ctx, d_wave, wave_dtype, d_offsets, d_sigma, B, K, total, seed, d_noisy));
+    if (E.host && noisy_or_null) F2_HIP(ctx, hipMemcpyAsync(noisy_or_null, d_noisy, noisy_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    F2_TRY(eval_strided_impl(ctx, cnn, d_noisy, F2_WAVE_F64, tiled.data(), coefs, U, C, lpf, cutoff_hz, fft_precision, radius, step, hop,
+                             d_scores, d_labels, nullptr, F2_MEM_DEVICE));
+    F2_HIP(ctx, hipMemsetAsync(d_stats, 0, sizeof(int64_t) * 2 * (size_t)U, ctx->stream));
+    if (n_total > 0) {
+        F2_TRY(f2_upload_async(ctx, d_wo, wo.data(), sizeof(int64_t) * ((size_t)U + 1)));
+        F2_TRY(f2_launch_label_tally(ctx, d_labels, d_wo, B, K, max_windows, d_stats));
+        if (E.host && scores_or_null)
+            F2_HIP(ctx, hipMemcpyAsync(scores_or_null, d_scores, sizeof(float) * 2 * (size_t)n_total, hipMemcpyDeviceToHost, ctx->stream));
+        if (E.host && labels_or_null)
+            F2_HIP(ctx, hipMemcpyAsync(labels_or_null, d_labels, (size_t)n_total, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    if (sigma_or_null) F2_HIP(ctx, hipMemcpyAsync(sigma_or_null, d_sigma, sizeof(double) * (size_t)U, hipMemcpyDeviceToHost, ctx->stream));
+    if (stats_or_null)
+        F2_HIP(ctx, hipMemcpyAsync(stats_or_null, d_stats, sizeof(int64_t) * 2 * (size_t)U, hipMemcpyDeviceToHost, ctx->stream));
+    F2_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return F2_OK;
+}
+
 extern "C" {
 
 int f2_eval_utterance(f2_ctx* ctx, const f2_cnn* cnn, const void* wave, int wave_dtype, int64_t N, const double* coefs,
@@ -417,6 +509,16 @@ int f2_eval_batch_strided(f2_ctx* ctx, const f2_cnn* cnn, const void* wave, int 
                           int hop, float* scores_or_null, uint8_t* labels_or_null, int64_t* window_offsets_or_null, int mem_space) {
     return eval_strided_impl(ctx, cnn, wave, wave_dtype, offsets, coefs, B, C, lpf, cutoff_hz, fft_precision, radius, step, hop,
                              scores_or_null, labels_or_null, window_offsets_or_null, mem_space);
+}
+
+int f2_eval_noise_sweep(f2_ctx* ctx, const f2_cnn* cnn, const void* wave, int wave_dtype, const int64_t* offsets,
+                        const double* coefs, int B, int C, int lpf, double cutoff_hz, int fft_precision, int radius, int step,
+                        int hop, const double* snr_db, int K, uint64_t seed, double* noisy_or_null, float* scores_or_null,
+                        uint8_t* labels_or_null, int64_t* window_offsets_or_null, double* sigma_or_null, int64_t* stats_or_null,
+                        int mem_space) {
+    return eval_noise_sweep_impl(ctx, cnn, wave, wave_dtype, offsets, coefs, B, C, lpf, cutoff_hz, fft_precision, radius, step, hop,
+                                 snr_db, K, seed, noisy_or_null, scores_or_null, labels_or_null, window_offsets_or_null,
+                                 sigma_or_null, stats_or_null, mem_space);
 }
 
 int f2_input_batch(f2_ctx* ctx, const void* wave, int wave_dtype, const int64_t* offsets, const double* coefs, int B, int C,

@@ -250,3 +250,94 @@ def EvaluateWithNoise(file, LPF=False, CUTOFF=100, model='last_trained_model', C
     _save(target + '.F2CNN.npz', scores, labels, hop, len(noisy), framerate)
     print("\t\t{}\tdone !".format(file))
     return scores, labels
+
+
+def _snr_text(SNRdB):
+    """how a level is printed: 10.0 -> '10', -3.0 -> '-3', 2.5 -> '2.5'"""
+    return '{:g}'.format(float(SNRdB))
+
+
+def EvaluateNoiseSweep(files, SNRdBs, seed=0, hop=None, LPF=False, CUTOFF=50, model='last_trained_model', save_wavs=False,
+                       ctx=None):
+    """`cnn noisesweep` (not in the reference, whose EvaluateWithNoise :193-221 takes one file at one level): every file at
+    every level of SNRdBs and clean in one device pass per group of files (f2_eval_noise_sweep: the noise is drawn on the device
+    from (seed, level, file's place in its group, sample), so a sweep repeats bit for bit), with the clean run of the same
+    network as the referee. Per file, OutputWavFiles/addedNoise/<stem>.sweep.npz holds snr_db, sigma, windows, rising, agree,
+    agreement (= agree / windows, NaN without windows) - one entry per level, the clean level last - seed, hop and labels_<k>
+    for level k of snr_db (labels_clean for the clean one); one line per level is printed and the same data is returned as a dict per
+    file. save_wavs also writes <stem><SNR>dB.WAV with copies of the annotation files, as EvaluateWithNoise names and writes
+    them. Files are grouped like EvaluateRandom groups them: one framerate and sample type per call. hop=None is hop 1."""
+    import shutil
+    from scipy.io import wavfile
+    if isinstance(files, (str, bytes, os.PathLike)):
+        files = [files]
+    snr = numpy.asarray(SNRdBs, dtype=numpy.float64).reshape(-1)
+    if not len(snr) or not numpy.isfinite(snr).all():
+        raise ValueError("a noise sweep needs at least one finite SNR in dB")
+    K = len(snr)
+    hop = 1 if hop is None else int(hop)
+    ctx = ctx or _lib.default_context()
+    cfg = F2Config()
+    if not isinstance(model, F2CNNModel):
+        model = load_model(model)
+    loaded = [(file,) + tuple(GetArrayFromWAV(file)) for file in files]
+    groups = {}
+    for file, framerate, wavArray in loaded:
+        wave, dt = filters._wave_args(wavArray)
+        groups.setdefault((framerate, dt), []).append((file, wave))
+    keys = [str(k) for k in range(K)] + ['clean']          # labels_<k>: level k of snr_db
+    names = [_snr_text(v) + 'dB' for v in snr] + ['clean']
+    results = {}
+    BATCH = 16                                    # files per device pass, as EvaluateRandom
+    for (framerate, dt), members in groups.items():
+        coefs = numpy.ascontiguousarray(filters.make_erb_filters(framerate, filters.centre_freqs(framerate, cfg.nchannels,
+                                                                                                  cfg.low_freq)))
+        Cn = coefs.shape[0]
+        STEP = _step(framerate, cfg)
+        for s0 in range(0, len(members), BATCH):
+            group = members[s0:s0 + BATCH]
+            B = len(group)
+            offsets = numpy.zeros(B + 1, numpy.int64)
+            offsets[1:] = numpy.cumsum([w.shape[0] for _, w in group])
+            flat = numpy.concatenate([w for _, w in group])
+            nbh = [_lib.strided_window_count(w.shape[0], cfg.radius, STEP, hop) for _, w in group]
+            labels = numpy.empty((K + 1) * sum(nbh), numpy.uint8)
+            noisy = numpy.empty((K + 1) * int(offsets[-1]), numpy.float64) if save_wavs else None
+            try:
+                wo, sigma, stats = ctx.eval_noise_sweep(model.handle(ctx), flat, dt, offsets, coefs, B, Cn, bool(LPF),
+                                                        CUTOFF if LPF else 0.0, FFT_PRECISION, cfg.radius, STEP, hop, snr, seed,
+                                                        noisy, None, labels, _lib.MEM_HOST)
+            except _lib.F2Error as e:
+                if e.code == _lib.F2_ERR_NONPOSITIVE:
+                    raise ValueError("values must all be positive")
+                raise
+            assert list(numpy.diff(wo)) == nbh * (K + 1)
+            os.makedirs(os.path.join('OutputWavFiles', 'addedNoise'), exist_ok=True)
+            for b, (file, w) in enumerate(group):
+                rows = [l * B + b for l in range(K + 1)]
+                windows = numpy.array([wo[u + 1] - wo[u] for u in rows], numpy.int64)
+                rising, agree = stats[rows, 0].copy(), stats[rows, 1].copy()
+                with numpy.errstate(invalid='ignore', divide='ignore'):
+                    agreement = numpy.where(windows > 0, agree / windows.astype(numpy.float64), numpy.nan)
+                res = dict(snr_db=snr.copy(), sigma=sigma[rows].copy(), windows=windows, rising=rising, agree=agree,
+                           agreement=agreement, seed=numpy.uint64(int(seed) & (2 ** 64 - 1)), hop=numpy.int64(hop))
+                for key, u in zip(keys, rows):
+                    res['labels_' + key] = labels[wo[u]:wo[u + 1]].copy()
+                source, _ = _noisy_copy_paths(file, 0)
+                out = os.path.join('OutputWavFiles', 'addedNoise', os.path.basename(source) + '.sweep.npz')
+                numpy.savez(out, **res)
+                print("File:\t\t{}".format(file))
+                for l in range(K + 1):
+                    print("\tSNR {:>8}\t{} windows\t{} rising\tagreement with clean {:.4f}".format(
+                        names[l], windows[l], rising[l], agreement[l]))
+                if save_wavs:
+                    for l in range(K):
+                        _, target = _noisy_copy_paths(file, snr[l])
+                        lo = l * int(offsets[-1]) + int(offsets[b])
+                        wavfile.write(target + '.WAV', framerate, noisy[lo:lo + w.shape[0]])
+                        for ext in ('.FB', '.PHN', '.WRD'):
+                            if os.path.exists(source + ext):
+                                shutil.copyfile(source + ext, target + ext)
+                print("\t\t{}\tdone ! -> {}".format(file, out))
+                results[file] = res
+    return results

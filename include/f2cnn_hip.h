@@ -16,7 +16,8 @@
  *     upload (offsets, utterance lists, ...) are staged through page-locked memory owned by the
  *     context, so a new batch shape does not wait for the stream either. What does wait: a scratch
  *     buffer that has to grow (the first call of a size), and the calls that hand an error flag of
- *     the device back (f2_gather_windows with normalisation, f2_eval_*: F2_ERR_NONPOSITIVE).
+ *     the device back (f2_gather_windows with normalisation, f2_eval_*: F2_ERR_NONPOSITIVE;
+ *     f2_eval_noise_sweep also waits to hand back sigma and stats).
  *   - ragged batches: utterance b has n_b = offsets[b+1]-offsets[b] samples; its wave starts at
  *     wave + offsets[b]; its (C, n_b) C-order float64 matrix starts at out + C*offsets[b]. For a
  *     uniform batch this is the plain [B][C][N] layout, and each utterance's block is bit-for-bit the
@@ -63,7 +64,7 @@ enum { F2_FFT_F32 = 0, F2_FFT_F64 = 1 };
 int f2_version(void);   /* 100 * major + minor; 101 added f2_eval_batch, 102 f2_host_alloc + F2_MEM_HOST_ASYNC, 103 f2_ctx_set_option, 105 f2_spectral_guard_read + f2_cnn_get_info,
                            106 f2_cnn_forward accepts any finite input on the split path (scales from the input's range; the
                            f2_cnn_get_info keys "f16x3_ok", "f16x3_check_diff", "last_input_bound"), 107 f2_input_batch,
-                           108 f2_eval_batch_strided */
+                           108 f2_eval_batch_strided, 109 f2_eval_noise_sweep */
 int f2_device_count(int* count);
 int f2_ctx_create(int device, f2_ctx** ctx);
 int f2_ctx_destroy(f2_ctx* ctx);
@@ -292,6 +293,51 @@ int f2_eval_batch_strided(f2_ctx* ctx, const f2_cnn* cnn, const void* wave, int 
                           const double* coefs, int B, int C, int lpf, double cutoff_hz, int fft_precision, int radius,
                           int step, int hop, float* scores_or_null, uint8_t* labels_or_null,
                           int64_t* window_offsets_or_null /* host, B+1 */, int mem_space);
+
+/* ---- `cnn noisesweep`: one ragged batch at K noise levels and clean, in one device pass -----------------------------------
+ * scripts/CNN/Evaluating.py:193-221 (EvaluateWithNoise) adds Gaussian noise to one file at one SNR with NumPy on the host and
+ * evaluates the float64 result. This call forms K+1 "levels" of the clean batch on the device - level k < K is every utterance
+ * plus its own noise at snr_db[k], level K the clean batch converted to float64 (exact for int16) - evaluates them as ONE
+ * (K+1)*B-utterance float64 batch and counts, on the device, how the labels of every level compare with the clean level's.
+ * Only the clean samples are uploaded. Level l, utterance b is utterance u = l*B + b of that batch; its offsets are the clean
+ * offsets tiled: tiled[u] = l*offsets[B] + offsets[b].
+ *   sigma   sigma[u] = RMS(clean_b) / 10^(snr_db[l] / 10): the reference's scaling (Evaluating.py:199), a power ratio where an
+ *           amplitude ratio belongs, reproduced and not corrected. 0 for level K and for an empty utterance. F2_WAVE_I16: the
+ *           squares are summed in int64 (exact), RMS = sqrt((double)sum / n) - the bits of numpy.sqrt(numpy.mean(numpy.square(
+ *           float64 samples))). F2_WAVE_F64: a float64 sum in a fixed order (no floating-point atomics): the same bits on every
+ *           call. 10^(snr_db / 10) is the host's pow().
+ *   noise   sample i (counted from the utterance's first sample) of utterance u becomes clean + sigma[u] * z (product and sum
+ *           rounded separately) with z = sqrt(-2 ln u1) * cos(2 pi u2),
+ *             (w0, w1, w2, w3) = Philox4x32-10(counter = (i & 0xffffffff, i >> 32, l, b), key = (seed & 0xffffffff, seed >> 32))
+ *             u1 = ((w0 >> 5) * 2^26 + (w1 >> 6) + 1) * 2^-53   in (0, 1]
+ *             u2 = ((w2 >> 5) * 2^26 + (w3 >> 6)) * 2^-53       in [0, 1)
+ *           Philox with the standard constants (multipliers 0xD2511F53 / 0xCD9E8D57, key increments 0x9E3779B9 / 0xBB67AE85);
+ *           everything after the 32-bit words in float64; 2 pi = 6.283185307179586. One Philox call serves one sample and the
+ *           sine twin is discarded, so a sample depends on (seed, level, utterance, i) alone - not on the launch shape, the
+ *           batch around it or the machine (up to the device's log / sqrt / cos, a few ulp). A level whose sigma is 0 is the
+ *           clean samples exactly.
+ *   noisy_or_null   (K+1) * offsets[B] float64, level-major, in mem_space: the waveforms that were evaluated (a device buffer
+ *                   serves as the call's own buffer; otherwise they live in context scratch)
+ *   scores_or_null, labels_or_null, window_offsets_or_null (host, (K+1)*B + 1)
+ *           bit for bit what f2_eval_batch_strided(F2_WAVE_F64) returns for the (K+1)*B batch `noisy` with the tiled offsets
+ *           and the same coefs ... hop: it is that call's code on that buffer. window_offsets is filled whenever the arguments
+ *           pass.
+ *   sigma_or_null   host, (K+1)*B
+ *   stats_or_null   host, (K+1)*B*2: stats[2u] = windows of u labelled rising, stats[2u+1] = windows of u whose label equals
+ *           the clean level's label for the same window of the same utterance (for level K: its window count). Counted by a
+ *           kernel over the device's label array (workgroup sums, then vector integer atomics on a zeroed buffer), also when
+ *           labels_or_null is NULL.
+ * Errors: everything f2_eval_batch_strided rejects, by the same checks and before anything is launched or written; K < 1, a
+ * NULL snr_db or a non-finite snr_db[k]: F2_ERR_INVALID. F2_ERR_NONPOSITIVE as in the strided call (only evaluated windows).
+ * B == 0, or no utterance long enough for a window: F2_OK with window_offsets / sigma / stats filled. The call waits for the
+ * stream before it returns (it hands back sigma, stats and the error flag), whatever mem_space is.
+ */
+int f2_eval_noise_sweep(f2_ctx* ctx, const f2_cnn* cnn, const void* wave, int wave_dtype, const int64_t* offsets,
+                        const double* coefs, int B, int C, int lpf, double cutoff_hz, int fft_precision, int radius,
+                        int step, int hop, const double* snr_db /* host, K */, int K, uint64_t seed,
+                        double* noisy_or_null, float* scores_or_null, uint8_t* labels_or_null,
+                        int64_t* window_offsets_or_null /* host, (K+1)*B + 1 */, double* sigma_or_null /* host, (K+1)*B */,
+                        int64_t* stats_or_null /* host, (K+1)*B*2 */, int mem_space);
 
 #ifdef __cplusplus
 }
