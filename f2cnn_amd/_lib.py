@@ -65,6 +65,7 @@ SIGNATURES = {
     "f2_eval_batch_strided": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _d, _i, _i, _i, _i, _vp, _vp, _vp, _i]),
     "f2_eval_noise_sweep": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _d, _i, _i, _i, _i, _vp, _i, C.c_uint64, _vp, _vp, _vp,
                                  _vp, _vp, _vp, _i]),
+    "f2_label_accuracy": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i64, _i, _i, _vp, _i]),
 }
 
 _lib = None
@@ -392,6 +393,29 @@ class Context:
                                                 _ptr(scores), _ptr(labels), _ptr(window_offsets), _ptr(sigma), _ptr(stats),
                                                 mem_space))
         return window_offsets, sigma, stats
+
+    def label_accuracy(self, labels, window_offsets, ref_offsets, ref_timepoints, ref_signs, origin, hop, step, mem_space,
+                       counts=None):
+        """The labels of a strided evaluation against reference labels (see f2_label_accuracy): utterance u owns rows
+        window_offsets[u] .. window_offsets[u + 1] of `labels` (uint8 numpy array or device pointer, by mem_space), row j at
+        sample origin + j * hop, and is scored against reference set u % R - timepoints (int64, strictly increasing) and signs
+        (uint8, 0 / 1) between ref_offsets[r] and ref_offsets[r + 1]. Returns the (U, 2, 2) int64 confusion matrices
+        [utterance][reference sign][label] of the counted rows (written into `counts` when given)."""
+        window_offsets = np.ascontiguousarray(window_offsets, dtype=np.int64)
+        ref_offsets = np.ascontiguousarray(ref_offsets, dtype=np.int64)
+        ref_timepoints = np.ascontiguousarray(ref_timepoints, dtype=np.int64)
+        ref_signs = np.ascontiguousarray(ref_signs, dtype=np.uint8)
+        if isinstance(labels, np.ndarray):
+            labels = np.ascontiguousarray(labels, dtype=np.uint8)
+        U, R = len(window_offsets) - 1, len(ref_offsets) - 1
+        if counts is None:
+            counts = np.zeros((U, 2, 2), np.int64)
+        if counts.dtype != np.int64 or counts.size != 4 * U or not counts.flags["C_CONTIGUOUS"]:
+            raise ValueError("counts must be contiguous int64 (U, 2, 2)")
+        self.check(self.lib.f2_label_accuracy(self.handle, _ptr(labels), _ptr(window_offsets), U, _ptr(ref_offsets),
+                                              _ptr(ref_timepoints), _ptr(ref_signs), R, int(origin), int(hop), int(step),
+                                              _ptr(counts), mem_space))
+        return counts.reshape(U, 2, 2)
 
 
 def strided_window_count(n, radius, step, hop):

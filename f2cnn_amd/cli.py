@@ -19,6 +19,10 @@ package implements:
                                                              with the clean decisions per level; not in the reference)
     python -m f2cnn_amd cnn evalrand [--count/-c N] [--lpf HZ] [--model/-m NPZ] [--hop N|frame]
     (--hop: a decision every N samples instead of every sample, `frame` = one per STEP of configF2CNN.conf; not in the reference)
+    (eval / evalnoise / evalrand / noisesweep also take --accuracy [reference|centre]: the decisions against the labels of the
+     source file's .FB / .PHN, as the reference's EvaluateOneWavArray ends - per file, per noise level, and for evalrand over
+     the corpus. `reference`, also the bare flag, compares the row index times the hop with the label timepoint as the
+     reference does; `centre` compares the row's centre sample, RADIUS * STEP further on)
     python -m f2cnn_amd --configure            (writes configF2CNN.conf with the reference's defaults)
 
 organize / plot need the licensed TIMIT+VTR corpora or matplotlib and stay with the reference.
@@ -90,6 +94,12 @@ def build_parser():
     c.add_argument('--seed', action='store', type=int, dest='seed', help="noisesweep: seed of the noise (default 0)")
     c.add_argument('--save-wavs', action='store_true', dest='save_wavs',
                    help="noisesweep: also write the noisy WAV files, as evalnoise does")
+    # (absent from the parsed arguments unless given: the commands parse as before without it)
+    c.add_argument('--accuracy', nargs='?', choices=('reference', 'centre'), const='reference', default=argparse.SUPPRESS,
+                   dest='accuracy',
+                   help="eval / evalnoise / evalrand / noisesweep: accuracy against the labels of the file's .FB / .PHN; "
+                        "'reference' (the bare flag) compares the row index with the label timepoint as the reference does, "
+                        "'centre' the row's centre sample")
     return parser
 
 
@@ -153,6 +163,8 @@ def main(argv=None):
             if args.hop == 'frame':
                 from .config import F2Config
                 kwargs['hop'] = F2Config().step
+        if getattr(args, 'accuracy', None) is not None:
+            kwargs['accuracy'] = args.accuracy
         if args.cnn_command == 'evalrand':                     # needs no --file (unreachable in the reference CLI)
             if args.count is not None:
                 kwargs['count'] = args.count

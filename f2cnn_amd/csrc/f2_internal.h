@@ -46,6 +46,7 @@ struct f2_ctx {
     f2_scratch dense_in;   // conv4 outputs (+ dense1 outputs) of the windows of several utterances: one dense launch for all
     f2_scratch noise_wave; // f2_eval_noise_sweep: the (K+1) x batch float64 waveform when the caller gives no device buffer for it
     f2_scratch noise_meta; // ... and its small arrays: sigma, 10^(snr / 10) per level, stats, window offsets
+    f2_scratch acc_meta;   // f2_label_accuracy: counts, window offsets, reference offsets / timepoints / signs
     f2_scratch gather_log; // ln of the envelope samples a chunk of every-sample windows touches + column min / max (f2_gather.hip)
     f2_scratch tw[2][16];  // FFT twiddle tables, [precision][log2 H], built on first use
     f2_scratch tw_fl[16];         // twiddle tables of f2_envelope_flagged.hip, by log2 H
@@ -389,5 +390,12 @@ int f2_launch_noise_levels(f2_ctx* ctx, const void* d_wave, int wave_dtype, cons
 // per utterance of the (K + 1) * B batch whose window offsets are d_window_offsets; max_windows: the most any utterance has
 int f2_launch_label_tally(f2_ctx* ctx, const uint8_t* d_labels, const int64_t* d_window_offsets, int B, int K, int64_t max_windows,
                           int64_t* d_stats);
+// f2_accuracy.hip, the kernel of f2_label_accuracy. d_counts (4 per utterance, zeroed by the caller)[4 u + 2 ref + pred] += rows
+// of utterance u (rows d_window_offsets[u] .. [u + 1] of d_labels, row j at sample origin + j * hop) that the rule of the header
+// counts against reference set u % R (d_ref_offsets: R + 1; timepoints strictly increasing inside a set, signs 0 / 1);
+// max_rows: the most any utterance has
+int f2_launch_label_accuracy(f2_ctx* ctx, const uint8_t* d_labels, const int64_t* d_window_offsets, int U, const int64_t* d_ref_offsets,
+                             const int64_t* d_ref_timepoints, const uint8_t* d_ref_signs, int R, int64_t origin, int hop, int step,
+                             int64_t max_rows, int64_t* d_counts);
 size_t f2_cnn_flat_floats(const f2_cnn* cnn);    // floats per window of the conv4 output
 size_t f2_cnn_dense_floats(const f2_cnn* cnn);   // ... plus dense1's output

@@ -521,6 +521,61 @@ int f2_eval_noise_sweep(f2_ctx* ctx, const f2_cnn* cnn, const void* wave, int wa
                                  sigma_or_null, stats_or_null, mem_space);
 }
 
+int f2_label_accuracy(f2_ctx* ctx, const uint8_t* labels, const int64_t* window_offsets, int U, const int64_t* ref_offsets,
+                      const int64_t* ref_timepoints, const uint8_t* ref_signs, int R, int64_t origin, int hop, int step,
+                      int64_t* counts, int mem_space) {
+    F2_TRY(f2_check_ctx(ctx));
+    F2_TRY(f2_check_mem_space(ctx, mem_space, false));
+    F2_CHECK(ctx, counts, F2_ERR_INVALID, "counts is NULL");
+    F2_CHECK(ctx, U >= 0 && R >= (U > 0 ? 1 : 0) && (U == 0 || U % R == 0), F2_ERR_INVALID,
+             "%d utterances cannot be scored against %d reference sets in turn", U, R);
+    F2_CHECK(ctx, hop >= 1 && step >= 1 && origin >= 0, F2_ERR_INVALID, "hop (%d) and step (%d) must be at least 1, origin (%lld) at least 0",
+             hop, step, (long long)origin);
+    F2_TRY(f2_check_offsets(ctx, window_offsets, U, "window_offsets"));
+    F2_TRY(f2_check_offsets(ctx, ref_offsets, R, "ref_offsets"));
+    const int64_t n_rows = window_offsets[U], M = ref_offsets[R];
+    F2_CHECK(ctx, labels || n_rows == 0, F2_ERR_INVALID, "null labels");
+    F2_CHECK(ctx, (ref_timepoints && ref_signs) || M == 0, F2_ERR_INVALID, "null ref_timepoints or ref_signs");
+    for (int r = 0; r < R; ++r)
+        for (int64_t i = ref_offsets[r]; i < ref_offsets[r + 1]; ++i) {
+            F2_CHECK(ctx, i == ref_offsets[r] || ref_timepoints[i] > ref_timepoints[i - 1], F2_ERR_INVALID,
+                     "reference set %d: timepoints must be strictly increasing (label %lld)", r, (long long)(i - ref_offsets[r]));
+            F2_CHECK(ctx, ref_signs[i] <= 1, F2_ERR_INVALID, "reference set %d: sign %d of label %lld is neither 0 nor 1", r,
+                     (int)ref_signs[i], (long long)(i - ref_offsets[r]));
+        }
+    int64_t max_rows = 0;
+    for (int u = 0; u < U; ++u) max_rows = std::max(max_rows, window_offsets[u + 1] - window_offsets[u]);
+    int64_t t_last = 0;   // the timepoint of the last row of the longest utterance has to be an int64
+    F2_CHECK(ctx, max_rows == 0 || (!__builtin_mul_overflow(max_rows - 1, (int64_t)hop, &t_last) && !__builtin_add_overflow(t_last, origin, &t_last)),
+             F2_ERR_UNSUPPORTED, "row %lld at hop %d from origin %lld is beyond int64", (long long)(max_rows - 1), hop, (long long)origin);
+    std::fill(counts, counts + 4 * (size_t)U, (int64_t)0);
+    if (n_rows == 0) return F2_OK;
+
+    // small arrays of the call: [counts (4 U) | window offsets (U + 1) | reference offsets (R + 1) | timepoints (M)] in 8-byte
+    // words, then the M signs
+    F2_TRY(f2_reserve(ctx, ctx->acc_meta, 8 * (4 * (size_t)U + U + 1 + R + 1 + (size_t)M) + (size_t)M));
+    int64_t* d_counts = (int64_t*)ctx->acc_meta.ptr;
+    int64_t* d_wo = d_counts + 4 * (size_t)U;
+    int64_t* d_ro = d_wo + U + 1;
+    int64_t* d_rt = d_ro + R + 1;
+    uint8_t* d_rs = (uint8_t*)(d_rt + M);
+    const uint8_t* d_labels = labels;
+    if (mem_space == F2_MEM_HOST) {
+        F2_TRY(f2_reserve(ctx, ctx->stage_in, (size_t)n_rows));
+        F2_HIP(ctx, hipMemcpyAsync(ctx->stage_in.ptr, labels, (size_t)n_rows, hipMemcpyHostToDevice, ctx->stream));
+        d_labels = (const uint8_t*)ctx->stage_in.ptr;
+    }
+    F2_HIP(ctx, hipMemsetAsync(d_counts, 0, sizeof(int64_t) * 4 * (size_t)U, ctx->stream));
+    F2_TRY(f2_upload_async(ctx, d_wo, window_offsets, sizeof(int64_t) * ((size_t)U + 1)));
+    F2_TRY(f2_upload_async(ctx, d_ro, ref_offsets, sizeof(int64_t) * ((size_t)R + 1)));
+    F2_TRY(f2_upload_async(ctx, d_rt, ref_timepoints, sizeof(int64_t) * (size_t)M));
+    F2_TRY(f2_upload_async(ctx, d_rs, ref_signs, (size_t)M));
+    F2_TRY(f2_launch_label_accuracy(ctx, d_labels, d_wo, U, d_ro, d_rt, d_rs, R, origin, hop, step, max_rows, d_counts));
+    F2_HIP(ctx, hipMemcpyAsync(counts, d_counts, sizeof(int64_t) * 4 * (size_t)U, hipMemcpyDeviceToHost, ctx->stream));
+    F2_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return F2_OK;
+}
+
 int f2_input_batch(f2_ctx* ctx, const void* wave, int wave_dtype, const int64_t* offsets, const double* coefs, int B, int C,
                    int lpf, double cutoff_hz, int fft_precision, const int64_t* center_offsets, const int64_t* centers,
                    int radius, int step, int normalize, float* windows, int mem_space) {

@@ -1,8 +1,14 @@
 """Drop-in for the hot-path part of the reference's ``scripts/CNN/Evaluating.py``: WAV -> filterbank ->
 envelope -> every-sample 11xC windows -> normalise -> CNN -> rising/falling label per sample
-(``EvaluateOneWavArray`` :42-87, ``EvaluateOneWavFile`` :116-135). Accuracy against VTR labels and the
-plots (:89-113) need the TIMIT/VTR side files and are outside this path; the scores and labels are
-returned and saved next to the WAV instead.
+(``EvaluateOneWavArray`` :42-87, ``EvaluateOneWavFile`` :116-135). The plots (:109-113) are outside this path; the
+scores and labels are returned and saved next to the WAV instead.
+
+``accuracy='reference'|'centre'`` (``cnn eval|evalnoise|evalrand|noisesweep --accuracy [MODE]``) is the end of the reference's
+``EvaluateOneWavArray`` (:38-40, :92-108): the decisions held against the labels ``LabelDataGenerator.ExtractLabel`` derives
+from the SOURCE file's ``.FB`` / ``.PHN``, counted on the device (``f2_label_accuracy``, where the rule is written out). A row
+within a STEP of a label timepoint is counted and takes the sign of the nearer label. ``reference`` compares the row's index
+times the hop with the label timepoint, as the reference does (its own TODO: the index is not the row's centre sample);
+``centre`` compares the row's true centre sample, radius*STEP further on. The default, ``accuracy=None``, changes nothing.
 
 ``hop=N`` (``cnn eval|evalnoise|evalrand --hop N``; not in the reference) evaluates every N-th of those windows only -
 row j is every-sample row j*N, bit for bit (``f2_eval_batch_strided``) - and the ``.F2CNN.npz`` then also holds ``hop`` and
@@ -23,15 +29,95 @@ def _step(framerate, cfg):
     return int(framerate * cfg.sampling_period * (1 / 1000000.))
 
 
-def _save(out, scores, labels, hop, N, framerate):
-    """<base>.F2CNN.npz: scores and labels; with a hop also the hop and the centre sample of every row"""
+def _save(out, scores, labels, hop, N, framerate, extra=None):
+    """<base>.F2CNN.npz: scores and labels; with a hop also the hop and the centre sample of every row; `extra`: the
+    accuracy keys of _accuracy_keys"""
+    extra = extra or {}
     if hop is None:
-        numpy.savez(out, scores=scores, labels=labels)
+        numpy.savez(out, scores=scores, labels=labels, **extra)
         return
     cfg = F2Config()
     timepoints = _lib.strided_timepoints(N, cfg.radius, _step(framerate, cfg), hop)
     assert len(timepoints) == len(labels)
-    numpy.savez(out, scores=scores, labels=labels, hop=numpy.int64(hop), timepoints=timepoints)
+    numpy.savez(out, scores=scores, labels=labels, hop=numpy.int64(hop), timepoints=timepoints, **extra)
+
+
+# ---- accuracy against the VTR labels (reference scripts/CNN/Evaluating.py:38-40, 92-108) -----------------------------
+ACCURACY_MODES = ('reference', 'centre')
+
+
+def ReferenceLabels(wavFile):
+    """(timepoints int64, signs uint8) of the rows LabelDataGenerator.ExtractLabel gives for the file, or None when its
+    .FB / .PHN side files are missing or give no rows (the reference's `labels is None`, :39-40)."""
+    from configparser import ConfigParser
+    from ...config import CONFIG_NAME
+    from ..processing.LabelDataGenerator import CSV_COLUMNS, ExtractLabel
+    config = ConfigParser()
+    config.read_dict({'CNN': {'FORMANT': '2', 'RADIUS': '5', 'RISK': '0.05', 'SAMPLING_PERIOD': '10000'}})   # configure.py's answers
+    config.read(CONFIG_NAME)
+    rows = ExtractLabel(wavFile, config)
+    if not rows:
+        return None
+    t, s = CSV_COLUMNS.index('timepoint'), CSV_COLUMNS.index('sign')
+    return (numpy.array([row[t] for row in rows], numpy.int64), numpy.array([row[s] for row in rows], numpy.uint8))
+
+
+def _accuracy_origin(accuracy, radius, STEP):
+    """the sample row 0 is compared at: 0 as in the reference, or the row's centre"""
+    if accuracy not in ACCURACY_MODES:
+        raise ValueError("accuracy must be None, 'reference' or 'centre', not {!r}".format(accuracy))
+    return 0 if accuracy == 'reference' else radius * STEP
+
+
+def _accuracy_of(confusion):
+    """correct / counted of confusion matrices (..., 2, 2) [ref][pred]; NaN where nothing is counted (the reference divides
+    by zero there)"""
+    confusion = numpy.asarray(confusion)
+    correct = numpy.trace(confusion, axis1=-2, axis2=-1).astype(numpy.float64)
+    counted = confusion.sum(axis=(-2, -1)).astype(numpy.float64)
+    with numpy.errstate(invalid='ignore', divide='ignore'):
+        return numpy.asarray(numpy.where(counted > 0, correct / counted, numpy.nan), numpy.float64)
+
+
+def _confusions(ctx, labels, window_offsets, refs, accuracy, hop, STEP):
+    """(U, 2, 2) int64 [utterance][ref][pred] of host labels (concatenated, utterance u in window_offsets[u] .. [u + 1])
+    against refs, one (timepoints, signs) or None per reference set; utterance u is scored against refs[u % len(refs)] (nothing
+    is counted against a None). One device pass (f2_label_accuracy)."""
+    cfg = F2Config()
+    sets = [r if r is not None else (numpy.zeros(0, numpy.int64), numpy.zeros(0, numpy.uint8)) for r in refs]
+    ref_offsets = numpy.zeros(len(sets) + 1, numpy.int64)
+    ref_offsets[1:] = numpy.cumsum([len(t) for t, _ in sets])
+    return ctx.label_accuracy(labels, window_offsets, ref_offsets, numpy.concatenate([t for t, _ in sets]),
+                              numpy.concatenate([s for _, s in sets]), _accuracy_origin(accuracy, cfg.radius, STEP),
+                              1 if hop is None else hop, STEP, _lib.MEM_HOST)
+
+
+def _no_side_files(file):
+    print("\t\t{}\tno labels from .FB / .PHN side files: no accuracy".format(file))
+
+
+def _accuracy_keys(confusion, accuracy):
+    """what a per-file .F2CNN.npz gains"""
+    return dict(accuracy=numpy.float64(_accuracy_of(confusion)), confusion=numpy.asarray(confusion, numpy.int64),
+                accuracy_mode=numpy.str_(accuracy))
+
+
+def _print_accuracy(what, confusion, accuracy):
+    print("\t\t{}\taccuracy against the VTR labels ({}): {:.4f} ({} of {} counted rows)".format(
+        what, accuracy, float(_accuracy_of(confusion)), int(numpy.trace(confusion)), int(confusion.sum())))
+
+
+def _file_accuracy(file, labels, accuracy, hop, framerate, ctx=None):
+    """The accuracy keys of one file's labels against the labels of `file`'s side files ({} without them), printed."""
+    _accuracy_origin(accuracy, 0, 0)      # (the mode is checked before anything is read)
+    ref = ReferenceLabels(file)
+    if ref is None:
+        _no_side_files(file)
+        return {}
+    confusion = _confusions(ctx or _lib.default_context(), labels, [0, len(labels)], [ref], accuracy, hop,
+                            _step(framerate, F2Config()))[0]
+    _print_accuracy(file, confusion, accuracy)
+    return _accuracy_keys(confusion, accuracy)
 
 
 def EvaluateOneWavArray(wavArray, framerate, wavFileName=None, model='last_trained_model', LPF=False, CUTOFF=100,
@@ -83,9 +169,9 @@ def EvaluateOneWavArray(wavArray, framerate, wavFileName=None, model='last_train
 
 
 def EvaluateOneWavFile(file, LPF=False, CUTOFF=50, model='last_trained_model', CENTER_FREQUENCIES=None,
-                       FILTERBANK_COEFFICIENTS=None, hop=None):
-    """`cnn eval --file X.WAV [--hop N]`: writes <base>.F2CNN.npz (scores, labels; with a hop also hop, timepoints) and
-    returns (scores, labels)."""
+                       FILTERBANK_COEFFICIENTS=None, hop=None, accuracy=None):
+    """`cnn eval --file X.WAV [--hop N] [--accuracy [MODE]]`: writes <base>.F2CNN.npz (scores, labels; with a hop also hop,
+    timepoints; with accuracy= and the file's .FB / .PHN also accuracy, confusion, accuracy_mode) and returns (scores, labels)."""
     print('Using model', model if not isinstance(model, F2CNNModel) else '<in-memory model>')
     print("File:\t\t{}".format(file))
     framerate, wavArray = GetArrayFromWAV(file)
@@ -93,7 +179,8 @@ def EvaluateOneWavFile(file, LPF=False, CUTOFF=50, model='last_trained_model', C
                                          CENTER_FREQUENCIES=CENTER_FREQUENCIES,
                                          FILTERBANK_COEFFICIENTS=FILTERBANK_COEFFICIENTS, hop=hop)
     out = os.path.splitext(file)[0] + '.F2CNN.npz'
-    _save(out, scores, labels, hop, len(wavArray), framerate)
+    extra = _file_accuracy(file, labels, accuracy, hop, framerate) if accuracy is not None else None
+    _save(out, scores, labels, hop, len(wavArray), framerate, extra)
     rising = int(labels.sum())
     print("\t\t{}\tdone ! {} windows: {} rising, {} falling -> {}".format(file, len(labels), rising,
                                                                           len(labels) - rising, out))
@@ -150,11 +237,12 @@ def EvaluateWavArrays(wavArrays, framerate, model='last_trained_model', LPF=Fals
     return out
 
 
-def EvaluateRandom(count=None, LPF=False, CUTOFF=50, model='last_trained_model', hop=None):
+def EvaluateRandom(count=None, LPF=False, CUTOFF=50, model='last_trained_model', hop=None, accuracy=None):
     """`cnn evalrand`: evaluate the WAV files under resources/f2cnn/*/ in random order (all of them, or `count`
     drawn with replacement like numpy.random.choice in the reference). The filterbank is designed once and the model
     is uploaded once (the reference reloads the Keras model for every file). With a hop each group of files is one
-    strided call."""
+    strided call. With accuracy= every file that has its .FB / .PHN is scored against them - a group in one device pass - and
+    the corpus total is printed from the summed confusion matrices."""
     import glob
     import time
     TotalTime = time.time()
@@ -174,6 +262,9 @@ def EvaluateRandom(count=None, LPF=False, CUTOFF=50, model='last_trained_model',
     elif count > 1:
         wavFiles = list(numpy.random.choice(wavFiles, count))
     results = {}
+    if accuracy is not None:
+        _accuracy_origin(accuracy, 0, 0)
+        corpus = numpy.zeros((2, 2), numpy.int64)
     BATCH = 16                                    # files per device pass
     for s0 in range(0, len(wavFiles), BATCH):
         group = wavFiles[s0:s0 + BATCH]
@@ -187,14 +278,31 @@ def EvaluateRandom(count=None, LPF=False, CUTOFF=50, model='last_trained_model',
                                         FILTERBANK_COEFFICIENTS=FILTERBANK_COEFFICIENTS if fr == cfg.framerate else None,
                                         hop=hop)
                     for file, (fr, w) in zip(group, loaded)]
-        for file, (fr, w), (scores, labels) in zip(group, loaded, outs):
+        extras = [None] * len(group)
+        if accuracy is not None:
+            refs = [ReferenceLabels(file) for file in group]
+            for file in [file for file, ref in zip(group, refs) if ref is None]:
+                _no_side_files(file)
+            # one pass per framerate of the group (the step is in samples of the file)
+            for rate in sorted({fr for (fr, _), ref in zip(loaded, refs) if ref is not None}):
+                members = [i for i, ((fr, _), ref) in enumerate(zip(loaded, refs)) if fr == rate and ref is not None]
+                wo = numpy.concatenate([[0], numpy.cumsum([len(outs[i][1]) for i in members])]).astype(numpy.int64)
+                confusions = _confusions(_lib.default_context(), numpy.concatenate([outs[i][1] for i in members]), wo,
+                                         [refs[i] for i in members], accuracy, hop, _step(rate, cfg))
+                for i, confusion in zip(members, confusions):
+                    _print_accuracy(group[i], confusion, accuracy)
+                    extras[i] = _accuracy_keys(confusion, accuracy)
+                    corpus += confusion
+        for file, (fr, w), (scores, labels), extra in zip(group, loaded, outs, extras):
             out = os.path.splitext(file)[0] + '.F2CNN.npz'
-            _save(out, scores, labels, hop, len(w), fr)
+            _save(out, scores, labels, hop, len(w), fr, extra)
             rising = int(labels.sum())
             print("\t\t{}\tdone ! {} windows: {} rising, {} falling -> {}".format(file, len(labels), rising,
                                                                                   len(labels) - rising, out))
             results[file] = (scores, labels)
     print("Evaluating network on all files.")
+    if accuracy is not None:
+        _print_accuracy("all files", corpus, accuracy)
     print('              Total time:', time.time() - TotalTime)
     print('')
     return results
@@ -225,11 +333,12 @@ def add_gaussian_noise(wave, SNRdB, rng=None):
 
 
 def EvaluateWithNoise(file, LPF=False, CUTOFF=100, model='last_trained_model', CENTER_FREQUENCIES=None,
-                      FILTERBANK_COEFFICIENTS=None, SNRdB=-3, rng=None, hop=None):
+                      FILTERBANK_COEFFICIENTS=None, SNRdB=-3, rng=None, hop=None, accuracy=None):
     """`cnn evalnoise` (reference: scripts/CNN/Evaluating.py:193-221): the file plus Gaussian noise at the requested level is
     written next to copies of its annotation files under OutputWavFiles/addedNoise/ and the float64 waveform is evaluated by
     the device pipeline. Returns (scores, labels) and also leaves them in <target>.F2CNN.npz; `rng` (a numpy Generator or
-    RandomState) makes the noise reproducible - the reference draws from the global numpy state."""
+    RandomState) makes the noise reproducible - the reference draws from the global numpy state. With accuracy= the noisy
+    run is scored against the labels of the clean file's .FB / .PHN (what the copies under addedNoise/ are there for)."""
     import shutil
     from scipy.io import wavfile
     print("File:\t\t{}".format(file))
@@ -247,7 +356,8 @@ def EvaluateWithNoise(file, LPF=False, CUTOFF=100, model='last_trained_model', C
     scores, labels = EvaluateOneWavArray(noisy, framerate, target + '.WAV', model=model, LPF=LPF, CUTOFF=CUTOFF,
                                          CENTER_FREQUENCIES=CENTER_FREQUENCIES,
                                          FILTERBANK_COEFFICIENTS=FILTERBANK_COEFFICIENTS, hop=hop)
-    _save(target + '.F2CNN.npz', scores, labels, hop, len(noisy), framerate)
+    extra = _file_accuracy(file, labels, accuracy, hop, framerate) if accuracy is not None else None
+    _save(target + '.F2CNN.npz', scores, labels, hop, len(noisy), framerate, extra)
     print("\t\t{}\tdone !".format(file))
     return scores, labels
 
@@ -258,7 +368,7 @@ def _snr_text(SNRdB):
 
 
 def EvaluateNoiseSweep(files, SNRdBs, seed=0, hop=None, LPF=False, CUTOFF=50, model='last_trained_model', save_wavs=False,
-                       ctx=None):
+                       ctx=None, accuracy=None):
     """`cnn noisesweep` (not in the reference, whose EvaluateWithNoise :193-221 takes one file at one level): every file at
     every level of SNRdBs and clean in one device pass per group of files (f2_eval_noise_sweep: the noise is drawn on the device
     from (seed, level, file's place in its group, sample), so a sweep repeats bit for bit), with the clean run of the same
@@ -266,7 +376,10 @@ def EvaluateNoiseSweep(files, SNRdBs, seed=0, hop=None, LPF=False, CUTOFF=50, mo
     agreement (= agree / windows, NaN without windows) - one entry per level, the clean level last - seed, hop and labels_<k>
     for level k of snr_db (labels_clean for the clean one); one line per level is printed and the same data is returned as a dict per
     file. save_wavs also writes <stem><SNR>dB.WAV with copies of the annotation files, as EvaluateWithNoise names and writes
-    them. Files are grouped like EvaluateRandom groups them: one framerate and sample type per call. hop=None is hop 1."""
+    them. Files are grouped like EvaluateRandom groups them: one framerate and sample type per call. hop=None is hop 1.
+    With accuracy= every level of a file that has its .FB / .PHN is also scored against their labels (one f2_label_accuracy
+    call per group): the file's results gain accuracy_vtr (K+1) and confusion (K+1, 2, 2), [level][ref][pred], the clean level
+    last, and the printed lines the accuracy."""
     import shutil
     from scipy.io import wavfile
     if isinstance(files, (str, bytes, os.PathLike)):
@@ -276,6 +389,8 @@ def EvaluateNoiseSweep(files, SNRdBs, seed=0, hop=None, LPF=False, CUTOFF=50, mo
         raise ValueError("a noise sweep needs at least one finite SNR in dB")
     K = len(snr)
     hop = 1 if hop is None else int(hop)
+    if accuracy is not None:
+        _accuracy_origin(accuracy, 0, 0)
     ctx = ctx or _lib.default_context()
     cfg = F2Config()
     if not isinstance(model, F2CNNModel):
@@ -312,6 +427,10 @@ def EvaluateNoiseSweep(files, SNRdBs, seed=0, hop=None, LPF=False, CUTOFF=50, mo
                     raise ValueError("values must all be positive")
                 raise
             assert list(numpy.diff(wo)) == nbh * (K + 1)
+            refs = [ReferenceLabels(file) for file, _ in group] if accuracy is not None else [None] * B
+            confusions = None
+            if any(ref is not None for ref in refs):
+                confusions = _confusions(ctx, labels, wo, refs, accuracy, hop, STEP)
             os.makedirs(os.path.join('OutputWavFiles', 'addedNoise'), exist_ok=True)
             for b, (file, w) in enumerate(group):
                 rows = [l * B + b for l in range(K + 1)]
@@ -323,13 +442,21 @@ def EvaluateNoiseSweep(files, SNRdBs, seed=0, hop=None, LPF=False, CUTOFF=50, mo
                            agreement=agreement, seed=numpy.uint64(int(seed) & (2 ** 64 - 1)), hop=numpy.int64(hop))
                 for key, u in zip(keys, rows):
                     res['labels_' + key] = labels[wo[u]:wo[u + 1]].copy()
+                if refs[b] is not None:
+                    res['confusion'] = confusions[rows].copy()
+                    res['accuracy_vtr'] = _accuracy_of(res['confusion'])
                 source, _ = _noisy_copy_paths(file, 0)
                 out = os.path.join('OutputWavFiles', 'addedNoise', os.path.basename(source) + '.sweep.npz')
                 numpy.savez(out, **res)
                 print("File:\t\t{}".format(file))
+                if accuracy is not None and refs[b] is None:
+                    _no_side_files(file)
                 for l in range(K + 1):
-                    print("\tSNR {:>8}\t{} windows\t{} rising\tagreement with clean {:.4f}".format(
-                        names[l], windows[l], rising[l], agreement[l]))
+                    line = "\tSNR {:>8}\t{} windows\t{} rising\tagreement with clean {:.4f}".format(
+                        names[l], windows[l], rising[l], agreement[l])
+                    if refs[b] is not None:
+                        line += "\taccuracy against the VTR labels ({}) {:.4f}".format(accuracy, res['accuracy_vtr'][l])
+                    print(line)
                 if save_wavs:
                     for l in range(K):
                         _, target = _noisy_copy_paths(file, snr[l])

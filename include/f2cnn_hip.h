@@ -64,7 +64,7 @@ enum { F2_FFT_F32 = 0, F2_FFT_F64 = 1 };
 int f2_version(void);   /* 100 * major + minor; 101 added f2_eval_batch, 102 f2_host_alloc + F2_MEM_HOST_ASYNC, 103 f2_ctx_set_option, 105 f2_spectral_guard_read + f2_cnn_get_info,
                            106 f2_cnn_forward accepts any finite input on the split path (scales from the input's range; the
                            f2_cnn_get_info keys "f16x3_ok", "f16x3_check_diff", "last_input_bound"), 107 f2_input_batch,
-                           108 f2_eval_batch_strided, 109 f2_eval_noise_sweep */
+                           108 f2_eval_batch_strided, 109 f2_eval_noise_sweep, 110 f2_label_accuracy */
 int f2_device_count(int* count);
 int f2_ctx_create(int device, f2_ctx** ctx);
 int f2_ctx_destroy(f2_ctx* ctx);
@@ -338,6 +338,44 @@ int f2_eval_noise_sweep(f2_ctx* ctx, const f2_cnn* cnn, const void* wave, int wa
                         double* noisy_or_null, float* scores_or_null, uint8_t* labels_or_null,
                         int64_t* window_offsets_or_null /* host, (K+1)*B + 1 */, double* sigma_or_null /* host, (K+1)*B */,
                         int64_t* stats_or_null /* host, (K+1)*B*2 */, int mem_space);
+
+/* ---- `cnn eval|evalnoise|evalrand|noisesweep --accuracy`: the labels of an evaluation against the VTR-derived labels --------
+ * scripts/CNN/Evaluating.py:38-40, 92-108 (the end of EvaluateOneWavArray) holds every decision of a file against the labels
+ * LabelDataGenerator.ExtractLabel derives from the file's .FB / .PHN, in a double loop of interpreted Python over decisions and
+ * label pairs. Here: one kernel over the label array of a strided evaluation, for a whole batch.
+ *   labels          (window_offsets[U]) uint8 in mem_space, 0 = falling, anything else = rising: utterance u owns rows
+ *                   window_offsets[u] .. window_offsets[u+1] - 1 (what f2_eval_batch_strided / f2_eval_noise_sweep return)
+ *   ref_offsets, ref_timepoints, ref_signs   R reference sets, set r being entries ref_offsets[r] .. ref_offsets[r+1] - 1:
+ *                   the label timepoints T[0..n) of a file in samples, strictly increasing, and their signs s[0..n), 0 falling,
+ *                   1 rising. Utterance u is scored against set u % R (a sweep passes U = (K+1)*B and R = B).
+ *   The rule. Row j of an utterance has the timepoint t = origin + j*hop (int64).
+ *     - the row is COUNTED if there is a k with T[k] < t < T[k+1] and (t - T[k] < step or T[k+1] - t < step);
+ *     - its reference sign is s[k] if t - T[k] <= T[k+1] - t, else s[k+1] (a tie goes to the earlier label); the row is correct
+ *       if its label equals that sign;
+ *     - never counted: a row with t equal to a label timepoint, a row before the first label or after the last, every row of
+ *       an utterance whose set has fewer than two labels.
+ *   origin          0 reproduces the reference, which compares the ROW INDEX with the label timepoint (Evaluating.py:96
+ *                   enumerates the decisions; its own TODO) although row j is centred on sample radius*step + j - reproduced,
+ *                   not corrected, like the noise scaling of f2_eval_noise_sweep. origin = radius*step gives every row its
+ *                   true centre sample (f2_eval_batch_strided: radius*step + j*hop).
+ *   counts          host, U*4: counts[4u + 2*ref + pred] = counted rows of utterance u with reference sign `ref` and label
+ *                   `pred`. Accuracy = (counts[4u] + counts[4u+3]) / (sum of the four); the reference divides by zero when
+ *                   nothing is counted. Workgroup sums, then 64-bit vector integer atomics on a zeroed buffer: the same bits
+ *                   on every call.
+ * The small arrays are uploaded through the context's page-locked staging; the call waits for the stream before it returns
+ * (it hands back counts), whatever mem_space is.
+ * F2_ERR_INVALID, with nothing launched and counts untouched: a NULL ctx / window_offsets / ref_offsets / counts; NULL labels
+ * with window_offsets[U] > 0; NULL ref_timepoints or ref_signs with ref_offsets[R] > 0; U < 0; R < 1 or U % R != 0 when U > 0
+ * (R < 0 always); hop < 1, step < 1 or origin < 0; offsets that do not start at 0 or decrease; timepoints not strictly increasing
+ * inside a set; a sign above 1; a mem_space other than F2_MEM_HOST / F2_MEM_DEVICE. F2_ERR_UNSUPPORTED: the timepoint of an
+ * utterance's last row does not fit int64. U == 0, or no rows at all: F2_OK with counts zeroed.
+ */
+int f2_label_accuracy(f2_ctx* ctx, const uint8_t* labels /* mem_space */,
+                      const int64_t* window_offsets /* host, U+1 */, int U,
+                      const int64_t* ref_offsets /* host, R+1 */, const int64_t* ref_timepoints /* host */,
+                      const uint8_t* ref_signs /* host */, int R,
+                      int64_t origin, int hop, int step,
+                      int64_t* counts /* host, U*4: counts[4u + 2*ref + pred] */, int mem_space);
 
 #ifdef __cplusplus
 }
