@@ -350,6 +350,9 @@ int f2_launch_gather(f2_ctx* ctx, const double* d_env, int C, int64_t N, const i
 int f2_launch_gather_ragged(f2_ctx* ctx, const double* d_env, int C, const int64_t* d_offsets, const int64_t* d_centers,
                             const int* d_win_utt, int64_t n_windows, int radius, int step, int normalize, float* d_out,
                             int* d_flag);
+// a window list on the device, in ctx->work2: the centres and, with win_utt != NULL, the utterance of every window behind them
+int f2_upload_windows(f2_ctx* ctx, const int64_t* centers, const int* win_utt, int64_t n_windows, const int64_t** d_centers,
+                      const int** d_win_utt);
 // Strided, normalised windows of a ragged batch (f2_eval_batch_strided): segment s is the windows first .. first + count - 1
 // of utterance utt, window j centred at radius * step + j * hop of its utterance; the segments' windows are written to d_out
 // one after the other. hop | step (and option "gather_blocked"): three launches for all segments, on the decimated envelope

@@ -105,11 +105,7 @@ int f2_gather_windows(f2_ctx* ctx, const double* env, int C, int64_t N, const in
                  "%lld every-sample windows do not fit in %lld samples", (long long)n_windows, (long long)N);
     }
     const int64_t* d_centers = nullptr;
-    if (centers) {
-        F2_TRY(f2_reserve(ctx, ctx->work2, sizeof(int64_t) * (size_t)n_windows));
-        F2_TRY(f2_upload_async(ctx, ctx->work2.ptr, centers, sizeof(int64_t) * (size_t)n_windows));
-        d_centers = (const int64_t*)ctx->work2.ptr;
-    }
+    if (centers) F2_TRY(f2_upload_windows(ctx, centers, nullptr, n_windows, &d_centers, nullptr));
     const size_t env_bytes = sizeof(double) * (size_t)C * (size_t)N;
     const size_t out_bytes = sizeof(float) * (size_t)n_windows * R * (size_t)C;
     const double* d_env = env;
@@ -614,10 +610,9 @@ int f2_input_batch(f2_ctx* ctx, const void* wave, int wave_dtype, const int64_t*
     F2_TRY(f2_envelopes_device(ctx, d_wave, wave_dtype, offsets, B, C, lpf, cutoff_hz, fft_precision, d_env, nullptr, true));
 
     // all windows of the batch in one gather launch: centres and the utterance of every window in one upload
-    const size_t cbytes = sizeof(int64_t) * (size_t)n_windows, ubytes = sizeof(int) * (size_t)n_windows;
-    F2_TRY(f2_reserve(ctx, ctx->work2, cbytes + ubytes));
-    F2_TRY(f2_upload_async(ctx, ctx->work2.ptr, centers, cbytes));
-    F2_TRY(f2_upload_async(ctx, (char*)ctx->work2.ptr + cbytes, win_utt.data(), ubytes));
+    const int64_t* d_centers;
+    const int* d_win_utt;
+    F2_TRY(f2_upload_windows(ctx, centers, win_utt.data(), n_windows, &d_centers, &d_win_utt));
     const size_t out_bytes = sizeof(float) * (size_t)n_windows * R * (size_t)C;
     float* d_out = windows;
     if (mem_space == F2_MEM_HOST) {
@@ -625,9 +620,8 @@ int f2_input_batch(f2_ctx* ctx, const void* wave, int wave_dtype, const int64_t*
         d_out = (float*)ctx->xbuf.ptr;
     }
     F2_TRY(reset_flag(ctx));
-    F2_TRY(f2_launch_gather_ragged(ctx, d_env, C, (const int64_t*)ctx->offsets.ptr, (const int64_t*)ctx->work2.ptr,
-                                   (const int*)((char*)ctx->work2.ptr + cbytes), n_windows, radius, step, normalize, d_out,
-                                   (int*)ctx->flags.ptr));
+    F2_TRY(f2_launch_gather_ragged(ctx, d_env, C, (const int64_t*)ctx->offsets.ptr, d_centers, d_win_utt, n_windows, radius, step,
+                                   normalize, d_out, (int*)ctx->flags.ptr));
     if (mem_space == F2_MEM_HOST) F2_HIP(ctx, hipMemcpyAsync(windows, d_out, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
     return normalize || mem_space == F2_MEM_HOST ? finish_positive(ctx) : F2_OK;
 }

@@ -155,6 +155,43 @@ def test_device_buffers_and_optional_outputs(ctx, model, coefs, ragged, hop):
         assert none is None and none2 is None and wo[-1] == sum((nb_of(n) + hop - 1) // hop for n in LENGTHS)
 
 
+@pytest.mark.parametrize("rows,channels", [(11, 67), (13, 40)], ids=["11x67", "13x40"])
+def test_strided_rows_are_the_every_sample_rows_where_the_channel_tails_run(ctx, rows, channels):
+    """The window kernels' partial channel group and their two store forms, on both routes: 67 channels end in a group of 3 and
+    take the scalar store tail (67 % 4 != 0), 40 end in a group of 8 and take the float4 stores. STEP = 16 keeps the batch tiny;
+    with W = rows * 16 the utterances have 1, 33 (a block of 32 windows and one), 200 (a partial last block), 500 - W (several
+    blocks), no window, and no samples. Hops 1, 2 and 16 divide STEP (table-driven kernels), 3 does not (per-window kernel);
+    the reference is f2_eval_batch on the same batch, whose utterances of 200 and 500 - W windows take the every-sample blocked
+    kernels and the shorter ones the per-window kernel. Raw bits of scores and labels."""
+    step, radius, W = 16, (rows - 1) // 2, rows * 16
+    assert 2 * radius + 1 == rows
+    lengths = (W + 1, W + 33, W + 200, 500, W, 0)
+    flat, offsets = ragged_waves(lengths, seed=70)
+    B = len(lengths)
+    cf = orc.make_erb_filters(16000, orc.centre_freqs(16000, channels, 100))
+    h = F2CNNModel.glorot(7, rows, channels).handle(ctx)
+    nbs = [max(0, n - W) for n in lengths]
+    off_1 = np.concatenate([[0], np.cumsum(nbs)]).astype(np.int64)
+    sc_1, lb_1 = np.empty((sum(nbs), 2), np.float32), np.empty(sum(nbs), np.uint8)
+    ctx.eval_batch(h, flat, _lib.WAVE_I16, offsets, cf, B, channels, False, 0.0, _lib.FFT_F32, radius, step, sc_1, lb_1, _lib.MEM_HOST)
+    for hop in (1, 2, 16, 3):
+        counts = [(nb + hop - 1) // hop for nb in nbs]
+        assert counts == [_lib.strided_window_count(n, radius, step, hop) for n in lengths]
+        sc = np.empty((sum(counts), 2), np.float32)
+        sc.view(np.uint8)[...] = 0x5A
+        lb = np.full(sum(counts), 0x5A, np.uint8)
+        wo = ctx.eval_batch_strided(h, flat, _lib.WAVE_I16, offsets, cf, B, channels, False, 0.0, _lib.FFT_F32, radius, step, hop, sc,
+                                    lb, _lib.MEM_HOST)
+        assert np.array_equal(wo, np.concatenate([[0], np.cumsum(counts)])), hop
+        for b, nb in enumerate(nbs):
+            rows_1 = off_1[b] + np.arange(0, nb, hop)
+            got, want = sc[wo[b]:wo[b + 1]], sc_1[rows_1]
+            assert np.array_equal(bits(got), bits(want)), \
+                f"utterance {b} ({lengths[b]} samples), hop {hop}: scores differ in {np.count_nonzero((got != want).any(axis=1))} of {len(rows_1)} windows"
+            assert np.array_equal(lb[wo[b]:wo[b + 1]], lb_1[rows_1]), (b, hop)
+        assert set(np.unique(lb)) <= {0, 1}                                                    # (written: not the fill byte)
+
+
 def test_per_window_route_when_the_blocked_kernels_are_switched_off(ctx, model, coefs, ragged):
     """option gather_blocked = 0 sends a hop that divides STEP through the per-window kernel as well: same rows"""
     flat, offsets, get = ragged

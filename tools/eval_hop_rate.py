@@ -1,11 +1,12 @@
 #!/usr/bin/env python3
-"""Rate of `cnn eval` with a hop (f2_eval_batch_strided) against the every-sample call of another build of the library.
+"""Rate of `cnn eval` with a hop (f2_eval_batch_strided) and without (f2_eval_batch), this tree's library against another build.
 
   eval_hop_rate.py build-baseline REV DIR      extract REV's library sources (git archive) into DIR and build them there
   eval_hop_rate.py ab BASELINE.so OUT.json [--rounds 2] [--batches 8,1000] [--hops 1,16,160] [--reps 3]
-        alternates fresh processes: BASELINE.so running f2_eval_batch, the tree's library running f2_eval_batch_strided
-        at each hop, on the same seeded batches of 1 s utterances in device memory; writes every run and a summary
-  eval_hop_rate.py measure every|strided OUT.json ...      one such process (F2CNN_PROBE_LIB picks the library)
+        alternates fresh processes, BASELINE.so and the tree's library: each runs f2_eval_batch and f2_eval_batch_strided at
+        each hop on the same seeded batches of 1 s utterances in device memory; writes every run and a summary in which
+        every entry point of the tree is held against the same entry point of the baseline
+  eval_hop_rate.py measure every|strided|both OUT.json ...      one such process (F2CNN_PROBE_LIB picks the library)
 
 Per case: one warm-up call, `reps` calls each between two device events (profiling off), then one call with f2_prof_enable
 for the per-kernel device times. audio-s/s = audio seconds of the batch over the mean event time. The spread quoted for the
@@ -29,7 +30,7 @@ def build_baseline(rev, dest):
     print(os.path.join(dest, "f2cnn_amd", "lib", "libf2cnn_hip.so"))
 
 
-def measure(entry, out, batches, hops, reps):
+def measure(which, out, batches, hops, reps):
     import numpy as np
     sys.path.insert(0, ROOT)
     if os.environ.get("F2CNN_PROBE_LIB"):
@@ -49,7 +50,8 @@ def measure(entry, out, batches, hops, reps):
         offsets = np.arange(B + 1, dtype=np.int64) * N
         d_wave, d_scores, d_labels = ctx.malloc(waves.nbytes), ctx.malloc(8 * nb * B), ctx.malloc(nb * B)
         ctx.h2d(d_wave, waves)
-        for hop in hops if entry == "strided" else [1]:
+        for entry, hop in [(e, h) for e in (("every", "strided") if which == "both" else (which,))
+                           for h in (hops if e == "strided" else [1])]:
             if entry == "strided":
                 windows = B * _lib.strided_window_count(N, RADIUS, STEP, hop)
                 call = lambda: ctx.eval_batch_strided(h, d_wave, _lib.WAVE_I16, offsets, coefs, B, C, False, 0.0, _lib.FFT_F32, RADIUS,
@@ -87,37 +89,38 @@ def measure(entry, out, batches, hops, reps):
 
 
 def summarise(runs):
-    def cases(lib, B, hop):
-        return [c for r in runs if r["lib"] == lib for c in r["cases"] if c["batch"] == B and c["hop"] == hop]
+    def cases(lib, B, entry, hop):
+        return [c for r in runs if r["lib"] == lib for c in r["cases"] if (c["batch"], c["entry"], c["hop"]) == (B, entry, hop)]
 
-    def window_stage(c):       # window + CNN device time per evaluated window, ns
-        k = c["kernels_launches_ms"]
-        return (k["k_gather_windows"][1] + k["k_cnn_forward"][1]) * 1e6 / c["windows"]
-    out = {}
-    for B in sorted({c["batch"] for r in runs for c in r["cases"]}):
-        base = cases("baseline", B, 1)
-        ms = [v for c in base for v in c["ms"]]
+    def ns_per_window(c, kernel):       # device time of one profiling bracket per evaluated window
+        return c["kernels_launches_ms"][kernel][1] * 1e6 / c["windows"]
+
+    def side(cs, B):
+        ms = [v for c in cs for v in c["ms"]]
         mean = sum(ms) / len(ms)
-        per_win = [window_stage(c) for c in base]
-        row = {"baseline f2_eval_batch": {"ms_mean": round(mean, 3), "ms_min": min(ms), "ms_max": max(ms),
-                                          "spread": round((max(ms) - min(ms)) / mean, 4),
-                                          "audio_s_per_s": round(B * N / FS / (mean / 1e3), 1),
-                                          "window_and_cnn_ns_per_window": [round(v, 2) for v in per_win]}}
-        for hop in sorted({c["hop"] for r in runs if r["lib"] == "tree" for c in r["cases"]}):
-            new = cases("tree", B, hop)
-            if not new:
-                continue
-            nms = [v for c in new for v in c["ms"]]
-            nmean = sum(nms) / len(nms)
-            k = new[-1]["kernels_launches_ms"]
-            total = sum(v[1] for v in k.values())
-            row[f"f2_eval_batch_strided hop {hop}"] = {
-                "windows": new[-1]["windows"], "ms_mean": round(nmean, 3), "ms_min": min(nms), "ms_max": max(nms),
-                "audio_s_per_s": round(B * N / FS / (nmean / 1e3), 1), "ms_over_baseline": round(nmean / mean, 4),
-                "window_and_cnn_ns_per_window": [round(window_stage(c), 2) for c in new],
-                "kernels_launches_ms": k,
+        win = [ns_per_window(c, "k_gather_windows") for c in cs]
+        k = cs[-1]["kernels_launches_ms"]
+        total = sum(v[1] for v in k.values())
+        return {"windows": cs[-1]["windows"], "ms_mean": round(mean, 4), "ms_min": min(ms), "ms_max": max(ms),
+                "spread": round((max(ms) - min(ms)) / mean, 4), "audio_s_per_s": round(B * N / FS / (mean / 1e3), 1),
+                "window_stage_ns_per_window": [round(v, 3) for v in win], "window_stage_ns_per_window_mean": round(sum(win) / len(win), 3),
+                "cnn_ns_per_window": [round(ns_per_window(c, "k_cnn_forward"), 2) for c in cs], "kernels_launches_ms": k,
                 "share_of_kernel_time": {name: round(v[1] / total, 4) for name, v in k.items()}}
-        out[f"{B} x 1 s"] = row
+    out = {}
+    keys = sorted({(c["batch"], c["entry"], c["hop"]) for r in runs for c in r["cases"]})
+    for B, entry, hop in keys:
+        old, new = cases("baseline", B, entry, hop), cases("tree", B, entry, hop)
+        if not old or not new:
+            continue
+        o, n = side(old, B), side(new, B)
+        # the tree's mean call time inside the baseline's own min .. max; its window stage within that relative spread
+        verdict = {"ms_over_baseline": round(n["ms_mean"] / o["ms_mean"], 4),
+                   "call_mean_within_baseline_min_max": bool(n["ms_mean"] <= o["ms_max"]),
+                   "window_stage_over_baseline": round(n["window_stage_ns_per_window_mean"] / o["window_stage_ns_per_window_mean"], 4),
+                   "window_stage_within_baseline_spread": bool(n["window_stage_ns_per_window_mean"] <=
+                                                               o["window_stage_ns_per_window_mean"] * (1 + o["spread"]))}
+        out.setdefault(f"{B} x 1 s", {})[entry + (f" hop {hop}" if entry.endswith("strided") else "")] = \
+            {"baseline": o, "tree": n, "tree against baseline": verdict}
     return out
 
 
@@ -126,12 +129,12 @@ def ab(baseline, out, rounds, batches, hops, reps):
     runs = []
     common = ["--batches", ",".join(map(str, batches)), "--hops", ",".join(map(str, hops)), "--reps", str(reps)]
     for rnd in range(rounds):
-        for lib, entry, path in (("baseline", "every", baseline), ("tree", "strided", None)):
+        for lib, path in (("baseline", baseline), ("tree", None)):
             env = dict(os.environ, F2CNN_PROBE_OLD_LIB="1")
             env.pop("F2CNN_PROBE_LIB", None)
             if path:
                 env["F2CNN_PROBE_LIB"] = path
-            res = subprocess.run([sys.executable, os.path.abspath(__file__), "measure", entry, tmp] + common, env=env, timeout=900)
+            res = subprocess.run([sys.executable, os.path.abspath(__file__), "measure", "both", tmp] + common, env=env, timeout=900)
             if res.returncode != 0:      # nothing more is started on the device after a failed run
                 sys.exit(f"{lib} run of round {rnd} ended with status {res.returncode}")
             runs.append({"lib": lib, "round": rnd, "cases": json.load(open(tmp))})
@@ -151,7 +154,7 @@ if __name__ == "__main__":
     p.add_argument("dest")
     for name in ("ab", "measure"):
         p = sub.add_parser(name)
-        p.add_argument("first")          # ab: the baseline library; measure: every | strided
+        p.add_argument("first")          # ab: the baseline library; measure: every | strided | both
         p.add_argument("out")
         p.add_argument("--rounds", type=int, default=2)
         p.add_argument("--batches", type=ints, default=[8, 1000])
