@@ -66,6 +66,7 @@ SIGNATURES = {
     "f2_eval_noise_sweep": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _d, _i, _i, _i, _i, _vp, _i, C.c_uint64, _vp, _vp, _vp,
                                  _vp, _vp, _vp, _i]),
     "f2_label_accuracy": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i64, _i, _i, _vp, _i]),
+    "f2_cnn_score_windows": (_i, [_vp, _vp, _vp, _i64, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i]),
 }
 
 _lib = None
@@ -416,6 +417,33 @@ class Context:
                                               _ptr(ref_timepoints), _ptr(ref_signs), R, int(origin), int(hop), int(step),
                                               _ptr(counts), mem_space))
         return counts.reshape(U, 2, 2)
+
+
+    def cnn_score_windows(self, handle, windows, n, normalize, signs, groups, n_groups, scores, labels, mem_space, counts=None,
+                          loss_sum=None):
+        """A model scored on n stored, labelled windows in one device pass (see f2_cnn_score_windows): `windows` (n, rows, C)
+        float32, `signs` (n) uint8 0 / 1, `groups` (n) int32 in [0, n_groups) or None (then n_groups must be 1), `scores` (n, 2)
+        float32 / `labels` (n) uint8 or None - numpy arrays or device pointers, by mem_space. normalize=True: the windows are raw
+        envelope windows, normalised on the device as normalizeInputBatch does. Returns (counts (n_groups, 2, 2) int64
+        [group][sign][label], loss_sum (n_groups,) float64), written into `counts` / `loss_sum` when given."""
+        G = int(n_groups)
+        if isinstance(windows, np.ndarray):
+            windows = np.ascontiguousarray(windows, dtype=np.float32)
+        if isinstance(signs, np.ndarray):
+            signs = np.ascontiguousarray(signs, dtype=np.uint8)
+        if isinstance(groups, np.ndarray):
+            groups = np.ascontiguousarray(groups, dtype=np.int32)
+        if counts is None:
+            counts = np.zeros((max(G, 0), 2, 2), np.int64)
+        if loss_sum is None:
+            loss_sum = np.zeros(max(G, 0), np.float64)
+        if G >= 1 and (counts.dtype != np.int64 or counts.size != 4 * G or not counts.flags["C_CONTIGUOUS"]
+                       or loss_sum.dtype != np.float64 or loss_sum.size != G or not loss_sum.flags["C_CONTIGUOUS"]):
+            raise ValueError("counts / loss_sum must be contiguous int64 (n_groups, 2, 2) / float64 (n_groups,)")
+        self.check(self.lib.f2_cnn_score_windows(self.handle, handle, _ptr(windows), int(n), int(normalize), _ptr(signs),
+                                                 _ptr(groups), G, _ptr(scores), _ptr(labels), _ptr(counts), _ptr(loss_sum),
+                                                 mem_space))
+        return counts.reshape(G, 2, 2), loss_sum
 
 
 def strided_window_count(n, radius, step, hop):

@@ -12,6 +12,11 @@ package implements:
     (filter / envelope / features also take --skip-existing to resume and --metrics FILE for a JSON summary; a file that
      cannot be read is reported and skipped, the exit status is then 2)
     python -m f2cnn_amd cnn train [--input/-i NPY] [--label/-l CSV]   (PyTorch-ROCm autograd; weights -> last_trained_model)
+    python -m f2cnn_amd cnn test [--input/-i NPY] [--label/-l CSV] [--model/-m NPZ] [--by set|region|speaker|phoneme] [--rows test|train|all]
+                                                            (loss, accuracy and the 2 x 2 counts of a saved model on the labelled
+                                                             windows, per value of a label column, in one device pass; writes
+                                                             <model>_test.json, a trailing .npz of the name dropped; the
+                                                             reference only scores right after training)
     python -m f2cnn_amd cnn eval --file/-f WAV [--lpf HZ] [--model/-m NPZ] [--hop N|frame]
     python -m f2cnn_amd cnn evalnoise --file/-f WAV --noise/-n SNRdB [--lpf HZ] [--model/-m NPZ] [--hop N|frame]
     python -m f2cnn_amd cnn noisesweep --file/-f WAV --snrs 20,10,0,-3 [--seed N] [--save-wavs] [--hop N|frame] [--lpf HZ] [--model/-m NPZ]
@@ -30,7 +35,7 @@ organize / plot need the licensed TIMIT+VTR corpora or matplotlib and stay with 
 import argparse
 
 PREPARE = ("filter", "envelope", "label", "input", "features")
-CNN = ("train", "eval", "evalnoise", "evalrand", "noisesweep")
+CNN = ("train", "test", "eval", "evalnoise", "evalrand", "noisesweep")
 
 
 def hop_argument(text):
@@ -94,6 +99,11 @@ def build_parser():
     c.add_argument('--seed', action='store', type=int, dest='seed', help="noisesweep: seed of the noise (default 0)")
     c.add_argument('--save-wavs', action='store_true', dest='save_wavs',
                    help="noisesweep: also write the noisy WAV files, as evalnoise does")
+    # (absent from the parsed arguments unless given: the commands parse as before without them)
+    c.add_argument('--by', action='store', dest='by', choices=('set', 'region', 'speaker', 'phoneme'), default=argparse.SUPPRESS,
+                   help="test: break the result down by this column of the label CSV")
+    c.add_argument('--rows', action='store', dest='rows', choices=('test', 'train', 'all'), default=argparse.SUPPRESS,
+                   help="test: score the TEST rows of the label CSV (default), the others, or all of them")
     # (absent from the parsed arguments unless given: the commands parse as before without it)
     c.add_argument('--accuracy', nargs='?', choices=('reference', 'centre'), const='reference', default=argparse.SUPPRESS,
                    dest='accuracy',
@@ -101,6 +111,21 @@ def build_parser():
                         "'reference' (the bare flag) compares the row index with the label timepoint as the reference does, "
                         "'centre' the row's centre sample")
     return parser
+
+
+def labelled_window_files(args):
+    """cnn train / cnn test: (input .npy, label .csv) as given or at their default places (f2cnn.py:126-143), or None after
+    saying which of the two has still to be made"""
+    import os
+    inputFile = args.inputFile or args.file or os.path.join('trainingData', 'last_input_data.npy')
+    labelFile = args.labelFile or os.path.join('trainingData', 'label_data.csv')
+    if not os.path.isfile(inputFile):
+        print("Please first generate the input data file with 'prepare input', or give one with --input")
+        return None
+    if not os.path.isfile(labelFile):
+        print("Please first generate a label data file with 'prepare label', or give one with --label")
+        return None
+    return inputFile, labelFile
 
 
 def main(argv=None):
@@ -139,17 +164,19 @@ def main(argv=None):
             return report.exit_status
     elif 'cnn_command' in args:
         if args.cnn_command == 'train':                        # f2cnn.py:126-143
-            import os
             from .scripts.CNN.Training import TrainAndPlotLoss
-            inputFile = args.inputFile or args.file or os.path.join('trainingData', 'last_input_data.npy')
-            labelFile = args.labelFile or os.path.join('trainingData', 'label_data.csv')
-            if not os.path.isfile(inputFile):
-                print("Please first generate the input data file with 'prepare input', or give one with --input")
+            files = labelled_window_files(args)
+            if files is None:
                 return 1
-            if not os.path.isfile(labelFile):
-                print("Please first generate a label data file with 'prepare label', or give one with --label")
+            TrainAndPlotLoss(labelFile=files[1], inputFile=files[0])
+            return 0
+        if args.cnn_command == 'test':
+            from .scripts.CNN.Training import TestModel
+            files = labelled_window_files(args)
+            if files is None:
                 return 1
-            TrainAndPlotLoss(labelFile=labelFile, inputFile=inputFile)
+            TestModel(labelFile=files[1], inputFile=files[0], model=args.model or 'last_trained_model',
+                      by=getattr(args, 'by', None), rows=getattr(args, 'rows', 'test'))
             return 0
         from .scripts.CNN import Evaluating
         kwargs = {}

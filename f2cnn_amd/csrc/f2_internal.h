@@ -47,6 +47,7 @@ struct f2_ctx {
     f2_scratch noise_wave; // f2_eval_noise_sweep: the (K+1) x batch float64 waveform when the caller gives no device buffer for it
     f2_scratch noise_meta; // ... and its small arrays: sigma, 10^(snr / 10) per level, stats, window offsets
     f2_scratch acc_meta;   // f2_label_accuracy: counts, window offsets, reference offsets / timepoints / signs
+    f2_scratch score_meta; // f2_cnn_score_windows: counts, loss sums, per-workgroup loss partials of the chunk in flight
     f2_scratch gather_log; // ln of the envelope samples a chunk of every-sample windows touches + column min / max (f2_gather.hip)
     f2_scratch tw[2][16];  // FFT twiddle tables, [precision][log2 H], built on first use
     f2_scratch tw_fl[16];         // twiddle tables of f2_envelope_flagged.hip, by log2 H
@@ -158,7 +159,7 @@ struct f2_cnn {
     // (f2_cnn_scale_set); each owns its sbias buffer, freed by f2_cnn_destroy
     mutable std::mutex sets_mu;
     mutable f2_scale_set* sets[F2_BOUND_EXP_MAX + 1] = {nullptr};
-    mutable double last_input_bound = 0.0;   // B of the last f2_cnn_forward, -1: the float32 kernels ran, 0: none yet
+    mutable double last_input_bound = 0.0;   // B of the last f2_cnn_forward / unnormalised f2_cnn_score_windows, -1: the float32 kernels ran, 0: none yet
     // f2_cnn_create's self-check of the weight-stationary kernels (hand-placed s_waitcnt around inline-asm loads: correct only
     // while the register allocator of the hipcc that built the library leaves those registers alone) against the per-tile
     // split-fp16 kernels on a fixed batch; a kernel that disagrees is not used with this network
@@ -400,5 +401,15 @@ int f2_launch_label_tally(f2_ctx* ctx, const uint8_t* d_labels, const int64_t* d
 int f2_launch_label_accuracy(f2_ctx* ctx, const uint8_t* d_labels, const int64_t* d_window_offsets, int U, const int64_t* d_ref_offsets,
                              const int64_t* d_ref_timepoints, const uint8_t* d_ref_signs, int R, int64_t origin, int hop, int step,
                              int64_t max_rows, int64_t* d_counts);
+// f2_score.hip, the kernels of f2_cnn_score_windows. k_normalize_windows: n windows of `total` contiguous float32 values each,
+// normalised with K3's arithmetic into d_out (may not alias d_in); a window with a value <= 0 or a NaN becomes zeros and ORs 1
+// into *d_flag.
+int f2_launch_normalize_windows(f2_ctx* ctx, const float* d_in, int64_t n, int total, float* d_out, int* d_flag);
+// k_score_tally + k_score_loss_fold over m windows: d_counts (4 G, zeroed by the caller before the first launch of a call)
+// [4 g + 2 sign + label] += windows, d_loss (G, likewise) [g] += the float64 loss terms in a fixed order; d_groups NULL: group 0.
+// d_partial: room for f2_score_partial_doubles(m, G) values. A sign above 1 ORs 1, a group outside [0, G) ORs 2 into *d_flag.
+int f2_launch_score_tally(f2_ctx* ctx, const float* d_scores, const uint8_t* d_labels, const uint8_t* d_signs, const int* d_groups,
+                          int G, int64_t m, int64_t* d_counts, double* d_partial, double* d_loss, int* d_flag);
+size_t f2_score_partial_doubles(int64_t max_windows, int G);
 size_t f2_cnn_flat_floats(const f2_cnn* cnn);    // floats per window of the conv4 output
 size_t f2_cnn_dense_floats(const f2_cnn* cnn);   // ... plus dense1's output

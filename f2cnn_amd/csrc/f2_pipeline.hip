@@ -68,6 +68,29 @@ int pick_scale_set(f2_ctx* ctx, const f2_cnn* cnn, const f2_scale_set** S, doubl
     return F2_OK;
 }
 
+// The route of f2_cnn_forward (and of f2_cnn_score_windows without normalisation). forward_measures: the split path's scales
+// follow the input (f2_cnn_split.h), so the call measures it - unless the float32 kernels run whatever the input.
+// forward_scale_set: the range pass over the nwin windows at d_x and the set of their bound (waits for the stream); without
+// `measure` *S = NULL and *bound = -1
+int forward_measures(f2_ctx* ctx, const f2_cnn* cnn, bool* measure) {
+    const f2_scale_set* S1 = nullptr;
+    F2_TRY(f2_cnn_scale_set(ctx, cnn, 0, &S1));
+    *measure = S1 && ctx->opt_cnn_f16x3;
+    return F2_OK;
+}
+
+int forward_scale_set(f2_ctx* ctx, const f2_cnn* cnn, bool measure, const float* d_x, int64_t nwin, const f2_scale_set** S,
+                      double* bound) {
+    *S = nullptr;
+    *bound = -1.0;
+    if (!measure) return F2_OK;
+    F2_TRY(run_input_range(ctx, d_x, nwin, cnn->rows * cnn->channels));
+    return pick_scale_set(ctx, cnn, S, bound);
+}
+
+// last_input_bound of a host call of several chunks (start at 0): the largest B, -1 once a chunk ran on the float32 kernels
+double chunks_bound(double bound, double b) { return b < 0 || bound < 0 ? -1.0 : b > bound ? b : bound; }
+
 int cnn_forward_device(f2_ctx* ctx, const f2_cnn* cnn, const f2_scale_set* S, const float* d_x, int64_t n, float* d_scores,
                        uint8_t* d_labels) {
     const size_t per = f2_cnn_workspace_floats(cnn);
@@ -134,17 +157,12 @@ int f2_cnn_forward(f2_ctx* ctx, const f2_cnn* cnn, const float* x, int64_t n, fl
     if (n == 0) return F2_OK;
     F2_CHECK(ctx, x, F2_ERR_INVALID, "x is NULL");
     const size_t xs = (size_t)cnn->rows * cnn->channels;
-    // the split path's scales follow the input (f2_cnn_split.h): a range pass, then the set of its bound
-    const f2_scale_set* S1 = nullptr;
-    F2_TRY(f2_cnn_scale_set(ctx, cnn, 0, &S1));
-    const bool measure = S1 && ctx->opt_cnn_f16x3;   // (else the float32 kernels run whatever the input)
+    bool measure = false;
+    F2_TRY(forward_measures(ctx, cnn, &measure));
     if (mem_space == F2_MEM_DEVICE) {
         const f2_scale_set* S = nullptr;
         double bound = -1.0;
-        if (measure) {
-            F2_TRY(run_input_range(ctx, x, n, (int)xs));
-            F2_TRY(pick_scale_set(ctx, cnn, &S, &bound));
-        }
+        F2_TRY(forward_scale_set(ctx, cnn, measure, x, n, &S, &bound));
         F2_TRY(cnn_forward_device(ctx, cnn, S, x, n, scores, labels));
         cnn->last_input_bound = bound;
         return F2_OK;
@@ -161,11 +179,8 @@ int f2_cnn_forward(f2_ctx* ctx, const f2_cnn* cnn, const float* x, int64_t n, fl
                                    hipMemcpyHostToDevice, ctx->stream));
         const f2_scale_set* S = nullptr;
         double b = -1.0;
-        if (measure) {
-            F2_TRY(run_input_range(ctx, (const float*)ctx->stage_in.ptr, m, (int)xs));
-            F2_TRY(pick_scale_set(ctx, cnn, &S, &b));
-        }
-        bound = b < 0 || bound < 0 ? -1.0 : b > bound ? b : bound;
+        F2_TRY(forward_scale_set(ctx, cnn, measure, (const float*)ctx->stage_in.ptr, m, &S, &b));
+        bound = chunks_bound(bound, b);
         F2_TRY(cnn_forward_device(ctx, cnn, S, (const float*)ctx->stage_in.ptr, m, d_scores, d_labels));
         if (scores)
             F2_HIP(ctx, hipMemcpyAsync(scores + 2 * s, d_scores, sizeof(float) * 2 * (size_t)m, hipMemcpyDeviceToHost, ctx->stream));
@@ -569,6 +584,104 @@ int f2_label_accuracy(f2_ctx* ctx, const uint8_t* labels, const int64_t* window_
     F2_TRY(f2_launch_label_accuracy(ctx, d_labels, d_wo, U, d_ro, d_rt, d_rs, R, origin, hop, step, max_rows, d_counts));
     F2_HIP(ctx, hipMemcpyAsync(counts, d_counts, sizeof(int64_t) * 4 * (size_t)U, hipMemcpyDeviceToHost, ctx->stream));
     F2_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return F2_OK;
+}
+
+// f2_cnn_score_windows: chunk by chunk of CNN_CHUNK windows - (upload,) normalise, forward chain, tally - with the windows of a
+// chunk, their scores, labels, signs and groups in context scratch where the caller gave host memory or none
+int f2_cnn_score_windows(f2_ctx* ctx, const f2_cnn* cnn, const float* windows, int64_t n, int normalize, const uint8_t* signs,
+                         const int32_t* groups_or_null, int G, float* scores_or_null, uint8_t* labels_or_null, int64_t* counts,
+                         double* loss_sum, int mem_space) {
+    constexpr int SCORE_WORD = 1;   // word of ctx->flags the tally kernel ORs into: 1 = a sign above 1, 2 = a group outside [0, G)
+    F2_TRY(f2_check_ctx(ctx));
+    F2_TRY(f2_check_cnn(ctx, cnn, 0, 0));
+    F2_TRY(f2_check_mem_space(ctx, mem_space, false));
+    F2_CHECK(ctx, counts && loss_sum, F2_ERR_INVALID, "counts or loss_sum is NULL");
+    F2_CHECK(ctx, n >= 0 && G >= 1, F2_ERR_INVALID, "negative window count (%lld) or no group (G=%d)", (long long)n, G);
+    F2_CHECK(ctx, normalize == 0 || normalize == 1, F2_ERR_INVALID, "normalize must be 0 or 1 (got %d)", normalize);
+    F2_CHECK(ctx, groups_or_null || G == 1, F2_ERR_INVALID, "%d groups but no group array", G);
+    F2_CHECK(ctx, (windows && signs) || n == 0, F2_ERR_INVALID, "null windows or signs");
+    F2_CHECK(ctx, G <= 1024, F2_ERR_UNSUPPORTED, "%d groups (at most 1024)", G);
+    std::fill(counts, counts + 4 * (size_t)G, (int64_t)0);
+    std::fill(loss_sum, loss_sum + (size_t)G, 0.0);
+    if (n == 0) return F2_OK;
+
+    const bool host = mem_space == F2_MEM_HOST;
+    const size_t xs = (size_t)cnn->rows * cnn->channels;
+    const int64_t chunk = n < CNN_CHUNK ? n : CNN_CHUNK;
+    // small arrays of the call: [counts (4 G) | loss (G) | loss partials of a chunk], all 8-byte words
+    F2_TRY(f2_reserve(ctx, ctx->score_meta, 8 * (5 * (size_t)G + f2_score_partial_doubles(chunk, G))));
+    int64_t* d_counts = (int64_t*)ctx->score_meta.ptr;
+    double* d_loss = (double*)(d_counts + 4 * (size_t)G);
+    double* d_partial = d_loss + G;
+    // per chunk in stage_aux: [scores (2 floats) | groups (int32) | labels | signs] for what the caller has not got on the device
+    const bool own_scores = host || !scores_or_null, own_labels = host || !labels_or_null;
+    F2_TRY(f2_reserve(ctx, ctx->stage_aux, (sizeof(float) * 2 + sizeof(int32_t) + 2) * (size_t)chunk + 64));
+    float* s_scores = (float*)ctx->stage_aux.ptr;
+    int32_t* s_groups = (int32_t*)(s_scores + 2 * chunk);
+    uint8_t* s_labels = (uint8_t*)(s_groups + chunk);
+    uint8_t* s_signs = s_labels + chunk;
+    if (host) F2_TRY(f2_reserve(ctx, ctx->stage_in, sizeof(float) * xs * (size_t)chunk));
+    if (normalize) F2_TRY(f2_reserve(ctx, ctx->xbuf, sizeof(float) * xs * (size_t)chunk));
+
+    // normalised windows lie in [0, 1]: the B = 1 scale set without the range pass, as in f2_eval_*; windows as they are take
+    // f2_cnn_forward's route - the range of the whole call for device memory, of each chunk for host memory, as there
+    bool measure = false;
+    const f2_scale_set* S = nullptr;
+    double bound = host ? 0.0 : -1.0;   // normalize = 0: what f2_cnn_forward leaves in last_input_bound (host: largest B of the chunks)
+    if (normalize) F2_TRY(f2_cnn_scale_set(ctx, cnn, 0, &S));
+    else F2_TRY(forward_measures(ctx, cnn, &measure));
+    if (!normalize && !host) F2_TRY(forward_scale_set(ctx, cnn, measure, windows, n, &S, &bound));
+
+    F2_HIP(ctx, hipMemsetAsync(d_counts, 0, 8 * 5 * (size_t)G, ctx->stream));
+    F2_HIP(ctx, hipMemsetAsync((int*)ctx->flags.ptr + SCORE_WORD, 0, sizeof(int), ctx->stream));
+    F2_TRY(reset_flag(ctx));
+    for (int64_t s = 0; s < n; s += chunk) {
+        const int64_t m = n - s < chunk ? n - s : chunk;
+        const float* d_w = windows + (size_t)s * xs;
+        const uint8_t* d_signs = signs + s;
+        const int32_t* d_groups = groups_or_null ? groups_or_null + s : nullptr;
+        if (host) {
+            // The windows (up to 92 MB a chunk) go up straight from the caller's memory, as in f2_cnn_forward: the pinned buffers
+            // of f2_upload_async would cost a host copy of every chunk first. The caller's memory is only read and outlives the
+            // copies (the call waits for the stream before it returns); stage_in / stage_aux are reused in stream order, behind the
+            // kernels of the chunk before, so the chunks need no wait of their own. Signs and groups: the pinned ring.
+            F2_HIP(ctx, hipMemcpyAsync(ctx->stage_in.ptr, d_w, sizeof(float) * xs * (size_t)m, hipMemcpyHostToDevice, ctx->stream));
+            F2_TRY(f2_upload_async(ctx, s_signs, d_signs, (size_t)m));
+            if (d_groups) {
+                F2_TRY(f2_upload_async(ctx, s_groups, d_groups, sizeof(int32_t) * (size_t)m));
+                d_groups = s_groups;
+            }
+            d_w = (const float*)ctx->stage_in.ptr;
+            d_signs = s_signs;
+        }
+        if (normalize) {
+            F2_TRY(f2_launch_normalize_windows(ctx, d_w, m, (int)xs, (float*)ctx->xbuf.ptr, (int*)ctx->flags.ptr));
+            d_w = (const float*)ctx->xbuf.ptr;
+        } else if (host) {
+            double b = -1.0;
+            F2_TRY(forward_scale_set(ctx, cnn, measure, d_w, m, &S, &b));
+            bound = chunks_bound(bound, b);
+        }
+        float* d_scores = own_scores ? s_scores : scores_or_null + 2 * s;
+        uint8_t* d_labels = own_labels ? s_labels : labels_or_null + s;
+        F2_TRY(cnn_forward_device(ctx, cnn, S, d_w, m, d_scores, d_labels));
+        F2_TRY(f2_launch_score_tally(ctx, d_scores, d_labels, d_signs, d_groups, G, m, d_counts, d_partial, d_loss,
+                                     (int*)ctx->flags.ptr + SCORE_WORD));
+        if (host && scores_or_null)
+            F2_HIP(ctx, hipMemcpyAsync(scores_or_null + 2 * s, d_scores, sizeof(float) * 2 * (size_t)m, hipMemcpyDeviceToHost, ctx->stream));
+        if (host && labels_or_null)
+            F2_HIP(ctx, hipMemcpyAsync(labels_or_null + s, d_labels, (size_t)m, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    if (!normalize) cnn->last_input_bound = bound;   // (normalize = 1 measures nothing and leaves it alone, as f2_eval_* do)
+    F2_HIP(ctx, hipMemcpyAsync(counts, d_counts, sizeof(int64_t) * 4 * (size_t)G, hipMemcpyDeviceToHost, ctx->stream));
+    F2_HIP(ctx, hipMemcpyAsync(loss_sum, d_loss, sizeof(double) * (size_t)G, hipMemcpyDeviceToHost, ctx->stream));
+    F2_HIP(ctx, hipMemcpyAsync(ctx->host_flags + SCORE_WORD, (int*)ctx->flags.ptr + SCORE_WORD, sizeof(int), hipMemcpyDeviceToHost,
+                               ctx->stream));
+    F2_TRY(finish_positive(ctx));
+    const int wrong = ctx->host_flags[SCORE_WORD];
+    F2_CHECK(ctx, !(wrong & 1), F2_ERR_INVALID, "a sign is neither 0 nor 1");
+    F2_CHECK(ctx, !(wrong & 2), F2_ERR_INVALID, "a group lies outside [0, %d)", G);
     return F2_OK;
 }
 

@@ -172,6 +172,33 @@ class F2CNNModel:
         ctx.cnn_forward(self.handle(ctx), x, x.shape[0], scores, labels, _lib.MEM_HOST)
         return scores, labels
 
+    def evaluate(self, x, y, groups=None, n_groups=1, normalize=False, ctx=None):
+        """(loss, accuracy) of the model on the windows x (n, rows, channels[,1]) with the signs y (n, 0 / 1): keras
+        model.evaluate's pair (reference Training.py:136) - the mean of -ln(clip(score of the true class, 1e-7, 1)) and
+        correct / n - formed on the device in one f2_cnn_score_windows call. normalize=True: x are raw envelope windows (the
+        rows of input_data.npy), normalised on the device as normalizeInputBatch does. With `groups` (n integers in
+        [0, n_groups)) it returns (loss, accuracy, counts (n_groups, 2, 2) int64 [group][sign][label], loss_sum (n_groups,))."""
+        ctx = ctx or _lib.default_context()
+        x = np.asarray(x)
+        if x.ndim == 4 and x.shape[-1] == 1:
+            x = x[..., 0]
+        if x.ndim != 3 or x.shape[1:] != (self.rows, self.channels):
+            raise ValueError(f"expected input of shape (n,{self.rows},{self.channels}[,1]), got {x.shape}")
+        n = x.shape[0]
+        y = np.asarray(y).reshape(-1)
+        if len(y) != n or (groups is not None and len(groups) != n):
+            raise ValueError("x, y and groups must have one entry per window")
+        if n and (y.min() < 0 or y.max() > 1):
+            raise ValueError("y holds the signs 0 (falling) and 1 (rising)")
+        G = int(n_groups) if groups is not None else 1
+        counts, loss_sum = ctx.cnn_score_windows(self.handle(ctx), np.ascontiguousarray(x, dtype=np.float32), n, bool(normalize),
+                                                 y.astype(np.uint8), None if groups is None else np.asarray(groups, np.int32), G,
+                                                 None, None, _lib.MEM_HOST)
+        total = max(n, 1)
+        loss = float(loss_sum.sum()) / total
+        accuracy = float(counts[:, 0, 0].sum() + counts[:, 1, 1].sum()) / total
+        return (loss, accuracy) if groups is None else (loss, accuracy, counts, loss_sum)
+
 
 def load_model(path):
     """Counterpart of keras.models.load_model: the .npz container, or a Keras HDF5 file where h5py is installed."""

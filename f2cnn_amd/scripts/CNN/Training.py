@@ -6,6 +6,9 @@
 accuracy (min_delta 0.01, patience 5), trained with PyTorch-ROCm autograd as the scope table asks. Training only
 produces weights; every forward pass used for evaluation is HIP kernel K4 (the trained weights are written in the
 ``.npz`` container K4 loads, under the reference's file name ``last_trained_model``).
+
+``TestModel`` (`cnn test`, not in the reference) is ``model.evaluate(x_test, y_test)`` (:136) for a saved model, broken down
+by a column of the label CSV: one ``f2_cnn_score_windows`` call on the stored windows.
 """
 import csv
 import json
@@ -221,3 +224,98 @@ def TrainAndPlotLoss(labelFile=None, inputFile=None, device=None, seed=None):
         json.dump(history, fp)
     print("History saved as 'last_trained_model_results.json'")
     return model, history
+
+
+MAX_TEST_GROUPS = 1024      # f2_cnn_score_windows tallies up to this many groups
+TEST_BY = ("set", "region", "speaker", "phoneme")
+TEST_ROWS = ("test", "train", "all")
+
+
+def GroupLabelRows(csv_rows, by=None, rows='test'):
+    """The rows of a label CSV (lists of strings, columns LabelDataGenerator.CSV_COLUMNS) that `cnn test` scores, and their
+    groups. rows = 'test' keeps the rows whose first column is 'TEST', 'train' the others (SeparateTestTrain's split), 'all'
+    every row. Returns (index, signs, group_ids, names): index (int64) = the kept rows' positions, which are also their rows
+    in input_data.npy; signs (uint8) their last column; names = the sorted distinct values of column `by` among the kept rows
+    and group_ids (int32) each kept row's position in names - by = None: one group 'all'. No device call in here."""
+    from ..processing.LabelDataGenerator import CSV_COLUMNS
+    if rows not in TEST_ROWS:
+        raise ValueError("rows must be one of {}, not {!r}".format(TEST_ROWS, rows))
+    if by is not None and by not in TEST_BY:
+        raise ValueError("by must be one of {}, not {!r}".format(TEST_BY, by))
+    set_col, sign_col = CSV_COLUMNS.index('set'), CSV_COLUMNS.index('sign')
+    index, signs, keys = [], [], []
+    for i, row in enumerate(csv_rows):
+        is_test = row[set_col] == 'TEST'
+        if rows == 'all' or is_test == (rows == 'test'):
+            sign = int(row[sign_col])
+            if sign not in (0, 1):
+                raise ValueError("row {}: sign {!r} is neither 0 nor 1".format(i, row[sign_col]))
+            index.append(i)
+            signs.append(sign)
+            keys.append('all' if by is None else row[CSV_COLUMNS.index(by)])
+    names = sorted(set(keys))
+    if len(names) > MAX_TEST_GROUPS:
+        raise ValueError("column '{}' has {} distinct values among the selected rows; at most {} groups can be tallied"
+                         .format(by, len(names), MAX_TEST_GROUPS))
+    if not names:
+        names = ['all'] if by is None else []
+    where = {name: g for g, name in enumerate(names)}
+    return (numpy.array(index, numpy.int64), numpy.array(signs, numpy.uint8),
+            numpy.array([where[k] for k in keys], numpy.int32), names)
+
+
+def TestResultPath(model):
+    """Where TestModel writes its numbers: '<model>_test.json' next to the model file, a trailing '.npz' of the name dropped
+    ('weights.npz' -> 'weights_test.json', as F2CNNModel.load finds 'weights.npz' under 'weights'). None for a model that is
+    not a file name: an F2CNNModel object has no place of its own, and nothing is written."""
+    if not isinstance(model, str):
+        return None
+    return (model[:-len('.npz')] if model.endswith('.npz') else model) + '_test.json'
+
+
+def TestModel(labelFile=None, inputFile=None, model='last_trained_model', by=None, rows='test', ctx=None):
+    """`cnn test`: scores a saved model on the labelled windows of `prepare input` / `prepare label` without retraining -
+    keras model.evaluate (Training.py:136) - with a breakdown by the CSV column `by` ('set', 'region', 'speaker', 'phoneme').
+    The selected rows of the .npy (memory-mapped: only they are copied) go through one f2_cnn_score_windows call, which
+    normalises them on the device as normalizeInputBatch does. Prints one line per group and the reference's 'Test loss:' /
+    'Test accuracy:' lines for the total and returns the same numbers as a dict. `model` is a file name (written too:
+    TestResultPath(model), '<model>_test.json') or an F2CNNModel object (nothing is written)."""
+    from ...model import F2CNNModel
+    inputPath = inputFile or os.path.join('trainingData', 'last_input_data.npy')
+    labelPath = labelFile or os.path.join('trainingData', 'label_data.csv')
+    with open(labelPath, 'r') as labels:
+        csv_rows = [row for row in csv.reader(labels) if row]
+    index, signs, group_ids, names = GroupLabelRows(csv_rows, by, rows)
+    data = numpy.load(inputPath, mmap_mode='r')
+    if len(index) and index[-1] >= len(data):
+        raise ValueError("{} has {} windows, {} has {} rows".format(inputPath, len(data), labelPath, len(csv_rows)))
+    x = numpy.ascontiguousarray(data[index], dtype=numpy.float32) if len(index) else numpy.empty((0,) + data.shape[1:], numpy.float32)
+    net = model if isinstance(model, F2CNNModel) else F2CNNModel.load(model)
+    G = max(len(names), 1)
+    try:
+        loss, acc, counts, loss_sum = net.evaluate(x, signs, groups=group_ids, n_groups=G, normalize=True, ctx=ctx)
+    except _lib.F2Error as e:
+        if e.code == _lib.F2_ERR_NONPOSITIVE:
+            raise ValueError("values must all be positive")
+        raise
+    result = {"model": model if isinstance(model, str) else None, "input": inputPath, "label": labelPath, "rows": rows, "by": by,
+              "windows": int(len(index)), "loss": loss, "accuracy": acc, "groups": []}
+    print("{:<12} {:>9} {:>10} {:>9}   [falling->falling falling->rising | rising->falling rising->rising]".format(
+        by or 'group', 'windows', 'loss', 'accuracy'))
+    for g, name in enumerate(names):
+        c = counts[g]
+        n_g = int(c.sum())
+        entry = {"name": name, "windows": n_g, "loss": float(loss_sum[g]) / n_g if n_g else None,
+                 "accuracy": float(c[0, 0] + c[1, 1]) / n_g if n_g else None, "counts": c.tolist(), "loss_sum": float(loss_sum[g])}
+        result["groups"].append(entry)
+        print("{:<12} {:>9} {:>10} {:>9}   [{} {} | {} {}]".format(
+            name, n_g, "-" if not n_g else "{:.4f}".format(entry["loss"]), "-" if not n_g else "{:.4f}".format(entry["accuracy"]),
+            int(c[0, 0]), int(c[0, 1]), int(c[1, 0]), int(c[1, 1])))
+    print('Test loss:', loss)
+    print('Test accuracy:', acc)
+    out = TestResultPath(model)
+    if out is not None:
+        with open(out, 'w') as fp:
+            json.dump(result, fp)
+        print("Results saved as '{}'".format(out))
+    return result

@@ -17,7 +17,8 @@
  *     context, so a new batch shape does not wait for the stream either. What does wait: a scratch
  *     buffer that has to grow (the first call of a size), and the calls that hand an error flag of
  *     the device back (f2_gather_windows with normalisation, f2_eval_*: F2_ERR_NONPOSITIVE;
- *     f2_eval_noise_sweep also waits to hand back sigma and stats).
+ *     f2_eval_noise_sweep also waits to hand back sigma and stats, f2_label_accuracy and
+ *     f2_cnn_score_windows their counts).
  *   - ragged batches: utterance b has n_b = offsets[b+1]-offsets[b] samples; its wave starts at
  *     wave + offsets[b]; its (C, n_b) C-order float64 matrix starts at out + C*offsets[b]. For a
  *     uniform batch this is the plain [B][C][N] layout, and each utterance's block is bit-for-bit the
@@ -64,7 +65,7 @@ enum { F2_FFT_F32 = 0, F2_FFT_F64 = 1 };
 int f2_version(void);   /* 100 * major + minor; 101 added f2_eval_batch, 102 f2_host_alloc + F2_MEM_HOST_ASYNC, 103 f2_ctx_set_option, 105 f2_spectral_guard_read + f2_cnn_get_info,
                            106 f2_cnn_forward accepts any finite input on the split path (scales from the input's range; the
                            f2_cnn_get_info keys "f16x3_ok", "f16x3_check_diff", "last_input_bound"), 107 f2_input_batch,
-                           108 f2_eval_batch_strided, 109 f2_eval_noise_sweep, 110 f2_label_accuracy */
+                           108 f2_eval_batch_strided, 109 f2_eval_noise_sweep, 110 f2_label_accuracy, 111 f2_cnn_score_windows */
 int f2_device_count(int* count);
 int f2_ctx_create(int device, f2_ctx** ctx);
 int f2_ctx_destroy(f2_ctx* ctx);
@@ -240,8 +241,8 @@ int f2_cnn_destroy(f2_ctx* ctx, f2_cnn* cnn);
  * "f16x3_ok" = 1 if the split-fp16 path serves this network: f2_cnn_create held it against the float32 kernels on its
  * self-check batch (inputs in [0, 1), and the same x 2^10 with the scales of B = 2^10) and it agreed to 5e-6, else 0 (the
  * network runs on the float32 kernels, said on stderr); "f16x3_check_diff" = the larger of the two score differences
- * measured (-1: no split path); "last_input_bound" = B of the last f2_cnn_forward on this network (a host call of several
- * chunks: the largest), -1 if the float32 kernels ran, 0 before the first call. */
+ * measured (-1: no split path); "last_input_bound" = B of the last f2_cnn_forward (or f2_cnn_score_windows with normalize = 0) on
+ * this network (a host call of several chunks: the largest), -1 if the float32 kernels ran, 0 before the first call. */
 int f2_cnn_get_info(f2_ctx* ctx, const f2_cnn* cnn, const char* key, double* value);
 int f2_cnn_forward(f2_ctx* ctx, const f2_cnn* cnn, const float* x, int64_t n, float* scores,
                    uint8_t* labels, int mem_space);
@@ -376,6 +377,50 @@ int f2_label_accuracy(f2_ctx* ctx, const uint8_t* labels /* mem_space */,
                       const uint8_t* ref_signs /* host */, int R,
                       int64_t origin, int hop, int step,
                       int64_t* counts /* host, U*4: counts[4u + 2*ref + pred] */, int mem_space);
+
+/* ---- `cnn test`: a model scored on stored, labelled windows in one device pass ---------------------------------------------
+ * scripts/CNN/Training.py:136 (model.evaluate(x_test, y_test), and validation_data in every epoch) answers "how good is this
+ * model on the labelled windows" - the rows of input_data.npy (`prepare input`) with the signs of label_data.csv (`prepare
+ * label`) - after normalising every window on the host (:71-75). Here: the stored float32 windows go up once, are normalised on
+ * the device, run through the forward chain of f2_cnn_forward and are tallied by a kernel, broken down by a caller-given group.
+ *   windows   (n, rows, C) float32 in mem_space, rows x C being the window shape of `cnn`
+ *   normalize 1: raw envelope windows. Each is normalised with the arithmetic of f2_gather_windows (normalize = 1): values
+ *             widened to float64, min / max over the window, (ln v - ln min) / (ln max - ln min) in float64, rounded once to
+ *             float32; an all-equal window gives zeros; a value <= 0 or a NaN anywhere: F2_ERR_NONPOSITIVE. Bit for bit what
+ *             f2_gather_windows returns for the same window held in an envelope (the convention this package trains under: not
+ *             the reference's float32 logarithms of Training.py:71-75). The network then runs with the scales of the input bound
+ *             B = 1, without the range pass, as in f2_eval_*.
+ *             0: the windows go to the network as they are, by f2_cnn_forward's route (range pass, scale set or float32 kernels;
+ *             the range is that of the whole call for device memory and of each chunk of 16384 windows for host memory, as there).
+ *             Like f2_cnn_forward it then sets "last_input_bound" of f2_cnn_get_info; a call with normalize = 1 measures no
+ *             range and leaves that value as it was.
+ *   scores_or_null (n, 2), labels_or_null (n), in mem_space: bit for bit what f2_cnn_forward returns for the same (normalised)
+ *             windows in the same mem_space; without them the scores and labels of a chunk live in context scratch.
+ *   signs     n uint8 in mem_space: 0 falling, 1 rising (the last column of label_data.csv)
+ *   groups_or_null  n int32 in mem_space, the group of every window, in [0, G); NULL requires G == 1: everything is group 0
+ *   counts    host, G*4: counts[4g + 2*sign + pred] = windows of group g with that sign and label. Workgroup counts in LDS, then
+ *             64-bit vector integer atomics on a zeroed buffer: the same bits on every call. Accuracy of a group =
+ *             (counts[4g] + counts[4g+3]) / (sum of the four).
+ *   loss_sum  host, G: sum over the group's windows of -ln(min(max((double)scores[i][signs[i]], 1e-7), 1.0)) in float64, the
+ *             categorical cross-entropy as Keras clips it. Mean loss = loss_sum[g] / windows of g, formed by the caller. No
+ *             floating-point atomics: a workgroup of 256 windows adds the terms of each group in window order, the workgroups'
+ *             partial sums are added in workgroup order, chunk after chunk - the same bits on every call and in both memory
+ *             spaces (up to the device's logarithm, a few ulp, against another machine's).
+ * The call works in chunks of 16384 windows (host memory: one chunk staged at a time) and waits for the stream before it returns
+ * (it hands back counts, loss_sum and the error flags), whatever mem_space is.
+ * F2_ERR_INVALID, with nothing launched and counts / loss_sum untouched: NULL ctx, cnn, counts or loss_sum; NULL windows or signs
+ * with n > 0; n < 0; G < 1; NULL groups with G != 1; normalize other than 0 / 1; a network on another device; a mem_space other
+ * than F2_MEM_HOST / F2_MEM_DEVICE. F2_ERR_UNSUPPORTED, likewise: G > 1024. Found by the kernels, so after the pass and with
+ * counts / loss_sum unspecified: a sign above 1 or a group outside [0, G) -> F2_ERR_INVALID (the message names the sign if both
+ * occurred); F2_ERR_NONPOSITIVE as above. n == 0: F2_OK with counts and loss_sum zeroed.
+ */
+int f2_cnn_score_windows(f2_ctx* ctx, const f2_cnn* cnn,
+                         const float* windows /* (n, rows, C) float32, mem_space */, int64_t n, int normalize,
+                         const uint8_t* signs /* n, mem_space: 0 falling, 1 rising */,
+                         const int32_t* groups_or_null /* n, mem_space: group of every window, in [0, G) */, int G,
+                         float* scores_or_null /* (n, 2), mem_space */, uint8_t* labels_or_null /* n, mem_space */,
+                         int64_t* counts /* host, G*4: counts[4g + 2*sign + pred] */,
+                         double* loss_sum /* host, G */, int mem_space);
 
 #ifdef __cplusplus
 }
