@@ -20,7 +20,7 @@ PER_FILE_FLAGS = {"f2_envelope.hip": ("-fno-slp-vectorize",),
 
 # Kernels whose inline-asm loads are waited for by hand (s_waitcnt counts written for ONE register allocation): a spill or
 # scratch slot in them means the compiler moved registers the waits do not cover. The build reports it; at run time
-# f2_cnn_create's self-check decides whether they are used (csrc/f2_cnn.hip: cnn_ws_selfcheck).
+# f2_cnn_create's self-check decides whether they are used (csrc/f2_cnn.hip: cnn_selfcheck).
 NO_SCRATCH_KERNELS = {"f2_cnn_ws.hip": ("k_conv12_ws", "k_conv34_ws", "k_dense1_ws")}
 RESOURCE_REPORT = os.path.join(LIB_DIR, "kernel_resources.txt")
 

@@ -25,39 +25,11 @@
 #include <algorithm>
 #include <cmath>
 
-#include "f2_internal.h"
+#include "f2_cnn_dims.h"
 
 namespace {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-constexpr int C1 = 32, C2 = 32, C3 = 64, C4 = 64, D1 = 516, D2 = 2;
-constexpr int PW = 34;  // patch width: 32 output columns + 2
-
-struct Dims {
-    int H1, W1;        // input / conv1 output
-    int H2, W2;        // conv2 output (valid)
-    int Hp1, Wp1;      // after pool 1 (= conv3 output, same)
-    int H4, W4;        // conv4 output (valid)
-    int Hp2, Wp2;      // after pool 2
-    int flat;
-};
-
-Dims make_dims(int rows, int channels) {
-    Dims d;
-    d.H1 = rows;
-    d.W1 = channels;
-    d.H2 = rows - 2;
-    d.W2 = channels - 2;
-    d.Hp1 = d.H2 / 2;
-    d.Wp1 = d.W2 / 2;
-    d.H4 = d.Hp1 - 2;
-    d.W4 = d.Wp1 - 2;
-    d.Hp2 = d.H4 / 2;
-    d.Wp2 = d.W4 / 2;
-    d.flat = d.Hp2 > 0 && d.Wp2 > 0 ? d.Hp2 * d.Wp2 * C4 : 0;
-    return d;
-}
 
 // ---- conv3 / conv4 for pooled inputs that do not have four rows: implicit GEMM on v_mfma_f32_32x32x2_f32 ----
 // NSPLIT waves share one task (one patch): each takes COUT/32/NSPLIT of the output tiles, so a 64-channel layer
@@ -308,7 +280,6 @@ __global__ __launch_bounds__(512) void k_conv12_mfma(const float* __restrict__ x
 // one tile of 30 conv4 output columns (15 pooled). Phase 1: wave w computes conv3 row w, 32 columns x 64 channels
 // (two N tiles) from a 6 x 34 x 32 patch of the pooled conv2 tensor, writes bias + ReLU into a 4 x 34 x 64 LDS patch.
 // Phase 2: wave w computes conv4 row w & 1, N tile w >> 1 from that patch; the rows meet through LDS for the pool.
-constexpr int T34 = 30;   // conv4 output columns per tile (32 conv3 columns)
 __global__ __launch_bounds__(256) void k_conv34_mfma(const float* __restrict__ in, const float* __restrict__ w3,
                                                      const float* __restrict__ b3, const float* __restrict__ w4,
                                                      const float* __restrict__ b4, float* __restrict__ out, int Win,
@@ -779,11 +750,11 @@ int launch_conv12_h16(f2_ctx* ctx, const f2_cnn* cnn, const f2_scale_set* S, con
     static_assert(lds <= 80 * 1024, "at least two workgroups per CU");
     auto kern = k_conv12_h16x3<RP, TPW>;
     F2_HIP(ctx, hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    const int64_t blocks = (tasks + TPW - 1) / TPW;
-    F2_CHECK(ctx, blocks < (int64_t(1) << 31), F2_ERR_UNSUPPORTED, "CNN chunk too large");
+    unsigned blocks;
+    F2_TRY(cnn_grid(ctx, (tasks + TPW - 1) / TPW, &blocks));
     f2_split_scales sc = S->sc;
     if (!fused) sc.c2 = S->c2_true;
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(128 * RP * TPW), lds, ctx->stream, d_x, cnn->t(0), cnn->t(1),
+    hipLaunchKernelGGL(kern, dim3(blocks), dim3(128 * RP * TPW), lds, ctx->stream, d_x, cnn->t(0), cnn->t(1),
                        (const h16x8*)(cnn->blob16 + cnn->off16[0]), fused ? S->sbias + F2_SB_B2 : cnn->t(3), a2, H1, W1, n, sc);
     return F2_OK;
 }
@@ -794,10 +765,6 @@ int launch_conv12_h16(f2_ctx* ctx, const f2_cnn* cnn, const f2_scale_set* S, con
 // chunks of 64: the 32 x 64 activation chunk is staged in LDS (double buffered, 16-byte loads, pitch 68) and
 // read back as the A operand with ds_read_b128; the B operand comes from the re-laid-out weights
 // wt[chunk][h][q][n (padded to 544)][4], one 16-byte load per four MFMA steps.
-constexpr int D1_TILES = (D1 + 31) / 32;   // 17
-constexpr int D1_NPAD = D1_TILES * 32;     // 544
-constexpr int D1_KC = 64;
-constexpr int D1_WAVES = 6;
 constexpr int D1_MT = 2;                   // M tiles (32 windows each) per workgroup: every weight load feeds 2 MFMA tiles
 __global__ __launch_bounds__(D1_WAVES * 64) void k_dense1_mfma(const float* __restrict__ a, const float* __restrict__ wt,
                                                                const float* __restrict__ bias, float* __restrict__ out,
@@ -1038,9 +1005,57 @@ int launch_conv(f2_ctx* ctx, const float* in, const float* w, const float* b, fl
     auto kern = k_conv3x3_mfma<CIN, COUT, SAME, POOL, WAVES, NSPLIT>;
     if (lds > 64 * 1024)
         F2_HIP(ctx, hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    const int64_t blocks = (tasks + TPB - 1) / TPB;
-    F2_CHECK(ctx, blocks < (int64_t(1) << 31), F2_ERR_UNSUPPORTED, "CNN chunk too large");
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(WAVES * 64), lds, ctx->stream, in, w, b, out, Hin, Win, n);
+    unsigned blocks;
+    F2_TRY(cnn_grid(ctx, (tasks + TPB - 1) / TPB, &blocks));
+    hipLaunchKernelGGL(kern, dim3(blocks), dim3(WAVES * 64), lds, ctx->stream, in, w, b, out, Hin, Win, n);
+    F2_HIP(ctx, hipGetLastError());
+    return F2_OK;
+}
+
+// conv1 + conv2 + pool of the per-tile kernels (conv1 is evaluated inside conv2's patch staging)
+int launch_conv12(f2_ctx* ctx, const f2_cnn* cnn, const f2_scale_set* S, bool split, const Dims& d, const float* d_x, int64_t n,
+                  float* a2) {
+    if (split) {
+        // four output rows per task where the pooled height allows (the reference's 11-row windows: 4 pooled rows)
+        F2_TRY(d.Hp1 % 2 == 0 ? (launch_conv12_h16<2, 1>(ctx, cnn, S, d_x, a2, d.H1, d.W1, n, d.Hp1 == 4))
+                              : (launch_conv12_h16<1, 2>(ctx, cnn, S, d_x, a2, d.H1, d.W1, n, d.Hp1 == 4)));
+    } else {
+        constexpr size_t lds12 = sizeof(float) * 4 * (4 * PW * (C1 + 4) + 6 * (PW + 2));
+        F2_HIP(ctx, hipFuncSetAttribute((const void*)k_conv12_mfma, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds12));
+        unsigned blocks;
+        F2_TRY(cnn_grid(ctx, (n * d.Hp1 * d.xtiles12() + 3) / 4, &blocks));
+        hipLaunchKernelGGL(k_conv12_mfma, dim3(blocks), dim3(512), lds12, ctx->stream, d_x, cnn->t(0), cnn->t(1), cnn->t(2), cnn->t(3),
+                           a2, d.H1, d.W1, n);
+    }
+    F2_HIP(ctx, hipGetLastError());
+    return F2_OK;
+}
+
+// conv3 + conv4 + pool of the per-tile kernels. Four pooled rows (the reference's 11-row windows): one kernel, conv3's output
+// stays in LDS; any other height: the float32 kernels layer by layer, through a3
+int launch_conv34(f2_ctx* ctx, const f2_cnn* cnn, const f2_scale_set* S, bool split, const Dims& d, const float* a2, int64_t n,
+                  float* a3, float* a4) {
+    if (d.Hp1 != 4) {
+        F2_TRY((launch_conv<C2, C3, true, false, 8, 2>(ctx, a2, cnn->t(4), cnn->t(5), a3, d.Hp1, d.Wp1, n)));
+        return launch_conv<C3, C4, false, true, 4, 2>(ctx, a3, cnn->t(6), cnn->t(7), a4, d.Hp1, d.Wp1, n);
+    }
+    const int xtiles = d.xtiles34();
+    unsigned blocks;
+    F2_TRY(cnn_grid(ctx, n * xtiles, &blocks));
+    if (split) {
+        constexpr size_t lds16 = 2 * (size_t)(6 * PW * PA16) + (size_t)(4 * PW * PB16);
+        static_assert(3 * lds16 <= 160 * 1024, "three workgroups per CU");
+        F2_HIP(ctx, hipFuncSetAttribute((const void*)k_conv34_h16x3, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds16));
+        hipLaunchKernelGGL(k_conv34_h16x3, dim3(blocks), dim3(256), lds16, ctx->stream, a2, (const h16x8*)(cnn->blob16 + cnn->off16[1]),
+                           S->sbias + F2_SB_B3F, (const h16x8*)(cnn->blob16 + cnn->off16[2]), S->sbias + F2_SB_B4, a4, d.Wp1, xtiles, n,
+                           S->sc);
+    } else {
+        constexpr size_t lds34 = sizeof(float) * (6 * PW * (C2 + 4) + 4 * PW * (C3 + 4));
+        static_assert(lds34 <= 80 * 1024, "two workgroups per CU");
+        F2_HIP(ctx, hipFuncSetAttribute((const void*)k_conv34_mfma, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds34));
+        hipLaunchKernelGGL(k_conv34_mfma, dim3(blocks), dim3(256), lds34, ctx->stream, a2, cnn->t(4), cnn->t(5), cnn->t(6), cnn->t(7), a4,
+                           d.Wp1, xtiles, n);
+    }
     F2_HIP(ctx, hipGetLastError());
     return F2_OK;
 }
@@ -1051,112 +1066,86 @@ size_t f2_cnn_workspace_floats(const f2_cnn* cnn) {
     const Dims d = make_dims(cnn->rows, cnn->channels);
     return (size_t)d.Hp1 * d.Wp1 * C2 + (size_t)d.Hp1 * d.Wp1 * C3 + (size_t)d.flat + D1;   // conv1's output never exists
 }
-
-int f2_launch_cnn(f2_ctx* ctx, const f2_cnn* cnn, const f2_scale_set* S, const float* d_x, int64_t n, float* d_ws, float* d_scores,
-                  uint8_t* d_labels) {
-    if (n <= 0) return F2_OK;
-    const Dims d = make_dims(cnn->rows, cnn->channels);
-    float* a4 = d_ws + (size_t)n * d.Hp1 * d.Wp1 * (C2 + C3);
-    F2_TRY(f2_launch_cnn_convs(ctx, cnn, S, d_x, n, d_ws, a4));
-    return f2_launch_cnn_dense(ctx, cnn, S, a4, n, a4 + (size_t)n * d.flat, d_scores, d_labels);
-}
-
 size_t f2_cnn_flat_floats(const f2_cnn* cnn) { return (size_t)make_dims(cnn->rows, cnn->channels).flat; }
 size_t f2_cnn_dense_floats(const f2_cnn* cnn) { return (size_t)make_dims(cnn->rows, cnn->channels).flat + D1; }
 
+// ---- the route: which kernels run (f2_internal.h: f2_cnn_route). These two functions are the only readers of the self-check's
+// verdicts and of the context's three CNN options ----
+f2_cnn_route f2_cnn_capability(const f2_cnn* cnn) {
+    f2_cnn_route r;
+    r.split = cnn->blob16 && cnn->f16x3_ok;
+    r.ws = cnn->blob16 && cnn->ws_ok && f2_cnn_ws_supported(cnn->rows, cnn->channels);
+    r.ws_dense = r.ws && cnn->ws_dense_ok && f2_dense1_ws_takes(cnn->flat, 1);
+    return r;
+}
+
+f2_cnn_route f2_cnn_call_route(const f2_ctx* ctx, const f2_cnn* cnn, bool have_scale_set) {
+    const f2_cnn_route can = f2_cnn_capability(cnn);
+    f2_cnn_route r;
+    r.split = have_scale_set && ctx->opt_cnn_f16x3 && can.split;
+    r.ws = r.split && ctx->opt_cnn_ws && can.ws;
+    r.ws_dense = r.ws && ctx->opt_cnn_ws_dense && can.ws_dense;
+    return r;
+}
+
+int f2_launch_cnn(f2_ctx* ctx, const f2_cnn* cnn, const f2_scale_set* S, f2_cnn_route route, const float* d_x, int64_t n, float* d_ws,
+                  float* d_scores, uint8_t* d_labels) {
+    if (n <= 0) return F2_OK;
+    const Dims d = make_dims(cnn->rows, cnn->channels);
+    float* a4 = d_ws + (size_t)n * d.Hp1 * d.Wp1 * (C2 + C3);
+    F2_TRY(f2_launch_cnn_convs(ctx, cnn, S, route, d_x, n, d_ws, a4));
+    return f2_launch_cnn_dense(ctx, cnn, S, route, a4, n, a4 + (size_t)n * d.flat, d_scores, d_labels);
+}
+
 // conv1 .. conv4 + pools of n windows: d_ws = workspace of (Hp1 Wp1 (C2 + C3)) floats per window, a4 = [n][flat] out
-int f2_launch_cnn_convs(f2_ctx* ctx, const f2_cnn* cnn, const f2_scale_set* S, const float* d_x, int64_t n, float* d_ws, float* a4) {
+int f2_launch_cnn_convs(f2_ctx* ctx, const f2_cnn* cnn, const f2_scale_set* S, f2_cnn_route route, const float* d_x, int64_t n,
+                        float* d_ws, float* a4) {
     if (n <= 0) return F2_OK;
     const Dims d = make_dims(cnn->rows, cnn->channels);
     float* a2 = d_ws;
     float* a3 = a2 + (size_t)n * d.Hp1 * d.Wp1 * C2;
     F2_TRY(f2_prof_begin(ctx, F2_K_CNN));
-    const bool split = S && ctx->opt_cnn_f16x3 && cnn->blob16;
-    const bool ws = split && ctx->opt_cnn_ws && cnn->ws_ok && f2_cnn_ws_supported(cnn->rows, cnn->channels);
-    if (ws) {
+    if (route.ws) {
         // weight-stationary persistent kernels (f2_cnn_ws.hip): conv1 on the matrix cores, one barrier per tile
         F2_TRY(f2_launch_cnn_ws(ctx, cnn, S, d_x, n, a2, a4));
     } else {
-        // conv1 + conv2 + pool (conv1 is evaluated inside conv2's patch staging)
-        const int Ho = d.H1 - 2, Wo = d.W1 - 2;
-        const int64_t tasks = n * (Ho / 2) * (((Wo / 2) * 2 + 31) / 32);
-        if (tasks > 0) {
-            constexpr size_t lds12 = sizeof(float) * 4 * (4 * PW * (C1 + 4) + 6 * (PW + 2));
-            F2_HIP(ctx, hipFuncSetAttribute((const void*)k_conv12_mfma, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds12));
-            const int64_t blocks = (tasks + 3) / 4;
-            F2_CHECK(ctx, blocks < (int64_t(1) << 31), F2_ERR_UNSUPPORTED, "CNN chunk too large");
-            if (split) {
-                // four output rows per task where the pooled height allows (the reference's 11-row windows: 4 pooled rows)
-                if ((Ho / 2) % 2 == 0) F2_TRY((launch_conv12_h16<2, 1>(ctx, cnn, S, d_x, a2, d.H1, d.W1, n, d.Hp1 == 4)));
-                else F2_TRY((launch_conv12_h16<1, 2>(ctx, cnn, S, d_x, a2, d.H1, d.W1, n, d.Hp1 == 4)));
-            } else {
-                hipLaunchKernelGGL(k_conv12_mfma, dim3((unsigned)blocks), dim3(512), lds12, ctx->stream, d_x, cnn->t(0), cnn->t(1),
-                                   cnn->t(2), cnn->t(3), a2, d.H1, d.W1, n);
-            }
-            F2_HIP(ctx, hipGetLastError());
-        }
+        F2_TRY(launch_conv12(ctx, cnn, S, route.split, d, d_x, n, a2));
+        F2_TRY(launch_conv34(ctx, cnn, S, route.split, d, a2, n, a3, a4));
     }
-    if (ws) {
-    } else if (d.Hp1 == 4) {
-        // four pooled rows (the reference's 11-row windows): conv3 + conv4 + pool in one kernel, conv3's output stays in LDS
-        const int xtiles = (2 * d.Wp2 + T34 - 1) / T34;
-        constexpr size_t lds34 = sizeof(float) * (6 * PW * (C2 + 4) + 4 * PW * (C3 + 4));
-        static_assert(lds34 <= 80 * 1024, "two workgroups per CU");
-        F2_HIP(ctx, hipFuncSetAttribute((const void*)k_conv34_mfma, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds34));
-        const int64_t blocks = n * xtiles;
-        F2_CHECK(ctx, blocks < (int64_t(1) << 31), F2_ERR_UNSUPPORTED, "CNN chunk too large");
-        if (split) {
-            constexpr size_t lds16 = 2 * (size_t)(6 * PW * PA16) + (size_t)(4 * PW * PB16);
-            static_assert(3 * lds16 <= 160 * 1024, "three workgroups per CU");
-            F2_HIP(ctx, hipFuncSetAttribute((const void*)k_conv34_h16x3, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds16));
-            hipLaunchKernelGGL(k_conv34_h16x3, dim3((unsigned)blocks), dim3(256), lds16, ctx->stream, a2,
-                               (const h16x8*)(cnn->blob16 + cnn->off16[1]), S->sbias + F2_SB_B3F,
-                               (const h16x8*)(cnn->blob16 + cnn->off16[2]), S->sbias + F2_SB_B4, a4, d.Wp1, xtiles, n, S->sc);
-        } else {
-            hipLaunchKernelGGL(k_conv34_mfma, dim3((unsigned)blocks), dim3(256), lds34, ctx->stream, a2, cnn->t(4), cnn->t(5),
-                               cnn->t(6), cnn->t(7), a4, d.Wp1, xtiles, n);
-        }
-        F2_HIP(ctx, hipGetLastError());
-    } else {
-        F2_TRY((launch_conv<C2, C3, true, false, 8, 2>(ctx, a2, cnn->t(4), cnn->t(5), a3, d.Hp1, d.Wp1, n)));
-        F2_TRY((launch_conv<C3, C4, false, true, 4, 2>(ctx, a3, cnn->t(6), cnn->t(7), a4, d.Hp1, d.Wp1, n)));
-    }
-    F2_TRY(f2_prof_end(ctx, F2_K_CNN));
-    return F2_OK;
+    return f2_prof_end(ctx, F2_K_CNN);
 }
 
 // dense1 + dense2 + softmax + labels of n windows from a4 = [n][flat]; a5 = workspace of D1 floats per window. Its workgroups
 // are (64 windows x 6 of the 17 output tiles): launched per 14 240-window utterance that is 669 workgroups for 512 resident
 // ones - a second round one third full - so f2_eval_batch hands it the windows of several utterances at once.
-int f2_launch_cnn_dense(f2_ctx* ctx, const f2_cnn* cnn, const f2_scale_set* S, const float* a4, int64_t n, float* a5, float* d_scores,
-                        uint8_t* d_labels) {
+int f2_launch_cnn_dense(f2_ctx* ctx, const f2_cnn* cnn, const f2_scale_set* S, f2_cnn_route route, const float* a4, int64_t n, float* a5,
+                        float* d_scores, uint8_t* d_labels) {
     if (n <= 0) return F2_OK;
     const Dims d = make_dims(cnn->rows, cnn->channels);
     F2_TRY(f2_prof_begin(ctx, F2_K_CNN));
-    const bool split = S && ctx->opt_cnn_f16x3 && cnn->blob16;
-    const bool ws = split && ctx->opt_cnn_ws && cnn->ws_ok && f2_cnn_ws_supported(cnn->rows, cnn->channels);
-    if (ws && ctx->opt_cnn_ws_dense && cnn->ws_dense_ok && d.flat % 64 == 0 && d.flat >= 128 && n * (int64_t)d.flat * 4 < (int64_t(1) << 32)) {
+    constexpr int MT16 = D1_MT;   // (3 - 96 windows, one round of workgroups per 14 240-window chunk - measured slower: 0.165 against 0.157 ms)
+    const dim3 grid((unsigned)((n + 32 * D1_MT - 1) / (32 * D1_MT)), (D1_TILES + D1_WAVES - 1) / D1_WAVES);
+    if (route.ws_dense && f2_dense1_ws_takes(d.flat, n)) {   // (a launch beyond its 4 GB of activations: the per-tile kernel)
         F2_TRY(f2_launch_dense1_ws(ctx, cnn, S, a4, n, d.flat, a5));
+    } else if (route.split) {
+        f2_split_scales sc = S->sc;
+        if (d.Hp1 != 4) sc.sin_d = S->sa_d1;     // (conv3 / conv4 of such windows ran on the float32 kernels: true units)
+        hipLaunchKernelGGL(k_dense1_h16x3<MT16>, grid, dim3(D1_WAVES * 64), 0, ctx->stream, a4, (const h16x8*)(cnn->blob16 + cnn->off16[3]),
+                           cnn->t(9), a5, d.flat, n, sc);
     } else {
-        const dim3 grid((unsigned)((n + 32 * D1_MT - 1) / (32 * D1_MT)), (D1_TILES + D1_WAVES - 1) / D1_WAVES);
-        constexpr int MT16 = 2;   // (3 - 96 windows, one round of workgroups per 14 240-window chunk - measured slower: 0.165 against 0.157 ms)
-        const dim3 grid16((unsigned)((n + 32 * MT16 - 1) / (32 * MT16)), (D1_TILES + D1_WAVES - 1) / D1_WAVES);
-        if (split) {
-            f2_split_scales sc = S->sc;
-            if (d.Hp1 != 4) sc.sin_d = S->sa_d1;     // (conv3 / conv4 of such windows ran on the float32 kernels: true units)
-            hipLaunchKernelGGL(k_dense1_h16x3<MT16>, grid16, dim3(D1_WAVES * 64), 0, ctx->stream, a4,
-                               (const h16x8*)(cnn->blob16 + cnn->off16[3]), cnn->t(9), a5, d.flat, n, sc);
-        }
-        else
-            hipLaunchKernelGGL(k_dense1_mfma, grid, dim3(D1_WAVES * 64), 0, ctx->stream, a4, cnn->t(8), cnn->t(9), a5, d.flat, n);
-        F2_HIP(ctx, hipGetLastError());
+        hipLaunchKernelGGL(k_dense1_mfma, grid, dim3(D1_WAVES * 64), 0, ctx->stream, a4, cnn->t(8), cnn->t(9), a5, d.flat, n);
     }
+    F2_HIP(ctx, hipGetLastError());
     hipLaunchKernelGGL(k_dense2_softmax, dim3((unsigned)((n * 8 + 255) / 256)), dim3(256), 0, ctx->stream, a5, cnn->t(10),
                        cnn->t(11), d_scores, d_labels, n);
     F2_HIP(ctx, hipGetLastError());
-    F2_TRY(f2_prof_end(ctx, F2_K_CNN));
-    return F2_OK;
+    return f2_prof_end(ctx, F2_K_CNN);
 }
+
+// the split path's scales are powers of two inside [2^-20, 2^20]
+static double pow2_floor(double v) { return v > 0 && std::isfinite(v) ? std::exp2(std::floor(std::log2(v))) : 1.0; }
+constexpr double SCALE_LO = 0x1p-20, SCALE_HI = 0x1p20;
+static double clamp_scale(double v) { return std::min(std::max(v, SCALE_LO), SCALE_HI); }
 
 // Scales of the split path for network inputs bounded by |x| <= B = 2^e (f2_cnn_split.h): the L1 cascade from conv1's outputs for
 // inputs up to B (upper bounds of every layer's input from the L1 norms of the weights before it) to the largest power of two that
@@ -1164,9 +1153,6 @@ int f2_launch_cnn_dense(f2_ctx* ctx, const f2_cnn* cnn, const f2_scale_set* S, c
 // whatever they are; for e > 0 S.ok is false when a scale would have to leave the clamp (the inputs are too large for fp16
 // pieces: f2_cnn_forward takes the float32 kernels).
 static void derive_scale_set(const f2_cnn_cascade& K, int e, f2_scale_set& S, std::vector<float>& sbias) {
-    auto pow2_floor = [](double v) { return v > 0 && std::isfinite(v) ? std::exp2(std::floor(std::log2(v))) : 1.0; };
-    const double lo = std::exp2(-20.0), hi = std::exp2(20.0);
-    auto clamp_scale = [&](double v) { return std::min(std::max(v, lo), hi); };
     // upper bound of layer l's outputs for inputs bounded by `inb`
     auto l1_bound = [&](int l, double inb) {
         double worst = 0.0;
@@ -1179,7 +1165,7 @@ static void derive_scale_set(const f2_cnn_cascade& K, int e, f2_scale_set& S, st
     double bound = l1_bound(0, B);       // conv1 outputs for inputs bounded by B
     for (int l = 0; l < 4; ++l) {
         const double q = 16384.0 / std::max(bound, 1e-30);
-        ok = ok && q >= lo;                // (false for an infinite or NaN bound too)
+        ok = ok && q >= SCALE_LO;          // (false for an infinite or NaN bound too)
         sa[l] = clamp_scale(pow2_floor(q));
         bound = l1_bound(l + 1, bound);
     }
@@ -1208,7 +1194,7 @@ static void derive_scale_set(const f2_cnn_cascade& K, int e, f2_scale_set& S, st
 
 int f2_cnn_scale_set(f2_ctx* ctx, const f2_cnn* cnn, int e, const f2_scale_set** out) {
     *out = nullptr;
-    if (!cnn->blob16 || !cnn->f16x3_ok || e < 0 || e > F2_BOUND_EXP_MAX) return F2_OK;
+    if (!f2_cnn_capability(cnn).split || e < 0 || e > F2_BOUND_EXP_MAX) return F2_OK;
     std::lock_guard<std::mutex> lock(cnn->sets_mu);
     f2_scale_set* S = cnn->sets[e];
     if (!S) {
@@ -1239,7 +1225,8 @@ int f2_cnn_scale_set(f2_ctx* ctx, const f2_cnn* cnn, int e, const f2_scale_set**
 // and through the per-tile split-fp16 kernels (compiler-scheduled waits); a kernel that disagrees beyond the rounding level
 // of the two summation orders is switched off for this network, loudly. The split path as a whole is then held against the
 // float32 kernels, on that batch (B = 1) and on the batch times 2^10 with the scales of B = 2^10 (the sets f2_cnn_forward takes
-// for inputs beyond [-1, 1]); if it disagrees, this network runs on the float32 kernels.
+// for inputs beyond [-1, 1]); if it disagrees, this network runs on the float32 kernels. Every run names its route: the
+// context's options play no part.
 static int cnn_selfcheck(f2_ctx* ctx, f2_cnn* cnn) {
     if (!cnn->blob16) return F2_OK;
     const bool ws_shape = f2_cnn_ws_supported(cnn->rows, cnn->channels);
@@ -1261,6 +1248,7 @@ static int cnn_selfcheck(f2_ctx* ctx, f2_cnn* cnn) {
     // runs: 0 per-tile split, 1 ws convolutions, 2 ws convolutions + ws dense1, 3 float32 kernels (B = 1 batch);
     //       4 per-tile split, 5 the weight-stationary kernels as decided from runs 0-2, 6 float32 kernels (2^10 batch)
     constexpr int NRUN = 7;
+    const f2_cnn_route F32 = {false, false, false}, TILE = {true, false, false}, WS = {true, true, false}, WS_DENSE = {true, true, true};
     float *d_x = nullptr, *d_ws = nullptr, *d_sc = nullptr;
     const size_t wsf = f2_cnn_workspace_floats(cnn) * NCHK;
     auto cleanup = [&]() {
@@ -1273,19 +1261,15 @@ static int cnn_selfcheck(f2_ctx* ctx, f2_cnn* cnn) {
         cleanup();
         return f2_fail(ctx, F2_ERR_NOMEM, "self-check buffers of the CNN kernels");
     }
-    const int o_b = ctx->opt_cnn_f16x3, o_w = ctx->opt_cnn_ws, o_d = ctx->opt_cnn_ws_dense;
     const bool prof = ctx->prof_on;
     ctx->prof_on = false;
     std::vector<float> sc(NRUN * 2 * NCHK, 0.f);
     std::vector<bool> ran(NRUN, false);
     int rc = F2_OK;
     hipError_t e = hipMemcpyAsync(d_x, x.data(), x.size() * 4, hipMemcpyHostToDevice, ctx->stream);
-    auto run = [&](int k, int big, const f2_scale_set* S, int ws, int ws_dense) {
+    auto run = [&](int k, int big, const f2_scale_set* S, f2_cnn_route route) {
         if (e != hipSuccess || rc != F2_OK) return;
-        ctx->opt_cnn_f16x3 = 1;
-        ctx->opt_cnn_ws = ws;
-        ctx->opt_cnn_ws_dense = ws_dense;
-        rc = f2_launch_cnn(ctx, cnn, S, d_x + (size_t)big * per * NCHK, NCHK, d_ws, d_sc + (size_t)k * 2 * NCHK, nullptr);
+        rc = f2_launch_cnn(ctx, cnn, S, route, d_x + (size_t)big * per * NCHK, NCHK, d_ws, d_sc + (size_t)k * 2 * NCHK, nullptr);
         ran[k] = true;
     };
     auto fetch = [&]() {
@@ -1300,12 +1284,12 @@ static int cnn_selfcheck(f2_ctx* ctx, f2_cnn* cnn) {
         }
         return m;
     };
-    run(0, 0, S1, 0, 0);
+    run(0, 0, S1, TILE);
     if (ws_shape) {
-        run(1, 0, S1, 1, 0);
-        run(2, 0, S1, 1, 1);
+        run(1, 0, S1, WS);
+        run(2, 0, S1, WS_DENSE);
     }
-    run(3, 0, nullptr, 0, 0);
+    run(3, 0, nullptr, F32);
     fetch();
     if (ws_shape && e == hipSuccess && rc == F2_OK) {
         cnn->ws_check_diff = maxdiff(1, 0);
@@ -1321,17 +1305,14 @@ static int cnn_selfcheck(f2_ctx* ctx, f2_cnn* cnn) {
                             "self-check batch: not used for this network\n", (double)cnn->ws_dense_check_diff);
         }
     }
-    const bool ws_used = ws_shape && cnn->ws_ok;
-    const int def1 = !ws_used ? 0 : cnn->ws_dense_ok ? 2 : 1;   // the B = 1 run of the kernels this network will use
+    const f2_cnn_route can = f2_cnn_capability(cnn);   // the kernels this network will use, as decided from runs 0-2
+    const int def1 = !can.ws ? 0 : can.ws_dense ? 2 : 1;   // ... and their B = 1 run
     if (Sbig) {
-        run(4, 1, Sbig, 0, 0);
-        if (ws_used) run(5, 1, Sbig, 1, 1);
-        run(6, 1, nullptr, 0, 0);
+        run(4, 1, Sbig, TILE);
+        if (can.ws) run(5, 1, Sbig, can.ws_dense ? WS_DENSE : WS);
+        run(6, 1, nullptr, F32);
         fetch();
     }
-    ctx->opt_cnn_f16x3 = o_b;
-    ctx->opt_cnn_ws = o_w;
-    ctx->opt_cnn_ws_dense = o_d;
     ctx->prof_on = prof;
     cleanup();
     if (rc != F2_OK) return rc;
@@ -1361,6 +1342,66 @@ static void free_cnn(f2_cnn* cnn) {
     delete cnn;
 }
 
+// ---- f2_cnn_create's packing of the weights. A layer's kernel in its Keras layout is the K x N operand w[k][n] of its GEMM
+// (convolutions: k = (dy*3+dx)*Cin + ci) ----
+
+// The float32 kernels' MFMA B operand wt[block][h][s/4][n (npad, zero beyond N)][s%4], k = block*blk + h*blk/2 + s: conv2 .. conv4
+// with blk = Cin (a block per tap), dense1 with blk = D1_KC
+static std::vector<float> relayout_f32(const float* w, size_t K, int N, int blk, int npad) {
+    std::vector<float> dst(K * npad, 0.f);
+    const int half = blk / 2;
+    for (size_t k = 0; k < K; ++k) {
+        const size_t b = k / blk, hh = k % blk / half, s = k % half;
+        for (int n = 0; n < N; ++n) dst[(((b * 2 + hh) * (half / 4) + s / 4) * npad + n) * 4 + s % 4] = w[k * N + n];
+    }
+    return dst;
+}
+
+// What the scales' L1 cascade needs (derive_scale_set): per layer and output column the L1 norm of the weights and |bias|, the
+// weight scales sb = the power of two that puts max |w| into [2^10, 2^11), and the biases of conv2 .. conv4
+static void capture_cascade(f2_cnn_cascade& K, const float* const* tensors, int flat) {
+    auto keep_l1 = [&](int l, const float* w, const float* b, size_t kin, size_t cout) {
+        K.l1[l].resize(cout);
+        K.absb[l].resize(cout);
+        for (size_t co = 0; co < cout; ++co) {
+            double acc = 0.0;
+            for (size_t k = 0; k < kin; ++k) acc += std::fabs((double)w[k * cout + co]);
+            K.l1[l][co] = acc;
+            K.absb[l][co] = std::fabs((double)b[co]);
+        }
+    };
+    const size_t kin[4] = {9 * (size_t)C1, 9 * (size_t)C2, 9 * (size_t)C3, (size_t)flat};
+    const size_t cout[4] = {C2, C3, C4, D1};
+    keep_l1(0, tensors[0], tensors[1], 9, C1);
+    for (int l = 0; l < 4; ++l) {
+        const float* w = tensors[2 + 2 * l];
+        double m = 0.0;
+        for (size_t k = 0; k < kin[l] * cout[l]; ++k) m = std::max(m, std::fabs((double)w[k]));
+        K.sb[l] = clamp_scale(pow2_floor(2048.0 / std::max(m, 1e-30)));
+        keep_l1(l + 1, w, tensors[3 + 2 * l], kin[l], cout[l]);
+    }
+    K.b2.assign(tensors[3], tensors[3] + C2);
+    K.b3.assign(tensors[5], tensors[5] + C3);
+    K.b4.assign(tensors[7], tensors[7] + C4);
+}
+
+// A layer for the split-fp16 kernels (f2_cnn_split.h), appended to w16: w[piece][k / 16][h][n (npad, zero beyond N)][8] with
+// k = 16 (k / 16) + 8 h + e (convolutions: [tap][kb]; dense1: [chunk][ks]), piece 0 = fp16(w scale), piece 1 = fp16(w scale - piece 0).
+// Returns the layer's element offset in w16.
+static size_t pack_f16_pieces(std::vector<uint16_t>& w16, const float* w, size_t K, int N, int npad, float scale) {
+    const size_t pos = w16.size(), per_piece = K * npad;
+    w16.resize(pos + 2 * per_piece, 0);
+    for (size_t k = 0; k < K; ++k)
+        for (int n = 0; n < N; ++n) {
+            const float wv = w[k * N + n] * scale;
+            const _Float16 p0 = (_Float16)wv, p1 = (_Float16)(wv - (float)p0);   // round to nearest even, subnormals kept (as v_cvt_f16_f32)
+            const size_t idx = ((k / 8) * npad + n) * 8 + k % 8;
+            memcpy(&w16[pos + idx], &p0, 2);
+            memcpy(&w16[pos + per_piece + idx], &p1, 2);
+        }
+    return pos;
+}
+
 extern "C" {
 
 int f2_cnn_create(f2_ctx* ctx, const float* const* tensors, int rows, int channels, f2_cnn** out) {
@@ -1370,12 +1411,13 @@ int f2_cnn_create(f2_ctx* ctx, const float* const* tensors, int rows, int channe
     const Dims d = make_dims(rows, channels);
     F2_CHECK(ctx, rows >= 3 && channels >= 3 && d.flat > 0, F2_ERR_INVALID,
              "input of %d x %d is too small for the network (needs a non-empty flatten)", rows, channels);
+    // (every shape f2_cnn_ws_supported accepts has Hp2 = 1 and Wp2 >= 3: flat = 64 Wp2 >= 192 meets k_dense1_ws's conditions on K,
+    // so whether it takes a launch depends on the window count alone - f2_launch_cnn_dense)
     const size_t sizes[12] = {9 * C1, C1, 9 * (size_t)C1 * C2, C2, 9 * (size_t)C2 * C3, C3, 9 * (size_t)C3 * C4, C4,
                               (size_t)d.flat * D1, D1, (size_t)D1 * D2, D2};
     for (int i = 0; i < 12; ++i) F2_CHECK(ctx, tensors[i], F2_ERR_INVALID, "weight tensor %d is NULL", i);
-    size_t dev_sizes[12];
-    for (int i = 0; i < 12; ++i) dev_sizes[i] = sizes[i];
-    dev_sizes[8] = (size_t)d.flat * D1_NPAD;   // dense1 kernel, output dimension padded to whole MFMA tiles
+    size_t dev_sizes[12];   // (dense1 kernel: output dimension padded to whole MFMA tiles)
+    for (int i = 0; i < 12; ++i) dev_sizes[i] = i == 8 ? (size_t)d.flat * D1_NPAD : sizes[i];
     F2_HIP(ctx, hipSetDevice(ctx->device));
     f2_cnn* cnn = new f2_cnn();
     cnn->rows = rows;
@@ -1392,116 +1434,18 @@ int f2_cnn_create(f2_ctx* ctx, const float* const* tensors, int rows, int channe
         delete cnn;
         return f2_fail(ctx, F2_ERR_NOMEM, "hipMalloc(%zu) -> %s", total * sizeof(float), hipGetErrorString(e));
     }
-    // conv2..conv4 kernels are stored as the MFMA B operand wt[tap][h][s/4][cout][s%4] (channel = h*Cin/2 + s);
-    // everything else stays in its Keras layout
-    std::vector<std::vector<float>> relaid(12);
+    // conv2 .. conv4 and dense1 kernels are stored as the MFMA B operand; everything else stays in its Keras layout
     const int conv_cin[3] = {C1, C2, C3}, conv_cout[3] = {C2, C3, C4};
-    for (int l = 0; l < 3; ++l) {
-        const int ti = 2 + 2 * l, ci_n = conv_cin[l], co_n = conv_cout[l], half = ci_n / 2;
-        std::vector<float>& dst = relaid[ti];
-        dst.resize(sizes[ti]);
-        for (int tap = 0; tap < 9; ++tap)
-            for (int hh = 0; hh < 2; ++hh)
-                for (int sidx = 0; sidx < half; ++sidx)
-                    for (int co = 0; co < co_n; ++co)
-                        dst[((((size_t)tap * 2 + hh) * (half / 4) + sidx / 4) * co_n + co) * 4 + sidx % 4] =
-                            tensors[ti][((size_t)tap * ci_n + hh * half + sidx) * co_n + co];
-    }
-    {
-        // dense1 kernel as wt[chunk][h][q][n][4]: k = chunk*64 + h*32 + q*4 + r, zero columns for n >= 516
-        std::vector<float>& dst = relaid[8];
-        dst.assign(dev_sizes[8], 0.f);
-        for (int k = 0; k < d.flat; ++k) {
-            const int kc = k / D1_KC, kk = k % D1_KC, hh = kk / (D1_KC / 2), sidx = kk % (D1_KC / 2);
-            for (int nn = 0; nn < D1; ++nn)
-                dst[((((size_t)kc * 2 + hh) * (D1_KC / 8) + sidx / 4) * D1_NPAD + nn) * 4 + sidx % 4] =
-                    tensors[8][(size_t)k * D1 + nn];
-        }
-    }
-    // conv2 .. conv4 and dense1 kernels once more for the split-fp16 kernels (f2_cnn_split.h): per-layer power-of-two scales,
-    // w[piece][tap][kb][h][cout][8] (channel = 16 kb + 8 h + e), piece 0 = fp16(w sb), piece 1 = fp16(w sb - piece 0)
+    std::vector<std::vector<float>> relaid(12);
+    for (int l = 0; l < 3; ++l) relaid[2 + 2 * l] = relayout_f32(tensors[2 + 2 * l], 9 * (size_t)conv_cin[l], conv_cout[l], conv_cin[l], conv_cout[l]);
+    relaid[8] = relayout_f32(tensors[8], (size_t)d.flat, D1, D1_KC, D1_NPAD);
+    // ... and once more, scaled and in two fp16 pieces, for the split-fp16 kernels
+    capture_cascade(cnn->cascade, tensors, d.flat);
+    const double* sb = cnn->cascade.sb;
     std::vector<uint16_t> w16;
-    {
-        auto pow2_floor = [](double v) { return v > 0 && std::isfinite(v) ? std::exp2(std::floor(std::log2(v))) : 1.0; };
-        auto clamp_scale = [](double v) { return std::min(std::max(v, std::exp2(-20.0)), std::exp2(20.0)); };
-        // what the scales' L1 cascade needs (derive_scale_set): per layer and output column, L1 norm of the weights and |bias|
-        f2_cnn_cascade& K = cnn->cascade;
-        auto keep_l1 = [&](int l, const float* w, const float* b, size_t kin, size_t cout) {
-            K.l1[l].resize(cout);
-            K.absb[l].resize(cout);
-            for (size_t co = 0; co < cout; ++co) {
-                double acc = 0.0;
-                for (size_t k = 0; k < kin; ++k) acc += std::fabs((double)w[k * cout + co]);
-                K.l1[l][co] = acc;
-                K.absb[l][co] = std::fabs((double)b[co]);
-            }
-        };
-        auto max_abs = [](const float* w, size_t n) {
-            double m = 0.0;
-            for (size_t k = 0; k < n; ++k) m = std::max(m, std::fabs((double)w[k]));
-            return m;
-        };
-        const size_t kin[4] = {9 * (size_t)C1, 9 * (size_t)C2, 9 * (size_t)C3, (size_t)d.flat};
-        const size_t cout[4] = {C2, C3, C4, D1};
-        const int wi[4] = {2, 4, 6, 8};
-        keep_l1(0, tensors[0], tensors[1], 9, C1);
-        for (int l = 0; l < 4; ++l) {
-            K.sb[l] = clamp_scale(pow2_floor(2048.0 / std::max(max_abs(tensors[wi[l]], kin[l] * cout[l]), 1e-30)));
-            keep_l1(l + 1, tensors[wi[l]], tensors[wi[l] + 1], kin[l], cout[l]);
-        }
-        K.b2.assign(tensors[3], tensors[3] + C2);
-        K.b3.assign(tensors[5], tensors[5] + C3);
-        K.b4.assign(tensors[7], tensors[7] + C4);
-        const double* sb = K.sb;
-        auto to_f16 = [](float x) -> uint16_t {
-            const _Float16 hv = (_Float16)x;          // round to nearest even, subnormals kept (as v_cvt_f16_f32)
-            uint16_t u;
-            memcpy(&u, &hv, 2);
-            return u;
-        };
-        auto from_f16 = [](uint16_t b) -> float {
-            _Float16 hv;
-            memcpy(&hv, &b, 2);
-            return (float)hv;
-        };
-        size_t pos = 0;
-        for (int l = 0; l < 3; ++l) {
-            const int ti = 2 + 2 * l, ci_n = conv_cin[l], co_n = conv_cout[l], kbn = ci_n / 16;
-            const float scale = (float)sb[l];
-            cnn->off16[l] = pos;
-            const size_t per_piece = (size_t)9 * ci_n * co_n;
-            w16.resize(pos + 2 * per_piece);
-            for (int tap = 0; tap < 9; ++tap)
-                for (int kb = 0; kb < kbn; ++kb)
-                    for (int hh = 0; hh < 2; ++hh)
-                        for (int co = 0; co < co_n; ++co)
-                            for (int e2 = 0; e2 < 8; ++e2) {
-                                const float wv = tensors[ti][((size_t)tap * ci_n + 16 * kb + 8 * hh + e2) * co_n + co] * scale;
-                                const uint16_t p0 = to_f16(wv), p1 = to_f16(wv - from_f16(p0));
-                                const size_t idx = ((((size_t)tap * kbn + kb) * 2 + hh) * co_n + co) * 8 + e2;
-                                w16[pos + idx] = p0;
-                                w16[pos + per_piece + idx] = p1;
-                            }
-            pos += 2 * per_piece;
-        }
-        {   // dense1: w[piece][chunk][ks][h][n (544, zero beyond 516)][8], k = 64 chunk + 16 ks + 8 h + e
-            const float scale = (float)sb[3];
-            cnn->off16[3] = pos;
-            const size_t per_piece = (size_t)d.flat * D1_NPAD;
-            w16.resize(pos + 2 * per_piece, 0);
-            for (int k = 0; k < d.flat; ++k) {
-                const int kc = k / D1_KC, kk = k % D1_KC, ks = kk / 16, hh = (kk % 16) / 8, e2 = kk % 8;
-                for (int nn = 0; nn < D1; ++nn) {
-                    const float wv = tensors[8][(size_t)k * D1 + nn] * scale;
-                    const uint16_t p0 = to_f16(wv), p1 = to_f16(wv - from_f16(p0));
-                    const size_t idx = ((((size_t)kc * 4 + ks) * 2 + hh) * D1_NPAD + nn) * 8 + e2;
-                    w16[pos + idx] = p0;
-                    w16[pos + per_piece + idx] = p1;
-                }
-            }
-            pos += 2 * per_piece;
-        }
-    }
+    for (int l = 0; l < 3; ++l)
+        cnn->off16[l] = pack_f16_pieces(w16, tensors[2 + 2 * l], 9 * (size_t)conv_cin[l], conv_cout[l], conv_cout[l], (float)sb[l]);
+    cnn->off16[3] = pack_f16_pieces(w16, tensors[8], (size_t)d.flat, D1, D1_NPAD, (float)sb[3]);
     const size_t zeros_at = (w16.size() + 127) & ~size_t(127);
     w16.resize(zeros_at + 128, 0);   // 256 zero bytes, 256-byte aligned
     e = hipMalloc((void**)&cnn->blob16, w16.size() * sizeof(uint16_t));
@@ -1511,7 +1455,6 @@ int f2_cnn_create(f2_ctx* ctx, const float* const* tensors, int rows, int channe
     for (int i = 0; e == hipSuccess && i < 12; ++i) {
         const float* src = relaid[i].empty() ? tensors[i] : relaid[i].data();
         e = hipMemcpyAsync(cnn->blob + cnn->off[i], src, dev_sizes[i] * sizeof(float), hipMemcpyHostToDevice, ctx->stream);
-        if (e != hipSuccess) break;
     }
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     if (e != hipSuccess) {
@@ -1530,12 +1473,13 @@ int f2_cnn_create(f2_ctx* ctx, const float* const* tensors, int rows, int channe
 int f2_cnn_get_info(f2_ctx* ctx, const f2_cnn* cnn, const char* key, double* value) {
     F2_CHECK(nullptr, ctx, F2_ERR_INVALID, "ctx is NULL");
     F2_CHECK(ctx, cnn && key && value, F2_ERR_INVALID, "null argument");
-    if (strcmp(key, "ws_ok") == 0) *value = cnn->ws_ok && cnn->blob16 && f2_cnn_ws_supported(cnn->rows, cnn->channels) ? 1.0 : 0.0;
-    else if (strcmp(key, "ws_dense_ok") == 0) *value = cnn->ws_dense_ok && cnn->ws_ok && cnn->blob16 && f2_cnn_ws_supported(cnn->rows, cnn->channels) ? 1.0 : 0.0;
+    const f2_cnn_route can = f2_cnn_capability(cnn);
+    if (strcmp(key, "ws_ok") == 0) *value = can.ws ? 1.0 : 0.0;
+    else if (strcmp(key, "ws_dense_ok") == 0) *value = can.ws_dense ? 1.0 : 0.0;
     else if (strcmp(key, "ws_check_diff") == 0) *value = (double)cnn->ws_check_diff;
     else if (strcmp(key, "ws_dense_check_diff") == 0) *value = (double)cnn->ws_dense_check_diff;
     else if (strcmp(key, "flat") == 0) *value = (double)cnn->flat;
-    else if (strcmp(key, "f16x3_ok") == 0) *value = cnn->f16x3_ok && cnn->blob16 ? 1.0 : 0.0;
+    else if (strcmp(key, "f16x3_ok") == 0) *value = can.split ? 1.0 : 0.0;
     else if (strcmp(key, "f16x3_check_diff") == 0) *value = (double)cnn->f16x3_check_diff;
     else if (strcmp(key, "last_input_bound") == 0) *value = cnn->last_input_bound;
     else return f2_fail(ctx, F2_ERR_INVALID, "unknown key '%s'", key);

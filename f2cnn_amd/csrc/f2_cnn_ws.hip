@@ -39,7 +39,7 @@
 // accumulator register q of lane (i, h) is row (q & 3) + 8 (q >> 2) + 4 h, column i.
 #include <type_traits>
 
-#include "f2_internal.h"
+#include "f2_cnn_dims.h"
 
 namespace {
 
@@ -47,10 +47,6 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int C1 = 32, C2 = 32, C3 = 64, C4 = 64;
-constexpr int PW = 34;            // patch width: 32 output columns + 2
-constexpr int T34 = 30;           // conv4 output columns per tile
 
 // LDS images of the activation patches. A matrix step takes 16 input channels (kb = which 16) of 32 pixels: lane (i, h) reads the
 // 16 bytes of channels 16 kb + 8 h .. + 7 of its pixel. Every piece (hi / lo) of a patch is stored as PLANES of 16-channel
@@ -734,7 +730,7 @@ __global__ __launch_bounds__(512) void k_conv34_ws(const uint4* __restrict__ in,
 // SIMDs (the two-wave workgroups of the filterbank kernel do spread: 4 waves per workgroup change nothing there). Now 12 waves =
 // 2 row halves x 6 output tiles: three waves per SIMD by construction, one workgroup per CU, 164 registers. What is left (113 us against 58 us of matrix time): the activation fragments -
 // 2 KB of LDS reads per 3 MT MFMAs and wave, 22 us with everything else knocked out - and the launch's fixed costs.
-constexpr int D1W_WAVES = 6, D1W_KC = 64, D1W_TILES = 17, D1W_NPAD = D1W_TILES * 32, D1W_N = 516;
+constexpr int D1W_WAVES = D1_WAVES, D1W_KC = D1_KC, D1W_TILES = D1_TILES, D1W_NPAD = D1_NPAD, D1W_N = D1;   // (f2_cnn_dims.h)
 constexpr int D1W_GROUPS = (D1W_TILES + D1W_WAVES - 1) / D1W_WAVES;
 constexpr int D1W_HALVES = 2;      // row halves of a workgroup: 6 x 2 = 12 waves, three on every SIMD
 constexpr int D1W_THREADS = D1W_WAVES * D1W_HALVES * 64;
@@ -935,10 +931,10 @@ __global__ __launch_bounds__(D1W_THREADS, 3) void k_dense1_ws(const float* __res
 // conv1 .. conv4 + pools of n windows: x (n, H1, W1) float32 -> a2s (n, 4, W1/2 - 1, [hi 32 | lo 32]) fp16, x sa_3 (scratch) ->
 // a4 (n, 1, Wp2, 64) float32. Only for windows with four pooled rows after conv2 (f2_cnn_ws_supported).
 bool f2_cnn_ws_supported(int rows, int channels) {
-    const int Hp1 = (rows - 2) / 2, Wp1 = (channels - 2) / 2;
+    const Dims d = make_dims(rows, channels);
     // Wp1 <= 200: k_conv34_ws packs a patch column and an image offset into one register; Wp1 >= 8: the padded conv2 output
     // (rows of 16 x tiles pixels, 128 bytes each) fits in the space f2_cnn_workspace_floats reserves for conv2's and conv3's
-    return Hp1 == 4 && Wp1 >= 8 && Wp1 <= 200;
+    return d.Hp1 == 4 && d.Wp1 >= 8 && d.Wp1 <= 200;
 }
 
 #ifdef F2_WS_STAMPS
@@ -983,12 +979,11 @@ int f2_launch_cnn_ws(f2_ctx* ctx, const f2_cnn* cnn, const f2_scale_set* S, cons
 #else
 #define WS_STAMP_PASS
 #endif
-    const int H1 = cnn->rows, W1 = cnn->channels;
-    const int Wo = W1 - 2, Wp1 = Wo / 2, Wp2 = (Wp1 - 2) / 2;
+    const Dims d = make_dims(cnn->rows, cnn->channels);
     const int grid_max = ctx->num_cus > 0 ? ctx->num_cus : 256;
-    const int Wa = 16 * (((Wo / 2) * 2 + 31) / 32);           // row pitch of the conv2 output in pixels (f2_cnn_ws_a2_floats)
+    const int Wa = 16 * d.xtiles12();           // row pitch of the conv2 output in pixels (f2_cnn_ws_a2_floats)
     {
-        const int xtiles = ((Wo / 2) * 2 + 31) / 32;
+        const int xtiles = d.xtiles12();
         const int64_t ntask = n * xtiles;
         F2_CHECK(ctx, ntask < (int64_t(1) << 27), F2_ERR_UNSUPPORTED, "CNN chunk too large");
         const tile_div xt = {(unsigned)xtiles, (unsigned)(((uint64_t(1) << 32) + xtiles - 1) / xtiles)};
@@ -996,7 +991,7 @@ int f2_launch_cnn_ws(f2_ctx* ctx, const f2_cnn* cnn, const f2_scale_set* S, cons
         F2_HIP(ctx, hipFuncSetAttribute((const void*)k_conv12_ws, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS12));
         const unsigned grid = (unsigned)(ntask < grid_max ? ntask : grid_max);
         hipLaunchKernelGGL(k_conv12_ws, dim3(grid), dim3(512), LDS12, ctx->stream, d_x, cnn->t(0), cnn->t(1),
-                           (const h16x8*)(cnn->blob16 + cnn->off16[0]), S->sbias + F2_SB_B2, (_Float16*)a2s, (const float*)cnn->zeros, H1, W1,
+                           (const h16x8*)(cnn->blob16 + cnn->off16[0]), S->sbias + F2_SB_B2, (_Float16*)a2s, (const float*)cnn->zeros, d.H1, d.W1,
                            Wa, xt, (unsigned)ntask, S->sc WS_STAMP_PASS);
         F2_HIP(ctx, hipGetLastError());
 #ifdef F2_WS_STAMPS
@@ -1005,7 +1000,7 @@ int f2_launch_cnn_ws(f2_ctx* ctx, const f2_cnn* cnn, const f2_scale_set* S, cons
 #endif
     }
     {
-        const int xtiles = (2 * Wp2 + T34 - 1) / T34;
+        const int xtiles = d.xtiles34();
         const int64_t ntile = n * xtiles;
         F2_CHECK(ctx, ntile < (int64_t(1) << 27), F2_ERR_UNSUPPORTED, "CNN chunk too large");
         const tile_div xt = {(unsigned)xtiles, (unsigned)(((uint64_t(1) << 32) + xtiles - 1) / xtiles)};
@@ -1013,7 +1008,7 @@ int f2_launch_cnn_ws(f2_ctx* ctx, const f2_cnn* cnn, const f2_scale_set* S, cons
         const unsigned grid = (unsigned)(ntile < grid_max ? ntile : grid_max);
         hipLaunchKernelGGL(k_conv34_ws, dim3(grid), dim3(512), LDS34, ctx->stream, (const uint4*)a2s,
                            (const h16x8*)(cnn->blob16 + cnn->off16[1]), S->sbias + F2_SB_B3I, (const h16x8*)(cnn->blob16 + cnn->off16[2]),
-                           S->sbias + F2_SB_B4, a4, (const uint4*)cnn->zeros, Wp1, Wa, xt, (unsigned)ntile, S->sc WS_STAMP_PASS);
+                           S->sbias + F2_SB_B4, a4, (const uint4*)cnn->zeros, d.Wp1, Wa, xt, (unsigned)ntile, S->sc WS_STAMP_PASS);
         F2_HIP(ctx, hipGetLastError());
 #ifdef F2_WS_STAMPS
         ws_stamp_report(ctx, "k_conv34_ws (waves 0-3 conv3; 4-7 conv4: slot4 = K halves combined + stored, slot5 = LDS-DMA issued)", d_stamps);
@@ -1022,10 +1017,12 @@ int f2_launch_cnn_ws(f2_ctx* ctx, const f2_cnn* cnn, const f2_scale_set* S, cons
     return F2_OK;
 }
 
+// what k_dense1_ws needs: whole K chunks, two of them for its pipeline's prologue, 32-bit byte offsets into the activations
+bool f2_dense1_ws_takes(int K, int64_t n) { return K % D1W_KC == 0 && K >= 2 * D1W_KC && n * (int64_t)K * 4 < (int64_t(1) << 32); }
+
 // dense1 of n windows: a4 (n, K) float32 -> a5 (n, 516) float32
 int f2_launch_dense1_ws(f2_ctx* ctx, const f2_cnn* cnn, const f2_scale_set* S, const float* a4, int64_t n, int K, float* a5) {
-    F2_CHECK(ctx, K % D1W_KC == 0 && K >= 2 * D1W_KC && n * (int64_t)K * 4 < (int64_t(1) << 32), F2_ERR_UNSUPPORTED,
-             "dense1: %lld windows x %d inputs", (long long)n, K);
+    F2_CHECK(ctx, f2_dense1_ws_takes(K, n), F2_ERR_UNSUPPORTED, "dense1: %lld windows x %d inputs", (long long)n, K);
     constexpr int MT = 3;   // M tiles of 32 windows per wave: 96 windows per weight fragment
     constexpr int LDSB = 2 * 2 * 32 * MT * D1W_HALVES * 128;
     F2_HIP(ctx, hipFuncSetAttribute((const void*)k_dense1_ws<MT>, hipFuncAttributeMaxDynamicSharedMemorySize, LDSB));

@@ -367,18 +367,30 @@ int f2_launch_gather_strided(f2_ctx* ctx, const double* d_env, int C, const int6
 bool f2_gather_strided_blocked(const f2_ctx* ctx, int C, int step, int hop);    // the three-launch route serves this call
 // ... and the columns of its scratch a segment of `count` windows takes (float64 values: C + 2 ceil(C / 16) per column)
 int64_t f2_gather_strided_columns(int64_t count, int radius, int step, int hop);
+// Which kernels a CNN launch takes - all false: the float32 kernels; split: the split-fp16 kernels (f2_cnn_split.h; needs a scale
+// set); ws: its weight-stationary convolutions (f2_cnn_ws.hip); ws_dense: k_dense1_ws too. f2_cnn_capability: what the network can
+// run (its shape and f2_cnn_create's self-check); f2_cnn_call_route: that, the context's options "cnn_f16x3" / "cnn_ws" /
+// "cnn_ws_dense" and whether the call has a scale set. Every caller decides the route once per call (per chunk of a host-memory
+// call, with the chunk's scale set) and hands it down; the launchers below test nothing else (f2_cnn.hip).
+struct f2_cnn_route {
+    bool split = false, ws = false, ws_dense = false;
+};
+f2_cnn_route f2_cnn_capability(const f2_cnn* cnn);
+f2_cnn_route f2_cnn_call_route(const f2_ctx* ctx, const f2_cnn* cnn, bool have_scale_set);
 // weight-stationary split-fp16 convolutions (f2_cnn_ws.hip): windows whose pooled conv2 output has four rows
 bool f2_cnn_ws_supported(int rows, int channels);
+bool f2_dense1_ws_takes(int K, int64_t n);   // k_dense1_ws serves n windows of K inputs (f2_launch_dense1_ws)
 int f2_launch_dense1_ws(f2_ctx* ctx, const f2_cnn* cnn, const f2_scale_set* S, const float* a4, int64_t n, int K, float* a5);
 int f2_launch_cnn_ws(f2_ctx* ctx, const f2_cnn* cnn, const f2_scale_set* S, const float* d_x, int64_t n, void* a2s, float* a4);
 // runs the network on n windows (n <= chunk the workspace was sized for); d_ws: n * workspace floats. S: the scale set of the
-// split path for inputs of this bound (f2_cnn_scale_set), NULL = the float32 kernels
-int f2_launch_cnn(f2_ctx* ctx, const f2_cnn* cnn, const f2_scale_set* S, const float* d_x, int64_t n, float* d_ws, float* d_scores,
-                  uint8_t* d_labels);
+// split path for inputs of this bound (f2_cnn_scale_set), NULL with a route that is not split
+int f2_launch_cnn(f2_ctx* ctx, const f2_cnn* cnn, const f2_scale_set* S, f2_cnn_route route, const float* d_x, int64_t n, float* d_ws,
+                  float* d_scores, uint8_t* d_labels);
 // the two halves of f2_launch_cnn (f2_cnn.hip): convolutions per chunk of windows, dense layers over several chunks at once
-int f2_launch_cnn_convs(f2_ctx* ctx, const f2_cnn* cnn, const f2_scale_set* S, const float* d_x, int64_t n, float* d_ws, float* a4);
-int f2_launch_cnn_dense(f2_ctx* ctx, const f2_cnn* cnn, const f2_scale_set* S, const float* a4, int64_t n, float* a5, float* d_scores,
-                        uint8_t* d_labels);
+int f2_launch_cnn_convs(f2_ctx* ctx, const f2_cnn* cnn, const f2_scale_set* S, f2_cnn_route route, const float* d_x, int64_t n,
+                        float* d_ws, float* a4);
+int f2_launch_cnn_dense(f2_ctx* ctx, const f2_cnn* cnn, const f2_scale_set* S, f2_cnn_route route, const float* a4, int64_t n, float* a5,
+                        float* d_scores, uint8_t* d_labels);
 // k_cnn_input_range (f2_cnn_range.hip) over nwin windows of S floats at d_x: atomicMax of the bit pattern of max |x| over the finite
 // values into d_words[0], of the complement of the quietest window's max |x| into d_words[2], and 1 into d_words[1] if a value is
 // inf / NaN. The caller zeroes the three words first.

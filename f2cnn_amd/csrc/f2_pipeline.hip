@@ -32,74 +32,63 @@ constexpr int RANGE_WORD = 4;
 // served worse than a window whose max is 2^-QUIET_BINADES is at B = 1.
 constexpr int QUIET_BINADES = 4;
 
-int run_input_range(f2_ctx* ctx, const float* d_x, int64_t nwin, int S) {
+// The range pass over nwin windows of S floats at d_x with its read-back (waits for the stream): max |x| over the finite values, the
+// quietest window's max |x|, and whether an inf / NaN was seen
+struct input_range { float max, quiet; bool bad; };
+int measure_input_range(f2_ctx* ctx, const float* d_x, int64_t nwin, int S, input_range* r) {
     unsigned* words = (unsigned*)ctx->flags.ptr + RANGE_WORD;
     F2_HIP(ctx, hipMemsetAsync(words, 0, 3 * sizeof(unsigned), ctx->stream));
     F2_TRY(f2_prof_begin(ctx, F2_K_CNN));
     F2_TRY(f2_launch_cnn_input_range(ctx, d_x, nwin, S, words));
     F2_TRY(f2_prof_end(ctx, F2_K_CNN));
+    F2_HIP(ctx, hipMemcpyAsync(ctx->host_flags + RANGE_WORD, words, 3 * sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
+    F2_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    const unsigned mbits = (unsigned)ctx->host_flags[RANGE_WORD], qbits = ~(unsigned)ctx->host_flags[RANGE_WORD + 2];
+    memcpy(&r->max, &mbits, sizeof(float));
+    memcpy(&r->quiet, &qbits, sizeof(float));
+    r->bad = ctx->host_flags[RANGE_WORD + 1] != 0;
     return F2_OK;
 }
 
-// waits for the stream. The scale set for what run_input_range saw - B = 1 for max |x| <= 1, else B = 2^ceil(log2 max |x|) -
-// and *bound = B; *S = NULL and *bound = -1 (the float32 kernels) after inf / NaN, for a B whose scales leave the clamp, or when
-// B > 2^QUIET_BINADES and a window's max |x| lies below B / 2^QUIET_BINADES
-int pick_scale_set(f2_ctx* ctx, const f2_cnn* cnn, const f2_scale_set** S, double* bound) {
-    F2_HIP(ctx, hipMemcpyAsync(ctx->host_flags + RANGE_WORD, (unsigned*)ctx->flags.ptr + RANGE_WORD, 3 * sizeof(unsigned),
-                               hipMemcpyDeviceToHost, ctx->stream));
-    F2_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    const unsigned mbits = (unsigned)ctx->host_flags[RANGE_WORD], bad = (unsigned)ctx->host_flags[RANGE_WORD + 1];
-    const unsigned qbits = ~(unsigned)ctx->host_flags[RANGE_WORD + 2];
+// Scale set, route and last_input_bound of f2_cnn_forward (and of f2_cnn_score_windows without normalisation) for the nwin windows
+// at d_x. The split path's scales follow the input (f2_cnn_split.h), so the windows are measured - unless the float32 kernels run
+// whatever the input: B = 1 for max |x| <= 1, else B = 2^ceil(log2 max |x|), and *bound = B. *S = NULL, the float32 route and
+// *bound = -1 without the split path, after inf / NaN, for a B whose scales leave the clamp, or when B > 2^QUIET_BINADES and a
+// window's max |x| lies below B / 2^QUIET_BINADES.
+int forward_route(f2_ctx* ctx, const f2_cnn* cnn, const float* d_x, int64_t nwin, const f2_scale_set** S, f2_cnn_route* route,
+                  double* bound) {
     *S = nullptr;
+    *route = f2_cnn_route();
     *bound = -1.0;
-    if (bad) return F2_OK;
-    float m, quiet;
-    memcpy(&m, &mbits, sizeof(m));
-    memcpy(&quiet, &qbits, sizeof(quiet));
+    if (!f2_cnn_call_route(ctx, cnn, true).split) return F2_OK;
+    input_range r;
+    F2_TRY(measure_input_range(ctx, d_x, nwin, cnn->rows * cnn->channels, &r));
+    if (r.bad) return F2_OK;
     int e = 0;
-    if (m > 1.f) {
+    if (r.max > 1.f) {
         int ex;
-        const float f = std::frexp(m, &ex);   // m = f 2^ex, f in [0.5, 1)
+        const float f = std::frexp(r.max, &ex);   // max = f 2^ex, f in [0.5, 1)
         e = f == 0.5f ? ex - 1 : ex;
-        if (e > QUIET_BINADES && (double)quiet < std::ldexp(1.0, e - QUIET_BINADES)) return F2_OK;
+        if (e > QUIET_BINADES && (double)r.quiet < std::ldexp(1.0, e - QUIET_BINADES)) return F2_OK;
     }
     F2_TRY(f2_cnn_scale_set(ctx, cnn, e, S));
     if (*S) *bound = std::ldexp(1.0, e);
+    *route = f2_cnn_call_route(ctx, cnn, *S != nullptr);
     return F2_OK;
-}
-
-// The route of f2_cnn_forward (and of f2_cnn_score_windows without normalisation). forward_measures: the split path's scales
-// follow the input (f2_cnn_split.h), so the call measures it - unless the float32 kernels run whatever the input.
-// forward_scale_set: the range pass over the nwin windows at d_x and the set of their bound (waits for the stream); without
-// `measure` *S = NULL and *bound = -1
-int forward_measures(f2_ctx* ctx, const f2_cnn* cnn, bool* measure) {
-    const f2_scale_set* S1 = nullptr;
-    F2_TRY(f2_cnn_scale_set(ctx, cnn, 0, &S1));
-    *measure = S1 && ctx->opt_cnn_f16x3;
-    return F2_OK;
-}
-
-int forward_scale_set(f2_ctx* ctx, const f2_cnn* cnn, bool measure, const float* d_x, int64_t nwin, const f2_scale_set** S,
-                      double* bound) {
-    *S = nullptr;
-    *bound = -1.0;
-    if (!measure) return F2_OK;
-    F2_TRY(run_input_range(ctx, d_x, nwin, cnn->rows * cnn->channels));
-    return pick_scale_set(ctx, cnn, S, bound);
 }
 
 // last_input_bound of a host call of several chunks (start at 0): the largest B, -1 once a chunk ran on the float32 kernels
 double chunks_bound(double bound, double b) { return b < 0 || bound < 0 ? -1.0 : b > bound ? b : bound; }
 
-int cnn_forward_device(f2_ctx* ctx, const f2_cnn* cnn, const f2_scale_set* S, const float* d_x, int64_t n, float* d_scores,
-                       uint8_t* d_labels) {
+int cnn_forward_device(f2_ctx* ctx, const f2_cnn* cnn, const f2_scale_set* S, f2_cnn_route route, const float* d_x, int64_t n,
+                       float* d_scores, uint8_t* d_labels) {
     const size_t per = f2_cnn_workspace_floats(cnn);
     const int64_t chunk = n < CNN_CHUNK ? n : CNN_CHUNK;
     F2_TRY(f2_reserve(ctx, ctx->work, sizeof(float) * per * (size_t)chunk));
     const size_t xs = (size_t)cnn->rows * cnn->channels;
     for (int64_t s = 0; s < n; s += chunk) {
         const int64_t m = n - s < chunk ? n - s : chunk;
-        F2_TRY(f2_launch_cnn(ctx, cnn, S, d_x + (size_t)s * xs, m, (float*)ctx->work.ptr, d_scores ? d_scores + 2 * s : nullptr,
+        F2_TRY(f2_launch_cnn(ctx, cnn, S, route, d_x + (size_t)s * xs, m, (float*)ctx->work.ptr, d_scores ? d_scores + 2 * s : nullptr,
                              d_labels ? d_labels + s : nullptr));
     }
     return F2_OK;
@@ -157,13 +146,12 @@ int f2_cnn_forward(f2_ctx* ctx, const f2_cnn* cnn, const float* x, int64_t n, fl
     if (n == 0) return F2_OK;
     F2_CHECK(ctx, x, F2_ERR_INVALID, "x is NULL");
     const size_t xs = (size_t)cnn->rows * cnn->channels;
-    bool measure = false;
-    F2_TRY(forward_measures(ctx, cnn, &measure));
+    const f2_scale_set* S = nullptr;
+    f2_cnn_route route;
     if (mem_space == F2_MEM_DEVICE) {
-        const f2_scale_set* S = nullptr;
         double bound = -1.0;
-        F2_TRY(forward_scale_set(ctx, cnn, measure, x, n, &S, &bound));
-        F2_TRY(cnn_forward_device(ctx, cnn, S, x, n, scores, labels));
+        F2_TRY(forward_route(ctx, cnn, x, n, &S, &route, &bound));
+        F2_TRY(cnn_forward_device(ctx, cnn, S, route, x, n, scores, labels));
         cnn->last_input_bound = bound;
         return F2_OK;
     }
@@ -177,11 +165,10 @@ int f2_cnn_forward(f2_ctx* ctx, const f2_cnn* cnn, const float* x, int64_t n, fl
         const int64_t m = n - s < chunk ? n - s : chunk;
         F2_HIP(ctx, hipMemcpyAsync(ctx->stage_in.ptr, x + (size_t)s * xs, sizeof(float) * xs * (size_t)m,
                                    hipMemcpyHostToDevice, ctx->stream));
-        const f2_scale_set* S = nullptr;
         double b = -1.0;
-        F2_TRY(forward_scale_set(ctx, cnn, measure, (const float*)ctx->stage_in.ptr, m, &S, &b));
+        F2_TRY(forward_route(ctx, cnn, (const float*)ctx->stage_in.ptr, m, &S, &route, &b));
         bound = chunks_bound(bound, b);
-        F2_TRY(cnn_forward_device(ctx, cnn, S, (const float*)ctx->stage_in.ptr, m, d_scores, d_labels));
+        F2_TRY(cnn_forward_device(ctx, cnn, S, route, (const float*)ctx->stage_in.ptr, m, d_scores, d_labels));
         if (scores)
             F2_HIP(ctx, hipMemcpyAsync(scores + 2 * s, d_scores, sizeof(float) * 2 * (size_t)m, hipMemcpyDeviceToHost, ctx->stream));
         if (labels) F2_HIP(ctx, hipMemcpyAsync(labels + s, d_labels, (size_t)m, hipMemcpyDeviceToHost, ctx->stream));
@@ -207,6 +194,7 @@ struct eval_call {
     float *d_a4 = nullptr, *d_a5 = nullptr, *d_scores = nullptr;
     uint8_t* d_labels = nullptr;
     const f2_scale_set* S1 = nullptr;
+    f2_cnn_route route;          // of every launch of the call
     int64_t g0 = 0, gn = 0;      // first window and size of the open dense group
 };
 
@@ -269,13 +257,14 @@ int eval_cnn_begin(f2_ctx* ctx, const f2_cnn* cnn, eval_call* E, int64_t chunk, 
         E->d_labels = (uint8_t*)(E->d_scores + 2 * n_total);
     }
     F2_TRY(f2_cnn_scale_set(ctx, cnn, 0, &E->S1));   // K3's normalised windows lie in [0, 1] by construction: no range pass
+    E->route = f2_cnn_call_route(ctx, cnn, E->S1 != nullptr);
     E->g0 = E->gn = 0;
     return reset_flag(ctx);
 }
 
 int eval_dense_flush(f2_ctx* ctx, const f2_cnn* cnn, eval_call* E) {
     if (E->gn > 0)
-        F2_TRY(f2_launch_cnn_dense(ctx, cnn, E->S1, E->d_a4, E->gn, E->d_a5, E->d_scores ? E->d_scores + 2 * E->g0 : nullptr,
+        F2_TRY(f2_launch_cnn_dense(ctx, cnn, E->S1, E->route, E->d_a4, E->gn, E->d_a5, E->d_scores ? E->d_scores + 2 * E->g0 : nullptr,
                                    E->d_labels ? E->d_labels + E->g0 : nullptr));
     E->g0 += E->gn;
     E->gn = 0;
@@ -289,7 +278,7 @@ int eval_chunk_room(f2_ctx* ctx, const f2_cnn* cnn, eval_call* E, int64_t m) {
 
 // conv1 .. conv4 of the m windows in xbuf, appended to the open dense group
 int eval_chunk_convs(f2_ctx* ctx, const f2_cnn* cnn, eval_call* E, int64_t m) {
-    F2_TRY(f2_launch_cnn_convs(ctx, cnn, E->S1, (const float*)ctx->xbuf.ptr, m, (float*)ctx->work.ptr, E->d_a4 + E->flat * (size_t)E->gn));
+    F2_TRY(f2_launch_cnn_convs(ctx, cnn, E->S1, E->route, (const float*)ctx->xbuf.ptr, m, (float*)ctx->work.ptr, E->d_a4 + E->flat * (size_t)E->gn));
     E->gn += m;
     return F2_OK;
 }
@@ -626,12 +615,15 @@ int f2_cnn_score_windows(f2_ctx* ctx, const f2_cnn* cnn, const float* windows, i
 
     // normalised windows lie in [0, 1]: the B = 1 scale set without the range pass, as in f2_eval_*; windows as they are take
     // f2_cnn_forward's route - the range of the whole call for device memory, of each chunk for host memory, as there
-    bool measure = false;
     const f2_scale_set* S = nullptr;
+    f2_cnn_route route;
     double bound = host ? 0.0 : -1.0;   // normalize = 0: what f2_cnn_forward leaves in last_input_bound (host: largest B of the chunks)
-    if (normalize) F2_TRY(f2_cnn_scale_set(ctx, cnn, 0, &S));
-    else F2_TRY(forward_measures(ctx, cnn, &measure));
-    if (!normalize && !host) F2_TRY(forward_scale_set(ctx, cnn, measure, windows, n, &S, &bound));
+    if (normalize) {
+        F2_TRY(f2_cnn_scale_set(ctx, cnn, 0, &S));
+        route = f2_cnn_call_route(ctx, cnn, S != nullptr);
+    } else if (!host) {
+        F2_TRY(forward_route(ctx, cnn, windows, n, &S, &route, &bound));
+    }
 
     F2_HIP(ctx, hipMemsetAsync(d_counts, 0, 8 * 5 * (size_t)G, ctx->stream));
     F2_HIP(ctx, hipMemsetAsync((int*)ctx->flags.ptr + SCORE_WORD, 0, sizeof(int), ctx->stream));
@@ -660,12 +652,12 @@ int f2_cnn_score_windows(f2_ctx* ctx, const f2_cnn* cnn, const float* windows, i
             d_w = (const float*)ctx->xbuf.ptr;
         } else if (host) {
             double b = -1.0;
-            F2_TRY(forward_scale_set(ctx, cnn, measure, d_w, m, &S, &b));
+            F2_TRY(forward_route(ctx, cnn, d_w, m, &S, &route, &b));
             bound = chunks_bound(bound, b);
         }
         float* d_scores = own_scores ? s_scores : scores_or_null + 2 * s;
         uint8_t* d_labels = own_labels ? s_labels : labels_or_null + s;
-        F2_TRY(cnn_forward_device(ctx, cnn, S, d_w, m, d_scores, d_labels));
+        F2_TRY(cnn_forward_device(ctx, cnn, S, route, d_w, m, d_scores, d_labels));
         F2_TRY(f2_launch_score_tally(ctx, d_scores, d_labels, d_signs, d_groups, G, m, d_counts, d_partial, d_loss,
                                      (int*)ctx->flags.ptr + SCORE_WORD));
         if (host && scores_or_null)

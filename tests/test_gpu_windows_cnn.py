@@ -245,6 +245,44 @@ def test_cnn_weight_stationary_kernels_at_awkward_window_counts(rows, channels):
             np.testing.assert_allclose(got, orc.cnn_forward(x, oracle_weights(m)), atol=2e-5)
 
 
+@pytest.mark.parametrize("rows,channels", [(11, 67), (10, 100), (13, 40)])
+def test_cnn_selfcheck_does_not_depend_on_the_callers_options(rows, channels):
+    """f2_cnn_create's self-check names the route of each of its runs: a handle created on a context whose three CNN options are 0
+    leaves them 0, reports the same verdicts and measured differences as one created under the defaults, and predicts bit for bit
+    what that one predicts - with the options back at 1 and with them at 0. 193 windows: one full 192-window workgroup of
+    k_dense1_ws plus one window; the first two shapes take the weight-stationary kernels, the third does not."""
+    opts = ("cnn_f16x3", "cnn_ws", "cnn_ws_dense")
+    infos = ("ws_ok", "ws_dense_ok", "f16x3_ok", "ws_check_diff", "ws_dense_check_diff", "f16x3_check_diff")
+    x = np.random.default_rng(31).random((193, rows, channels)).astype(np.float32)
+    ctx_def, ctx_off = _lib.Context(0), _lib.Context(0)
+    m_def, m_off = (F2CNNModel.glorot(9, rows, channels, zero_bias=False) for _ in range(2))
+    try:
+        h_def = m_def.handle(ctx_def)
+        for o in opts:
+            ctx_off.set_option(o, 0)
+        h_off = m_off.handle(ctx_off)
+        assert [ctx_off.get_option(o) for o in opts] == [0, 0, 0]
+        info_def, info_off = ([c.cnn_info(h, k) for k in infos] for c, h in ((ctx_def, h_def), (ctx_off, h_off)))
+        print(f"{rows} x {channels}: " + ", ".join(f"{k} {v:g}" for k, v in zip(infos, info_off)))
+        assert info_off == info_def
+        assert info_off[:3] == [1 if rows in (10, 11) else 0] * 2 + [1]
+        got = {}
+        for v in (1, 0):
+            for c in (ctx_def, ctx_off):
+                for o in opts:
+                    c.set_option(o, v)
+            got[v] = m_def.predict(x, ctx_def)
+            np.testing.assert_array_equal(m_off.predict(x, ctx_off), got[v])
+        assert not np.array_equal(got[0], got[1])                         # (the options are not a no-op)
+    finally:
+        for c, m in ((ctx_def, m_def), (ctx_off, m_off)):
+            for o in opts:
+                c.set_option(o, 1)
+            for _, h in m._handles.values():
+                c.cnn_destroy(h)
+            c.close()
+
+
 def test_cnn_structured_inputs():
     # a shifted impulse probes every tap / padding edge of the conv stack; zeros probe the biases
     m = F2CNNModel.glorot(11, zero_bias=False)

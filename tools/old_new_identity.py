@@ -3,7 +3,11 @@
     python tools/old_new_identity.py compare OLD.json NEW.json    the table "case: identical / differs"
 Cases: f2_filterbank_envelope_fused, f2_eval_batch, f2_eval_utterance (one utterance) and f2_input_batch on single utterances of
 1 700, 1 761, 16 000, 40 000 and 70 000 samples and on the 34-length ragged batch of tests/test_gpu_spectral.py; LPF off and
-50 Hz; int16 waves, host memory, 128 channels."""
+50 Hz; int16 waves, host memory, 128 channels. The CNN alone (profiles/r14_a_old_new_identity.txt): f2_cnn_forward on windows of
+11 x 128, 11 x 67, 10 x 100 and 13 x 40 under the options float32 / per-tile split / ws convolutions / ws convolutions + ws dense1,
+host and device memory, inputs in [0, 1), the same x 2^10, one window x 1e4 among normalised ones (the quiet-window route) and one
+NaN, last_input_bound in the digest; one host call of 16 384 + 70 windows whose second chunk is x 2^6; f2_cnn_score_windows with
+normalize 0 / 1 and three groups; the create-time *_check_diff values."""
 import hashlib, json, os, sys
 import numpy as np
 
@@ -23,6 +27,78 @@ def digest(*arrays):
     for a in arrays:
         h.update(np.ascontiguousarray(a).tobytes())
     return h.hexdigest()[:16]
+
+
+CNN_SHAPES = [(11, 128), (11, 67), (10, 100), (13, 40)]
+CNN_ROUTES = [("float32", 0, 0, 0), ("per-tile split", 1, 0, 0), ("ws convolutions", 1, 1, 0), ("ws convolutions + ws dense1", 1, 1, 1)]
+
+
+def on_device(ctx, arrays, call):
+    """call(*device pointers) with every array of `arrays` uploaded (None stays None); the arrays are read back afterwards"""
+    ptrs = [None if a is None else ctx.malloc(max(a.nbytes, 4)) for a in arrays]
+    try:
+        for p, a in zip(ptrs, arrays):
+            if p is not None:
+                ctx.h2d(p, a)
+        out = call(*ptrs)
+        ctx.synchronize()
+        for p, a in zip(ptrs, arrays):
+            if p is not None:
+                ctx.d2h(a, p)
+    finally:
+        for p in ptrs:
+            if p is not None:
+                ctx.free(p)
+    return out
+
+
+def cnn_cases(ctx, res):
+    from f2cnn_amd import _lib
+    from f2cnn_amd.model import F2CNNModel
+    n = 193
+    for rows, ch in CNN_SHAPES:
+        m = F2CNNModel.glorot(7, rows, ch, zero_bias=False)
+        h = m.handle(ctx)
+        res[f"f2_cnn_create {rows} x {ch}: check diffs"] = digest(np.array(
+            [ctx.cnn_info(h, k) for k in ("ws_ok", "ws_dense_ok", "f16x3_ok", "ws_check_diff", "ws_dense_check_diff", "f16x3_check_diff")]))
+        x = np.random.default_rng(rows * ch).random((n, rows, ch)).astype(np.float32)
+        spike, nan = x.copy(), x.copy()
+        spike[5] *= 1e4
+        nan[7, 2, 3] = np.nan
+        signs = (np.arange(n) % 2).astype(np.uint8)
+        groups = (np.arange(n) % 3).astype(np.int32)
+        for rname, sp, ws, wsd in CNN_ROUTES:
+            ctx.set_option("cnn_f16x3", sp)
+            ctx.set_option("cnn_ws", ws)
+            ctx.set_option("cnn_ws_dense", wsd)
+            for mname, mem in (("host", _lib.MEM_HOST), ("device", _lib.MEM_DEVICE)):
+                tag = f"{rows} x {ch}, {rname}, {mname} memory"
+                for iname, xi in (("in [0, 1)", x), ("x 2^10", x * np.float32(1024)), ("one window x 1e4", spike), ("one NaN", nan)):
+                    sc, lb = np.zeros((n, 2), np.float32), np.zeros(n, np.uint8)
+                    if mem == _lib.MEM_HOST:
+                        ctx.cnn_forward(h, xi, n, sc, lb, mem)
+                    else:
+                        on_device(ctx, [np.ascontiguousarray(xi), sc, lb], lambda dx, ds, dl: ctx.cnn_forward(h, dx, n, ds, dl, mem))
+                    res[f"f2_cnn_forward: {tag}, {iname}"] = digest(sc, lb, np.float64(ctx.cnn_info(h, "last_input_bound")))
+                for norm in (0, 1):
+                    w = x + np.float32(0.5)     # (strictly positive, as normalisation demands)
+                    sc, lb = np.zeros((n, 2), np.float32), np.zeros(n, np.uint8)
+                    if mem == _lib.MEM_HOST:
+                        counts, loss = ctx.cnn_score_windows(h, w, n, norm, signs, groups, 3, sc, lb, mem)
+                    else:
+                        counts, loss = on_device(ctx, [w, signs, groups, sc, lb], lambda dw, dsg, dg, ds, dl: ctx.cnn_score_windows(
+                            h, dw, n, norm, dsg, dg, 3, ds, dl, mem))
+                    res[f"f2_cnn_score_windows: {tag}, normalize {norm}"] = digest(sc, lb, counts, loss)
+        for o in ("cnn_f16x3", "cnn_ws", "cnn_ws_dense"):
+            ctx.set_option(o, 1)
+        print(f"CNN {rows} x {ch} done", flush=True)
+    m = F2CNNModel.glorot(7, 11, 40, zero_bias=False)
+    x = np.random.default_rng(40).random((16384 + 70, 11, 40)).astype(np.float32)
+    x[16384:] *= np.float32(64)
+    sc, lb = np.zeros((len(x), 2), np.float32), np.zeros(len(x), np.uint8)
+    ctx.cnn_forward(m.handle(ctx), x, len(x), sc, lb, _lib.MEM_HOST)
+    res["f2_cnn_forward: 11 x 40, 16 384 + 70 windows in host memory, second chunk x 2^6"] = digest(
+        sc, lb, np.float64(ctx.cnn_info(m.handle(ctx), "last_input_bound")))
 
 
 def run(lib, out):
@@ -63,6 +139,7 @@ def run(lib, out):
                             np.concatenate(cs) if len(cs) else np.zeros(0, np.int64), RADIUS, STEP, True, win, _lib.MEM_HOST)
             res[f"f2_input_batch: {tag}"] = digest(win)
             print(tag, "done", flush=True)
+    cnn_cases(ctx, res)
     ctx.close()
     json.dump(res, open(out, "w"), indent=1)
 
