@@ -165,35 +165,34 @@ __device__ __forceinline__ double dpp_mov(double v) {
 // ---- first-order low-pass in the register layout of the FFT, followed by the float64 stores ----
 // Thread t holds the envelope pairs (2m, 2m+1), m = t + NT*jj, jj < NBLK: one pair in each of NBLK blocks of 2*NT
 // consecutive samples (er[jj] = env[2m], ei[jj] = env[2m+1]).
-//   y[n] = q y[n-1] + u[n],  u[n] = b0 (e[n] + e[n-1]),  q = -a1,  zero initial state
-// pair:  z0 = u0, z1 = u1 + q u0                      (zero state at the pair start)
+//   y[n] = q y[n-1] + b0 (e[n] + e[n-1]),  q = -a1,  zero initial state, computed as
+//   s[n] = q s[n-1] + e[n] (the one-pole state: no sample of another thread enters),  y[n] = b0 (s[n] + s[n-1])
+//   (y[n] - q y[n-1] = b0 (s[n] - q s[n-1] + s[n-1] - q s[n-2]) = b0 (e[n] + e[n-1]);  y[0] = b0 e[0])
+// pair:  z1 = e1 + q e0                               (zero state at the pair start)
 // block: inclusive scan of z1 over the NT pairs with multiplier q^2 (DPP wave scan in F, then the wave totals and
-//        everything above them in float64)
+//        everything above them in float64): s at the end of every pair
 // row:   the NBLK block totals are chained sequentially (q^(2 NT) per block)
 // and the outputs leave as coalesced 16-byte stores straight from the registers. All threads of the workgroup must
 // call it, after a barrier that makes `smem` (lowpass_lds_bytes bytes) free.
 template <typename F, int NT, int NBLK>
 constexpr size_t lowpass_lds_bytes() {
-    return sizeof(F) * NBLK * NT + sizeof(double) * (2 * NBLK * (NT / 64) + NBLK);
+    return sizeof(double) * (2 * NBLK * (NT / 64) + NBLK);
 }
 
-// y_in / e_in: filter state entering the first sample (y[-1], e[-1]); the return value is y of the last of the
-// 2*NT*NBLK samples (rows longer than that are filtered segment by segment, f2_envelope_split.hip).
+// s_in: filter state entering the first sample (s[-1]); the return value is s of the last of the 2*NT*NBLK samples
+// (rows longer than that are filtered segment by segment, f2_envelope_split.hip).
 template <typename F, int NT, int NBLK>
 __device__ __forceinline__ double lowpass_pairs_store(const F (&er)[NBLK], const F (&ei)[NBLK], double a1, double b0,
                                                       unsigned char* smem, double* __restrict__ y, int n, int tid,
-                                                      double y_in = 0.0, F e_in = F(0)) {
+                                                      double s_in = 0.0) {
     constexpr int NW = NT / 64;
     static_assert(NBLK <= NT, "one thread per block chains the wave totals");
-    F* e1s = reinterpret_cast<F*>(smem);                           // [NBLK][NT] odd samples, for e[n-1]
-    double* wtot = reinterpret_cast<double*>(smem + sizeof(F) * NBLK * NT);   // [NBLK][NW] wave totals
+    double* wtot = reinterpret_cast<double*>(smem);                // [NBLK][NW] wave totals
     double* cwl = wtot + NBLK * NW;                                // [NBLK][NW] carry into each wave
     double* btot = cwl + NBLK * NW;                                // [NBLK] block totals
     const int lane = tid & 63, wv = tid >> 6;
     const double q = -a1;
     const F qf = (F)q, b0f = (F)b0;
-#pragma unroll
-    for (int jj = 0; jj < NBLK; ++jj) e1s[jj * NT + tid] = ei[jj];
     // powers of q^2 for the wave scan, q^(2(lane+1)), q^128, q^(2 tid), q^(2 NT)
     double g[6];
     g[0] = q * q;
@@ -221,15 +220,9 @@ __device__ __forceinline__ double lowpass_pairs_store(const F (&er)[NBLK], const
             gp *= gp;
         }
     }
-    __syncthreads();
-    F u0[NBLK], u1[NBLK], sc[NBLK];
+    F sc[NBLK];
 #pragma unroll
-    for (int jj = 0; jj < NBLK; ++jj) {
-        const F eprev = tid > 0 ? e1s[jj * NT + tid - 1] : (jj > 0 ? e1s[(jj - 1) * NT + NT - 1] : e_in);
-        u0[jj] = b0f * (er[jj] + eprev);
-        u1[jj] = b0f * (ei[jj] + er[jj]);
-        sc[jj] = u1[jj] + qf * u0[jj];
-    }
+    for (int jj = 0; jj < NBLK; ++jj) sc[jj] = ei[jj] + qf * er[jj];
     // inclusive weighted scan over the 64 pairs of the wave (all NBLK blocks interleaved) on DPP lane moves:
     // row_shr 1,2,4,8 inside each row of 16 lanes (lanes without a source read 0), then row_bcast:15 brings the
     // previous row's total into rows 1 and 3, and row_bcast:31 lane 31's total into rows 2 and 3
@@ -275,7 +268,7 @@ __device__ __forceinline__ double lowpass_pairs_store(const F (&er)[NBLK], const
         btot[tid] = c;
     }
     __syncthreads();
-    double ycarry = y_in;                                          // true y at the end of the previous block
+    double ycarry = s_in;                                          // true s at the end of the previous block
     const F glf = (F)gl, gtf = (F)gt;
 #pragma unroll
     for (int jj = 0; jj < NBLK; ++jj) {
@@ -285,8 +278,11 @@ __device__ __forceinline__ double lowpass_pairs_store(const F (&er)[NBLK], const
         const F sin_ = glf * cw + sc[jj];                          // zero-state value at the end of this pair
         const F up = dpp_mov<0x138, 0xF>(sin_);                    // wave_shr:1
         const F sprev = lane > 0 ? up : cw;                        // ... at the end of the previous pair
-        const F y0 = qf * (gtf * (F)ycarry + sprev) + u0[jj];
-        const F y1 = qf * y0 + u1[jj];
+        const F sp = gtf * (F)ycarry + sprev;                      // s[2m-1]
+        const F s0 = qf * sp + er[jj];
+        const F s1 = qf * s0 + ei[jj];
+        const F y0 = b0f * (s0 + sp);
+        const F y1 = b0f * (s1 + s0);
         const int i0 = 2 * (tid + NT * jj);
         // (a block that lies inside the row - a wave-uniform test - stores without a test per lane)
         if (2 * NT * (jj + 1) <= n) store_pair(y + i0, (double)y0, (double)y1);

@@ -130,7 +130,6 @@ __global__ __launch_bounds__((Geo<LOG2S>::NT), 4) void k_envelope_pair(PairParam
     constexpr size_t LDS_BYTES = sizeof(cpx<float>) * CS > LP ? sizeof(cpx<float>) * CS : LP;
     __shared__ __attribute__((aligned(16))) unsigned char smem[LDS_BYTES];
     __shared__ __attribute__((aligned(16))) cpx<float> twl[TWL > 0 ? TWL : 1];
-    __shared__ float e_mid;
 
     const int tid = threadIdx.x;
     const int u = blockIdx.x / P.C, c = blockIdx.x - u * P.C;
@@ -146,7 +145,6 @@ __global__ __launch_bounds__((Geo<LOG2S>::NT), 4) void k_envelope_pair(PairParam
         x = reinterpret_cast<const T*>(P.x32 + P.x32_off[b] + (size_t)c * (size_t)n);
     else
         x = reinterpret_cast<const T*>(P.gfb + row);
-    float* e_mid_p = &e_mid;
     cpx<float>* lds = reinterpret_cast<cpx<float>*>(smem);
     cpx<float>* park_b = reinterpret_cast<cpx<float>*>(y);      // b: [0, 128 KB) of the row's output slot
     cpx<float>* park_e = park_b + HS;                           // E: [128 KB, 256 KB)
@@ -217,7 +215,6 @@ __global__ __launch_bounds__((Geo<LOG2S>::NT), 4) void k_envelope_pair(PairParam
         }
         __builtin_amdgcn_sched_barrier(0);
     }
-    if (tid == NT - 1) *e_mid_p = ei[R0 - 1];   // envelope sample 2 HS - 1: e[n-1] entering the upper half's low-pass
     F2_STAMP(st, 5);
     __syncthreads();   // every read of the parked sub-rows (and the last LDS reads) precedes the stores over them
     if (!P.lpf) {
@@ -227,7 +224,7 @@ __global__ __launch_bounds__((Geo<LOG2S>::NT), 4) void k_envelope_pair(PairParam
         }
         return;
     }
-    const double ycarry = lowpass_pairs_store<float, NT, R0>(er, ei, P.a1, P.b0, smem, y, 2 * HS, tid);
+    const double scarry = lowpass_pairs_store<float, NT, R0>(er, ei, P.a1, P.b0, smem, y, 2 * HS, tid);   // s[2 HS - 1]
     F2_STAMP(st, 6);
 #pragma unroll
     for (int j = 0; j < R0; ++j) {
@@ -237,7 +234,7 @@ __global__ __launch_bounds__((Geo<LOG2S>::NT), 4) void k_envelope_pair(PairParam
         ei[j] = i1 + 1 < n ? p.im : 0.f;
     }
     __syncthreads();   // the scan's last LDS reads precede the next segment's writes
-    lowpass_pairs_store<float, NT, R0>(er, ei, P.a1, P.b0, smem, y + 2 * HS, n - 2 * HS, tid, ycarry, *e_mid_p);
+    lowpass_pairs_store<float, NT, R0>(er, ei, P.a1, P.b0, smem, y + 2 * HS, n - 2 * HS, tid, scarry);
     F2_STAMP(st, 7);
     F2_STAMP_STORE(st, 8, P.stamps);
 }

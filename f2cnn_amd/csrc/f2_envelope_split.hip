@@ -200,15 +200,13 @@ constexpr int LNT = 512, LNB = 16;
 template <int H1>
 __global__ __launch_bounds__(LNT, 2) void k_split_lowpass(SplitParams P) {
     __shared__ __attribute__((aligned(16))) unsigned char smem[lowpass_lds_bytes<float, LNT, LNB>()];
-    __shared__ float e_last;
     const int tid = threadIdx.x;
     if (row_skipped(P, blockIdx.x)) return;
     const Row rw = row_of(P, blockIdx.x);
     double* y = rw.y;
     const int n = rw.n;
     const cpx<float>* __restrict__ e = P.scratch + (size_t)blockIdx.x * (H1 * H2);   // envelope pairs left by k_split_last
-    double ycarry = 0.0;
-    float ecarry = 0.f;
+    double scarry = 0.0;   // one-pole state s at the end of the previous segment
     for (int base = 0; base < n; base += 2 * LNT * LNB) {
         const int left = n - base;
         float er[LNB], ei[LNB];
@@ -219,12 +217,9 @@ __global__ __launch_bounds__(LNT, 2) void k_split_lowpass(SplitParams P) {
             er[jj] = i0 < left ? p.re : 0.f;
             ei[jj] = i0 + 1 < left ? p.im : 0.f;
         }
-        if (tid == LNT - 1) e_last = ei[LNB - 1];   // e[-1] of the next segment
-        __syncthreads();   // every load of this segment precedes every store; smem and e_last are settled
-        const float e_next = e_last;
-        ycarry = lowpass_pairs_store<float, LNT, LNB>(er, ei, P.a1, P.b0, smem, y + base, left, tid, ycarry, ecarry);
-        __syncthreads();   // the scan's last LDS reads precede the next segment's writes (smem, e_last)
-        ecarry = e_next;
+        __syncthreads();   // every load of this segment precedes every store; smem is settled
+        scarry = lowpass_pairs_store<float, LNT, LNB>(er, ei, P.a1, P.b0, smem, y + base, left, tid, scarry);
+        __syncthreads();   // the scan's last LDS reads precede the next segment's writes (smem)
     }
 }
 

@@ -107,7 +107,7 @@ struct LowpassConsts {
 
 template <int NT, int NBLK>
 constexpr size_t lowpass_tab_lds_bytes() {
-    return sizeof(float) * ((size_t)NBLK * NT + 2 * NBLK * (NT / 64) + NBLK);
+    return sizeof(float) * (2 * (size_t)NBLK * (NT / 64) + NBLK);
 }
 
 // one step of the weighted scan on all blocks: sc[j] += g * lane_move(sc[j])
@@ -134,37 +134,31 @@ constexpr size_t lowpass_tab_lds_bytes() {
                  : "v"(mult))
 
 // Thread t holds the envelope pairs (2m, 2m+1), m = t + NT jj (er[jj], ei[jj]); y[n] = q y[n-1] + b0 (e[n] + e[n-1]) from
-// zero state; float64 rows out as coalesced 16-byte stores. lptab[t] = {q^(2 (lane+1)), q^(2 t), (q^2)^((lane & 15) + 1),
+// zero state; float64 rows out as coalesced 16-byte stores. What is scanned is the one-pole state s[n] = q s[n-1] + e[n]
+// (zero state), which needs no sample of another thread; y[n] = b0 (s[n] + s[n-1]) then follows per pair from the value
+// the scan hands every thread anyway, s[2m-1], the end of the previous pair (y[n] - q y[n-1] = b0 (s[n] - q s[n-1] +
+// s[n-1] - q s[n-2]) = b0 (e[n] + e[n-1]); y[0] = b0 e[0]). lptab[t] = {q^(2 (lane+1)), q^(2 t), (q^2)^((lane & 15) + 1),
 // (q^2)^((lane & 31) + 1)}. All threads call it, after a barrier that makes `smem` free.
 // CHAINED (rows longer than one sweep of the workgroup, k_spectral_envelope_long): the pairs are those of the samples from
-// `ibase` on, e_in = e[ibase - 1], *ychain = y[ibase - 1] on entry and y[ibase + 2 NT NBLK - 1] on return.
+// `ibase` on, *ychain = s[ibase - 1] on entry and s[ibase + 2 NT NBLK - 1] on return.
 // Returns this thread's maximum of |y| over the odd samples it stored (the accuracy guard's denominator when the low-pass is on).
 // INSIDE15: every block but the last lies entirely inside the row (n >= 15/16 of the samples the blocks cover): those blocks store
 // and take their maxima without a test per lane.
 template <int NT, int NBLK, bool CHAINED = false, bool INSIDE15 = false>
 __device__ __forceinline__ float lowpass_pairs_store_tab(const float (&er)[NBLK], const float (&ei)[NBLK], const LowpassConsts& K,
                                                         const f2_f4* __restrict__ lptab, unsigned char* smem,
-                                                        double* __restrict__ y, int n, int tid, int ibase = 0, float e_in = 0.f,
+                                                        double* __restrict__ y, int n, int tid, int ibase = 0,
                                                         double* ychain = nullptr) {
     static_assert(NBLK == 16, "sixteen blocks: one DPP row chains them");
     constexpr int NW = NT / 64;
-    float* e1s = reinterpret_cast<float*>(smem);   // [NBLK][NT] odd samples, for e[n-1]
-    float* wtot = e1s + NBLK * NT;                 // [NBLK][NW] zero-state value at the end of each wave
-    float* cwl = wtot + NBLK * NW;                 // [NBLK][NW] zero-state value of the block entering each wave
-    float* ycar = cwl + NBLK * NW;                 // [NBLK] true y entering each block
+    float* wtot = reinterpret_cast<float*>(smem);  // [NBLK][NW] zero-state s at the end of each wave
+    float* cwl = wtot + NBLK * NW;                 // [NBLK][NW] zero-state s of the block entering each wave
+    float* ycar = cwl + NBLK * NW;                 // [NBLK] true s entering each block
     const int lane = tid & 63, wv = tid >> 6;
-#pragma unroll
-    for (int jj = 0; jj < NBLK; ++jj) e1s[jj * NT + tid] = ei[jj];
     const f2_f4 tc = lptab[tid];
-    __syncthreads();
-    float u0[NBLK], u1[NBLK], sc[NBLK];
+    float sc[NBLK];
 #pragma unroll
-    for (int jj = 0; jj < NBLK; ++jj) {
-        const float eprev = tid > 0 ? e1s[jj * NT + tid - 1] : (jj > 0 ? e1s[(jj - 1) * NT + NT - 1] : (CHAINED ? e_in : 0.f));
-        u0[jj] = K.b0f * (er[jj] + eprev);
-        u1[jj] = K.b0f * (ei[jj] + er[jj]);
-        sc[jj] = fmaf(K.qf, u0[jj], u1[jj]);
-    }
+    for (int jj = 0; jj < NBLK; ++jj) sc[jj] = fmaf(K.qf, er[jj], ei[jj]);
     {
         float mult = K.g1;
         F2_DPP_STEP("row_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:0");
@@ -186,7 +180,7 @@ __device__ __forceinline__ float lowpass_pairs_store_tab(const float (&er)[NBLK]
     __syncthreads();
     if (tid < NBLK) {
         // thread jj chains the NW wave totals of block jj (float64), then the sixteen block totals are chained by a
-        // weighted scan over the sixteen lanes: ycar[jj] = true y at the end of block jj - 1
+        // weighted scan over the sixteen lanes: ycar[jj] = true s at the end of block jj - 1
         double c = 0.0;
 #pragma unroll
         for (int w2 = 0; w2 < NW; ++w2) {
@@ -220,8 +214,11 @@ __device__ __forceinline__ float lowpass_pairs_store_tab(const float (&er)[NBLK]
         const float sin_ = fmaf(tc.x, cw, sc[jj]);            // zero-state value at the end of this pair
         const float up = dpp_mov<0x138, 0xF>(sin_);            // wave_shr:1
         const float sprev = lane > 0 ? up : cw;                // ... at the end of the previous pair
-        const float y0 = fmaf(K.qf, fmaf(tc.y, ycar[jj], sprev), u0[jj]);
-        const float y1 = fmaf(K.qf, y0, u1[jj]);
+        const float sp = fmaf(tc.y, ycar[jj], sprev);          // s[2m-1]
+        const float s0 = fmaf(K.qf, sp, er[jj]);
+        const float s1 = fmaf(K.qf, s0, ei[jj]);
+        const float y0 = K.b0f * (s0 + sp);
+        const float y1 = K.b0f * (s1 + s0);
         const int i0 = ibase + 2 * (tid + NT * jj);
         // every second output sample is enough for the maximum of a low-passed row (it only scales the guard's threshold);
         // block boundaries are wave-uniform: only the block that holds sample n - 1 masks per lane
@@ -739,9 +736,7 @@ __global__ __launch_bounds__(1024, 4) void k_spectral_envelope_long(
 #pragma unroll
             for (int jj = 0; jj < NBLK; ++jj) store_row_pair_buf(yb, n, ibase + 2 * (tid + NT * jj), (double)er[jj], (double)ei[jj]);
         } else {
-            const float e_in =   // sample 32767: the last of plane 3 of bank 0
-                sw ? __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(yb, 4 * (park_plane(n, 0, 3) + 8191), 0, KSL_PARK_AUX)) : 0.f;
-            glp = fmaxf(glp, lowpass_pairs_store_tab<NT, NBLK, true>(er, ei, P.lp, lptab, smem, y, n, tid, ibase, e_in, &ychain));
+            glp = fmaxf(glp, lowpass_pairs_store_tab<NT, NBLK, true>(er, ei, P.lp, lptab, smem, y, n, tid, ibase, &ychain));
         }
         __syncthreads();   // (the second sweep's inputs were parked before the first barrier above; `smem` is free again)
         if (sw == 0) F2_STAMP(st, 5);

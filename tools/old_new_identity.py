@@ -1,6 +1,10 @@
 """Outputs of two builds of the library compared bit for bit (diagnostic; profiles/r08_a_old_new_identity.txt).
-    python tools/old_new_identity.py run LIB OUT.json     digests of every case's outputs with that library
-    python tools/old_new_identity.py compare OLD.json NEW.json    the table "case: identical / differs"
+    python tools/old_new_identity.py run LIB OUT.json [KEEP_DIR]    digests of every case's outputs with that library; with
+                                          KEEP_DIR the outputs of the low-pass cases themselves are kept there (float64, ~1.3 GB)
+    python tools/old_new_identity.py compare OLD.json NEW.json [OLD_KEEP_DIR NEW_KEEP_DIR]    the table "case: identical /
+                                          differs"; with the kept outputs, for a case that differs, the largest difference
+                                          relative to the row maximum (envelopes: per utterance and channel; scores and windows:
+                                          the whole array as one row)
 Cases: f2_filterbank_envelope_fused, f2_eval_batch, f2_eval_utterance (one utterance) and f2_input_batch on single utterances of
 1 700, 1 761, 16 000, 40 000 and 70 000 samples and on the 34-length ragged batch of tests/test_gpu_spectral.py; LPF off and
 50 Hz; int16 waves, host memory, 128 channels. The CNN alone (profiles/r14_a_old_new_identity.txt): f2_cnn_forward on windows of
@@ -101,7 +105,43 @@ def cnn_cases(ctx, res):
         sc, lb, np.float64(ctx.cnn_info(m.handle(ctx), "last_input_bound")))
 
 
-def run(lib, out):
+def keep_arrays(keep, key, arrays, lens=None, C=None, envelopes=()):
+    """the outputs of one case under KEEP_DIR: a<i>.npy each; `envelopes` = the indices of the arrays laid out
+    [utterance][channel][sample] for utterances of `lens` samples and C channels"""
+    if not keep:
+        return
+    d = os.path.join(keep, hashlib.sha256(key.encode()).hexdigest()[:16])
+    os.makedirs(d, exist_ok=True)
+    for i, a in enumerate(arrays):
+        np.save(os.path.join(d, f"a{i}.npy"), np.ascontiguousarray(a))
+    with open(os.path.join(d, "layout.json"), "w") as f:
+        json.dump({"case": key, "lens": lens, "C": C, "is_envelope": [i in envelopes for i in range(len(arrays))]}, f)
+
+
+def worst_row_difference(key, old_keep, new_keep):
+    """max over the kept arrays and their rows of max |new - old| / max |old| (None without kept outputs of this case)"""
+    d = hashlib.sha256(key.encode()).hexdigest()[:16]
+    lay = os.path.join(old_keep, d, "layout.json")
+    if not os.path.exists(lay) or not os.path.exists(os.path.join(new_keep, d, "a0.npy")):
+        return None
+    with open(lay) as f:
+        lay = json.load(f)
+    worst = 0.0
+    for i, is_env in enumerate(lay["is_envelope"]):
+        a = np.load(os.path.join(old_keep, d, f"a{i}.npy")).astype(np.float64)
+        b = np.load(os.path.join(new_keep, d, f"a{i}.npy")).astype(np.float64)
+        if is_env:
+            o = 0
+            for n in lay["lens"]:
+                ra, rb = a.ravel()[o:o + lay["C"] * n].reshape(lay["C"], n), b.ravel()[o:o + lay["C"] * n].reshape(lay["C"], n)
+                o += lay["C"] * n
+                worst = max(worst, float((np.abs(rb - ra).max(axis=1) / np.maximum(np.abs(ra).max(axis=1), 1e-300)).max()))
+        elif a.size:
+            worst = max(worst, float(np.abs(b - a).max() / max(np.abs(a).max(), 1e-300)))
+    return worst
+
+
+def run(lib, out, keep=None):
     from f2cnn_amd import build
     build.LIB_PATH = os.path.abspath(lib)
     import f2cnn_oracle as orc
@@ -126,35 +166,53 @@ def run(lib, out):
             env = np.zeros((C * total,))
             ctx.filterbank_envelope_fused(flat, _lib.WAVE_I16, offs, coefs, B, C, lpf, cut, _lib.FFT_F32, env, None, _lib.MEM_HOST)
             res[f"f2_filterbank_envelope_fused: {tag}"] = digest(env)
+            if lpf:
+                keep_arrays(keep, f"f2_filterbank_envelope_fused: {tag}", [env], lens, C, envelopes=(0,))
             sc, lb = np.zeros((sum(nbs), 2), np.float32), np.zeros(sum(nbs), np.uint8)
             ctx.eval_batch(h, flat, _lib.WAVE_I16, offs, coefs, B, C, lpf, cut, _lib.FFT_F32, RADIUS, STEP, sc, lb, _lib.MEM_HOST)
             res[f"f2_eval_batch: {tag}"] = digest(sc, lb)
+            if lpf:
+                keep_arrays(keep, f"f2_eval_batch: {tag}", [sc, lb])
             if B == 1:
                 sc, lb, env = np.zeros((nbs[0], 2), np.float32), np.zeros(nbs[0], np.uint8), np.zeros((C, total))
                 nb = ctx.eval_utterance(h, flat, _lib.WAVE_I16, total, coefs, C, lpf, cut, _lib.FFT_F32, RADIUS, STEP, env, sc, lb,
                                         _lib.MEM_HOST)
                 res[f"f2_eval_utterance: {tag}"] = digest(sc, lb, env, np.int64(nb))
+                if lpf:
+                    keep_arrays(keep, f"f2_eval_utterance: {tag}", [env, sc, lb], lens, C, envelopes=(0,))
             win = np.zeros((int(coffs[-1]), R, C), np.float32)
             ctx.input_batch(flat, _lib.WAVE_I16, offs, coefs, B, C, lpf, cut, _lib.FFT_F32, coffs,
                             np.concatenate(cs) if len(cs) else np.zeros(0, np.int64), RADIUS, STEP, True, win, _lib.MEM_HOST)
             res[f"f2_input_batch: {tag}"] = digest(win)
+            if lpf:
+                keep_arrays(keep, f"f2_input_batch: {tag}", [win])
             print(tag, "done", flush=True)
     cnn_cases(ctx, res)
     ctx.close()
-    json.dump(res, open(out, "w"), indent=1)
+    with open(out, "w") as f:
+        json.dump(res, f, indent=1)
 
 
-def compare(a, b):
-    old, new = json.load(open(a)), json.load(open(b))
+def compare(a, b, old_keep=None, new_keep=None):
+    with open(a) as fa, open(b) as fb:
+        old, new = json.load(fa), json.load(fb)
     assert list(old) == list(new)
-    bad = 0
+    bad, worst = 0, 0.0
     for k in old:
         same = old[k] == new[k]
         bad += not same
-        print(f"{k}: {'identical' if same else 'DIFFERS'} ({old[k]}{'' if same else ' / ' + new[k]})")
+        note = ""
+        if not same and old_keep and new_keep:
+            w = worst_row_difference(k, old_keep, new_keep)
+            if w is not None:
+                worst = max(worst, w)
+                note = f", largest difference relative to the row maximum {w:.3g}"
+        print(f"{k}: {'identical' if same else 'DIFFERS'} ({old[k]}{'' if same else ' / ' + new[k]}){note}")
     print(f"{len(old) - bad} of {len(old)} cases identical")
+    if bad and old_keep and new_keep:
+        print(f"largest difference relative to the row maximum over the cases that differ: {worst:.3g}")
     return 1 if bad else 0
 
 
 if __name__ == "__main__":
-    sys.exit(run(*sys.argv[2:4]) if sys.argv[1] == "run" else compare(*sys.argv[2:4]))
+    sys.exit(run(*sys.argv[2:5]) if sys.argv[1] == "run" else compare(*sys.argv[2:6]))
