@@ -67,6 +67,8 @@ SIGNATURES = {
                                  _vp, _vp, _vp, _i]),
     "f2_label_accuracy": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i64, _i, _i, _vp, _i]),
     "f2_cnn_score_windows": (_i, [_vp, _vp, _vp, _i64, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i]),
+    "f2_envelope_picture": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _i]),
+    "f2_gammatonegram_batch": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i, _i, _d, _i, _vp, _i, _i, _vp, _vp, _vp, _i]),
 }
 
 _lib = None
@@ -444,6 +446,38 @@ class Context:
                                                  _ptr(groups), G, _ptr(scores), _ptr(labels), _ptr(counts), _ptr(loss_sum),
                                                  mem_space))
         return counts.reshape(G, 2, 2), loss_sum
+
+    def _picture_args(self, offsets, B, spans, range_out):
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        if spans is not None:
+            spans = np.ascontiguousarray(spans, dtype=np.int64)
+            if spans.size != 2 * int(B):
+                raise ValueError("spans must hold (s_b, e_b) for each of the B utterances")
+        if range_out is None:
+            range_out = np.zeros((max(int(B), 0), 2), np.float64)
+        if range_out.dtype != np.float64 or range_out.size != 2 * max(int(B), 0) or not range_out.flags["C_CONTIGUOUS"]:
+            raise ValueError("range_out must be contiguous float64 (B, 2)")
+        return offsets, spans, range_out
+
+    def envelope_picture(self, env, offsets, B, Cn, spans, width, pool, pooled, levels, mem_space, range_out=None):
+        """Pictures of `width` columns of the ragged (Cn, n_b) float64 envelopes (see f2_envelope_picture): `pooled` (B, Cn, width)
+        float64 mean (pool=0) or maximum (pool=1) per column, `levels` (B, Cn, width) uint8 LogNorm levels - numpy arrays or device
+        pointers, by mem_space, either may be None. spans: (B, 2) sample spans [s_b, e_b) or None for whole utterances. Returns
+        the (B, 2) float64 range (smallest, largest pixel > 0) of every picture, written into `range_out` when given."""
+        offsets, spans, range_out = self._picture_args(offsets, B, spans, range_out)
+        self.check(self.lib.f2_envelope_picture(self.handle, _ptr(env), _ptr(offsets), int(B), Cn, _ptr(spans), int(width), int(pool),
+                                                _ptr(pooled), _ptr(levels), _ptr(range_out), mem_space))
+        return range_out.reshape(-1, 2)
+
+    def gammatonegram_batch(self, wave, wave_dtype, offsets, coefs, B, Cn, lpf, cutoff, precision, spans, width, pool, pooled, levels,
+                            mem_space, range_out=None):
+        """Ragged batch of waves -> the pictures f2_envelope_picture gives for its envelopes, which never leave the device (see
+        f2_gammatonegram_batch). Arguments and return value as in envelope_picture."""
+        offsets, spans, range_out = self._picture_args(offsets, B, spans, range_out)
+        self.check(self.lib.f2_gammatonegram_batch(self.handle, _ptr(wave), wave_dtype, _ptr(offsets), _ptr(coefs), int(B), Cn,
+                                                   int(bool(lpf)), float(cutoff), precision, _ptr(spans), int(width), int(pool),
+                                                   _ptr(pooled), _ptr(levels), _ptr(range_out), mem_space))
+        return range_out.reshape(-1, 2)
 
 
 def strided_window_count(n, radius, step, hop):

@@ -28,14 +28,20 @@ package implements:
      source file's .FB / .PHN, as the reference's EvaluateOneWavArray ends - per file, per noise level, and for evalrand over
      the corpus. `reference`, also the bare flag, compares the row index times the hop with the label timepoint as the
      reference does; `centre` compares the row's centre sample, RADIUS * STEP further on)
+    python -m f2cnn_amd plot gtg [--file/-f WAV | --all] [--width W] [--pool mean|max] [--cutoff HZ] [--formant N] [--start S --end E] [--out PNG]
+                                                            (gammatonegram pictures, pooled to W columns and log-normalised on the
+                                                             device, written as graphs/gtg/<basename>.png without matplotlib; the
+                                                             VTR formant tracks on top when the .FB is there; --all takes
+                                                             resources/f2cnn/*/*.WAV; S and E are sample indices)
     python -m f2cnn_amd --configure            (writes configF2CNN.conf with the reference's defaults)
 
-organize / plot need the licensed TIMIT+VTR corpora or matplotlib and stay with the reference.
+organize needs the licensed TIMIT+VTR corpora and stays with the reference.
 """
 import argparse
 
 PREPARE = ("filter", "envelope", "label", "input", "features")
 CNN = ("train", "test", "eval", "evalnoise", "evalrand", "noisesweep")
+PLOT = ("gtg",)
 
 
 def hop_argument(text):
@@ -110,6 +116,21 @@ def build_parser():
                    help="eval / evalnoise / evalrand / noisesweep: accuracy against the labels of the file's .FB / .PHN; "
                         "'reference' (the bare flag) compares the row index with the label timepoint as the reference does, "
                         "'centre' the row's centre sample")
+    g = sub.add_parser('plot', help='plotting commands')
+    g.add_argument('plot_command', choices=PLOT)
+    which = g.add_mutually_exclusive_group()
+    which.add_argument('--file', '-f', dest='file', nargs='?')
+    which.add_argument('--all', action='store_true', dest='all_files', help="gtg: every resources/f2cnn/*/*.WAV, sorted")
+    g.add_argument('--width', action='store', type=int, dest='width', default=1600, help="gtg: columns of the picture")
+    g.add_argument('--pool', action='store', dest='pool', choices=('mean', 'max'), default='mean',
+                   help="gtg: how the samples of a column are reduced")
+    g.add_argument('--cutoff', '-c', action='store', dest='CUTOFF', type=int,
+                   help="low pass filter the envelopes with this cutoff frequency")
+    g.add_argument('--formant', action='store', type=int, dest='formant', default=5,
+                   help="gtg: the formant track to draw, 1..4 (anything else: all four)")
+    g.add_argument('--start', action='store', type=int, dest='start', default=0, help="gtg: first sample of the picture")
+    g.add_argument('--end', action='store', type=int, dest='end', help="gtg: one past its last sample")
+    g.add_argument('--out', action='store', dest='out', help="gtg --file: the PNG to write")
     return parser
 
 
@@ -213,6 +234,26 @@ def main(argv=None):
             Evaluating.EvaluateWithNoise(**kwargs)
         else:
             Evaluating.EvaluateOneWavFile(**kwargs)
+    elif 'plot_command' in args:
+        from .scripts.plotting import PlottingProcessing
+        kwargs = dict(start=args.start, end=args.end, formantToPlot=args.formant, width=args.width, pool=args.pool,
+                      LPF=args.CUTOFF is not None, CUTOFF=args.CUTOFF)
+        if args.all_files:
+            import glob
+            import os
+            files = sorted(glob.glob(os.path.join('resources', 'f2cnn', '*', '*.WAV')))
+            if not files:
+                print("NO FILES FOUND, PLEASE ORGANIZE FILES")
+                return 1
+        elif args.file is None:
+            print("Please use --file or -f to give input file, or --all")
+            return 1
+        else:
+            files = [args.file]
+            kwargs['out'] = args.out
+        report = PlottingProcessing.PlotGammatonegrams(files, **kwargs)
+        if report.exit_status:
+            return report.exit_status
     elif args.configure:
         from .config import write_default
         print("Saving configuration file as '{}'".format(write_default()))

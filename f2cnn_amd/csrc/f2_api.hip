@@ -197,7 +197,7 @@ int f2_prof_end(f2_ctx* ctx, int kernel_id) {
 
 extern "C" {
 
-int f2_version(void) { return 111; }   // 101: f2_eval_batch; 102: f2_host_alloc, F2_MEM_HOST_ASYNC; 103: f2_ctx_set_option; 104: f2_event_query; 105: f2_spectral_guard_read; 106: f2_cnn_forward takes any finite input on the split path; 107: f2_input_batch; 108: f2_eval_batch_strided; 109: f2_eval_noise_sweep; 110: f2_label_accuracy; 111: f2_cnn_score_windows
+int f2_version(void) { return 112; }   // 101: f2_eval_batch; 102: f2_host_alloc, F2_MEM_HOST_ASYNC; 103: f2_ctx_set_option; 104: f2_event_query; 105: f2_spectral_guard_read; 106: f2_cnn_forward takes any finite input on the split path; 107: f2_input_batch; 108: f2_eval_batch_strided; 109: f2_eval_noise_sweep; 110: f2_label_accuracy; 111: f2_cnn_score_windows; 112: f2_envelope_picture, f2_gammatonegram_batch
 
 int f2_device_count(int* count) {
     if (!count) return f2_fail(nullptr, F2_ERR_INVALID, "count is NULL");
@@ -259,7 +259,8 @@ int f2_ctx_destroy(f2_ctx* ctx) {
     (void)hipStreamSynchronize(ctx->stream);
     f2_scratch* all[] = {&ctx->coefs, &ctx->offsets, &ctx->stage_in, &ctx->stage_out, &ctx->stage_aux,
                          &ctx->work,  &ctx->work2,   &ctx->xbuf,      &ctx->flags,    &ctx->gather_log, &ctx->dense_in,
-                         &ctx->stamps, &ctx->noise_wave, &ctx->noise_meta, &ctx->acc_meta, &ctx->score_meta};
+                         &ctx->stamps, &ctx->noise_wave, &ctx->noise_meta, &ctx->acc_meta, &ctx->score_meta,
+                         &ctx->pic_meta};
     for (f2_scratch* s : all)
         if (s->ptr) (void)hipFree(s->ptr);
     for (auto& v : ctx->prof)

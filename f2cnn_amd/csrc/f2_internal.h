@@ -48,6 +48,7 @@ struct f2_ctx {
     f2_scratch noise_meta; // ... and its small arrays: sigma, 10^(snr / 10) per level, stats, window offsets
     f2_scratch acc_meta;   // f2_label_accuracy: counts, window offsets, reference offsets / timepoints / signs
     f2_scratch score_meta; // f2_cnn_score_windows: counts, loss sums, per-workgroup loss partials of the chunk in flight
+    f2_scratch pic_meta;   // f2_envelope_picture / f2_gammatonegram_batch: per-utterance span records and the vmin / vmax words (f2_picture.hip)
     f2_scratch gather_log; // ln of the envelope samples a chunk of every-sample windows touches + column min / max (f2_gather.hip)
     f2_scratch tw[2][16];  // FFT twiddle tables, [precision][log2 H], built on first use
     f2_scratch tw_fl[16];         // twiddle tables of f2_envelope_flagged.hip, by log2 H
@@ -423,5 +424,15 @@ int f2_launch_normalize_windows(f2_ctx* ctx, const float* d_in, int64_t n, int t
 int f2_launch_score_tally(f2_ctx* ctx, const float* d_scores, const uint8_t* d_labels, const uint8_t* d_signs, const int* d_groups,
                           int G, int64_t m, int64_t* d_counts, double* d_partial, double* d_loss, int* d_flag);
 size_t f2_score_partial_doubles(int64_t max_windows, int G);
+// f2_picture.hip, the kernels of f2_envelope_picture / f2_gammatonegram_batch. d_utt: 4 int64 per utterance {s_b, m_b, m_b / width,
+// (m_b % width) << 8 | lg_b}, lg_b = f2_picture_lanes_log2(m_b, width) the log2 of the lanes per column; utterance b needs
+// f2_picture_pool_blocks(C, width, lg_b) workgroups and every utterance gets blocks_per_utt, the largest of them. d_range: 2 words
+// per utterance, preset to the bits of +inf and 0, left as the bits of the smallest and largest pixel > 0 (unchanged where there
+// is none).
+int f2_picture_lanes_log2(int64_t m, int width);
+int64_t f2_picture_pool_blocks(int C, int width, int lg);
+int f2_launch_picture_pool(f2_ctx* ctx, const double* d_env, const int64_t* d_offsets, const int64_t* d_utt, int B, int C, int width,
+                           int pool, int64_t blocks_per_utt, double* d_pooled, uint64_t* d_range);
+int f2_launch_picture_levels(f2_ctx* ctx, const double* d_pooled, const uint64_t* d_range, int B, int C, int width, uint8_t* d_levels);
 size_t f2_cnn_flat_floats(const f2_cnn* cnn);    // floats per window of the conv4 output
 size_t f2_cnn_dense_floats(const f2_cnn* cnn);   // ... plus dense1's output

@@ -732,3 +732,121 @@ int f2_input_batch(f2_ctx* ctx, const void* wave, int wave_dtype, const int64_t*
 }
 
 }  // extern "C"
+
+// ---- gammatonegram pictures: f2_envelope_picture and f2_gammatonegram_batch share everything behind the envelopes ----
+namespace {
+
+constexpr int PICTURE_MAX_WIDTH = 65536;
+
+// the argument errors of both calls (include/f2cnn_hip.h: f2_envelope_picture) apart from the data pointers; nothing is launched
+// or written before they pass
+int picture_check(f2_ctx* ctx, const int64_t* offsets, int B, int C, const int64_t* spans_or_null, int width, int pool, int mem_space) {
+    F2_TRY(f2_check_batch(ctx, offsets, B, C, mem_space, true));
+    F2_CHECK(ctx, width >= 1, F2_ERR_INVALID, "a picture needs at least one column (width=%d)", width);
+    F2_CHECK(ctx, pool == 0 || pool == 1, F2_ERR_INVALID, "pool must be 0 (mean) or 1 (maximum), got %d", pool);
+    F2_CHECK(ctx, width <= PICTURE_MAX_WIDTH, F2_ERR_UNSUPPORTED, "width %d (at most %d columns)", width, PICTURE_MAX_WIDTH);
+    if (spans_or_null)
+        for (int b = 0; b < B; ++b) {
+            const int64_t nb = offsets[b + 1] - offsets[b], s = spans_or_null[2 * b], e = spans_or_null[2 * b + 1];
+            F2_CHECK(ctx, s >= 0 && e >= s && e <= nb, F2_ERR_INVALID, "utterance %d: span [%lld, %lld) does not lie inside its %lld samples",
+                     b, (long long)s, (long long)e, (long long)nb);
+        }
+    return F2_OK;
+}
+
+// Pool, levels and range of the envelopes at d_env (device; offsets already uploaded), results to the caller's buffers in mem_space.
+// Pictures a host caller asked for, and the pooled values the levels are made from when nobody asked for them, live in ctx->work /
+// ctx->work2. Waits for the stream.
+int picture_device(f2_ctx* ctx, const double* d_env, const int64_t* offsets, int B, int C, const int64_t* spans_or_null, int width,
+                   int pool, double* pooled_or_null, uint8_t* levels_or_null, double* range_or_null, int mem_space) {
+    const bool host = mem_space == F2_MEM_HOST;
+    const size_t pixels = (size_t)B * (size_t)C * (size_t)width;
+    // small arrays of the call: [span records (4 B) | range words (2 B)], all 8-byte words, in one upload
+    std::vector<int64_t> meta(6 * (size_t)B);
+    int64_t blocks = 0;   // per utterance: what the one with the shortest bins needs
+    const double inf = INFINITY;
+    for (int b = 0; b < B; ++b) {
+        const int64_t s = spans_or_null ? spans_or_null[2 * b] : 0;
+        const int64_t m = (spans_or_null ? spans_or_null[2 * b + 1] : offsets[b + 1] - offsets[b]) - s;
+        const int lg = f2_picture_lanes_log2(m, width);
+        int64_t* u = &meta[4 * (size_t)b];
+        u[0] = s, u[1] = m, u[2] = m / width, u[3] = (m % width) << 8 | lg;
+        blocks = std::max(blocks, f2_picture_pool_blocks(C, width, lg));
+        memcpy(&meta[4 * (size_t)B + 2 * (size_t)b], &inf, sizeof(double));   // (the maximum's word stays 0)
+    }
+    F2_TRY(f2_reserve(ctx, ctx->pic_meta, sizeof(int64_t) * meta.size()));
+    const int64_t* d_utt = (const int64_t*)ctx->pic_meta.ptr;
+    uint64_t* d_range = (uint64_t*)ctx->pic_meta.ptr + 4 * (size_t)B;
+    double* d_pooled = pooled_or_null;
+    if (host || !pooled_or_null) {
+        F2_TRY(f2_reserve(ctx, ctx->work, sizeof(double) * pixels));
+        d_pooled = (double*)ctx->work.ptr;
+    }
+    uint8_t* d_levels = levels_or_null;
+    if (host && levels_or_null) {
+        F2_TRY(f2_reserve(ctx, ctx->work2, pixels));
+        d_levels = (uint8_t*)ctx->work2.ptr;
+    }
+    F2_TRY(f2_upload_async(ctx, ctx->pic_meta.ptr, meta.data(), sizeof(int64_t) * meta.size()));
+    F2_TRY(f2_launch_picture_pool(ctx, d_env, (const int64_t*)ctx->offsets.ptr, d_utt, B, C, width, pool, blocks, d_pooled, d_range));
+    if (levels_or_null) F2_TRY(f2_launch_picture_levels(ctx, d_pooled, d_range, B, C, width, d_levels));
+    if (host && pooled_or_null) F2_HIP(ctx, hipMemcpyAsync(pooled_or_null, d_pooled, sizeof(double) * pixels, hipMemcpyDeviceToHost, ctx->stream));
+    if (host && levels_or_null) F2_HIP(ctx, hipMemcpyAsync(levels_or_null, d_levels, pixels, hipMemcpyDeviceToHost, ctx->stream));
+    std::vector<double> r(2 * (size_t)B);
+    if (range_or_null) F2_HIP(ctx, hipMemcpyAsync(r.data(), d_range, sizeof(double) * r.size(), hipMemcpyDeviceToHost, ctx->stream));
+    F2_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (range_or_null)
+        for (int b = 0; b < B; ++b) {   // no pixel > 0: the maximum's word is still 0, the minimum's still +inf
+            const bool any = r[2 * (size_t)b + 1] > 0.0;
+            range_or_null[2 * b] = any ? r[2 * (size_t)b] : 0.0;
+            range_or_null[2 * b + 1] = any ? r[2 * (size_t)b + 1] : 0.0;
+        }
+    return F2_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int f2_envelope_picture(f2_ctx* ctx, const double* env, const int64_t* offsets, int B, int C, const int64_t* spans_or_null, int width,
+                        int pool, double* pooled_or_null, uint8_t* levels_or_null, double* range_or_null, int mem_space) {
+    F2_TRY(f2_check_ctx(ctx));
+    F2_TRY(picture_check(ctx, offsets, B, C, spans_or_null, width, pool, mem_space));
+    const int64_t total = offsets[B];
+    F2_CHECK(ctx, env || total == 0, F2_ERR_INVALID, "null env");
+    if (B == 0 || !(pooled_or_null || levels_or_null || range_or_null)) return F2_OK;
+    F2_TRY(f2_upload_offsets(ctx, offsets, B));
+    const double* d_env = env;
+    if (mem_space == F2_MEM_HOST && total > 0) {
+        const size_t bytes = sizeof(double) * (size_t)C * (size_t)total;
+        F2_TRY(f2_reserve(ctx, ctx->stage_aux, bytes));
+        F2_HIP(ctx, hipMemcpyAsync(ctx->stage_aux.ptr, env, bytes, hipMemcpyHostToDevice, ctx->stream));
+        d_env = (const double*)ctx->stage_aux.ptr;
+    }
+    return picture_device(ctx, d_env, offsets, B, C, spans_or_null, width, pool, pooled_or_null, levels_or_null, range_or_null, mem_space);
+}
+
+int f2_gammatonegram_batch(f2_ctx* ctx, const void* wave, int wave_dtype, const int64_t* offsets, const double* coefs, int B, int C,
+                           int lpf, double cutoff_hz, int fft_precision, const int64_t* spans_or_null, int width, int pool,
+                           double* pooled_or_null, uint8_t* levels_or_null, double* range_or_null, int mem_space) {
+    F2_TRY(f2_check_ctx(ctx));
+    F2_TRY(f2_check_dsp(ctx, wave_dtype, lpf, cutoff_hz, fft_precision));
+    F2_TRY(picture_check(ctx, offsets, B, C, spans_or_null, width, pool, mem_space));
+    const int64_t total = offsets[B];
+    F2_CHECK(ctx, (wave && coefs) || total == 0, F2_ERR_INVALID, "null wave or coefs");
+    if (B == 0 || !(pooled_or_null || levels_or_null || range_or_null)) return F2_OK;
+    // envelopes of the whole batch, by the routes of f2_filterbank_envelope_fused (gfb_or_null = NULL), into a scratch buffer
+    F2_TRY(f2_upload_offsets(ctx, offsets, B));
+    double* d_env = nullptr;
+    if (total > 0) {
+        F2_TRY(f2_upload_coefs(ctx, coefs, C));
+        F2_TRY(f2_reserve(ctx, ctx->stage_out, sizeof(double) * (size_t)C * (size_t)total));
+        d_env = (double*)ctx->stage_out.ptr;
+        const void* d_wave;
+        F2_TRY(f2_stage_wave(ctx, wave, wave_dtype, total, mem_space, &d_wave));
+        F2_TRY(f2_envelopes_device(ctx, d_wave, wave_dtype, offsets, B, C, lpf, cutoff_hz, fft_precision, d_env, nullptr, true));
+    }
+    return picture_device(ctx, d_env, offsets, B, C, spans_or_null, width, pool, pooled_or_null, levels_or_null, range_or_null, mem_space);
+}
+
+}  // extern "C"

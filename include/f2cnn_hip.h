@@ -18,7 +18,8 @@
  *     buffer that has to grow (the first call of a size), and the calls that hand an error flag of
  *     the device back (f2_gather_windows with normalisation, f2_eval_*: F2_ERR_NONPOSITIVE;
  *     f2_eval_noise_sweep also waits to hand back sigma and stats, f2_label_accuracy and
- *     f2_cnn_score_windows their counts).
+ *     f2_cnn_score_windows their counts, f2_envelope_picture and f2_gammatonegram_batch the range
+ *     of every picture).
  *   - ragged batches: utterance b has n_b = offsets[b+1]-offsets[b] samples; its wave starts at
  *     wave + offsets[b]; its (C, n_b) C-order float64 matrix starts at out + C*offsets[b]. For a
  *     uniform batch this is the plain [B][C][N] layout, and each utterance's block is bit-for-bit the
@@ -65,7 +66,8 @@ enum { F2_FFT_F32 = 0, F2_FFT_F64 = 1 };
 int f2_version(void);   /* 100 * major + minor; 101 added f2_eval_batch, 102 f2_host_alloc + F2_MEM_HOST_ASYNC, 103 f2_ctx_set_option, 105 f2_spectral_guard_read + f2_cnn_get_info,
                            106 f2_cnn_forward accepts any finite input on the split path (scales from the input's range; the
                            f2_cnn_get_info keys "f16x3_ok", "f16x3_check_diff", "last_input_bound"), 107 f2_input_batch,
-                           108 f2_eval_batch_strided, 109 f2_eval_noise_sweep, 110 f2_label_accuracy, 111 f2_cnn_score_windows */
+                           108 f2_eval_batch_strided, 109 f2_eval_noise_sweep, 110 f2_label_accuracy, 111 f2_cnn_score_windows,
+                           112 f2_envelope_picture + f2_gammatonegram_batch */
 int f2_device_count(int* count);
 int f2_ctx_create(int device, f2_ctx** ctx);
 int f2_ctx_destroy(f2_ctx* ctx);
@@ -421,6 +423,51 @@ int f2_cnn_score_windows(f2_ctx* ctx, const f2_cnn* cnn,
                          float* scores_or_null /* (n, 2), mem_space */, uint8_t* labels_or_null /* n, mem_space */,
                          int64_t* counts /* host, G*4: counts[4g + 2*sign + pred] */,
                          double* loss_sum /* host, G */, int mem_space);
+
+/* ---- `plot gtg`: gammatonegram pictures of a ragged batch, reduced on the device ---------------------------------------------
+ * scripts/plotting/PlottingProcessing.py:81-133 (PlotEnvelopesAndFormantsFromFile) runs filterbank and envelope on the CPU,
+ * replicates every channel row by its ERB ratio (:27-60) and hands a 941 x n float64 image to imshow(norm=LogNorm()). Here the
+ * envelopes are pooled over time columns and normalised on the device: a picture is C x width values, whatever n is. Row
+ * replication, colours and formant tracks are display work on C x width bytes and stay with the caller.
+ *   The picture of utterance b. Its envelope is the (C, n_b) block of the ragged batch; its span is [s_b, e_b) =
+ *   spans[2b], spans[2b+1] with 0 <= s_b <= e_b <= n_b (spans_or_null == NULL: [0, n_b)); m = e_b - s_b, W = width. Column x in
+ *   [0, W) covers the samples [lo_x, hi_x), lo_x = s_b + floor(x*m / W), hi_x = s_b + floor((x+1)*m / W), and hi_x = lo_x + 1
+ *   where that bin would be empty (m < W: the nearest sample is repeated). m == 0: every pixel of the utterance is 0.0 / level 0
+ *   and its range is (0, 0).
+ *   pooled  (B, C, W) float64: pool = 0 the mean of the bin (a float64 sum divided by the count), pool = 1 its maximum. A NaN
+ *           sample makes the pixel NaN in both modes. The sum has a fixed order (each lane of a wave adds its own samples of the
+ *           bin in index order, then a fixed shuffle tree) and uses no floating-point atomics: the same bits on every call and
+ *           in both memory spaces. Consecutive lanes read consecutive samples of a row for every bin size; rows may start at
+ *           any 8-byte alignment.
+ *   range   host, 2B: vmin_b = smallest pixel > 0 of picture b, vmax_b = largest (wave and workgroup minima / maxima, then
+ *           64-bit vector integer atomics on the bit patterns, which order as positive doubles do). Pixels <= 0 and NaN do not
+ *           enter; a picture without a positive pixel has the range (0, 0).
+ *   levels  (B, C, W) uint8: matplotlib's LogNorm() autoscaled over the picture. A pixel v > 0 gets the level
+ *           1 + (int)(254*t + 0.5), t = (ln v - ln vmin) / (ln vmax - ln vmin) in float64 (t = 0 when vmax == vmin); a pixel <= 0
+ *           or NaN gets level 0 (LogNorm masks it; a masked pixel is drawn as background).
+ * f2_envelope_picture is PlotEnvelopeSpectrogram's data side (:45-78) for envelopes that already exist; env, pooled and levels
+ * are in mem_space (host envelopes are staged like the input of f2_envelope_batch). f2_gammatonegram_batch is
+ * PlotEnvelopesAndFormantsFromFile's data side (:97-106): the envelopes are what f2_filterbank_envelope_fused computes for the
+ * same batch and options with gfb_or_null = NULL; they stay in device scratch memory as in f2_input_batch, and the code of
+ * f2_envelope_picture runs on that buffer - for host memory only the wave goes up and only pooled / levels come down.
+ * All three outputs are optional. Both calls wait for the stream before they return (they hand back the range), whatever
+ * mem_space is.
+ * F2_ERR_INVALID, with nothing launched and nothing written: a NULL ctx or NULL offsets; NULL env / wave / coefs with
+ * offsets[B] > 0; a mem_space other than F2_MEM_HOST / F2_MEM_DEVICE; B < 0, C <= 0, width < 1, pool not 0 / 1; offsets that do
+ * not start at 0 or that decrease; a span with s_b < 0, e_b < s_b or e_b > n_b (the message names the utterance); for the wave
+ * call, a wave_dtype or fft_precision that is not an enumerator and lpf with cutoff_hz outside (0, 8000).
+ * F2_ERR_UNSUPPORTED, likewise: width > 65536. B == 0: F2_OK.
+ */
+int f2_envelope_picture(f2_ctx* ctx, const double* env /* ragged (C, n_b) blocks, mem_space */,
+                        const int64_t* offsets /* host, B+1 */, int B, int C,
+                        const int64_t* spans_or_null /* host, 2B: s_b, e_b */, int width, int pool,
+                        double* pooled_or_null /* (B, C, width), mem_space */,
+                        uint8_t* levels_or_null /* (B, C, width), mem_space */,
+                        double* range_or_null /* host, 2B: vmin, vmax */, int mem_space);
+int f2_gammatonegram_batch(f2_ctx* ctx, const void* wave, int wave_dtype, const int64_t* offsets, const double* coefs,
+                           int B, int C, int lpf, double cutoff_hz, int fft_precision,
+                           const int64_t* spans_or_null, int width, int pool, double* pooled_or_null,
+                           uint8_t* levels_or_null, double* range_or_null, int mem_space);
 
 #ifdef __cplusplus
 }
