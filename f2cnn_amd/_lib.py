@@ -17,6 +17,7 @@ F2_OK, F2_ERR_INVALID, F2_ERR_HIP, F2_ERR_UNSUPPORTED, F2_ERR_NOMEM, F2_ERR_NONP
 MEM_HOST, MEM_DEVICE, MEM_HOST_ASYNC = 0, 1, 2
 WAVE_I16, WAVE_F64 = 0, 1
 FFT_F32, FFT_F64 = 0, 1
+PCM_U8, PCM_I16, PCM_I32, PCM_F32, PCM_F64 = 0, 1, 2, 3, 4
 K_COUNT = 7
 
 _vp, _i, _i64, _d = C.c_void_p, C.c_int, C.c_int64, C.c_double
@@ -69,6 +70,7 @@ SIGNATURES = {
     "f2_cnn_score_windows": (_i, [_vp, _vp, _vp, _i64, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i]),
     "f2_envelope_picture": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _i]),
     "f2_gammatonegram_batch": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i, _i, _d, _i, _vp, _i, _i, _vp, _vp, _vp, _i]),
+    "f2_resample_batch": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _i64, _i64, _vp, _i64, _vp, _vp, _i]),
 }
 
 _lib = None
@@ -478,6 +480,27 @@ class Context:
                                                    int(bool(lpf)), float(cutoff), precision, _ptr(spans), int(width), int(pool),
                                                    _ptr(pooled), _ptr(levels), _ptr(range_out), mem_space))
         return range_out.reshape(-1, 2)
+
+    def resample_batch(self, audio, pcm_format, channels, channel, offsets, B, up, down, taps, half_len, out, mem_space):
+        """Ragged batch of interleaved PCM frames (offsets in frames) -> mono float64 samples in int16 units at up / down times
+        the rate, scipy.signal.resample_poly's arithmetic (see f2_resample_batch). audio / out: numpy arrays or device pointers,
+        by mem_space; out holds sum(resampled_length(n_b, up, down)) samples. taps (2 * half_len + 1 float64) may be None when
+        up == down == 1. channel -1: the mean of the channels. Returns out_offsets (B + 1, int64)."""
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        if taps is not None:
+            taps = np.ascontiguousarray(taps, dtype=np.float64)
+            if taps.size != 2 * int(half_len) + 1:
+                raise ValueError("taps must hold 2 * half_len + 1 values")
+        out_offsets = np.zeros(max(int(B), 0) + 1, np.int64)
+        self.check(self.lib.f2_resample_batch(self.handle, _ptr(audio), int(pcm_format), int(channels), int(channel), _ptr(offsets),
+                                              int(B), int(up), int(down), _ptr(taps), int(half_len), _ptr(out), _ptr(out_offsets),
+                                              mem_space))
+        return out_offsets
+
+
+def resampled_length(n, up, down):
+    """Samples f2_resample_batch gives for n frames: ceil(n up / down), as scipy.signal.resample_poly."""
+    return -(-int(n) * int(up) // int(down))
 
 
 def strided_window_count(n, radius, step, hop):

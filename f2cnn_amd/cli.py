@@ -28,6 +28,11 @@ package implements:
      source file's .FB / .PHN, as the reference's EvaluateOneWavArray ends - per file, per noise level, and for evalrand over
      the corpus. `reference`, also the bare flag, compares the row index times the hop with the label timepoint as the
      reference does; `centre` compares the row's centre sample, RADIUS * STEP further on)
+    (eval / evalnoise / evalrand / noisesweep also take --resample: every file is brought to FRAMERATE of configF2CNN.conf and to
+     one channel on the device before anything else sees it - any sample rate, 8 / 16 / 24 / 32-bit integer and float RIFF files,
+     the channels of a stereo file averaged - with scipy.signal.resample_poly's filter; STEP and `--hop frame` are then those of
+     FRAMERATE, and the .npz files also hold framerate and source_framerate. Without it a file is evaluated at its own rate, as
+     the reference does; not in the reference)
     python -m f2cnn_amd plot gtg [--file/-f WAV | --all] [--width W] [--pool mean|max] [--cutoff HZ] [--formant N] [--start S --end E] [--out PNG]
                                                             (gammatonegram pictures, pooled to W columns and log-normalised on the
                                                              device, written as graphs/gtg/<basename>.png without matplotlib; the
@@ -116,6 +121,9 @@ def build_parser():
                    help="eval / evalnoise / evalrand / noisesweep: accuracy against the labels of the file's .FB / .PHN; "
                         "'reference' (the bare flag) compares the row index with the label timepoint as the reference does, "
                         "'centre' the row's centre sample")
+    c.add_argument('--resample', action='store_true', default=argparse.SUPPRESS, dest='resample',
+                   help="eval / evalnoise / evalrand / noisesweep: bring every file to FRAMERATE of configF2CNN.conf and to one "
+                        "channel on the device first (any rate; 8 / 16 / 24 / 32-bit and float RIFF files; stereo is averaged)")
     g = sub.add_parser('plot', help='plotting commands')
     g.add_argument('plot_command', choices=PLOT)
     which = g.add_mutually_exclusive_group()
@@ -213,6 +221,8 @@ def main(argv=None):
                 kwargs['hop'] = F2Config().step
         if getattr(args, 'accuracy', None) is not None:
             kwargs['accuracy'] = args.accuracy
+        if getattr(args, 'resample', False):
+            kwargs['resample'] = True
         if args.cnn_command == 'evalrand':                     # needs no --file (unreachable in the reference CLI)
             if args.count is not None:
                 kwargs['count'] = args.count

@@ -197,7 +197,7 @@ int f2_prof_end(f2_ctx* ctx, int kernel_id) {
 
 extern "C" {
 
-int f2_version(void) { return 112; }   // 101: f2_eval_batch; 102: f2_host_alloc, F2_MEM_HOST_ASYNC; 103: f2_ctx_set_option; 104: f2_event_query; 105: f2_spectral_guard_read; 106: f2_cnn_forward takes any finite input on the split path; 107: f2_input_batch; 108: f2_eval_batch_strided; 109: f2_eval_noise_sweep; 110: f2_label_accuracy; 111: f2_cnn_score_windows; 112: f2_envelope_picture, f2_gammatonegram_batch
+int f2_version(void) { return 113; }   // 101: f2_eval_batch; 102: f2_host_alloc, F2_MEM_HOST_ASYNC; 103: f2_ctx_set_option; 104: f2_event_query; 105: f2_spectral_guard_read; 106: f2_cnn_forward takes any finite input on the split path; 107: f2_input_batch; 108: f2_eval_batch_strided; 109: f2_eval_noise_sweep; 110: f2_label_accuracy; 111: f2_cnn_score_windows; 112: f2_envelope_picture, f2_gammatonegram_batch; 113: f2_resample_batch
 
 int f2_device_count(int* count) {
     if (!count) return f2_fail(nullptr, F2_ERR_INVALID, "count is NULL");
@@ -260,7 +260,7 @@ int f2_ctx_destroy(f2_ctx* ctx) {
     f2_scratch* all[] = {&ctx->coefs, &ctx->offsets, &ctx->stage_in, &ctx->stage_out, &ctx->stage_aux,
                          &ctx->work,  &ctx->work2,   &ctx->xbuf,      &ctx->flags,    &ctx->gather_log, &ctx->dense_in,
                          &ctx->stamps, &ctx->noise_wave, &ctx->noise_meta, &ctx->acc_meta, &ctx->score_meta,
-                         &ctx->pic_meta};
+                         &ctx->pic_meta, &ctx->rs_meta, &ctx->rs_tab};
     for (f2_scratch* s : all)
         if (s->ptr) (void)hipFree(s->ptr);
     for (auto& v : ctx->prof)
@@ -636,12 +636,15 @@ int f2_check_cnn(f2_ctx* ctx, const f2_cnn* cnn, int rows, int C) {
 }
 
 int f2_stage_wave(f2_ctx* ctx, const void* wave, int wave_dtype, int64_t total, int mem_space, const void** d_wave) {
-    *d_wave = wave;
+    return f2_stage_input(ctx, wave, (wave_dtype == F2_WAVE_I16 ? 2 : 8) * (size_t)total, mem_space, d_wave);
+}
+
+int f2_stage_input(f2_ctx* ctx, const void* src, size_t bytes, int mem_space, const void** d_src) {
+    *d_src = src;
     if (mem_space == F2_MEM_DEVICE) return F2_OK;
-    const size_t bytes = (wave_dtype == F2_WAVE_I16 ? 2 : 8) * (size_t)total;
     F2_TRY(f2_reserve(ctx, ctx->stage_in, bytes));
-    F2_HIP(ctx, hipMemcpyAsync(ctx->stage_in.ptr, wave, bytes, hipMemcpyHostToDevice, ctx->stream));
-    *d_wave = ctx->stage_in.ptr;
+    F2_HIP(ctx, hipMemcpyAsync(ctx->stage_in.ptr, src, bytes, hipMemcpyHostToDevice, ctx->stream));
+    *d_src = ctx->stage_in.ptr;
     return F2_OK;
 }
 

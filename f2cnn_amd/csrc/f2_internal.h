@@ -49,6 +49,10 @@ struct f2_ctx {
     f2_scratch acc_meta;   // f2_label_accuracy: counts, window offsets, reference offsets / timepoints / signs
     f2_scratch score_meta; // f2_cnn_score_windows: counts, loss sums, per-workgroup loss partials of the chunk in flight
     f2_scratch pic_meta;   // f2_envelope_picture / f2_gammatonegram_batch: per-utterance span records and the vmin / vmax words (f2_picture.hip)
+    f2_scratch rs_meta;    // f2_resample_batch: per-utterance records and the workgroup prefix of the call (f2_resample.hip)
+    f2_scratch rs_tab;     // ... and the polyphase table of the last (up, down, half_len, taps)
+    int64_t rs_up = 0, rs_down = 0, rs_half_len = -1;
+    std::vector<double> rs_taps_host;   // the taps rs_tab was built from (skip the rebuild and the upload when equal)
     f2_scratch gather_log; // ln of the envelope samples a chunk of every-sample windows touches + column min / max (f2_gather.hip)
     f2_scratch tw[2][16];  // FFT twiddle tables, [precision][log2 H], built on first use
     f2_scratch tw_fl[16];         // twiddle tables of f2_envelope_flagged.hip, by log2 H
@@ -204,6 +208,8 @@ int f2_check_batch(f2_ctx* ctx, const int64_t* offsets, int B, int C, int mem_sp
 int f2_check_cnn(f2_ctx* ctx, const f2_cnn* cnn, int rows, int C);
 // *d_wave = the caller's pointer for F2_MEM_DEVICE, else ctx->stage_in after an asynchronous copy of `total` samples into it
 int f2_stage_wave(f2_ctx* ctx, const void* wave, int wave_dtype, int64_t total, int mem_space, const void** d_wave);
+// the same for `bytes` bytes of any input (f2_stage_wave is this with the sample size of wave_dtype)
+int f2_stage_input(f2_ctx* ctx, const void* src, size_t bytes, int mem_space, const void** d_src);
 
 #define F2_HIP(ctx, call)                                                                      \
     do {                                                                                       \
@@ -434,5 +440,17 @@ int64_t f2_picture_pool_blocks(int C, int width, int lg);
 int f2_launch_picture_pool(f2_ctx* ctx, const double* d_env, const int64_t* d_offsets, const int64_t* d_utt, int B, int C, int width,
                            int pool, int64_t blocks_per_utt, double* d_pooled, uint64_t* d_range);
 int f2_launch_picture_levels(f2_ctx* ctx, const double* d_pooled, const uint64_t* d_range, int B, int C, int width, uint8_t* d_levels);
+// f2_resample.hip, the kernels of f2_resample_batch. F2_RESAMPLE_BLOCK outputs per workgroup, which stages at most
+// F2_RESAMPLE_SPAN_MAX input frames (f2_resample_span: what (up, down, T) need, T = taps per phase).
+// d_meta: 4 int64 per utterance {first input frame, frames, first output sample, output samples}, then B + 1 running sums of the
+// workgroups ceil(output samples / F2_RESAMPLE_BLOCK) of the utterances. d_table: (up, T) float64, row p = the taps p + t * up
+// in DESCENDING t (zero past the filter's end), so that a lane walks its row and its input frames upwards together.
+#define F2_RESAMPLE_BLOCK 256
+#define F2_RESAMPLE_SPAN_MAX 4096
+int64_t f2_resample_span(int64_t up, int64_t down, int64_t T);
+int f2_launch_resample(f2_ctx* ctx, const void* d_audio, int pcm_format, int channels, int channel, const int64_t* d_meta, int B,
+                       int64_t total_blocks, int64_t up, int64_t down, int64_t half_len, int T, const double* d_table, double* d_out);
+// up == down == 1: out[f] = frame f converted and mixed down, for the `frames` frames of the whole batch
+int f2_launch_pcm_convert(f2_ctx* ctx, const void* d_audio, int pcm_format, int channels, int channel, int64_t frames, double* d_out);
 size_t f2_cnn_flat_floats(const f2_cnn* cnn);    // floats per window of the conv4 output
 size_t f2_cnn_dense_floats(const f2_cnn* cnn);   // ... plus dense1's output

@@ -850,3 +850,120 @@ int f2_gammatonegram_batch(f2_ctx* ctx, const void* wave, int wave_dtype, const 
 }
 
 }  // extern "C"
+
+// ---- f2_resample_batch: recordings of any rate, PCM format and channel count to mono float64 at the model's rate ----
+namespace {
+
+constexpr int64_t RESAMPLE_MAX_RATIO_TERM = int64_t(1) << 22;   // up, down
+constexpr int64_t RESAMPLE_MAX_TABLE = int64_t(1) << 22;        // values of the polyphase table (32 MB)
+constexpr int64_t RESAMPLE_MAX_FRAMES = int64_t(1) << 40;       // per utterance: n * up stays inside int64
+
+int64_t gcd64(int64_t a, int64_t b) {
+    while (b) {
+        const int64_t t = a % b;
+        a = b, b = t;
+    }
+    return a;
+}
+
+// The polyphase table of (up, down, half_len, taps) in ctx->rs_tab (f2_internal.h: f2_launch_resample), rebuilt and uploaded only
+// when one of them differs from the previous call's.
+int resample_table(f2_ctx* ctx, int64_t up, int64_t down, const double* taps, int64_t half_len, int64_t T) {
+    const size_t ntaps = (size_t)(2 * half_len + 1);
+    if (ctx->rs_up == up && ctx->rs_down == down && ctx->rs_half_len == half_len && ctx->rs_taps_host.size() == ntaps &&
+        memcmp(ctx->rs_taps_host.data(), taps, sizeof(double) * ntaps) == 0)
+        return F2_OK;
+    ctx->rs_half_len = -1;
+    std::vector<double> table((size_t)up * (size_t)T);
+    for (int64_t p = 0; p < up; ++p)
+        for (int64_t s = 0; s < T; ++s) {
+            const int64_t idx = p + (T - 1 - s) * up;
+            table[(size_t)(p * T + s)] = idx <= 2 * half_len ? taps[idx] : 0.0;
+        }
+    F2_TRY(f2_reserve(ctx, ctx->rs_tab, sizeof(double) * table.size()));
+    F2_TRY(f2_upload_async(ctx, ctx->rs_tab.ptr, table.data(), sizeof(double) * table.size()));
+    ctx->rs_taps_host.assign(taps, taps + ntaps);
+    ctx->rs_up = up, ctx->rs_down = down, ctx->rs_half_len = half_len;
+    return F2_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int f2_resample_batch(f2_ctx* ctx, const void* audio, int pcm_format, int channels, int channel, const int64_t* offsets, int B,
+                      int64_t up, int64_t down, const double* taps, int64_t half_len, double* out, int64_t* out_offsets,
+                      int mem_space) {
+    static const size_t elem_bytes[] = {1, 2, 4, 4, 8};
+    F2_TRY(f2_check_ctx(ctx));
+    F2_TRY(f2_check_batch(ctx, offsets, B, channels, mem_space, true));
+    F2_CHECK(ctx, channel >= -1 && channel < channels, F2_ERR_INVALID, "channel %d of %d (-1: the mean of all)", channel, channels);
+    F2_CHECK(ctx, pcm_format >= F2_PCM_U8 && pcm_format <= F2_PCM_F64, F2_ERR_INVALID, "bad pcm_format %d", pcm_format);
+    F2_CHECK(ctx, up >= 1 && down >= 1 && half_len >= 0, F2_ERR_INVALID, "bad ratio %lld / %lld or filter half length %lld",
+             (long long)up, (long long)down, (long long)half_len);
+    F2_CHECK(ctx, gcd64(up, down) == 1, F2_ERR_INVALID, "up = %lld and down = %lld are not coprime", (long long)up, (long long)down);
+    F2_CHECK(ctx, out_offsets, F2_ERR_INVALID, "out_offsets is NULL");
+    const bool identity = up == 1 && down == 1;
+    F2_CHECK(ctx, taps || identity, F2_ERR_INVALID, "null taps");
+    const int64_t total = offsets[B];
+    F2_CHECK(ctx, audio || total == 0, F2_ERR_INVALID, "null audio");
+    // what the kernel covers
+    int64_t T = 0;
+    if (!identity) {
+        F2_CHECK(ctx, up <= RESAMPLE_MAX_RATIO_TERM && down <= RESAMPLE_MAX_RATIO_TERM, F2_ERR_UNSUPPORTED,
+                 "ratio %lld / %lld: up and down may be at most %lld", (long long)up, (long long)down, (long long)RESAMPLE_MAX_RATIO_TERM);
+        F2_CHECK(ctx, half_len <= RESAMPLE_MAX_TABLE, F2_ERR_UNSUPPORTED, "filter of %lld taps: the polyphase table may hold at most %lld values",
+                 (long long)half_len, (long long)RESAMPLE_MAX_TABLE);
+        T = (2 * half_len + up) / up;       // ceil((2 half_len + 1) / up) taps per phase
+        F2_CHECK(ctx, up * T <= RESAMPLE_MAX_TABLE, F2_ERR_UNSUPPORTED, "polyphase table of %lld x %lld values (at most %lld)", (long long)up,
+                 (long long)T, (long long)RESAMPLE_MAX_TABLE);
+        const int64_t span = f2_resample_span(up, down, T);
+        F2_CHECK(ctx, span <= F2_RESAMPLE_SPAN_MAX, F2_ERR_UNSUPPORTED,
+                 "ratio %lld / %lld with %lld taps per phase: %d outputs need %lld input frames (at most %d are staged per workgroup)",
+                 (long long)up, (long long)down, (long long)T, F2_RESAMPLE_BLOCK, (long long)span, F2_RESAMPLE_SPAN_MAX);
+    }
+    for (int b = 0; b < B; ++b)
+        F2_CHECK(ctx, offsets[b + 1] - offsets[b] < RESAMPLE_MAX_FRAMES, F2_ERR_UNSUPPORTED, "utterance %d has %lld frames (at most 2^40 - 1)",
+                 b, (long long)(offsets[b + 1] - offsets[b]));
+    // per-utterance records and the workgroup prefix, the output offsets
+    std::vector<int64_t> meta(4 * (size_t)B + (size_t)B + 1);
+    std::vector<int64_t> oo((size_t)B + 1, 0);
+    int64_t* first = &meta[4 * (size_t)B];
+    first[0] = 0;
+    for (int b = 0; b < B; ++b) {
+        const int64_t n = offsets[b + 1] - offsets[b], n_out = (n * up + down - 1) / down;
+        int64_t* u = &meta[4 * (size_t)b];
+        u[0] = offsets[b], u[1] = n, u[2] = oo[b], u[3] = n_out;
+        oo[b + 1] = oo[b] + n_out;
+        first[b + 1] = first[b] + (n_out + F2_RESAMPLE_BLOCK - 1) / F2_RESAMPLE_BLOCK;
+    }
+    const int64_t total_out = oo[B];
+    F2_CHECK(ctx, out || total_out == 0, F2_ERR_INVALID, "null out");
+    memcpy(out_offsets, oo.data(), sizeof(int64_t) * ((size_t)B + 1));
+    if (B == 0 || total_out == 0) return F2_OK;
+
+    const bool host = mem_space == F2_MEM_HOST;
+    const void* d_audio;
+    F2_TRY(f2_stage_input(ctx, audio, elem_bytes[pcm_format] * (size_t)channels * (size_t)total, mem_space, &d_audio));
+    double* d_out = out;
+    if (host) {
+        F2_TRY(f2_reserve(ctx, ctx->stage_out, sizeof(double) * (size_t)total_out));
+        d_out = (double*)ctx->stage_out.ptr;
+    }
+    if (identity) {
+        F2_TRY(f2_launch_pcm_convert(ctx, d_audio, pcm_format, channels, channel, total, d_out));
+    } else {
+        F2_TRY(resample_table(ctx, up, down, taps, half_len, T));
+        F2_TRY(f2_reserve(ctx, ctx->rs_meta, sizeof(int64_t) * meta.size()));
+        F2_TRY(f2_upload_async(ctx, ctx->rs_meta.ptr, meta.data(), sizeof(int64_t) * meta.size()));
+        F2_TRY(f2_launch_resample(ctx, d_audio, pcm_format, channels, channel, (const int64_t*)ctx->rs_meta.ptr, B, first[B], up, down,
+                                  half_len, (int)T, (const double*)ctx->rs_tab.ptr, d_out));
+    }
+    if (host) {
+        F2_HIP(ctx, hipMemcpyAsync(out, d_out, sizeof(double) * (size_t)total_out, hipMemcpyDeviceToHost, ctx->stream));
+        F2_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    return F2_OK;
+}
+
+}  // extern "C"

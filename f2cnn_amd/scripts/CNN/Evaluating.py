@@ -12,7 +12,15 @@ times the hop with the label timepoint, as the reference does (its own TODO: the
 
 ``hop=N`` (``cnn eval|evalnoise|evalrand --hop N``; not in the reference) evaluates every N-th of those windows only -
 row j is every-sample row j*N, bit for bit (``f2_eval_batch_strided``) - and the ``.F2CNN.npz`` then also holds ``hop`` and
-``timepoints``, the centre sample of every row. ``hop=None`` is the reference's every-sample loop."""
+``timepoints``, the centre sample of every row. ``hop=None`` is the reference's every-sample loop.
+
+``resample=True`` (``cnn eval|evalnoise|evalrand|noisesweep --resample``; not in the reference) brings every file to
+``F2Config().framerate`` and to one channel on the device before anything else sees it (``GetArraysFromWAVsResampled``:
+``f2_resample_batch``, one call per (rate, sample type, channel count) of a group of files): the filterbank, STEP and a ``frame``
+hop are then those of that rate whatever the file's, and the ``.npz`` files gain ``framerate`` and ``source_framerate``. A file
+that already is at that rate, mono and int16 is passed through untouched, so its results are bit for bit those without the flag.
+With ``accuracy=`` a file whose rate differed gets no accuracy: the timepoints of its ``.FB`` / ``.PHN`` count source samples.
+``resample=False`` changes nothing: a file is evaluated at its own rate, as the reference does."""
 import os
 
 import numpy
@@ -22,7 +30,7 @@ from ...config import F2Config
 from ...gammatone import filters
 from ...model import F2CNNModel, load_model
 from ..processing.EnvelopeExtraction import FFT_PRECISION
-from ..processing.GammatoneFiltering import GetArrayFromWAV
+from ..processing.GammatoneFiltering import GetArrayFromWAV, GetArraysFromWAVsResampled
 
 
 def _step(framerate, cfg):
@@ -40,6 +48,26 @@ def _save(out, scores, labels, hop, N, framerate, extra=None):
     timepoints = _lib.strided_timepoints(N, cfg.radius, _step(framerate, cfg), hop)
     assert len(timepoints) == len(labels)
     numpy.savez(out, scores=scores, labels=labels, hop=numpy.int64(hop), timepoints=timepoints, **extra)
+
+
+# ---- files at the model's rate (resample=True) ------------------------------------------------------------------------
+def _load(files, resample):
+    """[(source framerate, framerate of the samples, samples)] of the files: as they are read, or with resample= at
+    F2Config().framerate and one channel (GetArraysFromWAVsResampled: one device call per kind of file)"""
+    if not resample:
+        return [(fr, fr, w) for fr, w in (GetArrayFromWAV(file) for file in files)]
+    framerate = F2Config().framerate
+    return [(source, framerate, w) for source, w in GetArraysFromWAVsResampled(files, framerate)]
+
+
+def _rate_keys(resample, framerate, source):
+    """what an .npz gains with resample="""
+    return dict(framerate=numpy.int64(framerate), source_framerate=numpy.int64(source)) if resample else {}
+
+
+def _no_rate_accuracy(file, source, framerate):
+    print("\t\t{}\tresampled from {} Hz to {} Hz, the labels of its .FB / .PHN count source samples: no accuracy".format(
+        file, source, framerate))
 
 
 # ---- accuracy against the VTR labels (reference scripts/CNN/Evaluating.py:38-40, 92-108) -----------------------------
@@ -120,6 +148,18 @@ def _file_accuracy(file, labels, accuracy, hop, framerate, ctx=None):
     return _accuracy_keys(confusion, accuracy)
 
 
+def _scored_extra(file, labels, accuracy, hop, framerate, source, resample):
+    """the keys a per-file .npz gains from accuracy= and resample= (None: none)"""
+    extra = {}
+    if accuracy is not None and source != framerate:
+        _accuracy_origin(accuracy, 0, 0)
+        _no_rate_accuracy(file, source, framerate)
+    elif accuracy is not None:
+        extra = _file_accuracy(file, labels, accuracy, hop, framerate)
+    extra = dict(extra, **_rate_keys(resample, framerate, source))
+    return extra or None
+
+
 def EvaluateOneWavArray(wavArray, framerate, wavFileName=None, model='last_trained_model', LPF=False, CUTOFF=100,
                         CENTER_FREQUENCIES=None, FILTERBANK_COEFFICIENTS=None, ctx=None, return_envelopes=False, hop=None):
     """Returns (scores (nb,2) float32, labels (nb,) uint8 [, envelopes (C,N) float64]); nb = N - 11*STEP, or with a hop
@@ -169,17 +209,18 @@ def EvaluateOneWavArray(wavArray, framerate, wavFileName=None, model='last_train
 
 
 def EvaluateOneWavFile(file, LPF=False, CUTOFF=50, model='last_trained_model', CENTER_FREQUENCIES=None,
-                       FILTERBANK_COEFFICIENTS=None, hop=None, accuracy=None):
-    """`cnn eval --file X.WAV [--hop N] [--accuracy [MODE]]`: writes <base>.F2CNN.npz (scores, labels; with a hop also hop,
-    timepoints; with accuracy= and the file's .FB / .PHN also accuracy, confusion, accuracy_mode) and returns (scores, labels)."""
+                       FILTERBANK_COEFFICIENTS=None, hop=None, accuracy=None, resample=False):
+    """`cnn eval --file X.WAV [--hop N] [--accuracy [MODE]] [--resample]`: writes <base>.F2CNN.npz (scores, labels; with a hop
+    also hop, timepoints; with accuracy= and the file's .FB / .PHN also accuracy, confusion, accuracy_mode; with resample=
+    framerate, source_framerate) and returns (scores, labels)."""
     print('Using model', model if not isinstance(model, F2CNNModel) else '<in-memory model>')
     print("File:\t\t{}".format(file))
-    framerate, wavArray = GetArrayFromWAV(file)
+    source, framerate, wavArray = _load([file], resample)[0]
     scores, labels = EvaluateOneWavArray(wavArray, framerate, file, model=model, LPF=LPF, CUTOFF=CUTOFF,
                                          CENTER_FREQUENCIES=CENTER_FREQUENCIES,
                                          FILTERBANK_COEFFICIENTS=FILTERBANK_COEFFICIENTS, hop=hop)
     out = os.path.splitext(file)[0] + '.F2CNN.npz'
-    extra = _file_accuracy(file, labels, accuracy, hop, framerate) if accuracy is not None else None
+    extra = _scored_extra(file, labels, accuracy, hop, framerate, source, resample)
     _save(out, scores, labels, hop, len(wavArray), framerate, extra)
     rising = int(labels.sum())
     print("\t\t{}\tdone ! {} windows: {} rising, {} falling -> {}".format(file, len(labels), rising,
@@ -237,12 +278,13 @@ def EvaluateWavArrays(wavArrays, framerate, model='last_trained_model', LPF=Fals
     return out
 
 
-def EvaluateRandom(count=None, LPF=False, CUTOFF=50, model='last_trained_model', hop=None, accuracy=None):
+def EvaluateRandom(count=None, LPF=False, CUTOFF=50, model='last_trained_model', hop=None, accuracy=None, resample=False):
     """`cnn evalrand`: evaluate the WAV files under resources/f2cnn/*/ in random order (all of them, or `count`
     drawn with replacement like numpy.random.choice in the reference). The filterbank is designed once and the model
     is uploaded once (the reference reloads the Keras model for every file). With a hop each group of files is one
     strided call. With accuracy= every file that has its .FB / .PHN is scored against them - a group in one device pass - and
-    the corpus total is printed from the summed confusion matrices."""
+    the corpus total is printed from the summed confusion matrices. With resample= a group of files is brought to the
+    configured framerate first (a file whose rate differed is left out of the accuracy)."""
     import glob
     import time
     TotalTime = time.time()
@@ -268,7 +310,7 @@ def EvaluateRandom(count=None, LPF=False, CUTOFF=50, model='last_trained_model',
     BATCH = 16                                    # files per device pass
     for s0 in range(0, len(wavFiles), BATCH):
         group = wavFiles[s0:s0 + BATCH]
-        loaded = [GetArrayFromWAV(file) for file in group]
+        sources, loaded = zip(*[(source, (fr, w)) for source, fr, w in _load(group, resample)])
         rates = {fr for fr, _ in loaded}
         if len(rates) == 1 and len({numpy.asarray(w).dtype for _, w in loaded}) == 1:
             outs = EvaluateWavArrays([w for _, w in loaded], loaded[0][0], model=model, LPF=LPF, CUTOFF=CUTOFF,
@@ -280,9 +322,12 @@ def EvaluateRandom(count=None, LPF=False, CUTOFF=50, model='last_trained_model',
                     for file, (fr, w) in zip(group, loaded)]
         extras = [None] * len(group)
         if accuracy is not None:
-            refs = [ReferenceLabels(file) for file in group]
-            for file in [file for file, ref in zip(group, refs) if ref is None]:
-                _no_side_files(file)
+            refs = [ReferenceLabels(file) if source == fr else None for file, source, (fr, _) in zip(group, sources, loaded)]
+            for file, ref, source, (fr, _) in zip(group, refs, sources, loaded):
+                if source != fr:
+                    _no_rate_accuracy(file, source, fr)
+                elif ref is None:
+                    _no_side_files(file)
             # one pass per framerate of the group (the step is in samples of the file)
             for rate in sorted({fr for (fr, _), ref in zip(loaded, refs) if ref is not None}):
                 members = [i for i, ((fr, _), ref) in enumerate(zip(loaded, refs)) if fr == rate and ref is not None]
@@ -293,9 +338,9 @@ def EvaluateRandom(count=None, LPF=False, CUTOFF=50, model='last_trained_model',
                     _print_accuracy(group[i], confusion, accuracy)
                     extras[i] = _accuracy_keys(confusion, accuracy)
                     corpus += confusion
-        for file, (fr, w), (scores, labels), extra in zip(group, loaded, outs, extras):
+        for file, source, (fr, w), (scores, labels), extra in zip(group, sources, loaded, outs, extras):
             out = os.path.splitext(file)[0] + '.F2CNN.npz'
-            _save(out, scores, labels, hop, len(w), fr, extra)
+            _save(out, scores, labels, hop, len(w), fr, dict(extra or {}, **_rate_keys(resample, fr, source)) or None)
             rising = int(labels.sum())
             print("\t\t{}\tdone ! {} windows: {} rising, {} falling -> {}".format(file, len(labels), rising,
                                                                                   len(labels) - rising, out))
@@ -333,17 +378,18 @@ def add_gaussian_noise(wave, SNRdB, rng=None):
 
 
 def EvaluateWithNoise(file, LPF=False, CUTOFF=100, model='last_trained_model', CENTER_FREQUENCIES=None,
-                      FILTERBANK_COEFFICIENTS=None, SNRdB=-3, rng=None, hop=None, accuracy=None):
+                      FILTERBANK_COEFFICIENTS=None, SNRdB=-3, rng=None, hop=None, accuracy=None, resample=False):
     """`cnn evalnoise` (reference: scripts/CNN/Evaluating.py:193-221): the file plus Gaussian noise at the requested level is
     written next to copies of its annotation files under OutputWavFiles/addedNoise/ and the float64 waveform is evaluated by
     the device pipeline. Returns (scores, labels) and also leaves them in <target>.F2CNN.npz; `rng` (a numpy Generator or
     RandomState) makes the noise reproducible - the reference draws from the global numpy state. With accuracy= the noisy
-    run is scored against the labels of the clean file's .FB / .PHN (what the copies under addedNoise/ are there for)."""
+    run is scored against the labels of the clean file's .FB / .PHN (what the copies under addedNoise/ are there for). With
+    resample= the noise is added to the resampled, one-channel signal and the noisy WAV is written at the configured framerate."""
     import shutil
     from scipy.io import wavfile
     print("File:\t\t{}".format(file))
     print("Appyling gaussian noise, new SNR is {SNR}dB".format(SNR=SNRdB))      # (the reference's wording, kept for log parsers)
-    framerate, clean = GetArrayFromWAV(file)
+    source_rate, framerate, clean = _load([file], resample)[0]
     noisy = add_gaussian_noise(clean, SNRdB, rng)
     source, target = _noisy_copy_paths(file, SNRdB)
     os.makedirs(os.path.dirname(target), exist_ok=True)
@@ -356,7 +402,7 @@ def EvaluateWithNoise(file, LPF=False, CUTOFF=100, model='last_trained_model', C
     scores, labels = EvaluateOneWavArray(noisy, framerate, target + '.WAV', model=model, LPF=LPF, CUTOFF=CUTOFF,
                                          CENTER_FREQUENCIES=CENTER_FREQUENCIES,
                                          FILTERBANK_COEFFICIENTS=FILTERBANK_COEFFICIENTS, hop=hop)
-    extra = _file_accuracy(file, labels, accuracy, hop, framerate) if accuracy is not None else None
+    extra = _scored_extra(file, labels, accuracy, hop, framerate, source_rate, resample)
     _save(target + '.F2CNN.npz', scores, labels, hop, len(noisy), framerate, extra)
     print("\t\t{}\tdone !".format(file))
     return scores, labels
@@ -368,7 +414,7 @@ def _snr_text(SNRdB):
 
 
 def EvaluateNoiseSweep(files, SNRdBs, seed=0, hop=None, LPF=False, CUTOFF=50, model='last_trained_model', save_wavs=False,
-                       ctx=None, accuracy=None):
+                       ctx=None, accuracy=None, resample=False):
     """`cnn noisesweep` (not in the reference, whose EvaluateWithNoise :193-221 takes one file at one level): every file at
     every level of SNRdBs and clean in one device pass per group of files (f2_eval_noise_sweep: the noise is drawn on the device
     from (seed, level, file's place in its group, sample), so a sweep repeats bit for bit), with the clean run of the same
@@ -379,7 +425,9 @@ def EvaluateNoiseSweep(files, SNRdBs, seed=0, hop=None, LPF=False, CUTOFF=50, mo
     them. Files are grouped like EvaluateRandom groups them: one framerate and sample type per call. hop=None is hop 1.
     With accuracy= every level of a file that has its .FB / .PHN is also scored against their labels (one f2_label_accuracy
     call per group): the file's results gain accuracy_vtr (K+1) and confusion (K+1, 2, 2), [level][ref][pred], the clean level
-    last, and the printed lines the accuracy."""
+    last, and the printed lines the accuracy. With resample= the files are brought to the configured framerate first (one
+    device call per kind of file), the results gain framerate and source_framerate, and a file whose rate differed is left out
+    of the accuracy."""
     import shutil
     from scipy.io import wavfile
     if isinstance(files, (str, bytes, os.PathLike)):
@@ -395,7 +443,9 @@ def EvaluateNoiseSweep(files, SNRdBs, seed=0, hop=None, LPF=False, CUTOFF=50, mo
     cfg = F2Config()
     if not isinstance(model, F2CNNModel):
         model = load_model(model)
-    loaded = [(file,) + tuple(GetArrayFromWAV(file)) for file in files]
+    read = _load(files, resample)
+    loaded = [(file, framerate, wavArray) for file, (_, framerate, wavArray) in zip(files, read)]
+    sources = {file: source for file, (source, _, _) in zip(files, read)}
     groups = {}
     for file, framerate, wavArray in loaded:
         wave, dt = filters._wave_args(wavArray)
@@ -427,7 +477,9 @@ def EvaluateNoiseSweep(files, SNRdBs, seed=0, hop=None, LPF=False, CUTOFF=50, mo
                     raise ValueError("values must all be positive")
                 raise
             assert list(numpy.diff(wo)) == nbh * (K + 1)
-            refs = [ReferenceLabels(file) for file, _ in group] if accuracy is not None else [None] * B
+            refs = [None] * B
+            if accuracy is not None:     # (the labels of a file whose rate differed count source samples)
+                refs = [ReferenceLabels(file) if sources[file] == framerate else None for file, _ in group]
             confusions = None
             if any(ref is not None for ref in refs):
                 confusions = _confusions(ctx, labels, wo, refs, accuracy, hop, STEP)
@@ -439,7 +491,8 @@ def EvaluateNoiseSweep(files, SNRdBs, seed=0, hop=None, LPF=False, CUTOFF=50, mo
                 with numpy.errstate(invalid='ignore', divide='ignore'):
                     agreement = numpy.where(windows > 0, agree / windows.astype(numpy.float64), numpy.nan)
                 res = dict(snr_db=snr.copy(), sigma=sigma[rows].copy(), windows=windows, rising=rising, agree=agree,
-                           agreement=agreement, seed=numpy.uint64(int(seed) & (2 ** 64 - 1)), hop=numpy.int64(hop))
+                           agreement=agreement, seed=numpy.uint64(int(seed) & (2 ** 64 - 1)), hop=numpy.int64(hop),
+                           **_rate_keys(resample, framerate, sources[file]))
                 for key, u in zip(keys, rows):
                     res['labels_' + key] = labels[wo[u]:wo[u + 1]].copy()
                 if refs[b] is not None:
@@ -449,7 +502,9 @@ def EvaluateNoiseSweep(files, SNRdBs, seed=0, hop=None, LPF=False, CUTOFF=50, mo
                 out = os.path.join('OutputWavFiles', 'addedNoise', os.path.basename(source) + '.sweep.npz')
                 numpy.savez(out, **res)
                 print("File:\t\t{}".format(file))
-                if accuracy is not None and refs[b] is None:
+                if accuracy is not None and sources[file] != framerate:
+                    _no_rate_accuracy(file, sources[file], framerate)
+                elif accuracy is not None and refs[b] is None:
                     _no_side_files(file)
                 for l in range(K + 1):
                     line = "\tSNR {:>8}\t{} windows\t{} rising\tagreement with clean {:.4f}".format(

@@ -23,6 +23,29 @@ def GetArrayFromWAV(filename):
     return read_audio(filename)
 
 
+def GetArraysFromWAVsResampled(filenames, framerate, channel=-1, ctx=None):
+    """`--resample`: the files as one-channel signals at `framerate` - a list of (source framerate, samples), in the order of
+    the file names. A file that already is at that rate, one-dimensional and int16 is handed on untouched (its int16 array);
+    every other file comes back as float64 in int16 units: files of one (rate, sample type, channel count) go through one
+    f2_resample_batch call (resample.resample_arrays), rate conversion, format conversion and mixdown together - a file at the
+    right rate that is stereo or not int16 with up = down = 1. Not in the reference, which evaluates a file at its own rate."""
+    from ...resample import resample_arrays
+    loaded = [GetArrayFromWAV(filename) for filename in filenames]
+    out = [None] * len(loaded)
+    groups = {}
+    for i, (rate, samples) in enumerate(loaded):
+        samples = numpy.asarray(samples)
+        if rate == framerate and samples.ndim == 1 and samples.dtype == numpy.int16:
+            out[i] = (rate, samples)
+            continue
+        groups.setdefault((rate, samples.dtype, 1 if samples.ndim == 1 else samples.shape[1]), []).append(i)
+    for (rate, _, _), members in groups.items():
+        resampled = resample_arrays([loaded[i][1] for i in members], rate, framerate, channel=channel, ctx=ctx)
+        for i, samples in zip(members, resampled):
+            out[i] = (rate, samples)
+    return out
+
+
 def GetFilteredOutputFromArray(array, FILTERBANK_COEFFICIENTS):
     return filters.erb_filterbank(array, FILTERBANK_COEFFICIENTS)
 

@@ -67,7 +67,7 @@ int f2_version(void);   /* 100 * major + minor; 101 added f2_eval_batch, 102 f2_
                            106 f2_cnn_forward accepts any finite input on the split path (scales from the input's range; the
                            f2_cnn_get_info keys "f16x3_ok", "f16x3_check_diff", "last_input_bound"), 107 f2_input_batch,
                            108 f2_eval_batch_strided, 109 f2_eval_noise_sweep, 110 f2_label_accuracy, 111 f2_cnn_score_windows,
-                           112 f2_envelope_picture + f2_gammatonegram_batch */
+                           112 f2_envelope_picture + f2_gammatonegram_batch, 113 f2_resample_batch */
 int f2_device_count(int* count);
 int f2_ctx_create(int device, f2_ctx** ctx);
 int f2_ctx_destroy(f2_ctx* ctx);
@@ -468,6 +468,46 @@ int f2_gammatonegram_batch(f2_ctx* ctx, const void* wave, int wave_dtype, const 
                            int B, int C, int lpf, double cutoff_hz, int fft_precision,
                            const int64_t* spans_or_null, int width, int pool, double* pooled_or_null,
                            uint8_t* levels_or_null, double* range_or_null, int mem_space);
+
+/* ---- `cnn eval|evalnoise|evalrand|noisesweep --resample`: recordings of any rate and PCM format brought to the model's rate --
+ * The reference evaluates whatever scipy.io.wavfile.read returns at the file's own rate (scripts/CNN/Evaluating.py:116-135 hands
+ * it to the filterbank designed for that rate); a network trained at 16 kHz then sees another filterbank and another frame step.
+ * This call turns a ragged batch of interleaved PCM frames into mono float64 samples in int16 units at up/down times the rate:
+ * scipy.signal.resample_poly with zero padding, for the whole batch in one launch.
+ *   audio     interleaved frames (offsets[B], channels) of pcm_format, in mem_space; utterance b owns the frames offsets[b] ..
+ *             offsets[b+1] - 1 (offsets count FRAMES). Natural alignment of the element type is all that is needed: int16 data
+ *             may start at any even byte, uint8 data at any byte.
+ *   step 1    every element becomes a float64 in int16 units, exactly (all scalings are powers of two):
+ *               F2_PCM_U8 (v - 128) * 256 | F2_PCM_I16 v | F2_PCM_I32 v / 65536 (also 24-bit files read left-justified into
+ *               int32) | F2_PCM_F32, F2_PCM_F64 v * 32768
+ *             channel >= 0 picks that channel of every frame; channel == -1 is the mean (((c0 + c1) + c2) + ...) / channels, added
+ *             in float64 in channel order.
+ *   step 2    x = the mono signal of utterance b, n = its frames, n_out = ceil(n * up / down):
+ *               y[k] = sum over i of x[i] * taps[k*down + half_len - i*up],  0 <= i < n, 0 <= k*down + half_len - i*up <= 2*half_len,
+ *             the terms added in ascending i, for 0 <= k < n_out. With taps = firwin(2*half_len + 1, 1 / max(up, down),
+ *             window=('kaiser', 5.0)) * up and half_len = 10 * max(up, down) this is resample_poly(x, up, down) - bit for bit
+ *             when product and sum are rounded separately; the device may fuse them, which stays inside the rounding bound of a
+ *             dot product of ceil((2*half_len + 1) / up) terms. The order of the sum is fixed (one lane per output sample, no
+ *             atomics): the same bits on every call and in both memory spaces.
+ *             up == down == 1: step 1 only - out is the converted input bit for bit, taps may be NULL and is not read.
+ *   out       float64, out_offsets[B] samples in mem_space, utterance b at out + out_offsets[b]
+ *   out_offsets  host, B+1: the running sums of n_out, written whenever the arguments pass
+ * F2_MEM_DEVICE: the call enqueues on the context's stream and returns (out_offsets is computed on the host); F2_MEM_HOST: it
+ * returns when `out` is filled. The polyphase table of (up, down, half_len, taps) stays in the context for the next call.
+ * F2_ERR_INVALID, with nothing launched or written: a NULL ctx, offsets or out_offsets; NULL audio with offsets[B] > 0; NULL out
+ * with out_offsets[B] > 0; NULL taps unless up == down == 1; B < 0; channels < 1; channel outside [-1, channels); an unknown
+ * pcm_format; up < 1, down < 1 or half_len < 0; up and down not coprime; offsets that do not start at 0 or that decrease; a
+ * mem_space other than F2_MEM_HOST / F2_MEM_DEVICE.
+ * F2_ERR_UNSUPPORTED, likewise (the message names the limit): a workgroup of 256 outputs needs more than 4096 input frames
+ * (floor((up - 1 + 255*down) / up) + ceil((2*half_len + 1) / up): every ratio with max(up, down) <= 1024, 1/8 <= down/up <= 8 and
+ * half_len = 10 * max(up, down) fits), up or down above 2^22, a polyphase table above 2^22 values, an utterance of 2^40 frames or
+ * more. B == 0 or only empty utterances: F2_OK.
+ */
+enum { F2_PCM_U8 = 0, F2_PCM_I16 = 1, F2_PCM_I32 = 2, F2_PCM_F32 = 3, F2_PCM_F64 = 4 };
+int f2_resample_batch(f2_ctx* ctx, const void* audio /* (offsets[B], channels) interleaved, mem_space */, int pcm_format,
+                      int channels, int channel /* -1: mean */, const int64_t* offsets /* host, B+1, in FRAMES */, int B,
+                      int64_t up, int64_t down, const double* taps /* host, 2*half_len+1 */, int64_t half_len,
+                      double* out /* mem_space */, int64_t* out_offsets /* host, B+1, written by the call */, int mem_space);
 
 #ifdef __cplusplus
 }
