@@ -257,46 +257,12 @@ int f2_ctx_destroy(f2_ctx* ctx) {
     if (!ctx) return F2_OK;
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
-    f2_scratch* all[] = {&ctx->coefs, &ctx->offsets, &ctx->stage_in, &ctx->stage_out, &ctx->stage_aux,
-                         &ctx->work,  &ctx->work2,   &ctx->xbuf,      &ctx->flags,    &ctx->gather_log, &ctx->dense_in,
-                         &ctx->stamps, &ctx->noise_wave, &ctx->noise_meta, &ctx->acc_meta, &ctx->score_meta,
-                         &ctx->pic_meta, &ctx->rs_meta, &ctx->rs_tab};
-    for (f2_scratch* s : all)
-        if (s->ptr) (void)hipFree(s->ptr);
     for (auto& v : ctx->prof)
         for (auto& pr : v) {
             (void)hipEventDestroy(pr.first);
             (void)hipEventDestroy(pr.second);
         }
     for (hipEvent_t e : ctx->prof_pool) (void)hipEventDestroy(e);
-    for (auto& prec : ctx->tw)
-        for (f2_scratch& s : prec)
-            if (s.ptr) (void)hipFree(s.ptr);
-    for (auto& prec : ctx->tw_large)
-        for (f2_scratch& s : prec)
-            if (s.ptr) (void)hipFree(s.ptr);
-    for (f2_scratch& s : ctx->tw_p3)
-        if (s.ptr) (void)hipFree(s.ptr);
-    for (f2_scratch& s : ctx->tw_fl)
-        if (s.ptr) (void)hipFree(s.ptr);
-    for (f2_scratch& s : ctx->tw_split)
-        if (s.ptr) (void)hipFree(s.ptr);
-    for (f2_scratch* sc : {&ctx->tw_pair[0], &ctx->tw_pair[1], &ctx->pair_list[0], &ctx->pair_list[1]})
-        if (sc->ptr) (void)hipFree(sc->ptr);
-    if (ctx->work3.ptr) (void)hipFree(ctx->work3.ptr);
-    if (ctx->k1_states.ptr) (void)hipFree(ctx->k1_states.ptr);
-    if (ctx->k1_mtab.ptr) (void)hipFree(ctx->k1_mtab.ptr);
-    if (ctx->k1_order.ptr) (void)hipFree(ctx->k1_order.ptr);
-    if (ctx->handoff.ptr) (void)hipFree(ctx->handoff.ptr);
-    if (ctx->handoff_off.ptr) (void)hipFree(ctx->handoff_off.ptr);
-    for (auto& t : ctx->spec_tabs)
-        for (f2_scratch* sc : {&t.hu, &t.e, &t.lgroup, &t.e64})
-            if (sc->ptr) (void)hipFree(sc->ptr);
-    for (f2_scratch* sc : {&ctx->spec_x, &ctx->spec_rho, &ctx->spec_xpart, &ctx->spec_meta, &ctx->spec_uflag, &ctx->spec_lptab})
-        if (sc->ptr) (void)hipFree(sc->ptr);
-    for (auto& prec : ctx->tw_sp)
-        for (f2_scratch& sc : prec)
-            if (sc.ptr) (void)hipFree(sc.ptr);
     for (auto& sp : ctx->up_inflight) (void)hipEventDestroy(sp.done);
     for (auto& b : ctx->up_big) {
         if (b.ptr) (void)hipHostFree(b.ptr);
@@ -305,7 +271,7 @@ int f2_ctx_destroy(f2_ctx* ctx) {
     if (ctx->up_ring) (void)hipHostFree(ctx->up_ring);
     if (ctx->host_flags) (void)hipHostFree(ctx->host_flags);
     if (ctx->own_stream && ctx->stream) (void)hipStreamDestroy(ctx->stream);
-    delete ctx;
+    delete ctx;   // every f2_scratch frees itself
     return F2_OK;
 }
 
@@ -640,11 +606,76 @@ int f2_stage_wave(f2_ctx* ctx, const void* wave, int wave_dtype, int64_t total, 
 }
 
 int f2_stage_input(f2_ctx* ctx, const void* src, size_t bytes, int mem_space, const void** d_src) {
+    return f2_stage_into(ctx, ctx->stage_in, src, bytes, mem_space, d_src);
+}
+
+int f2_stage_into(f2_ctx* ctx, f2_scratch& area, const void* src, size_t bytes, int mem_space, const void** d_src) {
     *d_src = src;
-    if (mem_space == F2_MEM_DEVICE) return F2_OK;
-    F2_TRY(f2_reserve(ctx, ctx->stage_in, bytes));
-    F2_HIP(ctx, hipMemcpyAsync(ctx->stage_in.ptr, src, bytes, hipMemcpyHostToDevice, ctx->stream));
-    *d_src = ctx->stage_in.ptr;
+    if (mem_space == F2_MEM_DEVICE || bytes == 0) return F2_OK;
+    F2_TRY(f2_reserve(ctx, area, bytes));
+    F2_HIP(ctx, hipMemcpyAsync(area.ptr, src, bytes, hipMemcpyHostToDevice, ctx->stream));
+    *d_src = area.ptr;
+    return F2_OK;
+}
+
+int f2_host_wait(f2_ctx* ctx, int mem_space) {
+    if (mem_space == F2_MEM_HOST) F2_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return F2_OK;
+}
+
+// the decision of f2_place without the memory: true when the output needs scratch (o->dev is then the caller's to set)
+static bool place_decide(void* caller, size_t bytes, int mem_space, bool needed, f2_output* o) {
+    *o = f2_output();
+    o->bytes = bytes;
+    if (mem_space == F2_MEM_DEVICE && caller) {
+        o->dev = (char*)caller;
+        o->callers = true;
+        return false;
+    }
+    if (!caller && !needed) return false;
+    if (mem_space != F2_MEM_DEVICE) o->host = (char*)caller;
+    return true;
+}
+
+int f2_place(f2_ctx* ctx, f2_scratch& area, void* caller_or_null, size_t bytes, int mem_space, bool needed_on_device, f2_output* out) {
+    if (!place_decide(caller_or_null, bytes, mem_space, needed_on_device, out)) return F2_OK;
+    F2_TRY(f2_reserve(ctx, area, bytes));
+    out->dev = (char*)area.ptr;
+    return F2_OK;
+}
+
+int f2_copy_back(f2_ctx* ctx, const f2_output& o) {
+    if (o.host && o.bytes) F2_HIP(ctx, hipMemcpyAsync(o.host, o.dev, o.bytes, hipMemcpyDeviceToHost, ctx->stream));
+    return F2_OK;
+}
+
+int f2_place_scores(f2_ctx* ctx, float* scores_or_null, uint8_t* labels_or_null, int64_t n, int mem_space, bool need_scores,
+                    bool need_labels, size_t tail_bytes, f2_score_outputs* out) {
+    const size_t sbytes = sizeof(float) * 2 * (size_t)n;
+    const bool s = place_decide(scores_or_null, sbytes, mem_space, need_scores, &out->scores);
+    const bool l = place_decide(labels_or_null, (size_t)n, mem_space, need_labels, &out->labels);
+    out->tail = nullptr;
+    if (!s && !l && tail_bytes == 0) return F2_OK;
+    const size_t at_labels = s ? sbytes : 0, at_tail = (at_labels + (l ? (size_t)n : 0) + 7) & ~size_t(7);
+    F2_TRY(f2_reserve(ctx, ctx->stage_aux, at_tail + tail_bytes + 64));
+    char* base = (char*)ctx->stage_aux.ptr;
+    if (s) out->scores.dev = base;
+    if (l) out->labels.dev = base + at_labels;
+    if (tail_bytes) out->tail = base + at_tail;
+    return F2_OK;
+}
+
+int f2_meta_carve::reserve(f2_ctx* ctx) {
+    size_t total = 0;
+    for (int i = 0; i < n; ++i) total += items[i].bytes;
+    F2_TRY(f2_reserve(ctx, ctx->meta, total));
+    char* at = (char*)ctx->meta.ptr;
+    for (bool wide : {true, false})
+        for (int i = 0; i < n; ++i)
+            if (items[i].wide == wide) {
+                memcpy(items[i].slot, &at, sizeof(at));   // (the slot is a T*: object pointers share one representation)
+                at += items[i].bytes;
+            }
     return F2_OK;
 }
 
@@ -704,11 +735,13 @@ int f2_plan_handoff(f2_ctx* ctx, const int64_t* h_offsets, int B, int C, int pre
     return F2_OK;
 }
 
-// Filterbank + envelope of a ragged batch on the device: the part that f2_filterbank_envelope_fused, f2_input_batch
-// (`spectral` = true) and the eval calls (false) share. The caller has uploaded offsets and coefficients
-// (f2_upload_offsets / f2_upload_coefs) and staged the wave.
-int f2_envelopes_device(f2_ctx* ctx, const void* d_wave, int wave_dtype, const int64_t* offsets, int B, int C, int lpf,
-                        double cutoff_hz, int fft_precision, double* d_env, double* d_gfb, bool spectral) {
+// Filterbank + envelope of a ragged batch on the device (f2_batch_envelopes has uploaded offsets and coefficients and staged
+// the wave; d_gfb NULL: not wanted). `spectral`: by the routes of f2_filterbank_envelope_fused - spectral kernel with its guard,
+// then filterbank + envelope kernels for the rest; without it (the eval calls) the two kernels for every utterance.
+static int f2_envelopes_device(f2_ctx* ctx, const f2_batch& X, const void* d_wave, double* d_env, double* d_gfb, bool spectral) {
+    const int wave_dtype = X.wave_dtype, B = X.B, C = X.C, lpf = X.lpf, fft_precision = X.fft_precision;
+    const int64_t* offsets = X.offsets;
+    const double cutoff_hz = X.cutoff_hz;
     // Spectral path (f2_spectral.hip): utterances it can serve (float FFT, no GFB output wanted, make_erb_filters-shaped
     // table, 4097..65472 samples with padding to look at) get their envelopes from ONE kernel that never materialises
     // the filterbank rows. Everything else - and any utterance that kernel's accuracy guard flags on the device - goes
@@ -783,6 +816,21 @@ int f2_envelopes_device(f2_ctx* ctx, const void* d_wave, int wave_dtype, const i
     return F2_OK;
 }
 
+int f2_batch_envelopes(f2_ctx* ctx, const f2_batch& X, double* env_or_null, double* gfb_or_null, bool spectral, double** d_env) {
+    F2_TRY(f2_upload_offsets(ctx, X.offsets, X.B));
+    F2_TRY(f2_upload_coefs(ctx, X.coefs, X.C));
+    const size_t bytes = sizeof(double) * (size_t)X.C * (size_t)X.total();
+    f2_output env, gfb;
+    F2_TRY(f2_place(ctx, ctx->stage_out, env_or_null, bytes, X.mem_space, true, &env));
+    F2_TRY(f2_place(ctx, ctx->stage_aux, gfb_or_null, bytes, X.mem_space, false, &gfb));
+    const void* d_wave;
+    F2_TRY(f2_stage_wave(ctx, X.wave, X.wave_dtype, X.total(), X.mem_space, &d_wave));
+    *d_env = env.as<double>();
+    F2_TRY(f2_envelopes_device(ctx, X, d_wave, *d_env, gfb.as<double>(), spectral));
+    F2_TRY(f2_copy_back(ctx, env));
+    return f2_copy_back(ctx, gfb);
+}
+
 extern "C" {
 
 int f2_erb_filterbank_batch(f2_ctx* ctx, const void* wave, int wave_dtype, const int64_t* offsets,
@@ -795,22 +843,14 @@ int f2_erb_filterbank_batch(f2_ctx* ctx, const void* wave, int wave_dtype, const
     F2_CHECK(ctx, wave && coefs && gfb, F2_ERR_INVALID, "null data pointer");
     F2_TRY(f2_upload_offsets(ctx, offsets, B));
     F2_TRY(f2_upload_coefs(ctx, coefs, C));
-    double* d_gfb = gfb;
-    const size_t out_bytes = sizeof(double) * (size_t)C * (size_t)total;
-    const bool staged = mem_space != F2_MEM_DEVICE;
-    if (staged) {
-        F2_TRY(f2_reserve(ctx, ctx->stage_out, out_bytes));
-        d_gfb = (double*)ctx->stage_out.ptr;
-    }
+    f2_output out;
+    F2_TRY(f2_place(ctx, ctx->stage_out, gfb, sizeof(double) * (size_t)C * (size_t)total, mem_space, true, &out));
     const void* d_wave;
     F2_TRY(f2_stage_wave(ctx, wave, wave_dtype, total, mem_space, &d_wave));
     F2_TRY(f2_launch_filterbank(ctx, d_wave, wave_dtype, (const int64_t*)ctx->offsets.ptr, offsets,
-                                (const double*)ctx->coefs.ptr, B, C, d_gfb));
-    if (staged) {
-        F2_HIP(ctx, hipMemcpyAsync(gfb, d_gfb, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
-        if (mem_space == F2_MEM_HOST) F2_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    }
-    return F2_OK;
+                                (const double*)ctx->coefs.ptr, B, C, out.as<double>()));
+    F2_TRY(f2_copy_back(ctx, out));
+    return f2_host_wait(ctx, mem_space);
 }
 
 int f2_envelope_batch(f2_ctx* ctx, const double* gfb, const int64_t* offsets, int B, int C, int lpf,
@@ -822,26 +862,17 @@ int f2_envelope_batch(f2_ctx* ctx, const double* gfb, const int64_t* offsets, in
     if (B == 0 || C == 0 || total == 0) return F2_OK;
     F2_CHECK(ctx, gfb && env, F2_ERR_INVALID, "null data pointer");
     F2_TRY(f2_upload_offsets(ctx, offsets, B));
-    const double* d_gfb = gfb;
-    double* d_env = env;
     const size_t bytes = sizeof(double) * (size_t)C * (size_t)total;
-    const bool staged = mem_space != F2_MEM_DEVICE;
-    if (staged) {
-        // separate device buffers for the filterbank rows and the envelopes: rows of 32769..65536 samples then take the
-        // on-chip path (which parks intermediate data in the output rows) exactly as they do inside the fused call
-        F2_TRY(f2_reserve(ctx, ctx->stage_aux, bytes));
-        F2_TRY(f2_reserve(ctx, ctx->stage_out, bytes));
-        F2_HIP(ctx, hipMemcpyAsync(ctx->stage_aux.ptr, gfb, bytes, hipMemcpyHostToDevice, ctx->stream));
-        d_gfb = (const double*)ctx->stage_aux.ptr;
-        d_env = (double*)ctx->stage_out.ptr;
-    }
-    F2_TRY(f2_launch_envelope(ctx, d_gfb, (const int64_t*)ctx->offsets.ptr, offsets, B, C, lpf, cutoff_hz,
-                              fft_precision, d_env));
-    if (staged) {
-        F2_HIP(ctx, hipMemcpyAsync(env, d_env, bytes, hipMemcpyDeviceToHost, ctx->stream));
-        if (mem_space == F2_MEM_HOST) F2_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    }
-    return F2_OK;
+    // separate device buffers for the staged filterbank rows and the envelopes: rows of 32769..65536 samples then take the
+    // on-chip path (which parks intermediate data in the output rows) exactly as they do inside the fused call
+    const void* d_gfb;
+    F2_TRY(f2_stage_into(ctx, ctx->stage_aux, gfb, bytes, mem_space, &d_gfb));
+    f2_output out;
+    F2_TRY(f2_place(ctx, ctx->stage_out, env, bytes, mem_space, true, &out));
+    F2_TRY(f2_launch_envelope(ctx, (const double*)d_gfb, (const int64_t*)ctx->offsets.ptr, offsets, B, C, lpf, cutoff_hz,
+                              fft_precision, out.as<double>()));
+    F2_TRY(f2_copy_back(ctx, out));
+    return f2_host_wait(ctx, mem_space);
 }
 
 int f2_filterbank_envelope_fused(f2_ctx* ctx, const void* wave, int wave_dtype, const int64_t* offsets,
@@ -850,30 +881,12 @@ int f2_filterbank_envelope_fused(f2_ctx* ctx, const void* wave, int wave_dtype, 
     F2_TRY(f2_check_ctx(ctx));
     F2_TRY(f2_check_dsp(ctx, wave_dtype, lpf, cutoff_hz, fft_precision));
     F2_TRY(f2_check_batch(ctx, offsets, B, C, mem_space, false));
-    const int64_t total = offsets[B];
-    if (B == 0 || C == 0 || total == 0) return F2_OK;
+    if (B == 0 || C == 0 || offsets[B] == 0) return F2_OK;
     F2_CHECK(ctx, wave && coefs && env, F2_ERR_INVALID, "null data pointer");
-    F2_TRY(f2_upload_offsets(ctx, offsets, B));
-    F2_TRY(f2_upload_coefs(ctx, coefs, C));
-    const size_t bytes = sizeof(double) * (size_t)C * (size_t)total;
-    double* d_env = env;
-    double* d_gfb = gfb_or_null;
-    const bool staged = mem_space != F2_MEM_DEVICE;
-    if (staged) {
-        F2_TRY(f2_reserve(ctx, ctx->stage_out, bytes));
-        if (gfb_or_null) F2_TRY(f2_reserve(ctx, ctx->stage_aux, bytes));
-        d_env = (double*)ctx->stage_out.ptr;
-        d_gfb = gfb_or_null ? (double*)ctx->stage_aux.ptr : nullptr;
-    }
-    const void* d_wave;
-    F2_TRY(f2_stage_wave(ctx, wave, wave_dtype, total, mem_space, &d_wave));
-    F2_TRY(f2_envelopes_device(ctx, d_wave, wave_dtype, offsets, B, C, lpf, cutoff_hz, fft_precision, d_env, d_gfb, true));
-    if (staged) {
-        F2_HIP(ctx, hipMemcpyAsync(env, d_env, bytes, hipMemcpyDeviceToHost, ctx->stream));
-        if (gfb_or_null) F2_HIP(ctx, hipMemcpyAsync(gfb_or_null, d_gfb, bytes, hipMemcpyDeviceToHost, ctx->stream));
-        if (mem_space == F2_MEM_HOST) F2_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    }
-    return F2_OK;
+    const f2_batch X = {wave, wave_dtype, offsets, coefs, B, C, lpf, cutoff_hz, fft_precision, mem_space};
+    double* d_env;
+    F2_TRY(f2_batch_envelopes(ctx, X, env, gfb_or_null, true, &d_env));
+    return f2_host_wait(ctx, mem_space);
 }
 
 }  // extern "C"

@@ -13,9 +13,20 @@
 
 #include "../../include/f2cnn_hip.h"
 
+// A grow-only device allocation (f2_reserve) that frees itself. Move-only: a copy would free the block twice.
 struct f2_scratch {
     void* ptr = nullptr;
     size_t bytes = 0;
+    f2_scratch() = default;
+    f2_scratch(f2_scratch&& o) noexcept : ptr(o.ptr), bytes(o.bytes) { o.ptr = nullptr, o.bytes = 0; }
+    f2_scratch& operator=(f2_scratch&& o) noexcept {
+        std::swap(ptr, o.ptr);     // (o frees the old block when it goes)
+        std::swap(bytes, o.bytes);
+        return *this;
+    }
+    ~f2_scratch() {
+        if (ptr) (void)hipFree(ptr);
+    }
 };
 
 // tables of the spectral filterbank + envelope kernel (f2_spectral.hip) for one (coefficient table, length class)
@@ -34,7 +45,7 @@ struct f2_ctx {
     bool own_stream = true;
     int num_cus = 0;
     char err[512] = {0};
-    // grow-only device scratch areas (never freed before ctx destroy; stream-ordered reuse only)
+    // grow-only device scratch areas (freed by `delete ctx`, never before; stream-ordered reuse only)
     f2_scratch coefs;      // filter coefficients of the current call
     f2_scratch offsets;    // ragged offsets of the current call
     f2_scratch stage_in;   // F2_MEM_HOST staging
@@ -45,12 +56,16 @@ struct f2_ctx {
     f2_scratch xbuf;       // window tensor chunk between K3 and K4
     f2_scratch dense_in;   // conv4 outputs (+ dense1 outputs) of the windows of several utterances: one dense launch for all
     f2_scratch noise_wave; // f2_eval_noise_sweep: the (K+1) x batch float64 waveform when the caller gives no device buffer for it
-    f2_scratch noise_meta; // ... and its small arrays: sigma, 10^(snr / 10) per level, stats, window offsets
-    f2_scratch acc_meta;   // f2_label_accuracy: counts, window offsets, reference offsets / timepoints / signs
-    f2_scratch score_meta; // f2_cnn_score_windows: counts, loss sums, per-workgroup loss partials of the chunk in flight
-    f2_scratch pic_meta;   // f2_envelope_picture / f2_gammatonegram_batch: per-utterance span records and the vmin / vmax words (f2_picture.hip)
-    f2_scratch rs_meta;    // f2_resample_batch: per-utterance records and the workgroup prefix of the call (f2_resample.hip)
-    f2_scratch rs_tab;     // ... and the polyphase table of the last (up, down, half_len, taps)
+    // The small arrays of the call in flight (f2_meta_carve): sigma / stats / window offsets of the noise sweep, counts and reference
+    // labels of f2_label_accuracy, counts / loss sums / loss partials of f2_cnn_score_windows, span records and range words of the
+    // pictures, utterance records of f2_resample_batch. One area for all of them, which holds while
+    //  - nothing cached lives here: what a later call may find unchanged (spec_meta, rs_tab, offsets, coefs) has its own area;
+    //  - a call carves it once, before its first launch and before any nested entry point runs (f2_reserve frees and reallocates
+    //    on growth, and the noise sweep holds its pointers across the nested f2_eval_batch_strided), and no code reached from a
+    //    nested call reserves it;
+    //  - every reader and every upload goes through ctx->stream, so the next call's reuse is ordered behind them.
+    f2_scratch meta;
+    f2_scratch rs_tab;     // f2_resample_batch: the polyphase table of the last (up, down, half_len, taps)
     int64_t rs_up = 0, rs_down = 0, rs_half_len = -1;
     std::vector<double> rs_taps_host;   // the taps rs_tab was built from (skip the rebuild and the upload when equal)
     f2_scratch gather_log; // ln of the envelope samples a chunk of every-sample windows touches + column min / max (f2_gather.hip)
@@ -208,8 +223,76 @@ int f2_check_batch(f2_ctx* ctx, const int64_t* offsets, int B, int C, int mem_sp
 int f2_check_cnn(f2_ctx* ctx, const f2_cnn* cnn, int rows, int C);
 // *d_wave = the caller's pointer for F2_MEM_DEVICE, else ctx->stage_in after an asynchronous copy of `total` samples into it
 int f2_stage_wave(f2_ctx* ctx, const void* wave, int wave_dtype, int64_t total, int mem_space, const void** d_wave);
-// the same for `bytes` bytes of any input (f2_stage_wave is this with the sample size of wave_dtype)
+// the same for `bytes` bytes of any input (f2_stage_wave is this with the sample size of wave_dtype), and into another area
 int f2_stage_input(f2_ctx* ctx, const void* src, size_t bytes, int mem_space, const void** d_src);
+int f2_stage_into(f2_ctx* ctx, f2_scratch& area, const void* src, size_t bytes, int mem_space, const void** d_src);
+// the wait for the stream that ends an F2_MEM_HOST call (F2_MEM_DEVICE and F2_MEM_HOST_ASYNC calls only enqueue)
+int f2_host_wait(f2_ctx* ctx, int mem_space);
+
+// ---- where an output lives (f2_api.hip). The one rule of every entry point:
+//   device memory, pointer given   the caller's pointer
+//   device memory, NULL            `area` if a later kernel needs the data, else nowhere (dev == NULL)
+//   host memory, pointer given     `area`, and f2_copy_back enqueues the copy to the caller
+//   host memory, NULL              `area` without a copy back if a later kernel needs the data, else nowhere
+// (F2_MEM_HOST_ASYNC is host memory here.) ----
+struct f2_output {
+    char* dev = nullptr;    // what the kernels write
+    char* host = nullptr;   // where f2_copy_back sends it, or NULL
+    size_t bytes = 0;
+    bool callers = false;   // dev is the caller's buffer (all of it), not scratch
+    template <class T>
+    T* as() const { return (T*)dev; }
+    // bytes [first, first + n) of an output made chunk by chunk: scratch holds one chunk at a time, a caller's buffer all of them
+    f2_output chunk(size_t first, size_t n) const {
+        f2_output c;
+        c.dev = dev && callers ? dev + first : dev, c.host = host ? host + first : nullptr, c.bytes = n, c.callers = callers;
+        return c;
+    }
+};
+int f2_place(f2_ctx* ctx, f2_scratch& area, void* caller_or_null, size_t bytes, int mem_space, bool needed_on_device, f2_output* out);
+int f2_copy_back(f2_ctx* ctx, const f2_output& o);   // enqueued on the stream, not waited for; nothing without a host destination
+// Scores (2 floats) and labels (1 byte) of n windows by that rule, sharing ctx->stage_aux as [scores | labels | tail] + 64 bytes of
+// slack: only the parts that need scratch are there; `tail` (8-byte aligned, NULL for tail_bytes == 0) is the caller's to use.
+struct f2_score_outputs {
+    f2_output scores, labels;
+    char* tail = nullptr;
+};
+int f2_place_scores(f2_ctx* ctx, float* scores_or_null, uint8_t* labels_or_null, int64_t n, int mem_space, bool need_scores,
+                    bool need_labels, size_t tail_bytes, f2_score_outputs* out);
+
+// The small arrays of a call, carved from ctx->meta (see the three conditions there): name every array once with add(), then
+// reserve() sizes the area and sets the pointers - 8-byte elements first, byte arrays behind them, each kind in the order named
+// and without gaps (so arrays named in a row can go up in one upload).
+struct f2_meta_carve {
+    struct item {
+        void* slot;      // the T* to set
+        size_t bytes;
+        bool wide;
+    } items[8];
+    int n = 0;
+    template <class T>
+    void add(T** p, size_t count) {
+        static_assert(sizeof(T) == 8 || sizeof(T) == 1, "8-byte or byte elements");
+        items[n++] = {(void*)p, sizeof(T) * count, sizeof(T) == 8};
+    }
+    int reserve(f2_ctx* ctx);
+};
+
+// A ragged batch of waves and how its envelopes are made: the arguments the envelope calls share, filled once by the entry point
+struct f2_batch {
+    const void* wave;
+    int wave_dtype;
+    const int64_t* offsets;
+    const double* coefs;
+    int B, C, lpf;
+    double cutoff_hz;
+    int fft_precision, mem_space;
+    int64_t total() const { return offsets[B]; }
+};
+// Envelopes of the batch on the device: uploads offsets and coefficients, places the envelopes (stage_out, or the caller's device
+// buffer) and the filterbank rows if wanted (stage_aux), stages the wave, runs f2_envelopes_device and enqueues the copies to a host
+// caller. *d_env: where the envelopes are. Does not wait.
+int f2_batch_envelopes(f2_ctx* ctx, const f2_batch& X, double* env_or_null, double* gfb_or_null, bool spectral, double** d_env);
 
 #define F2_HIP(ctx, call)                                                                      \
     do {                                                                                       \
@@ -327,12 +410,6 @@ struct f2_handoff {
     const int64_t* h_x32_off = nullptr;     // the same on the host (owned by the context, valid until the next plan)
 };
 int f2_plan_handoff(f2_ctx* ctx, const int64_t* h_offsets, int B, int C, int precision, bool want_gfb, f2_handoff* plan);
-// Filterbank + envelope of a ragged batch on the device (f2_api.hip). `spectral`: by the routes of f2_filterbank_envelope_fused -
-// spectral kernel with its guard, then filterbank + envelope kernels for the rest; without it (the eval calls) the two kernels
-// for every utterance. Offsets and coefficients already uploaded (f2_upload_offsets / f2_upload_coefs); h_offsets host,
-// d_wave / d_env / d_gfb (NULL: not wanted) device.
-int f2_envelopes_device(f2_ctx* ctx, const void* d_wave, int wave_dtype, const int64_t* h_offsets, int B, int C, int lpf,
-                        double cutoff_hz, int fft_precision, double* d_env, double* d_gfb, bool spectral);
 // d_uflag (device, B ints) != NULL: only utterances whose flag is non-zero are processed (the rest were served by the
 // spectral kernel); the flags may be written by earlier launches on the stream.
 // h_flag0 (host, B ints, with d_uflag): the flags as they are before the spectral kernel runs - the utterances this launch

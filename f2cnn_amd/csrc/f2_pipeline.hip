@@ -23,6 +23,12 @@ int finish_positive(f2_ctx* ctx) {
     return F2_OK;
 }
 
+// the end of a call that gathers windows: their copy to a host caller; a host call and a normalising one wait (finish_positive)
+int finish_windows(f2_ctx* ctx, const f2_output& win, int normalize) {
+    F2_TRY(f2_copy_back(ctx, win));
+    return normalize || win.host ? finish_positive(ctx) : F2_OK;
+}
+
 // Input range of f2_cnn_forward: ctx->flags words RANGE_WORD .. + 2 = bit pattern of max |x| over the finite values, inf / NaN
 // seen, complement of the quietest window's max |x| (word 0 is the gather's flag)
 constexpr int RANGE_WORD = 4;
@@ -118,23 +124,14 @@ int f2_gather_windows(f2_ctx* ctx, const double* env, int C, int64_t N, const in
     }
     const int64_t* d_centers = nullptr;
     if (centers) F2_TRY(f2_upload_windows(ctx, centers, nullptr, n_windows, &d_centers, nullptr));
-    const size_t env_bytes = sizeof(double) * (size_t)C * (size_t)N;
-    const size_t out_bytes = sizeof(float) * (size_t)n_windows * R * (size_t)C;
-    const double* d_env = env;
-    float* d_out = out;
-    if (mem_space == F2_MEM_HOST) {
-        F2_TRY(f2_reserve(ctx, ctx->stage_in, env_bytes));
-        F2_TRY(f2_reserve(ctx, ctx->stage_out, out_bytes));
-        F2_HIP(ctx, hipMemcpyAsync(ctx->stage_in.ptr, env, env_bytes, hipMemcpyHostToDevice, ctx->stream));
-        d_env = (const double*)ctx->stage_in.ptr;
-        d_out = (float*)ctx->stage_out.ptr;
-    }
+    f2_output win;
+    F2_TRY(f2_place(ctx, ctx->stage_out, out, sizeof(float) * (size_t)n_windows * R * (size_t)C, mem_space, true, &win));
+    const void* d_env;
+    F2_TRY(f2_stage_input(ctx, env, sizeof(double) * (size_t)C * (size_t)N, mem_space, &d_env));
     F2_TRY(reset_flag(ctx));
-    F2_TRY(f2_launch_gather(ctx, d_env, C, N, d_centers, reach, n_windows, radius, step, normalize, d_out,
+    F2_TRY(f2_launch_gather(ctx, (const double*)d_env, C, N, d_centers, reach, n_windows, radius, step, normalize, win.as<float>(),
                             (int*)ctx->flags.ptr));
-    if (mem_space == F2_MEM_HOST)
-        F2_HIP(ctx, hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    return normalize || mem_space == F2_MEM_HOST ? finish_positive(ctx) : F2_OK;
+    return finish_windows(ctx, win, normalize);
 }
 
 int f2_cnn_forward(f2_ctx* ctx, const f2_cnn* cnn, const float* x, int64_t n, float* scores, uint8_t* labels,
@@ -146,33 +143,26 @@ int f2_cnn_forward(f2_ctx* ctx, const f2_cnn* cnn, const float* x, int64_t n, fl
     if (n == 0) return F2_OK;
     F2_CHECK(ctx, x, F2_ERR_INVALID, "x is NULL");
     const size_t xs = (size_t)cnn->rows * cnn->channels;
-    const f2_scale_set* S = nullptr;
-    f2_cnn_route route;
-    if (mem_space == F2_MEM_DEVICE) {
-        double bound = -1.0;
-        F2_TRY(forward_route(ctx, cnn, x, n, &S, &route, &bound));
-        F2_TRY(cnn_forward_device(ctx, cnn, S, route, x, n, scores, labels));
-        cnn->last_input_bound = bound;
-        return F2_OK;
-    }
-    const int64_t chunk = n < CNN_CHUNK ? n : CNN_CHUNK;
-    F2_TRY(f2_reserve(ctx, ctx->stage_in, sizeof(float) * xs * (size_t)chunk));
-    F2_TRY(f2_reserve(ctx, ctx->stage_aux, (sizeof(float) * 2 + 1) * (size_t)chunk + 64));
-    float* d_scores = (float*)ctx->stage_aux.ptr;
-    uint8_t* d_labels = (uint8_t*)(d_scores + 2 * chunk);
+    // Device memory: one range pass and one route for the whole call. Host memory: chunk by chunk through stage_in, each chunk
+    // with its own range pass and route, its scores and labels back before the next one goes up.
+    const int64_t chunk = mem_space == F2_MEM_DEVICE || n < CNN_CHUNK ? n : CNN_CHUNK;
+    f2_score_outputs out;
+    F2_TRY(f2_place_scores(ctx, scores, labels, chunk, mem_space, false, false, 0, &out));
     double bound = 0.0;   // largest B of the chunks, -1 once one of them ran on the float32 kernels
     for (int64_t s = 0; s < n; s += chunk) {
         const int64_t m = n - s < chunk ? n - s : chunk;
-        F2_HIP(ctx, hipMemcpyAsync(ctx->stage_in.ptr, x + (size_t)s * xs, sizeof(float) * xs * (size_t)m,
-                                   hipMemcpyHostToDevice, ctx->stream));
+        const void* d_x;
+        F2_TRY(f2_stage_input(ctx, x + (size_t)s * xs, sizeof(float) * xs * (size_t)m, mem_space, &d_x));
+        const f2_scale_set* S = nullptr;
+        f2_cnn_route route;
         double b = -1.0;
-        F2_TRY(forward_route(ctx, cnn, (const float*)ctx->stage_in.ptr, m, &S, &route, &b));
+        F2_TRY(forward_route(ctx, cnn, (const float*)d_x, m, &S, &route, &b));
         bound = chunks_bound(bound, b);
-        F2_TRY(cnn_forward_device(ctx, cnn, S, route, (const float*)ctx->stage_in.ptr, m, d_scores, d_labels));
-        if (scores)
-            F2_HIP(ctx, hipMemcpyAsync(scores + 2 * s, d_scores, sizeof(float) * 2 * (size_t)m, hipMemcpyDeviceToHost, ctx->stream));
-        if (labels) F2_HIP(ctx, hipMemcpyAsync(labels + s, d_labels, (size_t)m, hipMemcpyDeviceToHost, ctx->stream));
-        F2_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        const f2_output sc = out.scores.chunk(sizeof(float) * 2 * (size_t)s, sizeof(float) * 2 * (size_t)m), lb = out.labels.chunk((size_t)s, (size_t)m);
+        F2_TRY(cnn_forward_device(ctx, cnn, S, route, (const float*)d_x, m, sc.as<float>(), lb.as<uint8_t>()));
+        F2_TRY(f2_copy_back(ctx, sc));
+        F2_TRY(f2_copy_back(ctx, lb));
+        F2_TRY(f2_host_wait(ctx, mem_space));
     }
     cnn->last_input_bound = bound;
     return F2_OK;
@@ -184,54 +174,35 @@ int f2_cnn_forward(f2_ctx* ctx, const f2_cnn* cnn, const float* x, int64_t n, fl
 namespace {
 
 struct eval_call {
-    bool host = false;
     int R = 0;
-    int64_t total = 0;           // samples of the batch
     double* d_env = nullptr;     // envelopes of the batch, (C, n_b) blocks at C * offsets[b]
     // CNN side (eval_cnn_begin)
-    int64_t n_total = 0, group_cap = 0;
+    int64_t group_cap = 0;
     size_t flat = 0;
-    float *d_a4 = nullptr, *d_a5 = nullptr, *d_scores = nullptr;
-    uint8_t* d_labels = nullptr;
+    float *d_a4 = nullptr, *d_a5 = nullptr;
+    f2_score_outputs out;        // scores and labels of all windows of the call
     const f2_scale_set* S1 = nullptr;
     f2_cnn_route route;          // of every launch of the call
     int64_t g0 = 0, gn = 0;      // first window and size of the open dense group
 };
 
 // the argument errors of the eval calls (include/f2cnn_hip.h: f2_eval_batch); nothing is launched before they pass
-int eval_check(f2_ctx* ctx, const f2_cnn* cnn, int wave_dtype, const int64_t* offsets, const double* coefs, int B, int C, int lpf,
-               double cutoff_hz, int fft_precision, int radius, int step, int mem_space, eval_call* E) {
+int eval_check(f2_ctx* ctx, const f2_cnn* cnn, const f2_batch& X, int radius, int step, eval_call* E) {
     F2_TRY(f2_check_ctx(ctx));
-    F2_TRY(f2_check_dsp(ctx, wave_dtype, lpf, cutoff_hz, fft_precision));
-    F2_TRY(f2_check_batch(ctx, offsets, B, C, mem_space, true));
-    F2_CHECK(ctx, coefs && radius >= 0 && step >= 0, F2_ERR_INVALID, "coefs is NULL, or negative radius or step");
+    F2_TRY(f2_check_dsp(ctx, X.wave_dtype, X.lpf, X.cutoff_hz, X.fft_precision));
+    F2_TRY(f2_check_batch(ctx, X.offsets, X.B, X.C, X.mem_space, true));
+    F2_CHECK(ctx, X.coefs && radius >= 0 && step >= 0, F2_ERR_INVALID, "coefs is NULL, or negative radius or step");
     E->R = 2 * radius + 1;
-    F2_TRY(f2_check_cnn(ctx, cnn, E->R, C));
-    E->host = mem_space == F2_MEM_HOST;
-    E->total = offsets[B];
-    return F2_OK;
+    return f2_check_cnn(ctx, cnn, E->R, X.C);
 }
 
 // filterbank + envelope of the whole batch, always by the two kernels: one utterance evaluated alone and inside a batch
 // goes through the same envelope kernel. The envelopes stay in stage_out (or the caller's device buffer) for the window loop.
 // With no window to evaluate (n_windows == 0) a host call is complete when this returns.
-int eval_envelopes(f2_ctx* ctx, eval_call* E, const void* wave, int wave_dtype, const int64_t* offsets, const double* coefs, int B,
-                   int C, int lpf, double cutoff_hz, int fft_precision, double* env_or_null, int64_t n_windows, int mem_space) {
-    F2_CHECK(ctx, wave, F2_ERR_INVALID, "null wave");
-    F2_TRY(f2_upload_offsets(ctx, offsets, B));
-    F2_TRY(f2_upload_coefs(ctx, coefs, C));
-    const size_t env_bytes = sizeof(double) * (size_t)C * (size_t)E->total;
-    E->d_env = env_or_null;
-    if (E->host || !env_or_null) {
-        F2_TRY(f2_reserve(ctx, ctx->stage_out, env_bytes));
-        E->d_env = (double*)ctx->stage_out.ptr;
-    }
-    const void* d_wave;
-    F2_TRY(f2_stage_wave(ctx, wave, wave_dtype, E->total, mem_space, &d_wave));
-    F2_TRY(f2_envelopes_device(ctx, d_wave, wave_dtype, offsets, B, C, lpf, cutoff_hz, fft_precision, E->d_env, nullptr, false));
-    if (E->host && env_or_null) F2_HIP(ctx, hipMemcpyAsync(env_or_null, E->d_env, env_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    if (n_windows == 0 && E->host) F2_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return F2_OK;
+int eval_envelopes(f2_ctx* ctx, eval_call* E, const f2_batch& X, double* env_or_null, int64_t n_windows) {
+    F2_CHECK(ctx, X.wave, F2_ERR_INVALID, "null wave");
+    F2_TRY(f2_batch_envelopes(ctx, X, env_or_null, nullptr, false, &E->d_env));
+    return n_windows == 0 ? f2_host_wait(ctx, X.mem_space) : F2_OK;
 }
 
 // Buffers of the window loop: xbuf and the convolution workspace for `chunk` windows, conv4 / dense1 outputs of a dense group
@@ -239,8 +210,7 @@ int eval_envelopes(f2_ctx* ctx, eval_call* E, const void* wave, int wave_dtype, 
 // fills whole rounds of the device - launched per 14 240-window utterance its second round was one third full), scores and
 // labels of all n_total windows (staged for host calls); nothing leaves HBM. Clears the error flag.
 int eval_cnn_begin(f2_ctx* ctx, const f2_cnn* cnn, eval_call* E, int64_t chunk, int64_t n_total, int C, float* scores_or_null,
-                   uint8_t* labels_or_null) {
-    E->n_total = n_total;
+                   uint8_t* labels_or_null, int mem_space) {
     E->group_cap = n_total < DENSE_GROUP ? n_total : DENSE_GROUP;
     const size_t conv_floats = f2_cnn_workspace_floats(cnn) - f2_cnn_dense_floats(cnn);
     E->flat = f2_cnn_flat_floats(cnn);
@@ -249,13 +219,7 @@ int eval_cnn_begin(f2_ctx* ctx, const f2_cnn* cnn, eval_call* E, int64_t chunk, 
     F2_TRY(f2_reserve(ctx, ctx->dense_in, sizeof(float) * f2_cnn_dense_floats(cnn) * (size_t)E->group_cap));
     E->d_a4 = (float*)ctx->dense_in.ptr;
     E->d_a5 = E->d_a4 + E->flat * (size_t)E->group_cap;
-    E->d_scores = scores_or_null;
-    E->d_labels = labels_or_null;
-    if (E->host) {
-        F2_TRY(f2_reserve(ctx, ctx->stage_aux, (sizeof(float) * 2 + 1) * (size_t)n_total + 64));
-        E->d_scores = (float*)ctx->stage_aux.ptr;
-        E->d_labels = (uint8_t*)(E->d_scores + 2 * n_total);
-    }
+    F2_TRY(f2_place_scores(ctx, scores_or_null, labels_or_null, n_total, mem_space, false, false, 0, &E->out));
     F2_TRY(f2_cnn_scale_set(ctx, cnn, 0, &E->S1));   // K3's normalised windows lie in [0, 1] by construction: no range pass
     E->route = f2_cnn_call_route(ctx, cnn, E->S1 != nullptr);
     E->g0 = E->gn = 0;
@@ -263,9 +227,11 @@ int eval_cnn_begin(f2_ctx* ctx, const f2_cnn* cnn, eval_call* E, int64_t chunk, 
 }
 
 int eval_dense_flush(f2_ctx* ctx, const f2_cnn* cnn, eval_call* E) {
+    float* d_scores = E->out.scores.as<float>();
+    uint8_t* d_labels = E->out.labels.as<uint8_t>();
     if (E->gn > 0)
-        F2_TRY(f2_launch_cnn_dense(ctx, cnn, E->S1, E->route, E->d_a4, E->gn, E->d_a5, E->d_scores ? E->d_scores + 2 * E->g0 : nullptr,
-                                   E->d_labels ? E->d_labels + E->g0 : nullptr));
+        F2_TRY(f2_launch_cnn_dense(ctx, cnn, E->S1, E->route, E->d_a4, E->gn, E->d_a5, d_scores ? d_scores + 2 * E->g0 : nullptr,
+                                   d_labels ? d_labels + E->g0 : nullptr));
     E->g0 += E->gn;
     E->gn = 0;
     return F2_OK;
@@ -284,14 +250,10 @@ int eval_chunk_convs(f2_ctx* ctx, const f2_cnn* cnn, eval_call* E, int64_t m) {
 }
 
 // the last dense group, scores / labels to a host caller, and the wait for the stream with the windows' error flag
-int eval_cnn_end(f2_ctx* ctx, const f2_cnn* cnn, eval_call* E, float* scores_or_null, uint8_t* labels_or_null) {
+int eval_cnn_end(f2_ctx* ctx, const f2_cnn* cnn, eval_call* E) {
     F2_TRY(eval_dense_flush(ctx, cnn, E));
-    if (E->host) {
-        if (scores_or_null)
-            F2_HIP(ctx, hipMemcpyAsync(scores_or_null, E->d_scores, sizeof(float) * 2 * (size_t)E->n_total, hipMemcpyDeviceToHost, ctx->stream));
-        if (labels_or_null)
-            F2_HIP(ctx, hipMemcpyAsync(labels_or_null, E->d_labels, (size_t)E->n_total, hipMemcpyDeviceToHost, ctx->stream));
-    }
+    F2_TRY(f2_copy_back(ctx, E->out.scores));
+    F2_TRY(f2_copy_back(ctx, E->out.labels));
     return finish_positive(ctx);
 }
 
@@ -299,12 +261,12 @@ int eval_cnn_end(f2_ctx* ctx, const f2_cnn* cnn, eval_call* E, float* scores_or_
 
 // f2_eval_batch, and f2_eval_utterance as its B = 1 case with the envelope output (env_or_null, in mem_space) and the window
 // count (n_windows_out): every-sample windows -> normalise -> conv1 .. conv4, utterance by utterance, chunk by chunk
-static int eval_batch_impl(f2_ctx* ctx, const f2_cnn* cnn, const void* wave, int wave_dtype, const int64_t* offsets,
-                           const double* coefs, int B, int C, int lpf, double cutoff_hz, int fft_precision, int radius, int step,
-                           double* env_or_null, float* scores_or_null, uint8_t* labels_or_null, int64_t* n_windows_out,
-                           int mem_space) {
+static int eval_batch_impl(f2_ctx* ctx, const f2_cnn* cnn, const f2_batch& X, int radius, int step, double* env_or_null,
+                           float* scores_or_null, uint8_t* labels_or_null, int64_t* n_windows_out) {
     eval_call E;
-    F2_TRY(eval_check(ctx, cnn, wave_dtype, offsets, coefs, B, C, lpf, cutoff_hz, fft_precision, radius, step, mem_space, &E));
+    F2_TRY(eval_check(ctx, cnn, X, radius, step, &E));
+    const int64_t* offsets = X.offsets;
+    const int B = X.B, C = X.C;
     int64_t nb_total = 0, nb_max = 0;
     for (int b = 0; b < B; ++b) {
         const int64_t nb = offsets[b + 1] - offsets[b] - (int64_t)E.R * step;   // Evaluating.py:73
@@ -314,12 +276,11 @@ static int eval_batch_impl(f2_ctx* ctx, const f2_cnn* cnn, const void* wave, int
         }
     }
     if (n_windows_out) *n_windows_out = nb_total;
-    if (E.total == 0) return F2_OK;
-    F2_TRY(eval_envelopes(ctx, &E, wave, wave_dtype, offsets, coefs, B, C, lpf, cutoff_hz, fft_precision, env_or_null, nb_total,
-                          mem_space));
+    if (X.total() == 0) return F2_OK;
+    F2_TRY(eval_envelopes(ctx, &E, X, env_or_null, nb_total));
     if (nb_total == 0) return F2_OK;
     const int64_t chunk = nb_max < CNN_CHUNK ? nb_max : CNN_CHUNK;
-    F2_TRY(eval_cnn_begin(ctx, cnn, &E, chunk, nb_total, C, scores_or_null, labels_or_null));
+    F2_TRY(eval_cnn_begin(ctx, cnn, &E, chunk, nb_total, C, scores_or_null, labels_or_null, X.mem_space));
     const int64_t reach = (int64_t)radius * step;
     for (int b = 0; b < B; ++b) {
         const int64_t N = offsets[b + 1] - offsets[b];
@@ -333,7 +294,7 @@ static int eval_batch_impl(f2_ctx* ctx, const f2_cnn* cnn, const void* wave, int
             F2_TRY(eval_chunk_convs(ctx, cnn, &E, m));
         }
     }
-    return eval_cnn_end(ctx, cnn, &E, scores_or_null, labels_or_null);
+    return eval_cnn_end(ctx, cnn, &E);
 }
 
 // windows f2_eval_batch_strided evaluates in an utterance of n samples (R = 2 * radius + 1 rows)
@@ -342,18 +303,36 @@ static int64_t strided_windows(int64_t n, int R, int step, int hop) {
     return nb > 0 ? (nb + hop - 1) / hop : 0;
 }
 
+extern "C" {
+
+int f2_eval_utterance(f2_ctx* ctx, const f2_cnn* cnn, const void* wave, int wave_dtype, int64_t N, const double* coefs,
+                      int C, int lpf, double cutoff_hz, int fft_precision, int radius, int step, double* env_or_null,
+                      float* scores_or_null, uint8_t* labels_or_null, int64_t* n_windows_out, int mem_space) {
+    if (ctx && !wave) return f2_fail(ctx, F2_ERR_INVALID, "null wave");   // (also for N == 0, unlike f2_eval_batch)
+    const int64_t offsets[2] = {0, N};
+    const f2_batch X = {wave, wave_dtype, offsets, coefs, 1, C, lpf, cutoff_hz, fft_precision, mem_space};
+    return eval_batch_impl(ctx, cnn, X, radius, step, env_or_null, scores_or_null, labels_or_null, n_windows_out);
+}
+
+int f2_eval_batch(f2_ctx* ctx, const f2_cnn* cnn, const void* wave, int wave_dtype, const int64_t* offsets,
+                  const double* coefs, int B, int C, int lpf, double cutoff_hz, int fft_precision, int radius, int step,
+                  float* scores_or_null, uint8_t* labels_or_null, int mem_space) {
+    const f2_batch X = {wave, wave_dtype, offsets, coefs, B, C, lpf, cutoff_hz, fft_precision, mem_space};
+    return eval_batch_impl(ctx, cnn, X, radius, step, nullptr, scores_or_null, labels_or_null, nullptr);
+}
+
 // f2_eval_batch_strided: window j of utterance b is every-sample window j * hop. A chunk is up to CNN_CHUNK windows taken from
 // as many utterances as it holds (an utterance may continue in the next chunk): one window-stage launch set and one
 // convolution launch set per chunk, whatever B. (On the decimating route a chunk also closes at COLUMN_CAP columns of the
 // window stage's scratch - 2 * radius * step / hop columns per segment on top of its windows: 150 MB for 128 channels - which
 // only batches of very many very short utterances at a small hop reach.)
-static int eval_strided_impl(f2_ctx* ctx, const f2_cnn* cnn, const void* wave, int wave_dtype, const int64_t* offsets,
-                             const double* coefs, int B, int C, int lpf, double cutoff_hz, int fft_precision, int radius, int step,
-                             int hop, float* scores_or_null, uint8_t* labels_or_null, int64_t* window_offsets_or_null,
-                             int mem_space) {
+int f2_eval_batch_strided(f2_ctx* ctx, const f2_cnn* cnn, const void* wave, int wave_dtype, const int64_t* offsets,
+                          const double* coefs, int B, int C, int lpf, double cutoff_hz, int fft_precision, int radius, int step,
+                          int hop, float* scores_or_null, uint8_t* labels_or_null, int64_t* window_offsets_or_null, int mem_space) {
     constexpr int64_t COLUMN_CAP = 8 * CNN_CHUNK;
+    const f2_batch X = {wave, wave_dtype, offsets, coefs, B, C, lpf, cutoff_hz, fft_precision, mem_space};
     eval_call E;
-    F2_TRY(eval_check(ctx, cnn, wave_dtype, offsets, coefs, B, C, lpf, cutoff_hz, fft_precision, radius, step, mem_space, &E));
+    F2_TRY(eval_check(ctx, cnn, X, radius, step, &E));
     F2_CHECK(ctx, hop >= 1, F2_ERR_INVALID, "hop must be at least 1 sample (got %d)", hop);
     std::vector<int64_t> nbh((size_t)B);
     int64_t n_total = 0;
@@ -363,11 +342,11 @@ static int eval_strided_impl(f2_ctx* ctx, const f2_cnn* cnn, const void* wave, i
         n_total += nbh[(size_t)b];
         if (window_offsets_or_null) window_offsets_or_null[b + 1] = n_total;
     }
-    if (E.total == 0) return F2_OK;
-    F2_TRY(eval_envelopes(ctx, &E, wave, wave_dtype, offsets, coefs, B, C, lpf, cutoff_hz, fft_precision, nullptr, n_total, mem_space));
+    if (X.total() == 0) return F2_OK;
+    F2_TRY(eval_envelopes(ctx, &E, X, nullptr, n_total));
     if (n_total == 0) return F2_OK;
     const int64_t chunk = n_total < CNN_CHUNK ? n_total : CNN_CHUNK;
-    F2_TRY(eval_cnn_begin(ctx, cnn, &E, chunk, n_total, C, scores_or_null, labels_or_null));
+    F2_TRY(eval_cnn_begin(ctx, cnn, &E, chunk, n_total, C, scores_or_null, labels_or_null, mem_space));
     const bool columns = f2_gather_strided_blocked(ctx, C, step, hop);
     std::vector<f2_win_seg> segs;
     int64_t m = 0, cols = 0;     // windows and scratch columns of the open chunk
@@ -397,26 +376,27 @@ static int eval_strided_impl(f2_ctx* ctx, const f2_cnn* cnn, const void* wave, i
             if (m == chunk) F2_TRY(close_chunk());
         }
     F2_TRY(close_chunk());
-    return eval_cnn_end(ctx, cnn, &E, scores_or_null, labels_or_null);
+    return eval_cnn_end(ctx, cnn, &E);
 }
 
 // f2_eval_noise_sweep: the K noisy levels and the clean one of a ragged batch as ONE (K+1) * B-utterance float64 batch in device
-// memory (f2_noise.hip), through eval_strided_impl as a device call, then the tally of its labels on the device. Only the clean
+// memory (f2_noise.hip), through f2_eval_batch_strided as a device call, then the tally of its labels on the device. Only the clean
 // samples go up; sigma, stats and what the caller asked for come back behind one wait.
-static int eval_noise_sweep_impl(f2_ctx* ctx, const f2_cnn* cnn, const void* wave, int wave_dtype, const int64_t* offsets,
-                                 const double* coefs, int B, int C, int lpf, double cutoff_hz, int fft_precision, int radius, int step,
-                                 int hop, const double* snr_db, int K, uint64_t seed, double* noisy_or_null, float* scores_or_null,
-                                 uint8_t* labels_or_null, int64_t* window_offsets_or_null, double* sigma_or_null,
-                                 int64_t* stats_or_null, int mem_space) {
+int f2_eval_noise_sweep(f2_ctx* ctx, const f2_cnn* cnn, const void* wave, int wave_dtype, const int64_t* offsets,
+                        const double* coefs, int B, int C, int lpf, double cutoff_hz, int fft_precision, int radius, int step,
+                        int hop, const double* snr_db, int K, uint64_t seed, double* noisy_or_null, float* scores_or_null,
+                        uint8_t* labels_or_null, int64_t* window_offsets_or_null, double* sigma_or_null, int64_t* stats_or_null,
+                        int mem_space) {
+    const f2_batch X = {wave, wave_dtype, offsets, coefs, B, C, lpf, cutoff_hz, fft_precision, mem_space};
     eval_call E;
-    F2_TRY(eval_check(ctx, cnn, wave_dtype, offsets, coefs, B, C, lpf, cutoff_hz, fft_precision, radius, step, mem_space, &E));
+    F2_TRY(eval_check(ctx, cnn, X, radius, step, &E));
     F2_CHECK(ctx, hop >= 1, F2_ERR_INVALID, "hop must be at least 1 sample (got %d)", hop);
     F2_CHECK(ctx, K >= 1 && snr_db, F2_ERR_INVALID, "a sweep needs at least one noise level (K=%d) and their snr_db", K);
     for (int k = 0; k < K; ++k) F2_CHECK(ctx, std::isfinite(snr_db[k]), F2_ERR_INVALID, "snr_db[%d] is not finite", k);
     F2_CHECK(ctx, ((int64_t)K + 1) * (B > 0 ? B : 1) <= INT32_MAX / 2, F2_ERR_UNSUPPORTED, "%d levels of %d utterances", K + 1, B);
-    F2_CHECK(ctx, wave || E.total == 0, F2_ERR_INVALID, "null wave");
+    const int64_t total = X.total();
+    F2_CHECK(ctx, wave || total == 0, F2_ERR_INVALID, "null wave");
     const int U = (K + 1) * B;
-    const int64_t total = E.total;
     // the (K+1) * B batch: the clean offsets tiled, its window offsets, 10^(snr / 10) per level
     std::vector<int64_t> tiled((size_t)U + 1, 0), wo((size_t)U + 1, 0);
     int64_t max_windows = 0;
@@ -438,27 +418,18 @@ static int eval_noise_sweep_impl(f2_ctx* ctx, const f2_cnn* cnn, const void* wav
     std::vector<double> lin((size_t)K);
     for (int k = 0; k < K; ++k) lin[(size_t)k] = std::pow(10.0, snr_db[k] / 10.0);   // Evaluating.py:189 SNRdbToSNRlinear
 
-    // small arrays of the call: [sigma (U) | lin (K) | stats (2 U) | window offsets (U + 1)], all 8-byte words
-    F2_TRY(f2_reserve(ctx, ctx->noise_meta, 8 * ((size_t)U + K + 2 * (size_t)U + U + 1)));
-    double* d_sigma = (double*)ctx->noise_meta.ptr;
-    double* d_lin = d_sigma + U;
-    int64_t* d_stats = (int64_t*)(d_lin + K);
-    int64_t* d_wo = d_stats + 2 * (size_t)U;
-    const size_t noisy_bytes = sizeof(double) * (size_t)(K + 1) * (size_t)total;
-    double* d_noisy = noisy_or_null;
-    if (E.host || !noisy_or_null) {
-        F2_TRY(f2_reserve(ctx, ctx->noise_wave, noisy_bytes));
-        d_noisy = (double*)ctx->noise_wave.ptr;
-    }
-    // scores / labels of the device call below: the caller's device buffers, else staging (the tally always needs the labels)
-    float* d_scores = scores_or_null;
-    uint8_t* d_labels = labels_or_null;
-    if (E.host || !labels_or_null) {
-        const bool stage_scores = E.host && scores_or_null;
-        F2_TRY(f2_reserve(ctx, ctx->stage_aux, (stage_scores ? sizeof(float) * 2 : 0) * (size_t)n_total + (size_t)n_total + 64));
-        if (E.host) d_scores = stage_scores ? (float*)ctx->stage_aux.ptr : nullptr;
-        d_labels = (uint8_t*)ctx->stage_aux.ptr + (stage_scores ? sizeof(float) * 2 * (size_t)n_total : 0);
-    }
+    // small arrays of the call, held across the nested evaluation (which does not touch ctx->meta)
+    double *d_sigma, *d_lin;
+    int64_t *d_stats, *d_wo;
+    f2_meta_carve meta;
+    meta.add(&d_sigma, (size_t)U), meta.add(&d_lin, (size_t)K), meta.add(&d_stats, 2 * (size_t)U), meta.add(&d_wo, (size_t)U + 1);
+    F2_TRY(meta.reserve(ctx));
+    f2_output noisy;
+    F2_TRY(f2_place(ctx, ctx->noise_wave, noisy_or_null, sizeof(double) * (size_t)(K + 1) * (size_t)total, mem_space, true, &noisy));
+    // scores / labels of the device call below (the tally always needs the labels). They stay in stage_aux: the nested call, a
+    // device call with both pointers given, uses stage_out, xbuf, work and dense_in
+    f2_score_outputs out;
+    F2_TRY(f2_place_scores(ctx, scores_or_null, labels_or_null, n_total, mem_space, false, true, 0, &out));
     // the tiled offsets start with the clean ones: one device array serves the noise kernels and the evaluation
     F2_TRY(f2_upload_offsets(ctx, tiled.data(), U));
     F2_TRY(f2_upload_async(ctx, d_lin, lin.data(), sizeof(double) * (size_t)K));
@@ -466,59 +437,22 @@ static int eval_noise_sweep_impl(f2_ctx* ctx, const f2_cnn* cnn, const void* wav
     F2_TRY(f2_stage_wave(ctx, wave, wave_dtype, total, mem_space, &d_wave));
     const int64_t* d_offsets = (const int64_t*)ctx->offsets.ptr;
     F2_TRY(f2_launch_noise_sigma(ctx, d_wave, wave_dtype, d_offsets, d_lin, B, K, d_sigma));
-    F2_TRY(f2_launch_noise_levels(ctx, d_wave, wave_dtype, d_offsets, d_sigma, B, K, total, seed, d_noisy));
-    if (E.host && noisy_or_null) F2_HIP(ctx, hipMemcpyAsync(noisy_or_null, d_noisy, noisy_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    F2_TRY(eval_strided_impl(ctx, cnn, d_noisy, F2_WAVE_F64, tiled.data(), coefs, U, C, lpf, cutoff_hz, fft_precision, radius, step, hop,
-                             d_scores, d_labels, nullptr, F2_MEM_DEVICE));
+    F2_TRY(f2_launch_noise_levels(ctx, d_wave, wave_dtype, d_offsets, d_sigma, B, K, total, seed, noisy.as<double>()));
+    F2_TRY(f2_copy_back(ctx, noisy));
+    F2_TRY(f2_eval_batch_strided(ctx, cnn, noisy.dev, F2_WAVE_F64, tiled.data(), coefs, U, C, lpf, cutoff_hz, fft_precision, radius, step,
+                                 hop, out.scores.as<float>(), out.labels.as<uint8_t>(), nullptr, F2_MEM_DEVICE));
     F2_HIP(ctx, hipMemsetAsync(d_stats, 0, sizeof(int64_t) * 2 * (size_t)U, ctx->stream));
     if (n_total > 0) {
         F2_TRY(f2_upload_async(ctx, d_wo, wo.data(), sizeof(int64_t) * ((size_t)U + 1)));
-        F2_TRY(f2_launch_label_tally(ctx, d_labels, d_wo, B, K, max_windows, d_stats));
-        if (E.host && scores_or_null)
-            F2_HIP(ctx, hipMemcpyAsync(scores_or_null, d_scores, sizeof(float) * 2 * (size_t)n_total, hipMemcpyDeviceToHost, ctx->stream));
-        if (E.host && labels_or_null)
-            F2_HIP(ctx, hipMemcpyAsync(labels_or_null, d_labels, (size_t)n_total, hipMemcpyDeviceToHost, ctx->stream));
+        F2_TRY(f2_launch_label_tally(ctx, out.labels.as<uint8_t>(), d_wo, B, K, max_windows, d_stats));
+        F2_TRY(f2_copy_back(ctx, out.scores));
+        F2_TRY(f2_copy_back(ctx, out.labels));
     }
     if (sigma_or_null) F2_HIP(ctx, hipMemcpyAsync(sigma_or_null, d_sigma, sizeof(double) * (size_t)U, hipMemcpyDeviceToHost, ctx->stream));
     if (stats_or_null)
         F2_HIP(ctx, hipMemcpyAsync(stats_or_null, d_stats, sizeof(int64_t) * 2 * (size_t)U, hipMemcpyDeviceToHost, ctx->stream));
     F2_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return F2_OK;
-}
-
-extern "C" {
-
-int f2_eval_utterance(f2_ctx* ctx, const f2_cnn* cnn, const void* wave, int wave_dtype, int64_t N, const double* coefs,
-                      int C, int lpf, double cutoff_hz, int fft_precision, int radius, int step, double* env_or_null,
-                      float* scores_or_null, uint8_t* labels_or_null, int64_t* n_windows_out, int mem_space) {
-    if (ctx && !wave) return f2_fail(ctx, F2_ERR_INVALID, "null wave");   // (also for N == 0, unlike f2_eval_batch)
-    const int64_t offsets[2] = {0, N};
-    return eval_batch_impl(ctx, cnn, wave, wave_dtype, offsets, coefs, 1, C, lpf, cutoff_hz, fft_precision, radius, step,
-                           env_or_null, scores_or_null, labels_or_null, n_windows_out, mem_space);
-}
-
-int f2_eval_batch(f2_ctx* ctx, const f2_cnn* cnn, const void* wave, int wave_dtype, const int64_t* offsets,
-                  const double* coefs, int B, int C, int lpf, double cutoff_hz, int fft_precision, int radius, int step,
-                  float* scores_or_null, uint8_t* labels_or_null, int mem_space) {
-    return eval_batch_impl(ctx, cnn, wave, wave_dtype, offsets, coefs, B, C, lpf, cutoff_hz, fft_precision, radius, step, nullptr,
-                           scores_or_null, labels_or_null, nullptr, mem_space);
-}
-
-int f2_eval_batch_strided(f2_ctx* ctx, const f2_cnn* cnn, const void* wave, int wave_dtype, const int64_t* offsets,
-                          const double* coefs, int B, int C, int lpf, double cutoff_hz, int fft_precision, int radius, int step,
-                          int hop, float* scores_or_null, uint8_t* labels_or_null, int64_t* window_offsets_or_null, int mem_space) {
-    return eval_strided_impl(ctx, cnn, wave, wave_dtype, offsets, coefs, B, C, lpf, cutoff_hz, fft_precision, radius, step, hop,
-                             scores_or_null, labels_or_null, window_offsets_or_null, mem_space);
-}
-
-int f2_eval_noise_sweep(f2_ctx* ctx, const f2_cnn* cnn, const void* wave, int wave_dtype, const int64_t* offsets,
-                        const double* coefs, int B, int C, int lpf, double cutoff_hz, int fft_precision, int radius, int step,
-                        int hop, const double* snr_db, int K, uint64_t seed, double* noisy_or_null, float* scores_or_null,
-                        uint8_t* labels_or_null, int64_t* window_offsets_or_null, double* sigma_or_null, int64_t* stats_or_null,
-                        int mem_space) {
-    return eval_noise_sweep_impl(ctx, cnn, wave, wave_dtype, offsets, coefs, B, C, lpf, cutoff_hz, fft_precision, radius, step, hop,
-                                 snr_db, K, seed, noisy_or_null, scores_or_null, labels_or_null, window_offsets_or_null,
-                                 sigma_or_null, stats_or_null, mem_space);
 }
 
 int f2_label_accuracy(f2_ctx* ctx, const uint8_t* labels, const int64_t* window_offsets, int U, const int64_t* ref_offsets,
@@ -551,26 +485,20 @@ int f2_label_accuracy(f2_ctx* ctx, const uint8_t* labels, const int64_t* window_
     std::fill(counts, counts + 4 * (size_t)U, (int64_t)0);
     if (n_rows == 0) return F2_OK;
 
-    // small arrays of the call: [counts (4 U) | window offsets (U + 1) | reference offsets (R + 1) | timepoints (M)] in 8-byte
-    // words, then the M signs
-    F2_TRY(f2_reserve(ctx, ctx->acc_meta, 8 * (4 * (size_t)U + U + 1 + R + 1 + (size_t)M) + (size_t)M));
-    int64_t* d_counts = (int64_t*)ctx->acc_meta.ptr;
-    int64_t* d_wo = d_counts + 4 * (size_t)U;
-    int64_t* d_ro = d_wo + U + 1;
-    int64_t* d_rt = d_ro + R + 1;
-    uint8_t* d_rs = (uint8_t*)(d_rt + M);
-    const uint8_t* d_labels = labels;
-    if (mem_space == F2_MEM_HOST) {
-        F2_TRY(f2_reserve(ctx, ctx->stage_in, (size_t)n_rows));
-        F2_HIP(ctx, hipMemcpyAsync(ctx->stage_in.ptr, labels, (size_t)n_rows, hipMemcpyHostToDevice, ctx->stream));
-        d_labels = (const uint8_t*)ctx->stage_in.ptr;
-    }
+    int64_t *d_counts, *d_wo, *d_ro, *d_rt;
+    uint8_t* d_rs;
+    f2_meta_carve meta;
+    meta.add(&d_counts, 4 * (size_t)U), meta.add(&d_wo, (size_t)U + 1), meta.add(&d_ro, (size_t)R + 1), meta.add(&d_rt, (size_t)M);
+    meta.add(&d_rs, (size_t)M);
+    F2_TRY(meta.reserve(ctx));
+    const void* d_labels;
+    F2_TRY(f2_stage_input(ctx, labels, (size_t)n_rows, mem_space, &d_labels));
     F2_HIP(ctx, hipMemsetAsync(d_counts, 0, sizeof(int64_t) * 4 * (size_t)U, ctx->stream));
     F2_TRY(f2_upload_async(ctx, d_wo, window_offsets, sizeof(int64_t) * ((size_t)U + 1)));
     F2_TRY(f2_upload_async(ctx, d_ro, ref_offsets, sizeof(int64_t) * ((size_t)R + 1)));
     F2_TRY(f2_upload_async(ctx, d_rt, ref_timepoints, sizeof(int64_t) * (size_t)M));
     F2_TRY(f2_upload_async(ctx, d_rs, ref_signs, (size_t)M));
-    F2_TRY(f2_launch_label_accuracy(ctx, d_labels, d_wo, U, d_ro, d_rt, d_rs, R, origin, hop, step, max_rows, d_counts));
+    F2_TRY(f2_launch_label_accuracy(ctx, (const uint8_t*)d_labels, d_wo, U, d_ro, d_rt, d_rs, R, origin, hop, step, max_rows, d_counts));
     F2_HIP(ctx, hipMemcpyAsync(counts, d_counts, sizeof(int64_t) * 4 * (size_t)U, hipMemcpyDeviceToHost, ctx->stream));
     F2_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return F2_OK;
@@ -595,33 +523,33 @@ int f2_cnn_score_windows(f2_ctx* ctx, const f2_cnn* cnn, const float* windows, i
     std::fill(loss_sum, loss_sum + (size_t)G, 0.0);
     if (n == 0) return F2_OK;
 
-    const bool host = mem_space == F2_MEM_HOST;
+    // host memory: windows, signs and groups go up chunk by chunk, and (normalize = 0) every chunk has its own range pass and route
+    const bool per_chunk = mem_space != F2_MEM_DEVICE;
     const size_t xs = (size_t)cnn->rows * cnn->channels;
     const int64_t chunk = n < CNN_CHUNK ? n : CNN_CHUNK;
-    // small arrays of the call: [counts (4 G) | loss (G) | loss partials of a chunk], all 8-byte words
-    F2_TRY(f2_reserve(ctx, ctx->score_meta, 8 * (5 * (size_t)G + f2_score_partial_doubles(chunk, G))));
-    int64_t* d_counts = (int64_t*)ctx->score_meta.ptr;
-    double* d_loss = (double*)(d_counts + 4 * (size_t)G);
-    double* d_partial = d_loss + G;
-    // per chunk in stage_aux: [scores (2 floats) | groups (int32) | labels | signs] for what the caller has not got on the device
-    const bool own_scores = host || !scores_or_null, own_labels = host || !labels_or_null;
-    F2_TRY(f2_reserve(ctx, ctx->stage_aux, (sizeof(float) * 2 + sizeof(int32_t) + 2) * (size_t)chunk + 64));
-    float* s_scores = (float*)ctx->stage_aux.ptr;
-    int32_t* s_groups = (int32_t*)(s_scores + 2 * chunk);
-    uint8_t* s_labels = (uint8_t*)(s_groups + chunk);
-    uint8_t* s_signs = s_labels + chunk;
-    if (host) F2_TRY(f2_reserve(ctx, ctx->stage_in, sizeof(float) * xs * (size_t)chunk));
+    // small arrays of the call: counts and loss (one memset clears both), the loss partials of a chunk
+    int64_t* d_counts;
+    double *d_loss, *d_partial;
+    f2_meta_carve meta;
+    meta.add(&d_counts, 4 * (size_t)G), meta.add(&d_loss, (size_t)G), meta.add(&d_partial, f2_score_partial_doubles(chunk, G));
+    F2_TRY(meta.reserve(ctx));
+    // per chunk in stage_aux: scores and labels the caller has not got on the device (the tally reads both), behind them the
+    // groups and signs of a host caller
+    f2_score_outputs out;
+    F2_TRY(f2_place_scores(ctx, scores_or_null, labels_or_null, chunk, mem_space, true, true, (sizeof(int32_t) + 1) * (size_t)chunk, &out));
+    int32_t* s_groups = (int32_t*)out.tail;
+    uint8_t* s_signs = (uint8_t*)(s_groups + chunk);
     if (normalize) F2_TRY(f2_reserve(ctx, ctx->xbuf, sizeof(float) * xs * (size_t)chunk));
 
     // normalised windows lie in [0, 1]: the B = 1 scale set without the range pass, as in f2_eval_*; windows as they are take
     // f2_cnn_forward's route - the range of the whole call for device memory, of each chunk for host memory, as there
     const f2_scale_set* S = nullptr;
     f2_cnn_route route;
-    double bound = host ? 0.0 : -1.0;   // normalize = 0: what f2_cnn_forward leaves in last_input_bound (host: largest B of the chunks)
+    double bound = per_chunk ? 0.0 : -1.0;   // normalize = 0: what f2_cnn_forward leaves in last_input_bound (host: largest B of the chunks)
     if (normalize) {
         F2_TRY(f2_cnn_scale_set(ctx, cnn, 0, &S));
         route = f2_cnn_call_route(ctx, cnn, S != nullptr);
-    } else if (!host) {
+    } else if (!per_chunk) {
         F2_TRY(forward_route(ctx, cnn, windows, n, &S, &route, &bound));
     }
 
@@ -630,40 +558,36 @@ int f2_cnn_score_windows(f2_ctx* ctx, const f2_cnn* cnn, const float* windows, i
     F2_TRY(reset_flag(ctx));
     for (int64_t s = 0; s < n; s += chunk) {
         const int64_t m = n - s < chunk ? n - s : chunk;
-        const float* d_w = windows + (size_t)s * xs;
+        // The windows (up to 92 MB a chunk) go up straight from the caller's memory, as in f2_cnn_forward: the pinned buffers
+        // of f2_upload_async would cost a host copy of every chunk first. The caller's memory is only read and outlives the
+        // copies (the call waits for the stream before it returns); stage_in / stage_aux are reused in stream order, behind the
+        // kernels of the chunk before, so the chunks need no wait of their own. Signs and groups: the pinned ring.
+        const void* d_w;
+        F2_TRY(f2_stage_input(ctx, windows + (size_t)s * xs, sizeof(float) * xs * (size_t)m, mem_space, &d_w));
         const uint8_t* d_signs = signs + s;
         const int32_t* d_groups = groups_or_null ? groups_or_null + s : nullptr;
-        if (host) {
-            // The windows (up to 92 MB a chunk) go up straight from the caller's memory, as in f2_cnn_forward: the pinned buffers
-            // of f2_upload_async would cost a host copy of every chunk first. The caller's memory is only read and outlives the
-            // copies (the call waits for the stream before it returns); stage_in / stage_aux are reused in stream order, behind the
-            // kernels of the chunk before, so the chunks need no wait of their own. Signs and groups: the pinned ring.
-            F2_HIP(ctx, hipMemcpyAsync(ctx->stage_in.ptr, d_w, sizeof(float) * xs * (size_t)m, hipMemcpyHostToDevice, ctx->stream));
+        if (per_chunk) {
             F2_TRY(f2_upload_async(ctx, s_signs, d_signs, (size_t)m));
             if (d_groups) {
                 F2_TRY(f2_upload_async(ctx, s_groups, d_groups, sizeof(int32_t) * (size_t)m));
                 d_groups = s_groups;
             }
-            d_w = (const float*)ctx->stage_in.ptr;
             d_signs = s_signs;
         }
         if (normalize) {
-            F2_TRY(f2_launch_normalize_windows(ctx, d_w, m, (int)xs, (float*)ctx->xbuf.ptr, (int*)ctx->flags.ptr));
-            d_w = (const float*)ctx->xbuf.ptr;
-        } else if (host) {
+            F2_TRY(f2_launch_normalize_windows(ctx, (const float*)d_w, m, (int)xs, (float*)ctx->xbuf.ptr, (int*)ctx->flags.ptr));
+            d_w = ctx->xbuf.ptr;
+        } else if (per_chunk) {
             double b = -1.0;
-            F2_TRY(forward_route(ctx, cnn, d_w, m, &S, &route, &b));
+            F2_TRY(forward_route(ctx, cnn, (const float*)d_w, m, &S, &route, &b));
             bound = chunks_bound(bound, b);
         }
-        float* d_scores = own_scores ? s_scores : scores_or_null + 2 * s;
-        uint8_t* d_labels = own_labels ? s_labels : labels_or_null + s;
-        F2_TRY(cnn_forward_device(ctx, cnn, S, route, d_w, m, d_scores, d_labels));
-        F2_TRY(f2_launch_score_tally(ctx, d_scores, d_labels, d_signs, d_groups, G, m, d_counts, d_partial, d_loss,
+        const f2_output sc = out.scores.chunk(sizeof(float) * 2 * (size_t)s, sizeof(float) * 2 * (size_t)m), lb = out.labels.chunk((size_t)s, (size_t)m);
+        F2_TRY(cnn_forward_device(ctx, cnn, S, route, (const float*)d_w, m, sc.as<float>(), lb.as<uint8_t>()));
+        F2_TRY(f2_launch_score_tally(ctx, sc.as<float>(), lb.as<uint8_t>(), d_signs, d_groups, G, m, d_counts, d_partial, d_loss,
                                      (int*)ctx->flags.ptr + SCORE_WORD));
-        if (host && scores_or_null)
-            F2_HIP(ctx, hipMemcpyAsync(scores_or_null + 2 * s, d_scores, sizeof(float) * 2 * (size_t)m, hipMemcpyDeviceToHost, ctx->stream));
-        if (host && labels_or_null)
-            F2_HIP(ctx, hipMemcpyAsync(labels_or_null + s, d_labels, (size_t)m, hipMemcpyDeviceToHost, ctx->stream));
+        F2_TRY(f2_copy_back(ctx, sc));
+        F2_TRY(f2_copy_back(ctx, lb));
     }
     if (!normalize) cnn->last_input_bound = bound;   // (normalize = 1 measures nothing and leaves it alone, as f2_eval_* do)
     F2_HIP(ctx, hipMemcpyAsync(counts, d_counts, sizeof(int64_t) * 4 * (size_t)G, hipMemcpyDeviceToHost, ctx->stream));
@@ -702,33 +626,23 @@ int f2_input_batch(f2_ctx* ctx, const void* wave, int wave_dtype, const int64_t*
             win_utt[(size_t)e] = b;
         }
     }
-    const int64_t total = offsets[B];
     const int R = 2 * radius + 1;
 
     // envelopes of the whole batch, by the routes of f2_filterbank_envelope_fused (gfb_or_null = NULL), into a scratch buffer
-    F2_TRY(f2_upload_offsets(ctx, offsets, B));
-    F2_TRY(f2_upload_coefs(ctx, coefs, C));
-    F2_TRY(f2_reserve(ctx, ctx->stage_out, sizeof(double) * (size_t)C * (size_t)total));
-    double* d_env = (double*)ctx->stage_out.ptr;
-    const void* d_wave;
-    F2_TRY(f2_stage_wave(ctx, wave, wave_dtype, total, mem_space, &d_wave));
-    F2_TRY(f2_envelopes_device(ctx, d_wave, wave_dtype, offsets, B, C, lpf, cutoff_hz, fft_precision, d_env, nullptr, true));
+    const f2_batch X = {wave, wave_dtype, offsets, coefs, B, C, lpf, cutoff_hz, fft_precision, mem_space};
+    double* d_env;
+    F2_TRY(f2_batch_envelopes(ctx, X, nullptr, nullptr, true, &d_env));
 
     // all windows of the batch in one gather launch: centres and the utterance of every window in one upload
     const int64_t* d_centers;
     const int* d_win_utt;
     F2_TRY(f2_upload_windows(ctx, centers, win_utt.data(), n_windows, &d_centers, &d_win_utt));
-    const size_t out_bytes = sizeof(float) * (size_t)n_windows * R * (size_t)C;
-    float* d_out = windows;
-    if (mem_space == F2_MEM_HOST) {
-        F2_TRY(f2_reserve(ctx, ctx->xbuf, out_bytes));
-        d_out = (float*)ctx->xbuf.ptr;
-    }
+    f2_output win;
+    F2_TRY(f2_place(ctx, ctx->xbuf, windows, sizeof(float) * (size_t)n_windows * R * (size_t)C, mem_space, true, &win));
     F2_TRY(reset_flag(ctx));
     F2_TRY(f2_launch_gather_ragged(ctx, d_env, C, (const int64_t*)ctx->offsets.ptr, d_centers, d_win_utt, n_windows, radius, step,
-                                   normalize, d_out, (int*)ctx->flags.ptr));
-    if (mem_space == F2_MEM_HOST) F2_HIP(ctx, hipMemcpyAsync(windows, d_out, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    return normalize || mem_space == F2_MEM_HOST ? finish_positive(ctx) : F2_OK;
+                                   normalize, win.as<float>(), (int*)ctx->flags.ptr));
+    return finish_windows(ctx, win, normalize);
 }
 
 }  // extern "C"
@@ -759,7 +673,6 @@ int picture_check(f2_ctx* ctx, const int64_t* offsets, int B, int C, const int64
 // ctx->work2. Waits for the stream.
 int picture_device(f2_ctx* ctx, const double* d_env, const int64_t* offsets, int B, int C, const int64_t* spans_or_null, int width,
                    int pool, double* pooled_or_null, uint8_t* levels_or_null, double* range_or_null, int mem_space) {
-    const bool host = mem_space == F2_MEM_HOST;
     const size_t pixels = (size_t)B * (size_t)C * (size_t)width;
     // small arrays of the call: [span records (4 B) | range words (2 B)], all 8-byte words, in one upload
     std::vector<int64_t> meta(6 * (size_t)B);
@@ -774,24 +687,19 @@ int picture_device(f2_ctx* ctx, const double* d_env, const int64_t* offsets, int
         blocks = std::max(blocks, f2_picture_pool_blocks(C, width, lg));
         memcpy(&meta[4 * (size_t)B + 2 * (size_t)b], &inf, sizeof(double));   // (the maximum's word stays 0)
     }
-    F2_TRY(f2_reserve(ctx, ctx->pic_meta, sizeof(int64_t) * meta.size()));
-    const int64_t* d_utt = (const int64_t*)ctx->pic_meta.ptr;
-    uint64_t* d_range = (uint64_t*)ctx->pic_meta.ptr + 4 * (size_t)B;
-    double* d_pooled = pooled_or_null;
-    if (host || !pooled_or_null) {
-        F2_TRY(f2_reserve(ctx, ctx->work, sizeof(double) * pixels));
-        d_pooled = (double*)ctx->work.ptr;
-    }
-    uint8_t* d_levels = levels_or_null;
-    if (host && levels_or_null) {
-        F2_TRY(f2_reserve(ctx, ctx->work2, pixels));
-        d_levels = (uint8_t*)ctx->work2.ptr;
-    }
-    F2_TRY(f2_upload_async(ctx, ctx->pic_meta.ptr, meta.data(), sizeof(int64_t) * meta.size()));
-    F2_TRY(f2_launch_picture_pool(ctx, d_env, (const int64_t*)ctx->offsets.ptr, d_utt, B, C, width, pool, blocks, d_pooled, d_range));
-    if (levels_or_null) F2_TRY(f2_launch_picture_levels(ctx, d_pooled, d_range, B, C, width, d_levels));
-    if (host && pooled_or_null) F2_HIP(ctx, hipMemcpyAsync(pooled_or_null, d_pooled, sizeof(double) * pixels, hipMemcpyDeviceToHost, ctx->stream));
-    if (host && levels_or_null) F2_HIP(ctx, hipMemcpyAsync(levels_or_null, d_levels, pixels, hipMemcpyDeviceToHost, ctx->stream));
+    int64_t* d_utt;
+    uint64_t* d_range;
+    f2_meta_carve carve;
+    carve.add(&d_utt, 4 * (size_t)B), carve.add(&d_range, 2 * (size_t)B);
+    F2_TRY(carve.reserve(ctx));
+    f2_output pooled, levels;   // (the levels are made from the pooled values: those are needed whoever asked)
+    F2_TRY(f2_place(ctx, ctx->work, pooled_or_null, sizeof(double) * pixels, mem_space, true, &pooled));
+    F2_TRY(f2_place(ctx, ctx->work2, levels_or_null, pixels, mem_space, false, &levels));
+    F2_TRY(f2_upload_async(ctx, d_utt, meta.data(), sizeof(int64_t) * meta.size()));
+    F2_TRY(f2_launch_picture_pool(ctx, d_env, (const int64_t*)ctx->offsets.ptr, d_utt, B, C, width, pool, blocks, pooled.as<double>(), d_range));
+    if (levels.dev) F2_TRY(f2_launch_picture_levels(ctx, pooled.as<double>(), d_range, B, C, width, levels.as<uint8_t>()));
+    F2_TRY(f2_copy_back(ctx, pooled));
+    F2_TRY(f2_copy_back(ctx, levels));
     std::vector<double> r(2 * (size_t)B);
     if (range_or_null) F2_HIP(ctx, hipMemcpyAsync(r.data(), d_range, sizeof(double) * r.size(), hipMemcpyDeviceToHost, ctx->stream));
     F2_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -816,14 +724,9 @@ int f2_envelope_picture(f2_ctx* ctx, const double* env, const int64_t* offsets, 
     F2_CHECK(ctx, env || total == 0, F2_ERR_INVALID, "null env");
     if (B == 0 || !(pooled_or_null || levels_or_null || range_or_null)) return F2_OK;
     F2_TRY(f2_upload_offsets(ctx, offsets, B));
-    const double* d_env = env;
-    if (mem_space == F2_MEM_HOST && total > 0) {
-        const size_t bytes = sizeof(double) * (size_t)C * (size_t)total;
-        F2_TRY(f2_reserve(ctx, ctx->stage_aux, bytes));
-        F2_HIP(ctx, hipMemcpyAsync(ctx->stage_aux.ptr, env, bytes, hipMemcpyHostToDevice, ctx->stream));
-        d_env = (const double*)ctx->stage_aux.ptr;
-    }
-    return picture_device(ctx, d_env, offsets, B, C, spans_or_null, width, pool, pooled_or_null, levels_or_null, range_or_null, mem_space);
+    const void* d_env;
+    F2_TRY(f2_stage_into(ctx, ctx->stage_aux, env, sizeof(double) * (size_t)C * (size_t)total, mem_space, &d_env));
+    return picture_device(ctx, (const double*)d_env, offsets, B, C, spans_or_null, width, pool, pooled_or_null, levels_or_null, range_or_null, mem_space);
 }
 
 int f2_gammatonegram_batch(f2_ctx* ctx, const void* wave, int wave_dtype, const int64_t* offsets, const double* coefs, int B, int C,
@@ -836,16 +739,10 @@ int f2_gammatonegram_batch(f2_ctx* ctx, const void* wave, int wave_dtype, const 
     F2_CHECK(ctx, (wave && coefs) || total == 0, F2_ERR_INVALID, "null wave or coefs");
     if (B == 0 || !(pooled_or_null || levels_or_null || range_or_null)) return F2_OK;
     // envelopes of the whole batch, by the routes of f2_filterbank_envelope_fused (gfb_or_null = NULL), into a scratch buffer
-    F2_TRY(f2_upload_offsets(ctx, offsets, B));
+    F2_TRY(f2_upload_offsets(ctx, offsets, B));   // (a batch without a sample still gets its pictures: picture_device reads them)
+    const f2_batch X = {wave, wave_dtype, offsets, coefs, B, C, lpf, cutoff_hz, fft_precision, mem_space};
     double* d_env = nullptr;
-    if (total > 0) {
-        F2_TRY(f2_upload_coefs(ctx, coefs, C));
-        F2_TRY(f2_reserve(ctx, ctx->stage_out, sizeof(double) * (size_t)C * (size_t)total));
-        d_env = (double*)ctx->stage_out.ptr;
-        const void* d_wave;
-        F2_TRY(f2_stage_wave(ctx, wave, wave_dtype, total, mem_space, &d_wave));
-        F2_TRY(f2_envelopes_device(ctx, d_wave, wave_dtype, offsets, B, C, lpf, cutoff_hz, fft_precision, d_env, nullptr, true));
-    }
+    if (total > 0) F2_TRY(f2_batch_envelopes(ctx, X, nullptr, nullptr, true, &d_env));
     return picture_device(ctx, d_env, offsets, B, C, spans_or_null, width, pool, pooled_or_null, levels_or_null, range_or_null, mem_space);
 }
 
@@ -942,28 +839,24 @@ int f2_resample_batch(f2_ctx* ctx, const void* audio, int pcm_format, int channe
     memcpy(out_offsets, oo.data(), sizeof(int64_t) * ((size_t)B + 1));
     if (B == 0 || total_out == 0) return F2_OK;
 
-    const bool host = mem_space == F2_MEM_HOST;
+    int64_t* d_meta;
+    f2_meta_carve carve;
+    carve.add(&d_meta, meta.size());
+    F2_TRY(carve.reserve(ctx));
     const void* d_audio;
     F2_TRY(f2_stage_input(ctx, audio, elem_bytes[pcm_format] * (size_t)channels * (size_t)total, mem_space, &d_audio));
-    double* d_out = out;
-    if (host) {
-        F2_TRY(f2_reserve(ctx, ctx->stage_out, sizeof(double) * (size_t)total_out));
-        d_out = (double*)ctx->stage_out.ptr;
-    }
+    f2_output res;
+    F2_TRY(f2_place(ctx, ctx->stage_out, out, sizeof(double) * (size_t)total_out, mem_space, true, &res));
     if (identity) {
-        F2_TRY(f2_launch_pcm_convert(ctx, d_audio, pcm_format, channels, channel, total, d_out));
+        F2_TRY(f2_launch_pcm_convert(ctx, d_audio, pcm_format, channels, channel, total, res.as<double>()));
     } else {
         F2_TRY(resample_table(ctx, up, down, taps, half_len, T));
-        F2_TRY(f2_reserve(ctx, ctx->rs_meta, sizeof(int64_t) * meta.size()));
-        F2_TRY(f2_upload_async(ctx, ctx->rs_meta.ptr, meta.data(), sizeof(int64_t) * meta.size()));
-        F2_TRY(f2_launch_resample(ctx, d_audio, pcm_format, channels, channel, (const int64_t*)ctx->rs_meta.ptr, B, first[B], up, down,
-                                  half_len, (int)T, (const double*)ctx->rs_tab.ptr, d_out));
+        F2_TRY(f2_upload_async(ctx, d_meta, meta.data(), sizeof(int64_t) * meta.size()));
+        F2_TRY(f2_launch_resample(ctx, d_audio, pcm_format, channels, channel, d_meta, B, first[B], up, down, half_len, (int)T,
+                                  (const double*)ctx->rs_tab.ptr, res.as<double>()));
     }
-    if (host) {
-        F2_HIP(ctx, hipMemcpyAsync(out, d_out, sizeof(double) * (size_t)total_out, hipMemcpyDeviceToHost, ctx->stream));
-        F2_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    }
-    return F2_OK;
+    F2_TRY(f2_copy_back(ctx, res));
+    return f2_host_wait(ctx, mem_space);
 }
 
 }  // extern "C"

@@ -1097,10 +1097,7 @@ static int spectral_tables(f2_ctx* ctx, const double* d_coefs, int C, int log2h,
         }
     if (ctx->spec_tabs.size() >= 6) {   // a handful of (table, length class) pairs at most; drop the oldest
         F2_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        for (f2_scratch* s : {&ctx->spec_tabs.front().hu, &ctx->spec_tabs.front().e, &ctx->spec_tabs.front().lgroup,
-                              &ctx->spec_tabs.front().e64})
-            if (s->ptr) (void)hipFree(s->ptr);
-        ctx->spec_tabs.erase(ctx->spec_tabs.begin());
+        ctx->spec_tabs.erase(ctx->spec_tabs.begin());   // (its tables free themselves)
     }
     f2_spec_tables t;
     t.log2h = log2h;

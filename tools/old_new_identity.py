@@ -11,7 +11,11 @@ Cases: f2_filterbank_envelope_fused, f2_eval_batch, f2_eval_utterance (one utter
 11 x 128, 11 x 67, 10 x 100 and 13 x 40 under the options float32 / per-tile split / ws convolutions / ws convolutions + ws dense1,
 host and device memory, inputs in [0, 1), the same x 2^10, one window x 1e4 among normalised ones (the quiet-window route) and one
 NaN, last_input_bound in the digest; one host call of 16 384 + 70 windows whose second chunk is x 2^6; f2_cnn_score_windows with
-normalize 0 / 1 and three groups; the create-time *_check_diff values."""
+normalize 0 / 1 and three groups; the create-time *_check_diff values. The later entry points on small shapes
+(profiles/r18_a_old_new_identity.txt; tests/test_gpu_output_placement.py: radius 5, step 160, utterances of 1761, 2500 and 1000
+samples, an 11 x 10 network, 8 channels for the pictures), host and device memory, every output in the digest:
+f2_eval_batch_strided at hop 1 and 160, f2_eval_noise_sweep with 2 levels and a fixed seed, f2_label_accuracy on its labels,
+f2_envelope_picture / f2_gammatonegram_batch with both pools, f2_resample_batch at 3 : 2 and at the identity."""
 import hashlib, json, os, sys
 import numpy as np
 
@@ -105,6 +109,58 @@ def cnn_cases(ctx, res):
         sc, lb, np.float64(ctx.cnn_info(m.handle(ctx), "last_input_bound")))
 
 
+def entry_cases(ctx, res):
+    from f2cnn_amd import _lib
+    from f2cnn_amd.gammatone import filters
+    from f2cnn_amd.model import F2CNNModel
+    from f2cnn_amd.resample import design_resampler
+    import f2cnn_oracle as orc
+    lens, CN, CP, W = [1761, 2500, 1000], 10, 8, 7
+    B = len(lens)
+    offs = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+    total = int(offs[-1])
+    wave = np.concatenate([orc.synth_utterance(900 + i, n) for i, n in enumerate(lens)])
+    coefs = {c: filters.make_erb_filters(16000, filters.centre_freqs(16000, c, 100)) for c in (CN, CP)}
+    h = F2CNNModel.glorot(7, R, CN, zero_bias=False).handle(ctx)
+    snr = np.array([20.0, 5.0])
+    U = (len(snr) + 1) * B
+
+    def both(name, inputs, outs, call):
+        """call(mem, *inputs, *outs) in host memory and with every array on the device; host results of the call join the digest"""
+        for mname, mem in (("host", _lib.MEM_HOST), ("device", _lib.MEM_DEVICE)):
+            o = [np.zeros(n, dt) for dt, n in outs]
+            extra = call(mem, *inputs, *o) if mem == _lib.MEM_HOST else on_device(ctx, list(inputs) + o, lambda *p: call(mem, *p))
+            res[f"{name}, {mname} memory"] = digest(*o, *[np.asarray(e) for e in extra])
+        return o
+
+    for hop in (1, 160):
+        n = sum(_lib.strided_window_count(x, RADIUS, STEP, hop) for x in lens)
+        both(f"f2_eval_batch_strided: hop {hop}", [wave], [(np.float32, 2 * n), (np.uint8, n)], lambda mem, w, sc, lb: (
+            ctx.eval_batch_strided(h, w, _lib.WAVE_I16, offs, coefs[CN], B, CN, True, 50.0, _lib.FFT_F32, RADIUS, STEP, hop, sc, lb, mem),))
+    n = (len(snr) + 1) * sum(_lib.strided_window_count(x, RADIUS, STEP, 160) for x in lens)
+    sweep = both("f2_eval_noise_sweep: 2 levels, seed 1234", [wave], [(np.float64, (len(snr) + 1) * total), (np.float32, 2 * n), (np.uint8, n)],
+                 lambda mem, w, ny, sc, lb: ctx.eval_noise_sweep(h, w, _lib.WAVE_I16, offs, coefs[CN], B, CN, True, 50.0, _lib.FFT_F32, RADIUS, STEP,
+                                                                  160, snr, 1234, ny, sc, lb, mem))
+    wo = np.zeros(U + 1, np.int64)
+    wo[1:] = np.cumsum([_lib.strided_window_count(x, RADIUS, STEP, 160) for x in lens] * (len(snr) + 1))
+    both("f2_label_accuracy: the sweep's labels against three reference sets", [sweep[2]], [], lambda mem, lb: (ctx.label_accuracy(
+        lb, wo, np.array([0, 1, 4, 5]), np.array([900, 850, 1200, 2000, 400]), np.array([1, 0, 1, 0, 1]), RADIUS * STEP, 160, STEP, mem),))
+    env = np.zeros(CP * total)
+    ctx.filterbank_envelope_fused(wave, _lib.WAVE_I16, offs, coefs[CP], B, CP, True, 50.0, _lib.FFT_F32, env, None, _lib.MEM_HOST)
+    pix = [(np.float64, B * CP * W), (np.uint8, B * CP * W)]
+    for pool in (0, 1):
+        both(f"f2_envelope_picture: width {W}, pool {pool}", [env], pix, lambda mem, e, po, lv: (
+            ctx.envelope_picture(e, offs, B, CP, None, W, pool, po, lv, mem),))
+        both(f"f2_gammatonegram_batch: width {W}, pool {pool}", [wave], pix, lambda mem, w, po, lv: (
+            ctx.gammatonegram_batch(w, _lib.WAVE_I16, offs, coefs[CP], B, CP, True, 50.0, _lib.FFT_F32, None, W, pool, po, lv, mem),))
+    audio = np.random.default_rng(8).integers(-20000, 20000, (300, 2)).astype(np.int16)
+    for up, down in ((3, 2), (1, 1)):
+        _, _, half_len, taps = design_resampler(down, up)
+        both(f"f2_resample_batch: {up} : {down}, int16 stereo, 300 frames", [audio], [(np.float64, _lib.resampled_length(300, up, down))],
+             lambda mem, a, out: (ctx.resample_batch(a, _lib.PCM_I16, 2, -1, np.array([0, 300]), 1, up, down, taps, half_len, out, mem),))
+    print("later entry points done", flush=True)
+
+
 def keep_arrays(keep, key, arrays, lens=None, C=None, envelopes=()):
     """the outputs of one case under KEEP_DIR: a<i>.npy each; `envelopes` = the indices of the arrays laid out
     [utterance][channel][sample] for utterances of `lens` samples and C channels"""
@@ -188,6 +244,7 @@ def run(lib, out, keep=None):
                 keep_arrays(keep, f"f2_input_batch: {tag}", [win])
             print(tag, "done", flush=True)
     cnn_cases(ctx, res)
+    entry_cases(ctx, res)
     ctx.close()
     with open(out, "w") as f:
         json.dump(res, f, indent=1)

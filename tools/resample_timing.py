@@ -8,6 +8,9 @@ Prints one JSON line; --out FILE also writes it. Diagnostic."""
 import argparse, json, multiprocessing, os, statistics, sys, time
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+if os.environ.get("F2CNN_PROBE_LIB"):   # another build of the library, as for cfg1_latency.py
+    from f2cnn_amd import build
+    build.LIB_PATH = os.path.abspath(os.environ["F2CNN_PROBE_LIB"])
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--utterances", type=int, default=256)
