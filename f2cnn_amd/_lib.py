@@ -71,6 +71,9 @@ SIGNATURES = {
     "f2_envelope_picture": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _i]),
     "f2_gammatonegram_batch": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i, _i, _d, _i, _vp, _i, _i, _vp, _vp, _vp, _i]),
     "f2_resample_batch": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _i64, _i64, _vp, _i64, _vp, _vp, _i]),
+    "f2_score_track": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _i64, _i, _i, _vp, _i]),
+    "f2_eval_figure_batch": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _d, _i, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp,
+                                  _vp, _i]),
 }
 
 _lib = None
@@ -480,6 +483,42 @@ class Context:
                                                    int(bool(lpf)), float(cutoff), precision, _ptr(spans), int(width), int(pool),
                                                    _ptr(pooled), _ptr(levels), _ptr(range_out), mem_space))
         return range_out.reshape(-1, 2)
+
+    def score_track(self, scores, labels, window_offsets, spans, origin, hop, width, track, mem_space):
+        """The decisions of a strided evaluation reduced to `width` time columns per utterance (see f2_score_track): utterance u
+        owns rows window_offsets[u] .. window_offsets[u + 1] of `scores` (n, 2) float32 / `labels` (n) uint8, row j at sample
+        origin + j * hop; spans (U, 2): the sample span [s_u, e_u) its columns divide. `track` (U, width, 5) float64 - rows,
+        rising rows, mean / min / max of scores[:, 1] per column. scores / labels / track: numpy arrays or device pointers, by
+        mem_space. Returns `track`."""
+        window_offsets = np.ascontiguousarray(window_offsets, dtype=np.int64)
+        U = len(window_offsets) - 1
+        spans = np.ascontiguousarray(spans, dtype=np.int64)
+        if spans.size != 2 * U:
+            raise ValueError("spans must hold (s_u, e_u) for each of the U utterances")
+        if isinstance(scores, np.ndarray):
+            scores = np.ascontiguousarray(scores, dtype=np.float32)
+        if isinstance(labels, np.ndarray):
+            labels = np.ascontiguousarray(labels, dtype=np.uint8)
+        if isinstance(track, np.ndarray) and (track.dtype != np.float64 or track.size != 5 * U * int(width)
+                                              or not track.flags["C_CONTIGUOUS"]):
+            raise ValueError("track must be contiguous float64 (U, width, 5)")
+        self.check(self.lib.f2_score_track(self.handle, _ptr(scores), _ptr(labels), _ptr(window_offsets), U, _ptr(spans), int(origin),
+                                           int(hop), int(width), _ptr(track), mem_space))
+        return track
+
+    def eval_figure_batch(self, handle, wave, wave_dtype, offsets, coefs, B, Cn, lpf, cutoff, precision, radius, step, hop, spans,
+                          width, pool, levels, track, scores, labels, mem_space, range_out=None):
+        """eval_batch_strided, the picture of the envelopes it uses and the track of its decisions in one device pass (see
+        f2_eval_figure_batch). levels (B, Cn, width) uint8, track (B, width, 5) float64, scores, labels: numpy arrays or device
+        pointers, by mem_space, any may be None; spans as in envelope_picture. Returns (window_offsets (B + 1, int64), range
+        (B, 2) float64)."""
+        offsets, spans, range_out = self._picture_args(offsets, B, spans, range_out)
+        window_offsets = np.zeros(max(int(B), 0) + 1, np.int64)
+        self.check(self.lib.f2_eval_figure_batch(self.handle, handle, _ptr(wave), wave_dtype, _ptr(offsets), _ptr(coefs), int(B), Cn,
+                                                 int(bool(lpf)), float(cutoff), precision, radius, step, int(hop), _ptr(spans),
+                                                 int(width), int(pool), _ptr(levels), _ptr(range_out), _ptr(track), _ptr(scores),
+                                                 _ptr(labels), _ptr(window_offsets), mem_space))
+        return window_offsets, range_out.reshape(-1, 2)
 
     def resample_batch(self, audio, pcm_format, channels, channel, offsets, B, up, down, taps, half_len, out, mem_space):
         """Ragged batch of interleaved PCM frames (offsets in frames) -> mono float64 samples in int16 units at up / down times

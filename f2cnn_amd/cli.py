@@ -33,6 +33,11 @@ package implements:
      the channels of a stereo file averaged - with scipy.signal.resample_poly's filter; STEP and `--hop frame` are then those of
      FRAMERATE, and the .npz files also hold framerate and source_framerate. Without it a file is evaluated at its own rate, as
      the reference does; not in the reference)
+    (eval / evalnoise / evalrand also take --figure [--figure-width W]: the figure the reference's EvaluateOneWavArray ends in -
+     the gammatonegram with the formant track and a rising / falling tick per decision, below it the network's probability of
+     "rising" beside arctan of the formant's slope, its p-value and the phoneme boundaries - as
+     graphs/FallingOrRising/<basename>.png, W (default 1600) columns wide, without matplotlib; decisions and picture come from
+     one device pass and the .npz also holds figure_track and figure_span)
     python -m f2cnn_amd plot gtg [--file/-f WAV | --all] [--width W] [--pool mean|max] [--cutoff HZ] [--formant N] [--start S --end E] [--out PNG]
                                                             (gammatonegram pictures, pooled to W columns and log-normalised on the
                                                              device, written as graphs/gtg/<basename>.png without matplotlib; the
@@ -124,6 +129,11 @@ def build_parser():
     c.add_argument('--resample', action='store_true', default=argparse.SUPPRESS, dest='resample',
                    help="eval / evalnoise / evalrand / noisesweep: bring every file to FRAMERATE of configF2CNN.conf and to one "
                         "channel on the device first (any rate; 8 / 16 / 24 / 32-bit and float RIFF files; stereo is averaged)")
+    c.add_argument('--figure', action='store_true', default=argparse.SUPPRESS, dest='figure',
+                   help="eval / evalnoise / evalrand: also write graphs/FallingOrRising/<basename>.png, the decisions over the "
+                        "gammatonegram and the probability of 'rising' over time")
+    c.add_argument('--figure-width', action='store', type=int, default=argparse.SUPPRESS, dest='figure_width',
+                   help="--figure: columns of the picture (default 1600)")
     g = sub.add_parser('plot', help='plotting commands')
     g.add_argument('plot_command', choices=PLOT)
     which = g.add_mutually_exclusive_group()
@@ -223,6 +233,13 @@ def main(argv=None):
             kwargs['accuracy'] = args.accuracy
         if getattr(args, 'resample', False):
             kwargs['resample'] = True
+        if getattr(args, 'figure', False):
+            if args.cnn_command == 'noisesweep':
+                print("--figure is not supported by noisesweep (use evalnoise --figure for one level)")
+                return 1
+            kwargs['figure'] = True
+            if getattr(args, 'figure_width', None) is not None:
+                kwargs['figure_width'] = args.figure_width
         if args.cnn_command == 'evalrand':                     # needs no --file (unreachable in the reference CLI)
             if args.count is not None:
                 kwargs['count'] = args.count

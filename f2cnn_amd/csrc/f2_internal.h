@@ -517,6 +517,13 @@ int64_t f2_picture_pool_blocks(int C, int width, int lg);
 int f2_launch_picture_pool(f2_ctx* ctx, const double* d_env, const int64_t* d_offsets, const int64_t* d_utt, int B, int C, int width,
                            int pool, int64_t blocks_per_utt, double* d_pooled, uint64_t* d_range);
 int f2_launch_picture_levels(f2_ctx* ctx, const double* d_pooled, const uint64_t* d_range, int B, int C, int width, uint8_t* d_levels);
+// f2_track.hip, the kernel of f2_score_track / f2_eval_figure_batch. d_rec: 5 int64 per utterance {first row, rows, s_u, m_u, lg_u},
+// lg_u = f2_track_lanes_log2(m_u, width, hop) the log2 of the lanes per column; utterance u needs f2_track_blocks(width, lg_u)
+// workgroups and every utterance gets blocks_per_utt, the largest of them. d_track: (U, width, 5) float64.
+int f2_track_lanes_log2(int64_t m, int width, int hop);
+int64_t f2_track_blocks(int width, int lg);
+int f2_launch_score_track(f2_ctx* ctx, const float* d_scores, const uint8_t* d_labels, const int64_t* d_rec, int U, int64_t origin,
+                          int hop, int width, int64_t blocks_per_utt, double* d_track);
 // f2_resample.hip, the kernels of f2_resample_batch. F2_RESAMPLE_BLOCK outputs per workgroup, which stages at most
 // F2_RESAMPLE_SPAN_MAX input frames (f2_resample_span: what (up, down, T) need, T = taps per phase).
 // d_meta: 4 int64 per utterance {first input frame, frames, first output sample, output samples}, then B + 1 running sums of the

@@ -208,9 +208,10 @@ int eval_envelopes(f2_ctx* ctx, eval_call* E, const f2_batch& X, double* env_or_
 // Buffers of the window loop: xbuf and the convolution workspace for `chunk` windows, conv4 / dense1 outputs of a dense group
 // (the dense layers run over the conv4 outputs of up to DENSE_GROUP windows at once: dense1's grid of 64-window workgroups then
 // fills whole rounds of the device - launched per 14 240-window utterance its second round was one third full), scores and
-// labels of all n_total windows (staged for host calls); nothing leaves HBM. Clears the error flag.
+// labels of all n_total windows (staged for host calls); nothing leaves HBM. Clears the error flag. on_device: a kernel of the
+// call reads scores and labels (they get scratch when the caller gave no device buffer); tail_bytes: E->out.tail for the caller.
 int eval_cnn_begin(f2_ctx* ctx, const f2_cnn* cnn, eval_call* E, int64_t chunk, int64_t n_total, int C, float* scores_or_null,
-                   uint8_t* labels_or_null, int mem_space) {
+                   uint8_t* labels_or_null, int mem_space, bool on_device = false, size_t tail_bytes = 0) {
     E->group_cap = n_total < DENSE_GROUP ? n_total : DENSE_GROUP;
     const size_t conv_floats = f2_cnn_workspace_floats(cnn) - f2_cnn_dense_floats(cnn);
     E->flat = f2_cnn_flat_floats(cnn);
@@ -219,7 +220,7 @@ int eval_cnn_begin(f2_ctx* ctx, const f2_cnn* cnn, eval_call* E, int64_t chunk, 
     F2_TRY(f2_reserve(ctx, ctx->dense_in, sizeof(float) * f2_cnn_dense_floats(cnn) * (size_t)E->group_cap));
     E->d_a4 = (float*)ctx->dense_in.ptr;
     E->d_a5 = E->d_a4 + E->flat * (size_t)E->group_cap;
-    F2_TRY(f2_place_scores(ctx, scores_or_null, labels_or_null, n_total, mem_space, false, false, 0, &E->out));
+    F2_TRY(f2_place_scores(ctx, scores_or_null, labels_or_null, n_total, mem_space, on_device, on_device, tail_bytes, &E->out));
     F2_TRY(f2_cnn_scale_set(ctx, cnn, 0, &E->S1));   // K3's normalised windows lie in [0, 1] by construction: no range pass
     E->route = f2_cnn_call_route(ctx, cnn, E->S1 != nullptr);
     E->g0 = E->gn = 0;
@@ -303,59 +304,25 @@ static int64_t strided_windows(int64_t n, int R, int step, int hop) {
     return nb > 0 ? (nb + hop - 1) / hop : 0;
 }
 
-extern "C" {
-
-int f2_eval_utterance(f2_ctx* ctx, const f2_cnn* cnn, const void* wave, int wave_dtype, int64_t N, const double* coefs,
-                      int C, int lpf, double cutoff_hz, int fft_precision, int radius, int step, double* env_or_null,
-                      float* scores_or_null, uint8_t* labels_or_null, int64_t* n_windows_out, int mem_space) {
-    if (ctx && !wave) return f2_fail(ctx, F2_ERR_INVALID, "null wave");   // (also for N == 0, unlike f2_eval_batch)
-    const int64_t offsets[2] = {0, N};
-    const f2_batch X = {wave, wave_dtype, offsets, coefs, 1, C, lpf, cutoff_hz, fft_precision, mem_space};
-    return eval_batch_impl(ctx, cnn, X, radius, step, env_or_null, scores_or_null, labels_or_null, n_windows_out);
-}
-
-int f2_eval_batch(f2_ctx* ctx, const f2_cnn* cnn, const void* wave, int wave_dtype, const int64_t* offsets,
-                  const double* coefs, int B, int C, int lpf, double cutoff_hz, int fft_precision, int radius, int step,
-                  float* scores_or_null, uint8_t* labels_or_null, int mem_space) {
-    const f2_batch X = {wave, wave_dtype, offsets, coefs, B, C, lpf, cutoff_hz, fft_precision, mem_space};
-    return eval_batch_impl(ctx, cnn, X, radius, step, nullptr, scores_or_null, labels_or_null, nullptr);
-}
-
-// f2_eval_batch_strided: window j of utterance b is every-sample window j * hop. A chunk is up to CNN_CHUNK windows taken from
-// as many utterances as it holds (an utterance may continue in the next chunk): one window-stage launch set and one
-// convolution launch set per chunk, whatever B. (On the decimating route a chunk also closes at COLUMN_CAP columns of the
-// window stage's scratch - 2 * radius * step / hop columns per segment on top of its windows: 150 MB for 128 channels - which
-// only batches of very many very short utterances at a small hop reach.)
-int f2_eval_batch_strided(f2_ctx* ctx, const f2_cnn* cnn, const void* wave, int wave_dtype, const int64_t* offsets,
-                          const double* coefs, int B, int C, int lpf, double cutoff_hz, int fft_precision, int radius, int step,
-                          int hop, float* scores_or_null, uint8_t* labels_or_null, int64_t* window_offsets_or_null, int mem_space) {
+// The window loop of f2_eval_batch_strided (and f2_eval_figure_batch) between eval_cnn_begin and eval_cnn_end: utterance b has
+// nbh[b] windows. A chunk is up to `chunk` windows taken from as many utterances as it holds (an utterance may continue in the next
+// chunk): one window-stage launch set and one convolution launch set per chunk, whatever B. (On the decimating route a chunk also
+// closes at COLUMN_CAP columns of the window stage's scratch - 2 * radius * step / hop columns per segment on top of its windows:
+// 150 MB for 128 channels - which only batches of very many very short utterances at a small hop reach.)
+static int strided_window_loop(f2_ctx* ctx, const f2_cnn* cnn, eval_call* E, const f2_batch& X, const std::vector<int64_t>& nbh,
+                               int64_t chunk, int radius, int step, int hop) {
     constexpr int64_t COLUMN_CAP = 8 * CNN_CHUNK;
-    const f2_batch X = {wave, wave_dtype, offsets, coefs, B, C, lpf, cutoff_hz, fft_precision, mem_space};
-    eval_call E;
-    F2_TRY(eval_check(ctx, cnn, X, radius, step, &E));
-    F2_CHECK(ctx, hop >= 1, F2_ERR_INVALID, "hop must be at least 1 sample (got %d)", hop);
-    std::vector<int64_t> nbh((size_t)B);
-    int64_t n_total = 0;
-    if (window_offsets_or_null) window_offsets_or_null[0] = 0;
-    for (int b = 0; b < B; ++b) {
-        nbh[(size_t)b] = strided_windows(offsets[b + 1] - offsets[b], E.R, step, hop);
-        n_total += nbh[(size_t)b];
-        if (window_offsets_or_null) window_offsets_or_null[b + 1] = n_total;
-    }
-    if (X.total() == 0) return F2_OK;
-    F2_TRY(eval_envelopes(ctx, &E, X, nullptr, n_total));
-    if (n_total == 0) return F2_OK;
-    const int64_t chunk = n_total < CNN_CHUNK ? n_total : CNN_CHUNK;
-    F2_TRY(eval_cnn_begin(ctx, cnn, &E, chunk, n_total, C, scores_or_null, labels_or_null, mem_space));
+    const int64_t* offsets = X.offsets;
+    const int B = X.B, C = X.C;
     const bool columns = f2_gather_strided_blocked(ctx, C, step, hop);
     std::vector<f2_win_seg> segs;
     int64_t m = 0, cols = 0;     // windows and scratch columns of the open chunk
     auto close_chunk = [&]() -> int {
         if (m > 0) {
-            F2_TRY(eval_chunk_room(ctx, cnn, &E, m));
-            F2_TRY(f2_launch_gather_strided(ctx, E.d_env, C, (const int64_t*)ctx->offsets.ptr, offsets, segs.data(), (int)segs.size(),
+            F2_TRY(eval_chunk_room(ctx, cnn, E, m));
+            F2_TRY(f2_launch_gather_strided(ctx, E->d_env, C, (const int64_t*)ctx->offsets.ptr, offsets, segs.data(), (int)segs.size(),
                                             radius, step, hop, (float*)ctx->xbuf.ptr, (int*)ctx->flags.ptr));
-            F2_TRY(eval_chunk_convs(ctx, cnn, &E, m));
+            F2_TRY(eval_chunk_convs(ctx, cnn, E, m));
         }
         segs.clear();
         m = cols = 0;
@@ -375,7 +342,50 @@ int f2_eval_batch_strided(f2_ctx* ctx, const f2_cnn* cnn, const void* wave, int 
             cols += c;
             if (m == chunk) F2_TRY(close_chunk());
         }
-    F2_TRY(close_chunk());
+    return close_chunk();
+}
+
+extern "C" {
+
+int f2_eval_utterance(f2_ctx* ctx, const f2_cnn* cnn, const void* wave, int wave_dtype, int64_t N, const double* coefs,
+                      int C, int lpf, double cutoff_hz, int fft_precision, int radius, int step, double* env_or_null,
+                      float* scores_or_null, uint8_t* labels_or_null, int64_t* n_windows_out, int mem_space) {
+    if (ctx && !wave) return f2_fail(ctx, F2_ERR_INVALID, "null wave");   // (also for N == 0, unlike f2_eval_batch)
+    const int64_t offsets[2] = {0, N};
+    const f2_batch X = {wave, wave_dtype, offsets, coefs, 1, C, lpf, cutoff_hz, fft_precision, mem_space};
+    return eval_batch_impl(ctx, cnn, X, radius, step, env_or_null, scores_or_null, labels_or_null, n_windows_out);
+}
+
+int f2_eval_batch(f2_ctx* ctx, const f2_cnn* cnn, const void* wave, int wave_dtype, const int64_t* offsets,
+                  const double* coefs, int B, int C, int lpf, double cutoff_hz, int fft_precision, int radius, int step,
+                  float* scores_or_null, uint8_t* labels_or_null, int mem_space) {
+    const f2_batch X = {wave, wave_dtype, offsets, coefs, B, C, lpf, cutoff_hz, fft_precision, mem_space};
+    return eval_batch_impl(ctx, cnn, X, radius, step, nullptr, scores_or_null, labels_or_null, nullptr);
+}
+
+// f2_eval_batch_strided: window j of utterance b is every-sample window j * hop, in chunks of up to CNN_CHUNK windows
+// (strided_window_loop).
+int f2_eval_batch_strided(f2_ctx* ctx, const f2_cnn* cnn, const void* wave, int wave_dtype, const int64_t* offsets,
+                          const double* coefs, int B, int C, int lpf, double cutoff_hz, int fft_precision, int radius, int step,
+                          int hop, float* scores_or_null, uint8_t* labels_or_null, int64_t* window_offsets_or_null, int mem_space) {
+    const f2_batch X = {wave, wave_dtype, offsets, coefs, B, C, lpf, cutoff_hz, fft_precision, mem_space};
+    eval_call E;
+    F2_TRY(eval_check(ctx, cnn, X, radius, step, &E));
+    F2_CHECK(ctx, hop >= 1, F2_ERR_INVALID, "hop must be at least 1 sample (got %d)", hop);
+    std::vector<int64_t> nbh((size_t)B);
+    int64_t n_total = 0;
+    if (window_offsets_or_null) window_offsets_or_null[0] = 0;
+    for (int b = 0; b < B; ++b) {
+        nbh[(size_t)b] = strided_windows(offsets[b + 1] - offsets[b], E.R, step, hop);
+        n_total += nbh[(size_t)b];
+        if (window_offsets_or_null) window_offsets_or_null[b + 1] = n_total;
+    }
+    if (X.total() == 0) return F2_OK;
+    F2_TRY(eval_envelopes(ctx, &E, X, nullptr, n_total));
+    if (n_total == 0) return F2_OK;
+    const int64_t chunk = n_total < CNN_CHUNK ? n_total : CNN_CHUNK;
+    F2_TRY(eval_cnn_begin(ctx, cnn, &E, chunk, n_total, C, scores_or_null, labels_or_null, mem_space));
+    F2_TRY(strided_window_loop(ctx, cnn, &E, X, nbh, chunk, radius, step, hop));
     return eval_cnn_end(ctx, cnn, &E);
 }
 
@@ -668,13 +678,20 @@ int picture_check(f2_ctx* ctx, const int64_t* offsets, int B, int C, const int64
     return F2_OK;
 }
 
-// Pool, levels and range of the envelopes at d_env (device; offsets already uploaded), results to the caller's buffers in mem_space.
-// Pictures a host caller asked for, and the pooled values the levels are made from when nobody asked for them, live in ctx->work /
-// ctx->work2. Waits for the stream.
-int picture_device(f2_ctx* ctx, const double* d_env, const int64_t* offsets, int B, int C, const int64_t* spans_or_null, int width,
-                   int pool, double* pooled_or_null, uint8_t* levels_or_null, double* range_or_null, int mem_space) {
+// The small arrays of a picture call: [span records (4 B) | range words (2 B)], all 8-byte words, in one upload
+struct picture_meta {
+    int64_t* d_utt = nullptr;
+    uint64_t* d_range = nullptr;
+    std::vector<double> range;   // the range words as they come back (picture_range reads them after the wait)
+    void add(f2_meta_carve* carve, int B) { carve->add(&d_utt, 4 * (size_t)B), carve->add(&d_range, 2 * (size_t)B); }
+};
+
+// Pool, levels and range of the envelopes at d_env (device; offsets already uploaded; P carved), results to the caller's buffers in
+// mem_space. Pictures a host caller asked for, and the pooled values the levels are made from when nobody asked for them, live in
+// ctx->work / ctx->work2. Enqueues everything, the copies to the caller included, and does not wait.
+int picture_enqueue(f2_ctx* ctx, const double* d_env, const int64_t* offsets, int B, int C, const int64_t* spans_or_null, int width,
+                    int pool, picture_meta* P, double* pooled_or_null, uint8_t* levels_or_null, bool want_range, int mem_space) {
     const size_t pixels = (size_t)B * (size_t)C * (size_t)width;
-    // small arrays of the call: [span records (4 B) | range words (2 B)], all 8-byte words, in one upload
     std::vector<int64_t> meta(6 * (size_t)B);
     int64_t blocks = 0;   // per utterance: what the one with the shortest bins needs
     const double inf = INFINITY;
@@ -687,28 +704,41 @@ int picture_device(f2_ctx* ctx, const double* d_env, const int64_t* offsets, int
         blocks = std::max(blocks, f2_picture_pool_blocks(C, width, lg));
         memcpy(&meta[4 * (size_t)B + 2 * (size_t)b], &inf, sizeof(double));   // (the maximum's word stays 0)
     }
-    int64_t* d_utt;
-    uint64_t* d_range;
-    f2_meta_carve carve;
-    carve.add(&d_utt, 4 * (size_t)B), carve.add(&d_range, 2 * (size_t)B);
-    F2_TRY(carve.reserve(ctx));
     f2_output pooled, levels;   // (the levels are made from the pooled values: those are needed whoever asked)
     F2_TRY(f2_place(ctx, ctx->work, pooled_or_null, sizeof(double) * pixels, mem_space, true, &pooled));
     F2_TRY(f2_place(ctx, ctx->work2, levels_or_null, pixels, mem_space, false, &levels));
-    F2_TRY(f2_upload_async(ctx, d_utt, meta.data(), sizeof(int64_t) * meta.size()));
-    F2_TRY(f2_launch_picture_pool(ctx, d_env, (const int64_t*)ctx->offsets.ptr, d_utt, B, C, width, pool, blocks, pooled.as<double>(), d_range));
-    if (levels.dev) F2_TRY(f2_launch_picture_levels(ctx, pooled.as<double>(), d_range, B, C, width, levels.as<uint8_t>()));
+    F2_TRY(f2_upload_async(ctx, P->d_utt, meta.data(), sizeof(int64_t) * meta.size()));
+    F2_TRY(f2_launch_picture_pool(ctx, d_env, (const int64_t*)ctx->offsets.ptr, P->d_utt, B, C, width, pool, blocks, pooled.as<double>(), P->d_range));
+    if (levels.dev) F2_TRY(f2_launch_picture_levels(ctx, pooled.as<double>(), P->d_range, B, C, width, levels.as<uint8_t>()));
     F2_TRY(f2_copy_back(ctx, pooled));
     F2_TRY(f2_copy_back(ctx, levels));
-    std::vector<double> r(2 * (size_t)B);
-    if (range_or_null) F2_HIP(ctx, hipMemcpyAsync(r.data(), d_range, sizeof(double) * r.size(), hipMemcpyDeviceToHost, ctx->stream));
-    F2_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    P->range.assign(want_range ? 2 * (size_t)B : 0, 0.0);
+    if (want_range)
+        F2_HIP(ctx, hipMemcpyAsync(P->range.data(), P->d_range, sizeof(double) * P->range.size(), hipMemcpyDeviceToHost, ctx->stream));
+    return F2_OK;
+}
+
+// after the wait for the stream: the range words of picture_enqueue as the caller gets them
+void picture_range(const picture_meta& P, int B, double* range_or_null) {
     if (range_or_null)
         for (int b = 0; b < B; ++b) {   // no pixel > 0: the maximum's word is still 0, the minimum's still +inf
-            const bool any = r[2 * (size_t)b + 1] > 0.0;
-            range_or_null[2 * b] = any ? r[2 * (size_t)b] : 0.0;
-            range_or_null[2 * b + 1] = any ? r[2 * (size_t)b + 1] : 0.0;
+            const bool any = P.range[2 * (size_t)b + 1] > 0.0;
+            range_or_null[2 * b] = any ? P.range[2 * (size_t)b] : 0.0;
+            range_or_null[2 * b + 1] = any ? P.range[2 * (size_t)b + 1] : 0.0;
         }
+}
+
+// both, for a call that makes pictures only. Waits for the stream.
+int picture_device(f2_ctx* ctx, const double* d_env, const int64_t* offsets, int B, int C, const int64_t* spans_or_null, int width,
+                   int pool, double* pooled_or_null, uint8_t* levels_or_null, double* range_or_null, int mem_space) {
+    picture_meta P;
+    f2_meta_carve carve;
+    P.add(&carve, B);
+    F2_TRY(carve.reserve(ctx));
+    F2_TRY(picture_enqueue(ctx, d_env, offsets, B, C, spans_or_null, width, pool, &P, pooled_or_null, levels_or_null, range_or_null != nullptr,
+                           mem_space));
+    F2_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    picture_range(P, B, range_or_null);
     return F2_OK;
 }
 
@@ -744,6 +774,137 @@ int f2_gammatonegram_batch(f2_ctx* ctx, const void* wave, int wave_dtype, const 
     double* d_env = nullptr;
     if (total > 0) F2_TRY(f2_batch_envelopes(ctx, X, nullptr, nullptr, true, &d_env));
     return picture_device(ctx, d_env, offsets, B, C, spans_or_null, width, pool, pooled_or_null, levels_or_null, range_or_null, mem_space);
+}
+
+}  // extern "C"
+
+// ---- `cnn eval --figure`: f2_score_track, and f2_eval_figure_batch = strided evaluation + picture + track over one set of envelopes ----
+namespace {
+
+// the records of k_score_track (f2_internal.h) for U utterances with the spans given; returns the workgroups every utterance gets
+int64_t track_records(const int64_t* window_offsets, int U, const int64_t* spans, int hop, int width, std::vector<int64_t>* rec) {
+    rec->resize(5 * (size_t)U);
+    int64_t blocks = 0;
+    for (int u = 0; u < U; ++u) {
+        const int64_t s = spans[2 * u], m = spans[2 * u + 1] - s;
+        const int lg = f2_track_lanes_log2(m, width, hop);
+        int64_t* r = &(*rec)[5 * (size_t)u];
+        r[0] = window_offsets[u], r[1] = window_offsets[u + 1] - window_offsets[u], r[2] = s, r[3] = m, r[4] = lg;
+        blocks = std::max(blocks, f2_track_blocks(width, lg));
+    }
+    return blocks;
+}
+
+}  // namespace
+
+extern "C" {
+
+int f2_score_track(f2_ctx* ctx, const float* scores, const uint8_t* labels, const int64_t* window_offsets, int U, const int64_t* spans,
+                   int64_t origin, int hop, int width, double* track, int mem_space) {
+    F2_TRY(f2_check_ctx(ctx));
+    F2_TRY(f2_check_mem_space(ctx, mem_space, false));
+    F2_CHECK(ctx, U >= 0 && hop >= 1 && origin >= 0 && width >= 1, F2_ERR_INVALID,
+             "U (%d) and origin (%lld) must be at least 0, hop (%d) and width (%d) at least 1", U, (long long)origin, hop, width);
+    F2_TRY(f2_check_offsets(ctx, window_offsets, U, "window_offsets"));
+    F2_CHECK(ctx, spans, F2_ERR_INVALID, "spans is NULL");
+    const int64_t n_rows = window_offsets[U];
+    F2_CHECK(ctx, (scores && labels) || n_rows == 0, F2_ERR_INVALID, "null scores or labels");
+    F2_CHECK(ctx, track || U == 0, F2_ERR_INVALID, "track is NULL");
+    int64_t max_rows = 0;
+    for (int u = 0; u < U; ++u) {
+        F2_CHECK(ctx, spans[2 * u] >= 0 && spans[2 * u + 1] >= spans[2 * u], F2_ERR_INVALID, "utterance %d: [%lld, %lld) is not a span", u,
+                 (long long)spans[2 * u], (long long)spans[2 * u + 1]);
+        max_rows = std::max(max_rows, window_offsets[u + 1] - window_offsets[u]);
+    }
+    F2_CHECK(ctx, width <= PICTURE_MAX_WIDTH, F2_ERR_UNSUPPORTED, "width %d (at most %d columns)", width, PICTURE_MAX_WIDTH);
+    int64_t t_last = 0;   // the sample of the last row of the longest utterance has to be an int64
+    F2_CHECK(ctx, max_rows == 0 || (!__builtin_mul_overflow(max_rows - 1, (int64_t)hop, &t_last) && !__builtin_add_overflow(t_last, origin, &t_last)),
+             F2_ERR_UNSUPPORTED, "row %lld at hop %d from origin %lld is beyond int64", (long long)(max_rows - 1), hop, (long long)origin);
+    if (U == 0) return F2_OK;
+
+    std::vector<int64_t> rec;
+    const int64_t blocks = track_records(window_offsets, U, spans, hop, width, &rec);
+    int64_t* d_rec;
+    f2_meta_carve meta;
+    meta.add(&d_rec, rec.size());
+    F2_TRY(meta.reserve(ctx));
+    const void *d_scores, *d_labels;
+    F2_TRY(f2_stage_input(ctx, scores, sizeof(float) * 2 * (size_t)n_rows, mem_space, &d_scores));
+    F2_TRY(f2_stage_into(ctx, ctx->stage_aux, labels, (size_t)n_rows, mem_space, &d_labels));
+    f2_output out;
+    F2_TRY(f2_place(ctx, ctx->stage_out, track, sizeof(double) * 5 * (size_t)U * (size_t)width, mem_space, false, &out));
+    F2_TRY(f2_upload_async(ctx, d_rec, rec.data(), sizeof(int64_t) * rec.size()));
+    F2_TRY(f2_launch_score_track(ctx, (const float*)d_scores, (const uint8_t*)d_labels, d_rec, U, origin, hop, width, blocks, out.as<double>()));
+    F2_TRY(f2_copy_back(ctx, out));
+    return f2_host_wait(ctx, mem_space);
+}
+
+// The envelopes are made once (eval_envelopes) and stay in ctx->stage_out for the picture and the window loop. Order on the stream:
+// envelopes, picture (pooled values in ctx->work, a host caller's levels in ctx->work2, both copied out before anything else is
+// queued), window loop (which takes ctx->work as the convolution workspace and ctx->work2 for its window lists: behind the picture's
+// last reader on the stream, and f2_reserve waits for the stream before it moves a block), track. One carve of ctx->meta for all.
+int f2_eval_figure_batch(f2_ctx* ctx, const f2_cnn* cnn, const void* wave, int wave_dtype, const int64_t* offsets, const double* coefs,
+                         int B, int C, int lpf, double cutoff_hz, int fft_precision, int radius, int step, int hop,
+                         const int64_t* spans_or_null, int width, int pool, uint8_t* levels_or_null, double* range_or_null,
+                         double* track_or_null, float* scores_or_null, uint8_t* labels_or_null, int64_t* window_offsets_or_null,
+                         int mem_space) {
+    const f2_batch X = {wave, wave_dtype, offsets, coefs, B, C, lpf, cutoff_hz, fft_precision, mem_space};
+    eval_call E;
+    F2_TRY(eval_check(ctx, cnn, X, radius, step, &E));
+    F2_CHECK(ctx, hop >= 1, F2_ERR_INVALID, "hop must be at least 1 sample (got %d)", hop);
+    F2_TRY(picture_check(ctx, offsets, B, C, spans_or_null, width, pool, mem_space));
+    const int64_t total = X.total();
+    F2_CHECK(ctx, wave || total == 0, F2_ERR_INVALID, "null wave");
+    std::vector<int64_t> nbh((size_t)B), wo((size_t)B + 1, 0), spans(2 * (size_t)B);
+    for (int b = 0; b < B; ++b) {
+        nbh[(size_t)b] = strided_windows(offsets[b + 1] - offsets[b], E.R, step, hop);
+        wo[(size_t)b + 1] = wo[(size_t)b] + nbh[(size_t)b];
+        spans[2 * (size_t)b] = spans_or_null ? spans_or_null[2 * b] : 0;
+        spans[2 * (size_t)b + 1] = spans_or_null ? spans_or_null[2 * b + 1] : offsets[b + 1] - offsets[b];
+    }
+    const int64_t n_total = wo[(size_t)B];
+    if (window_offsets_or_null) memcpy(window_offsets_or_null, wo.data(), sizeof(int64_t) * wo.size());
+    if (B == 0) return F2_OK;
+
+    const bool want_picture = levels_or_null || range_or_null, want_track = track_or_null != nullptr;
+    const size_t track_bytes = sizeof(double) * 5 * (size_t)B * (size_t)width;
+    const size_t tail_bytes = want_track && mem_space != F2_MEM_DEVICE ? track_bytes : 0;   // a host caller's track: behind the scores
+    std::vector<int64_t> rec;
+    const int64_t track_blocks = track_records(wo.data(), B, spans.data(), hop, width, &rec);
+    picture_meta P;
+    int64_t* d_rec;
+    f2_meta_carve meta;
+    P.add(&meta, B), meta.add(&d_rec, rec.size());
+    F2_TRY(meta.reserve(ctx));
+    F2_TRY(f2_upload_offsets(ctx, offsets, B));   // (a batch without a sample still gets its pictures)
+    if (total > 0) F2_TRY(eval_envelopes(ctx, &E, X, nullptr, n_total));
+    if (want_picture)
+        F2_TRY(picture_enqueue(ctx, E.d_env, offsets, B, C, spans_or_null, width, pool, &P, nullptr, levels_or_null, range_or_null != nullptr,
+                               mem_space));
+    if (n_total > 0) {
+        const int64_t chunk = n_total < CNN_CHUNK ? n_total : CNN_CHUNK;
+        F2_TRY(eval_cnn_begin(ctx, cnn, &E, chunk, n_total, C, scores_or_null, labels_or_null, mem_space, want_track, tail_bytes));
+        F2_TRY(strided_window_loop(ctx, cnn, &E, X, nbh, chunk, radius, step, hop));
+        F2_TRY(eval_dense_flush(ctx, cnn, &E));
+    } else {
+        F2_TRY(f2_place_scores(ctx, nullptr, nullptr, 0, mem_space, false, false, tail_bytes, &E.out));
+    }
+    if (want_track) {
+        f2_output track;
+        track.dev = tail_bytes ? E.out.tail : (char*)track_or_null, track.host = tail_bytes ? (char*)track_or_null : nullptr;
+        track.bytes = track_bytes, track.callers = !tail_bytes;
+        F2_TRY(f2_upload_async(ctx, d_rec, rec.data(), sizeof(int64_t) * rec.size()));
+        F2_TRY(f2_launch_score_track(ctx, E.out.scores.as<float>(), E.out.labels.as<uint8_t>(), d_rec, B, (int64_t)radius * step, hop, width,
+                                     track_blocks, track.as<double>()));
+        F2_TRY(f2_copy_back(ctx, track));
+    }
+    int rc = F2_OK;
+    if (n_total > 0)
+        rc = eval_cnn_end(ctx, cnn, &E);   // (waits for the stream)
+    else
+        F2_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (rc == F2_OK || rc == F2_ERR_NONPOSITIVE) picture_range(P, B, range_or_null);
+    return rc;
 }
 
 }  // extern "C"

@@ -1,7 +1,17 @@
 """Drop-in for the hot-path part of the reference's ``scripts/CNN/Evaluating.py``: WAV -> filterbank ->
 envelope -> every-sample 11xC windows -> normalise -> CNN -> rising/falling label per sample
-(``EvaluateOneWavArray`` :42-87, ``EvaluateOneWavFile`` :116-135). The plots (:109-113) are outside this path; the
-scores and labels are returned and saved next to the WAV instead.
+(``EvaluateOneWavArray`` :42-87, ``EvaluateOneWavFile`` :116-135). The scores and labels are returned and saved next to the
+WAV; the figure the reference ends in (:109-113) is made with ``figure=True``.
+
+``figure=True`` (``cnn eval|evalnoise|evalrand --figure [--figure-width W]``) is that figure, ``scripts/plotting/PlottingCNN.py``:
+the gammatonegram with the formant track and a rising / falling tick per decision, and below it the network's probability of
+"rising" over time beside arctan of the formant's slope, its p-value and the phoneme boundaries. The evaluation then goes
+through ``f2_eval_figure_batch``: filterbank and envelope run once for decisions and picture, and the decisions come down
+reduced to the W (default 1600) columns of the picture. The PNG goes to ``graphs/FallingOrRising/<basename>.png`` (for
+``evalnoise`` the basename of the noisy file) and the ``.npz`` gains ``figure_track`` (W, 5: rows, rising rows, mean / min / max
+probability per column) and ``figure_span``. Formant, slope and phoneme overlays come from the source file's ``.FB`` / ``.PHN``
+where they exist (not for a file whose rate differed under ``resample=``), the accuracy text from ``accuracy=``. Scores and
+labels are bit for bit those without the flag; ``figure=False`` changes nothing.
 
 ``accuracy='reference'|'centre'`` (``cnn eval|evalnoise|evalrand|noisesweep --accuracy [MODE]``) is the end of the reference's
 ``EvaluateOneWavArray`` (:38-40, :92-108): the decisions held against the labels ``LabelDataGenerator.ExtractLabel`` derives
@@ -160,6 +170,58 @@ def _scored_extra(file, labels, accuracy, hop, framerate, source, resample):
     return extra or None
 
 
+# ---- the figure (reference scripts/CNN/Evaluating.py:109-113, scripts/plotting/PlottingCNN.py) ------------------------------
+FIGURE_WIDTH = 1600
+
+
+def _figure_path(stem):
+    return os.path.join('graphs', 'FallingOrRising', stem + '.png')
+
+
+def _formant_number():
+    """FORMANT of configF2CNN.conf (configure.py's answer without the file)"""
+    from configparser import ConfigParser
+    from ...config import CONFIG_NAME
+    config = ConfigParser()
+    config.read_dict({'CNN': {'FORMANT': '2'}})
+    config.read(CONFIG_NAME)
+    return config.getint('CNN', 'FORMANT')
+
+
+def _write_figure(file, stem, levels, track, N, framerate, source, extra):
+    """graphs/FallingOrRising/<stem>.png from the levels (C, W) and the track (W, 5) of a file of N samples, with the overlays
+    the side files of `file` give; returns the keys the .npz gains"""
+    from ...png import write_png
+    from ..plotting import PlottingCNN
+    from ..plotting.PlottingProcessing import GetNewHeightERB
+    from ..processing.FBFileReader import GetFormantFrequencies
+    from ..processing.PHNFileReader import ExtractPhonemes
+    cfg = F2Config()
+    _, ratios = GetNewHeightERB(levels, filters.centre_freqs(framerate, cfg.nchannels, cfg.low_freq))
+    formant = slope = phonemes = None
+    sampPeriod = cfg.sampling_period
+    base = os.path.splitext(file)[0]
+    if source != framerate:
+        print("\t\t{}\tresampled from {} Hz to {} Hz, its .FB / .PHN count source samples: figure without formant, slope "
+              "and phonemes".format(file, source, framerate))
+    else:
+        if os.path.exists(base + '.FB'):
+            formant, sampPeriod = GetFormantFrequencies(base + '.FB', _formant_number())
+            slope = PlottingCNN.FormantSlopeTrack(formant, cfg.radius, framerate * sampPeriod / 1000000.)
+        if os.path.exists(base + '.PHN'):
+            phonemes = ExtractPhonemes(base + '.PHN')
+    accuracy = (extra or {}).get('accuracy')
+    if accuracy is not None and not numpy.isfinite(accuracy):
+        accuracy = None
+    rgb = PlottingCNN.RenderFigure(levels, ratios, track, (0, N), framerate, formant, sampPeriod, slope, phonemes, accuracy,
+                                   cfg.low_freq)
+    path = _figure_path(stem)
+    os.makedirs(os.path.dirname(path), exist_ok=True)
+    write_png(path, rgb)
+    print("\t\t{}\tfigure -> {}".format(file, path))
+    return dict(figure_track=track, figure_span=numpy.array([0, N], numpy.int64))
+
+
 def EvaluateOneWavArray(wavArray, framerate, wavFileName=None, model='last_trained_model', LPF=False, CUTOFF=100,
                         CENTER_FREQUENCIES=None, FILTERBANK_COEFFICIENTS=None, ctx=None, return_envelopes=False, hop=None):
     """Returns (scores (nb,2) float32, labels (nb,) uint8 [, envelopes (C,N) float64]); nb = N - 11*STEP, or with a hop
@@ -209,18 +271,28 @@ def EvaluateOneWavArray(wavArray, framerate, wavFileName=None, model='last_train
 
 
 def EvaluateOneWavFile(file, LPF=False, CUTOFF=50, model='last_trained_model', CENTER_FREQUENCIES=None,
-                       FILTERBANK_COEFFICIENTS=None, hop=None, accuracy=None, resample=False):
-    """`cnn eval --file X.WAV [--hop N] [--accuracy [MODE]] [--resample]`: writes <base>.F2CNN.npz (scores, labels; with a hop
-    also hop, timepoints; with accuracy= and the file's .FB / .PHN also accuracy, confusion, accuracy_mode; with resample=
-    framerate, source_framerate) and returns (scores, labels)."""
+                       FILTERBANK_COEFFICIENTS=None, hop=None, accuracy=None, resample=False, figure=False,
+                       figure_width=FIGURE_WIDTH):
+    """`cnn eval --file X.WAV [--hop N] [--accuracy [MODE]] [--resample] [--figure]`: writes <base>.F2CNN.npz (scores, labels;
+    with a hop also hop, timepoints; with accuracy= and the file's .FB / .PHN also accuracy, confusion, accuracy_mode; with
+    resample= framerate, source_framerate; with figure= figure_track, figure_span, and graphs/FallingOrRising/<basename>.png)
+    and returns (scores, labels)."""
     print('Using model', model if not isinstance(model, F2CNNModel) else '<in-memory model>')
     print("File:\t\t{}".format(file))
     source, framerate, wavArray = _load([file], resample)[0]
-    scores, labels = EvaluateOneWavArray(wavArray, framerate, file, model=model, LPF=LPF, CUTOFF=CUTOFF,
-                                         CENTER_FREQUENCIES=CENTER_FREQUENCIES,
-                                         FILTERBANK_COEFFICIENTS=FILTERBANK_COEFFICIENTS, hop=hop)
+    if figure:
+        scores, labels, levels, track = EvaluateWavArrays([wavArray], framerate, model=model, LPF=LPF, CUTOFF=CUTOFF,
+                                                          FILTERBANK_COEFFICIENTS=FILTERBANK_COEFFICIENTS, hop=hop,
+                                                          figure_width=figure_width)[0]
+    else:
+        scores, labels = EvaluateOneWavArray(wavArray, framerate, file, model=model, LPF=LPF, CUTOFF=CUTOFF,
+                                             CENTER_FREQUENCIES=CENTER_FREQUENCIES,
+                                             FILTERBANK_COEFFICIENTS=FILTERBANK_COEFFICIENTS, hop=hop)
     out = os.path.splitext(file)[0] + '.F2CNN.npz'
     extra = _scored_extra(file, labels, accuracy, hop, framerate, source, resample)
+    if figure:
+        extra = dict(extra or {}, **_write_figure(file, os.path.splitext(os.path.basename(file))[0], levels, track, len(wavArray),
+                                                  framerate, source, extra))
     _save(out, scores, labels, hop, len(wavArray), framerate, extra)
     rising = int(labels.sum())
     print("\t\t{}\tdone ! {} windows: {} rising, {} falling -> {}".format(file, len(labels), rising,
@@ -230,11 +302,13 @@ def EvaluateOneWavFile(file, LPF=False, CUTOFF=50, model='last_trained_model', C
 
 # ---- batch / noise evaluation (reference scripts/CNN/Evaluating.py:138-221) -------------
 def EvaluateWavArrays(wavArrays, framerate, model='last_trained_model', LPF=False, CUTOFF=100,
-                      FILTERBANK_COEFFICIENTS=None, ctx=None, hop=None):
+                      FILTERBANK_COEFFICIENTS=None, ctx=None, hop=None, figure_width=None):
     """EvaluateOneWavArray for a list of utterances of one sample type in one device pass (f2_eval_batch): the
     filterbank and envelope kernels see the whole batch, windows and CNN run utterance by utterance. With a hop
     (f2_eval_batch_strided) every hop-th window, and the window stage and the CNN see the batch as well.
-    Returns a list of (scores (nb,2) float32, labels (nb,) uint8)."""
+    Returns a list of (scores (nb,2) float32, labels (nb,) uint8). With figure_width=W the pass is f2_eval_figure_batch
+    (hop=None: hop 1, the same rows) and every entry also holds the picture's levels (C, W) uint8 and the track (W, 5) float64
+    of the decisions over the whole utterance."""
     ctx = ctx or _lib.default_context()
     cfg = F2Config()
     if FILTERBANK_COEFFICIENTS is None:
@@ -258,8 +332,16 @@ def EvaluateWavArrays(wavArrays, framerate, model='last_trained_model', LPF=Fals
         nbs = [_lib.strided_window_count(w.shape[0], cfg.radius, STEP, hop) for w in waves]
     scores = numpy.empty((sum(nbs), 2), numpy.float32)
     labels = numpy.empty(sum(nbs), numpy.uint8)
+    levels = track = None
     try:
-        if hop is not None:
+        if figure_width is not None:
+            levels = numpy.zeros((len(waves), Cn, int(figure_width)), numpy.uint8)
+            track = numpy.empty((len(waves), int(figure_width), 5), numpy.float64)
+            got, _ = ctx.eval_figure_batch(model.handle(ctx), flat, dts[0], offsets, coefs, len(waves), Cn, bool(LPF),
+                                           CUTOFF if LPF else 0.0, FFT_PRECISION, cfg.radius, STEP, 1 if hop is None else hop,
+                                           None, int(figure_width), 0, levels, track, scores, labels, _lib.MEM_HOST)
+            assert list(numpy.diff(got)) == nbs
+        elif hop is not None:
             got = ctx.eval_batch_strided(model.handle(ctx), flat, dts[0], offsets, coefs, len(waves), Cn, bool(LPF),
                                          CUTOFF if LPF else 0.0, FFT_PRECISION, cfg.radius, STEP, hop, scores, labels,
                                          _lib.MEM_HOST)
@@ -272,19 +354,21 @@ def EvaluateWavArrays(wavArrays, framerate, model='last_trained_model', LPF=Fals
             raise ValueError("values must all be positive")
         raise
     out, pos = [], 0
-    for nb in nbs:
-        out.append((scores[pos:pos + nb], labels[pos:pos + nb]))
+    for b, nb in enumerate(nbs):
+        out.append((scores[pos:pos + nb], labels[pos:pos + nb]) + ((levels[b], track[b]) if figure_width is not None else ()))
         pos += nb
     return out
 
 
-def EvaluateRandom(count=None, LPF=False, CUTOFF=50, model='last_trained_model', hop=None, accuracy=None, resample=False):
+def EvaluateRandom(count=None, LPF=False, CUTOFF=50, model='last_trained_model', hop=None, accuracy=None, resample=False,
+                   figure=False, figure_width=FIGURE_WIDTH):
     """`cnn evalrand`: evaluate the WAV files under resources/f2cnn/*/ in random order (all of them, or `count`
     drawn with replacement like numpy.random.choice in the reference). The filterbank is designed once and the model
     is uploaded once (the reference reloads the Keras model for every file). With a hop each group of files is one
     strided call. With accuracy= every file that has its .FB / .PHN is scored against them - a group in one device pass - and
     the corpus total is printed from the summed confusion matrices. With resample= a group of files is brought to the
-    configured framerate first (a file whose rate differed is left out of the accuracy)."""
+    configured framerate first (a file whose rate differed is left out of the accuracy). With figure= each group of files is
+    one f2_eval_figure_batch call and every file gets its figure, as EvaluateOneWavFile writes it."""
     import glob
     import time
     TotalTime = time.time()
@@ -314,7 +398,13 @@ def EvaluateRandom(count=None, LPF=False, CUTOFF=50, model='last_trained_model',
         rates = {fr for fr, _ in loaded}
         if len(rates) == 1 and len({numpy.asarray(w).dtype for _, w in loaded}) == 1:
             outs = EvaluateWavArrays([w for _, w in loaded], loaded[0][0], model=model, LPF=LPF, CUTOFF=CUTOFF,
-                                     FILTERBANK_COEFFICIENTS=FILTERBANK_COEFFICIENTS, hop=hop)
+                                     FILTERBANK_COEFFICIENTS=FILTERBANK_COEFFICIENTS, hop=hop,
+                                     figure_width=figure_width if figure else None)
+        elif figure:                              # mixed files: one at a time
+            outs = [EvaluateWavArrays([w], fr, model=model, LPF=LPF, CUTOFF=CUTOFF,
+                                      FILTERBANK_COEFFICIENTS=FILTERBANK_COEFFICIENTS if fr == cfg.framerate else None, hop=hop,
+                                      figure_width=figure_width)[0]
+                    for fr, w in loaded]
         else:                                     # mixed files: one at a time
             outs = [EvaluateOneWavArray(w, fr, file, model=model, LPF=LPF, CUTOFF=CUTOFF,
                                         FILTERBANK_COEFFICIENTS=FILTERBANK_COEFFICIENTS if fr == cfg.framerate else None,
@@ -338,8 +428,12 @@ def EvaluateRandom(count=None, LPF=False, CUTOFF=50, model='last_trained_model',
                     _print_accuracy(group[i], confusion, accuracy)
                     extras[i] = _accuracy_keys(confusion, accuracy)
                     corpus += confusion
-        for file, source, (fr, w), (scores, labels), extra in zip(group, sources, loaded, outs, extras):
+        for file, source, (fr, w), result, extra in zip(group, sources, loaded, outs, extras):
+            scores, labels = result[:2]
             out = os.path.splitext(file)[0] + '.F2CNN.npz'
+            if figure:
+                extra = dict(extra or {}, **_write_figure(file, os.path.splitext(os.path.basename(file))[0], result[2], result[3],
+                                                          len(w), fr, source, extra))
             _save(out, scores, labels, hop, len(w), fr, dict(extra or {}, **_rate_keys(resample, fr, source)) or None)
             rising = int(labels.sum())
             print("\t\t{}\tdone ! {} windows: {} rising, {} falling -> {}".format(file, len(labels), rising,
@@ -378,13 +472,16 @@ def add_gaussian_noise(wave, SNRdB, rng=None):
 
 
 def EvaluateWithNoise(file, LPF=False, CUTOFF=100, model='last_trained_model', CENTER_FREQUENCIES=None,
-                      FILTERBANK_COEFFICIENTS=None, SNRdB=-3, rng=None, hop=None, accuracy=None, resample=False):
+                      FILTERBANK_COEFFICIENTS=None, SNRdB=-3, rng=None, hop=None, accuracy=None, resample=False, figure=False,
+                      figure_width=FIGURE_WIDTH):
     """`cnn evalnoise` (reference: scripts/CNN/Evaluating.py:193-221): the file plus Gaussian noise at the requested level is
     written next to copies of its annotation files under OutputWavFiles/addedNoise/ and the float64 waveform is evaluated by
     the device pipeline. Returns (scores, labels) and also leaves them in <target>.F2CNN.npz; `rng` (a numpy Generator or
     RandomState) makes the noise reproducible - the reference draws from the global numpy state. With accuracy= the noisy
     run is scored against the labels of the clean file's .FB / .PHN (what the copies under addedNoise/ are there for). With
-    resample= the noise is added to the resampled, one-channel signal and the noisy WAV is written at the configured framerate."""
+    resample= the noise is added to the resampled, one-channel signal and the noisy WAV is written at the configured framerate.
+    With figure= the noisy run's figure goes to graphs/FallingOrRising/<noisy stem>.png, its overlays from the clean file's
+    side files."""
     import shutil
     from scipy.io import wavfile
     print("File:\t\t{}".format(file))
@@ -399,10 +496,18 @@ def EvaluateWithNoise(file, LPF=False, CUTOFF=100, model='last_trained_model', C
         if os.path.exists(source + ext):
             shutil.copyfile(source + ext, target + ext)
     print('New noisy WAVE file saved as', target + '.WAV')
-    scores, labels = EvaluateOneWavArray(noisy, framerate, target + '.WAV', model=model, LPF=LPF, CUTOFF=CUTOFF,
-                                         CENTER_FREQUENCIES=CENTER_FREQUENCIES,
-                                         FILTERBANK_COEFFICIENTS=FILTERBANK_COEFFICIENTS, hop=hop)
+    if figure:
+        scores, labels, levels, track = EvaluateWavArrays([noisy], framerate, model=model, LPF=LPF, CUTOFF=CUTOFF,
+                                                          FILTERBANK_COEFFICIENTS=FILTERBANK_COEFFICIENTS, hop=hop,
+                                                          figure_width=figure_width)[0]
+    else:
+        scores, labels = EvaluateOneWavArray(noisy, framerate, target + '.WAV', model=model, LPF=LPF, CUTOFF=CUTOFF,
+                                             CENTER_FREQUENCIES=CENTER_FREQUENCIES,
+                                             FILTERBANK_COEFFICIENTS=FILTERBANK_COEFFICIENTS, hop=hop)
     extra = _scored_extra(file, labels, accuracy, hop, framerate, source_rate, resample)
+    if figure:
+        extra = dict(extra or {}, **_write_figure(file, os.path.basename(target), levels, track, len(noisy), framerate, source_rate,
+                                                  extra))
     _save(target + '.F2CNN.npz', scores, labels, hop, len(noisy), framerate, extra)
     print("\t\t{}\tdone !".format(file))
     return scores, labels

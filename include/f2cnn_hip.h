@@ -67,7 +67,8 @@ int f2_version(void);   /* 100 * major + minor; 101 added f2_eval_batch, 102 f2_
                            106 f2_cnn_forward accepts any finite input on the split path (scales from the input's range; the
                            f2_cnn_get_info keys "f16x3_ok", "f16x3_check_diff", "last_input_bound"), 107 f2_input_batch,
                            108 f2_eval_batch_strided, 109 f2_eval_noise_sweep, 110 f2_label_accuracy, 111 f2_cnn_score_windows,
-                           112 f2_envelope_picture + f2_gammatonegram_batch, 113 f2_resample_batch */
+                           112 f2_envelope_picture + f2_gammatonegram_batch, 113 f2_resample_batch,
+                           114 f2_score_track + f2_eval_figure_batch */
 int f2_device_count(int* count);
 int f2_ctx_create(int device, f2_ctx** ctx);
 int f2_ctx_destroy(f2_ctx* ctx);
@@ -508,6 +509,65 @@ int f2_resample_batch(f2_ctx* ctx, const void* audio /* (offsets[B], channels) i
                       int channels, int channel /* -1: mean */, const int64_t* offsets /* host, B+1, in FRAMES */, int B,
                       int64_t up, int64_t down, const double* taps /* host, 2*half_len+1 */, int64_t half_len,
                       double* out /* mem_space */, int64_t* out_offsets /* host, B+1, written by the call */, int mem_space);
+
+/* ---- `cnn eval|evalnoise|evalrand --figure`: the decisions of an evaluation over its gammatonegram, one device pass ------------
+ * scripts/plotting/PlottingCNN.py (called from EvaluateOneWavArray, scripts/CNN/Evaluating.py:109-113) draws the gammatonegram with
+ * a rising / falling tick per decision and, below it, the network's probability of "rising" over time - from every score, on the
+ * host, after a second filterbank + envelope pass for the picture. Here the scores are reduced on the device to the time columns
+ * of the picture, and one call makes the picture from the envelopes the evaluation uses.
+ *
+ * f2_score_track: scores (window_offsets[U], 2) float32 and labels (window_offsets[U]) uint8 in mem_space, as
+ * f2_eval_batch_strided returns them. Utterance u owns rows j = 0 .. n_u - 1, n_u = window_offsets[u+1] - window_offsets[u]; row j
+ * stands at sample t_j = origin + j*hop. Its span is [s_u, e_u) = spans[2u], spans[2u+1] (required), m = e_u - s_u, W = width;
+ * the columns are those of f2_envelope_picture: lo_x = s_u + floor(x*m / W), hi_x = s_u + floor((x+1)*m / W), and hi_x = lo_x + 1
+ * where that bin is empty. Column x owns the rows with lo_x <= t_j < hi_x, a contiguous range of j (for m < W neighbouring columns
+ * repeat a sample and each of them owns its rows); m == 0: no column owns a row.
+ *   track   (U, W, 5) float64 in mem_space, track[u][x] =
+ *             [0] rows    the count of owned rows, exact
+ *             [1] rising  the count of owned rows with labels[j] != 0, exact
+ *             [2] mean    the float64 sum of (double)scores[j][1] over the owned rows, divided by rows
+ *             [3] min     the smallest scores[j][1] of the owned rows, the float32 value widened
+ *             [4] max     the largest
+ *           A column without rows is {0, 0, NaN, NaN, NaN}; a NaN score makes mean, min and max of its column NaN.
+ *           The sum has a fixed order (2^lg lanes per column, lg from the most rows a column of the utterance can own, at most 64
+ *           lanes; each lane adds its own rows in index order, then a fixed shuffle tree) and uses no floating-point atomics: the
+ *           same bits on every call and in both memory spaces. A column may own any number of rows (width 1 over a long file).
+ * F2_MEM_DEVICE: the call enqueues on the context's stream and returns; F2_MEM_HOST: it returns when track is filled.
+ * F2_ERR_INVALID, with nothing launched and track untouched: a NULL ctx, window_offsets or spans; NULL scores or labels with
+ * window_offsets[U] > 0; NULL track with U > 0; U < 0, hop < 1, origin < 0 or width < 1; window offsets that do not start at 0 or
+ * that decrease; a span with s < 0 or e < s; a mem_space other than F2_MEM_HOST / F2_MEM_DEVICE. F2_ERR_UNSUPPORTED, likewise:
+ * width > 65536; an utterance whose last row's t_j does not fit int64. U == 0: F2_OK.
+ *
+ * f2_eval_figure_batch: filterbank, envelope, picture, strided evaluation and track of a ragged batch in one pass. The envelopes
+ * are computed once and never leave the device. Every output is optional and defined by the calls above, bit for bit:
+ *   scores, labels, window_offsets   what f2_eval_batch_strided returns for the same wave ... hop and mem_space
+ *   levels (B, C, W), range (host, 2B)   what f2_envelope_picture returns (spans, width, pool as there) for the envelopes the
+ *           evaluation uses: those of the two-kernel route, i.e. what f2_eval_utterance hands out in env_or_null for each
+ *           utterance, laid out as the ragged batch. They are NOT the envelopes f2_gammatonegram_batch may take from the spectral
+ *           route (equal to a few ulp only), so a `plot gtg` picture of the same file may differ from this one in a level here
+ *           and there.
+ *   track (B, W, 5)   what f2_score_track returns for those scores, labels and window_offsets, the same spans (NULL: [0, n_b)),
+ *           origin = radius*step, hop and width. An utterance too short for a window still gets its picture; its track is all
+ *           empty columns.
+ * hop == 1 evaluates every sample: scores and labels are then those of f2_eval_batch.
+ * Errors: everything f2_eval_batch_strided rejects and everything f2_envelope_picture rejects (width, pool, spans), by the same
+ * checks and before anything is launched or written. F2_ERR_NONPOSITIVE as in the strided call. B == 0: F2_OK. The call waits for
+ * the stream before it returns (it hands back the range and the error flag), whatever mem_space is.
+ */
+int f2_score_track(f2_ctx* ctx, const float* scores /* (window_offsets[U], 2), mem_space */,
+                   const uint8_t* labels /* (window_offsets[U]), mem_space */,
+                   const int64_t* window_offsets /* host, U+1 */, int U,
+                   const int64_t* spans /* host, 2U: s_u, e_u in samples, required */,
+                   int64_t origin, int hop, int width,
+                   double* track /* (U, width, 5), mem_space */, int mem_space);
+int f2_eval_figure_batch(f2_ctx* ctx, const f2_cnn* cnn, const void* wave, int wave_dtype, const int64_t* offsets,
+                         const double* coefs, int B, int C, int lpf, double cutoff_hz, int fft_precision,
+                         int radius, int step, int hop,
+                         const int64_t* spans_or_null /* host, 2B */, int width, int pool,
+                         uint8_t* levels_or_null /* (B, C, width), mem_space */, double* range_or_null /* host, 2B */,
+                         double* track_or_null /* (B, width, 5), mem_space */,
+                         float* scores_or_null, uint8_t* labels_or_null, int64_t* window_offsets_or_null /* host, B+1 */,
+                         int mem_space);
 
 #ifdef __cplusplus
 }
