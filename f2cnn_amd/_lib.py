@@ -74,6 +74,10 @@ SIGNATURES = {
     "f2_score_track": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _i64, _i, _i, _vp, _i]),
     "f2_eval_figure_batch": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _d, _i, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp,
                                   _vp, _i]),
+    "f2_occlude_windows": (_i, [_vp, _vp, _i64, _i, _i, _vp, _i, C.c_float, _vp, _i]),
+    "f2_occlusion_map": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _i64, _i, _i, _vp, _i]),
+    "f2_eval_occlusion_batch": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _d, _i, _i, _i, _i, _vp, _i, C.c_float, _vp, _i, _i, _vp,
+                                     _vp, _vp, _vp, _vp, _vp, _vp, _i]),
 }
 
 _lib = None
@@ -518,6 +522,58 @@ class Context:
                                                  int(bool(lpf)), float(cutoff), precision, radius, step, int(hop), _ptr(spans),
                                                  int(width), int(pool), _ptr(levels), _ptr(range_out), _ptr(track), _ptr(scores),
                                                  _ptr(labels), _ptr(window_offsets), mem_space))
+        return window_offsets, range_out.reshape(-1, 2)
+
+    @staticmethod
+    def _patch_args(patches, fill):
+        patches = np.ascontiguousarray(patches, dtype=np.int32).reshape(-1, 4)
+        # (a c_float made from the float32's bytes: a NaN payload reaches the library as it is)
+        return patches, len(patches), C.c_float.from_buffer_copy(np.float32(fill).tobytes())
+
+    def occlude_windows(self, x, n, R, Cn, patches, fill, out, mem_space):
+        """n windows (R, Cn) float32 -> (n, K + 1, R, Cn): level 0 the window, level k + 1 the window with the rectangle
+        patches[k] = (r0, r1, c0, c1), half-open, replaced by `fill` (see f2_occlude_windows). x / out: numpy arrays or device
+        pointers, by mem_space. Returns `out`."""
+        patches, K, fill = self._patch_args(patches, fill)
+        self.check(self.lib.f2_occlude_windows(self.handle, _ptr(x), int(n), int(R), int(Cn), _ptr(patches) if K else None, K, fill,
+                                               _ptr(out), mem_space))
+        return out
+
+    def occlusion_map(self, scores, labels, window_offsets, K, spans, origin, hop, width, map_out, mem_space):
+        """The scores (n, K + 1, 2) float32 and labels (n, K + 1) uint8 of an occluded evaluation reduced to `width` time columns per
+        utterance and patch (see f2_occlusion_map; rows, spans and columns as in score_track). `map_out` (U, K, width, 4) float64 -
+        rows, flipped rows, mean and mean absolute change of scores[:, k + 1, 1] against scores[:, 0, 1]. scores / labels /
+        map_out: numpy arrays or device pointers, by mem_space. Returns `map_out`."""
+        window_offsets = np.ascontiguousarray(window_offsets, dtype=np.int64)
+        U = len(window_offsets) - 1
+        spans = np.ascontiguousarray(spans, dtype=np.int64)
+        if spans.size != 2 * U:
+            raise ValueError("spans must hold (s_u, e_u) for each of the U utterances")
+        if isinstance(scores, np.ndarray):
+            scores = np.ascontiguousarray(scores, dtype=np.float32)
+        if isinstance(labels, np.ndarray):
+            labels = np.ascontiguousarray(labels, dtype=np.uint8)
+        if isinstance(map_out, np.ndarray) and (map_out.dtype != np.float64 or map_out.size != 4 * U * max(int(K), 0) * int(width)
+                                                or not map_out.flags["C_CONTIGUOUS"]):
+            raise ValueError("map_out must be contiguous float64 (U, K, width, 4)")
+        self.check(self.lib.f2_occlusion_map(self.handle, _ptr(scores), _ptr(labels), _ptr(window_offsets), U, int(K), _ptr(spans),
+                                             int(origin), int(hop), int(width), _ptr(map_out), mem_space))
+        return map_out
+
+    def eval_occlusion_batch(self, handle, wave, wave_dtype, offsets, coefs, B, Cn, lpf, cutoff, precision, radius, step, hop, patches,
+                             fill, spans, width, pool, levels, map_out, summary, scores, labels, mem_space, range_out=None):
+        """eval_figure_batch with every window evaluated at K + 1 occlusion levels and the occlusion map in the track's place (see
+        f2_eval_occlusion_batch). levels (B, Cn, width) uint8, map_out (B, K, width, 4) and summary (B, K, 4) float64, scores
+        (n, K + 1, 2) float32, labels (n, K + 1) uint8: numpy arrays or device pointers, by mem_space, any may be None; n counts
+        the windows of eval_batch_strided. Returns (window_offsets (B + 1, int64), range (B, 2) float64)."""
+        offsets, spans, range_out = self._picture_args(offsets, B, spans, range_out)
+        patches, K, fill = self._patch_args(patches, fill)
+        window_offsets = np.zeros(max(int(B), 0) + 1, np.int64)
+        self.check(self.lib.f2_eval_occlusion_batch(self.handle, handle, _ptr(wave), wave_dtype, _ptr(offsets), _ptr(coefs), int(B), Cn,
+                                                    int(bool(lpf)), float(cutoff), precision, radius, step, int(hop),
+                                                    _ptr(patches) if K else None, K, fill, _ptr(spans), int(width), int(pool),
+                                                    _ptr(levels), _ptr(range_out), _ptr(map_out), _ptr(summary), _ptr(scores),
+                                                    _ptr(labels), _ptr(window_offsets), mem_space))
         return window_offsets, range_out.reshape(-1, 2)
 
     def resample_batch(self, audio, pcm_format, channels, channel, offsets, B, up, down, taps, half_len, out, mem_space):

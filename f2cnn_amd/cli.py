@@ -38,6 +38,11 @@ package implements:
      "rising" beside arctan of the formant's slope, its p-value and the phoneme boundaries - as
      graphs/FallingOrRising/<basename>.png, W (default 1600) columns wide, without matplotlib; decisions and picture come from
      one device pass and the .npz also holds figure_track and figure_span)
+    (eval / evalnoise / evalrand also take --occlusion [BAND[:STRIDE]] [--occlusion-rows RBAND[:RSTRIDE]] [--occlusion-fill V]:
+     the occlusion map - every window evaluated again with each band of channels blanked, in the same device pass; one table
+     line per band (Hz range, rows, flips, mean change of P(rising)), graphs/Occlusion/<basename>.png with the map under the
+     gammatonegram, --figure-width columns wide, and occlusion_* keys in the .npz; scores and labels stay those without the
+     flag; not in the reference)
     python -m f2cnn_amd plot gtg [--file/-f WAV | --all] [--width W] [--pool mean|max] [--cutoff HZ] [--formant N] [--start S --end E] [--out PNG]
                                                             (gammatonegram pictures, pooled to W columns and log-normalised on the
                                                              device, written as graphs/gtg/<basename>.png without matplotlib; the
@@ -134,6 +139,15 @@ def build_parser():
                         "gammatonegram and the probability of 'rising' over time")
     c.add_argument('--figure-width', action='store', type=int, default=argparse.SUPPRESS, dest='figure_width',
                    help="--figure: columns of the picture (default 1600)")
+    c.add_argument('--occlusion', nargs='?', type=band_and_stride, const=(8, 8), default=argparse.SUPPRESS, dest='occlusion',
+                   metavar='BAND[:STRIDE]',
+                   help="eval / evalnoise / evalrand: the occlusion map - every window evaluated again with each band of BAND "
+                        "channels (one every STRIDE channels; the bare flag: 8:8, BAND alone: STRIDE = BAND) blanked; a table per "
+                        "patch, occlusion_* keys in the .npz and graphs/Occlusion/<basename>.png, --figure-width columns wide")
+    c.add_argument('--occlusion-rows', type=band_and_stride, default=argparse.SUPPRESS, dest='occlusion_rows',
+                   metavar='RBAND[:RSTRIDE]', help="--occlusion: blank bands of RBAND window rows as well (no picture then)")
+    c.add_argument('--occlusion-fill', type=float, default=argparse.SUPPRESS, dest='occlusion_fill', metavar='V',
+                   help="--occlusion: the value a blanked cell takes, in [0, 1] (default 0, a normalised window's minimum)")
     g = sub.add_parser('plot', help='plotting commands')
     g.add_argument('plot_command', choices=PLOT)
     which = g.add_mutually_exclusive_group()
@@ -150,6 +164,18 @@ def build_parser():
     g.add_argument('--end', action='store', type=int, dest='end', help="gtg: one past its last sample")
     g.add_argument('--out', action='store', dest='out', help="gtg --file: the PNG to write")
     return parser
+
+
+def band_and_stride(text):
+    """'BAND' or 'BAND:STRIDE', both at least 1 -> (band, stride); BAND alone: the bands lie side by side"""
+    parts = text.split(':')
+    try:
+        values = [int(p) for p in parts]
+    except ValueError:
+        values = []
+    if len(values) not in (1, 2) or len(values) != len(parts) or min(values) < 1:
+        raise argparse.ArgumentTypeError("expected BAND or BAND:STRIDE, whole numbers of at least 1, not {!r}".format(text))
+    return values[0], values[-1]
 
 
 def labelled_window_files(args):
@@ -240,6 +266,21 @@ def main(argv=None):
             kwargs['figure'] = True
             if getattr(args, 'figure_width', None) is not None:
                 kwargs['figure_width'] = args.figure_width
+        if 'occlusion' in args:
+            if args.cnn_command == 'noisesweep':
+                print("--occlusion is not supported by noisesweep (use evalnoise --occlusion for one level)")
+                return 1
+            fill = getattr(args, 'occlusion_fill', 0.0)
+            if not 0.0 <= fill <= 1.0:
+                print("--occlusion-fill must lie in [0, 1], the range of a normalised window")
+                return 1
+            rows = getattr(args, 'occlusion_rows', (None, None))
+            kwargs['occlusion'] = dict(band=args.occlusion[0], stride=args.occlusion[1], row_band=rows[0], row_stride=rows[1], fill=fill)
+            if getattr(args, 'figure_width', None) is not None:
+                kwargs['figure_width'] = args.figure_width
+        elif 'occlusion_rows' in args or 'occlusion_fill' in args:
+            print("--occlusion-rows and --occlusion-fill belong to --occlusion")
+            return 1
         if args.cnn_command == 'evalrand':                     # needs no --file (unreachable in the reference CLI)
             if args.count is not None:
                 kwargs['count'] = args.count

@@ -54,6 +54,7 @@ struct f2_ctx {
     f2_scratch work;       // intermediates (GFB between K1 and K2, activations, ...)
     f2_scratch work2;
     f2_scratch xbuf;       // window tensor chunk between K3 and K4
+    f2_scratch occ_src;    // f2_eval_occlusion_batch: the source windows of a chunk, which k_occlude_windows expands into xbuf
     f2_scratch dense_in;   // conv4 outputs (+ dense1 outputs) of the windows of several utterances: one dense launch for all
     f2_scratch noise_wave; // f2_eval_noise_sweep: the (K+1) x batch float64 waveform when the caller gives no device buffer for it
     // The small arrays of the call in flight (f2_meta_carve): sigma / stats / window offsets of the noise sweep, counts and reference
@@ -524,6 +525,14 @@ int f2_track_lanes_log2(int64_t m, int width, int hop);
 int64_t f2_track_blocks(int width, int lg);
 int f2_launch_score_track(f2_ctx* ctx, const float* d_scores, const uint8_t* d_labels, const int64_t* d_rec, int U, int64_t origin,
                           int hop, int width, int64_t blocks_per_utt, double* d_track);
+// f2_occlusion.hip, the kernels of f2_occlude_windows / f2_occlusion_map / f2_eval_occlusion_batch. d_x: n windows (R, C), d_out:
+// (n, K + 1, R, C), neither needs more than element alignment; d_patches: K x {r0, r1, c0, c1}, inside the window (the caller checks).
+// The map's d_rec, lanes and workgroups are those of f2_launch_score_track; d_scores (rows, K + 1, 2), d_labels (rows, K + 1),
+// d_map (U, K, width, 4) float64.
+int f2_launch_occlude_windows(f2_ctx* ctx, const float* d_x, int64_t n, int R, int C, const int32_t* d_patches, int K, float fill,
+                              float* d_out);
+int f2_launch_occlusion_map(f2_ctx* ctx, const float* d_scores, const uint8_t* d_labels, const int64_t* d_rec, int U, int K, int64_t origin,
+                            int hop, int width, int64_t blocks_per_utt, double* d_map);
 // f2_resample.hip, the kernels of f2_resample_batch. F2_RESAMPLE_BLOCK outputs per workgroup, which stages at most
 // F2_RESAMPLE_SPAN_MAX input frames (f2_resample_span: what (up, down, T) need, T = taps per phase).
 // d_meta: 4 int64 per utterance {first input frame, frames, first output sample, output samples}, then B + 1 running sums of the

@@ -309,8 +309,15 @@ static int64_t strided_windows(int64_t n, int R, int step, int hop) {
 // chunk): one window-stage launch set and one convolution launch set per chunk, whatever B. (On the decimating route a chunk also
 // closes at COLUMN_CAP columns of the window stage's scratch - 2 * radius * step / hop columns per segment on top of its windows:
 // 150 MB for 128 channels - which only batches of very many very short utterances at a small hop reach.)
+// d_windows: where the window stage writes a chunk (the eval calls: ctx->xbuf). occ (f2_eval_occlusion_batch): the chunk's windows
+// are then expanded into xbuf as (m, occ->K + 1, R, C) and the network sees m * (occ->K + 1) windows.
+struct occlusion_stage {
+    const int32_t* d_patches;
+    int K;
+    float fill;
+};
 static int strided_window_loop(f2_ctx* ctx, const f2_cnn* cnn, eval_call* E, const f2_batch& X, const std::vector<int64_t>& nbh,
-                               int64_t chunk, int radius, int step, int hop) {
+                               int64_t chunk, int radius, int step, int hop, float* d_windows, const occlusion_stage* occ = nullptr) {
     constexpr int64_t COLUMN_CAP = 8 * CNN_CHUNK;
     const int64_t* offsets = X.offsets;
     const int B = X.B, C = X.C;
@@ -319,10 +326,12 @@ static int strided_window_loop(f2_ctx* ctx, const f2_cnn* cnn, eval_call* E, con
     int64_t m = 0, cols = 0;     // windows and scratch columns of the open chunk
     auto close_chunk = [&]() -> int {
         if (m > 0) {
-            F2_TRY(eval_chunk_room(ctx, cnn, E, m));
+            const int64_t seen = occ ? m * (occ->K + 1) : m;   // windows the network sees
+            F2_TRY(eval_chunk_room(ctx, cnn, E, seen));
             F2_TRY(f2_launch_gather_strided(ctx, E->d_env, C, (const int64_t*)ctx->offsets.ptr, offsets, segs.data(), (int)segs.size(),
-                                            radius, step, hop, (float*)ctx->xbuf.ptr, (int*)ctx->flags.ptr));
-            F2_TRY(eval_chunk_convs(ctx, cnn, E, m));
+                                            radius, step, hop, d_windows, (int*)ctx->flags.ptr));
+            if (occ) F2_TRY(f2_launch_occlude_windows(ctx, d_windows, m, E->R, C, occ->d_patches, occ->K, occ->fill, (float*)ctx->xbuf.ptr));
+            F2_TRY(eval_chunk_convs(ctx, cnn, E, seen));
         }
         segs.clear();
         m = cols = 0;
@@ -385,7 +394,7 @@ int f2_eval_batch_strided(f2_ctx* ctx, const f2_cnn* cnn, const void* wave, int 
     if (n_total == 0) return F2_OK;
     const int64_t chunk = n_total < CNN_CHUNK ? n_total : CNN_CHUNK;
     F2_TRY(eval_cnn_begin(ctx, cnn, &E, chunk, n_total, C, scores_or_null, labels_or_null, mem_space));
-    F2_TRY(strided_window_loop(ctx, cnn, &E, X, nbh, chunk, radius, step, hop));
+    F2_TRY(strided_window_loop(ctx, cnn, &E, X, nbh, chunk, radius, step, hop, (float*)ctx->xbuf.ptr));
     return eval_cnn_end(ctx, cnn, &E);
 }
 
@@ -884,7 +893,7 @@ int f2_eval_figure_batch(f2_ctx* ctx, const f2_cnn* cnn, const void* wave, int w
     if (n_total > 0) {
         const int64_t chunk = n_total < CNN_CHUNK ? n_total : CNN_CHUNK;
         F2_TRY(eval_cnn_begin(ctx, cnn, &E, chunk, n_total, C, scores_or_null, labels_or_null, mem_space, want_track, tail_bytes));
-        F2_TRY(strided_window_loop(ctx, cnn, &E, X, nbh, chunk, radius, step, hop));
+        F2_TRY(strided_window_loop(ctx, cnn, &E, X, nbh, chunk, radius, step, hop, (float*)ctx->xbuf.ptr));
         F2_TRY(eval_dense_flush(ctx, cnn, &E));
     } else {
         F2_TRY(f2_place_scores(ctx, nullptr, nullptr, 0, mem_space, false, false, tail_bytes, &E.out));
@@ -898,6 +907,206 @@ int f2_eval_figure_batch(f2_ctx* ctx, const f2_cnn* cnn, const void* wave, int w
                                      track_blocks, track.as<double>()));
         F2_TRY(f2_copy_back(ctx, track));
     }
+    int rc = F2_OK;
+    if (n_total > 0)
+        rc = eval_cnn_end(ctx, cnn, &E);   // (waits for the stream)
+    else
+        F2_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (rc == F2_OK || rc == F2_ERR_NONPOSITIVE) picture_range(P, B, range_or_null);
+    return rc;
+}
+
+}  // extern "C"
+
+// ---- `cnn eval --occlusion`: f2_occlude_windows, f2_occlusion_map, and f2_eval_occlusion_batch = the figure call with every window
+// evaluated at K + 1 occlusion levels and the map of their differences instead of the track ----
+namespace {
+
+constexpr int OCCLUSION_MAX_PATCHES = 1024;
+
+// the argument errors the occlusion calls share: K patches inside an (R, C) window, n windows at K + 1 levels
+int occlusion_check(f2_ctx* ctx, const int32_t* patches, int K, int min_K, int R, int C, int64_t n) {
+    F2_CHECK(ctx, K >= min_K, F2_ERR_INVALID, "K (%d) must be at least %d", K, min_K);
+    F2_CHECK(ctx, patches || K == 0, F2_ERR_INVALID, "patches is NULL");
+    F2_CHECK(ctx, K <= OCCLUSION_MAX_PATCHES, F2_ERR_UNSUPPORTED, "%d patches (at most %d)", K, OCCLUSION_MAX_PATCHES);
+    for (int k = 0; k < K; ++k) {
+        const int32_t* p = patches + 4 * (size_t)k;
+        F2_CHECK(ctx, p[0] >= 0 && p[1] <= R && p[0] < p[1] && p[2] >= 0 && p[3] <= C && p[2] < p[3], F2_ERR_INVALID,
+                 "patch %d: rows [%d, %d) x channels [%d, %d) is empty or leaves the %d x %d window", k, p[0], p[1], p[2], p[3], R, C);
+    }
+    int64_t levels = 0;
+    F2_CHECK(ctx, !__builtin_mul_overflow(n, (int64_t)K + 1, &levels) && levels < (int64_t(1) << 31), F2_ERR_UNSUPPORTED,
+             "%lld windows at %d levels (fewer than 2^31 in all)", (long long)n, K + 1);
+    return F2_OK;
+}
+
+// the patch table as it goes up: K x 4 int32 in 2 K 8-byte words of the call's metadata
+void occlusion_patch_words(const int32_t* patches, int K, std::vector<int64_t>* words) {
+    words->assign(2 * (size_t)K, 0);
+    if (K > 0) memcpy(words->data(), patches, sizeof(int32_t) * 4 * (size_t)K);
+}
+
+}  // namespace
+
+extern "C" {
+
+int f2_occlude_windows(f2_ctx* ctx, const float* x, int64_t n, int R, int C, const int32_t* patches, int K, float fill, float* out,
+                       int mem_space) {
+    F2_TRY(f2_check_ctx(ctx));
+    F2_TRY(f2_check_mem_space(ctx, mem_space, false));
+    F2_CHECK(ctx, n >= 0 && R >= 0 && C >= 0 && K >= 0, F2_ERR_INVALID, "negative size (n=%lld, R=%d, C=%d, K=%d)", (long long)n, R, C, K);
+    F2_CHECK(ctx, (x && out) || n == 0, F2_ERR_INVALID, "null data pointer");
+    F2_TRY(occlusion_check(ctx, patches, K, 0, R, C, n));
+    F2_CHECK(ctx, (int64_t)R * C < (int64_t(1) << 31), F2_ERR_UNSUPPORTED, "windows of %d x %d values", R, C);
+    if (n == 0 || R == 0 || C == 0) return F2_OK;
+    const int64_t L = (int64_t)K + 1;
+    const size_t xs = (size_t)R * (size_t)C;
+
+    std::vector<int64_t> words;
+    occlusion_patch_words(patches, K, &words);
+    int64_t* d_words = nullptr;
+    f2_meta_carve meta;
+    meta.add(&d_words, words.size());
+    F2_TRY(meta.reserve(ctx));
+    if (K > 0) F2_TRY(f2_upload_async(ctx, d_words, words.data(), sizeof(int64_t) * words.size()));
+    // Device memory: one launch. Host memory: chunks of at most CNN_CHUNK output windows through stage_in / stage_out, each chunk's
+    // windows back before the next one goes up.
+    const int64_t per = CNN_CHUNK / L > 0 ? CNN_CHUNK / L : 1;
+    const int64_t chunk = mem_space == F2_MEM_DEVICE || n < per ? n : per;
+    f2_output win;
+    F2_TRY(f2_place(ctx, ctx->stage_out, out, sizeof(float) * xs * (size_t)(chunk * L), mem_space, true, &win));
+    win.bytes = sizeof(float) * xs * (size_t)(n * L);   // (of the whole output: chunk() cuts it)
+    for (int64_t s = 0; s < n; s += chunk) {
+        const int64_t m = n - s < chunk ? n - s : chunk;
+        const void* d_x;
+        F2_TRY(f2_stage_input(ctx, x + (size_t)s * xs, sizeof(float) * xs * (size_t)m, mem_space, &d_x));
+        const f2_output o = win.chunk(sizeof(float) * xs * (size_t)(s * L), sizeof(float) * xs * (size_t)(m * L));
+        F2_TRY(f2_launch_occlude_windows(ctx, (const float*)d_x, m, R, C, (const int32_t*)d_words, K, fill, o.as<float>()));
+        F2_TRY(f2_copy_back(ctx, o));
+        F2_TRY(f2_host_wait(ctx, mem_space));
+    }
+    return F2_OK;
+}
+
+int f2_occlusion_map(f2_ctx* ctx, const float* scores, const uint8_t* labels, const int64_t* window_offsets, int U, int K,
+                     const int64_t* spans, int64_t origin, int hop, int width, double* map, int mem_space) {
+    F2_TRY(f2_check_ctx(ctx));
+    F2_TRY(f2_check_mem_space(ctx, mem_space, false));
+    F2_CHECK(ctx, U >= 0 && hop >= 1 && origin >= 0 && width >= 1, F2_ERR_INVALID,
+             "U (%d) and origin (%lld) must be at least 0, hop (%d) and width (%d) at least 1", U, (long long)origin, hop, width);
+    F2_CHECK(ctx, K >= 1, F2_ERR_INVALID, "K (%d) must be at least 1", K);
+    F2_CHECK(ctx, K <= OCCLUSION_MAX_PATCHES, F2_ERR_UNSUPPORTED, "%d patches (at most %d)", K, OCCLUSION_MAX_PATCHES);
+    F2_TRY(f2_check_offsets(ctx, window_offsets, U, "window_offsets"));
+    F2_CHECK(ctx, spans, F2_ERR_INVALID, "spans is NULL");
+    const int64_t n_rows = window_offsets[U];
+    F2_CHECK(ctx, (scores && labels) || n_rows == 0, F2_ERR_INVALID, "null scores or labels");
+    F2_CHECK(ctx, map || U == 0, F2_ERR_INVALID, "map is NULL");
+    int64_t max_rows = 0;
+    for (int u = 0; u < U; ++u) {
+        F2_CHECK(ctx, spans[2 * u] >= 0 && spans[2 * u + 1] >= spans[2 * u], F2_ERR_INVALID, "utterance %d: [%lld, %lld) is not a span", u,
+                 (long long)spans[2 * u], (long long)spans[2 * u + 1]);
+        max_rows = std::max(max_rows, window_offsets[u + 1] - window_offsets[u]);
+    }
+    F2_CHECK(ctx, width <= PICTURE_MAX_WIDTH, F2_ERR_UNSUPPORTED, "width %d (at most %d columns)", width, PICTURE_MAX_WIDTH);
+    int64_t t_last = 0;   // the sample of the last row of the longest utterance has to be an int64
+    F2_CHECK(ctx, max_rows == 0 || (!__builtin_mul_overflow(max_rows - 1, (int64_t)hop, &t_last) && !__builtin_add_overflow(t_last, origin, &t_last)),
+             F2_ERR_UNSUPPORTED, "row %lld at hop %d from origin %lld is beyond int64", (long long)(max_rows - 1), hop, (long long)origin);
+    if (U == 0) return F2_OK;
+
+    const size_t L = (size_t)K + 1;
+    std::vector<int64_t> rec;
+    const int64_t blocks = track_records(window_offsets, U, spans, hop, width, &rec);
+    int64_t* d_rec;
+    f2_meta_carve meta;
+    meta.add(&d_rec, rec.size());
+    F2_TRY(meta.reserve(ctx));
+    const void *d_scores, *d_labels;
+    F2_TRY(f2_stage_input(ctx, scores, sizeof(float) * 2 * L * (size_t)n_rows, mem_space, &d_scores));
+    F2_TRY(f2_stage_into(ctx, ctx->stage_aux, labels, L * (size_t)n_rows, mem_space, &d_labels));
+    f2_output out;
+    F2_TRY(f2_place(ctx, ctx->stage_out, map, sizeof(double) * 4 * (size_t)U * (size_t)K * (size_t)width, mem_space, false, &out));
+    F2_TRY(f2_upload_async(ctx, d_rec, rec.data(), sizeof(int64_t) * rec.size()));
+    F2_TRY(f2_launch_occlusion_map(ctx, (const float*)d_scores, (const uint8_t*)d_labels, d_rec, U, K, origin, hop, width, blocks, out.as<double>()));
+    F2_TRY(f2_copy_back(ctx, out));
+    return f2_host_wait(ctx, mem_space);
+}
+
+// f2_eval_figure_batch's order on the stream, with two changes: the window stage writes a chunk of m = chunk / (K + 1) windows to
+// ctx->occ_src and k_occlude_windows expands them into ctx->xbuf, window-major, so that the convolutions and the dense groups see
+// m (K + 1) windows and write contiguous score rows; the map (the caller's spans and width) and the summary (spans [0, n_b), one
+// column) take the track's place, a host caller's behind the scores in ctx->stage_aux.
+int f2_eval_occlusion_batch(f2_ctx* ctx, const f2_cnn* cnn, const void* wave, int wave_dtype, const int64_t* offsets, const double* coefs,
+                            int B, int C, int lpf, double cutoff_hz, int fft_precision, int radius, int step, int hop,
+                            const int32_t* patches, int K, float fill, const int64_t* spans_or_null, int width, int pool,
+                            uint8_t* levels_or_null, double* range_or_null, double* map_or_null, double* summary_or_null,
+                            float* scores_or_null, uint8_t* labels_or_null, int64_t* window_offsets_or_null, int mem_space) {
+    const f2_batch X = {wave, wave_dtype, offsets, coefs, B, C, lpf, cutoff_hz, fft_precision, mem_space};
+    eval_call E;
+    F2_TRY(eval_check(ctx, cnn, X, radius, step, &E));
+    F2_CHECK(ctx, hop >= 1, F2_ERR_INVALID, "hop must be at least 1 sample (got %d)", hop);
+    F2_TRY(picture_check(ctx, offsets, B, C, spans_or_null, width, pool, mem_space));
+    const int64_t total = X.total();
+    F2_CHECK(ctx, wave || total == 0, F2_ERR_INVALID, "null wave");
+    F2_CHECK(ctx, fill >= 0.f && fill <= 1.f, F2_ERR_INVALID, "fill (%g) must lie in [0, 1], the range of a normalised window", (double)fill);
+    std::vector<int64_t> nbh((size_t)B), wo((size_t)B + 1, 0), spans(2 * (size_t)B), whole(2 * (size_t)B);
+    for (int b = 0; b < B; ++b) {
+        const int64_t nb = offsets[b + 1] - offsets[b];
+        nbh[(size_t)b] = strided_windows(nb, E.R, step, hop);
+        wo[(size_t)b + 1] = wo[(size_t)b] + nbh[(size_t)b];
+        spans[2 * (size_t)b] = spans_or_null ? spans_or_null[2 * b] : 0;
+        spans[2 * (size_t)b + 1] = spans_or_null ? spans_or_null[2 * b + 1] : nb;
+        whole[2 * (size_t)b] = 0, whole[2 * (size_t)b + 1] = nb;
+    }
+    const int64_t n_total = wo[(size_t)B];
+    F2_TRY(occlusion_check(ctx, patches, K, 1, E.R, C, n_total));
+    if (window_offsets_or_null) memcpy(window_offsets_or_null, wo.data(), sizeof(int64_t) * wo.size());
+    if (B == 0) return F2_OK;
+
+    const int64_t L = (int64_t)K + 1;
+    const bool want_picture = levels_or_null || range_or_null, want_map = map_or_null != nullptr, want_summary = summary_or_null != nullptr;
+    const bool host = mem_space != F2_MEM_DEVICE;
+    const size_t map_bytes = sizeof(double) * 4 * (size_t)B * (size_t)K * (size_t)width, summary_bytes = sizeof(double) * 4 * (size_t)B * (size_t)K;
+    const size_t tail_bytes = host ? (want_map ? map_bytes : 0) + (want_summary ? summary_bytes : 0) : 0;   // a host caller's: behind the scores
+    std::vector<int64_t> rec, rec1, words;
+    const int64_t map_blocks = track_records(wo.data(), B, spans.data(), hop, width, &rec);
+    const int64_t summary_blocks = track_records(wo.data(), B, whole.data(), hop, 1, &rec1);
+    occlusion_patch_words(patches, K, &words);
+    picture_meta P;
+    int64_t *d_rec, *d_rec1, *d_words;
+    f2_meta_carve meta;
+    P.add(&meta, B), meta.add(&d_rec, rec.size()), meta.add(&d_rec1, rec1.size()), meta.add(&d_words, words.size());
+    F2_TRY(meta.reserve(ctx));
+    F2_TRY(f2_upload_offsets(ctx, offsets, B));   // (a batch without a sample still gets its pictures)
+    if (total > 0) F2_TRY(eval_envelopes(ctx, &E, X, nullptr, n_total));
+    if (want_picture)
+        F2_TRY(picture_enqueue(ctx, E.d_env, offsets, B, C, spans_or_null, width, pool, &P, nullptr, levels_or_null, range_or_null != nullptr,
+                               mem_space));
+    if (n_total > 0) {
+        const int64_t per = CNN_CHUNK / L > 0 ? CNN_CHUNK / L : 1;   // source windows of a chunk
+        const int64_t chunk = n_total < per ? n_total : per;
+        F2_TRY(f2_reserve(ctx, ctx->occ_src, sizeof(float) * (size_t)chunk * E.R * (size_t)C));
+        F2_TRY(eval_cnn_begin(ctx, cnn, &E, chunk * L, n_total * L, C, scores_or_null, labels_or_null, mem_space, want_map || want_summary,
+                              tail_bytes));
+        F2_TRY(f2_upload_async(ctx, d_words, words.data(), sizeof(int64_t) * words.size()));
+        const occlusion_stage occ = {(const int32_t*)d_words, K, fill};
+        F2_TRY(strided_window_loop(ctx, cnn, &E, X, nbh, chunk, radius, step, hop, (float*)ctx->occ_src.ptr, &occ));
+        F2_TRY(eval_dense_flush(ctx, cnn, &E));
+    } else {
+        F2_TRY(f2_place_scores(ctx, nullptr, nullptr, 0, mem_space, false, false, tail_bytes, &E.out));
+    }
+    char* tail = E.out.tail;
+    auto reduce = [&](double* callers, size_t bytes, const std::vector<int64_t>& r, int64_t* d_r, int64_t blocks, int w) -> int {
+        f2_output o;
+        o.dev = host ? tail : (char*)callers, o.host = host ? (char*)callers : nullptr;
+        o.bytes = bytes, o.callers = !host;
+        if (host) tail += bytes;
+        F2_TRY(f2_upload_async(ctx, d_r, r.data(), sizeof(int64_t) * r.size()));
+        F2_TRY(f2_launch_occlusion_map(ctx, E.out.scores.as<float>(), E.out.labels.as<uint8_t>(), d_r, B, K, (int64_t)radius * step, hop, w,
+                                       blocks, o.as<double>()));
+        return f2_copy_back(ctx, o);
+    };
+    if (want_map) F2_TRY(reduce(map_or_null, map_bytes, rec, d_rec, map_blocks, width));
+    if (want_summary) F2_TRY(reduce(summary_or_null, summary_bytes, rec1, d_rec1, summary_blocks, 1));
     int rc = F2_OK;
     if (n_total > 0)
         rc = eval_cnn_end(ctx, cnn, &E);   // (waits for the stream)

@@ -13,6 +13,17 @@ probability per column) and ``figure_span``. Formant, slope and phoneme overlays
 where they exist (not for a file whose rate differed under ``resample=``), the accuracy text from ``accuracy=``. Scores and
 labels are bit for bit those without the flag; ``figure=False`` changes nothing.
 
+``occlusion=True | (band, stride) | dict`` (``cnn eval|evalnoise|evalrand --occlusion [BAND[:STRIDE]] [--occlusion-rows
+RBAND[:RSTRIDE]] [--occlusion-fill V]``; not in the reference) asks what the decisions rest on: every window is evaluated again
+with each patch of ``OcclusionPatches`` - bands of channels, optionally bands of window rows as well - replaced by the fill
+value, in the same device pass (``f2_eval_occlusion_batch``: the windows are expanded, evaluated and reduced on the device). Per
+patch a table line is printed - Hz range, rows, label flips, mean and mean absolute change of P(rising) - the ``.npz`` gains
+``occlusion_patches`` (K, 4), ``occlusion_fill``, ``occlusion_scores`` (n, K+1, 2), ``occlusion_summary`` (K, 4),
+``occlusion_map`` (K, W, 4: rows, flips, mean d, mean |d| per time column), ``occlusion_span`` and ``occlusion_hz`` (K, 2), and
+``graphs/Occlusion/<basename>.png`` shows the map under the gammatonegram (``PlottingCNN.RenderOcclusion``; W =
+``figure_width``; not with row bands). ``evalrand`` also prints the table of the corpus. Scores and labels are level 0 of the
+pass, bit for bit those without the flag; ``occlusion=None`` changes nothing.
+
 ``accuracy='reference'|'centre'`` (``cnn eval|evalnoise|evalrand|noisesweep --accuracy [MODE]``) is the end of the reference's
 ``EvaluateOneWavArray`` (:38-40, :92-108): the decisions held against the labels ``LabelDataGenerator.ExtractLabel`` derives
 from the SOURCE file's ``.FB`` / ``.PHN``, counted on the device (``f2_label_accuracy``, where the rule is written out). A row
@@ -222,6 +233,107 @@ def _write_figure(file, stem, levels, track, N, framerate, source, extra):
     return dict(figure_track=track, figure_span=numpy.array([0, N], numpy.int64))
 
 
+# ---- the occlusion map (not in the reference): which channel bands the decisions rest on -------------------------------------
+OCCLUSION_BAND, OCCLUSION_STRIDE = 8, 8
+
+
+def _bands(size, band, stride):
+    """[start, end) of the bands of `band` cells that start every `stride` cells along an axis of `size`: 1 + ceil(max(size - band,
+    0) / stride) of them, the last clipped at `size`"""
+    size, band, stride = int(size), int(band), int(stride)
+    if size < 1 or band < 1 or stride < 1:
+        raise ValueError("an occlusion band needs a size, a width and a stride of at least 1")
+    count = 1 + -(-max(size - band, 0) // stride)
+    return [(i * stride, min(i * stride + band, size)) for i in range(count)]
+
+
+def OcclusionPatches(rows, channels, band, stride, row_band=None, row_stride=None):
+    """(K, 4) int32 {r0, r1, c0, c1}, half-open: the patches of an occlusion map over (rows, channels) windows. Channel bands of
+    `band` channels start at i * stride, the last clipped at `channels`; row bands likewise from row_band / row_stride (default:
+    all rows, one band). Row band major."""
+    row_bands = [(0, int(rows))] if row_band is None else _bands(rows, row_band, row_band if row_stride is None else row_stride)
+    if int(rows) < 1:
+        raise ValueError("an occlusion band needs a size, a width and a stride of at least 1")
+    return numpy.array([(r0, r1, c0, c1) for r0, r1 in row_bands for c0, c1 in _bands(channels, band, stride)],
+                       numpy.int32).reshape(-1, 4)
+
+
+def _occlusion_spec(occlusion):
+    """occlusion= as the evaluation functions take it - True, (band, stride) or a dict with any of band, stride, row_band,
+    row_stride, fill - as a dict with all of them"""
+    spec = dict(band=OCCLUSION_BAND, stride=OCCLUSION_STRIDE, row_band=None, row_stride=None, fill=0.0)
+    if isinstance(occlusion, dict):
+        unknown = set(occlusion) - set(spec)
+        if unknown:
+            raise ValueError("occlusion= does not know {}".format(sorted(unknown)))
+        spec.update(occlusion)
+    elif occlusion is not True:
+        spec['band'], spec['stride'] = occlusion
+    if not 0.0 <= float(spec['fill']) <= 1.0:
+        raise ValueError("the occlusion fill must lie in [0, 1], the range of a normalised window")
+    return spec
+
+
+def CombineOcclusionSummaries(summaries):
+    """The (K, 4) summary {rows, flips, mean d, mean |d|} of several files as one: counts summed, means weighted by rows (a file
+    without rows, whose means are NaN, weighs nothing; no rows at all: NaN)."""
+    summaries = numpy.asarray(summaries, dtype=numpy.float64).reshape(len(summaries), -1, 4)
+    rows = summaries[..., 0]
+    out = numpy.full(summaries.shape[1:], numpy.nan)
+    out[:, 0], out[:, 1] = rows.sum(axis=0), summaries[..., 1].sum(axis=0)
+    some = out[:, 0] > 0
+    for c in (2, 3):
+        weighted = numpy.where(rows > 0, rows * summaries[..., c], 0.0).sum(axis=0)
+        out[some, c] = weighted[some] / out[some, 0]
+    return out
+
+
+def OcclusionTable(what, patches, hz, summary):
+    """The lines of the table `--occlusion` prints: one per patch - Hz range, rows, flips, flips %, mean d, mean |d|"""
+    lines = ["\t\t{}\tocclusion: change of P(rising) with a patch of the input blanked".format(what),
+             "\t\t{:>17} {:>7} {:>9} {:>9} {:>8} {:>10} {:>10}".format("Hz", "w.rows", "rows", "flips", "flips %", "mean d", "mean |d|")]
+    for (r0, r1, _, _), (f0, f1), (rows, flips, d, ad) in zip(patches, hz, summary):
+        lines.append("\t\t{:>8.0f}-{:<8.0f} {:>7} {:>9d} {:>9d} {:>8.2f} {:>+10.6f} {:>10.6f}".format(
+            min(f0, f1), max(f0, f1), "{}-{}".format(r0, r1 - 1), int(rows), int(flips), 100.0 * flips / rows if rows else float('nan'),
+            d, ad))
+    return lines
+
+
+def _occlusion_path(stem):
+    return os.path.join('graphs', 'Occlusion', stem + '.png')
+
+
+def _write_occlusion(file, stem, occ, N, framerate, source):
+    """The table of one file's occlusion pass `occ` (EvaluateWavArrays), graphs/Occlusion/<stem>.png when every patch spans all
+    rows of the window, and the keys the .npz gains"""
+    from ...png import write_png
+    from ..plotting import PlottingCNN
+    from ..plotting.PlottingProcessing import GetNewHeightERB
+    from ..processing.FBFileReader import GetFormantFrequencies
+    cfg = F2Config()
+    patches, levels = occ['patches'], occ['levels']
+    cf = numpy.asarray(filters.centre_freqs(framerate, levels.shape[0], cfg.low_freq), numpy.float64)
+    hz = numpy.stack([cf[patches[:, 2]], cf[patches[:, 3] - 1]], axis=1)
+    for line in OcclusionTable(file, patches, hz, occ['summary']):
+        print(line)
+    if ((patches[:, 0] == 0) & (patches[:, 1] == cfg.dots_per_input)).all():
+        _, ratios = GetNewHeightERB(levels, cf)
+        formant, sampPeriod = None, cfg.sampling_period
+        base = os.path.splitext(file)[0]
+        if source == framerate and os.path.exists(base + '.FB'):
+            formant, sampPeriod = GetFormantFrequencies(base + '.FB', _formant_number())
+        rgb = PlottingCNN.RenderOcclusion(levels, ratios, occ['map'], patches, (0, N), framerate, formant, sampPeriod, cfg.low_freq)
+        path = _occlusion_path(stem)
+        os.makedirs(os.path.dirname(path), exist_ok=True)
+        write_png(path, rgb)
+        print("\t\t{}\tocclusion map -> {}".format(file, path))
+    else:
+        print("\t\t{}\tocclusion patches with row bands: table and .npz keys only, no picture".format(file))
+    return dict(occlusion_patches=patches, occlusion_fill=numpy.float32(occ['fill']), occlusion_scores=occ['scores'],
+                occlusion_summary=occ['summary'], occlusion_map=occ['map'], occlusion_span=numpy.array([0, N], numpy.int64),
+                occlusion_hz=hz)
+
+
 def EvaluateOneWavArray(wavArray, framerate, wavFileName=None, model='last_trained_model', LPF=False, CUTOFF=100,
                         CENTER_FREQUENCIES=None, FILTERBANK_COEFFICIENTS=None, ctx=None, return_envelopes=False, hop=None):
     """Returns (scores (nb,2) float32, labels (nb,) uint8 [, envelopes (C,N) float64]); nb = N - 11*STEP, or with a hop
@@ -272,18 +384,25 @@ def EvaluateOneWavArray(wavArray, framerate, wavFileName=None, model='last_train
 
 def EvaluateOneWavFile(file, LPF=False, CUTOFF=50, model='last_trained_model', CENTER_FREQUENCIES=None,
                        FILTERBANK_COEFFICIENTS=None, hop=None, accuracy=None, resample=False, figure=False,
-                       figure_width=FIGURE_WIDTH):
-    """`cnn eval --file X.WAV [--hop N] [--accuracy [MODE]] [--resample] [--figure]`: writes <base>.F2CNN.npz (scores, labels;
-    with a hop also hop, timepoints; with accuracy= and the file's .FB / .PHN also accuracy, confusion, accuracy_mode; with
-    resample= framerate, source_framerate; with figure= figure_track, figure_span, and graphs/FallingOrRising/<basename>.png)
-    and returns (scores, labels)."""
+                       figure_width=FIGURE_WIDTH, occlusion=None):
+    """`cnn eval --file X.WAV [--hop N] [--accuracy [MODE]] [--resample] [--figure] [--occlusion]`: writes <base>.F2CNN.npz
+    (scores, labels; with a hop also hop, timepoints; with accuracy= and the file's .FB / .PHN also accuracy, confusion,
+    accuracy_mode; with resample= framerate, source_framerate; with figure= figure_track, figure_span, and
+    graphs/FallingOrRising/<basename>.png; with occlusion= the occlusion_* keys of _write_occlusion, its table, and
+    graphs/Occlusion/<basename>.png) and returns (scores, labels)."""
     print('Using model', model if not isinstance(model, F2CNNModel) else '<in-memory model>')
     print("File:\t\t{}".format(file))
     source, framerate, wavArray = _load([file], resample)[0]
-    if figure:
-        scores, labels, levels, track = EvaluateWavArrays([wavArray], framerate, model=model, LPF=LPF, CUTOFF=CUTOFF,
-                                                          FILTERBANK_COEFFICIENTS=FILTERBANK_COEFFICIENTS, hop=hop,
-                                                          figure_width=figure_width)[0]
+    occ = None
+    if figure or occlusion is not None:
+        result = EvaluateWavArrays([wavArray], framerate, model=model, LPF=LPF, CUTOFF=CUTOFF,
+                                   FILTERBANK_COEFFICIENTS=FILTERBANK_COEFFICIENTS, hop=hop,
+                                   figure_width=figure_width if figure else None, occlusion=occlusion, occlusion_width=figure_width)[0]
+        scores, labels = result[:2]
+        if figure:
+            levels, track = result[2:4]
+        if occlusion is not None:
+            occ = result[-1]
     else:
         scores, labels = EvaluateOneWavArray(wavArray, framerate, file, model=model, LPF=LPF, CUTOFF=CUTOFF,
                                              CENTER_FREQUENCIES=CENTER_FREQUENCIES,
@@ -293,6 +412,9 @@ def EvaluateOneWavFile(file, LPF=False, CUTOFF=50, model='last_trained_model', C
     if figure:
         extra = dict(extra or {}, **_write_figure(file, os.path.splitext(os.path.basename(file))[0], levels, track, len(wavArray),
                                                   framerate, source, extra))
+    if occ is not None:
+        extra = dict(extra or {}, **_write_occlusion(file, os.path.splitext(os.path.basename(file))[0], occ, len(wavArray), framerate,
+                                                     source))
     _save(out, scores, labels, hop, len(wavArray), framerate, extra)
     rising = int(labels.sum())
     print("\t\t{}\tdone ! {} windows: {} rising, {} falling -> {}".format(file, len(labels), rising,
@@ -302,13 +424,18 @@ def EvaluateOneWavFile(file, LPF=False, CUTOFF=50, model='last_trained_model', C
 
 # ---- batch / noise evaluation (reference scripts/CNN/Evaluating.py:138-221) -------------
 def EvaluateWavArrays(wavArrays, framerate, model='last_trained_model', LPF=False, CUTOFF=100,
-                      FILTERBANK_COEFFICIENTS=None, ctx=None, hop=None, figure_width=None):
+                      FILTERBANK_COEFFICIENTS=None, ctx=None, hop=None, figure_width=None, occlusion=None,
+                      occlusion_width=None):
     """EvaluateOneWavArray for a list of utterances of one sample type in one device pass (f2_eval_batch): the
     filterbank and envelope kernels see the whole batch, windows and CNN run utterance by utterance. With a hop
     (f2_eval_batch_strided) every hop-th window, and the window stage and the CNN see the batch as well.
     Returns a list of (scores (nb,2) float32, labels (nb,) uint8). With figure_width=W the pass is f2_eval_figure_batch
     (hop=None: hop 1, the same rows) and every entry also holds the picture's levels (C, W) uint8 and the track (W, 5) float64
-    of the decisions over the whole utterance."""
+    of the decisions over the whole utterance.
+    With occlusion= (True, (band, stride) or a dict: _occlusion_spec) the pass is f2_eval_occlusion_batch (hop=None: hop 1):
+    scores and labels are its level 0, the same bits, and every entry ends in a dict - patches (K, 4), fill, scores (nb, K + 1, 2),
+    summary (K, 4), map (K, W, 4) and levels (C, W), W = occlusion_width (default: figure_width, else FIGURE_WIDTH). With
+    figure_width as well the track is f2_score_track of the level-0 scores and the levels are the occlusion call's."""
     ctx = ctx or _lib.default_context()
     cfg = F2Config()
     if FILTERBANK_COEFFICIENTS is None:
@@ -332,9 +459,28 @@ def EvaluateWavArrays(wavArrays, framerate, model='last_trained_model', LPF=Fals
         nbs = [_lib.strided_window_count(w.shape[0], cfg.radius, STEP, hop) for w in waves]
     scores = numpy.empty((sum(nbs), 2), numpy.float32)
     labels = numpy.empty(sum(nbs), numpy.uint8)
-    levels = track = None
+    levels = track = occ = None
     try:
-        if figure_width is not None:
+        if occlusion is not None:
+            spec = _occlusion_spec(occlusion)
+            patches = OcclusionPatches(cfg.dots_per_input, Cn, spec['band'], spec['stride'], spec['row_band'], spec['row_stride'])
+            K, B = len(patches), len(waves)
+            W = int(occlusion_width or figure_width or FIGURE_WIDTH)
+            step_hop = 1 if hop is None else hop
+            occ = dict(patches=patches, fill=numpy.float32(spec['fill']), scores=numpy.empty((sum(nbs), K + 1, 2), numpy.float32),
+                       labels=numpy.empty((sum(nbs), K + 1), numpy.uint8), map=numpy.empty((B, K, W, 4), numpy.float64),
+                       summary=numpy.empty((B, K, 4), numpy.float64), levels=numpy.zeros((B, Cn, W), numpy.uint8))
+            got, _ = ctx.eval_occlusion_batch(model.handle(ctx), flat, dts[0], offsets, coefs, B, Cn, bool(LPF), CUTOFF if LPF else 0.0,
+                                              FFT_PRECISION, cfg.radius, STEP, step_hop, patches, occ['fill'], None, W, 0, occ['levels'],
+                                              occ['map'], occ['summary'], occ['scores'], occ['labels'], _lib.MEM_HOST)
+            assert list(numpy.diff(got)) == nbs
+            scores[...], labels[...] = occ['scores'][:, 0], occ['labels'][:, 0]
+            if figure_width is not None:
+                levels = occ['levels']
+                whole = numpy.stack([offsets[:-1] * 0, numpy.diff(offsets)], axis=1)
+                track = ctx.score_track(scores, labels, got, whole, cfg.radius * STEP, step_hop, W, numpy.empty((B, W, 5), numpy.float64),
+                                        _lib.MEM_HOST)
+        elif figure_width is not None:
             levels = numpy.zeros((len(waves), Cn, int(figure_width)), numpy.uint8)
             track = numpy.empty((len(waves), int(figure_width), 5), numpy.float64)
             got, _ = ctx.eval_figure_batch(model.handle(ctx), flat, dts[0], offsets, coefs, len(waves), Cn, bool(LPF),
@@ -355,20 +501,26 @@ def EvaluateWavArrays(wavArrays, framerate, model='last_trained_model', LPF=Fals
         raise
     out, pos = [], 0
     for b, nb in enumerate(nbs):
-        out.append((scores[pos:pos + nb], labels[pos:pos + nb]) + ((levels[b], track[b]) if figure_width is not None else ()))
+        entry = (scores[pos:pos + nb], labels[pos:pos + nb]) + ((levels[b], track[b]) if figure_width is not None else ())
+        if occ is not None:
+            entry += (dict(patches=occ['patches'], fill=occ['fill'], scores=occ['scores'][pos:pos + nb], summary=occ['summary'][b],
+                           map=occ['map'][b], levels=occ['levels'][b]),)
+        out.append(entry)
         pos += nb
     return out
 
 
 def EvaluateRandom(count=None, LPF=False, CUTOFF=50, model='last_trained_model', hop=None, accuracy=None, resample=False,
-                   figure=False, figure_width=FIGURE_WIDTH):
+                   figure=False, figure_width=FIGURE_WIDTH, occlusion=None):
     """`cnn evalrand`: evaluate the WAV files under resources/f2cnn/*/ in random order (all of them, or `count`
     drawn with replacement like numpy.random.choice in the reference). The filterbank is designed once and the model
     is uploaded once (the reference reloads the Keras model for every file). With a hop each group of files is one
     strided call. With accuracy= every file that has its .FB / .PHN is scored against them - a group in one device pass - and
     the corpus total is printed from the summed confusion matrices. With resample= a group of files is brought to the
     configured framerate first (a file whose rate differed is left out of the accuracy). With figure= each group of files is
-    one f2_eval_figure_batch call and every file gets its figure, as EvaluateOneWavFile writes it."""
+    one f2_eval_figure_batch call and every file gets its figure, as EvaluateOneWavFile writes it. With occlusion= each group
+    is one f2_eval_occlusion_batch call, every file gets its table, map and .npz keys, and the corpus table is printed at the
+    end: counts summed, means weighted by rows (CombineOcclusionSummaries)."""
     import glob
     import time
     TotalTime = time.time()
@@ -391,6 +543,7 @@ def EvaluateRandom(count=None, LPF=False, CUTOFF=50, model='last_trained_model',
     if accuracy is not None:
         _accuracy_origin(accuracy, 0, 0)
         corpus = numpy.zeros((2, 2), numpy.int64)
+    occlusion_corpus = []                         # (patches, hz, summary) per file
     BATCH = 16                                    # files per device pass
     for s0 in range(0, len(wavFiles), BATCH):
         group = wavFiles[s0:s0 + BATCH]
@@ -399,11 +552,13 @@ def EvaluateRandom(count=None, LPF=False, CUTOFF=50, model='last_trained_model',
         if len(rates) == 1 and len({numpy.asarray(w).dtype for _, w in loaded}) == 1:
             outs = EvaluateWavArrays([w for _, w in loaded], loaded[0][0], model=model, LPF=LPF, CUTOFF=CUTOFF,
                                      FILTERBANK_COEFFICIENTS=FILTERBANK_COEFFICIENTS, hop=hop,
-                                     figure_width=figure_width if figure else None)
-        elif figure:                              # mixed files: one at a time
+                                     figure_width=figure_width if figure else None, occlusion=occlusion,
+                                     occlusion_width=figure_width)
+        elif figure or occlusion is not None:     # mixed files: one at a time
             outs = [EvaluateWavArrays([w], fr, model=model, LPF=LPF, CUTOFF=CUTOFF,
                                       FILTERBANK_COEFFICIENTS=FILTERBANK_COEFFICIENTS if fr == cfg.framerate else None, hop=hop,
-                                      figure_width=figure_width)[0]
+                                      figure_width=figure_width if figure else None, occlusion=occlusion,
+                                      occlusion_width=figure_width)[0]
                     for fr, w in loaded]
         else:                                     # mixed files: one at a time
             outs = [EvaluateOneWavArray(w, fr, file, model=model, LPF=LPF, CUTOFF=CUTOFF,
@@ -434,6 +589,13 @@ def EvaluateRandom(count=None, LPF=False, CUTOFF=50, model='last_trained_model',
             if figure:
                 extra = dict(extra or {}, **_write_figure(file, os.path.splitext(os.path.basename(file))[0], result[2], result[3],
                                                           len(w), fr, source, extra))
+            if occlusion is not None:
+                extra = dict(extra or {}, **_write_occlusion(file, os.path.splitext(os.path.basename(file))[0], result[-1], len(w), fr,
+                                                             source))
+                if occlusion_corpus and not numpy.array_equal(occlusion_corpus[0][0], extra['occlusion_patches']):
+                    occlusion_corpus = None       # (files of another channel count: no common table)
+                if occlusion_corpus is not None:
+                    occlusion_corpus.append((extra['occlusion_patches'], extra['occlusion_hz'], extra['occlusion_summary']))
             _save(out, scores, labels, hop, len(w), fr, dict(extra or {}, **_rate_keys(resample, fr, source)) or None)
             rising = int(labels.sum())
             print("\t\t{}\tdone ! {} windows: {} rising, {} falling -> {}".format(file, len(labels), rising,
@@ -442,6 +604,10 @@ def EvaluateRandom(count=None, LPF=False, CUTOFF=50, model='last_trained_model',
     print("Evaluating network on all files.")
     if accuracy is not None:
         _print_accuracy("all files", corpus, accuracy)
+    if occlusion is not None and occlusion_corpus:
+        for line in OcclusionTable("all files", occlusion_corpus[0][0], occlusion_corpus[0][1],
+                                   CombineOcclusionSummaries([summary for _, _, summary in occlusion_corpus])):
+            print(line)
     print('              Total time:', time.time() - TotalTime)
     print('')
     return results
@@ -473,7 +639,7 @@ def add_gaussian_noise(wave, SNRdB, rng=None):
 
 def EvaluateWithNoise(file, LPF=False, CUTOFF=100, model='last_trained_model', CENTER_FREQUENCIES=None,
                       FILTERBANK_COEFFICIENTS=None, SNRdB=-3, rng=None, hop=None, accuracy=None, resample=False, figure=False,
-                      figure_width=FIGURE_WIDTH):
+                      figure_width=FIGURE_WIDTH, occlusion=None):
     """`cnn evalnoise` (reference: scripts/CNN/Evaluating.py:193-221): the file plus Gaussian noise at the requested level is
     written next to copies of its annotation files under OutputWavFiles/addedNoise/ and the float64 waveform is evaluated by
     the device pipeline. Returns (scores, labels) and also leaves them in <target>.F2CNN.npz; `rng` (a numpy Generator or
@@ -481,7 +647,7 @@ def EvaluateWithNoise(file, LPF=False, CUTOFF=100, model='last_trained_model', C
     run is scored against the labels of the clean file's .FB / .PHN (what the copies under addedNoise/ are there for). With
     resample= the noise is added to the resampled, one-channel signal and the noisy WAV is written at the configured framerate.
     With figure= the noisy run's figure goes to graphs/FallingOrRising/<noisy stem>.png, its overlays from the clean file's
-    side files."""
+    side files. With occlusion= the noisy run's occlusion table, .npz keys and graphs/Occlusion/<noisy stem>.png."""
     import shutil
     from scipy.io import wavfile
     print("File:\t\t{}".format(file))
@@ -496,10 +662,16 @@ def EvaluateWithNoise(file, LPF=False, CUTOFF=100, model='last_trained_model', C
         if os.path.exists(source + ext):
             shutil.copyfile(source + ext, target + ext)
     print('New noisy WAVE file saved as', target + '.WAV')
-    if figure:
-        scores, labels, levels, track = EvaluateWavArrays([noisy], framerate, model=model, LPF=LPF, CUTOFF=CUTOFF,
-                                                          FILTERBANK_COEFFICIENTS=FILTERBANK_COEFFICIENTS, hop=hop,
-                                                          figure_width=figure_width)[0]
+    occ = None
+    if figure or occlusion is not None:
+        result = EvaluateWavArrays([noisy], framerate, model=model, LPF=LPF, CUTOFF=CUTOFF,
+                                   FILTERBANK_COEFFICIENTS=FILTERBANK_COEFFICIENTS, hop=hop,
+                                   figure_width=figure_width if figure else None, occlusion=occlusion, occlusion_width=figure_width)[0]
+        scores, labels = result[:2]
+        if figure:
+            levels, track = result[2:4]
+        if occlusion is not None:
+            occ = result[-1]
     else:
         scores, labels = EvaluateOneWavArray(noisy, framerate, target + '.WAV', model=model, LPF=LPF, CUTOFF=CUTOFF,
                                              CENTER_FREQUENCIES=CENTER_FREQUENCIES,
@@ -508,6 +680,8 @@ def EvaluateWithNoise(file, LPF=False, CUTOFF=100, model='last_trained_model', C
     if figure:
         extra = dict(extra or {}, **_write_figure(file, os.path.basename(target), levels, track, len(noisy), framerate, source_rate,
                                                   extra))
+    if occ is not None:
+        extra = dict(extra or {}, **_write_occlusion(file, os.path.basename(target), occ, len(noisy), framerate, source_rate))
     _save(target + '.F2CNN.npz', scores, labels, hop, len(noisy), framerate, extra)
     print("\t\t{}\tdone !".format(file))
     return scores, labels

@@ -17,7 +17,10 @@ of the device's track (f2_score_track / f2_eval_figure_batch):
                   the top left.
     STRIP_ROWS    rows: every phoneme's name centred on its segment where text_mask fits between the boundaries
 
-Legends and axis labels are not drawn."""
+Legends and axis labels are not drawn.
+
+``RenderOcclusion`` (not in the reference) is the picture of ``--occlusion``: the same upper panel over a panel of the same
+geometry that shows, per channel band and time column, how far blanking the band moves the probability of "rising"."""
 import numpy
 
 from ..processing.FBFileReader import frame_windows
@@ -168,3 +171,51 @@ def RenderFigure(levels, ratios, track, span, framerate, formant_hz=None, sampPe
             _put_text(strip, mask, 2, left, BLACK)
     gap = numpy.full((GAP_ROWS, width, 3), 255, numpy.uint8)
     return numpy.concatenate([upper, gap, lower, strip], axis=0)
+
+
+def diverging_colours(values, scale):
+    """(..., 3) uint8 for values in [-scale, scale]: BLUE at -scale, white at 0, RED at +scale, linear in between (a ramp
+    symmetric about 0); scale <= 0 or a value that is not finite: white / GREY."""
+    values = numpy.asarray(values, dtype=numpy.float64)
+    finite = numpy.isfinite(values)
+    t = numpy.clip(numpy.where(finite, values, 0.0) / scale, -1.0, 1.0) if scale > 0 else numpy.zeros(values.shape)
+    end = numpy.where((t >= 0)[..., None], numpy.array(RED, numpy.float64), numpy.array(BLUE, numpy.float64))
+    rgb = numpy.rint(255.0 + numpy.abs(t)[..., None] * (end - 255.0)).astype(numpy.uint8)
+    rgb[~finite] = GREY
+    return rgb
+
+
+def RenderOcclusion(levels, ratios, map, patches, span, framerate, formant=None, sampPeriod=10000, low_freq=100):
+    """The occlusion figure as (2 * sum(ratios) + GAP_ROWS, W, 3) uint8, column x of both panels column x of the device's map
+    (f2_occlusion_map / f2_eval_occlusion_batch):
+
+        upper panel   the gammatonegram as RenderFigure draws it, the formant's track in black
+        GAP_ROWS      white rows
+        lower panel   the same geometry: channel c takes the ERB row height ratios[c] and, in column x, the colour of mean d =
+                      map[k][x][2] of the patch k that blanks it (the mean over the patches that do, where bands overlap) on
+                      diverging_colours, scaled to the largest |mean d| of the file: red where blanking the band raises P(rising),
+                      blue where it lowers it, white where it changes nothing. A column without rows is grey; a channel no patch
+                      blanks is white. The formant's track in black again.
+
+    levels (C, W) uint8; map (K, W, 4) float64 {rows, flips, mean d, mean |d|}; patches (K, 4) {r0, r1, c0, c1}, every one spanning
+    all rows of the window (the picture has one value per channel and column); span = (start, end) samples of a file at
+    `framerate`; formant: its track in Hz, one value per frame of sampPeriod microseconds, or None."""
+    levels, map = numpy.asarray(levels), numpy.asarray(map, dtype=numpy.float64)
+    patches = numpy.asarray(patches).reshape(-1, 4)
+    channels, width = levels.shape
+    start, end = int(span[0]), int(span[1])
+    upper = colour_table()[numpy.repeat(levels, ratios, axis=0)]
+    total, count = numpy.zeros((channels, width)), numpy.zeros((channels, 1))
+    for k, (_, _, c0, c1) in enumerate(patches):
+        total[c0:c1] += map[k, :, 2]
+        count[c0:c1] += 1
+    with numpy.errstate(invalid='ignore', divide='ignore'):
+        mean_d = numpy.where(count > 0, total / count, 0.0)
+    mean_d[:, map[0, :, 0] == 0] = numpy.nan           # (the columns own the same rows whatever the patch)
+    finite = numpy.abs(map[..., 2][numpy.isfinite(map[..., 2])])
+    lower = numpy.repeat(diverging_colours(mean_d, finite.max() if finite.size else 0.0), ratios, axis=0)
+    if formant is not None:
+        for panel in (upper, lower):
+            draw_formants(panel, [formant], sampPeriod, framerate, start, end, low_freq)
+    gap = numpy.full((GAP_ROWS, width, 3), 255, numpy.uint8)
+    return numpy.concatenate([upper, gap, lower], axis=0)

@@ -569,6 +569,64 @@ int f2_eval_figure_batch(f2_ctx* ctx, const f2_cnn* cnn, const void* wave, int w
                          float* scores_or_null, uint8_t* labels_or_null, int64_t* window_offsets_or_null /* host, B+1 */,
                          int mem_space);
 
+/* ---- `cnn eval|evalnoise|evalrand --occlusion`: which channel bands the decisions rest on, one device pass ----------------------
+ * An occlusion map: blank a band of channels in the network's input, run the network again, record how far P(rising) moves and how
+ * often the label flips. The windows are expanded, evaluated and reduced on the device; no window crosses the link.
+ * (f2_version stays 114 with these three entries: look the symbols up to find out whether a build has them.)
+ *
+ * f2_occlude_windows: x (n, R, C) float32 -> out (n, K+1, R, C) float32, both in mem_space, window-major. Level 0 of a window is
+ * the window; level k+1 is the window with patch k, the half-open rectangle [r0, r1) x [c0, c1) = patches[4k .. 4k+3] (host,
+ * int32), replaced by `fill`. Every element moves as its bit pattern: a NaN payload in x or in fill survives. K == 0: out is a copy
+ * of x. Patches may repeat and overlap (each level holds one patch). Device pointers need element alignment only. F2_MEM_DEVICE:
+ * the call enqueues and returns; F2_MEM_HOST: it works through device scratch in chunks of at most 16384 output windows and
+ * returns when out is filled.
+ * F2_ERR_INVALID, with nothing launched and out untouched: a NULL ctx; NULL x or out with n > 0; NULL patches with K > 0; n, R, C
+ * or K negative; a patch with r0 < 0, r1 > R or r0 >= r1, or the same on columns; a mem_space other than F2_MEM_HOST /
+ * F2_MEM_DEVICE. F2_ERR_UNSUPPORTED, likewise: K > 1024; n*(K+1) >= 2^31; R*C >= 2^31.
+ *
+ * f2_occlusion_map: scores (window_offsets[U], K+1, 2) float32 and labels (window_offsets[U], K+1) uint8 in mem_space, the
+ * network's outputs for such windows. Rows, spans and columns are those of f2_score_track (same origin, hop, spans, width rule).
+ * With d_j = (double)scores[j][k+1][1] - (double)scores[j][0][1]:
+ *   map   (U, K, W, 4) float64 in mem_space, map[u][k][x] =
+ *           [0] rows      the count of owned rows, exact
+ *           [1] flips     the count of owned rows with (labels[j][k+1] != 0) != (labels[j][0] != 0), exact
+ *           [2] mean d    the float64 sum of d_j over the owned rows, divided by rows
+ *           [3] mean |d|  the float64 sum of |d_j|, divided by rows
+ *         A column without rows is {0, 0, NaN, NaN}; a NaN score makes [2] and [3] of its column and patch NaN. The sums have
+ *         f2_score_track's fixed order: the same bits on every call and in both memory spaces.
+ * Argument errors: those of f2_score_track, and K < 1 (F2_ERR_INVALID), K > 1024 (F2_ERR_UNSUPPORTED). U == 0: F2_OK.
+ *
+ * f2_eval_occlusion_batch: f2_eval_figure_batch with every window evaluated at K+1 occlusion levels, and the map in the track's
+ * place. Every output is optional and defined by calls that exist, bit for bit:
+ *   scores (n, K+1, 2), labels (n, K+1), window_offsets   [:, 0] is what f2_eval_batch_strided returns for the same arguments;
+ *           [w][k+1] is what f2_cnn_forward returns for level k+1 of f2_occlude_windows applied to normalised window w - the one
+ *           f2_input_batch (normalize = 1) gives at centre radius*step + j*hop. The input stays in [0, 1] for 0 <= fill <= 1, so
+ *           the scale set is the one every eval call uses.
+ *   levels (B, C, W), range (host, 2B)   what f2_eval_figure_batch returns
+ *   map (B, K, W, 4)   f2_occlusion_map of those scores and labels, origin = radius*step, the same hop, spans (NULL: [0, n_b)), width
+ *   summary (B, K, 4)  f2_occlusion_map with spans [0, n_b) and width 1: every row of the utterance
+ * Errors, before anything is launched or written: everything f2_eval_figure_batch rejects; everything f2_occlude_windows rejects
+ * for R = 2*radius+1 and C, and K < 1; fill outside [0, 1] or NaN (F2_ERR_INVALID); total windows * (K+1) >= 2^31
+ * (F2_ERR_UNSUPPORTED). F2_ERR_NONPOSITIVE as in the strided call. B == 0: F2_OK. The call waits for the stream before it returns.
+ */
+int f2_occlude_windows(f2_ctx* ctx, const float* x /* (n, R, C), mem_space */, int64_t n, int R, int C,
+                       const int32_t* patches /* host, (K, 4): r0 r1 c0 c1 */, int K, float fill,
+                       float* out /* (n, K+1, R, C), mem_space */, int mem_space);
+int f2_occlusion_map(f2_ctx* ctx, const float* scores /* (window_offsets[U], K+1, 2), mem_space */,
+                     const uint8_t* labels /* (window_offsets[U], K+1), mem_space */,
+                     const int64_t* window_offsets /* host, U+1 */, int U, int K,
+                     const int64_t* spans /* host, 2U, required */, int64_t origin, int hop, int width,
+                     double* map /* (U, K, width, 4), mem_space */, int mem_space);
+int f2_eval_occlusion_batch(f2_ctx* ctx, const f2_cnn* cnn, const void* wave, int wave_dtype, const int64_t* offsets,
+                            const double* coefs, int B, int C, int lpf, double cutoff_hz, int fft_precision,
+                            int radius, int step, int hop,
+                            const int32_t* patches /* host, (K, 4) */, int K, float fill,
+                            const int64_t* spans_or_null /* host, 2B */, int width, int pool,
+                            uint8_t* levels_or_null /* (B, C, width), mem_space */, double* range_or_null /* host, 2B */,
+                            double* map_or_null /* (B, K, width, 4), mem_space */, double* summary_or_null /* (B, K, 4), mem_space */,
+                            float* scores_or_null /* (n, K+1, 2) */, uint8_t* labels_or_null /* (n, K+1) */,
+                            int64_t* window_offsets_or_null /* host, B+1 */, int mem_space);
+
 #ifdef __cplusplus
 }
 #endif
