@@ -78,6 +78,8 @@ SIGNATURES = {
     "f2_occlusion_map": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _i64, _i, _i, _vp, _i]),
     "f2_eval_occlusion_batch": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _d, _i, _i, _i, _i, _vp, _i, C.c_float, _vp, _i, _i, _vp,
                                      _vp, _vp, _vp, _vp, _vp, _vp, _i]),
+    "f2_lowpass_levels": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _vp, _i]),
+    "f2_eval_cutoff_sweep": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i]),
 }
 
 _lib = None
@@ -405,6 +407,38 @@ class Context:
                                                 _ptr(scores), _ptr(labels), _ptr(window_offsets), _ptr(sigma), _ptr(stats),
                                                 mem_space))
         return window_offsets, sigma, stats
+
+    def lowpass_levels(self, env, offsets, B, Cn, cutoffs, levels, mem_space):
+        """Envelopes that are already in memory at every cutoff of `cutoffs` and unfiltered, in one device pass (see
+        f2_lowpass_levels): env holds the ragged (Cn, n_b) float64 blocks of the batch, levels receives (K+1) * Cn *
+        offsets[B] float64, level-major, the copy last (numpy arrays or device pointers, by mem_space)."""
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        cut = np.ascontiguousarray(cutoffs, dtype=np.float64).reshape(-1)
+        self.check(self.lib.f2_lowpass_levels(self.handle, _ptr(env), _ptr(offsets), int(B), int(Cn), _ptr(cut) if len(cut) else None,
+                                              len(cut), _ptr(levels), mem_space))
+
+    def eval_cutoff_sweep(self, handle, wave, wave_dtype, offsets, coefs, B, Cn, precision, radius, step, hop, cutoffs, env_levels,
+                          scores, labels, mem_space, window_offsets=None, stats=None):
+        """The batch at every envelope cutoff of `cutoffs` and unfiltered, in one device pass (see f2_eval_cutoff_sweep):
+        utterance l * B + b of the evaluated batch is utterance b at level l, the unfiltered level last. env_levels / scores /
+        labels (numpy arrays or device pointers, by mem_space) may be None. Returns (window_offsets ((K+1)*B + 1, int64), stats
+        ((K+1)*B, 2) int64: rising windows, windows labelled as the unfiltered level labels them), allocating those it is not
+        given."""
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        cut = np.ascontiguousarray(cutoffs, dtype=np.float64).reshape(-1)
+        U = (len(cut) + 1) * int(B)
+        if window_offsets is None:
+            window_offsets = np.zeros(U + 1, np.int64)
+        if stats is None:
+            stats = np.zeros((U, 2), np.int64)
+        for a, n in ((window_offsets, U + 1), (stats, 2 * U)):
+            if a.dtype != np.int64 or a.size != n or not a.flags["C_CONTIGUOUS"]:
+                raise ValueError("window_offsets / stats must be contiguous int64 (K+1)*B + 1 / ((K+1)*B, 2)")
+        self.check(self.lib.f2_eval_cutoff_sweep(self.handle, handle, _ptr(wave), wave_dtype, _ptr(offsets), _ptr(coefs), int(B), Cn,
+                                                 precision, radius, step, int(hop), _ptr(cut) if len(cut) else None, len(cut),
+                                                 _ptr(env_levels), _ptr(scores), _ptr(labels), _ptr(window_offsets), _ptr(stats),
+                                                 mem_space))
+        return window_offsets, stats
 
     def label_accuracy(self, labels, window_offsets, ref_offsets, ref_timepoints, ref_signs, origin, hop, step, mem_space,
                        counts=None):

@@ -22,6 +22,11 @@ package implements:
     python -m f2cnn_amd cnn noisesweep --file/-f WAV --snrs 20,10,0,-3 [--seed N] [--save-wavs] [--hop N|frame] [--lpf HZ] [--model/-m NPZ]
                                                             (the file at every level and clean in one device pass, agreement
                                                              with the clean decisions per level; not in the reference)
+    python -m f2cnn_amd cnn lpfsweep --file/-f WAV --cutoffs 5,10,20,50,100 [--hop N|frame] [--accuracy [MODE]] [--resample] [--model/-m NPZ]
+                                                            (the file at every envelope cutoff and unfiltered in one device pass -
+                                                             filterbank and Hilbert envelope run once - agreement with the
+                                                             unfiltered decisions per cutoff, written to <base>.lpfsweep.npz; takes
+                                                             no --lpf, --figure or --occlusion; not in the reference)
     python -m f2cnn_amd cnn evalrand [--count/-c N] [--lpf HZ] [--model/-m NPZ] [--hop N|frame]
     (--hop: a decision every N samples instead of every sample, `frame` = one per STEP of configF2CNN.conf; not in the reference)
     (eval / evalnoise / evalrand / noisesweep also take --accuracy [reference|centre]: the decisions against the labels of the
@@ -55,7 +60,7 @@ organize needs the licensed TIMIT+VTR corpora and stays with the reference.
 import argparse
 
 PREPARE = ("filter", "envelope", "label", "input", "features")
-CNN = ("train", "test", "eval", "evalnoise", "evalrand", "noisesweep")
+CNN = ("train", "test", "eval", "evalnoise", "evalrand", "noisesweep", "lpfsweep")
 PLOT = ("gtg",)
 
 
@@ -82,6 +87,18 @@ def snrs_argument(text):
     if not snrs or not all(math.isfinite(v) for v in snrs):
         raise argparse.ArgumentTypeError("--snrs takes a comma-separated list of SNRs in dB, not {!r}".format(text))
     return snrs
+
+
+def cutoffs_argument(text):
+    """--cutoffs: a comma-separated list of at least one finite cutoff in (0, 8000) Hz"""
+    import math
+    try:
+        cutoffs = [float(part) for part in text.split(',')]
+    except ValueError:
+        cutoffs = []
+    if not cutoffs or not all(math.isfinite(v) and 0 < v < 8000 for v in cutoffs):
+        raise argparse.ArgumentTypeError("--cutoffs takes a comma-separated list of cutoffs in Hz inside (0, 8000), not {!r}".format(text))
+    return cutoffs
 
 
 def build_parser():
@@ -117,6 +134,9 @@ def build_parser():
                         "every sample")
     c.add_argument('--snrs', action='store', type=snrs_argument, dest='snrs',
                    help="noisesweep: comma-separated SNRs in dB, e.g. 20,10,0,-3")
+    # (absent from the parsed arguments unless given: the commands parse as before without it)
+    c.add_argument('--cutoffs', action='store', type=cutoffs_argument, dest='cutoffs', default=argparse.SUPPRESS,
+                   help="lpfsweep: comma-separated envelope cutoffs in Hz, e.g. 5,10,20,50,100")
     c.add_argument('--seed', action='store', type=int, dest='seed', help="noisesweep: seed of the noise (default 0)")
     c.add_argument('--save-wavs', action='store_true', dest='save_wavs',
                    help="noisesweep: also write the noisy WAV files, as evalnoise does")
@@ -245,6 +265,16 @@ def main(argv=None):
             return 0
         from .scripts.CNN import Evaluating
         kwargs = {}
+        if args.cnn_command == 'lpfsweep':
+            if args.CUTOFF is not None:
+                print("--lpf is not supported by lpfsweep (the cutoffs come from --cutoffs; the unfiltered level is always there)")
+                return 1
+            if getattr(args, 'figure', False):
+                print("--figure is not supported by lpfsweep (use eval --lpf HZ --figure for one cutoff)")
+                return 1
+            if 'occlusion' in args:
+                print("--occlusion is not supported by lpfsweep (use eval --lpf HZ --occlusion for one cutoff)")
+                return 1
         if args.CUTOFF is not None:                            # f2cnn.py:149-151
             kwargs['LPF'] = True
             kwargs['CUTOFF'] = args.CUTOFF
@@ -294,6 +324,12 @@ def main(argv=None):
                 print("Please use --snrs to give the noise levels, e.g. --snrs 20,10,0,-3")
                 return 1
             Evaluating.EvaluateNoiseSweep([args.file], args.snrs, seed=args.seed or 0, save_wavs=args.save_wavs, **kwargs)
+            return 0
+        if args.cnn_command == 'lpfsweep':
+            if getattr(args, 'cutoffs', None) is None:
+                print("Please use --cutoffs to give the envelope cutoffs in Hz, e.g. --cutoffs 5,10,20,50,100")
+                return 1
+            Evaluating.EvaluateCutoffSweep([args.file], args.cutoffs, **kwargs)
             return 0
         kwargs['file'] = args.file
         if args.cnn_command == 'evalnoise':

@@ -57,7 +57,9 @@ struct f2_ctx {
     f2_scratch occ_src;    // f2_eval_occlusion_batch: the source windows of a chunk, which k_occlude_windows expands into xbuf
     f2_scratch dense_in;   // conv4 outputs (+ dense1 outputs) of the windows of several utterances: one dense launch for all
     f2_scratch noise_wave; // f2_eval_noise_sweep: the (K+1) x batch float64 waveform when the caller gives no device buffer for it
-    // The small arrays of the call in flight (f2_meta_carve): sigma / stats / window offsets of the noise sweep, counts and reference
+    f2_scratch lp_levels;  // f2_lowpass_levels / f2_eval_cutoff_sweep: the (K+1) x batch envelopes when the caller gives no device buffer
+    // The small arrays of the call in flight (f2_meta_carve): sigma / stats / window offsets of the noise sweep, filter coefficients /
+    // stats / window offsets of the cutoff sweep, counts and reference
     // labels of f2_label_accuracy, counts / loss sums / loss partials of f2_cnn_score_windows, span records and range words of the
     // pictures, utterance records of f2_resample_batch. One area for all of them, which holds while
     //  - nothing cached lives here: what a later call may find unchanged (spec_meta, rs_tab, offsets, coefs) has its own area;
@@ -491,6 +493,15 @@ int f2_launch_noise_levels(f2_ctx* ctx, const void* d_wave, int wave_dtype, cons
 // per utterance of the (K + 1) * B batch whose window offsets are d_window_offsets; max_windows: the most any utterance has
 int f2_launch_label_tally(f2_ctx* ctx, const uint8_t* d_labels, const int64_t* d_window_offsets, int B, int K, int64_t max_windows,
                           int64_t* d_stats);
+// f2_lowpass.hip, the kernel of f2_lowpass_levels / f2_eval_cutoff_sweep. f2_check_cutoffs: K in 1 .. F2_LOWPASS_MAX_CUTOFFS (below:
+// F2_ERR_INVALID, above: F2_ERR_UNSUPPORTED), cutoff_hz non-NULL, every value finite and in (0, 8000). f2_upload_lowpass_coefs: K x
+// {b0, a1} of butter(1, cutoff / 8000) to d_coef (2 K doubles). The launch reads the (C, n_b) blocks of d_env (utterance b at
+// C * d_offsets[b], total = offsets[B]) once and writes (K + 1) * C * total doubles, level-major, level K the copy.
+#define F2_LOWPASS_MAX_CUTOFFS 64
+int f2_check_cutoffs(f2_ctx* ctx, const double* cutoff_hz, int K);
+int f2_upload_lowpass_coefs(f2_ctx* ctx, const double* cutoff_hz, int K, double* d_coef);
+int f2_launch_lowpass_levels(f2_ctx* ctx, const double* d_env, const int64_t* d_offsets, int B, int C, int64_t total,
+                             const double* d_coef, int K, double* d_levels);
 // f2_accuracy.hip, the kernel of f2_label_accuracy. d_counts (4 per utterance, zeroed by the caller)[4 u + 2 ref + pred] += rows
 // of utterance u (rows d_window_offsets[u] .. [u + 1] of d_labels, row j at sample origin + j * hop) that the rule of the header
 // counts against reference set u % R (d_ref_offsets: R + 1; timepoints strictly increasing inside a set, signs 0 / 1);

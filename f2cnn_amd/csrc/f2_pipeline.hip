@@ -474,6 +474,73 @@ int f2_eval_noise_sweep(f2_ctx* ctx, const f2_cnn* cnn, const void* wave, int wa
     return F2_OK;
 }
 
+// f2_eval_cutoff_sweep: filterbank + envelope of the batch once, unfiltered; its K low-passed levels and the copy as ONE
+// (K+1) * B-utterance batch of envelopes (f2_lowpass.hip); the window loop of f2_eval_batch_strided over that batch with the tiled
+// offsets; the tally of its labels against the unfiltered level. One wait at the end (eval_cnn_end).
+int f2_eval_cutoff_sweep(f2_ctx* ctx, const f2_cnn* cnn, const void* wave, int wave_dtype, const int64_t* offsets,
+                         const double* coefs, int B, int C, int fft_precision, int radius, int step, int hop,
+                         const double* cutoff_hz, int K, double* env_levels_or_null, float* scores_or_null, uint8_t* labels_or_null,
+                         int64_t* window_offsets_or_null, int64_t* stats_or_null, int mem_space) {
+    const f2_batch X = {wave, wave_dtype, offsets, coefs, B, C, 0, 0.0, fft_precision, mem_space};
+    eval_call E;
+    F2_TRY(eval_check(ctx, cnn, X, radius, step, &E));
+    F2_CHECK(ctx, hop >= 1, F2_ERR_INVALID, "hop must be at least 1 sample (got %d)", hop);
+    F2_TRY(f2_check_cutoffs(ctx, cutoff_hz, K));
+    F2_CHECK(ctx, ((int64_t)K + 1) * (B > 0 ? B : 1) <= INT32_MAX / 2, F2_ERR_UNSUPPORTED, "%d levels of %d utterances", K + 1, B);
+    F2_CHECK(ctx, (int64_t)B * C <= INT32_MAX, F2_ERR_UNSUPPORTED, "%d utterances of %d channels", B, C);
+    const int64_t total = X.total();
+    F2_CHECK(ctx, wave || total == 0, F2_ERR_INVALID, "null wave");
+    const int U = (K + 1) * B;
+    // the (K+1) * B batch: the clean offsets tiled, its windows
+    std::vector<int64_t> tiled((size_t)U + 1, 0), wo((size_t)U + 1, 0), nbh((size_t)U, 0);
+    int64_t max_windows = 0;
+    for (int l = 0; l <= K; ++l)
+        for (int b = 0; b < B; ++b) {
+            const size_t u = (size_t)l * B + b;
+            nbh[u] = strided_windows(offsets[b + 1] - offsets[b], E.R, step, hop);
+            tiled[u + 1] = (int64_t)l * total + offsets[b + 1];
+            wo[u + 1] = wo[u] + nbh[u];
+            max_windows = nbh[u] > max_windows ? nbh[u] : max_windows;
+        }
+    const int64_t n_total = wo[(size_t)U];
+    if (window_offsets_or_null) memcpy(window_offsets_or_null, wo.data(), sizeof(int64_t) * ((size_t)U + 1));
+    if (stats_or_null && n_total == 0) std::fill(stats_or_null, stats_or_null + 2 * (size_t)U, (int64_t)0);
+    if (total == 0) return F2_OK;   // nothing to launch
+
+    // small arrays and the levels first: nothing below reallocates what a queued kernel uses (eval_envelopes does not touch
+    // ctx->meta or ctx->lp_levels)
+    double* d_coef;
+    int64_t *d_stats, *d_wo;
+    f2_meta_carve meta;
+    meta.add(&d_coef, 2 * (size_t)K), meta.add(&d_stats, 2 * (size_t)U), meta.add(&d_wo, (size_t)U + 1);
+    F2_TRY(meta.reserve(ctx));
+    f2_output levels;
+    F2_TRY(f2_place(ctx, ctx->lp_levels, env_levels_or_null, sizeof(double) * ((size_t)K + 1) * (size_t)C * (size_t)total, mem_space, true,
+                    &levels));
+    F2_TRY(f2_upload_lowpass_coefs(ctx, cutoff_hz, K, d_coef));
+    F2_TRY(eval_envelopes(ctx, &E, X, nullptr, n_total));
+    // the tiled offsets start with the clean ones: one device array serves the low-pass kernel and the window stage
+    F2_TRY(f2_upload_offsets(ctx, tiled.data(), U));
+    F2_TRY(f2_launch_lowpass_levels(ctx, E.d_env, (const int64_t*)ctx->offsets.ptr, B, C, total, d_coef, K, levels.as<double>()));
+    F2_TRY(f2_copy_back(ctx, levels));
+    if (n_total == 0) {
+        F2_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        return F2_OK;
+    }
+    E.d_env = levels.as<double>();
+    const f2_batch XU = {nullptr, F2_WAVE_F64, tiled.data(), coefs, U, C, 0, 0.0, fft_precision, mem_space};
+    const int64_t chunk = n_total < CNN_CHUNK ? n_total : CNN_CHUNK;
+    F2_TRY(eval_cnn_begin(ctx, cnn, &E, chunk, n_total, C, scores_or_null, labels_or_null, mem_space, true));
+    F2_TRY(strided_window_loop(ctx, cnn, &E, XU, nbh, chunk, radius, step, hop, (float*)ctx->xbuf.ptr));
+    F2_TRY(eval_dense_flush(ctx, cnn, &E));   // the tally reads every label
+    F2_HIP(ctx, hipMemsetAsync(d_stats, 0, sizeof(int64_t) * 2 * (size_t)U, ctx->stream));
+    F2_TRY(f2_upload_async(ctx, d_wo, wo.data(), sizeof(int64_t) * ((size_t)U + 1)));
+    F2_TRY(f2_launch_label_tally(ctx, E.out.labels.as<uint8_t>(), d_wo, B, K, max_windows, d_stats));
+    if (stats_or_null)
+        F2_HIP(ctx, hipMemcpyAsync(stats_or_null, d_stats, sizeof(int64_t) * 2 * (size_t)U, hipMemcpyDeviceToHost, ctx->stream));
+    return eval_cnn_end(ctx, cnn, &E);   // (waits for the stream)
+}
+
 int f2_label_accuracy(f2_ctx* ctx, const uint8_t* labels, const int64_t* window_offsets, int U, const int64_t* ref_offsets,
                       const int64_t* ref_timepoints, const uint8_t* ref_signs, int R, int64_t origin, int hop, int step,
                       int64_t* counts, int mem_space) {

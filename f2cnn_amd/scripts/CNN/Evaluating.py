@@ -41,7 +41,12 @@ row j is every-sample row j*N, bit for bit (``f2_eval_batch_strided``) - and the
 hop are then those of that rate whatever the file's, and the ``.npz`` files gain ``framerate`` and ``source_framerate``. A file
 that already is at that rate, mono and int16 is passed through untouched, so its results are bit for bit those without the flag.
 With ``accuracy=`` a file whose rate differed gets no accuracy: the timepoints of its ``.FB`` / ``.PHN`` count source samples.
-``resample=False`` changes nothing: a file is evaluated at its own rate, as the reference does."""
+``resample=False`` changes nothing: a file is evaluated at its own rate, as the reference does.
+
+``EvaluateCutoffSweep`` (``cnn lpfsweep --file X.WAV --cutoffs 5,10,20,50,100``; not in the reference, whose route is one ``cnn eval
+--lpf HZ`` per cutoff) evaluates a file at every envelope cutoff and unfiltered in one device pass (``f2_eval_cutoff_sweep``): the
+filterbank and the Hilbert envelope run once, the low-pass of ``EnvelopeExtraction.py:39-67`` K times on the result, and
+``<base>.lpfsweep.npz`` holds the decisions of every level and their agreement with the unfiltered ones."""
 import os
 
 import numpy
@@ -799,6 +804,124 @@ def EvaluateNoiseSweep(files, SNRdBs, seed=0, hop=None, LPF=False, CUTOFF=50, mo
                         for ext in ('.FB', '.PHN', '.WRD'):
                             if os.path.exists(source + ext):
                                 shutil.copyfile(source + ext, target + ext)
+                print("\t\t{}\tdone ! -> {}".format(file, out))
+                results[file] = res
+    return results
+
+
+# ---- `cnn lpfsweep`: one file at several envelope cutoffs (the modulation axis; not in the reference, whose route is one
+# `cnn eval --lpf HZ` per cutoff) ---------------------------------------------------------------------------------------------
+LEVELS_LIMIT = 8 << 30           # bytes of envelope levels one device pass of EvaluateCutoffSweep may ask for
+
+
+def _cutoff_text(cutoff):
+    """how a level is printed: 50.0 -> '50', 2.5 -> '2.5'"""
+    return '{:g}'.format(float(cutoff))
+
+
+def _cutoff_groups(members, K, Cn, batch=16, limit=LEVELS_LIMIT):
+    """members [(file, wave)] in passes of up to `batch` files whose (K + 1) * Cn * samples * 8 bytes of levels stay within
+    `limit` (a single file beyond it still gets a pass of its own)"""
+    group, samples = [], 0
+    for file, wave in members:
+        n = wave.shape[0]
+        if group and (len(group) == batch or (K + 1) * Cn * (samples + n) * 8 > limit):
+            yield group
+            group, samples = [], 0
+        group.append((file, wave))
+        samples += n
+    if group:
+        yield group
+
+
+def EvaluateCutoffSweep(files, cutoffs, hop=None, model='last_trained_model', ctx=None, accuracy=None, resample=False):
+    """`cnn lpfsweep`: every file at every envelope cutoff of `cutoffs` (Hz) and unfiltered in one device pass per group of
+    files (f2_eval_cutoff_sweep: filterbank and Hilbert envelope run once, the first-order low-pass of EnvelopeExtraction.py:39-67
+    K times on the result, in float64), with the unfiltered run of the same network as the referee. Per file, <base>.lpfsweep.npz
+    next to the WAV holds cutoff_hz, windows, rising, agree, agreement (= agree / windows, NaN without windows) - K + 1 entries
+    each, the unfiltered level last - hop, timepoints, scores (K + 1, n, 2) and labels_<k> for level k of cutoff_hz (labels_nolpf
+    for the unfiltered one); one line per level is printed and the same data is returned as a dict per file. Files are grouped
+    like EvaluateNoiseSweep groups them - one framerate and sample type per call, up to 16 files - and a group is cut short where
+    its levels would take more than 8 GiB. hop=None is hop 1. accuracy= and resample= as in EvaluateNoiseSweep: confusion
+    (K + 1, 2, 2) and accuracy_vtr (K + 1) per file that has its .FB / .PHN (one f2_label_accuracy call per group), framerate and
+    source_framerate."""
+    if isinstance(files, (str, bytes, os.PathLike)):
+        files = [files]
+    cut = numpy.asarray(cutoffs, dtype=numpy.float64).reshape(-1)
+    if not len(cut) or not numpy.isfinite(cut).all() or (cut <= 0).any() or (cut >= 8000).any():
+        raise ValueError("a cutoff sweep needs at least one finite cutoff in (0, 8000) Hz")
+    K = len(cut)
+    hop = 1 if hop is None else int(hop)
+    if accuracy is not None:
+        _accuracy_origin(accuracy, 0, 0)
+    ctx = ctx or _lib.default_context()
+    cfg = F2Config()
+    if not isinstance(model, F2CNNModel):
+        model = load_model(model)
+    read = _load(files, resample)
+    sources = {file: source for file, (source, _, _) in zip(files, read)}
+    groups = {}
+    for file, (_, framerate, wavArray) in zip(files, read):
+        wave, dt = filters._wave_args(wavArray)
+        groups.setdefault((framerate, dt), []).append((file, wave))
+    keys = [str(k) for k in range(K)] + ['nolpf']          # labels_<k>: level k of cutoff_hz
+    names = [_cutoff_text(v) + 'Hz' for v in cut] + ['nolpf']
+    results = {}
+    for (framerate, dt), members in groups.items():
+        coefs = numpy.ascontiguousarray(filters.make_erb_filters(framerate, filters.centre_freqs(framerate, cfg.nchannels,
+                                                                                                  cfg.low_freq)))
+        Cn = coefs.shape[0]
+        STEP = _step(framerate, cfg)
+        for group in _cutoff_groups(members, K, Cn):
+            B = len(group)
+            offsets = numpy.zeros(B + 1, numpy.int64)
+            offsets[1:] = numpy.cumsum([w.shape[0] for _, w in group])
+            flat = numpy.concatenate([w for _, w in group])
+            nbh = [_lib.strided_window_count(w.shape[0], cfg.radius, STEP, hop) for _, w in group]
+            scores = numpy.empty(((K + 1) * sum(nbh), 2), numpy.float32)
+            labels = numpy.empty((K + 1) * sum(nbh), numpy.uint8)
+            try:
+                wo, stats = ctx.eval_cutoff_sweep(model.handle(ctx), flat, dt, offsets, coefs, B, Cn, FFT_PRECISION, cfg.radius, STEP,
+                                                  hop, cut, None, scores, labels, _lib.MEM_HOST)
+            except _lib.F2Error as e:
+                if e.code == _lib.F2_ERR_NONPOSITIVE:
+                    raise ValueError("values must all be positive")
+                raise
+            assert list(numpy.diff(wo)) == nbh * (K + 1)
+            refs = [None] * B
+            if accuracy is not None:     # (the labels of a file whose rate differed count source samples)
+                refs = [ReferenceLabels(file) if sources[file] == framerate else None for file, _ in group]
+            confusions = None
+            if any(ref is not None for ref in refs):
+                confusions = _confusions(ctx, labels, wo, refs, accuracy, hop, STEP)
+            for b, (file, w) in enumerate(group):
+                rows = [l * B + b for l in range(K + 1)]
+                windows = numpy.array([wo[u + 1] - wo[u] for u in rows], numpy.int64)
+                rising, agree = stats[rows, 0].copy(), stats[rows, 1].copy()
+                with numpy.errstate(invalid='ignore', divide='ignore'):
+                    agreement = numpy.where(windows > 0, agree / windows.astype(numpy.float64), numpy.nan)
+                res = dict(cutoff_hz=cut.copy(), windows=windows, rising=rising, agree=agree, agreement=agreement,
+                           hop=numpy.int64(hop), timepoints=_lib.strided_timepoints(w.shape[0], cfg.radius, STEP, hop),
+                           scores=numpy.stack([scores[wo[u]:wo[u + 1]] for u in rows]),
+                           **_rate_keys(resample, framerate, sources[file]))
+                for key, u in zip(keys, rows):
+                    res['labels_' + key] = labels[wo[u]:wo[u + 1]].copy()
+                if refs[b] is not None:
+                    res['confusion'] = confusions[rows].copy()
+                    res['accuracy_vtr'] = _accuracy_of(res['confusion'])
+                out = os.path.splitext(file)[0] + '.lpfsweep.npz'
+                numpy.savez(out, **res)
+                print("File:\t\t{}".format(file))
+                if accuracy is not None and sources[file] != framerate:
+                    _no_rate_accuracy(file, sources[file], framerate)
+                elif accuracy is not None and refs[b] is None:
+                    _no_side_files(file)
+                for l in range(K + 1):
+                    line = "\tcutoff {:>8}\t{} windows\t{} rising\tagreement with nolpf {:.4f}".format(
+                        names[l], windows[l], rising[l], agreement[l])
+                    if refs[b] is not None:
+                        line += "\taccuracy against the VTR labels ({}) {:.4f}".format(accuracy, res['accuracy_vtr'][l])
+                    print(line)
                 print("\t\t{}\tdone ! -> {}".format(file, out))
                 results[file] = res
     return results

@@ -627,6 +627,61 @@ int f2_eval_occlusion_batch(f2_ctx* ctx, const f2_cnn* cnn, const void* wave, in
                             float* scores_or_null /* (n, K+1, 2) */, uint8_t* labels_or_null /* (n, K+1) */,
                             int64_t* window_offsets_or_null /* host, B+1 */, int mem_space);
 
+/* ---- `cnn lpfsweep`: one ragged batch at K envelope cutoffs and unfiltered, in one device pass ------------------------------
+ * The reference low-passes the envelope after the magnitude (EnvelopeExtraction.py:39-67), so the filterbank and the Hilbert
+ * transform do not depend on the cutoff: a sweep needs them once, and one low-pass of envelopes that are already in memory.
+ * (f2_version stays 114 with these two entries: look the symbols up to find out whether a build has them.)
+ *
+ * f2_lowpass_levels: env holds the ragged float64 envelopes of a batch as f2_envelope_batch delivers them - (C, n_b) blocks,
+ * utterance b at C * offsets[b]. levels receives K+1 "levels" of it, level-major, (K+1) * C * offsets[B] doubles: level l < K is
+ * every row filtered with butter(1, cutoff_hz[l] / 8000), level K the input copied bit for bit (the reference's "NOLPF"). Level
+ * l, utterance b is utterance u = l*B + b of a (K+1)*B batch whose offsets are the clean offsets tiled:
+ * tiled[u] = l*offsets[B] + offsets[b] (the convention of f2_eval_noise_sweep).
+ *   coefficients   k = tan(pi * cutoff / 16000), b0 = k / (1 + k), a1 = (k - 1) / (k + 1): the host's tan(), float64. 8000 is
+ *                  hard-coded as in the reference and in f2_envelope_batch, whatever the framerate.
+ *   recurrence     y[n] = b0 * (x[n] + x[n-1]) - a1 * y[n-1], every row from zero state, everything in float64. A row is one
+ *                  (utterance, channel) pair; state never crosses a row or an utterance boundary. The input is any finite
+ *                  float64: the filter is linear and nothing assumes positive data.
+ *   formulation    s[n] = q * s[n-1] + x[n] with q = -a1, y[n] = b0 * (s[n] + s[n-1]). One workgroup walks a row in segments of
+ *                  4096 samples; inside a segment a lane folds its pairs of samples, a weighted scan (powers of q formed in
+ *                  float64) runs across the wave, the wave totals are chained through LDS, and s at the end of the segment
+ *                  enters the next one. The segmentation is a function of the row length alone and every sum has a fixed order
+ *                  (no floating-point atomics): the bits of a filtered row depend on its samples and its cutoff only - not on
+ *                  B, on the row's place in the batch, on K or on the other cutoffs. Rows of any length, 0 and 1 included.
+ *   memory         every input sample is read once for all K cutoffs; the K filters and the copy are produced from the same
+ *                  registers. Loads and stores are 16 bytes wide whatever the parity of the row start (dword-aligned wide
+ *                  accesses); only the last sample of an odd tail moves alone.
+ * F2_ERR_INVALID, with nothing launched and levels untouched: a NULL ctx or offsets; offsets that do not start at 0 or that
+ * decrease; B < 0; C <= 0; K < 1; a NULL cutoff_hz; a cutoff that is not finite or outside (0, 8000); NULL env or levels with
+ * offsets[B] > 0; a mem_space other than F2_MEM_HOST / F2_MEM_DEVICE. F2_ERR_UNSUPPORTED, likewise: K > 64. B == 0 or
+ * offsets[B] == 0: F2_OK.
+ *
+ * f2_eval_cutoff_sweep: filterbank + envelope of the batch once (unfiltered, the two kernels of the eval calls), f2_lowpass_levels'
+ * kernel on the result, then the window stage and the network of f2_eval_batch_strided over the (K+1)*B batch of envelopes,
+ * and the tally of f2_eval_noise_sweep. Only the int16 / float64 samples go up; one wait at the end. Every output is optional.
+ *   env_levels_or_null   (K+1) * C * offsets[B] float64, level-major, in mem_space (a device buffer serves as the call's own
+ *           buffer; otherwise the levels live in context scratch). Bit for bit f2_lowpass_levels of its own level K block.
+ *   scores_or_null, labels_or_null, window_offsets_or_null (host, (K+1)*B + 1)
+ *           Level K: bit for bit what f2_eval_batch_strided(lpf = 0) returns for the batch. Level l: bit for bit f2_cnn_forward
+ *           of the windows f2_gather_windows(normalize = 1) takes from level l's envelopes at centres radius*step + j*hop.
+ *   stats_or_null   host, (K+1)*B*2: stats[2u] = windows of u labelled rising, stats[2u+1] = windows of u whose label equals
+ *           the unfiltered level's label for the same window of the same utterance (for level K: its window count).
+ * Errors, all before anything is launched or written: everything f2_eval_batch_strided rejects; K < 1, a NULL cutoff_hz, a
+ * cutoff that is not finite or outside (0, 8000): F2_ERR_INVALID; K > 64, or (K+1)*B beyond what f2_eval_noise_sweep accepts:
+ * F2_ERR_UNSUPPORTED. F2_ERR_NONPOSITIVE as in the strided call: a cutoff above 4 kHz has q < 0 and can produce values <= 0,
+ * exactly as lpf = 1 does there. B == 0, or no utterance long enough for a window: F2_OK with window_offsets / stats filled.
+ */
+int f2_lowpass_levels(f2_ctx* ctx, const double* env /* ragged (C, n_b) blocks, mem_space */, const int64_t* offsets /* host, B+1 */,
+                      int B, int C, const double* cutoff_hz /* host, K */, int K,
+                      double* levels /* (K+1) * C * offsets[B], level-major, mem_space */, int mem_space);
+int f2_eval_cutoff_sweep(f2_ctx* ctx, const f2_cnn* cnn, const void* wave, int wave_dtype, const int64_t* offsets,
+                         const double* coefs, int B, int C, int fft_precision, int radius, int step, int hop,
+                         const double* cutoff_hz /* host, K */, int K,
+                         double* env_levels_or_null /* (K+1) * C * offsets[B], mem_space */,
+                         float* scores_or_null, uint8_t* labels_or_null,
+                         int64_t* window_offsets_or_null /* host, (K+1)*B + 1 */,
+                         int64_t* stats_or_null /* host, (K+1)*B*2 */, int mem_space);
+
 #ifdef __cplusplus
 }
 #endif
