@@ -19,6 +19,9 @@ WAVE_I16, WAVE_F64 = 0, 1
 FFT_F32, FFT_F64 = 0, 1
 PCM_U8, PCM_I16, PCM_I32, PCM_F32, PCM_F64 = 0, 1, 2, 3, 4
 K_COUNT = 7
+# tile constants of k_reverb_levels (csrc/f2_internal.h: F2_REVERB_BLOCK outputs per workgroup, F2_REVERB_TAP_CHUNK taps per staged
+# span) and the longest impulse response f2_reverb_levels takes (F2_REVERB_MAX_TAPS)
+REVERB_BLOCK, REVERB_TAP_CHUNK, REVERB_MAX_TAPS = 1024, 1024, 32768
 
 _vp, _i, _i64, _d = C.c_void_p, C.c_int, C.c_int64, C.c_double
 _P = C.POINTER
@@ -80,6 +83,9 @@ SIGNATURES = {
                                      _vp, _vp, _vp, _vp, _vp, _vp, _i]),
     "f2_lowpass_levels": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _vp, _i]),
     "f2_eval_cutoff_sweep": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i]),
+    "f2_reverb_levels": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _i]),
+    "f2_eval_reverb_sweep": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _d, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp,
+                                  _i]),
 }
 
 _lib = None
@@ -440,6 +446,38 @@ class Context:
                                                  mem_space))
         return window_offsets, stats
 
+    def reverb_levels(self, wave, wave_dtype, offsets, B, rirs, levels, mem_space):
+        """The batch convolved with every impulse response of `rirs` (a sequence of 1-D float64 arrays) and dry, in one device
+        pass (see f2_reverb_levels): levels receives (K+1) * offsets[B] float64, level-major, the dry level last (wave and levels
+        numpy arrays or device pointers, by mem_space; the responses always host arrays)."""
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        taps, rir_offsets = _pack_rirs(rirs)
+        self.check(self.lib.f2_reverb_levels(self.handle, _ptr(wave), wave_dtype, _ptr(offsets), int(B), _ptr(taps) if len(taps) else None,
+                                             _ptr(rir_offsets), len(rir_offsets) - 1, _ptr(levels), mem_space))
+
+    def eval_reverb_sweep(self, handle, wave, wave_dtype, offsets, coefs, B, Cn, lpf, cutoff, precision, radius, step, hop, rirs,
+                          wet, scores, labels, mem_space, window_offsets=None, stats=None):
+        """The batch at every impulse response of `rirs` and dry, in one device pass (see f2_eval_reverb_sweep): utterance
+        l * B + b of the evaluated batch is utterance b at level l, the dry level last. wet / scores / labels (numpy arrays or
+        device pointers, by mem_space) may be None. Returns (window_offsets ((K+1)*B + 1, int64), stats ((K+1)*B, 2) int64: rising
+        windows, windows labelled as the dry level labels them), allocating those it is not given."""
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        taps, rir_offsets = _pack_rirs(rirs)
+        K = len(rir_offsets) - 1
+        U = (K + 1) * int(B)
+        if window_offsets is None:
+            window_offsets = np.zeros(U + 1, np.int64)
+        if stats is None:
+            stats = np.zeros((U, 2), np.int64)
+        for a, n in ((window_offsets, U + 1), (stats, 2 * U)):
+            if a.dtype != np.int64 or a.size != n or not a.flags["C_CONTIGUOUS"]:
+                raise ValueError("window_offsets / stats must be contiguous int64 (K+1)*B + 1 / ((K+1)*B, 2)")
+        self.check(self.lib.f2_eval_reverb_sweep(self.handle, handle, _ptr(wave), wave_dtype, _ptr(offsets), _ptr(coefs), int(B), Cn,
+                                                 int(bool(lpf)), float(cutoff), precision, radius, step, int(hop),
+                                                 _ptr(taps) if len(taps) else None, _ptr(rir_offsets), K, _ptr(wet), _ptr(scores),
+                                                 _ptr(labels), _ptr(window_offsets), _ptr(stats), mem_space))
+        return window_offsets, stats
+
     def label_accuracy(self, labels, window_offsets, ref_offsets, ref_timepoints, ref_signs, origin, hop, step, mem_space,
                        counts=None):
         """The labels of a strided evaluation against reference labels (see f2_label_accuracy): utterance u owns rows
@@ -625,6 +663,15 @@ class Context:
                                               int(B), int(up), int(down), _ptr(taps), int(half_len), _ptr(out), _ptr(out_offsets),
                                               mem_space))
         return out_offsets
+
+
+def _pack_rirs(rirs):
+    """(taps, rir_offsets) of f2_reverb_levels: the responses one after the other as float64, and their K + 1 offsets"""
+    rirs = [np.ascontiguousarray(h, dtype=np.float64).reshape(-1) for h in rirs]
+    rir_offsets = np.zeros(len(rirs) + 1, np.int64)
+    rir_offsets[1:] = np.cumsum([len(h) for h in rirs])
+    taps = np.concatenate(rirs) if rirs else np.zeros(0, np.float64)
+    return np.ascontiguousarray(taps), rir_offsets
 
 
 def resampled_length(n, up, down):

@@ -27,6 +27,13 @@ package implements:
                                                              filterbank and Hilbert envelope run once - agreement with the
                                                              unfiltered decisions per cutoff, written to <base>.lpfsweep.npz; takes
                                                              no --lpf, --figure or --occlusion; not in the reference)
+    python -m f2cnn_amd cnn reverbsweep --file/-f WAV --t60 0.2,0.4,0.8 [--rir room.wav[,hall.wav]] [--drr DB] [--seed N] [--save-wavs] [--hop N|frame] [--lpf HZ] [--accuracy [MODE]] [--resample] [--model/-m NPZ]
+                                                            (the file in every room and dry in one device pass - synthetic
+                                                             responses of the given reverberation times in seconds, direct-to-
+                                                             reverberant ratio DB (default 0), and / or measured ones from mono
+                                                             WAV files at the file's rate - agreement with the dry decisions per
+                                                             level, written to OutputWavFiles/reverb/<stem>.reverbsweep.npz; takes
+                                                             no --figure or --occlusion; not in the reference)
     python -m f2cnn_amd cnn evalrand [--count/-c N] [--lpf HZ] [--model/-m NPZ] [--hop N|frame]
     (--hop: a decision every N samples instead of every sample, `frame` = one per STEP of configF2CNN.conf; not in the reference)
     (eval / evalnoise / evalrand / noisesweep also take --accuracy [reference|centre]: the decisions against the labels of the
@@ -60,7 +67,7 @@ organize needs the licensed TIMIT+VTR corpora and stays with the reference.
 import argparse
 
 PREPARE = ("filter", "envelope", "label", "input", "features")
-CNN = ("train", "test", "eval", "evalnoise", "evalrand", "noisesweep", "lpfsweep")
+CNN = ("train", "test", "eval", "evalnoise", "evalrand", "noisesweep", "lpfsweep", "reverbsweep")
 PLOT = ("gtg",)
 
 
@@ -101,6 +108,38 @@ def cutoffs_argument(text):
     return cutoffs
 
 
+def t60_argument(text):
+    """--t60: a comma-separated list of at least one finite, positive reverberation time in seconds"""
+    import math
+    try:
+        t60s = [float(part) for part in text.split(',')]
+    except ValueError:
+        t60s = []
+    if not t60s or not all(math.isfinite(v) and v > 0 for v in t60s):
+        raise argparse.ArgumentTypeError("--t60 takes a comma-separated list of positive reverberation times in seconds, not {!r}".format(text))
+    return t60s
+
+
+def rir_argument(text):
+    """--rir: a comma-separated list of at least one impulse response file"""
+    files = text.split(',')
+    if not all(files):
+        raise argparse.ArgumentTypeError("--rir takes a comma-separated list of WAV files, not {!r}".format(text))
+    return files
+
+
+def drr_argument(text):
+    """--drr: a finite direct-to-reverberant ratio in dB"""
+    import math
+    try:
+        drr = float(text)
+    except ValueError:
+        drr = math.nan
+    if not math.isfinite(drr):
+        raise argparse.ArgumentTypeError("--drr takes a direct-to-reverberant ratio in dB, not {!r}".format(text))
+    return drr
+
+
 def build_parser():
     parser = argparse.ArgumentParser(prog="f2cnn_amd", description="F2CNN hot path on MI355X.")
     parser.add_argument('--configure', action='store_true', help='write configF2CNN.conf with default values')
@@ -137,6 +176,13 @@ def build_parser():
     # (absent from the parsed arguments unless given: the commands parse as before without it)
     c.add_argument('--cutoffs', action='store', type=cutoffs_argument, dest='cutoffs', default=argparse.SUPPRESS,
                    help="lpfsweep: comma-separated envelope cutoffs in Hz, e.g. 5,10,20,50,100")
+    # (absent from the parsed arguments unless given: the commands parse as before without them)
+    c.add_argument('--t60', action='store', type=t60_argument, dest='t60', default=argparse.SUPPRESS,
+                   help="reverbsweep: comma-separated reverberation times in seconds, e.g. 0.2,0.4,0.8")
+    c.add_argument('--rir', action='store', type=rir_argument, dest='rir', default=argparse.SUPPRESS,
+                   help="reverbsweep: comma-separated mono WAV files with measured impulse responses at the file's rate")
+    c.add_argument('--drr', action='store', type=drr_argument, dest='drr', default=argparse.SUPPRESS,
+                   help="reverbsweep: direct-to-reverberant ratio of the synthetic responses in dB (default 0)")
     c.add_argument('--seed', action='store', type=int, dest='seed', help="noisesweep: seed of the noise (default 0)")
     c.add_argument('--save-wavs', action='store_true', dest='save_wavs',
                    help="noisesweep: also write the noisy WAV files, as evalnoise does")
@@ -275,6 +321,13 @@ def main(argv=None):
             if 'occlusion' in args:
                 print("--occlusion is not supported by lpfsweep (use eval --lpf HZ --occlusion for one cutoff)")
                 return 1
+        if args.cnn_command == 'reverbsweep':
+            if getattr(args, 'figure', False):
+                print("--figure is not supported by reverbsweep (use eval --figure on a WAV written with --save-wavs)")
+                return 1
+            if 'occlusion' in args:
+                print("--occlusion is not supported by reverbsweep (use eval --occlusion on a WAV written with --save-wavs)")
+                return 1
         if args.CUTOFF is not None:                            # f2cnn.py:149-151
             kwargs['LPF'] = True
             kwargs['CUTOFF'] = args.CUTOFF
@@ -330,6 +383,14 @@ def main(argv=None):
                 print("Please use --cutoffs to give the envelope cutoffs in Hz, e.g. --cutoffs 5,10,20,50,100")
                 return 1
             Evaluating.EvaluateCutoffSweep([args.file], args.cutoffs, **kwargs)
+            return 0
+        if args.cnn_command == 'reverbsweep':
+            if 't60' not in args and 'rir' not in args:
+                print("Please use --t60 to give the reverberation times in seconds, e.g. --t60 0.2,0.4,0.8, or --rir to give "
+                      "impulse response files")
+                return 1
+            Evaluating.EvaluateReverbSweep([args.file], t60s=getattr(args, 't60', ()), rirs=getattr(args, 'rir', ()),
+                                           drr_db=getattr(args, 'drr', 0.0), seed=args.seed or 0, save_wavs=args.save_wavs, **kwargs)
             return 0
         kwargs['file'] = args.file
         if args.cnn_command == 'evalnoise':

@@ -58,8 +58,9 @@ struct f2_ctx {
     f2_scratch dense_in;   // conv4 outputs (+ dense1 outputs) of the windows of several utterances: one dense launch for all
     f2_scratch noise_wave; // f2_eval_noise_sweep: the (K+1) x batch float64 waveform when the caller gives no device buffer for it
     f2_scratch lp_levels;  // f2_lowpass_levels / f2_eval_cutoff_sweep: the (K+1) x batch envelopes when the caller gives no device buffer
+    f2_scratch reverb_wave; // f2_reverb_levels / f2_eval_reverb_sweep: the (K+1) x batch float64 waveform when the caller gives no device buffer
     // The small arrays of the call in flight (f2_meta_carve): sigma / stats / window offsets of the noise sweep, filter coefficients /
-    // stats / window offsets of the cutoff sweep, counts and reference
+    // stats / window offsets of the cutoff sweep, taps / tile sums / stats / window offsets of the reverberation sweep, counts and reference
     // labels of f2_label_accuracy, counts / loss sums / loss partials of f2_cnn_score_windows, span records and range words of the
     // pictures, utterance records of f2_resample_batch. One area for all of them, which holds while
     //  - nothing cached lives here: what a later call may find unchanged (spec_meta, rs_tab, offsets, coefs) has its own area;
@@ -502,6 +503,26 @@ int f2_check_cutoffs(f2_ctx* ctx, const double* cutoff_hz, int K);
 int f2_upload_lowpass_coefs(f2_ctx* ctx, const double* cutoff_hz, int K, double* d_coef);
 int f2_launch_lowpass_levels(f2_ctx* ctx, const double* d_env, const int64_t* d_offsets, int B, int C, int64_t total,
                              const double* d_coef, int K, double* d_levels);
+// f2_reverb.hip, the kernel of f2_reverb_levels / f2_eval_reverb_sweep. A workgroup of k_reverb_levels makes F2_REVERB_BLOCK
+// consecutive outputs of one utterance at one level and walks the taps in chunks of F2_REVERB_TAP_CHUNK (the input span of a chunk,
+// F2_REVERB_BLOCK + F2_REVERB_TAP_CHUNK float64 samples, is what it stages in LDS).
+// f2_check_rir: K in 1 .. F2_REVERB_MAX_LEVELS, rir / rir_offsets non-NULL, rir_offsets from 0 and non-decreasing, every response of
+// 1 .. F2_REVERB_MAX_TAPS finite taps (F2_ERR_INVALID; too many levels or taps: F2_ERR_UNSUPPORTED). f2_reverb_meta names the
+// device arrays of a launch in the call's f2_meta_carve (before its reserve()); the launch uploads them (tile sums, rir_offsets and
+// taps, all from host memory), reads the B utterances of d_wave once per level and writes (K + 1) * h_offsets[B] doubles,
+// level-major, level K the dry samples.
+#define F2_REVERB_BLOCK 1024
+#define F2_REVERB_TAP_CHUNK 1024
+#define F2_REVERB_MAX_TAPS 32768
+#define F2_REVERB_MAX_LEVELS 64
+struct f2_reverb_arrays {
+    int64_t *d_first = nullptr, *d_rir_off = nullptr;   // B + 1 running sums of the utterances' tiles; K + 1 tap offsets
+    double* d_rir = nullptr;                            // rir_offsets[K] taps
+};
+int f2_check_rir(f2_ctx* ctx, const double* rir, const int64_t* rir_offsets, int K);
+void f2_reverb_meta(f2_meta_carve* meta, int B, const int64_t* rir_offsets, int K, f2_reverb_arrays* A);
+int f2_launch_reverb_levels(f2_ctx* ctx, const void* d_wave, int wave_dtype, const int64_t* d_offsets, const int64_t* h_offsets, int B,
+                            const double* rir, const int64_t* rir_offsets, int K, const f2_reverb_arrays& A, double* d_out);
 // f2_accuracy.hip, the kernel of f2_label_accuracy. d_counts (4 per utterance, zeroed by the caller)[4 u + 2 ref + pred] += rows
 // of utterance u (rows d_window_offsets[u] .. [u + 1] of d_labels, row j at sample origin + j * hop) that the rule of the header
 // counts against reference set u % R (d_ref_offsets: R + 1; timepoints strictly increasing inside a set, signs 0 / 1);

@@ -474,6 +474,74 @@ int f2_eval_noise_sweep(f2_ctx* ctx, const f2_cnn* cnn, const void* wave, int wa
     return F2_OK;
 }
 
+// f2_eval_reverb_sweep: f2_eval_noise_sweep with k_reverb_levels (f2_reverb.hip) in the place of the two noise kernels: the K wet
+// levels and the dry one as ONE (K+1) * B-utterance float64 batch in device memory, through f2_eval_batch_strided as a device call,
+// then the tally of its labels against the dry level. Only the dry samples and the taps go up; one wait at the end.
+int f2_eval_reverb_sweep(f2_ctx* ctx, const f2_cnn* cnn, const void* wave, int wave_dtype, const int64_t* offsets,
+                         const double* coefs, int B, int C, int lpf, double cutoff_hz, int fft_precision, int radius, int step,
+                         int hop, const double* rir, const int64_t* rir_offsets, int K, double* wet_or_null, float* scores_or_null,
+                         uint8_t* labels_or_null, int64_t* window_offsets_or_null, int64_t* stats_or_null, int mem_space) {
+    const f2_batch X = {wave, wave_dtype, offsets, coefs, B, C, lpf, cutoff_hz, fft_precision, mem_space};
+    eval_call E;
+    F2_TRY(eval_check(ctx, cnn, X, radius, step, &E));
+    F2_CHECK(ctx, hop >= 1, F2_ERR_INVALID, "hop must be at least 1 sample (got %d)", hop);
+    F2_TRY(f2_check_rir(ctx, rir, rir_offsets, K));
+    F2_CHECK(ctx, ((int64_t)K + 1) * (B > 0 ? B : 1) <= INT32_MAX / 2, F2_ERR_UNSUPPORTED, "%d levels of %d utterances", K + 1, B);
+    const int64_t total = X.total();
+    F2_CHECK(ctx, wave || total == 0, F2_ERR_INVALID, "null wave");
+    const int U = (K + 1) * B;
+    // the (K+1) * B batch: the dry offsets tiled, its window offsets
+    std::vector<int64_t> tiled((size_t)U + 1, 0), wo((size_t)U + 1, 0);
+    int64_t max_windows = 0;
+    for (int l = 0; l <= K; ++l)
+        for (int b = 0; b < B; ++b) {
+            const size_t u = (size_t)l * B + b;
+            const int64_t nw = strided_windows(offsets[b + 1] - offsets[b], E.R, step, hop);
+            tiled[u + 1] = (int64_t)l * total + offsets[b + 1];
+            wo[u + 1] = wo[u] + nw;
+            max_windows = nw > max_windows ? nw : max_windows;
+        }
+    const int64_t n_total = wo[(size_t)U];
+    if (window_offsets_or_null) memcpy(window_offsets_or_null, wo.data(), sizeof(int64_t) * ((size_t)U + 1));
+    if (total == 0) {   // nothing to launch: no sample and no window anywhere
+        if (stats_or_null) std::fill(stats_or_null, stats_or_null + 2 * (size_t)U, (int64_t)0);
+        return F2_OK;
+    }
+
+    // small arrays of the call, held across the nested evaluation (which does not touch ctx->meta)
+    f2_reverb_arrays A;
+    int64_t *d_stats, *d_wo;
+    f2_meta_carve meta;
+    f2_reverb_meta(&meta, B, rir_offsets, K, &A);
+    meta.add(&d_stats, 2 * (size_t)U), meta.add(&d_wo, (size_t)U + 1);
+    F2_TRY(meta.reserve(ctx));
+    f2_output wet;
+    F2_TRY(f2_place(ctx, ctx->reverb_wave, wet_or_null, sizeof(double) * (size_t)(K + 1) * (size_t)total, mem_space, true, &wet));
+    // scores / labels of the device call below (the tally always needs the labels), in stage_aux as in the noise sweep
+    f2_score_outputs out;
+    F2_TRY(f2_place_scores(ctx, scores_or_null, labels_or_null, n_total, mem_space, false, true, 0, &out));
+    // the tiled offsets start with the dry ones: one device array serves the reverberation kernel and the evaluation
+    F2_TRY(f2_upload_offsets(ctx, tiled.data(), U));
+    const void* d_wave;
+    F2_TRY(f2_stage_wave(ctx, wave, wave_dtype, total, mem_space, &d_wave));
+    F2_TRY(f2_launch_reverb_levels(ctx, d_wave, wave_dtype, (const int64_t*)ctx->offsets.ptr, offsets, B, rir, rir_offsets, K, A,
+                                   wet.as<double>()));
+    F2_TRY(f2_copy_back(ctx, wet));
+    F2_TRY(f2_eval_batch_strided(ctx, cnn, wet.dev, F2_WAVE_F64, tiled.data(), coefs, U, C, lpf, cutoff_hz, fft_precision, radius, step,
+                                 hop, out.scores.as<float>(), out.labels.as<uint8_t>(), nullptr, F2_MEM_DEVICE));
+    F2_HIP(ctx, hipMemsetAsync(d_stats, 0, sizeof(int64_t) * 2 * (size_t)U, ctx->stream));
+    if (n_total > 0) {
+        F2_TRY(f2_upload_async(ctx, d_wo, wo.data(), sizeof(int64_t) * ((size_t)U + 1)));
+        F2_TRY(f2_launch_label_tally(ctx, out.labels.as<uint8_t>(), d_wo, B, K, max_windows, d_stats));
+        F2_TRY(f2_copy_back(ctx, out.scores));
+        F2_TRY(f2_copy_back(ctx, out.labels));
+    }
+    if (stats_or_null)
+        F2_HIP(ctx, hipMemcpyAsync(stats_or_null, d_stats, sizeof(int64_t) * 2 * (size_t)U, hipMemcpyDeviceToHost, ctx->stream));
+    F2_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return F2_OK;
+}
+
 // f2_eval_cutoff_sweep: filterbank + envelope of the batch once, unfiltered; its K low-passed levels and the copy as ONE
 // (K+1) * B-utterance batch of envelopes (f2_lowpass.hip); the window loop of f2_eval_batch_strided over that batch with the tiled
 // offsets; the tally of its labels against the unfiltered level. One wait at the end (eval_cnn_end).

@@ -46,7 +46,13 @@ With ``accuracy=`` a file whose rate differed gets no accuracy: the timepoints o
 ``EvaluateCutoffSweep`` (``cnn lpfsweep --file X.WAV --cutoffs 5,10,20,50,100``; not in the reference, whose route is one ``cnn eval
 --lpf HZ`` per cutoff) evaluates a file at every envelope cutoff and unfiltered in one device pass (``f2_eval_cutoff_sweep``): the
 filterbank and the Hilbert envelope run once, the low-pass of ``EnvelopeExtraction.py:39-67`` K times on the result, and
-``<base>.lpfsweep.npz`` holds the decisions of every level and their agreement with the unfiltered ones."""
+``<base>.lpfsweep.npz`` holds the decisions of every level and their agreement with the unfiltered ones.
+
+``EvaluateReverbSweep`` (``cnn reverbsweep --file X.WAV --t60 0.2,0.4,0.8 [--rir room.wav]``; not in the reference) evaluates a file
+convolved with every room impulse response - synthetic ones of the given reverberation times and / or measured ones
+(``f2cnn_amd/reverb.py``) - and dry in one device pass (``f2_eval_reverb_sweep``: the convolution runs on the device, in float64),
+and ``OutputWavFiles/reverb/<stem>.reverbsweep.npz`` holds the decisions of every level, their agreement with the dry ones and the
+responses that were used."""
 import os
 
 import numpy
@@ -922,6 +928,150 @@ def EvaluateCutoffSweep(files, cutoffs, hop=None, model='last_trained_model', ct
                     if refs[b] is not None:
                         line += "\taccuracy against the VTR labels ({}) {:.4f}".format(accuracy, res['accuracy_vtr'][l])
                     print(line)
+                print("\t\t{}\tdone ! -> {}".format(file, out))
+                results[file] = res
+    return results
+
+
+# ---- `cnn reverbsweep`: one file at several reverberation times (the room axis; not in the reference, whose only route is a
+# host convolution, a WAV per room and one `cnn eval` per WAV) ---------------------------------------------------------------
+def _t60_text(t60):
+    """how a level is printed and named: 0.4 -> '0.4', 1.0 -> '1'"""
+    return '{:g}'.format(float(t60))
+
+
+def _reverb_copy_paths(file, name):
+    """Where `cnn reverbsweep` puts its outputs: OutputWavFiles/reverb/<stem><name>.*"""
+    stem = os.path.basename(os.path.splitext(file)[0])
+    return os.path.splitext(file)[0], os.path.join('OutputWavFiles', 'reverb', stem + name)
+
+
+def EvaluateReverbSweep(files, t60s=(), rirs=(), drr_db=0.0, seed=0, hop=None, LPF=False, CUTOFF=50, model='last_trained_model',
+                        save_wavs=False, ctx=None, accuracy=None, resample=False):
+    """`cnn reverbsweep`: every file convolved with every impulse response and dry in one device pass per group of files
+    (f2_eval_reverb_sweep: the causal convolution truncated to the file's own length, in float64, so a level keeps the window
+    count and the time axis of the dry one), with the dry run of the same network as the referee. The levels are the t60s
+    (seconds) in the order given - synthetic responses, reverb.SyntheticRIR(t60, framerate, drr_db, seed, level) - then the
+    measured responses of the WAV files `rirs` (reverb.LoadRIR), then `dry`; the responses are built once per framerate. Per
+    file, OutputWavFiles/reverb/<stem>.reverbsweep.npz holds t60, rir_files, drr_db, seed, taps, windows, rising, agree,
+    agreement (= agree / windows, NaN without windows) - windows ... agreement with one entry per level, the dry level last - hop,
+    labels_<k> for level k (labels_dry for the dry one) and rir_<k>, the response level k was made with (NumPy does not promise
+    standard_normal's stream across versions); one line per level is printed and the same data is returned as a dict per file.
+    save_wavs also writes <stem>_T60_<value>s.WAV (or <stem>_<rir stem>.WAV) with copies of the annotation files. Files are
+    grouped like EvaluateNoiseSweep groups them: one framerate and sample type per call, 16 files per pass. hop=None is hop 1.
+    accuracy= and resample= as in EvaluateNoiseSweep: confusion (K+1, 2, 2) and accuracy_vtr (K+1) per file that has its .FB /
+    .PHN, framerate and source_framerate. The arguments are checked before any file is read."""
+    import shutil
+    from scipy.io import wavfile
+    from ... import reverb
+    if isinstance(files, (str, bytes, os.PathLike)):
+        files = [files]
+    if isinstance(rirs, (str, bytes, os.PathLike)):
+        rirs = [rirs]
+    t60 = numpy.asarray(t60s, dtype=numpy.float64).reshape(-1)
+    rir_files = [os.fspath(r) for r in rirs]
+    if not numpy.isfinite(t60).all() or (t60 <= 0).any():
+        raise ValueError("a reverberation time must be finite and positive (seconds)")
+    K = len(t60) + len(rir_files)
+    if K < 1:
+        raise ValueError("a reverberation sweep needs at least one reverberation time or impulse response file")
+    if K > 64:
+        raise ValueError("a reverberation sweep takes at most 64 levels, not {}".format(K))
+    drr_db = float(drr_db)
+    if not numpy.isfinite(drr_db):
+        raise ValueError("drr_db must be finite")
+    hop = 1 if hop is None else int(hop)
+    if accuracy is not None:
+        _accuracy_origin(accuracy, 0, 0)
+    ctx = ctx or _lib.default_context()
+    cfg = F2Config()
+    if not isinstance(model, F2CNNModel):
+        model = load_model(model)
+    read = _load(files, resample)
+    sources = {file: source for file, (source, _, _) in zip(files, read)}
+    groups = {}
+    for file, (_, framerate, wavArray) in zip(files, read):
+        wave, dt = filters._wave_args(wavArray)
+        groups.setdefault((framerate, dt), []).append((file, wave))
+    keys = [str(k) for k in range(K)] + ['dry']             # labels_<k> / rir_<k>: level k
+    names = ['T60 ' + _t60_text(v) + 's' for v in t60] + [os.path.basename(r) for r in rir_files] + ['dry']
+    suffixes = ['_T60_' + _t60_text(v) + 's' for v in t60] + ['_' + os.path.splitext(os.path.basename(r))[0] for r in rir_files]
+    results = {}
+    responses = {}                                # per framerate
+    BATCH = 16                                    # files per device pass, as EvaluateNoiseSweep
+    for (framerate, dt), members in groups.items():
+        if framerate not in responses:
+            responses[framerate] = [reverb.SyntheticRIR(v, framerate, drr_db, seed, level) for level, v in enumerate(t60)] + \
+                                   [reverb.LoadRIR(r, framerate) for r in rir_files]
+        hs = responses[framerate]
+        taps = numpy.array([len(h) for h in hs], numpy.int64)
+        coefs = numpy.ascontiguousarray(filters.make_erb_filters(framerate, filters.centre_freqs(framerate, cfg.nchannels,
+                                                                                                  cfg.low_freq)))
+        Cn = coefs.shape[0]
+        STEP = _step(framerate, cfg)
+        for s0 in range(0, len(members), BATCH):
+            group = members[s0:s0 + BATCH]
+            B = len(group)
+            offsets = numpy.zeros(B + 1, numpy.int64)
+            offsets[1:] = numpy.cumsum([w.shape[0] for _, w in group])
+            flat = numpy.concatenate([w for _, w in group])
+            nbh = [_lib.strided_window_count(w.shape[0], cfg.radius, STEP, hop) for _, w in group]
+            labels = numpy.empty((K + 1) * sum(nbh), numpy.uint8)
+            wet = numpy.empty((K + 1) * int(offsets[-1]), numpy.float64) if save_wavs else None
+            try:
+                wo, stats = ctx.eval_reverb_sweep(model.handle(ctx), flat, dt, offsets, coefs, B, Cn, bool(LPF),
+                                                  CUTOFF if LPF else 0.0, FFT_PRECISION, cfg.radius, STEP, hop, hs, wet, None,
+                                                  labels, _lib.MEM_HOST)
+            except _lib.F2Error as e:
+                if e.code == _lib.F2_ERR_NONPOSITIVE:
+                    raise ValueError("values must all be positive")
+                raise
+            assert list(numpy.diff(wo)) == nbh * (K + 1)
+            refs = [None] * B
+            if accuracy is not None:     # (the labels of a file whose rate differed count source samples)
+                refs = [ReferenceLabels(file) if sources[file] == framerate else None for file, _ in group]
+            confusions = None
+            if any(ref is not None for ref in refs):
+                confusions = _confusions(ctx, labels, wo, refs, accuracy, hop, STEP)
+            os.makedirs(os.path.join('OutputWavFiles', 'reverb'), exist_ok=True)
+            for b, (file, w) in enumerate(group):
+                rows = [l * B + b for l in range(K + 1)]
+                windows = numpy.array([wo[u + 1] - wo[u] for u in rows], numpy.int64)
+                rising, agree = stats[rows, 0].copy(), stats[rows, 1].copy()
+                with numpy.errstate(invalid='ignore', divide='ignore'):
+                    agreement = numpy.where(windows > 0, agree / windows.astype(numpy.float64), numpy.nan)
+                res = dict(t60=t60.copy(), rir_files=numpy.array(rir_files, dtype=str), drr_db=numpy.float64(drr_db),
+                           seed=numpy.int64(seed), taps=taps.copy(), windows=windows, rising=rising, agree=agree,
+                           agreement=agreement, hop=numpy.int64(hop), **_rate_keys(resample, framerate, sources[file]))
+                for key, u in zip(keys, rows):
+                    res['labels_' + key] = labels[wo[u]:wo[u + 1]].copy()
+                for k, h in enumerate(hs):
+                    res['rir_' + str(k)] = h.copy()
+                if refs[b] is not None:
+                    res['confusion'] = confusions[rows].copy()
+                    res['accuracy_vtr'] = _accuracy_of(res['confusion'])
+                source, target = _reverb_copy_paths(file, '')
+                out = target + '.reverbsweep.npz'
+                numpy.savez(out, **res)
+                print("File:\t\t{}".format(file))
+                if accuracy is not None and sources[file] != framerate:
+                    _no_rate_accuracy(file, sources[file], framerate)
+                elif accuracy is not None and refs[b] is None:
+                    _no_side_files(file)
+                for l in range(K + 1):
+                    line = "\t{:>12}\t{} windows\t{} rising\tagreement with dry {:.4f}".format(
+                        names[l], windows[l], rising[l], agreement[l])
+                    if refs[b] is not None:
+                        line += "\taccuracy against the VTR labels ({}) {:.4f}".format(accuracy, res['accuracy_vtr'][l])
+                    print(line)
+                if save_wavs:
+                    for l in range(K):
+                        _, target = _reverb_copy_paths(file, suffixes[l])
+                        lo = l * int(offsets[-1]) + int(offsets[b])
+                        wavfile.write(target + '.WAV', framerate, wet[lo:lo + w.shape[0]])
+                        for ext in ('.FB', '.PHN', '.WRD'):
+                            if os.path.exists(source + ext):
+                                shutil.copyfile(source + ext, target + ext)
                 print("\t\t{}\tdone ! -> {}".format(file, out))
                 results[file] = res
     return results

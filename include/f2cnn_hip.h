@@ -682,6 +682,64 @@ int f2_eval_cutoff_sweep(f2_ctx* ctx, const f2_cnn* cnn, const void* wave, int w
                          int64_t* window_offsets_or_null /* host, (K+1)*B + 1 */,
                          int64_t* stats_or_null /* host, (K+1)*B*2 */, int mem_space);
 
+/* ---- `cnn reverbsweep`: one ragged batch at K impulse responses and dry, in one device pass ---------------------------------
+ * Reverberation acts on the waveform, before the filterbank. (f2_version stays 114 with these two entries: look the symbols up
+ * to find out whether a build has them.)
+ *
+ * f2_reverb_levels: for utterance b (n_b samples, int16 or float64) and level l < K with impulse response h_l (T_l =
+ * rir_offsets[l+1] - rir_offsets[l] float64 taps at rir + rir_offsets[l])
+ *     wet[l][b][k] = sum_{t = 0 .. min(k, T_l - 1)} h_l[t] * x_b[k - t],   k = 0 .. n_b - 1
+ * the causal convolution truncated to the utterance's own length (numpy.convolve(x, h)[:n]): a level has the offsets, the window
+ * count and the time axis of the dry one. Level K is the dry batch converted to float64 (exact for int16), as level K of
+ * f2_eval_noise_sweep. levels is level-major, (K+1) * offsets[B] float64; level l, utterance b is utterance u = l*B + b of a
+ * (K+1)*B batch whose offsets are the dry offsets tiled: tiled[u] = l*offsets[B] + offsets[b].
+ *   arithmetic     one float64 accumulator per output sample, starting from 0; taps in ascending t; each step is
+ *                  acc = fma(h[t], x[k-t], acc), the samples converted to float64 first. No atomics, and the sum of one output
+ *                  is never split across lanes or workgroups. A sample of a level therefore depends on (x_b, h_l, k) alone - not
+ *                  on the launch shape, the batch around it, K or the other responses, the memory space or the input dtype of
+ *                  equal values - and the same bits come out on every call. (A workgroup walks the taps in chunks and also adds
+ *                  the terms fma(h[t], 0, acc) of the taps k < t < T_l that its chunk holds; they leave acc as it is, except that
+ *                  a sum that has underflowed to -0 can come out as +0.)
+ *   kernel         direct form; one workgroup per (tile of 1024 outputs, level), the input span of a chunk of 1024 taps staged
+ *                  in LDS as float64 (zero before the utterance's start), the taps read through the scalar path, four
+ *                  consecutive outputs per lane on a sliding register window. The cost grows with n_b * T_l; an FFT route is
+ *                  not part of this call.
+ * rir and rir_offsets are always host pointers, like coefs. wave and levels are in mem_space; device pointers need element
+ * alignment only. F2_MEM_DEVICE: the call enqueues on the context's stream and returns; F2_MEM_HOST: it returns when levels is
+ * filled.
+ * F2_ERR_INVALID, with nothing launched and levels untouched: a NULL ctx or offsets; offsets that do not start at 0 or that
+ * decrease; B < 0; a bad wave_dtype; K < 1; a NULL rir or rir_offsets; rir_offsets that do not start at 0 or that decrease; a
+ * response of 0 taps; a tap that is not finite; NULL wave or levels with offsets[B] > 0; a mem_space other than F2_MEM_HOST /
+ * F2_MEM_DEVICE. F2_ERR_UNSUPPORTED, likewise: K > 64; a response of more than 32768 taps (F2_REVERB_MAX_TAPS, 2.05 s at 16 kHz);
+ * (K+1)*B beyond what f2_eval_noise_sweep accepts. B == 0 or offsets[B] == 0: F2_OK.
+ *
+ * f2_eval_reverb_sweep: f2_eval_noise_sweep with the two noise kernels replaced by f2_reverb_levels' kernel. Only the dry samples
+ * and the taps go up; the levels are evaluated as ONE (K+1)*B-utterance float64 batch; one wait at the end. Every output is
+ * optional.
+ *   wet_or_null   (K+1) * offsets[B] float64, level-major, in mem_space: the waveforms that were evaluated (a device buffer
+ *           serves as the call's own buffer; otherwise they live in context scratch). Bit for bit f2_reverb_levels.
+ *   scores_or_null, labels_or_null, window_offsets_or_null (host, (K+1)*B + 1)
+ *           bit for bit what f2_eval_batch_strided(F2_WAVE_F64) returns for the (K+1)*B batch `wet` with the tiled offsets and
+ *           the same coefs ... hop: it is that call's code on that buffer. window_offsets is filled whenever the arguments pass.
+ *   stats_or_null   host, (K+1)*B*2: stats[2u] = windows of u labelled rising, stats[2u+1] = windows of u whose label equals
+ *           the dry level's label for the same window of the same utterance (for level K: its window count), counted on the
+ *           device as in f2_eval_noise_sweep, also when labels_or_null is NULL.
+ * Errors, all before anything is launched or written: everything f2_eval_batch_strided rejects, by the same checks; what
+ * f2_reverb_levels rejects of K, rir and rir_offsets, with the same status. F2_ERR_NONPOSITIVE as in the strided call. B == 0, or
+ * no utterance long enough for a window: F2_OK with window_offsets / stats filled. The call waits for the stream before it
+ * returns, whatever mem_space is.
+ */
+int f2_reverb_levels(f2_ctx* ctx, const void* wave, int wave_dtype, const int64_t* offsets /* host, B+1 */, int B,
+                     const double* rir /* host, rir_offsets[K] taps */, const int64_t* rir_offsets /* host, K+1 */, int K,
+                     double* levels /* (K+1) * offsets[B], level-major, mem_space */, int mem_space);
+int f2_eval_reverb_sweep(f2_ctx* ctx, const f2_cnn* cnn, const void* wave, int wave_dtype, const int64_t* offsets,
+                         const double* coefs, int B, int C, int lpf, double cutoff_hz, int fft_precision, int radius,
+                         int step, int hop, const double* rir /* host, rir_offsets[K] taps */,
+                         const int64_t* rir_offsets /* host, K+1 */, int K,
+                         double* wet_or_null /* (K+1) * offsets[B], mem_space */, float* scores_or_null,
+                         uint8_t* labels_or_null, int64_t* window_offsets_or_null /* host, (K+1)*B + 1 */,
+                         int64_t* stats_or_null /* host, (K+1)*B*2 */, int mem_space);
+
 #ifdef __cplusplus
 }
 #endif
