@@ -396,17 +396,7 @@ class Context:
         those it is not given."""
         offsets = np.ascontiguousarray(offsets, dtype=np.int64)
         snr = np.ascontiguousarray(snr_db, dtype=np.float64).reshape(-1)
-        U = (len(snr) + 1) * int(B)
-        if window_offsets is None:
-            window_offsets = np.zeros(U + 1, np.int64)
-        if sigma is None:
-            sigma = np.zeros(U, np.float64)
-        if stats is None:
-            stats = np.zeros((U, 2), np.int64)
-        for a, dt, n in ((window_offsets, np.int64, U + 1), (sigma, np.float64, U), (stats, np.int64, 2 * U)):
-            if a.dtype != dt or a.size != n or not a.flags["C_CONTIGUOUS"]:
-                raise ValueError("window_offsets / sigma / stats must be contiguous int64 (K+1)*B + 1, float64 (K+1)*B, int64 "
-                                 "((K+1)*B, 2)")
+        window_offsets, stats, sigma = _sweep_outputs((len(snr) + 1) * int(B), window_offsets, stats, sigma, True)
         self.check(self.lib.f2_eval_noise_sweep(self.handle, handle, _ptr(wave), wave_dtype, _ptr(offsets), _ptr(coefs), int(B),
                                                 Cn, int(bool(lpf)), float(cutoff), precision, radius, step, int(hop),
                                                 _ptr(snr) if len(snr) else None, len(snr), int(seed) & (2 ** 64 - 1), _ptr(noisy),
@@ -432,14 +422,7 @@ class Context:
         given."""
         offsets = np.ascontiguousarray(offsets, dtype=np.int64)
         cut = np.ascontiguousarray(cutoffs, dtype=np.float64).reshape(-1)
-        U = (len(cut) + 1) * int(B)
-        if window_offsets is None:
-            window_offsets = np.zeros(U + 1, np.int64)
-        if stats is None:
-            stats = np.zeros((U, 2), np.int64)
-        for a, n in ((window_offsets, U + 1), (stats, 2 * U)):
-            if a.dtype != np.int64 or a.size != n or not a.flags["C_CONTIGUOUS"]:
-                raise ValueError("window_offsets / stats must be contiguous int64 (K+1)*B + 1 / ((K+1)*B, 2)")
+        window_offsets, stats, _ = _sweep_outputs((len(cut) + 1) * int(B), window_offsets, stats)
         self.check(self.lib.f2_eval_cutoff_sweep(self.handle, handle, _ptr(wave), wave_dtype, _ptr(offsets), _ptr(coefs), int(B), Cn,
                                                  precision, radius, step, int(hop), _ptr(cut) if len(cut) else None, len(cut),
                                                  _ptr(env_levels), _ptr(scores), _ptr(labels), _ptr(window_offsets), _ptr(stats),
@@ -464,14 +447,7 @@ class Context:
         offsets = np.ascontiguousarray(offsets, dtype=np.int64)
         taps, rir_offsets = _pack_rirs(rirs)
         K = len(rir_offsets) - 1
-        U = (K + 1) * int(B)
-        if window_offsets is None:
-            window_offsets = np.zeros(U + 1, np.int64)
-        if stats is None:
-            stats = np.zeros((U, 2), np.int64)
-        for a, n in ((window_offsets, U + 1), (stats, 2 * U)):
-            if a.dtype != np.int64 or a.size != n or not a.flags["C_CONTIGUOUS"]:
-                raise ValueError("window_offsets / stats must be contiguous int64 (K+1)*B + 1 / ((K+1)*B, 2)")
+        window_offsets, stats, _ = _sweep_outputs((K + 1) * int(B), window_offsets, stats)
         self.check(self.lib.f2_eval_reverb_sweep(self.handle, handle, _ptr(wave), wave_dtype, _ptr(offsets), _ptr(coefs), int(B), Cn,
                                                  int(bool(lpf)), float(cutoff), precision, radius, step, int(hop),
                                                  _ptr(taps) if len(taps) else None, _ptr(rir_offsets), K, _ptr(wet), _ptr(scores),
@@ -663,6 +639,17 @@ class Context:
                                               int(B), int(up), int(down), _ptr(taps), int(half_len), _ptr(out), _ptr(out_offsets),
                                               mem_space))
         return out_offsets
+
+
+def _sweep_outputs(U, window_offsets, stats, sigma=None, with_sigma=False):
+    """The small outputs of a sweep over U = (K+1)*B utterances, allocated where they are None and checked where they are given:
+    (window_offsets, stats, sigma); sigma stays None without with_sigma"""
+    want = [(np.int64, U + 1, (U + 1,)), (np.int64, 2 * U, (U, 2))] + ([(np.float64, U, (U,))] if with_sigma else [])
+    got = [np.zeros(shape, dt) if a is None else a for a, (dt, _, shape) in zip((window_offsets, stats, sigma), want)]
+    if any(a.dtype != dt or a.size != n or not a.flags["C_CONTIGUOUS"] for a, (dt, n, _) in zip(got, want)):
+        raise ValueError("window_offsets / sigma / stats must be contiguous int64 (K+1)*B + 1, float64 (K+1)*B, int64 ((K+1)*B, 2)"
+                         if with_sigma else "window_offsets / stats must be contiguous int64 (K+1)*B + 1 / ((K+1)*B, 2)")
+    return got + [None] * (3 - len(got))
 
 
 def _pack_rirs(rirs):

@@ -259,6 +259,34 @@ def labelled_window_files(args):
     return inputFile, labelFile
 
 
+# The sweep commands: command -> (whether the options it does not take are refused before anything else of the command line -
+# noisesweep reads --lpf, --model, --hop, --accuracy and --resample first -, what it says of --lpf if it does not take it, what to use
+# instead of --figure / --occlusion, the options of which one has to be given, what is said when none is, the call with the keyword
+# arguments main() made of the common options)
+SWEEPS = {
+    'noisesweep': (False, None, "use evalnoise {} for one level", ('snrs',),
+                   "Please use --snrs to give the noise levels, e.g. --snrs 20,10,0,-3",
+                   lambda E, a, kw: E.EvaluateNoiseSweep([a.file], a.snrs, seed=a.seed or 0, save_wavs=a.save_wavs, **kw)),
+    'lpfsweep': (True, "the cutoffs come from --cutoffs; the unfiltered level is always there", "use eval --lpf HZ {} for one cutoff",
+                 ('cutoffs',), "Please use --cutoffs to give the envelope cutoffs in Hz, e.g. --cutoffs 5,10,20,50,100",
+                 lambda E, a, kw: E.EvaluateCutoffSweep([a.file], a.cutoffs, **kw)),
+    'reverbsweep': (True, None, "use eval {} on a WAV written with --save-wavs", ('t60', 'rir'),
+                    "Please use --t60 to give the reverberation times in seconds, e.g. --t60 0.2,0.4,0.8, or --rir to give impulse "
+                    "response files",
+                    lambda E, a, kw: E.EvaluateReverbSweep([a.file], t60s=getattr(a, 't60', ()), rirs=getattr(a, 'rir', ()),
+                                                           drr_db=getattr(a, 'drr', 0.0), seed=a.seed or 0, save_wavs=a.save_wavs, **kw)),
+}
+
+
+def sweep_refusal(args, no_lpf, instead):
+    """says which option the sweep does not take, if one was given (an option that was not given is absent, None or False)"""
+    for attr, option, why in (('CUTOFF', '--lpf', no_lpf), ('figure', '--figure', instead), ('occlusion', '--occlusion', instead)):
+        if why and getattr(args, attr, None) not in (None, False):
+            print("{} is not supported by {} ({})".format(option, args.cnn_command, why.format(option)))
+            return True
+    return False
+
+
 def main(argv=None):
     args = build_parser().parse_args(argv)
     if 'prepare_command' in args:
@@ -311,23 +339,9 @@ def main(argv=None):
             return 0
         from .scripts.CNN import Evaluating
         kwargs = {}
-        if args.cnn_command == 'lpfsweep':
-            if args.CUTOFF is not None:
-                print("--lpf is not supported by lpfsweep (the cutoffs come from --cutoffs; the unfiltered level is always there)")
-                return 1
-            if getattr(args, 'figure', False):
-                print("--figure is not supported by lpfsweep (use eval --lpf HZ --figure for one cutoff)")
-                return 1
-            if 'occlusion' in args:
-                print("--occlusion is not supported by lpfsweep (use eval --lpf HZ --occlusion for one cutoff)")
-                return 1
-        if args.cnn_command == 'reverbsweep':
-            if getattr(args, 'figure', False):
-                print("--figure is not supported by reverbsweep (use eval --figure on a WAV written with --save-wavs)")
-                return 1
-            if 'occlusion' in args:
-                print("--occlusion is not supported by reverbsweep (use eval --occlusion on a WAV written with --save-wavs)")
-                return 1
+        sweep = SWEEPS.get(args.cnn_command)
+        if sweep and sweep[0] and sweep_refusal(args, *sweep[1:3]):
+            return 1
         if args.CUTOFF is not None:                            # f2cnn.py:149-151
             kwargs['LPF'] = True
             kwargs['CUTOFF'] = args.CUTOFF
@@ -342,17 +356,13 @@ def main(argv=None):
             kwargs['accuracy'] = args.accuracy
         if getattr(args, 'resample', False):
             kwargs['resample'] = True
+        if sweep and not sweep[0] and sweep_refusal(args, *sweep[1:3]):
+            return 1
         if getattr(args, 'figure', False):
-            if args.cnn_command == 'noisesweep':
-                print("--figure is not supported by noisesweep (use evalnoise --figure for one level)")
-                return 1
             kwargs['figure'] = True
             if getattr(args, 'figure_width', None) is not None:
                 kwargs['figure_width'] = args.figure_width
         if 'occlusion' in args:
-            if args.cnn_command == 'noisesweep':
-                print("--occlusion is not supported by noisesweep (use evalnoise --occlusion for one level)")
-                return 1
             fill = getattr(args, 'occlusion_fill', 0.0)
             if not 0.0 <= fill <= 1.0:
                 print("--occlusion-fill must lie in [0, 1], the range of a normalised window")
@@ -372,25 +382,11 @@ def main(argv=None):
         if args.file is None:
             print("Please use --file or -f to give input file")
             return 1
-        if args.cnn_command == 'noisesweep':
-            if args.snrs is None:
-                print("Please use --snrs to give the noise levels, e.g. --snrs 20,10,0,-3")
+        if sweep:
+            if all(getattr(args, name, None) is None for name in sweep[3]):
+                print(sweep[4])
                 return 1
-            Evaluating.EvaluateNoiseSweep([args.file], args.snrs, seed=args.seed or 0, save_wavs=args.save_wavs, **kwargs)
-            return 0
-        if args.cnn_command == 'lpfsweep':
-            if getattr(args, 'cutoffs', None) is None:
-                print("Please use --cutoffs to give the envelope cutoffs in Hz, e.g. --cutoffs 5,10,20,50,100")
-                return 1
-            Evaluating.EvaluateCutoffSweep([args.file], args.cutoffs, **kwargs)
-            return 0
-        if args.cnn_command == 'reverbsweep':
-            if 't60' not in args and 'rir' not in args:
-                print("Please use --t60 to give the reverberation times in seconds, e.g. --t60 0.2,0.4,0.8, or --rir to give "
-                      "impulse response files")
-                return 1
-            Evaluating.EvaluateReverbSweep([args.file], t60s=getattr(args, 't60', ()), rirs=getattr(args, 'rir', ()),
-                                           drr_db=getattr(args, 'drr', 0.0), seed=args.seed or 0, save_wavs=args.save_wavs, **kwargs)
+            sweep[5](Evaluating, args, kwargs)
             return 0
         kwargs['file'] = args.file
         if args.cnn_command == 'evalnoise':

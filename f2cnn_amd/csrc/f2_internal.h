@@ -56,9 +56,10 @@ struct f2_ctx {
     f2_scratch xbuf;       // window tensor chunk between K3 and K4
     f2_scratch occ_src;    // f2_eval_occlusion_batch: the source windows of a chunk, which k_occlude_windows expands into xbuf
     f2_scratch dense_in;   // conv4 outputs (+ dense1 outputs) of the windows of several utterances: one dense launch for all
-    f2_scratch noise_wave; // f2_eval_noise_sweep: the (K+1) x batch float64 waveform when the caller gives no device buffer for it
-    f2_scratch lp_levels;  // f2_lowpass_levels / f2_eval_cutoff_sweep: the (K+1) x batch envelopes when the caller gives no device buffer
-    f2_scratch reverb_wave; // f2_reverb_levels / f2_eval_reverb_sweep: the (K+1) x batch float64 waveform when the caller gives no device buffer
+    // the three sweeps, f2_lowpass_levels, f2_reverb_levels: the (K+1) x batch levels (float64 waveforms or envelopes) when the caller
+    // gives no device buffer. One area: each of these calls places one set of levels, and nothing they nest (f2_eval_batch_strided,
+    // with or without lpf; eval_envelopes) places another.
+    f2_scratch levels;
     // The small arrays of the call in flight (f2_meta_carve): sigma / stats / window offsets of the noise sweep, filter coefficients /
     // stats / window offsets of the cutoff sweep, taps / tile sums / stats / window offsets of the reverberation sweep, counts and reference
     // labels of f2_label_accuracy, counts / loss sums / loss partials of f2_cnn_score_windows, span records and range words of the

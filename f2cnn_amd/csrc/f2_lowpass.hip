@@ -110,7 +110,7 @@ extern "C" int f2_lowpass_levels(f2_ctx* ctx, const double* env, const int64_t* 
     F2_TRY(meta.reserve(ctx));
     const size_t bytes = sizeof(double) * (size_t)C * (size_t)total;
     f2_output out;
-    F2_TRY(f2_place(ctx, ctx->lp_levels, levels, bytes * ((size_t)K + 1), mem_space, true, &out));
+    F2_TRY(f2_place(ctx, ctx->levels, levels, bytes * ((size_t)K + 1), mem_space, true, &out));
     const void* d_env;
     F2_TRY(f2_stage_input(ctx, env, bytes, mem_space, &d_env));
     F2_TRY(f2_upload_offsets(ctx, offsets, B));

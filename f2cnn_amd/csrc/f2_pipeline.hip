@@ -398,148 +398,161 @@ int f2_eval_batch_strided(f2_ctx* ctx, const f2_cnn* cnn, const void* wave, int 
     return eval_cnn_end(ctx, cnn, &E);
 }
 
-// f2_eval_noise_sweep: the K noisy levels and the clean one of a ragged batch as ONE (K+1) * B-utterance float64 batch in device
-// memory (f2_noise.hip), through f2_eval_batch_strided as a device call, then the tally of its labels on the device. Only the clean
-// samples go up; sigma, stats and what the caller asked for come back behind one wait.
+}  // extern "C"
+
+// ---- the robustness sweeps: K levels of one axis (noise, room, envelope cutoff) and the unchanged level of a ragged batch as ONE
+// (K+1) * B-utterance batch in device memory - utterance l * B + b is utterance b at level l, the unchanged level last - evaluated
+// like f2_eval_batch_strided, its labels tallied against the unchanged level's on the device ----
+namespace {
+
+// The (K+1) * B batch on the host, and the tally's two small arrays. The empty cases, for every sweep: nothing is launched when
+// total == 0, and sigma is zeros then; stats are zeros whenever n_total == 0 (sweep_begin fills them; a wave sweep with samples but
+// no window still runs tally() and stats_back(), which bring the same zeros).
+struct sweep_plan {
+    int B = 0, K = 0, U = 0;
+    int64_t total = 0, n_total = 0, max_windows = 0;   // samples of a level; windows of all levels, of the utterance with the most
+    std::vector<int64_t> tiled, wo, nbh;               // the caller's offsets tiled (U + 1), window offsets (U + 1), windows (U)
+    int64_t *d_stats = nullptr, *d_wo = nullptr;
+    // after the axis's own arrays, before meta->reserve()
+    void carve(f2_meta_carve* meta) { meta->add(&d_stats, 2 * (size_t)U), meta->add(&d_wo, (size_t)U + 1); }
+    // stats of the U utterances from their labels (all written: behind the last dense launch)
+    int tally(f2_ctx* ctx, const uint8_t* d_labels) const {
+        F2_HIP(ctx, hipMemsetAsync(d_stats, 0, sizeof(int64_t) * 2 * (size_t)U, ctx->stream));
+        if (n_total == 0) return F2_OK;
+        F2_TRY(f2_upload_async(ctx, d_wo, wo.data(), sizeof(int64_t) * ((size_t)U + 1)));
+        return f2_launch_label_tally(ctx, d_labels, d_wo, B, K, max_windows, d_stats);
+    }
+    int stats_back(f2_ctx* ctx, int64_t* stats_or_null) const {
+        if (stats_or_null)
+            F2_HIP(ctx, hipMemcpyAsync(stats_or_null, d_stats, sizeof(int64_t) * 2 * (size_t)U, hipMemcpyDeviceToHost, ctx->stream));
+        return F2_OK;
+    }
+};
+
+// The argument errors of a sweep in their order - f2_eval_batch_strided's, the axis's own (level_check), the size of the (K+1) * B
+// batch (per_channel: of its B * C rows too, for levels that are envelopes), null wave - then the plan, window_offsets_or_null and
+// the zero stats of a call without windows.
+template <class LevelCheck>
+int sweep_begin(f2_ctx* ctx, const f2_cnn* cnn, const f2_batch& X, int radius, int step, int hop, int K, LevelCheck level_check,
+                bool per_channel, int64_t* window_offsets_or_null, int64_t* stats_or_null, eval_call* E, sweep_plan* P) {
+    F2_TRY(eval_check(ctx, cnn, X, radius, step, E));
+    F2_CHECK(ctx, hop >= 1, F2_ERR_INVALID, "hop must be at least 1 sample (got %d)", hop);
+    F2_TRY(level_check());
+    const int B = X.B;
+    F2_CHECK(ctx, ((int64_t)K + 1) * (B > 0 ? B : 1) <= INT32_MAX / 2, F2_ERR_UNSUPPORTED, "%d levels of %d utterances", K + 1, B);
+    F2_CHECK(ctx, !per_channel || (int64_t)B * X.C <= INT32_MAX, F2_ERR_UNSUPPORTED, "%d utterances of %d channels", B, X.C);
+    const int64_t total = X.total();
+    F2_CHECK(ctx, X.wave || total == 0, F2_ERR_INVALID, "null wave");
+    const int U = (K + 1) * B;
+    P->B = B, P->K = K, P->U = U, P->total = total;
+    P->tiled.assign((size_t)U + 1, 0), P->wo.assign((size_t)U + 1, 0), P->nbh.assign((size_t)U, 0);
+    for (int l = 0; l <= K; ++l)
+        for (int b = 0; b < B; ++b) {
+            const size_t u = (size_t)l * B + b;
+            P->nbh[u] = strided_windows(X.offsets[b + 1] - X.offsets[b], E->R, step, hop);
+            P->tiled[u + 1] = (int64_t)l * total + X.offsets[b + 1];
+            P->wo[u + 1] = P->wo[u] + P->nbh[u];
+            P->max_windows = std::max(P->max_windows, P->nbh[u]);
+        }
+    P->n_total = P->wo[(size_t)U];
+    if (window_offsets_or_null) memcpy(window_offsets_or_null, P->wo.data(), sizeof(int64_t) * ((size_t)U + 1));
+    if (stats_or_null && P->n_total == 0) std::fill(stats_or_null, stats_or_null + 2 * (size_t)U, (int64_t)0);
+    return F2_OK;
+}
+
+// A sweep whose levels are waveforms (noise, room): the levels as float64 in ctx->levels or the caller's device buffer, through
+// f2_eval_batch_strided as a device call on the tiled offsets, the tally, and what the caller asked for behind one wait. Of the axis:
+// level_check (sweep_begin); carve(meta, U) names its small arrays; fill(d_offsets, total, d_levels) stages the wave and queues the
+// launches that fill the levels (the tiled offsets on the device start with the caller's: one array serves them and the
+// evaluation); *d_sigma, if the axis has one: U doubles for sigma_or_null.
+template <class LevelCheck, class Carve, class Fill>
+int wave_sweep(f2_ctx* ctx, const f2_cnn* cnn, const f2_batch& X, int radius, int step, int hop, int K, LevelCheck level_check,
+               Carve carve, Fill fill, double* levels_or_null, float* scores_or_null, uint8_t* labels_or_null,
+               int64_t* window_offsets_or_null, int64_t* stats_or_null, double* sigma_or_null = nullptr, double** d_sigma = nullptr) {
+    eval_call E;
+    sweep_plan P;
+    F2_TRY(sweep_begin(ctx, cnn, X, radius, step, hop, K, level_check, false, window_offsets_or_null, stats_or_null, &E, &P));
+    if (P.total == 0) {
+        if (sigma_or_null) std::fill(sigma_or_null, sigma_or_null + P.U, 0.0);
+        return F2_OK;
+    }
+    // small arrays of the call, held across the nested evaluation (which does not touch ctx->meta)
+    f2_meta_carve meta;
+    carve(&meta, (size_t)P.U);
+    P.carve(&meta);
+    F2_TRY(meta.reserve(ctx));
+    f2_output levels;
+    F2_TRY(f2_place(ctx, ctx->levels, levels_or_null, sizeof(double) * (size_t)(K + 1) * (size_t)P.total, X.mem_space, true, &levels));
+    // scores / labels of the device call below (the tally always needs the labels). They stay in stage_aux: the nested call, a
+    // device call with both pointers given, uses stage_out, xbuf, work and dense_in
+    f2_score_outputs out;
+    F2_TRY(f2_place_scores(ctx, scores_or_null, labels_or_null, P.n_total, X.mem_space, false, true, 0, &out));
+    F2_TRY(f2_upload_offsets(ctx, P.tiled.data(), P.U));
+    F2_TRY(fill((const int64_t*)ctx->offsets.ptr, P.total, levels.as<double>()));
+    F2_TRY(f2_copy_back(ctx, levels));
+    F2_TRY(f2_eval_batch_strided(ctx, cnn, levels.dev, F2_WAVE_F64, P.tiled.data(), X.coefs, P.U, X.C, X.lpf, X.cutoff_hz, X.fft_precision,
+                                 radius, step, hop, out.scores.as<float>(), out.labels.as<uint8_t>(), nullptr, F2_MEM_DEVICE));
+    F2_TRY(P.tally(ctx, out.labels.as<uint8_t>()));
+    if (P.n_total > 0) {
+        F2_TRY(f2_copy_back(ctx, out.scores));
+        F2_TRY(f2_copy_back(ctx, out.labels));
+    }
+    if (sigma_or_null) F2_HIP(ctx, hipMemcpyAsync(sigma_or_null, *d_sigma, sizeof(double) * (size_t)P.U, hipMemcpyDeviceToHost, ctx->stream));
+    F2_TRY(P.stats_back(ctx, stats_or_null));
+    F2_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return F2_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+// f2_eval_noise_sweep: a wave sweep whose levels come from the two noise kernels (f2_noise.hip). Only the clean samples go up;
+// sigma, stats and what the caller asked for come back behind one wait.
 int f2_eval_noise_sweep(f2_ctx* ctx, const f2_cnn* cnn, const void* wave, int wave_dtype, const int64_t* offsets,
                         const double* coefs, int B, int C, int lpf, double cutoff_hz, int fft_precision, int radius, int step,
                         int hop, const double* snr_db, int K, uint64_t seed, double* noisy_or_null, float* scores_or_null,
                         uint8_t* labels_or_null, int64_t* window_offsets_or_null, double* sigma_or_null, int64_t* stats_or_null,
                         int mem_space) {
     const f2_batch X = {wave, wave_dtype, offsets, coefs, B, C, lpf, cutoff_hz, fft_precision, mem_space};
-    eval_call E;
-    F2_TRY(eval_check(ctx, cnn, X, radius, step, &E));
-    F2_CHECK(ctx, hop >= 1, F2_ERR_INVALID, "hop must be at least 1 sample (got %d)", hop);
-    F2_CHECK(ctx, K >= 1 && snr_db, F2_ERR_INVALID, "a sweep needs at least one noise level (K=%d) and their snr_db", K);
-    for (int k = 0; k < K; ++k) F2_CHECK(ctx, std::isfinite(snr_db[k]), F2_ERR_INVALID, "snr_db[%d] is not finite", k);
-    F2_CHECK(ctx, ((int64_t)K + 1) * (B > 0 ? B : 1) <= INT32_MAX / 2, F2_ERR_UNSUPPORTED, "%d levels of %d utterances", K + 1, B);
-    const int64_t total = X.total();
-    F2_CHECK(ctx, wave || total == 0, F2_ERR_INVALID, "null wave");
-    const int U = (K + 1) * B;
-    // the (K+1) * B batch: the clean offsets tiled, its window offsets, 10^(snr / 10) per level
-    std::vector<int64_t> tiled((size_t)U + 1, 0), wo((size_t)U + 1, 0);
-    int64_t max_windows = 0;
-    for (int l = 0; l <= K; ++l)
-        for (int b = 0; b < B; ++b) {
-            const size_t u = (size_t)l * B + b;
-            const int64_t nw = strided_windows(offsets[b + 1] - offsets[b], E.R, step, hop);
-            tiled[u + 1] = (int64_t)l * total + offsets[b + 1];
-            wo[u + 1] = wo[u] + nw;
-            max_windows = nw > max_windows ? nw : max_windows;
-        }
-    const int64_t n_total = wo[(size_t)U];
-    if (window_offsets_or_null) memcpy(window_offsets_or_null, wo.data(), sizeof(int64_t) * ((size_t)U + 1));
-    if (total == 0) {   // nothing to launch: no noise and no window anywhere
-        if (sigma_or_null) std::fill(sigma_or_null, sigma_or_null + U, 0.0);
-        if (stats_or_null) std::fill(stats_or_null, stats_or_null + 2 * (size_t)U, (int64_t)0);
-        return F2_OK;
-    }
-    std::vector<double> lin((size_t)K);
-    for (int k = 0; k < K; ++k) lin[(size_t)k] = std::pow(10.0, snr_db[k] / 10.0);   // Evaluating.py:189 SNRdbToSNRlinear
-
-    // small arrays of the call, held across the nested evaluation (which does not touch ctx->meta)
+    std::vector<double> lin;   // 10^(snr / 10) per level (Evaluating.py:189 SNRdbToSNRlinear)
     double *d_sigma, *d_lin;
-    int64_t *d_stats, *d_wo;
-    f2_meta_carve meta;
-    meta.add(&d_sigma, (size_t)U), meta.add(&d_lin, (size_t)K), meta.add(&d_stats, 2 * (size_t)U), meta.add(&d_wo, (size_t)U + 1);
-    F2_TRY(meta.reserve(ctx));
-    f2_output noisy;
-    F2_TRY(f2_place(ctx, ctx->noise_wave, noisy_or_null, sizeof(double) * (size_t)(K + 1) * (size_t)total, mem_space, true, &noisy));
-    // scores / labels of the device call below (the tally always needs the labels). They stay in stage_aux: the nested call, a
-    // device call with both pointers given, uses stage_out, xbuf, work and dense_in
-    f2_score_outputs out;
-    F2_TRY(f2_place_scores(ctx, scores_or_null, labels_or_null, n_total, mem_space, false, true, 0, &out));
-    // the tiled offsets start with the clean ones: one device array serves the noise kernels and the evaluation
-    F2_TRY(f2_upload_offsets(ctx, tiled.data(), U));
-    F2_TRY(f2_upload_async(ctx, d_lin, lin.data(), sizeof(double) * (size_t)K));
-    const void* d_wave;
-    F2_TRY(f2_stage_wave(ctx, wave, wave_dtype, total, mem_space, &d_wave));
-    const int64_t* d_offsets = (const int64_t*)ctx->offsets.ptr;
-    F2_TRY(f2_launch_noise_sigma(ctx, d_wave, wave_dtype, d_offsets, d_lin, B, K, d_sigma));
-    F2_TRY(f2_launch_noise_levels(ctx, d_wave, wave_dtype, d_offsets, d_sigma, B, K, total, seed, noisy.as<double>()));
-    F2_TRY(f2_copy_back(ctx, noisy));
-    F2_TRY(f2_eval_batch_strided(ctx, cnn, noisy.dev, F2_WAVE_F64, tiled.data(), coefs, U, C, lpf, cutoff_hz, fft_precision, radius, step,
-                                 hop, out.scores.as<float>(), out.labels.as<uint8_t>(), nullptr, F2_MEM_DEVICE));
-    F2_HIP(ctx, hipMemsetAsync(d_stats, 0, sizeof(int64_t) * 2 * (size_t)U, ctx->stream));
-    if (n_total > 0) {
-        F2_TRY(f2_upload_async(ctx, d_wo, wo.data(), sizeof(int64_t) * ((size_t)U + 1)));
-        F2_TRY(f2_launch_label_tally(ctx, out.labels.as<uint8_t>(), d_wo, B, K, max_windows, d_stats));
-        F2_TRY(f2_copy_back(ctx, out.scores));
-        F2_TRY(f2_copy_back(ctx, out.labels));
-    }
-    if (sigma_or_null) F2_HIP(ctx, hipMemcpyAsync(sigma_or_null, d_sigma, sizeof(double) * (size_t)U, hipMemcpyDeviceToHost, ctx->stream));
-    if (stats_or_null)
-        F2_HIP(ctx, hipMemcpyAsync(stats_or_null, d_stats, sizeof(int64_t) * 2 * (size_t)U, hipMemcpyDeviceToHost, ctx->stream));
-    F2_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return F2_OK;
+    return wave_sweep(
+        ctx, cnn, X, radius, step, hop, K,
+        [&]() -> int {
+            F2_CHECK(ctx, K >= 1 && snr_db, F2_ERR_INVALID, "a sweep needs at least one noise level (K=%d) and their snr_db", K);
+            for (int k = 0; k < K; ++k) F2_CHECK(ctx, std::isfinite(snr_db[k]), F2_ERR_INVALID, "snr_db[%d] is not finite", k);
+            return F2_OK;
+        },
+        [&](f2_meta_carve* meta, size_t U) { meta->add(&d_sigma, U), meta->add(&d_lin, (size_t)K); },
+        [&](const int64_t* d_offsets, int64_t total, double* d_noisy) -> int {
+            for (int k = 0; k < K; ++k) lin.push_back(std::pow(10.0, snr_db[k] / 10.0));
+            F2_TRY(f2_upload_async(ctx, d_lin, lin.data(), sizeof(double) * (size_t)K));
+            const void* d_wave;
+            F2_TRY(f2_stage_wave(ctx, wave, wave_dtype, total, mem_space, &d_wave));
+            F2_TRY(f2_launch_noise_sigma(ctx, d_wave, wave_dtype, d_offsets, d_lin, B, K, d_sigma));
+            return f2_launch_noise_levels(ctx, d_wave, wave_dtype, d_offsets, d_sigma, B, K, total, seed, d_noisy);
+        },
+        noisy_or_null, scores_or_null, labels_or_null, window_offsets_or_null, stats_or_null, sigma_or_null, &d_sigma);
 }
 
-// f2_eval_reverb_sweep: f2_eval_noise_sweep with k_reverb_levels (f2_reverb.hip) in the place of the two noise kernels: the K wet
-// levels and the dry one as ONE (K+1) * B-utterance float64 batch in device memory, through f2_eval_batch_strided as a device call,
-// then the tally of its labels against the dry level. Only the dry samples and the taps go up; one wait at the end.
+// f2_eval_reverb_sweep: a wave sweep whose levels come from k_reverb_levels (f2_reverb.hip). Only the dry samples and the taps go
+// up; one wait at the end.
 int f2_eval_reverb_sweep(f2_ctx* ctx, const f2_cnn* cnn, const void* wave, int wave_dtype, const int64_t* offsets,
                          const double* coefs, int B, int C, int lpf, double cutoff_hz, int fft_precision, int radius, int step,
                          int hop, const double* rir, const int64_t* rir_offsets, int K, double* wet_or_null, float* scores_or_null,
                          uint8_t* labels_or_null, int64_t* window_offsets_or_null, int64_t* stats_or_null, int mem_space) {
     const f2_batch X = {wave, wave_dtype, offsets, coefs, B, C, lpf, cutoff_hz, fft_precision, mem_space};
-    eval_call E;
-    F2_TRY(eval_check(ctx, cnn, X, radius, step, &E));
-    F2_CHECK(ctx, hop >= 1, F2_ERR_INVALID, "hop must be at least 1 sample (got %d)", hop);
-    F2_TRY(f2_check_rir(ctx, rir, rir_offsets, K));
-    F2_CHECK(ctx, ((int64_t)K + 1) * (B > 0 ? B : 1) <= INT32_MAX / 2, F2_ERR_UNSUPPORTED, "%d levels of %d utterances", K + 1, B);
-    const int64_t total = X.total();
-    F2_CHECK(ctx, wave || total == 0, F2_ERR_INVALID, "null wave");
-    const int U = (K + 1) * B;
-    // the (K+1) * B batch: the dry offsets tiled, its window offsets
-    std::vector<int64_t> tiled((size_t)U + 1, 0), wo((size_t)U + 1, 0);
-    int64_t max_windows = 0;
-    for (int l = 0; l <= K; ++l)
-        for (int b = 0; b < B; ++b) {
-            const size_t u = (size_t)l * B + b;
-            const int64_t nw = strided_windows(offsets[b + 1] - offsets[b], E.R, step, hop);
-            tiled[u + 1] = (int64_t)l * total + offsets[b + 1];
-            wo[u + 1] = wo[u] + nw;
-            max_windows = nw > max_windows ? nw : max_windows;
-        }
-    const int64_t n_total = wo[(size_t)U];
-    if (window_offsets_or_null) memcpy(window_offsets_or_null, wo.data(), sizeof(int64_t) * ((size_t)U + 1));
-    if (total == 0) {   // nothing to launch: no sample and no window anywhere
-        if (stats_or_null) std::fill(stats_or_null, stats_or_null + 2 * (size_t)U, (int64_t)0);
-        return F2_OK;
-    }
-
-    // small arrays of the call, held across the nested evaluation (which does not touch ctx->meta)
     f2_reverb_arrays A;
-    int64_t *d_stats, *d_wo;
-    f2_meta_carve meta;
-    f2_reverb_meta(&meta, B, rir_offsets, K, &A);
-    meta.add(&d_stats, 2 * (size_t)U), meta.add(&d_wo, (size_t)U + 1);
-    F2_TRY(meta.reserve(ctx));
-    f2_output wet;
-    F2_TRY(f2_place(ctx, ctx->reverb_wave, wet_or_null, sizeof(double) * (size_t)(K + 1) * (size_t)total, mem_space, true, &wet));
-    // scores / labels of the device call below (the tally always needs the labels), in stage_aux as in the noise sweep
-    f2_score_outputs out;
-    F2_TRY(f2_place_scores(ctx, scores_or_null, labels_or_null, n_total, mem_space, false, true, 0, &out));
-    // the tiled offsets start with the dry ones: one device array serves the reverberation kernel and the evaluation
-    F2_TRY(f2_upload_offsets(ctx, tiled.data(), U));
-    const void* d_wave;
-    F2_TRY(f2_stage_wave(ctx, wave, wave_dtype, total, mem_space, &d_wave));
-    F2_TRY(f2_launch_reverb_levels(ctx, d_wave, wave_dtype, (const int64_t*)ctx->offsets.ptr, offsets, B, rir, rir_offsets, K, A,
-                                   wet.as<double>()));
-    F2_TRY(f2_copy_back(ctx, wet));
-    F2_TRY(f2_eval_batch_strided(ctx, cnn, wet.dev, F2_WAVE_F64, tiled.data(), coefs, U, C, lpf, cutoff_hz, fft_precision, radius, step,
-                                 hop, out.scores.as<float>(), out.labels.as<uint8_t>(), nullptr, F2_MEM_DEVICE));
-    F2_HIP(ctx, hipMemsetAsync(d_stats, 0, sizeof(int64_t) * 2 * (size_t)U, ctx->stream));
-    if (n_total > 0) {
-        F2_TRY(f2_upload_async(ctx, d_wo, wo.data(), sizeof(int64_t) * ((size_t)U + 1)));
-        F2_TRY(f2_launch_label_tally(ctx, out.labels.as<uint8_t>(), d_wo, B, K, max_windows, d_stats));
-        F2_TRY(f2_copy_back(ctx, out.scores));
-        F2_TRY(f2_copy_back(ctx, out.labels));
-    }
-    if (stats_or_null)
-        F2_HIP(ctx, hipMemcpyAsync(stats_or_null, d_stats, sizeof(int64_t) * 2 * (size_t)U, hipMemcpyDeviceToHost, ctx->stream));
-    F2_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return F2_OK;
+    return wave_sweep(
+        ctx, cnn, X, radius, step, hop, K, [&] { return f2_check_rir(ctx, rir, rir_offsets, K); },
+        [&](f2_meta_carve* meta, size_t) { f2_reverb_meta(meta, B, rir_offsets, K, &A); },
+        [&](const int64_t* d_offsets, int64_t total, double* d_wet) -> int {
+            const void* d_wave;
+            F2_TRY(f2_stage_wave(ctx, wave, wave_dtype, total, mem_space, &d_wave));
+            return f2_launch_reverb_levels(ctx, d_wave, wave_dtype, d_offsets, offsets, B, rir, rir_offsets, K, A, d_wet);
+        },
+        wet_or_null, scores_or_null, labels_or_null, window_offsets_or_null, stats_or_null);
 }
 
 // f2_eval_cutoff_sweep: filterbank + envelope of the batch once, unfiltered; its K low-passed levels and the copy as ONE
@@ -551,61 +564,39 @@ int f2_eval_cutoff_sweep(f2_ctx* ctx, const f2_cnn* cnn, const void* wave, int w
                          int64_t* window_offsets_or_null, int64_t* stats_or_null, int mem_space) {
     const f2_batch X = {wave, wave_dtype, offsets, coefs, B, C, 0, 0.0, fft_precision, mem_space};
     eval_call E;
-    F2_TRY(eval_check(ctx, cnn, X, radius, step, &E));
-    F2_CHECK(ctx, hop >= 1, F2_ERR_INVALID, "hop must be at least 1 sample (got %d)", hop);
-    F2_TRY(f2_check_cutoffs(ctx, cutoff_hz, K));
-    F2_CHECK(ctx, ((int64_t)K + 1) * (B > 0 ? B : 1) <= INT32_MAX / 2, F2_ERR_UNSUPPORTED, "%d levels of %d utterances", K + 1, B);
-    F2_CHECK(ctx, (int64_t)B * C <= INT32_MAX, F2_ERR_UNSUPPORTED, "%d utterances of %d channels", B, C);
-    const int64_t total = X.total();
-    F2_CHECK(ctx, wave || total == 0, F2_ERR_INVALID, "null wave");
-    const int U = (K + 1) * B;
-    // the (K+1) * B batch: the clean offsets tiled, its windows
-    std::vector<int64_t> tiled((size_t)U + 1, 0), wo((size_t)U + 1, 0), nbh((size_t)U, 0);
-    int64_t max_windows = 0;
-    for (int l = 0; l <= K; ++l)
-        for (int b = 0; b < B; ++b) {
-            const size_t u = (size_t)l * B + b;
-            nbh[u] = strided_windows(offsets[b + 1] - offsets[b], E.R, step, hop);
-            tiled[u + 1] = (int64_t)l * total + offsets[b + 1];
-            wo[u + 1] = wo[u] + nbh[u];
-            max_windows = nbh[u] > max_windows ? nbh[u] : max_windows;
-        }
-    const int64_t n_total = wo[(size_t)U];
-    if (window_offsets_or_null) memcpy(window_offsets_or_null, wo.data(), sizeof(int64_t) * ((size_t)U + 1));
-    if (stats_or_null && n_total == 0) std::fill(stats_or_null, stats_or_null + 2 * (size_t)U, (int64_t)0);
-    if (total == 0) return F2_OK;   // nothing to launch
+    sweep_plan P;
+    F2_TRY(sweep_begin(ctx, cnn, X, radius, step, hop, K, [&] { return f2_check_cutoffs(ctx, cutoff_hz, K); }, true,
+                       window_offsets_or_null, stats_or_null, &E, &P));
+    if (P.total == 0) return F2_OK;
 
     // small arrays and the levels first: nothing below reallocates what a queued kernel uses (eval_envelopes does not touch
-    // ctx->meta or ctx->lp_levels)
+    // ctx->meta or ctx->levels)
     double* d_coef;
-    int64_t *d_stats, *d_wo;
     f2_meta_carve meta;
-    meta.add(&d_coef, 2 * (size_t)K), meta.add(&d_stats, 2 * (size_t)U), meta.add(&d_wo, (size_t)U + 1);
+    meta.add(&d_coef, 2 * (size_t)K);
+    P.carve(&meta);
     F2_TRY(meta.reserve(ctx));
     f2_output levels;
-    F2_TRY(f2_place(ctx, ctx->lp_levels, env_levels_or_null, sizeof(double) * ((size_t)K + 1) * (size_t)C * (size_t)total, mem_space, true,
+    F2_TRY(f2_place(ctx, ctx->levels, env_levels_or_null, sizeof(double) * ((size_t)K + 1) * (size_t)C * (size_t)P.total, mem_space, true,
                     &levels));
     F2_TRY(f2_upload_lowpass_coefs(ctx, cutoff_hz, K, d_coef));
-    F2_TRY(eval_envelopes(ctx, &E, X, nullptr, n_total));
+    F2_TRY(eval_envelopes(ctx, &E, X, nullptr, P.n_total));
     // the tiled offsets start with the clean ones: one device array serves the low-pass kernel and the window stage
-    F2_TRY(f2_upload_offsets(ctx, tiled.data(), U));
-    F2_TRY(f2_launch_lowpass_levels(ctx, E.d_env, (const int64_t*)ctx->offsets.ptr, B, C, total, d_coef, K, levels.as<double>()));
+    F2_TRY(f2_upload_offsets(ctx, P.tiled.data(), P.U));
+    F2_TRY(f2_launch_lowpass_levels(ctx, E.d_env, (const int64_t*)ctx->offsets.ptr, B, C, P.total, d_coef, K, levels.as<double>()));
     F2_TRY(f2_copy_back(ctx, levels));
-    if (n_total == 0) {
+    if (P.n_total == 0) {
         F2_HIP(ctx, hipStreamSynchronize(ctx->stream));
         return F2_OK;
     }
     E.d_env = levels.as<double>();
-    const f2_batch XU = {nullptr, F2_WAVE_F64, tiled.data(), coefs, U, C, 0, 0.0, fft_precision, mem_space};
-    const int64_t chunk = n_total < CNN_CHUNK ? n_total : CNN_CHUNK;
-    F2_TRY(eval_cnn_begin(ctx, cnn, &E, chunk, n_total, C, scores_or_null, labels_or_null, mem_space, true));
-    F2_TRY(strided_window_loop(ctx, cnn, &E, XU, nbh, chunk, radius, step, hop, (float*)ctx->xbuf.ptr));
+    const f2_batch XU = {nullptr, F2_WAVE_F64, P.tiled.data(), coefs, P.U, C, 0, 0.0, fft_precision, mem_space};
+    const int64_t chunk = P.n_total < CNN_CHUNK ? P.n_total : CNN_CHUNK;
+    F2_TRY(eval_cnn_begin(ctx, cnn, &E, chunk, P.n_total, C, scores_or_null, labels_or_null, mem_space, true));
+    F2_TRY(strided_window_loop(ctx, cnn, &E, XU, P.nbh, chunk, radius, step, hop, (float*)ctx->xbuf.ptr));
     F2_TRY(eval_dense_flush(ctx, cnn, &E));   // the tally reads every label
-    F2_HIP(ctx, hipMemsetAsync(d_stats, 0, sizeof(int64_t) * 2 * (size_t)U, ctx->stream));
-    F2_TRY(f2_upload_async(ctx, d_wo, wo.data(), sizeof(int64_t) * ((size_t)U + 1)));
-    F2_TRY(f2_launch_label_tally(ctx, E.out.labels.as<uint8_t>(), d_wo, B, K, max_windows, d_stats));
-    if (stats_or_null)
-        F2_HIP(ctx, hipMemcpyAsync(stats_or_null, d_stats, sizeof(int64_t) * 2 * (size_t)U, hipMemcpyDeviceToHost, ctx->stream));
+    F2_TRY(P.tally(ctx, E.out.labels.as<uint8_t>()));
+    F2_TRY(P.stats_back(ctx, stats_or_null));
     return eval_cnn_end(ctx, cnn, &E);   // (waits for the stream)
 }
 

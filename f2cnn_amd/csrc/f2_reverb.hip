@@ -187,7 +187,7 @@ extern "C" int f2_reverb_levels(f2_ctx* ctx, const void* wave, int wave_dtype, c
     f2_reverb_meta(&meta, B, rir_offsets, K, &A);
     F2_TRY(meta.reserve(ctx));
     f2_output out;
-    F2_TRY(f2_place(ctx, ctx->reverb_wave, levels, sizeof(double) * ((size_t)K + 1) * (size_t)total, mem_space, true, &out));
+    F2_TRY(f2_place(ctx, ctx->levels, levels, sizeof(double) * ((size_t)K + 1) * (size_t)total, mem_space, true, &out));
     const void* d_wave;
     F2_TRY(f2_stage_wave(ctx, wave, wave_dtype, total, mem_space, &d_wave));
     F2_TRY(f2_upload_offsets(ctx, offsets, B));

@@ -53,6 +53,7 @@ convolved with every room impulse response - synthetic ones of the given reverbe
 (``f2cnn_amd/reverb.py``) - and dry in one device pass (``f2_eval_reverb_sweep``: the convolution runs on the device, in float64),
 and ``OutputWavFiles/reverb/<stem>.reverbsweep.npz`` holds the decisions of every level, their agreement with the dry ones and the
 responses that were used."""
+import collections
 import os
 
 import numpy
@@ -698,131 +699,14 @@ def EvaluateWithNoise(file, LPF=False, CUTOFF=100, model='last_trained_model', C
     return scores, labels
 
 
-def _snr_text(SNRdB):
-    """how a level is printed: 10.0 -> '10', -3.0 -> '-3', 2.5 -> '2.5'"""
-    return '{:g}'.format(float(SNRdB))
+# ---- the robustness sweeps: a file at K levels of one axis (noise, envelope cutoff, room) and at the unchanged level, the
+# referee, in one device pass per group of files. _run_sweep is the file driver; an axis says what is its own ----------------
+def _level_text(value):
+    """how a level is printed and named: 10.0 -> '10', -3.0 -> '-3', 2.5 -> '2.5'"""
+    return '{:g}'.format(float(value))
 
 
-def EvaluateNoiseSweep(files, SNRdBs, seed=0, hop=None, LPF=False, CUTOFF=50, model='last_trained_model', save_wavs=False,
-                       ctx=None, accuracy=None, resample=False):
-    """`cnn noisesweep` (not in the reference, whose EvaluateWithNoise :193-221 takes one file at one level): every file at
-    every level of SNRdBs and clean in one device pass per group of files (f2_eval_noise_sweep: the noise is drawn on the device
-    from (seed, level, file's place in its group, sample), so a sweep repeats bit for bit), with the clean run of the same
-    network as the referee. Per file, OutputWavFiles/addedNoise/<stem>.sweep.npz holds snr_db, sigma, windows, rising, agree,
-    agreement (= agree / windows, NaN without windows) - one entry per level, the clean level last - seed, hop and labels_<k>
-    for level k of snr_db (labels_clean for the clean one); one line per level is printed and the same data is returned as a dict per
-    file. save_wavs also writes <stem><SNR>dB.WAV with copies of the annotation files, as EvaluateWithNoise names and writes
-    them. Files are grouped like EvaluateRandom groups them: one framerate and sample type per call. hop=None is hop 1.
-    With accuracy= every level of a file that has its .FB / .PHN is also scored against their labels (one f2_label_accuracy
-    call per group): the file's results gain accuracy_vtr (K+1) and confusion (K+1, 2, 2), [level][ref][pred], the clean level
-    last, and the printed lines the accuracy. With resample= the files are brought to the configured framerate first (one
-    device call per kind of file), the results gain framerate and source_framerate, and a file whose rate differed is left out
-    of the accuracy."""
-    import shutil
-    from scipy.io import wavfile
-    if isinstance(files, (str, bytes, os.PathLike)):
-        files = [files]
-    snr = numpy.asarray(SNRdBs, dtype=numpy.float64).reshape(-1)
-    if not len(snr) or not numpy.isfinite(snr).all():
-        raise ValueError("a noise sweep needs at least one finite SNR in dB")
-    K = len(snr)
-    hop = 1 if hop is None else int(hop)
-    if accuracy is not None:
-        _accuracy_origin(accuracy, 0, 0)
-    ctx = ctx or _lib.default_context()
-    cfg = F2Config()
-    if not isinstance(model, F2CNNModel):
-        model = load_model(model)
-    read = _load(files, resample)
-    loaded = [(file, framerate, wavArray) for file, (_, framerate, wavArray) in zip(files, read)]
-    sources = {file: source for file, (source, _, _) in zip(files, read)}
-    groups = {}
-    for file, framerate, wavArray in loaded:
-        wave, dt = filters._wave_args(wavArray)
-        groups.setdefault((framerate, dt), []).append((file, wave))
-    keys = [str(k) for k in range(K)] + ['clean']          # labels_<k>: level k of snr_db
-    names = [_snr_text(v) + 'dB' for v in snr] + ['clean']
-    results = {}
-    BATCH = 16                                    # files per device pass, as EvaluateRandom
-    for (framerate, dt), members in groups.items():
-        coefs = numpy.ascontiguousarray(filters.make_erb_filters(framerate, filters.centre_freqs(framerate, cfg.nchannels,
-                                                                                                  cfg.low_freq)))
-        Cn = coefs.shape[0]
-        STEP = _step(framerate, cfg)
-        for s0 in range(0, len(members), BATCH):
-            group = members[s0:s0 + BATCH]
-            B = len(group)
-            offsets = numpy.zeros(B + 1, numpy.int64)
-            offsets[1:] = numpy.cumsum([w.shape[0] for _, w in group])
-            flat = numpy.concatenate([w for _, w in group])
-            nbh = [_lib.strided_window_count(w.shape[0], cfg.radius, STEP, hop) for _, w in group]
-            labels = numpy.empty((K + 1) * sum(nbh), numpy.uint8)
-            noisy = numpy.empty((K + 1) * int(offsets[-1]), numpy.float64) if save_wavs else None
-            try:
-                wo, sigma, stats = ctx.eval_noise_sweep(model.handle(ctx), flat, dt, offsets, coefs, B, Cn, bool(LPF),
-                                                        CUTOFF if LPF else 0.0, FFT_PRECISION, cfg.radius, STEP, hop, snr, seed,
-                                                        noisy, None, labels, _lib.MEM_HOST)
-            except _lib.F2Error as e:
-                if e.code == _lib.F2_ERR_NONPOSITIVE:
-                    raise ValueError("values must all be positive")
-                raise
-            assert list(numpy.diff(wo)) == nbh * (K + 1)
-            refs = [None] * B
-            if accuracy is not None:     # (the labels of a file whose rate differed count source samples)
-                refs = [ReferenceLabels(file) if sources[file] == framerate else None for file, _ in group]
-            confusions = None
-            if any(ref is not None for ref in refs):
-                confusions = _confusions(ctx, labels, wo, refs, accuracy, hop, STEP)
-            os.makedirs(os.path.join('OutputWavFiles', 'addedNoise'), exist_ok=True)
-            for b, (file, w) in enumerate(group):
-                rows = [l * B + b for l in range(K + 1)]
-                windows = numpy.array([wo[u + 1] - wo[u] for u in rows], numpy.int64)
-                rising, agree = stats[rows, 0].copy(), stats[rows, 1].copy()
-                with numpy.errstate(invalid='ignore', divide='ignore'):
-                    agreement = numpy.where(windows > 0, agree / windows.astype(numpy.float64), numpy.nan)
-                res = dict(snr_db=snr.copy(), sigma=sigma[rows].copy(), windows=windows, rising=rising, agree=agree,
-                           agreement=agreement, seed=numpy.uint64(int(seed) & (2 ** 64 - 1)), hop=numpy.int64(hop),
-                           **_rate_keys(resample, framerate, sources[file]))
-                for key, u in zip(keys, rows):
-                    res['labels_' + key] = labels[wo[u]:wo[u + 1]].copy()
-                if refs[b] is not None:
-                    res['confusion'] = confusions[rows].copy()
-                    res['accuracy_vtr'] = _accuracy_of(res['confusion'])
-                source, _ = _noisy_copy_paths(file, 0)
-                out = os.path.join('OutputWavFiles', 'addedNoise', os.path.basename(source) + '.sweep.npz')
-                numpy.savez(out, **res)
-                print("File:\t\t{}".format(file))
-                if accuracy is not None and sources[file] != framerate:
-                    _no_rate_accuracy(file, sources[file], framerate)
-                elif accuracy is not None and refs[b] is None:
-                    _no_side_files(file)
-                for l in range(K + 1):
-                    line = "\tSNR {:>8}\t{} windows\t{} rising\tagreement with clean {:.4f}".format(
-                        names[l], windows[l], rising[l], agreement[l])
-                    if refs[b] is not None:
-                        line += "\taccuracy against the VTR labels ({}) {:.4f}".format(accuracy, res['accuracy_vtr'][l])
-                    print(line)
-                if save_wavs:
-                    for l in range(K):
-                        _, target = _noisy_copy_paths(file, snr[l])
-                        lo = l * int(offsets[-1]) + int(offsets[b])
-                        wavfile.write(target + '.WAV', framerate, noisy[lo:lo + w.shape[0]])
-                        for ext in ('.FB', '.PHN', '.WRD'):
-                            if os.path.exists(source + ext):
-                                shutil.copyfile(source + ext, target + ext)
-                print("\t\t{}\tdone ! -> {}".format(file, out))
-                results[file] = res
-    return results
-
-
-# ---- `cnn lpfsweep`: one file at several envelope cutoffs (the modulation axis; not in the reference, whose route is one
-# `cnn eval --lpf HZ` per cutoff) ---------------------------------------------------------------------------------------------
 LEVELS_LIMIT = 8 << 30           # bytes of envelope levels one device pass of EvaluateCutoffSweep may ask for
-
-
-def _cutoff_text(cutoff):
-    """how a level is printed: 50.0 -> '50', 2.5 -> '2.5'"""
-    return '{:g}'.format(float(cutoff))
 
 
 def _cutoff_groups(members, K, Cn, batch=16, limit=LEVELS_LIMIT):
@@ -840,6 +724,148 @@ def _cutoff_groups(members, K, Cn, batch=16, limit=LEVELS_LIMIT):
         yield group
 
 
+class _SweepAxis(collections.namedtuple('_SweepAxis', 'names referee label limit call own order out outdir wav_target')):
+    """What a sweep has of its own. names: how its K levels are printed; referee: the key and printed name of level K ('clean');
+    label: the format of a name at the start of a level's line. limit: bytes of levels a pass may ask for (_cutoff_groups).
+    call(ctx, handle, flat, dt, offsets, coefs, B, Cn, radius, STEP, hop, framerate, labels) -> (window offsets, stats, the
+    level waveforms or None, whatever own needs); own(got, rows, wo, n, radius, STEP, hop, framerate) -> the axis's keys of a
+    file of n samples whose levels are utterances `rows`: those `order` names go into the .npz in that order among windows ...
+    hop, the others behind the labels. out(file): the .npz; outdir: made before the first .npz of a pass (None: the file's own);
+    wav_target(file, l): the path, without extension, of level l's WAV and side-file copies (None: no WAVs)."""
+
+
+def _run_sweep(axis, files, hop, model, ctx, accuracy, resample):
+    K = len(axis.names)
+    hop = 1 if hop is None else int(hop)
+    if accuracy is not None:
+        _accuracy_origin(accuracy, 0, 0)
+    ctx = ctx or _lib.default_context()
+    cfg = F2Config()
+    if not isinstance(model, F2CNNModel):
+        model = load_model(model)
+    read = _load(files, resample)
+    sources = {file: source for file, (source, _, _) in zip(files, read)}
+    groups = {}                                   # one framerate and sample type per call
+    for file, (_, framerate, wavArray) in zip(files, read):
+        wave, dt = filters._wave_args(wavArray)
+        groups.setdefault((framerate, dt), []).append((file, wave))
+    keys = [str(k) for k in range(K)] + [axis.referee]          # labels_<k>: level k
+    names = list(axis.names) + [axis.referee]
+    line = "\t" + axis.label + "\t{} windows\t{} rising\tagreement with " + axis.referee + " {:.4f}"
+    results = {}
+    for (framerate, dt), members in groups.items():
+        coefs = numpy.ascontiguousarray(filters.make_erb_filters(framerate, filters.centre_freqs(framerate, cfg.nchannels,
+                                                                                                  cfg.low_freq)))
+        Cn = coefs.shape[0]
+        STEP = _step(framerate, cfg)
+        for group in _cutoff_groups(members, K, Cn, limit=axis.limit):
+            B = len(group)
+            offsets = numpy.zeros(B + 1, numpy.int64)
+            offsets[1:] = numpy.cumsum([w.shape[0] for _, w in group])
+            flat = numpy.concatenate([w for _, w in group])
+            nbh = [_lib.strided_window_count(w.shape[0], cfg.radius, STEP, hop) for _, w in group]
+            labels = numpy.empty((K + 1) * sum(nbh), numpy.uint8)
+            try:
+                wo, stats, waves, got = axis.call(ctx, model.handle(ctx), flat, dt, offsets, coefs, B, Cn, cfg.radius, STEP, hop,
+                                                  framerate, labels)
+            except _lib.F2Error as e:
+                if e.code == _lib.F2_ERR_NONPOSITIVE:
+                    raise ValueError("values must all be positive")
+                raise
+            assert list(numpy.diff(wo)) == nbh * (K + 1)
+            refs = [None] * B
+            if accuracy is not None:     # (the labels of a file whose rate differed count source samples)
+                refs = [ReferenceLabels(file) if sources[file] == framerate else None for file, _ in group]
+            confusions = None
+            if any(ref is not None for ref in refs):
+                confusions = _confusions(ctx, labels, wo, refs, accuracy, hop, STEP)
+            if axis.outdir:
+                os.makedirs(axis.outdir, exist_ok=True)
+            for b, (file, w) in enumerate(group):
+                rows = [l * B + b for l in range(K + 1)]
+                windows = numpy.array([wo[u + 1] - wo[u] for u in rows], numpy.int64)
+                rising, agree = stats[rows, 0].copy(), stats[rows, 1].copy()
+                with numpy.errstate(invalid='ignore', divide='ignore'):
+                    agreement = numpy.where(windows > 0, agree / windows.astype(numpy.float64), numpy.nan)
+                own = dict(axis.own(got, rows, wo, w.shape[0], cfg.radius, STEP, hop, framerate), windows=windows, rising=rising,
+                           agree=agree, agreement=agreement, hop=numpy.int64(hop))
+                res = dict({key: own.pop(key) for key in axis.order}, **_rate_keys(resample, framerate, sources[file]))
+                for key, u in zip(keys, rows):
+                    res['labels_' + key] = labels[wo[u]:wo[u + 1]].copy()
+                res.update(own)
+                if refs[b] is not None:
+                    res['confusion'] = confusions[rows].copy()
+                    res['accuracy_vtr'] = _accuracy_of(res['confusion'])
+                out = axis.out(file)
+                numpy.savez(out, **res)
+                print("File:\t\t{}".format(file))
+                if accuracy is not None and sources[file] != framerate:
+                    _no_rate_accuracy(file, sources[file], framerate)
+                elif accuracy is not None and refs[b] is None:
+                    _no_side_files(file)
+                for l in range(K + 1):
+                    text = line.format(names[l], windows[l], rising[l], agreement[l])
+                    if refs[b] is not None:
+                        text += "\taccuracy against the VTR labels ({}) {:.4f}".format(accuracy, res['accuracy_vtr'][l])
+                    print(text)
+                if waves is not None:
+                    import shutil
+                    from scipy.io import wavfile
+                    source = os.path.splitext(file)[0]
+                    for l in range(K):
+                        target = axis.wav_target(file, l)
+                        lo = l * int(offsets[-1]) + int(offsets[b])
+                        wavfile.write(target + '.WAV', framerate, waves[lo:lo + w.shape[0]])
+                        for ext in ('.FB', '.PHN', '.WRD'):
+                            if os.path.exists(source + ext):
+                                shutil.copyfile(source + ext, target + ext)
+                print("\t\t{}\tdone ! -> {}".format(file, out))
+                results[file] = res
+    return results
+
+
+def EvaluateNoiseSweep(files, SNRdBs, seed=0, hop=None, LPF=False, CUTOFF=50, model='last_trained_model', save_wavs=False,
+                       ctx=None, accuracy=None, resample=False):
+    """`cnn noisesweep` (not in the reference, whose EvaluateWithNoise :193-221 takes one file at one level): every file at
+    every level of SNRdBs and clean in one device pass per group of files (f2_eval_noise_sweep: the noise is drawn on the device
+    from (seed, level, file's place in its group, sample), so a sweep repeats bit for bit), with the clean run of the same
+    network as the referee. Per file, OutputWavFiles/addedNoise/<stem>.sweep.npz holds snr_db, sigma, windows, rising, agree,
+    agreement (= agree / windows, NaN without windows) - one entry per level, the clean level last - seed, hop and labels_<k>
+    for level k of snr_db (labels_clean for the clean one); one line per level is printed and the same data is returned as a dict per
+    file. save_wavs also writes <stem><SNR>dB.WAV with copies of the annotation files, as EvaluateWithNoise names and writes
+    them. Files are grouped like EvaluateRandom groups them: one framerate and sample type per call, 16 files per pass. hop=None
+    is hop 1.
+    With accuracy= every level of a file that has its .FB / .PHN is also scored against their labels (one f2_label_accuracy
+    call per group): the file's results gain accuracy_vtr (K+1) and confusion (K+1, 2, 2), [level][ref][pred], the clean level
+    last, and the printed lines the accuracy. With resample= the files are brought to the configured framerate first (one
+    device call per kind of file), the results gain framerate and source_framerate, and a file whose rate differed is left out
+    of the accuracy."""
+    if isinstance(files, (str, bytes, os.PathLike)):
+        files = [files]
+    snr = numpy.asarray(SNRdBs, dtype=numpy.float64).reshape(-1)
+    if not len(snr) or not numpy.isfinite(snr).all():
+        raise ValueError("a noise sweep needs at least one finite SNR in dB")
+    K = len(snr)
+
+    def call(ctx, handle, flat, dt, offsets, coefs, B, Cn, radius, STEP, hop, framerate, labels):
+        noisy = numpy.empty((K + 1) * int(offsets[-1]), numpy.float64) if save_wavs else None
+        wo, sigma, stats = ctx.eval_noise_sweep(handle, flat, dt, offsets, coefs, B, Cn, bool(LPF), CUTOFF if LPF else 0.0,
+                                                FFT_PRECISION, radius, STEP, hop, snr, seed, noisy, None, labels, _lib.MEM_HOST)
+        return wo, stats, noisy, sigma
+
+    def own(sigma, rows, wo, n, radius, STEP, hop, framerate):
+        return dict(snr_db=snr.copy(), sigma=sigma[rows].copy(), seed=numpy.uint64(int(seed) & (2 ** 64 - 1)))
+
+    outdir = os.path.join('OutputWavFiles', 'addedNoise')
+    axis = _SweepAxis(names=[_level_text(v) + 'dB' for v in snr], referee='clean', label="SNR {:>8}", limit=float('inf'), call=call,
+                      own=own, order=('snr_db', 'sigma', 'windows', 'rising', 'agree', 'agreement', 'seed', 'hop'),
+                      out=lambda file: os.path.join(outdir, os.path.basename(_noisy_copy_paths(file, 0)[0]) + '.sweep.npz'),
+                      outdir=outdir, wav_target=lambda file, l: _noisy_copy_paths(file, snr[l])[1])
+    return _run_sweep(axis, files, hop, model, ctx, accuracy, resample)
+
+
+# ---- `cnn lpfsweep`: one file at several envelope cutoffs (the modulation axis; not in the reference, whose route is one
+# `cnn eval --lpf HZ` per cutoff) ---------------------------------------------------------------------------------------------
 def EvaluateCutoffSweep(files, cutoffs, hop=None, model='last_trained_model', ctx=None, accuracy=None, resample=False):
     """`cnn lpfsweep`: every file at every envelope cutoff of `cutoffs` (Hz) and unfiltered in one device pass per group of
     files (f2_eval_cutoff_sweep: filterbank and Hilbert envelope run once, the first-order low-pass of EnvelopeExtraction.py:39-67
@@ -856,90 +882,25 @@ def EvaluateCutoffSweep(files, cutoffs, hop=None, model='last_trained_model', ct
     cut = numpy.asarray(cutoffs, dtype=numpy.float64).reshape(-1)
     if not len(cut) or not numpy.isfinite(cut).all() or (cut <= 0).any() or (cut >= 8000).any():
         raise ValueError("a cutoff sweep needs at least one finite cutoff in (0, 8000) Hz")
-    K = len(cut)
-    hop = 1 if hop is None else int(hop)
-    if accuracy is not None:
-        _accuracy_origin(accuracy, 0, 0)
-    ctx = ctx or _lib.default_context()
-    cfg = F2Config()
-    if not isinstance(model, F2CNNModel):
-        model = load_model(model)
-    read = _load(files, resample)
-    sources = {file: source for file, (source, _, _) in zip(files, read)}
-    groups = {}
-    for file, (_, framerate, wavArray) in zip(files, read):
-        wave, dt = filters._wave_args(wavArray)
-        groups.setdefault((framerate, dt), []).append((file, wave))
-    keys = [str(k) for k in range(K)] + ['nolpf']          # labels_<k>: level k of cutoff_hz
-    names = [_cutoff_text(v) + 'Hz' for v in cut] + ['nolpf']
-    results = {}
-    for (framerate, dt), members in groups.items():
-        coefs = numpy.ascontiguousarray(filters.make_erb_filters(framerate, filters.centre_freqs(framerate, cfg.nchannels,
-                                                                                                  cfg.low_freq)))
-        Cn = coefs.shape[0]
-        STEP = _step(framerate, cfg)
-        for group in _cutoff_groups(members, K, Cn):
-            B = len(group)
-            offsets = numpy.zeros(B + 1, numpy.int64)
-            offsets[1:] = numpy.cumsum([w.shape[0] for _, w in group])
-            flat = numpy.concatenate([w for _, w in group])
-            nbh = [_lib.strided_window_count(w.shape[0], cfg.radius, STEP, hop) for _, w in group]
-            scores = numpy.empty(((K + 1) * sum(nbh), 2), numpy.float32)
-            labels = numpy.empty((K + 1) * sum(nbh), numpy.uint8)
-            try:
-                wo, stats = ctx.eval_cutoff_sweep(model.handle(ctx), flat, dt, offsets, coefs, B, Cn, FFT_PRECISION, cfg.radius, STEP,
-                                                  hop, cut, None, scores, labels, _lib.MEM_HOST)
-            except _lib.F2Error as e:
-                if e.code == _lib.F2_ERR_NONPOSITIVE:
-                    raise ValueError("values must all be positive")
-                raise
-            assert list(numpy.diff(wo)) == nbh * (K + 1)
-            refs = [None] * B
-            if accuracy is not None:     # (the labels of a file whose rate differed count source samples)
-                refs = [ReferenceLabels(file) if sources[file] == framerate else None for file, _ in group]
-            confusions = None
-            if any(ref is not None for ref in refs):
-                confusions = _confusions(ctx, labels, wo, refs, accuracy, hop, STEP)
-            for b, (file, w) in enumerate(group):
-                rows = [l * B + b for l in range(K + 1)]
-                windows = numpy.array([wo[u + 1] - wo[u] for u in rows], numpy.int64)
-                rising, agree = stats[rows, 0].copy(), stats[rows, 1].copy()
-                with numpy.errstate(invalid='ignore', divide='ignore'):
-                    agreement = numpy.where(windows > 0, agree / windows.astype(numpy.float64), numpy.nan)
-                res = dict(cutoff_hz=cut.copy(), windows=windows, rising=rising, agree=agree, agreement=agreement,
-                           hop=numpy.int64(hop), timepoints=_lib.strided_timepoints(w.shape[0], cfg.radius, STEP, hop),
-                           scores=numpy.stack([scores[wo[u]:wo[u + 1]] for u in rows]),
-                           **_rate_keys(resample, framerate, sources[file]))
-                for key, u in zip(keys, rows):
-                    res['labels_' + key] = labels[wo[u]:wo[u + 1]].copy()
-                if refs[b] is not None:
-                    res['confusion'] = confusions[rows].copy()
-                    res['accuracy_vtr'] = _accuracy_of(res['confusion'])
-                out = os.path.splitext(file)[0] + '.lpfsweep.npz'
-                numpy.savez(out, **res)
-                print("File:\t\t{}".format(file))
-                if accuracy is not None and sources[file] != framerate:
-                    _no_rate_accuracy(file, sources[file], framerate)
-                elif accuracy is not None and refs[b] is None:
-                    _no_side_files(file)
-                for l in range(K + 1):
-                    line = "\tcutoff {:>8}\t{} windows\t{} rising\tagreement with nolpf {:.4f}".format(
-                        names[l], windows[l], rising[l], agreement[l])
-                    if refs[b] is not None:
-                        line += "\taccuracy against the VTR labels ({}) {:.4f}".format(accuracy, res['accuracy_vtr'][l])
-                    print(line)
-                print("\t\t{}\tdone ! -> {}".format(file, out))
-                results[file] = res
-    return results
+
+    def call(ctx, handle, flat, dt, offsets, coefs, B, Cn, radius, STEP, hop, framerate, labels):
+        scores = numpy.empty((len(labels), 2), numpy.float32)
+        wo, stats = ctx.eval_cutoff_sweep(handle, flat, dt, offsets, coefs, B, Cn, FFT_PRECISION, radius, STEP, hop, cut, None, scores,
+                                          labels, _lib.MEM_HOST)
+        return wo, stats, None, scores
+
+    def own(scores, rows, wo, n, radius, STEP, hop, framerate):
+        return dict(cutoff_hz=cut.copy(), timepoints=_lib.strided_timepoints(n, radius, STEP, hop),
+                    scores=numpy.stack([scores[wo[u]:wo[u + 1]] for u in rows]))
+
+    axis = _SweepAxis(names=[_level_text(v) + 'Hz' for v in cut], referee='nolpf', label="cutoff {:>8}", limit=LEVELS_LIMIT, call=call,
+                      own=own, order=('cutoff_hz', 'windows', 'rising', 'agree', 'agreement', 'hop', 'timepoints', 'scores'),
+                      out=lambda file: os.path.splitext(file)[0] + '.lpfsweep.npz', outdir=None, wav_target=None)
+    return _run_sweep(axis, files, hop, model, ctx, accuracy, resample)
 
 
 # ---- `cnn reverbsweep`: one file at several reverberation times (the room axis; not in the reference, whose only route is a
 # host convolution, a WAV per room and one `cnn eval` per WAV) ---------------------------------------------------------------
-def _t60_text(t60):
-    """how a level is printed and named: 0.4 -> '0.4', 1.0 -> '1'"""
-    return '{:g}'.format(float(t60))
-
-
 def _reverb_copy_paths(file, name):
     """Where `cnn reverbsweep` puts its outputs: OutputWavFiles/reverb/<stem><name>.*"""
     stem = os.path.basename(os.path.splitext(file)[0])
@@ -961,8 +922,6 @@ def EvaluateReverbSweep(files, t60s=(), rirs=(), drr_db=0.0, seed=0, hop=None, L
     grouped like EvaluateNoiseSweep groups them: one framerate and sample type per call, 16 files per pass. hop=None is hop 1.
     accuracy= and resample= as in EvaluateNoiseSweep: confusion (K+1, 2, 2) and accuracy_vtr (K+1) per file that has its .FB /
     .PHN, framerate and source_framerate. The arguments are checked before any file is read."""
-    import shutil
-    from scipy.io import wavfile
     from ... import reverb
     if isinstance(files, (str, bytes, os.PathLike)):
         files = [files]
@@ -980,98 +939,26 @@ def EvaluateReverbSweep(files, t60s=(), rirs=(), drr_db=0.0, seed=0, hop=None, L
     drr_db = float(drr_db)
     if not numpy.isfinite(drr_db):
         raise ValueError("drr_db must be finite")
-    hop = 1 if hop is None else int(hop)
-    if accuracy is not None:
-        _accuracy_origin(accuracy, 0, 0)
-    ctx = ctx or _lib.default_context()
-    cfg = F2Config()
-    if not isinstance(model, F2CNNModel):
-        model = load_model(model)
-    read = _load(files, resample)
-    sources = {file: source for file, (source, _, _) in zip(files, read)}
-    groups = {}
-    for file, (_, framerate, wavArray) in zip(files, read):
-        wave, dt = filters._wave_args(wavArray)
-        groups.setdefault((framerate, dt), []).append((file, wave))
-    keys = [str(k) for k in range(K)] + ['dry']             # labels_<k> / rir_<k>: level k
-    names = ['T60 ' + _t60_text(v) + 's' for v in t60] + [os.path.basename(r) for r in rir_files] + ['dry']
-    suffixes = ['_T60_' + _t60_text(v) + 's' for v in t60] + ['_' + os.path.splitext(os.path.basename(r))[0] for r in rir_files]
-    results = {}
+    suffixes = ['_T60_' + _level_text(v) + 's' for v in t60] + ['_' + os.path.splitext(os.path.basename(r))[0] for r in rir_files]
     responses = {}                                # per framerate
-    BATCH = 16                                    # files per device pass, as EvaluateNoiseSweep
-    for (framerate, dt), members in groups.items():
+
+    def call(ctx, handle, flat, dt, offsets, coefs, B, Cn, radius, STEP, hop, framerate, labels):
         if framerate not in responses:
             responses[framerate] = [reverb.SyntheticRIR(v, framerate, drr_db, seed, level) for level, v in enumerate(t60)] + \
                                    [reverb.LoadRIR(r, framerate) for r in rir_files]
+        wet = numpy.empty((K + 1) * int(offsets[-1]), numpy.float64) if save_wavs else None
+        wo, stats = ctx.eval_reverb_sweep(handle, flat, dt, offsets, coefs, B, Cn, bool(LPF), CUTOFF if LPF else 0.0, FFT_PRECISION,
+                                          radius, STEP, hop, responses[framerate], wet, None, labels, _lib.MEM_HOST)
+        return wo, stats, wet, None
+
+    def own(_, rows, wo, n, radius, STEP, hop, framerate):
         hs = responses[framerate]
-        taps = numpy.array([len(h) for h in hs], numpy.int64)
-        coefs = numpy.ascontiguousarray(filters.make_erb_filters(framerate, filters.centre_freqs(framerate, cfg.nchannels,
-                                                                                                  cfg.low_freq)))
-        Cn = coefs.shape[0]
-        STEP = _step(framerate, cfg)
-        for s0 in range(0, len(members), BATCH):
-            group = members[s0:s0 + BATCH]
-            B = len(group)
-            offsets = numpy.zeros(B + 1, numpy.int64)
-            offsets[1:] = numpy.cumsum([w.shape[0] for _, w in group])
-            flat = numpy.concatenate([w for _, w in group])
-            nbh = [_lib.strided_window_count(w.shape[0], cfg.radius, STEP, hop) for _, w in group]
-            labels = numpy.empty((K + 1) * sum(nbh), numpy.uint8)
-            wet = numpy.empty((K + 1) * int(offsets[-1]), numpy.float64) if save_wavs else None
-            try:
-                wo, stats = ctx.eval_reverb_sweep(model.handle(ctx), flat, dt, offsets, coefs, B, Cn, bool(LPF),
-                                                  CUTOFF if LPF else 0.0, FFT_PRECISION, cfg.radius, STEP, hop, hs, wet, None,
-                                                  labels, _lib.MEM_HOST)
-            except _lib.F2Error as e:
-                if e.code == _lib.F2_ERR_NONPOSITIVE:
-                    raise ValueError("values must all be positive")
-                raise
-            assert list(numpy.diff(wo)) == nbh * (K + 1)
-            refs = [None] * B
-            if accuracy is not None:     # (the labels of a file whose rate differed count source samples)
-                refs = [ReferenceLabels(file) if sources[file] == framerate else None for file, _ in group]
-            confusions = None
-            if any(ref is not None for ref in refs):
-                confusions = _confusions(ctx, labels, wo, refs, accuracy, hop, STEP)
-            os.makedirs(os.path.join('OutputWavFiles', 'reverb'), exist_ok=True)
-            for b, (file, w) in enumerate(group):
-                rows = [l * B + b for l in range(K + 1)]
-                windows = numpy.array([wo[u + 1] - wo[u] for u in rows], numpy.int64)
-                rising, agree = stats[rows, 0].copy(), stats[rows, 1].copy()
-                with numpy.errstate(invalid='ignore', divide='ignore'):
-                    agreement = numpy.where(windows > 0, agree / windows.astype(numpy.float64), numpy.nan)
-                res = dict(t60=t60.copy(), rir_files=numpy.array(rir_files, dtype=str), drr_db=numpy.float64(drr_db),
-                           seed=numpy.int64(seed), taps=taps.copy(), windows=windows, rising=rising, agree=agree,
-                           agreement=agreement, hop=numpy.int64(hop), **_rate_keys(resample, framerate, sources[file]))
-                for key, u in zip(keys, rows):
-                    res['labels_' + key] = labels[wo[u]:wo[u + 1]].copy()
-                for k, h in enumerate(hs):
-                    res['rir_' + str(k)] = h.copy()
-                if refs[b] is not None:
-                    res['confusion'] = confusions[rows].copy()
-                    res['accuracy_vtr'] = _accuracy_of(res['confusion'])
-                source, target = _reverb_copy_paths(file, '')
-                out = target + '.reverbsweep.npz'
-                numpy.savez(out, **res)
-                print("File:\t\t{}".format(file))
-                if accuracy is not None and sources[file] != framerate:
-                    _no_rate_accuracy(file, sources[file], framerate)
-                elif accuracy is not None and refs[b] is None:
-                    _no_side_files(file)
-                for l in range(K + 1):
-                    line = "\t{:>12}\t{} windows\t{} rising\tagreement with dry {:.4f}".format(
-                        names[l], windows[l], rising[l], agreement[l])
-                    if refs[b] is not None:
-                        line += "\taccuracy against the VTR labels ({}) {:.4f}".format(accuracy, res['accuracy_vtr'][l])
-                    print(line)
-                if save_wavs:
-                    for l in range(K):
-                        _, target = _reverb_copy_paths(file, suffixes[l])
-                        lo = l * int(offsets[-1]) + int(offsets[b])
-                        wavfile.write(target + '.WAV', framerate, wet[lo:lo + w.shape[0]])
-                        for ext in ('.FB', '.PHN', '.WRD'):
-                            if os.path.exists(source + ext):
-                                shutil.copyfile(source + ext, target + ext)
-                print("\t\t{}\tdone ! -> {}".format(file, out))
-                results[file] = res
-    return results
+        return dict(t60=t60.copy(), rir_files=numpy.array(rir_files, dtype=str), drr_db=numpy.float64(drr_db), seed=numpy.int64(seed),
+                    taps=numpy.array([len(h) for h in hs], numpy.int64), **{'rir_' + str(k): h.copy() for k, h in enumerate(hs)})
+
+    axis = _SweepAxis(names=['T60 ' + _level_text(v) + 's' for v in t60] + [os.path.basename(r) for r in rir_files], referee='dry',
+                      label="{:>12}", limit=float('inf'), call=call, own=own,
+                      order=('t60', 'rir_files', 'drr_db', 'seed', 'taps', 'windows', 'rising', 'agree', 'agreement', 'hop'),
+                      out=lambda file: _reverb_copy_paths(file, '')[1] + '.reverbsweep.npz',
+                      outdir=os.path.join('OutputWavFiles', 'reverb'), wav_target=lambda file, l: _reverb_copy_paths(file, suffixes[l])[1])
+    return _run_sweep(axis, files, hop, model, ctx, accuracy, resample)

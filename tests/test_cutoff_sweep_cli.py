@@ -187,14 +187,23 @@ def test_evaluate_cutoff_sweep_groups_and_writes(workdir, capsys):
     assert [c["B"] for c in stub.calls] == [16, 2, 1]
     assert stub.calls[0]["lengths"] == lengths[:16] and stub.calls[1]["lengths"] == lengths[16:] and stub.calls[2]["lengths"] == [2500]
     assert [c["step"] for c in stub.calls] == [160, 160, 80] and all(c["cutoffs"] == [5.0, 50.5] and c["hop"] == 160 for c in stub.calls)
-    assert sorted(res) == sorted(files)
+    assert list(res) == files
     K = 2
-    for i, file in enumerate(files[:18]):
+    expected = ""
+    for i, file in enumerate(files):
         out = os.path.splitext(file)[0] + ".lpfsweep.npz"
-        saved = dict(np.load(out))
-        assert sorted(saved) == sorted(["cutoff_hz", "windows", "rising", "agree", "agreement", "hop", "timepoints", "scores", "labels_0",
-                                        "labels_1", "labels_nolpf"])
-        n = _lib.strided_window_count(lengths[i], RADIUS, STEP, 160)
+        archive = np.load(out)
+        assert list(archive.files) == list(res[file]) == ["cutoff_hz", "windows", "rising", "agree", "agreement", "hop", "timepoints",
+                                                          "scores", "labels_0", "labels_1", "labels_nolpf"]
+        n = _lib.strided_window_count(lengths[i], RADIUS, STEP, 160) if i < 18 else _lib.strided_window_count(2500, RADIUS, 80, 160)
+        expected += "File:\t\t{}\n".format(file)
+        for l, name in enumerate(("5Hz", "50.5Hz", "nolpf")):
+            rising = ((np.arange(n) + l + (i % 16 if i < 18 else 0)) % 2 == 0).sum()
+            expected += "\tcutoff {:>8}\t{} windows\t{} rising\tagreement with nolpf {:.4f}\n".format(name, n, rising, (1.0, 0.0, 1.0)[l])
+        expected += "\t\t{}\tdone ! -> {}\n".format(file, out)
+        if i >= 18:
+            continue
+        saved = dict(archive)
         b = i % 16
         assert saved["windows"].tolist() == [n] * (K + 1) and int(saved["hop"]) == 160 and saved["cutoff_hz"].tolist() == [5.0, 50.5]
         assert saved["scores"].shape == (K + 1, n, 2) and saved["scores"].dtype == np.float32
@@ -208,6 +217,7 @@ def test_evaluate_cutoff_sweep_groups_and_writes(workdir, capsys):
     printed = capsys.readouterr().out
     assert printed.count("agreement with nolpf") == 19 * (K + 1) and "50.5Hz" in printed and "nolpf" in printed
     assert printed.count("File:") == 19
+    assert printed == expected
 
 
 def test_groups_shrink_where_the_levels_would_not_fit():

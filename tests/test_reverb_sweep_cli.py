@@ -277,16 +277,24 @@ def test_evaluate_reverb_sweep_groups_and_writes(workdir, capsys):
     for l in range(2):
         want = reverb.SyntheticRIR((0.05, 0.2)[l], 16000, 3.0, 5, l)
         assert all(np.array_equal(c["rirs"][l], want) for c in stub.calls[:2])
-    assert sorted(res) == sorted(files)
+    assert list(res) == files
     K = 2
+    expected = ""
     for i, file in enumerate(files):
         stem = os.path.basename(os.path.splitext(file)[0])
-        saved = dict(np.load(os.path.join("OutputWavFiles", "reverb", stem + ".reverbsweep.npz")))
-        assert sorted(saved) == sorted(["t60", "rir_files", "drr_db", "seed", "taps", "windows", "rising", "agree", "agreement", "hop",
-                                        "labels_0", "labels_1", "labels_dry", "rir_0", "rir_1"])
+        out = os.path.join("OutputWavFiles", "reverb", stem + ".reverbsweep.npz")
+        archive = np.load(out)
+        assert list(archive.files) == list(res[file]) == ["t60", "rir_files", "drr_db", "seed", "taps", "windows", "rising", "agree",
+                                                          "agreement", "hop", "labels_0", "labels_1", "labels_dry", "rir_0", "rir_1"]
+        saved = dict(archive)
         rate, n_samples = (16000, lengths[i]) if i < 18 else (8000, 2500)
         n = _lib.strided_window_count(n_samples, RADIUS, rate // 100, 160)
         b = i % 16 if i < 18 else 0
+        expected += "File:\t\t{}\n".format(file)
+        for l, name in enumerate(("T60 0.05s", "T60 0.2s", "dry")):
+            expected += "\t{:>12}\t{} windows\t{} rising\tagreement with dry {:.4f}\n".format(
+                name, n, ((np.arange(n) + l + b) % 2 == 0).sum(), (1.0, 0.0, 1.0)[l])
+        expected += "\t\t{}\tdone ! -> {}\n".format(file, out)
         assert saved["windows"].tolist() == [n] * (K + 1) and int(saved["hop"]) == 160 and saved["t60"].tolist() == [0.05, 0.2]
         assert float(saved["drr_db"]) == 3.0 and int(saved["seed"]) == 5 and saved["rir_files"].shape == (0,)
         assert saved["taps"].tolist() == [rate // 20, rate // 5]
@@ -300,6 +308,7 @@ def test_evaluate_reverb_sweep_groups_and_writes(workdir, capsys):
     printed = capsys.readouterr().out
     assert printed.count("agreement with dry") == 19 * (K + 1) and "T60 0.05s" in printed and "T60 0.2s" in printed
     assert printed.count("File:") == 19 and printed.count("done !") == 19
+    assert printed == expected
 
 
 def test_measured_responses_low_pass_and_saved_wavs(workdir, capsys):
@@ -325,8 +334,17 @@ def test_measured_responses_low_pass_and_saved_wavs(workdir, capsys):
         rate, data = wavfile.read(target + ".WAV")
         assert rate == 16000 and np.array_equal(data, dry * (l + 1))
         assert os.path.exists(target + ".PHN") and os.path.exists(target + ".WRD") and not os.path.exists(target + ".FB")
+    assert list(res) == ["t60", "rir_files", "drr_db", "seed", "taps", "windows", "rising", "agree", "agreement", "hop", "labels_0",
+                         "labels_1", "labels_dry", "rir_0", "rir_1"]
+    assert sorted(os.listdir(os.path.join("OutputWavFiles", "reverb"))) == sorted(
+        [stem + ".reverbsweep.npz"] + [stem + name + ext for name in ("_T60_0.1s", "_room") for ext in (".WAV", ".PHN", ".WRD")])
     printed = capsys.readouterr().out
     assert "room.wav" in printed and printed.count("agreement with dry") == 3
+    n = _lib.strided_window_count(2600, RADIUS, STEP, 1)
+    assert printed == "File:\t\t{}\n".format(file) + "".join(
+        "\t{:>12}\t{} windows\t{} rising\tagreement with dry {:.4f}\n".format(name, n, n // 2, agreement)
+        for name, agreement in (("T60 0.1s", 1.0), ("room.wav", 0.0), ("dry", 1.0))) + \
+        "\t\t{}\tdone ! -> {}\n".format(file, os.path.join("OutputWavFiles", "reverb", stem + ".reverbsweep.npz"))
 
 
 @pytest.mark.parametrize("kw", [dict(), dict(t60s=[0]), dict(t60s=[float("nan")]), dict(t60s=[0.2, -1]), dict(t60s=[0.1] * 65),

@@ -15,7 +15,10 @@ normalize 0 / 1 and three groups; the create-time *_check_diff values. The later
 (profiles/r18_a_old_new_identity.txt; tests/test_gpu_output_placement.py: radius 5, step 160, utterances of 1761, 2500 and 1000
 samples, an 11 x 10 network, 8 channels for the pictures), host and device memory, every output in the digest:
 f2_eval_batch_strided at hop 1 and 160, f2_eval_noise_sweep with 2 levels and a fixed seed, f2_label_accuracy on its labels,
-f2_envelope_picture / f2_gammatonegram_batch with both pools, f2_resample_batch at 3 : 2 and at the identity."""
+f2_envelope_picture / f2_gammatonegram_batch with both pools, f2_resample_batch at 3 : 2 and at the identity. The three sweeps
+(profiles/r23_a_old_new_identity.txt): f2_eval_noise_sweep, f2_eval_cutoff_sweep and f2_eval_reverb_sweep with K = 2 on utterances
+of 3000, 1000 (shorter than a window) and 2100 samples, int16 and float64, hop 16 and hop = STEP, host and device memory, the
+optional outputs given and left out; levels, scores, labels, window offsets, sigma and stats in the digest."""
 import hashlib, json, os, sys
 import numpy as np
 
@@ -161,6 +164,42 @@ def entry_cases(ctx, res):
     print("later entry points done", flush=True)
 
 
+def sweep_cases(ctx, res):
+    from f2cnn_amd import _lib
+    from f2cnn_amd.gammatone import filters
+    from f2cnn_amd.model import F2CNNModel
+    import f2cnn_oracle as orc
+    lens, CN, K = [3000, 1000, 2100], 10, 2
+    B = len(lens)
+    offs = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+    total = int(offs[-1])
+    i16 = np.concatenate([orc.synth_utterance(700 + i, n) for i, n in enumerate(lens)])
+    coefs = filters.make_erb_filters(16000, filters.centre_freqs(16000, CN, 100))
+    h = F2CNNModel.glorot(7, R, CN, zero_bias=False).handle(ctx)
+    rng = np.random.default_rng(23)
+    rirs = [np.concatenate([[1.0], 0.1 * rng.standard_normal(n - 1) * np.exp(-np.arange(1, n) / (n / 7.0))]) for n in (300, 1500)]
+    tail = (coefs, B, CN, True, 50.0, _lib.FFT_F32, RADIUS, STEP)
+    sweeps = [     # name, doubles of a level per sample, the call
+        ("f2_eval_noise_sweep", 1, lambda w, dt, hop, lv, sc, lb, mem: ctx.eval_noise_sweep(
+            h, w, dt, offs, *tail, hop, np.array([20.0, 5.0]), 1234, lv, sc, lb, mem)),
+        ("f2_eval_cutoff_sweep", CN, lambda w, dt, hop, lv, sc, lb, mem: ctx.eval_cutoff_sweep(
+            h, w, dt, offs, coefs, B, CN, _lib.FFT_F32, RADIUS, STEP, hop, np.array([8.0, 50.0]), lv, sc, lb, mem)),
+        ("f2_eval_reverb_sweep", 1, lambda w, dt, hop, lv, sc, lb, mem: ctx.eval_reverb_sweep(h, w, dt, offs, *tail, hop, rirs, lv, sc, lb, mem)),
+    ]
+    for dname, dt, wave in (("int16", _lib.WAVE_I16, i16), ("float64", _lib.WAVE_F64, i16.astype(np.float64))):
+        for hop in (16, STEP):
+            n = (K + 1) * sum(_lib.strided_window_count(x, RADIUS, STEP, hop) for x in lens)
+            for name, per, call in sweeps:
+                for mname, mem in (("host", _lib.MEM_HOST), ("device", _lib.MEM_DEVICE)):
+                    for given in (True, False):
+                        o = [np.zeros((K + 1) * per * total), np.zeros(2 * n, np.float32), np.zeros(n, np.uint8)] if given else [None] * 3
+                        small = call(wave, dt, hop, *o, mem) if mem == _lib.MEM_HOST else on_device(
+                            ctx, [wave] + o, lambda w, lv, sc, lb: call(w, dt, hop, lv, sc, lb, mem))
+                        res[f"{name}: {dname}, hop {hop}, {mname} memory, optional outputs {'given' if given else 'left out'}"] = digest(
+                            *[a for a in o if a is not None], *[np.asarray(a) for a in small])
+    print("sweeps done", flush=True)
+
+
 def keep_arrays(keep, key, arrays, lens=None, C=None, envelopes=()):
     """the outputs of one case under KEEP_DIR: a<i>.npy each; `envelopes` = the indices of the arrays laid out
     [utterance][channel][sample] for utterances of `lens` samples and C channels"""
@@ -245,6 +284,7 @@ def run(lib, out, keep=None):
             print(tag, "done", flush=True)
     cnn_cases(ctx, res)
     entry_cases(ctx, res)
+    sweep_cases(ctx, res)
     ctx.close()
     with open(out, "w") as f:
         json.dump(res, f, indent=1)
