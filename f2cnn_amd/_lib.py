@@ -22,6 +22,9 @@ K_COUNT = 7
 # tile constants of k_reverb_levels (csrc/f2_internal.h: F2_REVERB_BLOCK outputs per workgroup, F2_REVERB_TAP_CHUNK taps per staged
 # span) and the longest impulse response f2_reverb_levels takes (F2_REVERB_MAX_TAPS)
 REVERB_BLOCK, REVERB_TAP_CHUNK, REVERB_MAX_TAPS = 1024, 1024, 32768
+# tile constants of k_channel_mix_levels (csrc/f2_internal.h: F2_SMEAR_TILE_SAMPLES samples by F2_SMEAR_TILE_CHANNELS output channels
+# per workgroup) and the most channels and levels f2_channel_mix_levels takes (F2_SMEAR_MAX_CHANNELS, F2_SMEAR_MAX_LEVELS)
+SMEAR_TILE_SAMPLES, SMEAR_TILE_CHANNELS, SMEAR_MAX_CHANNELS, SMEAR_MAX_LEVELS = 512, 16, 512, 64
 
 _vp, _i, _i64, _d = C.c_void_p, C.c_int, C.c_int64, C.c_double
 _P = C.POINTER
@@ -86,6 +89,8 @@ SIGNATURES = {
     "f2_reverb_levels": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _i]),
     "f2_eval_reverb_sweep": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _d, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp,
                                   _i]),
+    "f2_channel_mix_levels": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _vp, _i]),
+    "f2_eval_smear_sweep": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _d, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i]),
 }
 
 _lib = None
@@ -454,6 +459,32 @@ class Context:
                                                  _ptr(labels), _ptr(window_offsets), _ptr(stats), mem_space))
         return window_offsets, stats
 
+    def channel_mix_levels(self, env, offsets, B, Cn, mix, levels, mem_space):
+        """Envelopes that are already in memory through every mixing matrix of `mix` ((K, Cn, Cn) float64, mix[l][c][c'] the
+        weight of input channel c' in output channel c; always a host array) and unchanged, in one device pass (see
+        f2_channel_mix_levels): env holds the ragged (Cn, n_b) float64 blocks of the batch, levels receives (K+1) * Cn *
+        offsets[B] float64, level-major, the copy last (numpy arrays or device pointers, by mem_space)."""
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        mix = _pack_mix(mix, Cn)
+        self.check(self.lib.f2_channel_mix_levels(self.handle, _ptr(env), _ptr(offsets), int(B), int(Cn), _ptr(mix) if len(mix) else None,
+                                                  len(mix), _ptr(levels), mem_space))
+
+    def eval_smear_sweep(self, handle, wave, wave_dtype, offsets, coefs, B, Cn, lpf, cutoff, precision, radius, step, hop, mix,
+                         env_levels, scores, labels, mem_space, window_offsets=None, stats=None):
+        """The batch at every mixing matrix of `mix` ((K, Cn, Cn) float64, host) and sharp, in one device pass (see
+        f2_eval_smear_sweep): utterance l * B + b of the evaluated batch is utterance b at level l, the sharp level last.
+        env_levels / scores / labels (numpy arrays or device pointers, by mem_space) may be None. Returns (window_offsets
+        ((K+1)*B + 1, int64), stats ((K+1)*B, 2) int64: rising windows, windows labelled as the sharp level labels them),
+        allocating those it is not given."""
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        mix = _pack_mix(mix, Cn)
+        window_offsets, stats, _ = _sweep_outputs((len(mix) + 1) * int(B), window_offsets, stats)
+        self.check(self.lib.f2_eval_smear_sweep(self.handle, handle, _ptr(wave), wave_dtype, _ptr(offsets), _ptr(coefs), int(B), Cn,
+                                                int(bool(lpf)), float(cutoff), precision, radius, step, int(hop),
+                                                _ptr(mix) if len(mix) else None, len(mix), _ptr(env_levels), _ptr(scores),
+                                                _ptr(labels), _ptr(window_offsets), _ptr(stats), mem_space))
+        return window_offsets, stats
+
     def label_accuracy(self, labels, window_offsets, ref_offsets, ref_timepoints, ref_signs, origin, hop, step, mem_space,
                        counts=None):
         """The labels of a strided evaluation against reference labels (see f2_label_accuracy): utterance u owns rows
@@ -659,6 +690,18 @@ def _pack_rirs(rirs):
     rir_offsets[1:] = np.cumsum([len(h) for h in rirs])
     taps = np.concatenate(rirs) if rirs else np.zeros(0, np.float64)
     return np.ascontiguousarray(taps), rir_offsets
+
+
+def _pack_mix(mix, Cn):
+    """the (K, Cn, Cn) float64 matrices of f2_channel_mix_levels as one contiguous array (K = 0 for an empty sequence)"""
+    mix = np.ascontiguousarray(mix, dtype=np.float64)
+    if mix.size == 0:
+        return np.zeros((0, int(Cn), int(Cn)), np.float64)
+    if mix.ndim == 2:
+        mix = mix[None]
+    if mix.ndim != 3 or mix.shape[1:] != (int(Cn), int(Cn)):
+        raise ValueError("mixing matrices must have the shape (K, {0}, {0}), not {1}".format(int(Cn), mix.shape))
+    return np.ascontiguousarray(mix)
 
 
 def resampled_length(n, up, down):

@@ -34,6 +34,14 @@ package implements:
                                                              WAV files at the file's rate - agreement with the dry decisions per
                                                              level, written to OutputWavFiles/reverb/<stem>.reverbsweep.npz; takes
                                                              no --figure or --occlusion; not in the reference)
+    python -m f2cnn_amd cnn smearsweep --file/-f WAV [--spreads 0.5,1,2,4] [--bands 32,16,8] [--hop N|frame] [--lpf HZ] [--accuracy [MODE]] [--resample] [--model/-m NPZ]
+                                                            (the file at every spectral resolution and sharp in one device pass -
+                                                             filterbank and envelope run once; --spreads: channel interaction, a
+                                                             Gaussian spread in ERB across the channels' envelopes; --bands: an
+                                                             N-band vocoder, every channel replaced by the mean of its band; at
+                                                             least one of the two - agreement with the sharp decisions per level,
+                                                             written to <base>.smearsweep.npz; takes no --figure or --occlusion;
+                                                             not in the reference)
     python -m f2cnn_amd cnn evalrand [--count/-c N] [--lpf HZ] [--model/-m NPZ] [--hop N|frame]
     (--hop: a decision every N samples instead of every sample, `frame` = one per STEP of configF2CNN.conf; not in the reference)
     (eval / evalnoise / evalrand / noisesweep also take --accuracy [reference|centre]: the decisions against the labels of the
@@ -67,7 +75,7 @@ organize needs the licensed TIMIT+VTR corpora and stays with the reference.
 import argparse
 
 PREPARE = ("filter", "envelope", "label", "input", "features")
-CNN = ("train", "test", "eval", "evalnoise", "evalrand", "noisesweep", "lpfsweep", "reverbsweep")
+CNN = ("train", "test", "eval", "evalnoise", "evalrand", "noisesweep", "lpfsweep", "reverbsweep", "smearsweep")
 PLOT = ("gtg",)
 
 
@@ -118,6 +126,29 @@ def t60_argument(text):
     if not t60s or not all(math.isfinite(v) and v > 0 for v in t60s):
         raise argparse.ArgumentTypeError("--t60 takes a comma-separated list of positive reverberation times in seconds, not {!r}".format(text))
     return t60s
+
+
+def spreads_argument(text):
+    """--spreads: a comma-separated list of at least one finite, positive spread in ERB"""
+    import math
+    try:
+        spreads = [float(part) for part in text.split(',')]
+    except ValueError:
+        spreads = []
+    if not spreads or not all(math.isfinite(v) and v > 0 for v in spreads):
+        raise argparse.ArgumentTypeError("--spreads takes a comma-separated list of positive spreads in ERB, not {!r}".format(text))
+    return spreads
+
+
+def bands_argument(text):
+    """--bands: a comma-separated list of at least one positive whole number of bands"""
+    try:
+        bands = [int(part) for part in text.split(',')]
+    except ValueError:
+        bands = []
+    if not bands or not all(v >= 1 for v in bands):
+        raise argparse.ArgumentTypeError("--bands takes a comma-separated list of positive whole numbers of bands, not {!r}".format(text))
+    return bands
 
 
 def rir_argument(text):
@@ -183,6 +214,10 @@ def build_parser():
                    help="reverbsweep: comma-separated mono WAV files with measured impulse responses at the file's rate")
     c.add_argument('--drr', action='store', type=drr_argument, dest='drr', default=argparse.SUPPRESS,
                    help="reverbsweep: direct-to-reverberant ratio of the synthetic responses in dB (default 0)")
+    c.add_argument('--spreads', action='store', type=spreads_argument, dest='spreads', default=argparse.SUPPRESS,
+                   help="smearsweep: comma-separated spreads of the channel interaction in ERB, e.g. 0.5,1,2,4")
+    c.add_argument('--bands', action='store', type=bands_argument, dest='bands', default=argparse.SUPPRESS,
+                   help="smearsweep: comma-separated numbers of vocoder bands, e.g. 32,16,8")
     c.add_argument('--seed', action='store', type=int, dest='seed', help="noisesweep: seed of the noise (default 0)")
     c.add_argument('--save-wavs', action='store_true', dest='save_wavs',
                    help="noisesweep: also write the noisy WAV files, as evalnoise does")
@@ -275,6 +310,10 @@ SWEEPS = {
                     "response files",
                     lambda E, a, kw: E.EvaluateReverbSweep([a.file], t60s=getattr(a, 't60', ()), rirs=getattr(a, 'rir', ()),
                                                            drr_db=getattr(a, 'drr', 0.0), seed=a.seed or 0, save_wavs=a.save_wavs, **kw)),
+    'smearsweep': (True, None, "use eval {} for the sharp level", ('spreads', 'bands'),
+                   "Please use --spreads to give the channel interaction in ERB, e.g. --spreads 0.5,1,2,4, or --bands to give numbers "
+                   "of vocoder bands, e.g. --bands 32,16,8",
+                   lambda E, a, kw: E.EvaluateSmearSweep([a.file], spreads=getattr(a, 'spreads', ()), bands=getattr(a, 'bands', ()), **kw)),
 }
 
 

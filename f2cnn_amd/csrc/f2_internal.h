@@ -56,10 +56,13 @@ struct f2_ctx {
     f2_scratch xbuf;       // window tensor chunk between K3 and K4
     f2_scratch occ_src;    // f2_eval_occlusion_batch: the source windows of a chunk, which k_occlude_windows expands into xbuf
     f2_scratch dense_in;   // conv4 outputs (+ dense1 outputs) of the windows of several utterances: one dense launch for all
-    // the three sweeps, f2_lowpass_levels, f2_reverb_levels: the (K+1) x batch levels (float64 waveforms or envelopes) when the caller
+    // the four sweeps, f2_lowpass_levels, f2_reverb_levels, f2_channel_mix_levels: the (K+1) x batch levels (float64 waveforms or envelopes) when the caller
     // gives no device buffer. One area: each of these calls places one set of levels, and nothing they nest (f2_eval_batch_strided,
     // with or without lpf; eval_envelopes) places another.
     f2_scratch levels;
+    // f2_channel_mix_levels, f2_eval_smear_sweep: tile sums, tile spans and the transposed mixing matrices of the call in flight (up to
+    // 134 MB at 64 levels of 512 channels: too much for `meta`). Reserved once per call, before its first launch.
+    f2_scratch mix;
     // The small arrays of the call in flight (f2_meta_carve): sigma / stats / window offsets of the noise sweep, filter coefficients /
     // stats / window offsets of the cutoff sweep, taps / tile sums / stats / window offsets of the reverberation sweep, counts and reference
     // labels of f2_label_accuracy, counts / loss sums / loss partials of f2_cnn_score_windows, span records and range words of the
@@ -524,6 +527,28 @@ int f2_check_rir(f2_ctx* ctx, const double* rir, const int64_t* rir_offsets, int
 void f2_reverb_meta(f2_meta_carve* meta, int B, const int64_t* rir_offsets, int K, f2_reverb_arrays* A);
 int f2_launch_reverb_levels(f2_ctx* ctx, const void* d_wave, int wave_dtype, const int64_t* d_offsets, const int64_t* h_offsets, int B,
                             const double* rir, const int64_t* rir_offsets, int K, const f2_reverb_arrays& A, double* d_out);
+// f2_smear.hip, the kernel of f2_channel_mix_levels / f2_eval_smear_sweep. A workgroup of k_channel_mix_levels makes
+// F2_SMEAR_TILE_CHANNELS output channels of F2_SMEAR_TILE_SAMPLES consecutive samples of one utterance at one level.
+// f2_check_mix: K in 1 .. F2_SMEAR_MAX_LEVELS and mix non-NULL (F2_ERR_INVALID; too many levels, or C above
+// F2_SMEAR_MAX_CHANNELS: F2_ERR_UNSUPPORTED), every weight finite (F2_ERR_INVALID, the message names level, row and column); in the
+// same walk it finds every row's support, folds them into the span of each channel tile and builds the image the kernel reads
+// (wT[l][c'][c] = mix[l][c][c'], rows padded with zeros to Cpad = nct * F2_SMEAR_TILE_CHANNELS). f2_smear_reserve sizes ctx->mix
+// for a launch over B utterances (before the call's first launch); the launch uploads tile sums, spans and the image, reads the
+// (C, n_b) blocks of d_env (utterance b at C * d_offsets[b]) and writes (K + 1) * C * h_offsets[B] doubles, level-major, level K
+// the copy.
+#define F2_SMEAR_TILE_SAMPLES 512
+#define F2_SMEAR_TILE_CHANNELS 16
+#define F2_SMEAR_MAX_CHANNELS 512
+#define F2_SMEAR_MAX_LEVELS 64
+struct f2_smear_plan {
+    int K = 0, C = 0, Cpad = 0, nct = 0;      // nct: channel tiles
+    std::vector<double> wT;                   // K * C * Cpad
+    std::vector<int64_t> spans;               // K * nct: lo | hi << 32, the input channels lo .. hi - 1 a tile walks
+};
+int f2_check_mix(f2_ctx* ctx, const double* mix, int K, int C, f2_smear_plan* P);
+int f2_smear_reserve(f2_ctx* ctx, const f2_smear_plan& P, int B);
+int f2_launch_channel_mix_levels(f2_ctx* ctx, const double* d_env, const int64_t* d_offsets, const int64_t* h_offsets, int B,
+                                 const f2_smear_plan& P, double* d_levels);
 // f2_accuracy.hip, the kernel of f2_label_accuracy. d_counts (4 per utterance, zeroed by the caller)[4 u + 2 ref + pred] += rows
 // of utterance u (rows d_window_offsets[u] .. [u + 1] of d_labels, row j at sample origin + j * hop) that the rule of the header
 // counts against reference set u % R (d_ref_offsets: R + 1; timepoints strictly increasing inside a set, signs 0 / 1);

@@ -400,7 +400,7 @@ int f2_eval_batch_strided(f2_ctx* ctx, const f2_cnn* cnn, const void* wave, int 
 
 }  // extern "C"
 
-// ---- the robustness sweeps: K levels of one axis (noise, room, envelope cutoff) and the unchanged level of a ragged batch as ONE
+// ---- the robustness sweeps: K levels of one axis (noise, room, envelope cutoff, spectral resolution) and the unchanged level of a ragged batch as ONE
 // (K+1) * B-utterance batch in device memory - utterance l * B + b is utterance b at level l, the unchanged level last - evaluated
 // like f2_eval_batch_strided, its labels tallied against the unchanged level's on the device ----
 namespace {
@@ -503,6 +503,52 @@ int wave_sweep(f2_ctx* ctx, const f2_cnn* cnn, const f2_batch& X, int radius, in
     return F2_OK;
 }
 
+// A sweep whose levels are envelopes (envelope cutoff, spectral resolution): filterbank + envelope of the batch once (eval_envelopes,
+// as X asks for them); the K levels and the copy as ONE (K+1) * B-utterance batch of envelopes in ctx->levels or the caller's device
+// buffer; the window loop of f2_eval_batch_strided over that batch with the tiled offsets; the tally of its labels against level K.
+// One wait at the end (eval_cnn_end). Of the axis: level_check (sweep_begin); carve(meta) names its small arrays; ready() reserves
+// and uploads what its kernel needs beside the envelopes, before anything is launched; fill(d_env, d_offsets, total, d_levels)
+// queues the launch that fills the levels (the tiled offsets on the device start with the caller's).
+template <class LevelCheck, class Carve, class Ready, class Fill>
+int envelope_sweep(f2_ctx* ctx, const f2_cnn* cnn, const f2_batch& X, int radius, int step, int hop, int K, LevelCheck level_check,
+                   Carve carve, Ready ready, Fill fill, double* env_levels_or_null, float* scores_or_null, uint8_t* labels_or_null,
+                   int64_t* window_offsets_or_null, int64_t* stats_or_null) {
+    const int C = X.C, mem_space = X.mem_space;
+    eval_call E;
+    sweep_plan P;
+    F2_TRY(sweep_begin(ctx, cnn, X, radius, step, hop, K, level_check, true, window_offsets_or_null, stats_or_null, &E, &P));
+    if (P.total == 0) return F2_OK;
+
+    // small arrays and the levels first: nothing below reallocates what a queued kernel uses (eval_envelopes does not touch
+    // ctx->meta, ctx->levels or ctx->mix)
+    f2_meta_carve meta;
+    carve(&meta);
+    P.carve(&meta);
+    F2_TRY(meta.reserve(ctx));
+    f2_output levels;
+    F2_TRY(f2_place(ctx, ctx->levels, env_levels_or_null, sizeof(double) * ((size_t)K + 1) * (size_t)C * (size_t)P.total, mem_space, true,
+                    &levels));
+    F2_TRY(ready());
+    F2_TRY(eval_envelopes(ctx, &E, X, nullptr, P.n_total));
+    // the tiled offsets start with the clean ones: one device array serves the level kernel and the window stage
+    F2_TRY(f2_upload_offsets(ctx, P.tiled.data(), P.U));
+    F2_TRY(fill(E.d_env, (const int64_t*)ctx->offsets.ptr, P.total, levels.as<double>()));
+    F2_TRY(f2_copy_back(ctx, levels));
+    if (P.n_total == 0) {
+        F2_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        return F2_OK;
+    }
+    E.d_env = levels.as<double>();
+    const f2_batch XU = {nullptr, F2_WAVE_F64, P.tiled.data(), X.coefs, P.U, C, 0, 0.0, X.fft_precision, mem_space};
+    const int64_t chunk = P.n_total < CNN_CHUNK ? P.n_total : CNN_CHUNK;
+    F2_TRY(eval_cnn_begin(ctx, cnn, &E, chunk, P.n_total, C, scores_or_null, labels_or_null, mem_space, true));
+    F2_TRY(strided_window_loop(ctx, cnn, &E, XU, P.nbh, chunk, radius, step, hop, (float*)ctx->xbuf.ptr));
+    F2_TRY(eval_dense_flush(ctx, cnn, &E));   // the tally reads every label
+    F2_TRY(P.tally(ctx, E.out.labels.as<uint8_t>()));
+    F2_TRY(P.stats_back(ctx, stats_or_null));
+    return eval_cnn_end(ctx, cnn, &E);   // (waits for the stream)
+}
+
 }  // namespace
 
 extern "C" {
@@ -555,49 +601,38 @@ int f2_eval_reverb_sweep(f2_ctx* ctx, const f2_cnn* cnn, const void* wave, int w
         wet_or_null, scores_or_null, labels_or_null, window_offsets_or_null, stats_or_null);
 }
 
-// f2_eval_cutoff_sweep: filterbank + envelope of the batch once, unfiltered; its K low-passed levels and the copy as ONE
-// (K+1) * B-utterance batch of envelopes (f2_lowpass.hip); the window loop of f2_eval_batch_strided over that batch with the tiled
-// offsets; the tally of its labels against the unfiltered level. One wait at the end (eval_cnn_end).
+// f2_eval_cutoff_sweep: an envelope sweep whose levels come from k_lowpass_levels (f2_lowpass.hip), on the unfiltered envelopes. Only
+// the samples and the K coefficient pairs go up; one wait at the end.
 int f2_eval_cutoff_sweep(f2_ctx* ctx, const f2_cnn* cnn, const void* wave, int wave_dtype, const int64_t* offsets,
                          const double* coefs, int B, int C, int fft_precision, int radius, int step, int hop,
                          const double* cutoff_hz, int K, double* env_levels_or_null, float* scores_or_null, uint8_t* labels_or_null,
                          int64_t* window_offsets_or_null, int64_t* stats_or_null, int mem_space) {
     const f2_batch X = {wave, wave_dtype, offsets, coefs, B, C, 0, 0.0, fft_precision, mem_space};
-    eval_call E;
-    sweep_plan P;
-    F2_TRY(sweep_begin(ctx, cnn, X, radius, step, hop, K, [&] { return f2_check_cutoffs(ctx, cutoff_hz, K); }, true,
-                       window_offsets_or_null, stats_or_null, &E, &P));
-    if (P.total == 0) return F2_OK;
-
-    // small arrays and the levels first: nothing below reallocates what a queued kernel uses (eval_envelopes does not touch
-    // ctx->meta or ctx->levels)
     double* d_coef;
-    f2_meta_carve meta;
-    meta.add(&d_coef, 2 * (size_t)K);
-    P.carve(&meta);
-    F2_TRY(meta.reserve(ctx));
-    f2_output levels;
-    F2_TRY(f2_place(ctx, ctx->levels, env_levels_or_null, sizeof(double) * ((size_t)K + 1) * (size_t)C * (size_t)P.total, mem_space, true,
-                    &levels));
-    F2_TRY(f2_upload_lowpass_coefs(ctx, cutoff_hz, K, d_coef));
-    F2_TRY(eval_envelopes(ctx, &E, X, nullptr, P.n_total));
-    // the tiled offsets start with the clean ones: one device array serves the low-pass kernel and the window stage
-    F2_TRY(f2_upload_offsets(ctx, P.tiled.data(), P.U));
-    F2_TRY(f2_launch_lowpass_levels(ctx, E.d_env, (const int64_t*)ctx->offsets.ptr, B, C, P.total, d_coef, K, levels.as<double>()));
-    F2_TRY(f2_copy_back(ctx, levels));
-    if (P.n_total == 0) {
-        F2_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        return F2_OK;
-    }
-    E.d_env = levels.as<double>();
-    const f2_batch XU = {nullptr, F2_WAVE_F64, P.tiled.data(), coefs, P.U, C, 0, 0.0, fft_precision, mem_space};
-    const int64_t chunk = P.n_total < CNN_CHUNK ? P.n_total : CNN_CHUNK;
-    F2_TRY(eval_cnn_begin(ctx, cnn, &E, chunk, P.n_total, C, scores_or_null, labels_or_null, mem_space, true));
-    F2_TRY(strided_window_loop(ctx, cnn, &E, XU, P.nbh, chunk, radius, step, hop, (float*)ctx->xbuf.ptr));
-    F2_TRY(eval_dense_flush(ctx, cnn, &E));   // the tally reads every label
-    F2_TRY(P.tally(ctx, E.out.labels.as<uint8_t>()));
-    F2_TRY(P.stats_back(ctx, stats_or_null));
-    return eval_cnn_end(ctx, cnn, &E);   // (waits for the stream)
+    return envelope_sweep(
+        ctx, cnn, X, radius, step, hop, K, [&] { return f2_check_cutoffs(ctx, cutoff_hz, K); },
+        [&](f2_meta_carve* meta) { meta->add(&d_coef, 2 * (size_t)K); }, [&] { return f2_upload_lowpass_coefs(ctx, cutoff_hz, K, d_coef); },
+        [&](const double* d_env, const int64_t* d_offsets, int64_t total, double* d_levels) {
+            return f2_launch_lowpass_levels(ctx, d_env, d_offsets, B, C, total, d_coef, K, d_levels);
+        },
+        env_levels_or_null, scores_or_null, labels_or_null, window_offsets_or_null, stats_or_null);
+}
+
+// f2_eval_smear_sweep: an envelope sweep whose levels come from k_channel_mix_levels (f2_smear.hip), on the envelopes as the strided
+// call makes them (low-passed if lpf). Only the samples and the matrices go up; one wait at the end.
+int f2_eval_smear_sweep(f2_ctx* ctx, const f2_cnn* cnn, const void* wave, int wave_dtype, const int64_t* offsets,
+                        const double* coefs, int B, int C, int lpf, double cutoff_hz, int fft_precision, int radius, int step, int hop,
+                        const double* mix, int K, double* env_levels_or_null, float* scores_or_null, uint8_t* labels_or_null,
+                        int64_t* window_offsets_or_null, int64_t* stats_or_null, int mem_space) {
+    const f2_batch X = {wave, wave_dtype, offsets, coefs, B, C, lpf, cutoff_hz, fft_precision, mem_space};
+    f2_smear_plan M;
+    return envelope_sweep(
+        ctx, cnn, X, radius, step, hop, K, [&] { return f2_check_mix(ctx, mix, K, C, &M); }, [](f2_meta_carve*) {},
+        [&] { return f2_smear_reserve(ctx, M, B); },
+        [&](const double* d_env, const int64_t* d_offsets, int64_t, double* d_levels) {
+            return f2_launch_channel_mix_levels(ctx, d_env, d_offsets, offsets, B, M, d_levels);
+        },
+        env_levels_or_null, scores_or_null, labels_or_null, window_offsets_or_null, stats_or_null);
 }
 
 int f2_label_accuracy(f2_ctx* ctx, const uint8_t* labels, const int64_t* window_offsets, int U, const int64_t* ref_offsets,

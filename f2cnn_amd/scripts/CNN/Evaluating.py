@@ -962,3 +962,61 @@ def EvaluateReverbSweep(files, t60s=(), rirs=(), drr_db=0.0, seed=0, hop=None, L
                       out=lambda file: _reverb_copy_paths(file, '')[1] + '.reverbsweep.npz',
                       outdir=os.path.join('OutputWavFiles', 'reverb'), wav_target=lambda file, l: _reverb_copy_paths(file, suffixes[l])[1])
     return _run_sweep(axis, files, hop, model, ctx, accuracy, resample)
+
+
+# ---- `cnn smearsweep`: one file at several spectral resolutions (the twin of the modulation axis; not in the reference, and
+# without the device call a host matrix product per level on envelopes that had to come down first) ---------------------------
+def EvaluateSmearSweep(files, spreads=(), bands=(), hop=None, LPF=False, CUTOFF=50, model='last_trained_model', ctx=None,
+                       accuracy=None, resample=False):
+    """`cnn smearsweep`: every file at every spectral resolution and sharp in one device pass per group of files
+    (f2_eval_smear_sweep: filterbank and envelope run once - low-passed at CUTOFF if LPF - and every level is a linear map across
+    the channels of those envelopes, in float64), with the sharp run of the same network as the referee. The levels are the
+    `spreads` in the order given - channel interaction, a Gaussian of that many ERB (smear.SmearMatrix on the group's centre
+    frequencies) - then the `bands` - an N-band vocoder (smear.BandMatrix) - then `sharp`. Per file, <base>.smearsweep.npz next
+    to the WAV holds spread_erb (K, NaN for a band level), bands (K, 0 for a spread level), windows, rising, agree, agreement
+    (= agree / windows, NaN without windows) - K + 1 entries each, the sharp level last - hop, timepoints, scores (K + 1, n, 2)
+    and labels_<k> for level k (labels_sharp for the sharp one); one line per level is printed and the same data is returned as
+    a dict per file. Files are grouped like EvaluateCutoffSweep groups them - one framerate and sample type per call, up to 16
+    files, a group cut short where its levels would take more than 8 GiB. hop=None is hop 1. accuracy= and resample= as in
+    EvaluateNoiseSweep: confusion (K + 1, 2, 2) and accuracy_vtr (K + 1) per file that has its .FB / .PHN, framerate and
+    source_framerate. The arguments are checked before any file is read."""
+    from ... import smear
+    if isinstance(files, (str, bytes, os.PathLike)):
+        files = [files]
+    spread = numpy.asarray(spreads, dtype=numpy.float64).reshape(-1)
+    if not numpy.isfinite(spread).all() or (spread <= 0).any():
+        raise ValueError("a spread must be finite and positive (ERB)")
+    counts = numpy.asarray(bands).reshape(-1)
+    if len(counts) and (counts != numpy.floor(counts)).any():
+        raise ValueError("a number of bands must be a whole number")
+    counts = counts.astype(numpy.int64)
+    nchannels = F2Config().nchannels
+    if (counts < 1).any() or (counts > nchannels).any():
+        raise ValueError("a number of bands must lie between 1 and the {} channels".format(nchannels))
+    K = len(spread) + len(counts)
+    if K < 1:
+        raise ValueError("a smear sweep needs at least one spread or number of bands")
+    if K > 64:
+        raise ValueError("a smear sweep takes at most 64 levels, not {}".format(K))
+    matrices = {}                                 # per (framerate, channels)
+
+    def call(ctx, handle, flat, dt, offsets, coefs, B, Cn, radius, STEP, hop, framerate, labels):
+        if (framerate, Cn) not in matrices:
+            freqs = filters.centre_freqs(framerate, Cn, F2Config().low_freq)
+            matrices[framerate, Cn] = numpy.stack([smear.SmearMatrix(freqs, v) for v in spread] +
+                                                  [smear.BandMatrix(Cn, v) for v in counts])
+        scores = numpy.empty((len(labels), 2), numpy.float32)
+        wo, stats = ctx.eval_smear_sweep(handle, flat, dt, offsets, coefs, B, Cn, bool(LPF), CUTOFF if LPF else 0.0, FFT_PRECISION,
+                                         radius, STEP, hop, matrices[framerate, Cn], None, scores, labels, _lib.MEM_HOST)
+        return wo, stats, None, scores
+
+    def own(scores, rows, wo, n, radius, STEP, hop, framerate):
+        return dict(spread_erb=numpy.concatenate([spread, numpy.full(len(counts), numpy.nan)]),
+                    bands=numpy.concatenate([numpy.zeros(len(spread), numpy.int64), counts]),
+                    timepoints=_lib.strided_timepoints(n, radius, STEP, hop), scores=numpy.stack([scores[wo[u]:wo[u + 1]] for u in rows]))
+
+    axis = _SweepAxis(names=[_level_text(v) + 'ERB' for v in spread] + ['{}bands'.format(v) for v in counts], referee='sharp',
+                      label="smear {:>8}", limit=LEVELS_LIMIT, call=call, own=own,
+                      order=('spread_erb', 'bands', 'windows', 'rising', 'agree', 'agreement', 'hop', 'timepoints', 'scores'),
+                      out=lambda file: os.path.splitext(file)[0] + '.smearsweep.npz', outdir=None, wav_target=None)
+    return _run_sweep(axis, files, hop, model, ctx, accuracy, resample)

@@ -740,6 +740,66 @@ int f2_eval_reverb_sweep(f2_ctx* ctx, const f2_cnn* cnn, const void* wave, int w
                          uint8_t* labels_or_null, int64_t* window_offsets_or_null /* host, (K+1)*B + 1 */,
                          int64_t* stats_or_null /* host, (K+1)*B*2 */, int mem_space);
 
+/* ---- `cnn smearsweep`: one ragged batch at K spectral resolutions and sharp, in one device pass ------------------------------
+ * The front end is a bank of C channels plus envelopes - the signal of a channel vocoder. Its two standard degradations, channel
+ * interaction (envelopes leak into neighbouring channels) and a reduced number of bands, are linear maps across the channels of
+ * envelopes that are already in device memory: one kernel, and the rest is the cutoff sweep's middle. (f2_version stays 114 with
+ * these two entries: look the symbols up to find out whether a build has them.)
+ *
+ * f2_channel_mix_levels: env holds the ragged float64 envelopes of a batch as f2_envelope_batch delivers them - (C, n_b) blocks,
+ * utterance b at C * offsets[b]. mix holds K matrices (C, C), row-major: mix[l][c][c'] is the weight of input channel c' in output
+ * channel c. levels receives K+1 "levels", level-major, (K+1) * C * offsets[B] doubles: level l < K is mix[l] applied to every
+ * sample column, level K the input copied bit for bit. Level l, utterance b is utterance u = l*B + b of a (K+1)*B batch whose
+ * offsets are the caller's tiled: tiled[u] = l*offsets[B] + offsets[b] (the convention of f2_lowpass_levels).
+ *   arithmetic     for level l < K, row c, sample i: lo the first and hi one past the last c' with mix[l][c][c'] != 0 (the row's
+ *                  support, found on the host during the argument check); acc = +0.0; for c' = lo .. hi-1 ascending
+ *                  acc = fma(mix[l][c][c'], env[b][c'][i], acc); store acc. One float64 accumulator per output, no atomics, no
+ *                  sum split across lanes; zeros inside the support are walked; a row of zeros stores +0.0. The bits of a sample
+ *                  therefore depend on its envelope column and its matrix row alone - not on B, on the utterance's place in the
+ *                  batch, on K, on the other levels or rows, or on the memory space. The one liberty: a result that is a zero is
+ *                  stored as +0.0 (a -0.0 under an identity row comes out +0.0, and so does a sum that has underflowed to -0).
+ *                  The input is any finite float64; nothing assumes positive data. Rows of any length, 0 and 1 included; any
+ *                  C from 1 to 512 (F2_SMEAR_MAX_CHANNELS); K <= 64.
+ *   kernel         lanes run along time; one workgroup per (tile of 512 samples of one utterance, level, tile of 16 output
+ *                  channels), a lane owning 2 samples x 16 accumulators. It walks the union of the supports of its 16 rows (outside
+ *                  its own support a row's weights are zeros, which leave its accumulator alone): per input channel two 8-byte
+ *                  loads per lane - consecutive lanes, consecutive doubles, so a row may start at any 8-byte boundary - feed 32
+ *                  FMAs, whose weights are wave-uniform, come through the scalar load path from a transposed, zero-padded image of
+ *                  the matrices (built in the argument check, uploaded once per call) and enter the FMA as its scalar operand.
+ * mix is always a host pointer, like coefs. env and levels are in mem_space; device pointers need element alignment only.
+ * F2_MEM_DEVICE: the call enqueues on the context's stream and returns; F2_MEM_HOST: it returns when levels is filled.
+ * F2_ERR_INVALID, with nothing launched and levels untouched: a NULL ctx or offsets; offsets that do not start at 0 or that
+ * decrease; B < 0; C <= 0; K < 1; a NULL mix; a weight that is not finite (the message names level, row and column); NULL env or
+ * levels with offsets[B] > 0; a mem_space other than F2_MEM_HOST / F2_MEM_DEVICE. F2_ERR_UNSUPPORTED, likewise: K > 64; C > 512.
+ * B == 0 or offsets[B] == 0: F2_OK.
+ *
+ * f2_eval_smear_sweep: filterbank + envelope of the batch once (the two kernels of the eval calls; low-passed at cutoff_hz if lpf,
+ * so that a model trained on low-passed envelopes can be asked), f2_channel_mix_levels' kernel on the result, then the window stage
+ * and the network of f2_eval_batch_strided over the (K+1)*B batch of envelopes, and the tally of f2_eval_noise_sweep. Only the int16
+ * / float64 samples and the matrices go up; one wait at the end. Every output is optional.
+ *   env_levels_or_null   (K+1) * C * offsets[B] float64, level-major, in mem_space (a device buffer serves as the call's own
+ *           buffer; otherwise the levels live in context scratch). Bit for bit f2_channel_mix_levels of its own level K block.
+ *   scores_or_null, labels_or_null, window_offsets_or_null (host, (K+1)*B + 1)
+ *           Level K: bit for bit what f2_eval_batch_strided returns for the batch with the same lpf and cutoff_hz. Level l: bit
+ *           for bit f2_cnn_forward of the windows f2_gather_windows(normalize = 1) takes from level l's envelopes at centres
+ *           radius*step + j*hop.
+ *   stats_or_null   host, (K+1)*B*2: stats[2u] = windows of u labelled rising, stats[2u+1] = windows of u whose label equals
+ *           the sharp level's label for the same window of the same utterance (for level K: its window count).
+ * Errors, all before anything is launched or written: everything f2_eval_batch_strided rejects, by the same checks; then what
+ * f2_channel_mix_levels rejects of K, mix and C, with the same status; then (K+1)*B beyond what f2_eval_noise_sweep accepts:
+ * F2_ERR_UNSUPPORTED. F2_ERR_NONPOSITIVE as in the strided call: a matrix with a zero row, or with negative weights, can produce
+ * values <= 0. B == 0, or no utterance long enough for a window: F2_OK with window_offsets / stats filled. The call waits for the
+ * stream before it returns, whatever mem_space is.
+ */
+int f2_channel_mix_levels(f2_ctx* ctx, const double* env /* ragged (C, n_b) blocks, mem_space */, const int64_t* offsets /* host, B+1 */,
+                          int B, int C, const double* mix /* host, (K, C, C) */, int K,
+                          double* levels /* (K+1) * C * offsets[B], level-major, mem_space */, int mem_space);
+int f2_eval_smear_sweep(f2_ctx* ctx, const f2_cnn* cnn, const void* wave, int wave_dtype, const int64_t* offsets,
+                        const double* coefs, int B, int C, int lpf, double cutoff_hz, int fft_precision, int radius, int step, int hop,
+                        const double* mix /* host, (K, C, C) */, int K,
+                        double* env_levels_or_null, float* scores_or_null, uint8_t* labels_or_null,
+                        int64_t* window_offsets_or_null /* host, (K+1)*B + 1 */, int64_t* stats_or_null /* host, (K+1)*B*2 */, int mem_space);
+
 #ifdef __cplusplus
 }
 #endif
