@@ -84,6 +84,10 @@ SIGNATURES = {
     "f2_occlusion_map": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _i64, _i, _i, _vp, _i]),
     "f2_eval_occlusion_batch": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _d, _i, _i, _i, _i, _vp, _i, C.c_float, _vp, _i, _i, _vp,
                                      _vp, _vp, _vp, _vp, _vp, _vp, _i]),
+    "f2_cnn_input_gradient": (_i, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _i]),
+    "f2_saliency_map": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i64, _i, _i, _vp, _i]),
+    "f2_eval_saliency_batch": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _d, _i, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp,
+                                    _vp, _vp, _i]),
     "f2_lowpass_levels": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _vp, _i]),
     "f2_eval_cutoff_sweep": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i]),
     "f2_reverb_levels": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _i]),
@@ -653,6 +657,47 @@ class Context:
                                                     _ptr(patches) if K else None, K, fill, _ptr(spans), int(width), int(pool),
                                                     _ptr(levels), _ptr(range_out), _ptr(map_out), _ptr(summary), _ptr(scores),
                                                     _ptr(labels), _ptr(window_offsets), mem_space))
+        return window_offsets, range_out.reshape(-1, 2)
+
+    def cnn_input_gradient(self, handle, x, n, grad, profile, scores, mem_space):
+        """G = dP(rising)/dx of n windows (rows, channels) float32 by one backward-data pass on the device (see
+        f2_cnn_input_gradient). grad (n, rows, channels) float32, profile (n, channels, 2) float64 - sum over the rows of G x and
+        of |G| - and scores (n, 2) float32 of the recorded forward: numpy arrays or device pointers, by mem_space, any may be
+        None."""
+        self.check(self.lib.f2_cnn_input_gradient(self.handle, handle, _ptr(x), int(n), _ptr(grad), _ptr(profile), _ptr(scores),
+                                                  mem_space))
+
+    def saliency_map(self, profile, window_offsets, Cn, spans, origin, hop, width, map_out, mem_space):
+        """The profile rows (n, Cn, 2) float64 of cnn_input_gradient reduced to `width` time columns per utterance and channel (see
+        f2_saliency_map; rows, spans and columns as in score_track). `map_out` (U, Cn, width, 3) float64 - rows, mean of
+        profile[:, c, 0], mean of profile[:, c, 1]. profile / map_out: numpy arrays or device pointers, by mem_space. Returns
+        `map_out`."""
+        window_offsets = np.ascontiguousarray(window_offsets, dtype=np.int64)
+        U = len(window_offsets) - 1
+        spans = np.ascontiguousarray(spans, dtype=np.int64)
+        if spans.size != 2 * U:
+            raise ValueError("spans must hold (s_u, e_u) for each of the U utterances")
+        if isinstance(profile, np.ndarray):
+            profile = np.ascontiguousarray(profile, dtype=np.float64)
+        if isinstance(map_out, np.ndarray) and (map_out.dtype != np.float64 or map_out.size != 3 * U * max(int(Cn), 0) * int(width)
+                                                or not map_out.flags["C_CONTIGUOUS"]):
+            raise ValueError("map_out must be contiguous float64 (U, Cn, width, 3)")
+        self.check(self.lib.f2_saliency_map(self.handle, _ptr(profile), _ptr(window_offsets), U, int(Cn), _ptr(spans), int(origin),
+                                            int(hop), int(width), _ptr(map_out), mem_space))
+        return map_out
+
+    def eval_saliency_batch(self, handle, wave, wave_dtype, offsets, coefs, B, Cn, lpf, cutoff, precision, radius, step, hop, spans,
+                            width, pool, levels, map_out, summary, scores, labels, mem_space, range_out=None):
+        """eval_figure_batch with every window differentiated while it is in device scratch and the saliency map in the track's
+        place (see f2_eval_saliency_batch). levels (B, Cn, width) uint8, map_out (B, Cn, width, 3) and summary (B, Cn, 3) float64,
+        scores (n, 2) float32, labels (n) uint8: numpy arrays or device pointers, by mem_space, any may be None. Returns
+        (window_offsets (B + 1, int64), range (B, 2) float64)."""
+        offsets, spans, range_out = self._picture_args(offsets, B, spans, range_out)
+        window_offsets = np.zeros(max(int(B), 0) + 1, np.int64)
+        self.check(self.lib.f2_eval_saliency_batch(self.handle, handle, _ptr(wave), wave_dtype, _ptr(offsets), _ptr(coefs), int(B), Cn,
+                                                   int(bool(lpf)), float(cutoff), precision, radius, step, int(hop), _ptr(spans),
+                                                   int(width), int(pool), _ptr(levels), _ptr(range_out), _ptr(map_out), _ptr(summary),
+                                                   _ptr(scores), _ptr(labels), _ptr(window_offsets), mem_space))
         return window_offsets, range_out.reshape(-1, 2)
 
     def resample_batch(self, audio, pcm_format, channels, channel, offsets, B, up, down, taps, half_len, out, mem_space):

@@ -26,7 +26,7 @@ package implements:
                                                             (the file at every envelope cutoff and unfiltered in one device pass -
                                                              filterbank and Hilbert envelope run once - agreement with the
                                                              unfiltered decisions per cutoff, written to <base>.lpfsweep.npz; takes
-                                                             no --lpf, --figure or --occlusion; not in the reference)
+                                                             no --lpf, --figure, --occlusion or --saliency; not in the reference)
     python -m f2cnn_amd cnn reverbsweep --file/-f WAV --t60 0.2,0.4,0.8 [--rir room.wav[,hall.wav]] [--drr DB] [--seed N] [--save-wavs] [--hop N|frame] [--lpf HZ] [--accuracy [MODE]] [--resample] [--model/-m NPZ]
                                                             (the file in every room and dry in one device pass - synthetic
                                                              responses of the given reverberation times in seconds, direct-to-
@@ -63,6 +63,12 @@ package implements:
      line per band (Hz range, rows, flips, mean change of P(rising)), graphs/Occlusion/<basename>.png with the map under the
      gammatonegram, --figure-width columns wide, and occlusion_* keys in the .npz; scores and labels stay those without the
      flag; not in the reference)
+    (eval / evalnoise / evalrand also take --saliency [--saliency-bands N]: the saliency map - the gradient of P(rising) at every
+     cell of every normalised window from one backward pass on the device, whatever the resolution; one table line per N channels
+     (default 8: Hz range, rows, sum of the mean G x, sum of the mean |G|; the G x column reads against --occlusion 8:8 with the sign
+     reversed), graphs/Saliency/<basename>.png with the G x map under the gammatonegram, --figure-width columns wide, and
+     saliency_map, saliency_summary, saliency_span in the .npz; scores and labels stay those without the flag; one map per run,
+     so not together with --occlusion, and not on the sweeps; not in the reference)
     python -m f2cnn_amd plot gtg [--file/-f WAV | --all] [--width W] [--pool mean|max] [--cutoff HZ] [--formant N] [--start S --end E] [--out PNG]
                                                             (gammatonegram pictures, pooled to W columns and log-normalised on the
                                                              device, written as graphs/gtg/<basename>.png without matplotlib; the
@@ -249,6 +255,12 @@ def build_parser():
                    metavar='RBAND[:RSTRIDE]', help="--occlusion: blank bands of RBAND window rows as well (no picture then)")
     c.add_argument('--occlusion-fill', type=float, default=argparse.SUPPRESS, dest='occlusion_fill', metavar='V',
                    help="--occlusion: the value a blanked cell takes, in [0, 1] (default 0, a normalised window's minimum)")
+    c.add_argument('--saliency', action='store_true', default=argparse.SUPPRESS, dest='saliency',
+                   help="eval / evalnoise / evalrand: the saliency map - the gradient of P(rising) at every cell of every window, one "
+                        "backward pass on the device; a table per band of channels, saliency_* keys in the .npz and "
+                        "graphs/Saliency/<basename>.png, --figure-width columns wide; not together with --occlusion")
+    c.add_argument('--saliency-bands', type=int, default=argparse.SUPPRESS, dest='saliency_bands', metavar='N',
+                   help="--saliency: channels per line of the table (default 8)")
     g = sub.add_parser('plot', help='plotting commands')
     g.add_argument('plot_command', choices=PLOT)
     which = g.add_mutually_exclusive_group()
@@ -319,7 +331,8 @@ SWEEPS = {
 
 def sweep_refusal(args, no_lpf, instead):
     """says which option the sweep does not take, if one was given (an option that was not given is absent, None or False)"""
-    for attr, option, why in (('CUTOFF', '--lpf', no_lpf), ('figure', '--figure', instead), ('occlusion', '--occlusion', instead)):
+    for attr, option, why in (('CUTOFF', '--lpf', no_lpf), ('figure', '--figure', instead), ('occlusion', '--occlusion', instead),
+                              ('saliency', '--saliency', instead)):
         if why and getattr(args, attr, None) not in (None, False):
             print("{} is not supported by {} ({})".format(option, args.cnn_command, why.format(option)))
             return True
@@ -412,6 +425,20 @@ def main(argv=None):
                 kwargs['figure_width'] = args.figure_width
         elif 'occlusion_rows' in args or 'occlusion_fill' in args:
             print("--occlusion-rows and --occlusion-fill belong to --occlusion")
+            return 1
+        if 'saliency' in args:
+            if 'occlusion' in args:
+                print("--saliency and --occlusion each make the one map of a run: give one of them")
+                return 1
+            bands = getattr(args, 'saliency_bands', 8)
+            if bands < 1:
+                print("--saliency-bands must be at least 1 channel")
+                return 1
+            kwargs['saliency'] = bands
+            if getattr(args, 'figure_width', None) is not None:
+                kwargs['figure_width'] = args.figure_width
+        elif 'saliency_bands' in args:
+            print("--saliency-bands belongs to --saliency")
             return 1
         if args.cnn_command == 'evalrand':                     # needs no --file (unreachable in the reference CLI)
             if args.count is not None:

@@ -1334,6 +1334,7 @@ static int cnn_selfcheck(f2_ctx* ctx, f2_cnn* cnn) {
 static void free_cnn(f2_cnn* cnn) {
     if (cnn->blob) (void)hipFree(cnn->blob);
     if (cnn->blob16) (void)hipFree(cnn->blob16);
+    if (cnn->grad_blob) (void)hipFree(cnn->grad_blob);
     for (f2_scale_set* S : cnn->sets) {
         if (!S) continue;
         if (S->sbias) (void)hipFree(S->sbias);

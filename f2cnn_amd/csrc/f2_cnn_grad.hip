@@ -1,0 +1,674 @@
+// Backward-data pass of K4 (f2_cnn.hip's head comment has the network): G = dP(rising)/dx for every cell of every window, the
+// kernels of f2_cnn_input_gradient / f2_saliency_map / f2_eval_saliency_batch (include/f2cnn_hip.h).
+//
+// Recorded forward: conv1 .. dense2 in float32 (fmaf chains: k_conv1_fwd on the VALU, the other layers on v_mfma_f32_32x32x2_f32),
+// every layer's post-ReLU output kept in HBM, the two pools as kernels of their own. A post-ReLU value is > 0 exactly where the
+// pre-activation is, so the activations are the ReLU masks; and where a 2 x 2 block's maximum is > 0 the first maximal post-ReLU
+// element is the first maximal pre-activation, so they are the pool positions too.
+//
+// Backward chain (all float32, fixed summation order, no atomics):
+//   k_grad_dense2     g5 = P (1 - P) (W2[:,1] - W2[:,0]) where a5 > 0, rows padded with zeros to GK = 576
+//   k_gemm_rows       dense1 transposed: (n x 576) . W1T (576 x flat)
+//   k_gconv UNPOOL/MASK   conv4 transposed: the un-pool of the flat gradient through a4 happens while the patch is staged, the conv3
+//                         mask (a3 > 0) in the epilogue
+//   k_gconv PLAIN/NONE    conv3 transposed
+//   k_gconv UNPOOL/MASK   conv2 transposed: un-pool through a2 in the staging, conv1 mask (a1 > 0) in the epilogue
+//   k_conv1_bwd       conv1 transposed (32 -> 1), VALU
+//   k_grad_profile    profile[w][c] = {sum_r G x, sum_r |G|} in float64
+// Backward-data of a 3 x 3 convolution with padding p is a 3 x 3 convolution with padding 2 - p whose kernel is the forward one
+// rotated by 180 degrees with Cin and Cout swapped: k_gconv is one implicit-GEMM template for the forward layers and for the
+// transposed ones, with k_conv3x3_mfma's tiling (one task = 2 output rows x 32 columns of one window, its 4 x 34 x CIN patch in LDS
+// at a (CIN + 4)-float pitch). The transposed weights are built from cnn->blob on an f2_cnn's first gradient call.
+// gfx950, wave64. Everything that reaches memory is written by plain C++ stores.
+#include <algorithm>
+#include <cmath>
+
+#include "f2_cnn_dims.h"
+
+namespace {
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+constexpr int GK = 576;          // dense1's 516 outputs padded to whole 64-value chunks: the K of the transposed dense1
+constexpr int GEMM_WAVES = 4;    // waves (output tiles) of a k_gemm_rows workgroup
+constexpr int GEMM_ROWS = 64;    // windows of a k_gemm_rows workgroup (two M tiles)
+constexpr int64_t GRAD_WS_BYTES = int64_t(1) << 30;   // everything the chain holds between kernels
+constexpr int64_t GRAD_WS_CHUNK = 1024;               // windows of a chunk, at most
+constexpr int64_t GRAD_HOST_CHUNK = 4096;             // windows a host call stages at a time
+
+enum { ST_PLAIN = 0, ST_UNPOOL = 1 };
+enum { EP_RELU = 0, EP_MASK = 1, EP_NONE = 2 };
+
+// ---- conv1 ('same', Cin = 1) + ReLU, recorded: eight threads per pixel, a channel quad each; the oracle's tap order ----
+__global__ __launch_bounds__(256) void k_conv1_fwd(const float* __restrict__ x, const float* __restrict__ w1, const float* __restrict__ b1,
+                                                   float* __restrict__ a1, int H, int W, int64_t nwin) {
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t total = nwin * H * W * (C1 / 4);
+    if (t >= total) return;
+    const int c4 = (int)(t % (C1 / 4));
+    const int64_t pix = t / (C1 / 4);
+    const int xo = (int)(pix % W);
+    const int64_t t2 = pix / W;
+    const int y = (int)(t2 % H);
+    const int64_t win = t2 / H;
+    const float* img = x + win * (int64_t)H * W;
+    float acc[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int tap = 0; tap < 9; ++tap) {
+        const int yi = y - 1 + tap / 3, xi = xo - 1 + tap % 3;
+        const float v = (yi >= 0 && yi < H && xi >= 0 && xi < W) ? img[(int64_t)yi * W + xi] : 0.f;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) acc[q] = fmaf(v, w1[tap * C1 + c4 * 4 + q], acc[q]);
+    }
+    float4 o;
+    o.x = fmaxf(acc[0] + b1[c4 * 4 + 0], 0.f);
+    o.y = fmaxf(acc[1] + b1[c4 * 4 + 1], 0.f);
+    o.z = fmaxf(acc[2] + b1[c4 * 4 + 2], 0.f);
+    o.w = fmaxf(acc[3] + b1[c4 * 4 + 3], 0.f);
+    *reinterpret_cast<float4*>(a1 + pix * C1 + c4 * 4) = o;
+}
+
+// ---- 2 x 2 max-pool of an (n, H, W, CH) tensor -> (n, H / 2, W / 2, CH): a thread per channel quad of a pooled pixel ----
+__global__ __launch_bounds__(256) void k_pool2x2(const float* __restrict__ a, float* __restrict__ p, int H, int W, int CH, int64_t nwin) {
+    const int Hp = H / 2, Wp = W / 2, Q = CH / 4;
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= nwin * Hp * Wp * Q) return;
+    const int c4 = (int)(t % Q);
+    const int64_t pix = t / Q;
+    const int px = (int)(pix % Wp);
+    const int64_t t2 = pix / Wp;
+    const int py = (int)(t2 % Hp);
+    const int64_t win = t2 / Hp;
+    const float* s = a + ((win * H + 2 * py) * (int64_t)W + 2 * px) * CH + c4 * 4;
+    const float4 v00 = *reinterpret_cast<const float4*>(s), v01 = *reinterpret_cast<const float4*>(s + CH);
+    const float4 v10 = *reinterpret_cast<const float4*>(s + (int64_t)W * CH), v11 = *reinterpret_cast<const float4*>(s + (int64_t)W * CH + CH);
+    float4 o;
+    o.x = fmaxf(fmaxf(v00.x, v01.x), fmaxf(v10.x, v11.x));
+    o.y = fmaxf(fmaxf(v00.y, v01.y), fmaxf(v10.y, v11.y));
+    o.z = fmaxf(fmaxf(v00.z, v01.z), fmaxf(v10.z, v11.z));
+    o.w = fmaxf(fmaxf(v00.w, v01.w), fmaxf(v10.w, v11.w));
+    *reinterpret_cast<float4*>(p + pix * CH + c4 * 4) = o;
+}
+
+// the gradient a pooled cell hands to element `me` (0 .. 3 in (row, column) order) of its block: all of it to the first maximal
+// element where that maximum is > 0 (the ReLU in front of the pool passes it), nothing otherwise
+__device__ __forceinline__ float unpool_pick(float g, float v0, float v1, float v2, float v3, int me) {
+    const float m = fmaxf(fmaxf(v0, v1), fmaxf(v2, v3));
+    const int first = v0 == m ? 0 : v1 == m ? 1 : v2 == m ? 2 : v3 == m ? 3 : 4;
+    return m > 0.f && first == me ? g : 0.f;
+}
+
+// ---- 3 x 3 convolution with padding PAD (0 'valid', 1 'same', 2 'full') as an implicit GEMM on v_mfma_f32_32x32x2_f32 ----
+// Output (Hin + 2 PAD - 2) x (Win + 2 PAD - 2) x COUT. NSPLIT waves share one task (one patch), each takes COUT / 32 / NSPLIT of
+// the output tiles (k_conv3x3_mfma's scheme; w is that kernel's B operand wt[tap][h][s/4][cout][s%4]).
+//   ST_PLAIN   the input is `in` (n, Hin, Win, CIN)
+//   ST_UNPOOL  the input is the un-pooled gradient of a 2 x 2 max-pool: `in` (n, Hin/2, Win/2, CIN) the gradient of the pooled
+//              tensor, `act` (n, Hin, Win, CIN) the pool's post-ReLU input; rows / columns the pool dropped are zero
+//   EP_RELU    out = max(acc + aux[cout], 0)                     (aux: the layer's biases)
+//   EP_MASK    out = aux[same index as out] > 0 ? acc : 0        (aux: the post-ReLU activations of the layer the gradient enters)
+//   EP_NONE    out = acc
+template <int CIN, int COUT, int PAD, int STAGE, int EPI, int WAVES, int NSPLIT>
+__global__ __launch_bounds__(WAVES * 64) void k_gconv(const float* __restrict__ in, const float* __restrict__ act, const float* __restrict__ w,
+                                                      const float* __restrict__ aux, float* __restrict__ out, int Hin, int Win,
+                                                      int64_t nwin) {
+    constexpr int PS = CIN + 4;
+    constexpr int PATCH = 4 * PW * PS;
+    constexpr int NT = COUT / 32 / NSPLIT;
+    constexpr int TPB = WAVES / NSPLIT;
+    constexpr int Q4 = CIN / 4;
+    constexpr int HALF = CIN / 2;
+    static_assert(NT >= 1 && TPB >= 1 && CIN % 8 == 0, "tile shape");
+    extern __shared__ __attribute__((aligned(16))) float lds_all[];
+
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int ns = wave % NSPLIT;
+    float* patch = lds_all + (wave / NSPLIT) * PATCH;
+
+    const int Ho = Hin + 2 * PAD - 2, Wo = Win + 2 * PAD - 2;
+    const int row_pairs = (Ho + 1) / 2, xtiles = (Wo + 31) / 32;
+    const int64_t tasks = nwin * row_pairs * xtiles;
+    int64_t task = (int64_t)blockIdx.x * TPB + wave / NSPLIT;
+    const bool live = task < tasks;
+    if (!live) task = tasks - 1;
+    const int xt = (int)(task % xtiles);
+    const int64_t t2 = task / xtiles;
+    const int rp = (int)(t2 % row_pairs);
+    const int64_t win = t2 / row_pairs;
+    const int y0 = 2 * rp, x0 = 32 * xt;
+
+    const int Hp = Hin / 2, Wp = Win / 2;   // (ST_UNPOOL)
+    const float* img = in + win * (STAGE == ST_UNPOOL ? (int64_t)Hp * Wp : (int64_t)Hin * Win) * CIN;
+    const float* aimg = STAGE == ST_UNPOOL ? act + win * (int64_t)Hin * Win * CIN : nullptr;
+#pragma unroll 2
+    for (int e = lane + 64 * ns; e < 4 * PW * Q4; e += 64 * NSPLIT) {
+        const int r = e / (PW * Q4);
+        const int rem = e - r * (PW * Q4);
+        const int p = rem / Q4, c4 = rem - p * Q4;
+        const int yi = y0 - PAD + r, xi = x0 - PAD + p;
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if constexpr (STAGE == ST_PLAIN) {
+            if (yi >= 0 && yi < Hin && xi >= 0 && xi < Win) v = *reinterpret_cast<const float4*>(img + ((int64_t)yi * Win + xi) * CIN + c4 * 4);
+        } else {
+            const int py = yi >> 1, px = xi >> 1;
+            if (yi >= 0 && xi >= 0 && py < Hp && px < Wp) {
+                const float4 g = *reinterpret_cast<const float4*>(img + ((int64_t)py * Wp + px) * CIN + c4 * 4);
+                const float* s = aimg + ((int64_t)(2 * py) * Win + 2 * px) * CIN + c4 * 4;
+                const float4 v00 = *reinterpret_cast<const float4*>(s), v01 = *reinterpret_cast<const float4*>(s + CIN);
+                const float4 v10 = *reinterpret_cast<const float4*>(s + (int64_t)Win * CIN);
+                const float4 v11 = *reinterpret_cast<const float4*>(s + (int64_t)Win * CIN + CIN);
+                const int me = (yi & 1) * 2 + (xi & 1);
+                v.x = unpool_pick(g.x, v00.x, v01.x, v10.x, v11.x, me);
+                v.y = unpool_pick(g.y, v00.y, v01.y, v10.y, v11.y, me);
+                v.z = unpool_pick(g.z, v00.z, v01.z, v10.z, v11.z, me);
+                v.w = unpool_pick(g.w, v00.w, v01.w, v10.w, v11.w, me);
+            }
+        }
+        *reinterpret_cast<float4*>(patch + (r * PW + p) * PS + c4 * 4) = v;
+    }
+    __syncthreads();
+
+    f32x16 acc[2][NT];
+#pragma unroll
+    for (int rr = 0; rr < 2; ++rr)
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+            for (int q = 0; q < 16; ++q) acc[rr][nt][q] = 0.f;
+
+    // lane = (pixel i, half h); step s of a tap multiplies channels s (h = 0) and HALF + s (h = 1); operands one step ahead
+    const int i = lane & 31, h = lane >> 5;
+    const float* pa0 = patch + i * PS + h * HALF;
+    const float4* wq = reinterpret_cast<const float4*>(w) + (int64_t)h * (HALF / 4) * COUT + ns * NT * 32 + i;
+    constexpr int QN = HALF / 4, NIT = 9 * QN;
+    float4 av0[2], av1[2], bq[2][NT];
+    auto fetch = [&](int it, int buf) {
+        const int tap = it / QN, q = it - tap * QN;
+        const int dy = tap / 3, dx = tap - dy * 3;
+        const float* pa = pa0 + (dy * PW + dx) * PS;
+        const float4* pb = wq + (int64_t)tap * 2 * QN * COUT;
+        av0[buf] = *reinterpret_cast<const float4*>(pa + 4 * q);
+        av1[buf] = *reinterpret_cast<const float4*>(pa + PW * PS + 4 * q);
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) bq[buf][nt] = pb[(int64_t)q * COUT + nt * 32];
+    };
+    fetch(0, 0);
+#pragma unroll
+    for (int it = 0; it < NIT; ++it) {
+        const int cur = it & 1;
+        if (it + 1 < NIT) fetch(it + 1, cur ^ 1);
+        __builtin_amdgcn_sched_barrier(0);
+        const float a0v[4] = {av0[cur].x, av0[cur].y, av0[cur].z, av0[cur].w};
+        const float a1v[4] = {av1[cur].x, av1[cur].y, av1[cur].z, av1[cur].w};
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt) {
+                const float4 bb = bq[cur][nt];
+                const float bv = r == 0 ? bb.x : r == 1 ? bb.y : r == 2 ? bb.z : bb.w;
+                acc[0][nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0v[r], bv, acc[0][nt], 0, 0, 0);
+                acc[1][nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1v[r], bv, acc[1][nt], 0, 0, 0);
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    }
+
+    if (!live) return;
+    const int64_t obase = win * (int64_t)Ho * Wo * COUT;
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) {
+        const int co = (ns * NT + nt) * 32 + i;
+        const float bv = EPI == EP_RELU ? aux[co] : 0.f;
+#pragma unroll
+        for (int rr = 0; rr < 2; ++rr) {
+            const int y = y0 + rr;
+#pragma unroll
+            for (int q = 0; q < 16; ++q) {
+                const int xo = x0 + (q & 3) + 8 * (q >> 2) + 4 * h;
+                if (y < Ho && xo < Wo) {
+                    const int64_t idx = obase + ((int64_t)y * Wo + xo) * COUT + co;
+                    float v = acc[rr][nt][q];
+                    if constexpr (EPI == EP_RELU) v = fmaxf(v + bv, 0.f);
+                    if constexpr (EPI == EP_MASK) v = aux[idx] > 0.f ? v : 0.f;
+                    out[idx] = v;
+                }
+            }
+        }
+    }
+}
+
+// ---- g5 (n, GK): the gradient of P = softmax(z)[1] at dense1's pre-activations ----
+// dP/dz1 = -dP/dz0 = P (1 - P) = s0 s1 with the recorded scores (the product keeps its precision where P is close to 1)
+__global__ __launch_bounds__(256) void k_grad_dense2(const float* __restrict__ a5, const float* __restrict__ scores, const float* __restrict__ w2,
+                                                     float* __restrict__ g5, int64_t n) {
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= n * GK) return;
+    const int k = (int)(t % GK);
+    const int64_t wv = t / GK;
+    float g = 0.f;
+    if (k < D1 && a5[wv * D1 + k] > 0.f) g = scores[2 * wv] * scores[2 * wv + 1] * (w2[2 * k + 1] - w2[2 * k]);
+    g5[t] = g;
+}
+
+// ---- out (n, N) = a (n, K) . w (K, N), K a multiple of 64 and N of 32: k_dense1_mfma's tiling without bias and ReLU ----
+// One workgroup = 64 rows x GEMM_WAVES output tiles; w is wt[chunk][h][q][n][4], k = 64 chunk + 32 h + 4 q + e.
+__global__ __launch_bounds__(GEMM_WAVES * 64) void k_gemm_rows(const float* __restrict__ a, const float* __restrict__ wt, float* __restrict__ out,
+                                                               int K, int N, int64_t n) {
+    constexpr int KC = 64, PS = KC + 4;
+    __shared__ __attribute__((aligned(16))) float As[2][GEMM_ROWS * PS];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int64_t w0 = (int64_t)blockIdx.x * GEMM_ROWS;
+    const int i = lane & 31, h = lane >> 5;
+    const int nchunks = K / KC;
+    const int nt = blockIdx.y * GEMM_WAVES + wave;
+    const bool live = nt < N / 32;
+
+    auto stage = [&](int kc, int buf) {
+        for (int e = tid; e < GEMM_ROWS * (KC / 4); e += GEMM_WAVES * 64) {
+            const int row = e / (KC / 4), c4 = e - row * (KC / 4);
+            const int64_t wr = w0 + row < n ? w0 + row : n - 1;
+            *reinterpret_cast<float4*>(&As[buf][row * PS + c4 * 4]) = *reinterpret_cast<const float4*>(a + wr * K + (int64_t)kc * KC + c4 * 4);
+        }
+    };
+    f32x16 acc[2];
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int q = 0; q < 16; ++q) acc[t][q] = 0.f;
+
+    stage(0, 0);
+    __syncthreads();
+    for (int kc = 0; kc < nchunks; ++kc) {
+        const int buf = kc & 1;
+        if (kc + 1 < nchunks) stage(kc + 1, buf ^ 1);
+        if (live) {
+            const float* pa = &As[buf][i * PS + h * (KC / 2)];
+            const float4* pb = reinterpret_cast<const float4*>(wt) + ((int64_t)(kc * 2 + h) * (KC / 8)) * N + nt * 32 + i;
+#pragma unroll
+            for (int q = 0; q < KC / 8; ++q) {
+                const float4 bv = pb[(int64_t)q * N];
+                float4 av[2];
+#pragma unroll
+                for (int t = 0; t < 2; ++t) av[t] = *reinterpret_cast<const float4*>(pa + t * 32 * PS + 4 * q);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const float b = r == 0 ? bv.x : r == 1 ? bv.y : r == 2 ? bv.z : bv.w;
+#pragma unroll
+                    for (int t = 0; t < 2; ++t) {
+                        const float av_r = r == 0 ? av[t].x : r == 1 ? av[t].y : r == 2 ? av[t].z : av[t].w;
+                        acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(av_r, b, acc[t], 0, 0, 0);
+                    }
+                }
+            }
+        }
+        __syncthreads();
+    }
+    if (!live) return;
+    const int col = nt * 32 + i;
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int q = 0; q < 16; ++q) {
+            const int64_t wr = w0 + t * 32 + (q & 3) + 8 * (q >> 2) + 4 * h;
+            if (wr < n) out[wr * N + col] = acc[t][q];
+        }
+}
+
+// ---- conv1 transposed ('same', 32 -> 1): a thread per cell of G, taps then channels in ascending order ----
+// G[y][x] = sum over (dy, dx, c) of g1[y + 1 - dy][x + 1 - dx][c] w1[dy][dx][c], g1 already masked by a1 > 0
+__global__ __launch_bounds__(256) void k_conv1_bwd(const float* __restrict__ g1, const float* __restrict__ w1, float* __restrict__ G, int H, int W,
+                                                   int64_t nwin) {
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= nwin * H * W) return;
+    const int xo = (int)(t % W);
+    const int64_t t2 = t / W;
+    const int y = (int)(t2 % H);
+    const int64_t win = t2 / H;
+    const float* img = g1 + win * (int64_t)H * W * C1;
+    float acc = 0.f;
+#pragma unroll
+    for (int tap = 0; tap < 9; ++tap) {
+        const int yi = y + 1 - tap / 3, xi = xo + 1 - tap % 3;
+        if (yi < 0 || yi >= H || xi < 0 || xi >= W) continue;
+        const float4* gp = reinterpret_cast<const float4*>(img + ((int64_t)yi * W + xi) * C1);
+        const float4* wp = reinterpret_cast<const float4*>(w1 + tap * C1);
+#pragma unroll
+        for (int q = 0; q < C1 / 4; ++q) {
+            const float4 g = gp[q], wv = wp[q];
+            acc = fmaf(g.x, wv.x, acc);
+            acc = fmaf(g.y, wv.y, acc);
+            acc = fmaf(g.z, wv.z, acc);
+            acc = fmaf(g.w, wv.w, acc);
+        }
+    }
+    G[t] = acc;
+}
+
+// ---- profile[w][c] = {sum_r (double)G (double)x, sum_r |(double)G|}, r ascending: a thread per (window, channel) ----
+__global__ __launch_bounds__(256) void k_grad_profile(const float* __restrict__ G, const float* __restrict__ x, double* __restrict__ profile, int R,
+                                                      int C, int64_t nwin) {
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= nwin * C) return;
+    const int c = (int)(t % C);
+    const int64_t win = t / C;
+    const float* g = G + win * (int64_t)R * C + c;
+    const float* xv = x + win * (int64_t)R * C + c;
+    double s = 0.0, sa = 0.0;
+    for (int r = 0; r < R; ++r) {
+        const double gv = (double)g[(int64_t)r * C];
+        s += gv * (double)xv[(int64_t)r * C];   // (the product of two float32 values is exact in float64)
+        sa += fabs(gv);
+    }
+    profile[2 * t] = s;
+    profile[2 * t + 1] = sa;
+}
+
+// ---- f2_saliency_map: k_occlusion_map's columns, lanes and fixed order (f2_occlusion.hip) over a (rows, C, 2) float64 profile ----
+// blockIdx.y = channel c. map[u][c][x] = {rows, mean of profile[..][c][0], mean of profile[..][c][1]} over the rows column x owns.
+constexpr int TT = 256;
+constexpr int AHEAD = 4;
+__global__ __launch_bounds__(TT) void k_saliency_map(const double* __restrict__ profile, const int64_t* __restrict__ rec, int64_t origin, int64_t hop,
+                                                      int W, unsigned bpu, double* __restrict__ map) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const unsigned u = blockIdx.x / bpu, local = blockIdx.x % bpu;
+    const unsigned c = blockIdx.y, C = gridDim.y;
+    const int64_t first = rec[5 * (size_t)u], n = rec[5 * (size_t)u + 1], s = rec[5 * (size_t)u + 2], m = rec[5 * (size_t)u + 3];
+    const int lg = (int)rec[5 * (size_t)u + 4];
+    const int G = 1 << lg, per = 64 >> lg;
+    const int run = (int)(local * (TT / 64) + wv);
+    if ((int64_t)run * per >= W) return;                // (the whole wave)
+    const int sub = lane & (G - 1), x = run * per + (lane >> lg);
+    const bool has = x < W;
+
+    int64_t j_lo = 0, j_hi = 0;
+    if (has && m > 0) {
+        const int64_t q = m / W, r = m % W;
+        const int64_t lo = s + (int64_t)x * q + (int64_t)x * r / W;
+        int64_t hi = s + (int64_t)(x + 1) * q + (int64_t)(x + 1) * r / W;
+        if (hi == lo) hi = lo + 1;
+        j_lo = lo <= origin ? 0 : min(n, (lo - origin - 1) / hop + 1);
+        j_hi = hi <= origin ? 0 : min(n, (hi - origin - 1) / hop + 1);
+    }
+    const size_t pitch = 2 * (size_t)C;
+    const double* p = profile + pitch * (size_t)first + 2 * (size_t)c;
+    double sum = 0.0, sum_abs = 0.0;
+    int64_t j = j_lo + sub;
+    for (; j + (int64_t)(AHEAD - 1) * G < j_hi; j += (int64_t)AHEAD * G) {     // AHEAD independent loads, added in index order
+        double a[AHEAD], b[AHEAD];
+#pragma unroll
+        for (int q = 0; q < AHEAD; ++q) {
+            const size_t row = (size_t)(j + (int64_t)q * G);
+            a[q] = p[pitch * row];
+            b[q] = p[pitch * row + 1];
+        }
+#pragma unroll
+        for (int q = 0; q < AHEAD; ++q) {
+            sum += a[q];
+            sum_abs += b[q];
+        }
+    }
+    for (; j < j_hi; j += G) {
+        sum += p[pitch * (size_t)j];
+        sum_abs += p[pitch * (size_t)j + 1];
+    }
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) {
+        if (d >= G) continue;      // (uniform: G belongs to the utterance)
+        sum += __shfl_xor(sum, d);
+        sum_abs += __shfl_xor(sum_abs, d);
+    }
+    if (has && sub == 0) {
+        const int64_t rows = j_hi - j_lo;
+        double* t = map + (((size_t)u * C + c) * (size_t)W + (size_t)x) * 3;
+        const double none = (double)NAN;
+        t[0] = (double)rows;
+        t[1] = rows > 0 ? sum / (double)rows : none;
+        t[2] = rows > 0 ? sum_abs / (double)rows : none;
+    }
+}
+
+template <int CIN, int COUT, int PAD, int STAGE, int EPI, int WAVES, int NSPLIT>
+int launch_gconv(f2_ctx* ctx, const float* in, const float* act, const float* w, const float* aux, float* out, int Hin, int Win, int64_t n) {
+    const int Ho = Hin + 2 * PAD - 2, Wo = Win + 2 * PAD - 2;
+    const int64_t tasks = n * ((Ho + 1) / 2) * ((Wo + 31) / 32);
+    if (tasks <= 0) return F2_OK;
+    constexpr int TPB = WAVES / NSPLIT;
+    constexpr size_t lds = sizeof(float) * TPB * 4 * PW * (CIN + 4);
+    static_assert(lds <= 160 * 1024, "a workgroup's patches fit the CU's LDS");
+    auto kern = k_gconv<CIN, COUT, PAD, STAGE, EPI, WAVES, NSPLIT>;
+    if (lds > 64 * 1024) F2_HIP(ctx, hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    unsigned blocks;
+    F2_TRY(cnn_grid(ctx, (tasks + TPB - 1) / TPB, &blocks));
+    hipLaunchKernelGGL(kern, dim3(blocks), dim3(WAVES * 64), lds, ctx->stream, in, act, w, aux, out, Hin, Win, n);
+    F2_HIP(ctx, hipGetLastError());
+    return F2_OK;
+}
+
+int grid256(f2_ctx* ctx, int64_t threads, unsigned* grid) { return cnn_grid(ctx, (threads + 255) / 256, grid); }
+
+// ---- the weights of the transposed layers, from cnn->blob ----
+// f2_cnn_create's MFMA B operand of a K x N matrix (f2_cnn.hip: relayout_f32): [block][h][s/4][n (npad)][s%4], k = block blk + h blk/2 + s
+size_t relaid_index(size_t k, int n, int blk, int npad) {
+    const int half = blk / 2;
+    const size_t b = k / blk, hh = k % blk / half, s = k % half;
+    return (((b * 2 + hh) * (half / 4) + s / 4) * npad + n) * 4 + s % 4;
+}
+
+struct grad_layout {
+    size_t off[4];   // conv2T, conv3T, conv4T, dense1T (floats)
+    size_t total;
+};
+grad_layout grad_weight_layout(int flat) {
+    grad_layout L;
+    const size_t sizes[4] = {9 * (size_t)C2 * C1, 9 * (size_t)C3 * C2, 9 * (size_t)C4 * C3, (size_t)GK * flat};
+    L.total = 0;
+    for (int i = 0; i < 4; ++i) L.off[i] = L.total, L.total += (sizes[i] + 63) & ~size_t(63);
+    return L;
+}
+
+// Rotated, transposed convolution kernels and W1T of `cnn`, built on its first gradient call and kept until f2_cnn_destroy
+int grad_weights(f2_ctx* ctx, const f2_cnn* cnn, const float** out) {
+    std::lock_guard<std::mutex> lock(cnn->sets_mu);
+    if (cnn->grad_blob) {
+        *out = cnn->grad_blob;
+        return F2_OK;
+    }
+    const grad_layout L = grad_weight_layout(cnn->flat);
+    std::vector<float> dst(L.total, 0.f);
+    const int cin[3] = {C1, C2, C3}, cout[3] = {C2, C3, C4};
+    std::vector<float> src;
+    for (int l = 0; l < 3; ++l) {
+        // forward k = tap cin + ci, n = co  ->  transposed k' = tap' cout + co, n' = ci, tap' = 8 - tap (the 180 degree turn)
+        const size_t count = 9 * (size_t)cin[l] * cout[l];
+        src.resize(count);
+        F2_HIP(ctx, hipMemcpyAsync(src.data(), cnn->t(2 + 2 * l), sizeof(float) * count, hipMemcpyDeviceToHost, ctx->stream));
+        F2_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        float* d = dst.data() + L.off[l];
+        for (int tap = 0; tap < 9; ++tap)
+            for (int ci = 0; ci < cin[l]; ++ci)
+                for (int co = 0; co < cout[l]; ++co)
+                    d[relaid_index((size_t)(8 - tap) * cout[l] + co, ci, cout[l], cin[l])] =
+                        src[relaid_index((size_t)tap * cin[l] + ci, co, cin[l], cout[l])];
+    }
+    {
+        const size_t count = (size_t)cnn->flat * D1_NPAD;
+        src.resize(count);
+        F2_HIP(ctx, hipMemcpyAsync(src.data(), cnn->t(8), sizeof(float) * count, hipMemcpyDeviceToHost, ctx->stream));
+        F2_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        float* d = dst.data() + L.off[3];
+        for (int j = 0; j < cnn->flat; ++j)
+            for (int k = 0; k < D1; ++k) d[relaid_index((size_t)k, j, 64, cnn->flat)] = src[relaid_index((size_t)j, k, D1_KC, D1_NPAD)];
+    }
+    float* blob = nullptr;
+    hipError_t e = hipMalloc((void**)&blob, sizeof(float) * L.total);
+    if (e != hipSuccess) return f2_fail(ctx, F2_ERR_NOMEM, "hipMalloc(%zu) -> %s", sizeof(float) * L.total, hipGetErrorString(e));
+    e = hipMemcpyAsync(blob, dst.data(), sizeof(float) * L.total, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) {
+        (void)hipFree(blob);
+        return f2_fail(ctx, F2_ERR_HIP, "uploading the transposed CNN weights -> %s", hipGetErrorString(e));
+    }
+    cnn->grad_blob = blob;
+    *out = blob;
+    return F2_OK;
+}
+
+// the chain's arrays of one chunk, floats per window (each array starts on a 256-byte boundary)
+struct grad_ws {
+    enum { A1, A2, P1, A3, A4, P2, A5, G5, GP2, G3, GP1, G1, GX, SC, COUNT };
+    size_t per[COUNT];
+    size_t bytes_per_window() const {
+        size_t s = 0;
+        for (size_t p : per) s += p;
+        return sizeof(float) * s;
+    }
+};
+grad_ws grad_ws_shape(const Dims& d) {
+    grad_ws w;
+    w.per[grad_ws::A1] = (size_t)d.H1 * d.W1 * C1;
+    w.per[grad_ws::A2] = (size_t)d.H2 * d.W2 * C2;
+    w.per[grad_ws::P1] = (size_t)d.Hp1 * d.Wp1 * C2;
+    w.per[grad_ws::A3] = (size_t)d.Hp1 * d.Wp1 * C3;
+    w.per[grad_ws::A4] = (size_t)d.H4 * d.W4 * C4;
+    w.per[grad_ws::P2] = (size_t)d.flat;
+    w.per[grad_ws::A5] = D1;
+    w.per[grad_ws::G5] = GK;
+    w.per[grad_ws::GP2] = (size_t)d.flat;
+    w.per[grad_ws::G3] = (size_t)d.Hp1 * d.Wp1 * C3;
+    w.per[grad_ws::GP1] = (size_t)d.Hp1 * d.Wp1 * C2;
+    w.per[grad_ws::G1] = (size_t)d.H1 * d.W1 * C1;
+    w.per[grad_ws::GX] = (size_t)d.H1 * d.W1;
+    w.per[grad_ws::SC] = 2;
+    return w;
+}
+
+}  // namespace
+
+int64_t f2_cnn_grad_chunk(const f2_cnn* cnn) {
+    const grad_ws shape = grad_ws_shape(make_dims(cnn->rows, cnn->channels));
+    const int64_t fit = (GRAD_WS_BYTES - 64 * grad_ws::COUNT * (int64_t)sizeof(float)) / (int64_t)shape.bytes_per_window();
+    return std::max<int64_t>(1, std::min<int64_t>(fit, GRAD_WS_CHUNK));
+}
+
+int f2_launch_cnn_input_gradient(f2_ctx* ctx, const f2_cnn* cnn, const float* d_x, int64_t n, float* d_grad, double* d_profile,
+                                 float* d_scores) {
+    if (n <= 0) return F2_OK;
+    const Dims d = make_dims(cnn->rows, cnn->channels);
+    const grad_ws shape = grad_ws_shape(d);
+    const bool backward = d_grad || d_profile;
+    const float* gw = nullptr;
+    if (backward) F2_TRY(grad_weights(ctx, cnn, &gw));
+    const grad_layout L = grad_weight_layout(cnn->flat);
+    const int64_t chunk = std::min(n, f2_cnn_grad_chunk(cnn));
+    float* arr[grad_ws::COUNT];
+    size_t total = 0;
+    for (int k = 0; k < grad_ws::COUNT; ++k) total += (shape.per[k] * (size_t)chunk + 63) & ~size_t(63);
+    F2_TRY(f2_reserve(ctx, ctx->grad_ws, sizeof(float) * total));
+    total = 0;
+    for (int k = 0; k < grad_ws::COUNT; ++k) arr[k] = (float*)ctx->grad_ws.ptr + total, total += (shape.per[k] * (size_t)chunk + 63) & ~size_t(63);
+    const size_t xs = (size_t)d.H1 * d.W1;
+    unsigned g;
+    for (int64_t s = 0; s < n; s += chunk) {
+        const int64_t m = std::min(chunk, n - s);
+        const float* x = d_x + (size_t)s * xs;
+        // recorded forward
+        F2_TRY(f2_prof_begin(ctx, F2_K_CNN));
+        F2_TRY(grid256(ctx, m * d.H1 * d.W1 * (C1 / 4), &g));
+        hipLaunchKernelGGL(k_conv1_fwd, dim3(g), dim3(256), 0, ctx->stream, x, cnn->t(0), cnn->t(1), arr[grad_ws::A1], d.H1, d.W1, m);
+        F2_HIP(ctx, hipGetLastError());
+        F2_TRY((launch_gconv<C1, C2, 0, ST_PLAIN, EP_RELU, 4, 1>(ctx, arr[grad_ws::A1], nullptr, cnn->t(2), cnn->t(3), arr[grad_ws::A2], d.H1, d.W1, m)));
+        F2_TRY(grid256(ctx, m * d.Hp1 * d.Wp1 * (C2 / 4), &g));
+        hipLaunchKernelGGL(k_pool2x2, dim3(g), dim3(256), 0, ctx->stream, arr[grad_ws::A2], arr[grad_ws::P1], d.H2, d.W2, C2, m);
+        F2_HIP(ctx, hipGetLastError());
+        F2_TRY((launch_gconv<C2, C3, 1, ST_PLAIN, EP_RELU, 4, 2>(ctx, arr[grad_ws::P1], nullptr, cnn->t(4), cnn->t(5), arr[grad_ws::A3], d.Hp1, d.Wp1, m)));
+        F2_TRY((launch_gconv<C3, C4, 0, ST_PLAIN, EP_RELU, 4, 2>(ctx, arr[grad_ws::A3], nullptr, cnn->t(6), cnn->t(7), arr[grad_ws::A4], d.Hp1, d.Wp1, m)));
+        F2_TRY(grid256(ctx, m * d.Hp2 * d.Wp2 * (C4 / 4), &g));
+        hipLaunchKernelGGL(k_pool2x2, dim3(g), dim3(256), 0, ctx->stream, arr[grad_ws::A4], arr[grad_ws::P2], d.H4, d.W4, C4, m);
+        F2_HIP(ctx, hipGetLastError());
+        F2_TRY(f2_prof_end(ctx, F2_K_CNN));
+        F2_TRY(f2_launch_cnn_dense(ctx, cnn, nullptr, f2_cnn_route(), arr[grad_ws::P2], m, arr[grad_ws::A5], arr[grad_ws::SC], nullptr));
+        if (d_scores)
+            F2_HIP(ctx, hipMemcpyAsync(d_scores + 2 * (size_t)s, arr[grad_ws::SC], sizeof(float) * 2 * (size_t)m, hipMemcpyDeviceToDevice, ctx->stream));
+        if (!backward) continue;
+        // backward-data chain
+        float* G = d_grad ? d_grad + (size_t)s * xs : arr[grad_ws::GX];
+        F2_TRY(f2_prof_begin(ctx, F2_K_CNN));
+        F2_TRY(grid256(ctx, m * GK, &g));
+        hipLaunchKernelGGL(k_grad_dense2, dim3(g), dim3(256), 0, ctx->stream, arr[grad_ws::A5], arr[grad_ws::SC], cnn->t(10), arr[grad_ws::G5], m);
+        F2_HIP(ctx, hipGetLastError());
+        const int ntiles = d.flat / 32;
+        hipLaunchKernelGGL(k_gemm_rows, dim3((unsigned)((m + GEMM_ROWS - 1) / GEMM_ROWS), (unsigned)((ntiles + GEMM_WAVES - 1) / GEMM_WAVES)),
+                           dim3(GEMM_WAVES * 64), 0, ctx->stream, arr[grad_ws::G5], gw + L.off[3], arr[grad_ws::GP2], GK, d.flat, m);
+        F2_HIP(ctx, hipGetLastError());
+        F2_TRY((launch_gconv<C4, C3, 2, ST_UNPOOL, EP_MASK, 4, 2>(ctx, arr[grad_ws::GP2], arr[grad_ws::A4], gw + L.off[2], arr[grad_ws::A3],
+                                                                  arr[grad_ws::G3], d.H4, d.W4, m)));
+        F2_TRY((launch_gconv<C3, C2, 1, ST_PLAIN, EP_NONE, 2, 1>(ctx, arr[grad_ws::G3], nullptr, gw + L.off[1], nullptr, arr[grad_ws::GP1], d.Hp1,
+                                                                 d.Wp1, m)));
+        F2_TRY((launch_gconv<C2, C1, 2, ST_UNPOOL, EP_MASK, 4, 1>(ctx, arr[grad_ws::GP1], arr[grad_ws::A2], gw + L.off[0], arr[grad_ws::A1],
+                                                                  arr[grad_ws::G1], d.H2, d.W2, m)));
+        F2_TRY(grid256(ctx, m * d.H1 * d.W1, &g));
+        hipLaunchKernelGGL(k_conv1_bwd, dim3(g), dim3(256), 0, ctx->stream, arr[grad_ws::G1], cnn->t(0), G, d.H1, d.W1, m);
+        F2_HIP(ctx, hipGetLastError());
+        if (d_profile) {
+            F2_TRY(grid256(ctx, m * d.W1, &g));
+            hipLaunchKernelGGL(k_grad_profile, dim3(g), dim3(256), 0, ctx->stream, G, x, d_profile + 2 * (size_t)s * d.W1, d.H1, d.W1, m);
+            F2_HIP(ctx, hipGetLastError());
+        }
+        F2_TRY(f2_prof_end(ctx, F2_K_CNN));
+    }
+    return F2_OK;
+}
+
+int f2_launch_saliency_map(f2_ctx* ctx, const double* d_profile, const int64_t* d_rec, int U, int C, int64_t origin, int hop, int width,
+                           int64_t blocks_per_utt, double* d_map) {
+    if (U <= 0 || C <= 0 || blocks_per_utt <= 0) return F2_OK;
+    F2_CHECK(ctx, blocks_per_utt * U < (int64_t(1) << 31), F2_ERR_UNSUPPORTED, "map of %d x %d columns needs too many workgroups", U, width);
+    k_saliency_map<<<dim3((unsigned)(blocks_per_utt * U), (unsigned)C), dim3(TT), 0, ctx->stream>>>(d_profile, d_rec, origin, (int64_t)hop, width,
+                                                                                                  (unsigned)blocks_per_utt, d_map);
+    F2_HIP(ctx, hipGetLastError());
+    return F2_OK;
+}
+
+extern "C" {
+
+int f2_cnn_input_gradient(f2_ctx* ctx, const f2_cnn* cnn, const float* x, int64_t n, float* grad_or_null, double* profile_or_null,
+                          float* scores_or_null, int mem_space) {
+    F2_TRY(f2_check_ctx(ctx));
+    F2_TRY(f2_check_cnn(ctx, cnn, 0, 0));
+    F2_TRY(f2_check_mem_space(ctx, mem_space, false));
+    F2_CHECK(ctx, n >= 0, F2_ERR_INVALID, "negative window count");
+    if (n == 0) return F2_OK;
+    F2_CHECK(ctx, x, F2_ERR_INVALID, "x is NULL");
+    const size_t xs = (size_t)cnn->rows * cnn->channels, C = (size_t)cnn->channels;
+    // Device memory: the whole call at once (the chain works through its scratch in chunks of its own). Host memory: GRAD_HOST_CHUNK
+    // windows at a time through stage_in / stage_out / stage_aux, each chunk's outputs back before the next one goes up.
+    const bool host = mem_space != F2_MEM_DEVICE;
+    const int64_t chunk = !host || n < GRAD_HOST_CHUNK ? n : GRAD_HOST_CHUNK;
+    f2_output grad;
+    F2_TRY(f2_place(ctx, ctx->stage_out, grad_or_null, sizeof(float) * xs * (size_t)chunk, mem_space, false, &grad));
+    grad.bytes = sizeof(float) * xs * (size_t)n;
+    const size_t tail_bytes = host && profile_or_null ? sizeof(double) * 2 * C * (size_t)chunk : 0;
+    f2_score_outputs out;
+    F2_TRY(f2_place_scores(ctx, scores_or_null, nullptr, chunk, mem_space, false, false, tail_bytes, &out));
+    for (int64_t s = 0; s < n; s += chunk) {
+        const int64_t m = n - s < chunk ? n - s : chunk;
+        const void* d_x;
+        F2_TRY(f2_stage_input(ctx, x + (size_t)s * xs, sizeof(float) * xs * (size_t)m, mem_space, &d_x));
+        const f2_output go = grad.chunk(sizeof(float) * xs * (size_t)s, sizeof(float) * xs * (size_t)m);
+        const f2_output sc = out.scores.chunk(sizeof(float) * 2 * (size_t)s, sizeof(float) * 2 * (size_t)m);
+        f2_output po;
+        if (profile_or_null) {
+            const size_t first = sizeof(double) * 2 * C * (size_t)s;
+            po.bytes = sizeof(double) * 2 * C * (size_t)m;
+            po.dev = host ? out.tail : (char*)profile_or_null + first, po.host = host ? (char*)profile_or_null + first : nullptr;
+            po.callers = !host;
+        }
+        F2_TRY(f2_launch_cnn_input_gradient(ctx, cnn, (const float*)d_x, m, go.as<float>(), po.as<double>(), sc.as<float>()));
+        F2_TRY(f2_copy_back(ctx, go));
+        F2_TRY(f2_copy_back(ctx, po));
+        F2_TRY(f2_copy_back(ctx, sc));
+        F2_TRY(f2_host_wait(ctx, mem_space));
+    }
+    return F2_OK;
+}
+
+}  // extern "C"

@@ -55,6 +55,8 @@ struct f2_ctx {
     f2_scratch work2;
     f2_scratch xbuf;       // window tensor chunk between K3 and K4
     f2_scratch occ_src;    // f2_eval_occlusion_batch: the source windows of a chunk, which k_occlude_windows expands into xbuf
+    f2_scratch grad_ws;    // f2_cnn_input_gradient: activations and gradients of a chunk of windows (f2_cnn_grad.hip), at most 1 GiB
+    f2_scratch sal_profile;  // f2_eval_saliency_batch: the (C, 2) float64 profile rows of all windows of the call
     f2_scratch dense_in;   // conv4 outputs (+ dense1 outputs) of the windows of several utterances: one dense launch for all
     // the four sweeps, f2_lowpass_levels, f2_reverb_levels, f2_channel_mix_levels: the (K+1) x batch levels (float64 waveforms or envelopes) when the caller
     // gives no device buffer. One area: each of these calls places one set of levels, and nothing they nest (f2_eval_batch_strided,
@@ -187,6 +189,9 @@ struct f2_cnn {
     // (f2_cnn_scale_set); each owns its sbias buffer, freed by f2_cnn_destroy
     mutable std::mutex sets_mu;
     mutable f2_scale_set* sets[F2_BOUND_EXP_MAX + 1] = {nullptr};
+    // rotated, transposed kernels of conv2 .. conv4 and W1T for the backward-data pass (f2_cnn_grad.hip), built under sets_mu on the
+    // first gradient call, freed by f2_cnn_destroy
+    mutable float* grad_blob = nullptr;
     mutable double last_input_bound = 0.0;   // B of the last f2_cnn_forward / unnormalised f2_cnn_score_windows, -1: the float32 kernels ran, 0: none yet
     // f2_cnn_create's self-check of the weight-stationary kernels (hand-placed s_waitcnt around inline-asm loads: correct only
     // while the register allocator of the hipcc that built the library leaves those registers alone) against the per-tile
@@ -591,6 +596,16 @@ int f2_launch_occlude_windows(f2_ctx* ctx, const float* d_x, int64_t n, int R, i
                               float* d_out);
 int f2_launch_occlusion_map(f2_ctx* ctx, const float* d_scores, const uint8_t* d_labels, const int64_t* d_rec, int U, int K, int64_t origin,
                             int hop, int width, int64_t blocks_per_utt, double* d_map);
+// f2_cnn_grad.hip, the kernels of f2_cnn_input_gradient / f2_saliency_map / f2_eval_saliency_batch. The gradient launch runs the
+// recorded float32 forward and the backward-data chain over n windows at d_x in chunks of f2_cnn_grad_chunk windows through
+// ctx->grad_ws (no other area of the context): d_grad (n, R, C) or NULL (the chain's own scratch), d_profile (n, C, 2) float64 or NULL,
+// d_scores (n, 2) or NULL; with neither d_grad nor d_profile only the forward runs. Element alignment is enough for all four.
+// The map's d_rec, lanes and workgroups are those of f2_launch_score_track; d_profile (rows, C, 2), d_map (U, C, width, 3) float64.
+int64_t f2_cnn_grad_chunk(const f2_cnn* cnn);
+int f2_launch_cnn_input_gradient(f2_ctx* ctx, const f2_cnn* cnn, const float* d_x, int64_t n, float* d_grad, double* d_profile,
+                                 float* d_scores);
+int f2_launch_saliency_map(f2_ctx* ctx, const double* d_profile, const int64_t* d_rec, int U, int C, int64_t origin, int hop, int width,
+                           int64_t blocks_per_utt, double* d_map);
 // f2_resample.hip, the kernels of f2_resample_batch. F2_RESAMPLE_BLOCK outputs per workgroup, which stages at most
 // F2_RESAMPLE_SPAN_MAX input frames (f2_resample_span: what (up, down, T) need, T = taps per phase).
 // d_meta: 4 int64 per utterance {first input frame, frames, first output sample, output samples}, then B + 1 running sums of the

@@ -316,8 +316,15 @@ struct occlusion_stage {
     int K;
     float fill;
 };
+// sal (f2_eval_saliency_batch): the chunk's windows are differentiated while they are in d_windows (f2_cnn_grad.hip: recorded
+// forward + backward-data chain through ctx->grad_ws) and only their profile rows are kept, at d_profile + 2 C * (windows so far).
+struct saliency_stage {
+    double* d_profile;
+    int64_t done;
+};
 static int strided_window_loop(f2_ctx* ctx, const f2_cnn* cnn, eval_call* E, const f2_batch& X, const std::vector<int64_t>& nbh,
-                               int64_t chunk, int radius, int step, int hop, float* d_windows, const occlusion_stage* occ = nullptr) {
+                               int64_t chunk, int radius, int step, int hop, float* d_windows, const occlusion_stage* occ = nullptr,
+                               saliency_stage* sal = nullptr) {
     constexpr int64_t COLUMN_CAP = 8 * CNN_CHUNK;
     const int64_t* offsets = X.offsets;
     const int B = X.B, C = X.C;
@@ -332,6 +339,10 @@ static int strided_window_loop(f2_ctx* ctx, const f2_cnn* cnn, eval_call* E, con
                                             radius, step, hop, d_windows, (int*)ctx->flags.ptr));
             if (occ) F2_TRY(f2_launch_occlude_windows(ctx, d_windows, m, E->R, C, occ->d_patches, occ->K, occ->fill, (float*)ctx->xbuf.ptr));
             F2_TRY(eval_chunk_convs(ctx, cnn, E, seen));
+            if (sal) {
+                F2_TRY(f2_launch_cnn_input_gradient(ctx, cnn, d_windows, m, nullptr, sal->d_profile + 2 * (size_t)C * (size_t)sal->done, nullptr));
+                sal->done += m;
+            }
         }
         segs.clear();
         m = cols = 0;
@@ -1264,6 +1275,132 @@ int f2_eval_occlusion_batch(f2_ctx* ctx, const f2_cnn* cnn, const void* wave, in
         F2_TRY(f2_upload_async(ctx, d_r, r.data(), sizeof(int64_t) * r.size()));
         F2_TRY(f2_launch_occlusion_map(ctx, E.out.scores.as<float>(), E.out.labels.as<uint8_t>(), d_r, B, K, (int64_t)radius * step, hop, w,
                                        blocks, o.as<double>()));
+        return f2_copy_back(ctx, o);
+    };
+    if (want_map) F2_TRY(reduce(map_or_null, map_bytes, rec, d_rec, map_blocks, width));
+    if (want_summary) F2_TRY(reduce(summary_or_null, summary_bytes, rec1, d_rec1, summary_blocks, 1));
+    int rc = F2_OK;
+    if (n_total > 0)
+        rc = eval_cnn_end(ctx, cnn, &E);   // (waits for the stream)
+    else
+        F2_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (rc == F2_OK || rc == F2_ERR_NONPOSITIVE) picture_range(P, B, range_or_null);
+    return rc;
+}
+
+}  // extern "C"
+
+// ---- `cnn eval --saliency`: f2_saliency_map, and f2_eval_saliency_batch = the figure call with every window differentiated while it
+// is in scratch (f2_cnn_grad.hip) and the map of the per-channel profiles instead of the track ----
+extern "C" {
+
+int f2_saliency_map(f2_ctx* ctx, const double* profile, const int64_t* window_offsets, int U, int C, const int64_t* spans, int64_t origin,
+                    int hop, int width, double* map, int mem_space) {
+    F2_TRY(f2_check_ctx(ctx));
+    F2_TRY(f2_check_mem_space(ctx, mem_space, false));
+    F2_CHECK(ctx, U >= 0 && hop >= 1 && origin >= 0 && width >= 1, F2_ERR_INVALID,
+             "U (%d) and origin (%lld) must be at least 0, hop (%d) and width (%d) at least 1", U, (long long)origin, hop, width);
+    F2_CHECK(ctx, C >= 1, F2_ERR_INVALID, "C (%d) must be at least 1", C);
+    F2_CHECK(ctx, C <= 65535, F2_ERR_UNSUPPORTED, "%d channels (at most 65535)", C);
+    F2_TRY(f2_check_offsets(ctx, window_offsets, U, "window_offsets"));
+    F2_CHECK(ctx, spans, F2_ERR_INVALID, "spans is NULL");
+    const int64_t n_rows = window_offsets[U];
+    F2_CHECK(ctx, profile || n_rows == 0, F2_ERR_INVALID, "profile is NULL");
+    F2_CHECK(ctx, map || U == 0, F2_ERR_INVALID, "map is NULL");
+    int64_t max_rows = 0;
+    for (int u = 0; u < U; ++u) {
+        F2_CHECK(ctx, spans[2 * u] >= 0 && spans[2 * u + 1] >= spans[2 * u], F2_ERR_INVALID, "utterance %d: [%lld, %lld) is not a span", u,
+                 (long long)spans[2 * u], (long long)spans[2 * u + 1]);
+        max_rows = std::max(max_rows, window_offsets[u + 1] - window_offsets[u]);
+    }
+    F2_CHECK(ctx, width <= PICTURE_MAX_WIDTH, F2_ERR_UNSUPPORTED, "width %d (at most %d columns)", width, PICTURE_MAX_WIDTH);
+    int64_t t_last = 0;   // the sample of the last row of the longest utterance has to be an int64
+    F2_CHECK(ctx, max_rows == 0 || (!__builtin_mul_overflow(max_rows - 1, (int64_t)hop, &t_last) && !__builtin_add_overflow(t_last, origin, &t_last)),
+             F2_ERR_UNSUPPORTED, "row %lld at hop %d from origin %lld is beyond int64", (long long)(max_rows - 1), hop, (long long)origin);
+    if (U == 0) return F2_OK;
+
+    std::vector<int64_t> rec;
+    const int64_t blocks = track_records(window_offsets, U, spans, hop, width, &rec);
+    int64_t* d_rec;
+    f2_meta_carve meta;
+    meta.add(&d_rec, rec.size());
+    F2_TRY(meta.reserve(ctx));
+    const void* d_profile;
+    F2_TRY(f2_stage_input(ctx, profile, sizeof(double) * 2 * (size_t)C * (size_t)n_rows, mem_space, &d_profile));
+    f2_output out;
+    F2_TRY(f2_place(ctx, ctx->stage_out, map, sizeof(double) * 3 * (size_t)U * (size_t)C * (size_t)width, mem_space, false, &out));
+    F2_TRY(f2_upload_async(ctx, d_rec, rec.data(), sizeof(int64_t) * rec.size()));
+    F2_TRY(f2_launch_saliency_map(ctx, (const double*)d_profile, d_rec, U, C, origin, hop, width, blocks, out.as<double>()));
+    F2_TRY(f2_copy_back(ctx, out));
+    return f2_host_wait(ctx, mem_space);
+}
+
+// f2_eval_figure_batch's order on the stream, with two changes: after the normal route's convolutions a chunk's windows (still in
+// ctx->xbuf) go through f2_launch_cnn_input_gradient, which keeps 16 C bytes of profile per window in ctx->sal_profile; the map (the
+// caller's spans and width) and the summary (spans [0, n_b), one column) take the track's place, a host caller's behind the scores
+// in ctx->stage_aux.
+int f2_eval_saliency_batch(f2_ctx* ctx, const f2_cnn* cnn, const void* wave, int wave_dtype, const int64_t* offsets, const double* coefs,
+                           int B, int C, int lpf, double cutoff_hz, int fft_precision, int radius, int step, int hop,
+                           const int64_t* spans_or_null, int width, int pool, uint8_t* levels_or_null, double* range_or_null,
+                           double* map_or_null, double* summary_or_null, float* scores_or_null, uint8_t* labels_or_null,
+                           int64_t* window_offsets_or_null, int mem_space) {
+    const f2_batch X = {wave, wave_dtype, offsets, coefs, B, C, lpf, cutoff_hz, fft_precision, mem_space};
+    eval_call E;
+    F2_TRY(eval_check(ctx, cnn, X, radius, step, &E));
+    F2_CHECK(ctx, hop >= 1, F2_ERR_INVALID, "hop must be at least 1 sample (got %d)", hop);
+    F2_TRY(picture_check(ctx, offsets, B, C, spans_or_null, width, pool, mem_space));
+    const int64_t total = X.total();
+    F2_CHECK(ctx, wave || total == 0, F2_ERR_INVALID, "null wave");
+    F2_CHECK(ctx, C <= 65535, F2_ERR_UNSUPPORTED, "%d channels (at most 65535)", C);
+    std::vector<int64_t> nbh((size_t)B), wo((size_t)B + 1, 0), spans(2 * (size_t)B), whole(2 * (size_t)B);
+    for (int b = 0; b < B; ++b) {
+        const int64_t nb = offsets[b + 1] - offsets[b];
+        nbh[(size_t)b] = strided_windows(nb, E.R, step, hop);
+        wo[(size_t)b + 1] = wo[(size_t)b] + nbh[(size_t)b];
+        spans[2 * (size_t)b] = spans_or_null ? spans_or_null[2 * b] : 0;
+        spans[2 * (size_t)b + 1] = spans_or_null ? spans_or_null[2 * b + 1] : nb;
+        whole[2 * (size_t)b] = 0, whole[2 * (size_t)b + 1] = nb;
+    }
+    const int64_t n_total = wo[(size_t)B];
+    if (window_offsets_or_null) memcpy(window_offsets_or_null, wo.data(), sizeof(int64_t) * wo.size());
+    if (B == 0) return F2_OK;
+
+    const bool want_picture = levels_or_null || range_or_null, want_map = map_or_null != nullptr, want_summary = summary_or_null != nullptr;
+    const bool host = mem_space != F2_MEM_DEVICE;
+    const size_t map_bytes = sizeof(double) * 3 * (size_t)B * (size_t)C * (size_t)width, summary_bytes = sizeof(double) * 3 * (size_t)B * (size_t)C;
+    const size_t tail_bytes = host ? (want_map ? map_bytes : 0) + (want_summary ? summary_bytes : 0) : 0;   // a host caller's: behind the scores
+    std::vector<int64_t> rec, rec1;
+    const int64_t map_blocks = track_records(wo.data(), B, spans.data(), hop, width, &rec);
+    const int64_t summary_blocks = track_records(wo.data(), B, whole.data(), hop, 1, &rec1);
+    picture_meta P;
+    int64_t *d_rec, *d_rec1;
+    f2_meta_carve meta;
+    P.add(&meta, B), meta.add(&d_rec, rec.size()), meta.add(&d_rec1, rec1.size());
+    F2_TRY(meta.reserve(ctx));
+    F2_TRY(f2_upload_offsets(ctx, offsets, B));   // (a batch without a sample still gets its pictures)
+    if (total > 0) F2_TRY(eval_envelopes(ctx, &E, X, nullptr, n_total));
+    if (want_picture)
+        F2_TRY(picture_enqueue(ctx, E.d_env, offsets, B, C, spans_or_null, width, pool, &P, nullptr, levels_or_null, range_or_null != nullptr,
+                               mem_space));
+    const bool differentiate = want_map || want_summary;
+    if (n_total > 0) {
+        const int64_t chunk = n_total < CNN_CHUNK ? n_total : CNN_CHUNK;
+        if (differentiate) F2_TRY(f2_reserve(ctx, ctx->sal_profile, sizeof(double) * 2 * (size_t)C * (size_t)n_total));
+        F2_TRY(eval_cnn_begin(ctx, cnn, &E, chunk, n_total, C, scores_or_null, labels_or_null, mem_space, false, tail_bytes));
+        saliency_stage sal = {(double*)ctx->sal_profile.ptr, 0};
+        F2_TRY(strided_window_loop(ctx, cnn, &E, X, nbh, chunk, radius, step, hop, (float*)ctx->xbuf.ptr, nullptr, differentiate ? &sal : nullptr));
+        F2_TRY(eval_dense_flush(ctx, cnn, &E));
+    } else {
+        F2_TRY(f2_place_scores(ctx, nullptr, nullptr, 0, mem_space, false, false, tail_bytes, &E.out));
+    }
+    char* tail = E.out.tail;
+    auto reduce = [&](double* callers, size_t bytes, const std::vector<int64_t>& r, int64_t* d_r, int64_t blocks, int w) -> int {
+        f2_output o;
+        o.dev = host ? tail : (char*)callers, o.host = host ? (char*)callers : nullptr;
+        o.bytes = bytes, o.callers = !host;
+        if (host) tail += bytes;
+        F2_TRY(f2_upload_async(ctx, d_r, r.data(), sizeof(int64_t) * r.size()));
+        F2_TRY(f2_launch_saliency_map(ctx, (const double*)ctx->sal_profile.ptr, d_r, B, C, (int64_t)radius * step, hop, w, blocks, o.as<double>()));
         return f2_copy_back(ctx, o);
     };
     if (want_map) F2_TRY(reduce(map_or_null, map_bytes, rec, d_rec, map_blocks, width));

@@ -172,6 +172,22 @@ class F2CNNModel:
         ctx.cnn_forward(self.handle(ctx), x, x.shape[0], scores, labels, _lib.MEM_HOST)
         return scores, labels
 
+    def input_gradient(self, x, ctx=None):
+        """(G, scores): G (n, rows, channels) float32 = dP(rising)/dx for x (n, rows, channels[,1]) by one backward-data pass on
+        the device, and the (n, 2) float32 scores of the float32 forward pass that recorded its masks (include/f2cnn_hip.h:
+        f2_cnn_input_gradient). Defined for finite x."""
+        ctx = ctx or _lib.default_context()
+        x = np.asarray(x)
+        if x.ndim == 4 and x.shape[-1] == 1:
+            x = x[..., 0]
+        if x.ndim != 3 or x.shape[1:] != (self.rows, self.channels):
+            raise ValueError(f"expected input of shape (n,{self.rows},{self.channels}[,1]), got {x.shape}")
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        grad = np.empty(x.shape, np.float32)
+        scores = np.empty((x.shape[0], 2), np.float32)
+        ctx.cnn_input_gradient(self.handle(ctx), x, x.shape[0], grad, None, scores, _lib.MEM_HOST)
+        return grad, scores
+
     def evaluate(self, x, y, groups=None, n_groups=1, normalize=False, ctx=None):
         """(loss, accuracy) of the model on the windows x (n, rows, channels[,1]) with the signs y (n, 0 / 1): keras
         model.evaluate's pair (reference Training.py:136) - the mean of -ln(clip(score of the true class, 1e-7, 1)) and

@@ -24,6 +24,16 @@ patch a table line is printed - Hz range, rows, label flips, mean and mean absol
 ``figure_width``; not with row bands). ``evalrand`` also prints the table of the corpus. Scores and labels are level 0 of the
 pass, bit for bit those without the flag; ``occlusion=None`` changes nothing.
 
+``saliency=True | N`` (``cnn eval|evalnoise|evalrand --saliency [--saliency-bands N]``; not in the reference) asks the same
+question with one backward pass instead of one forward pass per band: G = dP(rising)/dx for every cell of every normalised window,
+on the device (``f2_eval_saliency_batch``; only sum_r G x and sum_r |G| per window and channel are kept). Per N channels (default
+8) a table line is printed - Hz range, rows, the sums of the mean G x and of the mean |G| - the ``.npz`` gains ``saliency_map``
+(C, W, 3: rows, mean G x, mean |G| per channel and time column), ``saliency_summary`` (C, 3) and ``saliency_span``, and
+``graphs/Saliency/<basename>.png`` shows the G x map under the gammatonegram (``PlottingCNN.RenderSaliency``; W =
+``figure_width``). At N = 8 the G x column is the first-order prediction of ``--occlusion 8:8`` (fill 0) with the sign reversed.
+One map per run: not together with ``occlusion=``. Scores and labels are bit for bit those without the flag; ``saliency=None``
+changes nothing.
+
 ``accuracy='reference'|'centre'`` (``cnn eval|evalnoise|evalrand|noisesweep --accuracy [MODE]``) is the end of the reference's
 ``EvaluateOneWavArray`` (:38-40, :92-108): the decisions held against the labels ``LabelDataGenerator.ExtractLabel`` derives
 from the SOURCE file's ``.FB`` / ``.PHN``, counted on the device (``f2_label_accuracy``, where the rule is written out). A row
@@ -346,10 +356,86 @@ def _write_occlusion(file, stem, occ, N, framerate, source):
                 occlusion_hz=hz)
 
 
+# ---- the saliency map (not in the reference): the input gradient of the decisions, per channel ---------------------------------
+SALIENCY_BANDS = 8
+
+
+def _saliency_bands(saliency):
+    """saliency= as the evaluation functions take it - True, or the channels per line of the table - as that count"""
+    bands = SALIENCY_BANDS if saliency is True else int(saliency)
+    if bands < 1:
+        raise ValueError("a saliency band needs at least 1 channel")
+    return bands
+
+
+def CombineSaliencySummaries(summaries):
+    """The (C, 3) summary {rows, mean G x, mean |G|} of several files as one: rows summed, means weighted by rows (a file without
+    rows, whose means are NaN, weighs nothing; no rows at all: NaN)."""
+    summaries = numpy.asarray(summaries, dtype=numpy.float64).reshape(len(summaries), -1, 3)
+    rows = summaries[..., 0]
+    out = numpy.full(summaries.shape[1:], numpy.nan)
+    out[:, 0] = rows.sum(axis=0)
+    some = out[:, 0] > 0
+    for c in (1, 2):
+        weighted = numpy.where(rows > 0, rows * summaries[..., c], 0.0).sum(axis=0)
+        out[some, c] = weighted[some] / out[some, 0]
+    return out
+
+
+def SaliencyTable(what, cf, summary, bands=SALIENCY_BANDS):
+    """The lines of the table `--saliency` prints: one per `bands` channels - Hz range, rows, and the sums over the band's channels
+    of the mean G x and of the mean |G| of `summary` (C, 3). cf: the channels' centre frequencies. The third column is the
+    first-order prediction of what `--occlusion BANDS:BANDS` measures for the band with fill 0, with the sign reversed."""
+    summary = numpy.asarray(summary, dtype=numpy.float64).reshape(-1, 3)
+    lines = ["\t\t{}\tsaliency: gradient of P(rising) at the input, per band of {} channels".format(what, int(bands)),
+             "\t\t{:>17} {:>9} {:>9} {:>12} {:>12}".format("Hz", "channels", "rows", "sum G x", "sum |G|")]
+    for c0, c1 in _bands(len(summary), bands, bands):
+        part = summary[c0:c1]
+        lines.append("\t\t{:>8.0f}-{:<8.0f} {:>9} {:>9d} {:>+12.6f} {:>12.6f}".format(
+            min(cf[c0], cf[c1 - 1]), max(cf[c0], cf[c1 - 1]), "{}-{}".format(c0, c1 - 1), int(part[0, 0]), part[:, 1].sum(),
+            part[:, 2].sum()))
+    return lines
+
+
+def _saliency_path(stem):
+    return os.path.join('graphs', 'Saliency', stem + '.png')
+
+
+def _write_saliency(file, stem, sal, N, framerate, source):
+    """The table of one file's saliency pass `sal` (EvaluateWavArrays), graphs/Saliency/<stem>.png, and the keys the .npz gains"""
+    from ...png import write_png
+    from ..plotting import PlottingCNN
+    from ..plotting.PlottingProcessing import GetNewHeightERB
+    from ..processing.FBFileReader import GetFormantFrequencies
+    cfg = F2Config()
+    levels = sal['levels']
+    cf = numpy.asarray(filters.centre_freqs(framerate, levels.shape[0], cfg.low_freq), numpy.float64)
+    for line in SaliencyTable(file, cf, sal['summary'], sal['bands']):
+        print(line)
+    _, ratios = GetNewHeightERB(levels, cf)
+    formant, sampPeriod = None, cfg.sampling_period
+    base = os.path.splitext(file)[0]
+    if source == framerate and os.path.exists(base + '.FB'):
+        formant, sampPeriod = GetFormantFrequencies(base + '.FB', _formant_number())
+    rgb = PlottingCNN.RenderSaliency(levels, ratios, sal['map'], (0, N), framerate, formant, sampPeriod, cfg.low_freq)
+    path = _saliency_path(stem)
+    os.makedirs(os.path.dirname(path), exist_ok=True)
+    write_png(path, rgb)
+    print("\t\t{}\tsaliency map -> {}".format(file, path))
+    return dict(saliency_map=sal['map'], saliency_summary=sal['summary'], saliency_span=numpy.array([0, N], numpy.int64))
+
+
 def EvaluateOneWavArray(wavArray, framerate, wavFileName=None, model='last_trained_model', LPF=False, CUTOFF=100,
-                        CENTER_FREQUENCIES=None, FILTERBANK_COEFFICIENTS=None, ctx=None, return_envelopes=False, hop=None):
+                        CENTER_FREQUENCIES=None, FILTERBANK_COEFFICIENTS=None, ctx=None, return_envelopes=False, hop=None,
+                        saliency=None):
     """Returns (scores (nb,2) float32, labels (nb,) uint8 [, envelopes (C,N) float64]); nb = N - 11*STEP, or with a hop
-    ceil(nb / hop) rows, row j centred at sample radius*STEP + j*hop."""
+    ceil(nb / hop) rows, row j centred at sample radius*STEP + j*hop. With saliency= (True, or the channels per table line) the
+    pass is EvaluateWavArrays' and the tuple ends in its saliency dict."""
+    if saliency is not None:
+        if return_envelopes:
+            raise ValueError("the saliency pass does not return envelopes")
+        return EvaluateWavArrays([wavArray], framerate, model=model, LPF=LPF, CUTOFF=CUTOFF,
+                                 FILTERBANK_COEFFICIENTS=FILTERBANK_COEFFICIENTS, ctx=ctx, hop=hop, saliency=saliency)[0]
     if hop is not None and return_envelopes:
         raise ValueError("the strided evaluation (hop) does not return envelopes")
     ctx = ctx or _lib.default_context()
@@ -396,25 +482,29 @@ def EvaluateOneWavArray(wavArray, framerate, wavFileName=None, model='last_train
 
 def EvaluateOneWavFile(file, LPF=False, CUTOFF=50, model='last_trained_model', CENTER_FREQUENCIES=None,
                        FILTERBANK_COEFFICIENTS=None, hop=None, accuracy=None, resample=False, figure=False,
-                       figure_width=FIGURE_WIDTH, occlusion=None):
-    """`cnn eval --file X.WAV [--hop N] [--accuracy [MODE]] [--resample] [--figure] [--occlusion]`: writes <base>.F2CNN.npz
+                       figure_width=FIGURE_WIDTH, occlusion=None, saliency=None):
+    """`cnn eval --file X.WAV [--hop N] [--accuracy [MODE]] [--resample] [--figure] [--occlusion | --saliency]`: writes <base>.F2CNN.npz
     (scores, labels; with a hop also hop, timepoints; with accuracy= and the file's .FB / .PHN also accuracy, confusion,
     accuracy_mode; with resample= framerate, source_framerate; with figure= figure_track, figure_span, and
     graphs/FallingOrRising/<basename>.png; with occlusion= the occlusion_* keys of _write_occlusion, its table, and
-    graphs/Occlusion/<basename>.png) and returns (scores, labels)."""
+    graphs/Occlusion/<basename>.png; with saliency= the saliency_* keys of _write_saliency, its table, and
+    graphs/Saliency/<basename>.png) and returns (scores, labels)."""
     print('Using model', model if not isinstance(model, F2CNNModel) else '<in-memory model>')
     print("File:\t\t{}".format(file))
     source, framerate, wavArray = _load([file], resample)[0]
-    occ = None
-    if figure or occlusion is not None:
+    occ = sal = None
+    if figure or occlusion is not None or saliency is not None:
         result = EvaluateWavArrays([wavArray], framerate, model=model, LPF=LPF, CUTOFF=CUTOFF,
                                    FILTERBANK_COEFFICIENTS=FILTERBANK_COEFFICIENTS, hop=hop,
-                                   figure_width=figure_width if figure else None, occlusion=occlusion, occlusion_width=figure_width)[0]
+                                   figure_width=figure_width if figure else None, occlusion=occlusion, occlusion_width=figure_width,
+                                   saliency=saliency, saliency_width=figure_width)[0]
         scores, labels = result[:2]
         if figure:
             levels, track = result[2:4]
         if occlusion is not None:
             occ = result[-1]
+        if saliency is not None:
+            sal = result[-1]
     else:
         scores, labels = EvaluateOneWavArray(wavArray, framerate, file, model=model, LPF=LPF, CUTOFF=CUTOFF,
                                              CENTER_FREQUENCIES=CENTER_FREQUENCIES,
@@ -427,6 +517,9 @@ def EvaluateOneWavFile(file, LPF=False, CUTOFF=50, model='last_trained_model', C
     if occ is not None:
         extra = dict(extra or {}, **_write_occlusion(file, os.path.splitext(os.path.basename(file))[0], occ, len(wavArray), framerate,
                                                      source))
+    if sal is not None:
+        extra = dict(extra or {}, **_write_saliency(file, os.path.splitext(os.path.basename(file))[0], sal, len(wavArray), framerate,
+                                                    source))
     _save(out, scores, labels, hop, len(wavArray), framerate, extra)
     rising = int(labels.sum())
     print("\t\t{}\tdone ! {} windows: {} rising, {} falling -> {}".format(file, len(labels), rising,
@@ -437,7 +530,7 @@ def EvaluateOneWavFile(file, LPF=False, CUTOFF=50, model='last_trained_model', C
 # ---- batch / noise evaluation (reference scripts/CNN/Evaluating.py:138-221) -------------
 def EvaluateWavArrays(wavArrays, framerate, model='last_trained_model', LPF=False, CUTOFF=100,
                       FILTERBANK_COEFFICIENTS=None, ctx=None, hop=None, figure_width=None, occlusion=None,
-                      occlusion_width=None):
+                      occlusion_width=None, saliency=None, saliency_width=None):
     """EvaluateOneWavArray for a list of utterances of one sample type in one device pass (f2_eval_batch): the
     filterbank and envelope kernels see the whole batch, windows and CNN run utterance by utterance. With a hop
     (f2_eval_batch_strided) every hop-th window, and the window stage and the CNN see the batch as well.
@@ -447,7 +540,13 @@ def EvaluateWavArrays(wavArrays, framerate, model='last_trained_model', LPF=Fals
     With occlusion= (True, (band, stride) or a dict: _occlusion_spec) the pass is f2_eval_occlusion_batch (hop=None: hop 1):
     scores and labels are its level 0, the same bits, and every entry ends in a dict - patches (K, 4), fill, scores (nb, K + 1, 2),
     summary (K, 4), map (K, W, 4) and levels (C, W), W = occlusion_width (default: figure_width, else FIGURE_WIDTH). With
-    figure_width as well the track is f2_score_track of the level-0 scores and the levels are the occlusion call's."""
+    figure_width as well the track is f2_score_track of the level-0 scores and the levels are the occlusion call's.
+    With saliency= (True, or the channels per line of the table: _saliency_bands) the pass is f2_eval_saliency_batch (hop=None: hop
+    1): scores and labels are those without it, the same bits, and every entry ends in a dict - bands, summary (C, 3), map
+    (C, W, 3) and levels (C, W), W = saliency_width (default: figure_width, else FIGURE_WIDTH); with figure_width as well the track
+    is f2_score_track of the scores. One map per pass: not together with occlusion=."""
+    if occlusion is not None and saliency is not None:
+        raise ValueError("one map per pass: occlusion= or saliency=, not both")
     ctx = ctx or _lib.default_context()
     cfg = F2Config()
     if FILTERBANK_COEFFICIENTS is None:
@@ -471,9 +570,24 @@ def EvaluateWavArrays(wavArrays, framerate, model='last_trained_model', LPF=Fals
         nbs = [_lib.strided_window_count(w.shape[0], cfg.radius, STEP, hop) for w in waves]
     scores = numpy.empty((sum(nbs), 2), numpy.float32)
     labels = numpy.empty(sum(nbs), numpy.uint8)
-    levels = track = occ = None
+    levels = track = occ = sal = None
     try:
-        if occlusion is not None:
+        if saliency is not None:
+            B = len(waves)
+            W = int(saliency_width or figure_width or FIGURE_WIDTH)
+            step_hop = 1 if hop is None else hop
+            sal = dict(bands=_saliency_bands(saliency), map=numpy.empty((B, Cn, W, 3), numpy.float64),
+                       summary=numpy.empty((B, Cn, 3), numpy.float64), levels=numpy.zeros((B, Cn, W), numpy.uint8))
+            got, _ = ctx.eval_saliency_batch(model.handle(ctx), flat, dts[0], offsets, coefs, B, Cn, bool(LPF), CUTOFF if LPF else 0.0,
+                                             FFT_PRECISION, cfg.radius, STEP, step_hop, None, W, 0, sal['levels'], sal['map'],
+                                             sal['summary'], scores, labels, _lib.MEM_HOST)
+            assert list(numpy.diff(got)) == nbs
+            if figure_width is not None:
+                levels = sal['levels']
+                whole = numpy.stack([offsets[:-1] * 0, numpy.diff(offsets)], axis=1)
+                track = ctx.score_track(scores, labels, got, whole, cfg.radius * STEP, step_hop, W, numpy.empty((B, W, 5), numpy.float64),
+                                        _lib.MEM_HOST)
+        elif occlusion is not None:
             spec = _occlusion_spec(occlusion)
             patches = OcclusionPatches(cfg.dots_per_input, Cn, spec['band'], spec['stride'], spec['row_band'], spec['row_stride'])
             K, B = len(patches), len(waves)
@@ -517,13 +631,15 @@ def EvaluateWavArrays(wavArrays, framerate, model='last_trained_model', LPF=Fals
         if occ is not None:
             entry += (dict(patches=occ['patches'], fill=occ['fill'], scores=occ['scores'][pos:pos + nb], summary=occ['summary'][b],
                            map=occ['map'][b], levels=occ['levels'][b]),)
+        if sal is not None:
+            entry += (dict(bands=sal['bands'], summary=sal['summary'][b], map=sal['map'][b], levels=sal['levels'][b]),)
         out.append(entry)
         pos += nb
     return out
 
 
 def EvaluateRandom(count=None, LPF=False, CUTOFF=50, model='last_trained_model', hop=None, accuracy=None, resample=False,
-                   figure=False, figure_width=FIGURE_WIDTH, occlusion=None):
+                   figure=False, figure_width=FIGURE_WIDTH, occlusion=None, saliency=None):
     """`cnn evalrand`: evaluate the WAV files under resources/f2cnn/*/ in random order (all of them, or `count`
     drawn with replacement like numpy.random.choice in the reference). The filterbank is designed once and the model
     is uploaded once (the reference reloads the Keras model for every file). With a hop each group of files is one
@@ -532,7 +648,9 @@ def EvaluateRandom(count=None, LPF=False, CUTOFF=50, model='last_trained_model',
     configured framerate first (a file whose rate differed is left out of the accuracy). With figure= each group of files is
     one f2_eval_figure_batch call and every file gets its figure, as EvaluateOneWavFile writes it. With occlusion= each group
     is one f2_eval_occlusion_batch call, every file gets its table, map and .npz keys, and the corpus table is printed at the
-    end: counts summed, means weighted by rows (CombineOcclusionSummaries)."""
+    end: counts summed, means weighted by rows (CombineOcclusionSummaries). With saliency= each group is one
+    f2_eval_saliency_batch call, every file gets its table, map and .npz keys, and the corpus table is printed at the end
+    (CombineSaliencySummaries)."""
     import glob
     import time
     TotalTime = time.time()
@@ -556,6 +674,7 @@ def EvaluateRandom(count=None, LPF=False, CUTOFF=50, model='last_trained_model',
         _accuracy_origin(accuracy, 0, 0)
         corpus = numpy.zeros((2, 2), numpy.int64)
     occlusion_corpus = []                         # (patches, hz, summary) per file
+    saliency_corpus = []                          # (framerate, summary) per file
     BATCH = 16                                    # files per device pass
     for s0 in range(0, len(wavFiles), BATCH):
         group = wavFiles[s0:s0 + BATCH]
@@ -565,12 +684,12 @@ def EvaluateRandom(count=None, LPF=False, CUTOFF=50, model='last_trained_model',
             outs = EvaluateWavArrays([w for _, w in loaded], loaded[0][0], model=model, LPF=LPF, CUTOFF=CUTOFF,
                                      FILTERBANK_COEFFICIENTS=FILTERBANK_COEFFICIENTS, hop=hop,
                                      figure_width=figure_width if figure else None, occlusion=occlusion,
-                                     occlusion_width=figure_width)
-        elif figure or occlusion is not None:     # mixed files: one at a time
+                                     occlusion_width=figure_width, saliency=saliency, saliency_width=figure_width)
+        elif figure or occlusion is not None or saliency is not None:     # mixed files: one at a time
             outs = [EvaluateWavArrays([w], fr, model=model, LPF=LPF, CUTOFF=CUTOFF,
                                       FILTERBANK_COEFFICIENTS=FILTERBANK_COEFFICIENTS if fr == cfg.framerate else None, hop=hop,
                                       figure_width=figure_width if figure else None, occlusion=occlusion,
-                                      occlusion_width=figure_width)[0]
+                                      occlusion_width=figure_width, saliency=saliency, saliency_width=figure_width)[0]
                     for fr, w in loaded]
         else:                                     # mixed files: one at a time
             outs = [EvaluateOneWavArray(w, fr, file, model=model, LPF=LPF, CUTOFF=CUTOFF,
@@ -608,6 +727,10 @@ def EvaluateRandom(count=None, LPF=False, CUTOFF=50, model='last_trained_model',
                     occlusion_corpus = None       # (files of another channel count: no common table)
                 if occlusion_corpus is not None:
                     occlusion_corpus.append((extra['occlusion_patches'], extra['occlusion_hz'], extra['occlusion_summary']))
+            if saliency is not None:
+                extra = dict(extra or {}, **_write_saliency(file, os.path.splitext(os.path.basename(file))[0], result[-1], len(w), fr,
+                                                            source))
+                saliency_corpus.append((fr, extra['saliency_summary']))
             _save(out, scores, labels, hop, len(w), fr, dict(extra or {}, **_rate_keys(resample, fr, source)) or None)
             rising = int(labels.sum())
             print("\t\t{}\tdone ! {} windows: {} rising, {} falling -> {}".format(file, len(labels), rising,
@@ -619,6 +742,11 @@ def EvaluateRandom(count=None, LPF=False, CUTOFF=50, model='last_trained_model',
     if occlusion is not None and occlusion_corpus:
         for line in OcclusionTable("all files", occlusion_corpus[0][0], occlusion_corpus[0][1],
                                    CombineOcclusionSummaries([summary for _, _, summary in occlusion_corpus])):
+            print(line)
+    if saliency is not None and saliency_corpus and len({(fr, len(summary)) for fr, summary in saliency_corpus}) == 1:
+        cf = numpy.asarray(filters.centre_freqs(saliency_corpus[0][0], len(saliency_corpus[0][1]), cfg.low_freq), numpy.float64)
+        for line in SaliencyTable("all files", cf, CombineSaliencySummaries([summary for _, summary in saliency_corpus]),
+                                  _saliency_bands(saliency)):
             print(line)
     print('              Total time:', time.time() - TotalTime)
     print('')
@@ -651,7 +779,7 @@ def add_gaussian_noise(wave, SNRdB, rng=None):
 
 def EvaluateWithNoise(file, LPF=False, CUTOFF=100, model='last_trained_model', CENTER_FREQUENCIES=None,
                       FILTERBANK_COEFFICIENTS=None, SNRdB=-3, rng=None, hop=None, accuracy=None, resample=False, figure=False,
-                      figure_width=FIGURE_WIDTH, occlusion=None):
+                      figure_width=FIGURE_WIDTH, occlusion=None, saliency=None):
     """`cnn evalnoise` (reference: scripts/CNN/Evaluating.py:193-221): the file plus Gaussian noise at the requested level is
     written next to copies of its annotation files under OutputWavFiles/addedNoise/ and the float64 waveform is evaluated by
     the device pipeline. Returns (scores, labels) and also leaves them in <target>.F2CNN.npz; `rng` (a numpy Generator or
@@ -659,7 +787,8 @@ def EvaluateWithNoise(file, LPF=False, CUTOFF=100, model='last_trained_model', C
     run is scored against the labels of the clean file's .FB / .PHN (what the copies under addedNoise/ are there for). With
     resample= the noise is added to the resampled, one-channel signal and the noisy WAV is written at the configured framerate.
     With figure= the noisy run's figure goes to graphs/FallingOrRising/<noisy stem>.png, its overlays from the clean file's
-    side files. With occlusion= the noisy run's occlusion table, .npz keys and graphs/Occlusion/<noisy stem>.png."""
+    side files. With occlusion= the noisy run's occlusion table, .npz keys and graphs/Occlusion/<noisy stem>.png; with saliency=
+    its saliency table, .npz keys and graphs/Saliency/<noisy stem>.png."""
     import shutil
     from scipy.io import wavfile
     print("File:\t\t{}".format(file))
@@ -674,16 +803,19 @@ def EvaluateWithNoise(file, LPF=False, CUTOFF=100, model='last_trained_model', C
         if os.path.exists(source + ext):
             shutil.copyfile(source + ext, target + ext)
     print('New noisy WAVE file saved as', target + '.WAV')
-    occ = None
-    if figure or occlusion is not None:
+    occ = sal = None
+    if figure or occlusion is not None or saliency is not None:
         result = EvaluateWavArrays([noisy], framerate, model=model, LPF=LPF, CUTOFF=CUTOFF,
                                    FILTERBANK_COEFFICIENTS=FILTERBANK_COEFFICIENTS, hop=hop,
-                                   figure_width=figure_width if figure else None, occlusion=occlusion, occlusion_width=figure_width)[0]
+                                   figure_width=figure_width if figure else None, occlusion=occlusion, occlusion_width=figure_width,
+                                   saliency=saliency, saliency_width=figure_width)[0]
         scores, labels = result[:2]
         if figure:
             levels, track = result[2:4]
         if occlusion is not None:
             occ = result[-1]
+        if saliency is not None:
+            sal = result[-1]
     else:
         scores, labels = EvaluateOneWavArray(noisy, framerate, target + '.WAV', model=model, LPF=LPF, CUTOFF=CUTOFF,
                                              CENTER_FREQUENCIES=CENTER_FREQUENCIES,
@@ -694,6 +826,8 @@ def EvaluateWithNoise(file, LPF=False, CUTOFF=100, model='last_trained_model', C
                                                   extra))
     if occ is not None:
         extra = dict(extra or {}, **_write_occlusion(file, os.path.basename(target), occ, len(noisy), framerate, source_rate))
+    if sal is not None:
+        extra = dict(extra or {}, **_write_saliency(file, os.path.basename(target), sal, len(noisy), framerate, source_rate))
     _save(target + '.F2CNN.npz', scores, labels, hop, len(noisy), framerate, extra)
     print("\t\t{}\tdone !".format(file))
     return scores, labels

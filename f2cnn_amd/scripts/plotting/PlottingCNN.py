@@ -20,7 +20,9 @@ of the device's track (f2_score_track / f2_eval_figure_batch):
 Legends and axis labels are not drawn.
 
 ``RenderOcclusion`` (not in the reference) is the picture of ``--occlusion``: the same upper panel over a panel of the same
-geometry that shows, per channel band and time column, how far blanking the band moves the probability of "rising"."""
+geometry that shows, per channel band and time column, how far blanking the band moves the probability of "rising".
+``RenderSaliency`` (not in the reference) is the picture of ``--saliency``: the same two panels, the lower one the input gradient
+times the input, summed over the window's rows, per channel and time column."""
 import numpy
 
 from ..processing.FBFileReader import frame_windows
@@ -214,6 +216,33 @@ def RenderOcclusion(levels, ratios, map, patches, span, framerate, formant=None,
     mean_d[:, map[0, :, 0] == 0] = numpy.nan           # (the columns own the same rows whatever the patch)
     finite = numpy.abs(map[..., 2][numpy.isfinite(map[..., 2])])
     lower = numpy.repeat(diverging_colours(mean_d, finite.max() if finite.size else 0.0), ratios, axis=0)
+    if formant is not None:
+        for panel in (upper, lower):
+            draw_formants(panel, [formant], sampPeriod, framerate, start, end, low_freq)
+    gap = numpy.full((GAP_ROWS, width, 3), 255, numpy.uint8)
+    return numpy.concatenate([upper, gap, lower], axis=0)
+
+
+def RenderSaliency(levels, ratios, map, span, framerate, formant=None, sampPeriod=10000, low_freq=100):
+    """The saliency figure as (2 * sum(ratios) + GAP_ROWS, W, 3) uint8, column x of both panels column x of the device's map
+    (f2_saliency_map / f2_eval_saliency_batch):
+
+        upper panel   the gammatonegram as RenderFigure draws it, the formant's track in black
+        GAP_ROWS      white rows
+        lower panel   the same geometry: channel c takes the ERB row height ratios[c] and, in column x, the colour of the mean of
+                      sum_r G x = map[c][x][1] on diverging_colours, scaled to the largest magnitude of the file: red where the
+                      channel's energy pushes P(rising) up, blue where it pushes it down, white where it does nothing. A column
+                      without rows is grey. The formant's track in black again.
+
+    levels (C, W) uint8; map (C, W, 3) float64 {rows, mean G x, mean |G|}; span = (start, end) samples of a file at `framerate`;
+    formant: its track in Hz, one value per frame of sampPeriod microseconds, or None."""
+    levels, map = numpy.asarray(levels), numpy.asarray(map, dtype=numpy.float64)
+    width = levels.shape[1]
+    start, end = int(span[0]), int(span[1])
+    upper = colour_table()[numpy.repeat(levels, ratios, axis=0)]
+    gx = numpy.where(map[..., 0] > 0, map[..., 1], numpy.nan)
+    finite = numpy.abs(gx[numpy.isfinite(gx)])
+    lower = numpy.repeat(diverging_colours(gx, finite.max() if finite.size else 0.0), ratios, axis=0)
     if formant is not None:
         for panel in (upper, lower):
             draw_formants(panel, [formant], sampPeriod, framerate, start, end, low_freq)

@@ -627,6 +627,70 @@ int f2_eval_occlusion_batch(f2_ctx* ctx, const f2_cnn* cnn, const void* wave, in
                             float* scores_or_null /* (n, K+1, 2) */, uint8_t* labels_or_null /* (n, K+1) */,
                             int64_t* window_offsets_or_null /* host, B+1 */, int mem_space);
 
+/* ---- `cnn eval|evalnoise|evalrand --saliency`: the input gradient of the decisions, one backward pass on the device -----------
+ * The complement of the occlusion map: G = dP(rising)/dx for every cell of every normalised window comes from one backward-data
+ * pass through the network (f2_cnn.hip's head comment), at a cost that does not depend on the resolution asked for. sum G x over a
+ * band of channels is the first-order prediction of what the occlusion map measures for that band with fill 0, sign reversed.
+ * (f2_version stays 114 with these three entries: look the symbols up to find out whether a build has them.)
+ *
+ * f2_cnn_input_gradient: x (n, R, C) float32 in mem_space, R = rows and C = channels of the f2_cnn. With P = softmax(z)[1]:
+ *   grad    (n, R, C) float32   G[w][r][c] = dP_w/dx[w][r][c] = P (1 - P) d(z1 - z0)/dx
+ *   profile (n, C, 2) float64   [w][c][0] = sum over r (ascending) of (double)G[w][r][c] * (double)x[w][r][c]
+ *                               [w][c][1] = sum over r of |(double)G[w][r][c]|
+ *   scores  (n, 2) float32      the scores of the recorded forward
+ * Every output is optional (NULL), all in mem_space. All arithmetic is float32 with float32 accumulation. The masks come from the
+ * "recorded forward", a pass of the float32 kernels' arithmetic (fmaf chains; not the split-fp16 route), so its scores are not
+ * promised bit-equal to f2_cnn_forward's: they lie within the 2e-5 of the oracle that f2_cnn_forward's lie within.
+ *   ReLU       passes gradient where its pre-activation is > 0; at exactly 0 the gradient is 0
+ *   max-pool   sends the gradient to the maximal element of its 2 x 2 block, among equal elements to the first in (row, column)
+ *              order; rows and columns of conv2's and conv4's output that the pool drops (odd height or width) get gradient 0
+ * Behaviour is defined for finite x: a window with a non-finite value may get any G and any scores, without a fault and without
+ * changing another window's bits. Sums have a fixed order and there are no floating-point atomics: the same bits on every call, in
+ * both memory spaces and wherever a window stands in the batch. The chain works in chunks of at most 1024 windows whose
+ * activations and gradients stay within 1 GiB of context scratch whatever n is; F2_MEM_HOST calls stage 4096 windows at a time and
+ * return when the outputs are filled, F2_MEM_DEVICE calls enqueue and return (the first gradient call of an f2_cnn builds its
+ * rotated, transposed weights and waits for that). Device pointers need element alignment only.
+ * F2_ERR_INVALID, with nothing launched or written: a NULL ctx or cnn, a cnn of another device, n < 0, NULL x with n > 0, a
+ * mem_space other than F2_MEM_HOST / F2_MEM_DEVICE. n == 0: F2_OK.
+ *
+ * f2_saliency_map: profile (window_offsets[U], C, 2) float64 in mem_space, rows as f2_cnn_input_gradient writes them. Rows, spans
+ * and columns are those of f2_score_track (same origin, hop, spans, width rule).
+ *   map   (U, C, W, 3) float64 in mem_space, map[u][c][x] =
+ *           [0] rows        the count of owned rows, exact
+ *           [1] mean G x    the float64 sum of profile[j][c][0] over the owned rows, divided by rows
+ *           [2] mean |G|    the float64 sum of profile[j][c][1], divided by rows
+ *         A column without rows is {0, NaN, NaN}. The sums have f2_score_track's fixed order: the same bits on every call and in
+ *         both memory spaces.
+ * Argument errors: those of f2_score_track (profile in the place of scores and labels), and C < 1 (F2_ERR_INVALID), C > 65535
+ * (F2_ERR_UNSUPPORTED). U == 0: F2_OK.
+ *
+ * f2_eval_saliency_batch: f2_eval_figure_batch with every window differentiated while it is in scratch, and the map in the track's
+ * place. Every output is optional and defined by calls that exist, bit for bit:
+ *   scores (n, 2), labels (n), window_offsets, levels (B, C, W), range (host, 2B)   what f2_eval_figure_batch returns: the normal
+ *           route still makes the decisions
+ *   map (B, C, W, 3)   f2_saliency_map of the profile f2_cnn_input_gradient gives for the normalised windows of f2_input_batch
+ *           (normalize = 1) at the same centres; origin = radius*step, the same hop, spans (NULL: [0, n_b)), width
+ *   summary (B, C, 3)  f2_saliency_map with spans [0, n_b) and width 1: every row of the utterance
+ * Only the profile is kept for all windows (16 C bytes per window). Errors, before anything is launched or written: everything
+ * f2_eval_figure_batch rejects, and C > 65535 (F2_ERR_UNSUPPORTED). F2_ERR_NONPOSITIVE as in the strided call. B == 0: F2_OK. The
+ * call waits for the stream before it returns.
+ */
+int f2_cnn_input_gradient(f2_ctx* ctx, const f2_cnn* cnn, const float* x /* (n, R, C), mem_space */, int64_t n,
+                          float* grad_or_null /* (n, R, C), mem_space */, double* profile_or_null /* (n, C, 2), mem_space */,
+                          float* scores_or_null /* (n, 2), mem_space */, int mem_space);
+int f2_saliency_map(f2_ctx* ctx, const double* profile /* (window_offsets[U], C, 2), mem_space */,
+                    const int64_t* window_offsets /* host, U+1 */, int U, int C,
+                    const int64_t* spans /* host, 2U, required */, int64_t origin, int hop, int width,
+                    double* map /* (U, C, width, 3), mem_space */, int mem_space);
+int f2_eval_saliency_batch(f2_ctx* ctx, const f2_cnn* cnn, const void* wave, int wave_dtype, const int64_t* offsets,
+                           const double* coefs, int B, int C, int lpf, double cutoff_hz, int fft_precision,
+                           int radius, int step, int hop,
+                           const int64_t* spans_or_null /* host, 2B */, int width, int pool,
+                           uint8_t* levels_or_null /* (B, C, width), mem_space */, double* range_or_null /* host, 2B */,
+                           double* map_or_null /* (B, C, width, 3), mem_space */, double* summary_or_null /* (B, C, 3), mem_space */,
+                           float* scores_or_null /* (n, 2) */, uint8_t* labels_or_null /* (n) */,
+                           int64_t* window_offsets_or_null /* host, B+1 */, int mem_space);
+
 /* ---- `cnn lpfsweep`: one ragged batch at K envelope cutoffs and unfiltered, in one device pass ------------------------------
  * The reference low-passes the envelope after the magnitude (EnvelopeExtraction.py:39-67), so the filterbank and the Hilbert
  * transform do not depend on the cutoff: a sweep needs them once, and one low-pass of envelopes that are already in memory.
