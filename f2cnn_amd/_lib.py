@@ -14,6 +14,7 @@ import numpy as np
 from . import build as _build
 
 F2_OK, F2_ERR_INVALID, F2_ERR_HIP, F2_ERR_UNSUPPORTED, F2_ERR_NOMEM, F2_ERR_NONPOSITIVE = 0, -1, -2, -3, -4, -5
+CNN_ROUTES = {"call": 0, "f32": 1, "tile": 2, "ws": 3, "ws_dense": 4, "recorded": 5}   # F2_CNN_ROUTE_* of f2_cnn_layers
 MEM_HOST, MEM_DEVICE, MEM_HOST_ASYNC = 0, 1, 2
 WAVE_I16, WAVE_F64 = 0, 1
 FFT_F32, FFT_F64 = 0, 1
@@ -85,6 +86,7 @@ SIGNATURES = {
     "f2_eval_occlusion_batch": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _d, _i, _i, _i, _i, _vp, _i, C.c_float, _vp, _i, _i, _vp,
                                      _vp, _vp, _vp, _vp, _vp, _vp, _i]),
     "f2_cnn_input_gradient": (_i, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _i]),
+    "f2_cnn_layers": (_i, [_vp, _vp, _vp, _i64, _i, _vp, _vp, _vp, _i]),
     "f2_saliency_map": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i64, _i, _i, _vp, _i]),
     "f2_eval_saliency_batch": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _d, _i, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp,
                                     _vp, _vp, _i]),
@@ -367,6 +369,14 @@ class Context:
 
     def cnn_forward(self, handle, x, n, scores, labels, mem_space):
         self.check(self.lib.f2_cnn_forward(self.handle, handle, _ptr(x), int(n), _ptr(scores), _ptr(labels), mem_space))
+
+    def cnn_layers(self, handle, x, n, route, pooled, dense1, scores, mem_space):
+        """Inspection entry (f2_cnn_layers): conv4's pooled output (n, flat) in (row, column, channel) order, dense1's output
+        (n, 516) and the scores (n, 2), all float32, of n windows on `route` - a CNN_ROUTES value: "call" is what cnn_forward
+        does, the others force their kernels and raise F2Error (F2_ERR_UNSUPPORTED) where the network or the input cannot take
+        them. numpy arrays or device pointers, by mem_space; any output may be None."""
+        self.check(self.lib.f2_cnn_layers(self.handle, handle, _ptr(x), int(n), int(route), _ptr(pooled), _ptr(dense1), _ptr(scores),
+                                          mem_space))
 
     def eval_utterance(self, handle, wave, wave_dtype, N, coefs, Cn, lpf, cutoff, precision, radius, step, env, scores,
                        labels, mem_space):

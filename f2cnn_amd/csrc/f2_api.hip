@@ -197,7 +197,7 @@ int f2_prof_end(f2_ctx* ctx, int kernel_id) {
 
 extern "C" {
 
-int f2_version(void) { return 114; }   // 101: f2_eval_batch; 102: f2_host_alloc, F2_MEM_HOST_ASYNC; 103: f2_ctx_set_option; 104: f2_event_query; 105: f2_spectral_guard_read; 106: f2_cnn_forward takes any finite input on the split path; 107: f2_input_batch; 108: f2_eval_batch_strided; 109: f2_eval_noise_sweep; 110: f2_label_accuracy; 111: f2_cnn_score_windows; 112: f2_envelope_picture, f2_gammatonegram_batch; 113: f2_resample_batch; 114: f2_score_track, f2_eval_figure_batch (and, without a new number - tests/test_figure_host.py pins this one -, f2_occlude_windows, f2_occlusion_map, f2_eval_occlusion_batch)
+int f2_version(void) { return 115; }   // 101: f2_eval_batch; 102: f2_host_alloc, F2_MEM_HOST_ASYNC; 103: f2_ctx_set_option; 104: f2_event_query; 105: f2_spectral_guard_read; 106: f2_cnn_forward takes any finite input on the split path; 107: f2_input_batch; 108: f2_eval_batch_strided; 109: f2_eval_noise_sweep; 110: f2_label_accuracy; 111: f2_cnn_score_windows; 112: f2_envelope_picture, f2_gammatonegram_batch; 113: f2_resample_batch; 114: f2_score_track, f2_eval_figure_batch (and, without a new number - tests/test_figure_host.py pins this one -, f2_occlude_windows, f2_occlusion_map, f2_eval_occlusion_batch); 115: f2_cnn_layers
 
 int f2_device_count(int* count) {
     if (!count) return f2_fail(nullptr, F2_ERR_INVALID, "count is NULL");

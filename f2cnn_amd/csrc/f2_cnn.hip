@@ -1142,6 +1142,11 @@ int f2_launch_cnn_dense(f2_ctx* ctx, const f2_cnn* cnn, const f2_scale_set* S, f
     return f2_prof_end(ctx, F2_K_CNN);
 }
 
+// (the counterpart of sin_d above: the routes whose conv4 output is not in true units)
+float f2_cnn_a4_scale(const f2_cnn* cnn, const f2_scale_set* S, f2_cnn_route route) {
+    return route.split && S && make_dims(cnn->rows, cnn->channels).Hp1 == 4 ? S->sa_d1 : 1.f;
+}
+
 // the split path's scales are powers of two inside [2^-20, 2^20]
 static double pow2_floor(double v) { return v > 0 && std::isfinite(v) ? std::exp2(std::floor(std::log2(v))) : 1.0; }
 constexpr double SCALE_LO = 0x1p-20, SCALE_HI = 0x1p20;

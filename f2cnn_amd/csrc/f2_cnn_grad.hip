@@ -540,8 +540,23 @@ grad_ws grad_ws_shape(const Dims& d) {
     w.per[grad_ws::SC] = 2;
     return w;
 }
+// where the arrays of a chunk of `chunk` windows stand in ctx->grad_ws (float offsets); returns the floats all of them take
+size_t grad_ws_offsets(const grad_ws& shape, int64_t chunk, size_t off[grad_ws::COUNT]) {
+    size_t total = 0;
+    for (int k = 0; k < grad_ws::COUNT; ++k) off[k] = total, total += (shape.per[k] * (size_t)chunk + 63) & ~size_t(63);
+    return total;
+}
 
 }  // namespace
+
+// conv4's pooled output (m, flat) and dense1's output (m, 516) of the recorded forward, as the last f2_launch_cnn_input_gradient
+// on this context left them for a call of m <= f2_cnn_grad_chunk windows (valid until the next gradient launch reuses the area)
+void f2_cnn_grad_recorded(const f2_ctx* ctx, const f2_cnn* cnn, int64_t m, const float** p2, const float** a5) {
+    size_t off[grad_ws::COUNT];
+    grad_ws_offsets(grad_ws_shape(make_dims(cnn->rows, cnn->channels)), m, off);
+    *p2 = (const float*)ctx->grad_ws.ptr + off[grad_ws::P2];
+    *a5 = (const float*)ctx->grad_ws.ptr + off[grad_ws::A5];
+}
 
 int64_t f2_cnn_grad_chunk(const f2_cnn* cnn) {
     const grad_ws shape = grad_ws_shape(make_dims(cnn->rows, cnn->channels));
@@ -560,11 +575,9 @@ int f2_launch_cnn_input_gradient(f2_ctx* ctx, const f2_cnn* cnn, const float* d_
     const grad_layout L = grad_weight_layout(cnn->flat);
     const int64_t chunk = std::min(n, f2_cnn_grad_chunk(cnn));
     float* arr[grad_ws::COUNT];
-    size_t total = 0;
-    for (int k = 0; k < grad_ws::COUNT; ++k) total += (shape.per[k] * (size_t)chunk + 63) & ~size_t(63);
-    F2_TRY(f2_reserve(ctx, ctx->grad_ws, sizeof(float) * total));
-    total = 0;
-    for (int k = 0; k < grad_ws::COUNT; ++k) arr[k] = (float*)ctx->grad_ws.ptr + total, total += (shape.per[k] * (size_t)chunk + 63) & ~size_t(63);
+    size_t off[grad_ws::COUNT];
+    F2_TRY(f2_reserve(ctx, ctx->grad_ws, sizeof(float) * grad_ws_offsets(shape, chunk, off)));
+    for (int k = 0; k < grad_ws::COUNT; ++k) arr[k] = (float*)ctx->grad_ws.ptr + off[k];
     const size_t xs = (size_t)d.H1 * d.W1;
     unsigned g;
     for (int64_t s = 0; s < n; s += chunk) {

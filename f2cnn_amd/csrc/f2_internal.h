@@ -488,6 +488,11 @@ int f2_launch_cnn_convs(f2_ctx* ctx, const f2_cnn* cnn, const f2_scale_set* S, f
                         float* d_ws, float* a4);
 int f2_launch_cnn_dense(f2_ctx* ctx, const f2_cnn* cnn, const f2_scale_set* S, f2_cnn_route route, const float* a4, int64_t n, float* a5,
                         float* d_scores, uint8_t* d_labels);
+// what f2_launch_cnn_convs leaves a4 multiplied by on this route: dense1's input scale where the split conv4 kernels wrote it
+// (windows with four pooled rows after conv2), 1 everywhere else
+float f2_cnn_a4_scale(const f2_cnn* cnn, const f2_scale_set* S, f2_cnn_route route);
+// d_dst[i] = d_src[i] * factor for count floats (f2_cnn_layers.hip)
+int f2_launch_scale_copy(f2_ctx* ctx, const float* d_src, float* d_dst, int64_t count, float factor);
 // k_cnn_input_range (f2_cnn_range.hip) over nwin windows of S floats at d_x: atomicMax of the bit pattern of max |x| over the finite
 // values into d_words[0], of the complement of the quietest window's max |x| into d_words[2], and 1 into d_words[1] if a value is
 // inf / NaN. The caller zeroes the three words first.
@@ -602,6 +607,9 @@ int f2_launch_occlusion_map(f2_ctx* ctx, const float* d_scores, const uint8_t* d
 // d_scores (n, 2) or NULL; with neither d_grad nor d_profile only the forward runs. Element alignment is enough for all four.
 // The map's d_rec, lanes and workgroups are those of f2_launch_score_track; d_profile (rows, C, 2), d_map (U, C, width, 3) float64.
 int64_t f2_cnn_grad_chunk(const f2_cnn* cnn);
+// (f2_cnn_layers) the recorded forward's pooled conv4 output (m, flat) and dense1 output (m, 516) in ctx->grad_ws after a launch of
+// m <= f2_cnn_grad_chunk windows, valid until the next gradient launch on the context
+void f2_cnn_grad_recorded(const f2_ctx* ctx, const f2_cnn* cnn, int64_t m, const float** p2, const float** a5);
 int f2_launch_cnn_input_gradient(f2_ctx* ctx, const f2_cnn* cnn, const float* d_x, int64_t n, float* d_grad, double* d_profile,
                                  float* d_scores);
 int f2_launch_saliency_map(f2_ctx* ctx, const double* d_profile, const int64_t* d_rec, int U, int C, int64_t origin, int hop, int width,

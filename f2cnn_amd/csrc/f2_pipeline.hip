@@ -56,17 +56,12 @@ int measure_input_range(f2_ctx* ctx, const float* d_x, int64_t nwin, int S, inpu
     return F2_OK;
 }
 
-// Scale set, route and last_input_bound of f2_cnn_forward (and of f2_cnn_score_windows without normalisation) for the nwin windows
-// at d_x. The split path's scales follow the input (f2_cnn_split.h), so the windows are measured - unless the float32 kernels run
-// whatever the input: B = 1 for max |x| <= 1, else B = 2^ceil(log2 max |x|), and *bound = B. *S = NULL, the float32 route and
-// *bound = -1 without the split path, after inf / NaN, for a B whose scales leave the clamp, or when B > 2^QUIET_BINADES and a
-// window's max |x| lies below B / 2^QUIET_BINADES.
-int forward_route(f2_ctx* ctx, const f2_cnn* cnn, const float* d_x, int64_t nwin, const f2_scale_set** S, f2_cnn_route* route,
-                  double* bound) {
+// The range pass over the nwin windows at d_x and the scale set of its bound: B = 1 for max |x| <= 1, else B = 2^ceil(log2 max |x|),
+// and *bound = B. *S = NULL and *bound = -1 after inf / NaN, for a B whose scales leave the clamp (or a network without the split
+// path), or when B > 2^QUIET_BINADES and a window's max |x| lies below B / 2^QUIET_BINADES.
+int measured_scale_set(f2_ctx* ctx, const f2_cnn* cnn, const float* d_x, int64_t nwin, const f2_scale_set** S, double* bound) {
     *S = nullptr;
-    *route = f2_cnn_route();
     *bound = -1.0;
-    if (!f2_cnn_call_route(ctx, cnn, true).split) return F2_OK;
     input_range r;
     F2_TRY(measure_input_range(ctx, d_x, nwin, cnn->rows * cnn->channels, &r));
     if (r.bad) return F2_OK;
@@ -79,6 +74,20 @@ int forward_route(f2_ctx* ctx, const f2_cnn* cnn, const float* d_x, int64_t nwin
     }
     F2_TRY(f2_cnn_scale_set(ctx, cnn, e, S));
     if (*S) *bound = std::ldexp(1.0, e);
+    return F2_OK;
+}
+
+// Scale set, route and last_input_bound of f2_cnn_forward (and of f2_cnn_score_windows without normalisation) for the nwin windows
+// at d_x. The split path's scales follow the input (f2_cnn_split.h), so the windows are measured (measured_scale_set) - unless the
+// float32 kernels run whatever the input. *S = NULL, the float32 route and *bound = -1 without the split path and for the inputs
+// measured_scale_set has no set for.
+int forward_route(f2_ctx* ctx, const f2_cnn* cnn, const float* d_x, int64_t nwin, const f2_scale_set** S, f2_cnn_route* route,
+                  double* bound) {
+    *S = nullptr;
+    *route = f2_cnn_route();
+    *bound = -1.0;
+    if (!f2_cnn_call_route(ctx, cnn, true).split) return F2_OK;
+    F2_TRY(measured_scale_set(ctx, cnn, d_x, nwin, S, bound));
     *route = f2_cnn_call_route(ctx, cnn, *S != nullptr);
     return F2_OK;
 }
@@ -166,6 +175,76 @@ int f2_cnn_forward(f2_ctx* ctx, const f2_cnn* cnn, const float* x, int64_t n, fl
     }
     cnn->last_input_bound = bound;
     return F2_OK;
+}
+
+// The inspection entry: one launch group of f2_cnn_forward's kernels on a named route, with conv4's pooled output and dense1's
+// output copied out of the workspace. Every refusal comes before the first output byte is written.
+int f2_cnn_layers(f2_ctx* ctx, const f2_cnn* cnn, const float* x, int64_t n, int route, float* pooled_or_null, float* dense1_or_null,
+                  float* scores_or_null, int mem_space) {
+    F2_TRY(f2_check_ctx(ctx));
+    F2_TRY(f2_check_cnn(ctx, cnn, 0, 0));
+    F2_TRY(f2_check_mem_space(ctx, mem_space, false));
+    F2_CHECK(ctx, n >= 0, F2_ERR_INVALID, "negative window count");
+    F2_CHECK(ctx, route >= F2_CNN_ROUTE_CALL && route <= F2_CNN_ROUTE_RECORDED, F2_ERR_INVALID, "bad route %d", route);
+    if (n == 0) return F2_OK;
+    F2_CHECK(ctx, x, F2_ERR_INVALID, "x is NULL");
+    F2_CHECK(ctx, n <= CNN_CHUNK, F2_ERR_UNSUPPORTED, "%lld windows: f2_cnn_layers takes at most %lld", (long long)n, (long long)CNN_CHUNK);
+    const bool recorded = route == F2_CNN_ROUTE_RECORDED;
+    f2_cnn_route want;   // of a forced route
+    want.split = !recorded && route >= F2_CNN_ROUTE_TILE, want.ws = !recorded && route >= F2_CNN_ROUTE_WS, want.ws_dense = route == F2_CNN_ROUTE_WS_DENSE;
+    const f2_cnn_route can = f2_cnn_capability(cnn);
+    F2_CHECK(ctx, (can.split || !want.split) && (can.ws || !want.ws) && (can.ws_dense || !want.ws_dense), F2_ERR_UNSUPPORTED,
+             "this %d x %d network does not run on route %d (split %d, weight-stationary %d, its dense1 %d)", cnn->rows, cnn->channels,
+             route, (int)can.split, (int)can.ws, (int)can.ws_dense);
+    const size_t xs = (size_t)cnn->rows * cnn->channels, flat = f2_cnn_flat_floats(cnn), d1 = f2_cnn_dense_floats(cnn) - flat;
+    F2_CHECK(ctx, !want.ws_dense || f2_dense1_ws_takes((int)flat, n), F2_ERR_UNSUPPORTED, "k_dense1_ws does not take %lld windows of %zu",
+             (long long)n, flat);
+    const void* d_x;
+    F2_TRY(f2_stage_input(ctx, x, sizeof(float) * xs * (size_t)n, mem_space, &d_x));
+    const f2_scale_set* S = nullptr;
+    f2_cnn_route r;
+    double b = -1.0;
+    if (route == F2_CNN_ROUTE_CALL) {
+        F2_TRY(forward_route(ctx, cnn, (const float*)d_x, n, &S, &r, &b));
+    } else if (want.split) {
+        F2_TRY(measured_scale_set(ctx, cnn, (const float*)d_x, n, &S, &b));
+        F2_CHECK(ctx, S, F2_ERR_UNSUPPORTED, "no scale set of the split path for this input (inf / NaN, or out of its range)");
+        r = want;
+    }
+    f2_output po, do1;
+    f2_score_outputs so;
+    F2_TRY(f2_place(ctx, ctx->stage_out, pooled_or_null, sizeof(float) * flat * (size_t)n, mem_space, false, &po));
+    F2_TRY(f2_place(ctx, ctx->work2, dense1_or_null, sizeof(float) * d1 * (size_t)n, mem_space, false, &do1));
+    F2_TRY(f2_place_scores(ctx, scores_or_null, nullptr, n, mem_space, false, false, 0, &so));
+    if (recorded) {
+        // the gradient chain's forward, chunk by chunk through its own scratch: what it recorded is copied out before the next chunk
+        const int64_t chunk = f2_cnn_grad_chunk(cnn);
+        for (int64_t s = 0; s < n; s += chunk) {
+            const int64_t m = n - s < chunk ? n - s : chunk;
+            float* sc = so.scores.dev ? so.scores.as<float>() + 2 * (size_t)s : nullptr;
+            F2_TRY(f2_launch_cnn_input_gradient(ctx, cnn, (const float*)d_x + (size_t)s * xs, m, nullptr, nullptr, sc));
+            const float *p2, *a5;
+            f2_cnn_grad_recorded(ctx, cnn, m, &p2, &a5);
+            if (po.dev)
+                F2_HIP(ctx, hipMemcpyAsync(po.as<float>() + flat * (size_t)s, p2, sizeof(float) * flat * (size_t)m, hipMemcpyDeviceToDevice, ctx->stream));
+            if (do1.dev)
+                F2_HIP(ctx, hipMemcpyAsync(do1.as<float>() + d1 * (size_t)s, a5, sizeof(float) * d1 * (size_t)m, hipMemcpyDeviceToDevice, ctx->stream));
+        }
+    } else {
+        const size_t per = f2_cnn_workspace_floats(cnn);
+        F2_TRY(f2_reserve(ctx, ctx->work, sizeof(float) * per * (size_t)n));
+        float* d_ws = (float*)ctx->work.ptr;
+        float* a4 = d_ws + (size_t)n * (per - flat - d1);   // the workspace as f2_launch_cnn lays it out: [conv2 | conv3 | conv4 | dense1]
+        float* a5 = a4 + (size_t)n * flat;
+        F2_TRY(f2_launch_cnn_convs(ctx, cnn, S, r, (const float*)d_x, n, d_ws, a4));
+        F2_TRY(f2_launch_cnn_dense(ctx, cnn, S, r, a4, n, a5, so.scores.as<float>(), nullptr));
+        if (po.dev) F2_TRY(f2_launch_scale_copy(ctx, a4, po.as<float>(), (int64_t)(flat * (size_t)n), 1.f / f2_cnn_a4_scale(cnn, S, r)));
+        if (do1.dev) F2_HIP(ctx, hipMemcpyAsync(do1.dev, a5, do1.bytes, hipMemcpyDeviceToDevice, ctx->stream));
+    }
+    F2_TRY(f2_copy_back(ctx, po));
+    F2_TRY(f2_copy_back(ctx, do1));
+    F2_TRY(f2_copy_back(ctx, so.scores));
+    return f2_host_wait(ctx, mem_space);
 }
 
 }  // extern "C"

@@ -188,6 +188,28 @@ class F2CNNModel:
         ctx.cnn_input_gradient(self.handle(ctx), x, x.shape[0], grad, None, scores, _lib.MEM_HOST)
         return grad, scores
 
+    def layers(self, x, route="call", ctx=None):
+        """(pooled, dense1, scores) of x (n, rows, channels[,1]) for tests and diagnosis (include/f2cnn_hip.h: f2_cnn_layers):
+        conv4's pooled output (n, flat) float32 in (row, column, channel) order - the row order of dense1_w -, dense1's output
+        (n, 516) after ReLU and the scores (n, 2). route: "call" (what predict does) or a forced one - "f32", "tile", "ws",
+        "ws_dense" -, which raises _lib.F2Error with code F2_ERR_UNSUPPORTED rather than run other kernels than it names, or
+        "recorded", the float32 forward pass input_gradient takes its masks from."""
+        ctx = ctx or _lib.default_context()
+        x = np.asarray(x)
+        if x.ndim == 4 and x.shape[-1] == 1:
+            x = x[..., 0]
+        if x.ndim != 3 or x.shape[1:] != (self.rows, self.channels):
+            raise ValueError(f"expected input of shape (n,{self.rows},{self.channels}[,1]), got {x.shape}")
+        if route not in _lib.CNN_ROUTES:
+            raise ValueError(f"route must be one of {sorted(_lib.CNN_ROUTES)}, got {route!r}")
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        n = x.shape[0]
+        pooled = np.empty((n, flatten_size(self.rows, self.channels)[2]), np.float32)
+        dense1 = np.empty((n, 516), np.float32)
+        scores = np.empty((n, 2), np.float32)
+        ctx.cnn_layers(self.handle(ctx), x, n, _lib.CNN_ROUTES[route], pooled, dense1, scores, _lib.MEM_HOST)
+        return pooled, dense1, scores
+
     def evaluate(self, x, y, groups=None, n_groups=1, normalize=False, ctx=None):
         """(loss, accuracy) of the model on the windows x (n, rows, channels[,1]) with the signs y (n, 0 / 1): keras
         model.evaluate's pair (reference Training.py:136) - the mean of -ln(clip(score of the true class, 1e-7, 1)) and

@@ -68,7 +68,7 @@ int f2_version(void);   /* 100 * major + minor; 101 added f2_eval_batch, 102 f2_
                            f2_cnn_get_info keys "f16x3_ok", "f16x3_check_diff", "last_input_bound"), 107 f2_input_batch,
                            108 f2_eval_batch_strided, 109 f2_eval_noise_sweep, 110 f2_label_accuracy, 111 f2_cnn_score_windows,
                            112 f2_envelope_picture + f2_gammatonegram_batch, 113 f2_resample_batch,
-                           114 f2_score_track + f2_eval_figure_batch */
+                           114 f2_score_track + f2_eval_figure_batch, 115 f2_cnn_layers */
 int f2_device_count(int* count);
 int f2_ctx_create(int device, f2_ctx** ctx);
 int f2_ctx_destroy(f2_ctx* ctx);
@@ -249,6 +249,32 @@ int f2_cnn_destroy(f2_ctx* ctx, f2_cnn* cnn);
 int f2_cnn_get_info(f2_ctx* ctx, const f2_cnn* cnn, const char* key, double* value);
 int f2_cnn_forward(f2_ctx* ctx, const f2_cnn* cnn, const float* x, int64_t n, float* scores,
                    uint8_t* labels, int mem_space);
+
+/* An inspection entry, for tests and diagnosis (no reference counterpart; nothing in the product calls it): the activations behind the
+ * two scores of f2_cnn_forward, on a route the caller names. x (n, R, C) float32 in mem_space. Every output is optional (NULL), all
+ * in mem_space:
+ *   pooled (n, flat) float32   conv4 + ReLU + max-pool in true units, flattened in the order (pooled row, pooled column, channel) -
+ *                              the row order of dense1's kernel. The split routes keep it multiplied by a power of two between
+ *                              the kernels; that is undone here, exactly
+ *   dense1 (n, 516) float32    dense1 + ReLU as the dense kernels of the route wrote it
+ *   scores (n, 2) float32      the softmax
+ * route = F2_CNN_ROUTE_CALL: the kernels and scales f2_cnn_forward takes for this x on this context (its options, its range pass);
+ * the scores are f2_cnn_forward's bit for bit. The forced routes ignore the context's options: F32 the float32 kernels, TILE the
+ * per-tile split-fp16 kernels (float32 conv3 / conv4 for windows whose conv2 output does not pool to four rows), WS the
+ * weight-stationary convolutions with the per-tile dense1, WS_DENSE those with k_dense1_ws. A forced split route runs with the scale
+ * set f2_cnn_forward would take for the measured input bound. RECORDED is the float32 forward pass that f2_cnn_input_gradient
+ * records its masks from (its own convolution kernels, in chunks of at most 1024 windows), with that call's scores.
+ * F2_ERR_UNSUPPORTED, with nothing written: a forced route this network or this input cannot take - f2_cnn_get_info's "f16x3_ok" /
+ * "ws_ok" / "ws_dense_ok" is 0 for it, x holds inf / NaN or has no scale set (the cases in which f2_cnn_forward takes the float32
+ * kernels) on a split route -, so that a forced route never runs other kernels than the ones it names; and n > 16384 (the entry does
+ * not chunk). F2_ERR_INVALID, with nothing written: f2_cnn_forward's argument errors, and a route outside the enumerators. n == 0:
+ * F2_OK. The call leaves "last_input_bound" alone. F2_MEM_HOST calls return with the outputs filled; F2_MEM_DEVICE calls wait for the
+ * stream once where the input is measured, and enqueue the rest. */
+enum { F2_CNN_ROUTE_CALL = 0, F2_CNN_ROUTE_F32 = 1, F2_CNN_ROUTE_TILE = 2, F2_CNN_ROUTE_WS = 3, F2_CNN_ROUTE_WS_DENSE = 4,
+       F2_CNN_ROUTE_RECORDED = 5 };
+int f2_cnn_layers(f2_ctx* ctx, const f2_cnn* cnn, const float* x /* (n, R, C), mem_space */, int64_t n, int route,
+                  float* pooled_or_null /* (n, flat), mem_space */, float* dense1_or_null /* (n, 516), mem_space */,
+                  float* scores_or_null /* (n, 2), mem_space */, int mem_space);
 
 /* ---- `cnn eval` device pipeline -----------------------------------------------------------------
  * scripts/CNN/Evaluating.py:42-87 for one utterance with every intermediate kept in HBM:

@@ -165,6 +165,6 @@ def test_abi_declares_the_figure_calls():
         assert len(m.group(1).split(",")) == nargs == len(_lib.SIGNATURES[name][1]), name
     lib = ctypes.CDLL(build.build_library())
     lib.f2_version.restype = ctypes.c_int
-    assert lib.f2_version() == 114
+    assert lib.f2_version() == 115      # (114 came with these two calls; 115 added f2_cnn_layers)
     assert hasattr(lib, "f2_score_track") and hasattr(lib, "f2_eval_figure_batch")
     assert callable(_lib.Context.score_track) and callable(_lib.Context.eval_figure_batch)

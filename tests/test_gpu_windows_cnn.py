@@ -94,7 +94,7 @@ def test_eval_windows_match_the_reference_predict_argument(golden_eval, tag, lpf
     np.testing.assert_allclose(out.reshape(nb, -1).astype(np.float64).sum(axis=1), sums, rtol=1e-6)
 
 
-@pytest.mark.parametrize("rows,channels,n", [(11, 128, 257), (11, 64, 40), (13, 40, 33), (10, 100, 19), (11, 190, 9)])
+@pytest.mark.parametrize("rows,channels,n", [(11, 128, 257), (11, 64, 40), (13, 40, 33), (10, 100, 19), (11, 190, 9), (18, 20, 33), (14, 24, 19)])
 def test_cnn_forward_vs_oracle(rows, channels, n):
     m = F2CNNModel.glorot(7, rows, channels, zero_bias=False)
     x = np.random.default_rng(3).random((n, rows, channels)).astype(np.float32)

@@ -102,4 +102,4 @@ def test_abi_declares_the_saliency_calls():
         assert hasattr(lib, name), name
     assert callable(_lib.Context.cnn_input_gradient) and callable(_lib.Context.saliency_map) and callable(_lib.Context.eval_saliency_batch)
     assert callable(F2CNNModel.input_gradient)
-    assert lib.f2_version() == 114
+    assert lib.f2_version() == 115      # (114 until f2_cnn_layers: the saliency calls came without a new number)
