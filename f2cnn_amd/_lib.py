@@ -97,7 +97,15 @@ SIGNATURES = {
                                   _i]),
     "f2_channel_mix_levels": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _vp, _i]),
     "f2_eval_smear_sweep": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _d, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i]),
+    "f2_cnn_loss_gradient": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, C.c_uint64, C.c_uint64, _vp, _vp, _vp, _i]),
+    "f2_trainer_create": (_i, [_vp, _P(_vp), _i, _i, _d, _d, _d, _d, _vp, C.c_uint64, _P(_vp)]),
+    "f2_trainer_destroy": (_i, [_vp, _vp]),
+    "f2_trainer_set_data": (_i, [_vp, _vp, _vp, _vp, _i64]),
+    "f2_trainer_steps": (_i, [_vp, _vp, _vp, _i64, _i, _vp, _vp]),
+    "f2_trainer_get": (_i, [_vp, _vp, _i, _P(_vp)]),
+    "f2_trainer_get_info": (_i, [_vp, _vp, C.c_char_p, _P(_d)]),
 }
+TRAINER_WHAT = {"weights": 0, "accumulators": 1, "gradient": 2}   # F2_TRAINER_* of f2_trainer_get
 
 _lib = None
 _lock = threading.Lock()
@@ -676,6 +684,68 @@ class Context:
         None."""
         self.check(self.lib.f2_cnn_input_gradient(self.handle, handle, _ptr(x), int(n), _ptr(grad), _ptr(profile), _ptr(scores),
                                                   mem_space))
+
+    def cnn_loss_gradient(self, handle, x, y, index, m, drop, seed, step, grads, mem_space, want_loss=True):
+        """The gradient of the summed cross-entropy of m labelled windows for the 12 weight tensors, training mode (see
+        f2_cnn_loss_gradient): x (n_all, rows, channels) float32, y (n_all) uint8, index (m) int64 or None (the first m) - numpy
+        arrays or device pointers, by mem_space. drop: the three dropout rates; seed, step: of the masks. grads: None, or 12 numpy
+        arrays / device pointers in the Keras layouts, filled. Returns (loss sum, windows decided as labelled), or None with
+        want_loss=False (a device-memory call then only enqueues)."""
+        rates = (_d * 3)(*[float(r) for r in drop])
+        ptrs = None
+        if grads is not None:
+            if len(grads) != 12:
+                raise ValueError("the network has 12 weight tensors")
+            ptrs = (_vp * 12)(*[_ptr(g) for g in grads])
+        loss, hits = _d(), _i64()
+        self.check(self.lib.f2_cnn_loss_gradient(self.handle, handle, _ptr(x), _ptr(y), _ptr(index), int(m), rates, int(seed), int(step), ptrs,
+                                                 C.byref(loss) if want_loss else None, C.byref(hits) if want_loss else None, mem_space))
+        return (loss.value, hits.value) if want_loss else None
+
+    def trainer_create(self, tensors, rows, channels, lr, rho, eps, decay, drop, seed):
+        """A training state on the device (see f2_trainer_create): 12 float32 tensors in Keras layouts, RMSprop's constants, the
+        three dropout rates and the seed of the masks. Returns a handle."""
+        arrs = [np.ascontiguousarray(t, dtype=np.float32) for t in tensors]
+        if len(arrs) != 12:
+            raise ValueError("the network has 12 weight tensors")
+        ptrs = (_vp * 12)(*[a.ctypes.data for a in arrs])
+        rates = (_d * 3)(*[float(r) for r in drop])
+        h = _vp()
+        self.check(self.lib.f2_trainer_create(self.handle, ptrs, int(rows), int(channels), float(lr), float(rho), float(eps), float(decay),
+                                              rates, int(seed), C.byref(h)))
+        return h
+
+    def trainer_destroy(self, handle):
+        self.check(self.lib.f2_trainer_destroy(self.handle, handle))
+
+    def trainer_set_data(self, handle, x, y):
+        """x (n, rows, channels) float32 normalised windows and y (n) 0 / 1 labels, copied to the device once"""
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        y = np.ascontiguousarray(y, dtype=np.uint8)
+        if x.ndim != 3 or len(y) != len(x):
+            raise ValueError("expected (n, rows, channels) windows and n labels")
+        self.check(self.lib.f2_trainer_set_data(self.handle, handle, x.ctypes.data, y.ctypes.data, len(x)))
+
+    def trainer_steps(self, handle, order, batch):
+        """ceil(len(order) / batch) RMSprop steps over the windows order[...] of the training set, enqueued back to back (see
+        f2_trainer_steps). Returns (sum of the steps' loss sums, windows decided as labelled)."""
+        order = np.ascontiguousarray(order, dtype=np.int64)
+        loss, hits = _d(), _i64()
+        self.check(self.lib.f2_trainer_steps(self.handle, handle, order.ctypes.data, len(order), int(batch), C.byref(loss), C.byref(hits)))
+        return loss.value, hits.value
+
+    def trainer_get(self, handle, what, shapes):
+        """The trainer's 'weights', 'accumulators' or last 'gradient' as 12 float32 arrays of `shapes` (Keras layouts)"""
+        out = [np.empty(shp, np.float32) for shp in shapes]
+        ptrs = (_vp * 12)(*[a.ctypes.data for a in out])
+        self.check(self.lib.f2_trainer_get(self.handle, handle, TRAINER_WHAT[what], ptrs))
+        return out
+
+    def trainer_info(self, handle, key):
+        """f2_trainer_get_info: 'iterations'"""
+        v = _d()
+        self.check(self.lib.f2_trainer_get_info(self.handle, handle, key.encode(), C.byref(v)))
+        return v.value
 
     def saliency_map(self, profile, window_offsets, Cn, spans, origin, hop, width, map_out, mem_space):
         """The profile rows (n, Cn, 2) float64 of cnn_input_gradient reduced to `width` time columns per utterance and channel (see

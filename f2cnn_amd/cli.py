@@ -11,7 +11,11 @@ package implements:
     python -m f2cnn_amd prepare features [--cutoff HZ]     (filter + envelope in one pass, not in the reference)
     (filter / envelope / features also take --skip-existing to resume and --metrics FILE for a JSON summary; a file that
      cannot be read is reported and skipped, the exit status is then 2)
-    python -m f2cnn_amd cnn train [--input/-i NPY] [--label/-l CSV]   (PyTorch-ROCm autograd; weights -> last_trained_model)
+    python -m f2cnn_amd cnn train [--input/-i NPY] [--label/-l CSV] [--engine torch|hip]
+                                                            (weights -> last_trained_model; --engine torch, the default: PyTorch-ROCm
+                                                             autograd; --engine hip: the library's own training step - weight
+                                                             gradients, dropout and RMSprop on the device, the same seed giving the
+                                                             same weights bit for bit)
     python -m f2cnn_amd cnn test [--input/-i NPY] [--label/-l CSV] [--model/-m NPZ] [--by set|region|speaker|phoneme] [--rows test|train|all]
                                                             (loss, accuracy and the 2 x 2 counts of a saved model on the labelled
                                                              windows, per value of a label column, in one device pass; writes
@@ -224,6 +228,9 @@ def build_parser():
                    help="smearsweep: comma-separated spreads of the channel interaction in ERB, e.g. 0.5,1,2,4")
     c.add_argument('--bands', action='store', type=bands_argument, dest='bands', default=argparse.SUPPRESS,
                    help="smearsweep: comma-separated numbers of vocoder bands, e.g. 32,16,8")
+    # (absent from the parsed arguments unless given: the commands parse as before without it)
+    c.add_argument('--engine', action='store', dest='engine', choices=('torch', 'hip'), default=argparse.SUPPRESS,
+                   help="train: 'torch' (PyTorch-ROCm autograd, the default) or 'hip' (the library's own training step)")
     c.add_argument('--seed', action='store', type=int, dest='seed', help="noisesweep: seed of the noise (default 0)")
     c.add_argument('--save-wavs', action='store_true', dest='save_wavs',
                    help="noisesweep: also write the noisy WAV files, as evalnoise does")
@@ -379,7 +386,7 @@ def main(argv=None):
             files = labelled_window_files(args)
             if files is None:
                 return 1
-            TrainAndPlotLoss(labelFile=files[1], inputFile=files[0])
+            TrainAndPlotLoss(labelFile=files[1], inputFile=files[0], engine=getattr(args, 'engine', 'torch'))
             return 0
         if args.cnn_command == 'test':
             from .scripts.CNN.Training import TestModel

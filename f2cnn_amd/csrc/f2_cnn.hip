@@ -1119,7 +1119,7 @@ int f2_launch_cnn_convs(f2_ctx* ctx, const f2_cnn* cnn, const f2_scale_set* S, f
 // are (64 windows x 6 of the 17 output tiles): launched per 14 240-window utterance that is 669 workgroups for 512 resident
 // ones - a second round one third full - so f2_eval_batch hands it the windows of several utterances at once.
 int f2_launch_cnn_dense(f2_ctx* ctx, const f2_cnn* cnn, const f2_scale_set* S, f2_cnn_route route, const float* a4, int64_t n, float* a5,
-                        float* d_scores, uint8_t* d_labels) {
+                        float* d_scores, uint8_t* d_labels, bool with_dense2) {
     if (n <= 0) return F2_OK;
     const Dims d = make_dims(cnn->rows, cnn->channels);
     F2_TRY(f2_prof_begin(ctx, F2_K_CNN));
@@ -1136,9 +1136,11 @@ int f2_launch_cnn_dense(f2_ctx* ctx, const f2_cnn* cnn, const f2_scale_set* S, f
         hipLaunchKernelGGL(k_dense1_mfma, grid, dim3(D1_WAVES * 64), 0, ctx->stream, a4, cnn->t(8), cnn->t(9), a5, d.flat, n);
     }
     F2_HIP(ctx, hipGetLastError());
-    hipLaunchKernelGGL(k_dense2_softmax, dim3((unsigned)((n * 8 + 255) / 256)), dim3(256), 0, ctx->stream, a5, cnn->t(10),
-                       cnn->t(11), d_scores, d_labels, n);
-    F2_HIP(ctx, hipGetLastError());
+    if (with_dense2) {
+        hipLaunchKernelGGL(k_dense2_softmax, dim3((unsigned)((n * 8 + 255) / 256)), dim3(256), 0, ctx->stream, a5, cnn->t(10),
+                           cnn->t(11), d_scores, d_labels, n);
+        F2_HIP(ctx, hipGetLastError());
+    }
     return f2_prof_end(ctx, F2_K_CNN);
 }
 

@@ -24,6 +24,8 @@
 #include <cmath>
 
 #include "f2_cnn_dims.h"
+#include "f2_cnn_train.h"
+#include "f2_cnn_unpool.h"
 
 namespace {
 
@@ -88,14 +90,6 @@ __global__ __launch_bounds__(256) void k_pool2x2(const float* __restrict__ a, fl
     o.z = fmaxf(fmaxf(v00.z, v01.z), fmaxf(v10.z, v11.z));
     o.w = fmaxf(fmaxf(v00.w, v01.w), fmaxf(v10.w, v11.w));
     *reinterpret_cast<float4*>(p + pix * CH + c4 * 4) = o;
-}
-
-// the gradient a pooled cell hands to element `me` (0 .. 3 in (row, column) order) of its block: all of it to the first maximal
-// element where that maximum is > 0 (the ReLU in front of the pool passes it), nothing otherwise
-__device__ __forceinline__ float unpool_pick(float g, float v0, float v1, float v2, float v3, int me) {
-    const float m = fmaxf(fmaxf(v0, v1), fmaxf(v2, v3));
-    const int first = v0 == m ? 0 : v1 == m ? 1 : v2 == m ? 2 : v3 == m ? 3 : 4;
-    return m > 0.f && first == me ? g : 0.f;
 }
 
 // ---- 3 x 3 convolution with padding PAD (0 'valid', 1 'same', 2 'full') as an implicit GEMM on v_mfma_f32_32x32x2_f32 ----
@@ -564,6 +558,39 @@ int64_t f2_cnn_grad_chunk(const f2_cnn* cnn) {
     return std::max<int64_t>(1, std::min<int64_t>(fit, GRAD_WS_CHUNK));
 }
 
+namespace {
+
+// Dropout of a training step (f2_cnn_train.hip): rates, mask seed and step, and the place of the chunk's first window in the batch
+struct train_masks {
+    const double* drop;
+    uint64_t seed, step;
+    int64_t b0;
+};
+
+// The recorded forward from conv1 to the second pool on the m windows at x, every activation kept in arr; with `masks` the
+// inverted dropout goes onto p1 and p2 in place, behind the pools
+int launch_recorded_convs(f2_ctx* ctx, const f2_cnn* cnn, const Dims& d, float* const* arr, const float* x, int64_t m, const train_masks* masks) {
+    unsigned g;
+    F2_TRY(f2_prof_begin(ctx, F2_K_CNN));
+    F2_TRY(grid256(ctx, m * d.H1 * d.W1 * (C1 / 4), &g));
+    hipLaunchKernelGGL(k_conv1_fwd, dim3(g), dim3(256), 0, ctx->stream, x, cnn->t(0), cnn->t(1), arr[grad_ws::A1], d.H1, d.W1, m);
+    F2_HIP(ctx, hipGetLastError());
+    F2_TRY((launch_gconv<C1, C2, 0, ST_PLAIN, EP_RELU, 4, 1>(ctx, arr[grad_ws::A1], nullptr, cnn->t(2), cnn->t(3), arr[grad_ws::A2], d.H1, d.W1, m)));
+    F2_TRY(grid256(ctx, m * d.Hp1 * d.Wp1 * (C2 / 4), &g));
+    hipLaunchKernelGGL(k_pool2x2, dim3(g), dim3(256), 0, ctx->stream, arr[grad_ws::A2], arr[grad_ws::P1], d.H2, d.W2, C2, m);
+    F2_HIP(ctx, hipGetLastError());
+    if (masks) F2_TRY(f2_train_dropout(ctx, arr[grad_ws::P1], m, d.Hp1 * d.Wp1 * C2, 0, masks->b0, masks->drop[0], masks->seed, masks->step));
+    F2_TRY((launch_gconv<C2, C3, 1, ST_PLAIN, EP_RELU, 4, 2>(ctx, arr[grad_ws::P1], nullptr, cnn->t(4), cnn->t(5), arr[grad_ws::A3], d.Hp1, d.Wp1, m)));
+    F2_TRY((launch_gconv<C3, C4, 0, ST_PLAIN, EP_RELU, 4, 2>(ctx, arr[grad_ws::A3], nullptr, cnn->t(6), cnn->t(7), arr[grad_ws::A4], d.Hp1, d.Wp1, m)));
+    F2_TRY(grid256(ctx, m * d.Hp2 * d.Wp2 * (C4 / 4), &g));
+    hipLaunchKernelGGL(k_pool2x2, dim3(g), dim3(256), 0, ctx->stream, arr[grad_ws::A4], arr[grad_ws::P2], d.H4, d.W4, C4, m);
+    F2_HIP(ctx, hipGetLastError());
+    if (masks) F2_TRY(f2_train_dropout(ctx, arr[grad_ws::P2], m, d.flat, 1, masks->b0, masks->drop[1], masks->seed, masks->step));
+    return f2_prof_end(ctx, F2_K_CNN);
+}
+
+}  // namespace
+
 int f2_launch_cnn_input_gradient(f2_ctx* ctx, const f2_cnn* cnn, const float* d_x, int64_t n, float* d_grad, double* d_profile,
                                  float* d_scores) {
     if (n <= 0) return F2_OK;
@@ -584,20 +611,7 @@ int f2_launch_cnn_input_gradient(f2_ctx* ctx, const f2_cnn* cnn, const float* d_
         const int64_t m = std::min(chunk, n - s);
         const float* x = d_x + (size_t)s * xs;
         // recorded forward
-        F2_TRY(f2_prof_begin(ctx, F2_K_CNN));
-        F2_TRY(grid256(ctx, m * d.H1 * d.W1 * (C1 / 4), &g));
-        hipLaunchKernelGGL(k_conv1_fwd, dim3(g), dim3(256), 0, ctx->stream, x, cnn->t(0), cnn->t(1), arr[grad_ws::A1], d.H1, d.W1, m);
-        F2_HIP(ctx, hipGetLastError());
-        F2_TRY((launch_gconv<C1, C2, 0, ST_PLAIN, EP_RELU, 4, 1>(ctx, arr[grad_ws::A1], nullptr, cnn->t(2), cnn->t(3), arr[grad_ws::A2], d.H1, d.W1, m)));
-        F2_TRY(grid256(ctx, m * d.Hp1 * d.Wp1 * (C2 / 4), &g));
-        hipLaunchKernelGGL(k_pool2x2, dim3(g), dim3(256), 0, ctx->stream, arr[grad_ws::A2], arr[grad_ws::P1], d.H2, d.W2, C2, m);
-        F2_HIP(ctx, hipGetLastError());
-        F2_TRY((launch_gconv<C2, C3, 1, ST_PLAIN, EP_RELU, 4, 2>(ctx, arr[grad_ws::P1], nullptr, cnn->t(4), cnn->t(5), arr[grad_ws::A3], d.Hp1, d.Wp1, m)));
-        F2_TRY((launch_gconv<C3, C4, 0, ST_PLAIN, EP_RELU, 4, 2>(ctx, arr[grad_ws::A3], nullptr, cnn->t(6), cnn->t(7), arr[grad_ws::A4], d.Hp1, d.Wp1, m)));
-        F2_TRY(grid256(ctx, m * d.Hp2 * d.Wp2 * (C4 / 4), &g));
-        hipLaunchKernelGGL(k_pool2x2, dim3(g), dim3(256), 0, ctx->stream, arr[grad_ws::A4], arr[grad_ws::P2], d.H4, d.W4, C4, m);
-        F2_HIP(ctx, hipGetLastError());
-        F2_TRY(f2_prof_end(ctx, F2_K_CNN));
+        F2_TRY(launch_recorded_convs(ctx, cnn, d, arr, x, m, nullptr));
         F2_TRY(f2_launch_cnn_dense(ctx, cnn, nullptr, f2_cnn_route(), arr[grad_ws::P2], m, arr[grad_ws::A5], arr[grad_ws::SC], nullptr));
         if (d_scores)
             F2_HIP(ctx, hipMemcpyAsync(d_scores + 2 * (size_t)s, arr[grad_ws::SC], sizeof(float) * 2 * (size_t)m, hipMemcpyDeviceToDevice, ctx->stream));
@@ -626,6 +640,115 @@ int f2_launch_cnn_input_gradient(f2_ctx* ctx, const f2_cnn* cnn, const float* d_
             hipLaunchKernelGGL(k_grad_profile, dim3(g), dim3(256), 0, ctx->stream, G, x, d_profile + 2 * (size_t)s * d.W1, d.H1, d.W1, m);
             F2_HIP(ctx, hipGetLastError());
         }
+        F2_TRY(f2_prof_end(ctx, F2_K_CNN));
+    }
+    return F2_OK;
+}
+
+// ---- a training step's gradient (f2_cnn_loss_gradient, f2_trainer_steps; the kernels it adds are f2_cnn_train.hip's) ----
+int f2_cnn_grad_blob(f2_ctx* ctx, const f2_cnn* cnn, float** blob, size_t off[4]) {
+    const float* gw = nullptr;
+    F2_TRY(grad_weights(ctx, cnn, &gw));
+    const grad_layout L = grad_weight_layout(cnn->flat);
+    for (int i = 0; i < 4; ++i) off[i] = L.off[i];
+    *blob = cnn->grad_blob;
+    return F2_OK;
+}
+
+int64_t f2_cnn_loss_gradient_host_chunk(const f2_cnn* cnn) {
+    const int64_t chunk = f2_cnn_grad_chunk(cnn);
+    return std::max<int64_t>(1, GRAD_HOST_CHUNK / chunk) * chunk;
+}
+
+namespace {
+
+// the launch's scratch besides ctx->grad_ws, for chunks of `chunk` windows (byte offsets, each on a 256-byte boundary)
+struct loss_ws {
+    enum { XG, DZ, LOSSW, YG, HIT, PARTIAL, COUNT };
+    size_t off[COUNT], total;
+};
+loss_ws loss_ws_layout(const Dims& d, int64_t chunk) {
+    const size_t bytes[loss_ws::COUNT] = {sizeof(float) * (size_t)d.H1 * d.W1 * (size_t)chunk, sizeof(float) * 2 * (size_t)chunk,
+                                          sizeof(double) * (size_t)chunk, (size_t)chunk, (size_t)chunk, f2_train_partial_bytes(d, chunk)};
+    loss_ws w;
+    w.total = 0;
+    for (int k = 0; k < loss_ws::COUNT; ++k) w.off[k] = w.total, w.total += (bytes[k] + 255) & ~size_t(255);
+    return w;
+}
+
+}  // namespace
+
+size_t f2_cnn_loss_gradient_ws_bytes(const f2_cnn* cnn, int64_t m) {
+    return loss_ws_layout(make_dims(cnn->rows, cnn->channels), std::min(std::max<int64_t>(m, 1), f2_cnn_grad_chunk(cnn))).total;
+}
+
+int f2_launch_cnn_loss_gradient(f2_ctx* ctx, const f2_cnn* cnn, const float* d_x, const uint8_t* d_y, const int64_t* d_index, int64_t n,
+                                int64_t b0, const double drop[3], uint64_t seed, uint64_t step, void* ws, double* d_acc, bool zero_acc,
+                                double* d_tally) {
+    const Dims d = make_dims(cnn->rows, cnn->channels);
+    const f2_train_layout TL = f2_train_tensor_layout(d.flat);
+    if (zero_acc) F2_HIP(ctx, hipMemsetAsync(d_acc, 0, sizeof(double) * TL.total(), ctx->stream));
+    if (n <= 0) return F2_OK;
+    const grad_ws shape = grad_ws_shape(d);
+    const float* gw = nullptr;
+    F2_TRY(grad_weights(ctx, cnn, &gw));
+    const grad_layout L = grad_weight_layout(cnn->flat);
+    const int64_t chunk = std::min(n, f2_cnn_grad_chunk(cnn));
+    float* arr[grad_ws::COUNT];
+    size_t off[grad_ws::COUNT];
+    F2_TRY(f2_reserve(ctx, ctx->grad_ws, sizeof(float) * grad_ws_offsets(shape, chunk, off)));
+    for (int k = 0; k < grad_ws::COUNT; ++k) arr[k] = (float*)ctx->grad_ws.ptr + off[k];
+    const loss_ws W = loss_ws_layout(d, chunk);
+    char* wb = (char*)ws;
+    float* xg = (float*)(wb + W.off[loss_ws::XG]);
+    float* dz = (float*)(wb + W.off[loss_ws::DZ]);
+    double* lossw = (double*)(wb + W.off[loss_ws::LOSSW]);
+    uint8_t* yg = (uint8_t*)(wb + W.off[loss_ws::YG]);
+    uint8_t* hit = (uint8_t*)(wb + W.off[loss_ws::HIT]);
+    const size_t xs = (size_t)d.H1 * d.W1;
+    const float keep[3] = {f2_train_keep_scale(drop[0]), f2_train_keep_scale(drop[1]), f2_train_keep_scale(drop[2])};
+    unsigned g;
+    for (int64_t s = 0; s < n; s += chunk) {
+        const int64_t m = std::min(chunk, n - s);
+        const float* x = d_x + (size_t)s * xs;
+        const uint8_t* y = d_y + s;
+        if (d_index) {
+            F2_TRY(f2_train_gather(ctx, d_x, d_y, d_index + s, m, xs, xg, yg));
+            x = xg, y = yg;
+        }
+        // recorded forward, training mode: the masks go onto p1, p2 and a5 in place
+        const train_masks masks = {drop, seed, step, b0 + s};
+        F2_TRY(launch_recorded_convs(ctx, cnn, d, arr, x, m, &masks));
+        F2_TRY(f2_launch_cnn_dense(ctx, cnn, nullptr, f2_cnn_route(), arr[grad_ws::P2], m, arr[grad_ws::A5], nullptr, nullptr, false));   // dense1 alone
+        F2_TRY(f2_prof_begin(ctx, F2_K_CNN));
+        F2_TRY(f2_train_dropout(ctx, arr[grad_ws::A5], m, D1, 2, b0 + s, drop[2], seed, step));
+        F2_TRY(f2_train_dense2(ctx, arr[grad_ws::A5], cnn->t(10), cnn->t(11), y, m, arr[grad_ws::SC], dz, lossw, hit));
+        F2_TRY(f2_train_tally(ctx, lossw, hit, m, d_tally));
+        // backward-data chain from the loss seed, each layer's weight gradient as soon as its two operands stand
+        f2_train_chunk T;
+        T.d = d, T.m = m, T.gk = GK;
+        T.x = x, T.a1 = arr[grad_ws::A1], T.a2 = arr[grad_ws::A2], T.p1 = arr[grad_ws::P1], T.a3 = arr[grad_ws::A3], T.a4 = arr[grad_ws::A4];
+        T.p2 = arr[grad_ws::P2], T.a5 = arr[grad_ws::A5], T.g5 = arr[grad_ws::G5], T.gp2 = arr[grad_ws::GP2], T.g3 = arr[grad_ws::G3];
+        T.gp1 = arr[grad_ws::GP1], T.g1 = arr[grad_ws::G1], T.dz = dz;
+        T.partial = wb + W.off[loss_ws::PARTIAL], T.acc = d_acc;
+        F2_TRY(f2_train_seed(ctx, arr[grad_ws::A5], dz, cnn->t(10), keep[2], arr[grad_ws::G5], GK, m));
+        F2_TRY(f2_train_wgrad_head(ctx, T));
+        const int ntiles = d.flat / 32;
+        hipLaunchKernelGGL(k_gemm_rows, dim3((unsigned)((m + GEMM_ROWS - 1) / GEMM_ROWS), (unsigned)((ntiles + GEMM_WAVES - 1) / GEMM_WAVES)),
+                           dim3(GEMM_WAVES * 64), 0, ctx->stream, arr[grad_ws::G5], gw + L.off[3], arr[grad_ws::GP2], GK, d.flat, m);
+        F2_HIP(ctx, hipGetLastError());
+        F2_TRY(f2_train_mask_scale(ctx, arr[grad_ws::GP2], arr[grad_ws::P2], keep[1], m * d.flat));
+        F2_TRY(f2_train_wgrad_conv(ctx, T, 4));
+        F2_TRY((launch_gconv<C4, C3, 2, ST_UNPOOL, EP_MASK, 4, 2>(ctx, arr[grad_ws::GP2], arr[grad_ws::A4], gw + L.off[2], arr[grad_ws::A3],
+                                                                  arr[grad_ws::G3], d.H4, d.W4, m)));
+        F2_TRY(f2_train_wgrad_conv(ctx, T, 3));
+        F2_TRY((launch_gconv<C3, C2, 1, ST_PLAIN, EP_NONE, 2, 1>(ctx, arr[grad_ws::G3], nullptr, gw + L.off[1], nullptr, arr[grad_ws::GP1], d.Hp1,
+                                                                 d.Wp1, m)));
+        F2_TRY(f2_train_mask_scale(ctx, arr[grad_ws::GP1], arr[grad_ws::P1], keep[0], m * d.Hp1 * d.Wp1 * C2));
+        F2_TRY(f2_train_wgrad_conv(ctx, T, 2));
+        F2_TRY((launch_gconv<C2, C1, 2, ST_UNPOOL, EP_MASK, 4, 1>(ctx, arr[grad_ws::GP1], arr[grad_ws::A2], gw + L.off[0], arr[grad_ws::A1],
+                                                                  arr[grad_ws::G1], d.H2, d.W2, m)));
+        F2_TRY(f2_train_wgrad_conv(ctx, T, 1));
         F2_TRY(f2_prof_end(ctx, F2_K_CNN));
     }
     return F2_OK;

@@ -1,0 +1,902 @@
+// A training step of K4 on the device: f2_cnn_loss_gradient and the f2_trainer_* entry points (include/f2cnn_hip.h).
+//
+// The recorded forward and the backward-data chain are f2_cnn_grad.hip's (f2_launch_cnn_loss_gradient there strings a step
+// together); this file holds what training adds to them:
+//   k_dropout          inverted dropout in place on p1, p2 and a5, masks from Philox4x32-10 (the formula is in the header)
+//   k_dense2_train     dense2 + softmax on the dropped a5, dz = softmax - onehot, the float64 loss term and the hit of every window
+//   k_loss_seed        g5 = [a5 > 0] / keep (dz0 W2[k][0] + dz1 W2[k][1]), padded like k_grad_dense2's
+//   k_mask_scale       the backward factor of a dropout layer: g = p > 0 ? g / keep : 0
+//   k_wgrad_conv       conv2 .. conv4: dW[tap][ci][co] = sum over windows and pixels of in[pixel + tap][ci] g[pixel][co] on
+//                      v_mfma_f32_32x32x2_f32 with the pixel as the MFMA's k; k_gconv's task (2 output rows x 32 columns of one
+//                      window, its 4 x 34 x CIN patch in LDS at a (CIN + 4) pitch) and beside it the task's 64 x COUT gradient
+//                      tile, un-pooled while it is staged for conv2 / conv4. Wave w of a workgroup takes the kernel row w % 3 and
+//                      the w / 3-th share of the output channels. The layer's bias gradient is the column sum of the same tile.
+//   k_wgrad_conv1      conv1 (Cin = 1) and its bias on the VALU, float64
+//   k_wgrad_dense1     p2^T g5 on the float64 matrix cores (exact products, float64 sums), the window as the MFMA's k
+//   k_wgrad_head       dense2's kernel and bias and dense1's bias, float64 throughout
+//   k_reduce_partials  the float64 sum of the partial sums, added to the float64 gradient
+//   k_round_f32, k_rmsprop, k_relayout
+// Summation rule. No float32 chain is longer than 1024 terms: a k_wgrad_conv workgroup takes at most WGRAD_MAX_PER = 16 tasks
+// (64 pixels each) of ONE window - the window's tasks in equal shares, a function of the window shape alone - and writes its
+// accumulators out as one partial sum, so a window's partial sums have the same bits wherever it stands and whatever else is in
+// the batch. conv1, dense1, dense2 and the dense biases are float64 sums of exact products of float32 values. Partial sums are added in float64, in an order fixed by the shapes and the window count alone (eight
+// interleaved runs over the partial index, then those eight in order), onto a float64 gradient that also carries the sum over
+// the chain's chunks of <= 1024 windows and is rounded to float32 once (k_round_f32). No floating-point atomics, no atomics at all.
+// gfx950, wave64. Everything that reaches memory is written by plain C++ stores.
+#include <algorithm>
+#include <cmath>
+
+#include "f2_cnn_train.h"
+#include "f2_cnn_unpool.h"
+#include "f2_philox.h"
+
+namespace {
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+constexpr int WGRAD_MAX_PER = 16;       // tasks of 64 pixels per partial sum, at most: 1024 terms
+constexpr int C1_PIX = 256;             // pixels of a k_wgrad_conv1 workgroup: 8 runs of 32
+constexpr int D1_SEG = 64;              // windows of a k_wgrad_dense1 partial sum (16 dependent steps of loads per wave)
+constexpr int HEAD_COLS = D1 * D2 + D2 + D1;   // dense2 kernel, dense2 bias, dense1 bias
+
+// ---- dropout: a thread per four elements (one Philox call), element e of window b uses word e & 3 of
+// Philox(counter = (e >> 2, b, layer, step & 0xffffffff), key = (seed & 0xffffffff, seed >> 32)); kept iff word >= rate 2^32 ----
+__global__ __launch_bounds__(256) void k_dropout(float* __restrict__ a, int64_t m, int per4, uint32_t layer, int64_t b0, double thresh,
+                                                 float scale, uint32_t k0, uint32_t k1, uint32_t step) {
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= m * per4) return;
+    const uint32_t q = (uint32_t)(t % per4);
+    const int64_t wv = t / per4;
+    const philox_words w = philox4x32_10(q, (uint32_t)(b0 + wv), layer, step, k0, k1);
+    float4* p = reinterpret_cast<float4*>(a) + t;
+    float4 v = *p;
+    v.x = (double)w.w0 >= thresh ? v.x * scale : 0.f;
+    v.y = (double)w.w1 >= thresh ? v.y * scale : 0.f;
+    v.z = (double)w.w2 >= thresh ? v.z * scale : 0.f;
+    v.w = (double)w.w3 >= thresh ? v.w * scale : 0.f;
+    *p = v;
+}
+
+// ---- dense2 + softmax in training mode: k_dense2_softmax's eight threads per window and summation order ----
+__global__ __launch_bounds__(256) void k_dense2_train(const float* __restrict__ a, const float* __restrict__ w, const float* __restrict__ bias,
+                                                      const uint8_t* __restrict__ y, float* __restrict__ scores, float* __restrict__ dz,
+                                                      double* __restrict__ lossw, uint8_t* __restrict__ hit, int64_t n) {
+    static_assert(D1 % 4 == 0, "rows walked in float4 pieces");
+    const int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> 3;
+    const int part = threadIdx.x & 7;
+    const int64_t row = i < n ? i : n - 1;
+    const float4* r = reinterpret_cast<const float4*>(a + row * D1);
+    const float4* w4 = reinterpret_cast<const float4*>(w);          // (k, class) pairs: two k per float4
+    float z0 = 0.f, z1 = 0.f;
+    for (int q = part; q < D1 / 4; q += 8) {
+        const float4 v = r[q];
+        const float4 wa = w4[2 * q], wb = w4[2 * q + 1];
+        z0 = fmaf(v.x, wa.x, z0);
+        z1 = fmaf(v.x, wa.y, z1);
+        z0 = fmaf(v.y, wa.z, z0);
+        z1 = fmaf(v.y, wa.w, z1);
+        z0 = fmaf(v.z, wb.x, z0);
+        z1 = fmaf(v.z, wb.y, z1);
+        z0 = fmaf(v.w, wb.z, z0);
+        z1 = fmaf(v.w, wb.w, z1);
+    }
+#pragma unroll
+    for (int d = 1; d < 8; d <<= 1) {
+        z0 += __shfl_xor(z0, d);
+        z1 += __shfl_xor(z1, d);
+    }
+    if (part != 0 || i >= n) return;
+    z0 += bias[0];
+    z1 += bias[1];
+    const float mx = fmaxf(z0, z1);
+    const float e0 = expf(z0 - mx), e1 = expf(z1 - mx);
+    const float s = e0 + e1;
+    const float s0 = e0 / s, s1 = e1 / s;
+    scores[2 * i] = s0;
+    scores[2 * i + 1] = s1;
+    const bool rising = y[i] != 0;
+    // softmax - onehot: the true class's entry is minus the other score (s - 1 would lose it where s is close to 1)
+    const float d1 = rising ? -s0 : s1;
+    dz[2 * i] = -d1;
+    dz[2 * i + 1] = d1;
+    // -ln softmax(z)[y] = ln(exp(z0 - mx) + exp(z1 - mx)) - (z_y - mx), in float64 from the float32 logits, no clipping
+    const double t0 = (double)z0 - (double)mx, t1 = (double)z1 - (double)mx;
+    lossw[i] = log(exp(t0) + exp(t1)) - (rising ? t1 : t0);
+    hit[i] = (s1 > s0) == rising ? 1 : 0;
+}
+
+// ---- tally[0] += sum of lossw (float64: 256 interleaved runs, then those in thread order), tally[1] (int64) += hits ----
+__global__ __launch_bounds__(256) void k_train_tally(const double* __restrict__ lossw, const uint8_t* __restrict__ hit, int64_t m,
+                                                     double* __restrict__ tally) {
+    __shared__ double sl[256];
+    __shared__ int sh[256];
+    double s = 0.0;
+    int h = 0;
+    for (int64_t i = threadIdx.x; i < m; i += 256) {
+        s += lossw[i];
+        h += hit[i];
+    }
+    sl[threadIdx.x] = s;
+    sh[threadIdx.x] = h;
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    double total = 0.0;
+    int64_t hits = 0;
+    for (int t = 0; t < 256; ++t) {
+        total += sl[t];
+        hits += sh[t];
+    }
+    tally[0] += total;
+    reinterpret_cast<int64_t*>(tally)[1] += hits;
+}
+
+__global__ __launch_bounds__(256) void k_loss_seed(const float* __restrict__ a5, const float* __restrict__ dz, const float* __restrict__ w2,
+                                                   float scale, float* __restrict__ g5, int gk, int64_t n) {
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= n * gk) return;
+    const int k = (int)(t % gk);
+    const int64_t wv = t / gk;
+    float g = 0.f;
+    if (k < D1 && a5[wv * D1 + k] > 0.f) g = scale * fmaf(dz[2 * wv + 1], w2[2 * k + 1], dz[2 * wv] * w2[2 * k]);
+    g5[t] = g;
+}
+
+__global__ __launch_bounds__(256) void k_mask_scale(float* __restrict__ g, const float* __restrict__ p, float scale, int64_t count) {
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= count) return;
+    g[t] = p[t] > 0.f ? g[t] * scale : 0.f;
+}
+
+__global__ __launch_bounds__(256) void k_gather_indexed(const float* __restrict__ x, const uint8_t* __restrict__ y,
+                                                        const int64_t* __restrict__ index, int64_t m, int64_t xs, float* __restrict__ xg,
+                                                        uint8_t* __restrict__ yg) {
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= m * xs) return;
+    const int64_t j = t / xs, e = t - j * xs;
+    const int64_t src = index[j];
+    xg[t] = x[src * xs + e];
+    if (e == 0) yg[j] = y[src];
+}
+
+// ---- conv2 .. conv4 weight and bias gradients ----
+// in (n, Hin, Win, CIN) the layer's input, padding PAD; the gradient at its pre-activations over (Ho, Wo) = (Hin, Win) + 2 PAD - 2:
+//   ST_PLAIN   g (n, Ho, Wo, COUT)
+//   ST_UNPOOL  g (n, Ho / 2, Wo / 2, COUT) the gradient of the pooled tensor, act (n, Ho, Wo, COUT) the pool's post-ReLU input
+// Cells of a task outside the output - the second x-tile's unused columns, the missing row of an odd row pair, rows and columns the
+// pool dropped - are zeros in the gradient tile, so their products are exact zeros.
+// Workgroup b takes the tasks (b % gpw) per .. + per - 1 of window b / gpw and writes partial[b] = {dW (9, CIN, COUT) | db (COUT)}.
+// MFMA operands: A[ci][k] = patch value of pixel 2 s + k shifted by the tap (lane = ci, conflict-free: a row of 32 floats), B[k][co] =
+// the gradient tile's pixel 2 s + k (lane = co, likewise).
+enum { ST_PLAIN = 0, ST_UNPOOL = 1 };
+template <int CIN, int COUT, int PAD, int STAGE, int COSPLIT>
+__global__ __launch_bounds__(3 * COSPLIT * 64) void k_wgrad_conv(const float* __restrict__ in, const float* __restrict__ g,
+                                                                 const float* __restrict__ act, float* __restrict__ partial, int Hin, int Win,
+                                                                 int64_t nwin, int per, int gpw) {
+    constexpr int NTHR = 3 * COSPLIT * 64;
+    constexpr int PS = CIN + 4, GS = COUT + 4;
+    constexpr int CIT = CIN / 32, COT = COUT / 32 / COSPLIT;
+    constexpr int Q4 = CIN / 4, QG = COUT / 4;
+    constexpr int BPARTS = NTHR / COUT;   // the bias sum: thread (bpart, bco) adds every BPARTS-th pixel of column bco
+    static_assert(COT >= 1 && CIN % 32 == 0 && COUT % 32 == 0 && NTHR % COUT == 0 && BPARTS * COUT <= 64 * GS, "tile shape");
+    __shared__ __attribute__((aligned(16))) float patch[4 * PW * PS];
+    __shared__ __attribute__((aligned(16))) float gt[64 * GS];
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int i = lane & 31, h = lane >> 5;
+    const int dy = wave % 3, cs = wave / 3;
+    const int bco = tid % COUT, bpart = tid / COUT;
+    const int Ho = Hin + 2 * PAD - 2, Wo = Win + 2 * PAD - 2;
+    const int row_pairs = (Ho + 1) / 2, xtiles = (Wo + 31) / 32;
+    const int tpw = row_pairs * xtiles;   // tasks per window
+    const int64_t win = blockIdx.x / gpw;
+    const int first = (int)(blockIdx.x % gpw) * per;
+    const int last = first + per < tpw ? first + per : tpw;
+    const int Hp = Ho / 2, Wp = Wo / 2;   // (ST_UNPOOL)
+    const float* img = in + win * (int64_t)Hin * Win * CIN;
+
+    f32x16 acc[3][CIT][COT];
+#pragma unroll
+    for (int dx = 0; dx < 3; ++dx)
+#pragma unroll
+        for (int a = 0; a < CIT; ++a)
+#pragma unroll
+            for (int b = 0; b < COT; ++b)
+#pragma unroll
+                for (int q = 0; q < 16; ++q) acc[dx][a][b][q] = 0.f;
+    float bsum = 0.f;
+
+    for (int task = first; task < last; ++task) {
+        const int xt = task % xtiles, rp = task / xtiles;
+        const int y0 = 2 * rp, x0 = 32 * xt;
+        for (int e = tid; e < 4 * PW * Q4; e += NTHR) {
+            const int r = e / (PW * Q4);
+            const int rem = e - r * (PW * Q4);
+            const int p = rem / Q4, c4 = rem - p * Q4;
+            const int yi = y0 - PAD + r, xi = x0 - PAD + p;
+            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (yi >= 0 && yi < Hin && xi >= 0 && xi < Win) v = *reinterpret_cast<const float4*>(img + ((int64_t)yi * Win + xi) * CIN + c4 * 4);
+            *reinterpret_cast<float4*>(patch + (r * PW + p) * PS + c4 * 4) = v;
+        }
+        for (int e = tid; e < 64 * QG; e += NTHR) {
+            const int pix = e / QG, c4 = e - pix * QG;
+            const int yo = y0 + (pix >> 5), xo = x0 + (pix & 31);
+            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (yo < Ho && xo < Wo) {
+                if constexpr (STAGE == ST_PLAIN) {
+                    v = *reinterpret_cast<const float4*>(g + ((win * Ho + yo) * (int64_t)Wo + xo) * COUT + c4 * 4);
+                } else {
+                    const int py = yo >> 1, px = xo >> 1;
+                    if (py < Hp && px < Wp) {
+                        const float4 gv = *reinterpret_cast<const float4*>(g + ((win * Hp + py) * (int64_t)Wp + px) * COUT + c4 * 4);
+                        const float* s = act + ((win * Ho + 2 * py) * (int64_t)Wo + 2 * px) * COUT + c4 * 4;
+                        const float4 v00 = *reinterpret_cast<const float4*>(s), v01 = *reinterpret_cast<const float4*>(s + COUT);
+                        const float4 v10 = *reinterpret_cast<const float4*>(s + (int64_t)Wo * COUT);
+                        const float4 v11 = *reinterpret_cast<const float4*>(s + (int64_t)Wo * COUT + COUT);
+                        const int me = (yo & 1) * 2 + (xo & 1);
+                        v.x = unpool_pick(gv.x, v00.x, v01.x, v10.x, v11.x, me);
+                        v.y = unpool_pick(gv.y, v00.y, v01.y, v10.y, v11.y, me);
+                        v.z = unpool_pick(gv.z, v00.z, v01.z, v10.z, v11.z, me);
+                        v.w = unpool_pick(gv.w, v00.w, v01.w, v10.w, v11.w, me);
+                    }
+                }
+            }
+            *reinterpret_cast<float4*>(gt + pix * GS + c4 * 4) = v;
+        }
+        __syncthreads();
+
+#pragma unroll 2
+        for (int s = 0; s < 32; ++s) {
+            const int pix = 2 * s + h;
+            const int rr = pix >> 5, col = pix & 31;
+            float bv[COT];
+#pragma unroll
+            for (int b = 0; b < COT; ++b) bv[b] = gt[pix * GS + (cs * COT + b) * 32 + i];
+            const float* pa = patch + ((rr + dy) * PW + col) * PS + i;
+#pragma unroll
+            for (int dx = 0; dx < 3; ++dx)
+#pragma unroll
+                for (int a = 0; a < CIT; ++a) {
+                    const float av = pa[dx * PS + a * 32];
+#pragma unroll
+                    for (int b = 0; b < COT; ++b) acc[dx][a][b] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv[b], acc[dx][a][b], 0, 0, 0);
+                }
+        }
+#pragma unroll 4
+        for (int pix = bpart; pix < 64; pix += BPARTS) bsum += gt[pix * GS + bco];
+        __syncthreads();
+    }
+    gt[bpart * COUT + bco] = bsum;   // (behind the loop's last barrier: nobody reads the tile any more)
+    __syncthreads();
+
+    float* P = partial + (int64_t)blockIdx.x * (9 * CIN * COUT + COUT);
+#pragma unroll
+    for (int dx = 0; dx < 3; ++dx)
+#pragma unroll
+        for (int a = 0; a < CIT; ++a)
+#pragma unroll
+            for (int b = 0; b < COT; ++b)
+#pragma unroll
+                for (int q = 0; q < 16; ++q) {
+                    const int ci = a * 32 + (q & 3) + 8 * (q >> 2) + 4 * h;
+                    const int co = (cs * COT + b) * 32 + i;
+                    P[((dy * 3 + dx) * CIN + ci) * COUT + co] = acc[dx][a][b][q];
+                }
+    if (tid < COUT) {
+        float t = gt[tid];
+        for (int part = 1; part < BPARTS; ++part) t += gt[part * COUT + tid];
+        P[9 * CIN * COUT + tid] = t;
+    }
+}
+
+// ---- conv1 ('same', Cin = 1): dW[tap][co] = sum x[y + dy - 1][x + dx - 1] g1[y][x][co], db[co] = sum g1 ----
+// Workgroup b takes the pixels C1_PIX b .. of the chunk (all windows end to end): thread (run, co) adds every eighth of them in
+// float64 (the products of two float32 values are exact there), the eight runs are added in run order
+// -> partial[b] = {dW (9, 32) | db (32)} float64
+__global__ __launch_bounds__(256) void k_wgrad_conv1(const float* __restrict__ x, const float* __restrict__ g1, double* __restrict__ partial, int H,
+                                                     int W, int64_t nwin) {
+    __shared__ double sm[8][10][C1];
+    const int co = threadIdx.x & 31, run = threadIdx.x >> 5;
+    const int64_t npix = nwin * H * W;
+    const int64_t base = (int64_t)blockIdx.x * C1_PIX;
+    double acc[10];
+#pragma unroll
+    for (int t = 0; t < 10; ++t) acc[t] = 0.0;
+    const int HW = H * W;
+    int64_t win = (base + run) / HW;
+    int rem = (int)(base + run - win * HW);   // the pixel's place in its window; eight further on every turn
+    for (int j = 0; j < C1_PIX / 8; ++j, rem += 8) {
+        const int64_t pix = base + run + 8 * j;
+        if (pix >= npix) break;
+        while (rem >= HW) rem -= HW, ++win;
+        const int y = rem / W, xo = rem - y * W;
+        const float* img = x + win * (int64_t)HW;
+        const double gv = (double)g1[pix * C1 + co];
+#pragma unroll
+        for (int tap = 0; tap < 9; ++tap) {
+            const int yi = y - 1 + tap / 3, xi = xo - 1 + tap % 3;
+            const float v = (yi >= 0 && yi < H && xi >= 0 && xi < W) ? img[(int64_t)yi * W + xi] : 0.f;
+            acc[tap] = fma((double)v, gv, acc[tap]);
+        }
+        acc[9] += gv;
+    }
+#pragma unroll
+    for (int t = 0; t < 10; ++t) sm[run][t][co] = acc[t];
+    __syncthreads();
+    for (int e = threadIdx.x; e < 10 * C1; e += 256) {
+        double s = 0.0;
+        for (int r = 0; r < 8; ++r) s += sm[r][e / C1][e % C1];
+        partial[(int64_t)blockIdx.x * (10 * C1) + e] = s;
+    }
+}
+
+// ---- dense1: dW[j][k] = sum over windows of p2[w][j] g5[w][k] ----
+// On v_mfma_f64_16x16x4_f64 with the window as the MFMA's k: the product of two float32 values is exact in float64 and the sums
+// are float64, so the gradient of a batch is the float64 sum of its windows' products, rounded once (a float32 chain over the
+// windows of a batch is not: its roundings are as large as those of the terms themselves). A wave owns 64 rows j x 32 columns k of
+// segment blockIdx.y (D1_SEG windows): 4 x 2 tiles of 16 x 16, operands straight from memory (lane & 15 = j resp. k, lane >> 4 =
+// the window of the step's four). partial[seg] = dW (flat, 516) of that segment's windows, float64.
+// C/D of this instruction: column = lane & 15, row = (lane >> 4) + 4 v for register v.
+typedef double f64x4 __attribute__((ext_vector_type(4)));
+__global__ __launch_bounds__(256) void k_wgrad_dense1(const float* __restrict__ p2, const float* __restrict__ g5, double* __restrict__ partial, int flat,
+                                                      int gk, int64_t m) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int r = lane & 15, kq = lane >> 4;
+    const int tile = blockIdx.x * 4 + wave;
+    const int jt = tile / D1_TILES, kt = tile - jt * D1_TILES;
+    if (jt >= flat / 64) return;   // (the whole wave; no barrier in this kernel)
+    const int64_t w0 = (int64_t)blockIdx.y * D1_SEG;
+    const int64_t w1 = w0 + D1_SEG < m ? w0 + D1_SEG : m;
+    f64x4 acc[4][2];
+#pragma unroll
+    for (int a = 0; a < 4; ++a)
+#pragma unroll
+        for (int b = 0; b < 2; ++b)
+#pragma unroll
+            for (int v = 0; v < 4; ++v) acc[a][b][v] = 0.0;
+    const float* pa = p2 + jt * 64 + r;
+    const float* pb = g5 + kt * 32 + r;
+    const int steps = (int)((w1 - w0 + 3) / 4);
+    for (int s = 0; s < steps; ++s) {
+        const int64_t w = w0 + 4 * s + kq;
+        const bool has = w < w1;
+        double av[4], bv[2];
+#pragma unroll
+        for (int a = 0; a < 4; ++a) av[a] = has ? (double)pa[w * flat + a * 16] : 0.0;
+#pragma unroll
+        for (int b = 0; b < 2; ++b) bv[b] = has ? (double)pb[w * gk + b * 16] : 0.0;
+#pragma unroll
+        for (int a = 0; a < 4; ++a)
+#pragma unroll
+            for (int b = 0; b < 2; ++b) acc[a][b] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[a], bv[b], acc[a][b], 0, 0, 0);
+    }
+    double* P = partial + (int64_t)blockIdx.y * flat * D1;
+#pragma unroll
+    for (int a = 0; a < 4; ++a)
+#pragma unroll
+        for (int b = 0; b < 2; ++b) {
+            const int k = kt * 32 + b * 16 + r;
+            if (k >= D1) continue;
+#pragma unroll
+            for (int v = 0; v < 4; ++v) {
+                const int j = jt * 64 + a * 16 + kq + 4 * v;
+                P[(int64_t)j * D1 + k] = acc[a][b][v];
+            }
+        }
+}
+
+// ---- dense2's kernel a5^T dz (516, 2), its bias sum dz (2) and dense1's bias sum g5 (516): float64 products and sums ----
+// thread (run, column): every eighth window in ascending order, the eight runs added in run order
+__global__ __launch_bounds__(256) void k_wgrad_head(const float* __restrict__ a5, const float* __restrict__ dz, const float* __restrict__ g5, int gk,
+                                                    int64_t m, double* __restrict__ d2w, double* __restrict__ d2b, double* __restrict__ d1b) {
+    __shared__ double sm[8][32];
+    const int cx = threadIdx.x & 31, run = threadIdx.x >> 5;
+    const int c = blockIdx.x * 32 + cx;
+    double s = 0.0;
+    if (c < HEAD_COLS) {
+        for (int64_t w = run; w < m; w += 8) {
+            double v;
+            if (c < D1 * D2) v = (double)a5[w * D1 + c / D2] * (double)dz[w * D2 + c % D2];
+            else if (c < D1 * D2 + D2) v = (double)dz[w * D2 + (c - D1 * D2)];
+            else v = (double)g5[w * gk + (c - D1 * D2 - D2)];
+            s += v;
+        }
+    }
+    sm[run][cx] = s;
+    __syncthreads();
+    if (run != 0 || c >= HEAD_COLS) return;
+    double t = sm[0][cx];
+    for (int r = 1; r < 8; ++r) t += sm[r][cx];
+    if (c < D1 * D2) d2w[c] += t;
+    else if (c < D1 * D2 + D2) d2b[c - D1 * D2] += t;
+    else d1b[c - D1 * D2 - D2] += t;
+}
+
+// ---- acc[e] += sum over the np partial sums of partial[p][e], in float64: thread (run, e) adds every eighth partial in ascending
+// order, the eight runs are added in run order ----
+template <class T>
+__global__ __launch_bounds__(256) void k_reduce_partials(const T* __restrict__ partial, int64_t np, int64_t stride, int64_t count,
+                                                         double* __restrict__ acc) {
+    __shared__ double sm[8][32];
+    const int ex = threadIdx.x & 31, run = threadIdx.x >> 5;
+    const int64_t e = (int64_t)blockIdx.x * 32 + ex;
+    double s = 0.0;
+    if (e < count) {
+#pragma unroll 4
+        for (int64_t p = run; p < np; p += 8) s += (double)partial[p * stride + e];
+    }
+    sm[run][ex] = s;
+    __syncthreads();
+    if (run != 0 || e >= count) return;
+    double t = sm[0][ex];
+    for (int r = 1; r < 8; ++r) t += sm[r][ex];
+    acc[e] += t;
+}
+
+__global__ __launch_bounds__(256) void k_round_f32(const double* __restrict__ acc, float* __restrict__ out, int64_t count) {
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t < count) out[t] = (float)acc[t];
+}
+
+__global__ __launch_bounds__(256) void k_rmsprop(float* __restrict__ p, float* __restrict__ a, const float* __restrict__ g, int64_t count, float m,
+                                                 float lr_t, float rho, float one_minus_rho, float eps) {
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= count) return;
+    const float gm = g[t] / m;
+    const float an = fmaf(rho, a[t], one_minus_rho * (gm * gm));
+    a[t] = an;
+    p[t] = p[t] - lr_t * gm / (sqrtf(an) + eps);
+}
+
+// f2_cnn_create's MFMA B operand of a K x N matrix (f2_cnn.hip: relayout_f32; f2_cnn_grad.hip: relaid_index):
+// [block][h][s/4][n (npad)][s%4], k = block blk + h blk/2 + s
+__device__ __forceinline__ size_t relaid_at(size_t k, int n, int blk, int npad) {
+    const int half = blk / 2;
+    const size_t b = k / blk, hh = k % blk / half, s = k % half;
+    return (((b * 2 + hh) * (half / 4) + s / 4) * npad + n) * 4 + s % 4;
+}
+
+struct relayout_args {
+    size_t src[13];    // f2_train_tensor_layout
+    size_t dst[12];    // cnn->off
+    size_t gdst[4];    // conv2T, conv3T, conv4T, dense1T in grad_blob
+    int flat;
+};
+// a thread per master weight: its place in cnn->blob (conv2 .. conv4 and dense1 as the MFMA B operand, the rest as they are) and,
+// for those four, in grad_blob (the kernel turned by 180 degrees with Cin and Cout swapped; dense1 transposed)
+__global__ __launch_bounds__(256) void k_relayout(const float* __restrict__ w, float* __restrict__ blob, float* __restrict__ gblob, relayout_args A) {
+    const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= A.src[12]) return;
+    int l = 0;
+    size_t first = 0, dst = A.dst[0];
+#pragma unroll
+    for (int k = 1; k < 12; ++k)
+        if (t >= A.src[k]) l = k, first = A.src[k], dst = A.dst[k];
+    const size_t e = t - first;
+    const float v = w[t];
+    if (l == 2 || l == 4 || l == 6) {
+        const int cin = l == 6 ? C3 : l == 4 ? C2 : C1, cout = l == 2 ? C2 : l == 4 ? C3 : C4;
+        const int co = (int)(e % cout);
+        const size_t k = e / cout;             // tap cin + ci
+        const int ci = (int)(k % cin), tap = (int)(k / cin);
+        blob[dst + relaid_at(k, co, cin, cout)] = v;
+        gblob[(l == 2 ? A.gdst[0] : l == 4 ? A.gdst[1] : A.gdst[2]) + relaid_at((size_t)(8 - tap) * cout + co, ci, cout, cin)] = v;
+    } else if (l == 8) {
+        const int k = (int)(e % D1);
+        const size_t j = e / D1;
+        blob[dst + relaid_at(j, k, D1_KC, D1_NPAD)] = v;
+        gblob[A.gdst[3] + relaid_at((size_t)k, (int)j, 64, A.flat)] = v;
+    } else {
+        blob[dst + e] = v;
+    }
+}
+
+int grid256(f2_ctx* ctx, int64_t threads, unsigned* grid) { return cnn_grid(ctx, (threads + 255) / 256, grid); }
+
+// a window's tasks of 64 pixels in gpw equal shares of per <= WGRAD_MAX_PER: a function of the window shape alone
+struct wgrad_share {
+    int per, gpw;
+};
+wgrad_share wgrad_shares(int Ho, int Wo) {
+    const int tpw = ((Ho + 1) / 2) * ((Wo + 31) / 32);
+    wgrad_share s;
+    s.gpw = std::max(1, (tpw + WGRAD_MAX_PER - 1) / WGRAD_MAX_PER);
+    s.per = (tpw + s.gpw - 1) / s.gpw;
+    return s;
+}
+
+template <class T>
+int reduce_partials(f2_ctx* ctx, const T* partial, int64_t np, int64_t stride, int64_t count, double* acc) {
+    unsigned g;
+    F2_TRY(cnn_grid(ctx, (count + 31) / 32, &g));
+    hipLaunchKernelGGL(k_reduce_partials<T>, dim3(g), dim3(256), 0, ctx->stream, partial, np, stride, count, acc);
+    F2_HIP(ctx, hipGetLastError());
+    return F2_OK;
+}
+
+template <int CIN, int COUT, int PAD, int STAGE, int COSPLIT>
+int launch_wgrad_conv(f2_ctx* ctx, const float* in, const float* g, const float* act, float* partial, int Hin, int Win, int64_t m, double* acc) {
+    const wgrad_share sh = wgrad_shares(Hin + 2 * PAD - 2, Win + 2 * PAD - 2);
+    const int64_t groups = m * sh.gpw;
+    if (groups <= 0) return F2_OK;
+    unsigned grid;
+    F2_TRY(cnn_grid(ctx, groups, &grid));
+    hipLaunchKernelGGL((k_wgrad_conv<CIN, COUT, PAD, STAGE, COSPLIT>), dim3(grid), dim3(3 * COSPLIT * 64), 0, ctx->stream, in, g, act, partial,
+                       Hin, Win, m, sh.per, sh.gpw);
+    F2_HIP(ctx, hipGetLastError());
+    constexpr int64_t count = 9 * CIN * COUT + COUT;   // (kernel and bias stand one after the other in the gradient too)
+    return reduce_partials(ctx, partial, groups, count, count, acc);
+}
+
+}  // namespace
+
+f2_train_layout f2_train_tensor_layout(int flat) {
+    const size_t sizes[12] = {9 * C1, C1, 9 * (size_t)C1 * C2, C2, 9 * (size_t)C2 * C3, C3, 9 * (size_t)C3 * C4, C4,
+                              (size_t)flat * D1, D1, (size_t)D1 * D2, D2};
+    f2_train_layout L;
+    L.off[0] = 0;
+    for (int i = 0; i < 12; ++i) L.off[i + 1] = L.off[i] + sizes[i];
+    return L;
+}
+
+float f2_train_keep_scale(double rate) { return (float)(1.0 / (1.0 - rate)); }
+
+int f2_train_dropout(f2_ctx* ctx, float* a, int64_t m, int per, int layer, int64_t b0, double rate, uint64_t seed, uint64_t step) {
+    if (rate <= 0.0 || m <= 0) return F2_OK;
+    F2_CHECK(ctx, per % 4 == 0, F2_ERR_UNSUPPORTED, "dropout over %d values per window", per);
+    unsigned g;
+    F2_TRY(grid256(ctx, m * (per / 4), &g));
+    hipLaunchKernelGGL(k_dropout, dim3(g), dim3(256), 0, ctx->stream, a, m, per / 4, (uint32_t)layer, b0, rate * 4294967296.0,
+                       f2_train_keep_scale(rate), (uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)step);
+    F2_HIP(ctx, hipGetLastError());
+    return F2_OK;
+}
+
+int f2_train_dense2(f2_ctx* ctx, const float* a5, const float* w2, const float* b2, const uint8_t* y, int64_t m, float* scores, float* dz,
+                    double* lossw, uint8_t* hit) {
+    unsigned g;
+    F2_TRY(grid256(ctx, m * 8, &g));
+    hipLaunchKernelGGL(k_dense2_train, dim3(g), dim3(256), 0, ctx->stream, a5, w2, b2, y, scores, dz, lossw, hit, m);
+    F2_HIP(ctx, hipGetLastError());
+    return F2_OK;
+}
+
+int f2_train_tally(f2_ctx* ctx, const double* lossw, const uint8_t* hit, int64_t m, double* tally) {
+    hipLaunchKernelGGL(k_train_tally, dim3(1), dim3(256), 0, ctx->stream, lossw, hit, m, tally);
+    F2_HIP(ctx, hipGetLastError());
+    return F2_OK;
+}
+
+int f2_train_seed(f2_ctx* ctx, const float* a5, const float* dz, const float* w2, float scale, float* g5, int gk, int64_t m) {
+    unsigned g;
+    F2_TRY(grid256(ctx, m * gk, &g));
+    hipLaunchKernelGGL(k_loss_seed, dim3(g), dim3(256), 0, ctx->stream, a5, dz, w2, scale, g5, gk, m);
+    F2_HIP(ctx, hipGetLastError());
+    return F2_OK;
+}
+
+int f2_train_mask_scale(f2_ctx* ctx, float* gv, const float* p, float scale, int64_t count) {
+    unsigned g;
+    F2_TRY(grid256(ctx, count, &g));
+    hipLaunchKernelGGL(k_mask_scale, dim3(g), dim3(256), 0, ctx->stream, gv, p, scale, count);
+    F2_HIP(ctx, hipGetLastError());
+    return F2_OK;
+}
+
+int f2_train_gather(f2_ctx* ctx, const float* x, const uint8_t* y, const int64_t* index, int64_t m, size_t xs, float* xg, uint8_t* yg) {
+    unsigned g;
+    F2_TRY(grid256(ctx, m * (int64_t)xs, &g));
+    hipLaunchKernelGGL(k_gather_indexed, dim3(g), dim3(256), 0, ctx->stream, x, y, index, m, (int64_t)xs, xg, yg);
+    F2_HIP(ctx, hipGetLastError());
+    return F2_OK;
+}
+
+size_t f2_train_partial_bytes(const Dims& d, int64_t m) {
+    auto conv = [&](int Ho, int Wo, int cin, int cout) {
+        return sizeof(float) * (size_t)(m * wgrad_shares(Ho, Wo).gpw) * (9 * (size_t)cin * cout + cout);
+    };
+    size_t need = conv(d.H2, d.W2, C1, C2);
+    need = std::max(need, conv(d.Hp1, d.Wp1, C2, C3));
+    need = std::max(need, conv(d.H4, d.W4, C3, C4));
+    need = std::max(need, sizeof(double) * (size_t)((m * d.H1 * d.W1 + C1_PIX - 1) / C1_PIX) * 10 * C1);
+    need = std::max(need, sizeof(double) * (size_t)((m + D1_SEG - 1) / D1_SEG) * d.flat * D1);
+    return need;
+}
+
+int f2_train_wgrad_head(f2_ctx* ctx, const f2_train_chunk& T) {
+    const f2_train_layout L = f2_train_tensor_layout(T.d.flat);
+    hipLaunchKernelGGL(k_wgrad_head, dim3((HEAD_COLS + 31) / 32), dim3(256), 0, ctx->stream, T.a5, T.dz, T.g5, T.gk, T.m, T.acc + L.off[10],
+                       T.acc + L.off[11], T.acc + L.off[9]);
+    F2_HIP(ctx, hipGetLastError());
+    const int tiles = (T.d.flat / 64) * D1_TILES;
+    const int64_t segs = (T.m + D1_SEG - 1) / D1_SEG;
+    hipLaunchKernelGGL(k_wgrad_dense1, dim3((unsigned)((tiles + 3) / 4), (unsigned)segs), dim3(256), 0, ctx->stream, T.p2, T.g5,
+                       (double*)T.partial, T.d.flat, T.gk, T.m);
+    F2_HIP(ctx, hipGetLastError());
+    const int64_t count = (int64_t)T.d.flat * D1;
+    return reduce_partials(ctx, (const double*)T.partial, segs, count, count, T.acc + L.off[8]);
+}
+
+int f2_train_wgrad_conv(f2_ctx* ctx, const f2_train_chunk& T, int layer) {
+    const f2_train_layout L = f2_train_tensor_layout(T.d.flat);
+    const Dims& d = T.d;
+    float* part = (float*)T.partial;
+    switch (layer) {
+    case 4: return launch_wgrad_conv<C3, C4, 0, ST_UNPOOL, 2>(ctx, T.a3, T.gp2, T.a4, part, d.Hp1, d.Wp1, T.m, T.acc + L.off[6]);
+    case 3: return launch_wgrad_conv<C2, C3, 1, ST_PLAIN, 1>(ctx, T.p1, T.g3, nullptr, part, d.Hp1, d.Wp1, T.m, T.acc + L.off[4]);
+    case 2: return launch_wgrad_conv<C1, C2, 0, ST_UNPOOL, 1>(ctx, T.a1, T.gp1, T.a2, part, d.H1, d.W1, T.m, T.acc + L.off[2]);
+    default: break;
+    }
+    const int64_t groups = (T.m * d.H1 * d.W1 + C1_PIX - 1) / C1_PIX;
+    unsigned g;
+    F2_TRY(cnn_grid(ctx, groups, &g));
+    hipLaunchKernelGGL(k_wgrad_conv1, dim3(g), dim3(256), 0, ctx->stream, T.x, T.g1, (double*)T.partial, d.H1, d.W1, T.m);
+    F2_HIP(ctx, hipGetLastError());
+    return reduce_partials(ctx, (const double*)T.partial, groups, (int64_t)10 * C1, (int64_t)10 * C1, T.acc + L.off[0]);
+}
+
+int f2_train_round(f2_ctx* ctx, const double* acc, float* out, size_t count) {
+    unsigned g;
+    F2_TRY(grid256(ctx, (int64_t)count, &g));
+    hipLaunchKernelGGL(k_round_f32, dim3(g), dim3(256), 0, ctx->stream, acc, out, (int64_t)count);
+    F2_HIP(ctx, hipGetLastError());
+    return F2_OK;
+}
+
+int f2_train_rmsprop(f2_ctx* ctx, float* p, float* a, const float* gr, size_t count, int64_t m, float lr_t, float rho, float one_minus_rho,
+                     float eps) {
+    unsigned g;
+    F2_TRY(grid256(ctx, (int64_t)count, &g));
+    hipLaunchKernelGGL(k_rmsprop, dim3(g), dim3(256), 0, ctx->stream, p, a, gr, (int64_t)count, (float)m, lr_t, rho, one_minus_rho, eps);
+    F2_HIP(ctx, hipGetLastError());
+    return F2_OK;
+}
+
+int f2_train_relayout(f2_ctx* ctx, const float* w, const f2_cnn* cnn, float* grad_blob, const size_t grad_off[4]) {
+    relayout_args A;
+    const f2_train_layout L = f2_train_tensor_layout(cnn->flat);
+    for (int i = 0; i < 13; ++i) A.src[i] = L.off[i];
+    for (int i = 0; i < 12; ++i) A.dst[i] = cnn->off[i];
+    for (int i = 0; i < 4; ++i) A.gdst[i] = grad_off[i];
+    A.flat = cnn->flat;
+    unsigned g;
+    F2_TRY(grid256(ctx, (int64_t)L.total(), &g));
+    hipLaunchKernelGGL(k_relayout, dim3(g), dim3(256), 0, ctx->stream, w, cnn->blob, grad_blob, A);
+    F2_HIP(ctx, hipGetLastError());
+    return F2_OK;
+}
+
+// ---- entry points ----
+struct f2_trainer {
+    f2_cnn* cnn = nullptr;   // private: the float32 recorded route reads its blob and grad_blob, nothing reads its split-fp16 tables
+    int rows = 0, channels = 0, dev = 0;
+    f2_train_layout L;
+    f2_scratch w, a, g, acc;   // master weights, RMSprop accumulators, the last step's gradient (float32); float64 gradient + tally
+    f2_scratch x, y, order;    // the training windows, their labels, the order of the steps call in flight
+    int64_t n = 0;
+    float* grad_blob = nullptr;
+    size_t grad_off[4] = {0, 0, 0, 0};
+    double lr = 0, rho = 0, eps = 0, decay = 0, drop[3] = {0, 0, 0};
+    uint64_t seed = 0;
+    int64_t iterations = 0;
+};
+
+namespace {
+
+int check_drop(f2_ctx* ctx, const double* drop) {
+    F2_CHECK(ctx, drop, F2_ERR_INVALID, "drop is NULL");
+    for (int l = 0; l < 3; ++l) F2_CHECK(ctx, drop[l] >= 0.0 && drop[l] < 1.0, F2_ERR_INVALID, "dropout rate %d is %g, not in [0, 1)", l, drop[l]);
+    return F2_OK;
+}
+
+size_t align256(size_t b) { return (b + 255) & ~size_t(255); }
+
+}  // namespace
+
+extern "C" {
+
+int f2_cnn_loss_gradient(f2_ctx* ctx, const f2_cnn* cnn, const float* x, const uint8_t* y, const int64_t* index_or_null, int64_t m,
+                         const double* drop, uint64_t seed, uint64_t step, float* const* grads_or_null, double* loss_sum_or_null,
+                         int64_t* correct_or_null, int mem_space) {
+    F2_TRY(f2_check_ctx(ctx));
+    F2_TRY(f2_check_cnn(ctx, cnn, 0, 0));
+    F2_TRY(f2_check_mem_space(ctx, mem_space, false));
+    F2_CHECK(ctx, m >= 0, F2_ERR_INVALID, "negative window count");
+    F2_TRY(check_drop(ctx, drop));
+    F2_CHECK(ctx, m == 0 || (x && y), F2_ERR_INVALID, "x or y is NULL");
+    const bool host = mem_space != F2_MEM_DEVICE;
+    if (host && index_or_null)
+        for (int64_t j = 0; j < m; ++j) F2_CHECK(ctx, index_or_null[j] >= 0, F2_ERR_INVALID, "index[%lld] is negative", (long long)j);
+    if (grads_or_null)
+        for (int i = 0; i < 12; ++i) F2_CHECK(ctx, grads_or_null[i], F2_ERR_INVALID, "gradient tensor %d is NULL", i);
+    const f2_train_layout L = f2_train_tensor_layout(cnn->flat);
+    const size_t T = L.total(), xs = (size_t)cnn->rows * cnn->channels;
+    const int64_t piece = host ? f2_cnn_loss_gradient_host_chunk(cnn) : std::max<int64_t>(m, 1);
+    // scratch of the call: [the launch's | float64 gradient | {loss sum, hits} | float32 gradient]
+    const size_t ws_bytes = align256(f2_cnn_loss_gradient_ws_bytes(cnn, std::min<int64_t>(std::max<int64_t>(m, 1), piece)));
+    const size_t at_tally = ws_bytes + align256(sizeof(double) * T), at_g32 = at_tally + 256;
+    F2_TRY(f2_reserve(ctx, ctx->train_ws, at_g32 + sizeof(float) * T));
+    char* base = (char*)ctx->train_ws.ptr;
+    double* d_acc = (double*)(base + ws_bytes);
+    double* d_tally = (double*)(base + at_tally);
+    float* d_g32 = (float*)(base + at_g32);
+    F2_HIP(ctx, hipMemsetAsync(d_acc, 0, at_g32 - ws_bytes, ctx->stream));   // (m == 0: zero gradients, loss 0, 0 hits)
+    std::vector<float> hx;
+    std::vector<uint8_t> hy;
+    for (int64_t s = 0; s < m; s += piece) {
+        const int64_t mm = std::min(piece, m - s);
+        const float* d_x = x;
+        const uint8_t* d_y = y;
+        const int64_t* d_index = index_or_null ? index_or_null + s : nullptr;
+        if (host) {   // only the windows of the call go up: gathered here, staged, and waited for before the next piece reuses the buffers
+            const void *px, *py;
+            if (index_or_null) {
+                hx.resize((size_t)mm * xs);
+                hy.resize((size_t)mm);
+                for (int64_t j = 0; j < mm; ++j) {
+                    memcpy(hx.data() + (size_t)j * xs, x + (size_t)index_or_null[s + j] * xs, sizeof(float) * xs);
+                    hy[(size_t)j] = y[index_or_null[s + j]];
+                }
+                F2_TRY(f2_stage_input(ctx, hx.data(), sizeof(float) * xs * (size_t)mm, mem_space, &px));
+                F2_TRY(f2_stage_into(ctx, ctx->stage_aux, hy.data(), (size_t)mm, mem_space, &py));
+            } else {
+                F2_TRY(f2_stage_input(ctx, x + (size_t)s * xs, sizeof(float) * xs * (size_t)mm, mem_space, &px));
+                F2_TRY(f2_stage_into(ctx, ctx->stage_aux, y + s, (size_t)mm, mem_space, &py));
+            }
+            d_x = (const float*)px, d_y = (const uint8_t*)py, d_index = nullptr;
+        } else if (!index_or_null) {
+            d_x = x + (size_t)s * xs, d_y = y + s;
+        }
+        F2_TRY(f2_launch_cnn_loss_gradient(ctx, cnn, d_x, d_y, d_index, mm, s, drop, seed, step, base, d_acc, false, d_tally));
+        if (host) F2_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    if (grads_or_null) {
+        F2_TRY(f2_train_round(ctx, d_acc, d_g32, T));
+        for (int i = 0; i < 12; ++i)
+            F2_HIP(ctx, hipMemcpyAsync(grads_or_null[i], d_g32 + L.off[i], sizeof(float) * (L.off[i + 1] - L.off[i]),
+                                       host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, ctx->stream));
+    }
+    // the two tallies are host values in both memory spaces: the call waits for them
+    if (loss_sum_or_null || correct_or_null) {
+        double t[2];
+        F2_HIP(ctx, hipMemcpyAsync(t, d_tally, sizeof(t), hipMemcpyDeviceToHost, ctx->stream));
+        F2_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        if (loss_sum_or_null) *loss_sum_or_null = t[0];
+        if (correct_or_null) memcpy(correct_or_null, &t[1], sizeof(int64_t));
+    }
+    return f2_host_wait(ctx, mem_space);
+}
+
+int f2_trainer_create(f2_ctx* ctx, const float* const* tensors, int rows, int channels, double lr, double rho, double eps, double decay,
+                      const double* drop, uint64_t seed, f2_trainer** out) {
+    F2_TRY(f2_check_ctx(ctx));
+    F2_CHECK(ctx, tensors && out, F2_ERR_INVALID, "null argument");
+    *out = nullptr;
+    F2_TRY(check_drop(ctx, drop));
+    F2_CHECK(ctx, std::isfinite(lr) && lr >= 0.0 && rho >= 0.0 && rho <= 1.0 && eps >= 0.0 && std::isfinite(eps) && decay >= 0.0 &&
+                      std::isfinite(decay),
+             F2_ERR_INVALID, "bad optimiser constants (lr %g, rho %g, eps %g, decay %g)", lr, rho, eps, decay);
+    f2_cnn* cnn = nullptr;
+    F2_TRY(f2_cnn_create(ctx, tensors, rows, channels, &cnn));
+    f2_trainer* t = new f2_trainer();
+    t->cnn = cnn, t->rows = rows, t->channels = channels, t->dev = ctx->device;
+    t->L = f2_train_tensor_layout(cnn->flat);
+    t->lr = lr, t->rho = rho, t->eps = eps, t->decay = decay, t->seed = seed;
+    for (int l = 0; l < 3; ++l) t->drop[l] = drop[l];
+    const size_t T = t->L.total();
+    int rc = f2_reserve(ctx, t->w, sizeof(float) * T);
+    if (rc == F2_OK) rc = f2_reserve(ctx, t->a, sizeof(float) * T);
+    if (rc == F2_OK) rc = f2_reserve(ctx, t->g, sizeof(float) * T);
+    if (rc == F2_OK) rc = f2_reserve(ctx, t->acc, align256(sizeof(double) * T) + 256);
+    if (rc == F2_OK) rc = f2_cnn_grad_blob(ctx, cnn, &t->grad_blob, t->grad_off);
+    hipError_t e = hipSuccess;
+    for (int i = 0; rc == F2_OK && e == hipSuccess && i < 12; ++i)
+        e = hipMemcpyAsync((float*)t->w.ptr + t->L.off[i], tensors[i], sizeof(float) * (t->L.off[i + 1] - t->L.off[i]), hipMemcpyHostToDevice,
+                           ctx->stream);
+    if (rc == F2_OK && e == hipSuccess) e = hipMemsetAsync(t->a.ptr, 0, sizeof(float) * T, ctx->stream);
+    if (rc == F2_OK && e == hipSuccess) e = hipMemsetAsync(t->g.ptr, 0, sizeof(float) * T, ctx->stream);
+    if (rc == F2_OK && e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (rc == F2_OK && e != hipSuccess) rc = f2_fail(ctx, F2_ERR_HIP, "uploading the master weights -> %s", hipGetErrorString(e));
+    if (rc != F2_OK) {
+        (void)f2_cnn_destroy(ctx, cnn);
+        delete t;
+        return rc;
+    }
+    *out = t;
+    return F2_OK;
+}
+
+int f2_trainer_destroy(f2_ctx* ctx, f2_trainer* t) {
+    if (!t) return F2_OK;
+    if (ctx) (void)hipStreamSynchronize(ctx->stream);
+    (void)f2_cnn_destroy(ctx, t->cnn);
+    delete t;
+    return F2_OK;
+}
+
+static int check_trainer(f2_ctx* ctx, const f2_trainer* t) {
+    F2_CHECK(ctx, t, F2_ERR_INVALID, "trainer is NULL");
+    F2_CHECK(ctx, t->dev == ctx->device, F2_ERR_INVALID, "trainer lives on device %d, context on %d", t->dev, ctx->device);
+    return F2_OK;
+}
+
+int f2_trainer_set_data(f2_ctx* ctx, f2_trainer* t, const float* x, const uint8_t* y, int64_t n) {
+    F2_TRY(f2_check_ctx(ctx));
+    F2_TRY(check_trainer(ctx, t));
+    F2_CHECK(ctx, n >= 0 && (n == 0 || (x && y)), F2_ERR_INVALID, "bad training set (n %lld)", (long long)n);
+    const size_t xs = (size_t)t->rows * t->channels;
+    t->n = 0;
+    if (n == 0) return F2_OK;
+    F2_TRY(f2_reserve(ctx, t->x, sizeof(float) * xs * (size_t)n));
+    F2_TRY(f2_reserve(ctx, t->y, (size_t)n));
+    F2_HIP(ctx, hipMemcpyAsync(t->x.ptr, x, sizeof(float) * xs * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+    F2_HIP(ctx, hipMemcpyAsync(t->y.ptr, y, (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+    F2_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    t->n = n;
+    return F2_OK;
+}
+
+int f2_trainer_steps(f2_ctx* ctx, f2_trainer* t, const int64_t* order, int64_t count, int batch, double* loss_sum_or_null,
+                     int64_t* correct_or_null) {
+    F2_TRY(f2_check_ctx(ctx));
+    F2_TRY(check_trainer(ctx, t));
+    F2_CHECK(ctx, count >= 0 && batch >= 1, F2_ERR_INVALID, "bad step shape (count %lld, batch %d)", (long long)count, batch);
+    F2_CHECK(ctx, count == 0 || order, F2_ERR_INVALID, "order is NULL");
+    for (int64_t j = 0; j < count; ++j)
+        F2_CHECK(ctx, order[j] >= 0 && order[j] < t->n, F2_ERR_INVALID, "order[%lld] = %lld is outside the %lld windows of the training set",
+                 (long long)j, (long long)order[j], (long long)t->n);
+    const size_t T = t->L.total();
+    double* d_acc = (double*)t->acc.ptr;
+    double* d_tally = (double*)((char*)t->acc.ptr + align256(sizeof(double) * T));
+    if (count > 0) {
+        F2_TRY(f2_reserve(ctx, t->order, sizeof(int64_t) * (size_t)count));
+        F2_TRY(f2_upload_async(ctx, t->order.ptr, order, sizeof(int64_t) * (size_t)count));
+        F2_TRY(f2_reserve(ctx, ctx->train_ws, f2_cnn_loss_gradient_ws_bytes(t->cnn, std::min<int64_t>(count, batch))));
+        F2_HIP(ctx, hipMemsetAsync(d_tally, 0, 16, ctx->stream));
+    }
+    // the steps go onto the stream back to back; one wait at the end
+    for (int64_t s = 0; s < count; s += batch) {
+        const int64_t mb = std::min<int64_t>(batch, count - s);
+        F2_TRY(f2_launch_cnn_loss_gradient(ctx, t->cnn, (const float*)t->x.ptr, (const uint8_t*)t->y.ptr, (const int64_t*)t->order.ptr + s, mb, 0,
+                                           t->drop, t->seed, (uint64_t)t->iterations, ctx->train_ws.ptr, d_acc, true, d_tally));
+        F2_TRY(f2_train_round(ctx, d_acc, (float*)t->g.ptr, T));
+        const double lr_t = t->lr / (1.0 + t->decay * (double)t->iterations);
+        F2_TRY(f2_train_rmsprop(ctx, (float*)t->w.ptr, (float*)t->a.ptr, (const float*)t->g.ptr, T, mb, (float)lr_t, (float)t->rho,
+                                (float)(1.0 - t->rho), (float)t->eps));
+        F2_TRY(f2_train_relayout(ctx, (const float*)t->w.ptr, t->cnn, t->grad_blob, t->grad_off));
+        ++t->iterations;
+    }
+    double tl[2] = {0.0, 0.0};
+    if (count > 0) {
+        F2_HIP(ctx, hipMemcpyAsync(tl, d_tally, sizeof(tl), hipMemcpyDeviceToHost, ctx->stream));
+        F2_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    if (loss_sum_or_null) *loss_sum_or_null = tl[0];
+    if (correct_or_null) memcpy(correct_or_null, &tl[1], sizeof(int64_t));
+    return F2_OK;
+}
+
+int f2_trainer_get(f2_ctx* ctx, const f2_trainer* t, int what, float* const* tensors) {
+    F2_TRY(f2_check_ctx(ctx));
+    F2_TRY(check_trainer(ctx, t));
+    F2_CHECK(ctx, what == F2_TRAINER_WEIGHTS || what == F2_TRAINER_ACCUMULATORS || what == F2_TRAINER_GRADIENT, F2_ERR_INVALID,
+             "what = %d is not one of F2_TRAINER_*", what);
+    F2_CHECK(ctx, tensors, F2_ERR_INVALID, "tensors is NULL");
+    for (int i = 0; i < 12; ++i) F2_CHECK(ctx, tensors[i], F2_ERR_INVALID, "tensor %d is NULL", i);
+    const float* src = (const float*)(what == F2_TRAINER_WEIGHTS ? t->w.ptr : what == F2_TRAINER_ACCUMULATORS ? t->a.ptr : t->g.ptr);
+    for (int i = 0; i < 12; ++i)
+        F2_HIP(ctx, hipMemcpyAsync(tensors[i], src + t->L.off[i], sizeof(float) * (t->L.off[i + 1] - t->L.off[i]), hipMemcpyDeviceToHost,
+                                   ctx->stream));
+    F2_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return F2_OK;
+}
+
+int f2_trainer_get_info(f2_ctx* ctx, const f2_trainer* t, const char* key, double* value) {
+    F2_TRY(f2_check_ctx(ctx));
+    F2_TRY(check_trainer(ctx, t));
+    F2_CHECK(ctx, key && value, F2_ERR_INVALID, "null argument");
+    if (strcmp(key, "iterations") == 0) *value = (double)t->iterations;
+    else return f2_fail(ctx, F2_ERR_INVALID, "unknown key '%s'", key);
+    return F2_OK;
+}
+
+}  // extern "C"

@@ -56,6 +56,7 @@ struct f2_ctx {
     f2_scratch xbuf;       // window tensor chunk between K3 and K4
     f2_scratch occ_src;    // f2_eval_occlusion_batch: the source windows of a chunk, which k_occlude_windows expands into xbuf
     f2_scratch grad_ws;    // f2_cnn_input_gradient: activations and gradients of a chunk of windows (f2_cnn_grad.hip), at most 1 GiB
+    f2_scratch train_ws;   // f2_cnn_loss_gradient / f2_trainer_steps: partial sums, float64 gradient and the small per-window arrays (f2_cnn_train.hip)
     f2_scratch sal_profile;  // f2_eval_saliency_batch: the (C, 2) float64 profile rows of all windows of the call
     f2_scratch dense_in;   // conv4 outputs (+ dense1 outputs) of the windows of several utterances: one dense launch for all
     // the four sweeps, f2_lowpass_levels, f2_reverb_levels, f2_channel_mix_levels: the (K+1) x batch levels (float64 waveforms or envelopes) when the caller
@@ -486,8 +487,9 @@ int f2_launch_cnn(f2_ctx* ctx, const f2_cnn* cnn, const f2_scale_set* S, f2_cnn_
 // the two halves of f2_launch_cnn (f2_cnn.hip): convolutions per chunk of windows, dense layers over several chunks at once
 int f2_launch_cnn_convs(f2_ctx* ctx, const f2_cnn* cnn, const f2_scale_set* S, f2_cnn_route route, const float* d_x, int64_t n,
                         float* d_ws, float* a4);
+// (with_dense2 = false: dense1 alone, a5 filled and nothing else written - a training step masks a5 before its own dense2)
 int f2_launch_cnn_dense(f2_ctx* ctx, const f2_cnn* cnn, const f2_scale_set* S, f2_cnn_route route, const float* a4, int64_t n, float* a5,
-                        float* d_scores, uint8_t* d_labels);
+                        float* d_scores, uint8_t* d_labels, bool with_dense2 = true);
 // what f2_launch_cnn_convs leaves a4 multiplied by on this route: dense1's input scale where the split conv4 kernels wrote it
 // (windows with four pooled rows after conv2), 1 everywhere else
 float f2_cnn_a4_scale(const f2_cnn* cnn, const f2_scale_set* S, f2_cnn_route route);

@@ -146,6 +146,38 @@ class F2CNNModel:
             h = self._handles[id(ctx)] = (ctx, ctx.cnn_create(self.ordered(), self.rows, self.channels))
         return h[1]
 
+    def release(self, ctx=None):
+        """Frees the device copy of the weights on `ctx` (a model made for one use, e.g. a training epoch's validation)"""
+        ctx = ctx or _lib.default_context()
+        h = self._handles.pop(id(ctx), None)
+        if h is not None:
+            ctx.cnn_destroy(h[1])
+
+    def loss_gradient(self, x, y, index=None, drop=(0.0, 0.0, 0.0), seed=0, step=0, ctx=None):
+        """(grads, loss_sum, correct): the gradient of the summed cross-entropy of the windows x[index] (all of x without an
+        index) with the labels y for the 12 weight tensors - a dict like .tensors -, by the recorded float32 forward in training
+        mode and one backward pass on the device (include/f2cnn_hip.h: f2_cnn_loss_gradient). drop: the three dropout rates,
+        seed / step: of their masks."""
+        ctx = ctx or _lib.default_context()
+        x = np.asarray(x)
+        if x.ndim == 4 and x.shape[-1] == 1:
+            x = x[..., 0]
+        if x.ndim != 3 or x.shape[1:] != (self.rows, self.channels):
+            raise ValueError(f"expected input of shape (n,{self.rows},{self.channels}[,1]), got {x.shape}")
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        y = np.ascontiguousarray(np.asarray(y).reshape(-1), dtype=np.uint8)
+        if len(y) != len(x):
+            raise ValueError("x and y must have one entry per window")
+        if index is not None:
+            index = np.ascontiguousarray(index, dtype=np.int64)
+            if len(index) and (index.min() < 0 or index.max() >= len(x)):
+                raise ValueError("index reaches outside x")
+        m = len(x) if index is None else len(index)
+        names = [n + s for n in NAMES for s in ("_w", "_b")]
+        grads = {k: np.empty(self.tensors[k].shape, np.float32) for k in names}
+        loss, hits = ctx.cnn_loss_gradient(self.handle(ctx), x, y, index, m, drop, seed, step, [grads[k] for k in names], _lib.MEM_HOST)
+        return grads, loss, hits
+
     def predict(self, x, ctx=None):
         """Softmax scores (n,2) float32 for x (n, rows, channels[,1]); like keras model.predict, any finite input. The default
         split-fp16 path scales its operands for the range it measures in x (per chunk of 16384 windows); inputs it cannot take

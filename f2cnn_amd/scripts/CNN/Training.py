@@ -3,7 +3,8 @@
 ``normalizeInput`` (:13-28) is on the hot path and runs through HIP kernel K3. ``SeparateTestTrain`` (:31-44) and
 ``TrainAndPlotLoss`` (:47-156) are SURVEY section 8f row n4: the same network (:93-114; weights in
 ``f2cnn_amd.model``), RMSprop(lr 1e-4, decay 1e-6), categorical cross-entropy, early stopping on the validation
-accuracy (min_delta 0.01, patience 5), trained with PyTorch-ROCm autograd as the scope table asks. Training only
+accuracy (min_delta 0.01, patience 5), trained with PyTorch-ROCm autograd as the scope table asks, or (``engine='hip'``,
+``cnn train --engine hip``) with the library's own training step: weight gradients, dropout and RMSprop on the device. Training only
 produces weights; every forward pass used for evaluation is HIP kernel K4 (the trained weights are written in the
 ``.npz`` container K4 loads, under the reference's file name ``last_trained_model``).
 
@@ -119,11 +120,12 @@ def build_network(rows=11, channels=128):
     return Net()
 
 
-def train_network(x_train, y_train, x_test, y_test, batch_size=32, epochs=20, device=None, seed=None, verbose=1,
-                  lr=1e-4, decay=1e-6, min_delta=0.01, patience=5):
-    """model.compile + model.fit of Training.py:117-135 on already normalised float32 windows (n, rows, C).
-    Returns (F2CNNModel, history) with history = {'loss','acc','val_loss','val_acc'} per epoch.
-    RMSprop as Keras 2.2 runs it: rho 0.9, epsilon 1e-7, lr_t = lr / (1 + decay * iterations)."""
+ENGINES = ("torch", "hip")
+DROPOUT = (0.25, 0.25, 0.5)     # the three Dropout layers of Training.py:93-114
+
+
+def _torch_engine(x_train, y_train, x_test, y_test, batch_size, device, seed, lr, decay):
+    """PyTorch-ROCm autograd: (run_epoch() -> (loss sum, hits), validate() -> (val_loss, val_acc), export() -> F2CNNModel)"""
     import torch
     from ...model import F2CNNModel
     if device is None:
@@ -132,8 +134,6 @@ def train_network(x_train, y_train, x_test, y_test, batch_size=32, epochs=20, de
         device = "cuda"
     if seed is not None:
         torch.manual_seed(seed)
-    x_train = numpy.asarray(x_train, numpy.float32)
-    x_test = numpy.asarray(x_test, numpy.float32)
     rows, channels = x_train.shape[1], x_train.shape[2]
     net = build_network(rows, channels).to(device)
     xt = torch.from_numpy(x_train).unsqueeze(1).to(device)
@@ -155,9 +155,7 @@ def train_network(x_train, y_train, x_test, y_test, batch_size=32, epochs=20, de
         n = max(len(x), 1)
         return tot / n, hit / n
 
-    history = {"loss": [], "acc": [], "val_loss": [], "val_acc": []}
-    best, wait = -numpy.inf, 0
-    for epoch in range(epochs):
+    def run_epoch():
         net.train()
         perm = torch.randperm(len(xt), device=device)          # fit(shuffle=True)
         tot, hit = 0.0, 0
@@ -171,8 +169,64 @@ def train_network(x_train, y_train, x_test, y_test, batch_size=32, epochs=20, de
             sched.step()
             tot += float(loss.detach())
             hit += int((lg.argmax(1) == yt[idx]).sum())
-        vl, va = evaluate(xv, yv) if len(xv) else (float("nan"), float("nan"))
-        for k, val in zip(("loss", "acc", "val_loss", "val_acc"), (tot / len(xt), hit / len(xt), vl, va)):
+        return tot, hit
+
+    def validate():
+        return evaluate(xv, yv) if len(xv) else (float("nan"), float("nan"))
+
+    return run_epoch, validate, lambda: F2CNNModel.from_torch_state_dict(net.state_dict(), rows, channels)
+
+
+def _hip_engine(x_train, y_train, x_test, y_test, batch_size, seed, lr, decay, ctx=None):
+    """The library's own training step (f2_trainer_*): weights, RMSprop accumulators and the training set stay on the device, an
+    epoch is one f2_trainer_steps call over a NumPy permutation. Initial weights F2CNNModel.glorot(seed, zero_bias=True) (Keras'
+    defaults); the same seed gives the same weights bit for bit. Validation goes through F2CNNModel.evaluate
+    (f2_cnn_score_windows) on the exported weights."""
+    from ...trainer import Trainer
+    from ...model import F2CNNModel
+    ctx = ctx or _lib.default_context()       # (no library or no device: raises here)
+    rows, channels = x_train.shape[1], x_train.shape[2]
+    rng = numpy.random.default_rng(seed)
+    mask_seed = int(seed) if seed is not None else int(rng.integers(0, 2 ** 63))
+    trainer = Trainer(F2CNNModel.glorot(seed, rows, channels, zero_bias=True), lr=lr, rho=0.9, eps=1e-7, decay=decay, drop=DROPOUT,
+                      seed=mask_seed, ctx=ctx)
+    trainer.set_data(x_train, numpy.asarray(y_train))
+    y_val = numpy.asarray(y_test)
+
+    def validate():
+        if not len(x_test):
+            return float("nan"), float("nan")
+        model = trainer.model()
+        try:
+            return model.evaluate(x_test, y_val, ctx=ctx)
+        finally:
+            model.release(ctx)
+
+    return lambda: trainer.steps(rng.permutation(len(x_train)), batch_size), validate, trainer.model
+
+
+def train_network(x_train, y_train, x_test, y_test, batch_size=32, epochs=20, device=None, seed=None, verbose=1,
+                  lr=1e-4, decay=1e-6, min_delta=0.01, patience=5, engine="torch"):
+    """model.compile + model.fit of Training.py:117-135 on already normalised float32 windows (n, rows, C).
+    Returns (F2CNNModel, history) with history = {'loss','acc','val_loss','val_acc'} per epoch.
+    RMSprop as Keras 2.2 runs it: rho 0.9, epsilon 1e-7, lr_t = lr / (1 + decay * iterations).
+    engine: 'torch' (PyTorch-ROCm autograd) or 'hip' (the library's own kernels, on the default context's device; `device` is
+    not used). Both share the epoch loop and the early-stopping rule below."""
+    if engine not in ENGINES:
+        raise ValueError("engine must be one of {}, not {!r}".format(ENGINES, engine))
+    x_train = numpy.asarray(x_train, numpy.float32)
+    x_test = numpy.asarray(x_test, numpy.float32)
+    if engine == "torch":
+        run_epoch, validate, export = _torch_engine(x_train, y_train, x_test, y_test, batch_size, device, seed, lr, decay)
+    else:
+        run_epoch, validate, export = _hip_engine(x_train, y_train, x_test, y_test, batch_size, seed, lr, decay)
+    n_train = len(x_train)
+    history = {"loss": [], "acc": [], "val_loss": [], "val_acc": []}
+    best, wait = -numpy.inf, 0
+    for epoch in range(epochs):
+        tot, hit = run_epoch()
+        vl, va = validate()
+        for k, val in zip(("loss", "acc", "val_loss", "val_acc"), (tot / n_train, hit / n_train, vl, va)):
             history[k].append(val)
         if verbose:
             print("Epoch {}/{} - loss: {:.4f} - acc: {:.4f} - val_loss: {:.4f} - val_acc: {:.4f}".format(
@@ -186,12 +240,12 @@ def train_network(x_train, y_train, x_test, y_test, batch_size=32, epochs=20, de
                 if verbose:
                     print("Epoch {:05d}: early stopping".format(epoch + 1))
                 break
-    model = F2CNNModel.from_torch_state_dict(net.state_dict(), rows, channels)
-    return model, history
+    return export(), history
 
 
-def TrainAndPlotLoss(labelFile=None, inputFile=None, device=None, seed=None):
-    """Trains the CNN on an input tensor (N x 11 x 128, ``prepare input``) and its label CSV (``prepare label``);
+def TrainAndPlotLoss(labelFile=None, inputFile=None, device=None, seed=None, engine="torch"):
+    """Trains the CNN on an input tensor (N x 11 x 128, ``prepare input``) and its label CSV (``prepare label``), with
+    PyTorch-ROCm autograd (engine 'torch') or the library's own training step (engine 'hip');
     BATCH_SIZE and EPOCHS come from configF2CNN.conf. Saves the weights as 'last_trained_model' (the .npz container
     ``cnn eval`` loads) and the per-epoch history as 'last_trained_model_results.json' (the reference plots it)."""
     from configparser import ConfigParser
@@ -211,7 +265,7 @@ def TrainAndPlotLoss(labelFile=None, inputFile=None, device=None, seed=None):
     print(x_train.shape, 'train samples')
     print(x_test.shape, 'test samples')
     print("Categories: [falling, rising]")
-    model, history = train_network(x_train, y_train, x_test, y_test, batch_size, epochs, device=device, seed=seed)
+    model, history = train_network(x_train, y_train, x_test, y_test, batch_size, epochs, device=device, seed=seed, engine=engine)
     model.save('last_trained_model')
     print("Model saved as 'last_trained_model'.")
     # model.evaluate on the test set, through the HIP forward pass that `cnn eval` uses

@@ -890,6 +890,72 @@ int f2_eval_smear_sweep(f2_ctx* ctx, const f2_cnn* cnn, const void* wave, int wa
                         double* env_levels_or_null, float* scores_or_null, uint8_t* labels_or_null,
                         int64_t* window_offsets_or_null /* host, (K+1)*B + 1 */, int64_t* stats_or_null /* host, (K+1)*B*2 */, int mem_space);
 
+/* ---- `cnn train --engine hip`: a training step on the device ------------------------------------------------------------------
+ * The reference trains with Keras (Training.py:117-135): categorical cross-entropy, RMSprop(lr 1e-4, decay 1e-6), three Dropout
+ * layers. These entries run that step on the recorded float32 forward and the backward-data chain of f2_cnn_input_gradient, with
+ * weight-gradient kernels, dropout and the optimiser beside them. (f2_version stays 115 with these entries: look the symbols up.)
+ *
+ * f2_cnn_loss_gradient (stateless): x (n_all, R, C) float32 and y (n_all) uint8 labels (0 falling, anything else rising) in
+ * mem_space; the m windows of the call are x[index[j]] (index (m) int64 in mem_space), or the first m without an index. Window j
+ * is window b = j of the call's batch. Outputs, every one optional (NULL) and none changing another:
+ *   grads      host array of 12 pointers, each to a tensor in mem_space in f2_cnn_create's order and Keras layouts: the gradient of
+ *              L = sum over the m windows of -ln softmax(z)[y] (the sum, not the mean; the probabilities are not clipped)
+ *   loss_sum   host, one double: L, float64 from the float32 logits
+ *   correct    host, one int64: the windows whose training-mode decision (scores[1] > scores[0], ties falling) equals the label
+ * The forward is the recorded float32 pass in training mode: Keras' three Dropout layers, after the two pools and after dense1's
+ * ReLU, with the rates drop[0..2] and inverted scaling. With the element's index e in the library's order of the tensor -
+ * (Hp1, Wp1, 32), (Hp2, Wp2, 64), (516) - and l = 0 / 1 / 2 for the layer:
+ *             (w0, w1, w2, w3) = Philox4x32-10(counter = (e >> 2, b, l, step & 0xffffffff), key = (seed & 0xffffffff, seed >> 32))
+ *             the element uses word e & 3; it is kept iff word * 2^-32 >= rate, and a kept value is multiplied by the float32
+ *             nearest 1 / (1 - rate). Philox with the standard constants, as in f2_eval_noise_sweep. A rate of 0 draws nothing:
+ *             drop = {0, 0, 0} is the chain without dropout, whatever seed and step are.
+ * The gradient at the logits is dz = softmax(z) - onehot(y); ReLU and max-pool pass gradient by f2_cnn_input_gradient's rules; a
+ * dropped cell passes none, a kept one 1 / (1 - rate) times it. Weight gradients: dW[tap][ci][co] = sum over windows and output
+ * pixels of in[pixel + tap][ci] g[pixel][co], biases the sums of g, dense layers a^T g. Summation: no float32 chain is longer than
+ * 1024 terms (conv2 .. conv4: at most 1024 pixels of one window per partial sum on the f32 matrix cores, the window cut the same
+ * way wherever it stands); partial sums are added in float64, in an order that depends on the window shape and on m alone, on a
+ * float64 gradient that also carries the sum over the chain's chunks of at most 1024 windows and is rounded to float32 once.
+ * conv1, dense1 (on the float64 matrix cores), dense2 and the dense biases are float64 sums of exact products of float32 values. No
+ * floating-point atomics: the same bits on every call and in both memory spaces.
+ * F2_MEM_HOST calls stage only the m windows of the call (4096 at a time) and return when the outputs are filled; F2_MEM_DEVICE
+ * calls enqueue, and wait for the stream only when loss_sum or correct is asked for. The call shares ctx's gradient scratch with
+ * f2_cnn_input_gradient. F2_ERR_INVALID, with nothing launched or written: a NULL ctx, cnn or drop; a cnn of another device; m < 0;
+ * NULL x or y with m > 0; a rate outside [0, 1); a NULL entry of grads; a negative index in host memory; a mem_space other than
+ * F2_MEM_HOST / F2_MEM_DEVICE. The call is not told n_all: that every index is below it is the caller's duty, as is an index in
+ * device memory being non-negative. m == 0: F2_OK, zero gradients, loss 0, 0 correct.
+ *
+ * f2_trainer_*: the weights, RMSprop's accumulators and the training set stay on the device between steps.
+ *   create     12 host tensors (f2_cnn_create's order and checks), the window shape, RMSprop's constants, the three rates and the
+ *              seed of the masks. Accumulators start at 0, "iterations" at 0.
+ *   set_data   x (n, R, C) float32 normalised windows and y (n) uint8 labels, host memory, copied to the device once
+ *   steps      order (count) int64, host, indices into the training set: ceil(count / batch) steps, step s on the windows
+ *              order[s batch .. min((s + 1) batch, count)), the last one partial, enqueued back to back with one wait at the end.
+ *              Each step: the gradient g of f2_cnn_loss_gradient with those indices, the trainer's rates and seed and step =
+ *              "iterations" (same launch, same bits), then with m the step's window count, in float32 per element,
+ *                  gm = g / m;  a = rho a + (1 - rho) gm^2;  p = p - lr_t gm / (sqrt(a) + eps),
+ *              lr_t = lr / (1 + decay iterations) formed in double and rounded to float32 - RMSprop as Keras 2.2 runs it -, then
+ *              the layouts the kernels read are rebuilt from the new weights on the device and "iterations" goes up by one.
+ *              loss_sum / correct (host, optional): the sums of the steps' L and hits, each step with the weights it started from.
+ *   get        what = F2_TRAINER_WEIGHTS, F2_TRAINER_ACCUMULATORS or F2_TRAINER_GRADIENT (the last step's g): 12 host tensors
+ *   get_info   "iterations": steps taken so far
+ * F2_ERR_INVALID, with nothing launched: NULL arguments, a trainer of another device, non-finite or negative constants, rho outside
+ * [0, 1], a rate outside [0, 1), batch < 1, count < 0, an order entry outside [0, n), an unknown `what` or key.
+ */
+typedef struct f2_trainer f2_trainer;
+enum { F2_TRAINER_WEIGHTS = 0, F2_TRAINER_ACCUMULATORS = 1, F2_TRAINER_GRADIENT = 2 };
+int f2_cnn_loss_gradient(f2_ctx* ctx, const f2_cnn* cnn, const float* x /* (n_all, R, C), mem_space */, const uint8_t* y /* (n_all), mem_space */,
+                         const int64_t* index_or_null /* (m), mem_space */, int64_t m, const double* drop /* host, 3 */, uint64_t seed,
+                         uint64_t step, float* const* grads_or_null /* host, 12 pointers into mem_space */, double* loss_sum_or_null /* host */,
+                         int64_t* correct_or_null /* host */, int mem_space);
+int f2_trainer_create(f2_ctx* ctx, const float* const* tensors, int rows, int channels, double lr, double rho, double eps, double decay,
+                      const double* drop /* host, 3 */, uint64_t seed, f2_trainer** trainer);
+int f2_trainer_destroy(f2_ctx* ctx, f2_trainer* trainer);
+int f2_trainer_set_data(f2_ctx* ctx, f2_trainer* trainer, const float* x /* host, (n, R, C) */, const uint8_t* y /* host, (n) */, int64_t n);
+int f2_trainer_steps(f2_ctx* ctx, f2_trainer* trainer, const int64_t* order /* host, count */, int64_t count, int batch,
+                     double* loss_sum_or_null /* host */, int64_t* correct_or_null /* host */);
+int f2_trainer_get(f2_ctx* ctx, const f2_trainer* trainer, int what, float* const* tensors /* host, 12 pointers to host tensors */);
+int f2_trainer_get_info(f2_ctx* ctx, const f2_trainer* trainer, const char* key, double* value);
+
 #ifdef __cplusplus
 }
 #endif
