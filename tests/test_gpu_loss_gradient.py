@@ -2,7 +2,9 @@
 mode, the backward chain and the weight-gradient kernels of csrc/f2_cnn_train.hip, against the PyTorch autograd referee
 (tests/train_referee.py, which states the acceptance rule, the window selection and where the tolerance comes from), and the
 promises of the header: the same bits on every call and in both memory spaces, an index that only gathers, sums that are the
-float64 sums of their pieces, masks that follow (seed, step, place), exact zeros for a dead network."""
+float64 sums of their pieces, masks that follow (seed, step, place) also past the first chunk of the chain's scratch and past the
+first piece a host call stages, any nonzero label rising, a saturated softmax, exact zeros for a dead network and - in every
+comparison with the referee - wherever every term of an element is zero."""
 import ctypes
 
 import numpy as np
@@ -155,6 +157,73 @@ def test_chunk_crossing(ctx):
     assert correct == ca + cb and abs(loss - (la + lb)) <= 1e-12 * loss
     device, t = loss_gradient(ctx, model, x, y, mem=_lib.MEM_DEVICE)
     assert same_bits(whole, device) and t == (loss, correct)
+
+
+def test_dropout_and_index_past_the_first_chunk(ctx):
+    """CHUNK_CASE: 1094 selected windows with dropout, so the windows at the places 1024 .. 1093 stand in the chain's second chunk.
+    The referee pins their masks to the header's formula (place b = b0 + s of the batch, not of the chunk); the device-memory call
+    and the calls on the shuffled arrays with the index that undoes the shuffle (the device index and the host gather, both offset
+    by the chunk) give the host-memory call's bits."""
+    ref = tr.referee(*tr.CHUNK_CASE, tr.DROP)
+    n = len(ref.x)
+    assert n > 1024
+    first, tally = loss_gradient(ctx, ref.model, ref.x, ref.y, drop=tr.DROP)
+    assert all(np.isfinite(g).all() for g in first.values())
+    tr.accept(first, tally[0], ref, "device {} {}".format(tr.CHUNK_CASE, tr.DROP))
+    device, td = loss_gradient(ctx, ref.model, ref.x, ref.y, drop=tr.DROP, mem=_lib.MEM_DEVICE)
+    assert same_bits(first, device) and td == tally
+    perm = np.random.default_rng(5).permutation(n).astype(np.int64)
+    back = np.argsort(perm).astype(np.int64)
+    assert (back[1024:] != np.arange(1024, n)).any() and (back[:1024] >= 1024).any()      # windows cross the chunk boundary both ways
+    xp, yp = np.ascontiguousarray(ref.x[perm]), np.ascontiguousarray(ref.y[perm])
+    for mem in (_lib.MEM_HOST, _lib.MEM_DEVICE):
+        got, t = loss_gradient(ctx, ref.model, xp, yp, index=back, drop=tr.DROP, mem=mem)
+        assert same_bits(first, got) and t == tally, mem
+
+
+def test_past_the_first_host_piece(ctx):
+    """4100 windows with dropout: the host-memory call stages a piece of 4096 and one of 4 (places 4096 + 0 ..), the device-memory
+    call works through five chunks of the chain's scratch in one launch sequence (places 0 + 0 .. 4096): the same bits and tallies,
+    also with a reversing index on the reversed arrays (the host gather `index[s + j]` past the first piece)"""
+    model = F2CNNModel.glorot(SMALL[0], SMALL[2], SMALL[3], zero_bias=False)
+    rng = np.random.default_rng(13)
+    n = 4100
+    x = rng.random((n, SMALL[2], SMALL[3])).astype(np.float32)
+    y = rng.integers(0, 2, n).astype(np.uint8)
+    host, th = loss_gradient(ctx, model, x, y, drop=tr.DROP)
+    device, td = loss_gradient(ctx, model, x, y, drop=tr.DROP, mem=_lib.MEM_DEVICE)
+    assert all(np.isfinite(g).all() and g.any() for g in host.values())
+    assert same_bits(host, device) and th == td
+    rev = np.arange(n - 1, -1, -1, dtype=np.int64)
+    turned, tt = loss_gradient(ctx, model, np.ascontiguousarray(x[::-1]), np.ascontiguousarray(y[::-1]), index=rev, drop=tr.DROP)
+    assert same_bits(host, turned) and tt == th
+
+
+@pytest.mark.parametrize("mem", (_lib.MEM_HOST, _lib.MEM_DEVICE), ids=("host", "device"))
+def test_any_nonzero_label_is_rising(ctx, small, mem):
+    ref, (first, tally) = small
+    assert set(np.unique(ref.y)) == {0, 1}
+    for label in (2, 255):
+        y = np.where(ref.y != 0, label, 0).astype(np.uint8)
+        got, t = loss_gradient(ctx, ref.model, ref.x, y, drop=tr.DROP, mem=mem)
+        assert same_bits(first, got) and t == tally, label
+
+
+def test_saturated_softmax(ctx):
+    """dense2 times SATURATION_GAIN: more than a quarter of the windows have |z1 - z0| > 110, where float32 expf underflows and the
+    losing score is exactly 0 - the regime dz = rising ? -s0 : s1 was written for -, more than a quarter < 80, none < 20. Half of
+    either group is decided against its label and costs about |z1 - z0| a window, unclipped, so the loss is part of the rule as ever."""
+    ref = tr.referee(*SMALL, NODROP, dense2_gain=tr.SATURATION_GAIN)
+    gap = np.abs(ref.z64[:, 1] - ref.z64[:, 0])
+    assert (gap > tr.SATURATED).sum() >= len(gap) / 4 and (gap < tr.UNSATURATED).sum() >= len(gap) / 4
+    tr.accept(ref.g32, ref.loss32, ref, "float32 CPU chain, dense2 x {}".format(tr.SATURATION_GAIN), tol=tr.CHAIN_BOUND)
+    for mem in (_lib.MEM_HOST, _lib.MEM_DEVICE):
+        grads, (loss, correct) = loss_gradient(ctx, ref.model, ref.x, ref.y, mem=mem)
+        assert all(np.isfinite(g).all() for g in grads.values()) and np.isfinite(loss)
+        tr.accept(grads, loss, ref, "device, dense2 x {}, memory space {}".format(tr.SATURATION_GAIN, mem))
+        decided = gap > 1e-2                                       # (float32 logits of this size are good to about 1e-3)
+        want = int(((ref.z64[:, 1] > ref.z64[:, 0]) == (ref.y != 0)).sum())
+        assert abs(correct - want) <= int((~decided).sum())
 
 
 def test_masks_follow_seed_step_and_rate(ctx, small):

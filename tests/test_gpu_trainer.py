@@ -78,6 +78,29 @@ def test_three_steps_against_the_stateless_gradient_and_the_rmsprop_rule(ctx, da
     t.close()
 
 
+def test_one_step_over_more_than_a_chunk(ctx):
+    """batch = 1094: the step's launch works through two chunks of the chain's scratch with the offset device index and masks at
+    the places 1024 .. 1093; its gradient and tallies are the stateless call's (which tests/test_gpu_loss_gradient.py holds to the
+    referee on these windows)"""
+    ref = tr.referee(*tr.CHUNK_CASE, tr.DROP)
+    n = len(ref.x)
+    seed = 0xABCDEF0123
+    order = np.arange(n, dtype=np.int64)
+    t = Trainer(ref.model, lr=LR, rho=RHO, eps=EPS, decay=DECAY, drop=tr.DROP, seed=seed, ctx=ctx)
+    t.set_data(ref.x, ref.y)
+    loss, hits = t.steps(order, n)
+    assert t.iterations == 1
+    g = t.gradient()
+    t.close()
+    model = F2CNNModel(ref.model.tensors, ROWS, CHANNELS)         # (a model of this test's own: its device copy lives on this context)
+    want, want_loss, want_hits = model.loss_gradient(ref.x, ref.y, drop=tr.DROP, seed=seed, step=0, ctx=ctx)
+    indexed, il, ih = model.loss_gradient(ref.x, ref.y, index=order, drop=tr.DROP, seed=seed, step=0, ctx=ctx)
+    model.release(ctx)
+    for k in tr.TENSORS:
+        assert g[k].tobytes() == want[k].tobytes() == indexed[k].tobytes(), k
+    assert (loss, hits) == (want_loss, want_hits) == (il, ih)
+
+
 def test_same_seed_same_bytes(ctx, data):
     order = np.random.default_rng(5).permutation(70).astype(np.int64)
     a = run(ctx, data, 11, order)
