@@ -1353,15 +1353,12 @@ static void free_cnn(f2_cnn* cnn) {
 // ---- f2_cnn_create's packing of the weights. A layer's kernel in its Keras layout is the K x N operand w[k][n] of its GEMM
 // (convolutions: k = (dy*3+dx)*Cin + ci) ----
 
-// The float32 kernels' MFMA B operand wt[block][h][s/4][n (npad, zero beyond N)][s%4], k = block*blk + h*blk/2 + s: conv2 .. conv4
-// with blk = Cin (a block per tap), dense1 with blk = D1_KC
+// The float32 kernels' MFMA B operand (cnn_b_operand_index, zero beyond N): conv2 .. conv4 with blk = Cin (a block per tap), dense1
+// with blk = D1_KC
 static std::vector<float> relayout_f32(const float* w, size_t K, int N, int blk, int npad) {
     std::vector<float> dst(K * npad, 0.f);
-    const int half = blk / 2;
-    for (size_t k = 0; k < K; ++k) {
-        const size_t b = k / blk, hh = k % blk / half, s = k % half;
-        for (int n = 0; n < N; ++n) dst[(((b * 2 + hh) * (half / 4) + s / 4) * npad + n) * 4 + s % 4] = w[k * N + n];
-    }
+    for (size_t k = 0; k < K; ++k)
+        for (int n = 0; n < N; ++n) dst[cnn_b_operand_index(k, n, blk, npad)] = w[k * N + n];
     return dst;
 }
 

@@ -1,6 +1,6 @@
 // Shape arithmetic of K4 that f2_cnn.hip and f2_cnn_ws.hip have to agree on: layer widths, tile constants of the fused convolution
-// kernels and of dense1's weight layouts, and the sizes of every layer's output for a rows x channels window. Host and
-// compile-time values only.
+// kernels and of dense1's weight layouts, the sizes of every layer's output for a rows x channels window, the index rule of the
+// MFMA B operand and the launcher of the thread-per-element kernels.
 #ifndef F2_CNN_DIMS_H
 #define F2_CNN_DIMS_H
 
@@ -47,6 +47,25 @@ inline int cnn_grid(f2_ctx* ctx, int64_t blocks, unsigned* grid) {
     F2_CHECK(ctx, blocks < (int64_t(1) << 31), F2_ERR_UNSUPPORTED, "CNN chunk too large");
     *grid = (unsigned)blocks;
     return F2_OK;
+}
+
+// a kernel of one thread per element, 256 to a workgroup, on ctx->stream: the grid check, the launch and its error
+template <class... P, class... A>
+int launch256(f2_ctx* ctx, void (*kernel)(P...), int64_t threads, A... args) {
+    unsigned grid;
+    F2_TRY(cnn_grid(ctx, (threads + 255) / 256, &grid));
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, ctx->stream, args...);
+    F2_HIP(ctx, hipGetLastError());
+    return F2_OK;
+}
+
+// Where w[k][n] of a K x N matrix stands in the float32 kernels' MFMA B operand wt[block][h][s/4][n (npad)][s%4],
+// k = block blk + h blk/2 + s: conv2 .. conv4 with blk = Cin (a block per tap), dense1 with blk = D1_KC, the transposed layers of
+// the backward chain likewise. f2_cnn_create, the chain's transposed weights and the trainer's k_relayout all place by it.
+__host__ __device__ __forceinline__ size_t cnn_b_operand_index(size_t k, int n, int blk, int npad) {
+    const int half = blk / 2;
+    const size_t b = k / blk, hh = k % blk / half, s = k % half;
+    return (((b * 2 + hh) * (half / 4) + s / 4) * npad + n) * 4 + s % 4;
 }
 
 #endif

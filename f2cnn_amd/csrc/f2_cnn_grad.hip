@@ -19,6 +19,8 @@
 // rotated by 180 degrees with Cin and Cout swapped: k_gconv is one implicit-GEMM template for the forward layers and for the
 // transposed ones, with k_conv3x3_mfma's tiling (one task = 2 output rows x 32 columns of one window, its 4 x 34 x CIN patch in LDS
 // at a (CIN + 4)-float pitch). The transposed weights are built from cnn->blob on an f2_cnn's first gradient call.
+// Host side: every launch of the forward and of the chain is a step of f2_grad_chain (f2_cnn_train.h), defined once below;
+// f2_launch_cnn_input_gradient here and the training step of f2_cnn_train.hip are two drivers over those steps.
 // gfx950, wave64. Everything that reaches memory is written by plain C++ stores.
 #include <algorithm>
 #include <cmath>
@@ -29,17 +31,10 @@
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-constexpr int GK = 576;          // dense1's 516 outputs padded to whole 64-value chunks: the K of the transposed dense1
 constexpr int GEMM_WAVES = 4;    // waves (output tiles) of a k_gemm_rows workgroup
 constexpr int GEMM_ROWS = 64;    // windows of a k_gemm_rows workgroup (two M tiles)
 constexpr int64_t GRAD_WS_BYTES = int64_t(1) << 30;   // everything the chain holds between kernels
 constexpr int64_t GRAD_WS_CHUNK = 1024;               // windows of a chunk, at most
-constexpr int64_t GRAD_HOST_CHUNK = 4096;             // windows a host call stages at a time
-
-enum { ST_PLAIN = 0, ST_UNPOOL = 1 };
-enum { EP_RELU = 0, EP_MASK = 1, EP_NONE = 2 };
 
 // ---- conv1 ('same', Cin = 1) + ReLU, recorded: eight threads per pixel, a channel quad each; the oracle's tap order ----
 __global__ __launch_bounds__(256) void k_conv1_fwd(const float* __restrict__ x, const float* __restrict__ w1, const float* __restrict__ b1,
@@ -437,37 +432,23 @@ int launch_gconv(f2_ctx* ctx, const float* in, const float* act, const float* w,
     return F2_OK;
 }
 
-int grid256(f2_ctx* ctx, int64_t threads, unsigned* grid) { return cnn_grid(ctx, (threads + 255) / 256, grid); }
-
-// ---- the weights of the transposed layers, from cnn->blob ----
-// f2_cnn_create's MFMA B operand of a K x N matrix (f2_cnn.hip: relayout_f32): [block][h][s/4][n (npad)][s%4], k = block blk + h blk/2 + s
-size_t relaid_index(size_t k, int n, int blk, int npad) {
-    const int half = blk / 2;
-    const size_t b = k / blk, hh = k % blk / half, s = k % half;
-    return (((b * 2 + hh) * (half / 4) + s / 4) * npad + n) * 4 + s % 4;
-}
-
-struct grad_layout {
-    size_t off[4];   // conv2T, conv3T, conv4T, dense1T (floats)
-    size_t total;
-};
-grad_layout grad_weight_layout(int flat) {
-    grad_layout L;
+// ---- the weights of the transposed layers, from cnn->blob (both in cnn_b_operand_index's layout) ----
+// where conv2T, conv3T, conv4T and dense1T start in grad_blob (floats); returns the floats of all four
+size_t grad_weight_layout(int flat, size_t off[4]) {
     const size_t sizes[4] = {9 * (size_t)C2 * C1, 9 * (size_t)C3 * C2, 9 * (size_t)C4 * C3, (size_t)GK * flat};
-    L.total = 0;
-    for (int i = 0; i < 4; ++i) L.off[i] = L.total, L.total += (sizes[i] + 63) & ~size_t(63);
-    return L;
+    return f2_carve(sizes, 4, 64, off);
 }
 
 // Rotated, transposed convolution kernels and W1T of `cnn`, built on its first gradient call and kept until f2_cnn_destroy
-int grad_weights(f2_ctx* ctx, const f2_cnn* cnn, const float** out) {
+int grad_weights(f2_ctx* ctx, const f2_cnn* cnn, float** out) {
     std::lock_guard<std::mutex> lock(cnn->sets_mu);
     if (cnn->grad_blob) {
         *out = cnn->grad_blob;
         return F2_OK;
     }
-    const grad_layout L = grad_weight_layout(cnn->flat);
-    std::vector<float> dst(L.total, 0.f);
+    size_t off[4];
+    const size_t total = grad_weight_layout(cnn->flat, off);
+    std::vector<float> dst(total, 0.f);
     const int cin[3] = {C1, C2, C3}, cout[3] = {C2, C3, C4};
     std::vector<float> src;
     for (int l = 0; l < 3; ++l) {
@@ -476,26 +457,26 @@ int grad_weights(f2_ctx* ctx, const f2_cnn* cnn, const float** out) {
         src.resize(count);
         F2_HIP(ctx, hipMemcpyAsync(src.data(), cnn->t(2 + 2 * l), sizeof(float) * count, hipMemcpyDeviceToHost, ctx->stream));
         F2_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        float* d = dst.data() + L.off[l];
+        float* d = dst.data() + off[l];
         for (int tap = 0; tap < 9; ++tap)
             for (int ci = 0; ci < cin[l]; ++ci)
                 for (int co = 0; co < cout[l]; ++co)
-                    d[relaid_index((size_t)(8 - tap) * cout[l] + co, ci, cout[l], cin[l])] =
-                        src[relaid_index((size_t)tap * cin[l] + ci, co, cin[l], cout[l])];
+                    d[cnn_b_operand_index((size_t)(8 - tap) * cout[l] + co, ci, cout[l], cin[l])] =
+                        src[cnn_b_operand_index((size_t)tap * cin[l] + ci, co, cin[l], cout[l])];
     }
     {
         const size_t count = (size_t)cnn->flat * D1_NPAD;
         src.resize(count);
         F2_HIP(ctx, hipMemcpyAsync(src.data(), cnn->t(8), sizeof(float) * count, hipMemcpyDeviceToHost, ctx->stream));
         F2_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        float* d = dst.data() + L.off[3];
+        float* d = dst.data() + off[3];
         for (int j = 0; j < cnn->flat; ++j)
-            for (int k = 0; k < D1; ++k) d[relaid_index((size_t)k, j, 64, cnn->flat)] = src[relaid_index((size_t)j, k, D1_KC, D1_NPAD)];
+            for (int k = 0; k < D1; ++k) d[cnn_b_operand_index((size_t)k, j, 64, cnn->flat)] = src[cnn_b_operand_index((size_t)j, k, D1_KC, D1_NPAD)];
     }
     float* blob = nullptr;
-    hipError_t e = hipMalloc((void**)&blob, sizeof(float) * L.total);
-    if (e != hipSuccess) return f2_fail(ctx, F2_ERR_NOMEM, "hipMalloc(%zu) -> %s", sizeof(float) * L.total, hipGetErrorString(e));
-    e = hipMemcpyAsync(blob, dst.data(), sizeof(float) * L.total, hipMemcpyHostToDevice, ctx->stream);
+    hipError_t e = hipMalloc((void**)&blob, sizeof(float) * total);
+    if (e != hipSuccess) return f2_fail(ctx, F2_ERR_NOMEM, "hipMalloc(%zu) -> %s", sizeof(float) * total, hipGetErrorString(e));
+    e = hipMemcpyAsync(blob, dst.data(), sizeof(float) * total, hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     if (e != hipSuccess) {
         (void)hipFree(blob);
@@ -506,39 +487,30 @@ int grad_weights(f2_ctx* ctx, const f2_cnn* cnn, const float** out) {
     return F2_OK;
 }
 
-// the chain's arrays of one chunk, floats per window (each array starts on a 256-byte boundary)
-struct grad_ws {
-    enum { A1, A2, P1, A3, A4, P2, A5, G5, GP2, G3, GP1, G1, GX, SC, COUNT };
-    size_t per[COUNT];
-    size_t bytes_per_window() const {
-        size_t s = 0;
-        for (size_t p : per) s += p;
-        return sizeof(float) * s;
-    }
-};
-grad_ws grad_ws_shape(const Dims& d) {
-    grad_ws w;
-    w.per[grad_ws::A1] = (size_t)d.H1 * d.W1 * C1;
-    w.per[grad_ws::A2] = (size_t)d.H2 * d.W2 * C2;
-    w.per[grad_ws::P1] = (size_t)d.Hp1 * d.Wp1 * C2;
-    w.per[grad_ws::A3] = (size_t)d.Hp1 * d.Wp1 * C3;
-    w.per[grad_ws::A4] = (size_t)d.H4 * d.W4 * C4;
-    w.per[grad_ws::P2] = (size_t)d.flat;
-    w.per[grad_ws::A5] = D1;
-    w.per[grad_ws::G5] = GK;
-    w.per[grad_ws::GP2] = (size_t)d.flat;
-    w.per[grad_ws::G3] = (size_t)d.Hp1 * d.Wp1 * C3;
-    w.per[grad_ws::GP1] = (size_t)d.Hp1 * d.Wp1 * C2;
-    w.per[grad_ws::G1] = (size_t)d.H1 * d.W1 * C1;
-    w.per[grad_ws::GX] = (size_t)d.H1 * d.W1;
-    w.per[grad_ws::SC] = 2;
-    return w;
+// floats per window of the chain's arrays
+void grad_ws_per(const Dims& d, size_t per[f2_grad_chain::COUNT]) {
+    per[f2_grad_chain::A1] = (size_t)d.H1 * d.W1 * C1;
+    per[f2_grad_chain::A2] = (size_t)d.H2 * d.W2 * C2;
+    per[f2_grad_chain::P1] = (size_t)d.Hp1 * d.Wp1 * C2;
+    per[f2_grad_chain::A3] = (size_t)d.Hp1 * d.Wp1 * C3;
+    per[f2_grad_chain::A4] = (size_t)d.H4 * d.W4 * C4;
+    per[f2_grad_chain::P2] = (size_t)d.flat;
+    per[f2_grad_chain::A5] = D1;
+    per[f2_grad_chain::G5] = GK;
+    per[f2_grad_chain::GP2] = (size_t)d.flat;
+    per[f2_grad_chain::G3] = (size_t)d.Hp1 * d.Wp1 * C3;
+    per[f2_grad_chain::GP1] = (size_t)d.Hp1 * d.Wp1 * C2;
+    per[f2_grad_chain::G1] = (size_t)d.H1 * d.W1 * C1;
+    per[f2_grad_chain::GX] = (size_t)d.H1 * d.W1;
+    per[f2_grad_chain::SC] = 2;
 }
-// where the arrays of a chunk of `chunk` windows stand in ctx->grad_ws (float offsets); returns the floats all of them take
-size_t grad_ws_offsets(const grad_ws& shape, int64_t chunk, size_t off[grad_ws::COUNT]) {
-    size_t total = 0;
-    for (int k = 0; k < grad_ws::COUNT; ++k) off[k] = total, total += (shape.per[k] * (size_t)chunk + 63) & ~size_t(63);
-    return total;
+// where the arrays of a chunk of `chunk` windows stand in ctx->grad_ws (float offsets, each on a 256-byte boundary); returns the
+// floats all of them take
+size_t grad_ws_offsets(const Dims& d, int64_t chunk, size_t off[f2_grad_chain::COUNT]) {
+    size_t sizes[f2_grad_chain::COUNT];
+    grad_ws_per(d, sizes);
+    for (size_t& s : sizes) s *= (size_t)chunk;
+    return f2_carve(sizes, f2_grad_chain::COUNT, 64, off);
 }
 
 }  // namespace
@@ -546,209 +518,103 @@ size_t grad_ws_offsets(const grad_ws& shape, int64_t chunk, size_t off[grad_ws::
 // conv4's pooled output (m, flat) and dense1's output (m, 516) of the recorded forward, as the last f2_launch_cnn_input_gradient
 // on this context left them for a call of m <= f2_cnn_grad_chunk windows (valid until the next gradient launch reuses the area)
 void f2_cnn_grad_recorded(const f2_ctx* ctx, const f2_cnn* cnn, int64_t m, const float** p2, const float** a5) {
-    size_t off[grad_ws::COUNT];
-    grad_ws_offsets(grad_ws_shape(make_dims(cnn->rows, cnn->channels)), m, off);
-    *p2 = (const float*)ctx->grad_ws.ptr + off[grad_ws::P2];
-    *a5 = (const float*)ctx->grad_ws.ptr + off[grad_ws::A5];
+    size_t off[f2_grad_chain::COUNT];
+    grad_ws_offsets(make_dims(cnn->rows, cnn->channels), m, off);
+    *p2 = (const float*)ctx->grad_ws.ptr + off[f2_grad_chain::P2];
+    *a5 = (const float*)ctx->grad_ws.ptr + off[f2_grad_chain::A5];
 }
 
 int64_t f2_cnn_grad_chunk(const f2_cnn* cnn) {
-    const grad_ws shape = grad_ws_shape(make_dims(cnn->rows, cnn->channels));
-    const int64_t fit = (GRAD_WS_BYTES - 64 * grad_ws::COUNT * (int64_t)sizeof(float)) / (int64_t)shape.bytes_per_window();
+    size_t per[f2_grad_chain::COUNT], floats = 0;
+    grad_ws_per(make_dims(cnn->rows, cnn->channels), per);
+    for (size_t p : per) floats += p;
+    const int64_t fit = (GRAD_WS_BYTES - 64 * f2_grad_chain::COUNT * (int64_t)sizeof(float)) / (int64_t)(sizeof(float) * floats);
     return std::max<int64_t>(1, std::min<int64_t>(fit, GRAD_WS_CHUNK));
 }
 
-namespace {
-
-// Dropout of a training step (f2_cnn_train.hip): rates, mask seed and step, and the place of the chunk's first window in the batch
-struct train_masks {
-    const double* drop;
-    uint64_t seed, step;
-    int64_t b0;
-};
-
-// The recorded forward from conv1 to the second pool on the m windows at x, every activation kept in arr; with `masks` the
-// inverted dropout goes onto p1 and p2 in place, behind the pools
-int launch_recorded_convs(f2_ctx* ctx, const f2_cnn* cnn, const Dims& d, float* const* arr, const float* x, int64_t m, const train_masks* masks) {
-    unsigned g;
-    F2_TRY(f2_prof_begin(ctx, F2_K_CNN));
-    F2_TRY(grid256(ctx, m * d.H1 * d.W1 * (C1 / 4), &g));
-    hipLaunchKernelGGL(k_conv1_fwd, dim3(g), dim3(256), 0, ctx->stream, x, cnn->t(0), cnn->t(1), arr[grad_ws::A1], d.H1, d.W1, m);
-    F2_HIP(ctx, hipGetLastError());
-    F2_TRY((launch_gconv<C1, C2, 0, ST_PLAIN, EP_RELU, 4, 1>(ctx, arr[grad_ws::A1], nullptr, cnn->t(2), cnn->t(3), arr[grad_ws::A2], d.H1, d.W1, m)));
-    F2_TRY(grid256(ctx, m * d.Hp1 * d.Wp1 * (C2 / 4), &g));
-    hipLaunchKernelGGL(k_pool2x2, dim3(g), dim3(256), 0, ctx->stream, arr[grad_ws::A2], arr[grad_ws::P1], d.H2, d.W2, C2, m);
-    F2_HIP(ctx, hipGetLastError());
-    if (masks) F2_TRY(f2_train_dropout(ctx, arr[grad_ws::P1], m, d.Hp1 * d.Wp1 * C2, 0, masks->b0, masks->drop[0], masks->seed, masks->step));
-    F2_TRY((launch_gconv<C2, C3, 1, ST_PLAIN, EP_RELU, 4, 2>(ctx, arr[grad_ws::P1], nullptr, cnn->t(4), cnn->t(5), arr[grad_ws::A3], d.Hp1, d.Wp1, m)));
-    F2_TRY((launch_gconv<C3, C4, 0, ST_PLAIN, EP_RELU, 4, 2>(ctx, arr[grad_ws::A3], nullptr, cnn->t(6), cnn->t(7), arr[grad_ws::A4], d.Hp1, d.Wp1, m)));
-    F2_TRY(grid256(ctx, m * d.Hp2 * d.Wp2 * (C4 / 4), &g));
-    hipLaunchKernelGGL(k_pool2x2, dim3(g), dim3(256), 0, ctx->stream, arr[grad_ws::A4], arr[grad_ws::P2], d.H4, d.W4, C4, m);
-    F2_HIP(ctx, hipGetLastError());
-    if (masks) F2_TRY(f2_train_dropout(ctx, arr[grad_ws::P2], m, d.flat, 1, masks->b0, masks->drop[1], masks->seed, masks->step));
-    return f2_prof_end(ctx, F2_K_CNN);
+int f2_grad_chain_open(f2_ctx* ctx, const f2_cnn* cnn, int64_t n, bool need_backward, f2_grad_chain* c) {
+    c->ctx = ctx, c->cnn = cnn;
+    c->d = make_dims(cnn->rows, cnn->channels);
+    c->xs = (size_t)c->d.H1 * c->d.W1;
+    c->gw = nullptr;
+    if (need_backward) F2_TRY(grad_weights(ctx, cnn, &c->gw));
+    grad_weight_layout(cnn->flat, c->goff);
+    c->chunk = std::min(n, f2_cnn_grad_chunk(cnn));
+    size_t off[f2_grad_chain::COUNT];
+    F2_TRY(f2_reserve(ctx, ctx->grad_ws, sizeof(float) * grad_ws_offsets(c->d, c->chunk, off)));
+    for (int k = 0; k < f2_grad_chain::COUNT; ++k) c->arr[k] = (float*)ctx->grad_ws.ptr + off[k];
+    return F2_OK;
 }
 
-}  // namespace
+// ---- the steps of the chain: every launch of the recorded forward and of the backward-data pass stands here, once ----
+int f2_grad_chain::conv12(const float* x, int64_t m) const {
+    F2_TRY(launch256(ctx, k_conv1_fwd, m * d.H1 * d.W1 * (C1 / 4), x, cnn->t(0), cnn->t(1), arr[A1], d.H1, d.W1, m));
+    F2_TRY((launch_gconv<C1, C2, 0, ST_PLAIN, EP_RELU, 4, 1>(ctx, arr[A1], nullptr, cnn->t(2), cnn->t(3), arr[A2], d.H1, d.W1, m)));
+    return launch256(ctx, k_pool2x2, m * d.Hp1 * d.Wp1 * (C2 / 4), arr[A2], arr[P1], d.H2, d.W2, C2, m);
+}
+
+int f2_grad_chain::conv34(int64_t m) const {
+    F2_TRY((launch_gconv<C2, C3, 1, ST_PLAIN, EP_RELU, 4, 2>(ctx, arr[P1], nullptr, cnn->t(4), cnn->t(5), arr[A3], d.Hp1, d.Wp1, m)));
+    F2_TRY((launch_gconv<C3, C4, 0, ST_PLAIN, EP_RELU, 4, 2>(ctx, arr[A3], nullptr, cnn->t(6), cnn->t(7), arr[A4], d.Hp1, d.Wp1, m)));
+    return launch256(ctx, k_pool2x2, m * d.Hp2 * d.Wp2 * (C4 / 4), arr[A4], arr[P2], d.H4, d.W4, C4, m);
+}
+
+int f2_grad_chain::dense(int64_t m, bool with_dense2) const {
+    return f2_launch_cnn_dense(ctx, cnn, nullptr, f2_cnn_route(), arr[P2], m, arr[A5], with_dense2 ? arr[SC] : nullptr, nullptr, with_dense2);
+}
+
+int f2_grad_chain::dense1T(int64_t m) const {
+    const int ntiles = d.flat / 32;
+    hipLaunchKernelGGL(k_gemm_rows, dim3((unsigned)((m + GEMM_ROWS - 1) / GEMM_ROWS), (unsigned)((ntiles + GEMM_WAVES - 1) / GEMM_WAVES)),
+                       dim3(GEMM_WAVES * 64), 0, ctx->stream, arr[G5], gw + goff[3], arr[GP2], GK, d.flat, m);
+    F2_HIP(ctx, hipGetLastError());
+    return F2_OK;
+}
+
+int f2_grad_chain::conv4T(int64_t m) const {
+    return launch_gconv<C4, C3, 2, ST_UNPOOL, EP_MASK, 4, 2>(ctx, arr[GP2], arr[A4], gw + goff[2], arr[A3], arr[G3], d.H4, d.W4, m);
+}
+
+int f2_grad_chain::conv3T(int64_t m) const {
+    return launch_gconv<C3, C2, 1, ST_PLAIN, EP_NONE, 2, 1>(ctx, arr[G3], nullptr, gw + goff[1], nullptr, arr[GP1], d.Hp1, d.Wp1, m);
+}
+
+int f2_grad_chain::conv2T(int64_t m) const {
+    return launch_gconv<C2, C1, 2, ST_UNPOOL, EP_MASK, 4, 1>(ctx, arr[GP1], arr[A2], gw + goff[0], arr[A1], arr[G1], d.H2, d.W2, m);
+}
+
+int f2_grad_chain::conv1T(float* G, int64_t m) const {
+    return launch256(ctx, k_conv1_bwd, m * d.H1 * d.W1, arr[G1], cnn->t(0), G, d.H1, d.W1, m);
+}
 
 int f2_launch_cnn_input_gradient(f2_ctx* ctx, const f2_cnn* cnn, const float* d_x, int64_t n, float* d_grad, double* d_profile,
                                  float* d_scores) {
     if (n <= 0) return F2_OK;
-    const Dims d = make_dims(cnn->rows, cnn->channels);
-    const grad_ws shape = grad_ws_shape(d);
     const bool backward = d_grad || d_profile;
-    const float* gw = nullptr;
-    if (backward) F2_TRY(grad_weights(ctx, cnn, &gw));
-    const grad_layout L = grad_weight_layout(cnn->flat);
-    const int64_t chunk = std::min(n, f2_cnn_grad_chunk(cnn));
-    float* arr[grad_ws::COUNT];
-    size_t off[grad_ws::COUNT];
-    F2_TRY(f2_reserve(ctx, ctx->grad_ws, sizeof(float) * grad_ws_offsets(shape, chunk, off)));
-    for (int k = 0; k < grad_ws::COUNT; ++k) arr[k] = (float*)ctx->grad_ws.ptr + off[k];
-    const size_t xs = (size_t)d.H1 * d.W1;
-    unsigned g;
-    for (int64_t s = 0; s < n; s += chunk) {
-        const int64_t m = std::min(chunk, n - s);
-        const float* x = d_x + (size_t)s * xs;
+    f2_grad_chain c;
+    F2_TRY(f2_grad_chain_open(ctx, cnn, n, backward, &c));
+    for (int64_t s = 0; s < n; s += c.chunk) {
+        const int64_t m = std::min(c.chunk, n - s);
+        const float* x = d_x + (size_t)s * c.xs;
         // recorded forward
-        F2_TRY(launch_recorded_convs(ctx, cnn, d, arr, x, m, nullptr));
-        F2_TRY(f2_launch_cnn_dense(ctx, cnn, nullptr, f2_cnn_route(), arr[grad_ws::P2], m, arr[grad_ws::A5], arr[grad_ws::SC], nullptr));
-        if (d_scores)
-            F2_HIP(ctx, hipMemcpyAsync(d_scores + 2 * (size_t)s, arr[grad_ws::SC], sizeof(float) * 2 * (size_t)m, hipMemcpyDeviceToDevice, ctx->stream));
+        F2_TRY(f2_prof_begin(ctx, F2_K_CNN));
+        F2_TRY(c.conv12(x, m));
+        F2_TRY(c.conv34(m));
+        F2_TRY(f2_prof_end(ctx, F2_K_CNN));
+        F2_TRY(c.dense(m, true));
+        float* sc = c.arr[f2_grad_chain::SC];
+        if (d_scores) F2_HIP(ctx, hipMemcpyAsync(d_scores + 2 * (size_t)s, sc, sizeof(float) * 2 * (size_t)m, hipMemcpyDeviceToDevice, ctx->stream));
         if (!backward) continue;
         // backward-data chain
-        float* G = d_grad ? d_grad + (size_t)s * xs : arr[grad_ws::GX];
+        float* G = d_grad ? d_grad + (size_t)s * c.xs : c.arr[f2_grad_chain::GX];
         F2_TRY(f2_prof_begin(ctx, F2_K_CNN));
-        F2_TRY(grid256(ctx, m * GK, &g));
-        hipLaunchKernelGGL(k_grad_dense2, dim3(g), dim3(256), 0, ctx->stream, arr[grad_ws::A5], arr[grad_ws::SC], cnn->t(10), arr[grad_ws::G5], m);
-        F2_HIP(ctx, hipGetLastError());
-        const int ntiles = d.flat / 32;
-        hipLaunchKernelGGL(k_gemm_rows, dim3((unsigned)((m + GEMM_ROWS - 1) / GEMM_ROWS), (unsigned)((ntiles + GEMM_WAVES - 1) / GEMM_WAVES)),
-                           dim3(GEMM_WAVES * 64), 0, ctx->stream, arr[grad_ws::G5], gw + L.off[3], arr[grad_ws::GP2], GK, d.flat, m);
-        F2_HIP(ctx, hipGetLastError());
-        F2_TRY((launch_gconv<C4, C3, 2, ST_UNPOOL, EP_MASK, 4, 2>(ctx, arr[grad_ws::GP2], arr[grad_ws::A4], gw + L.off[2], arr[grad_ws::A3],
-                                                                  arr[grad_ws::G3], d.H4, d.W4, m)));
-        F2_TRY((launch_gconv<C3, C2, 1, ST_PLAIN, EP_NONE, 2, 1>(ctx, arr[grad_ws::G3], nullptr, gw + L.off[1], nullptr, arr[grad_ws::GP1], d.Hp1,
-                                                                 d.Wp1, m)));
-        F2_TRY((launch_gconv<C2, C1, 2, ST_UNPOOL, EP_MASK, 4, 1>(ctx, arr[grad_ws::GP1], arr[grad_ws::A2], gw + L.off[0], arr[grad_ws::A1],
-                                                                  arr[grad_ws::G1], d.H2, d.W2, m)));
-        F2_TRY(grid256(ctx, m * d.H1 * d.W1, &g));
-        hipLaunchKernelGGL(k_conv1_bwd, dim3(g), dim3(256), 0, ctx->stream, arr[grad_ws::G1], cnn->t(0), G, d.H1, d.W1, m);
-        F2_HIP(ctx, hipGetLastError());
-        if (d_profile) {
-            F2_TRY(grid256(ctx, m * d.W1, &g));
-            hipLaunchKernelGGL(k_grad_profile, dim3(g), dim3(256), 0, ctx->stream, G, x, d_profile + 2 * (size_t)s * d.W1, d.H1, d.W1, m);
-            F2_HIP(ctx, hipGetLastError());
-        }
-        F2_TRY(f2_prof_end(ctx, F2_K_CNN));
-    }
-    return F2_OK;
-}
-
-// ---- a training step's gradient (f2_cnn_loss_gradient, f2_trainer_steps; the kernels it adds are f2_cnn_train.hip's) ----
-int f2_cnn_grad_blob(f2_ctx* ctx, const f2_cnn* cnn, float** blob, size_t off[4]) {
-    const float* gw = nullptr;
-    F2_TRY(grad_weights(ctx, cnn, &gw));
-    const grad_layout L = grad_weight_layout(cnn->flat);
-    for (int i = 0; i < 4; ++i) off[i] = L.off[i];
-    *blob = cnn->grad_blob;
-    return F2_OK;
-}
-
-int64_t f2_cnn_loss_gradient_host_chunk(const f2_cnn* cnn) {
-    const int64_t chunk = f2_cnn_grad_chunk(cnn);
-    return std::max<int64_t>(1, GRAD_HOST_CHUNK / chunk) * chunk;
-}
-
-namespace {
-
-// the launch's scratch besides ctx->grad_ws, for chunks of `chunk` windows (byte offsets, each on a 256-byte boundary)
-struct loss_ws {
-    enum { XG, DZ, LOSSW, YG, HIT, PARTIAL, COUNT };
-    size_t off[COUNT], total;
-};
-loss_ws loss_ws_layout(const Dims& d, int64_t chunk) {
-    const size_t bytes[loss_ws::COUNT] = {sizeof(float) * (size_t)d.H1 * d.W1 * (size_t)chunk, sizeof(float) * 2 * (size_t)chunk,
-                                          sizeof(double) * (size_t)chunk, (size_t)chunk, (size_t)chunk, f2_train_partial_bytes(d, chunk)};
-    loss_ws w;
-    w.total = 0;
-    for (int k = 0; k < loss_ws::COUNT; ++k) w.off[k] = w.total, w.total += (bytes[k] + 255) & ~size_t(255);
-    return w;
-}
-
-}  // namespace
-
-size_t f2_cnn_loss_gradient_ws_bytes(const f2_cnn* cnn, int64_t m) {
-    return loss_ws_layout(make_dims(cnn->rows, cnn->channels), std::min(std::max<int64_t>(m, 1), f2_cnn_grad_chunk(cnn))).total;
-}
-
-int f2_launch_cnn_loss_gradient(f2_ctx* ctx, const f2_cnn* cnn, const float* d_x, const uint8_t* d_y, const int64_t* d_index, int64_t n,
-                                int64_t b0, const double drop[3], uint64_t seed, uint64_t step, void* ws, double* d_acc, bool zero_acc,
-                                double* d_tally) {
-    const Dims d = make_dims(cnn->rows, cnn->channels);
-    const f2_train_layout TL = f2_train_tensor_layout(d.flat);
-    if (zero_acc) F2_HIP(ctx, hipMemsetAsync(d_acc, 0, sizeof(double) * TL.total(), ctx->stream));
-    if (n <= 0) return F2_OK;
-    const grad_ws shape = grad_ws_shape(d);
-    const float* gw = nullptr;
-    F2_TRY(grad_weights(ctx, cnn, &gw));
-    const grad_layout L = grad_weight_layout(cnn->flat);
-    const int64_t chunk = std::min(n, f2_cnn_grad_chunk(cnn));
-    float* arr[grad_ws::COUNT];
-    size_t off[grad_ws::COUNT];
-    F2_TRY(f2_reserve(ctx, ctx->grad_ws, sizeof(float) * grad_ws_offsets(shape, chunk, off)));
-    for (int k = 0; k < grad_ws::COUNT; ++k) arr[k] = (float*)ctx->grad_ws.ptr + off[k];
-    const loss_ws W = loss_ws_layout(d, chunk);
-    char* wb = (char*)ws;
-    float* xg = (float*)(wb + W.off[loss_ws::XG]);
-    float* dz = (float*)(wb + W.off[loss_ws::DZ]);
-    double* lossw = (double*)(wb + W.off[loss_ws::LOSSW]);
-    uint8_t* yg = (uint8_t*)(wb + W.off[loss_ws::YG]);
-    uint8_t* hit = (uint8_t*)(wb + W.off[loss_ws::HIT]);
-    const size_t xs = (size_t)d.H1 * d.W1;
-    const float keep[3] = {f2_train_keep_scale(drop[0]), f2_train_keep_scale(drop[1]), f2_train_keep_scale(drop[2])};
-    unsigned g;
-    for (int64_t s = 0; s < n; s += chunk) {
-        const int64_t m = std::min(chunk, n - s);
-        const float* x = d_x + (size_t)s * xs;
-        const uint8_t* y = d_y + s;
-        if (d_index) {
-            F2_TRY(f2_train_gather(ctx, d_x, d_y, d_index + s, m, xs, xg, yg));
-            x = xg, y = yg;
-        }
-        // recorded forward, training mode: the masks go onto p1, p2 and a5 in place
-        const train_masks masks = {drop, seed, step, b0 + s};
-        F2_TRY(launch_recorded_convs(ctx, cnn, d, arr, x, m, &masks));
-        F2_TRY(f2_launch_cnn_dense(ctx, cnn, nullptr, f2_cnn_route(), arr[grad_ws::P2], m, arr[grad_ws::A5], nullptr, nullptr, false));   // dense1 alone
-        F2_TRY(f2_prof_begin(ctx, F2_K_CNN));
-        F2_TRY(f2_train_dropout(ctx, arr[grad_ws::A5], m, D1, 2, b0 + s, drop[2], seed, step));
-        F2_TRY(f2_train_dense2(ctx, arr[grad_ws::A5], cnn->t(10), cnn->t(11), y, m, arr[grad_ws::SC], dz, lossw, hit));
-        F2_TRY(f2_train_tally(ctx, lossw, hit, m, d_tally));
-        // backward-data chain from the loss seed, each layer's weight gradient as soon as its two operands stand
-        f2_train_chunk T;
-        T.d = d, T.m = m, T.gk = GK;
-        T.x = x, T.a1 = arr[grad_ws::A1], T.a2 = arr[grad_ws::A2], T.p1 = arr[grad_ws::P1], T.a3 = arr[grad_ws::A3], T.a4 = arr[grad_ws::A4];
-        T.p2 = arr[grad_ws::P2], T.a5 = arr[grad_ws::A5], T.g5 = arr[grad_ws::G5], T.gp2 = arr[grad_ws::GP2], T.g3 = arr[grad_ws::G3];
-        T.gp1 = arr[grad_ws::GP1], T.g1 = arr[grad_ws::G1], T.dz = dz;
-        T.partial = wb + W.off[loss_ws::PARTIAL], T.acc = d_acc;
-        F2_TRY(f2_train_seed(ctx, arr[grad_ws::A5], dz, cnn->t(10), keep[2], arr[grad_ws::G5], GK, m));
-        F2_TRY(f2_train_wgrad_head(ctx, T));
-        const int ntiles = d.flat / 32;
-        hipLaunchKernelGGL(k_gemm_rows, dim3((unsigned)((m + GEMM_ROWS - 1) / GEMM_ROWS), (unsigned)((ntiles + GEMM_WAVES - 1) / GEMM_WAVES)),
-                           dim3(GEMM_WAVES * 64), 0, ctx->stream, arr[grad_ws::G5], gw + L.off[3], arr[grad_ws::GP2], GK, d.flat, m);
-        F2_HIP(ctx, hipGetLastError());
-        F2_TRY(f2_train_mask_scale(ctx, arr[grad_ws::GP2], arr[grad_ws::P2], keep[1], m * d.flat));
-        F2_TRY(f2_train_wgrad_conv(ctx, T, 4));
-        F2_TRY((launch_gconv<C4, C3, 2, ST_UNPOOL, EP_MASK, 4, 2>(ctx, arr[grad_ws::GP2], arr[grad_ws::A4], gw + L.off[2], arr[grad_ws::A3],
-                                                                  arr[grad_ws::G3], d.H4, d.W4, m)));
-        F2_TRY(f2_train_wgrad_conv(ctx, T, 3));
-        F2_TRY((launch_gconv<C3, C2, 1, ST_PLAIN, EP_NONE, 2, 1>(ctx, arr[grad_ws::G3], nullptr, gw + L.off[1], nullptr, arr[grad_ws::GP1], d.Hp1,
-                                                                 d.Wp1, m)));
-        F2_TRY(f2_train_mask_scale(ctx, arr[grad_ws::GP1], arr[grad_ws::P1], keep[0], m * d.Hp1 * d.Wp1 * C2));
-        F2_TRY(f2_train_wgrad_conv(ctx, T, 2));
-        F2_TRY((launch_gconv<C2, C1, 2, ST_UNPOOL, EP_MASK, 4, 1>(ctx, arr[grad_ws::GP1], arr[grad_ws::A2], gw + L.off[0], arr[grad_ws::A1],
-                                                                  arr[grad_ws::G1], d.H2, d.W2, m)));
-        F2_TRY(f2_train_wgrad_conv(ctx, T, 1));
+        F2_TRY(launch256(ctx, k_grad_dense2, m * GK, c.arr[f2_grad_chain::A5], sc, cnn->t(10), c.arr[f2_grad_chain::G5], m));
+        F2_TRY(c.dense1T(m));
+        F2_TRY(c.conv4T(m));
+        F2_TRY(c.conv3T(m));
+        F2_TRY(c.conv2T(m));
+        F2_TRY(c.conv1T(G, m));
+        if (d_profile) F2_TRY(launch256(ctx, k_grad_profile, m * c.d.W1, G, x, d_profile + 2 * (size_t)s * c.d.W1, c.d.H1, c.d.W1, m));
         F2_TRY(f2_prof_end(ctx, F2_K_CNN));
     }
     return F2_OK;

@@ -1,66 +1,65 @@
-// What f2_cnn_grad.hip (the chain of a training step), f2_cnn_train.hip (its new kernels) and the entry points share.
+// What f2_cnn_grad.hip (the recorded forward and the backward-data chain, step by step) and f2_cnn_train.hip (the training step
+// that interleaves its own kernels with those steps) share.
 #ifndef F2_CNN_TRAIN_H
 #define F2_CNN_TRAIN_H
 
 #include "f2_cnn_dims.h"
+
+constexpr int GK = 576;                    // dense1's 516 outputs padded to whole 64-value chunks: the K of the transposed dense1
+constexpr int64_t GRAD_HOST_CHUNK = 4096;  // windows a host call of the gradient entry points stages at a time
 
 // The 12 tensors of the network in their Keras layouts, one after the other without gaps (f2_cnn_create's order): element offsets,
 // off[12] = the count of all of them. Gradients, master weights and RMSprop accumulators all use it.
 struct f2_train_layout {
     size_t off[13];
     size_t total() const { return off[12]; }
+    size_t count(int i) const { return off[i + 1] - off[i]; }
 };
-f2_train_layout f2_train_tensor_layout(int flat);
+inline f2_train_layout f2_train_tensor_layout(int flat) {
+    const size_t sizes[12] = {9 * C1, C1, 9 * (size_t)C1 * C2, C2, 9 * (size_t)C2 * C3, C3, 9 * (size_t)C3 * C4, C4,
+                              (size_t)flat * D1, D1, (size_t)D1 * D2, D2};
+    f2_train_layout L;
+    L.off[0] = 0;
+    for (int i = 0; i < 12; ++i) L.off[i + 1] = L.off[i] + sizes[i];
+    return L;
+}
 
-// ---- kernels of f2_cnn_train.hip (device pointers, enqueued on ctx->stream) ----
-// a (m, per) *= the inverted-dropout mask of layer `layer` for the windows b0 .. b0 + m - 1 of the call's batch (rate 0: nothing)
-int f2_train_dropout(f2_ctx* ctx, float* a, int64_t m, int per, int layer, int64_t b0, double rate, uint64_t seed, uint64_t step);
-float f2_train_keep_scale(double rate);   // the float32 nearest 1 / (1 - rate)
-// dense2 + softmax on a5 (m, 516) with the labels y: scores (m, 2), dz = softmax - onehot (m, 2), the float64 loss terms and
-// whether the decision (scores[1] > scores[0]) equals the label
-int f2_train_dense2(f2_ctx* ctx, const float* a5, const float* w2, const float* b2, const uint8_t* y, int64_t m, float* scores, float* dz,
-                    double* lossw, uint8_t* hit);
-// tally[0] += the loss terms (float64, fixed order), ((int64_t*)tally)[1] += the hits
-int f2_train_tally(f2_ctx* ctx, const double* lossw, const uint8_t* hit, int64_t m, double* tally);
-// g5 (m, gk) = [a5 > 0] scale (dz0 W2[k][0] + dz1 W2[k][1]), zeros from column 516 on
-int f2_train_seed(f2_ctx* ctx, const float* a5, const float* dz, const float* w2, float scale, float* g5, int gk, int64_t m);
-// g[i] = p[i] > 0 ? g[i] * scale : 0 (the backward factor of a dropout layer, and of the ReLU in front of it)
-int f2_train_mask_scale(f2_ctx* ctx, float* g, const float* p, float scale, int64_t count);
-// xg[j] = x[index[j]], yg[j] = y[index[j]] for j < m, windows of xs floats
-int f2_train_gather(f2_ctx* ctx, const float* x, const uint8_t* y, const int64_t* index, int64_t m, size_t xs, float* xg, uint8_t* yg);
+// `count` pieces of sizes[k] units carved out of one block, each on a boundary of `align` units (a power of two): off[k], returns
+// what all of them take
+inline size_t f2_carve(const size_t* sizes, int count, size_t align, size_t* off) {
+    size_t total = 0;
+    for (int k = 0; k < count; ++k) off[k] = total, total += (sizes[k] + align - 1) & ~(align - 1);
+    return total;
+}
 
-// The weight gradients of one chunk of m windows, added in float64 to acc (f2_train_tensor_layout): every array as the chain left
-// it in ctx->grad_ws. `partial`: f2_train_partial_bytes(d, m) bytes of scratch.
-struct f2_train_chunk {
+// The chain over one chunk of windows: every array the recorded forward and the backward-data pass leave in ctx->grad_ws, and the
+// rotated / transposed weights of the backward layers. Its steps enqueue on ctx->stream; the caller holds the f2_prof brackets.
+struct f2_grad_chain {
+    enum { A1, A2, P1, A3, A4, P2, A5, G5, GP2, G3, GP1, G1, GX, SC, COUNT };
+    f2_ctx* ctx;
+    const f2_cnn* cnn;
     Dims d;
-    int64_t m;
-    int gk;
-    const float *x, *a1, *a2, *p1, *a3, *a4, *p2, *a5, *g5, *gp2, *g3, *gp1, *g1, *dz;
-    void* partial;
-    double* acc;
-};
-size_t f2_train_partial_bytes(const Dims& d, int64_t m);
-int f2_train_wgrad_head(f2_ctx* ctx, const f2_train_chunk& T);    // dense2, dense1 (before the chain overwrites nothing: any time)
-int f2_train_wgrad_conv(f2_ctx* ctx, const f2_train_chunk& T, int layer /* 4, 3, 2, 1 */);
-// out[i] = (float)acc[i]
-int f2_train_round(f2_ctx* ctx, const double* acc, float* out, size_t count);
-// RMSprop as Keras 2.2 runs it, g / m the gradient of the mean loss: a = rho a + (1 - rho) (g / m)^2, p -= lr_t (g / m) / (sqrt(a) + eps)
-int f2_train_rmsprop(f2_ctx* ctx, float* p, float* a, const float* g, size_t count, int64_t m, float lr_t, float rho, float one_minus_rho,
-                     float eps);
-// the master weights w (f2_train_tensor_layout) into cnn->blob's layouts and into the rotated / transposed grad_blob
-int f2_train_relayout(f2_ctx* ctx, const float* w, const f2_cnn* cnn, float* grad_blob, const size_t grad_off[4]);
+    int64_t chunk;       // windows a step takes at most
+    size_t xs;           // floats of a window
+    float* arr[COUNT];   // (chunk, per-window shape) each, on 256-byte boundaries
+    float* gw;           // cnn->grad_blob, built on the network's first backward chain (NULL without need_backward)
+    size_t goff[4];      // conv2T, conv3T, conv4T, dense1T in it (floats)
 
-// ---- f2_cnn_grad.hip ----
-// the rotated / transposed weights of `cnn` (built on first use) and where conv2T, conv3T, conv4T and dense1T start in them
-int f2_cnn_grad_blob(f2_ctx* ctx, const f2_cnn* cnn, float** blob, size_t off[4]);
-// bytes of scratch a loss-gradient launch over at most `m` windows per call needs besides ctx->grad_ws
-size_t f2_cnn_loss_gradient_ws_bytes(const f2_cnn* cnn, int64_t m);
-// Recorded forward in training mode, loss seed, backward-data chain and weight gradients of the m windows x[index[j]] (index NULL:
-// the first m), window j being window b0 + j of the call's batch for the dropout masks. acc (f2_train_tensor_layout doubles) is
-// zeroed first if zero_acc, then += the gradient of the summed loss; tally += {loss sum, hits}. ws: f2_cnn_loss_gradient_ws_bytes.
-int f2_launch_cnn_loss_gradient(f2_ctx* ctx, const f2_cnn* cnn, const float* d_x, const uint8_t* d_y, const int64_t* d_index, int64_t m,
-                                int64_t b0, const double drop[3], uint64_t seed, uint64_t step, void* ws, double* d_acc, bool zero_acc,
-                                double* d_tally);
-int64_t f2_cnn_loss_gradient_host_chunk(const f2_cnn* cnn);   // windows a host call stages at a time: whole chunks of the chain
+    // the steps (f2_cnn_grad.hip), each over the first m <= chunk windows of the arrays.
+    // Recorded forward of the m windows at x: conv1, conv2, pool1 -> A1, A2, P1; conv3, conv4, pool2 -> A3, A4, P2; dense1 -> A5,
+    // with_dense2 also dense2 + softmax -> SC (f2_launch_cnn_dense, which brackets itself)
+    int conv12(const float* x, int64_t m) const;
+    int conv34(int64_t m) const;
+    int dense(int64_t m, bool with_dense2) const;
+    // backward-data: G5 -> GP2 (dense1 transposed), -> G3 (un-pool through A4, conv4 transposed, conv3's mask), -> GP1 (conv3
+    // transposed), -> G1 (un-pool through A2, conv2 transposed, conv1's mask), -> G (m, rows, channels) (conv1 transposed)
+    int dense1T(int64_t m) const;
+    int conv4T(int64_t m) const;
+    int conv3T(int64_t m) const;
+    int conv2T(int64_t m) const;
+    int conv1T(float* G, int64_t m) const;
+};
+// the chain for calls of n windows in chunks of min(n, f2_cnn_grad_chunk); n == 0 reserves nothing and only builds the weights
+int f2_grad_chain_open(f2_ctx* ctx, const f2_cnn* cnn, int64_t n, bool need_backward, f2_grad_chain* c);
 
 #endif

@@ -1,7 +1,7 @@
 // A training step of K4 on the device: f2_cnn_loss_gradient and the f2_trainer_* entry points (include/f2cnn_hip.h).
 //
-// The recorded forward and the backward-data chain are f2_cnn_grad.hip's (f2_launch_cnn_loss_gradient there strings a step
-// together); this file holds what training adds to them:
+// The recorded forward and the backward-data chain are f2_cnn_grad.hip's, as the steps of an f2_grad_chain (f2_cnn_train.h);
+// launch_loss_gradient here strings a step together from them and from what training adds, the kernels of this file:
 //   k_dropout          inverted dropout in place on p1, p2 and a5, masks from Philox4x32-10 (the formula is in the header)
 //   k_dense2_train     dense2 + softmax on the dropped a5, dz = softmax - onehot, the float64 loss term and the hit of every window
 //   k_loss_seed        g5 = [a5 > 0] / keep (dz0 W2[k][0] + dz1 W2[k][1]), padded like k_grad_dense2's
@@ -31,8 +31,6 @@
 #include "f2_philox.h"
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int WGRAD_MAX_PER = 16;       // tasks of 64 pixels per partial sum, at most: 1024 terms
 constexpr int C1_PIX = 256;             // pixels of a k_wgrad_conv1 workgroup: 8 runs of 32
@@ -167,7 +165,6 @@ __global__ __launch_bounds__(256) void k_gather_indexed(const float* __restrict_
 // Workgroup b takes the tasks (b % gpw) per .. + per - 1 of window b / gpw and writes partial[b] = {dW (9, CIN, COUT) | db (COUT)}.
 // MFMA operands: A[ci][k] = patch value of pixel 2 s + k shifted by the tap (lane = ci, conflict-free: a row of 32 floats), B[k][co] =
 // the gradient tile's pixel 2 s + k (lane = co, likewise).
-enum { ST_PLAIN = 0, ST_UNPOOL = 1 };
 template <int CIN, int COUT, int PAD, int STAGE, int COSPLIT>
 __global__ __launch_bounds__(3 * COSPLIT * 64) void k_wgrad_conv(const float* __restrict__ in, const float* __restrict__ g,
                                                                  const float* __restrict__ act, float* __restrict__ partial, int Hin, int Win,
@@ -447,14 +444,6 @@ __global__ __launch_bounds__(256) void k_rmsprop(float* __restrict__ p, float* _
     p[t] = p[t] - lr_t * gm / (sqrtf(an) + eps);
 }
 
-// f2_cnn_create's MFMA B operand of a K x N matrix (f2_cnn.hip: relayout_f32; f2_cnn_grad.hip: relaid_index):
-// [block][h][s/4][n (npad)][s%4], k = block blk + h blk/2 + s
-__device__ __forceinline__ size_t relaid_at(size_t k, int n, int blk, int npad) {
-    const int half = blk / 2;
-    const size_t b = k / blk, hh = k % blk / half, s = k % half;
-    return (((b * 2 + hh) * (half / 4) + s / 4) * npad + n) * 4 + s % 4;
-}
-
 struct relayout_args {
     size_t src[13];    // f2_train_tensor_layout
     size_t dst[12];    // cnn->off
@@ -478,19 +467,17 @@ __global__ __launch_bounds__(256) void k_relayout(const float* __restrict__ w, f
         const int co = (int)(e % cout);
         const size_t k = e / cout;             // tap cin + ci
         const int ci = (int)(k % cin), tap = (int)(k / cin);
-        blob[dst + relaid_at(k, co, cin, cout)] = v;
-        gblob[(l == 2 ? A.gdst[0] : l == 4 ? A.gdst[1] : A.gdst[2]) + relaid_at((size_t)(8 - tap) * cout + co, ci, cout, cin)] = v;
+        blob[dst + cnn_b_operand_index(k, co, cin, cout)] = v;
+        gblob[(l == 2 ? A.gdst[0] : l == 4 ? A.gdst[1] : A.gdst[2]) + cnn_b_operand_index((size_t)(8 - tap) * cout + co, ci, cout, cin)] = v;
     } else if (l == 8) {
         const int k = (int)(e % D1);
         const size_t j = e / D1;
-        blob[dst + relaid_at(j, k, D1_KC, D1_NPAD)] = v;
-        gblob[A.gdst[3] + relaid_at((size_t)k, (int)j, 64, A.flat)] = v;
+        blob[dst + cnn_b_operand_index(j, k, D1_KC, D1_NPAD)] = v;
+        gblob[A.gdst[3] + cnn_b_operand_index((size_t)k, (int)j, 64, A.flat)] = v;
     } else {
         blob[dst + e] = v;
     }
 }
-
-int grid256(f2_ctx* ctx, int64_t threads, unsigned* grid) { return cnn_grid(ctx, (threads + 255) / 256, grid); }
 
 // a window's tasks of 64 pixels in gpw equal shares of per <= WGRAD_MAX_PER: a function of the window shape alone
 struct wgrad_share {
@@ -527,70 +514,24 @@ int launch_wgrad_conv(f2_ctx* ctx, const float* in, const float* g, const float*
     return reduce_partials(ctx, partial, groups, count, count, acc);
 }
 
-}  // namespace
+float keep_scale(double rate) { return (float)(1.0 / (1.0 - rate)); }   // the float32 nearest 1 / (1 - rate)
 
-f2_train_layout f2_train_tensor_layout(int flat) {
-    const size_t sizes[12] = {9 * C1, C1, 9 * (size_t)C1 * C2, C2, 9 * (size_t)C2 * C3, C3, 9 * (size_t)C3 * C4, C4,
-                              (size_t)flat * D1, D1, (size_t)D1 * D2, D2};
-    f2_train_layout L;
-    L.off[0] = 0;
-    for (int i = 0; i < 12; ++i) L.off[i + 1] = L.off[i] + sizes[i];
-    return L;
-}
-
-float f2_train_keep_scale(double rate) { return (float)(1.0 / (1.0 - rate)); }
-
-int f2_train_dropout(f2_ctx* ctx, float* a, int64_t m, int per, int layer, int64_t b0, double rate, uint64_t seed, uint64_t step) {
+// Dropout of a training step: rates, mask seed and step
+struct train_masks {
+    const double* drop;
+    uint64_t seed, step;
+};
+// a (m, per) *= the inverted-dropout mask of layer `layer` for the windows b0 .. b0 + m - 1 of the call's batch (rate 0: nothing)
+int launch_dropout(f2_ctx* ctx, float* a, int64_t m, int per, int layer, int64_t b0, const train_masks& K) {
+    const double rate = K.drop[layer];
     if (rate <= 0.0 || m <= 0) return F2_OK;
     F2_CHECK(ctx, per % 4 == 0, F2_ERR_UNSUPPORTED, "dropout over %d values per window", per);
-    unsigned g;
-    F2_TRY(grid256(ctx, m * (per / 4), &g));
-    hipLaunchKernelGGL(k_dropout, dim3(g), dim3(256), 0, ctx->stream, a, m, per / 4, (uint32_t)layer, b0, rate * 4294967296.0,
-                       f2_train_keep_scale(rate), (uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)step);
-    F2_HIP(ctx, hipGetLastError());
-    return F2_OK;
+    return launch256(ctx, k_dropout, m * (per / 4), a, m, per / 4, (uint32_t)layer, b0, rate * 4294967296.0, keep_scale(rate), (uint32_t)K.seed,
+                     (uint32_t)(K.seed >> 32), (uint32_t)K.step);
 }
 
-int f2_train_dense2(f2_ctx* ctx, const float* a5, const float* w2, const float* b2, const uint8_t* y, int64_t m, float* scores, float* dz,
-                    double* lossw, uint8_t* hit) {
-    unsigned g;
-    F2_TRY(grid256(ctx, m * 8, &g));
-    hipLaunchKernelGGL(k_dense2_train, dim3(g), dim3(256), 0, ctx->stream, a5, w2, b2, y, scores, dz, lossw, hit, m);
-    F2_HIP(ctx, hipGetLastError());
-    return F2_OK;
-}
-
-int f2_train_tally(f2_ctx* ctx, const double* lossw, const uint8_t* hit, int64_t m, double* tally) {
-    hipLaunchKernelGGL(k_train_tally, dim3(1), dim3(256), 0, ctx->stream, lossw, hit, m, tally);
-    F2_HIP(ctx, hipGetLastError());
-    return F2_OK;
-}
-
-int f2_train_seed(f2_ctx* ctx, const float* a5, const float* dz, const float* w2, float scale, float* g5, int gk, int64_t m) {
-    unsigned g;
-    F2_TRY(grid256(ctx, m * gk, &g));
-    hipLaunchKernelGGL(k_loss_seed, dim3(g), dim3(256), 0, ctx->stream, a5, dz, w2, scale, g5, gk, m);
-    F2_HIP(ctx, hipGetLastError());
-    return F2_OK;
-}
-
-int f2_train_mask_scale(f2_ctx* ctx, float* gv, const float* p, float scale, int64_t count) {
-    unsigned g;
-    F2_TRY(grid256(ctx, count, &g));
-    hipLaunchKernelGGL(k_mask_scale, dim3(g), dim3(256), 0, ctx->stream, gv, p, scale, count);
-    F2_HIP(ctx, hipGetLastError());
-    return F2_OK;
-}
-
-int f2_train_gather(f2_ctx* ctx, const float* x, const uint8_t* y, const int64_t* index, int64_t m, size_t xs, float* xg, uint8_t* yg) {
-    unsigned g;
-    F2_TRY(grid256(ctx, m * (int64_t)xs, &g));
-    hipLaunchKernelGGL(k_gather_indexed, dim3(g), dim3(256), 0, ctx->stream, x, y, index, m, (int64_t)xs, xg, yg);
-    F2_HIP(ctx, hipGetLastError());
-    return F2_OK;
-}
-
-size_t f2_train_partial_bytes(const Dims& d, int64_t m) {
+// bytes of partial sums the weight gradients of a chunk of m windows need
+size_t wgrad_partial_bytes(const Dims& d, int64_t m) {
     auto conv = [&](int Ho, int Wo, int cin, int cout) {
         return sizeof(float) * (size_t)(m * wgrad_shares(Ho, Wo).gpw) * (9 * (size_t)cin * cout + cout);
     };
@@ -602,68 +543,174 @@ size_t f2_train_partial_bytes(const Dims& d, int64_t m) {
     return need;
 }
 
-int f2_train_wgrad_head(f2_ctx* ctx, const f2_train_chunk& T) {
-    const f2_train_layout L = f2_train_tensor_layout(T.d.flat);
-    hipLaunchKernelGGL(k_wgrad_head, dim3((HEAD_COLS + 31) / 32), dim3(256), 0, ctx->stream, T.a5, T.dz, T.g5, T.gk, T.m, T.acc + L.off[10],
-                       T.acc + L.off[11], T.acc + L.off[9]);
+// The weight gradients of one chunk of m windows, added in float64 to acc (f2_train_tensor_layout L), from the chain's arrays as they
+// stand when the call is reached; `partial`: wgrad_partial_bytes(d, m) bytes of scratch
+struct wgrad_target {
+    f2_train_layout L;
+    void* partial;
+    double* acc;
+};
+// dense2's kernel and bias, dense1's bias and kernel: once G5 stands
+int wgrad_head(const f2_grad_chain& c, const float* dz, int64_t m, const wgrad_target& T) {
+    f2_ctx* ctx = c.ctx;
+    const float *a5 = c.arr[f2_grad_chain::A5], *g5 = c.arr[f2_grad_chain::G5];
+    hipLaunchKernelGGL(k_wgrad_head, dim3((HEAD_COLS + 31) / 32), dim3(256), 0, ctx->stream, a5, dz, g5, GK, m, T.acc + T.L.off[10],
+                       T.acc + T.L.off[11], T.acc + T.L.off[9]);
     F2_HIP(ctx, hipGetLastError());
-    const int tiles = (T.d.flat / 64) * D1_TILES;
-    const int64_t segs = (T.m + D1_SEG - 1) / D1_SEG;
-    hipLaunchKernelGGL(k_wgrad_dense1, dim3((unsigned)((tiles + 3) / 4), (unsigned)segs), dim3(256), 0, ctx->stream, T.p2, T.g5,
-                       (double*)T.partial, T.d.flat, T.gk, T.m);
+    const int tiles = (c.d.flat / 64) * D1_TILES;
+    const int64_t segs = (m + D1_SEG - 1) / D1_SEG;
+    hipLaunchKernelGGL(k_wgrad_dense1, dim3((unsigned)((tiles + 3) / 4), (unsigned)segs), dim3(256), 0, ctx->stream, c.arr[f2_grad_chain::P2], g5,
+                       (double*)T.partial, c.d.flat, GK, m);
     F2_HIP(ctx, hipGetLastError());
-    const int64_t count = (int64_t)T.d.flat * D1;
-    return reduce_partials(ctx, (const double*)T.partial, segs, count, count, T.acc + L.off[8]);
+    const int64_t count = (int64_t)c.d.flat * D1;
+    return reduce_partials(ctx, (const double*)T.partial, segs, count, count, T.acc + T.L.off[8]);
 }
 
-int f2_train_wgrad_conv(f2_ctx* ctx, const f2_train_chunk& T, int layer) {
-    const f2_train_layout L = f2_train_tensor_layout(T.d.flat);
-    const Dims& d = T.d;
+// conv4 (once GP2 stands), conv3 (G3), conv2 (GP1), conv1 (G1; x: the chunk's windows)
+int wgrad_conv(const f2_grad_chain& c, int layer, const float* x, int64_t m, const wgrad_target& T) {
+    typedef f2_grad_chain A;
+    f2_ctx* ctx = c.ctx;
+    const Dims& d = c.d;
+    float* const* arr = c.arr;
     float* part = (float*)T.partial;
     switch (layer) {
-    case 4: return launch_wgrad_conv<C3, C4, 0, ST_UNPOOL, 2>(ctx, T.a3, T.gp2, T.a4, part, d.Hp1, d.Wp1, T.m, T.acc + L.off[6]);
-    case 3: return launch_wgrad_conv<C2, C3, 1, ST_PLAIN, 1>(ctx, T.p1, T.g3, nullptr, part, d.Hp1, d.Wp1, T.m, T.acc + L.off[4]);
-    case 2: return launch_wgrad_conv<C1, C2, 0, ST_UNPOOL, 1>(ctx, T.a1, T.gp1, T.a2, part, d.H1, d.W1, T.m, T.acc + L.off[2]);
+    case 4: return launch_wgrad_conv<C3, C4, 0, ST_UNPOOL, 2>(ctx, arr[A::A3], arr[A::GP2], arr[A::A4], part, d.Hp1, d.Wp1, m, T.acc + T.L.off[6]);
+    case 3: return launch_wgrad_conv<C2, C3, 1, ST_PLAIN, 1>(ctx, arr[A::P1], arr[A::G3], nullptr, part, d.Hp1, d.Wp1, m, T.acc + T.L.off[4]);
+    case 2: return launch_wgrad_conv<C1, C2, 0, ST_UNPOOL, 1>(ctx, arr[A::A1], arr[A::GP1], arr[A::A2], part, d.H1, d.W1, m, T.acc + T.L.off[2]);
     default: break;
     }
-    const int64_t groups = (T.m * d.H1 * d.W1 + C1_PIX - 1) / C1_PIX;
+    const int64_t groups = (m * d.H1 * d.W1 + C1_PIX - 1) / C1_PIX;
     unsigned g;
     F2_TRY(cnn_grid(ctx, groups, &g));
-    hipLaunchKernelGGL(k_wgrad_conv1, dim3(g), dim3(256), 0, ctx->stream, T.x, T.g1, (double*)T.partial, d.H1, d.W1, T.m);
+    hipLaunchKernelGGL(k_wgrad_conv1, dim3(g), dim3(256), 0, ctx->stream, x, arr[A::G1], (double*)T.partial, d.H1, d.W1, m);
     F2_HIP(ctx, hipGetLastError());
-    return reduce_partials(ctx, (const double*)T.partial, groups, (int64_t)10 * C1, (int64_t)10 * C1, T.acc + L.off[0]);
+    return reduce_partials(ctx, (const double*)T.partial, groups, (int64_t)10 * C1, (int64_t)10 * C1, T.acc + T.L.off[0]);
 }
 
-int f2_train_round(f2_ctx* ctx, const double* acc, float* out, size_t count) {
-    unsigned g;
-    F2_TRY(grid256(ctx, (int64_t)count, &g));
-    hipLaunchKernelGGL(k_round_f32, dim3(g), dim3(256), 0, ctx->stream, acc, out, (int64_t)count);
-    F2_HIP(ctx, hipGetLastError());
-    return F2_OK;
-}
-
-int f2_train_rmsprop(f2_ctx* ctx, float* p, float* a, const float* gr, size_t count, int64_t m, float lr_t, float rho, float one_minus_rho,
-                     float eps) {
-    unsigned g;
-    F2_TRY(grid256(ctx, (int64_t)count, &g));
-    hipLaunchKernelGGL(k_rmsprop, dim3(g), dim3(256), 0, ctx->stream, p, a, gr, (int64_t)count, (float)m, lr_t, rho, one_minus_rho, eps);
-    F2_HIP(ctx, hipGetLastError());
-    return F2_OK;
-}
-
-int f2_train_relayout(f2_ctx* ctx, const float* w, const f2_cnn* cnn, float* grad_blob, const size_t grad_off[4]) {
+// the master weights w (f2_train_tensor_layout) into cnn->blob's layouts and into the rotated / transposed grad_blob
+int launch_relayout(f2_ctx* ctx, const float* w, const f2_cnn* cnn, float* grad_blob, const size_t grad_off[4]) {
     relayout_args A;
     const f2_train_layout L = f2_train_tensor_layout(cnn->flat);
     for (int i = 0; i < 13; ++i) A.src[i] = L.off[i];
     for (int i = 0; i < 12; ++i) A.dst[i] = cnn->off[i];
     for (int i = 0; i < 4; ++i) A.gdst[i] = grad_off[i];
     A.flat = cnn->flat;
-    unsigned g;
-    F2_TRY(grid256(ctx, (int64_t)L.total(), &g));
-    hipLaunchKernelGGL(k_relayout, dim3(g), dim3(256), 0, ctx->stream, w, cnn->blob, grad_blob, A);
-    F2_HIP(ctx, hipGetLastError());
+    return launch256(ctx, k_relayout, (int64_t)L.total(), w, cnn->blob, grad_blob, A);
+}
+
+// the launch's scratch besides ctx->grad_ws, for chunks of `chunk` windows (byte offsets, each on a 256-byte boundary)
+struct loss_ws {
+    enum { XG, DZ, LOSSW, YG, HIT, PARTIAL, COUNT };
+    size_t off[COUNT], total;
+};
+loss_ws loss_ws_layout(const Dims& d, int64_t chunk) {
+    const size_t bytes[loss_ws::COUNT] = {sizeof(float) * (size_t)d.H1 * d.W1 * (size_t)chunk, sizeof(float) * 2 * (size_t)chunk,
+                                          sizeof(double) * (size_t)chunk, (size_t)chunk, (size_t)chunk, wgrad_partial_bytes(d, chunk)};
+    loss_ws w;
+    w.total = f2_carve(bytes, loss_ws::COUNT, 256, w.off);
+    return w;
+}
+// bytes of scratch a loss-gradient launch over at most `m` windows per call needs besides ctx->grad_ws
+size_t loss_gradient_ws_bytes(const f2_cnn* cnn, int64_t m) {
+    return loss_ws_layout(make_dims(cnn->rows, cnn->channels), std::min(std::max<int64_t>(m, 1), f2_cnn_grad_chunk(cnn))).total;
+}
+// windows a host call stages at a time: whole chunks of the chain
+int64_t loss_gradient_host_chunk(const f2_cnn* cnn) {
+    const int64_t chunk = f2_cnn_grad_chunk(cnn);
+    return std::max<int64_t>(1, GRAD_HOST_CHUNK / chunk) * chunk;
+}
+
+// Recorded forward in training mode, loss seed, backward-data chain and weight gradients of the n windows x[index[j]] (index NULL:
+// the first n), window j being window b0 + j of the call's batch for the dropout masks. acc (f2_train_tensor_layout doubles) is
+// zeroed first if zero_acc, then += the gradient of the summed loss; tally += {loss sum, hits}. ws: loss_gradient_ws_bytes.
+// Every line of the loop is a step of the chain (f2_cnn_grad.hip) or a kernel of this file.
+int launch_loss_gradient(f2_ctx* ctx, const f2_cnn* cnn, const float* d_x, const uint8_t* d_y, const int64_t* d_index, int64_t n, int64_t b0,
+                         const train_masks& K, void* ws, double* d_acc, bool zero_acc, double* d_tally) {
+    typedef f2_grad_chain A;
+    wgrad_target T;
+    T.L = f2_train_tensor_layout(cnn->flat), T.acc = d_acc;
+    if (zero_acc) F2_HIP(ctx, hipMemsetAsync(d_acc, 0, sizeof(double) * T.L.total(), ctx->stream));
+    if (n <= 0) return F2_OK;
+    f2_grad_chain c;
+    F2_TRY(f2_grad_chain_open(ctx, cnn, n, true, &c));
+    const Dims& d = c.d;
+    float* const* arr = c.arr;
+    const loss_ws W = loss_ws_layout(d, c.chunk);
+    char* wb = (char*)ws;
+    float* xg = (float*)(wb + W.off[loss_ws::XG]);
+    float* dz = (float*)(wb + W.off[loss_ws::DZ]);
+    double* lossw = (double*)(wb + W.off[loss_ws::LOSSW]);
+    uint8_t* yg = (uint8_t*)(wb + W.off[loss_ws::YG]);
+    uint8_t* hit = (uint8_t*)(wb + W.off[loss_ws::HIT]);
+    T.partial = wb + W.off[loss_ws::PARTIAL];
+    const float keep[3] = {keep_scale(K.drop[0]), keep_scale(K.drop[1]), keep_scale(K.drop[2])};
+    for (int64_t s = 0; s < n; s += c.chunk) {
+        const int64_t m = std::min(c.chunk, n - s);
+        const float* x = d_x + (size_t)s * c.xs;
+        const uint8_t* y = d_y + s;
+        if (d_index) {
+            F2_TRY(launch256(ctx, k_gather_indexed, m * (int64_t)c.xs, d_x, d_y, d_index + s, m, (int64_t)c.xs, xg, yg));
+            x = xg, y = yg;
+        }
+        // recorded forward, training mode: the masks go onto p1, p2 and a5 in place
+        F2_TRY(f2_prof_begin(ctx, F2_K_CNN));
+        F2_TRY(c.conv12(x, m));
+        F2_TRY(launch_dropout(ctx, arr[A::P1], m, d.Hp1 * d.Wp1 * C2, 0, b0 + s, K));
+        F2_TRY(c.conv34(m));
+        F2_TRY(launch_dropout(ctx, arr[A::P2], m, d.flat, 1, b0 + s, K));
+        F2_TRY(f2_prof_end(ctx, F2_K_CNN));
+        F2_TRY(c.dense(m, false));
+        F2_TRY(f2_prof_begin(ctx, F2_K_CNN));
+        F2_TRY(launch_dropout(ctx, arr[A::A5], m, D1, 2, b0 + s, K));
+        F2_TRY(launch256(ctx, k_dense2_train, m * 8, arr[A::A5], cnn->t(10), cnn->t(11), y, arr[A::SC], dz, lossw, hit, m));
+        hipLaunchKernelGGL(k_train_tally, dim3(1), dim3(256), 0, ctx->stream, lossw, hit, m, d_tally);
+        F2_HIP(ctx, hipGetLastError());
+        // backward-data chain from the loss seed, each layer's weight gradient as soon as its two operands stand
+        F2_TRY(launch256(ctx, k_loss_seed, m * GK, arr[A::A5], dz, cnn->t(10), keep[2], arr[A::G5], GK, m));
+        F2_TRY(wgrad_head(c, dz, m, T));
+        F2_TRY(c.dense1T(m));
+        F2_TRY(launch256(ctx, k_mask_scale, m * d.flat, arr[A::GP2], arr[A::P2], keep[1], m * d.flat));
+        F2_TRY(wgrad_conv(c, 4, x, m, T));
+        F2_TRY(c.conv4T(m));
+        F2_TRY(wgrad_conv(c, 3, x, m, T));
+        F2_TRY(c.conv3T(m));
+        F2_TRY(launch256(ctx, k_mask_scale, m * d.Hp1 * d.Wp1 * C2, arr[A::GP1], arr[A::P1], keep[0], m * d.Hp1 * d.Wp1 * C2));
+        F2_TRY(wgrad_conv(c, 2, x, m, T));
+        F2_TRY(c.conv2T(m));
+        F2_TRY(wgrad_conv(c, 1, x, m, T));
+        F2_TRY(f2_prof_end(ctx, F2_K_CNN));
+    }
     return F2_OK;
 }
+
+// the 12 tensors between 12 arrays (`tensors`) and one array in layout L (`flat`), on the stream: into `flat` or out of it
+hipError_t copy_tensors(f2_ctx* ctx, const f2_train_layout& L, float* flat, float* const* tensors, bool into_flat, hipMemcpyKind kind) {
+    hipError_t e = hipSuccess;
+    for (int i = 0; e == hipSuccess && i < 12; ++i)
+        e = hipMemcpyAsync(into_flat ? flat + L.off[i] : tensors[i], into_flat ? tensors[i] : flat + L.off[i], sizeof(float) * L.count(i), kind,
+                           ctx->stream);
+    return e;
+}
+
+// {loss sum, hits} of a tally on the device, as host values: waits for the stream
+int read_tally(f2_ctx* ctx, const double* d_tally, double* loss_sum_or_null, int64_t* correct_or_null) {
+    double t[2];
+    F2_HIP(ctx, hipMemcpyAsync(t, d_tally, sizeof(t), hipMemcpyDeviceToHost, ctx->stream));
+    F2_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (loss_sum_or_null) *loss_sum_or_null = t[0];
+    if (correct_or_null) memcpy(correct_or_null, &t[1], sizeof(int64_t));
+    return F2_OK;
+}
+
+int check_drop(f2_ctx* ctx, const double* drop) {
+    F2_CHECK(ctx, drop, F2_ERR_INVALID, "drop is NULL");
+    for (int l = 0; l < 3; ++l) F2_CHECK(ctx, drop[l] >= 0.0 && drop[l] < 1.0, F2_ERR_INVALID, "dropout rate %d is %g, not in [0, 1)", l, drop[l]);
+    return F2_OK;
+}
+
+size_t align256(size_t b) { return (b + 255) & ~size_t(255); }
+
+}  // namespace
 
 // ---- entry points ----
 struct f2_trainer {
@@ -679,18 +726,6 @@ struct f2_trainer {
     uint64_t seed = 0;
     int64_t iterations = 0;
 };
-
-namespace {
-
-int check_drop(f2_ctx* ctx, const double* drop) {
-    F2_CHECK(ctx, drop, F2_ERR_INVALID, "drop is NULL");
-    for (int l = 0; l < 3; ++l) F2_CHECK(ctx, drop[l] >= 0.0 && drop[l] < 1.0, F2_ERR_INVALID, "dropout rate %d is %g, not in [0, 1)", l, drop[l]);
-    return F2_OK;
-}
-
-size_t align256(size_t b) { return (b + 255) & ~size_t(255); }
-
-}  // namespace
 
 extern "C" {
 
@@ -710,9 +745,9 @@ int f2_cnn_loss_gradient(f2_ctx* ctx, const f2_cnn* cnn, const float* x, const u
         for (int i = 0; i < 12; ++i) F2_CHECK(ctx, grads_or_null[i], F2_ERR_INVALID, "gradient tensor %d is NULL", i);
     const f2_train_layout L = f2_train_tensor_layout(cnn->flat);
     const size_t T = L.total(), xs = (size_t)cnn->rows * cnn->channels;
-    const int64_t piece = host ? f2_cnn_loss_gradient_host_chunk(cnn) : std::max<int64_t>(m, 1);
+    const int64_t piece = host ? loss_gradient_host_chunk(cnn) : std::max<int64_t>(m, 1);
     // scratch of the call: [the launch's | float64 gradient | {loss sum, hits} | float32 gradient]
-    const size_t ws_bytes = align256(f2_cnn_loss_gradient_ws_bytes(cnn, std::min<int64_t>(std::max<int64_t>(m, 1), piece)));
+    const size_t ws_bytes = align256(loss_gradient_ws_bytes(cnn, std::min<int64_t>(std::max<int64_t>(m, 1), piece)));
     const size_t at_tally = ws_bytes + align256(sizeof(double) * T), at_g32 = at_tally + 256;
     F2_TRY(f2_reserve(ctx, ctx->train_ws, at_g32 + sizeof(float) * T));
     char* base = (char*)ctx->train_ws.ptr;
@@ -746,23 +781,15 @@ int f2_cnn_loss_gradient(f2_ctx* ctx, const f2_cnn* cnn, const float* x, const u
         } else if (!index_or_null) {
             d_x = x + (size_t)s * xs, d_y = y + s;
         }
-        F2_TRY(f2_launch_cnn_loss_gradient(ctx, cnn, d_x, d_y, d_index, mm, s, drop, seed, step, base, d_acc, false, d_tally));
+        F2_TRY(launch_loss_gradient(ctx, cnn, d_x, d_y, d_index, mm, s, {drop, seed, step}, base, d_acc, false, d_tally));
         if (host) F2_HIP(ctx, hipStreamSynchronize(ctx->stream));
     }
     if (grads_or_null) {
-        F2_TRY(f2_train_round(ctx, d_acc, d_g32, T));
-        for (int i = 0; i < 12; ++i)
-            F2_HIP(ctx, hipMemcpyAsync(grads_or_null[i], d_g32 + L.off[i], sizeof(float) * (L.off[i + 1] - L.off[i]),
-                                       host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, ctx->stream));
+        F2_TRY(launch256(ctx, k_round_f32, (int64_t)T, d_acc, d_g32, (int64_t)T));
+        F2_HIP(ctx, copy_tensors(ctx, L, d_g32, grads_or_null, false, host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice));
     }
     // the two tallies are host values in both memory spaces: the call waits for them
-    if (loss_sum_or_null || correct_or_null) {
-        double t[2];
-        F2_HIP(ctx, hipMemcpyAsync(t, d_tally, sizeof(t), hipMemcpyDeviceToHost, ctx->stream));
-        F2_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        if (loss_sum_or_null) *loss_sum_or_null = t[0];
-        if (correct_or_null) memcpy(correct_or_null, &t[1], sizeof(int64_t));
-    }
+    if (loss_sum_or_null || correct_or_null) F2_TRY(read_tally(ctx, d_tally, loss_sum_or_null, correct_or_null));
     return f2_host_wait(ctx, mem_space);
 }
 
@@ -787,11 +814,14 @@ int f2_trainer_create(f2_ctx* ctx, const float* const* tensors, int rows, int ch
     if (rc == F2_OK) rc = f2_reserve(ctx, t->a, sizeof(float) * T);
     if (rc == F2_OK) rc = f2_reserve(ctx, t->g, sizeof(float) * T);
     if (rc == F2_OK) rc = f2_reserve(ctx, t->acc, align256(sizeof(double) * T) + 256);
-    if (rc == F2_OK) rc = f2_cnn_grad_blob(ctx, cnn, &t->grad_blob, t->grad_off);
+    f2_grad_chain c;   // (of no windows: the rotated / transposed weights alone)
+    if (rc == F2_OK) rc = f2_grad_chain_open(ctx, cnn, 0, true, &c);
     hipError_t e = hipSuccess;
-    for (int i = 0; rc == F2_OK && e == hipSuccess && i < 12; ++i)
-        e = hipMemcpyAsync((float*)t->w.ptr + t->L.off[i], tensors[i], sizeof(float) * (t->L.off[i + 1] - t->L.off[i]), hipMemcpyHostToDevice,
-                           ctx->stream);
+    if (rc == F2_OK) {
+        t->grad_blob = c.gw;
+        for (int i = 0; i < 4; ++i) t->grad_off[i] = c.goff[i];
+        e = copy_tensors(ctx, t->L, (float*)t->w.ptr, const_cast<float* const*>(tensors), true, hipMemcpyHostToDevice);
+    }
     if (rc == F2_OK && e == hipSuccess) e = hipMemsetAsync(t->a.ptr, 0, sizeof(float) * T, ctx->stream);
     if (rc == F2_OK && e == hipSuccess) e = hipMemsetAsync(t->g.ptr, 0, sizeof(float) * T, ctx->stream);
     if (rc == F2_OK && e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
@@ -850,29 +880,25 @@ int f2_trainer_steps(f2_ctx* ctx, f2_trainer* t, const int64_t* order, int64_t c
     if (count > 0) {
         F2_TRY(f2_reserve(ctx, t->order, sizeof(int64_t) * (size_t)count));
         F2_TRY(f2_upload_async(ctx, t->order.ptr, order, sizeof(int64_t) * (size_t)count));
-        F2_TRY(f2_reserve(ctx, ctx->train_ws, f2_cnn_loss_gradient_ws_bytes(t->cnn, std::min<int64_t>(count, batch))));
+        F2_TRY(f2_reserve(ctx, ctx->train_ws, loss_gradient_ws_bytes(t->cnn, std::min<int64_t>(count, batch))));
         F2_HIP(ctx, hipMemsetAsync(d_tally, 0, 16, ctx->stream));
     }
     // the steps go onto the stream back to back; one wait at the end
     for (int64_t s = 0; s < count; s += batch) {
         const int64_t mb = std::min<int64_t>(batch, count - s);
-        F2_TRY(f2_launch_cnn_loss_gradient(ctx, t->cnn, (const float*)t->x.ptr, (const uint8_t*)t->y.ptr, (const int64_t*)t->order.ptr + s, mb, 0,
-                                           t->drop, t->seed, (uint64_t)t->iterations, ctx->train_ws.ptr, d_acc, true, d_tally));
-        F2_TRY(f2_train_round(ctx, d_acc, (float*)t->g.ptr, T));
+        F2_TRY(launch_loss_gradient(ctx, t->cnn, (const float*)t->x.ptr, (const uint8_t*)t->y.ptr, (const int64_t*)t->order.ptr + s, mb, 0,
+                                    {t->drop, t->seed, (uint64_t)t->iterations}, ctx->train_ws.ptr, d_acc, true, d_tally));
+        F2_TRY(launch256(ctx, k_round_f32, (int64_t)T, d_acc, (float*)t->g.ptr, (int64_t)T));
+        // RMSprop as Keras 2.2 runs it, g / mb the gradient of the mean loss: a = rho a + (1 - rho) (g / mb)^2, p -= lr_t (g / mb) / (sqrt(a) + eps)
         const double lr_t = t->lr / (1.0 + t->decay * (double)t->iterations);
-        F2_TRY(f2_train_rmsprop(ctx, (float*)t->w.ptr, (float*)t->a.ptr, (const float*)t->g.ptr, T, mb, (float)lr_t, (float)t->rho,
-                                (float)(1.0 - t->rho), (float)t->eps));
-        F2_TRY(f2_train_relayout(ctx, (const float*)t->w.ptr, t->cnn, t->grad_blob, t->grad_off));
+        F2_TRY(launch256(ctx, k_rmsprop, (int64_t)T, (float*)t->w.ptr, (float*)t->a.ptr, (const float*)t->g.ptr, (int64_t)T, (float)mb, (float)lr_t,
+                         (float)t->rho, (float)(1.0 - t->rho), (float)t->eps));
+        F2_TRY(launch_relayout(ctx, (const float*)t->w.ptr, t->cnn, t->grad_blob, t->grad_off));
         ++t->iterations;
     }
-    double tl[2] = {0.0, 0.0};
-    if (count > 0) {
-        F2_HIP(ctx, hipMemcpyAsync(tl, d_tally, sizeof(tl), hipMemcpyDeviceToHost, ctx->stream));
-        F2_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    }
-    if (loss_sum_or_null) *loss_sum_or_null = tl[0];
-    if (correct_or_null) memcpy(correct_or_null, &tl[1], sizeof(int64_t));
-    return F2_OK;
+    if (loss_sum_or_null) *loss_sum_or_null = 0.0;
+    if (correct_or_null) *correct_or_null = 0;
+    return count > 0 ? read_tally(ctx, d_tally, loss_sum_or_null, correct_or_null) : F2_OK;
 }
 
 int f2_trainer_get(f2_ctx* ctx, const f2_trainer* t, int what, float* const* tensors) {
@@ -882,10 +908,8 @@ int f2_trainer_get(f2_ctx* ctx, const f2_trainer* t, int what, float* const* ten
              "what = %d is not one of F2_TRAINER_*", what);
     F2_CHECK(ctx, tensors, F2_ERR_INVALID, "tensors is NULL");
     for (int i = 0; i < 12; ++i) F2_CHECK(ctx, tensors[i], F2_ERR_INVALID, "tensor %d is NULL", i);
-    const float* src = (const float*)(what == F2_TRAINER_WEIGHTS ? t->w.ptr : what == F2_TRAINER_ACCUMULATORS ? t->a.ptr : t->g.ptr);
-    for (int i = 0; i < 12; ++i)
-        F2_HIP(ctx, hipMemcpyAsync(tensors[i], src + t->L.off[i], sizeof(float) * (t->L.off[i + 1] - t->L.off[i]), hipMemcpyDeviceToHost,
-                                   ctx->stream));
+    float* src = (float*)(what == F2_TRAINER_WEIGHTS ? t->w.ptr : what == F2_TRAINER_ACCUMULATORS ? t->a.ptr : t->g.ptr);
+    F2_HIP(ctx, copy_tensors(ctx, t->L, src, tensors, false, hipMemcpyDeviceToHost));
     F2_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return F2_OK;
 }

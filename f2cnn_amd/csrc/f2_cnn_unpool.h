@@ -1,9 +1,14 @@
-// The un-pool rule of the backward pass, shared by the backward-data chain (f2_cnn_grad.hip) and the weight gradients
-// (f2_cnn_train.hip).
+// What the kernels of the backward-data chain (f2_cnn_grad.hip) and of the weight gradients (f2_cnn_train.hip) share on the
+// device: the accumulator type, the staging and epilogue switches of their templates, and the un-pool rule.
 #ifndef F2_CNN_UNPOOL_H
 #define F2_CNN_UNPOOL_H
 
 #include <hip/hip_runtime.h>
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+enum { ST_PLAIN = 0, ST_UNPOOL = 1 };               // how a kernel stages its gradient: as it stands / un-pooled on the way
+enum { EP_RELU = 0, EP_MASK = 1, EP_NONE = 2 };     // k_gconv's epilogue
 
 // the gradient a pooled cell hands to element `me` (0 .. 3 in (row, column) order) of its block: all of it to the first maximal
 // element where that maximum is > 0 (the ReLU in front of the pool passes it), nothing otherwise

@@ -18,7 +18,14 @@ f2_eval_batch_strided at hop 1 and 160, f2_eval_noise_sweep with 2 levels and a 
 f2_envelope_picture / f2_gammatonegram_batch with both pools, f2_resample_batch at 3 : 2 and at the identity. The three sweeps
 (profiles/r23_a_old_new_identity.txt): f2_eval_noise_sweep, f2_eval_cutoff_sweep and f2_eval_reverb_sweep with K = 2 on utterances
 of 3000, 1000 (shorter than a window) and 2100 samples, int16 and float64, hop 16 and hop = STEP, host and device memory, the
-optional outputs given and left out; levels, scores, labels, window offsets, sigma and stats in the digest."""
+optional outputs given and left out; levels, scores, labels, window offsets, sigma and stats in the digest. The backward pass and
+the training step (profiles/r28_a_old_new_identity.txt), host and device memory, seeds fixed here: f2_cnn_input_gradient on an
+11 x 10 network and 1024 + 70 windows (two chunks of the chain) and on 13 x 40 and 11 x 67 networks and 193 windows, all three
+outputs and the scores alone; f2_cnn_layers on the recorded route; f2_cnn_loss_gradient on 1094 windows of 11 x 10 without and
+with dropout, without an index and with a permutation that repeats, on 4100 windows from host memory (two host pieces), on none,
+and on 193 windows of 13 x 40 - the 12 gradients, the loss sum and the hits in the digest; f2_trainer_steps twice over 70 windows
+in batches of 32 - weights, accumulators, last gradient, loss, hits and iterations after each call; f2_eval_saliency_batch on the
+case of tests/test_gpu_saliency_placement.py."""
 import hashlib, json, os, sys
 import numpy as np
 
@@ -200,6 +207,99 @@ def sweep_cases(ctx, res):
     print("sweeps done", flush=True)
 
 
+def grad_cases(ctx, res):
+    from f2cnn_amd import _lib
+    from f2cnn_amd.gammatone import filters
+    from f2cnn_amd.model import F2CNNModel, tensor_shapes
+    from f2cnn_amd.trainer import Trainer
+    import f2cnn_oracle as orc
+    MEMS = (("host", _lib.MEM_HOST), ("device", _lib.MEM_DEVICE))
+    DROP = (0.25, 0.25, 0.5)
+
+    def windows(seed, n, rows, ch):
+        rng = np.random.default_rng(seed)
+        return rng.random((n, rows, ch)).astype(np.float32), rng.integers(0, 2, n).astype(np.uint8)
+
+    # f2_cnn_input_gradient: 1024 + 70 windows cross the chain's chunk; 13 x 40 has an odd row count after conv2, 11 x 67 an odd width
+    for rows, ch, n in ((R, 10, 1094), (13, 40, 193), (R, 67, 193)):
+        h = F2CNNModel.glorot(7, rows, ch, zero_bias=False).handle(ctx)
+        x, _ = windows(rows * ch + n, n, rows, ch)
+        for mname, mem in MEMS:
+            for oname, full in (("gradient, profile and scores", True), ("scores alone", False)):
+                G, prof, sc = np.zeros((n, rows, ch), np.float32), np.zeros((n, ch, 2)), np.zeros((n, 2), np.float32)
+                outs = [G, prof, sc] if full else [None, None, sc]
+                if mem == _lib.MEM_HOST:
+                    ctx.cnn_input_gradient(h, x, n, *outs, mem)
+                else:
+                    on_device(ctx, [x] + outs, lambda dx, dg, dp, ds: ctx.cnn_input_gradient(h, dx, n, dg, dp, ds, mem))
+                res[f"f2_cnn_input_gradient: {rows} x {ch}, {n} windows, {oname}, {mname} memory"] = digest(*[a for a in outs if a is not None])
+    small = F2CNNModel.glorot(7, R, 10, zero_bias=False)
+    h = small.handle(ctx)
+    flat = tensor_shapes(R, 10)["dense1_w"][0]
+    x, _ = windows(193, 193, R, 10)
+    for mname, mem in MEMS:
+        outs = [np.zeros((193, flat), np.float32), np.zeros((193, 516), np.float32), np.zeros((193, 2), np.float32)]
+        if mem == _lib.MEM_HOST:
+            ctx.cnn_layers(h, x, 193, _lib.CNN_ROUTES["recorded"], *outs, mem)
+        else:
+            on_device(ctx, [x] + outs, lambda dx, dp, d1, ds: ctx.cnn_layers(h, dx, 193, _lib.CNN_ROUTES["recorded"], dp, d1, ds, mem))
+        res[f"f2_cnn_layers: recorded route, {R} x 10, 193 windows, {mname} memory"] = digest(*outs)
+    print("input gradient done", flush=True)
+
+    def loss_gradient(name, model, x, y, index, m, drop, mems=MEMS):
+        shapes = list(tensor_shapes(model.rows, model.channels).values())
+        hm = model.handle(ctx)
+        for mname, mem in mems:
+            grads = [np.full(s, 7.0, np.float32) for s in shapes]
+            if mem == _lib.MEM_HOST:
+                loss, hits = ctx.cnn_loss_gradient(hm, x, y, index, m, drop, 99, 3, grads, mem)
+            else:
+                loss, hits = on_device(ctx, [x, y, index] + grads, lambda dx, dy, di, *dg: ctx.cnn_loss_gradient(
+                    hm, dx, dy, di, m, drop, 99, 3, list(dg), mem))
+            res[f"f2_cnn_loss_gradient: {name}, {mname} memory"] = digest(*grads, np.float64(loss), np.int64(hits))
+
+    n = 1094
+    x, y = windows(11, n, R, 10)
+    index = np.random.default_rng(12).permutation(n).astype(np.int64)
+    index[5::97] = index[3]                                   # (repeats)
+    for drop in ((0.0, 0.0, 0.0), DROP):
+        for iname, idx in (("no index", None), ("index a permutation with repeats", index)):
+            loss_gradient(f"{R} x 10, {n} windows, dropout {drop}, {iname}", small, x, y, idx, n, drop)
+    loss_gradient(f"{R} x 10, m = 0", small, x[:1], y[:1], None, 0, DROP)
+    xl, yl = windows(13, 4100, R, 10)
+    loss_gradient(f"{R} x 10, 4100 windows (two host pieces), dropout {DROP}", small, xl, yl, None, 4100, DROP, MEMS[:1])
+    x, y = windows(14, 193, 13, 40)
+    loss_gradient(f"13 x 40, 193 windows, dropout {DROP}", F2CNNModel.glorot(7, 13, 40, zero_bias=False), x, y, None, 193, DROP)
+    print("loss gradient done", flush=True)
+
+    # f2_trainer_steps: 70 windows in batches of 32 (the last one of 6), twice
+    x, y = windows(15, 70, R, 10)
+    tr = Trainer(small, lr=1e-3, decay=1e-6, drop=DROP, seed=5, ctx=ctx)
+    tr.set_data(x, y)
+    for call in (1, 2):
+        loss, hits = tr.steps(np.random.default_rng(15 + call).permutation(70), 32)
+        res[f"f2_trainer_steps: {R} x 10, 70 windows, batch 32, call {call}"] = digest(
+            *tr.weights().values(), *tr.accumulators().values(), *tr.gradient().values(), np.float64(loss), np.int64(hits), np.int64(tr.iterations))
+    tr.close()
+
+    # f2_eval_saliency_batch: the case of tests/test_gpu_saliency_placement.py
+    lens, CS, W, hop = [2500, 1761, 3001, 1700], 16, 40, 16
+    B = len(lens)
+    coefs = np.ascontiguousarray(filters.make_erb_filters(16000, filters.centre_freqs(16000, CS, 100)))
+    offs = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+    wave = np.concatenate([orc.synth_utterance(3100 + i, k) for i, k in enumerate(lens)]).astype(np.int16)
+    nwin = sum(_lib.strided_window_count(k, RADIUS, STEP, hop) for k in lens)
+    h = F2CNNModel.glorot(7, R, CS, zero_bias=False).handle(ctx)
+    for mname, mem in MEMS:
+        outs = [np.zeros((B, CS, W), np.uint8), np.zeros((B, CS, W, 3)), np.zeros((B, CS, 3)), np.zeros((nwin, 2), np.float32),
+                np.zeros(nwin, np.uint8)]
+        call = lambda w, lv, mp, sm, sc, lb: ctx.eval_saliency_batch(h, w, _lib.WAVE_I16, offs, coefs, B, CS, True, 50.0, _lib.FFT_F32, RADIUS, STEP,
+                                                                    hop, None, W, 0, lv, mp, sm, sc, lb, mem)
+        wo, rng = call(wave, *outs) if mem == _lib.MEM_HOST else on_device(ctx, [wave] + outs, call)
+        res[f"f2_eval_saliency_batch: 4 utterances, 16 channels, hop 16, {mname} memory"] = digest(*outs, wo, rng)
+    print("gradient cases done", flush=True)
+
+
 def keep_arrays(keep, key, arrays, lens=None, C=None, envelopes=()):
     """the outputs of one case under KEEP_DIR: a<i>.npy each; `envelopes` = the indices of the arrays laid out
     [utterance][channel][sample] for utterances of `lens` samples and C channels"""
@@ -285,6 +385,7 @@ def run(lib, out, keep=None):
     cnn_cases(ctx, res)
     entry_cases(ctx, res)
     sweep_cases(ctx, res)
+    grad_cases(ctx, res)
     ctx.close()
     with open(out, "w") as f:
         json.dump(res, f, indent=1)
