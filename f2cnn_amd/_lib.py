@@ -104,6 +104,12 @@ SIGNATURES = {
     "f2_trainer_steps": (_i, [_vp, _vp, _vp, _i64, _i, _vp, _vp]),
     "f2_trainer_get": (_i, [_vp, _vp, _i, _P(_vp)]),
     "f2_trainer_get_info": (_i, [_vp, _vp, C.c_char_p, _P(_d)]),
+    "f2_noise_pick": (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _vp, C.c_uint32, C.c_uint64, _vp, _vp, _i]),
+    "f2_input_batch_noisy": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i, _i, _d, _i, _vp, _vp, _i, _i, _i, _vp, _i, _vp, C.c_uint32, C.c_uint64,
+                                  _vp, _i]),
+    "f2_trainer_set_waves": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _d, _i, _vp, _vp, _vp, _i, _i, _i]),
+    "f2_trainer_render": (_i, [_vp, _vp, _vp, _i, _vp, C.c_uint64]),
+    "f2_trainer_get_windows": (_i, [_vp, _vp, _i64, _i64, _vp, _vp]),
 }
 TRAINER_WHAT = {"weights": 0, "accumulators": 1, "gradient": 2}   # F2_TRAINER_* of f2_trainer_get
 
@@ -354,6 +360,32 @@ class Context:
         self.check(self.lib.f2_input_batch(self.handle, _ptr(wave), wave_dtype, _ptr(offsets), _ptr(coefs), int(B), Cn,
                                            int(bool(lpf)), float(cutoff), precision, _ptr(center_offsets), _ptr(centers),
                                            radius, step, int(bool(normalize)), _ptr(windows), mem_space))
+
+    def noise_pick(self, wave, wave_dtype, offsets, B, snr_db, level_of, first_utterance, seed, noisy, mem_space, sigma=None):
+        """The batch with one noise level per utterance (see f2_noise_pick): utterance b at snr_db[level_of[b]], or clean where
+        level_of[b] == len(snr_db); level_of None: all clean. wave / noisy are numpy arrays or device pointers, by mem_space.
+        sigma: True for a new (B) float64 array, an array to fill, or None. Returns sigma (or None)."""
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        snr, lev = _noise_levels(snr_db, level_of)
+        if sigma is True:
+            sigma = np.zeros(int(B), np.float64)
+        self.check(self.lib.f2_noise_pick(self.handle, _ptr(wave), wave_dtype, _ptr(offsets), int(B), _ptr(snr) if len(snr) else None,
+                                          len(snr), _ptr(lev), int(first_utterance), int(seed) & (2 ** 64 - 1), _ptr(noisy), _ptr(sigma),
+                                          mem_space))
+        return sigma
+
+    def input_batch_noisy(self, wave, wave_dtype, offsets, coefs, B, Cn, lpf, cutoff, precision, center_offsets, centers, radius,
+                          step, normalize, snr_db, level_of, first_utterance, seed, windows, mem_space):
+        """input_batch on the batch as noise_pick leaves it, the noisy waveform never leaving the device; see
+        f2_input_batch_noisy."""
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        center_offsets = np.ascontiguousarray(center_offsets, dtype=np.int64)
+        centers = np.ascontiguousarray(centers, dtype=np.int64)
+        snr, lev = _noise_levels(snr_db, level_of)
+        self.check(self.lib.f2_input_batch_noisy(self.handle, _ptr(wave), wave_dtype, _ptr(offsets), _ptr(coefs), int(B), Cn,
+                                                 int(bool(lpf)), float(cutoff), precision, _ptr(center_offsets), _ptr(centers),
+                                                 radius, step, int(bool(normalize)), _ptr(snr) if len(snr) else None, len(snr),
+                                                 _ptr(lev), int(first_utterance), int(seed) & (2 ** 64 - 1), _ptr(windows), mem_space))
 
     def cnn_create(self, tensors, rows, channels):
         """tensors: 12 contiguous float32 arrays in Keras layouts (see include/f2cnn_hip.h). Returns a handle."""
@@ -726,6 +758,30 @@ class Context:
             raise ValueError("expected (n, rows, channels) windows and n labels")
         self.check(self.lib.f2_trainer_set_data(self.handle, handle, x.ctypes.data, y.ctypes.data, len(x)))
 
+    def trainer_set_waves(self, handle, wave, wave_dtype, offsets, coefs, B, Cn, lpf, cutoff, precision, center_offsets, centers, signs,
+                          radius, step, group):
+        """The corpus the trainer renders its windows from (see f2_trainer_set_waves): host arrays, copied to the device once"""
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        center_offsets = np.ascontiguousarray(center_offsets, dtype=np.int64)
+        centers = np.ascontiguousarray(centers, dtype=np.int64)
+        signs = np.ascontiguousarray(signs, dtype=np.uint8)
+        self.check(self.lib.f2_trainer_set_waves(self.handle, handle, _ptr(wave), wave_dtype, _ptr(offsets), _ptr(coefs), int(B), Cn,
+                                                 int(bool(lpf)), float(cutoff), precision, _ptr(center_offsets), _ptr(centers),
+                                                 _ptr(signs), radius, step, int(group)))
+
+    def trainer_render(self, handle, snr_db=(), level_of=None, seed=0):
+        """The training windows from the stored waves, utterance b at snr_db[level_of[b]] (see f2_trainer_render)"""
+        snr, lev = _noise_levels(snr_db, level_of)
+        self.check(self.lib.f2_trainer_render(self.handle, handle, _ptr(snr) if len(snr) else None, len(snr), _ptr(lev),
+                                              int(seed) & (2 ** 64 - 1)))
+
+    def trainer_get_windows(self, handle, first, count, shape):
+        """Rows first .. first + count - 1 of the training set: (count, *shape) float32 windows and (count) uint8 labels"""
+        x = np.empty((int(count),) + tuple(shape), np.float32)
+        y = np.empty(int(count), np.uint8)
+        self.check(self.lib.f2_trainer_get_windows(self.handle, handle, int(first), int(count), _ptr(x), _ptr(y)))
+        return x, y
+
     def trainer_steps(self, handle, order, batch):
         """ceil(len(order) / batch) RMSprop steps over the windows order[...] of the training set, enqueued back to back (see
         f2_trainer_steps). Returns (sum of the steps' loss sums, windows decided as labelled)."""
@@ -742,7 +798,7 @@ class Context:
         return out
 
     def trainer_info(self, handle, key):
-        """f2_trainer_get_info: 'iterations'"""
+        """f2_trainer_get_info: 'iterations', 'windows', 'utterances'"""
         v = _d()
         self.check(self.lib.f2_trainer_get_info(self.handle, handle, key.encode(), C.byref(v)))
         return v.value
@@ -806,6 +862,13 @@ def _sweep_outputs(U, window_offsets, stats, sigma=None, with_sigma=False):
         raise ValueError("window_offsets / sigma / stats must be contiguous int64 (K+1)*B + 1, float64 (K+1)*B, int64 ((K+1)*B, 2)"
                          if with_sigma else "window_offsets / stats must be contiguous int64 (K+1)*B + 1 / ((K+1)*B, 2)")
     return got + [None] * (3 - len(got))
+
+
+def _noise_levels(snr_db, level_of):
+    """(snr_db as float64 (K), level_of as int32 or None) for the calls that give every utterance a noise level of its own"""
+    snr = np.ascontiguousarray(snr_db if snr_db is not None else (), dtype=np.float64).reshape(-1)
+    lev = None if level_of is None else np.ascontiguousarray(level_of, dtype=np.int32).reshape(-1)
+    return snr, lev
 
 
 def _pack_rirs(rirs):

@@ -16,6 +16,13 @@ package implements:
                                                              autograd; --engine hip: the library's own training step - weight
                                                              gradients, dropout and RMSprop on the device, the same seed giving the
                                                              same weights bit for bit)
+    python -m f2cnn_amd cnn train --engine hip --from-wav [--lpf HZ] [--augment-snrs 20,10,5,0] [--seed S] [--label/-l CSV]
+                                                            (training windows rendered on the device from the WAV files of the
+                                                             label CSV's TRAIN rows, no input .npy; with --augment-snrs they are
+                                                             rendered again before every epoch, every file at a level drawn from
+                                                             the list or clean under fresh white noise, and the TEST files are
+                                                             validated clean and at every level; --engine torch cannot do either;
+                                                             not in the reference)
     python -m f2cnn_amd cnn test [--input/-i NPY] [--label/-l CSV] [--model/-m NPZ] [--by set|region|speaker|phoneme] [--rows test|train|all]
                                                             (loss, accuracy and the 2 x 2 counts of a saved model on the labelled
                                                              windows, per value of a label column, in one device pass; writes
@@ -112,6 +119,14 @@ def snrs_argument(text):
     if not snrs or not all(math.isfinite(v) for v in snrs):
         raise argparse.ArgumentTypeError("--snrs takes a comma-separated list of SNRs in dB, not {!r}".format(text))
     return snrs
+
+
+def augment_snrs_argument(text):
+    """--augment-snrs: as --snrs"""
+    try:
+        return snrs_argument(text)
+    except argparse.ArgumentTypeError:
+        raise argparse.ArgumentTypeError("--augment-snrs takes a comma-separated list of SNRs in dB, not {!r}".format(text))
 
 
 def cutoffs_argument(text):
@@ -231,7 +246,14 @@ def build_parser():
     # (absent from the parsed arguments unless given: the commands parse as before without it)
     c.add_argument('--engine', action='store', dest='engine', choices=('torch', 'hip'), default=argparse.SUPPRESS,
                    help="train: 'torch' (PyTorch-ROCm autograd, the default) or 'hip' (the library's own training step)")
-    c.add_argument('--seed', action='store', type=int, dest='seed', help="noisesweep: seed of the noise (default 0)")
+    c.add_argument('--from-wav', action='store_true', dest='from_wav', default=argparse.SUPPRESS,
+                   help="train --engine hip: render the training windows from the WAV files on the device (envelopes low-passed at "
+                        "--lpf), without an input .npy")
+    c.add_argument('--augment-snrs', action='store', type=augment_snrs_argument, dest='augment_snrs', default=argparse.SUPPRESS,
+                   help="train --engine hip --from-wav: comma-separated SNRs in dB; every epoch each file is rendered at one of them "
+                        "or clean, under fresh noise")
+    c.add_argument('--seed', action='store', type=int, dest='seed',
+                   help="noisesweep: seed of the noise (default 0); train --from-wav: seed of the weights, the order and the noise")
     c.add_argument('--save-wavs', action='store_true', dest='save_wavs',
                    help="noisesweep: also write the noisy WAV files, as evalnoise does")
     # (absent from the parsed arguments unless given: the commands parse as before without them)
@@ -336,6 +358,20 @@ SWEEPS = {
 }
 
 
+def from_wav_refusal(args):
+    """What is wrong with --from-wav / --augment-snrs on this command line, or None. Looks at the arguments alone."""
+    given = [opt for attr, opt in (('from_wav', '--from-wav'), ('augment_snrs', '--augment-snrs')) if attr in args]
+    if not given:
+        return None
+    if args.cnn_command != 'train':
+        return "{} only applies to 'cnn train'".format(given[0])
+    if getattr(args, 'engine', 'torch') != 'hip':
+        return "{} needs --engine hip: only the library's own training step renders windows from the waves".format(given[0])
+    if 'from_wav' not in args:
+        return "--augment-snrs needs --from-wav: stored windows cannot be rendered again under noise"
+    return None
+
+
 def sweep_refusal(args, no_lpf, instead):
     """says which option the sweep does not take, if one was given (an option that was not given is absent, None or False)"""
     for attr, option, why in (('CUTOFF', '--lpf', no_lpf), ('figure', '--figure', instead), ('occlusion', '--occlusion', instead),
@@ -381,6 +417,20 @@ def main(argv=None):
         if getattr(report, "exit_status", 0):          # some files could not be processed (the others were)
             return report.exit_status
     elif 'cnn_command' in args:
+        refusal = from_wav_refusal(args)
+        if refusal:
+            print(refusal)
+            return 1
+        if args.cnn_command == 'train' and 'from_wav' in args:
+            import os
+            from .scripts.CNN.Training import TrainFromWav
+            labelFile = args.labelFile or os.path.join('trainingData', 'label_data.csv')
+            if not os.path.isfile(labelFile):
+                print("Please first generate a label data file with 'prepare label', or give one with --label")
+                return 1
+            TrainFromWav(labelFile=labelFile, LPF=args.CUTOFF is not None, CUTOFF=args.CUTOFF, snrs=tuple(getattr(args, 'augment_snrs', ())),
+                         seed=args.seed)
+            return 0
         if args.cnn_command == 'train':                        # f2cnn.py:126-143
             from .scripts.CNN.Training import TrainAndPlotLoss
             files = labelled_window_files(args)

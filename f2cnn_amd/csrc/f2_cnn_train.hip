@@ -725,6 +725,13 @@ struct f2_trainer {
     double lr = 0, rho = 0, eps = 0, decay = 0, drop[3] = {0, 0, 0};
     uint64_t seed = 0;
     int64_t iterations = 0;
+    // f2_trainer_set_waves: the corpus x is rendered from (f2_trainer_render), instead of windows handed in by set_data
+    bool have_waves = false;
+    f2_scratch wave, centers;   // the waves; [the centres | the utterance of every window, counted inside its group]
+    std::vector<int64_t> offsets, center_offsets;
+    std::vector<double> coefs;
+    int wave_dtype = 0, B = 0, lpf = 0, fft_precision = 0, radius = 0, step = 0, group = 1;
+    double cutoff_hz = 0;
 };
 
 extern "C" {
@@ -854,7 +861,7 @@ int f2_trainer_set_data(f2_ctx* ctx, f2_trainer* t, const float* x, const uint8_
     F2_TRY(check_trainer(ctx, t));
     F2_CHECK(ctx, n >= 0 && (n == 0 || (x && y)), F2_ERR_INVALID, "bad training set (n %lld)", (long long)n);
     const size_t xs = (size_t)t->rows * t->channels;
-    t->n = 0;
+    t->n = 0, t->have_waves = false, t->B = 0;
     if (n == 0) return F2_OK;
     F2_TRY(f2_reserve(ctx, t->x, sizeof(float) * xs * (size_t)n));
     F2_TRY(f2_reserve(ctx, t->y, (size_t)n));
@@ -862,6 +869,89 @@ int f2_trainer_set_data(f2_ctx* ctx, f2_trainer* t, const float* x, const uint8_
     F2_HIP(ctx, hipMemcpyAsync(t->y.ptr, y, (size_t)n, hipMemcpyHostToDevice, ctx->stream));
     F2_HIP(ctx, hipStreamSynchronize(ctx->stream));
     t->n = n;
+    return F2_OK;
+}
+
+int f2_trainer_set_waves(f2_ctx* ctx, f2_trainer* t, const void* wave, int wave_dtype, const int64_t* offsets, const double* coefs, int B,
+                         int C, int lpf, double cutoff_hz, int fft_precision, const int64_t* center_offsets, const int64_t* centers,
+                         const uint8_t* signs, int radius, int step, int group) {
+    F2_TRY(f2_check_ctx(ctx));
+    F2_TRY(check_trainer(ctx, t));
+    F2_CHECK(ctx, C == t->channels && 2 * (int64_t)radius + 1 == t->rows, F2_ERR_INVALID,
+             "the trainer was built for %d x %d windows, asked for %lld x %d", t->rows, t->channels, 2 * (long long)radius + 1, C);
+    F2_CHECK(ctx, group >= 1, F2_ERR_INVALID, "group must be at least 1 utterance (got %d)", group);
+    int64_t n = 0;
+    std::vector<int> win_utt;
+    F2_TRY(f2_check_input_batch(ctx, wave, wave_dtype, offsets, coefs, B, C, lpf, cutoff_hz, fft_precision, center_offsets, centers, radius, step,
+                                t, F2_MEM_HOST, nullptr, &n, &win_utt));
+    F2_CHECK(ctx, n == 0 || signs, F2_ERR_INVALID, "signs is NULL");
+    for (int64_t e = 0; e < n; ++e) F2_CHECK(ctx, signs[e] <= 1, F2_ERR_INVALID, "signs[%lld] = %d is neither 0 nor 1", (long long)e, (int)signs[e]);
+    F2_CHECK(ctx, B == 0 || coefs, F2_ERR_INVALID, "coefs is NULL");
+
+    t->n = 0, t->have_waves = false, t->B = 0;
+    t->wave_dtype = wave_dtype, t->lpf = lpf, t->cutoff_hz = cutoff_hz, t->fft_precision = fft_precision, t->radius = radius, t->step = step;
+    t->group = group;
+    if (B > 0) {
+        t->offsets.assign(offsets, offsets + B + 1);
+        t->center_offsets.assign(center_offsets, center_offsets + B + 1);
+        t->coefs.assign(coefs, coefs + 10 * (size_t)C);
+    }
+    if (n > 0) {
+        for (int64_t e = 0; e < n; ++e) win_utt[(size_t)e] %= group;
+        const size_t wbytes = (wave_dtype == F2_WAVE_I16 ? 2 : 8) * (size_t)offsets[B], cbytes = sizeof(int64_t) * (size_t)n;
+        F2_TRY(f2_reserve(ctx, t->wave, wbytes));
+        F2_TRY(f2_reserve(ctx, t->centers, cbytes + sizeof(int) * (size_t)n));
+        F2_TRY(f2_reserve(ctx, t->x, sizeof(float) * (size_t)t->rows * t->channels * (size_t)n));
+        F2_TRY(f2_reserve(ctx, t->y, (size_t)n));
+        F2_HIP(ctx, hipMemcpyAsync(t->wave.ptr, wave, wbytes, hipMemcpyHostToDevice, ctx->stream));
+        F2_HIP(ctx, hipMemcpyAsync(t->centers.ptr, centers, cbytes, hipMemcpyHostToDevice, ctx->stream));
+        F2_HIP(ctx, hipMemcpyAsync((char*)t->centers.ptr + cbytes, win_utt.data(), sizeof(int) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+        F2_HIP(ctx, hipMemcpyAsync(t->y.ptr, signs, (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+        F2_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    t->n = n, t->B = B, t->have_waves = true;
+    return F2_OK;
+}
+
+int f2_trainer_render(f2_ctx* ctx, f2_trainer* t, const double* snr_db, int K, const int32_t* level_of, uint64_t seed) {
+    F2_TRY(f2_check_ctx(ctx));
+    F2_TRY(check_trainer(ctx, t));
+    F2_CHECK(ctx, t->have_waves, F2_ERR_INVALID, "the trainer has no waves to render from (f2_trainer_set_waves)");
+    F2_TRY(f2_check_noise_pick(ctx, t->B, {snr_db, K, level_of, 0, seed}));
+    if (t->n == 0) return F2_OK;
+    const size_t xs = (size_t)t->rows * t->channels, ws = t->wave_dtype == F2_WAVE_I16 ? 2 : 8;
+    const int64_t* d_centers = (const int64_t*)t->centers.ptr;
+    const int* d_win_utt = (const int*)((const char*)t->centers.ptr + sizeof(int64_t) * (size_t)t->n);
+    F2_HIP(ctx, hipMemsetAsync(ctx->flags.ptr, 0, sizeof(int), ctx->stream));
+    std::vector<int64_t> off;
+    // group after group onto the stream, each into its rows of x; one wait at the end
+    for (int b0 = 0; b0 < t->B; b0 += std::min(t->group, t->B - b0)) {
+        const int nb = std::min(t->group, t->B - b0);
+        const int64_t w0 = t->center_offsets[(size_t)b0], nw = t->center_offsets[(size_t)b0 + nb] - w0;
+        if (nw == 0) continue;
+        off.resize((size_t)nb + 1);
+        for (int b = 0; b <= nb; ++b) off[(size_t)b] = t->offsets[(size_t)b0 + b] - t->offsets[(size_t)b0];
+        const f2_noise_pick_args N = {snr_db, K, level_of ? level_of + b0 : nullptr, (uint32_t)b0, seed};
+        F2_TRY(f2_launch_noisy_windows(ctx, (const char*)t->wave.ptr + ws * (size_t)t->offsets[(size_t)b0], t->wave_dtype, off.data(),
+                                       t->coefs.data(), nb, t->channels, t->lpf, t->cutoff_hz, t->fft_precision, d_centers + w0, d_win_utt + w0,
+                                       true, nw, t->radius, t->step, 1, N, (float*)t->x.ptr + xs * (size_t)w0));
+    }
+    F2_HIP(ctx, hipMemcpyAsync(ctx->host_flags, ctx->flags.ptr, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    F2_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    F2_CHECK(ctx, !ctx->host_flags[0], F2_ERR_NONPOSITIVE, "values must all be positive (normalizeInput)");
+    return F2_OK;
+}
+
+int f2_trainer_get_windows(f2_ctx* ctx, const f2_trainer* t, int64_t first, int64_t count, float* x, uint8_t* y) {
+    F2_TRY(f2_check_ctx(ctx));
+    F2_TRY(check_trainer(ctx, t));
+    F2_CHECK(ctx, first >= 0 && count >= 0 && first <= t->n && count <= t->n - first, F2_ERR_INVALID,
+             "windows %lld .. + %lld are outside the %lld of the training set", (long long)first, (long long)count, (long long)t->n);
+    if (count == 0) return F2_OK;
+    const size_t xs = (size_t)t->rows * t->channels;
+    if (x) F2_HIP(ctx, hipMemcpyAsync(x, (const float*)t->x.ptr + xs * (size_t)first, sizeof(float) * xs * (size_t)count, hipMemcpyDeviceToHost, ctx->stream));
+    if (y) F2_HIP(ctx, hipMemcpyAsync(y, (const uint8_t*)t->y.ptr + first, (size_t)count, hipMemcpyDeviceToHost, ctx->stream));
+    F2_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return F2_OK;
 }
 
@@ -919,6 +1009,8 @@ int f2_trainer_get_info(f2_ctx* ctx, const f2_trainer* t, const char* key, doubl
     F2_TRY(check_trainer(ctx, t));
     F2_CHECK(ctx, key && value, F2_ERR_INVALID, "null argument");
     if (strcmp(key, "iterations") == 0) *value = (double)t->iterations;
+    else if (strcmp(key, "windows") == 0) *value = (double)t->n;
+    else if (strcmp(key, "utterances") == 0) *value = (double)t->B;
     else return f2_fail(ctx, F2_ERR_INVALID, "unknown key '%s'", key);
     return F2_OK;
 }

@@ -61,7 +61,8 @@ struct f2_ctx {
     f2_scratch dense_in;   // conv4 outputs (+ dense1 outputs) of the windows of several utterances: one dense launch for all
     // the four sweeps, f2_lowpass_levels, f2_reverb_levels, f2_channel_mix_levels: the (K+1) x batch levels (float64 waveforms or envelopes) when the caller
     // gives no device buffer. One area: each of these calls places one set of levels, and nothing they nest (f2_eval_batch_strided,
-    // with or without lpf; eval_envelopes) places another.
+    // with or without lpf; eval_envelopes) places another. f2_noise_pick / f2_launch_noisy_windows: the noisy float64 batch, by the same rule
+    // (f2_batch_envelopes, which they nest, places nothing here).
     f2_scratch levels;
     // f2_channel_mix_levels, f2_eval_smear_sweep: tile sums, tile spans and the transposed mixing matrices of the call in flight (up to
     // 134 MB at 64 levels of 512 channels: too much for `meta`). Reserved once per call, before its first launch.
@@ -69,7 +70,7 @@ struct f2_ctx {
     // The small arrays of the call in flight (f2_meta_carve): sigma / stats / window offsets of the noise sweep, filter coefficients /
     // stats / window offsets of the cutoff sweep, taps / tile sums / stats / window offsets of the reverberation sweep, counts and reference
     // labels of f2_label_accuracy, counts / loss sums / loss partials of f2_cnn_score_windows, span records and range words of the
-    // pictures, utterance records of f2_resample_batch. One area for all of them, which holds while
+    // pictures, utterance records of f2_resample_batch, sigma / level factors / levels of f2_noise_pick. One area for all of them, which holds while
     //  - nothing cached lives here: what a later call may find unchanged (spec_meta, rs_tab, offsets, coefs) has its own area;
     //  - a call carves it once, before its first launch and before any nested entry point runs (f2_reserve frees and reallocates
     //    on growth, and the noise sweep holds its pointers across the nested f2_eval_batch_strided), and no code reached from a
@@ -506,6 +507,36 @@ int f2_launch_noise_sigma(f2_ctx* ctx, const void* d_wave, int wave_dtype, const
                           int K, double* d_sigma);
 int f2_launch_noise_levels(f2_ctx* ctx, const void* d_wave, int wave_dtype, const int64_t* d_offsets, const double* d_sigma, int B,
                            int K, int64_t total, uint64_t seed, double* d_out);
+// The kernels of f2_noise_pick: utterance b at level d_level[b] in [0, K] (K: clean), utterance first_utterance + b of its corpus.
+// d_sigma (B) is written by the first launch and read by the second, which writes `total` float64 samples to d_out. d_sigma == NULL:
+// every utterance is clean, d_lin and d_level are not read.
+int f2_launch_noise_pick(f2_ctx* ctx, const void* d_wave, int wave_dtype, const int64_t* d_offsets, const double* d_lin,
+                         const int32_t* d_level, int B, int K, int64_t total, uint32_t first_utterance, uint64_t seed, double* d_sigma,
+                         double* d_out);
+// f2_pipeline.hip, the driver f2_input_batch_noisy and f2_trainer_render share: the B utterances at d_wave (device, offsets from 0
+// on the host) through the noise kernels into ctx->levels, then f2_input_batch's envelopes and gather on that float64 buffer, the
+// windows written to d_windows (device). The centres and the utterance of every window (counted inside this batch) are either on
+// the device already (lists_on_device) or host arrays that go up behind the envelope launches, as in f2_input_batch. Enqueues only; the gather ORs into word 0 of ctx->flags, which the caller resets before and reads after. The arguments
+// have passed f2_check_noise_pick and f2_input_batch's checks.
+struct f2_noise_pick_args {
+    const double* snr_db;
+    int K;
+    const int32_t* level_of;
+    uint32_t first_utterance;
+    uint64_t seed;
+    bool clean() const { return K == 0 || !level_of; }
+};
+int f2_check_noise_pick(f2_ctx* ctx, int B, const f2_noise_pick_args& N);
+// The argument checks of f2_input_batch, and behind them f2_check_noise_pick when the call has a noise stage (noise != NULL), all
+// before anything is launched. `windows`: where the windows go (only tested for NULL). *n_windows == 0 on F2_OK: an empty call.
+// win_utt: the utterance of every window.
+int f2_check_input_batch(f2_ctx* ctx, const void* wave, int wave_dtype, const int64_t* offsets, const double* coefs, int B, int C, int lpf,
+                         double cutoff_hz, int fft_precision, const int64_t* center_offsets, const int64_t* centers, int radius, int step,
+                         const void* windows, int mem_space, const f2_noise_pick_args* noise, int64_t* n_windows,
+                         std::vector<int>* win_utt);
+int f2_launch_noisy_windows(f2_ctx* ctx, const void* d_wave, int wave_dtype, const int64_t* offsets, const double* coefs, int B, int C,
+                            int lpf, double cutoff_hz, int fft_precision, const int64_t* centers, const int* win_utt,
+                            bool lists_on_device, int64_t n_windows, int radius, int step, int normalize, const f2_noise_pick_args& N, float* d_windows);
 // d_stats ((K + 1) * B pairs, zeroed by the caller) += {windows labelled rising, windows labelled as the clean level labels them}
 // per utterance of the (K + 1) * B batch whose window offsets are d_window_offsets; max_windows: the most any utterance has
 int f2_launch_label_tally(f2_ctx* ctx, const uint8_t* d_labels, const int64_t* d_window_offsets, int B, int K, int64_t max_windows,

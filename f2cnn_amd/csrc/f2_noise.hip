@@ -1,6 +1,7 @@
-// Kernels of f2_eval_noise_sweep (include/f2cnn_hip.h): the noise levels of a ragged batch and the tally of its labels.
+// Kernels of f2_eval_noise_sweep and f2_noise_pick (include/f2cnn_hip.h): the noise levels of a ragged batch and the tally of its labels.
 //   k_noise_sigma  sum of squares of every clean utterance (one workgroup per row, fixed order) -> sigma per (level, utterance)
 //   k_noise_levels the (K+1) x batch float64 waveform: clean + sigma * z, z from Philox4x32-10 per sample; level K is the clean one
+//   k_noise_pick_sigma, k_noise_pick  the same two for a batch in which every utterance has one level of its own
 //   k_label_tally  per (level, utterance): windows labelled rising, windows whose label is the clean level's
 // gfx950, wave64. Everything that reaches memory is written by plain C++ stores or vector integer atomics.
 #include "f2_internal.h"
@@ -31,16 +32,12 @@ __device__ inline T block_sum(T v, T* lds) {
     return total;
 }
 
-// Row b of the clean batch. int16: the squares are summed in int64 (exact, so the order does not matter), then
-// sqrt((double)sum / n). float64: thread t adds samples t, t + THREADS, ... in that order, then the fixed tree of block_sum.
-// sigma[l * B + b] = rms / lin[l] for l < K (lin[l] = 10^(snr_db[l] / 10), from the host) and 0 for the clean level l = K.
+// RMS of row b of the clean batch, valid in thread 0. int16: the squares are summed in int64 (exact, so the order does not matter),
+// then sqrt((double)sum / n). float64: thread t adds samples t, t + THREADS, ... in that order, then the fixed tree of block_sum.
 template <typename T>
-__global__ __launch_bounds__(SIGMA_THREADS) void k_noise_sigma(const T* __restrict__ wave, const int64_t* __restrict__ offsets,
-                                                                const double* __restrict__ lin, int B, int K,
-                                                                double* __restrict__ sigma) {
+__device__ inline double row_rms(const T* __restrict__ wave, const int64_t* __restrict__ offsets, int b) {
     using acc_t = typename std::conditional<std::is_same<T, int16_t>::value, long long, double>::type;
     __shared__ acc_t lds[SIGMA_THREADS / 64];
-    const int b = blockIdx.x;
     const int64_t n = offsets[b + 1] - offsets[b];
     const T* x = wave + offsets[b];
     acc_t acc = 0;
@@ -49,10 +46,37 @@ __global__ __launch_bounds__(SIGMA_THREADS) void k_noise_sigma(const T* __restri
         acc += v * v;
     }
     const acc_t total = block_sum<acc_t, SIGMA_THREADS>(acc, lds);
+    return n > 0 ? sqrt((double)total / (double)n) : 0.0;
+}
+// sigma of an utterance of that RMS at the level whose 10^(snr_db / 10) is lin; an empty utterance has none
+__device__ inline double sigma_of(double rms, double lin, bool empty) { return empty ? 0.0 : rms / lin; }
+
+// sigma[l * B + b] = rms / lin[l] for l < K (lin[l] = 10^(snr_db[l] / 10), from the host) and 0 for the clean level l = K.
+template <typename T>
+__global__ __launch_bounds__(SIGMA_THREADS) void k_noise_sigma(const T* __restrict__ wave, const int64_t* __restrict__ offsets,
+                                                                const double* __restrict__ lin, int B, int K,
+                                                                double* __restrict__ sigma) {
+    const int b = blockIdx.x;
+    const double rms = row_rms(wave, offsets, b);
     if (threadIdx.x != 0) return;
-    const double rms = n > 0 ? sqrt((double)total / (double)n) : 0.0;
-    for (int l = 0; l < K; ++l) sigma[(size_t)l * B + b] = n > 0 ? rms / lin[l] : 0.0;
+    const bool empty = offsets[b + 1] == offsets[b];
+    for (int l = 0; l < K; ++l) sigma[(size_t)l * B + b] = sigma_of(rms, lin[l], empty);
     sigma[(size_t)K * B + b] = 0.0;
+}
+
+// The same for a batch whose utterance b runs at level level[b] alone: sigma[b], 0 for the clean level K
+template <typename T>
+__global__ __launch_bounds__(SIGMA_THREADS) void k_noise_pick_sigma(const T* __restrict__ wave, const int64_t* __restrict__ offsets,
+                                                                     const double* __restrict__ lin, const int32_t* __restrict__ level,
+                                                                     int K, double* __restrict__ sigma) {
+    const int b = blockIdx.x;
+    const int l = level[b];
+    if (l >= K) {   // (the whole workgroup: no barrier is skipped by a part of it)
+        if (threadIdx.x == 0) sigma[b] = 0.0;
+        return;
+    }
+    const double rms = row_rms(wave, offsets, b);
+    if (threadIdx.x == 0) sigma[b] = sigma_of(rms, lin[l], offsets[b + 1] == offsets[b]);
 }
 
 // the standard normal deviate of (seed, level, utterance, sample): the cosine branch of Box-Muller on two 53-bit uniforms
@@ -61,6 +85,16 @@ __device__ inline double noise_deviate(uint64_t seed, uint32_t level, uint32_t u
     const double u1 = ((double)(w.w0 >> 5) * 67108864.0 + (double)(w.w1 >> 6) + 1.0) * 0x1p-53;   // (0, 1]
     const double u2 = ((double)(w.w2 >> 5) * 67108864.0 + (double)(w.w3 >> 6)) * 0x1p-53;         // [0, 1)
     return sqrt(-2.0 * log(u1)) * cos(6.283185307179586 * u2);
+}
+
+// utterance of sample p of the batch: the last b with offsets[b] <= p (empty utterances are stepped over)
+__device__ inline int utterance_of(const int64_t* __restrict__ offsets, int B, int64_t p) {
+    int lo = 0, hi = B;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (offsets[mid] <= p) lo = mid; else hi = mid;
+    }
+    return lo;
 }
 
 // One thread per sample of one level (blockIdx.y strides over the levels): out[l * total + p] = clean[p] + sigma[l * B + b] * z,
@@ -72,13 +106,7 @@ __global__ __launch_bounds__(NOISE_THREADS) void k_noise_levels(const T* __restr
                                                                  uint64_t seed, double* __restrict__ out) {
 #pragma clang fp contract(off)
     for (int64_t p = (int64_t)blockIdx.x * NOISE_THREADS + threadIdx.x; p < total; p += (int64_t)gridDim.x * NOISE_THREADS) {
-        // utterance of sample p: the last b with offsets[b] <= p (empty utterances are stepped over)
-        int lo = 0, hi = B;
-        while (hi - lo > 1) {
-            const int mid = (lo + hi) >> 1;
-            if (offsets[mid] <= p) lo = mid; else hi = mid;
-        }
-        const int b = lo;
+        const int b = utterance_of(offsets, B, p);
         const uint64_t i = (uint64_t)(p - offsets[b]);
         const double clean = (double)wave[p];
         for (int l = blockIdx.y; l < levels; l += gridDim.y) {
@@ -90,6 +118,28 @@ __global__ __launch_bounds__(NOISE_THREADS) void k_noise_levels(const T* __restr
             }
             out[(size_t)l * (size_t)total + (size_t)p] = v;
         }
+    }
+}
+
+// One thread per sample of a batch whose utterance b runs at level[b] and is utterance first_utt + b of its corpus:
+// out[p] = clean[p] + sigma[b] * z(seed, level[b], first_utt + b, i), what k_noise_levels writes for that level of that utterance.
+// sigma == NULL: every utterance is clean (the conversion to float64 alone). Consecutive lanes write consecutive float64 values.
+template <typename T>
+__global__ __launch_bounds__(NOISE_THREADS) void k_noise_pick(const T* __restrict__ wave, const int64_t* __restrict__ offsets,
+                                                               const double* __restrict__ sigma, const int32_t* __restrict__ level, int B,
+                                                               int64_t total, uint32_t first_utt, uint64_t seed, double* __restrict__ out) {
+#pragma clang fp contract(off)
+    for (int64_t p = (int64_t)blockIdx.x * NOISE_THREADS + threadIdx.x; p < total; p += (int64_t)gridDim.x * NOISE_THREADS) {
+        double v = (double)wave[p];
+        if (sigma) {
+            const int b = utterance_of(offsets, B, p);
+            const double s = sigma[b];
+            if (s != 0.0) {
+                const double nz = s * noise_deviate(seed, (uint32_t)level[b], first_utt + (uint32_t)b, (uint64_t)(p - offsets[b]));
+                v = v + nz;
+            }
+        }
+        out[p] = v;
     }
 }
 
@@ -140,6 +190,31 @@ int f2_launch_noise_levels(f2_ctx* ctx, const void* d_wave, int wave_dtype, cons
     else
         k_noise_levels<double><<<grid, dim3(NOISE_THREADS), 0, ctx->stream>>>((const double*)d_wave, d_offsets, d_sigma, B, K + 1, total,
                                                                              seed, d_out);
+    F2_HIP(ctx, hipGetLastError());
+    return F2_OK;
+}
+
+int f2_launch_noise_pick(f2_ctx* ctx, const void* d_wave, int wave_dtype, const int64_t* d_offsets, const double* d_lin,
+                         const int32_t* d_level, int B, int K, int64_t total, uint32_t first_utterance, uint64_t seed, double* d_sigma,
+                         double* d_out) {
+    if (B == 0) return F2_OK;
+    const bool i16 = wave_dtype == F2_WAVE_I16;
+    if (d_sigma) {
+        if (i16)
+            k_noise_pick_sigma<int16_t><<<dim3(B), dim3(SIGMA_THREADS), 0, ctx->stream>>>((const int16_t*)d_wave, d_offsets, d_lin, d_level, K, d_sigma);
+        else
+            k_noise_pick_sigma<double><<<dim3(B), dim3(SIGMA_THREADS), 0, ctx->stream>>>((const double*)d_wave, d_offsets, d_lin, d_level, K, d_sigma);
+        F2_HIP(ctx, hipGetLastError());
+    }
+    if (total == 0) return F2_OK;
+    const int64_t blocks = (total + NOISE_THREADS - 1) / NOISE_THREADS;
+    const dim3 grid((unsigned)(blocks < (1 << 20) ? blocks : (1 << 20)));
+    if (i16)
+        k_noise_pick<int16_t><<<grid, dim3(NOISE_THREADS), 0, ctx->stream>>>((const int16_t*)d_wave, d_offsets, d_sigma, d_level, B, total,
+                                                                            first_utterance, seed, d_out);
+    else
+        k_noise_pick<double><<<grid, dim3(NOISE_THREADS), 0, ctx->stream>>>((const double*)d_wave, d_offsets, d_sigma, d_level, B, total,
+                                                                           first_utterance, seed, d_out);
     F2_HIP(ctx, hipGetLastError());
     return F2_OK;
 }

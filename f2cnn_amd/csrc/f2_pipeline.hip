@@ -871,31 +871,114 @@ int f2_cnn_score_windows(f2_ctx* ctx, const f2_cnn* cnn, const float* windows, i
     return F2_OK;
 }
 
-int f2_input_batch(f2_ctx* ctx, const void* wave, int wave_dtype, const int64_t* offsets, const double* coefs, int B, int C,
-                   int lpf, double cutoff_hz, int fft_precision, const int64_t* center_offsets, const int64_t* centers,
-                   int radius, int step, int normalize, float* windows, int mem_space) {
+}  // extern "C"
+
+namespace {
+
+// The small arrays of a noise stage in ctx->meta and its two launches. A clean stage (N.clean()) has none and converts alone.
+struct noise_pick_meta {
+    double *d_sigma = nullptr, *d_lin = nullptr;
+    int64_t* d_level = nullptr;   // B int32 values in 8-byte slots
+    void carve(f2_meta_carve* meta, int B, const f2_noise_pick_args& N) {
+        if (N.clean()) return;
+        meta->add(&d_sigma, (size_t)B), meta->add(&d_lin, (size_t)N.K), meta->add(&d_level, ((size_t)B + 1) / 2);
+    }
+    int launch(f2_ctx* ctx, const void* d_wave, int wave_dtype, const int64_t* d_offsets, int B, int64_t total, const f2_noise_pick_args& N,
+               double* d_noisy) const {
+        if (!N.clean()) {
+            std::vector<double> lin;   // 10^(snr / 10) per level (Evaluating.py:189 SNRdbToSNRlinear)
+            for (int k = 0; k < N.K; ++k) lin.push_back(std::pow(10.0, N.snr_db[k] / 10.0));
+            F2_TRY(f2_upload_async(ctx, d_lin, lin.data(), sizeof(double) * (size_t)N.K));
+            F2_TRY(f2_upload_async(ctx, d_level, N.level_of, sizeof(int32_t) * (size_t)B));
+        }
+        return f2_launch_noise_pick(ctx, d_wave, wave_dtype, d_offsets, d_lin, (const int32_t*)d_level, B, N.K, total, N.first_utterance,
+                                    N.seed, d_sigma, d_noisy);
+    }
+};
+
+}  // namespace
+
+// The argument checks of f2_input_batch, and behind them those of the noise stage when the call has one (noise != NULL), all before
+// anything is launched. *n_windows == 0 on F2_OK: an empty call. win_utt: the utterance of every window.
+int f2_check_input_batch(f2_ctx* ctx, const void* wave, int wave_dtype, const int64_t* offsets, const double* coefs, int B, int C, int lpf,
+                      double cutoff_hz, int fft_precision, const int64_t* center_offsets, const int64_t* centers, int radius, int step,
+                      const void* windows, int mem_space, const f2_noise_pick_args* noise, int64_t* n_windows, std::vector<int>* win_utt) {
+    *n_windows = 0;
     F2_TRY(f2_check_ctx(ctx));
     F2_TRY(f2_check_mem_space(ctx, mem_space, false));
     F2_TRY(f2_check_dsp(ctx, wave_dtype, lpf, cutoff_hz, fft_precision));
     F2_CHECK(ctx, B >= 0 && C > 0 && radius >= 0 && step >= 0, F2_ERR_INVALID, "bad size");
+    if (noise) F2_TRY(f2_check_noise_pick(ctx, B, *noise));
     if (B == 0) return F2_OK;      // (before the offsets are looked at: they may be NULL then)
     F2_TRY(f2_check_offsets(ctx, offsets, B, "offsets"));
     F2_TRY(f2_check_offsets(ctx, center_offsets, B, "center_offsets"));
-    const int64_t n_windows = center_offsets[B];
-    if (n_windows == 0) return F2_OK;
+    const int64_t n = center_offsets[B];
+    if (n == 0) return F2_OK;
     F2_CHECK(ctx, wave && coefs && centers && windows, F2_ERR_INVALID, "null data pointer");
     // InputGenerator.py:73-80 indexes each utterance's own envelope: a window must lie inside it
     const int64_t reach = (int64_t)radius * step;
-    std::vector<int> win_utt((size_t)n_windows);
+    win_utt->resize((size_t)n);
     for (int b = 0; b < B; ++b) {
         const int64_t nb = offsets[b + 1] - offsets[b];
         for (int64_t e = center_offsets[b]; e < center_offsets[b + 1]; ++e) {
             F2_CHECK(ctx, centers[e] - reach >= 0 && centers[e] + reach < nb, F2_ERR_INVALID,
                      "utterance %d: window %lld (centre %lld, +-%lld) reaches outside its %lld-sample envelope", b,
                      (long long)(e - center_offsets[b]), (long long)centers[e], (long long)reach, (long long)nb);
-            win_utt[(size_t)e] = b;
+            (*win_utt)[(size_t)e] = b;
         }
     }
+    *n_windows = n;
+    return F2_OK;
+}
+
+int f2_check_noise_pick(f2_ctx* ctx, int B, const f2_noise_pick_args& N) {
+    F2_CHECK(ctx, N.K >= 0, F2_ERR_INVALID, "negative number of noise levels (K=%d)", N.K);
+    F2_CHECK(ctx, ((int64_t)N.K + 1) * (B > 0 ? B : 1) <= INT32_MAX / 2, F2_ERR_UNSUPPORTED, "%d levels of %d utterances", N.K + 1, B);
+    F2_CHECK(ctx, (uint64_t)N.first_utterance + (uint64_t)(B > 0 ? B : 0) <= (uint64_t(1) << 32), F2_ERR_UNSUPPORTED,
+             "utterances %u .. %u + %d do not fit the generator's 32-bit utterance number", N.first_utterance, N.first_utterance, B);
+    if (N.clean()) return F2_OK;
+    F2_CHECK(ctx, N.snr_db, F2_ERR_INVALID, "level_of is given for K=%d levels, but snr_db is NULL", N.K);
+    for (int k = 0; k < N.K; ++k) F2_CHECK(ctx, std::isfinite(N.snr_db[k]), F2_ERR_INVALID, "snr_db[%d] is not finite", k);
+    for (int b = 0; b < B; ++b)
+        F2_CHECK(ctx, N.level_of[b] >= 0 && N.level_of[b] <= N.K, F2_ERR_INVALID, "utterance %d: level %d is outside [0, %d]", b,
+                 (int)N.level_of[b], N.K);
+    return F2_OK;
+}
+
+int f2_launch_noisy_windows(f2_ctx* ctx, const void* d_wave, int wave_dtype, const int64_t* offsets, const double* coefs, int B, int C,
+                            int lpf, double cutoff_hz, int fft_precision, const int64_t* centers, const int* win_utt,
+                            bool lists_on_device, int64_t n_windows, int radius, int step, int normalize, const f2_noise_pick_args& N,
+                            float* d_windows) {
+    const int64_t total = offsets[B];
+    // the small arrays and the noisy waveform first: nothing the envelopes reserve is one of these two areas
+    noise_pick_meta M;
+    f2_meta_carve meta;
+    M.carve(&meta, B, N);
+    F2_TRY(meta.reserve(ctx));
+    F2_TRY(f2_reserve(ctx, ctx->levels, sizeof(double) * (size_t)total));
+    F2_TRY(f2_upload_offsets(ctx, offsets, B));
+    F2_TRY(M.launch(ctx, d_wave, wave_dtype, (const int64_t*)ctx->offsets.ptr, B, total, N, (double*)ctx->levels.ptr));
+    // f2_input_batch from here on, as a device call on the float64 buffer
+    const f2_batch X = {ctx->levels.ptr, F2_WAVE_F64, offsets, coefs, B, C, lpf, cutoff_hz, fft_precision, F2_MEM_DEVICE};
+    double* d_env;
+    F2_TRY(f2_batch_envelopes(ctx, X, nullptr, nullptr, true, &d_env));
+    const int64_t* d_centers = centers;
+    const int* d_win_utt = win_utt;
+    if (!lists_on_device) F2_TRY(f2_upload_windows(ctx, centers, win_utt, n_windows, &d_centers, &d_win_utt));
+    return f2_launch_gather_ragged(ctx, d_env, C, (const int64_t*)ctx->offsets.ptr, d_centers, d_win_utt, n_windows, radius, step, normalize,
+                                   d_windows, (int*)ctx->flags.ptr);
+}
+
+extern "C" {
+
+int f2_input_batch(f2_ctx* ctx, const void* wave, int wave_dtype, const int64_t* offsets, const double* coefs, int B, int C,
+                   int lpf, double cutoff_hz, int fft_precision, const int64_t* center_offsets, const int64_t* centers,
+                   int radius, int step, int normalize, float* windows, int mem_space) {
+    int64_t n_windows;
+    std::vector<int> win_utt;
+    F2_TRY(f2_check_input_batch(ctx, wave, wave_dtype, offsets, coefs, B, C, lpf, cutoff_hz, fft_precision, center_offsets, centers, radius,
+                             step, windows, mem_space, nullptr, &n_windows, &win_utt));
+    if (n_windows == 0) return F2_OK;
     const int R = 2 * radius + 1;
 
     // envelopes of the whole batch, by the routes of f2_filterbank_envelope_fused (gfb_or_null = NULL), into a scratch buffer
@@ -912,6 +995,64 @@ int f2_input_batch(f2_ctx* ctx, const void* wave, int wave_dtype, const int64_t*
     F2_TRY(reset_flag(ctx));
     F2_TRY(f2_launch_gather_ragged(ctx, d_env, C, (const int64_t*)ctx->offsets.ptr, d_centers, d_win_utt, n_windows, radius, step,
                                    normalize, win.as<float>(), (int*)ctx->flags.ptr));
+    return finish_windows(ctx, win, normalize);
+}
+
+// f2_noise_pick: the clean samples go up (host calls), the two kernels of f2_launch_noise_pick run, the float64 samples and sigma come
+// back. A device call waits only for sigma.
+int f2_noise_pick(f2_ctx* ctx, const void* wave, int wave_dtype, const int64_t* offsets, int B, const double* snr_db, int K,
+                  const int32_t* level_of, uint32_t first_utterance, uint64_t seed, double* noisy, double* sigma_or_null, int mem_space) {
+    F2_TRY(f2_check_ctx(ctx));
+    F2_TRY(f2_check_wave_dtype(ctx, wave_dtype));
+    F2_CHECK(ctx, B >= 0, F2_ERR_INVALID, "bad batch size (B=%d)", B);
+    F2_TRY(f2_check_mem_space(ctx, mem_space, false));
+    const f2_noise_pick_args N = {snr_db, K, level_of, first_utterance, seed};
+    F2_TRY(f2_check_noise_pick(ctx, B, N));
+    if (B == 0) return F2_OK;
+    F2_TRY(f2_check_offsets(ctx, offsets, B, "offsets"));
+    const int64_t total = offsets[B];
+    if (total == 0) {
+        if (sigma_or_null) std::fill(sigma_or_null, sigma_or_null + B, 0.0);
+        return F2_OK;
+    }
+    F2_CHECK(ctx, wave && noisy, F2_ERR_INVALID, "null data pointer");
+    noise_pick_meta M;
+    f2_meta_carve meta;
+    M.carve(&meta, B, N);
+    F2_TRY(meta.reserve(ctx));
+    f2_output out;
+    F2_TRY(f2_place(ctx, ctx->levels, noisy, sizeof(double) * (size_t)total, mem_space, true, &out));
+    F2_TRY(f2_upload_offsets(ctx, offsets, B));
+    const void* d_wave;
+    F2_TRY(f2_stage_wave(ctx, wave, wave_dtype, total, mem_space, &d_wave));
+    F2_TRY(M.launch(ctx, d_wave, wave_dtype, (const int64_t*)ctx->offsets.ptr, B, total, N, out.as<double>()));
+    F2_TRY(f2_copy_back(ctx, out));
+    if (sigma_or_null) {
+        if (M.d_sigma) F2_HIP(ctx, hipMemcpyAsync(sigma_or_null, M.d_sigma, sizeof(double) * (size_t)B, hipMemcpyDeviceToHost, ctx->stream));
+        else std::fill(sigma_or_null, sigma_or_null + B, 0.0);
+        F2_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        return F2_OK;
+    }
+    return f2_host_wait(ctx, mem_space);
+}
+
+int f2_input_batch_noisy(f2_ctx* ctx, const void* wave, int wave_dtype, const int64_t* offsets, const double* coefs, int B, int C,
+                         int lpf, double cutoff_hz, int fft_precision, const int64_t* center_offsets, const int64_t* centers,
+                         int radius, int step, int normalize, const double* snr_db, int K, const int32_t* level_of,
+                         uint32_t first_utterance, uint64_t seed, float* windows, int mem_space) {
+    const f2_noise_pick_args N = {snr_db, K, level_of, first_utterance, seed};
+    int64_t n_windows;
+    std::vector<int> win_utt;
+    F2_TRY(f2_check_input_batch(ctx, wave, wave_dtype, offsets, coefs, B, C, lpf, cutoff_hz, fft_precision, center_offsets, centers, radius,
+                             step, windows, mem_space, &N, &n_windows, &win_utt));
+    if (n_windows == 0) return F2_OK;
+    const void* d_wave;
+    F2_TRY(f2_stage_wave(ctx, wave, wave_dtype, offsets[B], mem_space, &d_wave));
+    f2_output win;
+    F2_TRY(f2_place(ctx, ctx->xbuf, windows, sizeof(float) * (size_t)n_windows * (2 * radius + 1) * (size_t)C, mem_space, true, &win));
+    F2_TRY(reset_flag(ctx));
+    F2_TRY(f2_launch_noisy_windows(ctx, d_wave, wave_dtype, offsets, coefs, B, C, lpf, cutoff_hz, fft_precision, centers, win_utt.data(),
+                                   false, n_windows, radius, step, normalize, N, win.as<float>()));
     return finish_windows(ctx, win, normalize);
 }
 

@@ -8,6 +8,9 @@ accuracy (min_delta 0.01, patience 5), trained with PyTorch-ROCm autograd as the
 produces weights; every forward pass used for evaluation is HIP kernel K4 (the trained weights are written in the
 ``.npz`` container K4 loads, under the reference's file name ``last_trained_model``).
 
+``TrainFromWav`` (`cnn train --engine hip --from-wav`, not in the reference) trains on windows the device renders from the WAV files,
+again before every epoch under fresh noise when asked (``--augment-snrs``).
+
 ``TestModel`` (`cnn test`, not in the reference) is ``model.evaluate(x_test, y_test)`` (:136) for a saved model, broken down
 by a column of the label CSV: one ``f2_cnn_score_windows`` call on the stored windows.
 """
@@ -177,30 +180,41 @@ def _torch_engine(x_train, y_train, x_test, y_test, batch_size, device, seed, lr
     return run_epoch, validate, lambda: F2CNNModel.from_torch_state_dict(net.state_dict(), rows, channels)
 
 
+def _hip_trainer(rows, channels, seed, lr, decay, ctx):
+    """(Trainer, rng of the epochs' order): initial weights F2CNNModel.glorot(seed, zero_bias=True) (Keras' defaults), the masks'
+    seed the run's; the same seed gives the same weights bit for bit"""
+    from ...trainer import Trainer
+    from ...model import F2CNNModel
+    rng = numpy.random.default_rng(seed)
+    mask_seed = int(seed) if seed is not None else int(rng.integers(0, 2 ** 63))
+    trainer = Trainer(F2CNNModel.glorot(seed, rows, channels, zero_bias=True), lr=lr, rho=0.9, eps=1e-7, decay=decay, drop=DROPOUT,
+                      seed=mask_seed, ctx=ctx)
+    return trainer, rng
+
+
+def _hip_validate(trainer, ctx, x_test, y_val, **groups):
+    """F2CNNModel.evaluate (f2_cnn_score_windows) of the trainer's exported weights on the validation windows"""
+    model = trainer.model()
+    try:
+        return model.evaluate(x_test, y_val, ctx=ctx, **groups)
+    finally:
+        model.release(ctx)
+
+
 def _hip_engine(x_train, y_train, x_test, y_test, batch_size, seed, lr, decay, ctx=None):
     """The library's own training step (f2_trainer_*): weights, RMSprop accumulators and the training set stay on the device, an
     epoch is one f2_trainer_steps call over a NumPy permutation. Initial weights F2CNNModel.glorot(seed, zero_bias=True) (Keras'
     defaults); the same seed gives the same weights bit for bit. Validation goes through F2CNNModel.evaluate
     (f2_cnn_score_windows) on the exported weights."""
-    from ...trainer import Trainer
-    from ...model import F2CNNModel
     ctx = ctx or _lib.default_context()       # (no library or no device: raises here)
-    rows, channels = x_train.shape[1], x_train.shape[2]
-    rng = numpy.random.default_rng(seed)
-    mask_seed = int(seed) if seed is not None else int(rng.integers(0, 2 ** 63))
-    trainer = Trainer(F2CNNModel.glorot(seed, rows, channels, zero_bias=True), lr=lr, rho=0.9, eps=1e-7, decay=decay, drop=DROPOUT,
-                      seed=mask_seed, ctx=ctx)
+    trainer, rng = _hip_trainer(x_train.shape[1], x_train.shape[2], seed, lr, decay, ctx)
     trainer.set_data(x_train, numpy.asarray(y_train))
     y_val = numpy.asarray(y_test)
 
     def validate():
         if not len(x_test):
             return float("nan"), float("nan")
-        model = trainer.model()
-        try:
-            return model.evaluate(x_test, y_val, ctx=ctx)
-        finally:
-            model.release(ctx)
+        return _hip_validate(trainer, ctx, x_test, y_val)
 
     return lambda: trainer.steps(rng.permutation(len(x_train)), batch_size), validate, trainer.model
 
@@ -220,7 +234,12 @@ def train_network(x_train, y_train, x_test, y_test, batch_size=32, epochs=20, de
         run_epoch, validate, export = _torch_engine(x_train, y_train, x_test, y_test, batch_size, device, seed, lr, decay)
     else:
         run_epoch, validate, export = _hip_engine(x_train, y_train, x_test, y_test, batch_size, seed, lr, decay)
-    n_train = len(x_train)
+    return fit_epochs(run_epoch, validate, export, len(x_train), epochs, verbose, min_delta, patience)
+
+
+def fit_epochs(run_epoch, validate, export, n_train, epochs, verbose=1, min_delta=0.01, patience=5):
+    """The epoch loop and the early-stopping rule every engine shares: run_epoch() -> (loss sum, hits) over the n_train windows,
+    validate() -> (val_loss, val_acc), export() -> F2CNNModel. Returns (export(), history)."""
     history = {"loss": [], "acc": [], "val_loss": [], "val_acc": []}
     best, wait = -numpy.inf, 0
     for epoch in range(epochs):
@@ -241,6 +260,199 @@ def train_network(x_train, y_train, x_test, y_test, batch_size=32, epochs=20, de
                     print("Epoch {:05d}: early stopping".format(epoch + 1))
                 break
     return export(), history
+
+
+class LabelledWaves:
+    """The label CSV read once: per file, in sorted key order (the row order of `prepare input`), `wavs` its WAV path
+    (wav_for_label_key), `centers` its timepoints in CSV order (int64), `signs` their 0 / 1 labels (uint8) and `is_test` whether its
+    rows say TEST. A label key without its WAV raises FileNotFoundError here; read(reach) loads the audio and raises ValueError
+    for a timepoint whose window leaves its file - both with GenerateInputDataFromWav's messages, before any device work."""
+
+    def __init__(self, labelFile):
+        from ..processing.InputGenerator import wav_for_label_key
+        from ..processing.LabelDataGenerator import CSV_COLUMNS
+        sign_col = CSV_COLUMNS.index('sign')
+        per_file = {}
+        with open(labelFile, 'r') as labels:
+            for i, row in enumerate(csv.reader(labels)):
+                if not row:
+                    continue
+                testOrTrain, region, speaker, sentence, _phoneme, timepoint = row[:6]
+                sign = int(row[sign_col])
+                if sign not in (0, 1):
+                    raise ValueError("row {}: sign {!r} is neither 0 nor 1".format(i, row[sign_col]))
+                key = os.path.join(testOrTrain, '.'.join((region, speaker, sentence, 'ENV1.npy')))
+                entry = per_file.setdefault(key, ([], [], testOrTrain == 'TEST'))
+                entry[0].append(int(timepoint))
+                entry[1].append(sign)
+        self.keys = sorted(per_file)
+        self.wavs = [wav_for_label_key(key) for key in self.keys]
+        self.centers = [numpy.array(per_file[key][0], numpy.int64) for key in self.keys]
+        self.signs = [numpy.array(per_file[key][1], numpy.uint8) for key in self.keys]
+        self.is_test = [per_file[key][2] for key in self.keys]
+        for key, wav in zip(self.keys, self.wavs):
+            if not os.path.isfile(wav):
+                raise FileNotFoundError("{} (label key {}) does not exist".format(wav, key))
+
+    def __len__(self):
+        return len(self.keys)
+
+    def read(self, reach):
+        """The samples of every file (int16, or float64 where the file is not 16-bit), each window checked against its file"""
+        from ...gammatone import filters
+        from ..processing.GammatoneFiltering import GetArrayFromWAV
+        waves = []
+        for wav, centers in zip(self.wavs, self.centers):
+            samples = filters._wave_args(GetArrayFromWAV(wav)[1])[0]
+            n = samples.shape[0]
+            for tp in centers:
+                if tp - reach < 0 or tp + reach >= n:
+                    raise ValueError("{}: the window at timepoint {} (+-{} samples) reaches outside its {} samples".format(
+                        wav, int(tp), reach, n))
+            waves.append(samples)
+        return waves
+
+    def split(self, test):
+        """indices of the TEST (test=True) or the other files"""
+        return [k for k, t in enumerate(self.is_test) if t == test]
+
+
+NOISE_STREAM = 0x6E6F6973       # 'nois': the generator of the epochs' noise conditions is default_rng([seed, NOISE_STREAM])
+VALIDATION_NOISE_SEED = 0x76616C69    # 'vali': the noisy validation sets are rendered once, with this seed
+RENDER_GROUP = 64               # files per envelope pass, as `prepare input --from-wav`
+
+
+def draw_epoch_noise(rng, K, B):
+    """(level_of (B) int32 in [0, K], noise seed) of one epoch, drawn from rng in that order"""
+    level_of = rng.integers(0, K + 1, B).astype(numpy.int32)
+    return level_of, int(rng.integers(0, 2 ** 63))
+
+
+def _render_windows(ctx, waves, centers, coefs, cfg, LPF, CUTOFF, precision, snrs=(), level=None, seed=0):
+    """Normalised windows of some files through f2_input_batch_noisy, RENDER_GROUP files per call, every file at snrs[level]
+    (level None: clean)"""
+    Cn = coefs.shape[0]
+    out = numpy.empty((int(sum(len(c) for c in centers)), cfg.dots_per_input, Cn), numpy.float32)
+    row = 0
+    for g in range(0, len(waves), RENDER_GROUP):
+        ws, cs = waves[g:g + RENDER_GROUP], centers[g:g + RENDER_GROUP]
+        f64 = any(w.dtype != numpy.int16 for w in ws)
+        flat = numpy.concatenate([w.astype(numpy.float64 if f64 else numpy.int16, copy=False) for w in ws])
+        offsets = numpy.concatenate([[0], numpy.cumsum([len(w) for w in ws])]).astype(numpy.int64)
+        center_offsets = numpy.concatenate([[0], numpy.cumsum([len(c) for c in cs])]).astype(numpy.int64)
+        n = int(center_offsets[-1])
+        if n == 0:
+            continue
+        level_of = None if level is None else numpy.full(len(ws), level, numpy.int32)
+        ctx.input_batch_noisy(flat, _lib.WAVE_F64 if f64 else _lib.WAVE_I16, offsets, coefs, len(ws), Cn, bool(LPF),
+                              float(CUTOFF) if LPF else 0.0, precision, center_offsets, numpy.concatenate(cs), cfg.radius, cfg.step,
+                              True, snrs, level_of, g, seed, out[row:row + n], _lib.MEM_HOST)
+        row += n
+    return out
+
+
+def TrainFromWav(labelFile=None, LPF=False, CUTOFF=100, snrs=(), seed=None, ctx=None, verbose=1, on_epoch=None):
+    """`cnn train --engine hip --from-wav`: trains on windows rendered on the device from the WAV files of the label CSV.
+
+    The TRAIN files go to the trainer once (Trainer.set_waves); the TEST files become normalised windows once, clean - the
+    validation set early stopping watches, by train_network's rule. Without `snrs` the training windows are rendered once, clean,
+    and the epochs are those of `cnn train --engine hip`. With `snrs` (dB) every epoch draws, from
+    numpy.random.default_rng([seed, NOISE_STREAM]), a level in [0, K] per file (K: clean) and a noise seed (draw_epoch_noise), and
+    renders the windows again before its steps; one more validation set per level is rendered once with
+    VALIDATION_NOISE_SEED, and the history gains 'val_acc_snr' / 'val_loss_snr' (a list per level, an entry per epoch).
+    'last_trained_model_results.json' gains augment = {snrs, seed, noise_seed per epoch}. seed None: one is drawn and recorded.
+    on_epoch(iterations, trainer), if given, is called after each epoch's render, before its steps (for tests and for looking at
+    what the network is about to see).
+    BATCH_SIZE and EPOCHS come from configF2CNN.conf. Returns (F2CNNModel, history)."""
+    from configparser import ConfigParser
+    from ...config import F2Config
+    from ..processing.EnvelopeExtraction import FFT_PRECISION
+    from ..processing.GammatoneFiltering import filterbank_from_config
+    config = ConfigParser()
+    config.read('configF2CNN.conf')
+    batch_size = config.getint('CNN', 'BATCH_SIZE', fallback=32)
+    epochs = config.getint('CNN', 'EPOCHS', fallback=20)
+    snrs = tuple(float(v) for v in snrs)
+    K = len(snrs)
+    if seed is None:
+        seed = int(numpy.random.default_rng().integers(0, 2 ** 63))
+    labelPath = labelFile or os.path.join('trainingData', 'label_data.csv')
+    cfg = F2Config()
+    lw = LabelledWaves(labelPath)
+    waves = lw.read(cfg.radius * cfg.step)
+    train, test = lw.split(False), lw.split(True)
+    y_train = numpy.concatenate([lw.signs[k] for k in train]) if train else numpy.zeros(0, numpy.uint8)
+    y_test = numpy.concatenate([lw.signs[k] for k in test]) if test else numpy.zeros(0, numpy.uint8)
+    if not len(y_train):
+        raise ValueError("{} has no TRAIN rows".format(labelPath))
+    print('Rising test:', int((y_test == 1).sum()))
+    print('Falling test:', int((y_test == 0).sum()))
+    print('Rising train:', int((y_train == 1).sum()))
+    print('Falling train:', int((y_train == 0).sum()))
+    print(len(train), 'train files,', len(test), 'test files; noise levels (dB):', list(snrs) or 'none')
+    _, coefs = filterbank_from_config(cfg)
+    coefs = numpy.ascontiguousarray(coefs, dtype=numpy.float64)
+    ctx = ctx or _lib.default_context()
+    try:
+        # validation windows: the clean set, then one set per level, in one array with the level as the group
+        val = [_render_windows(ctx, [waves[k] for k in test], [lw.centers[k] for k in test], coefs, cfg, LPF, CUTOFF, FFT_PRECISION)]
+        for l in range(K if len(y_test) else 0):
+            val.append(_render_windows(ctx, [waves[k] for k in test], [lw.centers[k] for k in test], coefs, cfg, LPF, CUTOFF,
+                                       FFT_PRECISION, snrs, l, VALIDATION_NOISE_SEED))
+        x_val, y_val = numpy.concatenate(val), numpy.tile(y_test, len(val))
+        groups = numpy.repeat(numpy.arange(len(val), dtype=numpy.int32), len(y_test))
+        trainer, rng = _hip_trainer(cfg.dots_per_input, coefs.shape[0], seed, 1e-4, 1e-6, ctx)
+        trainer.set_waves([waves[k] for k in train], [lw.centers[k] for k in train], [lw.signs[k] for k in train], coefs, cfg.radius,
+                          cfg.step, lpf=bool(LPF), cutoff=float(CUTOFF) if LPF else 0.0, precision=FFT_PRECISION, group=RENDER_GROUP)
+        noise_rng = numpy.random.default_rng([seed, NOISE_STREAM])
+        noise_seeds, val_snr = [], {"val_acc_snr": [[] for _ in snrs], "val_loss_snr": [[] for _ in snrs]}
+        if not K:
+            trainer.render()
+
+        def run_epoch():
+            if K:
+                level_of, noise_seed = draw_epoch_noise(noise_rng, K, len(train))
+                trainer.render(snrs, level_of, noise_seed)
+                noise_seeds.append(noise_seed)
+            if on_epoch:
+                on_epoch(trainer.iterations, trainer)
+            return trainer.steps(rng.permutation(len(y_train)), batch_size)
+
+        def validate():
+            if not len(y_test):
+                for k in val_snr:
+                    for per_level in val_snr[k]:
+                        per_level.append(float("nan"))
+                return float("nan"), float("nan")
+            _, _, counts, loss_sum = _hip_validate(trainer, ctx, x_val, y_val, groups=groups, n_groups=len(val))
+            acc = (counts[:, 0, 0] + counts[:, 1, 1]) / float(len(y_test))
+            loss = loss_sum / float(len(y_test))
+            for l in range(K):
+                val_snr["val_acc_snr"][l].append(float(acc[l + 1]))
+                val_snr["val_loss_snr"][l].append(float(loss[l + 1]))
+            if verbose and K:
+                print("    val_acc clean {:.4f}".format(acc[0]) + "".join(" | {:g} dB {:.4f}".format(s, a) for s, a in zip(snrs, acc[1:])))
+            return float(loss[0]), float(acc[0])
+
+        model, history = fit_epochs(run_epoch, validate, trainer.model, len(y_train), epochs, verbose)
+    except _lib.F2Error as e:
+        if e.code == _lib.F2_ERR_NONPOSITIVE:
+            raise ValueError("values must all be positive")
+        raise
+    if K:
+        history.update(val_snr)
+    model.save('last_trained_model')
+    print("Model saved as 'last_trained_model'.")
+    if len(y_test):
+        print('Test loss:', history["val_loss"][-1])
+        print('Test accuracy:', history["val_acc"][-1])
+    results = dict(history)
+    if K:
+        results["augment"] = {"snrs": list(snrs), "seed": int(seed), "noise_seed": noise_seeds}
+    with open('last_trained_model_results.json', 'w') as fp:
+        json.dump(results, fp)
+    print("History saved as 'last_trained_model_results.json'")
+    return model, history
 
 
 def TrainAndPlotLoss(labelFile=None, inputFile=None, device=None, seed=None, engine="torch"):

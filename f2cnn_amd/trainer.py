@@ -6,6 +6,12 @@ weight-gradient kernels, the optimiser and the refresh of the layouts the kernel
     t.set_data(x_train, y_train)                      # normalised float32 windows, 0 / 1 labels
     loss_sum, hits = t.steps(permutation, batch)      # one epoch: ceil(len / batch) steps, one wait
     model = t.model()                                 # the weights as an F2CNNModel
+
+A trainer can own the waves instead of the windows and rebuild the windows under new noise before every epoch:
+
+    t.set_waves(waves, centers, signs, coefs, radius=5, step=160)   # one array of samples and of centres per utterance
+    t.render(snrs=(20, 10), level_of=levels, seed=s)                # utterance b at snrs[levels[b]], len(snrs) = clean
+    x, y = t.windows()                                              # what the network is about to see
 """
 import numpy as np
 
@@ -43,6 +49,41 @@ class Trainer:
         if len(y) != len(x) or (len(y) and (y.min() < 0 or y.max() > 1)):
             raise ValueError("y holds one sign, 0 (falling) or 1 (rising), per window")
         self.ctx.trainer_set_data(self.handle, x, y)
+
+    def set_waves(self, waves, centers, signs, coefs, radius, step, lpf=False, cutoff=50.0, precision=None, group=64):
+        """The corpus the windows are rendered from: `waves` one int16 or float64 array per utterance, `centers` / `signs` one array
+        per utterance of window centres (samples from the utterance's start) and of 0 / 1 labels. Replaces set_data's windows."""
+        waves = [np.ascontiguousarray(w).reshape(-1) for w in waves]
+        if len(centers) != len(waves) or len(signs) != len(waves):
+            raise ValueError("centers and signs hold one array per utterance")
+        f64 = any(w.dtype != np.int16 for w in waves)
+        dtype = np.float64 if f64 else np.int16
+        wave = np.concatenate([w.astype(dtype, copy=False) for w in waves]) if waves else np.zeros(0, dtype)
+        offsets = np.concatenate([[0], np.cumsum([len(w) for w in waves])]).astype(np.int64)
+        cen = [np.asarray(c, dtype=np.int64).reshape(-1) for c in centers]
+        sg = [np.asarray(g).reshape(-1) for g in signs]
+        if any(len(c) != len(g) for c, g in zip(cen, sg)):
+            raise ValueError("every centre has one sign")
+        center_offsets = np.concatenate([[0], np.cumsum([len(c) for c in cen])]).astype(np.int64)
+        flat = np.concatenate(cen) if cen else np.zeros(0, np.int64)
+        y = np.concatenate(sg) if sg else np.zeros(0, np.uint8)
+        if len(y) and (y.min() < 0 or y.max() > 1):
+            raise ValueError("signs are 0 (falling) or 1 (rising)")
+        coefs = np.ascontiguousarray(coefs, dtype=np.float64)
+        self.ctx.trainer_set_waves(self.handle, wave, _lib.WAVE_F64 if f64 else _lib.WAVE_I16, offsets, coefs, len(waves), coefs.shape[0],
+                                   lpf, cutoff, _lib.FFT_F32 if precision is None else precision, center_offsets, flat,
+                                   y.astype(np.uint8), int(radius), int(step), group)
+
+    def render(self, snrs=(), level_of=None, seed=0):
+        """Rebuild the training windows from the stored waves: utterance b at snrs[level_of[b]] dB, clean where level_of[b] ==
+        len(snrs) or level_of is None; the noise of an utterance depends on (seed, its level, its number) alone."""
+        self.ctx.trainer_render(self.handle, snrs, level_of, seed)
+
+    def windows(self, first=0, count=None):
+        """(x, y): rows first .. first + count - 1 of the training set as it stands on the device (count None: to the end)"""
+        n = int(self.ctx.trainer_info(self.handle, "windows"))
+        count = n - first if count is None else count
+        return self.ctx.trainer_get_windows(self.handle, first, count, (self.rows, self.channels))
 
     def steps(self, order, batch):
         """(loss sum, windows decided as labelled) over the steps, each with the weights it started from"""

@@ -956,6 +956,66 @@ int f2_trainer_steps(f2_ctx* ctx, f2_trainer* trainer, const int64_t* order /* h
 int f2_trainer_get(f2_ctx* ctx, const f2_trainer* trainer, int what, float* const* tensors /* host, 12 pointers to host tensors */);
 int f2_trainer_get_info(f2_ctx* ctx, const f2_trainer* trainer, const char* key, double* value);
 
+/* ---- Training from the waves: windows re-rendered under fresh noise --------------------------------
+ * The reference adds noise to a waveform before the filterbank (scripts/CNN/Evaluating.py:193-221) and trains on a fixed tensor of
+ * stored windows, an epoch being one pass over it (scripts/CNN/Training.py:129-134). These entries rebuild the training windows from
+ * the audio under a new noise condition per utterance, so that an epoch can see the corpus as no earlier epoch did. (f2_version
+ * stays 115 with these entries: look the symbols up.)
+ *
+ * f2_noise_pick (stateless): f2_eval_noise_sweep's noise with one level per utterance. Utterance b runs at level l = level_of[b]:
+ *   l < K    sample i becomes clean + sigma_b * z, product and sum rounded separately, sigma_b = RMS(clean_b) / 10^(snr_db[l] / 10)
+ *            by the sweep's rule (int64 sums for int16, its fixed-order float64 sum otherwise) and z the sweep's deviate for
+ *            (seed, level l, utterance first_utterance + b, i)
+ *   l == K   the sample converted to float64, exactly
+ *   level_of == NULL or K == 0: every utterance is clean.
+ * With first_utterance == 0, utterance b of `noisy` is bit for bit utterance b of level level_of[b] of the sweep's noisy_or_null for
+ * the same snr_db and seed, and sigma[b] its sigma[level_of[b] * B + b]. A sample depends on (seed, level, utterance number, i)
+ * alone: not on B, the launch shape, the memory space or the input dtype of equal values. One workgroup per utterance for sigma,
+ * one thread per sample for the noise, plain vector stores.
+ *   wave, noisy      in mem_space (F2_MEM_HOST or F2_MEM_DEVICE); noisy: offsets[B] float64
+ *   offsets, snr_db (K), level_of (B, each in [0, K]), sigma_or_null (B)    host
+ * Errors, before anything is launched or written: what f2_eval_noise_sweep rejects of offsets, wave_dtype, mem_space and snr_db
+ * (non-finite), and its limit on (K + 1) * B (F2_ERR_UNSUPPORTED); K < 0, level_of given with K > 0 and a NULL snr_db, a level_of
+ * entry outside [0, K] (the message names the utterance): F2_ERR_INVALID; first_utterance + B beyond 2^32: F2_ERR_UNSUPPORTED.
+ * B == 0 or no samples: F2_OK. F2_MEM_DEVICE calls enqueue and return; they wait only when sigma_or_null is asked for.
+ *
+ * f2_input_batch_noisy: bit for bit f2_input_batch(F2_WAVE_F64, ...) on f2_noise_pick's output for the same arguments - that call's
+ * code on that buffer, which lives in context scratch and never leaves the device. Always the float64 route, also when every
+ * utterance is clean. f2_input_batch's checks and statuses plus those of f2_noise_pick.
+ *
+ * f2_trainer_set_waves / render / get_windows: a trainer that owns the waves.
+ *   set_waves    copies the waves, coefficients, centres and signs (host memory) to the device once. The training set becomes the
+ *                n = center_offsets[B] windows with labels `signs`; x is reserved and undefined until the first render. It
+ *                replaces what set_data put there, and set_data replaces it.
+ *   render       utterances in groups [g group, min((g + 1) group, B)): group g is bit for bit f2_input_batch_noisy on those
+ *                utterances with first_utterance = g group, normalize = 1 and the stored options, written straight to row
+ *                center_offsets[g group] of x. The envelope scratch is bounded by the group, not by the corpus. Everything is
+ *                enqueued on the context's stream; one wait at the end, for the error flag. level_of: host, B, or NULL.
+ *   get_windows  rows first .. first + count - 1 of x and of the labels to host memory (either pointer may be NULL)
+ *   get_info     "windows": n; "utterances": B of set_waves (0 after set_data)
+ * f2_trainer_steps is unchanged and trains on what was rendered last.
+ * F2_ERR_INVALID, with nothing changed: C or 2 radius + 1 other than the trainer's window shape, group < 1, a sign above 1, a window
+ * that leaves its utterance (found in set_waves; the message names utterance, centre and length as f2_input_batch's does), what
+ * f2_input_batch and f2_noise_pick reject, render without waves, rows outside [0, n) in get_windows. Utterances without centres,
+ * empty utterances, B == 0: F2_OK. F2_ERR_NONPOSITIVE from the normaliser comes back from render, with x unspecified.
+ */
+int f2_noise_pick(f2_ctx* ctx, const void* wave, int wave_dtype, const int64_t* offsets /* host, B+1 */, int B,
+                  const double* snr_db /* host, K */, int K, const int32_t* level_of /* host, B, each in [0, K] */,
+                  uint32_t first_utterance, uint64_t seed, double* noisy /* offsets[B] float64, mem_space */,
+                  double* sigma_or_null /* host, B */, int mem_space);
+int f2_input_batch_noisy(f2_ctx* ctx, const void* wave, int wave_dtype, const int64_t* offsets, const double* coefs, int B, int C,
+                         int lpf, double cutoff_hz, int fft_precision, const int64_t* center_offsets, const int64_t* centers,
+                         int radius, int step, int normalize, const double* snr_db, int K, const int32_t* level_of,
+                         uint32_t first_utterance, uint64_t seed, float* windows, int mem_space);
+int f2_trainer_set_waves(f2_ctx* ctx, f2_trainer* trainer, const void* wave /* host */, int wave_dtype, const int64_t* offsets,
+                         const double* coefs, int B, int C, int lpf, double cutoff_hz, int fft_precision,
+                         const int64_t* center_offsets, const int64_t* centers, const uint8_t* signs /* host, center_offsets[B] */,
+                         int radius, int step, int group);
+int f2_trainer_render(f2_ctx* ctx, f2_trainer* trainer, const double* snr_db, int K, const int32_t* level_of /* host, B, or NULL */,
+                      uint64_t seed);
+int f2_trainer_get_windows(f2_ctx* ctx, const f2_trainer* trainer, int64_t first, int64_t count, float* x /* host */,
+                           uint8_t* y /* host */);
+
 #ifdef __cplusplus
 }
 #endif
