@@ -13,7 +13,16 @@
 //     Y(k) = s [ u^4 N_1 N_2 N_3 N_4 X(k)  +  w^n u^4 Q(w) ],   Q = R_4 D^3 + N_4 R_3 D^2 + N_4 N_3 R_2 D + N_4 N_3 N_2 R_1
 //
 // is the DFT of the zero-padded filterbank row: the first term is the M-periodic steady response, the second removes
-// the ringing after sample n (which a circular product alone would wrap around). Q is evaluated through its D-adic
+// the ringing after sample n (which a circular product alone would wrap around). The factor w^n is there only because the
+// padding stands behind the row. Rows of up to 32768 samples are padded IN FRONT instead: the row sits at the transform's
+// indices [M - n, M), the cut between row and ringing falls on index M = 0, w^M = 1, and
+//
+//     Y'(k) = conj(w^n) Y(k) = s [ u^4 N_1 N_2 N_3 N_4 X'(k)  +  u^4 Q(w) ],   X' = DFT_M(x padded in front)
+//
+// (k_utterance_spectrum shifts its sample index while loading; zeros fed to a zero state leave it zero, so the filter's
+// states, the digits below and the tables are the same). The analytic signal of a circularly shifted sequence is the
+// shifted analytic signal: the same envelope, found M - n indices later. k_spectral_envelope_long keeps the first form.
+// Q is evaluated through its D-adic
 // digits  Q = r_0 + r_1 D + r_2 D^2 + r_3 D^3  (deg r_j <= 1):  u^4 Q = u (r_3 + u (r_2 + u (r_1 + u r_0))), a Horner
 // chain without cancellation (the monomial form of Q loses 1/|D|^3 ~ 1e9 near the resonance of the low channels).
 // The state words at sample n only depend on the last L samples of the utterance (poles of radius r: n^3 r^n < 1e-8
@@ -30,7 +39,7 @@
 // Accuracy guard: the two terms of Y are rounded in float32 separately, each ~6e-8 of the LARGER of (steady response,
 // ringing). A row whose ringing after sample n dwarfs everything inside [0, n) (an isolated click in the last
 // milliseconds) would therefore lose accuracy relative to its own maximum. Every workgroup computes all M samples
-// anyway: the real part of a over the padding region [n, M) - the zero-padded row itself, zero in exact arithmetic
+// anyway: the real part of a over the padding region ([n, M), or [0, M - n) in front) - the zero-padded row itself, zero in exact arithmetic
 // (the imaginary part is not: a Hilbert transform is not time-limited) - measures the error directly;
 // if its maximum exceeds `tol` x the row's maximum the utterance is flagged and the caller's K1 -> K2 launches (which skip
 // unflagged utterances) recompute it. Utterances with fewer padding samples than the slowest channel's ringing needs to
@@ -90,6 +99,17 @@ __device__ __forceinline__ void store_row_pair_buf(__amdgpu_buffer_rsrc_t r, int
         __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(f2_u2, a), r, i0 * 8, 0, KS_STORE_AUX);
     }
 }
+// envelope samples t0, t0 + 1 of a row that ends with the transform (padding in front): t0 + 1 always lies inside the row, t0 = -1
+// is the pair that straddles the row's start (odd padding) and stores its second element only; pairs further in front store
+// nothing. (Tested here, not left to the buffer's range check: a negative offset would drop both halves of the straddling pair.)
+__device__ __forceinline__ void store_row_pair_front(__amdgpu_buffer_rsrc_t r, int t0, double a, double b) {
+    if (t0 >= 0) {
+        const f2_d2 v = {a, b};
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(f2_u4, v), r, t0 * 8, 0, KS_STORE_AUX);
+    } else if (t0 == -1) {
+        __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(f2_u2, b), r, 0, 0, KS_STORE_AUX);
+    }
+}
 
 // ---- first-order low-pass in the register layout of the transforms, constants from a table ----
 // Same decomposition as lowpass_pairs_store (f2_envelope_core.h: pair -> weighted DPP scan over the wave -> wave totals ->
@@ -142,13 +162,16 @@ constexpr size_t lowpass_tab_lds_bytes() {
 // CHAINED (rows longer than one sweep of the workgroup, k_spectral_envelope_long): the pairs are those of the samples from
 // `ibase` on, *ychain = s[ibase - 1] on entry and s[ibase + 2 NT NBLK - 1] on return.
 // Returns this thread's maximum of |y| over the odd samples it stored (the accuracy guard's denominator when the low-pass is on).
-// INSIDE15: every block but the last lies entirely inside the row (n >= 15/16 of the samples the blocks cover): those blocks store
-// and take their maxima without a test per lane.
-template <int NT, int NBLK, bool CHAINED = false, bool INSIDE15 = false>
+// Not CHAINED (k_spectral_envelope): the row is padded IN FRONT - pair index i is row sample i - np, np = 2 NT NBLK - n, the row
+// ends with the last pair. The caller has set the inputs in front of the row to 0 (zero_front_padding): the zero state then
+// holds up to the row's first sample, also when that is the odd element of its pair (s0 = 0, y1 = b0 e: y[0] = b0 e[0]).
+// INSIDE_BUT_FIRST: every block but the first lies entirely inside the row (n >= 15/16 of the samples the blocks cover): those
+// blocks store and take their maxima without a test per lane.
+template <int NT, int NBLK, bool CHAINED = false, bool INSIDE_BUT_FIRST = false>
 __device__ __forceinline__ float lowpass_pairs_store_tab(const float (&er)[NBLK], const float (&ei)[NBLK], const LowpassConsts& K,
                                                         const f2_f4* __restrict__ lptab, unsigned char* smem,
                                                         double* __restrict__ y, int n, int tid, int ibase = 0,
-                                                        double* ychain = nullptr) {
+                                                        double* ychain = nullptr, int np = 0) {
     static_assert(NBLK == 16, "sixteen blocks: one DPP row chains them");
     constexpr int NW = NT / 64;
     float* wtot = reinterpret_cast<float*>(smem);  // [NBLK][NW] zero-state s at the end of each wave
@@ -209,7 +232,9 @@ __device__ __forceinline__ float lowpass_pairs_store_tab(const float (&er)[NBLK]
     const __amdgpu_buffer_rsrc_t yb = CHAINED ? row_buffer_uniform(y, n) : row_buffer(y, n);
     float ymax = 0.f;
 #pragma unroll
-    for (int jj = 0; jj < NBLK; ++jj) {
+    for (int k = 0; k < NBLK; ++k) {
+        // (INSIDE_BUT_FIRST: the block with the tests comes last - the LDS reads of the others are then issued together)
+        const int jj = INSIDE_BUT_FIRST ? (k + 1) % NBLK : k;
         const float cw = cwl[jj * NW + wv];
         const float sin_ = fmaf(tc.x, cw, sc[jj]);            // zero-state value at the end of this pair
         const float up = dpp_mov<0x138, 0xF>(sin_);            // wave_shr:1
@@ -221,30 +246,20 @@ __device__ __forceinline__ float lowpass_pairs_store_tab(const float (&er)[NBLK]
         const float y1 = K.b0f * (s1 + s0);
         const int i0 = ibase + 2 * (tid + NT * jj);
         // every second output sample is enough for the maximum of a low-passed row (it only scales the guard's threshold);
-        // block boundaries are wave-uniform: only the block that holds sample n - 1 masks per lane
-        if constexpr (INSIDE15) {
-            if (jj < NBLK - 1) {
-                store_row_pair_inside(yb, i0, (double)y0, (double)y1);
-                ymax = fmaxf(ymax, fabsf(y1));
-            } else {
-                store_row_pair_buf(yb, n, i0, (double)y0, (double)y1);
-                ymax = fmaxf(ymax, i0 + 1 < n ? fabsf(y1) : (i0 < n ? fabsf(y0) : 0.f));
-            }
-        } else if constexpr (CHAINED) {
+        // block boundaries are wave-uniform: only the block that holds the row's first (CHAINED: last) sample masks per lane
+        if constexpr (CHAINED) {
             // (the long-row kernel is short of registers: per-lane tests cost it less than the uniform branches' live ranges)
             store_row_pair_buf(yb, n, i0, (double)y0, (double)y1);
             const int lo = ibase + 2 * NT * jj;
             if (lo + 2 * NT <= n) ymax = fmaxf(ymax, fabsf(y1));
             else if (lo < n) ymax = fmaxf(ymax, i0 + 1 < n ? fabsf(y1) : fabsf(y0));
         } else {
-            const int lo = ibase + 2 * NT * jj;
-            if (lo + 2 * NT <= n) {                      // (wave-uniform: the whole block lies inside the row)
-                store_row_pair_inside(yb, i0, (double)y0, (double)y1);
-                ymax = fmaxf(ymax, fabsf(y1));
-            } else if (lo < n) {
-                store_row_pair_buf(yb, n, i0, (double)y0, (double)y1);
-                ymax = fmaxf(ymax, i0 + 1 < n ? fabsf(y1) : (i0 < n ? fabsf(y0) : 0.f));
-            }
+            // (in front of the row the inputs were zeroed, so y is 0 there: the maximum needs no mask. The second half of the
+            // blocks lies inside every row of a length class, n > M / 2)
+            ymax = fmaxf(ymax, fabsf(y1));
+            const int lo = 2 * NT * jj;
+            if ((INSIDE_BUT_FIRST && jj > 0) || jj >= NBLK / 2 || lo >= np) store_row_pair_inside(yb, i0 - np, (double)y0, (double)y1);
+            else if (lo + 2 * NT > np) store_row_pair_front(yb, i0 - np, (double)y0, (double)y1);
         }
     }
     return ymax;
@@ -266,8 +281,8 @@ struct SpecParams {
     unsigned long long* stamps;   // diagnostic build only
 };
 
-// Y'(k) = (2/M) Y(k) of one bin
-__device__ __forceinline__ cpx<float> spectral_bin(cpx<float> X, f2_f4 hu, cpx<float> w, cpx<float> z, const float* __restrict__ rho) {
+// the ringing term (2/M) s u^4 Q(w) of one bin: the Horner chain over the digits of Q
+__device__ __forceinline__ cpx<float> ringing_bin(f2_f4 hu, cpx<float> w, const float* __restrict__ rho) {
     const float ur = hu.z, ui = hu.w;
     float tr = fmaf(rho[1], w.re, rho[0]), ti = rho[1] * w.im;
 #pragma unroll
@@ -278,7 +293,19 @@ __device__ __forceinline__ cpx<float> spectral_bin(cpx<float> X, f2_f4 hu, cpx<f
         tr = nr;
         ti = ni;
     }
-    const float qr = ur * tr - ui * ti, qi = ur * ti + ui * tr;
+    return {ur * tr - ui * ti, ur * ti + ui * tr};
+}
+// Y'(k) = (2/M) Y(k) of one bin, row padded in front: the cut between row and ringing falls on index M = 0, no phase factor
+__device__ __forceinline__ cpx<float> spectral_bin(cpx<float> X, f2_f4 hu, cpx<float> w, const float* __restrict__ rho) {
+    const cpx<float> q = ringing_bin(hu, w, rho);
+    const float yr = fmaf(-hu.y, X.im, fmaf(hu.x, X.re, q.re));
+    const float yi = fmaf(hu.y, X.re, fmaf(hu.x, X.im, q.im));
+    return {yr, yi};
+}
+// ... row padded behind sample n (long rows): z = w^n moves the ringing term to the cut
+__device__ __forceinline__ cpx<float> spectral_bin(cpx<float> X, f2_f4 hu, cpx<float> w, cpx<float> z, const float* __restrict__ rho) {
+    const cpx<float> q = ringing_bin(hu, w, rho);
+    const float qr = q.re, qi = q.im;
     float yr = hu.x * X.re;
     yr = fmaf(-hu.y, X.im, yr);
     yr = fmaf(z.re, qr, yr);
@@ -331,20 +358,34 @@ __device__ __forceinline__ float wave_max63(float v) {
     return v;
 }
 
-// max |Re a| over this thread's samples in the padding region [n, M): v[brev(j)] = sample 2 (tid + NT j) + odd.
-// PADLAST: every row of the launch has its padding inside the last block (n >= 15/16 M: every 1 s row of a 16384-point class).
-template <int R0, int NT, bool PADLAST>
-__device__ __forceinline__ float pad_residual(const cpx<float> (&v)[R0], int n, int tid, int odd, float gout) {
-    if constexpr (PADLAST) {
-        return fmaxf(gout, 2 * (tid + NT * (R0 - 1)) + odd >= n ? fabsf(v[brev<R0>(R0 - 1)].re) : 0.f);
+// max |Re a| over this thread's samples in the padding region [0, np), np = M - n: v[brev(j)] = sample 2 (tid + NT j) + odd.
+// PADFIRST: every row of the launch has its padding inside the first block (n >= 15/16 M: every 1 s row of a 16384-point class).
+template <int R0, int NT, bool PADFIRST>
+__device__ __forceinline__ float pad_residual(const cpx<float> (&v)[R0], int np, int tid, int odd, float gout) {
+    if constexpr (PADFIRST) {
+        return fmaxf(gout, 2 * tid + odd < np ? fabsf(v[brev<R0>(0)].re) : 0.f);
     } else {
-        // sample 2 (tid + NT j) + odd >= n  <=>  j >= jmin (one register; the compiler would otherwise keep sixteen sample indices)
-        int jmin = (n - 2 * tid - odd + 2 * NT - 1) >> (__builtin_ctz(2 * NT));
-        asm volatile("" : "+v"(jmin));
-        // (rows of this length class have n > M / 2: the first half of the blocks never holds padding)
+        // sample 2 (tid + NT j) + odd < np  <=>  j < jlim (one register; the compiler would otherwise keep sixteen sample indices)
+        int jlim = (np - 2 * tid - odd + 2 * NT - 1) >> (__builtin_ctz(2 * NT));
+        asm volatile("" : "+v"(jlim));
+        // (rows of this length class have n > M / 2: the second half of the blocks never holds padding)
 #pragma unroll
-        for (int j = R0 / 2; j < R0; ++j) gout = fmaxf(gout, j >= jmin ? fabsf(v[brev<R0>(j)].re) : 0.f);
+        for (int j = 0; j < R0 / 2; ++j) gout = fmaxf(gout, j < jlim ? fabsf(v[brev<R0>(j)].re) : 0.f);
         return gout;
+    }
+}
+
+// the envelope in front of the row is not part of it (|a| there is the Hilbert transform's tail, not zero): set to 0 before the
+// low-pass scans the pairs. FIRSTONLY: the padding lies inside block 0; otherwise inside the first half of the blocks (n > M / 2).
+// Selects against one register (branches here would have the compiler copy both arrays where they join).
+template <int NT, int NBLK, bool FIRSTONLY>
+__device__ __forceinline__ void zero_front_padding(float (&er)[NBLK], float (&ei)[NBLK], int np, int tid) {
+    int d = 2 * tid - np;            // pair (i0, i0 + 1) of block jj: i0 - np = d + 2 NT jj
+    asm volatile("" : "+v"(d));
+#pragma unroll
+    for (int jj = 0; jj < (FIRSTONLY ? 1 : NBLK / 2); ++jj) {
+        er[jj] = d >= -2 * NT * jj ? er[jj] : 0.f;
+        ei[jj] = d >= -2 * NT * jj - 1 ? ei[jj] : 0.f;
     }
 }
 
@@ -364,7 +405,7 @@ __device__ __forceinline__ void guard_decide(const SpecParams& P, const unsigned
     }
 }
 
-template <int LOG2H, bool PADLAST>
+template <int LOG2H, bool PADFIRST>
 __global__ __launch_bounds__((threads_for<float, LOG2H>()), (min_waves_for<float, LOG2H>())) void k_spectral_envelope(
     SpecParams P, const cpx<float>* __restrict__ Xall /* utterance spectra */, const f2_f4* __restrict__ HUall,
     const cpx<float>* __restrict__ E /* [M] exp(-2 pi i q / M) */, const float* __restrict__ rho_all /* [rows][8] digits of Q */,
@@ -386,7 +427,7 @@ __global__ __launch_bounds__((threads_for<float, LOG2H>()), (min_waves_for<float
     __shared__ __attribute__((aligned(16))) unsigned char smem[LDS_BYTES];
     constexpr int TWL = plan_tw_lds_count(LOG2H);
     __shared__ __attribute__((aligned(16))) cpx<float> twl[TWL > 0 ? TWL : 1];
-    __shared__ unsigned guard[4];   // max |a| inside [0, n) / Re a inside [n, M) / low-passed row maximum, as float bits (>= 0); waves counted in
+    __shared__ unsigned guard[4];   // max |a| inside the row / Re a inside the padding / low-passed row maximum, as float bits (>= 0); waves counted in
     cpx<float>* lds = reinterpret_cast<cpx<float>*>(smem);
 
     const int tid = threadIdx.x;
@@ -408,6 +449,7 @@ __global__ __launch_bounds__((threads_for<float, LOG2H>()), (min_waves_for<float
     const int b = ulist[u];
     const int64_t off = offsets[b];
     const int n = (int)(offsets[b + 1] - off);
+    const int np = M - n;            // the row is padded in front: transform sample i is row sample i - np
     double* __restrict__ y = P.env + ((size_t)P.C * (size_t)off + (size_t)c * (size_t)n);
     const float* __restrict__ rho = rho_all + (size_t)row_id * 8;
     const cpx<float>* __restrict__ Xu = Xall + (size_t)u * P.xpitch;
@@ -418,20 +460,18 @@ __global__ __launch_bounds__((threads_for<float, LOG2H>()), (min_waves_for<float
     for (int i = tid; i < TWL; i += NT) twl[i] = tw[plan_tw_offset(LOG2H, 1) + i];
     if (tid < 4) guard[tid] = 0u;
 
-    // 1. spectrum of the zero-padded row at this thread's bins k = tid + j NB0 (first-pass register layout). Per bin two
-    //    loads (utterance spectrum, channel table); the two phase factors follow from one load each: w_k = w_tid e^{-2 pi i
-    //    j / 32} (compile-time constants) and w_k^n = w_tid^n (w_NB0^n)^j (wave-uniform factors, scalar loads). The bins
-    //    go in groups of GB with the next group's loads in flight - all 32 loads at once would need 96 registers.
+    // 1. spectrum of the front-padded row at this thread's bins k = tid + j NB0 (first-pass register layout). Per bin two
+    //    loads (utterance spectrum, channel table); the phase factor follows from one load: w_k = w_tid e^{-2 pi i j / 32}
+    //    (compile-time constants). No load of this phase needs the row's length (the end of the scalar chain ulist -> offsets).
+    //    The bins go in groups of GB with the next group's loads in flight - all 32 loads at once would need 96 registers.
     static_assert(ITER0 == 1 && R0 == 16, "one radix-16 butterfly per thread in the first pass");
     constexpr int GB = SPEC_GB, NG = R0 / GB;
     cpx<float> yk[PT], v[PT];
     // rows whose first pass is one radix-16 butterfly per thread (all three length classes served): the two transforms share it
     static_assert(NB0 == NT && plan_npass(LOG2H) >= 3, "fft_pass0_pair + fft_from_pass0");
     cpx<float> vo[PT];   // conj(A_o) / M = conj(A) w_k / M, formed while the bin's phase factor is at hand
-    const unsigned zstep = ((unsigned)NB0 * (unsigned)n) & (M - 1);
     cpx<float> w0 = E[tid];
-    cpx<float> z0 = E[__umul24((unsigned)tid, (unsigned)n) & (M - 1)];
-    const cpx<float> XH = Xu[H];     // Nyquist bin (wave-uniform addresses: scalar loads, issued up front)
+    const cpx<float> XH = Xu[H];    // Nyquist bin (wave-uniform addresses: scalar loads, issued up front)
     const f2_f4 HUH = HUc[H];
     cpx<float> Xl[2][GB];
     f2_f4 Hl[2][GB];
@@ -456,9 +496,8 @@ __global__ __launch_bounds__((threads_for<float, LOG2H>()), (min_waves_for<float
 #pragma unroll
         for (int q = 0; q < GB; ++q) {
             const int j = g * GB + q;
-            const cpx<float> zj = E[(j * zstep) & (M - 1)];                       // wave-uniform
             const cpx<float> wj = bin_w<R0>(w0, j);
-            yk[j] = spectral_bin(Xl[g & 1][q], Hl[g & 1][q], wj, cmul(z0, zj), rho);
+            yk[j] = spectral_bin(Xl[g & 1][q], Hl[g & 1][q], wj, rho);
             vo[j] = {yk[j].re * wj.re + yk[j].im * wj.im, yk[j].re * wj.im - yk[j].im * wj.re};
 #ifdef F2_STAMPS
             if (j == 0 || j == 7) {
@@ -468,8 +507,8 @@ __global__ __launch_bounds__((threads_for<float, LOG2H>()), (min_waves_for<float
             }
 #endif
         }
-        // (w0 / z0 pass through as well: the phase factors of a later group are then not formed ahead of time either)
-        asm volatile("" : "+v"(kb), "+v"(w0.re), "+v"(w0.im), "+v"(z0.re), "+v"(z0.im), "+v"(yk[g * GB].re), "+v"(yk[g * GB + GB - 1].re));
+        // (w0 passes through as well: the phase factors of a later group are then not formed ahead of time either)
+        asm volatile("" : "+v"(kb), "+v"(w0.re), "+v"(w0.im), "+v"(yk[g * GB].re), "+v"(yk[g * GB + GB - 1].re));
     }
 #ifdef F2_STAMPS
     asm volatile("s_nop 0" : "+v"(yk[15].re), "+v"(yk[15].im));
@@ -479,14 +518,15 @@ __global__ __launch_bounds__((threads_for<float, LOG2H>()), (min_waves_for<float
     // k = 0 carries the Nyquist term: A_e(0) = A(0) + A(H), A_o(0) = A(0) - A(H) (both real); thread 0 keeps
     // (Y'(0), Y'(H)) in yk[0]
     if (tid == 0) {
-        const cpx<float> yh = spectral_bin(XH, HUH, cpx<float>{-1.f, 0.f}, cpx<float>{(n & 1) ? -1.f : 1.f, 0.f}, rho);
+        const cpx<float> yh = spectral_bin(XH, HUH, cpx<float>{-1.f, 0.f}, rho);
         yk[0] = {yk[0].re, yh.re};
     }
     float er[NBLK], ei[NBLK];
-    // 4. accuracy guard: block jj of this thread is the sample pair 2 (tid + NT jj), + 1. Inside [0, n) the row's maximum;
-    //    over the WHOLE padding region [n, M) the real part of a (the zero-padded row itself: zero in exact arithmetic,
-    //    while the imaginary part, the Hilbert transform of a time-limited signal, is not) - the error itself, including the
-    //    ringing-shaped part that starts at n. Block boundaries are wave-uniform: only blocks that hold padding pay for it.
+    // 4. accuracy guard: block jj of this thread is the sample pair 2 (tid + NT jj), + 1 of the transform. Inside the row,
+    //    [np, M), the row's maximum; over the WHOLE padding region [0, np) the real part of a (the zero-padded row itself:
+    //    zero in exact arithmetic, while the imaginary part, the Hilbert transform of a time-limited signal, is not) - the
+    //    error itself, including the ringing-shaped part that starts at M = 0. Block boundaries are wave-uniform: only
+    //    blocks that hold padding pay for it.
     float gin = 0.f, gout = 0.f;
     constexpr bool T0R = derive_tw0<float, LOG2H>();
     {
@@ -504,7 +544,7 @@ __global__ __launch_bounds__((threads_for<float, LOG2H>()), (min_waves_for<float
         asm volatile("" : "+v"(tid_e), "+v"(v[0].re), "+v"(vo[PT - 1].im));
         fft_pass0_pair<LOG2H, NT, PT>(tw, tid_e, v, vo);
         fft_from_pass0<LOG2H, PT, NT, T0R>(lds, tw, twl, tid_e, v);
-        gout = pad_residual<R0, NT, PADLAST>(v, n, tid, 0, gout);
+        gout = pad_residual<R0, NT, PADFIRST>(v, np, tid, 0, gout);
 #pragma unroll
         for (int j = 0; j < R0; ++j) {
             const cpx<float> a = v[brev<R0>(j)];
@@ -512,23 +552,17 @@ __global__ __launch_bounds__((threads_for<float, LOG2H>()), (min_waves_for<float
         }
         fft_from_pass0<LOG2H, PT, NT, T0R>(lds, tw, twl, tid_e, vo);
         F2_STAMP(st, 5);
-        gout = pad_residual<R0, NT, PADLAST>(vo, n, tid, 1, gout);
+        gout = pad_residual<R0, NT, PADFIRST>(vo, np, tid, 1, gout);
 #pragma unroll
         for (int j = 0; j < R0; ++j) {
             const cpx<float> a = vo[brev<R0>(j)];
             ei[j] = fsqrt(a.re * a.re + a.im * a.im);
         }
     }
+    // (the magnitudes in front of the row leave here: the row's maximum then needs no test, and the low-pass starts from zeros)
+    zero_front_padding<NT, NBLK, PADFIRST>(er, ei, np, tid);
 #pragma unroll
-    for (int jj = 0; jj < NBLK; ++jj) {
-        const int lo = 2 * NT * jj;
-        if ((PADLAST && jj < NBLK - 1) || lo + 2 * NT <= n) {     // (PADLAST: every block but the last is inside the row)
-            gin = fmaxf(gin, fmaxf(er[jj], ei[jj]));
-        } else if (lo < n) {
-            const int i0 = lo + 2 * tid;
-            gin = fmaxf(gin, fmaxf(i0 < n ? er[jj] : 0.f, i0 + 1 < n ? ei[jj] : 0.f));
-        }
-    }
+    for (int jj = 0; jj < NBLK; ++jj) gin = fmaxf(gin, fmaxf(er[jj], ei[jj]));
     float glp = 0.f;
     wave_max63x2(gin, gout);
     if ((tid & 63) == 63) {           // (posted here: they travel while the low-pass runs)
@@ -541,13 +575,15 @@ __global__ __launch_bounds__((threads_for<float, LOG2H>()), (min_waves_for<float
         const __amdgpu_buffer_rsrc_t yb = row_buffer(y, n);
 #pragma unroll
         for (int jj = 0; jj < NBLK; ++jj) {
-            if ((PADLAST && jj < NBLK - 1) || 2 * NT * (jj + 1) <= n) store_row_pair_inside(yb, 2 * (tid + NT * jj), (double)er[jj], (double)ei[jj]);
-            else if (2 * NT * jj < n) store_row_pair_buf(yb, n, 2 * (tid + NT * jj), (double)er[jj], (double)ei[jj]);
+            const int t0 = 2 * (tid + NT * jj) - np;     // row sample of the pair's first element
+            // (PADFIRST: every block but the first is inside the row; always: the second half of the blocks, n > M / 2)
+            if ((PADFIRST && jj > 0) || jj >= NBLK / 2 || 2 * NT * jj >= np) store_row_pair_inside(yb, t0, (double)er[jj], (double)ei[jj]);
+            else if (2 * NT * (jj + 1) > np) store_row_pair_front(yb, t0, (double)er[jj], (double)ei[jj]);
         }
     } else {
         // the parity bar is written on the LOW-PASSED row (EnvelopeExtraction.py:57-66): its maximum, which a bursty row
         // keeps several times below the raw one, is what the residual is compared with
-        glp = wave_max63(lowpass_pairs_store_tab<NT, NBLK, false, PADLAST>(er, ei, P.lp, lptab, smem, y, n, tid));   // (contains barriers)
+        glp = wave_max63(lowpass_pairs_store_tab<NT, NBLK, false, PADFIRST>(er, ei, P.lp, lptab, smem, y, n, tid, 0, nullptr, np));   // (contains barriers)
     }
     // No barrier for the verdict: every wave posts its maxima and then counts itself in; the LDS serves a wave's operations in
     // order, so the wave that counts in last sees everybody's maxima and decides for the row.
@@ -761,7 +797,10 @@ __global__ __launch_bounds__(1024, 4) void k_spectral_envelope_long(
 // decimated in time: workgroup (utterance, p) transforms x_p[m] = x[D m + p] and leaves its float64 spectrum
 // X_p(k), k = 0..HS; k_spectrum_combine then forms X(k) = sum_p W_M^(p k) X_p(k mod 2 HS) (X_p is 2 HS-periodic and
 // conjugate-symmetric), k = 0..M/2.
-template <typename WaveT, int LOG2HS, int LOGD>
+// FRONT: the utterance is padded in front, x'[t] = x[t - (M - n)] (0 for t < M - n) - the sequence the front-padded rows of
+// k_spectral_envelope are filtered from. The shift is applied while loading, before the decimation (an odd M - n swaps what
+// the two phases of LOGD = 1 hold, nothing else); k_spectrum_combine is the same for both paddings.
+template <typename WaveT, int LOG2HS, int LOGD, bool FRONT>
 __global__ __launch_bounds__((threads_for<double, LOG2HS>())) void k_utterance_spectrum(const WaveT* __restrict__ wave,
                                                                                       const int64_t* __restrict__ offsets,
                                                                                       const int* __restrict__ ulist,
@@ -788,6 +827,7 @@ __global__ __launch_bounds__((threads_for<double, LOG2HS>())) void k_utterance_s
     const int64_t off = offsets[b];
     const int n = (int)(offsets[b + 1] - off);
     const WaveT* __restrict__ x = wave + off;
+    const int np = FRONT ? 2 * D * H - n : 0;   // samples of padding in front
     for (int i = tid; i < TWL; i += NT) twl[i] = tw[plan_tw_offset(LOG2H, 1) + i];
     cpx<double> v[PT];
 #pragma unroll
@@ -796,8 +836,8 @@ __global__ __launch_bounds__((threads_for<double, LOG2HS>())) void k_utterance_s
         if (FULL0 || bf < NB0) {
 #pragma unroll
             for (int j = 0; j < R0; ++j) {
-                const int i0 = D * 2 * (bf + j * NB0) + ph, i1 = i0 + D;   // samples 2 m' and 2 m' + 1 of x_p
-                v[i * R0 + j] = {i0 < n ? (double)x[i0] : 0.0, i1 < n ? (double)x[i1] : 0.0};
+                const int i0 = D * 2 * (bf + j * NB0) + ph - np, i1 = i0 + D;   // samples 2 m' and 2 m' + 1 of x_p
+                v[i * R0 + j] = {i0 >= 0 && i0 < n ? (double)x[i0] : 0.0, i1 >= 0 && i1 < n ? (double)x[i1] : 0.0};
             }
         }
     }
@@ -1171,7 +1211,8 @@ static int launch_group(f2_ctx* ctx, const WaveT* d_wave, const int64_t* d_offse
         F2_TRY(f2_reserve(ctx, ctx->spec_xpart, sizeof(double) * 2 * ((size_t)(1 << LOG2HS) + 1) * (size_t)nutt << LOGD));
         d_part = (cpx<double>*)ctx->spec_xpart.ptr;
     }
-    hipLaunchKernelGGL((k_utterance_spectrum<WaveT, LOG2HS, LOGD>), dim3((unsigned)nutt << LOGD), dim3(threads_for<double, LOG2HS>()),
+    constexpr bool FRONT = LOG2H != 15;   // (the long-row kernel still pads behind the row)
+    hipLaunchKernelGGL((k_utterance_spectrum<WaveT, LOG2HS, LOGD, FRONT>), dim3((unsigned)nutt << LOGD), dim3(threads_for<double, LOG2HS>()),
                        0, ctx->stream, d_wave, d_offsets, d_ulist, d_X, xpitch, d_part,
                        (const cpx<double>*)ctx->tw_sp[1][LOG2HS].ptr);
     F2_HIP(ctx, hipGetLastError());
@@ -1209,7 +1250,7 @@ static int launch_group(f2_ctx* ctx, const WaveT* d_wave, const int64_t* d_offse
         hipLaunchKernelGGL(k_spectral_envelope_long, dim3((unsigned)((size_t)nutt * C)), dim3(threads_for<float, FFTLOG>()), 0,
                            ctx->stream, P, (const cpx<float>*)d_X, (const f2_f4*)tab->hu.ptr, (const cpx<float>*)tab->e.ptr,
                            (const float*)d_rho, d_offsets, d_ulist, d_lptab, (const cpx<float>*)ctx->tw_sp[0][FFTLOG].ptr);
-    else if (min_n >= 15 * (M / 16))    // every row's padding lies in the last block: the guard looks at that block only
+    else if (min_n >= 15 * (M / 16))    // every row's padding lies in the first block: the guard looks at that block only
         hipLaunchKernelGGL((k_spectral_envelope<FFTLOG, true>), dim3((unsigned)((size_t)nutt * C)), dim3(threads_for<float, FFTLOG>()), 0,
                            ctx->stream, P, (const cpx<float>*)d_X, (const f2_f4*)tab->hu.ptr, (const cpx<float>*)tab->e.ptr,
                            (const float*)d_rho, d_offsets, d_ulist, d_lptab, (const cpx<float>*)ctx->tw_sp[0][FFTLOG].ptr);
