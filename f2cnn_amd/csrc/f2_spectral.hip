@@ -86,6 +86,10 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t row_buffer_uniform(double* y, 
     return row_buffer((double*)(((unsigned long long)hi << 32) | lo), __builtin_amdgcn_readfirstlane(n));
 }
 // envelope samples i0, i0 + 1, both known to lie inside the row
+// (The block's distance stays in the lane's offset register, one vector add per block. Moved into the scalar offset of the store
+// - the blocks are 2 NT pairs apart, wave-uniform - it gave wrong samples on the device wherever the compiler's schedule put the
+// conversion of the next block right behind the store: with a register in the scalar-offset field this compiler no longer keeps
+// the wait state between a 16-byte store and a vector write to its data registers. See DESIGN.md section 6g.)
 __device__ __forceinline__ void store_row_pair_inside(__amdgpu_buffer_rsrc_t r, int i0, double a, double b) {
     const f2_d2 v = {a, b};
     __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(f2_u4, v), r, i0 * 8, 0, KS_STORE_AUX);
@@ -237,8 +241,9 @@ __device__ __forceinline__ float lowpass_pairs_store_tab(const float (&er)[NBLK]
         const int jj = INSIDE_BUT_FIRST ? (k + 1) % NBLK : k;
         const float cw = cwl[jj * NW + wv];
         const float sin_ = fmaf(tc.x, cw, sc[jj]);            // zero-state value at the end of this pair
-        const float up = dpp_mov<0x138, 0xF>(sin_);            // wave_shr:1
-        const float sprev = lane > 0 ? up : cw;                // ... at the end of the previous pair
+        // ... at the end of the previous pair: wave_shr:1 written over a copy of cw, which lane 0 (no source lane) keeps
+        const float sprev = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, cw), __builtin_bit_cast(int, sin_),
+                                                                                   0x138, 0xF, 0xF, false));
         const float sp = fmaf(tc.y, ycar[jj], sprev);          // s[2m-1]
         const float s0 = fmaf(K.qf, sp, er[jj]);
         const float s1 = fmaf(K.qf, s0, ei[jj]);
@@ -318,6 +323,19 @@ __device__ __forceinline__ cpx<float> spectral_bin(cpx<float> X, f2_f4 hu, cpx<f
 }
 
 #include "f2_fft13_merged.h"
+
+// ---- table loads of the spectrum phase: scalar descriptor + this lane's byte offset + a compile-time scalar offset per bin ----
+// (Plain pointer arithmetic does not get there: whatever form the lane offset has, the compiler folds base + lane offset into one
+// 64-bit vector address and adds every bin's constant to it, an add / add-with-carry pair in front of each of the 32 loads.)
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t table_buffer(const void* p, int bytes) {
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, bytes, 0x00020000);
+}
+template <typename T>
+__device__ __forceinline__ T lane_load(__amdgpu_buffer_rsrc_t r, unsigned lane_bytes, int elem) {
+    static_assert(sizeof(T) == 8 || sizeof(T) == 16, "cpx<float> or f2_f4");
+    if constexpr (sizeof(T) == 8) return __builtin_bit_cast(T, __builtin_amdgcn_raw_buffer_load_b64(r, lane_bytes, elem * 8, 0));
+    else return __builtin_bit_cast(T, __builtin_amdgcn_raw_buffer_load_b128(r, lane_bytes, elem * 16, 0));
+}
 
 // w_k of bin k = tid + j NB0: w_tid exp(-2 pi i j / (2 R0))  (NB0 / M = 1 / (2 R0))
 template <int R0, int J = 0>
@@ -457,7 +475,13 @@ __global__ __launch_bounds__((threads_for<float, LOG2H>()), (min_waves_for<float
 
     F2_STAMP_ARRAY(st, 8);   // (-DF2_STAMPS: phase boundaries)
     F2_STAMP(st, 0);
-    for (int i = tid; i < TWL; i += NT) twl[i] = tw[plan_tw_offset(LOG2H, 1) + i];
+    {
+        // (table base + pass offset stay scalar, the lane's part is a 32-bit byte offset with the scalar part added in 32 bits)
+        unsigned tw1 = plan_tw_offset(LOG2H, 1) * (unsigned)sizeof(cpx<float>);
+        asm volatile("" : "+s"(tw1));
+        for (int i = tid; i < TWL; i += NT)
+            twl[i] = *reinterpret_cast<const cpx<float>*>(reinterpret_cast<const char*>(tw) + ((unsigned)i * (unsigned)sizeof(cpx<float>) + tw1));
+    }
     if (tid < 4) guard[tid] = 0u;
 
     // 1. spectrum of the front-padded row at this thread's bins k = tid + j NB0 (first-pass register layout). Per bin two
@@ -475,22 +499,26 @@ __global__ __launch_bounds__((threads_for<float, LOG2H>()), (min_waves_for<float
     const f2_f4 HUH = HUc[H];
     cpx<float> Xl[2][GB];
     f2_f4 Hl[2][GB];
-    // `kb` is laundered through an empty asm together with a result of each group, so that the loads of group g + 2
-    // cannot be issued before group g has been computed (the compiler would otherwise hoist all 32 loads and spill)
-    //  (unsigned lane offset + wave-uniform row pointers: one offset register serves every load)
-    unsigned kb = (unsigned)tid;
+    // The lane offset is laundered through an empty asm together with a result of each group, so that the loads of group g + 2
+    // cannot be issued before group g has been computed (the compiler would otherwise hoist all 32 loads and spill).
+    // It is an unsigned BYTE offset (8 bytes per bin of X; HU, 16 bytes per bin, takes twice that, formed where a group's loads
+    // are issued: one register carried from group to group). The row of X and the channel's table are scalar buffer descriptors
+    // (their 64-bit bases stay in scalar arithmetic), the bin's distance a scalar offset: no vector instruction forms an address.
+    unsigned kb8 = (unsigned)tid * (unsigned)sizeof(cpx<float>);
+    asm volatile("" : "+v"(kb8));
+    const __amdgpu_buffer_rsrc_t Xb = table_buffer(Xu, (H + 1) * (int)sizeof(cpx<float>)), HUb = table_buffer(HUc, (H + 1) * (int)sizeof(f2_f4));
 #pragma unroll
     for (int q = 0; q < GB; ++q) {
-        Xl[0][q] = (Xu + q * NB0)[kb];
-        Hl[0][q] = (HUc + q * NB0)[kb];
+        Xl[0][q] = lane_load<cpx<float>>(Xb, kb8, q * NB0);
+        Hl[0][q] = lane_load<f2_f4>(HUb, 2 * kb8, q * NB0);
     }
 #pragma unroll
     for (int g = 0; g < NG; ++g) {
         if (g + 1 < NG) {
 #pragma unroll
             for (int q = 0; q < GB; ++q) {
-                Xl[(g + 1) & 1][q] = (Xu + ((g + 1) * GB + q) * NB0)[kb];
-                Hl[(g + 1) & 1][q] = (HUc + ((g + 1) * GB + q) * NB0)[kb];
+                Xl[(g + 1) & 1][q] = lane_load<cpx<float>>(Xb, kb8, ((g + 1) * GB + q) * NB0);
+                Hl[(g + 1) & 1][q] = lane_load<f2_f4>(HUb, 2 * kb8, ((g + 1) * GB + q) * NB0);
             }
         }
 #pragma unroll
@@ -508,7 +536,7 @@ __global__ __launch_bounds__((threads_for<float, LOG2H>()), (min_waves_for<float
 #endif
         }
         // (w0 passes through as well: the phase factors of a later group are then not formed ahead of time either)
-        asm volatile("" : "+v"(kb), "+v"(w0.re), "+v"(w0.im), "+v"(yk[g * GB].re), "+v"(yk[g * GB + GB - 1].re));
+        asm volatile("" : "+v"(kb8), "+v"(w0.re), "+v"(w0.im), "+v"(yk[g * GB].re), "+v"(yk[g * GB + GB - 1].re));
     }
 #ifdef F2_STAMPS
     asm volatile("s_nop 0" : "+v"(yk[15].re), "+v"(yk[15].im));
@@ -672,6 +700,7 @@ __global__ __launch_bounds__(1024, 4) void k_spectral_envelope_long(
     if (tid == 0) yh = spectral_bin(Xu[H], HUc[H], cpx<float>{-1.f, 0.f}, cpx<float>{(n & 1) ? -1.f : 1.f, 0.f}, rho).re;
     constexpr bool T0R = derive_tw0<float, LOG2Q>();
     float gin = 0.f, gout = 0.f;
+    // (pointer + lane index as before: with the descriptor form of k_spectral_envelope this kernel, short of registers, spills more)
     unsigned kb = (unsigned)tid;
     F2_STAMP_ARRAY(st, 8);
     F2_STAMP(st, 0);
