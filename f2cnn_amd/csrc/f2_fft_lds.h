@@ -1,5 +1,5 @@
 // LDS-resident Stockham FFT machinery shared by the envelope kernels: radix plans, per-pass twiddle tables, one pass
-// (fft_pass) and whole transforms (fft_all, fft_regs_to_regs). See f2_envelope.hip for how K2 uses it.
+// (fft_pass) and whole transforms (fft_all, fft_regs_to_regs). See f2_envelope_row.h for how K2 uses it.
 #pragma once
 #include <cmath>
 #include <vector>
@@ -8,9 +8,6 @@
 
 namespace f2fft {
 
-#ifndef F2_PLAN13_PASSES
-#define F2_PLAN13_PASSES 4
-#endif
 constexpr int THREADS13 = 512;   // workgroup size of the H = 8192 float transform (256: no faster)
 constexpr int MINWAVES13 = 4;
 // threads per workgroup: 256, or 512 where 256 threads would need more than 256 registers each (the host's launch
@@ -41,47 +38,49 @@ constexpr bool fuse_hilbert() { return LOG2H >= 1 && LOG2H <= FUSE_HILBERT_MAX &
 // H = 8192 (the 1 s / 16 kHz row) runs as 16-8-4-16 on 512 threads: 16 points per thread in every pass keeps
 // the kernel under 128 registers, i.e. 16 waves per CU to hide LDS / barrier / HBM latency. H = 16384 does the same
 // with 16-16-4-16 on 1024 threads (one workgroup per CU by LDS, still 16 waves).
-constexpr int plan_npass(int h) {
-    return h == 0 ? 0 : h <= 5 ? 1 : h <= 10 ? ((h & 1) ? 3 : 2) : (h == 13 && F2_PLAN13_PASSES == 4) ? 4 : h == 14 ? 4 : 3;
+// p13, the trailing argument of every plan function (and the trailing template parameter P13 of the transforms below), is the
+// number of passes of the H = 8192 plan: 4 for 16-8-4-16, 3 for 16-32-16 (k_envelope<F, 13, 3>). No other length looks at it.
+constexpr int plan_npass(int h, int p13 = 4) {
+    return h == 0 ? 0 : h <= 5 ? 1 : h <= 10 ? ((h & 1) ? 3 : 2) : (h == 13 && p13 == 4) ? 4 : h == 14 ? 4 : 3;
 }
-constexpr int plan_bits(int h, int pass) {
+constexpr int plan_bits(int h, int pass, int p13 = 4) {
     if (h <= 5) return h;
     if (h <= 10) return (h & 1) ? (pass == 1 ? 1 : (h - 1) / 2) : h / 2;
-    if (h == 13 && F2_PLAN13_PASSES == 4) return pass == 1 ? 3 : pass == 2 ? 2 : 4;
+    if (h == 13 && p13 == 4) return pass == 1 ? 3 : pass == 2 ? 2 : 4;
     if (h == 14) return pass == 2 ? 2 : 4;   // 16-16-4-16 on 1024 threads: 16 points per thread, as for h == 13
     const int a = h <= 13 ? 4 : 5;
     return pass == 1 ? h - 2 * a : a;
 }
 // most complex points a thread holds in any pass
-constexpr int plan_points_per_thread(int h, int nt) {
+constexpr int plan_points_per_thread(int h, int nt, int p13 = 4) {
     int m = 1;
-    for (int p = 0; p < plan_npass(h); ++p) {
-        const int R = 1 << plan_bits(h, p);
+    for (int p = 0; p < plan_npass(h, p13); ++p) {
+        const int R = 1 << plan_bits(h, p, p13);
         const int nb = (1 << h) / R;
         const int pts = ((nb + nt - 1) / nt) * R;
         m = pts > m ? pts : m;
     }
     return m;
 }
-constexpr int plan_shift(int h, int pass) {  // log2 of the stride entering `pass`
+constexpr int plan_shift(int h, int pass, int p13 = 4) {  // log2 of the stride entering `pass`
     int s = 0;
-    for (int i = 0; i < pass; ++i) s += plan_bits(h, i);
+    for (int i = 0; i < pass; ++i) s += plan_bits(h, i, p13);
     return s;
 }
 // per-pass twiddle table: entry (k-1)*(NB/S) + p holds exp(-2 pi i (p*S) k / H), p < NB/S, 1 <= k < R
-constexpr int plan_tw_count(int h, int pass) {
-    const int R = 1 << plan_bits(h, pass), S = 1 << plan_shift(h, pass), H = 1 << h;
+constexpr int plan_tw_count(int h, int pass, int p13 = 4) {
+    const int R = 1 << plan_bits(h, pass, p13), S = 1 << plan_shift(h, pass, p13), H = 1 << h;
     return S * R == H ? 0 : (R - 1) * (H / R / S);
 }
-constexpr int plan_tw_offset(int h, int pass) {
+constexpr int plan_tw_offset(int h, int pass, int p13 = 4) {
     int o = 0;
-    for (int i = 0; i < pass; ++i) o += plan_tw_count(h, i);
+    for (int i = 0; i < pass; ++i) o += plan_tw_count(h, i, p13);
     return o;
 }
-constexpr int plan_tw_total(int h) { return plan_tw_offset(h, plan_npass(h)); }
+constexpr int plan_tw_total(int h, int p13 = 4) { return plan_tw_offset(h, plan_npass(h, p13), p13); }
 // The tables of passes >= 1 are small (a pass with stride S has only NB/S distinct twiddle columns): each workgroup
 // copies them to LDS once, so only pass 0 (one distinct column per butterfly) reads its twiddles from global memory.
-constexpr int plan_tw_lds_count(int h) { return plan_npass(h) >= 2 ? plan_tw_total(h) - plan_tw_offset(h, 1) : 0; }   // then H/2+1 entries of V
+constexpr int plan_tw_lds_count(int h, int p13 = 4) { return plan_npass(h, p13) >= 2 ? plan_tw_total(h, p13) - plan_tw_offset(h, 1, p13) : 0; }   // then H/2+1 entries of V
 
 // LDS index padding of the complex array: one extra slot per 16
 __device__ __forceinline__ int cpad(int i) { return i + (i >> 4); }
@@ -95,19 +94,19 @@ constexpr int cpad_size(int h) { return h + (h >> 4) + 1; }
 //   W[m] = i sin(t_m) Z[m] + cos(t_m) conj(Z[H-m]),  t_m = 2 pi m / M,  W[0] = 0
 // so the spectrum never makes a separate trip through LDS.
 template <typename F, int LOG2H, int PASS, bool SRC_REGS, bool DST_REGS, int PTV, int NT, bool HILBERT = false,
-          bool T0REGS = false>
+          bool T0REGS = false, int P13 = 4>
 __device__ __forceinline__ void fft_pass(cpx<F>* lds, const cpx<F>* __restrict__ tw, const cpx<F>* twl, int tid,
                                          cpx<F> (&v)[PTV]) {
     constexpr int H = 1 << LOG2H;
-    constexpr int R = 1 << plan_bits(LOG2H, PASS);
-    constexpr int LOG2S = plan_shift(LOG2H, PASS);
+    constexpr int R = 1 << plan_bits(LOG2H, PASS, P13);
+    constexpr int LOG2S = plan_shift(LOG2H, PASS, P13);
     constexpr int S = 1 << LOG2S;
     constexpr int NB = H / R;
     constexpr int ITER = (NB + NT - 1) / NT;
     constexpr bool LAST = (S * R == H);
     static_assert(ITER * R <= PTV, "register array too small");
     constexpr bool FULL = NB % NT == 0;   // every thread owns ITER whole butterflies: no guards
-    const cpx<F>* __restrict__ twp = tw + plan_tw_offset(LOG2H, PASS);
+    const cpx<F>* __restrict__ twp = tw + plan_tw_offset(LOG2H, PASS, P13);
     if constexpr (!SRC_REGS) {
 #pragma unroll
         for (int i = 0; i < ITER; ++i) {
@@ -123,7 +122,7 @@ __device__ __forceinline__ void fft_pass(cpx<F>* lds, const cpx<F>* __restrict__
                     for (int j = 0; j < R; ++j) v[i * R + j] = lds[cpad(bf + j * NB)];
                 }
                 if constexpr (HILBERT) {
-                    const cpx<F>* __restrict__ V = tw + plan_tw_total(LOG2H);   // (cos t_k, -sin t_k), k <= H/2
+                    const cpx<F>* __restrict__ V = tw + plan_tw_total(LOG2H, P13);   // (cos t_k, -sin t_k), k <= H/2
                     const F sc = F(1.0 / H);
 #pragma unroll
                     for (int j = 0; j < R; ++j) {
@@ -148,7 +147,7 @@ __device__ __forceinline__ void fft_pass(cpx<F>* lds, const cpx<F>* __restrict__
         if (FULL || bf < NB) {
             dft<R>(&v[i * R]);   // X[k] now sits in v[i*R + brev<R>(k)]
             if constexpr (!LAST) {
-                const cpx<F>* twq = (PASS >= 1 ? twl + (plan_tw_offset(LOG2H, PASS) - plan_tw_offset(LOG2H, 1)) : twp) +
+                const cpx<F>* twq = (PASS >= 1 ? twl + (plan_tw_offset(LOG2H, PASS, P13) - plan_tw_offset(LOG2H, 1, P13)) : twp) +
                                     (bf >> LOG2S);
                 if constexpr (PASS == 0 && T0REGS && R == 16) {
                     // pass 0 has one distinct twiddle column per butterfly: load w and w^4 (two coalesced loads from
@@ -195,15 +194,15 @@ __device__ __forceinline__ void fft_pass(cpx<F>* lds, const cpx<F>* __restrict__
     if constexpr (!DST_REGS) __syncthreads();
 }
 
-template <typename F, int LOG2H, bool INVERSE, int PTV, int NT, bool T0REGS = false, int PASS = 0>
+template <typename F, int LOG2H, bool INVERSE, int PTV, int NT, bool T0REGS = false, int PASS = 0, int P13 = 4>
 __device__ __forceinline__ void fft_all(cpx<F>* lds, const cpx<F>* __restrict__ tw, const cpx<F>* twl, int tid,
                                         cpx<F> (&v)[PTV]) {
-    constexpr int NP = plan_npass(LOG2H);
+    constexpr int NP = plan_npass(LOG2H, P13);
     if constexpr (PASS < NP) {
         constexpr bool SRC = !INVERSE && PASS == 0;
         constexpr bool DST = INVERSE && PASS == NP - 1;
-        fft_pass<F, LOG2H, PASS, SRC, DST, PTV, NT, INVERSE && PASS == 0 && fuse_hilbert<F, LOG2H>(), T0REGS>(lds, tw, twl, tid, v);
-        fft_all<F, LOG2H, INVERSE, PTV, NT, T0REGS, PASS + 1>(lds, tw, twl, tid, v);
+        fft_pass<F, LOG2H, PASS, SRC, DST, PTV, NT, INVERSE && PASS == 0 && fuse_hilbert<F, LOG2H>(), T0REGS, P13>(lds, tw, twl, tid, v);
+        fft_all<F, LOG2H, INVERSE, PTV, NT, T0REGS, PASS + 1, P13>(lds, tw, twl, tid, v);
     }
 }
 
@@ -222,14 +221,14 @@ __device__ __forceinline__ void fft_regs_to_regs(cpx<F>* lds, const cpx<F>* __re
 
 // host: per-pass twiddle tables followed by V[k] = exp(-2 pi i k / M), k <= H/2 (long double trigonometry)
 template <typename F>
-int ensure_twiddles(f2_ctx* ctx, int log2h, f2_scratch& slot) {
+int ensure_twiddles(f2_ctx* ctx, int log2h, f2_scratch& slot, int p13 = 4) {
     if (slot.ptr) return F2_OK;
     const int H = 1 << log2h;
     const long double tau = 2.0L * 3.14159265358979323846264338327950288L;
     std::vector<cpx<F>> host;
-    host.reserve((size_t)plan_tw_total(log2h) + H / 2 + 1);
-    for (int pass = 0; pass < plan_npass(log2h); ++pass) {
-        const int R = 1 << plan_bits(log2h, pass), S = 1 << plan_shift(log2h, pass);
+    host.reserve((size_t)plan_tw_total(log2h, p13) + H / 2 + 1);
+    for (int pass = 0; pass < plan_npass(log2h, p13); ++pass) {
+        const int R = 1 << plan_bits(log2h, pass, p13), S = 1 << plan_shift(log2h, pass, p13);
         if (S * R == H) continue;
         const int np = H / R / S;
         for (int k = 1; k < R; ++k)
@@ -238,7 +237,7 @@ int ensure_twiddles(f2_ctx* ctx, int log2h, f2_scratch& slot) {
                 host.push_back({(F)cosl(ang), (F)(-sinl(ang))});
             }
     }
-    if ((int)host.size() != plan_tw_total(log2h)) return f2_fail(ctx, F2_ERR_INVALID, "twiddle plan mismatch");
+    if ((int)host.size() != plan_tw_total(log2h, p13)) return f2_fail(ctx, F2_ERR_INVALID, "twiddle plan mismatch");
     for (int k = 0; k <= H / 2; ++k) {
         const long double ang = tau * (long double)k / (long double)(2 * H);
         host.push_back({(F)cosl(ang), (F)(-sinl(ang))});

@@ -81,9 +81,10 @@ struct f2_ctx {
     int64_t rs_up = 0, rs_down = 0, rs_half_len = -1;
     std::vector<double> rs_taps_host;   // the taps rs_tab was built from (skip the rebuild and the upload when equal)
     f2_scratch gather_log; // ln of the envelope samples a chunk of every-sample windows touches + column min / max (f2_gather.hip)
-    f2_scratch tw[2][16];  // FFT twiddle tables, [precision][log2 H], built on first use
-    f2_scratch tw_fl[16];         // twiddle tables of f2_envelope_flagged.hip, by log2 H
-    f2_scratch tw_p3[2];   // the same for the three-pass plan of H = 8192 (f2_envelope_p3.hip), [precision]
+    // FFT twiddle tables (ensure_twiddles, f2_fft_lds.h), [precision][log2 H], built on first use: one per context for the
+    // row launch, the flagged launch and the spectral kernels
+    f2_scratch tw[2][16];
+    f2_scratch tw_p3[2];   // the same for the three-pass plan of H = 8192 (k_envelope<F, 13, 3>), [precision]
     f2_scratch tw_large[2][24];   // same for the global-memory transform of long rows
     f2_scratch tw_split[24];      // tables of the four-step transform (f2_envelope_split.hip), by log2 H
     std::vector<int> pair_list_host[2];   // what pair_list currently holds (skip the upload when equal)
@@ -115,7 +116,6 @@ struct f2_ctx {
     int spec_coefs_ok = -1;               // coefs_host eligible for the spectral kernel: -1 not decided, 0, 1
     int spec_min_pad = 64;                // ... and the padding samples its accuracy guard needs (ringing peak of the slowest channel)
     size_t spec_last_B = 0;               // batch size of the last fused call that used the spectral kernel (0: none)
-    f2_scratch tw_sp[2][16];              // its twiddle tables, [precision][log2 H]
     f2_scratch spec_lptab;                // low-pass powers per thread (lowpass_pairs_store_tab) ...
     double spec_lptab_a1 = 0.0;           // ... for this a1
     int spec_lptab_nt = 0;                // ... and workgroup size
@@ -383,11 +383,6 @@ struct f2_env_params {
     unsigned long long* stamps;   // diagnostic build only
     double b0, a1;     // y[n] = b0 (e[n] + e[n-1]) - a1 y[n-1]
 };
-// H = 8192 rows (the 1 s / 16 kHz row) with the three-pass plan 16-32-16: f2_envelope_p3.hip compiles f2_envelope.hip
-// a second time with F2_PLAN13_PASSES = 3 - in its own namespace, the radix plans being compile-time functions of the
-// macro - and exports only this launcher. Measured against the four-pass plan: 8 % faster without the low-pass, 6 % with
-// the float64 transform, 4 % slower with the float low-pass; f2_launch_envelope picks per call.
-int f2_launch_envelope13_p3(f2_ctx* ctx, const f2_env_params& P, int precision, unsigned rows);
 // f2_envelope_flagged.hip: the utterances P.ulist[0..nutt) of length class log2h whose P.uflag entry is set (float FFT)
 int f2_launch_envelope_flagged(f2_ctx* ctx, const f2_env_params& P, int log2h, unsigned nutt);
 

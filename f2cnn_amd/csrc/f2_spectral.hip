@@ -48,9 +48,6 @@
 // Traffic: 8 bytes written per sample-channel (the ENV1 rows); tables (1 MB per XCD for 128 channels), utterance
 // spectra (64 KB per utterance, shared by its C rows) and 32 bytes of digits per row come from L2. Bound: f32 VALU +
 // LDS exchanges.
-#define f2fft f2fft_sp   // own copy of the FFT templates (the radix plan of this kernel is chosen independently of K2's)
-#undef F2_PLAN13_PASSES   // (fft13_pass12_merged is the four-pass plan, also in a build that gives K2 the three-pass one)
-#define F2_PLAN13_PASSES 4
 #include <algorithm>
 #include <cmath>
 #include <complex>
@@ -1230,8 +1227,8 @@ static int launch_group(f2_ctx* ctx, const WaveT* d_wave, const int64_t* d_offse
     // float64 transform of the utterances: 2^13 packed complex points fit in LDS; longer rows are decimated in time
     constexpr int LOGD = LOG2H > 13 ? LOG2H - 13 : 0, LOG2HS = LOG2H - LOGD;
     constexpr int FFTLOG = LOG2H == 15 ? 14 : LOG2H;   // rows of the longest class: four 16384-point transforms each
-    F2_TRY(ensure_twiddles<double>(ctx, LOG2HS, ctx->tw_sp[1][LOG2HS]));
-    F2_TRY(ensure_twiddles<float>(ctx, FFTLOG, ctx->tw_sp[0][FFTLOG]));
+    F2_TRY(ensure_twiddles<double>(ctx, LOG2HS, ctx->tw[1][LOG2HS]));
+    F2_TRY(ensure_twiddles<float>(ctx, FFTLOG, ctx->tw[0][FFTLOG]));
     const int64_t xpitch = H + 8;
     const int groups = (C + 63) / 64;
     F2_TRY(f2_prof_begin(ctx, F2_K_SPECTRUM));
@@ -1243,7 +1240,7 @@ static int launch_group(f2_ctx* ctx, const WaveT* d_wave, const int64_t* d_offse
     constexpr bool FRONT = LOG2H != 15;   // (the long-row kernel still pads behind the row)
     hipLaunchKernelGGL((k_utterance_spectrum<WaveT, LOG2HS, LOGD, FRONT>), dim3((unsigned)nutt << LOGD), dim3(threads_for<double, LOG2HS>()),
                        0, ctx->stream, d_wave, d_offsets, d_ulist, d_X, xpitch, d_part,
-                       (const cpx<double>*)ctx->tw_sp[1][LOG2HS].ptr);
+                       (const cpx<double>*)ctx->tw[1][LOG2HS].ptr);
     F2_HIP(ctx, hipGetLastError());
     if constexpr (LOGD > 0) {
         hipLaunchKernelGGL((k_spectrum_combine<LOG2HS, LOGD>), dim3((unsigned)((H + 256) / 256), (unsigned)nutt), dim3(256), 0,
@@ -1278,15 +1275,15 @@ static int launch_group(f2_ctx* ctx, const WaveT* d_wave, const int64_t* d_offse
     if constexpr (LOG2H == 15)
         hipLaunchKernelGGL(k_spectral_envelope_long, dim3((unsigned)((size_t)nutt * C)), dim3(threads_for<float, FFTLOG>()), 0,
                            ctx->stream, P, (const cpx<float>*)d_X, (const f2_f4*)tab->hu.ptr, (const cpx<float>*)tab->e.ptr,
-                           (const float*)d_rho, d_offsets, d_ulist, d_lptab, (const cpx<float>*)ctx->tw_sp[0][FFTLOG].ptr);
+                           (const float*)d_rho, d_offsets, d_ulist, d_lptab, (const cpx<float>*)ctx->tw[0][FFTLOG].ptr);
     else if (min_n >= 15 * (M / 16))    // every row's padding lies in the first block: the guard looks at that block only
         hipLaunchKernelGGL((k_spectral_envelope<FFTLOG, true>), dim3((unsigned)((size_t)nutt * C)), dim3(threads_for<float, FFTLOG>()), 0,
                            ctx->stream, P, (const cpx<float>*)d_X, (const f2_f4*)tab->hu.ptr, (const cpx<float>*)tab->e.ptr,
-                           (const float*)d_rho, d_offsets, d_ulist, d_lptab, (const cpx<float>*)ctx->tw_sp[0][FFTLOG].ptr);
+                           (const float*)d_rho, d_offsets, d_ulist, d_lptab, (const cpx<float>*)ctx->tw[0][FFTLOG].ptr);
     else
         hipLaunchKernelGGL((k_spectral_envelope<FFTLOG, false>), dim3((unsigned)((size_t)nutt * C)), dim3(threads_for<float, FFTLOG>()), 0,
                            ctx->stream, P, (const cpx<float>*)d_X, (const f2_f4*)tab->hu.ptr, (const cpx<float>*)tab->e.ptr,
-                           (const float*)d_rho, d_offsets, d_ulist, d_lptab, (const cpx<float>*)ctx->tw_sp[0][FFTLOG].ptr);
+                           (const float*)d_rho, d_offsets, d_ulist, d_lptab, (const cpx<float>*)ctx->tw[0][FFTLOG].ptr);
     F2_HIP(ctx, hipGetLastError());
     F2_TRY(f2_prof_end(ctx, F2_K_FUSED));
 #ifdef F2_STAMPS

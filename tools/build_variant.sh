@@ -1,6 +1,6 @@
 #!/bin/bash
 # usage: tools/build_variant.sh <name> <extra hipcc flags...>  ->  tools/libf2cnn_hip_<name>.so
-# Diagnostic variants of the library: -DF2_STAMPS, -DF2_WS_STAMPS (phase stamps), -DF2_PLAN13_PASSES=3. Never used for results.
+# Diagnostic variants of the library: -DF2_STAMPS, -DF2_WS_STAMPS (phase stamps). Never used for results.
 set -e
 cd "$(dirname "$0")/.."
 name=$1; shift
