@@ -117,8 +117,7 @@ struct f2_ctx {
     int spec_min_pad = 64;                // ... and the padding samples its accuracy guard needs (ringing peak of the slowest channel)
     size_t spec_last_B = 0;               // batch size of the last fused call that used the spectral kernel (0: none)
     f2_scratch spec_lptab;                // low-pass powers per thread (lowpass_pairs_store_tab) ...
-    double spec_lptab_a1 = 0.0;           // ... for this a1
-    int spec_lptab_nt = 0;                // ... and workgroup size
+    double spec_lptab_a1 = 0.0;           // ... for this a1 (one table for every workgroup size: tests/test_gpu_call_history.py)
     // options (f2_ctx_set_option); -1 = decide from the batch
     int opt_spectral = 1;                 // route eligible utterances of the fused call through the spectral kernel
     int opt_spectral_min_rows = 4096;     // ... when the call has at least this many eligible rows (utterances x channels)
