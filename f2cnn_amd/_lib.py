@@ -110,6 +110,10 @@ SIGNATURES = {
     "f2_trainer_set_waves": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _d, _i, _vp, _vp, _vp, _i, _i, _i]),
     "f2_trainer_render": (_i, [_vp, _vp, _vp, _i, _vp, C.c_uint64]),
     "f2_trainer_get_windows": (_i, [_vp, _vp, _i64, _i64, _vp, _vp]),
+    "f2_reverb_pick": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _i]),
+    "f2_input_batch_wet": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i, _i, _d, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _vp,
+                                C.c_uint32, C.c_uint64, _vp, _i]),
+    "f2_trainer_render_wet": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, C.c_uint64]),
 }
 TRAINER_WHAT = {"weights": 0, "accumulators": 1, "gradient": 2}   # F2_TRAINER_* of f2_trainer_get
 
@@ -386,6 +390,30 @@ class Context:
                                                  int(bool(lpf)), float(cutoff), precision, _ptr(center_offsets), _ptr(centers),
                                                  radius, step, int(bool(normalize)), _ptr(snr) if len(snr) else None, len(snr),
                                                  _ptr(lev), int(first_utterance), int(seed) & (2 ** 64 - 1), _ptr(windows), mem_space))
+
+    def reverb_pick(self, wave, wave_dtype, offsets, B, rirs, room_of, wet, mem_space):
+        """The batch with one room per utterance (see f2_reverb_pick): utterance b convolved with rirs[room_of[b]] (a sequence of
+        1-D float64 arrays), or dry where room_of[b] == len(rirs); room_of None: all dry. wet receives offsets[B] float64 in the
+        layout of wave (numpy arrays or device pointers, by mem_space)."""
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        taps, rir_offsets, room = _rooms(rirs, room_of)
+        self.check(self.lib.f2_reverb_pick(self.handle, _ptr(wave), wave_dtype, _ptr(offsets), int(B), _ptr(taps) if len(taps) else None,
+                                           _ptr(rir_offsets), len(rir_offsets) - 1, _ptr(room), _ptr(wet), mem_space))
+
+    def input_batch_wet(self, wave, wave_dtype, offsets, coefs, B, Cn, lpf, cutoff, precision, center_offsets, centers, radius, step,
+                        normalize, rirs, room_of, snr_db, level_of, first_utterance, seed, windows, mem_space):
+        """input_batch on the batch as reverb_pick, then noise_pick leave it, neither waveform leaving the device; see
+        f2_input_batch_wet."""
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        center_offsets = np.ascontiguousarray(center_offsets, dtype=np.int64)
+        centers = np.ascontiguousarray(centers, dtype=np.int64)
+        snr, lev = _noise_levels(snr_db, level_of)
+        taps, rir_offsets, room = _rooms(rirs, room_of)
+        self.check(self.lib.f2_input_batch_wet(self.handle, _ptr(wave), wave_dtype, _ptr(offsets), _ptr(coefs), int(B), Cn,
+                                               int(bool(lpf)), float(cutoff), precision, _ptr(center_offsets), _ptr(centers), radius,
+                                               step, int(bool(normalize)), _ptr(taps) if len(taps) else None, _ptr(rir_offsets),
+                                               len(rir_offsets) - 1, _ptr(room), _ptr(snr) if len(snr) else None, len(snr), _ptr(lev),
+                                               int(first_utterance), int(seed) & (2 ** 64 - 1), _ptr(windows), mem_space))
 
     def cnn_create(self, tensors, rows, channels):
         """tensors: 12 contiguous float32 arrays in Keras layouts (see include/f2cnn_hip.h). Returns a handle."""
@@ -775,6 +803,15 @@ class Context:
         self.check(self.lib.f2_trainer_render(self.handle, handle, _ptr(snr) if len(snr) else None, len(snr), _ptr(lev),
                                               int(seed) & (2 ** 64 - 1)))
 
+    def trainer_render_wet(self, handle, rirs=(), room_of=None, snr_db=(), level_of=None, seed=0):
+        """The training windows from the stored waves, utterance b in room rirs[room_of[b]] and at snr_db[level_of[b]] (see
+        f2_trainer_render_wet)"""
+        snr, lev = _noise_levels(snr_db, level_of)
+        taps, rir_offsets, room = _rooms(rirs, room_of)
+        self.check(self.lib.f2_trainer_render_wet(self.handle, handle, _ptr(taps) if len(taps) else None, _ptr(rir_offsets),
+                                                  len(rir_offsets) - 1, _ptr(room), _ptr(snr) if len(snr) else None, len(snr),
+                                                  _ptr(lev), int(seed) & (2 ** 64 - 1)))
+
     def trainer_get_windows(self, handle, first, count, shape):
         """Rows first .. first + count - 1 of the training set: (count, *shape) float32 windows and (count) uint8 labels"""
         x = np.empty((int(count),) + tuple(shape), np.float32)
@@ -878,6 +915,13 @@ def _pack_rirs(rirs):
     rir_offsets[1:] = np.cumsum([len(h) for h in rirs])
     taps = np.concatenate(rirs) if rirs else np.zeros(0, np.float64)
     return np.ascontiguousarray(taps), rir_offsets
+
+
+def _rooms(rirs, room_of):
+    """(taps, rir_offsets, room_of as int32 or None) for the calls that give every utterance a room of its own"""
+    taps, rir_offsets = _pack_rirs(rirs if rirs is not None else ())
+    room = None if room_of is None else np.ascontiguousarray(room_of, dtype=np.int32).reshape(-1)
+    return taps, rir_offsets, room
 
 
 def _pack_mix(mix, Cn):

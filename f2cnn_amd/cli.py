@@ -23,6 +23,12 @@ package implements:
                                                              the list or clean under fresh white noise, and the TEST files are
                                                              validated clean and at every level; --engine torch cannot do either;
                                                              not in the reference)
+    python -m f2cnn_amd cnn train --engine hip --from-wav [--augment-t60 0.2,0.4,0.8] [--augment-rirs a.wav,b.wav] [--drr DB] [--augment-snrs ...] [--seed S]
+                                                            (every epoch each TRAIN file is also convolved on the device with the
+                                                             response of a room drawn from the list - synthetic ones built anew
+                                                             every epoch, measured ones fixed - or left dry; room first, then
+                                                             noise at an SNR of the reverberant signal; the TEST files are also
+                                                             validated once per room; not in the reference)
     python -m f2cnn_amd cnn test [--input/-i NPY] [--label/-l CSV] [--model/-m NPZ] [--by set|region|speaker|phoneme] [--rows test|train|all]
                                                             (loss, accuracy and the 2 x 2 counts of a saved model on the labelled
                                                              windows, per value of a label column, in one device pass; writes
@@ -127,6 +133,23 @@ def augment_snrs_argument(text):
         return snrs_argument(text)
     except argparse.ArgumentTypeError:
         raise argparse.ArgumentTypeError("--augment-snrs takes a comma-separated list of SNRs in dB, not {!r}".format(text))
+
+
+def augment_t60_argument(text):
+    """--augment-t60: as --t60"""
+    try:
+        return t60_argument(text)
+    except argparse.ArgumentTypeError:
+        raise argparse.ArgumentTypeError("--augment-t60 takes a comma-separated list of positive reverberation times in seconds, not {!r}"
+                                         .format(text))
+
+
+def augment_rirs_argument(text):
+    """--augment-rirs: as --rir"""
+    try:
+        return rir_argument(text)
+    except argparse.ArgumentTypeError:
+        raise argparse.ArgumentTypeError("--augment-rirs takes a comma-separated list of WAV files, not {!r}".format(text))
 
 
 def cutoffs_argument(text):
@@ -252,6 +275,12 @@ def build_parser():
     c.add_argument('--augment-snrs', action='store', type=augment_snrs_argument, dest='augment_snrs', default=argparse.SUPPRESS,
                    help="train --engine hip --from-wav: comma-separated SNRs in dB; every epoch each file is rendered at one of them "
                         "or clean, under fresh noise")
+    c.add_argument('--augment-t60', action='store', type=augment_t60_argument, dest='augment_t60', default=argparse.SUPPRESS,
+                   help="train --engine hip --from-wav: comma-separated reverberation times in seconds; every epoch each file is "
+                        "rendered in a fresh synthetic room of one of them (--drr: their direct-to-reverberant ratio) or dry")
+    c.add_argument('--augment-rirs', action='store', type=augment_rirs_argument, dest='augment_rirs', default=argparse.SUPPRESS,
+                   help="train --engine hip --from-wav: comma-separated mono WAV files with measured impulse responses, further rooms "
+                        "of the draw")
     c.add_argument('--seed', action='store', type=int, dest='seed',
                    help="noisesweep: seed of the noise (default 0); train --from-wav: seed of the weights, the order and the noise")
     c.add_argument('--save-wavs', action='store_true', dest='save_wavs',
@@ -372,6 +401,20 @@ def from_wav_refusal(args):
     return None
 
 
+def rooms_refusal(args):
+    """The same for --augment-t60 / --augment-rirs, asked once from_wav_refusal has nothing to say"""
+    given = [opt for attr, opt in (('augment_t60', '--augment-t60'), ('augment_rirs', '--augment-rirs')) if attr in args]
+    if not given:
+        return None
+    if args.cnn_command != 'train':
+        return "{} only applies to 'cnn train'".format(given[0])
+    if getattr(args, 'engine', 'torch') != 'hip':
+        return "{} needs --engine hip: only the library's own training step renders windows from the waves".format(given[0])
+    if 'from_wav' not in args:
+        return "{} needs --from-wav: stored windows cannot be reverberated".format(given[0])
+    return None
+
+
 def sweep_refusal(args, no_lpf, instead):
     """says which option the sweep does not take, if one was given (an option that was not given is absent, None or False)"""
     for attr, option, why in (('CUTOFF', '--lpf', no_lpf), ('figure', '--figure', instead), ('occlusion', '--occlusion', instead),
@@ -417,7 +460,7 @@ def main(argv=None):
         if getattr(report, "exit_status", 0):          # some files could not be processed (the others were)
             return report.exit_status
     elif 'cnn_command' in args:
-        refusal = from_wav_refusal(args)
+        refusal = from_wav_refusal(args) or rooms_refusal(args)
         if refusal:
             print(refusal)
             return 1
@@ -428,8 +471,12 @@ def main(argv=None):
             if not os.path.isfile(labelFile):
                 print("Please first generate a label data file with 'prepare label', or give one with --label")
                 return 1
+            rooms = {}                                         # (only when asked for: the call without rooms is the one it was)
+            if 'augment_t60' in args or 'augment_rirs' in args:
+                rooms = dict(t60s=tuple(getattr(args, 'augment_t60', ())), rirs=tuple(getattr(args, 'augment_rirs', ())),
+                             drr_db=getattr(args, 'drr', 0.0))
             TrainFromWav(labelFile=labelFile, LPF=args.CUTOFF is not None, CUTOFF=args.CUTOFF, snrs=tuple(getattr(args, 'augment_snrs', ())),
-                         seed=args.seed)
+                         seed=args.seed, **rooms)
             return 0
         if args.cnn_command == 'train':                        # f2cnn.py:126-143
             from .scripts.CNN.Training import TrainAndPlotLoss

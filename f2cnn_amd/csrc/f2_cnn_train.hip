@@ -728,6 +728,7 @@ struct f2_trainer {
     // f2_trainer_set_waves: the corpus x is rendered from (f2_trainer_render), instead of windows handed in by set_data
     bool have_waves = false;
     f2_scratch wave, centers;   // the waves; [the centres | the utterance of every window, counted inside its group]
+    f2_scratch rir;             // f2_trainer_render_wet: [rir_offsets | taps] of the render in flight, uploaded once for all groups
     std::vector<int64_t> offsets, center_offsets;
     std::vector<double> coefs;
     int wave_dtype = 0, B = 0, lpf = 0, fft_precision = 0, radius = 0, step = 0, group = 1;
@@ -913,15 +914,25 @@ int f2_trainer_set_waves(f2_ctx* ctx, f2_trainer* t, const void* wave, int wave_
     return F2_OK;
 }
 
-int f2_trainer_render(f2_ctx* ctx, f2_trainer* t, const double* snr_db, int K, const int32_t* level_of, uint64_t seed) {
+int f2_trainer_render_wet(f2_ctx* ctx, f2_trainer* t, const double* rir, const int64_t* rir_offsets, int Kr, const int32_t* room_of,
+                          const double* snr_db, int K, const int32_t* level_of, uint64_t seed) {
     F2_TRY(f2_check_ctx(ctx));
     F2_TRY(check_trainer(ctx, t));
     F2_CHECK(ctx, t->have_waves, F2_ERR_INVALID, "the trainer has no waves to render from (f2_trainer_set_waves)");
     F2_TRY(f2_check_noise_pick(ctx, t->B, {snr_db, K, level_of, 0, seed}));
+    f2_reverb_pick_args R = {rir, rir_offsets, Kr, room_of, nullptr, nullptr};
+    F2_TRY(f2_check_reverb_pick(ctx, t->B, R));
     if (t->n == 0) return F2_OK;
     const size_t xs = (size_t)t->rows * t->channels, ws = t->wave_dtype == F2_WAVE_I16 ? 2 : 8;
     const int64_t* d_centers = (const int64_t*)t->centers.ptr;
     const int* d_win_utt = (const int*)((const char*)t->centers.ptr + sizeof(int64_t) * (size_t)t->n);
+    if (!R.dry()) {   // the taps and their offsets go up once, for every group
+        const size_t obytes = sizeof(int64_t) * ((size_t)Kr + 1);
+        F2_TRY(f2_reserve(ctx, t->rir, obytes + sizeof(double) * (size_t)rir_offsets[Kr]));
+        F2_TRY(f2_upload_async(ctx, t->rir.ptr, rir_offsets, obytes));
+        F2_TRY(f2_upload_async(ctx, (char*)t->rir.ptr + obytes, rir, sizeof(double) * (size_t)rir_offsets[Kr]));
+        R.d_rir_off = (const int64_t*)t->rir.ptr, R.d_rir = (const double*)((const char*)t->rir.ptr + obytes);
+    }
     F2_HIP(ctx, hipMemsetAsync(ctx->flags.ptr, 0, sizeof(int), ctx->stream));
     std::vector<int64_t> off;
     // group after group onto the stream, each into its rows of x; one wait at the end
@@ -932,14 +943,21 @@ int f2_trainer_render(f2_ctx* ctx, f2_trainer* t, const double* snr_db, int K, c
         off.resize((size_t)nb + 1);
         for (int b = 0; b <= nb; ++b) off[(size_t)b] = t->offsets[(size_t)b0 + b] - t->offsets[(size_t)b0];
         const f2_noise_pick_args N = {snr_db, K, level_of ? level_of + b0 : nullptr, (uint32_t)b0, seed};
+        f2_reverb_pick_args Rg = R;
+        if (!R.dry()) Rg.room_of = room_of + b0;
         F2_TRY(f2_launch_noisy_windows(ctx, (const char*)t->wave.ptr + ws * (size_t)t->offsets[(size_t)b0], t->wave_dtype, off.data(),
                                        t->coefs.data(), nb, t->channels, t->lpf, t->cutoff_hz, t->fft_precision, d_centers + w0, d_win_utt + w0,
-                                       true, nw, t->radius, t->step, 1, N, (float*)t->x.ptr + xs * (size_t)w0));
+                                       true, nw, t->radius, t->step, 1, N, (float*)t->x.ptr + xs * (size_t)w0, &Rg));
     }
     F2_HIP(ctx, hipMemcpyAsync(ctx->host_flags, ctx->flags.ptr, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     F2_HIP(ctx, hipStreamSynchronize(ctx->stream));
     F2_CHECK(ctx, !ctx->host_flags[0], F2_ERR_NONPOSITIVE, "values must all be positive (normalizeInput)");
     return F2_OK;
+}
+
+// the render without rooms: the same code, whose reverberant stage is then skipped altogether
+int f2_trainer_render(f2_ctx* ctx, f2_trainer* t, const double* snr_db, int K, const int32_t* level_of, uint64_t seed) {
+    return f2_trainer_render_wet(ctx, t, nullptr, nullptr, 0, nullptr, snr_db, K, level_of, seed);
 }
 
 int f2_trainer_get_windows(f2_ctx* ctx, const f2_trainer* t, int64_t first, int64_t count, float* x, uint8_t* y) {

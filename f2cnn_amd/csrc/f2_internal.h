@@ -64,6 +64,9 @@ struct f2_ctx {
     // with or without lpf; eval_envelopes) places another. f2_noise_pick / f2_launch_noisy_windows: the noisy float64 batch, by the same rule
     // (f2_batch_envelopes, which they nest, places nothing here).
     f2_scratch levels;
+    // f2_reverb_pick / f2_launch_noisy_windows with rooms: the reverberant float64 batch, which the noise kernels read while they
+    // write `levels` (a span of its own: k_noise_pick's pointers are __restrict__)
+    f2_scratch wet;
     // f2_channel_mix_levels, f2_eval_smear_sweep: tile sums, tile spans and the transposed mixing matrices of the call in flight (up to
     // 134 MB at 64 levels of 512 channels: too much for `meta`). Reserved once per call, before its first launch.
     f2_scratch mix;
@@ -131,6 +134,7 @@ struct f2_ctx {
     int opt_cnn_f16x3 = 1;               // conv2 .. conv4 + dense1 on the fp16 matrix cores, operands split in two pieces (3 MFMAs per product; "cnn_f16x3")
     int opt_cnn_ws = 1;                   // ... with the weights of each wave's role held in registers (f2_cnn_ws.hip; windows of 10 / 11 rows)
     int opt_cnn_ws_dense = 1;             // ... and dense1 with 96 windows per weight fragment, loads waited for by hand (k_dense1_ws)
+    int opt_reverb_pick_sort = 1;         // k_reverb_pick's tile list: most taps first (0: utterance by utterance; the same results)
     int opt_gather_blocked = 1;           // every-sample windows: logarithm once per sample, blocks of 32 windows (0: one workgroup per window)
     int opt_env_plan4 = 0;                // four-pass plan for every 1 s row (default: three passes where measured faster)
     // pinned staging of small host -> device uploads (f2_upload_async): a ring of page-locked memory the copies read from,
@@ -511,7 +515,8 @@ int f2_launch_noise_pick(f2_ctx* ctx, const void* d_wave, int wave_dtype, const 
 // on the host) through the noise kernels into ctx->levels, then f2_input_batch's envelopes and gather on that float64 buffer, the
 // windows written to d_windows (device). The centres and the utterance of every window (counted inside this batch) are either on
 // the device already (lists_on_device) or host arrays that go up behind the envelope launches, as in f2_input_batch. Enqueues only; the gather ORs into word 0 of ctx->flags, which the caller resets before and reads after. The arguments
-// have passed f2_check_noise_pick and f2_input_batch's checks.
+// have passed f2_check_noise_pick and f2_input_batch's checks. With `rooms` (passed f2_check_reverb_pick) that are not dry, the
+// utterances go through f2_launch_reverb_pick into ctx->wet first and the noise kernels read that float64 buffer.
 struct f2_noise_pick_args {
     const double* snr_db;
     int K;
@@ -530,7 +535,8 @@ int f2_check_input_batch(f2_ctx* ctx, const void* wave, int wave_dtype, const in
                          std::vector<int>* win_utt);
 int f2_launch_noisy_windows(f2_ctx* ctx, const void* d_wave, int wave_dtype, const int64_t* offsets, const double* coefs, int B, int C,
                             int lpf, double cutoff_hz, int fft_precision, const int64_t* centers, const int* win_utt,
-                            bool lists_on_device, int64_t n_windows, int radius, int step, int normalize, const f2_noise_pick_args& N, float* d_windows);
+                            bool lists_on_device, int64_t n_windows, int radius, int step, int normalize, const f2_noise_pick_args& N, float* d_windows,
+                            const struct f2_reverb_pick_args* rooms = nullptr);
 // d_stats ((K + 1) * B pairs, zeroed by the caller) += {windows labelled rising, windows labelled as the clean level labels them}
 // per utterance of the (K + 1) * B batch whose window offsets are d_window_offsets; max_windows: the most any utterance has
 int f2_launch_label_tally(f2_ctx* ctx, const uint8_t* d_labels, const int64_t* d_window_offsets, int B, int K, int64_t max_windows,
@@ -564,6 +570,30 @@ int f2_check_rir(f2_ctx* ctx, const double* rir, const int64_t* rir_offsets, int
 void f2_reverb_meta(f2_meta_carve* meta, int B, const int64_t* rir_offsets, int K, f2_reverb_arrays* A);
 int f2_launch_reverb_levels(f2_ctx* ctx, const void* d_wave, int wave_dtype, const int64_t* d_offsets, const int64_t* h_offsets, int B,
                             const double* rir, const int64_t* rir_offsets, int K, const f2_reverb_arrays& A, double* d_out);
+// The kernel of f2_reverb_pick: utterance b at room room_of[b] in [0, K] (K: dry), the output in the layout of the waves. The
+// arguments of a stage (rir, rir_offsets, room_of: host) pass f2_check_reverb_pick before anything is launched: K >= 0; unless the
+// stage is dry, a non-NULL rir, f2_check_rir, and every room_of entry in [0, K] (the message names the utterance).
+// d_rir / d_rir_off: device copies of the taps and their offsets that are up already (a render uploads them once for all its
+// groups), or NULL: the launch uploads them into the arrays f2_reverb_pick_meta named. The launch builds and uploads the tile list
+// (option "reverb_pick_sort": most taps first), reads the B utterances once and writes h_offsets[B] doubles.
+struct f2_reverb_pick_args {
+    const double* rir;
+    const int64_t* rir_offsets;
+    int K;
+    const int32_t* room_of;
+    const double* d_rir;
+    const int64_t* d_rir_off;
+    bool dry() const { return K == 0 || !room_of; }
+};
+struct f2_reverb_pick_arrays {
+    int64_t *d_tiles = nullptr, *d_rir_off = nullptr;   // one entry per tile: utterance << 32 | tile; K + 1 tap offsets
+    int64_t* d_room = nullptr;                          // B int32 values in 8-byte slots
+    double* d_rir = nullptr;
+};
+int f2_check_reverb_pick(f2_ctx* ctx, int B, const f2_reverb_pick_args& R);
+void f2_reverb_pick_meta(f2_meta_carve* meta, int B, const int64_t* h_offsets, const f2_reverb_pick_args& R, f2_reverb_pick_arrays* A);
+int f2_launch_reverb_pick(f2_ctx* ctx, const void* d_wave, int wave_dtype, const int64_t* d_offsets, const int64_t* h_offsets, int B,
+                          const f2_reverb_pick_args& R, const f2_reverb_pick_arrays& A, double* d_out);
 // f2_smear.hip, the kernel of f2_channel_mix_levels / f2_eval_smear_sweep. A workgroup of k_channel_mix_levels makes
 // F2_SMEAR_TILE_CHANNELS output channels of F2_SMEAR_TILE_SAMPLES consecutive samples of one utterance at one level.
 // f2_check_mix: K in 1 .. F2_SMEAR_MAX_LEVELS and mix non-NULL (F2_ERR_INVALID; too many levels, or C above

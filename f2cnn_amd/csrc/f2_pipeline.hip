@@ -948,15 +948,23 @@ int f2_check_noise_pick(f2_ctx* ctx, int B, const f2_noise_pick_args& N) {
 int f2_launch_noisy_windows(f2_ctx* ctx, const void* d_wave, int wave_dtype, const int64_t* offsets, const double* coefs, int B, int C,
                             int lpf, double cutoff_hz, int fft_precision, const int64_t* centers, const int* win_utt,
                             bool lists_on_device, int64_t n_windows, int radius, int step, int normalize, const f2_noise_pick_args& N,
-                            float* d_windows) {
+                            float* d_windows, const f2_reverb_pick_args* rooms) {
     const int64_t total = offsets[B];
-    // the small arrays and the noisy waveform first: nothing the envelopes reserve is one of these two areas
+    const bool wet = rooms && !rooms->dry();
+    // the small arrays and the waveforms first: nothing the envelopes reserve is one of these areas
     noise_pick_meta M;
+    f2_reverb_pick_arrays A;
     f2_meta_carve meta;
     M.carve(&meta, B, N);
+    if (wet) f2_reverb_pick_meta(&meta, B, offsets, *rooms, &A);
     F2_TRY(meta.reserve(ctx));
     F2_TRY(f2_reserve(ctx, ctx->levels, sizeof(double) * (size_t)total));
+    if (wet) F2_TRY(f2_reserve(ctx, ctx->wet, sizeof(double) * (size_t)total));
     F2_TRY(f2_upload_offsets(ctx, offsets, B));
+    if (wet) {   // f2_reverb_pick into ctx->wet, then f2_noise_pick(F2_WAVE_F64) from there: sigma is the reverberant signal's
+        F2_TRY(f2_launch_reverb_pick(ctx, d_wave, wave_dtype, (const int64_t*)ctx->offsets.ptr, offsets, B, *rooms, A, (double*)ctx->wet.ptr));
+        d_wave = ctx->wet.ptr, wave_dtype = F2_WAVE_F64;
+    }
     F2_TRY(M.launch(ctx, d_wave, wave_dtype, (const int64_t*)ctx->offsets.ptr, B, total, N, (double*)ctx->levels.ptr));
     // f2_input_batch from here on, as a device call on the float64 buffer
     const f2_batch X = {ctx->levels.ptr, F2_WAVE_F64, offsets, coefs, B, C, lpf, cutoff_hz, fft_precision, F2_MEM_DEVICE};
@@ -1053,6 +1061,28 @@ int f2_input_batch_noisy(f2_ctx* ctx, const void* wave, int wave_dtype, const in
     F2_TRY(reset_flag(ctx));
     F2_TRY(f2_launch_noisy_windows(ctx, d_wave, wave_dtype, offsets, coefs, B, C, lpf, cutoff_hz, fft_precision, centers, win_utt.data(),
                                    false, n_windows, radius, step, normalize, N, win.as<float>()));
+    return finish_windows(ctx, win, normalize);
+}
+
+int f2_input_batch_wet(f2_ctx* ctx, const void* wave, int wave_dtype, const int64_t* offsets, const double* coefs, int B, int C, int lpf,
+                       double cutoff_hz, int fft_precision, const int64_t* center_offsets, const int64_t* centers, int radius, int step,
+                       int normalize, const double* rir, const int64_t* rir_offsets, int Kr, const int32_t* room_of, const double* snr_db,
+                       int K, const int32_t* level_of, uint32_t first_utterance, uint64_t seed, float* windows, int mem_space) {
+    const f2_noise_pick_args N = {snr_db, K, level_of, first_utterance, seed};
+    const f2_reverb_pick_args R = {rir, rir_offsets, Kr, room_of, nullptr, nullptr};
+    int64_t n_windows;
+    std::vector<int> win_utt;
+    F2_TRY(f2_check_input_batch(ctx, wave, wave_dtype, offsets, coefs, B, C, lpf, cutoff_hz, fft_precision, center_offsets, centers, radius,
+                             step, windows, mem_space, &N, &n_windows, &win_utt));
+    F2_TRY(f2_check_reverb_pick(ctx, B, R));
+    if (n_windows == 0) return F2_OK;
+    const void* d_wave;
+    F2_TRY(f2_stage_wave(ctx, wave, wave_dtype, offsets[B], mem_space, &d_wave));
+    f2_output win;
+    F2_TRY(f2_place(ctx, ctx->xbuf, windows, sizeof(float) * (size_t)n_windows * (2 * radius + 1) * (size_t)C, mem_space, true, &win));
+    F2_TRY(reset_flag(ctx));
+    F2_TRY(f2_launch_noisy_windows(ctx, d_wave, wave_dtype, offsets, coefs, B, C, lpf, cutoff_hz, fft_precision, centers, win_utt.data(),
+                                   false, n_windows, radius, step, normalize, N, win.as<float>(), &R));
     return finish_windows(ctx, win, normalize);
 }
 

@@ -6,10 +6,14 @@
 //                    utterance's start, as k_resample does), then every lane slides a register window of its RV_R consecutive
 //                    outputs over it - one 8-byte LDS read and RV_R FMAs per tap, the tap itself a wave-uniform load from global
 //                    memory.
+//   k_reverb_pick    wet[b][k] for the one room room[b] of every utterance (f2_reverb_pick; the reverberant stage of
+//                    f2_input_batch_wet / f2_trainer_render_wet), in the layout of the waves. The grid is the tiles alone, in the
+//                    order of a list the host uploads (most taps first); the per-tile tap walk is rv_walk, shared with the sweep.
 // Arithmetic contract of the header: one float64 accumulator per output, taps in ascending t, acc = fma(h[t], x[k - t], acc), no
 // atomics, no sum split across lanes. gfx950, wave64; plain vector stores only.
 #include "f2_internal.h"
 
+#include <algorithm>
 #include <cmath>
 
 namespace {
@@ -31,43 +35,19 @@ static_assert(RV_R * RV_PLANE * sizeof(double) <= 64 * 1024, "one span in LDS");
 __device__ __forceinline__ int rv_at(int j) { return (j & (RV_R - 1)) * RV_PLANE + (j >> 2); }
 static_assert(RV_R == 4, "rv_at and the unrolled window below are written for four outputs per lane");
 
-// Workgroup (blockIdx.x, l = blockIdx.y) serves outputs k0 .. k0 + RV_BLOCK - 1 of the utterance b with first[b] <= blockIdx.x <
-// first[b + 1] (first: running sums of the utterances' tiles; an empty utterance has none). Lane L owns k0 + 4 L + c, c < 4.
+// The tap walk of one tile: outputs k0 .. k0 + nk - 1 (nk >= 1) of the utterance x of n samples under the response h of `taps` taps,
+// lane L owning k0 + 4 L + c, c < 4, in a0 .. a3 (which enter as 0).
 // Chunk t0 needs x[k0 - t0 - (RV_TC - 1)] .. x[k0 + RV_BLOCK - 1 - t0]; samples before the utterance are staged as 0 (a tap
 // beyond k adds fma(h, 0, acc), which leaves acc as it is), samples from n on - read only by outputs that are not stored - too.
-// Chunks whose span lies before the utterance altogether are not walked, and no tap at or beyond T_l is ever read.
+// Chunks whose span lies before the utterance altogether are not walked, and no tap at or beyond `taps` is ever read.
+// xs: the workgroup's RV_R * RV_PLANE doubles of LDS. Every thread of the workgroup calls it (barriers inside).
 template <typename T>
-__global__ __launch_bounds__(RV_NT) void k_reverb_levels(const T* __restrict__ wave, const int64_t* __restrict__ offsets,
-                                                          const int64_t* __restrict__ first, int B, const double* __restrict__ rir,
-                                                          const int64_t* __restrict__ rir_offsets, int K, int64_t total,
-                                                          double* __restrict__ out) {
-    __shared__ double xs[RV_R * RV_PLANE];
+__device__ __forceinline__ void rv_walk(double* __restrict__ xs, const T* __restrict__ x, int64_t n, int64_t k0, int nk,
+                                        const double* __restrict__ h, int64_t taps, double& a0, double& a1, double& a2, double& a3) {
     const int tid = threadIdx.x;
-    const int l = blockIdx.y;
-    const int64_t blk = blockIdx.x;
-    int b = 0, hi = B;      // first[b] <= blk < first[hi]
-    while (hi - b > 1) {
-        const int mid = (b + hi) >> 1;
-        if (first[mid] <= blk) b = mid;
-        else hi = mid;
-    }
-    const int64_t n = offsets[b + 1] - offsets[b];
-    const int64_t k0 = (blk - first[b]) * RV_BLOCK;
-    const int nk = (int)min((int64_t)RV_BLOCK, n - k0);      // outputs of this workgroup, >= 1
-    const T* __restrict__ x = wave + offsets[b];
-    double* __restrict__ y = out + (size_t)l * (size_t)total + (size_t)offsets[b] + (size_t)k0;
     const int o = RV_R * tid;                                // first output of this lane inside the tile
-    if (l == K) {                                            // the dry level: the samples themselves
-#pragma unroll
-        for (int c = 0; c < RV_R; ++c)
-            if (o + c < nk) y[o + c] = (double)x[k0 + o + c];
-        return;
-    }
-    const double* __restrict__ h = rir + rir_offsets[l];
-    const int64_t taps = rir_offsets[l + 1] - rir_offsets[l];
     // taps that reach a sample of the utterance for some stored output of the tile: t <= k0 + nk - 1
     const int t_end = (int)min(taps, k0 + (int64_t)nk);
-    double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
     for (int t0 = 0; t0 < t_end; t0 += RV_TC) {
         const int ns = min(RV_TC, t_end - t0);               // taps of this chunk
         const int64_t lo = k0 - (int64_t)t0 - RV_TC;         // utterance index of xs[0]
@@ -112,6 +92,73 @@ __global__ __launch_bounds__(RV_NT) void k_reverb_levels(const T* __restrict__ w
             w3 = w2, w2 = w1, w1 = w0, w0 = xs[rv_at(RV_TC + o - s - 1)];
         }
     }
+}
+
+// Workgroup (blockIdx.x, l = blockIdx.y) serves outputs k0 .. k0 + RV_BLOCK - 1 of the utterance b with first[b] <= blockIdx.x <
+// first[b + 1] (first: running sums of the utterances' tiles; an empty utterance has none). Lane L owns k0 + 4 L + c, c < 4.
+template <typename T>
+__global__ __launch_bounds__(RV_NT) void k_reverb_levels(const T* __restrict__ wave, const int64_t* __restrict__ offsets,
+                                                          const int64_t* __restrict__ first, int B, const double* __restrict__ rir,
+                                                          const int64_t* __restrict__ rir_offsets, int K, int64_t total,
+                                                          double* __restrict__ out) {
+    __shared__ double xs[RV_R * RV_PLANE];
+    const int tid = threadIdx.x;
+    const int l = blockIdx.y;
+    const int64_t blk = blockIdx.x;
+    int b = 0, hi = B;      // first[b] <= blk < first[hi]
+    while (hi - b > 1) {
+        const int mid = (b + hi) >> 1;
+        if (first[mid] <= blk) b = mid;
+        else hi = mid;
+    }
+    const int64_t n = offsets[b + 1] - offsets[b];
+    const int64_t k0 = (blk - first[b]) * RV_BLOCK;
+    const int nk = (int)min((int64_t)RV_BLOCK, n - k0);      // outputs of this workgroup, >= 1
+    const T* __restrict__ x = wave + offsets[b];
+    double* __restrict__ y = out + (size_t)l * (size_t)total + (size_t)offsets[b] + (size_t)k0;
+    const int o = RV_R * tid;                                // first output of this lane inside the tile
+    if (l == K) {                                            // the dry level: the samples themselves
+#pragma unroll
+        for (int c = 0; c < RV_R; ++c)
+            if (o + c < nk) y[o + c] = (double)x[k0 + o + c];
+        return;
+    }
+    double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+    rv_walk(xs, x, n, k0, nk, rir + rir_offsets[l], rir_offsets[l + 1] - rir_offsets[l], a0, a1, a2, a3);
+    if (o < nk) y[o] = a0;
+    if (o + 1 < nk) y[o + 1] = a1;
+    if (o + 2 < nk) y[o + 2] = a2;
+    if (o + 3 < nk) y[o + 3] = a3;
+}
+
+// One room per utterance, the output in the layout of the waves. Workgroup blockIdx.x serves the tile tiles[blockIdx.x] =
+// utterance << 32 | tile index of the utterance (a list from the host, so that no workgroup searches and the expensive tiles can
+// start first); the utterance runs at room[b] in [0, K], K the dry one; room == NULL: every utterance is dry. The same walk, the
+// same bits as level room[b] of k_reverb_levels.
+template <typename T>
+__global__ __launch_bounds__(RV_NT) void k_reverb_pick(const T* __restrict__ wave, const int64_t* __restrict__ offsets,
+                                                        const int64_t* __restrict__ tiles, const double* __restrict__ rir,
+                                                        const int64_t* __restrict__ rir_offsets, const int32_t* __restrict__ room, int K,
+                                                        double* __restrict__ out) {
+    __shared__ double xs[RV_R * RV_PLANE];
+    const int tid = threadIdx.x;
+    const int64_t entry = tiles[blockIdx.x];
+    const int b = (int)(entry >> 32);
+    const int l = room ? room[b] : K;
+    const int64_t n = offsets[b + 1] - offsets[b];
+    const int64_t k0 = (entry & 0xffffffffll) * RV_BLOCK;
+    const int nk = (int)min((int64_t)RV_BLOCK, n - k0);      // outputs of this workgroup, >= 1
+    const T* __restrict__ x = wave + offsets[b];
+    double* __restrict__ y = out + (size_t)offsets[b] + (size_t)k0;
+    const int o = RV_R * tid;
+    if (l == K) {                                            // a dry utterance: the samples themselves
+#pragma unroll
+        for (int c = 0; c < RV_R; ++c)
+            if (o + c < nk) y[o + c] = (double)x[k0 + o + c];
+        return;
+    }
+    double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+    rv_walk(xs, x, n, k0, nk, rir + rir_offsets[l], rir_offsets[l + 1] - rir_offsets[l], a0, a1, a2, a3);
     if (o < nk) y[o] = a0;
     if (o + 1 < nk) y[o + 1] = a1;
     if (o + 2 < nk) y[o + 2] = a2;
@@ -193,6 +240,111 @@ extern "C" int f2_reverb_levels(f2_ctx* ctx, const void* wave, int wave_dtype, c
     F2_TRY(f2_upload_offsets(ctx, offsets, B));
     F2_TRY(f2_launch_reverb_levels(ctx, d_wave, wave_dtype, (const int64_t*)ctx->offsets.ptr, offsets, B, rir, rir_offsets, K, A,
                                    out.as<double>()));
+    F2_TRY(f2_copy_back(ctx, out));
+    return f2_host_wait(ctx, mem_space);
+}
+
+// ---- one room per utterance: f2_reverb_pick, the reverberant stage of f2_input_batch_wet / f2_trainer_render_wet ----
+
+int f2_check_reverb_pick(f2_ctx* ctx, int B, const f2_reverb_pick_args& R) {
+    F2_CHECK(ctx, R.K >= 0, F2_ERR_INVALID, "negative number of rooms (K=%d)", R.K);
+    if (R.dry()) return F2_OK;
+    F2_CHECK(ctx, R.rir, F2_ERR_INVALID, "room_of is given for K=%d rooms, but rir is NULL", R.K);
+    F2_TRY(f2_check_rir(ctx, R.rir, R.rir_offsets, R.K));
+    for (int b = 0; b < B; ++b)
+        F2_CHECK(ctx, R.room_of[b] >= 0 && R.room_of[b] <= R.K, F2_ERR_INVALID, "utterance %d: room %d is outside [0, %d]", b,
+                 (int)R.room_of[b], R.K);
+    return F2_OK;
+}
+
+static int64_t rv_tiles(const int64_t* h_offsets, int B) {
+    int64_t tiles = 0;
+    for (int b = 0; b < B; ++b) tiles += (h_offsets[b + 1] - h_offsets[b] + RV_BLOCK - 1) / RV_BLOCK;
+    return tiles;
+}
+
+void f2_reverb_pick_meta(f2_meta_carve* meta, int B, const int64_t* h_offsets, const f2_reverb_pick_args& R, f2_reverb_pick_arrays* A) {
+    meta->add(&A->d_tiles, (size_t)rv_tiles(h_offsets, B));
+    if (R.dry()) return;
+    meta->add(&A->d_room, ((size_t)B + 1) / 2);
+    if (!R.d_rir) meta->add(&A->d_rir_off, (size_t)R.K + 1), meta->add(&A->d_rir, (size_t)R.rir_offsets[R.K]);
+}
+
+int f2_launch_reverb_pick(f2_ctx* ctx, const void* d_wave, int wave_dtype, const int64_t* d_offsets, const int64_t* h_offsets, int B,
+                          const f2_reverb_pick_args& R, const f2_reverb_pick_arrays& A, double* d_out) {
+    if (B == 0 || h_offsets[B] == 0) return F2_OK;
+    const int64_t ntiles = rv_tiles(h_offsets, B);
+    F2_CHECK(ctx, ntiles < (int64_t(1) << 31), F2_ERR_UNSUPPORTED, "reverberation needs %lld workgroups (at most 2^31 - 1)",
+             (long long)ntiles);
+    const bool dry = R.dry();
+    // the tile list, utterance << 32 | tile, in (utterance, tile) order ...
+    std::vector<int64_t> tiles;
+    std::vector<int32_t> cost;   // taps the tile walks: min(T_room, k0 + nk), 0 for a dry utterance
+    tiles.reserve((size_t)ntiles);
+    for (int b = 0; b < B; ++b) {
+        const int64_t n = h_offsets[b + 1] - h_offsets[b], nt = (n + RV_BLOCK - 1) / RV_BLOCK;
+        const int l = dry ? R.K : R.room_of[b];
+        const int64_t taps = l < R.K ? R.rir_offsets[l + 1] - R.rir_offsets[l] : 0;
+        for (int64_t i = 0; i < nt; ++i) {
+            tiles.push_back((int64_t)b << 32 | i);
+            if (!dry && ctx->opt_reverb_pick_sort) cost.push_back((int32_t)std::min(taps, std::min(n, (i + 1) * RV_BLOCK)));
+        }
+    }
+    // ... or most taps first, ties in that order: the tiles that run longest do not start last. The results do not depend on it.
+    if (!cost.empty()) {
+        std::vector<int32_t> idx((size_t)ntiles);
+        for (int64_t i = 0; i < ntiles; ++i) idx[(size_t)i] = (int32_t)i;
+        std::stable_sort(idx.begin(), idx.end(), [&](int32_t a, int32_t c) { return cost[(size_t)a] > cost[(size_t)c]; });
+        std::vector<int64_t> sorted((size_t)ntiles);
+        for (int64_t i = 0; i < ntiles; ++i) sorted[(size_t)i] = tiles[(size_t)idx[(size_t)i]];
+        tiles.swap(sorted);
+    }
+    F2_TRY(f2_upload_async(ctx, A.d_tiles, tiles.data(), sizeof(int64_t) * tiles.size()));
+    const double* d_rir = nullptr;
+    const int64_t* d_rir_off = nullptr;
+    if (!dry) {
+        F2_TRY(f2_upload_async(ctx, A.d_room, R.room_of, sizeof(int32_t) * (size_t)B));
+        d_rir = R.d_rir, d_rir_off = R.d_rir_off;
+        if (!d_rir) {   // (a caller that serves several launches from one upload hands the device copies in)
+            F2_TRY(f2_upload_async(ctx, A.d_rir_off, R.rir_offsets, sizeof(int64_t) * ((size_t)R.K + 1)));
+            F2_TRY(f2_upload_async(ctx, A.d_rir, R.rir, sizeof(double) * (size_t)R.rir_offsets[R.K]));
+            d_rir = A.d_rir, d_rir_off = A.d_rir_off;
+        }
+    }
+    const int32_t* d_room = dry ? nullptr : (const int32_t*)A.d_room;
+    const dim3 grid((unsigned)ntiles);
+    if (wave_dtype == F2_WAVE_I16)
+        k_reverb_pick<int16_t><<<grid, dim3(RV_NT), 0, ctx->stream>>>((const int16_t*)d_wave, d_offsets, A.d_tiles, d_rir, d_rir_off, d_room,
+                                                                     R.K, d_out);
+    else
+        k_reverb_pick<double><<<grid, dim3(RV_NT), 0, ctx->stream>>>((const double*)d_wave, d_offsets, A.d_tiles, d_rir, d_rir_off, d_room,
+                                                                    R.K, d_out);
+    F2_HIP(ctx, hipGetLastError());
+    return F2_OK;
+}
+
+extern "C" int f2_reverb_pick(f2_ctx* ctx, const void* wave, int wave_dtype, const int64_t* offsets, int B, const double* rir,
+                              const int64_t* rir_offsets, int K, const int32_t* room_of, double* wet, int mem_space) {
+    F2_TRY(f2_check_ctx(ctx));
+    F2_CHECK(ctx, B >= 0, F2_ERR_INVALID, "bad batch size (B=%d)", B);
+    F2_TRY(f2_check_wave_dtype(ctx, wave_dtype));
+    F2_TRY(f2_check_mem_space(ctx, mem_space, false));
+    F2_TRY(f2_check_offsets(ctx, offsets, B, "offsets"));
+    const f2_reverb_pick_args R = {rir, rir_offsets, K, room_of, nullptr, nullptr};
+    F2_TRY(f2_check_reverb_pick(ctx, B, R));
+    const int64_t total = offsets[B];
+    if (B == 0 || total == 0) return F2_OK;
+    F2_CHECK(ctx, wave && wet, F2_ERR_INVALID, "null data pointer");
+    f2_reverb_pick_arrays A;
+    f2_meta_carve meta;
+    f2_reverb_pick_meta(&meta, B, offsets, R, &A);
+    F2_TRY(meta.reserve(ctx));
+    f2_output out;
+    F2_TRY(f2_place(ctx, ctx->wet, wet, sizeof(double) * (size_t)total, mem_space, true, &out));
+    const void* d_wave;
+    F2_TRY(f2_stage_wave(ctx, wave, wave_dtype, total, mem_space, &d_wave));
+    F2_TRY(f2_upload_offsets(ctx, offsets, B));
+    F2_TRY(f2_launch_reverb_pick(ctx, d_wave, wave_dtype, (const int64_t*)ctx->offsets.ptr, offsets, B, R, A, out.as<double>()));
     F2_TRY(f2_copy_back(ctx, out));
     return f2_host_wait(ctx, mem_space);
 }

@@ -9,7 +9,8 @@ produces weights; every forward pass used for evaluation is HIP kernel K4 (the t
 ``.npz`` container K4 loads, under the reference's file name ``last_trained_model``).
 
 ``TrainFromWav`` (`cnn train --engine hip --from-wav`, not in the reference) trains on windows the device renders from the WAV files,
-again before every epoch under fresh noise when asked (``--augment-snrs``).
+again before every epoch under fresh noise (``--augment-snrs``) and in a freshly drawn room per file (``--augment-t60``,
+``--augment-rirs``) when asked.
 
 ``TestModel`` (`cnn test`, not in the reference) is ``model.evaluate(x_test, y_test)`` (:136) for a saved model, broken down
 by a column of the label CSV: one ``f2_cnn_score_windows`` call on the stored windows.
@@ -319,6 +320,8 @@ class LabelledWaves:
 
 NOISE_STREAM = 0x6E6F6973       # 'nois': the generator of the epochs' noise conditions is default_rng([seed, NOISE_STREAM])
 VALIDATION_NOISE_SEED = 0x76616C69    # 'vali': the noisy validation sets are rendered once, with this seed
+ROOM_STREAM = 0x726F6F6D        # 'room': the generator of the epochs' rooms is default_rng([seed, ROOM_STREAM])
+VALIDATION_ROOM_SEED = 0x76726F6D     # 'vrom': the synthetic responses of the reverberant validation sets are built once, from this seed
 RENDER_GROUP = 64               # files per envelope pass, as `prepare input --from-wav`
 
 
@@ -328,9 +331,22 @@ def draw_epoch_noise(rng, K, B):
     return level_of, int(rng.integers(0, 2 ** 63))
 
 
-def _render_windows(ctx, waves, centers, coefs, cfg, LPF, CUTOFF, precision, snrs=(), level=None, seed=0):
+def draw_epoch_rooms(rng, Kr, B):
+    """(room_of (B) int32 in [0, Kr], room seed) of one epoch, drawn from rng in that order; Kr is the dry one"""
+    room_of = rng.integers(0, Kr + 1, B).astype(numpy.int32)
+    return room_of, int(rng.integers(0, 2 ** 63))
+
+
+def build_rooms(t60s, measured, framerate, drr_db, room_seed):
+    """The responses of one epoch (or of the validation sets): reverb.SyntheticRIR(t60, framerate, drr_db, room_seed, level) per
+    reverberation time, level its place in the list, then the measured responses, which do not change"""
+    from ... import reverb
+    return [reverb.SyntheticRIR(v, framerate, drr_db, room_seed, level) for level, v in enumerate(t60s)] + list(measured)
+
+
+def _render_windows(ctx, waves, centers, coefs, cfg, LPF, CUTOFF, precision, snrs=(), level=None, seed=0, rirs=(), room=None):
     """Normalised windows of some files through f2_input_batch_noisy, RENDER_GROUP files per call, every file at snrs[level]
-    (level None: clean)"""
+    (level None: clean); with `room`, through f2_input_batch_wet with every file in rirs[room]"""
     Cn = coefs.shape[0]
     out = numpy.empty((int(sum(len(c) for c in centers)), cfg.dots_per_input, Cn), numpy.float32)
     row = 0
@@ -344,14 +360,21 @@ def _render_windows(ctx, waves, centers, coefs, cfg, LPF, CUTOFF, precision, snr
         if n == 0:
             continue
         level_of = None if level is None else numpy.full(len(ws), level, numpy.int32)
-        ctx.input_batch_noisy(flat, _lib.WAVE_F64 if f64 else _lib.WAVE_I16, offsets, coefs, len(ws), Cn, bool(LPF),
-                              float(CUTOFF) if LPF else 0.0, precision, center_offsets, numpy.concatenate(cs), cfg.radius, cfg.step,
-                              True, snrs, level_of, g, seed, out[row:row + n], _lib.MEM_HOST)
+        if room is None:
+            ctx.input_batch_noisy(flat, _lib.WAVE_F64 if f64 else _lib.WAVE_I16, offsets, coefs, len(ws), Cn, bool(LPF),
+                                  float(CUTOFF) if LPF else 0.0, precision, center_offsets, numpy.concatenate(cs), cfg.radius, cfg.step,
+                                  True, snrs, level_of, g, seed, out[row:row + n], _lib.MEM_HOST)
+        else:
+            ctx.input_batch_wet(flat, _lib.WAVE_F64 if f64 else _lib.WAVE_I16, offsets, coefs, len(ws), Cn, bool(LPF),
+                                float(CUTOFF) if LPF else 0.0, precision, center_offsets, numpy.concatenate(cs), cfg.radius, cfg.step,
+                                True, rirs, numpy.full(len(ws), room, numpy.int32), snrs, level_of, g, seed, out[row:row + n],
+                                _lib.MEM_HOST)
         row += n
     return out
 
 
-def TrainFromWav(labelFile=None, LPF=False, CUTOFF=100, snrs=(), seed=None, ctx=None, verbose=1, on_epoch=None):
+def TrainFromWav(labelFile=None, LPF=False, CUTOFF=100, snrs=(), seed=None, ctx=None, verbose=1, on_epoch=None, t60s=(), rirs=(),
+                 drr_db=0.0):
     """`cnn train --engine hip --from-wav`: trains on windows rendered on the device from the WAV files of the label CSV.
 
     The TRAIN files go to the trainer once (Trainer.set_waves); the TEST files become normalised windows once, clean - the
@@ -361,6 +384,14 @@ def TrainFromWav(labelFile=None, LPF=False, CUTOFF=100, snrs=(), seed=None, ctx=
     renders the windows again before its steps; one more validation set per level is rendered once with
     VALIDATION_NOISE_SEED, and the history gains 'val_acc_snr' / 'val_loss_snr' (a list per level, an entry per epoch).
     'last_trained_model_results.json' gains augment = {snrs, seed, noise_seed per epoch}. seed None: one is drawn and recorded.
+    With `t60s` (seconds) and / or `rirs` (mono WAV files at the corpus' rate, reverb.LoadRIR) every epoch also draws, from
+    numpy.random.default_rng([seed, ROOM_STREAM]), a room in [0, Kr] per TRAIN file (Kr: dry) and a room seed (draw_epoch_rooms),
+    builds that epoch's synthetic responses on the host (build_rooms: SyntheticRIR(t60, framerate, drr_db, room seed, level); the
+    measured ones are fixed) and renders through Trainer.render_wet: room first, then noise at an SNR of the reverberant signal. The
+    noise generator is drawn exactly as without rooms. The TEST files are validated clean, at every SNR, and once per room (dry
+    of noise; the responses built once from VALIDATION_ROOM_SEED): the history gains 'val_acc_room' / 'val_loss_room' and augment
+    gains t60, rirs, drr and room_seed per epoch. A t60 or a measured response beyond reverb.MAX_TAPS raises reverb.py's
+    ValueError before any device work.
     on_epoch(iterations, trainer), if given, is called after each epoch's render, before its steps (for tests and for looking at
     what the network is about to see).
     BATCH_SIZE and EPOCHS come from configF2CNN.conf. Returns (F2CNNModel, history)."""
@@ -374,10 +405,16 @@ def TrainFromWav(labelFile=None, LPF=False, CUTOFF=100, snrs=(), seed=None, ctx=
     epochs = config.getint('CNN', 'EPOCHS', fallback=20)
     snrs = tuple(float(v) for v in snrs)
     K = len(snrs)
+    t60s, rir_files = tuple(float(v) for v in t60s), tuple(rirs)
+    Kr = len(t60s) + len(rir_files)
     if seed is None:
         seed = int(numpy.random.default_rng().integers(0, 2 ** 63))
     labelPath = labelFile or os.path.join('trainingData', 'label_data.csv')
     cfg = F2Config()
+    # (the rooms before anything else: a response that is too long is refused here, with reverb.py's message)
+    from ... import reverb
+    measured = [reverb.LoadRIR(r, cfg.framerate) for r in rir_files]
+    val_rooms = build_rooms(t60s, measured, cfg.framerate, drr_db, VALIDATION_ROOM_SEED)
     lw = LabelledWaves(labelPath)
     waves = lw.read(cfg.radius * cfg.step)
     train, test = lw.split(False), lw.split(True)
@@ -390,6 +427,8 @@ def TrainFromWav(labelFile=None, LPF=False, CUTOFF=100, snrs=(), seed=None, ctx=
     print('Rising train:', int((y_train == 1).sum()))
     print('Falling train:', int((y_train == 0).sum()))
     print(len(train), 'train files,', len(test), 'test files; noise levels (dB):', list(snrs) or 'none')
+    if Kr:
+        print('rooms: t60 (s)', list(t60s) or 'none', '| measured', list(rir_files) or 'none', '| drr (dB) {:g}'.format(float(drr_db)))
     _, coefs = filterbank_from_config(cfg)
     coefs = numpy.ascontiguousarray(coefs, dtype=numpy.float64)
     ctx = ctx or _lib.default_context()
@@ -399,30 +438,42 @@ def TrainFromWav(labelFile=None, LPF=False, CUTOFF=100, snrs=(), seed=None, ctx=
         for l in range(K if len(y_test) else 0):
             val.append(_render_windows(ctx, [waves[k] for k in test], [lw.centers[k] for k in test], coefs, cfg, LPF, CUTOFF,
                                        FFT_PRECISION, snrs, l, VALIDATION_NOISE_SEED))
+        for r in range(Kr if len(y_test) else 0):
+            val.append(_render_windows(ctx, [waves[k] for k in test], [lw.centers[k] for k in test], coefs, cfg, LPF, CUTOFF,
+                                       FFT_PRECISION, rirs=val_rooms, room=r))
         x_val, y_val = numpy.concatenate(val), numpy.tile(y_test, len(val))
         groups = numpy.repeat(numpy.arange(len(val), dtype=numpy.int32), len(y_test))
         trainer, rng = _hip_trainer(cfg.dots_per_input, coefs.shape[0], seed, 1e-4, 1e-6, ctx)
         trainer.set_waves([waves[k] for k in train], [lw.centers[k] for k in train], [lw.signs[k] for k in train], coefs, cfg.radius,
                           cfg.step, lpf=bool(LPF), cutoff=float(CUTOFF) if LPF else 0.0, precision=FFT_PRECISION, group=RENDER_GROUP)
         noise_rng = numpy.random.default_rng([seed, NOISE_STREAM])
+        room_rng = numpy.random.default_rng([seed, ROOM_STREAM])
         noise_seeds, val_snr = [], {"val_acc_snr": [[] for _ in snrs], "val_loss_snr": [[] for _ in snrs]}
-        if not K:
+        room_seeds, val_room = [], {"val_acc_room": [[] for _ in range(Kr)], "val_loss_room": [[] for _ in range(Kr)]}
+        if not K and not Kr:
             trainer.render()
 
         def run_epoch():
+            level_of, noise_seed = None, 0
             if K:
                 level_of, noise_seed = draw_epoch_noise(noise_rng, K, len(train))
-                trainer.render(snrs, level_of, noise_seed)
                 noise_seeds.append(noise_seed)
+            if Kr:
+                room_of, room_seed = draw_epoch_rooms(room_rng, Kr, len(train))
+                room_seeds.append(room_seed)
+                trainer.render_wet(build_rooms(t60s, measured, cfg.framerate, drr_db, room_seed), room_of, snrs, level_of, noise_seed)
+            elif K:
+                trainer.render(snrs, level_of, noise_seed)
             if on_epoch:
                 on_epoch(trainer.iterations, trainer)
             return trainer.steps(rng.permutation(len(y_train)), batch_size)
 
         def validate():
             if not len(y_test):
-                for k in val_snr:
-                    for per_level in val_snr[k]:
-                        per_level.append(float("nan"))
+                for per in (val_snr, val_room):
+                    for k in per:
+                        for per_level in per[k]:
+                            per_level.append(float("nan"))
                 return float("nan"), float("nan")
             _, _, counts, loss_sum = _hip_validate(trainer, ctx, x_val, y_val, groups=groups, n_groups=len(val))
             acc = (counts[:, 0, 0] + counts[:, 1, 1]) / float(len(y_test))
@@ -430,8 +481,12 @@ def TrainFromWav(labelFile=None, LPF=False, CUTOFF=100, snrs=(), seed=None, ctx=
             for l in range(K):
                 val_snr["val_acc_snr"][l].append(float(acc[l + 1]))
                 val_snr["val_loss_snr"][l].append(float(loss[l + 1]))
-            if verbose and K:
-                print("    val_acc clean {:.4f}".format(acc[0]) + "".join(" | {:g} dB {:.4f}".format(s, a) for s, a in zip(snrs, acc[1:])))
+            for r in range(Kr):
+                val_room["val_acc_room"][r].append(float(acc[K + 1 + r]))
+                val_room["val_loss_room"][r].append(float(loss[K + 1 + r]))
+            if verbose and (K or Kr):
+                print("    val_acc clean {:.4f}".format(acc[0]) + "".join(" | {:g} dB {:.4f}".format(s, a) for s, a in zip(snrs, acc[1:])) +
+                      "".join(" | room {} {:.4f}".format(r, a) for r, a in enumerate(acc[K + 1:])))
             return float(loss[0]), float(acc[0])
 
         model, history = fit_epochs(run_epoch, validate, trainer.model, len(y_train), epochs, verbose)
@@ -441,14 +496,18 @@ def TrainFromWav(labelFile=None, LPF=False, CUTOFF=100, snrs=(), seed=None, ctx=
         raise
     if K:
         history.update(val_snr)
+    if Kr:
+        history.update(val_room)
     model.save('last_trained_model')
     print("Model saved as 'last_trained_model'.")
     if len(y_test):
         print('Test loss:', history["val_loss"][-1])
         print('Test accuracy:', history["val_acc"][-1])
     results = dict(history)
-    if K:
+    if K or Kr:
         results["augment"] = {"snrs": list(snrs), "seed": int(seed), "noise_seed": noise_seeds}
+    if Kr:
+        results["augment"].update({"t60": list(t60s), "rirs": list(rir_files), "drr": float(drr_db), "room_seed": room_seeds})
     with open('last_trained_model_results.json', 'w') as fp:
         json.dump(results, fp)
     print("History saved as 'last_trained_model_results.json'")

@@ -1016,6 +1016,61 @@ int f2_trainer_render(f2_ctx* ctx, f2_trainer* trainer, const double* snr_db, in
 int f2_trainer_get_windows(f2_ctx* ctx, const f2_trainer* trainer, int64_t first, int64_t count, float* x /* host */,
                            uint8_t* y /* host */);
 
+/* ---- Training in rooms: one impulse response per utterance, new every epoch -------------------------------------------------
+ * Reverberation acts on the waveform, before the filterbank, as noise does; a tensor of stored windows cannot be reverberated.
+ * f2_reverb_levels makes every one of K rooms for every utterance, level-major - what a sweep wants. A training render wants one
+ * room per utterance, in the layout of the waves, and these entries make that and nothing else. They compose with the noise
+ * entries above: room first, then noise at an SNR of the reverberant signal. (f2_version stays 115 with these entries: look the
+ * symbols up.)
+ *
+ * f2_reverb_pick (stateless): utterance b of `wet` (offsets[B] float64, the layout of `wave`) at room l = room_of[b]:
+ *   l < K    wet[b][k] = sum_{t = 0 .. min(k, T_l - 1)} h_l[t] * x_b[k - t], numpy.convolve(x_b, h_l)[:n_b], by f2_reverb_levels'
+ *            arithmetic word for word: one float64 accumulator per output, taps in ascending t, acc = fma(h[t], x[k-t], acc), no
+ *            atomics, no sum split across lanes. Bit for bit utterance b of level l of f2_reverb_levels for the same rir - the
+ *            tile of 1024 outputs and the chunk of 1024 taps are walked by the same code, so that this holds for a sum that
+ *            underflowed to a signed zero as well (that call's one liberty).
+ *   l == K   the samples converted to float64, exactly
+ *   room_of == NULL or K == 0: every utterance is dry, and rir / rir_offsets may be NULL.
+ * A sample depends on (x_b, h_l, k) alone: not on B, the utterance's place in the batch, the rooms of the other utterances, the
+ * memory space or the input dtype of equal values.
+ *   kernel   one workgroup per tile of 1024 outputs and nothing else (the sweep's grid is tiles x levels); the tap walk of a tile
+ *            is the sweep's own function. A tile costs min(T_l, k0 + 1024) taps and nothing when dry, so the host, which knows every
+ *            cost, uploads the list of (utterance, tile) most taps first, ties in (utterance, tile) order, and a workgroup reads
+ *            its entry: the long tiles do not start last, and no workgroup searches the offsets. The results do not depend on
+ *            the order (context option "reverb_pick_sort" = 0: utterance by utterance).
+ *   wave, wet   in mem_space (F2_MEM_HOST or F2_MEM_DEVICE); device pointers need element alignment only; plain vector stores
+ *   offsets, rir, rir_offsets (K+1), room_of (B)   host
+ * F2_MEM_DEVICE: the call enqueues on the context's stream and returns; F2_MEM_HOST: it returns when wet is filled.
+ * Errors, before anything is launched or written: what f2_reverb_levels rejects of ctx, offsets, B, wave_dtype and mem_space; K < 0;
+ * unless every utterance is dry: a NULL rir (room_of given with K > 0), what f2_reverb_levels rejects of rir and rir_offsets with its
+ * statuses (K > 64 and more than F2_REVERB_MAX_TAPS = 32768 taps: F2_ERR_UNSUPPORTED), a room_of entry outside [0, K] (the message
+ * names the utterance): F2_ERR_INVALID. NULL wave or wet with samples: F2_ERR_INVALID. B == 0 or no samples: F2_OK.
+ *
+ * f2_input_batch_wet: f2_input_batch_noisy's arguments plus rir, rir_offsets, Kr, room_of. Bit for bit
+ * f2_input_batch(F2_WAVE_F64, ...) on f2_noise_pick(F2_WAVE_F64, ...) on f2_reverb_pick(...): the same code on two buffers in
+ * context scratch that never leave the device (the noise kernels read one and write the other). Sigma of an utterance is
+ * therefore the RMS of its reverberant signal by the sweep's fixed-order float64 rule, for a dry utterance among rooms too. With
+ * Kr == 0 or room_of == NULL there is no reverberant stage and the result is bit for bit f2_input_batch_noisy (whose sigma of
+ * int16 samples is the int64 one). Errors: those of f2_input_batch_noisy, then those of f2_reverb_pick, all before a launch.
+ *
+ * f2_trainer_render_wet: f2_trainer_render with a room per utterance. Group g is bit for bit f2_input_batch_wet on its utterances
+ * with first_utterance = g group, normalize = 1 and the stored options, written straight to its rows of x; the scratch is bounded
+ * by the group; the taps go up once per call, not once per group; one wait at the end. room_of, level_of: host, B, or NULL.
+ * f2_trainer_render is this call without rooms, bit for bit. Errors: f2_trainer_render's and f2_reverb_pick's, nothing launched.
+ */
+int f2_reverb_pick(f2_ctx* ctx, const void* wave, int wave_dtype, const int64_t* offsets /* host, B+1 */, int B,
+                   const double* rir /* host, rir_offsets[K] taps */, const int64_t* rir_offsets /* host, K+1 */, int K,
+                   const int32_t* room_of /* host, B, each in [0, K], or NULL */,
+                   double* wet /* offsets[B] float64, mem_space, layout of `wave` */, int mem_space);
+int f2_input_batch_wet(f2_ctx* ctx, const void* wave, int wave_dtype, const int64_t* offsets, const double* coefs, int B, int C,
+                       int lpf, double cutoff_hz, int fft_precision, const int64_t* center_offsets, const int64_t* centers,
+                       int radius, int step, int normalize, const double* rir, const int64_t* rir_offsets, int Kr,
+                       const int32_t* room_of, const double* snr_db, int K, const int32_t* level_of, uint32_t first_utterance,
+                       uint64_t seed, float* windows, int mem_space);
+int f2_trainer_render_wet(f2_ctx* ctx, f2_trainer* trainer, const double* rir, const int64_t* rir_offsets, int Kr,
+                          const int32_t* room_of /* host, B, or NULL */, const double* snr_db, int K,
+                          const int32_t* level_of /* host, B, or NULL */, uint64_t seed);
+
 #ifdef __cplusplus
 }
 #endif
