@@ -270,18 +270,53 @@ __device__ __forceinline__ float lowpass_pairs_store_tab(const float (&er)[NBLK]
 // (the read-only tables are separate __restrict__ kernel arguments: pointers inside a by-value struct carry no
 // no-alias information, and the wave-uniform reads among them would then go through the vector memory path)
 struct SpecParams {
-    int64_t xpitch;           // X: [nutt][xpitch] spectra of the utterances of this launch, k = 0..H
-    int64_t tpitch;           // HU: [C][tpitch] {Hs.re, Hs.im, u.re, u.im}, Hs = (2/M) s N_1..N_4 u^4
+    // (what a row's first addresses need comes first: eight words, one scalar load behind the eight table pointers)
+    unsigned xpitch;          // X: [nutt][xpitch] spectra of the utterances of this launch, k = 0..H
+    unsigned tpitch;          // HU: [C][tpitch] {Hs.re, Hs.im, u.re, u.im}, Hs = (2/M) s N_1..N_4 u^4
+    int C;
+    int c0;                   // first channel of this launch, see row_decode
+    int gdiv;                 // channels per channel group in this launch
+    unsigned gmul;            // rr / gdiv = (rr * gmul) >> gshift for rr < 2^31
+    int gshift;
+    int lpf;
     double* env;
     int* uflag;               // [B] set to 1 when a row of the utterance fails the accuracy guard
-    int C;
-    int nutt;
-    int lpf;
-    LowpassConsts lp;
     float tol;
+    LowpassConsts lp;
     float* gdump;             // diagnostic (option "spectral_guard_dump"): [B][C][4] {row max, padding residual, low-passed row max, flagged}
     unsigned long long* stamps;   // diagnostic build only
 };
+
+// Rows in the order (channel group of CG channels, utterance, channel in the group): the workgroups in flight then
+// share CG channel tables instead of C (workgroups are handed to the XCDs in turn: CG / 8 tables of 128 KB per XCD's L2)
+// while an utterance's spectrum is still used by CG consecutive workgroups. Measured on 1000 x 1 s, 128 channels: 6.54 ms
+// with CG = 32 against 6.71 ms with the plain (utterance, channel) order.
+// The grid is two-dimensional - blockIdx.y the channel group, blockIdx.x the row inside it, so the linear dispatch order
+// is this order - and the division by the group's size a multiplication by a reciprocal from the host (row_decode_consts):
+// no run-time division stands in front of a row's addresses. The partial last group (C % CG channels) has fewer rows than
+// the full ones and is a launch of its own (c0 = its first channel).
+template <int CG>
+__device__ __forceinline__ void row_decode(const SpecParams& P, int& u, int& c) {
+    const unsigned rr = blockIdx.x;
+    const unsigned uu = (unsigned)(((unsigned long long)rr * P.gmul) >> P.gshift);
+    u = (int)uu;
+    c = P.c0 + (int)(blockIdx.y * CG + (rr - uu * (unsigned)P.gdiv));
+}
+// Host: the constants of row_decode for groups of d channels (1 <= d <= 32) from channel c0 on, and the grid of `ngroups` such
+// groups. gmul = ceil(2^(31 + l) / d), l = ceil(log2 d): floor(rr gmul / 2^(31 + l)) = floor(rr / d) for every rr < 2^31
+// (Granlund & Montgomery 1994, theorem 4.2 with N = 31), and gmul <= 2^32 / (1 + 2^(1 - l)) (d a power of two: 2^31) fits 32 bits.
+// False: more rows per group than a grid row holds.
+static bool row_decode_consts(int c0, int d, int ngroups, int nutt, SpecParams* P, dim3* grid) {
+    if (d < 1 || d > 32 || (int64_t)nutt * d > 0x7fffffff) return false;
+    int l = 0;
+    while ((1 << l) < d) ++l;
+    P->c0 = c0;
+    P->gdiv = d;
+    P->gmul = (unsigned)((((unsigned long long)1 << (31 + l)) + (unsigned)d - 1) / (unsigned)d);
+    P->gshift = 31 + l;
+    *grid = dim3((unsigned)(nutt * d), (unsigned)ngroups);
+    return true;
+}
 
 // the ringing term (2/M) s u^4 Q(w) of one bin: the Horner chain over the digits of Q
 __device__ __forceinline__ cpx<float> ringing_bin(f2_f4 hu, cpx<float> w, const float* __restrict__ rho) {
@@ -404,6 +439,19 @@ __device__ __forceinline__ void zero_front_padding(float (&er)[NBLK], float (&ei
     }
 }
 
+// (diagnostic build: the stamps of a row go to its slot - the grid is two-dimensional, F2_STAMP_STORE counts along x alone)
+#ifdef F2_STAMPS
+#define F2_STAMP_STORE_ROW(st, N, out, row)                                                             \
+    do {                                                                                                \
+        if (threadIdx.x == 0 && (out))                                                                  \
+            for (int k_ = 0; k_ < (N); ++k_) (out)[(size_t)(row) * (N) + k_] = (st)[k_];                \
+    } while (0)
+#else
+#define F2_STAMP_STORE_ROW(st, N, out, row) \
+    do {                                    \
+    } while (0)
+#endif
+
 // one thread per row, after the barrier behind the last atomicMax: flag the utterance if the padding-region residual exceeds
 // tol x the maximum of the row AS DELIVERED (low-passed when the low-pass is on)
 __device__ __forceinline__ void guard_decide(const SpecParams& P, const unsigned* guard, int b, int c) {
@@ -420,12 +468,13 @@ __device__ __forceinline__ void guard_decide(const SpecParams& P, const unsigned
     }
 }
 
+// (the eight pointers are the first 64 bytes of the kernel arguments, what a row's addresses need of P the next 32: loaded together, one wait)
 template <int LOG2H, bool PADFIRST>
 __global__ __launch_bounds__((threads_for<float, LOG2H>()), (min_waves_for<float, LOG2H>())) void k_spectral_envelope(
-    SpecParams P, const cpx<float>* __restrict__ Xall /* utterance spectra */, const f2_f4* __restrict__ HUall,
+    const cpx<float>* __restrict__ Xall /* utterance spectra */, const f2_f4* __restrict__ HUall,
     const cpx<float>* __restrict__ E /* [M] exp(-2 pi i q / M) */, const float* __restrict__ rho_all /* [rows][8] digits of Q */,
-    const int64_t* __restrict__ offsets, const int* __restrict__ ulist, const f2_f4* __restrict__ lptab,
-    const cpx<float>* __restrict__ tw) {
+    const int64_t* __restrict__ offsets, const int* __restrict__ ulist, const cpx<float>* __restrict__ tw,
+    const f2_f4* __restrict__ lptab, SpecParams P) {
     constexpr int NT = threads_for<float, LOG2H>();
     constexpr int H = 1 << LOG2H;
     constexpr int M = 2 * H;
@@ -446,39 +495,15 @@ __global__ __launch_bounds__((threads_for<float, LOG2H>()), (min_waves_for<float
     cpx<float>* lds = reinterpret_cast<cpx<float>*>(smem);
 
     const int tid = threadIdx.x;
-    // Rows in the order (channel group of CG channels, utterance, channel in the group): the workgroups in flight then
-    // share CG channel tables instead of C (workgroup b runs on XCD b % 8: CG / 8 tables of 128 KB per XCD's L2) while an
-    // utterance's spectrum is still used by CG consecutive workgroups. Measured on 1000 x 1 s, 128 channels: 6.54 ms
-    // with CG = 32 against 6.71 ms with the plain (utterance, channel) order.
     int u, c;
-    {
-        constexpr int CG = KS_CGROUP;
-        const int nfull = P.C / CG, per = P.nutt * CG;
-        const int cg = min((int)(blockIdx.x / per), nfull);          // the last group may be partial
-        const int rr = blockIdx.x - cg * per;
-        const int gsz = cg < nfull ? CG : P.C - nfull * CG;
-        u = rr / gsz;
-        c = cg * CG + (rr - u * gsz);
-    }
+    row_decode<KS_CGROUP>(P, u, c);
     const int row_id = u * P.C + c;
-    const int b = ulist[u];
-    const int64_t off = offsets[b];
-    const int n = (int)(offsets[b + 1] - off);
-    const int np = M - n;            // the row is padded in front: transform sample i is row sample i - np
-    double* __restrict__ y = P.env + ((size_t)P.C * (size_t)off + (size_t)c * (size_t)n);
-    const float* __restrict__ rho = rho_all + (size_t)row_id * 8;
-    const cpx<float>* __restrict__ Xu = Xall + (size_t)u * P.xpitch;
-    const f2_f4* __restrict__ HUc = HUall + (size_t)c * P.tpitch;
+    const float* __restrict__ rho_g = rho_all + (size_t)row_id * 8;
+    const cpx<float>* __restrict__ Xu = Xall + (size_t)((unsigned long long)(unsigned)u * P.xpitch);   // (32 x 32 -> 64 bits)
+    const f2_f4* __restrict__ HUc = HUall + (size_t)((unsigned long long)(unsigned)c * P.tpitch);
 
     F2_STAMP_ARRAY(st, 8);   // (-DF2_STAMPS: phase boundaries)
     F2_STAMP(st, 0);
-    {
-        // (table base + pass offset stay scalar, the lane's part is a 32-bit byte offset with the scalar part added in 32 bits)
-        unsigned tw1 = plan_tw_offset(LOG2H, 1) * (unsigned)sizeof(cpx<float>);
-        asm volatile("" : "+s"(tw1));
-        for (int i = tid; i < TWL; i += NT)
-            twl[i] = *reinterpret_cast<const cpx<float>*>(reinterpret_cast<const char*>(tw) + ((unsigned)i * (unsigned)sizeof(cpx<float>) + tw1));
-    }
     if (tid < 4) guard[tid] = 0u;
 
     // 1. spectrum of the front-padded row at this thread's bins k = tid + j NB0 (first-pass register layout). Per bin two
@@ -492,8 +517,32 @@ __global__ __launch_bounds__((threads_for<float, LOG2H>()), (min_waves_for<float
     static_assert(NB0 == NT && plan_npass(LOG2H) >= 3, "fft_pass0_pair + fft_from_pass0");
     cpx<float> vo[PT];   // conj(A_o) / M = conj(A) w_k / M, formed while the bin's phase factor is at hand
     cpx<float> w0 = E[tid];
-    const cpx<float> XH = Xu[H];    // Nyquist bin (wave-uniform addresses: scalar loads, issued up front)
+    // Every vector load a row starts with is issued before the first wait for one. The twiddles of the later passes go to LDS:
+    // each thread loads its entries here, without a branch (threads beyond the table take its last entry), and writes them
+    // below, behind the issue of the table loads - `twl` is first read after the first barrier of the transforms.
+    constexpr int TWIT = (TWL + NT - 1) / NT;
+    cpx<float> twr[TWIT > 0 ? TWIT : 1];
+    {
+        // (table base + pass offset stay scalar, the lane's part is a 32-bit byte offset with the scalar part added in 32 bits)
+        unsigned tw1 = plan_tw_offset(LOG2H, 1) * (unsigned)sizeof(cpx<float>);
+        asm volatile("" : "+s"(tw1));
+#pragma unroll
+        for (int it = 0; it < TWIT; ++it) {
+            const unsigned i = (it + 1) * NT <= TWL ? (unsigned)(tid + it * NT) : min((unsigned)(tid + it * NT), (unsigned)(TWL - 1));
+            twr[it] = *reinterpret_cast<const cpx<float>*>(reinterpret_cast<const char*>(tw) + (i * (unsigned)sizeof(cpx<float>) + tw1));
+        }
+    }
+    // (The two twiddles the first pass of the transforms loads - their addresses need `tid` only - stay where they are, behind
+    // the spectrum phase: loaded here and handed to fft_pass0_pair, every row came out different in the last bit. The
+    // compiler then fuses other products of the pass's complex multiplications. DESIGN.md section 6h.)
+    // Nyquist bin and the row's digits (wave-uniform addresses: scalar loads), issued here by every wave and pinned in scalar
+    // registers below: left alone the compiler sinks the bin's loads into thread 0's block behind the bin loop, loads the
+    // digits a second time there, and wave 0 of every row waits for that round trip on its own
+    const cpx<float> XH = Xu[H];
     const f2_f4 HUH = HUc[H];
+    float rho[8];
+#pragma unroll
+    for (int q = 0; q < 8; ++q) rho[q] = rho_g[q];
     cpx<float> Xl[2][GB];
     f2_f4 Hl[2][GB];
     // The lane offset is laundered through an empty asm together with a result of each group, so that the loads of group g + 2
@@ -504,11 +553,39 @@ __global__ __launch_bounds__((threads_for<float, LOG2H>()), (min_waves_for<float
     unsigned kb8 = (unsigned)tid * (unsigned)sizeof(cpx<float>);
     asm volatile("" : "+v"(kb8));
     const __amdgpu_buffer_rsrc_t Xb = table_buffer(Xu, (H + 1) * (int)sizeof(cpx<float>)), HUb = table_buffer(HUc, (H + 1) * (int)sizeof(f2_f4));
+    // Issued in the order the bins are consumed in - the first and the last bin of the group come first, the laundering below
+    // asks for their results - and kept in it: the waits of those two bins are then counted ones that leave the other 28 loads
+    // in flight. (Left to the scheduler the loads come in clusters per table, and the first two bins wait for 24 of the 32.)
+    int b = 0;
 #pragma unroll
-    for (int q = 0; q < GB; ++q) {
+    for (int qq = 0; qq < GB; ++qq) {
+        const int q = qq == 0 ? 0 : qq == 1 ? GB - 1 : qq - 1;
         Xl[0][q] = lane_load<cpx<float>>(Xb, kb8, q * NB0);
         Hl[0][q] = lane_load<f2_f4>(HUb, 2 * kb8, q * NB0);
+        __builtin_amdgcn_sched_barrier(0);
+        // The row's place and length (ulist -> offsets, two dependent scalar round trips) are needed by nothing before the
+        // transforms: the first load of that chain is issued here, behind the first table loads, so that the wait for the
+        // table pointers in front of them does not also wait for it. It is waited for with the Nyquist bin and the digits
+        // below, the second where the compiler puts it (behind the first two bins), both while table loads are in flight.
+        if (qq == 0) {
+            int u_late = u;
+            asm volatile("" : "+s"(u_late));
+            b = ulist[u_late];
+        }
     }
+    float nyq[6] = {XH.re, XH.im, HUH.x, HUH.y, HUH.z, HUH.w};
+    asm volatile("" : "+s"(nyq[0]), "+s"(nyq[1]), "+s"(nyq[2]), "+s"(nyq[3]), "+s"(nyq[4]), "+s"(nyq[5]));
+    asm volatile("" : "+s"(rho[0]), "+s"(rho[1]), "+s"(rho[2]), "+s"(rho[3]), "+s"(rho[4]), "+s"(rho[5]), "+s"(rho[6]), "+s"(rho[7]));
+    // (the twiddles were loaded in front of the tables: their wait is a counted one that leaves the table loads in flight. No
+    // branch here either - the threads beyond the table write its last entry once more, the value it gets anyway: inside a
+    // branch the compiler sinks the load to the write, behind all the table loads, and waits for every one of them)
+#pragma unroll
+    for (int it = 0; it < TWIT; ++it) twl[(it + 1) * NT <= TWL ? tid + it * NT : min(tid + it * NT, TWL - 1)] = twr[it];
+    asm volatile("" : "+s"(b));
+    const int64_t off = offsets[b];
+    const int n = (int)(offsets[b + 1] - off);
+    const int np = M - n;            // the row is padded in front: transform sample i is row sample i - np
+    double* __restrict__ y = P.env + ((size_t)P.C * (size_t)off + (size_t)c * (size_t)n);
 #pragma unroll
     for (int g = 0; g < NG; ++g) {
         if (g + 1 < NG) {
@@ -543,7 +620,7 @@ __global__ __launch_bounds__((threads_for<float, LOG2H>()), (min_waves_for<float
     // k = 0 carries the Nyquist term: A_e(0) = A(0) + A(H), A_o(0) = A(0) - A(H) (both real); thread 0 keeps
     // (Y'(0), Y'(H)) in yk[0]
     if (tid == 0) {
-        const cpx<float> yh = spectral_bin(XH, HUH, cpx<float>{-1.f, 0.f}, rho);
+        const cpx<float> yh = spectral_bin(cpx<float>{nyq[0], nyq[1]}, f2_f4{nyq[2], nyq[3], nyq[4], nyq[5]}, cpx<float>{-1.f, 0.f}, rho);
         yk[0] = {yk[0].re, yh.re};
     }
     float er[NBLK], ei[NBLK];
@@ -618,7 +695,7 @@ __global__ __launch_bounds__((threads_for<float, LOG2H>()), (min_waves_for<float
             guard_decide(P, guard, b, c);
     }
     F2_STAMP(st, 7);
-    F2_STAMP_STORE(st, 8, P.stamps);
+    F2_STAMP_STORE_ROW(st, 8, P.stamps, row_id);
 }
 
 // ---- rows of 32769 .. 65472 samples: M = 65536, H = 32768 ----
@@ -648,9 +725,9 @@ __device__ __forceinline__ int park_plane(int n, int bank, int r) {
     return n + 4 * MB + before;
 }
 __global__ __launch_bounds__(1024, 4) void k_spectral_envelope_long(
-    SpecParams P, const cpx<float>* __restrict__ Xall, const f2_f4* __restrict__ HUall, const cpx<float>* __restrict__ E,
+    const cpx<float>* __restrict__ Xall, const f2_f4* __restrict__ HUall, const cpx<float>* __restrict__ E,
     const float* __restrict__ rho_all, const int64_t* __restrict__ offsets, const int* __restrict__ ulist,
-    const f2_f4* __restrict__ lptab, const cpx<float>* __restrict__ tw) {
+    const cpx<float>* __restrict__ tw, const f2_f4* __restrict__ lptab, SpecParams P) {
     constexpr int LOG2Q = 14, NT = 1024, Q = 1 << LOG2Q, H = 2 * Q, M = 2 * H;
     static_assert(threads_for<float, LOG2Q>() == NT, "the 16-16-4-16 plan on 1024 threads");
     constexpr int CS = cpad_size(Q);
@@ -667,25 +744,22 @@ __global__ __launch_bounds__(1024, 4) void k_spectral_envelope_long(
 
     const int tid = threadIdx.x;
     int u, c;
-    {
-        constexpr int CG = KS_CGROUP_LONG;
-        const int nfull = P.C / CG, per = P.nutt * CG;
-        const int cg = min((int)(blockIdx.x / per), nfull);
-        const int rr = blockIdx.x - cg * per;
-        const int gsz = cg < nfull ? CG : P.C - nfull * CG;
-        u = rr / gsz;
-        c = cg * CG + (rr - u * gsz);
-    }
+    row_decode<KS_CGROUP_LONG>(P, u, c);
     const int row_id = u * P.C + c;
     const int b = ulist[u];
     const int64_t off = offsets[b];
     const int n = (int)(offsets[b + 1] - off);
     double* __restrict__ y = P.env + ((size_t)P.C * (size_t)off + (size_t)c * (size_t)n);
     const float* __restrict__ rho = rho_all + (size_t)row_id * 8;
-    const cpx<float>* __restrict__ Xu = Xall + (size_t)u * P.xpitch;
-    const f2_f4* __restrict__ HUc = HUall + (size_t)c * P.tpitch;
+    const cpx<float>* __restrict__ Xu = Xall + (size_t)((unsigned long long)(unsigned)u * P.xpitch);   // (32 x 32 -> 64 bits)
+    const f2_f4* __restrict__ HUc = HUall + (size_t)((unsigned long long)(unsigned)c * P.tpitch);
 
-    for (int i = tid; i < TWL; i += NT) twl[i] = tw[plan_tw_offset(LOG2Q, 1) + i];
+    // (as in k_spectral_envelope: the twiddles of the later passes are loaded without a branch and written to LDS behind the
+    // issue of the loads that follow)
+    constexpr int TWIT = (TWL + NT - 1) / NT;
+    cpx<float> twr[TWIT];
+#pragma unroll
+    for (int it = 0; it < TWIT; ++it) twr[it] = tw[plan_tw_offset(LOG2Q, 1) + ((it + 1) * NT <= TWL ? tid + it * NT : min(tid + it * NT, TWL - 1))];
     if (tid < 4) guard[tid] = 0u;
     if (tid == 0) ychain = 0.0;
 
@@ -693,6 +767,9 @@ __global__ __launch_bounds__(1024, 4) void k_spectral_envelope_long(
     cpx<float> w0 = E[tid];
     cpx<float> z0 = E[((unsigned)tid * (unsigned)n) & (M - 1)];
     const cpx<float> zq = E[((unsigned)Q * (unsigned)n) & (M - 1)];   // w_Q^n = (-i)^n
+#pragma unroll
+    for (int it = 0; it < TWIT; ++it)
+        if ((it + 1) * NT <= TWL || tid + it * NT < TWL) twl[tid + it * NT] = twr[it];
     float yh = 0.f;   // Y'(H) (real)
     if (tid == 0) yh = spectral_bin(Xu[H], HUc[H], cpx<float>{-1.f, 0.f}, cpx<float>{(n & 1) ? -1.f : 1.f, 0.f}, rho).re;
     constexpr bool T0R = derive_tw0<float, LOG2Q>();
@@ -812,7 +889,7 @@ __global__ __launch_bounds__(1024, 4) void k_spectral_envelope_long(
             guard_decide(P, guard, b, c);
     }
     F2_STAMP(st, 7);
-    F2_STAMP_STORE(st, 8, P.stamps);
+    F2_STAMP_STORE_ROW(st, 8, P.stamps, row_id);
 }
 
 // ---- X = DFT_M(x zero-padded), k = 0..H, float64 arithmetic, float32 out ----
@@ -1256,12 +1333,11 @@ static int launch_group(f2_ctx* ctx, const WaveT* d_wave, const int64_t* d_offse
     F2_HIP(ctx, hipGetLastError());
     F2_TRY(f2_prof_end(ctx, F2_K_TAIL));
     SpecParams P;
-    P.xpitch = xpitch;
-    P.tpitch = tab->tpitch;
+    P.xpitch = (unsigned)xpitch;
+    P.tpitch = (unsigned)tab->tpitch;
     P.env = d_env;
     P.uflag = d_uflag;
     P.C = C;
-    P.nutt = nutt;
     P.lpf = lpf;
     const f2_f4* d_lptab = nullptr;
     F2_TRY(lowpass_table(ctx, a1, b0, threads_for<float, FFTLOG>(), 2, &P.lp, &d_lptab));
@@ -1272,19 +1348,28 @@ static int launch_group(f2_ctx* ctx, const WaveT* d_wave, const int64_t* d_offse
     F2_TRY(f2_stamps_buffer(ctx, (size_t)nutt * C, 8, &P.stamps));
 #endif
     F2_TRY(f2_prof_begin(ctx, F2_K_FUSED));
-    if constexpr (LOG2H == 15)
-        hipLaunchKernelGGL(k_spectral_envelope_long, dim3((unsigned)((size_t)nutt * C)), dim3(threads_for<float, FFTLOG>()), 0,
-                           ctx->stream, P, (const cpx<float>*)d_X, (const f2_f4*)tab->hu.ptr, (const cpx<float>*)tab->e.ptr,
-                           (const float*)d_rho, d_offsets, d_ulist, d_lptab, (const cpx<float>*)ctx->tw[0][FFTLOG].ptr);
-    else if (min_n >= 15 * (M / 16))    // every row's padding lies in the first block: the guard looks at that block only
-        hipLaunchKernelGGL((k_spectral_envelope<FFTLOG, true>), dim3((unsigned)((size_t)nutt * C)), dim3(threads_for<float, FFTLOG>()), 0,
-                           ctx->stream, P, (const cpx<float>*)d_X, (const f2_f4*)tab->hu.ptr, (const cpx<float>*)tab->e.ptr,
-                           (const float*)d_rho, d_offsets, d_ulist, d_lptab, (const cpx<float>*)ctx->tw[0][FFTLOG].ptr);
-    else
-        hipLaunchKernelGGL((k_spectral_envelope<FFTLOG, false>), dim3((unsigned)((size_t)nutt * C)), dim3(threads_for<float, FFTLOG>()), 0,
-                           ctx->stream, P, (const cpx<float>*)d_X, (const f2_f4*)tab->hu.ptr, (const cpx<float>*)tab->e.ptr,
-                           (const float*)d_rho, d_offsets, d_ulist, d_lptab, (const cpx<float>*)ctx->tw[0][FFTLOG].ptr);
-    F2_HIP(ctx, hipGetLastError());
+    // the full channel groups in one launch, the partial last group (C % CG channels) in a second one
+    constexpr int CG = LOG2H == 15 ? KS_CGROUP_LONG : KS_CGROUP;
+    for (int part = 0; part < 2; ++part) {
+        const int ngroups = part ? 1 : C / CG, d = part ? C % CG : CG;
+        if (ngroups == 0 || d == 0) continue;
+        dim3 grid;
+        if (!row_decode_consts(part ? C - d : 0, d, ngroups, nutt, &P, &grid))
+            return f2_fail(ctx, F2_ERR_UNSUPPORTED, "spectral path: %d utterances in one launch", nutt);
+        if constexpr (LOG2H == 15)
+            hipLaunchKernelGGL(k_spectral_envelope_long, grid, dim3(threads_for<float, FFTLOG>()), 0, ctx->stream, (const cpx<float>*)d_X,
+                               (const f2_f4*)tab->hu.ptr, (const cpx<float>*)tab->e.ptr, (const float*)d_rho, d_offsets, d_ulist,
+                               (const cpx<float>*)ctx->tw[0][FFTLOG].ptr, d_lptab, P);
+        else if (min_n >= 15 * (M / 16))    // every row's padding lies in the first block: the guard looks at that block only
+            hipLaunchKernelGGL((k_spectral_envelope<FFTLOG, true>), grid, dim3(threads_for<float, FFTLOG>()), 0, ctx->stream,
+                               (const cpx<float>*)d_X, (const f2_f4*)tab->hu.ptr, (const cpx<float>*)tab->e.ptr, (const float*)d_rho, d_offsets,
+                               d_ulist, (const cpx<float>*)ctx->tw[0][FFTLOG].ptr, d_lptab, P);
+        else
+            hipLaunchKernelGGL((k_spectral_envelope<FFTLOG, false>), grid, dim3(threads_for<float, FFTLOG>()), 0, ctx->stream,
+                               (const cpx<float>*)d_X, (const f2_f4*)tab->hu.ptr, (const cpx<float>*)tab->e.ptr, (const float*)d_rho, d_offsets,
+                               d_ulist, (const cpx<float>*)ctx->tw[0][FFTLOG].ptr, d_lptab, P);
+        F2_HIP(ctx, hipGetLastError());
+    }
     F2_TRY(f2_prof_end(ctx, F2_K_FUSED));
 #ifdef F2_STAMPS
     static const char* names_s[8] = {"", "bin 0 ready", "bin 7 ready", "bin 15 ready", "transform inputs", "both transforms + even magnitudes", "odd magnitudes + guard", "lpf+stores"};
