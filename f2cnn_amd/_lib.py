@@ -26,6 +26,9 @@ REVERB_BLOCK, REVERB_TAP_CHUNK, REVERB_MAX_TAPS = 1024, 1024, 32768
 # tile constants of k_channel_mix_levels (csrc/f2_internal.h: F2_SMEAR_TILE_SAMPLES samples by F2_SMEAR_TILE_CHANNELS output channels
 # per workgroup) and the most channels and levels f2_channel_mix_levels takes (F2_SMEAR_MAX_CHANNELS, F2_SMEAR_MAX_LEVELS)
 SMEAR_TILE_SAMPLES, SMEAR_TILE_CHANNELS, SMEAR_MAX_CHANNELS, SMEAR_MAX_LEVELS = 512, 16, 512, 64
+# tile constant of k_shaped_noise_levels (csrc/f2_internal.h: F2_SHAPED_BLOCK outputs per workgroup) and the longest filter and the most
+# levels f2_shaped_noise_levels takes (F2_SHAPED_MAX_TAPS, F2_SHAPED_MAX_LEVELS)
+SHAPED_BLOCK, SHAPED_MAX_TAPS, SHAPED_MAX_LEVELS = 1024, 2048, 64
 
 _vp, _i, _i64, _d = C.c_void_p, C.c_int, C.c_int64, C.c_double
 _P = C.POINTER
@@ -114,6 +117,9 @@ SIGNATURES = {
     "f2_input_batch_wet": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i, _i, _d, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _vp,
                                 C.c_uint32, C.c_uint64, _vp, _i]),
     "f2_trainer_render_wet": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, C.c_uint64]),
+    "f2_shaped_noise_levels": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _i, C.c_uint64, _vp, _vp, _i]),
+    "f2_eval_shaped_noise_sweep": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _d, _i, _i, _i, _i, _vp, _vp, _vp, _i, C.c_uint64, _vp,
+                                        _vp, _vp, _vp, _vp, _vp, _i]),
 }
 TRAINER_WHAT = {"weights": 0, "accumulators": 1, "gradient": 2}   # F2_TRAINER_* of f2_trainer_get
 
@@ -489,6 +495,36 @@ class Context:
                                                 _ptr(snr) if len(snr) else None, len(snr), int(seed) & (2 ** 64 - 1), _ptr(noisy),
                                                 _ptr(scores), _ptr(labels), _ptr(window_offsets), _ptr(sigma), _ptr(stats),
                                                 mem_space))
+        return window_offsets, sigma, stats
+
+    def shaped_noise_levels(self, wave, wave_dtype, offsets, B, snr_db, firs, seed, noisy, mem_space, sigma=None):
+        """The batch under coloured noise at every level and clean, in one device pass (see f2_shaped_noise_levels): level l has the
+        SNR snr_db[l] and the filter firs[l] (a sequence of 1-D float64 arrays, always host arrays; the library does not normalise
+        them). noisy receives (K+1) * offsets[B] float64, level-major, the clean level last (wave and noisy numpy arrays or device
+        pointers, by mem_space). Returns sigma ((K+1)*B, float64), allocating it if it is not given."""
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        snr = np.ascontiguousarray(snr_db, dtype=np.float64).reshape(-1)
+        taps, fir_offsets = _pack_firs(firs, len(snr))
+        if sigma is None:
+            sigma = np.zeros((len(snr) + 1) * int(B), np.float64)
+        self.check(self.lib.f2_shaped_noise_levels(self.handle, _ptr(wave), wave_dtype, _ptr(offsets), int(B),
+                                                   _ptr(snr) if len(snr) else None, _ptr(taps) if len(taps) else None, _ptr(fir_offsets),
+                                                   len(snr), int(seed) & (2 ** 64 - 1), _ptr(noisy), _ptr(sigma), mem_space))
+        return sigma
+
+    def eval_shaped_noise_sweep(self, handle, wave, wave_dtype, offsets, coefs, B, Cn, lpf, cutoff, precision, radius, step, hop,
+                                snr_db, firs, seed, noisy, scores, labels, mem_space, window_offsets=None, sigma=None, stats=None):
+        """eval_noise_sweep with a filter per level (see f2_eval_shaped_noise_sweep): level l is the batch under noise of the colour
+        firs[l] at snr_db[l], the clean level last. Returns (window_offsets, sigma, stats) as eval_noise_sweep does."""
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        snr = np.ascontiguousarray(snr_db, dtype=np.float64).reshape(-1)
+        taps, fir_offsets = _pack_firs(firs, len(snr))
+        window_offsets, stats, sigma = _sweep_outputs((len(snr) + 1) * int(B), window_offsets, stats, sigma, True)
+        self.check(self.lib.f2_eval_shaped_noise_sweep(self.handle, handle, _ptr(wave), wave_dtype, _ptr(offsets), _ptr(coefs), int(B),
+                                                       Cn, int(bool(lpf)), float(cutoff), precision, radius, step, int(hop),
+                                                       _ptr(snr) if len(snr) else None, _ptr(taps) if len(taps) else None,
+                                                       _ptr(fir_offsets), len(snr), int(seed) & (2 ** 64 - 1), _ptr(noisy), _ptr(scores),
+                                                       _ptr(labels), _ptr(window_offsets), _ptr(sigma), _ptr(stats), mem_space))
         return window_offsets, sigma, stats
 
     def lowpass_levels(self, env, offsets, B, Cn, cutoffs, levels, mem_space):
@@ -915,6 +951,14 @@ def _pack_rirs(rirs):
     rir_offsets[1:] = np.cumsum([len(h) for h in rirs])
     taps = np.concatenate(rirs) if rirs else np.zeros(0, np.float64)
     return np.ascontiguousarray(taps), rir_offsets
+
+
+def _pack_firs(firs, K):
+    """(taps, fir_offsets) of f2_shaped_noise_levels: one filter per level of snr_db, packed as _pack_rirs packs responses"""
+    firs = list(firs)
+    if len(firs) != K:
+        raise ValueError("{} filters for {} noise levels (one per level is needed)".format(len(firs), K))
+    return _pack_rirs(firs)
 
 
 def _rooms(rirs, room_of):

@@ -39,6 +39,16 @@ package implements:
     python -m f2cnn_amd cnn noisesweep --file/-f WAV --snrs 20,10,0,-3 [--seed N] [--save-wavs] [--hop N|frame] [--lpf HZ] [--model/-m NPZ]
                                                             (the file at every level and clean in one device pass, agreement
                                                              with the clean decisions per level; not in the reference)
+    python -m f2cnn_amd cnn noisesweep --file/-f WAV --snrs 20,10,0 --colours white,pink,speech,like:babble.wav,fir:taps.npy [--noise-taps N] [--seed N] [--hop N|frame] [--lpf HZ] [--accuracy [MODE]] [--resample] [--save-wavs]
+                                                            (the same under coloured noise: every colour at every level, colour-
+                                                             major, at most 64 levels, in one device pass - Gaussian noise through
+                                                             a filter of N taps (default 1025, odd) with the long-term spectrum of
+                                                             pink or brown noise, of speech, of a mono recording at the file's rate
+                                                             (like:) or of taps of one's own (fir:), scaled so that an SNR means
+                                                             what it means for white noise; levels are named like `pink 10dB`,
+                                                             written to OutputWavFiles/addedNoise/<stem>.coloursweep.npz; --colours
+                                                             and --noise-taps are refused on every other command; not in the
+                                                             reference)
     python -m f2cnn_amd cnn lpfsweep --file/-f WAV --cutoffs 5,10,20,50,100 [--hop N|frame] [--accuracy [MODE]] [--resample] [--model/-m NPZ]
                                                             (the file at every envelope cutoff and unfiltered in one device pass -
                                                              filterbank and Hilbert envelope run once - agreement with the
@@ -219,6 +229,32 @@ def drr_argument(text):
     return drr
 
 
+NOISE_COLOURS = ('white', 'pink', 'brown', 'speech')     # noise.COLOURS (kept here so that parsing imports nothing)
+NOISE_LEVELS_MAX = 64
+
+
+def colours_argument(text):
+    """--colours: a comma-separated list of at least one colour - a name of NOISE_COLOURS, like:<recording.wav> or fir:<taps.npy>"""
+    colours = text.split(',')
+    for c in colours:
+        named = c.split(':', 1)
+        if not (c in NOISE_COLOURS or (len(named) == 2 and named[0] in ('like', 'fir') and named[1])):
+            raise argparse.ArgumentTypeError("--colours takes a comma-separated list of {}, like:<recording.wav> or fir:<taps.npy>, "
+                                             "not {!r}".format(', '.join(NOISE_COLOURS), text))
+    return colours
+
+
+def noise_taps_argument(text):
+    """--noise-taps: an odd, positive number of filter taps (the library's limit is checked where the filters are built)"""
+    try:
+        taps = int(text)
+    except ValueError:
+        taps = 0
+    if taps < 1 or taps % 2 == 0:
+        raise argparse.ArgumentTypeError("--noise-taps takes an odd, positive number of taps, not {!r}".format(text))
+    return taps
+
+
 def build_parser():
     parser = argparse.ArgumentParser(prog="f2cnn_amd", description="F2CNN hot path on MI355X.")
     parser.add_argument('--configure', action='store_true', help='write configF2CNN.conf with default values')
@@ -281,6 +317,12 @@ def build_parser():
     c.add_argument('--augment-rirs', action='store', type=augment_rirs_argument, dest='augment_rirs', default=argparse.SUPPRESS,
                    help="train --engine hip --from-wav: comma-separated mono WAV files with measured impulse responses, further rooms "
                         "of the draw")
+    # (absent from the parsed arguments unless given: the commands parse as before without them)
+    c.add_argument('--colours', action='store', type=colours_argument, dest='colours', default=argparse.SUPPRESS,
+                   help="noisesweep: comma-separated noise colours - white, pink, brown, speech, like:<recording.wav> (the long-term "
+                        "spectrum of a mono recording at the file's rate), fir:<taps.npy> - every one at every level of --snrs")
+    c.add_argument('--noise-taps', action='store', type=noise_taps_argument, dest='noise_taps', default=argparse.SUPPRESS,
+                   help="noisesweep --colours: taps of the designed noise filters, odd (default 1025, at most 2047)")
     c.add_argument('--seed', action='store', type=int, dest='seed',
                    help="noisesweep: seed of the noise (default 0); train --from-wav: seed of the weights, the order and the noise")
     c.add_argument('--save-wavs', action='store_true', dest='save_wavs',
@@ -371,7 +413,8 @@ def labelled_window_files(args):
 SWEEPS = {
     'noisesweep': (False, None, "use evalnoise {} for one level", ('snrs',),
                    "Please use --snrs to give the noise levels, e.g. --snrs 20,10,0,-3",
-                   lambda E, a, kw: E.EvaluateNoiseSweep([a.file], a.snrs, seed=a.seed or 0, save_wavs=a.save_wavs, **kw)),
+                   lambda E, a, kw: E.EvaluateNoiseSweep([a.file], a.snrs, seed=a.seed or 0, save_wavs=a.save_wavs, **kw,
+                                                         **colour_keywords(a))),
     'lpfsweep': (True, "the cutoffs come from --cutoffs; the unfiltered level is always there", "use eval --lpf HZ {} for one cutoff",
                  ('cutoffs',), "Please use --cutoffs to give the envelope cutoffs in Hz, e.g. --cutoffs 5,10,20,50,100",
                  lambda E, a, kw: E.EvaluateCutoffSweep([a.file], a.cutoffs, **kw)),
@@ -385,6 +428,34 @@ SWEEPS = {
                    "of vocoder bands, e.g. --bands 32,16,8",
                    lambda E, a, kw: E.EvaluateSmearSweep([a.file], spreads=getattr(a, 'spreads', ()), bands=getattr(a, 'bands', ()), **kw)),
 }
+
+
+def colour_keywords(args):
+    """what --colours / --noise-taps add to EvaluateNoiseSweep's call: nothing unless given, so that the call without them is the
+    one it was"""
+    kw = {}
+    if 'colours' in args:
+        kw['colours'] = args.colours
+        if 'noise_taps' in args:
+            kw['noise_taps'] = args.noise_taps
+    return kw
+
+
+def colours_refusal(args):
+    """What is wrong with --colours / --noise-taps on this command line, or None. Looks at the arguments alone."""
+    given = [opt for attr, opt in (('colours', '--colours'), ('noise_taps', '--noise-taps')) if attr in args]
+    if not given:
+        return None
+    if args.cnn_command != 'noisesweep':
+        if args.cnn_command in SWEEPS:
+            return "{} is not supported by {} (the noise colours belong to noisesweep)".format(given[0], args.cnn_command)
+        return "{} only applies to 'cnn noisesweep'".format(given[0])
+    if 'colours' not in args:
+        return "--noise-taps belongs to --colours"
+    if args.snrs is not None and len(args.colours) * len(args.snrs) > NOISE_LEVELS_MAX:
+        return "a noise sweep takes at most {} levels, not {} colours x {} SNRs = {}".format(
+            NOISE_LEVELS_MAX, len(args.colours), len(args.snrs), len(args.colours) * len(args.snrs))
+    return None
 
 
 def from_wav_refusal(args):
@@ -460,7 +531,7 @@ def main(argv=None):
         if getattr(report, "exit_status", 0):          # some files could not be processed (the others were)
             return report.exit_status
     elif 'cnn_command' in args:
-        refusal = from_wav_refusal(args) or rooms_refusal(args)
+        refusal = from_wav_refusal(args) or rooms_refusal(args) or colours_refusal(args)
         if refusal:
             print(refusal)
             return 1

@@ -594,6 +594,29 @@ int f2_check_reverb_pick(f2_ctx* ctx, int B, const f2_reverb_pick_args& R);
 void f2_reverb_pick_meta(f2_meta_carve* meta, int B, const int64_t* h_offsets, const f2_reverb_pick_args& R, f2_reverb_pick_arrays* A);
 int f2_launch_reverb_pick(f2_ctx* ctx, const void* d_wave, int wave_dtype, const int64_t* d_offsets, const int64_t* h_offsets, int B,
                           const f2_reverb_pick_args& R, const f2_reverb_pick_arrays& A, double* d_out);
+// f2_noise_shaped.hip, the kernel of f2_shaped_noise_levels / f2_eval_shaped_noise_sweep. A workgroup of k_shaped_noise_levels makes
+// F2_SHAPED_BLOCK consecutive outputs of one utterance at one level; the deviates of its whole span, up to F2_SHAPED_BLOCK +
+// F2_SHAPED_MAX_TAPS float64 values, are what it stages in LDS.
+// f2_check_fir: the white sweep's checks of K and snr_db (K >= 1, snr_db non-NULL and finite: F2_ERR_INVALID), then fir / fir_offsets
+// non-NULL (F2_ERR_INVALID), K <= F2_SHAPED_MAX_LEVELS (F2_ERR_UNSUPPORTED), fir_offsets from 0 and non-decreasing, every filter of
+// 1 .. F2_SHAPED_MAX_TAPS finite taps (F2_ERR_INVALID; too many taps: F2_ERR_UNSUPPORTED); the messages name the level.
+// f2_shaped_meta names the device arrays of a launch in the call's f2_meta_carve (before its reserve()); the launch uploads them
+// (10^(snr_db / 10), tile sums, fir_offsets and taps, all from host memory), runs f2_launch_noise_sigma into d_sigma ((K + 1) * B,
+// level-major), reads the B utterances of d_wave once per level and writes (K + 1) * h_offsets[B] doubles, level-major, level K the
+// clean samples.
+#define F2_SHAPED_BLOCK 1024
+#define F2_SHAPED_MAX_TAPS 2048
+#define F2_SHAPED_MAX_LEVELS 64
+struct f2_shaped_arrays {
+    double *d_sigma = nullptr, *d_lin = nullptr;        // (K + 1) * B sigmas; K values 10^(snr_db / 10)
+    int64_t *d_first = nullptr, *d_fir_off = nullptr;   // B + 1 running sums of the utterances' tiles; K + 1 tap offsets
+    double* d_fir = nullptr;                            // fir_offsets[K] taps
+};
+int f2_check_fir(f2_ctx* ctx, const double* snr_db, const double* fir, const int64_t* fir_offsets, int K);
+void f2_shaped_meta(f2_meta_carve* meta, int B, const int64_t* fir_offsets, int K, f2_shaped_arrays* A);
+int f2_launch_shaped_noise_levels(f2_ctx* ctx, const void* d_wave, int wave_dtype, const int64_t* d_offsets, const int64_t* h_offsets,
+                                  int B, const double* snr_db, const double* fir, const int64_t* fir_offsets, int K, uint64_t seed,
+                                  const f2_shaped_arrays& A, double* d_out);
 // f2_smear.hip, the kernel of f2_channel_mix_levels / f2_eval_smear_sweep. A workgroup of k_channel_mix_levels makes
 // F2_SMEAR_TILE_CHANNELS output channels of F2_SMEAR_TILE_SAMPLES consecutive samples of one utterance at one level.
 // f2_check_mix: K in 1 .. F2_SMEAR_MAX_LEVELS and mix non-NULL (F2_ERR_INVALID; too many levels, or C above

@@ -79,13 +79,8 @@ __global__ __launch_bounds__(SIGMA_THREADS) void k_noise_pick_sigma(const T* __r
     if (threadIdx.x == 0) sigma[b] = sigma_of(rms, lin[l], offsets[b + 1] == offsets[b]);
 }
 
-// the standard normal deviate of (seed, level, utterance, sample): the cosine branch of Box-Muller on two 53-bit uniforms
-__device__ inline double noise_deviate(uint64_t seed, uint32_t level, uint32_t utt, uint64_t i) {
-    const philox_words w = philox4x32_10((uint32_t)i, (uint32_t)(i >> 32), level, utt, (uint32_t)seed, (uint32_t)(seed >> 32));
-    const double u1 = ((double)(w.w0 >> 5) * 67108864.0 + (double)(w.w1 >> 6) + 1.0) * 0x1p-53;   // (0, 1]
-    const double u2 = ((double)(w.w2 >> 5) * 67108864.0 + (double)(w.w3 >> 6)) * 0x1p-53;         // [0, 1)
-    return sqrt(-2.0 * log(u1)) * cos(6.283185307179586 * u2);
-}
+// (noise_deviate, the standard normal deviate of (seed, level, utterance, sample), lives in f2_philox.h: k_shaped_noise_levels of
+// f2_noise_shaped.hip draws from the same function)
 
 // utterance of sample p of the batch: the last b with offsets[b] <= p (empty utterances are stepped over)
 __device__ inline int utterance_of(const int64_t* __restrict__ offsets, int B, int64_t p) {

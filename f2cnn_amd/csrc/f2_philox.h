@@ -24,4 +24,13 @@ __device__ inline philox_words philox4x32_10(uint32_t c0, uint32_t c1, uint32_t 
     return {c0, c1, c2, c3};
 }
 
+// the standard normal deviate of (seed, level, utterance, sample): the cosine branch of Box-Muller on two 53-bit uniforms. One
+// function for the white noise kernels (f2_noise.hip) and the coloured one (f2_noise_shaped.hip): the same bits in both.
+__device__ inline double noise_deviate(uint64_t seed, uint32_t level, uint32_t utt, uint64_t i) {
+    const philox_words w = philox4x32_10((uint32_t)i, (uint32_t)(i >> 32), level, utt, (uint32_t)seed, (uint32_t)(seed >> 32));
+    const double u1 = ((double)(w.w0 >> 5) * 67108864.0 + (double)(w.w1 >> 6) + 1.0) * 0x1p-53;   // (0, 1]
+    const double u2 = ((double)(w.w2 >> 5) * 67108864.0 + (double)(w.w3 >> 6)) * 0x1p-53;         // [0, 1)
+    return sqrt(-2.0 * log(u1)) * cos(6.283185307179586 * u2);
+}
+
 #endif

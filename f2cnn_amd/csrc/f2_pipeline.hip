@@ -691,6 +691,27 @@ int f2_eval_reverb_sweep(f2_ctx* ctx, const f2_cnn* cnn, const void* wave, int w
         wet_or_null, scores_or_null, labels_or_null, window_offsets_or_null, stats_or_null);
 }
 
+// f2_eval_shaped_noise_sweep: a wave sweep whose levels come from k_noise_sigma and k_shaped_noise_levels (f2_noise_shaped.hip). Only
+// the clean samples and the taps go up; sigma, stats and what the caller asked for come back behind one wait.
+int f2_eval_shaped_noise_sweep(f2_ctx* ctx, const f2_cnn* cnn, const void* wave, int wave_dtype, const int64_t* offsets,
+                               const double* coefs, int B, int C, int lpf, double cutoff_hz, int fft_precision, int radius, int step,
+                               int hop, const double* snr_db, const double* fir, const int64_t* fir_offsets, int K, uint64_t seed,
+                               double* noisy_or_null, float* scores_or_null, uint8_t* labels_or_null, int64_t* window_offsets_or_null,
+                               double* sigma_or_null, int64_t* stats_or_null, int mem_space) {
+    const f2_batch X = {wave, wave_dtype, offsets, coefs, B, C, lpf, cutoff_hz, fft_precision, mem_space};
+    f2_shaped_arrays A;
+    return wave_sweep(
+        ctx, cnn, X, radius, step, hop, K, [&] { return f2_check_fir(ctx, snr_db, fir, fir_offsets, K); },
+        [&](f2_meta_carve* meta, size_t) { f2_shaped_meta(meta, B, fir_offsets, K, &A); },
+        [&](const int64_t* d_offsets, int64_t total, double* d_noisy) -> int {
+            const void* d_wave;
+            F2_TRY(f2_stage_wave(ctx, wave, wave_dtype, total, mem_space, &d_wave));
+            return f2_launch_shaped_noise_levels(ctx, d_wave, wave_dtype, d_offsets, offsets, B, snr_db, fir, fir_offsets, K, seed, A,
+                                                 d_noisy);
+        },
+        noisy_or_null, scores_or_null, labels_or_null, window_offsets_or_null, stats_or_null, sigma_or_null, &A.d_sigma);
+}
+
 // f2_eval_cutoff_sweep: an envelope sweep whose levels come from k_lowpass_levels (f2_lowpass.hip), on the unfiltered envelopes. Only
 // the samples and the K coefficient pairs go up; one wait at the end.
 int f2_eval_cutoff_sweep(f2_ctx* ctx, const f2_cnn* cnn, const void* wave, int wave_dtype, const int64_t* offsets,

@@ -959,7 +959,7 @@ def _run_sweep(axis, files, hop, model, ctx, accuracy, resample):
 
 
 def EvaluateNoiseSweep(files, SNRdBs, seed=0, hop=None, LPF=False, CUTOFF=50, model='last_trained_model', save_wavs=False,
-                       ctx=None, accuracy=None, resample=False):
+                       ctx=None, accuracy=None, resample=False, colours=None, noise_taps=1025):
     """`cnn noisesweep` (not in the reference, whose EvaluateWithNoise :193-221 takes one file at one level): every file at
     every level of SNRdBs and clean in one device pass per group of files (f2_eval_noise_sweep: the noise is drawn on the device
     from (seed, level, file's place in its group, sample), so a sweep repeats bit for bit), with the clean run of the same
@@ -973,12 +973,21 @@ def EvaluateNoiseSweep(files, SNRdBs, seed=0, hop=None, LPF=False, CUTOFF=50, mo
     call per group): the file's results gain accuracy_vtr (K+1) and confusion (K+1, 2, 2), [level][ref][pred], the clean level
     last, and the printed lines the accuracy. With resample= the files are brought to the configured framerate first (one
     device call per kind of file), the results gain framerate and source_framerate, and a file whose rate differed is left out
-    of the accuracy."""
+    of the accuracy.
+    With colours= (`--colours`: names of noise.COLOURS, 'like:<recording.wav>', 'fir:<taps.npy>') the noise of a level is
+    Gaussian noise of that colour (f2_eval_shaped_noise_sweep: the same deviates through a filter of noise_taps taps, built once
+    per framerate by noise.FromSpec and normalised to sum h^2 = 1, so an SNR means what it means without the option). The levels
+    are colour-major over SNRdBs, at most 64, named like 'pink 10dB'; the file is <stem>.coloursweep.npz - a white sweep's
+    .sweep.npz is never overwritten - with the keys above, snr_db per level, and colours (a string per level), fir and fir_offsets
+    (the taps of all levels and where each level's start); save_wavs writes <stem>_<colour>_<SNR>dB.WAV. colours=None is the
+    white sweep as it was, to the byte."""
     if isinstance(files, (str, bytes, os.PathLike)):
         files = [files]
     snr = numpy.asarray(SNRdBs, dtype=numpy.float64).reshape(-1)
     if not len(snr) or not numpy.isfinite(snr).all():
         raise ValueError("a noise sweep needs at least one finite SNR in dB")
+    if colours is not None:
+        return _EvaluateColourSweep(files, snr, colours, noise_taps, seed, hop, LPF, CUTOFF, model, save_wavs, ctx, accuracy, resample)
     K = len(snr)
 
     def call(ctx, handle, flat, dt, offsets, coefs, B, Cn, radius, STEP, hop, framerate, labels):
@@ -995,6 +1004,72 @@ def EvaluateNoiseSweep(files, SNRdBs, seed=0, hop=None, LPF=False, CUTOFF=50, mo
                       own=own, order=('snr_db', 'sigma', 'windows', 'rising', 'agree', 'agreement', 'seed', 'hop'),
                       out=lambda file: os.path.join(outdir, os.path.basename(_noisy_copy_paths(file, 0)[0]) + '.sweep.npz'),
                       outdir=outdir, wav_target=lambda file, l: _noisy_copy_paths(file, snr[l])[1])
+    return _run_sweep(axis, files, hop, model, ctx, accuracy, resample)
+
+
+COLOUR_LEVELS_MAX = 64
+
+
+def ColourLevels(colours, snrs):
+    """The level grid of a coloured sweep, colour-major over the SNRs: [(colour spec, printed colour, SNR)] - level
+    c * len(snrs) + s is colour c at SNR s. ValueError for no colour, an unknown one, or more than COLOUR_LEVELS_MAX levels."""
+    from ... import noise
+    if isinstance(colours, str):
+        colours = colours.split(',')
+    colours = [str(c) for c in colours]
+    if not colours or not all(colours):
+        raise ValueError("a coloured noise sweep needs at least one colour")
+    for c in colours:
+        if not c.startswith(('like:', 'fir:')) and c not in noise.COLOURS:
+            raise ValueError("unknown noise colour {!r} (one of {}, like:<recording.wav>, fir:<taps.npy>)".format(
+                c, ', '.join(noise.COLOURS)))
+        if c in ('like:', 'fir:'):
+            raise ValueError("{} needs a file name behind it".format(c))
+    if len(colours) * len(snrs) > COLOUR_LEVELS_MAX:
+        raise ValueError("a noise sweep takes at most {} levels, not {} colours x {} SNRs = {}".format(
+            COLOUR_LEVELS_MAX, len(colours), len(snrs), len(colours) * len(snrs)))
+    return [(c, noise.SpecName(c), float(v)) for c in colours for v in snrs]
+
+
+def _EvaluateColourSweep(files, snr, colours, noise_taps, seed, hop, LPF, CUTOFF, model, save_wavs, ctx, accuracy, resample):
+    """EvaluateNoiseSweep with colours: the arguments are checked before any file is read"""
+    from ... import noise
+    grid = ColourLevels(colours, snr)
+    noise._check_taps(noise_taps)
+    K = len(grid)
+    level_snr = numpy.array([v for _, _, v in grid], numpy.float64)
+    level_colour = numpy.array([name for _, name, _ in grid], dtype=str)
+    filters_at = {}                               # per framerate: one filter per colour, shared by its levels
+
+    def firs(framerate):
+        if framerate not in filters_at:
+            built = {}
+            for spec, _, _ in grid:
+                if spec not in built:
+                    built[spec] = noise.FromSpec(spec, framerate, noise_taps)
+            filters_at[framerate] = [built[spec] for spec, _, _ in grid]
+        return filters_at[framerate]
+
+    def call(ctx, handle, flat, dt, offsets, coefs, B, Cn, radius, STEP, hop, framerate, labels):
+        noisy = numpy.empty((K + 1) * int(offsets[-1]), numpy.float64) if save_wavs else None
+        wo, sigma, stats = ctx.eval_shaped_noise_sweep(handle, flat, dt, offsets, coefs, B, Cn, bool(LPF), CUTOFF if LPF else 0.0,
+                                                       FFT_PRECISION, radius, STEP, hop, level_snr, firs(framerate), seed, noisy, None,
+                                                       labels, _lib.MEM_HOST)
+        return wo, stats, noisy, sigma
+
+    def own(sigma, rows, wo, n, radius, STEP, hop, framerate):
+        hs = firs(framerate)
+        return dict(snr_db=level_snr.copy(), colours=level_colour.copy(), sigma=sigma[rows].copy(),
+                    seed=numpy.uint64(int(seed) & (2 ** 64 - 1)), fir=numpy.concatenate(hs),
+                    fir_offsets=numpy.concatenate([[0], numpy.cumsum([len(h) for h in hs])]).astype(numpy.int64))
+
+    outdir = os.path.join('OutputWavFiles', 'addedNoise')
+    stem = lambda file: os.path.basename(os.path.splitext(file)[0])
+    axis = _SweepAxis(names=['{} {}dB'.format(name, _level_text(v)) for _, name, v in grid], referee='clean', label="{:>16}",
+                      limit=float('inf'), call=call, own=own,
+                      order=('snr_db', 'colours', 'sigma', 'windows', 'rising', 'agree', 'agreement', 'seed', 'hop'),
+                      out=lambda file: os.path.join(outdir, stem(file) + '.coloursweep.npz'), outdir=outdir,
+                      wav_target=lambda file, l: os.path.join(outdir, '{}_{}_{}dB'.format(stem(file), grid[l][1], _level_text(grid[l][2]))))
     return _run_sweep(axis, files, hop, model, ctx, accuracy, resample)
 
 

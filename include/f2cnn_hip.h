@@ -1071,6 +1071,75 @@ int f2_trainer_render_wet(f2_ctx* ctx, f2_trainer* trainer, const double* rir, c
                           const int32_t* room_of /* host, B, or NULL */, const double* snr_db, int K,
                           const int32_t* level_of /* host, B, or NULL */, uint64_t seed);
 
+/* ---- `cnn noisesweep --colours`: one ragged batch under K coloured noises and clean, in one device pass ---------------------
+ * The white sweep (f2_eval_noise_sweep) with a filter per level between the generator and the sum: pink, speech-shaped or
+ * matched noise instead of white. (f2_version stays 114 with these two entries: look the symbols up to find out whether a
+ * build has them.)
+ *
+ * f2_shaped_noise_levels: level l < K has an SNR snr_db[l] and a filter h_l of T_l = fir_offsets[l+1] - fir_offsets[l] float64
+ * taps at fir + fir_offsets[l]. Sample i (counted from the utterance's first sample) of utterance b becomes
+ *     c     = sum over t = 0 .. T_l - 1 of h_l[t] * z(seed, l, b, (i - t) mod 2^64)
+ *     noisy = clean + sigma * c
+ *     sigma = RMS(clean_b) / 10^(snr_db[l] / 10)
+ *   deviate      z(seed, l, b, i) is the deviate of f2_eval_noise_sweep - Philox4x32-10 with counter (i & 0xffffffff, i >> 32, l,
+ *                b) and key (seed & 0xffffffff, seed >> 32), two 53-bit uniforms, the cosine branch of Box-Muller - made by the
+ *                same device function.
+ *   before the utterance   the index i - t wraps as an unsigned 64-bit counter, so the samples before the utterance's first are
+ *                deviates like any others, with counter words (low, 0xffffffff, l, b): the noise is stationary from sample 0 on;
+ *                there is no zero lead-in and no transient.
+ *   arithmetic   one float64 accumulator per output sample, starting from 0.0; taps in ascending t; each step is
+ *                acc = fma(h[t], z[i-t], acc). Then noisy = clean + sigma * c, product and sum rounded separately; where sigma
+ *                is 0 (level K, an all-zero or empty utterance) the clean sample exactly. No atomics, and the sum of one
+ *                output is never split across lanes or workgroups. A sample therefore depends on (seed, l, b, i, h_l) and its
+ *                clean utterance alone - not on B, the utterances around it, the launch shape, the tile size, the memory space
+ *                or the input dtype of equal values.
+ *   sigma        the white sweep's rule and its kernel: the same bits as f2_eval_noise_sweep's sigma for the same snr_db.
+ *   filter gain  the library does not normalise the filters. With sum h^2 = 1 the expected noise power is sigma^2, so that "SNR"
+ *                means what it means for the white sweep; f2cnn_amd/noise.py normalises every filter it hands out.
+ *   white        T_l = 1, h_l = [1.0] reproduces level l of f2_eval_noise_sweep bit for bit: fma(1.0, z, 0.0) is z.
+ *   level K      the clean batch converted to float64 (exact for int16).
+ *   kernel       direct form; one workgroup per (tile of 1024 outputs, level); the deviates of the tile's span [k0 - (T_l - 1),
+ *                k0 + 1024) generated once into LDS as float64 (24 KB at 2048 taps), the taps read through the scalar path, four
+ *                consecutive outputs per lane on a sliding register window: the walk of f2_reverb_levels.
+ * noisy is level-major, (K+1) * offsets[B] float64; level l, utterance b is utterance u = l*B + b of a (K+1)*B batch whose
+ * offsets are the clean offsets tiled, as in f2_eval_noise_sweep. snr_db, fir and fir_offsets are always host pointers, and so
+ * is sigma_or_null ((K+1)*B, level-major, 0 for level K). wave and noisy are in mem_space; device pointers need element
+ * alignment only. F2_MEM_DEVICE: the call enqueues on the context's stream and returns (it waits only to hand back sigma);
+ * F2_MEM_HOST: it returns when noisy is filled.
+ * Limits: T_l <= 2048 (F2_SHAPED_MAX_TAPS, 128 ms at 16 kHz), K <= 64.
+ * F2_ERR_INVALID, with nothing launched and no output written: a NULL ctx or offsets; offsets that do not start at 0 or that
+ * decrease; B < 0; a bad wave_dtype or mem_space; K < 1, a NULL snr_db or a snr_db[k] that is not finite (f2_eval_noise_sweep's
+ * checks); a NULL fir or fir_offsets; fir_offsets[0] != 0 or decreasing fir_offsets; a level with no taps; a tap that is not
+ * finite (the messages name the level); NULL wave or noisy with offsets[B] > 0. F2_ERR_UNSUPPORTED, likewise: K > 64; a filter of
+ * more than 2048 taps; (K+1)*B beyond what f2_eval_noise_sweep accepts. B == 0 or offsets[B] == 0: F2_OK, sigma filled with zeros.
+ *
+ * f2_eval_shaped_noise_sweep: f2_eval_noise_sweep with k_noise_levels replaced by f2_shaped_noise_levels' kernel. Only the
+ * clean samples and the taps go up; the levels are evaluated as ONE (K+1)*B-utterance float64 batch; one wait at the end. Every
+ * output is optional.
+ *   noisy_or_null   (K+1) * offsets[B] float64, level-major, in mem_space. Bit for bit f2_shaped_noise_levels.
+ *   scores_or_null, labels_or_null, window_offsets_or_null (host, (K+1)*B + 1)
+ *           bit for bit what f2_eval_batch_strided(F2_WAVE_F64) returns for the (K+1)*B batch `noisy` with the tiled offsets and
+ *           the same coefs ... hop: it is that call's code on that buffer. window_offsets is filled whenever the arguments pass.
+ *   sigma_or_null, stats_or_null   as in f2_eval_noise_sweep, the tally by the same kernel.
+ * Errors, all before anything is launched or written, in the sweeps' order: everything f2_eval_batch_strided rejects, by the same
+ * checks; hop < 1; then what f2_shaped_noise_levels rejects of K, snr_db, fir and fir_offsets, with the same status.
+ * F2_ERR_NONPOSITIVE as in the strided call. B == 0, or no utterance long enough for a window: F2_OK with window_offsets / sigma /
+ * stats filled as f2_eval_noise_sweep fills them. The call waits for the stream before it returns, whatever mem_space is.
+ */
+int f2_shaped_noise_levels(f2_ctx* ctx, const void* wave, int wave_dtype, const int64_t* offsets /* host, B+1 */, int B,
+                           const double* snr_db /* host, K */, const double* fir /* host, fir_offsets[K] taps */,
+                           const int64_t* fir_offsets /* host, K+1 */, int K, uint64_t seed,
+                           double* noisy /* (K+1) * offsets[B], level-major, mem_space */,
+                           double* sigma_or_null /* host, (K+1)*B */, int mem_space);
+int f2_eval_shaped_noise_sweep(f2_ctx* ctx, const f2_cnn* cnn, const void* wave, int wave_dtype, const int64_t* offsets,
+                               const double* coefs, int B, int C, int lpf, double cutoff_hz, int fft_precision, int radius,
+                               int step, int hop, const double* snr_db /* host, K */,
+                               const double* fir /* host, fir_offsets[K] taps */, const int64_t* fir_offsets /* host, K+1 */,
+                               int K, uint64_t seed, double* noisy_or_null /* (K+1) * offsets[B], mem_space */,
+                               float* scores_or_null, uint8_t* labels_or_null,
+                               int64_t* window_offsets_or_null /* host, (K+1)*B + 1 */, double* sigma_or_null /* host, (K+1)*B */,
+                               int64_t* stats_or_null /* host, (K+1)*B*2 */, int mem_space);
+
 #ifdef __cplusplus
 }
 #endif
