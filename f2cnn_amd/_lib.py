@@ -691,11 +691,7 @@ class Context:
         origin + j * hop; spans (U, 2): the sample span [s_u, e_u) its columns divide. `track` (U, width, 5) float64 - rows,
         rising rows, mean / min / max of scores[:, 1] per column. scores / labels / track: numpy arrays or device pointers, by
         mem_space. Returns `track`."""
-        window_offsets = np.ascontiguousarray(window_offsets, dtype=np.int64)
-        U = len(window_offsets) - 1
-        spans = np.ascontiguousarray(spans, dtype=np.int64)
-        if spans.size != 2 * U:
-            raise ValueError("spans must hold (s_u, e_u) for each of the U utterances")
+        window_offsets, spans, U = _track_args(window_offsets, spans)
         if isinstance(scores, np.ndarray):
             scores = np.ascontiguousarray(scores, dtype=np.float32)
         if isinstance(labels, np.ndarray):
@@ -707,19 +703,25 @@ class Context:
                                            int(hop), int(width), _ptr(track), mem_space))
         return track
 
+    def _figure_call(self, fn, handle, wave, wave_dtype, offsets, coefs, B, Cn, lpf, cutoff, precision, radius, step, hop, own, spans,
+                     width, pool, levels, range_out, reduced, scores, labels, mem_space):
+        """The three fused figure calls: `own` - the call's arguments between hop and spans, as they go down; `reduced` - its
+        outputs between the range and the scores. Returns (window_offsets (B + 1, int64), range (B, 2) float64)."""
+        offsets, spans, range_out = self._picture_args(offsets, B, spans, range_out)
+        window_offsets = np.zeros(max(int(B), 0) + 1, np.int64)
+        self.check(fn(self.handle, handle, _ptr(wave), wave_dtype, _ptr(offsets), _ptr(coefs), int(B), Cn, int(bool(lpf)), float(cutoff),
+                      precision, radius, step, int(hop), *own, _ptr(spans), int(width), int(pool), _ptr(levels), _ptr(range_out),
+                      *[_ptr(a) for a in reduced], _ptr(scores), _ptr(labels), _ptr(window_offsets), mem_space))
+        return window_offsets, range_out.reshape(-1, 2)
+
     def eval_figure_batch(self, handle, wave, wave_dtype, offsets, coefs, B, Cn, lpf, cutoff, precision, radius, step, hop, spans,
                           width, pool, levels, track, scores, labels, mem_space, range_out=None):
         """eval_batch_strided, the picture of the envelopes it uses and the track of its decisions in one device pass (see
         f2_eval_figure_batch). levels (B, Cn, width) uint8, track (B, width, 5) float64, scores, labels: numpy arrays or device
         pointers, by mem_space, any may be None; spans as in envelope_picture. Returns (window_offsets (B + 1, int64), range
         (B, 2) float64)."""
-        offsets, spans, range_out = self._picture_args(offsets, B, spans, range_out)
-        window_offsets = np.zeros(max(int(B), 0) + 1, np.int64)
-        self.check(self.lib.f2_eval_figure_batch(self.handle, handle, _ptr(wave), wave_dtype, _ptr(offsets), _ptr(coefs), int(B), Cn,
-                                                 int(bool(lpf)), float(cutoff), precision, radius, step, int(hop), _ptr(spans),
-                                                 int(width), int(pool), _ptr(levels), _ptr(range_out), _ptr(track), _ptr(scores),
-                                                 _ptr(labels), _ptr(window_offsets), mem_space))
-        return window_offsets, range_out.reshape(-1, 2)
+        return self._figure_call(self.lib.f2_eval_figure_batch, handle, wave, wave_dtype, offsets, coefs, B, Cn, lpf, cutoff, precision,
+                                 radius, step, hop, (), spans, width, pool, levels, range_out, (track,), scores, labels, mem_space)
 
     @staticmethod
     def _patch_args(patches, fill):
@@ -741,11 +743,7 @@ class Context:
         utterance and patch (see f2_occlusion_map; rows, spans and columns as in score_track). `map_out` (U, K, width, 4) float64 -
         rows, flipped rows, mean and mean absolute change of scores[:, k + 1, 1] against scores[:, 0, 1]. scores / labels /
         map_out: numpy arrays or device pointers, by mem_space. Returns `map_out`."""
-        window_offsets = np.ascontiguousarray(window_offsets, dtype=np.int64)
-        U = len(window_offsets) - 1
-        spans = np.ascontiguousarray(spans, dtype=np.int64)
-        if spans.size != 2 * U:
-            raise ValueError("spans must hold (s_u, e_u) for each of the U utterances")
+        window_offsets, spans, U = _track_args(window_offsets, spans)
         if isinstance(scores, np.ndarray):
             scores = np.ascontiguousarray(scores, dtype=np.float32)
         if isinstance(labels, np.ndarray):
@@ -763,15 +761,10 @@ class Context:
         f2_eval_occlusion_batch). levels (B, Cn, width) uint8, map_out (B, K, width, 4) and summary (B, K, 4) float64, scores
         (n, K + 1, 2) float32, labels (n, K + 1) uint8: numpy arrays or device pointers, by mem_space, any may be None; n counts
         the windows of eval_batch_strided. Returns (window_offsets (B + 1, int64), range (B, 2) float64)."""
-        offsets, spans, range_out = self._picture_args(offsets, B, spans, range_out)
         patches, K, fill = self._patch_args(patches, fill)
-        window_offsets = np.zeros(max(int(B), 0) + 1, np.int64)
-        self.check(self.lib.f2_eval_occlusion_batch(self.handle, handle, _ptr(wave), wave_dtype, _ptr(offsets), _ptr(coefs), int(B), Cn,
-                                                    int(bool(lpf)), float(cutoff), precision, radius, step, int(hop),
-                                                    _ptr(patches) if K else None, K, fill, _ptr(spans), int(width), int(pool),
-                                                    _ptr(levels), _ptr(range_out), _ptr(map_out), _ptr(summary), _ptr(scores),
-                                                    _ptr(labels), _ptr(window_offsets), mem_space))
-        return window_offsets, range_out.reshape(-1, 2)
+        return self._figure_call(self.lib.f2_eval_occlusion_batch, handle, wave, wave_dtype, offsets, coefs, B, Cn, lpf, cutoff, precision,
+                                 radius, step, hop, (_ptr(patches) if K else None, K, fill), spans, width, pool, levels, range_out,
+                                 (map_out, summary), scores, labels, mem_space)
 
     def cnn_input_gradient(self, handle, x, n, grad, profile, scores, mem_space):
         """G = dP(rising)/dx of n windows (rows, channels) float32 by one backward-data pass on the device (see
@@ -881,11 +874,7 @@ class Context:
         f2_saliency_map; rows, spans and columns as in score_track). `map_out` (U, Cn, width, 3) float64 - rows, mean of
         profile[:, c, 0], mean of profile[:, c, 1]. profile / map_out: numpy arrays or device pointers, by mem_space. Returns
         `map_out`."""
-        window_offsets = np.ascontiguousarray(window_offsets, dtype=np.int64)
-        U = len(window_offsets) - 1
-        spans = np.ascontiguousarray(spans, dtype=np.int64)
-        if spans.size != 2 * U:
-            raise ValueError("spans must hold (s_u, e_u) for each of the U utterances")
+        window_offsets, spans, U = _track_args(window_offsets, spans)
         if isinstance(profile, np.ndarray):
             profile = np.ascontiguousarray(profile, dtype=np.float64)
         if isinstance(map_out, np.ndarray) and (map_out.dtype != np.float64 or map_out.size != 3 * U * max(int(Cn), 0) * int(width)
@@ -901,13 +890,8 @@ class Context:
         place (see f2_eval_saliency_batch). levels (B, Cn, width) uint8, map_out (B, Cn, width, 3) and summary (B, Cn, 3) float64,
         scores (n, 2) float32, labels (n) uint8: numpy arrays or device pointers, by mem_space, any may be None. Returns
         (window_offsets (B + 1, int64), range (B, 2) float64)."""
-        offsets, spans, range_out = self._picture_args(offsets, B, spans, range_out)
-        window_offsets = np.zeros(max(int(B), 0) + 1, np.int64)
-        self.check(self.lib.f2_eval_saliency_batch(self.handle, handle, _ptr(wave), wave_dtype, _ptr(offsets), _ptr(coefs), int(B), Cn,
-                                                   int(bool(lpf)), float(cutoff), precision, radius, step, int(hop), _ptr(spans),
-                                                   int(width), int(pool), _ptr(levels), _ptr(range_out), _ptr(map_out), _ptr(summary),
-                                                   _ptr(scores), _ptr(labels), _ptr(window_offsets), mem_space))
-        return window_offsets, range_out.reshape(-1, 2)
+        return self._figure_call(self.lib.f2_eval_saliency_batch, handle, wave, wave_dtype, offsets, coefs, B, Cn, lpf, cutoff, precision,
+                                 radius, step, hop, (), spans, width, pool, levels, range_out, (map_out, summary), scores, labels, mem_space)
 
     def resample_batch(self, audio, pcm_format, channels, channel, offsets, B, up, down, taps, half_len, out, mem_space):
         """Ragged batch of interleaved PCM frames (offsets in frames) -> mono float64 samples in int16 units at up / down times
@@ -924,6 +908,16 @@ class Context:
                                               int(B), int(up), int(down), _ptr(taps), int(half_len), _ptr(out), _ptr(out_offsets),
                                               mem_space))
         return out_offsets
+
+
+def _track_args(window_offsets, spans):
+    """window offsets and spans of score_track, occlusion_map and saliency_map as they go down, and U"""
+    window_offsets = np.ascontiguousarray(window_offsets, dtype=np.int64)
+    U = len(window_offsets) - 1
+    spans = np.ascontiguousarray(spans, dtype=np.int64)
+    if spans.size != 2 * U:
+        raise ValueError("spans must hold (s_u, e_u) for each of the U utterances")
+    return window_offsets, spans, U
 
 
 def _sweep_outputs(U, window_offsets, stats, sigma=None, with_sigma=False):

@@ -1230,38 +1230,46 @@ int f2_gammatonegram_batch(f2_ctx* ctx, const void* wave, int wave_dtype, const 
 
 }  // extern "C"
 
-// ---- `cnn eval --figure`: f2_score_track, and f2_eval_figure_batch = strided evaluation + picture + track over one set of envelopes ----
+// ---- `cnn eval --figure`, `--occlusion`, `--saliency`: the reductions f2_score_track, f2_occlusion_map and f2_saliency_map share their
+// argument checks and their records; the fused calls f2_eval_figure_batch, f2_eval_occlusion_batch and f2_eval_saliency_batch are one
+// body (figure_call) = strided evaluation + picture + reductions over one set of envelopes ----
 namespace {
 
-// the records of k_score_track (f2_internal.h) for U utterances with the spans given; returns the workgroups every utterance gets
-int64_t track_records(const int64_t* window_offsets, int U, const int64_t* spans, int hop, int width, std::vector<int64_t>* rec) {
-    rec->resize(5 * (size_t)U);
+// The records of k_score_track (f2_internal.h) of one reduction: made for U utterances with the spans given and named among the
+// call's small arrays (add; `blocks`: the workgroups every utterance gets), uploaded right before the launch (upload)
+struct track_meta {
+    std::vector<int64_t> rec;
+    int64_t* d_rec = nullptr;
     int64_t blocks = 0;
-    for (int u = 0; u < U; ++u) {
-        const int64_t s = spans[2 * u], m = spans[2 * u + 1] - s;
-        const int lg = f2_track_lanes_log2(m, width, hop);
-        int64_t* r = &(*rec)[5 * (size_t)u];
-        r[0] = window_offsets[u], r[1] = window_offsets[u + 1] - window_offsets[u], r[2] = s, r[3] = m, r[4] = lg;
-        blocks = std::max(blocks, f2_track_blocks(width, lg));
+    void add(f2_meta_carve* carve, const int64_t* window_offsets, int U, const int64_t* spans, int hop, int width) {
+        rec.resize(5 * (size_t)U);
+        for (int u = 0; u < U; ++u) {
+            const int64_t s = spans[2 * u], m = spans[2 * u + 1] - s;
+            const int lg = f2_track_lanes_log2(m, width, hop);
+            int64_t* r = &rec[5 * (size_t)u];
+            r[0] = window_offsets[u], r[1] = window_offsets[u + 1] - window_offsets[u], r[2] = s, r[3] = m, r[4] = lg;
+            blocks = std::max(blocks, f2_track_blocks(width, lg));
+        }
+        carve->add(&d_rec, rec.size());
     }
-    return blocks;
-}
+    int upload(f2_ctx* ctx) const { return f2_upload_async(ctx, d_rec, rec.data(), sizeof(int64_t) * rec.size()); }
+};
 
-}  // namespace
-
-extern "C" {
-
-int f2_score_track(f2_ctx* ctx, const float* scores, const uint8_t* labels, const int64_t* window_offsets, int U, const int64_t* spans,
-                   int64_t origin, int hop, int width, double* track, int mem_space) {
+// The argument errors of the three reductions, in their order; nothing is launched or written before they pass. Of the call: own()
+// - the checks of its own size argument; have_data - its input pointers are there (asked for once there is a row) - and what to say
+// when they or `out` are not.
+template <class Own>
+int reduction_check(f2_ctx* ctx, int U, int hop, int64_t origin, int width, const int64_t* window_offsets, const int64_t* spans,
+                    int mem_space, Own own, bool have_data, const char* no_data, const void* out, const char* no_out) {
     F2_TRY(f2_check_ctx(ctx));
     F2_TRY(f2_check_mem_space(ctx, mem_space, false));
     F2_CHECK(ctx, U >= 0 && hop >= 1 && origin >= 0 && width >= 1, F2_ERR_INVALID,
              "U (%d) and origin (%lld) must be at least 0, hop (%d) and width (%d) at least 1", U, (long long)origin, hop, width);
+    F2_TRY(own());
     F2_TRY(f2_check_offsets(ctx, window_offsets, U, "window_offsets"));
     F2_CHECK(ctx, spans, F2_ERR_INVALID, "spans is NULL");
-    const int64_t n_rows = window_offsets[U];
-    F2_CHECK(ctx, (scores && labels) || n_rows == 0, F2_ERR_INVALID, "null scores or labels");
-    F2_CHECK(ctx, track || U == 0, F2_ERR_INVALID, "track is NULL");
+    F2_CHECK(ctx, have_data || window_offsets[U] == 0, F2_ERR_INVALID, "%s", no_data);
+    F2_CHECK(ctx, out || U == 0, F2_ERR_INVALID, "%s", no_out);
     int64_t max_rows = 0;
     for (int u = 0; u < U; ++u) {
         F2_CHECK(ctx, spans[2 * u] >= 0 && spans[2 * u + 1] >= spans[2 * u], F2_ERR_INVALID, "utterance %d: [%lld, %lld) is not a span", u,
@@ -1272,61 +1280,65 @@ int f2_score_track(f2_ctx* ctx, const float* scores, const uint8_t* labels, cons
     int64_t t_last = 0;   // the sample of the last row of the longest utterance has to be an int64
     F2_CHECK(ctx, max_rows == 0 || (!__builtin_mul_overflow(max_rows - 1, (int64_t)hop, &t_last) && !__builtin_add_overflow(t_last, origin, &t_last)),
              F2_ERR_UNSUPPORTED, "row %lld at hop %d from origin %lld is beyond int64", (long long)(max_rows - 1), hop, (long long)origin);
-    if (U == 0) return F2_OK;
-
-    std::vector<int64_t> rec;
-    const int64_t blocks = track_records(window_offsets, U, spans, hop, width, &rec);
-    int64_t* d_rec;
-    f2_meta_carve meta;
-    meta.add(&d_rec, rec.size());
-    F2_TRY(meta.reserve(ctx));
-    const void *d_scores, *d_labels;
-    F2_TRY(f2_stage_input(ctx, scores, sizeof(float) * 2 * (size_t)n_rows, mem_space, &d_scores));
-    F2_TRY(f2_stage_into(ctx, ctx->stage_aux, labels, (size_t)n_rows, mem_space, &d_labels));
-    f2_output out;
-    F2_TRY(f2_place(ctx, ctx->stage_out, track, sizeof(double) * 5 * (size_t)U * (size_t)width, mem_space, false, &out));
-    F2_TRY(f2_upload_async(ctx, d_rec, rec.data(), sizeof(int64_t) * rec.size()));
-    F2_TRY(f2_launch_score_track(ctx, (const float*)d_scores, (const uint8_t*)d_labels, d_rec, U, origin, hop, width, blocks, out.as<double>()));
-    F2_TRY(f2_copy_back(ctx, out));
-    return f2_host_wait(ctx, mem_space);
+    return F2_OK;
 }
 
-// The envelopes are made once (eval_envelopes) and stay in ctx->stage_out for the picture and the window loop. Order on the stream:
-// envelopes, picture (pooled values in ctx->work, a host caller's levels in ctx->work2, both copied out before anything else is
-// queued), window loop (which takes ctx->work as the convolution workspace and ctx->work2 for its window lists: behind the picture's
-// last reader on the stream, and f2_reserve waits for the stream before it moves a block), track. One carve of ctx->meta for all.
-int f2_eval_figure_batch(f2_ctx* ctx, const f2_cnn* cnn, const void* wave, int wave_dtype, const int64_t* offsets, const double* coefs,
-                         int B, int C, int lpf, double cutoff_hz, int fft_precision, int radius, int step, int hop,
-                         const int64_t* spans_or_null, int width, int pool, uint8_t* levels_or_null, double* range_or_null,
-                         double* track_or_null, float* scores_or_null, uint8_t* labels_or_null, int64_t* window_offsets_or_null,
-                         int mem_space) {
-    const f2_batch X = {wave, wave_dtype, offsets, coefs, B, C, lpf, cutoff_hz, fft_precision, mem_space};
+// One output a fused call reduces its windows to: over the caller's spans in `width` columns (the track, a map), or - summary - over
+// the whole utterances [0, n_b) in one column
+struct figure_reduction {
+    double* callers;   // NULL: not asked for (its records are still named)
+    size_t bytes;
+    bool summary;
+};
+
+// The body of the three fused calls. The envelopes are made once (eval_envelopes) and stay in ctx->stage_out for the picture and the
+// window loop. Order on the stream: envelopes, picture (pooled values in ctx->work, a host caller's levels in ctx->work2, both copied
+// out before anything else is queued), window loop (which takes ctx->work as the convolution workspace and ctx->work2 for its window
+// lists: behind the picture's last reader on the stream, and f2_reserve waits for the stream before it moves a block), the reductions
+// in the order of `red`, each with its copy to a host caller, whose outputs lie in that order behind the scores in ctx->stage_aux.
+// One carve of ctx->meta for all. Of the call:
+//   check(R, n_total)   its own argument errors, behind the shared ones (the tables between them cannot fail) and before
+//                       window_offsets_or_null, the first thing written
+//   carve(meta)         names its small arrays behind the picture's and the records
+//   windows(E, nbh, n_total, tail_bytes)   for n_total > 0: its scratch, eval_cnn_begin and strided_window_loop
+//   launch(E, d_rec, width, blocks, out)   the kernel of its reductions (also over no rows, when there is no window)
+template <class Check, class Carve, class Windows, class Launch>
+int figure_call(f2_ctx* ctx, const f2_cnn* cnn, const f2_batch& X, int radius, int step, int hop, const int64_t* spans_or_null, int width,
+                int pool, uint8_t* levels_or_null, double* range_or_null, int64_t* window_offsets_or_null, Check check, Carve carve,
+                Windows windows, const figure_reduction* red, int n_red, Launch launch) {
+    const int64_t* offsets = X.offsets;
+    const int B = X.B, C = X.C, mem_space = X.mem_space;
     eval_call E;
     F2_TRY(eval_check(ctx, cnn, X, radius, step, &E));
     F2_CHECK(ctx, hop >= 1, F2_ERR_INVALID, "hop must be at least 1 sample (got %d)", hop);
     F2_TRY(picture_check(ctx, offsets, B, C, spans_or_null, width, pool, mem_space));
     const int64_t total = X.total();
-    F2_CHECK(ctx, wave || total == 0, F2_ERR_INVALID, "null wave");
-    std::vector<int64_t> nbh((size_t)B), wo((size_t)B + 1, 0), spans(2 * (size_t)B);
+    F2_CHECK(ctx, X.wave || total == 0, F2_ERR_INVALID, "null wave");
+    std::vector<int64_t> nbh((size_t)B), wo((size_t)B + 1, 0), spans(2 * (size_t)B), whole(2 * (size_t)B);
     for (int b = 0; b < B; ++b) {
-        nbh[(size_t)b] = strided_windows(offsets[b + 1] - offsets[b], E.R, step, hop);
+        const int64_t nb = offsets[b + 1] - offsets[b];
+        nbh[(size_t)b] = strided_windows(nb, E.R, step, hop);
         wo[(size_t)b + 1] = wo[(size_t)b] + nbh[(size_t)b];
         spans[2 * (size_t)b] = spans_or_null ? spans_or_null[2 * b] : 0;
-        spans[2 * (size_t)b + 1] = spans_or_null ? spans_or_null[2 * b + 1] : offsets[b + 1] - offsets[b];
+        spans[2 * (size_t)b + 1] = spans_or_null ? spans_or_null[2 * b + 1] : nb;
+        whole[2 * (size_t)b] = 0, whole[2 * (size_t)b + 1] = nb;
     }
     const int64_t n_total = wo[(size_t)B];
+    F2_TRY(check(E.R, n_total));
     if (window_offsets_or_null) memcpy(window_offsets_or_null, wo.data(), sizeof(int64_t) * wo.size());
     if (B == 0) return F2_OK;
 
-    const bool want_picture = levels_or_null || range_or_null, want_track = track_or_null != nullptr;
-    const size_t track_bytes = sizeof(double) * 5 * (size_t)B * (size_t)width;
-    const size_t tail_bytes = want_track && mem_space != F2_MEM_DEVICE ? track_bytes : 0;   // a host caller's track: behind the scores
-    std::vector<int64_t> rec;
-    const int64_t track_blocks = track_records(wo.data(), B, spans.data(), hop, width, &rec);
+    const bool want_picture = levels_or_null || range_or_null, host = mem_space != F2_MEM_DEVICE;
+    size_t tail_bytes = 0;   // a host caller's reductions: behind the scores
     picture_meta P;
-    int64_t* d_rec;
+    track_meta T[2];
     f2_meta_carve meta;
-    P.add(&meta, B), meta.add(&d_rec, rec.size());
+    P.add(&meta, B);
+    for (int i = 0; i < n_red; ++i) {
+        T[i].add(&meta, wo.data(), B, red[i].summary ? whole.data() : spans.data(), hop, red[i].summary ? 1 : width);
+        if (host && red[i].callers) tail_bytes += red[i].bytes;
+    }
+    carve(&meta);
     F2_TRY(meta.reserve(ctx));
     F2_TRY(f2_upload_offsets(ctx, offsets, B));   // (a batch without a sample still gets its pictures)
     if (total > 0) F2_TRY(eval_envelopes(ctx, &E, X, nullptr, n_total));
@@ -1334,21 +1346,21 @@ int f2_eval_figure_batch(f2_ctx* ctx, const f2_cnn* cnn, const void* wave, int w
         F2_TRY(picture_enqueue(ctx, E.d_env, offsets, B, C, spans_or_null, width, pool, &P, nullptr, levels_or_null, range_or_null != nullptr,
                                mem_space));
     if (n_total > 0) {
-        const int64_t chunk = n_total < CNN_CHUNK ? n_total : CNN_CHUNK;
-        F2_TRY(eval_cnn_begin(ctx, cnn, &E, chunk, n_total, C, scores_or_null, labels_or_null, mem_space, want_track, tail_bytes));
-        F2_TRY(strided_window_loop(ctx, cnn, &E, X, nbh, chunk, radius, step, hop, (float*)ctx->xbuf.ptr));
+        F2_TRY(windows(&E, nbh, n_total, tail_bytes));
         F2_TRY(eval_dense_flush(ctx, cnn, &E));
     } else {
         F2_TRY(f2_place_scores(ctx, nullptr, nullptr, 0, mem_space, false, false, tail_bytes, &E.out));
     }
-    if (want_track) {
-        f2_output track;
-        track.dev = tail_bytes ? E.out.tail : (char*)track_or_null, track.host = tail_bytes ? (char*)track_or_null : nullptr;
-        track.bytes = track_bytes, track.callers = !tail_bytes;
-        F2_TRY(f2_upload_async(ctx, d_rec, rec.data(), sizeof(int64_t) * rec.size()));
-        F2_TRY(f2_launch_score_track(ctx, E.out.scores.as<float>(), E.out.labels.as<uint8_t>(), d_rec, B, (int64_t)radius * step, hop, width,
-                                     track_blocks, track.as<double>()));
-        F2_TRY(f2_copy_back(ctx, track));
+    char* tail = E.out.tail;
+    for (int i = 0; i < n_red; ++i) {
+        if (!red[i].callers) continue;
+        f2_output o;
+        o.dev = host ? tail : (char*)red[i].callers, o.host = host ? (char*)red[i].callers : nullptr;
+        o.bytes = red[i].bytes, o.callers = !host;
+        if (host) tail += red[i].bytes;
+        F2_TRY(T[i].upload(ctx));
+        F2_TRY(launch(E, T[i].d_rec, red[i].summary ? 1 : width, T[i].blocks, o.as<double>()));
+        F2_TRY(f2_copy_back(ctx, o));
     }
     int rc = F2_OK;
     if (n_total > 0)
@@ -1357,6 +1369,51 @@ int f2_eval_figure_batch(f2_ctx* ctx, const f2_cnn* cnn, const void* wave, int w
         F2_HIP(ctx, hipStreamSynchronize(ctx->stream));
     if (rc == F2_OK || rc == F2_ERR_NONPOSITIVE) picture_range(P, B, range_or_null);
     return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+int f2_score_track(f2_ctx* ctx, const float* scores, const uint8_t* labels, const int64_t* window_offsets, int U, const int64_t* spans,
+                   int64_t origin, int hop, int width, double* track, int mem_space) {
+    F2_TRY(reduction_check(ctx, U, hop, origin, width, window_offsets, spans, mem_space, [] { return F2_OK; }, scores && labels,
+                           "null scores or labels", track, "track is NULL"));
+    if (U == 0) return F2_OK;
+    const size_t n_rows = (size_t)window_offsets[U];
+    track_meta T;
+    f2_meta_carve meta;
+    T.add(&meta, window_offsets, U, spans, hop, width);
+    F2_TRY(meta.reserve(ctx));
+    const void *d_scores, *d_labels;
+    F2_TRY(f2_stage_input(ctx, scores, sizeof(float) * 2 * n_rows, mem_space, &d_scores));
+    F2_TRY(f2_stage_into(ctx, ctx->stage_aux, labels, n_rows, mem_space, &d_labels));
+    f2_output out;
+    F2_TRY(f2_place(ctx, ctx->stage_out, track, sizeof(double) * 5 * (size_t)U * (size_t)width, mem_space, false, &out));
+    F2_TRY(T.upload(ctx));
+    F2_TRY(f2_launch_score_track(ctx, (const float*)d_scores, (const uint8_t*)d_labels, T.d_rec, U, origin, hop, width, T.blocks, out.as<double>()));
+    F2_TRY(f2_copy_back(ctx, out));
+    return f2_host_wait(ctx, mem_space);
+}
+
+// figure_call with the network's own windows and one reduction, the track
+int f2_eval_figure_batch(f2_ctx* ctx, const f2_cnn* cnn, const void* wave, int wave_dtype, const int64_t* offsets, const double* coefs,
+                         int B, int C, int lpf, double cutoff_hz, int fft_precision, int radius, int step, int hop,
+                         const int64_t* spans_or_null, int width, int pool, uint8_t* levels_or_null, double* range_or_null,
+                         double* track_or_null, float* scores_or_null, uint8_t* labels_or_null, int64_t* window_offsets_or_null,
+                         int mem_space) {
+    const f2_batch X = {wave, wave_dtype, offsets, coefs, B, C, lpf, cutoff_hz, fft_precision, mem_space};
+    auto windows = [&](eval_call* E, const std::vector<int64_t>& nbh, int64_t n_total, size_t tail_bytes) -> int {
+        const int64_t chunk = n_total < CNN_CHUNK ? n_total : CNN_CHUNK;
+        F2_TRY(eval_cnn_begin(ctx, cnn, E, chunk, n_total, C, scores_or_null, labels_or_null, mem_space, track_or_null != nullptr, tail_bytes));
+        return strided_window_loop(ctx, cnn, E, X, nbh, chunk, radius, step, hop, (float*)ctx->xbuf.ptr);
+    };
+    auto launch = [&](const eval_call& E, const int64_t* d_rec, int w, int64_t blocks, double* out) {
+        return f2_launch_score_track(ctx, E.out.scores.as<float>(), E.out.labels.as<uint8_t>(), d_rec, B, (int64_t)radius * step, hop, w, blocks, out);
+    };
+    const figure_reduction track = {track_or_null, sizeof(double) * 5 * (size_t)B * (size_t)width, false};
+    return figure_call(ctx, cnn, X, radius, step, hop, spans_or_null, width, pool, levels_or_null, range_or_null, window_offsets_or_null,
+                       [](int, int64_t) { return F2_OK; }, [](f2_meta_carve*) {}, windows, &track, 1, launch);
 }
 
 }  // extern "C"
@@ -1433,130 +1490,64 @@ int f2_occlude_windows(f2_ctx* ctx, const float* x, int64_t n, int R, int C, con
 
 int f2_occlusion_map(f2_ctx* ctx, const float* scores, const uint8_t* labels, const int64_t* window_offsets, int U, int K,
                      const int64_t* spans, int64_t origin, int hop, int width, double* map, int mem_space) {
-    F2_TRY(f2_check_ctx(ctx));
-    F2_TRY(f2_check_mem_space(ctx, mem_space, false));
-    F2_CHECK(ctx, U >= 0 && hop >= 1 && origin >= 0 && width >= 1, F2_ERR_INVALID,
-             "U (%d) and origin (%lld) must be at least 0, hop (%d) and width (%d) at least 1", U, (long long)origin, hop, width);
-    F2_CHECK(ctx, K >= 1, F2_ERR_INVALID, "K (%d) must be at least 1", K);
-    F2_CHECK(ctx, K <= OCCLUSION_MAX_PATCHES, F2_ERR_UNSUPPORTED, "%d patches (at most %d)", K, OCCLUSION_MAX_PATCHES);
-    F2_TRY(f2_check_offsets(ctx, window_offsets, U, "window_offsets"));
-    F2_CHECK(ctx, spans, F2_ERR_INVALID, "spans is NULL");
-    const int64_t n_rows = window_offsets[U];
-    F2_CHECK(ctx, (scores && labels) || n_rows == 0, F2_ERR_INVALID, "null scores or labels");
-    F2_CHECK(ctx, map || U == 0, F2_ERR_INVALID, "map is NULL");
-    int64_t max_rows = 0;
-    for (int u = 0; u < U; ++u) {
-        F2_CHECK(ctx, spans[2 * u] >= 0 && spans[2 * u + 1] >= spans[2 * u], F2_ERR_INVALID, "utterance %d: [%lld, %lld) is not a span", u,
-                 (long long)spans[2 * u], (long long)spans[2 * u + 1]);
-        max_rows = std::max(max_rows, window_offsets[u + 1] - window_offsets[u]);
-    }
-    F2_CHECK(ctx, width <= PICTURE_MAX_WIDTH, F2_ERR_UNSUPPORTED, "width %d (at most %d columns)", width, PICTURE_MAX_WIDTH);
-    int64_t t_last = 0;   // the sample of the last row of the longest utterance has to be an int64
-    F2_CHECK(ctx, max_rows == 0 || (!__builtin_mul_overflow(max_rows - 1, (int64_t)hop, &t_last) && !__builtin_add_overflow(t_last, origin, &t_last)),
-             F2_ERR_UNSUPPORTED, "row %lld at hop %d from origin %lld is beyond int64", (long long)(max_rows - 1), hop, (long long)origin);
+    auto own = [&]() -> int {
+        F2_CHECK(ctx, K >= 1, F2_ERR_INVALID, "K (%d) must be at least 1", K);
+        F2_CHECK(ctx, K <= OCCLUSION_MAX_PATCHES, F2_ERR_UNSUPPORTED, "%d patches (at most %d)", K, OCCLUSION_MAX_PATCHES);
+        return F2_OK;
+    };
+    F2_TRY(reduction_check(ctx, U, hop, origin, width, window_offsets, spans, mem_space, own, scores && labels, "null scores or labels", map,
+                           "map is NULL"));
     if (U == 0) return F2_OK;
-
-    const size_t L = (size_t)K + 1;
-    std::vector<int64_t> rec;
-    const int64_t blocks = track_records(window_offsets, U, spans, hop, width, &rec);
-    int64_t* d_rec;
+    const size_t level_rows = ((size_t)K + 1) * (size_t)window_offsets[U];
+    track_meta T;
     f2_meta_carve meta;
-    meta.add(&d_rec, rec.size());
+    T.add(&meta, window_offsets, U, spans, hop, width);
     F2_TRY(meta.reserve(ctx));
     const void *d_scores, *d_labels;
-    F2_TRY(f2_stage_input(ctx, scores, sizeof(float) * 2 * L * (size_t)n_rows, mem_space, &d_scores));
-    F2_TRY(f2_stage_into(ctx, ctx->stage_aux, labels, L * (size_t)n_rows, mem_space, &d_labels));
+    F2_TRY(f2_stage_input(ctx, scores, sizeof(float) * 2 * level_rows, mem_space, &d_scores));
+    F2_TRY(f2_stage_into(ctx, ctx->stage_aux, labels, level_rows, mem_space, &d_labels));
     f2_output out;
     F2_TRY(f2_place(ctx, ctx->stage_out, map, sizeof(double) * 4 * (size_t)U * (size_t)K * (size_t)width, mem_space, false, &out));
-    F2_TRY(f2_upload_async(ctx, d_rec, rec.data(), sizeof(int64_t) * rec.size()));
-    F2_TRY(f2_launch_occlusion_map(ctx, (const float*)d_scores, (const uint8_t*)d_labels, d_rec, U, K, origin, hop, width, blocks, out.as<double>()));
+    F2_TRY(T.upload(ctx));
+    F2_TRY(f2_launch_occlusion_map(ctx, (const float*)d_scores, (const uint8_t*)d_labels, T.d_rec, U, K, origin, hop, width, T.blocks, out.as<double>()));
     F2_TRY(f2_copy_back(ctx, out));
     return f2_host_wait(ctx, mem_space);
 }
 
-// f2_eval_figure_batch's order on the stream, with two changes: the window stage writes a chunk of m = chunk / (K + 1) windows to
-// ctx->occ_src and k_occlude_windows expands them into ctx->xbuf, window-major, so that the convolutions and the dense groups see
-// m (K + 1) windows and write contiguous score rows; the map (the caller's spans and width) and the summary (spans [0, n_b), one
-// column) take the track's place, a host caller's behind the scores in ctx->stage_aux.
+// figure_call with two changes: the window stage writes a chunk of m = chunk / (K + 1) windows to ctx->occ_src and k_occlude_windows
+// expands them into ctx->xbuf, window-major, so that the convolutions and the dense groups see m (K + 1) windows and write contiguous
+// score rows; the map and the summary take the track's place.
 int f2_eval_occlusion_batch(f2_ctx* ctx, const f2_cnn* cnn, const void* wave, int wave_dtype, const int64_t* offsets, const double* coefs,
                             int B, int C, int lpf, double cutoff_hz, int fft_precision, int radius, int step, int hop,
                             const int32_t* patches, int K, float fill, const int64_t* spans_or_null, int width, int pool,
                             uint8_t* levels_or_null, double* range_or_null, double* map_or_null, double* summary_or_null,
                             float* scores_or_null, uint8_t* labels_or_null, int64_t* window_offsets_or_null, int mem_space) {
     const f2_batch X = {wave, wave_dtype, offsets, coefs, B, C, lpf, cutoff_hz, fft_precision, mem_space};
-    eval_call E;
-    F2_TRY(eval_check(ctx, cnn, X, radius, step, &E));
-    F2_CHECK(ctx, hop >= 1, F2_ERR_INVALID, "hop must be at least 1 sample (got %d)", hop);
-    F2_TRY(picture_check(ctx, offsets, B, C, spans_or_null, width, pool, mem_space));
-    const int64_t total = X.total();
-    F2_CHECK(ctx, wave || total == 0, F2_ERR_INVALID, "null wave");
-    F2_CHECK(ctx, fill >= 0.f && fill <= 1.f, F2_ERR_INVALID, "fill (%g) must lie in [0, 1], the range of a normalised window", (double)fill);
-    std::vector<int64_t> nbh((size_t)B), wo((size_t)B + 1, 0), spans(2 * (size_t)B), whole(2 * (size_t)B);
-    for (int b = 0; b < B; ++b) {
-        const int64_t nb = offsets[b + 1] - offsets[b];
-        nbh[(size_t)b] = strided_windows(nb, E.R, step, hop);
-        wo[(size_t)b + 1] = wo[(size_t)b] + nbh[(size_t)b];
-        spans[2 * (size_t)b] = spans_or_null ? spans_or_null[2 * b] : 0;
-        spans[2 * (size_t)b + 1] = spans_or_null ? spans_or_null[2 * b + 1] : nb;
-        whole[2 * (size_t)b] = 0, whole[2 * (size_t)b + 1] = nb;
-    }
-    const int64_t n_total = wo[(size_t)B];
-    F2_TRY(occlusion_check(ctx, patches, K, 1, E.R, C, n_total));
-    if (window_offsets_or_null) memcpy(window_offsets_or_null, wo.data(), sizeof(int64_t) * wo.size());
-    if (B == 0) return F2_OK;
-
     const int64_t L = (int64_t)K + 1;
-    const bool want_picture = levels_or_null || range_or_null, want_map = map_or_null != nullptr, want_summary = summary_or_null != nullptr;
-    const bool host = mem_space != F2_MEM_DEVICE;
-    const size_t map_bytes = sizeof(double) * 4 * (size_t)B * (size_t)K * (size_t)width, summary_bytes = sizeof(double) * 4 * (size_t)B * (size_t)K;
-    const size_t tail_bytes = host ? (want_map ? map_bytes : 0) + (want_summary ? summary_bytes : 0) : 0;   // a host caller's: behind the scores
-    std::vector<int64_t> rec, rec1, words;
-    const int64_t map_blocks = track_records(wo.data(), B, spans.data(), hop, width, &rec);
-    const int64_t summary_blocks = track_records(wo.data(), B, whole.data(), hop, 1, &rec1);
-    occlusion_patch_words(patches, K, &words);
-    picture_meta P;
-    int64_t *d_rec, *d_rec1, *d_words;
-    f2_meta_carve meta;
-    P.add(&meta, B), meta.add(&d_rec, rec.size()), meta.add(&d_rec1, rec1.size()), meta.add(&d_words, words.size());
-    F2_TRY(meta.reserve(ctx));
-    F2_TRY(f2_upload_offsets(ctx, offsets, B));   // (a batch without a sample still gets its pictures)
-    if (total > 0) F2_TRY(eval_envelopes(ctx, &E, X, nullptr, n_total));
-    if (want_picture)
-        F2_TRY(picture_enqueue(ctx, E.d_env, offsets, B, C, spans_or_null, width, pool, &P, nullptr, levels_or_null, range_or_null != nullptr,
-                               mem_space));
-    if (n_total > 0) {
+    std::vector<int64_t> words;
+    int64_t* d_words = nullptr;
+    auto check = [&](int R, int64_t n_total) -> int {
+        F2_CHECK(ctx, fill >= 0.f && fill <= 1.f, F2_ERR_INVALID, "fill (%g) must lie in [0, 1], the range of a normalised window", (double)fill);
+        return occlusion_check(ctx, patches, K, 1, R, C, n_total);
+    };
+    auto windows = [&](eval_call* E, const std::vector<int64_t>& nbh, int64_t n_total, size_t tail_bytes) -> int {
         const int64_t per = CNN_CHUNK / L > 0 ? CNN_CHUNK / L : 1;   // source windows of a chunk
         const int64_t chunk = n_total < per ? n_total : per;
-        F2_TRY(f2_reserve(ctx, ctx->occ_src, sizeof(float) * (size_t)chunk * E.R * (size_t)C));
-        F2_TRY(eval_cnn_begin(ctx, cnn, &E, chunk * L, n_total * L, C, scores_or_null, labels_or_null, mem_space, want_map || want_summary,
+        F2_TRY(f2_reserve(ctx, ctx->occ_src, sizeof(float) * (size_t)chunk * E->R * (size_t)C));
+        F2_TRY(eval_cnn_begin(ctx, cnn, E, chunk * L, n_total * L, C, scores_or_null, labels_or_null, mem_space, map_or_null || summary_or_null,
                               tail_bytes));
         F2_TRY(f2_upload_async(ctx, d_words, words.data(), sizeof(int64_t) * words.size()));
         const occlusion_stage occ = {(const int32_t*)d_words, K, fill};
-        F2_TRY(strided_window_loop(ctx, cnn, &E, X, nbh, chunk, radius, step, hop, (float*)ctx->occ_src.ptr, &occ));
-        F2_TRY(eval_dense_flush(ctx, cnn, &E));
-    } else {
-        F2_TRY(f2_place_scores(ctx, nullptr, nullptr, 0, mem_space, false, false, tail_bytes, &E.out));
-    }
-    char* tail = E.out.tail;
-    auto reduce = [&](double* callers, size_t bytes, const std::vector<int64_t>& r, int64_t* d_r, int64_t blocks, int w) -> int {
-        f2_output o;
-        o.dev = host ? tail : (char*)callers, o.host = host ? (char*)callers : nullptr;
-        o.bytes = bytes, o.callers = !host;
-        if (host) tail += bytes;
-        F2_TRY(f2_upload_async(ctx, d_r, r.data(), sizeof(int64_t) * r.size()));
-        F2_TRY(f2_launch_occlusion_map(ctx, E.out.scores.as<float>(), E.out.labels.as<uint8_t>(), d_r, B, K, (int64_t)radius * step, hop, w,
-                                       blocks, o.as<double>()));
-        return f2_copy_back(ctx, o);
+        return strided_window_loop(ctx, cnn, E, X, nbh, chunk, radius, step, hop, (float*)ctx->occ_src.ptr, &occ);
     };
-    if (want_map) F2_TRY(reduce(map_or_null, map_bytes, rec, d_rec, map_blocks, width));
-    if (want_summary) F2_TRY(reduce(summary_or_null, summary_bytes, rec1, d_rec1, summary_blocks, 1));
-    int rc = F2_OK;
-    if (n_total > 0)
-        rc = eval_cnn_end(ctx, cnn, &E);   // (waits for the stream)
-    else
-        F2_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (rc == F2_OK || rc == F2_ERR_NONPOSITIVE) picture_range(P, B, range_or_null);
-    return rc;
+    auto launch = [&](const eval_call& E, const int64_t* d_rec, int w, int64_t blocks, double* out) {
+        return f2_launch_occlusion_map(ctx, E.out.scores.as<float>(), E.out.labels.as<uint8_t>(), d_rec, B, K, (int64_t)radius * step, hop, w, blocks, out);
+    };
+    const size_t summary_bytes = sizeof(double) * 4 * (size_t)B * (size_t)K;
+    const figure_reduction red[2] = {{map_or_null, summary_bytes * (size_t)width, false}, {summary_or_null, summary_bytes, true}};
+    auto carve = [&](f2_meta_carve* meta) { occlusion_patch_words(patches, K, &words), meta->add(&d_words, words.size()); };
+    return figure_call(ctx, cnn, X, radius, step, hop, spans_or_null, width, pool, levels_or_null, range_or_null, window_offsets_or_null, check,
+                       carve, windows, red, 2, launch);
 }
 
 }  // extern "C"
@@ -1567,122 +1558,56 @@ extern "C" {
 
 int f2_saliency_map(f2_ctx* ctx, const double* profile, const int64_t* window_offsets, int U, int C, const int64_t* spans, int64_t origin,
                     int hop, int width, double* map, int mem_space) {
-    F2_TRY(f2_check_ctx(ctx));
-    F2_TRY(f2_check_mem_space(ctx, mem_space, false));
-    F2_CHECK(ctx, U >= 0 && hop >= 1 && origin >= 0 && width >= 1, F2_ERR_INVALID,
-             "U (%d) and origin (%lld) must be at least 0, hop (%d) and width (%d) at least 1", U, (long long)origin, hop, width);
-    F2_CHECK(ctx, C >= 1, F2_ERR_INVALID, "C (%d) must be at least 1", C);
-    F2_CHECK(ctx, C <= 65535, F2_ERR_UNSUPPORTED, "%d channels (at most 65535)", C);
-    F2_TRY(f2_check_offsets(ctx, window_offsets, U, "window_offsets"));
-    F2_CHECK(ctx, spans, F2_ERR_INVALID, "spans is NULL");
-    const int64_t n_rows = window_offsets[U];
-    F2_CHECK(ctx, profile || n_rows == 0, F2_ERR_INVALID, "profile is NULL");
-    F2_CHECK(ctx, map || U == 0, F2_ERR_INVALID, "map is NULL");
-    int64_t max_rows = 0;
-    for (int u = 0; u < U; ++u) {
-        F2_CHECK(ctx, spans[2 * u] >= 0 && spans[2 * u + 1] >= spans[2 * u], F2_ERR_INVALID, "utterance %d: [%lld, %lld) is not a span", u,
-                 (long long)spans[2 * u], (long long)spans[2 * u + 1]);
-        max_rows = std::max(max_rows, window_offsets[u + 1] - window_offsets[u]);
-    }
-    F2_CHECK(ctx, width <= PICTURE_MAX_WIDTH, F2_ERR_UNSUPPORTED, "width %d (at most %d columns)", width, PICTURE_MAX_WIDTH);
-    int64_t t_last = 0;   // the sample of the last row of the longest utterance has to be an int64
-    F2_CHECK(ctx, max_rows == 0 || (!__builtin_mul_overflow(max_rows - 1, (int64_t)hop, &t_last) && !__builtin_add_overflow(t_last, origin, &t_last)),
-             F2_ERR_UNSUPPORTED, "row %lld at hop %d from origin %lld is beyond int64", (long long)(max_rows - 1), hop, (long long)origin);
+    auto own = [&]() -> int {
+        F2_CHECK(ctx, C >= 1, F2_ERR_INVALID, "C (%d) must be at least 1", C);
+        F2_CHECK(ctx, C <= 65535, F2_ERR_UNSUPPORTED, "%d channels (at most 65535)", C);
+        return F2_OK;
+    };
+    F2_TRY(reduction_check(ctx, U, hop, origin, width, window_offsets, spans, mem_space, own, profile != nullptr, "profile is NULL", map,
+                           "map is NULL"));
     if (U == 0) return F2_OK;
-
-    std::vector<int64_t> rec;
-    const int64_t blocks = track_records(window_offsets, U, spans, hop, width, &rec);
-    int64_t* d_rec;
+    track_meta T;
     f2_meta_carve meta;
-    meta.add(&d_rec, rec.size());
+    T.add(&meta, window_offsets, U, spans, hop, width);
     F2_TRY(meta.reserve(ctx));
     const void* d_profile;
-    F2_TRY(f2_stage_input(ctx, profile, sizeof(double) * 2 * (size_t)C * (size_t)n_rows, mem_space, &d_profile));
+    F2_TRY(f2_stage_input(ctx, profile, sizeof(double) * 2 * (size_t)C * (size_t)window_offsets[U], mem_space, &d_profile));
     f2_output out;
     F2_TRY(f2_place(ctx, ctx->stage_out, map, sizeof(double) * 3 * (size_t)U * (size_t)C * (size_t)width, mem_space, false, &out));
-    F2_TRY(f2_upload_async(ctx, d_rec, rec.data(), sizeof(int64_t) * rec.size()));
-    F2_TRY(f2_launch_saliency_map(ctx, (const double*)d_profile, d_rec, U, C, origin, hop, width, blocks, out.as<double>()));
+    F2_TRY(T.upload(ctx));
+    F2_TRY(f2_launch_saliency_map(ctx, (const double*)d_profile, T.d_rec, U, C, origin, hop, width, T.blocks, out.as<double>()));
     F2_TRY(f2_copy_back(ctx, out));
     return f2_host_wait(ctx, mem_space);
 }
 
-// f2_eval_figure_batch's order on the stream, with two changes: after the normal route's convolutions a chunk's windows (still in
-// ctx->xbuf) go through f2_launch_cnn_input_gradient, which keeps 16 C bytes of profile per window in ctx->sal_profile; the map (the
-// caller's spans and width) and the summary (spans [0, n_b), one column) take the track's place, a host caller's behind the scores
-// in ctx->stage_aux.
+// figure_call with two changes: after the normal route's convolutions a chunk's windows (still in ctx->xbuf) go through
+// f2_launch_cnn_input_gradient, which keeps 16 C bytes of profile per window in ctx->sal_profile; the map and the summary, reduced
+// from those rows, take the track's place.
 int f2_eval_saliency_batch(f2_ctx* ctx, const f2_cnn* cnn, const void* wave, int wave_dtype, const int64_t* offsets, const double* coefs,
                            int B, int C, int lpf, double cutoff_hz, int fft_precision, int radius, int step, int hop,
                            const int64_t* spans_or_null, int width, int pool, uint8_t* levels_or_null, double* range_or_null,
                            double* map_or_null, double* summary_or_null, float* scores_or_null, uint8_t* labels_or_null,
                            int64_t* window_offsets_or_null, int mem_space) {
     const f2_batch X = {wave, wave_dtype, offsets, coefs, B, C, lpf, cutoff_hz, fft_precision, mem_space};
-    eval_call E;
-    F2_TRY(eval_check(ctx, cnn, X, radius, step, &E));
-    F2_CHECK(ctx, hop >= 1, F2_ERR_INVALID, "hop must be at least 1 sample (got %d)", hop);
-    F2_TRY(picture_check(ctx, offsets, B, C, spans_or_null, width, pool, mem_space));
-    const int64_t total = X.total();
-    F2_CHECK(ctx, wave || total == 0, F2_ERR_INVALID, "null wave");
-    F2_CHECK(ctx, C <= 65535, F2_ERR_UNSUPPORTED, "%d channels (at most 65535)", C);
-    std::vector<int64_t> nbh((size_t)B), wo((size_t)B + 1, 0), spans(2 * (size_t)B), whole(2 * (size_t)B);
-    for (int b = 0; b < B; ++b) {
-        const int64_t nb = offsets[b + 1] - offsets[b];
-        nbh[(size_t)b] = strided_windows(nb, E.R, step, hop);
-        wo[(size_t)b + 1] = wo[(size_t)b] + nbh[(size_t)b];
-        spans[2 * (size_t)b] = spans_or_null ? spans_or_null[2 * b] : 0;
-        spans[2 * (size_t)b + 1] = spans_or_null ? spans_or_null[2 * b + 1] : nb;
-        whole[2 * (size_t)b] = 0, whole[2 * (size_t)b + 1] = nb;
-    }
-    const int64_t n_total = wo[(size_t)B];
-    if (window_offsets_or_null) memcpy(window_offsets_or_null, wo.data(), sizeof(int64_t) * wo.size());
-    if (B == 0) return F2_OK;
-
-    const bool want_picture = levels_or_null || range_or_null, want_map = map_or_null != nullptr, want_summary = summary_or_null != nullptr;
-    const bool host = mem_space != F2_MEM_DEVICE;
-    const size_t map_bytes = sizeof(double) * 3 * (size_t)B * (size_t)C * (size_t)width, summary_bytes = sizeof(double) * 3 * (size_t)B * (size_t)C;
-    const size_t tail_bytes = host ? (want_map ? map_bytes : 0) + (want_summary ? summary_bytes : 0) : 0;   // a host caller's: behind the scores
-    std::vector<int64_t> rec, rec1;
-    const int64_t map_blocks = track_records(wo.data(), B, spans.data(), hop, width, &rec);
-    const int64_t summary_blocks = track_records(wo.data(), B, whole.data(), hop, 1, &rec1);
-    picture_meta P;
-    int64_t *d_rec, *d_rec1;
-    f2_meta_carve meta;
-    P.add(&meta, B), meta.add(&d_rec, rec.size()), meta.add(&d_rec1, rec1.size());
-    F2_TRY(meta.reserve(ctx));
-    F2_TRY(f2_upload_offsets(ctx, offsets, B));   // (a batch without a sample still gets its pictures)
-    if (total > 0) F2_TRY(eval_envelopes(ctx, &E, X, nullptr, n_total));
-    if (want_picture)
-        F2_TRY(picture_enqueue(ctx, E.d_env, offsets, B, C, spans_or_null, width, pool, &P, nullptr, levels_or_null, range_or_null != nullptr,
-                               mem_space));
-    const bool differentiate = want_map || want_summary;
-    if (n_total > 0) {
-        const int64_t chunk = n_total < CNN_CHUNK ? n_total : CNN_CHUNK;
-        if (differentiate) F2_TRY(f2_reserve(ctx, ctx->sal_profile, sizeof(double) * 2 * (size_t)C * (size_t)n_total));
-        F2_TRY(eval_cnn_begin(ctx, cnn, &E, chunk, n_total, C, scores_or_null, labels_or_null, mem_space, false, tail_bytes));
-        saliency_stage sal = {(double*)ctx->sal_profile.ptr, 0};
-        F2_TRY(strided_window_loop(ctx, cnn, &E, X, nbh, chunk, radius, step, hop, (float*)ctx->xbuf.ptr, nullptr, differentiate ? &sal : nullptr));
-        F2_TRY(eval_dense_flush(ctx, cnn, &E));
-    } else {
-        F2_TRY(f2_place_scores(ctx, nullptr, nullptr, 0, mem_space, false, false, tail_bytes, &E.out));
-    }
-    char* tail = E.out.tail;
-    auto reduce = [&](double* callers, size_t bytes, const std::vector<int64_t>& r, int64_t* d_r, int64_t blocks, int w) -> int {
-        f2_output o;
-        o.dev = host ? tail : (char*)callers, o.host = host ? (char*)callers : nullptr;
-        o.bytes = bytes, o.callers = !host;
-        if (host) tail += bytes;
-        F2_TRY(f2_upload_async(ctx, d_r, r.data(), sizeof(int64_t) * r.size()));
-        F2_TRY(f2_launch_saliency_map(ctx, (const double*)ctx->sal_profile.ptr, d_r, B, C, (int64_t)radius * step, hop, w, blocks, o.as<double>()));
-        return f2_copy_back(ctx, o);
+    auto check = [&](int, int64_t) -> int {
+        F2_CHECK(ctx, C <= 65535, F2_ERR_UNSUPPORTED, "%d channels (at most 65535)", C);
+        return F2_OK;
     };
-    if (want_map) F2_TRY(reduce(map_or_null, map_bytes, rec, d_rec, map_blocks, width));
-    if (want_summary) F2_TRY(reduce(summary_or_null, summary_bytes, rec1, d_rec1, summary_blocks, 1));
-    int rc = F2_OK;
-    if (n_total > 0)
-        rc = eval_cnn_end(ctx, cnn, &E);   // (waits for the stream)
-    else
-        F2_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (rc == F2_OK || rc == F2_ERR_NONPOSITIVE) picture_range(P, B, range_or_null);
-    return rc;
+    auto windows = [&](eval_call* E, const std::vector<int64_t>& nbh, int64_t n_total, size_t tail_bytes) -> int {
+        const int64_t chunk = n_total < CNN_CHUNK ? n_total : CNN_CHUNK;
+        const bool differentiate = map_or_null || summary_or_null;
+        if (differentiate) F2_TRY(f2_reserve(ctx, ctx->sal_profile, sizeof(double) * 2 * (size_t)C * (size_t)n_total));
+        F2_TRY(eval_cnn_begin(ctx, cnn, E, chunk, n_total, C, scores_or_null, labels_or_null, mem_space, false, tail_bytes));
+        saliency_stage sal = {(double*)ctx->sal_profile.ptr, 0};
+        return strided_window_loop(ctx, cnn, E, X, nbh, chunk, radius, step, hop, (float*)ctx->xbuf.ptr, nullptr, differentiate ? &sal : nullptr);
+    };
+    auto launch = [&](const eval_call&, const int64_t* d_rec, int w, int64_t blocks, double* out) {
+        return f2_launch_saliency_map(ctx, (const double*)ctx->sal_profile.ptr, d_rec, B, C, (int64_t)radius * step, hop, w, blocks, out);
+    };
+    const size_t summary_bytes = sizeof(double) * 3 * (size_t)B * (size_t)C;
+    const figure_reduction red[2] = {{map_or_null, summary_bytes * (size_t)width, false}, {summary_or_null, summary_bytes, true}};
+    return figure_call(ctx, cnn, X, radius, step, hop, spans_or_null, width, pool, levels_or_null, range_or_null, window_offsets_or_null, check,
+                       [](f2_meta_carve*) {}, windows, red, 2, launch);
 }
 
 }  // extern "C"

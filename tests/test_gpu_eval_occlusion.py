@@ -262,6 +262,21 @@ def test_optional_outputs_and_empty_batches(ctx, model, coefs):
     mp = fill((B, K, WIDTH, 4), np.float64, 0x5A)
     ctx.eval_occlusion_batch(h, flat, _lib.WAVE_I16, offsets, *args, None, mp, None, None, None, _lib.MEM_HOST)             # the map alone
     assert np.array_equal(bits(mp), bits(full["mp"]))
+    for key in ("mp", "sm"):                     # and each of them alone in device memory
+        a = fill(full[key].shape, np.float64, 0x5A)
+        dw, da = ctx.malloc(flat.nbytes), ctx.malloc(a.nbytes)
+        try:
+            ctx.h2d(dw, flat)
+            ctx.h2d(da, a)
+            ctx.eval_occlusion_batch(h, dw, _lib.WAVE_I16, offsets, *args, None, da if key == "mp" else None, da if key == "sm" else None,
+                                     None, None, _lib.MEM_DEVICE)
+            ctx.synchronize()
+            ctx.d2h(a, da)
+        finally:
+            ctx.synchronize()
+            ctx.free(dw)
+            ctx.free(da)
+        assert np.array_equal(bits(a), bits(full[key])), key
     for lengths in ((1700, 0, 900), (0, 0)):     # no window at all: pictures, empty maps, no scores
         flat2, off2 = batch_of(lengths) if sum(lengths) else (np.zeros(0, np.int16), np.zeros(len(lengths) + 1, np.int64))
         for mem in MEMS:

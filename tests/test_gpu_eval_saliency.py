@@ -152,6 +152,31 @@ def test_optional_outputs(ctx, model, coefs):
     sc = fill((int(wo[-1]), 2), np.float32, 0x5A)
     ctx.eval_saliency_batch(h, flat, _lib.WAVE_I16, offsets, *args, None, None, None, sc, None, _lib.MEM_HOST)               # no map at all
     assert np.array_equal(bits(sc), bits(want["figure"][0]))
+    mp = fill((B, C, WIDTH, 3), np.float64, 0x5A)
+    ctx.eval_saliency_batch(h, flat, _lib.WAVE_I16, offsets, *args, None, mp, None, None, None, _lib.MEM_HOST)               # the map alone
+    assert np.array_equal(bits(mp), bits(want["mp"]))
+    for key in ("mp", "sm"):                     # and each of them alone in device memory
+        a = fill(want[key].shape, np.float64, 0x5A)
+        dw, da = ctx.malloc(flat.nbytes), ctx.malloc(a.nbytes)
+        try:
+            ctx.h2d(dw, flat)
+            ctx.h2d(da, a)
+            ctx.eval_saliency_batch(h, dw, _lib.WAVE_I16, offsets, *args, None, da if key == "mp" else None, da if key == "sm" else None,
+                                    None, None, _lib.MEM_DEVICE)
+            ctx.synchronize()
+            ctx.d2h(a, da)
+        finally:
+            ctx.synchronize()
+            ctx.free(dw)
+            ctx.free(da)
+        assert np.array_equal(bits(a), bits(want[key])), key
+    lengths = (1700, 0, 900)                     # samples but no window: pictures, a map and a summary over no rows, no scores
+    flat2, off2 = batch_of(lengths)
+    for mem in MEMS:
+        o = saliency(ctx, model, coefs, flat2, off2, 160, None, 7, mem)
+        assert not o["wo"].any() and (o["mp"][..., 0] == 0).all() and np.isnan(o["mp"][..., 1:]).all()
+        assert (o["sm"][..., 0] == 0).all() and np.isnan(o["sm"][..., 1:]).all()
+        assert [o["lv"][b].any() for b in range(len(lengths))] == [n > 0 for n in lengths]
     wo, rg = ctx.eval_saliency_batch(h, None, _lib.WAVE_I16, np.zeros(1, np.int64), coefs, 0, C, False, 0.0, _lib.FFT_F32, RADIUS, STEP, 5,
                                      None, 7, 0, None, None, None, None, None, _lib.MEM_HOST)
     assert wo.tolist() == [0] and rg.shape == (0, 2)

@@ -10,6 +10,9 @@ are compared before anything is timed. Prints one JSON line; --out FILE also wri
 import argparse, json, os, statistics, sys, time
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+if os.environ.get("F2CNN_PROBE_LIB"):   # another build of the library, as for saliency_timing.py
+    from f2cnn_amd import build
+    build.LIB_PATH = os.path.abspath(os.environ["F2CNN_PROBE_LIB"])
 from f2cnn_amd import _lib
 from f2cnn_amd.gammatone import filters
 from f2cnn_amd.model import F2CNNModel

@@ -1,6 +1,8 @@
 """Outputs of two builds of the library compared bit for bit (diagnostic; profiles/r08_a_old_new_identity.txt).
-    python tools/old_new_identity.py run LIB OUT.json [KEEP_DIR]    digests of every case's outputs with that library; with
-                                          KEEP_DIR the outputs of the low-pass cases themselves are kept there (float64, ~1.3 GB)
+    python tools/old_new_identity.py run LIB OUT.json [KEEP_DIR] [--only=GROUP,...]    digests of every case's outputs with that
+                                          library; with KEEP_DIR the outputs of the low-pass cases themselves are kept there (float64,
+                                          ~1.3 GB); --only: the named groups alone (cnn_cases, entry_cases, sweep_cases, grad_cases,
+                                          figure_cases)
     python tools/old_new_identity.py compare OLD.json NEW.json [OLD_KEEP_DIR NEW_KEEP_DIR]    the table "case: identical /
                                           differs"; with the kept outputs, for a case that differs, the largest difference
                                           relative to the row maximum (envelopes: per utterance and channel; scores and windows:
@@ -25,7 +27,10 @@ outputs and the scores alone; f2_cnn_layers on the recorded route; f2_cnn_loss_g
 with dropout, without an index and with a permutation that repeats, on 4100 windows from host memory (two host pieces), on none,
 and on 193 windows of 13 x 40 - the 12 gradients, the loss sum and the hits in the digest; f2_trainer_steps twice over 70 windows
 in batches of 32 - weights, accumulators, last gradient, loss, hits and iterations after each call; f2_eval_saliency_batch on the
-case of tests/test_gpu_saliency_placement.py."""
+case of tests/test_gpu_saliency_placement.py. The figure family (profiles/r37_a_old_new_identity.txt) on that case's utterances with
+spans given, hop 16 and hop = STEP, host and device memory: f2_eval_figure_batch and f2_eval_occlusion_batch (K = 2 patches) with
+every output, with each reduction alone and with none of them - every output given, window_offsets and the range in the digest;
+f2_score_track, f2_occlusion_map and f2_saliency_map on random rows."""
 import hashlib, json, os, sys
 import numpy as np
 
@@ -300,6 +305,62 @@ def grad_cases(ctx, res):
     print("gradient cases done", flush=True)
 
 
+def figure_cases(ctx, res):
+    from f2cnn_amd import _lib
+    from f2cnn_amd.gammatone import filters
+    from f2cnn_amd.model import F2CNNModel
+    import f2cnn_oracle as orc
+    MEMS = (("host", _lib.MEM_HOST), ("device", _lib.MEM_DEVICE))
+    lens, CS, W, K = [2500, 1761, 3001, 1700], 16, 40, 2       # (the saliency case of grad_cases; 1700 is shorter than a window)
+    B = len(lens)
+    coefs = np.ascontiguousarray(filters.make_erb_filters(16000, filters.centre_freqs(16000, CS, 100)))
+    offs = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+    wave = np.concatenate([orc.synth_utterance(3100 + i, k) for i, k in enumerate(lens)]).astype(np.int16)
+    spans = np.array([[100, 2400], [0, 1761], [500, 3001], [0, 1700]], np.int64)
+    patches, fillv = np.array([[0, R, 0, 8], [3, 8, 4, CS]], np.int32), 0.25
+    h = F2CNNModel.glorot(7, R, CS, zero_bias=False).handle(ctx)
+    for hop in (16, STEP):
+        front = (_lib.WAVE_I16, offs, coefs, B, CS, True, 50.0, _lib.FFT_F32, RADIUS, STEP, hop)
+        wo = np.concatenate([[0], np.cumsum([_lib.strided_window_count(k, RADIUS, STEP, hop) for k in lens])]).astype(np.int64)
+        n = int(wo[-1])
+        fused = [
+            ("f2_eval_figure_batch", dict(levels=((B, CS, W), np.uint8), track=((B, W, 5), np.float64), scores=((n, 2), np.float32), labels=(n, np.uint8)),
+             lambda mem, w, lv, tr, sc, lb: ctx.eval_figure_batch(h, w, *front, spans, W, 0, lv, tr, sc, lb, mem),
+             (("every output", "levels track scores labels"), ("the track alone", "track"), ("no track", "levels scores labels"))),
+            ("f2_eval_occlusion_batch", dict(levels=((B, CS, W), np.uint8), map=((B, K, W, 4), np.float64), summary=((B, K, 4), np.float64),
+                                             scores=((n, K + 1, 2), np.float32), labels=((n, K + 1), np.uint8)),
+             lambda mem, w, lv, mp, sm, sc, lb: ctx.eval_occlusion_batch(h, w, *front, patches, fillv, spans, W, 0, lv, mp, sm, sc, lb, mem),
+             (("every output", "levels map summary scores labels"), ("the map alone", "map"), ("the summary alone", "summary"),
+              ("neither map nor summary", "levels scores labels"))),
+        ]
+        for name, shapes, call, variants in fused:
+            for mname, mem in MEMS:
+                for vname, given in variants:
+                    outs = [np.zeros(s, dt) if k in given.split() else None for k, (s, dt) in shapes.items()]
+                    f = lambda *p: call(mem, *p)
+                    small = f(wave, *outs) if mem == _lib.MEM_HOST else on_device(ctx, [wave] + outs, f)
+                    res[f"{name}: hop {hop}, {mname} memory, {vname}"] = digest(*[a for a in outs if a is not None], *small)
+        # the reductions alone, on rows that do not come from the library
+        rng = np.random.default_rng(370 + hop)
+        sc = rng.standard_normal((n, K + 1, 2)).astype(np.float32)
+        lb = (sc[..., 1] > sc[..., 0]).astype(np.uint8)
+        prof, origin = rng.standard_normal((n, CS, 2)), RADIUS * STEP
+        alone = [
+            ("f2_score_track", [sc[:, 0].copy(), lb[:, 0].copy()], (B, W, 5), lambda mem, s, l, o: ctx.score_track(s, l, wo, spans, origin, hop, W, o, mem)),
+            ("f2_occlusion_map", [sc, lb], (B, K, W, 4), lambda mem, s, l, o: ctx.occlusion_map(s, l, wo, K, spans, origin, hop, W, o, mem)),
+            ("f2_saliency_map", [prof], (B, CS, W, 3), lambda mem, p, o: ctx.saliency_map(p, wo, CS, spans, origin, hop, W, o, mem)),
+        ]
+        for name, ins, shape, call in alone:
+            for mname, mem in MEMS:
+                out = np.zeros(shape)
+                if mem == _lib.MEM_HOST:
+                    call(mem, *ins, out)
+                else:
+                    on_device(ctx, ins + [out], lambda *p: call(mem, *p))
+                res[f"{name}: hop {hop}, {mname} memory"] = digest(out)
+    print("figure cases done", flush=True)
+
+
 def keep_arrays(keep, key, arrays, lens=None, C=None, envelopes=()):
     """the outputs of one case under KEEP_DIR: a<i>.npy each; `envelopes` = the indices of the arrays laid out
     [utterance][channel][sample] for utterances of `lens` samples and C channels"""
@@ -336,7 +397,7 @@ def worst_row_difference(key, old_keep, new_keep):
     return worst
 
 
-def run(lib, out, keep=None):
+def run(lib, out, keep=None, only=None):
     from f2cnn_amd import build
     build.LIB_PATH = os.path.abspath(lib)
     import f2cnn_oracle as orc
@@ -346,7 +407,7 @@ def run(lib, out, keep=None):
     coefs = orc.make_erb_filters(16000, orc.centre_freqs(16000, C, 100))
     h = F2CNNModel.glorot(11).handle(ctx)
     res = {}
-    for name, lens in BATCHES:
+    for name, lens in BATCHES if not only else []:
         waves = [orc.synth_utterance(500 + i, n) for i, n in enumerate(lens)]
         flat = np.concatenate(waves)
         offs = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
@@ -382,10 +443,9 @@ def run(lib, out, keep=None):
             if lpf:
                 keep_arrays(keep, f"f2_input_batch: {tag}", [win])
             print(tag, "done", flush=True)
-    cnn_cases(ctx, res)
-    entry_cases(ctx, res)
-    sweep_cases(ctx, res)
-    grad_cases(ctx, res)
+    for group in (cnn_cases, entry_cases, sweep_cases, grad_cases, figure_cases):
+        if not only or group.__name__ in only.split(","):
+            group(ctx, res)
     ctx.close()
     with open(out, "w") as f:
         json.dump(res, f, indent=1)
@@ -413,4 +473,6 @@ def compare(a, b, old_keep=None, new_keep=None):
 
 
 if __name__ == "__main__":
-    sys.exit(run(*sys.argv[2:5]) if sys.argv[1] == "run" else compare(*sys.argv[2:6]))
+    only = [a[len("--only="):] for a in sys.argv if a.startswith("--only=")]
+    args = [a for a in sys.argv if not a.startswith("--only=")]
+    sys.exit(run(*args[2:5], only=only[0] if only else None) if args[1] == "run" else compare(*args[2:6]))
