@@ -2,6 +2,8 @@
 // pointer handling around the kernel launchers. See include/f2cnn_hip.h for the contract.
 #include "f2_internal.h"
 
+#include <cmath>
+
 char g_f2_err[512] = {0};
 
 int f2_fail(f2_ctx* ctx, int code, const char* fmt, ...) {
@@ -592,6 +594,46 @@ int f2_check_batch(f2_ctx* ctx, const int64_t* offsets, int B, int C, int mem_sp
     F2_CHECK(ctx, B >= 0 && C >= (pipeline ? 1 : 0), F2_ERR_INVALID, "bad batch size (B=%d) or channel count (C=%d)", B, C);
     F2_TRY(f2_check_mem_space(ctx, mem_space, !pipeline));
     return f2_check_offsets(ctx, offsets, B, "offsets");
+}
+
+int f2_check_wave_batch(f2_ctx* ctx, int wave_dtype, const int64_t* offsets, int B, int mem_space) {
+    F2_CHECK(ctx, B >= 0, F2_ERR_INVALID, "bad batch size (B=%d)", B);
+    F2_TRY(f2_check_wave_dtype(ctx, wave_dtype));
+    F2_TRY(f2_check_mem_space(ctx, mem_space, false));
+    return f2_check_offsets(ctx, offsets, B, "offsets");
+}
+
+int f2_check_taps(f2_ctx* ctx, const double* taps, const int64_t* offsets, int K, int max_levels, int max_taps, const f2_tap_words& W) {
+    F2_CHECK(ctx, K <= max_levels, F2_ERR_UNSUPPORTED, "%d %s (at most %d)", K, W.many, max_levels);
+    F2_CHECK(ctx, offsets[0] == 0, F2_ERR_INVALID, "%s[0] must be 0%s", W.offsets, W.at_zero);
+    for (int l = 0; l < K; ++l) {
+        const int64_t n = offsets[l + 1] - offsets[l];
+        F2_CHECK(ctx, n >= 0, F2_ERR_INVALID, "%s must be non-decreasing (%s%d)", W.offsets, W.index, l);
+        F2_CHECK(ctx, n >= 1, F2_ERR_INVALID, "%s %d has no taps", W.one, l);
+    }
+    for (int l = 0; l < K; ++l) {
+        const int64_t n = offsets[l + 1] - offsets[l];
+        F2_CHECK(ctx, n <= max_taps, F2_ERR_UNSUPPORTED, "%s %d has %lld taps (at most %d)", W.one, l, (long long)n, max_taps);
+    }
+    for (int l = 0; l < K; ++l)
+        for (int64_t t = offsets[l]; t < offsets[l + 1]; ++t)
+            F2_CHECK(ctx, std::isfinite(taps[t]), F2_ERR_INVALID, "tap %lld of %s %d is not finite", (long long)(t - offsets[l]), W.one, l);
+    return F2_OK;
+}
+
+int64_t f2_tile_table(const int64_t* h_offsets, int B, int block, std::vector<int64_t>* first) {
+    if (first) first->assign((size_t)B + 1, 0);
+    int64_t tiles = 0;
+    for (int b = 0; b < B; ++b) {
+        tiles += (h_offsets[b + 1] - h_offsets[b] + block - 1) / block;
+        if (first) (*first)[(size_t)b + 1] = tiles;
+    }
+    return tiles;
+}
+
+int f2_check_workgroups(f2_ctx* ctx, int64_t count, const char* what, const char* per) {
+    F2_CHECK(ctx, count < (int64_t(1) << 31), F2_ERR_UNSUPPORTED, "%s needs %lld workgroups%s (at most 2^31 - 1)", what, (long long)count, per);
+    return F2_OK;
 }
 
 int f2_check_cnn(f2_ctx* ctx, const f2_cnn* cnn, int rows, int C) {

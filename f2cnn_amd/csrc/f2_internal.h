@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
@@ -237,6 +238,21 @@ int f2_check_offsets(f2_ctx* ctx, const int64_t* offsets, int B, const char* nam
 // B, C, mem_space and offsets of a ragged batch. `pipeline` (the calls of f2_pipeline.hip): C == 0 and F2_MEM_HOST_ASYNC are
 // errors; without it C == 0 is an empty call and the third memory space is accepted
 int f2_check_batch(f2_ctx* ctx, const int64_t* offsets, int B, int C, int mem_space, bool pipeline);
+// B, wave_dtype, mem_space and offsets of a ragged batch of waves, in that order (the stage calls of waves)
+int f2_check_wave_batch(f2_ctx* ctx, int wave_dtype, const int64_t* offsets, int B, int mem_space);
+// A packed table of K runs of taps (taps, offsets: K + 1 entries) behind the caller's own checks of K and the two pointers:
+// K <= max_levels (F2_ERR_UNSUPPORTED), offsets from 0 and non-decreasing, every run of 1 .. max_taps (above: F2_ERR_UNSUPPORTED)
+// finite taps (F2_ERR_INVALID), tested in that order. The caller's words make the messages: "<K> <many> (at most ..)",
+// "<offsets>[0] must be 0<at_zero>", "<offsets> must be non-decreasing (<index><l>)", "<one> <l> has no taps" and so on.
+struct f2_tap_words {
+    const char *many, *offsets, *at_zero, *index, *one;
+};
+int f2_check_taps(f2_ctx* ctx, const double* taps, const int64_t* offsets, int K, int max_levels, int max_taps, const f2_tap_words& W);
+// The tile table of a ragged batch: the total of ceil(n_b / block) over the B utterances of h_offsets, and with `first` the B + 1
+// running sums (what tile_owner of f2_tile_owner.h searches). f2_check_workgroups: a grid dimension of `count` workgroups exists
+// (F2_ERR_UNSUPPORTED from 2^31 on: "<what> needs <count> workgroups<per> (at most 2^31 - 1)").
+int64_t f2_tile_table(const int64_t* h_offsets, int B, int block, std::vector<int64_t>* first = nullptr);
+int f2_check_workgroups(f2_ctx* ctx, int64_t count, const char* what, const char* per);
 // non-NULL, weights on the context's device, built for rows x C windows (rows == 0: the call has no window shape of its own)
 int f2_check_cnn(f2_ctx* ctx, const f2_cnn* cnn, int rows, int C);
 // *d_wave = the caller's pointer for F2_MEM_DEVICE, else ctx->stage_in after an asynchronous copy of `total` samples into it
@@ -330,6 +346,46 @@ int f2_batch_envelopes(f2_ctx* ctx, const f2_batch& X, double* env_or_null, doub
         int rc_ = (expr);         \
         if (rc_ != F2_OK) return rc_; \
     } while (0)
+
+// One body for the calls that turn a ragged batch into levels, or into one level per utterance (f2_reverb_levels, f2_reverb_pick,
+// f2_shaped_noise_levels, f2_noise_pick, f2_lowpass_levels, f2_channel_mix_levels). Of the call:
+//   check()                 every argument check behind the context's, in the call's own order (the tests pin the precedence); after
+//                           it offsets is valid wherever B > 0
+//   carve(meta)             names its small arrays (and reserves what it keeps elsewhere)
+//   in, stage(total, &d_in) its input and how that reaches the device (f2_stage_wave, f2_stage_input)
+//   area, out, bytes_per_sample   where its output goes by the rule of f2_place, and how large it is per sample of the batch
+//   launch(d_in, d_offsets, total, d_out)   its uploads and launches
+//   sigma_or_null, n_sigma, d_sigma   a call with a sigma: n_sigma values from *d_sigma (which the carve sets, or leaves NULL: zeros)
+//                           come back; zeros on an empty batch
+// A host call waits for the stream; a device call only with a sigma to bring back.
+template <class Check, class Carve, class Stage, class Launch>
+int f2_stage_call(f2_ctx* ctx, const int64_t* offsets, int B, int mem_space, Check check, Carve carve, const void* in, Stage stage,
+                  f2_scratch f2_ctx::*area, double* out, size_t bytes_per_sample, Launch launch, double* sigma_or_null = nullptr,
+                  size_t n_sigma = 0, double* const* d_sigma = nullptr) {
+    F2_TRY(f2_check_ctx(ctx));
+    F2_TRY(check());
+    const int64_t total = B > 0 ? offsets[B] : 0;
+    if (total == 0) {
+        if (sigma_or_null) std::fill(sigma_or_null, sigma_or_null + n_sigma, 0.0);
+        return F2_OK;
+    }
+    F2_CHECK(ctx, in && out, F2_ERR_INVALID, "null data pointer");
+    f2_meta_carve meta;
+    F2_TRY(carve(&meta));
+    F2_TRY(meta.reserve(ctx));
+    f2_output o;
+    F2_TRY(f2_place(ctx, ctx->*area, out, bytes_per_sample * (size_t)total, mem_space, true, &o));
+    const void* d_in;
+    F2_TRY(stage(total, &d_in));
+    F2_TRY(f2_upload_offsets(ctx, offsets, B));
+    F2_TRY(launch(d_in, (const int64_t*)ctx->offsets.ptr, total, o.as<double>()));
+    F2_TRY(f2_copy_back(ctx, o));
+    if (!sigma_or_null) return f2_host_wait(ctx, mem_space);
+    if (*d_sigma) F2_HIP(ctx, hipMemcpyAsync(sigma_or_null, *d_sigma, sizeof(double) * n_sigma, hipMemcpyDeviceToHost, ctx->stream));
+    else std::fill(sigma_or_null, sigma_or_null + n_sigma, 0.0);
+    F2_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return F2_OK;
+}
 
 // ---- per-workgroup phase stamps, diagnostic build only (-DF2_STAMPS; tools/k2_stamps.py, tools/pair_stamps.py) ----
 // F2_STAMP_ARRAY(st, N) declares N stamps in registers; F2_STAMP(st, k) records s_memrealtime (100 MHz, 10 ns ticks) into

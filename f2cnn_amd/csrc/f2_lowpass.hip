@@ -95,27 +95,23 @@ int f2_launch_lowpass_levels(f2_ctx* ctx, const double* d_env, const int64_t* d_
 
 extern "C" int f2_lowpass_levels(f2_ctx* ctx, const double* env, const int64_t* offsets, int B, int C, const double* cutoff_hz, int K,
                                  double* levels, int mem_space) {
-    F2_TRY(f2_check_ctx(ctx));
-    F2_CHECK(ctx, B >= 0 && C >= 1, F2_ERR_INVALID, "bad batch size (B=%d) or channel count (C=%d)", B, C);
-    F2_TRY(f2_check_mem_space(ctx, mem_space, false));
-    F2_TRY(f2_check_offsets(ctx, offsets, B, "offsets"));
-    F2_TRY(f2_check_cutoffs(ctx, cutoff_hz, K));
-    F2_CHECK(ctx, (int64_t)B * C <= INT32_MAX, F2_ERR_UNSUPPORTED, "%d utterances of %d channels", B, C);
-    const int64_t total = offsets[B];
-    if (B == 0 || total == 0) return F2_OK;
-    F2_CHECK(ctx, env && levels, F2_ERR_INVALID, "null data pointer");
     double* d_coef;
-    f2_meta_carve meta;
-    meta.add(&d_coef, 2 * (size_t)K);
-    F2_TRY(meta.reserve(ctx));
-    const size_t bytes = sizeof(double) * (size_t)C * (size_t)total;
-    f2_output out;
-    F2_TRY(f2_place(ctx, ctx->levels, levels, bytes * ((size_t)K + 1), mem_space, true, &out));
-    const void* d_env;
-    F2_TRY(f2_stage_input(ctx, env, bytes, mem_space, &d_env));
-    F2_TRY(f2_upload_offsets(ctx, offsets, B));
-    F2_TRY(f2_upload_lowpass_coefs(ctx, cutoff_hz, K, d_coef));
-    F2_TRY(f2_launch_lowpass_levels(ctx, (const double*)d_env, (const int64_t*)ctx->offsets.ptr, B, C, total, d_coef, K, out.as<double>()));
-    F2_TRY(f2_copy_back(ctx, out));
-    return f2_host_wait(ctx, mem_space);
+    return f2_stage_call(
+        ctx, offsets, B, mem_space,
+        [&]() -> int {
+            F2_TRY(f2_check_batch(ctx, offsets, B, C, mem_space, true));
+            F2_TRY(f2_check_cutoffs(ctx, cutoff_hz, K));
+            F2_CHECK(ctx, (int64_t)B * C <= INT32_MAX, F2_ERR_UNSUPPORTED, "%d utterances of %d channels", B, C);
+            return F2_OK;
+        },
+        [&](f2_meta_carve* meta) {
+            meta->add(&d_coef, 2 * (size_t)K);
+            return F2_OK;
+        },
+        env, [&](int64_t total, const void** d_env) { return f2_stage_input(ctx, env, sizeof(double) * (size_t)C * (size_t)total, mem_space, d_env); },
+        &f2_ctx::levels, levels, sizeof(double) * (size_t)C * ((size_t)K + 1),
+        [&](const void* d_env, const int64_t* d_offsets, int64_t total, double* d_out) -> int {
+            F2_TRY(f2_upload_lowpass_coefs(ctx, cutoff_hz, K, d_coef));
+            return f2_launch_lowpass_levels(ctx, (const double*)d_env, d_offsets, B, C, total, d_coef, K, d_out);
+        });
 }

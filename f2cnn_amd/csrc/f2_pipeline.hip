@@ -1031,38 +1031,27 @@ int f2_input_batch(f2_ctx* ctx, const void* wave, int wave_dtype, const int64_t*
 // back. A device call waits only for sigma.
 int f2_noise_pick(f2_ctx* ctx, const void* wave, int wave_dtype, const int64_t* offsets, int B, const double* snr_db, int K,
                   const int32_t* level_of, uint32_t first_utterance, uint64_t seed, double* noisy, double* sigma_or_null, int mem_space) {
-    F2_TRY(f2_check_ctx(ctx));
-    F2_TRY(f2_check_wave_dtype(ctx, wave_dtype));
-    F2_CHECK(ctx, B >= 0, F2_ERR_INVALID, "bad batch size (B=%d)", B);
-    F2_TRY(f2_check_mem_space(ctx, mem_space, false));
     const f2_noise_pick_args N = {snr_db, K, level_of, first_utterance, seed};
-    F2_TRY(f2_check_noise_pick(ctx, B, N));
-    if (B == 0) return F2_OK;
-    F2_TRY(f2_check_offsets(ctx, offsets, B, "offsets"));
-    const int64_t total = offsets[B];
-    if (total == 0) {
-        if (sigma_or_null) std::fill(sigma_or_null, sigma_or_null + B, 0.0);
-        return F2_OK;
-    }
-    F2_CHECK(ctx, wave && noisy, F2_ERR_INVALID, "null data pointer");
     noise_pick_meta M;
-    f2_meta_carve meta;
-    M.carve(&meta, B, N);
-    F2_TRY(meta.reserve(ctx));
-    f2_output out;
-    F2_TRY(f2_place(ctx, ctx->levels, noisy, sizeof(double) * (size_t)total, mem_space, true, &out));
-    F2_TRY(f2_upload_offsets(ctx, offsets, B));
-    const void* d_wave;
-    F2_TRY(f2_stage_wave(ctx, wave, wave_dtype, total, mem_space, &d_wave));
-    F2_TRY(M.launch(ctx, d_wave, wave_dtype, (const int64_t*)ctx->offsets.ptr, B, total, N, out.as<double>()));
-    F2_TRY(f2_copy_back(ctx, out));
-    if (sigma_or_null) {
-        if (M.d_sigma) F2_HIP(ctx, hipMemcpyAsync(sigma_or_null, M.d_sigma, sizeof(double) * (size_t)B, hipMemcpyDeviceToHost, ctx->stream));
-        else std::fill(sigma_or_null, sigma_or_null + B, 0.0);
-        F2_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        return F2_OK;
-    }
-    return f2_host_wait(ctx, mem_space);
+    return f2_stage_call(
+        ctx, offsets, B, mem_space,
+        [&]() -> int {   // (the dtype before B, and the offsets last and only where there is an utterance: they may be NULL without)
+            F2_TRY(f2_check_wave_dtype(ctx, wave_dtype));
+            F2_CHECK(ctx, B >= 0, F2_ERR_INVALID, "bad batch size (B=%d)", B);
+            F2_TRY(f2_check_mem_space(ctx, mem_space, false));
+            F2_TRY(f2_check_noise_pick(ctx, B, N));
+            return B == 0 ? F2_OK : f2_check_offsets(ctx, offsets, B, "offsets");
+        },
+        [&](f2_meta_carve* meta) {
+            M.carve(meta, B, N);
+            return F2_OK;
+        },
+        wave, [&](int64_t total, const void** d_wave) { return f2_stage_wave(ctx, wave, wave_dtype, total, mem_space, d_wave); },
+        &f2_ctx::levels, noisy, sizeof(double),
+        [&](const void* d_wave, const int64_t* d_offsets, int64_t total, double* d_out) {
+            return M.launch(ctx, d_wave, wave_dtype, d_offsets, B, total, N, d_out);
+        },
+        sigma_or_null, (size_t)(B > 0 ? B : 0), &M.d_sigma);
 }
 
 int f2_input_batch_noisy(f2_ctx* ctx, const void* wave, int wave_dtype, const int64_t* offsets, const double* coefs, int B, int C,

@@ -5,6 +5,7 @@
 //   k_pcm_convert  up == down == 1: the conversion and the mixdown alone
 // gfx950, wave64. Everything that reaches memory is written by plain C++ stores.
 #include "f2_internal.h"
+#include "f2_tile_owner.h"
 
 namespace {
 
@@ -51,8 +52,8 @@ __device__ __forceinline__ double mono_frame(const typename pcm<FMT>::type* __re
     return s / (double)channels;
 }
 
-// Workgroup blockIdx.x serves outputs k0 .. k0 + RT - 1 of the utterance b with first[b] <= blockIdx.x < first[b + 1] (first: the
-// running sums of the utterances' workgroups behind the 4 B records of `meta`; an utterance without output has none).
+// Workgroup blockIdx.x serves outputs k0 .. k0 + RT - 1 of the utterance that owns it (tile_owner over `first`: the running sums
+// of the utterances' workgroups behind the 4 B records of `meta`).
 // Output k reads x[i_hi - t] taps[p + t up], c = k down + half_len (64-bit), i_hi = c / up, p = c % up, t < T. The 64-bit division
 // is made once per workgroup, for k0: c = c0 + j down for lane j, so i_hi = c0 / up + (c0 % up + j down) / up in 32 bits
 // (up, down <= 2^22). The workgroup needs the frames i_lo = c0 / up - (T - 1) .. i_hi of its last lane: `span` <= SPAN of them
@@ -67,12 +68,7 @@ __global__ __launch_bounds__(RT) void k_resample(const typename pcm<FMT>::type* 
     const int tid = threadIdx.x;
     const int64_t* first = meta + 4 * (size_t)B;
     const int64_t blk = blockIdx.x;
-    int b = 0, hi = B;      // first[b] <= blk < first[hi]
-    while (hi - b > 1) {
-        const int mid = (b + hi) >> 1;
-        if (first[mid] <= blk) b = mid;
-        else hi = mid;
-    }
+    const int b = tile_owner(first, B, blk);
     const int64_t in0 = meta[4 * (size_t)b], n = meta[4 * (size_t)b + 1], out0 = meta[4 * (size_t)b + 2], n_out = meta[4 * (size_t)b + 3];
     const int64_t k0 = (blk - first[b]) * RT;
     const int nk = (int)min((int64_t)RT, n_out - k0);      // outputs of this workgroup, >= 1
@@ -120,8 +116,7 @@ int64_t f2_resample_span(int64_t up, int64_t down, int64_t T) { return (up - 1 +
 int f2_launch_resample(f2_ctx* ctx, const void* d_audio, int pcm_format, int channels, int channel, const int64_t* d_meta, int B,
                        int64_t total_blocks, int64_t up, int64_t down, int64_t half_len, int T, const double* d_table, double* d_out) {
     if (B <= 0 || total_blocks <= 0) return F2_OK;
-    F2_CHECK(ctx, total_blocks < (int64_t(1) << 31), F2_ERR_UNSUPPORTED, "resampling needs %lld workgroups (at most 2^31 - 1)",
-             (long long)total_blocks);
+    F2_TRY(f2_check_workgroups(ctx, total_blocks, "resampling", ""));
     const dim3 grid((unsigned)total_blocks);
 #define F2_RS_CALL(F)                                                                                                              \
     k_resample<F><<<grid, dim3(RT), 0, ctx->stream>>>((const pcm<F>::type*)d_audio, d_meta, B, channels, channel, (unsigned)up, \

@@ -13,6 +13,7 @@
 // weights are zero by the definition of a support, and fma(0, x, acc) leaves acc as it is for finite x - up to the sign of a zero,
 // which the closing acc + 0.0 settles (a zero is stored as +0.0). gfx950, wave64; plain vector stores only.
 #include "f2_internal.h"
+#include "f2_tile_owner.h"
 
 #include <algorithm>
 #include <cmath>
@@ -31,8 +32,8 @@ constexpr unsigned SM_XCDS = 8;                         // dies a launch is deal
 // tiles of all levels - have neighbouring ids. Workgroups are dealt round-robin over the chip's SM_XCDS dies, each with an L2 of its
 // own, so workgroup w takes tile id (w % SM_XCDS) * (gridDim.x / SM_XCDS) + w / SM_XCDS: one die then walks a contiguous range of
 // ids, and an input tile is fetched into one L2 instead of all of them (for speed only: any placement computes the same; the grid is
-// padded to a multiple of SM_XCDS and ids from `tiles` on have nothing to do). Time tile t serves samples k0 .. k0 + SM_TS - 1 of the utterance b with first[b] <= t < first[b + 1] (first: running
-// sums of the utterances' tiles; an empty utterance has none). Lane L owns k0 + L and k0 + L + SM_NT; a lane beyond the
+// padded to a multiple of SM_XCDS and ids from `tiles` on have nothing to do). Time tile t serves samples k0 .. k0 + SM_TS - 1 of the utterance that owns it
+// (tile_owner over `first`). Lane L owns k0 + L and k0 + L + SM_NT; a lane beyond the
 // utterance's end reads its last sample instead (never stored). wT: per level C rows of Cpad doubles, wT[l][c'][c] =
 // mix[l][c][c'], zero for c >= C; spans[l * nct + ct] = lo | hi << 32, the input channels lo .. hi - 1 the tile walks.
 __global__ __launch_bounds__(SM_NT) void k_channel_mix_levels(const double* __restrict__ env, const int64_t* __restrict__ offsets,
@@ -45,12 +46,7 @@ __global__ __launch_bounds__(SM_NT) void k_channel_mix_levels(const double* __re
     const unsigned per = (unsigned)nct * (unsigned)(K + 1);
     const unsigned t = id / per, r = id - t * per;
     const int l = (int)(r / (unsigned)nct), ct = (int)(r - (unsigned)l * (unsigned)nct);
-    int b = 0, top = B;      // first[b] <= t < first[top]
-    while (top - b > 1) {
-        const int mid = (b + top) >> 1;
-        if (first[mid] <= (int64_t)t) b = mid;
-        else top = mid;
-    }
+    const int b = tile_owner(first, B, (int64_t)t);
     const int64_t n = offsets[b + 1] - offsets[b];
     const int64_t k0 = ((int64_t)t - first[b]) * SM_TS;
     const int64_t i0 = k0 + tid, i1 = i0 + SM_NT;                  // k0 < n: the tile has at least one sample
@@ -138,11 +134,10 @@ int f2_launch_channel_mix_levels(f2_ctx* ctx, const double* d_env, const int64_t
                                  const f2_smear_plan& P, double* d_levels) {
     const int64_t total = h_offsets[B];
     if (B == 0 || total == 0) return F2_OK;
-    std::vector<int64_t> small((size_t)B + 1, 0);      // [running sums of the utterances' tiles | spans]
-    for (int b = 0; b < B; ++b) small[(size_t)b + 1] = small[(size_t)b] + (h_offsets[b + 1] - h_offsets[b] + SM_TS - 1) / SM_TS;
-    const int64_t tiles = small[(size_t)B] * (int64_t)P.nct * (P.K + 1);
+    std::vector<int64_t> small;                        // [running sums of the utterances' tiles | spans]
+    const int64_t tiles = f2_tile_table(h_offsets, B, SM_TS, &small) * (int64_t)P.nct * (P.K + 1);
     const int64_t blocks = (tiles + SM_XCDS - 1) / SM_XCDS * SM_XCDS;
-    F2_CHECK(ctx, blocks < (int64_t(1) << 31), F2_ERR_UNSUPPORTED, "the channel mix needs %lld workgroups (at most 2^31 - 1)", (long long)blocks);
+    F2_TRY(f2_check_workgroups(ctx, blocks, "the channel mix", ""));
     small.insert(small.end(), P.spans.begin(), P.spans.end());
     int64_t* d_first = (int64_t*)ctx->mix.ptr;
     int64_t* d_spans = d_first + B + 1;
@@ -157,24 +152,19 @@ int f2_launch_channel_mix_levels(f2_ctx* ctx, const double* d_env, const int64_t
 
 extern "C" int f2_channel_mix_levels(f2_ctx* ctx, const double* env, const int64_t* offsets, int B, int C, const double* mix, int K,
                                      double* levels, int mem_space) {
-    F2_TRY(f2_check_ctx(ctx));
-    F2_CHECK(ctx, B >= 0 && C >= 1, F2_ERR_INVALID, "bad batch size (B=%d) or channel count (C=%d)", B, C);
-    F2_TRY(f2_check_mem_space(ctx, mem_space, false));
-    F2_TRY(f2_check_offsets(ctx, offsets, B, "offsets"));
     f2_smear_plan P;
-    F2_TRY(f2_check_mix(ctx, mix, K, C, &P));
-    F2_CHECK(ctx, (int64_t)B * C <= INT32_MAX, F2_ERR_UNSUPPORTED, "%d utterances of %d channels", B, C);
-    const int64_t total = offsets[B];
-    if (B == 0 || total == 0) return F2_OK;
-    F2_CHECK(ctx, env && levels, F2_ERR_INVALID, "null data pointer");
-    F2_TRY(f2_smear_reserve(ctx, P, B));
-    const size_t bytes = sizeof(double) * (size_t)C * (size_t)total;
-    f2_output out;
-    F2_TRY(f2_place(ctx, ctx->levels, levels, bytes * ((size_t)K + 1), mem_space, true, &out));
-    const void* d_env;
-    F2_TRY(f2_stage_input(ctx, env, bytes, mem_space, &d_env));
-    F2_TRY(f2_upload_offsets(ctx, offsets, B));
-    F2_TRY(f2_launch_channel_mix_levels(ctx, (const double*)d_env, (const int64_t*)ctx->offsets.ptr, offsets, B, P, out.as<double>()));
-    F2_TRY(f2_copy_back(ctx, out));
-    return f2_host_wait(ctx, mem_space);
+    return f2_stage_call(
+        ctx, offsets, B, mem_space,
+        [&]() -> int {
+            F2_TRY(f2_check_batch(ctx, offsets, B, C, mem_space, true));
+            F2_TRY(f2_check_mix(ctx, mix, K, C, &P));
+            F2_CHECK(ctx, (int64_t)B * C <= INT32_MAX, F2_ERR_UNSUPPORTED, "%d utterances of %d channels", B, C);
+            return F2_OK;
+        },
+        [&](f2_meta_carve*) { return f2_smear_reserve(ctx, P, B); }, env,
+        [&](int64_t total, const void** d_env) { return f2_stage_input(ctx, env, sizeof(double) * (size_t)C * (size_t)total, mem_space, d_env); },
+        &f2_ctx::levels, levels, sizeof(double) * (size_t)C * ((size_t)K + 1),
+        [&](const void* d_env, const int64_t* d_offsets, int64_t, double* d_out) {
+            return f2_launch_channel_mix_levels(ctx, (const double*)d_env, d_offsets, offsets, B, P, d_out);
+        });
 }

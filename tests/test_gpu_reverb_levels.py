@@ -101,6 +101,20 @@ def test_integer_data_is_numpys_convolution_bit_for_bit(int_case, int_levels):
     assert np.array_equal(bits(int_levels[K]), bits(wave.astype(np.float64)))        # the dry level
 
 
+@pytest.mark.parametrize("n", [1, 3, BLK + 1])
+def test_every_tap_count_up_to_sixteen_is_numpys_convolution_bit_for_bit(ctx, n):
+    """1 .. 16 taps are every combination of the walk's paired turns (0 .. 2), its single step (0 / 1) and its 0 .. 3 last taps; an
+    utterance of BLK + 1 samples has a full tile and a tile of one output, those of 1 and 3 samples a lane with fewer outputs than
+    it owns. Integer data as in int_case: sums below 16 * 8 * 32768 < 2^53"""
+    rng = np.random.default_rng([14, n])
+    x = rng.integers(-32768, 32768, n).astype(np.int16)
+    rirs = [rng.integers(-8, 9, t).astype(np.float64) for t in range(1, 17)]
+    got = levels_of(ctx, x, offsets_of((n,)), rirs)
+    for h, y in zip(rirs, got):
+        assert np.array_equal(bits(y), bits(reference(x, h) + 0.0)), (n, len(h))
+    assert np.array_equal(bits(got[16]), bits(x.astype(np.float64)))
+
+
 @pytest.mark.parametrize("kind", ["unit", "delay", "half"])
 def test_the_three_responses_anyone_can_check_by_eye(ctx, int_case, kind):
     wave, offsets, _ = int_case

@@ -146,6 +146,20 @@ def test_integer_data_is_numpys_convolution_bit_for_bit(ctx, int_case):
             assert np.array_equal(bits(cut(got, offsets, b)), bits(want)), (room_of, b)
 
 
+@pytest.mark.parametrize("n", [1, 3, BLK + 1])
+def test_every_tap_count_up_to_sixteen_is_numpys_convolution_bit_for_bit(ctx, n):
+    """sixteen utterances of n samples, utterance b in a room of b + 1 taps: 1 .. 16 taps are every combination of the walk's paired
+    turns (0 .. 2), its single step (0 / 1) and its 0 .. 3 last taps; BLK + 1 samples have a full tile and a tile of one output, 1
+    and 3 samples a lane with fewer outputs than it owns. Integer data as in int_case: sums below 16 * 8 * 32768 < 2^53"""
+    rng = np.random.default_rng([24, n])
+    offsets = offsets_of((n,) * 16)
+    wave = rng.integers(-32768, 32768, 16 * n).astype(np.int16)
+    rirs = [rng.integers(-8, 9, t).astype(np.float64) for t in range(1, 17)]
+    got = pick(ctx, wave, offsets, rirs, range(16))
+    for b, h in enumerate(rirs):
+        assert np.array_equal(bits(cut(got, offsets, b)), bits(reference(cut(wave, offsets, b), h) + 0.0)), (n, len(h))
+
+
 @pytest.mark.parametrize("dtype,mem", [(I16, HOST), (F64, HOST), (I16, DEV), (F64, DEV)])
 def test_every_utterance_is_its_level_of_the_sweep(ctx, int_case, float_rirs, float_levels, dtype, mem):
     wave, offsets, _ = int_case

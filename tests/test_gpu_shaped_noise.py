@@ -304,6 +304,20 @@ def test_noise_is_the_headers_formula(batch, frame_sweeps, name):
     print("taps", TAPS[name], "worst error / bound", worst)
 
 
+@pytest.mark.parametrize("n", [1, 3, 1025])
+def test_every_tap_count_up_to_sixteen_is_the_headers_formula(ctx, n):
+    """sixteen levels of 1 .. 16 taps: every combination of the walk's paired turns (0 .. 2), its single step (0 / 1) and its 0 .. 3
+    last taps; 1025 samples have a full tile and a tile of one output, 1 and 3 samples a lane with fewer outputs than it owns (the
+    samples are not zero, so that no sigma is and every level is filtered noise)"""
+    flat = np.random.default_rng([70, n]).integers(1000, 20000, n).astype(np.int16)
+    offsets = np.array([0, n], np.int64)
+    firs = [random_filter(t, 7) for t in range(1, 17)]
+    noisy, sigma = levels(ctx, flat, _lib.WAVE_I16, offsets, firs, snr=(3.0,) * 16)
+    assert (sigma[:16] > 0).all()
+    worst = check_formula(noisy, sigma, flat, offsets, firs)
+    print("n", n, "worst error / bound", worst)
+
+
 def test_a_span_that_crosses_two_tiles_and_wraps_below_zero(ctx):
     """2048 taps on 2500 samples: the span of the second tile starts inside the first, the first one's 2047 samples below zero"""
     flat, offsets = ragged_waves((2500,), seed=60)

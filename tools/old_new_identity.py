@@ -2,7 +2,7 @@
     python tools/old_new_identity.py run LIB OUT.json [KEEP_DIR] [--only=GROUP,...]    digests of every case's outputs with that
                                           library; with KEEP_DIR the outputs of the low-pass cases themselves are kept there (float64,
                                           ~1.3 GB); --only: the named groups alone (cnn_cases, entry_cases, sweep_cases, grad_cases,
-                                          figure_cases)
+                                          figure_cases, stage_cases)
     python tools/old_new_identity.py compare OLD.json NEW.json [OLD_KEEP_DIR NEW_KEEP_DIR]    the table "case: identical /
                                           differs"; with the kept outputs, for a case that differs, the largest difference
                                           relative to the row maximum (envelopes: per utterance and channel; scores and windows:
@@ -30,7 +30,13 @@ in batches of 32 - weights, accumulators, last gradient, loss, hits and iteratio
 case of tests/test_gpu_saliency_placement.py. The figure family (profiles/r37_a_old_new_identity.txt) on that case's utterances with
 spans given, hop 16 and hop = STEP, host and device memory: f2_eval_figure_batch and f2_eval_occlusion_batch (K = 2 patches) with
 every output, with each reduction alone and with none of them - every output given, window_offsets and the range in the digest;
-f2_score_track, f2_occlusion_map and f2_saliency_map on random rows."""
+f2_score_track, f2_occlusion_map and f2_saliency_map on random rows. The stage calls (profiles/r38_a_old_new_identity.txt):
+f2_reverb_levels, f2_reverb_pick, f2_shaped_noise_levels, f2_noise_pick, f2_lowpass_levels and f2_channel_mix_levels on utterances
+of 0, 1, 1023, 1024, 1025 and 3000 samples, int16 and float64, host and device memory, K = 3 with 1, 1025 and 2500 taps (rooms) and
+2, 1025 and 2048 taps (noise filters), sigma given and left out, all-dry / all-clean stages and a batch without samples;
+f2_input_batch_wet and a render_wet of the trainer with one pass of steps behind it; and per call the status and message of a
+fixed list of invalid calls - those of tests/test_gpu_reverb_levels.py, tests/test_gpu_reverb_pick.py, tests/test_gpu_noise_pick.py
+and ERROR_CASES of tests/test_gpu_shaped_noise.py, and calls with two things wrong at once (which one is named)."""
 import hashlib, json, os, sys
 import numpy as np
 
@@ -361,6 +367,170 @@ def figure_cases(ctx, res):
     print("figure cases done", flush=True)
 
 
+def stage_cases(ctx, res):
+    """the six stage calls (profiles/r38_a_old_new_identity.txt): outputs, sigma given and left out, and the status and message
+    of the invalid calls of tests/test_gpu_reverb_levels.py, test_gpu_reverb_pick.py, test_gpu_noise_pick.py (their CASES) and
+    tests/test_gpu_shaped_noise.py (ERROR_CASES)"""
+    from f2cnn_amd import _lib
+    from f2cnn_amd.gammatone import filters
+    from f2cnn_amd.model import F2CNNModel
+    from f2cnn_amd.trainer import Trainer
+    MEMS = (("host", _lib.MEM_HOST), ("device", _lib.MEM_DEVICE))
+    INV, UNS = _lib.F2_ERR_INVALID, _lib.F2_ERR_UNSUPPORTED
+    lens, K, CE = [0, 1, 1023, 1024, 1025, 3000], 3, 10
+    B = len(lens)
+    offs = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+    total = int(offs[-1])
+    rng = np.random.default_rng(38)
+    i16 = rng.integers(-20000, 20000, total).astype(np.int16)
+    rirs = [rng.standard_normal(t) * np.exp(-np.arange(t) / (t / 5.0 + 1)) for t in (1, 1025, 2500)]
+    firs = [h / np.sqrt(h @ h) for h in (rng.standard_normal(t) for t in (2, 1025, 2048))]
+    snr, seed = np.array([10.0, -3.0, 20.0]), 0x1234_5678_9ABC
+    ftaps, foffs = _lib._pack_firs(firs, K)
+    room_of, level_of = np.arange(B, dtype=np.int32) % (K + 1), (np.arange(B, dtype=np.int32) + 1) % (K + 1)
+    env = np.abs(rng.standard_normal(CE * total)) + 0.01
+    mix = rng.standard_normal((K, CE, CE)) * (np.abs(np.subtract.outer(np.arange(CE), np.arange(CE))) < 3)
+    cutoffs = np.array([8.0, 50.0, 400.0])
+
+    def both(name, inputs, outs, call):
+        for mname, mem in MEMS:
+            o = [np.zeros(n, dt) for dt, n in outs]
+            extra = call(mem, *inputs, *o) if mem == _lib.MEM_HOST else on_device(ctx, list(inputs) + o, lambda *p: call(mem, *p))
+            res[f"{name}, {mname} memory"] = digest(*o, *[np.asarray(e) for e in extra if e is not None])
+
+    for dname, dt, wave in (("int16", _lib.WAVE_I16, i16), ("float64", _lib.WAVE_F64, i16.astype(np.float64))):
+        both(f"f2_reverb_levels: {dname}", [wave], [(np.float64, (K + 1) * total)],
+             lambda mem, w, o: (ctx.reverb_levels(w, dt, offs, B, rirs, o, mem),))
+        both(f"f2_reverb_pick: {dname}", [wave], [(np.float64, total)], lambda mem, w, o: (ctx.reverb_pick(w, dt, offs, B, rirs, room_of, o, mem),))
+        both(f"f2_reverb_pick: {dname}, every utterance dry", [wave], [(np.float64, total)],
+             lambda mem, w, o: (ctx.reverb_pick(w, dt, offs, B, rirs, None, o, mem),))
+        both(f"f2_shaped_noise_levels: {dname}, sigma given", [wave], [(np.float64, (K + 1) * total)],
+             lambda mem, w, o: (ctx.shaped_noise_levels(w, dt, offs, B, snr, firs, seed, o, mem),))
+        both(f"f2_shaped_noise_levels: {dname}, sigma left out", [wave], [(np.float64, (K + 1) * total)], lambda mem, w, o: (
+            ctx.check(ctx.lib.f2_shaped_noise_levels(ctx.handle, _lib._ptr(w), dt, offs.ctypes.data, B, snr.ctypes.data, ftaps.ctypes.data,
+                                                     foffs.ctypes.data, K, seed, _lib._ptr(o), None, mem)),))
+        for sname, sg in (("given", True), ("left out", None)):
+            both(f"f2_noise_pick: {dname}, sigma {sname}", [wave], [(np.float64, total)],
+                 lambda mem, w, o: (ctx.noise_pick(w, dt, offs, B, snr, level_of, 7, seed, o, mem, sigma=sg),))
+            both(f"f2_noise_pick: {dname}, every utterance clean, sigma {sname}", [wave], [(np.float64, total)],
+                 lambda mem, w, o: (ctx.noise_pick(w, dt, offs, B, snr, None, 7, seed, o, mem, sigma=sg),))
+    both("f2_lowpass_levels", [env], [(np.float64, (K + 1) * CE * total)], lambda mem, e, o: (ctx.lowpass_levels(e, offs, B, CE, cutoffs, o, mem),))
+    both("f2_channel_mix_levels", [env], [(np.float64, (K + 1) * CE * total)], lambda mem, e, o: (ctx.channel_mix_levels(e, offs, B, CE, mix, o, mem),))
+    # empty batches: nothing written, sigma zeroed
+    zeros5, sig = np.zeros(B + 1, np.int64), np.full((K + 1) * B, 7.0)
+    ctx.shaped_noise_levels(None, _lib.WAVE_I16, zeros5, B, snr, firs, seed, None, _lib.MEM_HOST, sigma=sig)
+    sig2 = ctx.noise_pick(None, _lib.WAVE_I16, zeros5, B, snr, level_of, 0, seed, None, _lib.MEM_HOST, sigma=np.full(B, 7.0))
+    res["f2_shaped_noise_levels / f2_noise_pick: utterances without samples, sigma"] = digest(sig, sig2)
+    print("stage outputs done", flush=True)
+
+    # f2_input_batch_wet and a render_wet of the trainer on the utterances long enough for a window
+    wl = [3000, 2500, 1761]
+    woffs = np.concatenate([[0], np.cumsum(wl)]).astype(np.int64)
+    ww = rng.integers(-20000, 20000, int(woffs[-1])).astype(np.int16)
+    coefs = np.ascontiguousarray(filters.make_erb_filters(16000, filters.centre_freqs(16000, CE, 100)))
+    cs = [np.array([RADIUS * STEP, n - 1 - RADIUS * STEP], np.int64) for n in wl]
+    coffs = np.arange(0, 2 * len(wl) + 1, 2, dtype=np.int64)
+    rooms, levs = np.array([0, 3, 2], np.int32), np.array([1, 0, 3], np.int32)
+    both("f2_input_batch_wet: three utterances, K = 3 rooms, 3 noise levels", [ww], [(np.float32, 2 * len(wl) * R * CE)], lambda mem, w, o: (
+        ctx.input_batch_wet(w, _lib.WAVE_I16, woffs, coefs, len(wl), CE, True, 50.0, _lib.FFT_F32, coffs, np.concatenate(cs), RADIUS, STEP, True,
+                            rirs, rooms, snr, levs, 0, seed, o, mem),))
+    tr = Trainer(F2CNNModel.glorot(7, R, CE, zero_bias=False), lr=1e-3, decay=1e-6, drop=(0.0, 0.0, 0.0), seed=5, ctx=ctx)
+    tr.set_waves([ww[a:b] for a, b in zip(woffs[:-1], woffs[1:])], cs, [np.array([0, 1], np.uint8)] * len(wl), coefs, RADIUS, STEP, lpf=True)
+    tr.render_wet(rirs=rirs, room_of=rooms, snrs=snr, level_of=levs, seed=seed)
+    res["f2_trainer_render_wet: three utterances, the rendered windows"] = digest(*tr.windows())
+    tr.close()
+    print("wet windows done", flush=True)
+
+    # invalid calls: status and message
+    p = lambda a: None if a is None else a.ctypes.data
+    eo = np.array([0, 65, 67, 130], np.int64)
+    ew = np.arange(130).astype(np.int16)
+    bad0, dec = eo.copy(), eo.copy()
+    bad0[0], dec[2] = 1, dec[1] - 1
+    tap = {"rir": np.array([1.0, 0.5, 0.25, 1.0]), "ro": np.array([0, 3, 4], np.int64), "k": 2}
+    nan, inf = tap["rir"].copy(), tap["rir"].copy()
+    nan[3], inf[3] = np.nan, -np.inf
+    table_cases = [("K=65", dict(rir=np.ones(65), ro=np.arange(66, dtype=np.int64), k=65)), ("rir NULL", dict(rir=None)),
+                   ("rir_offsets NULL", dict(ro=None)), ("rir_offsets[0]=1", dict(ro=np.array([1, 3, 4], np.int64))),
+                   ("rir_offsets decreasing", dict(ro=np.array([0, 3, 2], np.int64))), ("no taps", dict(ro=np.array([0, 4, 4], np.int64))),
+                   ("tap nan", dict(rir=nan)), ("tap inf", dict(rir=inf)),
+                   ("32769 taps", dict(rir=np.full(32770, 1e-3), ro=np.array([0, 1, 32770], np.int64)))]
+    batch_cases = [("B<0", dict(nb=-1)), ("wave_dtype", dict(dt=2)), ("offsets NULL", dict(off=None)), ("offsets[0]=1", dict(off=bad0)),
+                   ("offsets decreasing", dict(off=dec)), ("wave NULL", dict(wave=None)), ("output NULL", dict(out=None)), ("mem_space", dict(mem=7)),
+                   # two things wrong at once: which one the call names
+                   ("B<0 and wave_dtype", dict(nb=-1, dt=2)), ("wave_dtype and mem_space", dict(dt=2, mem=7)),
+                   ("offsets decreasing and the call's own check", dict(off=dec, k=-1))]
+    out = np.zeros(3 * 130)
+
+    def invalid(name, call, cases):
+        rows = []
+        for cname, kw in cases:
+            rc = call(**kw)
+            rows.append(f"{cname}: {rc} {ctx.lib.f2_last_error(ctx.handle).decode()}")
+            assert rc != _lib.F2_OK, (name, cname)
+        res[f"{name}: {len(cases)} invalid calls, status and message"] = digest(np.frombuffer("\n".join(rows).encode(), np.uint8))
+
+    def levels_call(wave=ew, dt=_lib.WAVE_I16, off=eo, nb=3, rir=tap["rir"], ro=tap["ro"], k=2, out=out, mem=_lib.MEM_HOST):
+        return ctx.lib.f2_reverb_levels(ctx.handle, p(wave), dt, p(off), nb, p(rir), p(ro), k, p(out), mem)
+    big = 1 << 24
+    invalid("f2_reverb_levels", levels_call, [("K=0", dict(k=0))] + table_cases + [("levels x utterances", dict(
+        nb=big, off=np.zeros(big + 1, np.int64), rir=np.ones(64), ro=np.arange(65, dtype=np.int64), k=64))] + batch_cases)
+
+    room = np.array([0, 2, 1], np.int32)
+    r3, rm1 = room.copy(), room.copy()
+    r3[1], rm1[1] = 3, -1
+
+    def pick_call(wave=ew, dt=_lib.WAVE_I16, off=eo, nb=3, rir=tap["rir"], ro=tap["ro"], k=2, room=room, out=out, mem=_lib.MEM_HOST):
+        return ctx.lib.f2_reverb_pick(ctx.handle, p(wave), dt, p(off), nb, p(rir), p(ro), k, p(room), p(out), mem)
+    invalid("f2_reverb_pick", pick_call, [("K<0", dict(k=-1)), ("room 3", dict(room=r3)), ("room -1", dict(room=rm1))] + table_cases + batch_cases)
+
+    lev = np.array([0, 2, 1], np.int32)
+    high, neg = lev.copy(), lev.copy()
+    high[2], neg[1] = K + 1, -1
+    nsnr, isnr = snr.copy(), snr.copy()
+    nsnr[1], isnr[0] = np.nan, np.inf
+    sigma = np.zeros(4 * 3)
+
+    def noise_call(wave=ew, dt=_lib.WAVE_I16, off=eo, nb=3, s=snr, k=K, lv=lev, first=0, out=out, mem=_lib.MEM_HOST):
+        return ctx.lib.f2_noise_pick(ctx.handle, p(wave), dt, p(off), nb, p(s), k, p(lv), first, seed, p(out), p(sigma), mem)
+    invalid("f2_noise_pick", noise_call, [
+        ("wave_dtype", dict(dt=7)), ("mem_space", dict(mem=5)), ("mem_space async", dict(mem=_lib.MEM_HOST_ASYNC)), ("offsets NULL", dict(off=None)),
+        ("offsets[0]=1", dict(off=bad0)), ("offsets decreasing", dict(off=dec)), ("B<0", dict(nb=-1)), ("snr nan", dict(s=nsnr)),
+        ("snr inf", dict(s=isnr)), ("K<0", dict(k=-1)), ("snr NULL", dict(s=None)), ("level high", dict(lv=high)), ("level negative", dict(lv=neg)),
+        ("levels x utterances", dict(k=2 ** 30)), ("utterance number", dict(first=2 ** 32 - 3 + 1)), ("wave NULL", dict(wave=None)),
+        ("output NULL", dict(out=None)), ("B<0 and wave_dtype", dict(nb=-1, dt=7)), ("B<0 and mem_space", dict(nb=-1, mem=5)),
+        ("offsets decreasing and level high", dict(off=dec, lv=high)), ("offsets NULL and K<0", dict(off=None, k=-1))])
+
+    f3 = [np.ones(1), np.ones(3) / np.sqrt(3), np.ones(2) / np.sqrt(2)]
+    fir, fo = _lib._pack_rirs(f3)
+    finf = fir.copy()
+    finf[2] = np.inf
+    many = _lib._pack_rirs([np.ones(1), np.ones(2049) / np.sqrt(2049), np.ones(2)])
+    k65 = _lib._pack_rirs([np.ones(1)] * 65)
+
+    def shaped_call(wave=ew, dt=_lib.WAVE_I16, off=eo, nb=3, s=snr, fir=fir, fo=fo, k=K, out=np.zeros(4 * 130), mem=_lib.MEM_HOST):
+        return ctx.lib.f2_shaped_noise_levels(ctx.handle, p(wave), dt, p(off), nb, p(s), p(fir), p(fo), k, seed, p(out), p(sigma), mem)
+    invalid("f2_shaped_noise_levels", shaped_call, [
+        ("K=0", dict(k=0)), ("snr NULL", dict(s=None)), ("snr nan", dict(s=nsnr)), ("offsets decreasing", dict(off=dec)), ("fir NULL", dict(fir=None)),
+        ("fir_offsets NULL", dict(fo=None)), ("fir_offsets[0] != 0", dict(fo=fo + 1, fir=np.concatenate([[0.5], fir]))),
+        ("fir_offsets decreasing", dict(fo=np.array([0, 4, 3, 6], np.int64))), ("a level with no taps", dict(fo=np.array([0, 1, 6, 6], np.int64))),
+        ("a tap that is not finite", dict(fir=finf)), ("too many taps", dict(fir=many[0], fo=many[1])),
+        ("K=65", dict(k=65, s=np.zeros(65), fir=k65[0], fo=k65[1]))] + [c for c in batch_cases if "own check" not in c[0]] + [
+        ("offsets decreasing and snr nan", dict(off=dec, s=nsnr))])
+
+    def env_call(f):
+        return lambda env=env[:CE * 130], off=eo, nb=3, c=CE, k=K, out=np.zeros(4 * CE * 130), mem=_lib.MEM_HOST, **kw: f(env, off, nb, c, k, out, mem, **kw)
+    env_cases = [("B<0", dict(nb=-1)), ("C=0", dict(c=0)), ("mem_space", dict(mem=7)), ("mem_space async", dict(mem=_lib.MEM_HOST_ASYNC)),
+                 ("offsets NULL", dict(off=None)), ("offsets decreasing", dict(off=dec)), ("K=0", dict(k=0)), ("K=65", dict(k=65)),
+                 ("env NULL", dict(env=None)), ("output NULL", dict(out=None)), ("offsets decreasing and K=0", dict(off=dec, k=0))]
+    invalid("f2_lowpass_levels", env_call(lambda e, off, nb, c, k, o, mem, cut=np.resize(cutoffs, 65): ctx.lib.f2_lowpass_levels(
+        ctx.handle, p(e), p(off), nb, c, p(cut), k, p(o), mem)), env_cases + [("cutoff 9000 Hz", dict(cut=np.array([8.0, 9000.0, 50.0]))), ("cutoffs NULL", dict(cut=None))])
+    invalid("f2_channel_mix_levels", env_call(lambda e, off, nb, c, k, o, mem, m=np.resize(mix, (65, CE, CE)): ctx.lib.f2_channel_mix_levels(
+        ctx.handle, p(e), p(off), nb, c, p(m), k, p(o), mem)), env_cases + [("weight nan", dict(m=np.full((K, CE, CE), np.nan))), ("mix NULL", dict(m=None)),
+                                                                          ("C=513", dict(c=513))])
+    print("stage cases done", flush=True)
+
+
 def keep_arrays(keep, key, arrays, lens=None, C=None, envelopes=()):
     """the outputs of one case under KEEP_DIR: a<i>.npy each; `envelopes` = the indices of the arrays laid out
     [utterance][channel][sample] for utterances of `lens` samples and C channels"""
@@ -443,7 +613,7 @@ def run(lib, out, keep=None, only=None):
             if lpf:
                 keep_arrays(keep, f"f2_input_batch: {tag}", [win])
             print(tag, "done", flush=True)
-    for group in (cnn_cases, entry_cases, sweep_cases, grad_cases, figure_cases):
+    for group in (cnn_cases, entry_cases, sweep_cases, grad_cases, figure_cases, stage_cases):
         if not only or group.__name__ in only.split(","):
             group(ctx, res)
     ctx.close()

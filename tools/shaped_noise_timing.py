@@ -12,6 +12,9 @@ Prints one JSON line; --out FILE also writes it. Diagnostic."""
 import argparse, json, os, socket, statistics, sys, time
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+if os.environ.get("F2CNN_PROBE_LIB"):   # another build of the library, as for noise_sweep_timing.py
+    from f2cnn_amd import build
+    build.LIB_PATH = os.path.abspath(os.environ["F2CNN_PROBE_LIB"])
 from f2cnn_amd import _lib
 from f2cnn_amd.gammatone import filters
 from f2cnn_amd.model import F2CNNModel

@@ -41,9 +41,10 @@ def fmas(n, taps):
 
 def child(a):
     """One build's measurements, one JSON line on stdout"""
-    if a.lib:
+    lib = a.lib or os.environ.get("F2CNN_PROBE_LIB")   # (the latter: another build measured as the tree is, render_wet and the pick kernel too)
+    if lib:
         from f2cnn_amd import build
-        build.LIB_PATH = os.path.abspath(a.lib)
+        build.LIB_PATH = os.path.abspath(lib)
     from f2cnn_amd import _lib
     from f2cnn_amd.gammatone import filters
     from f2cnn_amd.model import F2CNNModel
