@@ -120,6 +120,10 @@ SIGNATURES = {
     "f2_shaped_noise_levels": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _i, C.c_uint64, _vp, _vp, _i]),
     "f2_eval_shaped_noise_sweep": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _d, _i, _i, _i, _i, _vp, _vp, _vp, _i, C.c_uint64, _vp,
                                         _vp, _vp, _vp, _vp, _vp, _i]),
+    "f2_shaped_noise_pick": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _i, _vp, C.c_uint32, C.c_uint64, _vp, _vp, _i]),
+    "f2_input_batch_coloured": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i, _i, _d, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp,
+                                     _i, _vp, C.c_uint32, C.c_uint64, _vp, _i]),
+    "f2_trainer_render_coloured": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, C.c_uint64]),
 }
 TRAINER_WHAT = {"weights": 0, "accumulators": 1, "gradient": 2}   # F2_TRAINER_* of f2_trainer_get
 
@@ -420,6 +424,40 @@ class Context:
                                                step, int(bool(normalize)), _ptr(taps) if len(taps) else None, _ptr(rir_offsets),
                                                len(rir_offsets) - 1, _ptr(room), _ptr(snr) if len(snr) else None, len(snr), _ptr(lev),
                                                int(first_utterance), int(seed) & (2 ** 64 - 1), _ptr(windows), mem_space))
+
+    def shaped_noise_pick(self, wave, wave_dtype, offsets, B, snr_db, firs, level_of, first_utterance, seed, noisy, mem_space,
+                          sigma=None):
+        """The batch with one coloured-noise level per utterance (see f2_shaped_noise_pick): utterance b at snr_db[level_of[b]]
+        under the filter firs[level_of[b]] (a sequence of 1-D float64 arrays, one per level, always host arrays; None: no taps are
+        handed over), or clean where level_of[b] == len(snr_db); level_of None: all clean. wave / noisy are numpy arrays or device
+        pointers, by mem_space. sigma: True for a new (B) float64 array, an array to fill, or None. Returns sigma (or None)."""
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        snr, lev = _noise_levels(snr_db, level_of)
+        taps, fir_offsets = _colours(firs, len(snr))
+        if sigma is True:
+            sigma = np.zeros(int(B), np.float64)
+        self.check(self.lib.f2_shaped_noise_pick(self.handle, _ptr(wave), wave_dtype, _ptr(offsets), int(B),
+                                                 _ptr(snr) if len(snr) else None, _ptr(taps), _ptr(fir_offsets), len(snr), _ptr(lev),
+                                                 int(first_utterance), int(seed) & (2 ** 64 - 1), _ptr(noisy), _ptr(sigma), mem_space))
+        return sigma
+
+    def input_batch_coloured(self, wave, wave_dtype, offsets, coefs, B, Cn, lpf, cutoff, precision, center_offsets, centers, radius,
+                             step, normalize, rirs, room_of, snr_db, firs, level_of, first_utterance, seed, windows, mem_space):
+        """input_batch on the batch as reverb_pick, then shaped_noise_pick leave it, neither waveform leaving the device; firs None:
+        input_batch_wet. See f2_input_batch_coloured."""
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        center_offsets = np.ascontiguousarray(center_offsets, dtype=np.int64)
+        centers = np.ascontiguousarray(centers, dtype=np.int64)
+        snr, lev = _noise_levels(snr_db, level_of)
+        fir_taps, fir_offsets = _colours(firs, len(snr))
+        taps, rir_offsets, room = _rooms(rirs, room_of)
+        self.check(self.lib.f2_input_batch_coloured(self.handle, _ptr(wave), wave_dtype, _ptr(offsets), _ptr(coefs), int(B), Cn,
+                                                    int(bool(lpf)), float(cutoff), precision, _ptr(center_offsets), _ptr(centers),
+                                                    radius, step, int(bool(normalize)), _ptr(taps) if len(taps) else None,
+                                                    _ptr(rir_offsets), len(rir_offsets) - 1, _ptr(room),
+                                                    _ptr(snr) if len(snr) else None, _ptr(fir_taps), _ptr(fir_offsets), len(snr),
+                                                    _ptr(lev), int(first_utterance), int(seed) & (2 ** 64 - 1), _ptr(windows),
+                                                    mem_space))
 
     def cnn_create(self, tensors, rows, channels):
         """tensors: 12 contiguous float32 arrays in Keras layouts (see include/f2cnn_hip.h). Returns a handle."""
@@ -841,6 +879,17 @@ class Context:
                                                   len(rir_offsets) - 1, _ptr(room), _ptr(snr) if len(snr) else None, len(snr),
                                                   _ptr(lev), int(seed) & (2 ** 64 - 1)))
 
+    def trainer_render_coloured(self, handle, rirs=(), room_of=None, snr_db=(), firs=None, level_of=None, seed=0):
+        """The training windows from the stored waves, utterance b in room rirs[room_of[b]] and under noise of the colour
+        firs[level_of[b]] at snr_db[level_of[b]]; firs None: trainer_render_wet (see f2_trainer_render_coloured)"""
+        snr, lev = _noise_levels(snr_db, level_of)
+        fir_taps, fir_offsets = _colours(firs, len(snr))
+        taps, rir_offsets, room = _rooms(rirs, room_of)
+        self.check(self.lib.f2_trainer_render_coloured(self.handle, handle, _ptr(taps) if len(taps) else None, _ptr(rir_offsets),
+                                                       len(rir_offsets) - 1, _ptr(room), _ptr(snr) if len(snr) else None,
+                                                       _ptr(fir_taps), _ptr(fir_offsets), len(snr), _ptr(lev),
+                                                       int(seed) & (2 ** 64 - 1)))
+
     def trainer_get_windows(self, handle, first, count, shape):
         """Rows first .. first + count - 1 of the training set: (count, *shape) float32 windows and (count) uint8 labels"""
         x = np.empty((int(count),) + tuple(shape), np.float32)
@@ -953,6 +1002,14 @@ def _pack_firs(firs, K):
     if len(firs) != K:
         raise ValueError("{} filters for {} noise levels (one per level is needed)".format(len(firs), K))
     return _pack_rirs(firs)
+
+
+def _colours(firs, K):
+    """(taps, fir_offsets) for the calls that give every utterance a coloured level of its own, (None, None) without filters"""
+    if firs is None:
+        return None, None
+    taps, fir_offsets = _pack_firs(firs, K)
+    return (taps if len(taps) else None), fir_offsets
 
 
 def _rooms(rirs, room_of):

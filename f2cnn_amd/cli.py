@@ -29,6 +29,12 @@ package implements:
                                                              every epoch, measured ones fixed - or left dry; room first, then
                                                              noise at an SNR of the reverberant signal; the TEST files are also
                                                              validated once per room; not in the reference)
+    python -m f2cnn_amd cnn train --engine hip --from-wav --augment-snrs 20,10 --augment-colours white,pink,speech,like:babble.wav [--augment-noise-taps N] [--seed S]
+                                                            (a noise level is a pair (colour, SNR), colour-major over the SNRs as
+                                                             in noisesweep --colours, at most 64: every epoch each TRAIN file is
+                                                             rendered under one of them or clean, the noise filtered on the
+                                                             device; the TEST files are validated once per pair; needs
+                                                             --augment-snrs; not in the reference)
     python -m f2cnn_amd cnn test [--input/-i NPY] [--label/-l CSV] [--model/-m NPZ] [--by set|region|speaker|phoneme] [--rows test|train|all]
                                                             (loss, accuracy and the 2 x 2 counts of a saved model on the labelled
                                                              windows, per value of a label column, in one device pass; writes
@@ -255,6 +261,23 @@ def noise_taps_argument(text):
     return taps
 
 
+def augment_colours_argument(text):
+    """--augment-colours: as --colours"""
+    try:
+        return colours_argument(text)
+    except argparse.ArgumentTypeError:
+        raise argparse.ArgumentTypeError("--augment-colours takes a comma-separated list of {}, like:<recording.wav> or "
+                                         "fir:<taps.npy>, not {!r}".format(', '.join(NOISE_COLOURS), text))
+
+
+def augment_noise_taps_argument(text):
+    """--augment-noise-taps: as --noise-taps"""
+    try:
+        return noise_taps_argument(text)
+    except argparse.ArgumentTypeError:
+        raise argparse.ArgumentTypeError("--augment-noise-taps takes an odd, positive number of taps, not {!r}".format(text))
+
+
 def build_parser():
     parser = argparse.ArgumentParser(prog="f2cnn_amd", description="F2CNN hot path on MI355X.")
     parser.add_argument('--configure', action='store_true', help='write configF2CNN.conf with default values')
@@ -317,6 +340,11 @@ def build_parser():
     c.add_argument('--augment-rirs', action='store', type=augment_rirs_argument, dest='augment_rirs', default=argparse.SUPPRESS,
                    help="train --engine hip --from-wav: comma-separated mono WAV files with measured impulse responses, further rooms "
                         "of the draw")
+    c.add_argument('--augment-colours', action='store', type=augment_colours_argument, dest='augment_colours', default=argparse.SUPPRESS,
+                   help="train --engine hip --from-wav --augment-snrs: comma-separated noise colours, as noisesweep's --colours; every "
+                        "epoch each file is rendered under one (colour, SNR) pair or clean")
+    c.add_argument('--augment-noise-taps', action='store', type=augment_noise_taps_argument, dest='augment_noise_taps',
+                   default=argparse.SUPPRESS, help="train --augment-colours: taps of the designed noise filters, odd (default 1025, at most 2047)")
     # (absent from the parsed arguments unless given: the commands parse as before without them)
     c.add_argument('--colours', action='store', type=colours_argument, dest='colours', default=argparse.SUPPRESS,
                    help="noisesweep: comma-separated noise colours - white, pink, brown, speech, like:<recording.wav> (the long-term "
@@ -486,6 +514,23 @@ def rooms_refusal(args):
     return None
 
 
+def augment_colours_refusal(args):
+    """The same for --augment-colours / --augment-noise-taps, asked once from_wav_refusal has nothing to say"""
+    given = [opt for attr, opt in (('augment_colours', '--augment-colours'), ('augment_noise_taps', '--augment-noise-taps')) if attr in args]
+    if not given:
+        return None
+    if args.cnn_command != 'train':
+        return "{} only applies to 'cnn train'".format(given[0])
+    if 'augment_colours' not in args:
+        return "--augment-noise-taps belongs to --augment-colours"
+    if 'augment_snrs' not in args:
+        return "--augment-colours needs --augment-snrs: a colour is drawn together with the SNR it is added at"
+    if len(args.augment_colours) * len(args.augment_snrs) > NOISE_LEVELS_MAX:
+        return "training takes at most {} noise levels, not {} colours x {} SNRs = {}".format(
+            NOISE_LEVELS_MAX, len(args.augment_colours), len(args.augment_snrs), len(args.augment_colours) * len(args.augment_snrs))
+    return None
+
+
 def sweep_refusal(args, no_lpf, instead):
     """says which option the sweep does not take, if one was given (an option that was not given is absent, None or False)"""
     for attr, option, why in (('CUTOFF', '--lpf', no_lpf), ('figure', '--figure', instead), ('occlusion', '--occlusion', instead),
@@ -531,7 +576,7 @@ def main(argv=None):
         if getattr(report, "exit_status", 0):          # some files could not be processed (the others were)
             return report.exit_status
     elif 'cnn_command' in args:
-        refusal = from_wav_refusal(args) or rooms_refusal(args) or colours_refusal(args)
+        refusal = from_wav_refusal(args) or rooms_refusal(args) or augment_colours_refusal(args) or colours_refusal(args)
         if refusal:
             print(refusal)
             return 1
@@ -546,6 +591,10 @@ def main(argv=None):
             if 'augment_t60' in args or 'augment_rirs' in args:
                 rooms = dict(t60s=tuple(getattr(args, 'augment_t60', ())), rirs=tuple(getattr(args, 'augment_rirs', ())),
                              drr_db=getattr(args, 'drr', 0.0))
+            if 'augment_colours' in args:                      # (likewise)
+                rooms['colours'] = tuple(args.augment_colours)
+                if 'augment_noise_taps' in args:
+                    rooms['noise_taps'] = args.augment_noise_taps
             TrainFromWav(labelFile=labelFile, LPF=args.CUTOFF is not None, CUTOFF=args.CUTOFF, snrs=tuple(getattr(args, 'augment_snrs', ())),
                          seed=args.seed, **rooms)
             return 0

@@ -325,6 +325,7 @@ const opt_entry kOptions[] = {
     {"cnn_ws_dense", &f2_ctx::opt_cnn_ws_dense, nullptr, 0, 1},
     {"gather_blocked", &f2_ctx::opt_gather_blocked, nullptr, 0, 1},
     {"reverb_pick_sort", &f2_ctx::opt_reverb_pick_sort, nullptr, 0, 1},
+    {"noise_pick_sort", &f2_ctx::opt_noise_pick_sort, nullptr, 0, 1},
 };
 const opt_entry* find_option(const char* key) {
     if (!key) return nullptr;

@@ -729,6 +729,7 @@ struct f2_trainer {
     bool have_waves = false;
     f2_scratch wave, centers;   // the waves; [the centres | the utterance of every window, counted inside its group]
     f2_scratch rir;             // f2_trainer_render_wet: [rir_offsets | taps] of the render in flight, uploaded once for all groups
+    f2_scratch fir;             // f2_trainer_render_coloured: [fir_offsets | taps] of the render in flight, likewise
     std::vector<int64_t> offsets, center_offsets;
     std::vector<double> coefs;
     int wave_dtype = 0, B = 0, lpf = 0, fft_precision = 0, radius = 0, step = 0, group = 1;
@@ -914,12 +915,15 @@ int f2_trainer_set_waves(f2_ctx* ctx, f2_trainer* t, const void* wave, int wave_
     return F2_OK;
 }
 
-int f2_trainer_render_wet(f2_ctx* ctx, f2_trainer* t, const double* rir, const int64_t* rir_offsets, int Kr, const int32_t* room_of,
-                          const double* snr_db, int K, const int32_t* level_of, uint64_t seed) {
+int f2_trainer_render_coloured(f2_ctx* ctx, f2_trainer* t, const double* rir, const int64_t* rir_offsets, int Kr, const int32_t* room_of,
+                               const double* snr_db, const double* fir, const int64_t* fir_offsets, int K, const int32_t* level_of,
+                               uint64_t seed) {
     F2_TRY(f2_check_ctx(ctx));
     F2_TRY(check_trainer(ctx, t));
     F2_CHECK(ctx, t->have_waves, F2_ERR_INVALID, "the trainer has no waves to render from (f2_trainer_set_waves)");
-    F2_TRY(f2_check_noise_pick(ctx, t->B, {snr_db, K, level_of, 0, seed}));
+    f2_noise_pick_args Nall = {snr_db, K, level_of, 0, seed, fir, fir_offsets};
+    F2_TRY(f2_check_noise_pick(ctx, t->B, Nall));
+    F2_TRY(f2_check_noise_colours(ctx, t->B, &Nall, false));
     f2_reverb_pick_args R = {rir, rir_offsets, Kr, room_of, nullptr, nullptr};
     F2_TRY(f2_check_reverb_pick(ctx, t->B, R));
     if (t->n == 0) return F2_OK;
@@ -933,6 +937,13 @@ int f2_trainer_render_wet(f2_ctx* ctx, f2_trainer* t, const double* rir, const i
         F2_TRY(f2_upload_async(ctx, (char*)t->rir.ptr + obytes, rir, sizeof(double) * (size_t)rir_offsets[Kr]));
         R.d_rir_off = (const int64_t*)t->rir.ptr, R.d_rir = (const double*)((const char*)t->rir.ptr + obytes);
     }
+    if (Nall.coloured()) {   // ... and so do the filters of the noise
+        const size_t obytes = sizeof(int64_t) * ((size_t)K + 1);
+        F2_TRY(f2_reserve(ctx, t->fir, obytes + sizeof(double) * (size_t)fir_offsets[K]));
+        F2_TRY(f2_upload_async(ctx, t->fir.ptr, fir_offsets, obytes));
+        F2_TRY(f2_upload_async(ctx, (char*)t->fir.ptr + obytes, fir, sizeof(double) * (size_t)fir_offsets[K]));
+        Nall.d_fir_off = (const int64_t*)t->fir.ptr, Nall.d_fir = (const double*)((const char*)t->fir.ptr + obytes);
+    }
     F2_HIP(ctx, hipMemsetAsync(ctx->flags.ptr, 0, sizeof(int), ctx->stream));
     std::vector<int64_t> off;
     // group after group onto the stream, each into its rows of x; one wait at the end
@@ -942,7 +953,8 @@ int f2_trainer_render_wet(f2_ctx* ctx, f2_trainer* t, const double* rir, const i
         if (nw == 0) continue;
         off.resize((size_t)nb + 1);
         for (int b = 0; b <= nb; ++b) off[(size_t)b] = t->offsets[(size_t)b0 + b] - t->offsets[(size_t)b0];
-        const f2_noise_pick_args N = {snr_db, K, level_of ? level_of + b0 : nullptr, (uint32_t)b0, seed};
+        f2_noise_pick_args N = Nall;   // (a group whose utterances are all clean keeps the colours: its tiles copy)
+        N.level_of = level_of ? level_of + b0 : nullptr, N.first_utterance = (uint32_t)b0;
         f2_reverb_pick_args Rg = R;
         if (!R.dry()) Rg.room_of = room_of + b0;
         F2_TRY(f2_launch_noisy_windows(ctx, (const char*)t->wave.ptr + ws * (size_t)t->offsets[(size_t)b0], t->wave_dtype, off.data(),
@@ -953,6 +965,12 @@ int f2_trainer_render_wet(f2_ctx* ctx, f2_trainer* t, const double* rir, const i
     F2_HIP(ctx, hipStreamSynchronize(ctx->stream));
     F2_CHECK(ctx, !ctx->host_flags[0], F2_ERR_NONPOSITIVE, "values must all be positive (normalizeInput)");
     return F2_OK;
+}
+
+// the render under white noise: the same code, whose noise stage is then k_noise_pick
+int f2_trainer_render_wet(f2_ctx* ctx, f2_trainer* t, const double* rir, const int64_t* rir_offsets, int Kr, const int32_t* room_of,
+                          const double* snr_db, int K, const int32_t* level_of, uint64_t seed) {
+    return f2_trainer_render_coloured(ctx, t, rir, rir_offsets, Kr, room_of, snr_db, nullptr, nullptr, K, level_of, seed);
 }
 
 // the render without rooms: the same code, whose reverberant stage is then skipped altogether

@@ -136,7 +136,8 @@ struct f2_ctx {
     int opt_cnn_ws = 1;                   // ... with the weights of each wave's role held in registers (f2_cnn_ws.hip; windows of 10 / 11 rows)
     int opt_cnn_ws_dense = 1;             // ... and dense1 with 96 windows per weight fragment, loads waited for by hand (k_dense1_ws)
     int opt_reverb_pick_sort = 1;         // k_reverb_pick's tile list: most taps first (0: utterance by utterance; the same results)
-    int opt_gather_blocked = 1;           // every-sample windows: logarithm once per sample, blocks of 32 windows (0: one workgroup per window)
+    int opt_noise_pick_sort = 1;          // k_shaped_noise_pick's tile list: most taps first (0: utterance by utterance; the same results)
+    int opt_gather_blocked = 1;          // every-sample windows: logarithm once per sample, blocks of 32 windows (0: one workgroup per window)
     int opt_env_plan4 = 0;                // four-pass plan for every 1 s row (default: three passes where measured faster)
     // pinned staging of small host -> device uploads (f2_upload_async): a ring of page-locked memory the copies read from,
     // so that a call with device pointers only enqueues (the caller's / a local's array is copied on the host at once)
@@ -253,6 +254,28 @@ int f2_check_taps(f2_ctx* ctx, const double* taps, const int64_t* offsets, int K
 // (F2_ERR_UNSUPPORTED from 2^31 on: "<what> needs <count> workgroups<per> (at most 2^31 - 1)").
 int64_t f2_tile_table(const int64_t* h_offsets, int B, int block, std::vector<int64_t>* first = nullptr);
 int f2_check_workgroups(f2_ctx* ctx, int64_t count, const char* what, const char* per);
+// The tile list of a kernel whose grid is the tiles alone (k_reverb_pick, k_shaped_noise_pick): one entry utterance << 32 | tile
+// per tile of `block` outputs, in (utterance, tile) order; with `sorted`, most expensive first by cost(b, n_b, tile), ties in that
+// order (a stable sort), so that the tiles that run longest do not start last. What the kernels compute does not depend on the order.
+template <class Cost>
+void f2_tile_list(const int64_t* h_offsets, int B, int block, bool sorted, std::vector<int64_t>* tiles, Cost cost) {
+    tiles->clear();
+    std::vector<int32_t> costs;
+    for (int b = 0; b < B; ++b) {
+        const int64_t n = h_offsets[b + 1] - h_offsets[b], nt = (n + block - 1) / block;
+        for (int64_t i = 0; i < nt; ++i) {
+            tiles->push_back((int64_t)b << 32 | i);
+            if (sorted) costs.push_back(cost(b, n, i));
+        }
+    }
+    if (!sorted) return;
+    std::vector<int32_t> idx(tiles->size());
+    for (size_t i = 0; i < idx.size(); ++i) idx[i] = (int32_t)i;
+    std::stable_sort(idx.begin(), idx.end(), [&](int32_t a, int32_t c) { return costs[(size_t)a] > costs[(size_t)c]; });
+    std::vector<int64_t> out(tiles->size());
+    for (size_t i = 0; i < idx.size(); ++i) out[i] = (*tiles)[(size_t)idx[i]];
+    tiles->swap(out);
+}
 // non-NULL, weights on the context's device, built for rows x C windows (rows == 0: the call has no window shape of its own)
 int f2_check_cnn(f2_ctx* ctx, const f2_cnn* cnn, int rows, int C);
 // *d_wave = the caller's pointer for F2_MEM_DEVICE, else ctx->stage_in after an asynchronous copy of `total` samples into it
@@ -302,7 +325,7 @@ struct f2_meta_carve {
         void* slot;      // the T* to set
         size_t bytes;
         bool wide;
-    } items[8];
+    } items[12];
     int n = 0;
     template <class T>
     void add(T** p, size_t count) {
@@ -567,21 +590,47 @@ int f2_launch_noise_levels(f2_ctx* ctx, const void* d_wave, int wave_dtype, cons
 int f2_launch_noise_pick(f2_ctx* ctx, const void* d_wave, int wave_dtype, const int64_t* d_offsets, const double* d_lin,
                          const int32_t* d_level, int B, int K, int64_t total, uint32_t first_utterance, uint64_t seed, double* d_sigma,
                          double* d_out);
+// ... and its first launch alone (k_noise_pick_sigma), for a stage whose second kernel is another (k_shaped_noise_pick)
+int f2_launch_noise_pick_sigma(f2_ctx* ctx, const void* d_wave, int wave_dtype, const int64_t* d_offsets, const double* d_lin,
+                               const int32_t* d_level, int B, int K, double* d_sigma);
 // f2_pipeline.hip, the driver f2_input_batch_noisy and f2_trainer_render share: the B utterances at d_wave (device, offsets from 0
 // on the host) through the noise kernels into ctx->levels, then f2_input_batch's envelopes and gather on that float64 buffer, the
 // windows written to d_windows (device). The centres and the utterance of every window (counted inside this batch) are either on
 // the device already (lists_on_device) or host arrays that go up behind the envelope launches, as in f2_input_batch. Enqueues only; the gather ORs into word 0 of ctx->flags, which the caller resets before and reads after. The arguments
 // have passed f2_check_noise_pick and f2_input_batch's checks. With `rooms` (passed f2_check_reverb_pick) that are not dry, the
 // utterances go through f2_launch_reverb_pick into ctx->wet first and the noise kernels read that float64 buffer.
+// A coloured stage (fir != NULL, passed f2_check_noise_colours) filters the deviates of level l with the taps fir + fir_offsets[l]
+// (host, K + 1 offsets) through k_shaped_noise_pick instead of k_noise_pick; sigma is k_noise_pick_sigma's in both.
+// d_fir / d_fir_off: device copies that are up already (a render uploads them once for all its groups), or NULL.
 struct f2_noise_pick_args {
     const double* snr_db;
     int K;
     const int32_t* level_of;
     uint32_t first_utterance;
     uint64_t seed;
+    const double* fir = nullptr;
+    const int64_t* fir_offsets = nullptr;
+    const double* d_fir = nullptr;
+    const int64_t* d_fir_off = nullptr;
     bool clean() const { return K == 0 || !level_of; }
+    bool coloured() const { return fir && !clean(); }
 };
 int f2_check_noise_pick(f2_ctx* ctx, int B, const f2_noise_pick_args& N);
+// The colours of a noise stage that passed f2_check_noise_pick, before anything is launched. Where every utterance is clean
+// (N->clean(), or every level_of entry is K) no tap is read: fir and fir_offsets are cleared and never looked at. Otherwise a NULL
+// fir is the white stage, or with need_fir (f2_shaped_noise_pick) F2_ERR_INVALID; a fir passes f2_check_fir_taps.
+int f2_check_noise_colours(f2_ctx* ctx, int B, f2_noise_pick_args* N, bool need_fir);
+// The coloured kernel of a stage (f2_noise_shaped.hip): f2_shaped_pick_meta names the tile list and, unless N.d_fir is given, the
+// taps in the call's f2_meta_carve; the launch builds the list (option "noise_pick_sort": most taps first), uploads and runs
+// k_shaped_noise_pick with the stage's d_level (B int32) and d_sigma (B, written by f2_launch_noise_pick_sigma on the stream).
+struct f2_shaped_pick_arrays {
+    int64_t *d_tiles = nullptr, *d_fir_off = nullptr;   // one entry per tile: utterance << 32 | tile; K + 1 tap offsets
+    double* d_fir = nullptr;
+};
+void f2_shaped_pick_meta(f2_meta_carve* meta, int B, const int64_t* h_offsets, const f2_noise_pick_args& N, f2_shaped_pick_arrays* A);
+int f2_launch_shaped_noise_pick(f2_ctx* ctx, const void* d_wave, int wave_dtype, const int64_t* d_offsets, const int64_t* h_offsets, int B,
+                                const f2_noise_pick_args& N, const f2_shaped_pick_arrays& A, const int32_t* d_level,
+                                const double* d_sigma, double* d_out);
 // The argument checks of f2_input_batch, and behind them f2_check_noise_pick when the call has a noise stage (noise != NULL), all
 // before anything is launched. `windows`: where the windows go (only tested for NULL). *n_windows == 0 on F2_OK: an empty call.
 // win_utt: the utterance of every window.
@@ -669,6 +718,8 @@ struct f2_shaped_arrays {
     double* d_fir = nullptr;                            // fir_offsets[K] taps
 };
 int f2_check_fir(f2_ctx* ctx, const double* snr_db, const double* fir, const int64_t* fir_offsets, int K);
+// ... its checks of fir / fir_offsets alone, behind a caller's own checks of K and snr_db (`who` opens the NULL message)
+int f2_check_fir_taps(f2_ctx* ctx, const double* fir, const int64_t* fir_offsets, int K, const char* who);
 void f2_shaped_meta(f2_meta_carve* meta, int B, const int64_t* fir_offsets, int K, f2_shaped_arrays* A);
 int f2_launch_shaped_noise_levels(f2_ctx* ctx, const void* d_wave, int wave_dtype, const int64_t* d_offsets, const int64_t* h_offsets,
                                   int B, const double* snr_db, const double* fir, const int64_t* fir_offsets, int K, uint64_t seed,

@@ -189,18 +189,23 @@ int f2_launch_noise_levels(f2_ctx* ctx, const void* d_wave, int wave_dtype, cons
     return F2_OK;
 }
 
+int f2_launch_noise_pick_sigma(f2_ctx* ctx, const void* d_wave, int wave_dtype, const int64_t* d_offsets, const double* d_lin,
+                               const int32_t* d_level, int B, int K, double* d_sigma) {
+    if (B == 0) return F2_OK;
+    if (wave_dtype == F2_WAVE_I16)
+        k_noise_pick_sigma<int16_t><<<dim3(B), dim3(SIGMA_THREADS), 0, ctx->stream>>>((const int16_t*)d_wave, d_offsets, d_lin, d_level, K, d_sigma);
+    else
+        k_noise_pick_sigma<double><<<dim3(B), dim3(SIGMA_THREADS), 0, ctx->stream>>>((const double*)d_wave, d_offsets, d_lin, d_level, K, d_sigma);
+    F2_HIP(ctx, hipGetLastError());
+    return F2_OK;
+}
+
 int f2_launch_noise_pick(f2_ctx* ctx, const void* d_wave, int wave_dtype, const int64_t* d_offsets, const double* d_lin,
                          const int32_t* d_level, int B, int K, int64_t total, uint32_t first_utterance, uint64_t seed, double* d_sigma,
                          double* d_out) {
     if (B == 0) return F2_OK;
     const bool i16 = wave_dtype == F2_WAVE_I16;
-    if (d_sigma) {
-        if (i16)
-            k_noise_pick_sigma<int16_t><<<dim3(B), dim3(SIGMA_THREADS), 0, ctx->stream>>>((const int16_t*)d_wave, d_offsets, d_lin, d_level, K, d_sigma);
-        else
-            k_noise_pick_sigma<double><<<dim3(B), dim3(SIGMA_THREADS), 0, ctx->stream>>>((const double*)d_wave, d_offsets, d_lin, d_level, K, d_sigma);
-        F2_HIP(ctx, hipGetLastError());
-    }
+    if (d_sigma) F2_TRY(f2_launch_noise_pick_sigma(ctx, d_wave, wave_dtype, d_offsets, d_lin, d_level, B, K, d_sigma));
     if (total == 0) return F2_OK;
     const int64_t blocks = (total + NOISE_THREADS - 1) / NOISE_THREADS;
     const dim3 grid((unsigned)(blocks < (1 << 20) ? blocks : (1 << 20)));

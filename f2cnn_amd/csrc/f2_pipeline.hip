@@ -897,20 +897,29 @@ int f2_cnn_score_windows(f2_ctx* ctx, const f2_cnn* cnn, const float* windows, i
 namespace {
 
 // The small arrays of a noise stage in ctx->meta and its two launches. A clean stage (N.clean()) has none and converts alone.
+// A coloured stage (N.coloured()) also names the arrays of k_shaped_noise_pick, which then takes the place of k_noise_pick behind
+// the same sigma kernel. h_offsets: the batch's offsets on the host.
 struct noise_pick_meta {
     double *d_sigma = nullptr, *d_lin = nullptr;
     int64_t* d_level = nullptr;   // B int32 values in 8-byte slots
-    void carve(f2_meta_carve* meta, int B, const f2_noise_pick_args& N) {
+    f2_shaped_pick_arrays S;
+    void carve(f2_meta_carve* meta, int B, const int64_t* h_offsets, const f2_noise_pick_args& N) {
         if (N.clean()) return;
         meta->add(&d_sigma, (size_t)B), meta->add(&d_lin, (size_t)N.K), meta->add(&d_level, ((size_t)B + 1) / 2);
+        if (N.coloured()) f2_shaped_pick_meta(meta, B, h_offsets, N, &S);
     }
-    int launch(f2_ctx* ctx, const void* d_wave, int wave_dtype, const int64_t* d_offsets, int B, int64_t total, const f2_noise_pick_args& N,
-               double* d_noisy) const {
+    int launch(f2_ctx* ctx, const void* d_wave, int wave_dtype, const int64_t* d_offsets, const int64_t* h_offsets, int B, int64_t total,
+               const f2_noise_pick_args& N, double* d_noisy) const {
         if (!N.clean()) {
             std::vector<double> lin;   // 10^(snr / 10) per level (Evaluating.py:189 SNRdbToSNRlinear)
             for (int k = 0; k < N.K; ++k) lin.push_back(std::pow(10.0, N.snr_db[k] / 10.0));
             F2_TRY(f2_upload_async(ctx, d_lin, lin.data(), sizeof(double) * (size_t)N.K));
             F2_TRY(f2_upload_async(ctx, d_level, N.level_of, sizeof(int32_t) * (size_t)B));
+        }
+        if (N.coloured()) {
+            F2_TRY(f2_launch_noise_pick_sigma(ctx, d_wave, wave_dtype, d_offsets, d_lin, (const int32_t*)d_level, B, N.K, d_sigma));
+            return f2_launch_shaped_noise_pick(ctx, d_wave, wave_dtype, d_offsets, h_offsets, B, N, S, (const int32_t*)d_level, d_sigma,
+                                               d_noisy);
         }
         return f2_launch_noise_pick(ctx, d_wave, wave_dtype, d_offsets, d_lin, (const int32_t*)d_level, B, N.K, total, N.first_utterance,
                                     N.seed, d_sigma, d_noisy);
@@ -976,7 +985,7 @@ int f2_launch_noisy_windows(f2_ctx* ctx, const void* d_wave, int wave_dtype, con
     noise_pick_meta M;
     f2_reverb_pick_arrays A;
     f2_meta_carve meta;
-    M.carve(&meta, B, N);
+    M.carve(&meta, B, offsets, N);
     if (wet) f2_reverb_pick_meta(&meta, B, offsets, *rooms, &A);
     F2_TRY(meta.reserve(ctx));
     F2_TRY(f2_reserve(ctx, ctx->levels, sizeof(double) * (size_t)total));
@@ -986,7 +995,7 @@ int f2_launch_noisy_windows(f2_ctx* ctx, const void* d_wave, int wave_dtype, con
         F2_TRY(f2_launch_reverb_pick(ctx, d_wave, wave_dtype, (const int64_t*)ctx->offsets.ptr, offsets, B, *rooms, A, (double*)ctx->wet.ptr));
         d_wave = ctx->wet.ptr, wave_dtype = F2_WAVE_F64;
     }
-    F2_TRY(M.launch(ctx, d_wave, wave_dtype, (const int64_t*)ctx->offsets.ptr, B, total, N, (double*)ctx->levels.ptr));
+    F2_TRY(M.launch(ctx, d_wave, wave_dtype, (const int64_t*)ctx->offsets.ptr, offsets, B, total, N, (double*)ctx->levels.ptr));
     // f2_input_batch from here on, as a device call on the float64 buffer
     const f2_batch X = {ctx->levels.ptr, F2_WAVE_F64, offsets, coefs, B, C, lpf, cutoff_hz, fft_precision, F2_MEM_DEVICE};
     double* d_env;
@@ -1027,11 +1036,11 @@ int f2_input_batch(f2_ctx* ctx, const void* wave, int wave_dtype, const int64_t*
     return finish_windows(ctx, win, normalize);
 }
 
-// f2_noise_pick: the clean samples go up (host calls), the two kernels of f2_launch_noise_pick run, the float64 samples and sigma come
-// back. A device call waits only for sigma.
-int f2_noise_pick(f2_ctx* ctx, const void* wave, int wave_dtype, const int64_t* offsets, int B, const double* snr_db, int K,
-                  const int32_t* level_of, uint32_t first_utterance, uint64_t seed, double* noisy, double* sigma_or_null, int mem_space) {
-    const f2_noise_pick_args N = {snr_db, K, level_of, first_utterance, seed};
+// f2_noise_pick / f2_shaped_noise_pick: the clean samples go up (host calls), the sigma kernel and k_noise_pick or k_shaped_noise_pick
+// run, the float64 samples and sigma come back. A device call waits only for sigma. colours: the call is f2_shaped_noise_pick,
+// which needs its taps unless every utterance is clean.
+static int noise_pick_call(f2_ctx* ctx, const void* wave, int wave_dtype, const int64_t* offsets, int B, f2_noise_pick_args N, bool colours,
+                           double* noisy, double* sigma_or_null, int mem_space) {
     noise_pick_meta M;
     return f2_stage_call(
         ctx, offsets, B, mem_space,
@@ -1040,50 +1049,48 @@ int f2_noise_pick(f2_ctx* ctx, const void* wave, int wave_dtype, const int64_t* 
             F2_CHECK(ctx, B >= 0, F2_ERR_INVALID, "bad batch size (B=%d)", B);
             F2_TRY(f2_check_mem_space(ctx, mem_space, false));
             F2_TRY(f2_check_noise_pick(ctx, B, N));
-            return B == 0 ? F2_OK : f2_check_offsets(ctx, offsets, B, "offsets");
+            if (B > 0) F2_TRY(f2_check_offsets(ctx, offsets, B, "offsets"));
+            return colours ? f2_check_noise_colours(ctx, B, &N, true) : F2_OK;
         },
         [&](f2_meta_carve* meta) {
-            M.carve(meta, B, N);
+            M.carve(meta, B, offsets, N);
             return F2_OK;
         },
         wave, [&](int64_t total, const void** d_wave) { return f2_stage_wave(ctx, wave, wave_dtype, total, mem_space, d_wave); },
         &f2_ctx::levels, noisy, sizeof(double),
         [&](const void* d_wave, const int64_t* d_offsets, int64_t total, double* d_out) {
-            return M.launch(ctx, d_wave, wave_dtype, d_offsets, B, total, N, d_out);
+            return M.launch(ctx, d_wave, wave_dtype, d_offsets, offsets, B, total, N, d_out);
         },
         sigma_or_null, (size_t)(B > 0 ? B : 0), &M.d_sigma);
 }
 
-int f2_input_batch_noisy(f2_ctx* ctx, const void* wave, int wave_dtype, const int64_t* offsets, const double* coefs, int B, int C,
-                         int lpf, double cutoff_hz, int fft_precision, const int64_t* center_offsets, const int64_t* centers,
-                         int radius, int step, int normalize, const double* snr_db, int K, const int32_t* level_of,
-                         uint32_t first_utterance, uint64_t seed, float* windows, int mem_space) {
-    const f2_noise_pick_args N = {snr_db, K, level_of, first_utterance, seed};
-    int64_t n_windows;
-    std::vector<int> win_utt;
-    F2_TRY(f2_check_input_batch(ctx, wave, wave_dtype, offsets, coefs, B, C, lpf, cutoff_hz, fft_precision, center_offsets, centers, radius,
-                             step, windows, mem_space, &N, &n_windows, &win_utt));
-    if (n_windows == 0) return F2_OK;
-    const void* d_wave;
-    F2_TRY(f2_stage_wave(ctx, wave, wave_dtype, offsets[B], mem_space, &d_wave));
-    f2_output win;
-    F2_TRY(f2_place(ctx, ctx->xbuf, windows, sizeof(float) * (size_t)n_windows * (2 * radius + 1) * (size_t)C, mem_space, true, &win));
-    F2_TRY(reset_flag(ctx));
-    F2_TRY(f2_launch_noisy_windows(ctx, d_wave, wave_dtype, offsets, coefs, B, C, lpf, cutoff_hz, fft_precision, centers, win_utt.data(),
-                                   false, n_windows, radius, step, normalize, N, win.as<float>()));
-    return finish_windows(ctx, win, normalize);
+int f2_noise_pick(f2_ctx* ctx, const void* wave, int wave_dtype, const int64_t* offsets, int B, const double* snr_db, int K,
+                  const int32_t* level_of, uint32_t first_utterance, uint64_t seed, double* noisy, double* sigma_or_null, int mem_space) {
+    return noise_pick_call(ctx, wave, wave_dtype, offsets, B, {snr_db, K, level_of, first_utterance, seed}, false, noisy, sigma_or_null,
+                           mem_space);
 }
 
-int f2_input_batch_wet(f2_ctx* ctx, const void* wave, int wave_dtype, const int64_t* offsets, const double* coefs, int B, int C, int lpf,
-                       double cutoff_hz, int fft_precision, const int64_t* center_offsets, const int64_t* centers, int radius, int step,
-                       int normalize, const double* rir, const int64_t* rir_offsets, int Kr, const int32_t* room_of, const double* snr_db,
-                       int K, const int32_t* level_of, uint32_t first_utterance, uint64_t seed, float* windows, int mem_space) {
-    const f2_noise_pick_args N = {snr_db, K, level_of, first_utterance, seed};
+int f2_shaped_noise_pick(f2_ctx* ctx, const void* wave, int wave_dtype, const int64_t* offsets, int B, const double* snr_db,
+                         const double* fir, const int64_t* fir_offsets, int K, const int32_t* level_of, uint32_t first_utterance,
+                         uint64_t seed, double* noisy, double* sigma_or_null, int mem_space) {
+    return noise_pick_call(ctx, wave, wave_dtype, offsets, B, {snr_db, K, level_of, first_utterance, seed, fir, fir_offsets}, true, noisy,
+                           sigma_or_null, mem_space);
+}
+
+// The one window path behind a noise stage: f2_input_batch_coloured, and with fir == NULL f2_input_batch_wet, and without rooms
+// f2_input_batch_noisy.
+int f2_input_batch_coloured(f2_ctx* ctx, const void* wave, int wave_dtype, const int64_t* offsets, const double* coefs, int B, int C, int lpf,
+                            double cutoff_hz, int fft_precision, const int64_t* center_offsets, const int64_t* centers, int radius, int step,
+                            int normalize, const double* rir, const int64_t* rir_offsets, int Kr, const int32_t* room_of, const double* snr_db,
+                            const double* fir, const int64_t* fir_offsets, int K, const int32_t* level_of, uint32_t first_utterance,
+                            uint64_t seed, float* windows, int mem_space) {
+    f2_noise_pick_args N = {snr_db, K, level_of, first_utterance, seed, fir, fir_offsets};
     const f2_reverb_pick_args R = {rir, rir_offsets, Kr, room_of, nullptr, nullptr};
     int64_t n_windows;
     std::vector<int> win_utt;
     F2_TRY(f2_check_input_batch(ctx, wave, wave_dtype, offsets, coefs, B, C, lpf, cutoff_hz, fft_precision, center_offsets, centers, radius,
                              step, windows, mem_space, &N, &n_windows, &win_utt));
+    F2_TRY(f2_check_noise_colours(ctx, B, &N, false));
     F2_TRY(f2_check_reverb_pick(ctx, B, R));
     if (n_windows == 0) return F2_OK;
     const void* d_wave;
@@ -1094,6 +1101,24 @@ int f2_input_batch_wet(f2_ctx* ctx, const void* wave, int wave_dtype, const int6
     F2_TRY(f2_launch_noisy_windows(ctx, d_wave, wave_dtype, offsets, coefs, B, C, lpf, cutoff_hz, fft_precision, centers, win_utt.data(),
                                    false, n_windows, radius, step, normalize, N, win.as<float>(), &R));
     return finish_windows(ctx, win, normalize);
+}
+
+int f2_input_batch_wet(f2_ctx* ctx, const void* wave, int wave_dtype, const int64_t* offsets, const double* coefs, int B, int C, int lpf,
+                       double cutoff_hz, int fft_precision, const int64_t* center_offsets, const int64_t* centers, int radius, int step,
+                       int normalize, const double* rir, const int64_t* rir_offsets, int Kr, const int32_t* room_of, const double* snr_db,
+                       int K, const int32_t* level_of, uint32_t first_utterance, uint64_t seed, float* windows, int mem_space) {
+    return f2_input_batch_coloured(ctx, wave, wave_dtype, offsets, coefs, B, C, lpf, cutoff_hz, fft_precision, center_offsets, centers, radius,
+                                   step, normalize, rir, rir_offsets, Kr, room_of, snr_db, nullptr, nullptr, K, level_of, first_utterance,
+                                   seed, windows, mem_space);
+}
+
+int f2_input_batch_noisy(f2_ctx* ctx, const void* wave, int wave_dtype, const int64_t* offsets, const double* coefs, int B, int C,
+                         int lpf, double cutoff_hz, int fft_precision, const int64_t* center_offsets, const int64_t* centers,
+                         int radius, int step, int normalize, const double* snr_db, int K, const int32_t* level_of,
+                         uint32_t first_utterance, uint64_t seed, float* windows, int mem_space) {
+    return f2_input_batch_coloured(ctx, wave, wave_dtype, offsets, coefs, B, C, lpf, cutoff_hz, fft_precision, center_offsets, centers, radius,
+                                   step, normalize, nullptr, nullptr, 0, nullptr, snr_db, nullptr, nullptr, K, level_of, first_utterance,
+                                   seed, windows, mem_space);
 }
 
 }  // extern "C"

@@ -188,28 +188,13 @@ int f2_launch_reverb_pick(f2_ctx* ctx, const void* d_wave, int wave_dtype, const
     const int64_t ntiles = f2_tile_table(h_offsets, B, FT_BLOCK);
     F2_TRY(f2_check_workgroups(ctx, ntiles, "reverberation", ""));
     const bool dry = R.dry();
-    // the tile list, utterance << 32 | tile, in (utterance, tile) order ...
+    // the tile list (f2_tile_list), most taps first: a tile walks min(T_room, k0 + nk) taps, none for a dry utterance
     std::vector<int64_t> tiles;
-    std::vector<int32_t> cost;   // taps the tile walks: min(T_room, k0 + nk), 0 for a dry utterance
-    tiles.reserve((size_t)ntiles);
-    for (int b = 0; b < B; ++b) {
-        const int64_t n = h_offsets[b + 1] - h_offsets[b], nt = (n + FT_BLOCK - 1) / FT_BLOCK;
-        const int l = dry ? R.K : R.room_of[b];
+    f2_tile_list(h_offsets, B, FT_BLOCK, !dry && ctx->opt_reverb_pick_sort, &tiles, [&](int b, int64_t n, int64_t i) {
+        const int l = R.room_of[b];
         const int64_t taps = l < R.K ? R.rir_offsets[l + 1] - R.rir_offsets[l] : 0;
-        for (int64_t i = 0; i < nt; ++i) {
-            tiles.push_back((int64_t)b << 32 | i);
-            if (!dry && ctx->opt_reverb_pick_sort) cost.push_back((int32_t)std::min(taps, std::min(n, (i + 1) * FT_BLOCK)));
-        }
-    }
-    // ... or most taps first, ties in that order: the tiles that run longest do not start last. The results do not depend on it.
-    if (!cost.empty()) {
-        std::vector<int32_t> idx((size_t)ntiles);
-        for (int64_t i = 0; i < ntiles; ++i) idx[(size_t)i] = (int32_t)i;
-        std::stable_sort(idx.begin(), idx.end(), [&](int32_t a, int32_t c) { return cost[(size_t)a] > cost[(size_t)c]; });
-        std::vector<int64_t> sorted((size_t)ntiles);
-        for (int64_t i = 0; i < ntiles; ++i) sorted[(size_t)i] = tiles[(size_t)idx[(size_t)i]];
-        tiles.swap(sorted);
-    }
+        return (int32_t)std::min(taps, std::min(n, (i + 1) * FT_BLOCK));
+    });
     F2_TRY(f2_upload_async(ctx, A.d_tiles, tiles.data(), sizeof(int64_t) * tiles.size()));
     const double* d_rir = nullptr;
     const int64_t* d_rir_off = nullptr;

@@ -9,8 +9,8 @@ produces weights; every forward pass used for evaluation is HIP kernel K4 (the t
 ``.npz`` container K4 loads, under the reference's file name ``last_trained_model``).
 
 ``TrainFromWav`` (`cnn train --engine hip --from-wav`, not in the reference) trains on windows the device renders from the WAV files,
-again before every epoch under fresh noise (``--augment-snrs``) and in a freshly drawn room per file (``--augment-t60``,
-``--augment-rirs``) when asked.
+again before every epoch under fresh noise (``--augment-snrs``), of a colour drawn per file (``--augment-colours``), and in a
+freshly drawn room per file (``--augment-t60``, ``--augment-rirs``) when asked.
 
 ``TestModel`` (`cnn test`, not in the reference) is ``model.evaluate(x_test, y_test)`` (:136) for a saved model, broken down
 by a column of the label CSV: one ``f2_cnn_score_windows`` call on the stored windows.
@@ -344,9 +344,10 @@ def build_rooms(t60s, measured, framerate, drr_db, room_seed):
     return [reverb.SyntheticRIR(v, framerate, drr_db, room_seed, level) for level, v in enumerate(t60s)] + list(measured)
 
 
-def _render_windows(ctx, waves, centers, coefs, cfg, LPF, CUTOFF, precision, snrs=(), level=None, seed=0, rirs=(), room=None):
+def _render_windows(ctx, waves, centers, coefs, cfg, LPF, CUTOFF, precision, snrs=(), level=None, seed=0, rirs=(), room=None, firs=None):
     """Normalised windows of some files through f2_input_batch_noisy, RENDER_GROUP files per call, every file at snrs[level]
-    (level None: clean); with `room`, through f2_input_batch_wet with every file in rirs[room]"""
+    (level None: clean); with `room`, through f2_input_batch_wet with every file in rirs[room]; with `firs` (a filter per level),
+    through f2_input_batch_coloured"""
     Cn = coefs.shape[0]
     out = numpy.empty((int(sum(len(c) for c in centers)), cfg.dots_per_input, Cn), numpy.float32)
     row = 0
@@ -360,7 +361,13 @@ def _render_windows(ctx, waves, centers, coefs, cfg, LPF, CUTOFF, precision, snr
         if n == 0:
             continue
         level_of = None if level is None else numpy.full(len(ws), level, numpy.int32)
-        if room is None:
+        if firs is not None:
+            ctx.input_batch_coloured(flat, _lib.WAVE_F64 if f64 else _lib.WAVE_I16, offsets, coefs, len(ws), Cn, bool(LPF),
+                                     float(CUTOFF) if LPF else 0.0, precision, center_offsets, numpy.concatenate(cs), cfg.radius,
+                                     cfg.step, True, rirs if room is not None else (),
+                                     None if room is None else numpy.full(len(ws), room, numpy.int32), snrs, firs, level_of, g, seed,
+                                     out[row:row + n], _lib.MEM_HOST)
+        elif room is None:
             ctx.input_batch_noisy(flat, _lib.WAVE_F64 if f64 else _lib.WAVE_I16, offsets, coefs, len(ws), Cn, bool(LPF),
                                   float(CUTOFF) if LPF else 0.0, precision, center_offsets, numpy.concatenate(cs), cfg.radius, cfg.step,
                                   True, snrs, level_of, g, seed, out[row:row + n], _lib.MEM_HOST)
@@ -374,7 +381,7 @@ def _render_windows(ctx, waves, centers, coefs, cfg, LPF, CUTOFF, precision, snr
 
 
 def TrainFromWav(labelFile=None, LPF=False, CUTOFF=100, snrs=(), seed=None, ctx=None, verbose=1, on_epoch=None, t60s=(), rirs=(),
-                 drr_db=0.0):
+                 drr_db=0.0, colours=(), noise_taps=1025):
     """`cnn train --engine hip --from-wav`: trains on windows rendered on the device from the WAV files of the label CSV.
 
     The TRAIN files go to the trainer once (Trainer.set_waves); the TEST files become normalised windows once, clean - the
@@ -392,6 +399,15 @@ def TrainFromWav(labelFile=None, LPF=False, CUTOFF=100, snrs=(), seed=None, ctx=
     of noise; the responses built once from VALIDATION_ROOM_SEED): the history gains 'val_acc_room' / 'val_loss_room' and augment
     gains t60, rirs, drr and room_seed per epoch. A t60 or a measured response beyond reverb.MAX_TAPS raises reverb.py's
     ValueError before any device work.
+    With `colours` (names of noise.COLOURS, 'like:<recording.wav>', 'fir:<taps.npy>'; needs `snrs`) a noise level is a pair
+    (colour, SNR): the levels are Evaluating.ColourLevels(colours, snrs), colour-major over the SNRs and at most 64 - the level
+    numbers of `cnn noisesweep --colours` - and their filters are built once with noise.FromSpec(spec, framerate, noise_taps),
+    before any file is read (a bad colour, a recording at another rate or too many taps raise noise.py's ValueError there).
+    Every epoch draws a level per TRAIN file and a noise seed exactly as without colours, with K the number of levels, and
+    renders through Trainer.render / render_wet(firs=...); the TEST files are validated clean, once per level
+    (f2_input_batch_coloured, VALIDATION_NOISE_SEED) and once per room. 'val_acc_snr' / 'val_loss_snr' hold a list per level and
+    augment gains colours (a name per level), level_snr_db and noise_taps. 'white' is the filter [1.0]: colours=('white',) trains
+    the weights of `snrs` alone, bit for bit.
     on_epoch(iterations, trainer), if given, is called after each epoch's render, before its steps (for tests and for looking at
     what the network is about to see).
     BATCH_SIZE and EPOCHS come from configF2CNN.conf. Returns (F2CNNModel, history)."""
@@ -404,14 +420,31 @@ def TrainFromWav(labelFile=None, LPF=False, CUTOFF=100, snrs=(), seed=None, ctx=
     batch_size = config.getint('CNN', 'BATCH_SIZE', fallback=32)
     epochs = config.getint('CNN', 'EPOCHS', fallback=20)
     snrs = tuple(float(v) for v in snrs)
-    K = len(snrs)
+    colours = tuple(colours.split(',')) if isinstance(colours, str) else tuple(colours)
+    cfg = F2Config()
+    # (the colours before anything else: a filter that cannot be built is refused here, with noise.py's message)
+    firs, level_names = None, ['{:g} dB'.format(v) for v in snrs]
+    level_snrs = snrs               # the SNR of every level: with colours, colour-major over snrs
+    if colours:
+        from ... import noise
+        from .Evaluating import ColourLevels, _level_text
+        if not snrs:
+            raise ValueError("noise colours need the SNRs they are drawn at (snrs)")
+        grid = ColourLevels(colours, snrs)
+        built = {}
+        for spec, _, _ in grid:
+            if spec not in built:
+                built[spec] = noise.FromSpec(spec, cfg.framerate, noise_taps)
+        firs = [built[spec] for spec, _, _ in grid]
+        level_snrs = tuple(v for _, _, v in grid)
+        level_names = ['{} {}dB'.format(name, _level_text(v)) for _, name, v in grid]
+    K = len(level_snrs)
     t60s, rir_files = tuple(float(v) for v in t60s), tuple(rirs)
     Kr = len(t60s) + len(rir_files)
     if seed is None:
         seed = int(numpy.random.default_rng().integers(0, 2 ** 63))
     labelPath = labelFile or os.path.join('trainingData', 'label_data.csv')
-    cfg = F2Config()
-    # (the rooms before anything else: a response that is too long is refused here, with reverb.py's message)
+    # (the rooms before any file: a response that is too long is refused here, with reverb.py's message)
     from ... import reverb
     measured = [reverb.LoadRIR(r, cfg.framerate) for r in rir_files]
     val_rooms = build_rooms(t60s, measured, cfg.framerate, drr_db, VALIDATION_ROOM_SEED)
@@ -427,6 +460,8 @@ def TrainFromWav(labelFile=None, LPF=False, CUTOFF=100, snrs=(), seed=None, ctx=
     print('Rising train:', int((y_train == 1).sum()))
     print('Falling train:', int((y_train == 0).sum()))
     print(len(train), 'train files,', len(test), 'test files; noise levels (dB):', list(snrs) or 'none')
+    if colours:
+        print('noise colours:', ', '.join(level_names), '| taps', int(noise_taps))
     if Kr:
         print('rooms: t60 (s)', list(t60s) or 'none', '| measured', list(rir_files) or 'none', '| drr (dB) {:g}'.format(float(drr_db)))
     _, coefs = filterbank_from_config(cfg)
@@ -437,7 +472,7 @@ def TrainFromWav(labelFile=None, LPF=False, CUTOFF=100, snrs=(), seed=None, ctx=
         val = [_render_windows(ctx, [waves[k] for k in test], [lw.centers[k] for k in test], coefs, cfg, LPF, CUTOFF, FFT_PRECISION)]
         for l in range(K if len(y_test) else 0):
             val.append(_render_windows(ctx, [waves[k] for k in test], [lw.centers[k] for k in test], coefs, cfg, LPF, CUTOFF,
-                                       FFT_PRECISION, snrs, l, VALIDATION_NOISE_SEED))
+                                       FFT_PRECISION, level_snrs, l, VALIDATION_NOISE_SEED, firs=firs))
         for r in range(Kr if len(y_test) else 0):
             val.append(_render_windows(ctx, [waves[k] for k in test], [lw.centers[k] for k in test], coefs, cfg, LPF, CUTOFF,
                                        FFT_PRECISION, rirs=val_rooms, room=r))
@@ -448,7 +483,7 @@ def TrainFromWav(labelFile=None, LPF=False, CUTOFF=100, snrs=(), seed=None, ctx=
                           cfg.step, lpf=bool(LPF), cutoff=float(CUTOFF) if LPF else 0.0, precision=FFT_PRECISION, group=RENDER_GROUP)
         noise_rng = numpy.random.default_rng([seed, NOISE_STREAM])
         room_rng = numpy.random.default_rng([seed, ROOM_STREAM])
-        noise_seeds, val_snr = [], {"val_acc_snr": [[] for _ in snrs], "val_loss_snr": [[] for _ in snrs]}
+        noise_seeds, val_snr = [], {"val_acc_snr": [[] for _ in level_snrs], "val_loss_snr": [[] for _ in level_snrs]}
         room_seeds, val_room = [], {"val_acc_room": [[] for _ in range(Kr)], "val_loss_room": [[] for _ in range(Kr)]}
         if not K and not Kr:
             trainer.render()
@@ -461,9 +496,10 @@ def TrainFromWav(labelFile=None, LPF=False, CUTOFF=100, snrs=(), seed=None, ctx=
             if Kr:
                 room_of, room_seed = draw_epoch_rooms(room_rng, Kr, len(train))
                 room_seeds.append(room_seed)
-                trainer.render_wet(build_rooms(t60s, measured, cfg.framerate, drr_db, room_seed), room_of, snrs, level_of, noise_seed)
+                trainer.render_wet(build_rooms(t60s, measured, cfg.framerate, drr_db, room_seed), room_of, level_snrs, level_of, noise_seed,
+                                   firs=firs)
             elif K:
-                trainer.render(snrs, level_of, noise_seed)
+                trainer.render(level_snrs, level_of, noise_seed, firs=firs)
             if on_epoch:
                 on_epoch(trainer.iterations, trainer)
             return trainer.steps(rng.permutation(len(y_train)), batch_size)
@@ -485,7 +521,7 @@ def TrainFromWav(labelFile=None, LPF=False, CUTOFF=100, snrs=(), seed=None, ctx=
                 val_room["val_acc_room"][r].append(float(acc[K + 1 + r]))
                 val_room["val_loss_room"][r].append(float(loss[K + 1 + r]))
             if verbose and (K or Kr):
-                print("    val_acc clean {:.4f}".format(acc[0]) + "".join(" | {:g} dB {:.4f}".format(s, a) for s, a in zip(snrs, acc[1:])) +
+                print("    val_acc clean {:.4f}".format(acc[0]) + "".join(" | {} {:.4f}".format(s, a) for s, a in zip(level_names, acc[1:])) +
                       "".join(" | room {} {:.4f}".format(r, a) for r, a in enumerate(acc[K + 1:])))
             return float(loss[0]), float(acc[0])
 
@@ -506,6 +542,8 @@ def TrainFromWav(labelFile=None, LPF=False, CUTOFF=100, snrs=(), seed=None, ctx=
     results = dict(history)
     if K or Kr:
         results["augment"] = {"snrs": list(snrs), "seed": int(seed), "noise_seed": noise_seeds}
+    if colours:
+        results["augment"].update({"colours": [name for _, name, _ in grid], "level_snr_db": list(level_snrs), "noise_taps": int(noise_taps)})
     if Kr:
         results["augment"].update({"t60": list(t60s), "rirs": list(rir_files), "drr": float(drr_db), "room_seed": room_seeds})
     with open('last_trained_model_results.json', 'w') as fp:

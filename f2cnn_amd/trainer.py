@@ -12,6 +12,7 @@ A trainer can own the waves instead of the windows and rebuild the windows under
     t.set_waves(waves, centers, signs, coefs, radius=5, step=160)   # one array of samples and of centres per utterance
     t.render(snrs=(20, 10), level_of=levels, seed=s)                # utterance b at snrs[levels[b]], len(snrs) = clean
     t.render_wet(rirs=[h0, h1], room_of=rooms, snrs=(20, 10), level_of=levels, seed=s)   # ... in room rirs[rooms[b]] first
+    t.render(snrs=(20, 10), level_of=levels, seed=s, firs=[pink, speech])   # ... under noise of the colour firs[levels[b]]
     x, y = t.windows()                                              # what the network is about to see
 """
 import numpy as np
@@ -75,16 +76,23 @@ class Trainer:
                                    lpf, cutoff, _lib.FFT_F32 if precision is None else precision, center_offsets, flat,
                                    y.astype(np.uint8), int(radius), int(step), group)
 
-    def render(self, snrs=(), level_of=None, seed=0):
+    def render(self, snrs=(), level_of=None, seed=0, firs=None):
         """Rebuild the training windows from the stored waves: utterance b at snrs[level_of[b]] dB, clean where level_of[b] ==
-        len(snrs) or level_of is None; the noise of an utterance depends on (seed, its level, its number) alone."""
-        self.ctx.trainer_render(self.handle, snrs, level_of, seed)
+        len(snrs) or level_of is None; the noise of an utterance depends on (seed, its level, its number) alone. firs (one 1-D
+        float64 filter per level): the noise of level l is filtered with firs[l] (f2_trainer_render_coloured); None: white."""
+        if firs is None:
+            self.ctx.trainer_render(self.handle, snrs, level_of, seed)
+        else:
+            self.ctx.trainer_render_coloured(self.handle, (), None, snrs, firs, level_of, seed)
 
-    def render_wet(self, rirs=(), room_of=None, snrs=(), level_of=None, seed=0):
+    def render_wet(self, rirs=(), room_of=None, snrs=(), level_of=None, seed=0, firs=None):
         """render() with a room per utterance: utterance b is convolved with rirs[room_of[b]] (float64 arrays), dry where
         room_of[b] == len(rirs) or room_of is None, and then noised at snrs[level_of[b]] dB of the reverberant signal. Without
-        rooms it is render(), bit for bit."""
-        self.ctx.trainer_render_wet(self.handle, rirs, room_of, snrs, level_of, seed)
+        rooms it is render(), bit for bit. firs: as in render()."""
+        if firs is None:
+            self.ctx.trainer_render_wet(self.handle, rirs, room_of, snrs, level_of, seed)
+        else:
+            self.ctx.trainer_render_coloured(self.handle, rirs, room_of, snrs, firs, level_of, seed)
 
     def windows(self, first=0, count=None):
         """(x, y): rows first .. first + count - 1 of the training set as it stands on the device (count None: to the end)"""

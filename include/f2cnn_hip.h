@@ -1140,6 +1140,72 @@ int f2_eval_shaped_noise_sweep(f2_ctx* ctx, const f2_cnn* cnn, const void* wave,
                                int64_t* window_offsets_or_null /* host, (K+1)*B + 1 */, double* sigma_or_null /* host, (K+1)*B */,
                                int64_t* stats_or_null /* host, (K+1)*B*2 */, int mem_space);
 
+/* ---- Training against colours: one coloured-noise level per utterance, new every epoch --------------------------------------
+ * f2_shaped_noise_levels makes every one of K levels for every utterance, level-major - what a sweep wants. A training render wants
+ * one level per utterance, in the layout of the waves, and these entries make that and nothing else. A level is a pair (filter,
+ * SNR), as in the sweep. They compose with the entries of "Training in rooms": room first, then coloured noise at an SNR of the
+ * reverberant signal. (f2_version stays 115 with these entries: look the symbols up.)
+ *
+ * f2_shaped_noise_pick (stateless): utterance b of `noisy` (offsets[B] float64, the layout of `wave`) at level l = level_of[b]:
+ *   l < K    sample i becomes clean + sigma_b * c, product and sum rounded separately, with
+ *                c = sum over t = 0 .. T_l - 1 of h_l[t] * z(seed, l, first_utterance + b, (i - t) mod 2^64)
+ *            by f2_shaped_noise_levels' arithmetic word for word: one float64 accumulator per output, starting from 0.0; taps in
+ *            ascending t; acc = fma(h[t], z[i-t], acc); no atomics; the sum of one output never split across lanes; the index
+ *            wraps below zero as a 64-bit counter. sigma_b = RMS(clean_b) / 10^(snr_db[l] / 10) by f2_noise_pick's kernel: the
+ *            same bits as f2_noise_pick's sigma.
+ *   l == K, or sigma_b == 0 (an all-zero or empty utterance)    the sample converted to float64, exactly
+ *   level_of == NULL or K == 0: every utterance is clean, and fir / fir_offsets may be NULL.
+ * Identity with the sweep: with first_utterance == 0, utterance b is bit for bit utterance b of level level_of[b] of
+ * f2_shaped_noise_levels for the same snr_db, fir and seed - the tile of 1024 outputs and the epilogue are the same device
+ * functions - and sigma[b] is that call's sigma[level_of[b] * B + b]. Identity with white: with every filter one tap of 1.0 the
+ * result is bit for bit f2_noise_pick, for any first_utterance. A sample depends on (seed, l, utterance number, i, h_l) and its
+ * clean utterance alone: not on B, the utterance's place in the batch, the levels of the other utterances, the memory space or the
+ * input dtype of equal values.
+ *   kernel   one workgroup of 256 threads per tile of 1024 outputs and nothing else (the sweep's grid is tiles x levels). A tile
+ *            costs T_l taps and nothing when clean, so the host uploads the list of (utterance, tile) most taps first, ties in
+ *            (utterance, tile) order - the list builder of f2_reverb_pick - and a workgroup reads its entry: no workgroup
+ *            searches the offsets. The results do not depend on the order (context option "noise_pick_sort" = 0: utterance by
+ *            utterance). LDS as the sweep's (24 KB at 2048 taps), taps through the scalar path, plain vector stores.
+ *   wave, noisy   in mem_space (F2_MEM_HOST or F2_MEM_DEVICE); device pointers need element alignment only
+ *   offsets, snr_db (K), fir, fir_offsets (K+1), level_of (B), sigma_or_null (B)   host
+ * F2_MEM_DEVICE: the call enqueues on the context's stream and returns; it waits only when sigma_or_null is asked for.
+ * F2_MEM_HOST: it returns when noisy is filled.
+ * Errors, before anything is launched or written: those of f2_noise_pick; then, unless every utterance is clean (level_of NULL,
+ * K == 0, or every entry equal to K): a NULL fir or fir_offsets (F2_ERR_INVALID) and what f2_shaped_noise_levels rejects of them,
+ * with its statuses - K > 64 and more than F2_SHAPED_MAX_TAPS = 2048 taps: F2_ERR_UNSUPPORTED; fir_offsets[0] != 0, decreasing
+ * fir_offsets, a level with no taps, a tap that is not finite: F2_ERR_INVALID (the messages name the level). NULL wave or noisy
+ * with samples: F2_ERR_INVALID. B == 0 or no samples: F2_OK, sigma filled with zeros.
+ *
+ * f2_input_batch_coloured: f2_input_batch_wet's arguments plus fir, fir_offsets after snr_db. Bit for bit
+ * f2_input_batch(F2_WAVE_F64, ...) on f2_shaped_noise_pick(F2_WAVE_F64, ...) on f2_reverb_pick(...): the same code on two buffers
+ * in context scratch that never leave the device. fir == NULL: bit for bit f2_input_batch_wet (it is that call). With Kr == 0 or
+ * room_of == NULL there is no reverberant stage and the noise stage reads the waves themselves (the sigma of int16 samples is then
+ * the int64 one, as in f2_input_batch_noisy). Errors: those of f2_input_batch_noisy, then those of f2_shaped_noise_pick's taps
+ * (with a non-NULL fir), then those of f2_reverb_pick, all before a launch.
+ *
+ * f2_trainer_render_coloured: f2_trainer_render_wet's arguments plus fir, fir_offsets after snr_db. Group g is bit for bit
+ * f2_input_batch_coloured on its utterances with first_utterance = g group, normalize = 1 and the stored options, written straight
+ * to its rows of x; the taps of rooms and filters go up once per call into buffers the trainer owns, not once per group; one wait
+ * at the end. f2_trainer_render_wet is this call with fir == NULL, bit for bit. Errors: f2_trainer_render_wet's and those of the
+ * taps, nothing launched.
+ */
+int f2_shaped_noise_pick(f2_ctx* ctx, const void* wave, int wave_dtype, const int64_t* offsets /* host, B+1 */, int B,
+                         const double* snr_db /* host, K */, const double* fir /* host, fir_offsets[K] taps */,
+                         const int64_t* fir_offsets /* host, K+1 */, int K,
+                         const int32_t* level_of /* host, B, each in [0, K], or NULL */, uint32_t first_utterance, uint64_t seed,
+                         double* noisy /* offsets[B] float64, mem_space, layout of `wave` */, double* sigma_or_null /* host, B */,
+                         int mem_space);
+int f2_input_batch_coloured(f2_ctx* ctx, const void* wave, int wave_dtype, const int64_t* offsets, const double* coefs, int B, int C,
+                            int lpf, double cutoff_hz, int fft_precision, const int64_t* center_offsets, const int64_t* centers,
+                            int radius, int step, int normalize, const double* rir, const int64_t* rir_offsets, int Kr,
+                            const int32_t* room_of, const double* snr_db, const double* fir /* or NULL: white */,
+                            const int64_t* fir_offsets, int K, const int32_t* level_of, uint32_t first_utterance, uint64_t seed,
+                            float* windows, int mem_space);
+int f2_trainer_render_coloured(f2_ctx* ctx, f2_trainer* trainer, const double* rir, const int64_t* rir_offsets, int Kr,
+                               const int32_t* room_of /* host, B, or NULL */, const double* snr_db,
+                               const double* fir /* or NULL: white */, const int64_t* fir_offsets, int K,
+                               const int32_t* level_of /* host, B, or NULL */, uint64_t seed);
+
 #ifdef __cplusplus
 }
 #endif
