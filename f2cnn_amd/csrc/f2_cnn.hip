@@ -13,150 +13,18 @@
 // their Keras layouts: a (3,3,Cin,Cout) HWIO kernel flattened is exactly the K x N operand
 // (k = (dy*3+dx)*Cin + ci). Activations are NHWC in HBM between layers, processed in chunks of windows.
 //
-// Implicit-GEMM tile: one task = 2 output rows x 32 output columns of one window; its 4 x 34 x Cin input patch sits in
-// LDS at a (Cin+4)-float pitch per pixel (16-byte aligned, conflict-free for ds_read_b128). MFMA step s multiplies
-// channel s (half-wave 0) and channel Cin/2 + s (half-wave 1), so four steps are one 16-byte LDS read of the patch
-// (A operand, lane = pixel) and one 16-byte load of the re-laid-out weights wt[tap][h][s/4][cout][s%4] (B operand,
-// lane = Cout); both are requested one step ahead of the MFMAs that use them. ReLU, bias and the 2x2 max-pool are
-// applied from the accumulators: the 32x32 accumulator keeps pixel pairs (2t, 2t+1) in one lane, and the second
-// pooled row is the wave's second M-tile, so pooling needs no cross-lane traffic (k_conv3x3_mfma). The reference's
-// window shape runs two fused kernels instead: k_conv12_mfma (conv1 computed inside conv2's staging, two waves per
-// task) and k_conv34_mfma (conv3's output stays in LDS).
+// Implicit-GEMM tile of the float32 kernels: one task = 2 output rows x 32 output columns of one window, its 4 x 34 x Cin
+// input patch in LDS; f2_cnn_f32_tile.h describes it and holds its pieces - the 9-tap loop, the patch staging, the pool
+// exchange, the row GEMM - and the per-layer kernel k_conv3x3_f32 that conv3 / conv4 of windows without four pooled rows
+// run on (ReLU, bias and the 2x2 max-pool applied from the accumulators). The reference's window shape runs two fused
+// kernels instead: k_conv12_mfma (conv1 computed inside conv2's staging, two waves per task) and k_conv34_mfma (conv3's
+// output stays in LDS).
 #include <algorithm>
 #include <cmath>
 
-#include "f2_cnn_dims.h"
+#include "f2_cnn_f32_tile.h"
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-// ---- conv3 / conv4 for pooled inputs that do not have four rows: implicit GEMM on v_mfma_f32_32x32x2_f32 ----
-// NSPLIT waves share one task (one patch): each takes COUT/32/NSPLIT of the output tiles, so a 64-channel layer
-// keeps twice the waves per CU for the same LDS.
-template <int CIN, int COUT, bool SAME, bool POOL, int WAVES, int NSPLIT>
-__global__ __launch_bounds__(WAVES * 64) void k_conv3x3_mfma(const float* __restrict__ in, const float* __restrict__ w,
-                                                             const float* __restrict__ bias, float* __restrict__ out,
-                                                             int Hin, int Win, int64_t nwin) {
-    constexpr int PS = CIN + 4;           // LDS pitch per pixel: 16-byte aligned and conflict-free for ds_read_b128
-    constexpr int PATCH = 4 * PW * PS;    // floats per wave
-    constexpr int NT = COUT / 32 / NSPLIT;   // output tiles of this wave
-    constexpr int TPB = WAVES / NSPLIT;      // tasks (patches) per workgroup
-    constexpr int PAD = SAME ? 1 : 0;
-    constexpr int C4 = CIN / 4;           // float4 per pixel
-    constexpr int HALF = CIN / 2;         // MFMA k = 0 takes channel s, k = 1 takes channel HALF + s
-    extern __shared__ __attribute__((aligned(16))) float lds_all[];
-
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int ns = wave % NSPLIT;
-    float* patch = lds_all + (wave / NSPLIT) * PATCH;
-
-    const int Ho = SAME ? Hin : Hin - 2, Wo = SAME ? Win : Win - 2;
-    const int Hout = POOL ? Ho / 2 : Ho, Wout = POOL ? Wo / 2 : Wo;
-    const int row_pairs = POOL ? Ho / 2 : (Ho + 1) / 2;
-    const int wneed = POOL ? (Wo / 2) * 2 : Wo;
-    const int xtiles = (wneed + 31) / 32;
-    const int64_t tasks = nwin * row_pairs * xtiles;
-    int64_t task = (int64_t)blockIdx.x * TPB + wave / NSPLIT;
-    const bool live = task < tasks;
-    if (!live) task = tasks - 1;
-    const int xt = (int)(task % xtiles);
-    const int64_t t2 = task / xtiles;
-    const int rp = (int)(t2 % row_pairs);
-    const int64_t win = t2 / row_pairs;
-    const int y0 = 2 * rp, x0 = 32 * xt;
-
-    // stage the 4 x 34 x CIN patch with 16-byte loads (zero outside the image: 'same' padding / tile overhang)
-    const float* img = in + win * (int64_t)Hin * Win * CIN;
-#pragma unroll 4
-    for (int e = lane + 64 * ns; e < 4 * PW * C4; e += 64 * NSPLIT) {
-        const int r = e / (PW * C4);
-        const int rem = e - r * (PW * C4);
-        const int p = rem / C4, c4 = rem - p * C4;
-        const int yi = y0 - PAD + r, xi = x0 - PAD + p;
-        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (yi >= 0 && yi < Hin && xi >= 0 && xi < Win)
-            v = *reinterpret_cast<const float4*>(img + ((int64_t)yi * Win + xi) * CIN + c4 * 4);
-        *reinterpret_cast<float4*>(patch + (r * PW + p) * PS + c4 * 4) = v;
-    }
-    __syncthreads();
-
-    f32x16 acc[2][NT];
-#pragma unroll
-    for (int rr = 0; rr < 2; ++rr)
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-            for (int q = 0; q < 16; ++q) acc[rr][nt][q] = 0.f;
-
-    // lane = (pixel i, half h). Step s of a tap multiplies channels s (h = 0) and HALF + s (h = 1): four
-    // consecutive steps are one float4 of the patch (A) and one float4 of the re-laid-out weights (B),
-    // wt[tap][h][s/4][cout][s%4].
-    const int i = lane & 31, h = lane >> 5;
-    const float* pa0 = patch + i * PS + h * HALF;
-    const float4* wq = reinterpret_cast<const float4*>(w) + (int64_t)h * (HALF / 4) * COUT + ns * NT * 32 + i;
-    // The (tap, q) steps are software pipelined: the A (LDS) and B (weights) operands of step it+1 are requested before
-    // the eight MFMAs of step it are issued, so their latency hides behind 512 cycles of matrix-core time instead of
-    // stalling the wave after them (an MFMA occupies the pipe for 64 cycles; the loads used to trail the last one).
-    constexpr int QN = HALF / 4, NIT = 9 * QN;
-    float4 av0[2], av1[2], bq[2][NT];
-    auto fetch = [&](int it, int buf) {
-        const int tap = it / QN, q = it - tap * QN;
-        const int dy = tap / 3, dx = tap - dy * 3;
-        const float* pa = pa0 + (dy * PW + dx) * PS;
-        const float4* pb = wq + (int64_t)tap * 2 * QN * COUT;
-        av0[buf] = *reinterpret_cast<const float4*>(pa + 4 * q);
-        av1[buf] = *reinterpret_cast<const float4*>(pa + PW * PS + 4 * q);
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) bq[buf][nt] = pb[(int64_t)q * COUT + nt * 32];
-    };
-    fetch(0, 0);
-#pragma unroll
-    for (int it = 0; it < NIT; ++it) {
-        const int cur = it & 1;
-        if (it + 1 < NIT) fetch(it + 1, cur ^ 1);
-        __builtin_amdgcn_sched_barrier(0);
-        const float a0v[4] = {av0[cur].x, av0[cur].y, av0[cur].z, av0[cur].w};
-        const float a1v[4] = {av1[cur].x, av1[cur].y, av1[cur].z, av1[cur].w};
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt) {
-                const float4 bb = bq[cur][nt];
-                const float bv = r == 0 ? bb.x : r == 1 ? bb.y : r == 2 ? bb.z : bb.w;
-                acc[0][nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0v[r], bv, acc[0][nt], 0, 0, 0);
-                acc[1][nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1v[r], bv, acc[1][nt], 0, 0, 0);
-            }
-        }
-        __builtin_amdgcn_sched_barrier(0);
-    }
-
-    if (!live) return;
-    float* o = out + win * (int64_t)Hout * Wout * COUT;
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt) {
-        const int co = (ns * NT + nt) * 32 + i;
-        const float bv = bias[co];
-        if constexpr (POOL) {
-#pragma unroll
-            for (int q = 0; q < 16; q += 2) {
-                const int px = (x0 + (q & 3) + 8 * (q >> 2) + 4 * h) >> 1;
-                const float m = fmaxf(fmaxf(acc[0][nt][q], acc[0][nt][q + 1]), fmaxf(acc[1][nt][q], acc[1][nt][q + 1]));
-                if (px < Wout) o[((int64_t)rp * Wout + px) * COUT + co] = fmaxf(m + bv, 0.f);
-            }
-        } else {
-#pragma unroll
-            for (int rr = 0; rr < 2; ++rr) {
-                const int y = y0 + rr;
-#pragma unroll
-                for (int q = 0; q < 16; ++q) {
-                    const int xo = x0 + (q & 3) + 8 * (q >> 2) + 4 * h;
-                    if (y < Ho && xo < Wo) o[((int64_t)y * Wout + xo) * COUT + co] = fmaxf(acc[rr][nt][q] + bv, 0.f);
-                }
-            }
-        }
-    }
-}
 
 // ---- conv1 ('same', Cin = 1) + conv2 ('valid') + 2x2 max-pool in one kernel ----
 // One task = 2 conv2 output rows x 32 columns of one window (one pooled row x 16). conv1 has no tensor of its own: the
@@ -169,7 +37,7 @@ __global__ __launch_bounds__(512) void k_conv12_mfma(const float* __restrict__ x
                                                      const float* __restrict__ b1, const float* __restrict__ w2,
                                                      const float* __restrict__ b2, float* __restrict__ out, int Hin,
                                                      int Win, int64_t nwin) {
-    constexpr int PS = C1 + 4, PATCH = 4 * PW * PS, XW = PW + 2, HALF = C1 / 2, QN = HALF / 4, NIT = 9 * QN;
+    constexpr int PS = C1 + 4, PATCH = 4 * PW * PS, XW = PW + 2, HALF = C1 / 2;
     extern __shared__ __attribute__((aligned(16))) float lds_all[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int pair = wave >> 1, r = wave & 1;                  // r: which of the task's two output rows this wave computes
@@ -226,51 +94,21 @@ __global__ __launch_bounds__(512) void k_conv12_mfma(const float* __restrict__ x
     }
     __syncthreads();
 
-    // conv2 row y0 + r: lane = (pixel i, half h); operands requested one step ahead (see k_conv3x3_mfma)
+    // conv2 row y0 + r: lane = (pixel i, half h)
     const int i = lane & 31, h = lane >> 5;
-    f32x16 acc;
-#pragma unroll
-    for (int q = 0; q < 16; ++q) acc[q] = 0.f;
-    const float* pa0 = patch + (r * PW + i) * PS + h * HALF;
-    const float4* wq = reinterpret_cast<const float4*>(w2) + (int64_t)h * QN * C2 + i;
-    float4 av[2], bq[2];
-    auto fetch = [&](int it, int buf) {
-        const int tap = it / QN, q = it - tap * QN;
-        const int dy = tap / 3, dx = tap - dy * 3;
-        av[buf] = *reinterpret_cast<const float4*>(pa0 + (dy * PW + dx) * PS + 4 * q);
-        bq[buf] = wq[(int64_t)tap * 2 * QN * C2 + (int64_t)q * C2];
-    };
-    fetch(0, 0);
-#pragma unroll
-    for (int it = 0; it < NIT; ++it) {
-        const int cur = it & 1;
-        if (it + 1 < NIT) fetch(it + 1, cur ^ 1);
-        __builtin_amdgcn_sched_barrier(0);
-        const float a[4] = {av[cur].x, av[cur].y, av[cur].z, av[cur].w};
-        const float b[4] = {bq[cur].x, bq[cur].y, bq[cur].z, bq[cur].w};
-#pragma unroll
-        for (int k = 0; k < 4; ++k) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[k], b[k], acc, 0, 0, 0);
-        __builtin_amdgcn_sched_barrier(0);
-    }
-    // 2x2 pool: horizontal pairs sit in one lane; row 1 hands its eight pair maxima to row 0 through the (now idle) patch
-    float hm[8];
-#pragma unroll
-    for (int q = 0; q < 16; q += 2) hm[q / 2] = fmaxf(acc[q], acc[q + 1]);
+    f32x16 acc[1][1];
+    conv_taps<C1, C2, PS, 1, 1>(patch + (r * PW + i) * PS + h * HALF, reinterpret_cast<const float4*>(w2) + (int64_t)h * (HALF / 4) * C2 + i, acc);
+    // 2x2 pool: row 1 hands its pair maxima to row 0 through the (now idle) patch
+    float m[8];
     __syncthreads();
-    if (r == 1) {
-#pragma unroll
-        for (int k = 0; k < 8; ++k) patch[k * 64 + lane] = hm[k];
-    }
-    __syncthreads();
+    pool_exchange(acc[0][0], patch, r == 1, lane, m);
     if (r == 0 && live) {
         const float bv = b2[i];
         float* o = out + win * (int64_t)row_pairs * Wout * C2;
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
-            const int q = 2 * k;
-            const int px = (x0 + (q & 3) + 8 * (q >> 2) + 4 * h) >> 1;
-            const float m = fmaxf(hm[k], patch[k * 64 + lane]);
-            if (px < Wout) o[((int64_t)rp * Wout + px) * C2 + i] = fmaxf(m + bv, 0.f);
+            const int px = (x0 + acc_row(2 * k, h)) >> 1;
+            if (px < Wout) o[((int64_t)rp * Wout + px) * C2 + i] = fmaxf(m[k] + bv, 0.f);
         }
     }
 }
@@ -297,17 +135,7 @@ __global__ __launch_bounds__(256) void k_conv34_mfma(const float* __restrict__ i
     const int Wo4 = Win - 2, Wp = Wo4 / 2;                   // conv4 output / pooled width
     if (win >= nwin) return;
 
-    const float* img = in + win * (int64_t)4 * Win * C2;
-    for (int e = tid; e < 6 * PW * (C2 / 4); e += 256) {
-        const int r = e / (PW * (C2 / 4));
-        const int rem = e - r * (PW * (C2 / 4));
-        const int p = rem / (C2 / 4), c4 = rem - p * (C2 / 4);
-        const int yi = r - 1, xi = c0 - 1 + p;
-        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (yi >= 0 && yi < 4 && xi >= 0 && xi < Win)
-            v = *reinterpret_cast<const float4*>(img + ((int64_t)yi * Win + xi) * C2 + c4 * 4);
-        *reinterpret_cast<float4*>(pA + (r * PW + p) * PSA + c4 * 4) = v;
-    }
+    stage_patch<6, C2>(pA, in + win * (int64_t)4 * Win * C2, nullptr, 4, Win, -1, c0 - 1, tid, 256);
     for (int e = tid; e < 4 * 2 * PSB; e += 256) {            // the two columns conv4's discarded outputs touch
         const int r = e / (2 * PSB), rem = e - r * (2 * PSB);
         pB[(r * PW + 32) * PSB + rem] = 0.f;
@@ -316,103 +144,35 @@ __global__ __launch_bounds__(256) void k_conv34_mfma(const float* __restrict__ i
 
     // ---- phase 1: conv3, row = wave ----
     {
-        constexpr int HALF = C2 / 2, QN = HALF / 4, NIT = 9 * QN;
-        f32x16 acc[2];
-#pragma unroll
-        for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-            for (int q = 0; q < 16; ++q) acc[nt][q] = 0.f;
-        const float* pa0 = pA + (wave * PW + i) * PSA + h * HALF;
-        const float4* wq = reinterpret_cast<const float4*>(w3) + (int64_t)h * QN * C3 + i;
-        float4 av[2], bq[2][2];
-        auto fetch = [&](int it, int buf) {
-            const int tap = it / QN, q = it - tap * QN;
-            const int dy = tap / 3, dx = tap - dy * 3;
-            av[buf] = *reinterpret_cast<const float4*>(pa0 + (dy * PW + dx) * PSA + 4 * q);
-            const float4* pb = wq + (int64_t)tap * 2 * QN * C3 + (int64_t)q * C3;
-            bq[buf][0] = pb[0];
-            bq[buf][1] = pb[32];
-        };
-        fetch(0, 0);
-#pragma unroll
-        for (int it = 0; it < NIT; ++it) {
-            const int cur = it & 1;
-            if (it + 1 < NIT) fetch(it + 1, cur ^ 1);
-            __builtin_amdgcn_sched_barrier(0);
-            const float a[4] = {av[cur].x, av[cur].y, av[cur].z, av[cur].w};
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-#pragma unroll
-                for (int nt = 0; nt < 2; ++nt) {
-                    const float4 bb = bq[cur][nt];
-                    const float bv = r == 0 ? bb.x : r == 1 ? bb.y : r == 2 ? bb.z : bb.w;
-                    acc[nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[r], bv, acc[nt], 0, 0, 0);
-                }
-            __builtin_amdgcn_sched_barrier(0);
-        }
+        f32x16 acc[1][2];
+        conv_taps<C2, C3, PSA, 1, 2>(pA + (wave * PW + i) * PSA + h * (C2 / 2), reinterpret_cast<const float4*>(w3) + (int64_t)h * (C2 / 8) * C3 + i, acc);
 #pragma unroll
         for (int nt = 0; nt < 2; ++nt) {
             const int co = nt * 32 + i;
             const float bv = b3[co];
 #pragma unroll
-            for (int q = 0; q < 16; ++q) {
-                const int px = (q & 3) + 8 * (q >> 2) + 4 * h;
-                pB[(wave * PW + px) * PSB + co] = fmaxf(acc[nt][q] + bv, 0.f);
-            }
+            for (int q = 0; q < 16; ++q) pB[(wave * PW + acc_row(q, h)) * PSB + co] = fmaxf(acc[0][nt][q] + bv, 0.f);
         }
     }
     __syncthreads();
 
     // ---- phase 2: conv4, row = wave & 1, N tile = wave >> 1 ----
     const int r4 = wave & 1, nt4 = wave >> 1;
-    f32x16 acc4;
-#pragma unroll
-    for (int q = 0; q < 16; ++q) acc4[q] = 0.f;
-    {
-        constexpr int HALF = C3 / 2, QN = HALF / 4, NIT = 9 * QN;
-        const float* pa0 = pB + (r4 * PW + i) * PSB + h * HALF;
-        const float4* wq = reinterpret_cast<const float4*>(w4) + (int64_t)h * QN * C4 + nt4 * 32 + i;
-        float4 av[2], bq[2];
-        auto fetch = [&](int it, int buf) {
-            const int tap = it / QN, q = it - tap * QN;
-            const int dy = tap / 3, dx = tap - dy * 3;
-            av[buf] = *reinterpret_cast<const float4*>(pa0 + (dy * PW + dx) * PSB + 4 * q);
-            bq[buf] = wq[(int64_t)tap * 2 * QN * C4 + (int64_t)q * C4];
-        };
-        fetch(0, 0);
-#pragma unroll
-        for (int it = 0; it < NIT; ++it) {
-            const int cur = it & 1;
-            if (it + 1 < NIT) fetch(it + 1, cur ^ 1);
-            __builtin_amdgcn_sched_barrier(0);
-            const float a[4] = {av[cur].x, av[cur].y, av[cur].z, av[cur].w};
-            const float b[4] = {bq[cur].x, bq[cur].y, bq[cur].z, bq[cur].w};
-#pragma unroll
-            for (int r = 0; r < 4; ++r) acc4 = __builtin_amdgcn_mfma_f32_32x32x2f32(a[r], b[r], acc4, 0, 0, 0);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-    }
-    // 2x2 pool: the horizontal pair sits in one lane; row 1 hands its eight pair maxima to row 0 through LDS (pA is free)
-    float hm[8];
-#pragma unroll
-    for (int q = 0; q < 16; q += 2) hm[q / 2] = fmaxf(acc4[q], acc4[q + 1]);
-    float* xch = pA + nt4 * (8 * 64);
-    if (r4 == 1) {
-#pragma unroll
-        for (int k = 0; k < 8; ++k) xch[k * 64 + lane] = hm[k];
-    }
-    __syncthreads();
+    f32x16 acc4[1][1];
+    conv_taps<C3, C4, PSB, 1, 1>(pB + (r4 * PW + i) * PSB + h * (C3 / 2), reinterpret_cast<const float4*>(w4) + (int64_t)h * (C3 / 8) * C4 + nt4 * 32 + i,
+                                 acc4);
+    // 2x2 pool: row 1 hands its pair maxima to row 0 through LDS (pA is free)
+    float m[8];
+    pool_exchange(acc4[0][0], pA + nt4 * (8 * 64), r4 == 1, lane, m);
     if (r4 == 0) {
         const int co = nt4 * 32 + i;
         const float bv = b4[co];
         float* o = out + win * (int64_t)Wp * C4;
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
-            const int q = 2 * k;
-            const int xl = (q & 3) + 8 * (q >> 2) + 4 * h;      // even conv4 column inside the tile
+            const int xl = acc_row(2 * k, h);                    // even conv4 column inside the tile
             const int pxp = (c0 + xl) >> 1;
-            const float m = fmaxf(hm[k], xch[k * 64 + lane]);
-            if (xl < T34 && pxp < Wp) o[(int64_t)pxp * C4 + co] = fmaxf(m + bv, 0.f);
+            if (xl < T34 && pxp < Wp) o[(int64_t)pxp * C4 + co] = fmaxf(m[k] + bv, 0.f);
         }
     }
 }
@@ -528,7 +288,7 @@ __global__ __launch_bounds__(256) void k_conv34_h16x3(const float* __restrict__ 
             const float bv = b3[co];
 #pragma unroll
             for (int q = 0; q < 16; ++q) {
-                const int px = (q & 3) + 8 * (q >> 2) + 4 * h;
+                const int px = acc_row(q, h);
                 _Float16 vh, vl;
                 split_h16(fmaxf(fmaf(acc[nt][q], S.c3, bv), 0.f), vh, vl);
                 *reinterpret_cast<_Float16*>(pBh + (wave * PW + px) * PB16 + co * 2) = vh;
@@ -593,7 +353,7 @@ __global__ __launch_bounds__(256) void k_conv34_h16x3(const float* __restrict__ 
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
             const int q = 2 * k;
-            const int xl = (q & 3) + 8 * (q >> 2) + 4 * h;
+            const int xl = acc_row(q, h);
             const int pxp = (c0 + xl) >> 1;
             const float m = fmaxf(hm[k], xch[k * 64 + lane]);
             if (xl < T34 && pxp < Wp) o[(int64_t)pxp * C4 + co] = fmaxf(fmaf(m, S.c4, bv), 0.f);
@@ -732,7 +492,7 @@ __global__ __launch_bounds__(128 * RP * TPW) void k_conv12_h16x3(const float* __
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
             const int q = 2 * k;
-            const int px = (x0 + (q & 3) + 8 * (q >> 2) + 4 * h) >> 1;
+            const int px = (x0 + acc_row(q, h)) >> 1;
             const float m = fmaxf(hm[k], xch[k * 64 + lane]);
             if (px < Wout) o[((int64_t)rp * Wout + px) * C2 + i] = fmaxf(fmaf(m, S.c2, bv), 0.f);
         }
@@ -759,76 +519,29 @@ int launch_conv12_h16(f2_ctx* ctx, const f2_cnn* cnn, const f2_scale_set* S, con
     return F2_OK;
 }
 
-// ---- dense1: (n, K) x (K, 516) on the same MFMA ----
+// ---- dense1: (n, K) x (K, 516) on the same MFMA: gemm_rows_tile with N = the padded 544, then bias + ReLU ----
 // One 6-wave workgroup = 64 windows (two M tiles) x 6 of the 17 output tiles (blockIdx.y picks the group, one output
-// tile per wave, every weight load feeds both M tiles). K is walked in
-// chunks of 64: the 32 x 64 activation chunk is staged in LDS (double buffered, 16-byte loads, pitch 68) and
-// read back as the A operand with ds_read_b128; the B operand comes from the re-laid-out weights
-// wt[chunk][h][q][n (padded to 544)][4], one 16-byte load per four MFMA steps.
+// tile per wave); weights wt[chunk][h][q][n (padded to 544)][4].
 constexpr int D1_MT = 2;                   // M tiles (32 windows each) per workgroup: every weight load feeds 2 MFMA tiles
+static_assert(32 * D1_MT == GEMM_ROWS, "k_dense1_mfma and k_dense1_h16x3 share a grid");
 __global__ __launch_bounds__(D1_WAVES * 64) void k_dense1_mfma(const float* __restrict__ a, const float* __restrict__ wt,
                                                                const float* __restrict__ bias, float* __restrict__ out,
                                                                int K, int64_t n) {
-    constexpr int PS = D1_KC + 4;
-    constexpr int ROWS = 32 * D1_MT;
-    __shared__ __attribute__((aligned(16))) float As[2][ROWS * PS];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int64_t w0 = (int64_t)blockIdx.x * ROWS;
-    const int i = lane & 31, h = lane >> 5;
-    const int nchunks = K / D1_KC;
+    __shared__ __attribute__((aligned(16))) float As[2][GEMM_ROWS * GEMM_PS];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t w0 = (int64_t)blockIdx.x * GEMM_ROWS;
     const int nt = blockIdx.y * D1_WAVES + wave;       // this wave's output tile
     const bool live = nt < D1_TILES;
-
-    auto stage = [&](int kc, int buf) {
-        for (int e = tid; e < ROWS * (D1_KC / 4); e += D1_WAVES * 64) {
-            const int row = e / (D1_KC / 4), c4 = e - row * (D1_KC / 4);
-            const int64_t wr = w0 + row < n ? w0 + row : n - 1;
-            *reinterpret_cast<float4*>(&As[buf][row * PS + c4 * 4]) =
-                *reinterpret_cast<const float4*>(a + wr * K + (int64_t)kc * D1_KC + c4 * 4);
-        }
-    };
-
-    f32x16 acc[D1_MT];
-#pragma unroll
-    for (int t = 0; t < D1_MT; ++t)
-#pragma unroll
-        for (int q = 0; q < 16; ++q) acc[t][q] = 0.f;
-
-    stage(0, 0);
-    __syncthreads();
-    for (int kc = 0; kc < nchunks; ++kc) {
-        const int buf = kc & 1;
-        if (kc + 1 < nchunks) stage(kc + 1, buf ^ 1);
-        if (live) {
-            const float* pa = &As[buf][i * PS + h * (D1_KC / 2)];
-            const float4* pb = reinterpret_cast<const float4*>(wt) + ((int64_t)(kc * 2 + h) * (D1_KC / 8)) * D1_NPAD + nt * 32 + i;
-#pragma unroll
-            for (int q = 0; q < D1_KC / 8; ++q) {
-                const float4 bv = pb[(int64_t)q * D1_NPAD];
-                float4 av[D1_MT];
-#pragma unroll
-                for (int t = 0; t < D1_MT; ++t) av[t] = *reinterpret_cast<const float4*>(pa + t * 32 * PS + 4 * q);
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const float b = r == 0 ? bv.x : r == 1 ? bv.y : r == 2 ? bv.z : bv.w;
-#pragma unroll
-                    for (int t = 0; t < D1_MT; ++t) {
-                        const float av_r = r == 0 ? av[t].x : r == 1 ? av[t].y : r == 2 ? av[t].z : av[t].w;
-                        acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(av_r, b, acc[t], 0, 0, 0);
-                    }
-                }
-            }
-        }
-        __syncthreads();
-    }
-    const int col = nt * 32 + i;
+    f32x16 acc[2];
+    gemm_rows_tile<D1_WAVES>(a, wt, K, D1_NPAD, n, w0, nt, live, As, acc);
+    const int col = nt * 32 + (lane & 31);
     if (live && col < D1) {
         const float b = bias[col];
 #pragma unroll
-        for (int t = 0; t < D1_MT; ++t)
+        for (int t = 0; t < 2; ++t)
 #pragma unroll
             for (int q = 0; q < 16; ++q) {
-                const int64_t wr = w0 + t * 32 + (q & 3) + 8 * (q >> 2) + 4 * h;
+                const int64_t wr = w0 + t * 32 + acc_row(q, lane >> 5);
                 if (wr < n) out[wr * D1 + col] = fmaxf(acc[t][q] + b, 0.f);
             }
     }
@@ -941,7 +654,7 @@ __global__ __launch_bounds__(D1_WAVES * 64) void k_dense1_h16x3(const float* __r
         for (int t = 0; t < D1_MT; ++t)
 #pragma unroll
             for (int q = 0; q < 16; ++q) {
-                const int64_t wr = w0 + t * 32 + (q & 3) + 8 * (q >> 2) + 4 * h;
+                const int64_t wr = w0 + t * 32 + acc_row(q, h);
                 if (wr < n) out[wr * D1 + col] = fmaxf(fmaf(acc[t][q], S.cd, b), 0.f);
             }
     }
@@ -992,26 +705,6 @@ __global__ __launch_bounds__(256) void k_dense2_softmax(const float* __restrict_
     if (labels) labels[i] = s1 > s0 ? 1 : 0;   // ties -> 0 ("falling"), Evaluating.py:87
 }
 
-template <int CIN, int COUT, bool SAME, bool POOL, int WAVES, int NSPLIT>
-int launch_conv(f2_ctx* ctx, const float* in, const float* w, const float* b, float* out, int Hin, int Win, int64_t n) {
-    const int Ho = SAME ? Hin : Hin - 2, Wo = SAME ? Win : Win - 2;
-    const int row_pairs = POOL ? Ho / 2 : (Ho + 1) / 2;
-    const int wneed = POOL ? (Wo / 2) * 2 : Wo;
-    const int xtiles = (wneed + 31) / 32;
-    const int64_t tasks = n * row_pairs * xtiles;
-    if (tasks <= 0) return F2_OK;
-    constexpr int TPB = WAVES / NSPLIT;
-    constexpr size_t lds = sizeof(float) * TPB * 4 * PW * (CIN + 4);
-    auto kern = k_conv3x3_mfma<CIN, COUT, SAME, POOL, WAVES, NSPLIT>;
-    if (lds > 64 * 1024)
-        F2_HIP(ctx, hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    unsigned blocks;
-    F2_TRY(cnn_grid(ctx, (tasks + TPB - 1) / TPB, &blocks));
-    hipLaunchKernelGGL(kern, dim3(blocks), dim3(WAVES * 64), lds, ctx->stream, in, w, b, out, Hin, Win, n);
-    F2_HIP(ctx, hipGetLastError());
-    return F2_OK;
-}
-
 // conv1 + conv2 + pool of the per-tile kernels (conv1 is evaluated inside conv2's patch staging)
 int launch_conv12(f2_ctx* ctx, const f2_cnn* cnn, const f2_scale_set* S, bool split, const Dims& d, const float* d_x, int64_t n,
                   float* a2) {
@@ -1036,8 +729,8 @@ int launch_conv12(f2_ctx* ctx, const f2_cnn* cnn, const f2_scale_set* S, bool sp
 int launch_conv34(f2_ctx* ctx, const f2_cnn* cnn, const f2_scale_set* S, bool split, const Dims& d, const float* a2, int64_t n,
                   float* a3, float* a4) {
     if (d.Hp1 != 4) {
-        F2_TRY((launch_conv<C2, C3, true, false, 8, 2>(ctx, a2, cnn->t(4), cnn->t(5), a3, d.Hp1, d.Wp1, n)));
-        return launch_conv<C3, C4, false, true, 4, 2>(ctx, a3, cnn->t(6), cnn->t(7), a4, d.Hp1, d.Wp1, n);
+        F2_TRY((launch_conv3x3<C2, C3, 1, ST_PLAIN, EP_RELU, 8, 2>(ctx, a2, nullptr, cnn->t(4), cnn->t(5), a3, d.Hp1, d.Wp1, n)));
+        return launch_conv3x3<C3, C4, 0, ST_PLAIN, EP_POOL, 4, 2>(ctx, a3, nullptr, cnn->t(6), cnn->t(7), a4, d.Hp1, d.Wp1, n);
     }
     const int xtiles = d.xtiles34();
     unsigned blocks;

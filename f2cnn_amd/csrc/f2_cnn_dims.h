@@ -1,4 +1,5 @@
-// Shape arithmetic of K4 that f2_cnn.hip and f2_cnn_ws.hip have to agree on: layer widths, tile constants of the fused convolution
+// Shape arithmetic of K4 that f2_cnn.hip and f2_cnn_ws.hip have to agree on (f2_cnn_f32_tile.h beside it: the device pieces of
+// the float32 matrix-core kernels): layer widths, tile constants of the fused convolution
 // kernels and of dense1's weight layouts, the sizes of every layer's output for a rows x channels window, the index rule of the
 // MFMA B operand and the launcher of the thread-per-element kernels.
 #ifndef F2_CNN_DIMS_H

@@ -9,30 +9,28 @@
 // Backward chain (all float32, fixed summation order, no atomics):
 //   k_grad_dense2     g5 = P (1 - P) (W2[:,1] - W2[:,0]) where a5 > 0, rows padded with zeros to GK = 576
 //   k_gemm_rows       dense1 transposed: (n x 576) . W1T (576 x flat)
-//   k_gconv UNPOOL/MASK   conv4 transposed: the un-pool of the flat gradient through a4 happens while the patch is staged, the conv3
-//                         mask (a3 > 0) in the epilogue
-//   k_gconv PLAIN/NONE    conv3 transposed
-//   k_gconv UNPOOL/MASK   conv2 transposed: un-pool through a2 in the staging, conv1 mask (a1 > 0) in the epilogue
+//   k_conv3x3_f32 UNPOOL/MASK   conv4 transposed: the un-pool of the flat gradient through a4 happens while the patch is staged,
+//                               the conv3 mask (a3 > 0) in the epilogue
+//   k_conv3x3_f32 PLAIN/NONE    conv3 transposed
+//   k_conv3x3_f32 UNPOOL/MASK   conv2 transposed: un-pool through a2 in the staging, conv1 mask (a1 > 0) in the epilogue
 //   k_conv1_bwd       conv1 transposed (32 -> 1), VALU
 //   k_grad_profile    profile[w][c] = {sum_r G x, sum_r |G|} in float64
 // Backward-data of a 3 x 3 convolution with padding p is a 3 x 3 convolution with padding 2 - p whose kernel is the forward one
-// rotated by 180 degrees with Cin and Cout swapped: k_gconv is one implicit-GEMM template for the forward layers and for the
-// transposed ones, with k_conv3x3_mfma's tiling (one task = 2 output rows x 32 columns of one window, its 4 x 34 x CIN patch in LDS
-// at a (CIN + 4)-float pitch). The transposed weights are built from cnn->blob on an f2_cnn's first gradient call.
+// rotated by 180 degrees with Cin and Cout swapped: k_conv3x3_f32 (f2_cnn_f32_tile.h, which describes the tile) is one implicit-GEMM
+// template for the forward layers, here and in f2_cnn.hip's layer-by-layer route, and for the transposed ones. k_gemm_rows is the
+// row GEMM of that header. The transposed weights are built from cnn->blob on an f2_cnn's first gradient call.
 // Host side: every launch of the forward and of the chain is a step of f2_grad_chain (f2_cnn_train.h), defined once below;
 // f2_launch_cnn_input_gradient here and the training step of f2_cnn_train.hip are two drivers over those steps.
 // gfx950, wave64. Everything that reaches memory is written by plain C++ stores.
 #include <algorithm>
 #include <cmath>
 
-#include "f2_cnn_dims.h"
+#include "f2_cnn_f32_tile.h"
 #include "f2_cnn_train.h"
-#include "f2_cnn_unpool.h"
 
 namespace {
 
 constexpr int GEMM_WAVES = 4;    // waves (output tiles) of a k_gemm_rows workgroup
-constexpr int GEMM_ROWS = 64;    // windows of a k_gemm_rows workgroup (two M tiles)
 constexpr int64_t GRAD_WS_BYTES = int64_t(1) << 30;   // everything the chain holds between kernels
 constexpr int64_t GRAD_WS_CHUNK = 1024;               // windows of a chunk, at most
 
@@ -87,144 +85,6 @@ __global__ __launch_bounds__(256) void k_pool2x2(const float* __restrict__ a, fl
     *reinterpret_cast<float4*>(p + pix * CH + c4 * 4) = o;
 }
 
-// ---- 3 x 3 convolution with padding PAD (0 'valid', 1 'same', 2 'full') as an implicit GEMM on v_mfma_f32_32x32x2_f32 ----
-// Output (Hin + 2 PAD - 2) x (Win + 2 PAD - 2) x COUT. NSPLIT waves share one task (one patch), each takes COUT / 32 / NSPLIT of
-// the output tiles (k_conv3x3_mfma's scheme; w is that kernel's B operand wt[tap][h][s/4][cout][s%4]).
-//   ST_PLAIN   the input is `in` (n, Hin, Win, CIN)
-//   ST_UNPOOL  the input is the un-pooled gradient of a 2 x 2 max-pool: `in` (n, Hin/2, Win/2, CIN) the gradient of the pooled
-//              tensor, `act` (n, Hin, Win, CIN) the pool's post-ReLU input; rows / columns the pool dropped are zero
-//   EP_RELU    out = max(acc + aux[cout], 0)                     (aux: the layer's biases)
-//   EP_MASK    out = aux[same index as out] > 0 ? acc : 0        (aux: the post-ReLU activations of the layer the gradient enters)
-//   EP_NONE    out = acc
-template <int CIN, int COUT, int PAD, int STAGE, int EPI, int WAVES, int NSPLIT>
-__global__ __launch_bounds__(WAVES * 64) void k_gconv(const float* __restrict__ in, const float* __restrict__ act, const float* __restrict__ w,
-                                                      const float* __restrict__ aux, float* __restrict__ out, int Hin, int Win,
-                                                      int64_t nwin) {
-    constexpr int PS = CIN + 4;
-    constexpr int PATCH = 4 * PW * PS;
-    constexpr int NT = COUT / 32 / NSPLIT;
-    constexpr int TPB = WAVES / NSPLIT;
-    constexpr int Q4 = CIN / 4;
-    constexpr int HALF = CIN / 2;
-    static_assert(NT >= 1 && TPB >= 1 && CIN % 8 == 0, "tile shape");
-    extern __shared__ __attribute__((aligned(16))) float lds_all[];
-
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int ns = wave % NSPLIT;
-    float* patch = lds_all + (wave / NSPLIT) * PATCH;
-
-    const int Ho = Hin + 2 * PAD - 2, Wo = Win + 2 * PAD - 2;
-    const int row_pairs = (Ho + 1) / 2, xtiles = (Wo + 31) / 32;
-    const int64_t tasks = nwin * row_pairs * xtiles;
-    int64_t task = (int64_t)blockIdx.x * TPB + wave / NSPLIT;
-    const bool live = task < tasks;
-    if (!live) task = tasks - 1;
-    const int xt = (int)(task % xtiles);
-    const int64_t t2 = task / xtiles;
-    const int rp = (int)(t2 % row_pairs);
-    const int64_t win = t2 / row_pairs;
-    const int y0 = 2 * rp, x0 = 32 * xt;
-
-    const int Hp = Hin / 2, Wp = Win / 2;   // (ST_UNPOOL)
-    const float* img = in + win * (STAGE == ST_UNPOOL ? (int64_t)Hp * Wp : (int64_t)Hin * Win) * CIN;
-    const float* aimg = STAGE == ST_UNPOOL ? act + win * (int64_t)Hin * Win * CIN : nullptr;
-#pragma unroll 2
-    for (int e = lane + 64 * ns; e < 4 * PW * Q4; e += 64 * NSPLIT) {
-        const int r = e / (PW * Q4);
-        const int rem = e - r * (PW * Q4);
-        const int p = rem / Q4, c4 = rem - p * Q4;
-        const int yi = y0 - PAD + r, xi = x0 - PAD + p;
-        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if constexpr (STAGE == ST_PLAIN) {
-            if (yi >= 0 && yi < Hin && xi >= 0 && xi < Win) v = *reinterpret_cast<const float4*>(img + ((int64_t)yi * Win + xi) * CIN + c4 * 4);
-        } else {
-            const int py = yi >> 1, px = xi >> 1;
-            if (yi >= 0 && xi >= 0 && py < Hp && px < Wp) {
-                const float4 g = *reinterpret_cast<const float4*>(img + ((int64_t)py * Wp + px) * CIN + c4 * 4);
-                const float* s = aimg + ((int64_t)(2 * py) * Win + 2 * px) * CIN + c4 * 4;
-                const float4 v00 = *reinterpret_cast<const float4*>(s), v01 = *reinterpret_cast<const float4*>(s + CIN);
-                const float4 v10 = *reinterpret_cast<const float4*>(s + (int64_t)Win * CIN);
-                const float4 v11 = *reinterpret_cast<const float4*>(s + (int64_t)Win * CIN + CIN);
-                const int me = (yi & 1) * 2 + (xi & 1);
-                v.x = unpool_pick(g.x, v00.x, v01.x, v10.x, v11.x, me);
-                v.y = unpool_pick(g.y, v00.y, v01.y, v10.y, v11.y, me);
-                v.z = unpool_pick(g.z, v00.z, v01.z, v10.z, v11.z, me);
-                v.w = unpool_pick(g.w, v00.w, v01.w, v10.w, v11.w, me);
-            }
-        }
-        *reinterpret_cast<float4*>(patch + (r * PW + p) * PS + c4 * 4) = v;
-    }
-    __syncthreads();
-
-    f32x16 acc[2][NT];
-#pragma unroll
-    for (int rr = 0; rr < 2; ++rr)
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-            for (int q = 0; q < 16; ++q) acc[rr][nt][q] = 0.f;
-
-    // lane = (pixel i, half h); step s of a tap multiplies channels s (h = 0) and HALF + s (h = 1); operands one step ahead
-    const int i = lane & 31, h = lane >> 5;
-    const float* pa0 = patch + i * PS + h * HALF;
-    const float4* wq = reinterpret_cast<const float4*>(w) + (int64_t)h * (HALF / 4) * COUT + ns * NT * 32 + i;
-    constexpr int QN = HALF / 4, NIT = 9 * QN;
-    float4 av0[2], av1[2], bq[2][NT];
-    auto fetch = [&](int it, int buf) {
-        const int tap = it / QN, q = it - tap * QN;
-        const int dy = tap / 3, dx = tap - dy * 3;
-        const float* pa = pa0 + (dy * PW + dx) * PS;
-        const float4* pb = wq + (int64_t)tap * 2 * QN * COUT;
-        av0[buf] = *reinterpret_cast<const float4*>(pa + 4 * q);
-        av1[buf] = *reinterpret_cast<const float4*>(pa + PW * PS + 4 * q);
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) bq[buf][nt] = pb[(int64_t)q * COUT + nt * 32];
-    };
-    fetch(0, 0);
-#pragma unroll
-    for (int it = 0; it < NIT; ++it) {
-        const int cur = it & 1;
-        if (it + 1 < NIT) fetch(it + 1, cur ^ 1);
-        __builtin_amdgcn_sched_barrier(0);
-        const float a0v[4] = {av0[cur].x, av0[cur].y, av0[cur].z, av0[cur].w};
-        const float a1v[4] = {av1[cur].x, av1[cur].y, av1[cur].z, av1[cur].w};
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt) {
-                const float4 bb = bq[cur][nt];
-                const float bv = r == 0 ? bb.x : r == 1 ? bb.y : r == 2 ? bb.z : bb.w;
-                acc[0][nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0v[r], bv, acc[0][nt], 0, 0, 0);
-                acc[1][nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1v[r], bv, acc[1][nt], 0, 0, 0);
-            }
-        }
-        __builtin_amdgcn_sched_barrier(0);
-    }
-
-    if (!live) return;
-    const int64_t obase = win * (int64_t)Ho * Wo * COUT;
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt) {
-        const int co = (ns * NT + nt) * 32 + i;
-        const float bv = EPI == EP_RELU ? aux[co] : 0.f;
-#pragma unroll
-        for (int rr = 0; rr < 2; ++rr) {
-            const int y = y0 + rr;
-#pragma unroll
-            for (int q = 0; q < 16; ++q) {
-                const int xo = x0 + (q & 3) + 8 * (q >> 2) + 4 * h;
-                if (y < Ho && xo < Wo) {
-                    const int64_t idx = obase + ((int64_t)y * Wo + xo) * COUT + co;
-                    float v = acc[rr][nt][q];
-                    if constexpr (EPI == EP_RELU) v = fmaxf(v + bv, 0.f);
-                    if constexpr (EPI == EP_MASK) v = aux[idx] > 0.f ? v : 0.f;
-                    out[idx] = v;
-                }
-            }
-        }
-    }
-}
-
 // ---- g5 (n, GK): the gradient of P = softmax(z)[1] at dense1's pre-activations ----
 // dP/dz1 = -dP/dz0 = P (1 - P) = s0 s1 with the recorded scores (the product keeps its precision where P is close to 1)
 __global__ __launch_bounds__(256) void k_grad_dense2(const float* __restrict__ a5, const float* __restrict__ scores, const float* __restrict__ w2,
@@ -238,66 +98,23 @@ __global__ __launch_bounds__(256) void k_grad_dense2(const float* __restrict__ a
     g5[t] = g;
 }
 
-// ---- out (n, N) = a (n, K) . w (K, N), K a multiple of 64 and N of 32: k_dense1_mfma's tiling without bias and ReLU ----
-// One workgroup = 64 rows x GEMM_WAVES output tiles; w is wt[chunk][h][q][n][4], k = 64 chunk + 32 h + 4 q + e.
+// ---- out (n, N) = a (n, K) . w (K, N), K a multiple of 64 and N of 32: gemm_rows_tile (k_dense1_mfma's body), stored plain ----
 __global__ __launch_bounds__(GEMM_WAVES * 64) void k_gemm_rows(const float* __restrict__ a, const float* __restrict__ wt, float* __restrict__ out,
                                                                int K, int N, int64_t n) {
-    constexpr int KC = 64, PS = KC + 4;
-    __shared__ __attribute__((aligned(16))) float As[2][GEMM_ROWS * PS];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    __shared__ __attribute__((aligned(16))) float As[2][GEMM_ROWS * GEMM_PS];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int64_t w0 = (int64_t)blockIdx.x * GEMM_ROWS;
-    const int i = lane & 31, h = lane >> 5;
-    const int nchunks = K / KC;
     const int nt = blockIdx.y * GEMM_WAVES + wave;
     const bool live = nt < N / 32;
-
-    auto stage = [&](int kc, int buf) {
-        for (int e = tid; e < GEMM_ROWS * (KC / 4); e += GEMM_WAVES * 64) {
-            const int row = e / (KC / 4), c4 = e - row * (KC / 4);
-            const int64_t wr = w0 + row < n ? w0 + row : n - 1;
-            *reinterpret_cast<float4*>(&As[buf][row * PS + c4 * 4]) = *reinterpret_cast<const float4*>(a + wr * K + (int64_t)kc * KC + c4 * 4);
-        }
-    };
     f32x16 acc[2];
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int q = 0; q < 16; ++q) acc[t][q] = 0.f;
-
-    stage(0, 0);
-    __syncthreads();
-    for (int kc = 0; kc < nchunks; ++kc) {
-        const int buf = kc & 1;
-        if (kc + 1 < nchunks) stage(kc + 1, buf ^ 1);
-        if (live) {
-            const float* pa = &As[buf][i * PS + h * (KC / 2)];
-            const float4* pb = reinterpret_cast<const float4*>(wt) + ((int64_t)(kc * 2 + h) * (KC / 8)) * N + nt * 32 + i;
-#pragma unroll
-            for (int q = 0; q < KC / 8; ++q) {
-                const float4 bv = pb[(int64_t)q * N];
-                float4 av[2];
-#pragma unroll
-                for (int t = 0; t < 2; ++t) av[t] = *reinterpret_cast<const float4*>(pa + t * 32 * PS + 4 * q);
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const float b = r == 0 ? bv.x : r == 1 ? bv.y : r == 2 ? bv.z : bv.w;
-#pragma unroll
-                    for (int t = 0; t < 2; ++t) {
-                        const float av_r = r == 0 ? av[t].x : r == 1 ? av[t].y : r == 2 ? av[t].z : av[t].w;
-                        acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(av_r, b, acc[t], 0, 0, 0);
-                    }
-                }
-            }
-        }
-        __syncthreads();
-    }
+    gemm_rows_tile<GEMM_WAVES>(a, wt, K, N, n, w0, nt, live, As, acc);
     if (!live) return;
-    const int col = nt * 32 + i;
+    const int col = nt * 32 + (lane & 31);
 #pragma unroll
     for (int t = 0; t < 2; ++t)
 #pragma unroll
         for (int q = 0; q < 16; ++q) {
-            const int64_t wr = w0 + t * 32 + (q & 3) + 8 * (q >> 2) + 4 * h;
+            const int64_t wr = w0 + t * 32 + acc_row(q, lane >> 5);
             if (wr < n) out[wr * N + col] = acc[t][q];
         }
 }
@@ -413,23 +230,6 @@ __global__ __launch_bounds__(TT) void k_saliency_map(const double* __restrict__ 
         t[1] = rows > 0 ? sum / (double)rows : none;
         t[2] = rows > 0 ? sum_abs / (double)rows : none;
     }
-}
-
-template <int CIN, int COUT, int PAD, int STAGE, int EPI, int WAVES, int NSPLIT>
-int launch_gconv(f2_ctx* ctx, const float* in, const float* act, const float* w, const float* aux, float* out, int Hin, int Win, int64_t n) {
-    const int Ho = Hin + 2 * PAD - 2, Wo = Win + 2 * PAD - 2;
-    const int64_t tasks = n * ((Ho + 1) / 2) * ((Wo + 31) / 32);
-    if (tasks <= 0) return F2_OK;
-    constexpr int TPB = WAVES / NSPLIT;
-    constexpr size_t lds = sizeof(float) * TPB * 4 * PW * (CIN + 4);
-    static_assert(lds <= 160 * 1024, "a workgroup's patches fit the CU's LDS");
-    auto kern = k_gconv<CIN, COUT, PAD, STAGE, EPI, WAVES, NSPLIT>;
-    if (lds > 64 * 1024) F2_HIP(ctx, hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    unsigned blocks;
-    F2_TRY(cnn_grid(ctx, (tasks + TPB - 1) / TPB, &blocks));
-    hipLaunchKernelGGL(kern, dim3(blocks), dim3(WAVES * 64), lds, ctx->stream, in, act, w, aux, out, Hin, Win, n);
-    F2_HIP(ctx, hipGetLastError());
-    return F2_OK;
 }
 
 // ---- the weights of the transposed layers, from cnn->blob (both in cnn_b_operand_index's layout) ----
@@ -549,13 +349,13 @@ int f2_grad_chain_open(f2_ctx* ctx, const f2_cnn* cnn, int64_t n, bool need_back
 // ---- the steps of the chain: every launch of the recorded forward and of the backward-data pass stands here, once ----
 int f2_grad_chain::conv12(const float* x, int64_t m) const {
     F2_TRY(launch256(ctx, k_conv1_fwd, m * d.H1 * d.W1 * (C1 / 4), x, cnn->t(0), cnn->t(1), arr[A1], d.H1, d.W1, m));
-    F2_TRY((launch_gconv<C1, C2, 0, ST_PLAIN, EP_RELU, 4, 1>(ctx, arr[A1], nullptr, cnn->t(2), cnn->t(3), arr[A2], d.H1, d.W1, m)));
+    F2_TRY((launch_conv3x3<C1, C2, 0, ST_PLAIN, EP_RELU, 4, 1>(ctx, arr[A1], nullptr, cnn->t(2), cnn->t(3), arr[A2], d.H1, d.W1, m)));
     return launch256(ctx, k_pool2x2, m * d.Hp1 * d.Wp1 * (C2 / 4), arr[A2], arr[P1], d.H2, d.W2, C2, m);
 }
 
 int f2_grad_chain::conv34(int64_t m) const {
-    F2_TRY((launch_gconv<C2, C3, 1, ST_PLAIN, EP_RELU, 4, 2>(ctx, arr[P1], nullptr, cnn->t(4), cnn->t(5), arr[A3], d.Hp1, d.Wp1, m)));
-    F2_TRY((launch_gconv<C3, C4, 0, ST_PLAIN, EP_RELU, 4, 2>(ctx, arr[A3], nullptr, cnn->t(6), cnn->t(7), arr[A4], d.Hp1, d.Wp1, m)));
+    F2_TRY((launch_conv3x3<C2, C3, 1, ST_PLAIN, EP_RELU, 4, 2>(ctx, arr[P1], nullptr, cnn->t(4), cnn->t(5), arr[A3], d.Hp1, d.Wp1, m)));
+    F2_TRY((launch_conv3x3<C3, C4, 0, ST_PLAIN, EP_RELU, 4, 2>(ctx, arr[A3], nullptr, cnn->t(6), cnn->t(7), arr[A4], d.Hp1, d.Wp1, m)));
     return launch256(ctx, k_pool2x2, m * d.Hp2 * d.Wp2 * (C4 / 4), arr[A4], arr[P2], d.H4, d.W4, C4, m);
 }
 
@@ -572,15 +372,15 @@ int f2_grad_chain::dense1T(int64_t m) const {
 }
 
 int f2_grad_chain::conv4T(int64_t m) const {
-    return launch_gconv<C4, C3, 2, ST_UNPOOL, EP_MASK, 4, 2>(ctx, arr[GP2], arr[A4], gw + goff[2], arr[A3], arr[G3], d.H4, d.W4, m);
+    return launch_conv3x3<C4, C3, 2, ST_UNPOOL, EP_MASK, 4, 2>(ctx, arr[GP2], arr[A4], gw + goff[2], arr[A3], arr[G3], d.H4, d.W4, m);
 }
 
 int f2_grad_chain::conv3T(int64_t m) const {
-    return launch_gconv<C3, C2, 1, ST_PLAIN, EP_NONE, 2, 1>(ctx, arr[G3], nullptr, gw + goff[1], nullptr, arr[GP1], d.Hp1, d.Wp1, m);
+    return launch_conv3x3<C3, C2, 1, ST_PLAIN, EP_NONE, 2, 1>(ctx, arr[G3], nullptr, gw + goff[1], nullptr, arr[GP1], d.Hp1, d.Wp1, m);
 }
 
 int f2_grad_chain::conv2T(int64_t m) const {
-    return launch_gconv<C2, C1, 2, ST_UNPOOL, EP_MASK, 4, 1>(ctx, arr[GP1], arr[A2], gw + goff[0], arr[A1], arr[G1], d.H2, d.W2, m);
+    return launch_conv3x3<C2, C1, 2, ST_UNPOOL, EP_MASK, 4, 1>(ctx, arr[GP1], arr[A2], gw + goff[0], arr[A1], arr[G1], d.H2, d.W2, m);
 }
 
 int f2_grad_chain::conv1T(float* G, int64_t m) const {

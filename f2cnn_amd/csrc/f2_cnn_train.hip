@@ -7,9 +7,9 @@
 //   k_loss_seed        g5 = [a5 > 0] / keep (dz0 W2[k][0] + dz1 W2[k][1]), padded like k_grad_dense2's
 //   k_mask_scale       the backward factor of a dropout layer: g = p > 0 ? g / keep : 0
 //   k_wgrad_conv       conv2 .. conv4: dW[tap][ci][co] = sum over windows and pixels of in[pixel + tap][ci] g[pixel][co] on
-//                      v_mfma_f32_32x32x2_f32 with the pixel as the MFMA's k; k_gconv's task (2 output rows x 32 columns of one
-//                      window, its 4 x 34 x CIN patch in LDS at a (CIN + 4) pitch) and beside it the task's 64 x COUT gradient
-//                      tile, un-pooled while it is staged for conv2 / conv4. Wave w of a workgroup takes the kernel row w % 3 and
+//                      v_mfma_f32_32x32x2_f32 with the pixel as the MFMA's k; the task and the patch of f2_cnn_f32_tile.h
+//                      (stage_patch) and beside the patch the task's 64 x COUT gradient tile, un-pooled while it is staged
+//                      for conv2 / conv4 (unpool4). Wave w of a workgroup takes the kernel row w % 3 and
 //                      the w / 3-th share of the output channels. The layer's bias gradient is the column sum of the same tile.
 //   k_wgrad_conv1      conv1 (Cin = 1) and its bias on the VALU, float64
 //   k_wgrad_dense1     p2^T g5 on the float64 matrix cores (exact products, float64 sums), the window as the MFMA's k
@@ -26,8 +26,8 @@
 #include <algorithm>
 #include <cmath>
 
+#include "f2_cnn_f32_tile.h"
 #include "f2_cnn_train.h"
-#include "f2_cnn_unpool.h"
 #include "f2_philox.h"
 
 namespace {
@@ -172,7 +172,7 @@ __global__ __launch_bounds__(3 * COSPLIT * 64) void k_wgrad_conv(const float* __
     constexpr int NTHR = 3 * COSPLIT * 64;
     constexpr int PS = CIN + 4, GS = COUT + 4;
     constexpr int CIT = CIN / 32, COT = COUT / 32 / COSPLIT;
-    constexpr int Q4 = CIN / 4, QG = COUT / 4;
+    constexpr int QG = COUT / 4;
     constexpr int BPARTS = NTHR / COUT;   // the bias sum: thread (bpart, bco) adds every BPARTS-th pixel of column bco
     static_assert(COT >= 1 && CIN % 32 == 0 && COUT % 32 == 0 && NTHR % COUT == 0 && BPARTS * COUT <= 64 * GS, "tile shape");
     __shared__ __attribute__((aligned(16))) float patch[4 * PW * PS];
@@ -188,8 +188,9 @@ __global__ __launch_bounds__(3 * COSPLIT * 64) void k_wgrad_conv(const float* __
     const int64_t win = blockIdx.x / gpw;
     const int first = (int)(blockIdx.x % gpw) * per;
     const int last = first + per < tpw ? first + per : tpw;
-    const int Hp = Ho / 2, Wp = Wo / 2;   // (ST_UNPOOL)
     const float* img = in + win * (int64_t)Hin * Win * CIN;
+    const float* gimg = g + win * (STAGE == ST_UNPOOL ? (int64_t)(Ho / 2) * (Wo / 2) : (int64_t)Ho * Wo) * COUT;
+    const float* aimg = STAGE == ST_UNPOOL ? act + win * (int64_t)Ho * Wo * COUT : nullptr;
 
     f32x16 acc[3][CIT][COT];
 #pragma unroll
@@ -205,37 +206,15 @@ __global__ __launch_bounds__(3 * COSPLIT * 64) void k_wgrad_conv(const float* __
     for (int task = first; task < last; ++task) {
         const int xt = task % xtiles, rp = task / xtiles;
         const int y0 = 2 * rp, x0 = 32 * xt;
-        for (int e = tid; e < 4 * PW * Q4; e += NTHR) {
-            const int r = e / (PW * Q4);
-            const int rem = e - r * (PW * Q4);
-            const int p = rem / Q4, c4 = rem - p * Q4;
-            const int yi = y0 - PAD + r, xi = x0 - PAD + p;
-            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (yi >= 0 && yi < Hin && xi >= 0 && xi < Win) v = *reinterpret_cast<const float4*>(img + ((int64_t)yi * Win + xi) * CIN + c4 * 4);
-            *reinterpret_cast<float4*>(patch + (r * PW + p) * PS + c4 * 4) = v;
-        }
+        stage_patch<4, CIN>(patch, img, nullptr, Hin, Win, y0 - PAD, x0 - PAD, tid, NTHR);
         for (int e = tid; e < 64 * QG; e += NTHR) {
             const int pix = e / QG, c4 = e - pix * QG;
             const int yo = y0 + (pix >> 5), xo = x0 + (pix & 31);
             float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (yo < Ho && xo < Wo) {
-                if constexpr (STAGE == ST_PLAIN) {
-                    v = *reinterpret_cast<const float4*>(g + ((win * Ho + yo) * (int64_t)Wo + xo) * COUT + c4 * 4);
-                } else {
-                    const int py = yo >> 1, px = xo >> 1;
-                    if (py < Hp && px < Wp) {
-                        const float4 gv = *reinterpret_cast<const float4*>(g + ((win * Hp + py) * (int64_t)Wp + px) * COUT + c4 * 4);
-                        const float* s = act + ((win * Ho + 2 * py) * (int64_t)Wo + 2 * px) * COUT + c4 * 4;
-                        const float4 v00 = *reinterpret_cast<const float4*>(s), v01 = *reinterpret_cast<const float4*>(s + COUT);
-                        const float4 v10 = *reinterpret_cast<const float4*>(s + (int64_t)Wo * COUT);
-                        const float4 v11 = *reinterpret_cast<const float4*>(s + (int64_t)Wo * COUT + COUT);
-                        const int me = (yo & 1) * 2 + (xo & 1);
-                        v.x = unpool_pick(gv.x, v00.x, v01.x, v10.x, v11.x, me);
-                        v.y = unpool_pick(gv.y, v00.y, v01.y, v10.y, v11.y, me);
-                        v.z = unpool_pick(gv.z, v00.z, v01.z, v10.z, v11.z, me);
-                        v.w = unpool_pick(gv.w, v00.w, v01.w, v10.w, v11.w, me);
-                    }
-                }
+            if constexpr (STAGE == ST_PLAIN) {
+                if (yo < Ho && xo < Wo) v = *reinterpret_cast<const float4*>(gimg + ((int64_t)yo * Wo + xo) * COUT + c4 * 4);
+            } else {
+                v = unpool4<COUT>(gimg, aimg, Ho, Wo, yo, xo, c4);
             }
             *reinterpret_cast<float4*>(gt + pix * GS + c4 * 4) = v;
         }
@@ -274,7 +253,7 @@ __global__ __launch_bounds__(3 * COSPLIT * 64) void k_wgrad_conv(const float* __
             for (int b = 0; b < COT; ++b)
 #pragma unroll
                 for (int q = 0; q < 16; ++q) {
-                    const int ci = a * 32 + (q & 3) + 8 * (q >> 2) + 4 * h;
+                    const int ci = a * 32 + acc_row(q, h);
                     const int co = (cs * COT + b) * 32 + i;
                     P[((dy * 3 + dx) * CIN + ci) * COUT + co] = acc[dx][a][b][q];
                 }

@@ -21,8 +21,10 @@ from f2cnn_amd.model import F2CNNModel
 
 # (rows, channels, n) of tests/test_gpu_cnn_layers.py. Shapes the weight-stationary kernels take ...
 WS_CASES = ((10, 18, 33), (11, 18, 97), (10, 35, 33), (11, 36, 33), (11, 66, 33), (11, 68, 33), (11, 70, 33), (11, 128, 193), (11, 403, 9))
-# ... and shapes they refuse: one past their width limit, too narrow for them, and pooled heights other than four
-OFF_WS_CASES = ((11, 404, 9), (11, 16, 33), (13, 40, 33), (12, 21, 33), (14, 24, 33), (18, 20, 33))
+# ... and shapes they refuse: one past their width limit, too narrow for them, and pooled heights other than four. 13 x 76 (pooled
+# 5 x 37) gives the layer-by-layer forward a second x-tile: five conv3 columns and one pooled conv4 column in it, an odd last conv3
+# row pair and a conv4 row the pool drops.
+OFF_WS_CASES = ((11, 404, 9), (11, 16, 33), (13, 40, 33), (12, 21, 33), (14, 24, 33), (18, 20, 33), (13, 76, 9))
 # the shapes that also run with inputs up to 2^10 (kind "big")
 BIG_CASES = ((11, 70, 33), (13, 40, 33))
 ALL = tuple((c, "unit") for c in WS_CASES + OFF_WS_CASES) + tuple((c, "big") for c in BIG_CASES)

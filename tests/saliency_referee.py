@@ -22,10 +22,10 @@ TOL = 5e-6       # four times the largest no-flip error of the float32 CPU chain
 MARGIN = 1e-5
 CAP = 0.02       # one flipped window in 128 was the most the float32 CPU chain showed: under 1 %
 # (seed, xseed, rows, channels, n) of the GPU tests; tests/test_saliency_referee.py holds the float32 CPU chain to the rule on them
-# The two tall shapes are those of train_referee.CASES, where the training step reuses this backward chain (k_gconv) with many row
+# The two tall shapes are those of train_referee.CASES, where the training step reuses this backward chain (k_conv3x3_f32) with many row
 # pairs per window. At these sizes every window's margin is <= MARGIN, so the margin excuses nothing and excludes nothing: what binds
 # is CAP and TOL - at most one window of 64 may lie beyond TOL (the float32 CPU chain: 0 of 64 at either shape, largest e_w 5.5e-7).
-# A failure here without one in test_gpu_loss_gradient.py's cases of the same shapes places a fault in k_gconv, not in the
+# A failure here without one in test_gpu_loss_gradient.py's cases of the same shapes places a fault in k_conv3x3_f32, not in the
 # weight-gradient kernels.
 CASES = ((7, 9, 13, 40, 256), (7, 9, 10, 100, 128), (5, 4, 11, 128, 128), (7, 9, 18, 20, 128),   # (18 x 20: three pooled rows into dense1)
          (7, 9, 75, 21, 64), (7, 9, 36, 35, 64))

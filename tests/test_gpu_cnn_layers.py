@@ -6,6 +6,8 @@ kernels change tile counts, branches or routes - and the entry's own promises: a
 Measured on an MI355X, worst e_w over all shapes and both input kinds (the float32 CPU chain has 6.7e-7; TOL32 = 2.68e-6, the split
 layers get twice that): float32 kernels and recorded forward 1.32e-6 pooled / 1.81e-6 dense1, per-tile split kernels 1.29e-6 /
 1.58e-6, weight-stationary kernels 6.5e-7 / 1.49e-6 with either dense1; scores within 7.3e-8. Per shape: DESIGN.md, "K4 per element".
+13 x 76 x 9, the one shape with a second x-tile in the layer-by-layer float32 kernels: float32 kernels and recorded forward 8.5e-7 /
+6.0e-7, per-tile split route (float32 conv3 / conv4) 6.7e-7 / 1.45e-6, scores within 5.0e-8; the float32 CPU chain 3.0e-7 / 3.5e-7.
 """
 import numpy as np
 import pytest
@@ -172,10 +174,17 @@ def test_recorded_route_is_the_gradient_chains_forward(ctx):
         assert a[1000:].tobytes() == b.tobytes()
     assert whole[2].tobytes() == m.input_gradient(x, ctx=ctx)[1].tobytes()
     f32 = m.layers(x, "f32", ctx=ctx)
-    # other convolution kernels, the same network. (k_gconv keeps k_conv3x3_mfma's tiling and summation order: on an MI355X its
-    # pooled output came out bit-identical to the float32 route's on every shape of this file, which nothing promises)
-    print("recorded against the float32 route: pooled differs in {} of {} elements".format(int((whole[0] != f32[0]).sum()), whole[0].size))
     assert np.abs(whole[2] - f32[2]).max() <= 5e-7
+
+
+@pytest.mark.parametrize("case", lr.WS_CASES + lr.OFF_WS_CASES, ids=case_id)
+def test_recorded_route_has_the_float32_routes_bits(ctx, case):
+    """Other kernels, the same sums: conv1 is an fmaf chain in tap order on both routes, conv2 .. conv4 run the one 9-tap loop of
+    f2_cnn_f32_tile.h (conv_taps) whether fused or layer by layer, bias + ReLU commute with the max of the pool, and dense1 is
+    the same kernel. So pooled, dense1 and scores are the same bytes."""
+    recorded, f32 = device(ctx, case, "unit", "recorded"), device(ctx, case, "unit", "f32")
+    for name, a, b in zip(("pooled", "dense1", "scores"), recorded, f32):
+        assert a.tobytes() == b.tobytes(), "{} {}: {} of {} elements differ".format(case_id(case), name, int((a != b).sum()), a.size)
 
 
 def layers_raw(ctx, model, x, n, route, mem, want=(True, True, True), x_arg="x"):

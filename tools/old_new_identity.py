@@ -13,7 +13,9 @@ Cases: f2_filterbank_envelope_fused, f2_eval_batch, f2_eval_utterance (one utter
 11 x 128, 11 x 67, 10 x 100 and 13 x 40 under the options float32 / per-tile split / ws convolutions / ws convolutions + ws dense1,
 host and device memory, inputs in [0, 1), the same x 2^10, one window x 1e4 among normalised ones (the quiet-window route) and one
 NaN, last_input_bound in the digest; one host call of 16 384 + 70 windows whose second chunk is x 2^6; f2_cnn_score_windows with
-normalize 0 / 1 and three groups; the create-time *_check_diff values. The later entry points on small shapes
+normalize 0 / 1 and three groups; the create-time *_check_diff values; f2_cnn_layers on the forced routes f32 and recorded for
+13 x 40, 18 x 20, 14 x 24, 12 x 21 and 13 x 76 windows (pooled heights other than four, a second x-tile of the layer-by-layer kernels;
+profiles/r40_a_old_new_identity.txt). The later entry points on small shapes
 (profiles/r18_a_old_new_identity.txt; tests/test_gpu_output_placement.py: radius 5, step 160, utterances of 1761, 2500 and 1000
 samples, an 11 x 10 network, 8 channels for the pictures), host and device memory, every output in the digest:
 f2_eval_batch_strided at hop 1 and 160, f2_eval_noise_sweep with 2 levels and a fixed seed, f2_label_accuracy on its labels,
@@ -59,6 +61,7 @@ def digest(*arrays):
 
 
 CNN_SHAPES = [(11, 128), (11, 67), (10, 100), (13, 40)]
+LAYER_SHAPES = [(13, 40), (18, 20), (14, 24), (12, 21), (13, 76)]
 CNN_ROUTES = [("float32", 0, 0, 0), ("per-tile split", 1, 0, 0), ("ws convolutions", 1, 1, 0), ("ws convolutions + ws dense1", 1, 1, 1)]
 
 
@@ -128,6 +131,12 @@ def cnn_cases(ctx, res):
     ctx.cnn_forward(m.handle(ctx), x, len(x), sc, lb, _lib.MEM_HOST)
     res["f2_cnn_forward: 11 x 40, 16 384 + 70 windows in host memory, second chunk x 2^6"] = digest(
         sc, lb, np.float64(ctx.cnn_info(m.handle(ctx), "last_input_bound")))
+    # the float32 kernels layer by layer (three, five, six and eight pooled rows; 13 x 76: a second x-tile) and the recorded forward
+    for rows, ch in LAYER_SHAPES:
+        m = F2CNNModel.glorot(7, rows, ch, zero_bias=False)
+        x = np.random.default_rng(rows * ch + 1).random((33, rows, ch)).astype(np.float32)
+        for route in ("f32", "recorded"):
+            res[f"f2_cnn_layers: {rows} x {ch}, 33 windows, route {route}, host memory"] = digest(*m.layers(x, route, ctx=ctx))
 
 
 def entry_cases(ctx, res):

@@ -59,17 +59,17 @@ def chain_work(nwin):
     a1, a2, p1, a3, a4 = H1 * W1 * 32, H2 * W2 * 32, Hp1 * Wp1 * 32, Hp1 * Wp1 * 64, H4 * W4 * 64
     return {
         "k_conv1_fwd": (nwin * H1 * W1 * 9 * 32, f * (H1 * W1 + a1)),
-        "k_gconv<32, 32, 0, 0, 0": (nwin * H2 * W2 * 9 * 32 * 32, f * (a1 + a2)),
+        "k_conv3x3_f32<32, 32, 0, 0, 0": (nwin * H2 * W2 * 9 * 32 * 32, f * (a1 + a2)),
         "k_pool2x2": (0, None),
-        "k_gconv<32, 64, 1, 0, 0": (nwin * Hp1 * Wp1 * 9 * 32 * 64, f * (p1 + a3)),
-        "k_gconv<64, 64, 0, 0, 0": (nwin * H4 * W4 * 9 * 64 * 64, f * (a3 + a4)),
+        "k_conv3x3_f32<32, 64, 1, 0, 0": (nwin * Hp1 * Wp1 * 9 * 32 * 64, f * (p1 + a3)),
+        "k_conv3x3_f32<64, 64, 0, 0, 0": (nwin * H4 * W4 * 9 * 64 * 64, f * (a3 + a4)),
         "k_dense1_mfma": (nwin * flat * 544, f * (flat + 516)),
         "k_dense2_softmax": (nwin * 516 * 2, f * 518),
         "k_grad_dense2": (nwin * 516, f * (516 + 576)),
         "k_gemm_rows": (nwin * 576 * flat, f * (576 + flat)),
-        "k_gconv<64, 64, 2, 1, 1": (nwin * Hp1 * Wp1 * 9 * 64 * 64, f * (flat + a4 + 2 * a3)),
-        "k_gconv<64, 32, 1, 0, 2": (nwin * Hp1 * Wp1 * 9 * 64 * 32, f * (a3 + p1)),
-        "k_gconv<32, 32, 2, 1, 1": (nwin * H1 * W1 * 9 * 32 * 32, f * (p1 + a2 + 2 * a1)),
+        "k_conv3x3_f32<64, 64, 2, 1, 1": (nwin * Hp1 * Wp1 * 9 * 64 * 64, f * (flat + a4 + 2 * a3)),
+        "k_conv3x3_f32<64, 32, 1, 0, 2": (nwin * Hp1 * Wp1 * 9 * 64 * 32, f * (a3 + p1)),
+        "k_conv3x3_f32<32, 32, 2, 1, 1": (nwin * H1 * W1 * 9 * 32 * 32, f * (p1 + a2 + 2 * a1)),
         "k_conv1_bwd": (nwin * H1 * W1 * 9 * 32, f * (a1 + H1 * W1)),
         "k_grad_profile": (0, nwin * (8 * H1 * W1 + 16 * W1)),
     }
@@ -80,7 +80,7 @@ def fold_kernel_stats(path, nwin, calls):
     work = chain_work(nwin)
     pool_bytes = 4 * nwin * ((R - 2) * (C - 2) * 32 * 1.25 + ((R - 2) // 2 - 2) * ((C - 2) // 2 - 2) * 64 * 1.25)
     out, total = [], 0.0
-    def mangled(k):      # "k_gconv<32, 32, 0, 0, 0" as the statistics name it when they keep the mangled symbol
+    def mangled(k):      # "k_conv3x3_f32<32, 32, 0, 0, 0" as the statistics name it when they keep the mangled symbol
         if "<" not in k:
             return k
         base, params = k.split("<")
