@@ -124,6 +124,10 @@ SIGNATURES = {
     "f2_input_batch_coloured": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i, _i, _d, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp,
                                      _i, _vp, C.c_uint32, C.c_uint64, _vp, _i]),
     "f2_trainer_render_coloured": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, C.c_uint64]),
+    "f2_gather_windows_mixed": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _i]),
+    "f2_input_batch_smeared": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i, _i, _d, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp,
+                                    _i, _vp, C.c_uint32, C.c_uint64, _vp, _i, _vp, _vp, _i]),
+    "f2_trainer_render_smeared": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, C.c_uint64, _vp, _i, _vp]),
 }
 TRAINER_WHAT = {"weights": 0, "accumulators": 1, "gradient": 2}   # F2_TRAINER_* of f2_trainer_get
 
@@ -458,6 +462,41 @@ class Context:
                                                     _ptr(snr) if len(snr) else None, _ptr(fir_taps), _ptr(fir_offsets), len(snr),
                                                     _ptr(lev), int(first_utterance), int(seed) & (2 ** 64 - 1), _ptr(windows),
                                                     mem_space))
+
+    def gather_windows_mixed(self, env, offsets, B, Cn, center_offsets, centers, radius, step, normalize, mixes, mix_of, windows,
+                             mem_space):
+        """The ragged gather of input_batch on envelopes that are already in memory, the channels of utterance b's windows mixed
+        by mixes[mix_of[b]] ((K, Cn, Cn) float64, always a host array) before the normaliser, or sharp where mix_of[b] == K;
+        mixes None or mix_of None: all sharp. env holds the ragged (Cn, n_b) float64 blocks, windows receives
+        (center_offsets[B], 2 * radius + 1, Cn) float32 (numpy arrays or device pointers, by mem_space). See
+        f2_gather_windows_mixed."""
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        center_offsets = np.ascontiguousarray(center_offsets, dtype=np.int64)
+        centers = np.ascontiguousarray(centers, dtype=np.int64)
+        mix, mlev = _smears(mixes, mix_of, Cn)
+        self.check(self.lib.f2_gather_windows_mixed(self.handle, _ptr(env), _ptr(offsets), int(B), int(Cn), _ptr(center_offsets),
+                                                    _ptr(centers), radius, step, int(bool(normalize)),
+                                                    _ptr(mix) if len(mix) else None, len(mix), _ptr(mlev), _ptr(windows), mem_space))
+
+    def input_batch_smeared(self, wave, wave_dtype, offsets, coefs, B, Cn, lpf, cutoff, precision, center_offsets, centers, radius,
+                            step, normalize, rirs, room_of, snr_db, firs, level_of, first_utterance, seed, mixes, mix_of, windows,
+                            mem_space):
+        """input_batch_coloured whose gather is gather_windows_mixed: room, noise, envelopes, then the windows of utterance b
+        through mixes[mix_of[b]], nothing leaving the device; mixes None: input_batch_coloured. See f2_input_batch_smeared."""
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        center_offsets = np.ascontiguousarray(center_offsets, dtype=np.int64)
+        centers = np.ascontiguousarray(centers, dtype=np.int64)
+        snr, lev = _noise_levels(snr_db, level_of)
+        fir_taps, fir_offsets = _colours(firs, len(snr))
+        taps, rir_offsets, room = _rooms(rirs, room_of)
+        mix, mlev = _smears(mixes, mix_of, Cn)
+        self.check(self.lib.f2_input_batch_smeared(self.handle, _ptr(wave), wave_dtype, _ptr(offsets), _ptr(coefs), int(B), Cn,
+                                                   int(bool(lpf)), float(cutoff), precision, _ptr(center_offsets), _ptr(centers),
+                                                   radius, step, int(bool(normalize)), _ptr(taps) if len(taps) else None,
+                                                   _ptr(rir_offsets), len(rir_offsets) - 1, _ptr(room),
+                                                   _ptr(snr) if len(snr) else None, _ptr(fir_taps), _ptr(fir_offsets), len(snr),
+                                                   _ptr(lev), int(first_utterance), int(seed) & (2 ** 64 - 1),
+                                                   _ptr(mix) if len(mix) else None, len(mix), _ptr(mlev), _ptr(windows), mem_space))
 
     def cnn_create(self, tensors, rows, channels):
         """tensors: 12 contiguous float32 arrays in Keras layouts (see include/f2cnn_hip.h). Returns a handle."""
@@ -890,6 +929,20 @@ class Context:
                                                        _ptr(fir_taps), _ptr(fir_offsets), len(snr), _ptr(lev),
                                                        int(seed) & (2 ** 64 - 1)))
 
+    def trainer_render_smeared(self, handle, rirs=(), room_of=None, snr_db=(), firs=None, level_of=None, seed=0, mixes=None,
+                               mix_of=None, channels=None):
+        """trainer_render_coloured with the windows of utterance b mixed across their channels by mixes[mix_of[b]] ((K, C, C)
+        float64), sharp where mix_of[b] == K; mixes None: trainer_render_coloured (see f2_trainer_render_smeared)"""
+        snr, lev = _noise_levels(snr_db, level_of)
+        fir_taps, fir_offsets = _colours(firs, len(snr))
+        taps, rir_offsets, room = _rooms(rirs, room_of)
+        mix, mlev = _smears(mixes, mix_of, channels)
+        self.check(self.lib.f2_trainer_render_smeared(self.handle, handle, _ptr(taps) if len(taps) else None, _ptr(rir_offsets),
+                                                      len(rir_offsets) - 1, _ptr(room), _ptr(snr) if len(snr) else None,
+                                                      _ptr(fir_taps), _ptr(fir_offsets), len(snr), _ptr(lev),
+                                                      int(seed) & (2 ** 64 - 1), _ptr(mix) if len(mix) else None, len(mix),
+                                                      _ptr(mlev)))
+
     def trainer_get_windows(self, handle, first, count, shape):
         """Rows first .. first + count - 1 of the training set: (count, *shape) float32 windows and (count) uint8 labels"""
         x = np.empty((int(count),) + tuple(shape), np.float32)
@@ -1029,6 +1082,19 @@ def _pack_mix(mix, Cn):
     if mix.ndim != 3 or mix.shape[1:] != (int(Cn), int(Cn)):
         raise ValueError("mixing matrices must have the shape (K, {0}, {0}), not {1}".format(int(Cn), mix.shape))
     return np.ascontiguousarray(mix)
+
+
+def _smears(mixes, mix_of, Cn):
+    """(mix as (K, Cn, Cn) float64, mix_of as int32 or None) for the calls that give every utterance a spectral resolution of its
+    own; mixes None: no matrices. Cn None: the matrices say how many channels they have."""
+    if mixes is None:
+        mixes = ()
+    if Cn is None:
+        mixes = np.asarray(mixes, dtype=np.float64)
+        Cn = mixes.shape[-1] if mixes.size else 1
+    mix = _pack_mix(mixes, Cn)
+    lev = None if mix_of is None else np.ascontiguousarray(mix_of, dtype=np.int32).reshape(-1)
+    return mix, lev
 
 
 def resampled_length(n, up, down):

@@ -35,6 +35,14 @@ package implements:
                                                              rendered under one of them or clean, the noise filtered on the
                                                              device; the TEST files are validated once per pair; needs
                                                              --augment-snrs; not in the reference)
+    python -m f2cnn_amd cnn train --engine hip --from-wav [--augment-spreads 0.5,1,2,4] [--augment-bands 16,8] [--augment-snrs ...] [--augment-t60 ...] [--seed S]
+                                                            (every epoch each TRAIN file is also rendered at a spectral resolution
+                                                             drawn from the levels of smearsweep - channel interaction of that
+                                                             many ERB, then N-band vocoders - or sharp: the envelopes of its
+                                                             windows are mixed across the channels on the device, in the gather,
+                                                             before they are normalised; the TEST files are also validated once
+                                                             per resolution; combines with every other --augment option; not in
+                                                             the reference)
     python -m f2cnn_amd cnn test [--input/-i NPY] [--label/-l CSV] [--model/-m NPZ] [--by set|region|speaker|phoneme] [--rows test|train|all]
                                                             (loss, accuracy and the 2 x 2 counts of a saved model on the labelled
                                                              windows, per value of a label column, in one device pass; writes
@@ -237,6 +245,7 @@ def drr_argument(text):
 
 NOISE_COLOURS = ('white', 'pink', 'brown', 'speech')     # noise.COLOURS (kept here so that parsing imports nothing)
 NOISE_LEVELS_MAX = 64
+SMEAR_LEVELS_MAX = 64                                    # F2_SMEAR_MAX_LEVELS (likewise)
 
 
 def colours_argument(text):
@@ -343,6 +352,12 @@ def build_parser():
     c.add_argument('--augment-colours', action='store', type=augment_colours_argument, dest='augment_colours', default=argparse.SUPPRESS,
                    help="train --engine hip --from-wav --augment-snrs: comma-separated noise colours, as noisesweep's --colours; every "
                         "epoch each file is rendered under one (colour, SNR) pair or clean")
+    c.add_argument('--augment-spreads', action='store', type=spreads_argument, dest='augment_spreads', default=argparse.SUPPRESS,
+                   help="train --engine hip --from-wav: comma-separated spreads in ERB, as smearsweep's --spreads; every epoch each "
+                        "file is rendered at one of the spectral resolutions, or sharp")
+    c.add_argument('--augment-bands', action='store', type=bands_argument, dest='augment_bands', default=argparse.SUPPRESS,
+                   help="train --engine hip --from-wav: comma-separated numbers of vocoder bands, as smearsweep's --bands; levels "
+                        "behind those of --augment-spreads")
     c.add_argument('--augment-noise-taps', action='store', type=augment_noise_taps_argument, dest='augment_noise_taps',
                    default=argparse.SUPPRESS, help="train --augment-colours: taps of the designed noise filters, odd (default 1025, at most 2047)")
     # (absent from the parsed arguments unless given: the commands parse as before without them)
@@ -531,6 +546,23 @@ def augment_colours_refusal(args):
     return None
 
 
+def augment_smear_refusal(args):
+    """The same for --augment-spreads / --augment-bands, asked once from_wav_refusal has nothing to say"""
+    given = [opt for attr, opt in (('augment_spreads', '--augment-spreads'), ('augment_bands', '--augment-bands')) if attr in args]
+    if not given:
+        return None
+    if args.cnn_command != 'train':
+        return "{} only applies to 'cnn train'".format(given[0])
+    if getattr(args, 'engine', 'torch') != 'hip':
+        return "{} needs --engine hip: only the library's own training step renders windows from the waves".format(given[0])
+    if 'from_wav' not in args:
+        return "{} needs --from-wav: stored windows are normalised already and cannot be mixed across their channels".format(given[0])
+    levels = len(getattr(args, 'augment_spreads', ())) + len(getattr(args, 'augment_bands', ()))
+    if levels > SMEAR_LEVELS_MAX:
+        return "training takes at most {} spectral resolutions, not {}".format(SMEAR_LEVELS_MAX, levels)
+    return None
+
+
 def sweep_refusal(args, no_lpf, instead):
     """says which option the sweep does not take, if one was given (an option that was not given is absent, None or False)"""
     for attr, option, why in (('CUTOFF', '--lpf', no_lpf), ('figure', '--figure', instead), ('occlusion', '--occlusion', instead),
@@ -576,7 +608,8 @@ def main(argv=None):
         if getattr(report, "exit_status", 0):          # some files could not be processed (the others were)
             return report.exit_status
     elif 'cnn_command' in args:
-        refusal = from_wav_refusal(args) or rooms_refusal(args) or augment_colours_refusal(args) or colours_refusal(args)
+        refusal = (from_wav_refusal(args) or rooms_refusal(args) or augment_colours_refusal(args) or augment_smear_refusal(args) or
+                   colours_refusal(args))
         if refusal:
             print(refusal)
             return 1
@@ -595,6 +628,8 @@ def main(argv=None):
                 rooms['colours'] = tuple(args.augment_colours)
                 if 'augment_noise_taps' in args:
                     rooms['noise_taps'] = args.augment_noise_taps
+            if 'augment_spreads' in args or 'augment_bands' in args:
+                rooms.update(spreads=tuple(getattr(args, 'augment_spreads', ())), bands=tuple(getattr(args, 'augment_bands', ())))
             TrainFromWav(labelFile=labelFile, LPF=args.CUTOFF is not None, CUTOFF=args.CUTOFF, snrs=tuple(getattr(args, 'augment_snrs', ())),
                          seed=args.seed, **rooms)
             return 0

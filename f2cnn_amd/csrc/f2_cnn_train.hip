@@ -709,6 +709,7 @@ struct f2_trainer {
     f2_scratch wave, centers;   // the waves; [the centres | the utterance of every window, counted inside its group]
     f2_scratch rir;             // f2_trainer_render_wet: [rir_offsets | taps] of the render in flight, uploaded once for all groups
     f2_scratch fir;             // f2_trainer_render_coloured: [fir_offsets | taps] of the render in flight, likewise
+    f2_scratch mix;             // f2_trainer_render_smeared: [tile spans | transposed mixing matrices] of the render in flight, likewise
     std::vector<int64_t> offsets, center_offsets;
     std::vector<double> coefs;
     int wave_dtype = 0, B = 0, lpf = 0, fft_precision = 0, radius = 0, step = 0, group = 1;
@@ -894,9 +895,9 @@ int f2_trainer_set_waves(f2_ctx* ctx, f2_trainer* t, const void* wave, int wave_
     return F2_OK;
 }
 
-int f2_trainer_render_coloured(f2_ctx* ctx, f2_trainer* t, const double* rir, const int64_t* rir_offsets, int Kr, const int32_t* room_of,
-                               const double* snr_db, const double* fir, const int64_t* fir_offsets, int K, const int32_t* level_of,
-                               uint64_t seed) {
+int f2_trainer_render_smeared(f2_ctx* ctx, f2_trainer* t, const double* rir, const int64_t* rir_offsets, int Kr, const int32_t* room_of,
+                              const double* snr_db, const double* fir, const int64_t* fir_offsets, int K, const int32_t* level_of,
+                              uint64_t seed, const double* mix, int Km, const int32_t* mix_of) {
     F2_TRY(f2_check_ctx(ctx));
     F2_TRY(check_trainer(ctx, t));
     F2_CHECK(ctx, t->have_waves, F2_ERR_INVALID, "the trainer has no waves to render from (f2_trainer_set_waves)");
@@ -905,6 +906,9 @@ int f2_trainer_render_coloured(f2_ctx* ctx, f2_trainer* t, const double* rir, co
     F2_TRY(f2_check_noise_colours(ctx, t->B, &Nall, false));
     f2_reverb_pick_args R = {rir, rir_offsets, Kr, room_of, nullptr, nullptr};
     F2_TRY(f2_check_reverb_pick(ctx, t->B, R));
+    f2_mix_gather_args S;
+    S.mix = mix, S.K = Km, S.mix_of = mix_of;
+    F2_TRY(f2_check_mix_gather(ctx, t->B, t->channels, t->radius, &S));
     if (t->n == 0) return F2_OK;
     const size_t xs = (size_t)t->rows * t->channels, ws = t->wave_dtype == F2_WAVE_I16 ? 2 : 8;
     const int64_t* d_centers = (const int64_t*)t->centers.ptr;
@@ -923,6 +927,10 @@ int f2_trainer_render_coloured(f2_ctx* ctx, f2_trainer* t, const double* rir, co
         F2_TRY(f2_upload_async(ctx, (char*)t->fir.ptr + obytes, fir, sizeof(double) * (size_t)fir_offsets[K]));
         Nall.d_fir_off = (const int64_t*)t->fir.ptr, Nall.d_fir = (const double*)((const char*)t->fir.ptr + obytes);
     }
+    if (!S.sharp() && !S.all_sharp) {   // ... and the mixing matrices, as the image the gather reads
+        F2_TRY(f2_reserve(ctx, t->mix, f2_mix_image_bytes(S.plan)));
+        F2_TRY(f2_upload_mix_image(ctx, S.plan, t->mix.ptr, &S.d_spans, &S.d_wT));
+    }
     F2_HIP(ctx, hipMemsetAsync(ctx->flags.ptr, 0, sizeof(int), ctx->stream));
     std::vector<int64_t> off;
     // group after group onto the stream, each into its rows of x; one wait at the end
@@ -936,14 +944,22 @@ int f2_trainer_render_coloured(f2_ctx* ctx, f2_trainer* t, const double* rir, co
         N.level_of = level_of ? level_of + b0 : nullptr, N.first_utterance = (uint32_t)b0;
         f2_reverb_pick_args Rg = R;
         if (!R.dry()) Rg.room_of = room_of + b0;
+        if (!S.sharp()) S.mix_of = mix_of + b0;   // (a group whose utterances are all sharp takes the mixing gather's sharp path)
         F2_TRY(f2_launch_noisy_windows(ctx, (const char*)t->wave.ptr + ws * (size_t)t->offsets[(size_t)b0], t->wave_dtype, off.data(),
                                        t->coefs.data(), nb, t->channels, t->lpf, t->cutoff_hz, t->fft_precision, d_centers + w0, d_win_utt + w0,
-                                       true, nw, t->radius, t->step, 1, N, (float*)t->x.ptr + xs * (size_t)w0, &Rg));
+                                       true, nw, t->radius, t->step, 1, N, (float*)t->x.ptr + xs * (size_t)w0, &Rg, &S));
     }
     F2_HIP(ctx, hipMemcpyAsync(ctx->host_flags, ctx->flags.ptr, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     F2_HIP(ctx, hipStreamSynchronize(ctx->stream));
     F2_CHECK(ctx, !ctx->host_flags[0], F2_ERR_NONPOSITIVE, "values must all be positive (normalizeInput)");
     return F2_OK;
+}
+
+// the render at full resolution: the same code, whose last call is then the plain gather
+int f2_trainer_render_coloured(f2_ctx* ctx, f2_trainer* t, const double* rir, const int64_t* rir_offsets, int Kr, const int32_t* room_of,
+                               const double* snr_db, const double* fir, const int64_t* fir_offsets, int K, const int32_t* level_of,
+                               uint64_t seed) {
+    return f2_trainer_render_smeared(ctx, t, rir, rir_offsets, Kr, room_of, snr_db, fir, fir_offsets, K, level_of, seed, nullptr, 0, nullptr);
 }
 
 // the render under white noise: the same code, whose noise stage is then k_noise_pick

@@ -16,6 +16,7 @@
 // except that without normalisation the values go straight from the envelope to the output (no LDS stage, no
 // barrier). The windows of neighbouring labelled timepoints share most of their tap columns in L2.
 #include "f2_internal.h"
+#include "f2_gather_tail.h"
 
 namespace {
 
@@ -58,39 +59,7 @@ __global__ __launch_bounds__(GT) void k_gather_windows(const double* __restrict_
         mn = fmin(mn, v);
         mx = fmax(mx, v);
     }
-    float* o = out + (size_t)e * (size_t)total;
-    if (!normalize) {
-        __syncthreads();
-        for (int idx = tid; idx < total; idx += GT) o[idx] = (float)win[idx];
-        return;
-    }
-    for (int d = 32; d > 0; d >>= 1) {
-        mn = fmin(mn, __shfl_xor(mn, d));
-        mx = fmax(mx, __shfl_xor(mx, d));
-    }
-    if ((tid & 63) == 0) {
-        red_min[tid >> 6] = mn;
-        red_max[tid >> 6] = mx;
-    }
-    __syncthreads();
-    mn = red_min[0];
-    mx = red_max[0];
-    for (int w = 1; w < GT / 64; ++w) {
-        mn = fmin(mn, red_min[w]);
-        mx = fmax(mx, red_max[w]);
-    }
-    if (!(mn > 0.0)) {   // also catches NaN
-        if (tid == 0) atomicOr(flag, 1);
-        for (int idx = tid; idx < total; idx += GT) o[idx] = 0.f;
-        return;
-    }
-    if (mn == mx) {
-        for (int idx = tid; idx < total; idx += GT) o[idx] = 0.f;
-        return;
-    }
-    const double lmn = log(mn);
-    const double range = log(mx) - lmn;
-    for (int idx = tid; idx < total; idx += GT) o[idx] = (float)((log(win[idx]) - lmn) / range);
+    gather_window_tail<GT>(win, total, mn, mx, normalize, out + (size_t)e * (size_t)total, flag, red_min, red_max);
 }
 
 // ---- every-sample windows (`cnn eval`: centres first_center + e, normalised): two passes over coalesced data ----

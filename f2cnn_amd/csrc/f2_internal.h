@@ -602,6 +602,8 @@ int f2_launch_noise_pick_sigma(f2_ctx* ctx, const void* d_wave, int wave_dtype, 
 // A coloured stage (fir != NULL, passed f2_check_noise_colours) filters the deviates of level l with the taps fir + fir_offsets[l]
 // (host, K + 1 offsets) through k_shaped_noise_pick instead of k_noise_pick; sigma is k_noise_pick_sigma's in both.
 // d_fir / d_fir_off: device copies that are up already (a render uploads them once for all its groups), or NULL.
+// With `smear` (passed f2_check_mix_gather) that mixes anything, the last call is f2_launch_gather_mixed instead of
+// f2_launch_gather_ragged; its image goes into ctx->mix unless smear->d_wT says it is up already.
 struct f2_noise_pick_args {
     const double* snr_db;
     int K;
@@ -638,10 +640,14 @@ int f2_check_input_batch(f2_ctx* ctx, const void* wave, int wave_dtype, const in
                          double cutoff_hz, int fft_precision, const int64_t* center_offsets, const int64_t* centers, int radius, int step,
                          const void* windows, int mem_space, const f2_noise_pick_args* noise, int64_t* n_windows,
                          std::vector<int>* win_utt);
+// ... its checks of the window lists alone: offsets, center_offsets, and every window inside its utterance's envelope; data_given:
+// the call's data pointers are all non-NULL (tested only where there are windows)
+int f2_check_window_lists(f2_ctx* ctx, const int64_t* offsets, int B, const int64_t* center_offsets, const int64_t* centers, int radius,
+                          int step, bool data_given, int64_t* n_windows, std::vector<int>* win_utt);
 int f2_launch_noisy_windows(f2_ctx* ctx, const void* d_wave, int wave_dtype, const int64_t* offsets, const double* coefs, int B, int C,
                             int lpf, double cutoff_hz, int fft_precision, const int64_t* centers, const int* win_utt,
                             bool lists_on_device, int64_t n_windows, int radius, int step, int normalize, const f2_noise_pick_args& N, float* d_windows,
-                            const struct f2_reverb_pick_args* rooms = nullptr);
+                            const struct f2_reverb_pick_args* rooms = nullptr, const struct f2_mix_gather_args* smear = nullptr);
 // d_stats ((K + 1) * B pairs, zeroed by the caller) += {windows labelled rising, windows labelled as the clean level labels them}
 // per utterance of the (K + 1) * B batch whose window offsets are d_window_offsets; max_windows: the most any utterance has
 int f2_launch_label_tally(f2_ctx* ctx, const uint8_t* d_labels, const int64_t* d_window_offsets, int B, int K, int64_t max_windows,
@@ -746,6 +752,32 @@ int f2_check_mix(f2_ctx* ctx, const double* mix, int K, int C, f2_smear_plan* P)
 int f2_smear_reserve(f2_ctx* ctx, const f2_smear_plan& P, int B);
 int f2_launch_channel_mix_levels(f2_ctx* ctx, const double* d_env, const int64_t* d_offsets, const int64_t* h_offsets, int B,
                                  const f2_smear_plan& P, double* d_levels);
+// f2_gather_mix.hip, the kernel of f2_gather_windows_mixed and the last stage of f2_input_batch_smeared / f2_trainer_render_smeared:
+// the ragged gather of f2_launch_gather_ragged with the channels of every window mixed by the matrix of its utterance's level
+// (mix_of[b] in [0, K], K: sharp) before the normaliser; bit for bit that gather on the level's block of f2_channel_mix_levels.
+// The stage of a call (mix: K x C x C, mix_of: B, host) passes f2_check_mix_gather before anything is launched: K >= 0; unless the
+// stage is sharp(), f2_check_mix (which builds `plan`), every mix_of entry in [0, K] (F2_ERR_INVALID, the message names the
+// utterance) and a window whose two LDS arrays (f2_gather_mixed_lds bytes) fit a workgroup (F2_ERR_UNSUPPORTED). all_sharp: no
+// utterance of the call is mixed - the call is the plain gather and takes f2_launch_gather_ragged.
+// d_spans / d_wT: the device image of the plan, [spans | wT] in f2_mix_image_bytes bytes, which f2_upload_mix_image puts up - once
+// per call into ctx->mix, or once per render into the trainer's buffer. d_mix_of: the B levels on the device (int32).
+struct f2_mix_gather_args {
+    const double* mix = nullptr;
+    int K = 0;
+    const int32_t* mix_of = nullptr;
+    f2_smear_plan plan;
+    bool all_sharp = true;
+    const int64_t* d_spans = nullptr;
+    const double* d_wT = nullptr;
+    bool sharp() const { return K == 0 || !mix_of; }
+};
+size_t f2_gather_mixed_lds(int radius, int C);
+int f2_check_mix_gather(f2_ctx* ctx, int B, int C, int radius, f2_mix_gather_args* S);
+size_t f2_mix_image_bytes(const f2_smear_plan& P);
+int f2_upload_mix_image(f2_ctx* ctx, const f2_smear_plan& P, void* d_image, const int64_t** d_spans, const double** d_wT);
+int f2_launch_gather_mixed(f2_ctx* ctx, const double* d_env, int C, const int64_t* d_offsets, const int64_t* d_centers, const int* d_win_utt,
+                           int64_t n_windows, int radius, int step, int normalize, const f2_smear_plan& P, const int64_t* d_spans,
+                           const double* d_wT, const int32_t* d_mix_of, float* d_out, int* d_flag);
 // f2_accuracy.hip, the kernel of f2_label_accuracy. d_counts (4 per utterance, zeroed by the caller)[4 u + 2 ref + pred] += rows
 // of utterance u (rows d_window_offsets[u] .. [u + 1] of d_labels, row j at sample origin + j * hop) that the rule of the header
 // counts against reference set u % R (d_ref_offsets: R + 1; timepoints strictly increasing inside a set, signs 0 / 1);

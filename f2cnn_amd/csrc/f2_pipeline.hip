@@ -926,6 +926,34 @@ struct noise_pick_meta {
     }
 };
 
+// The gather that ends a window call with a smear stage (S NULL, sharp or all_sharp: the plain ragged gather and nothing else). carve
+// names the levels of the utterances in the call's f2_meta_carve; reserve sizes ctx->mix for the image unless it is up already
+// (before the call's first launch); launch uploads what is not up and gathers from d_env with the offsets in ctx->offsets, ORing into
+// word 0 of ctx->flags.
+struct mix_gather_meta {
+    const f2_mix_gather_args* S = nullptr;
+    int64_t* d_mix_of = nullptr;   // B int32 values in 8-byte slots
+    void carve(f2_meta_carve* meta, int B, const f2_mix_gather_args* smear) {
+        if (!smear || smear->sharp() || smear->all_sharp) return;
+        S = smear;
+        meta->add(&d_mix_of, ((size_t)B + 1) / 2);
+    }
+    int reserve(f2_ctx* ctx) const { return S && !S->d_wT ? f2_reserve(ctx, ctx->mix, f2_mix_image_bytes(S->plan)) : F2_OK; }
+    int launch(f2_ctx* ctx, const double* d_env, int B, int C, const int64_t* d_centers, const int* d_win_utt, int64_t n_windows, int radius,
+               int step, int normalize, float* d_windows) const {
+        const int64_t* d_offsets = (const int64_t*)ctx->offsets.ptr;
+        if (!S)
+            return f2_launch_gather_ragged(ctx, d_env, C, d_offsets, d_centers, d_win_utt, n_windows, radius, step, normalize, d_windows,
+                                           (int*)ctx->flags.ptr);
+        const int64_t* d_spans = S->d_spans;
+        const double* d_wT = S->d_wT;
+        if (!d_wT) F2_TRY(f2_upload_mix_image(ctx, S->plan, ctx->mix.ptr, &d_spans, &d_wT));
+        F2_TRY(f2_upload_async(ctx, d_mix_of, S->mix_of, sizeof(int32_t) * (size_t)B));
+        return f2_launch_gather_mixed(ctx, d_env, C, d_offsets, d_centers, d_win_utt, n_windows, radius, step, normalize, S->plan, d_spans, d_wT,
+                                      (const int32_t*)d_mix_of, d_windows, (int*)ctx->flags.ptr);
+    }
+};
+
 }  // namespace
 
 // The argument checks of f2_input_batch, and behind them those of the noise stage when the call has one (noise != NULL), all before
@@ -939,12 +967,18 @@ int f2_check_input_batch(f2_ctx* ctx, const void* wave, int wave_dtype, const in
     F2_TRY(f2_check_dsp(ctx, wave_dtype, lpf, cutoff_hz, fft_precision));
     F2_CHECK(ctx, B >= 0 && C > 0 && radius >= 0 && step >= 0, F2_ERR_INVALID, "bad size");
     if (noise) F2_TRY(f2_check_noise_pick(ctx, B, *noise));
+    return f2_check_window_lists(ctx, offsets, B, center_offsets, centers, radius, step, wave && coefs && centers && windows, n_windows, win_utt);
+}
+
+int f2_check_window_lists(f2_ctx* ctx, const int64_t* offsets, int B, const int64_t* center_offsets, const int64_t* centers, int radius,
+                          int step, bool data_given, int64_t* n_windows, std::vector<int>* win_utt) {
+    *n_windows = 0;
     if (B == 0) return F2_OK;      // (before the offsets are looked at: they may be NULL then)
     F2_TRY(f2_check_offsets(ctx, offsets, B, "offsets"));
     F2_TRY(f2_check_offsets(ctx, center_offsets, B, "center_offsets"));
     const int64_t n = center_offsets[B];
     if (n == 0) return F2_OK;
-    F2_CHECK(ctx, wave && coefs && centers && windows, F2_ERR_INVALID, "null data pointer");
+    F2_CHECK(ctx, data_given, F2_ERR_INVALID, "null data pointer");
     // InputGenerator.py:73-80 indexes each utterance's own envelope: a window must lie inside it
     const int64_t reach = (int64_t)radius * step;
     win_utt->resize((size_t)n);
@@ -978,16 +1012,19 @@ int f2_check_noise_pick(f2_ctx* ctx, int B, const f2_noise_pick_args& N) {
 int f2_launch_noisy_windows(f2_ctx* ctx, const void* d_wave, int wave_dtype, const int64_t* offsets, const double* coefs, int B, int C,
                             int lpf, double cutoff_hz, int fft_precision, const int64_t* centers, const int* win_utt,
                             bool lists_on_device, int64_t n_windows, int radius, int step, int normalize, const f2_noise_pick_args& N,
-                            float* d_windows, const f2_reverb_pick_args* rooms) {
+                            float* d_windows, const f2_reverb_pick_args* rooms, const f2_mix_gather_args* smear) {
     const int64_t total = offsets[B];
     const bool wet = rooms && !rooms->dry();
+    mix_gather_meta G;
     // the small arrays and the waveforms first: nothing the envelopes reserve is one of these areas
     noise_pick_meta M;
     f2_reverb_pick_arrays A;
     f2_meta_carve meta;
     M.carve(&meta, B, offsets, N);
     if (wet) f2_reverb_pick_meta(&meta, B, offsets, *rooms, &A);
+    G.carve(&meta, B, smear);
     F2_TRY(meta.reserve(ctx));
+    F2_TRY(G.reserve(ctx));
     F2_TRY(f2_reserve(ctx, ctx->levels, sizeof(double) * (size_t)total));
     if (wet) F2_TRY(f2_reserve(ctx, ctx->wet, sizeof(double) * (size_t)total));
     F2_TRY(f2_upload_offsets(ctx, offsets, B));
@@ -1003,8 +1040,7 @@ int f2_launch_noisy_windows(f2_ctx* ctx, const void* d_wave, int wave_dtype, con
     const int64_t* d_centers = centers;
     const int* d_win_utt = win_utt;
     if (!lists_on_device) F2_TRY(f2_upload_windows(ctx, centers, win_utt, n_windows, &d_centers, &d_win_utt));
-    return f2_launch_gather_ragged(ctx, d_env, C, (const int64_t*)ctx->offsets.ptr, d_centers, d_win_utt, n_windows, radius, step, normalize,
-                                   d_windows, (int*)ctx->flags.ptr);
+    return G.launch(ctx, d_env, B, C, d_centers, d_win_utt, n_windows, radius, step, normalize, d_windows);
 }
 
 extern "C" {
@@ -1077,21 +1113,57 @@ int f2_shaped_noise_pick(f2_ctx* ctx, const void* wave, int wave_dtype, const in
                            sigma_or_null, mem_space);
 }
 
-// The one window path behind a noise stage: f2_input_batch_coloured, and with fir == NULL f2_input_batch_wet, and without rooms
-// f2_input_batch_noisy.
-int f2_input_batch_coloured(f2_ctx* ctx, const void* wave, int wave_dtype, const int64_t* offsets, const double* coefs, int B, int C, int lpf,
-                            double cutoff_hz, int fft_precision, const int64_t* center_offsets, const int64_t* centers, int radius, int step,
-                            int normalize, const double* rir, const int64_t* rir_offsets, int Kr, const int32_t* room_of, const double* snr_db,
-                            const double* fir, const int64_t* fir_offsets, int K, const int32_t* level_of, uint32_t first_utterance,
-                            uint64_t seed, float* windows, int mem_space) {
+// f2_gather_windows_mixed: the envelopes go up (host calls), the windows are gathered through the matrices of their utterances' levels
+// and come back; the end of the call is f2_input_batch's.
+int f2_gather_windows_mixed(f2_ctx* ctx, const double* env, const int64_t* offsets, int B, int C, const int64_t* center_offsets,
+                            const int64_t* centers, int radius, int step, int normalize, const double* mix, int K, const int32_t* mix_of,
+                            float* windows, int mem_space) {
+    F2_TRY(f2_check_ctx(ctx));
+    F2_TRY(f2_check_mem_space(ctx, mem_space, false));
+    F2_CHECK(ctx, B >= 0 && C > 0 && radius >= 0 && step >= 0, F2_ERR_INVALID, "bad size");
+    f2_mix_gather_args S;
+    S.mix = mix, S.K = K, S.mix_of = mix_of;
+    F2_TRY(f2_check_mix_gather(ctx, B, C, radius, &S));
+    int64_t n_windows;
+    std::vector<int> win_utt;
+    F2_TRY(f2_check_window_lists(ctx, offsets, B, center_offsets, centers, radius, step, env && centers && windows, &n_windows, &win_utt));
+    if (n_windows == 0) return F2_OK;
+    mix_gather_meta G;
+    f2_meta_carve meta;
+    G.carve(&meta, B, &S);
+    F2_TRY(meta.reserve(ctx));
+    F2_TRY(G.reserve(ctx));
+    const void* d_env;
+    F2_TRY(f2_stage_input(ctx, env, sizeof(double) * (size_t)C * (size_t)offsets[B], mem_space, &d_env));
+    F2_TRY(f2_upload_offsets(ctx, offsets, B));
+    const int64_t* d_centers;
+    const int* d_win_utt;
+    F2_TRY(f2_upload_windows(ctx, centers, win_utt.data(), n_windows, &d_centers, &d_win_utt));
+    f2_output win;
+    F2_TRY(f2_place(ctx, ctx->xbuf, windows, sizeof(float) * (size_t)n_windows * (2 * radius + 1) * (size_t)C, mem_space, true, &win));
+    F2_TRY(reset_flag(ctx));
+    F2_TRY(G.launch(ctx, (const double*)d_env, B, C, d_centers, d_win_utt, n_windows, radius, step, normalize, win.as<float>()));
+    return finish_windows(ctx, win, normalize);
+}
+
+// The one window path behind a noise stage: f2_input_batch_smeared, and without matrices f2_input_batch_coloured, and with
+// fir == NULL f2_input_batch_wet, and without rooms f2_input_batch_noisy.
+int f2_input_batch_smeared(f2_ctx* ctx, const void* wave, int wave_dtype, const int64_t* offsets, const double* coefs, int B, int C, int lpf,
+                           double cutoff_hz, int fft_precision, const int64_t* center_offsets, const int64_t* centers, int radius, int step,
+                           int normalize, const double* rir, const int64_t* rir_offsets, int Kr, const int32_t* room_of, const double* snr_db,
+                           const double* fir, const int64_t* fir_offsets, int K, const int32_t* level_of, uint32_t first_utterance,
+                           uint64_t seed, const double* mix, int Km, const int32_t* mix_of, float* windows, int mem_space) {
     f2_noise_pick_args N = {snr_db, K, level_of, first_utterance, seed, fir, fir_offsets};
     const f2_reverb_pick_args R = {rir, rir_offsets, Kr, room_of, nullptr, nullptr};
+    f2_mix_gather_args S;
+    S.mix = mix, S.K = Km, S.mix_of = mix_of;
     int64_t n_windows;
     std::vector<int> win_utt;
     F2_TRY(f2_check_input_batch(ctx, wave, wave_dtype, offsets, coefs, B, C, lpf, cutoff_hz, fft_precision, center_offsets, centers, radius,
                              step, windows, mem_space, &N, &n_windows, &win_utt));
     F2_TRY(f2_check_noise_colours(ctx, B, &N, false));
     F2_TRY(f2_check_reverb_pick(ctx, B, R));
+    F2_TRY(f2_check_mix_gather(ctx, B, C, radius, &S));
     if (n_windows == 0) return F2_OK;
     const void* d_wave;
     F2_TRY(f2_stage_wave(ctx, wave, wave_dtype, offsets[B], mem_space, &d_wave));
@@ -1099,8 +1171,18 @@ int f2_input_batch_coloured(f2_ctx* ctx, const void* wave, int wave_dtype, const
     F2_TRY(f2_place(ctx, ctx->xbuf, windows, sizeof(float) * (size_t)n_windows * (2 * radius + 1) * (size_t)C, mem_space, true, &win));
     F2_TRY(reset_flag(ctx));
     F2_TRY(f2_launch_noisy_windows(ctx, d_wave, wave_dtype, offsets, coefs, B, C, lpf, cutoff_hz, fft_precision, centers, win_utt.data(),
-                                   false, n_windows, radius, step, normalize, N, win.as<float>(), &R));
+                                   false, n_windows, radius, step, normalize, N, win.as<float>(), &R, &S));
     return finish_windows(ctx, win, normalize);
+}
+
+int f2_input_batch_coloured(f2_ctx* ctx, const void* wave, int wave_dtype, const int64_t* offsets, const double* coefs, int B, int C, int lpf,
+                            double cutoff_hz, int fft_precision, const int64_t* center_offsets, const int64_t* centers, int radius, int step,
+                            int normalize, const double* rir, const int64_t* rir_offsets, int Kr, const int32_t* room_of, const double* snr_db,
+                            const double* fir, const int64_t* fir_offsets, int K, const int32_t* level_of, uint32_t first_utterance,
+                            uint64_t seed, float* windows, int mem_space) {
+    return f2_input_batch_smeared(ctx, wave, wave_dtype, offsets, coefs, B, C, lpf, cutoff_hz, fft_precision, center_offsets, centers, radius,
+                                  step, normalize, rir, rir_offsets, Kr, room_of, snr_db, fir, fir_offsets, K, level_of, first_utterance, seed,
+                                  nullptr, 0, nullptr, windows, mem_space);
 }
 
 int f2_input_batch_wet(f2_ctx* ctx, const void* wave, int wave_dtype, const int64_t* offsets, const double* coefs, int B, int C, int lpf,

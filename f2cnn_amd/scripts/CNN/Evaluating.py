@@ -1175,6 +1175,28 @@ def EvaluateReverbSweep(files, t60s=(), rirs=(), drr_db=0.0, seed=0, hop=None, L
 
 # ---- `cnn smearsweep`: one file at several spectral resolutions (the twin of the modulation axis; not in the reference, and
 # without the device call a host matrix product per level on envelopes that had to come down first) ---------------------------
+def SmearLevels(spreads, bands, nchannels):
+    """(spread (float64), counts (int64), names) of the spectral resolutions of `cnn smearsweep` and `cnn train --augment-spreads /
+    --augment-bands`: the spreads in the order given, then the numbers of bands; a level's number is its place in names.
+    ValueError for a spread that is not finite and positive, a number of bands that is not whole or not in 1 .. nchannels, no
+    level at all, or more than 64."""
+    spread = numpy.asarray(spreads, dtype=numpy.float64).reshape(-1)
+    if not numpy.isfinite(spread).all() or (spread <= 0).any():
+        raise ValueError("a spread must be finite and positive (ERB)")
+    counts = numpy.asarray(bands).reshape(-1)
+    if len(counts) and (counts != numpy.floor(counts)).any():
+        raise ValueError("a number of bands must be a whole number")
+    counts = counts.astype(numpy.int64)
+    if (counts < 1).any() or (counts > nchannels).any():
+        raise ValueError("a number of bands must lie between 1 and the {} channels".format(nchannels))
+    K = len(spread) + len(counts)
+    if K < 1:
+        raise ValueError("a smear sweep needs at least one spread or number of bands")
+    if K > 64:
+        raise ValueError("a smear sweep takes at most 64 levels, not {}".format(K))
+    return spread, counts, [_level_text(v) + 'ERB' for v in spread] + ['{}bands'.format(v) for v in counts]
+
+
 def EvaluateSmearSweep(files, spreads=(), bands=(), hop=None, LPF=False, CUTOFF=50, model='last_trained_model', ctx=None,
                        accuracy=None, resample=False):
     """`cnn smearsweep`: every file at every spectral resolution and sharp in one device pass per group of files
@@ -1192,21 +1214,7 @@ def EvaluateSmearSweep(files, spreads=(), bands=(), hop=None, LPF=False, CUTOFF=
     from ... import smear
     if isinstance(files, (str, bytes, os.PathLike)):
         files = [files]
-    spread = numpy.asarray(spreads, dtype=numpy.float64).reshape(-1)
-    if not numpy.isfinite(spread).all() or (spread <= 0).any():
-        raise ValueError("a spread must be finite and positive (ERB)")
-    counts = numpy.asarray(bands).reshape(-1)
-    if len(counts) and (counts != numpy.floor(counts)).any():
-        raise ValueError("a number of bands must be a whole number")
-    counts = counts.astype(numpy.int64)
-    nchannels = F2Config().nchannels
-    if (counts < 1).any() or (counts > nchannels).any():
-        raise ValueError("a number of bands must lie between 1 and the {} channels".format(nchannels))
-    K = len(spread) + len(counts)
-    if K < 1:
-        raise ValueError("a smear sweep needs at least one spread or number of bands")
-    if K > 64:
-        raise ValueError("a smear sweep takes at most 64 levels, not {}".format(K))
+    spread, counts, names = SmearLevels(spreads, bands, F2Config().nchannels)
     matrices = {}                                 # per (framerate, channels)
 
     def call(ctx, handle, flat, dt, offsets, coefs, B, Cn, radius, STEP, hop, framerate, labels):
@@ -1224,7 +1232,7 @@ def EvaluateSmearSweep(files, spreads=(), bands=(), hop=None, LPF=False, CUTOFF=
                     bands=numpy.concatenate([numpy.zeros(len(spread), numpy.int64), counts]),
                     timepoints=_lib.strided_timepoints(n, radius, STEP, hop), scores=numpy.stack([scores[wo[u]:wo[u + 1]] for u in rows]))
 
-    axis = _SweepAxis(names=[_level_text(v) + 'ERB' for v in spread] + ['{}bands'.format(v) for v in counts], referee='sharp',
+    axis = _SweepAxis(names=names, referee='sharp',
                       label="smear {:>8}", limit=LEVELS_LIMIT, call=call, own=own,
                       order=('spread_erb', 'bands', 'windows', 'rising', 'agree', 'agreement', 'hop', 'timepoints', 'scores'),
                       out=lambda file: os.path.splitext(file)[0] + '.smearsweep.npz', outdir=None, wav_target=None)

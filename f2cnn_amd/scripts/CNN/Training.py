@@ -10,7 +10,8 @@ produces weights; every forward pass used for evaluation is HIP kernel K4 (the t
 
 ``TrainFromWav`` (`cnn train --engine hip --from-wav`, not in the reference) trains on windows the device renders from the WAV files,
 again before every epoch under fresh noise (``--augment-snrs``), of a colour drawn per file (``--augment-colours``), and in a
-freshly drawn room per file (``--augment-t60``, ``--augment-rirs``) when asked.
+freshly drawn room per file (``--augment-t60``, ``--augment-rirs``) and at a spectral resolution drawn per file
+(``--augment-spreads``, ``--augment-bands``) when asked.
 
 ``TestModel`` (`cnn test`, not in the reference) is ``model.evaluate(x_test, y_test)`` (:136) for a saved model, broken down
 by a column of the label CSV: one ``f2_cnn_score_windows`` call on the stored windows.
@@ -322,6 +323,7 @@ NOISE_STREAM = 0x6E6F6973       # 'nois': the generator of the epochs' noise con
 VALIDATION_NOISE_SEED = 0x76616C69    # 'vali': the noisy validation sets are rendered once, with this seed
 ROOM_STREAM = 0x726F6F6D        # 'room': the generator of the epochs' rooms is default_rng([seed, ROOM_STREAM])
 VALIDATION_ROOM_SEED = 0x76726F6D     # 'vrom': the synthetic responses of the reverberant validation sets are built once, from this seed
+SMEAR_STREAM = 0x736D6561       # 'smea': the generator of the epochs' spectral resolutions is default_rng([seed, SMEAR_STREAM])
 RENDER_GROUP = 64               # files per envelope pass, as `prepare input --from-wav`
 
 
@@ -337,6 +339,23 @@ def draw_epoch_rooms(rng, Kr, B):
     return room_of, int(rng.integers(0, 2 ** 63))
 
 
+def draw_epoch_smear(rng, Km, B):
+    """mix_of (B) int32 in [0, Km] of one epoch, drawn from rng; Km is the sharp one (the mixing is deterministic: no seed)"""
+    return rng.integers(0, Km + 1, B).astype(numpy.int32)
+
+
+def build_smear_levels(spreads, bands, centre_freqs):
+    """((Km, C, C) float64 matrices, names) of the spectral resolutions of a training run, ordered and named as
+    Evaluating.EvaluateSmearSweep orders and names them: the spreads (smear.SmearMatrix on the centre frequencies), then the
+    numbers of bands (smear.BandMatrix); (None, []) without either"""
+    from ... import smear
+    from .Evaluating import SmearLevels
+    if not len(spreads) and not len(bands):
+        return None, []
+    spread, counts, names = SmearLevels(spreads, bands, len(centre_freqs))
+    return numpy.stack([smear.SmearMatrix(centre_freqs, v) for v in spread] + [smear.BandMatrix(len(centre_freqs), v) for v in counts]), names
+
+
 def build_rooms(t60s, measured, framerate, drr_db, room_seed):
     """The responses of one epoch (or of the validation sets): reverb.SyntheticRIR(t60, framerate, drr_db, room_seed, level) per
     reverberation time, level its place in the list, then the measured responses, which do not change"""
@@ -344,10 +363,11 @@ def build_rooms(t60s, measured, framerate, drr_db, room_seed):
     return [reverb.SyntheticRIR(v, framerate, drr_db, room_seed, level) for level, v in enumerate(t60s)] + list(measured)
 
 
-def _render_windows(ctx, waves, centers, coefs, cfg, LPF, CUTOFF, precision, snrs=(), level=None, seed=0, rirs=(), room=None, firs=None):
+def _render_windows(ctx, waves, centers, coefs, cfg, LPF, CUTOFF, precision, snrs=(), level=None, seed=0, rirs=(), room=None, firs=None,
+                    mix=None):
     """Normalised windows of some files through f2_input_batch_noisy, RENDER_GROUP files per call, every file at snrs[level]
     (level None: clean); with `room`, through f2_input_batch_wet with every file in rirs[room]; with `firs` (a filter per level),
-    through f2_input_batch_coloured"""
+    through f2_input_batch_coloured; with `mix` (a (C, C) matrix), through f2_input_batch_smeared with every file mixed by it"""
     Cn = coefs.shape[0]
     out = numpy.empty((int(sum(len(c) for c in centers)), cfg.dots_per_input, Cn), numpy.float32)
     row = 0
@@ -361,7 +381,13 @@ def _render_windows(ctx, waves, centers, coefs, cfg, LPF, CUTOFF, precision, snr
         if n == 0:
             continue
         level_of = None if level is None else numpy.full(len(ws), level, numpy.int32)
-        if firs is not None:
+        if mix is not None:
+            ctx.input_batch_smeared(flat, _lib.WAVE_F64 if f64 else _lib.WAVE_I16, offsets, coefs, len(ws), Cn, bool(LPF),
+                                    float(CUTOFF) if LPF else 0.0, precision, center_offsets, numpy.concatenate(cs), cfg.radius,
+                                    cfg.step, True, rirs if room is not None else (),
+                                    None if room is None else numpy.full(len(ws), room, numpy.int32), snrs, firs, level_of, g, seed,
+                                    mix[None], numpy.zeros(len(ws), numpy.int32), out[row:row + n], _lib.MEM_HOST)
+        elif firs is not None:
             ctx.input_batch_coloured(flat, _lib.WAVE_F64 if f64 else _lib.WAVE_I16, offsets, coefs, len(ws), Cn, bool(LPF),
                                      float(CUTOFF) if LPF else 0.0, precision, center_offsets, numpy.concatenate(cs), cfg.radius,
                                      cfg.step, True, rirs if room is not None else (),
@@ -381,7 +407,7 @@ def _render_windows(ctx, waves, centers, coefs, cfg, LPF, CUTOFF, precision, snr
 
 
 def TrainFromWav(labelFile=None, LPF=False, CUTOFF=100, snrs=(), seed=None, ctx=None, verbose=1, on_epoch=None, t60s=(), rirs=(),
-                 drr_db=0.0, colours=(), noise_taps=1025):
+                 drr_db=0.0, colours=(), noise_taps=1025, spreads=(), bands=()):
     """`cnn train --engine hip --from-wav`: trains on windows rendered on the device from the WAV files of the label CSV.
 
     The TRAIN files go to the trainer once (Trainer.set_waves); the TEST files become normalised windows once, clean - the
@@ -408,6 +434,14 @@ def TrainFromWav(labelFile=None, LPF=False, CUTOFF=100, snrs=(), seed=None, ctx=
     (f2_input_batch_coloured, VALIDATION_NOISE_SEED) and once per room. 'val_acc_snr' / 'val_loss_snr' hold a list per level and
     augment gains colours (a name per level), level_snr_db and noise_taps. 'white' is the filter [1.0]: colours=('white',) trains
     the weights of `snrs` alone, bit for bit.
+    With `spreads` (ERB) and / or `bands` (numbers of vocoder bands) every epoch also draws, from
+    numpy.random.default_rng([seed, SMEAR_STREAM]), a spectral resolution in [0, Km] per TRAIN file (Km: sharp; draw_epoch_smear)
+    and renders through Trainer.render / render_wet(mixes=..., mix_of=...): the envelopes of the file's windows are mixed across
+    their channels before they are normalised (f2_trainer_render_smeared). The levels are those of `cnn smearsweep`, in its order -
+    the spreads, then the bands - and their matrices are built once with smear.SmearMatrix / smear.BandMatrix before any file is
+    read (a bad spread raises smear.py's ValueError there). The noise and room generators are drawn exactly as without them. The
+    TEST files are validated sharp as before and once more per resolution, clean and dry (f2_input_batch_smeared): the history
+    gains 'val_acc_smear' / 'val_loss_smear' and augment gains spreads, bands and smear_levels (a name per level).
     on_epoch(iterations, trainer), if given, is called after each epoch's render, before its steps (for tests and for looking at
     what the network is about to see).
     BATCH_SIZE and EPOCHS come from configF2CNN.conf. Returns (F2CNNModel, history)."""
@@ -439,6 +473,11 @@ def TrainFromWav(labelFile=None, LPF=False, CUTOFF=100, snrs=(), seed=None, ctx=
         level_snrs = tuple(v for _, _, v in grid)
         level_names = ['{} {}dB'.format(name, _level_text(v)) for _, name, v in grid]
     K = len(level_snrs)
+    # (the mixing matrices likewise: a bad spread or number of bands is refused here, with smear.py's message)
+    spreads, bands = tuple(float(v) for v in spreads), tuple(bands)
+    centre_freqs, coefs = filterbank_from_config(cfg)
+    mixes, smear_names = build_smear_levels(spreads, bands, centre_freqs)
+    Km = len(smear_names)
     t60s, rir_files = tuple(float(v) for v in t60s), tuple(rirs)
     Kr = len(t60s) + len(rir_files)
     if seed is None:
@@ -464,7 +503,8 @@ def TrainFromWav(labelFile=None, LPF=False, CUTOFF=100, snrs=(), seed=None, ctx=
         print('noise colours:', ', '.join(level_names), '| taps', int(noise_taps))
     if Kr:
         print('rooms: t60 (s)', list(t60s) or 'none', '| measured', list(rir_files) or 'none', '| drr (dB) {:g}'.format(float(drr_db)))
-    _, coefs = filterbank_from_config(cfg)
+    if Km:
+        print('spectral resolutions:', ', '.join(smear_names))
     coefs = numpy.ascontiguousarray(coefs, dtype=numpy.float64)
     ctx = ctx or _lib.default_context()
     try:
@@ -476,6 +516,9 @@ def TrainFromWav(labelFile=None, LPF=False, CUTOFF=100, snrs=(), seed=None, ctx=
         for r in range(Kr if len(y_test) else 0):
             val.append(_render_windows(ctx, [waves[k] for k in test], [lw.centers[k] for k in test], coefs, cfg, LPF, CUTOFF,
                                        FFT_PRECISION, rirs=val_rooms, room=r))
+        for m in range(Km if len(y_test) else 0):
+            val.append(_render_windows(ctx, [waves[k] for k in test], [lw.centers[k] for k in test], coefs, cfg, LPF, CUTOFF,
+                                       FFT_PRECISION, mix=mixes[m]))
         x_val, y_val = numpy.concatenate(val), numpy.tile(y_test, len(val))
         groups = numpy.repeat(numpy.arange(len(val), dtype=numpy.int32), len(y_test))
         trainer, rng = _hip_trainer(cfg.dots_per_input, coefs.shape[0], seed, 1e-4, 1e-6, ctx)
@@ -485,11 +528,14 @@ def TrainFromWav(labelFile=None, LPF=False, CUTOFF=100, snrs=(), seed=None, ctx=
         room_rng = numpy.random.default_rng([seed, ROOM_STREAM])
         noise_seeds, val_snr = [], {"val_acc_snr": [[] for _ in level_snrs], "val_loss_snr": [[] for _ in level_snrs]}
         room_seeds, val_room = [], {"val_acc_room": [[] for _ in range(Kr)], "val_loss_room": [[] for _ in range(Kr)]}
-        if not K and not Kr:
+        smear_rng = numpy.random.default_rng([seed, SMEAR_STREAM])
+        val_smear = {"val_acc_smear": [[] for _ in range(Km)], "val_loss_smear": [[] for _ in range(Km)]}
+        if not K and not Kr and not Km:
             trainer.render()
 
         def run_epoch():
             level_of, noise_seed = None, 0
+            mix_of = draw_epoch_smear(smear_rng, Km, len(train)) if Km else None
             if K:
                 level_of, noise_seed = draw_epoch_noise(noise_rng, K, len(train))
                 noise_seeds.append(noise_seed)
@@ -497,16 +543,16 @@ def TrainFromWav(labelFile=None, LPF=False, CUTOFF=100, snrs=(), seed=None, ctx=
                 room_of, room_seed = draw_epoch_rooms(room_rng, Kr, len(train))
                 room_seeds.append(room_seed)
                 trainer.render_wet(build_rooms(t60s, measured, cfg.framerate, drr_db, room_seed), room_of, level_snrs, level_of, noise_seed,
-                                   firs=firs)
-            elif K:
-                trainer.render(level_snrs, level_of, noise_seed, firs=firs)
+                                   firs=firs, mixes=mixes, mix_of=mix_of)
+            elif K or Km:
+                trainer.render(level_snrs, level_of, noise_seed, firs=firs, mixes=mixes, mix_of=mix_of)
             if on_epoch:
                 on_epoch(trainer.iterations, trainer)
             return trainer.steps(rng.permutation(len(y_train)), batch_size)
 
         def validate():
             if not len(y_test):
-                for per in (val_snr, val_room):
+                for per in (val_snr, val_room, val_smear):
                     for k in per:
                         for per_level in per[k]:
                             per_level.append(float("nan"))
@@ -520,9 +566,13 @@ def TrainFromWav(labelFile=None, LPF=False, CUTOFF=100, snrs=(), seed=None, ctx=
             for r in range(Kr):
                 val_room["val_acc_room"][r].append(float(acc[K + 1 + r]))
                 val_room["val_loss_room"][r].append(float(loss[K + 1 + r]))
-            if verbose and (K or Kr):
+            for m in range(Km):
+                val_smear["val_acc_smear"][m].append(float(acc[K + Kr + 1 + m]))
+                val_smear["val_loss_smear"][m].append(float(loss[K + Kr + 1 + m]))
+            if verbose and (K or Kr or Km):
                 print("    val_acc clean {:.4f}".format(acc[0]) + "".join(" | {} {:.4f}".format(s, a) for s, a in zip(level_names, acc[1:])) +
-                      "".join(" | room {} {:.4f}".format(r, a) for r, a in enumerate(acc[K + 1:])))
+                      "".join(" | room {} {:.4f}".format(r, a) for r, a in enumerate(acc[K + 1:K + Kr + 1])) +
+                      "".join(" | {} {:.4f}".format(s, a) for s, a in zip(smear_names, acc[K + Kr + 1:])))
             return float(loss[0]), float(acc[0])
 
         model, history = fit_epochs(run_epoch, validate, trainer.model, len(y_train), epochs, verbose)
@@ -534,18 +584,22 @@ def TrainFromWav(labelFile=None, LPF=False, CUTOFF=100, snrs=(), seed=None, ctx=
         history.update(val_snr)
     if Kr:
         history.update(val_room)
+    if Km:
+        history.update(val_smear)
     model.save('last_trained_model')
     print("Model saved as 'last_trained_model'.")
     if len(y_test):
         print('Test loss:', history["val_loss"][-1])
         print('Test accuracy:', history["val_acc"][-1])
     results = dict(history)
-    if K or Kr:
+    if K or Kr or Km:
         results["augment"] = {"snrs": list(snrs), "seed": int(seed), "noise_seed": noise_seeds}
     if colours:
         results["augment"].update({"colours": [name for _, name, _ in grid], "level_snr_db": list(level_snrs), "noise_taps": int(noise_taps)})
     if Kr:
         results["augment"].update({"t60": list(t60s), "rirs": list(rir_files), "drr": float(drr_db), "room_seed": room_seeds})
+    if Km:
+        results["augment"].update({"spreads": list(spreads), "bands": [int(v) for v in bands], "smear_levels": list(smear_names)})
     with open('last_trained_model_results.json', 'w') as fp:
         json.dump(results, fp)
     print("History saved as 'last_trained_model_results.json'")

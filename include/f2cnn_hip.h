@@ -1206,6 +1206,73 @@ int f2_trainer_render_coloured(f2_ctx* ctx, f2_trainer* trainer, const double* r
                                const double* fir /* or NULL: white */, const int64_t* fir_offsets, int K,
                                const int32_t* level_of /* host, B, or NULL */, uint64_t seed);
 
+/* ---- Training at reduced resolution: one spectral resolution per utterance, new every epoch ---------------------------------
+ * f2_channel_mix_levels mixes every sample of every envelope at every one of K levels - what a sweep wants. A training render
+ * wants the windows of its labelled timepoints, one level per utterance: 3.8 % of the sample columns of a corpus of 3 s files with
+ * 164 windows each. These entries mix those columns and no others, inside the gather: no second envelope buffer. The degradation
+ * acts on the envelopes, so it comes last: room, noise, envelopes, mixing gather. (f2_version stays 115 with these entries: look
+ * the symbols up.)
+ *
+ * f2_gather_windows_mixed (stateless): the ragged gather of f2_input_batch on envelopes that are already in memory, with a mixing
+ * matrix per utterance. Window e of utterance b, at level l = mix_of[b]:
+ *   l < K    v[k][c] = sum over c' of mix[l][c][c'] * env_b[c'][centers[e] + step * (k - radius)], by f2_channel_mix_levels'
+ *            arithmetic word for word: one float64 accumulator per output, starting from +0.0; c' ascending over a span that
+ *            holds the row's support (first to one past the last non-zero weight, found on the host; zeros inside it are walked);
+ *            acc = fma(w, x, acc); the sum of one output never split across lanes; no atomics; a closing acc + 0.0. Then
+ *            f2_input_batch's normaliser on v: (ln v - ln min) / (ln max - ln min) over the window in float64, then float32; an
+ *            all-equal window is zeros; with normalize == 0 the window is (float) v.
+ *   l == K   sharp: f2_input_batch's gather, with no mixing pass. An identity matrix is mixed like any other.
+ *   mix_of == NULL or K == 0: every utterance is sharp, and mix may be NULL.
+ * Identity with the sweep: the bits of a mixed value depend on its envelope column and its matrix row alone, so window e is bit
+ * for bit the plain ragged gather on utterance b's block of level mix_of[b] of f2_channel_mix_levels(env, mix, K). A window does
+ * not depend on B, the utterance's place in the batch, the levels of the other utterances, K, or the memory space.
+ *   kernel   one workgroup of 256 threads per window. The window's R x C values are read once into LDS, the mixed window is
+ *            formed into a second LDS array, and the reduction, the flag rule and the epilogue are the device function the plain
+ *            gather calls. The weights are uploaded once per call as the transposed, zero-padded image of f2_channel_mix_levels
+ *            with the span of every tile of 16 rows beside it. Plain vector stores.
+ *   env      ragged (C, n_b) float64 blocks, utterance b at C * offsets[b], in mem_space (F2_MEM_HOST or F2_MEM_DEVICE)
+ *   windows  (center_offsets[B], 2 * radius + 1, C) float32, in mem_space; device pointers need element alignment only
+ *   offsets (B+1), center_offsets (B+1), centers (relative to their utterance), mix (K, C, C), mix_of (B)   host
+ * F2_MEM_DEVICE: the call enqueues on the context's stream and waits only for the flag, that is with normalize != 0, as
+ * f2_input_batch. F2_MEM_HOST: it returns when windows is filled.
+ * Errors, before anything is launched or written: what f2_input_batch rejects of B, C, radius, step, offsets, center_offsets,
+ * NULL data pointers and windows that leave their utterance (F2_ERR_INVALID); K < 0 (F2_ERR_INVALID); unless every utterance is
+ * sharp by mix_of == NULL or K == 0: what f2_channel_mix_levels rejects of mix, K and C, with its statuses - a NULL mix or a
+ * weight that is not finite: F2_ERR_INVALID, K > F2_SMEAR_MAX_LEVELS = 64 or C > F2_SMEAR_MAX_CHANNELS = 512:
+ * F2_ERR_UNSUPPORTED - a mix_of entry outside [0, K] (F2_ERR_INVALID, the message names the utterance), and a window whose two
+ * arrays, (2 * radius + 1) * (2 C + 1) float64 values, do not fit the 150 KiB of LDS of a workgroup (F2_ERR_UNSUPPORTED).
+ * A value <= 0 in a window under normalisation (a matrix row of zeros, for one): F2_ERR_NONPOSITIVE after the run, that window
+ * zeros, as f2_input_batch.
+ *
+ * f2_input_batch_smeared: f2_input_batch_coloured's arguments plus mix, Km, mix_of behind seed. Bit for bit
+ * f2_gather_windows_mixed on the envelopes f2_input_batch_coloured gathers from; nothing leaves the device in between. Km == 0 or
+ * mix_of == NULL: bit for bit f2_input_batch_coloured (it is that call). Errors: those of f2_input_batch_coloured, then those of
+ * f2_gather_windows_mixed's matrices and levels, all before a launch.
+ *
+ * f2_trainer_render_smeared: f2_trainer_render_coloured's arguments plus mix, Km, mix_of behind seed. Group g is bit for bit
+ * f2_input_batch_smeared on its utterances with first_utterance = g group, normalize = 1 and the stored options; the image of the
+ * matrices goes up once per call into a buffer the trainer owns, not once per group. f2_trainer_render_coloured is this call
+ * without matrices, bit for bit. Errors: f2_trainer_render_coloured's and those of the matrices and levels, nothing launched.
+ */
+int f2_gather_windows_mixed(f2_ctx* ctx, const double* env /* ragged (C, n_b) blocks, mem_space */, const int64_t* offsets /* host, B+1 */,
+                            int B, int C, const int64_t* center_offsets /* host, B+1 */, const int64_t* centers /* host */, int radius,
+                            int step, int normalize, const double* mix /* host, (K, C, C), or NULL */, int K,
+                            const int32_t* mix_of /* host, B, each in [0, K], or NULL */,
+                            float* windows /* (center_offsets[B], 2 radius + 1, C), mem_space */, int mem_space);
+int f2_input_batch_smeared(f2_ctx* ctx, const void* wave, int wave_dtype, const int64_t* offsets, const double* coefs, int B, int C,
+                           int lpf, double cutoff_hz, int fft_precision, const int64_t* center_offsets, const int64_t* centers,
+                           int radius, int step, int normalize, const double* rir, const int64_t* rir_offsets, int Kr,
+                           const int32_t* room_of, const double* snr_db, const double* fir /* or NULL: white */,
+                           const int64_t* fir_offsets, int K, const int32_t* level_of, uint32_t first_utterance, uint64_t seed,
+                           const double* mix /* host, (Km, C, C), or NULL: sharp */, int Km,
+                           const int32_t* mix_of /* host, B, each in [0, Km], or NULL */, float* windows, int mem_space);
+int f2_trainer_render_smeared(f2_ctx* ctx, f2_trainer* trainer, const double* rir, const int64_t* rir_offsets, int Kr,
+                              const int32_t* room_of /* host, B, or NULL */, const double* snr_db,
+                              const double* fir /* or NULL: white */, const int64_t* fir_offsets, int K,
+                              const int32_t* level_of /* host, B, or NULL */, uint64_t seed,
+                              const double* mix /* host, (Km, C, C), or NULL: sharp */, int Km,
+                              const int32_t* mix_of /* host, B, or NULL */);
+
 #ifdef __cplusplus
 }
 #endif
