@@ -392,18 +392,20 @@ class Context:
                                           mem_space))
         return sigma
 
+    def _input_batch_staged(self, name, v):
+        """f2_input_batch_<name> from the arguments `v` of its method: input_batch's, with that symbol's stage arguments before `windows`"""
+        offsets, center_offsets, centers = (np.ascontiguousarray(v[k], dtype=np.int64) for k in ("offsets", "center_offsets", "centers"))
+        args, alive = _stage_args(_STAGE_KEYS[name], v)
+        self.check(getattr(self.lib, "f2_input_batch_" + name)(
+            self.handle, _ptr(v["wave"]), v["wave_dtype"], _ptr(offsets), _ptr(v["coefs"]), int(v["B"]), v["Cn"], int(bool(v["lpf"])),
+            float(v["cutoff"]), v["precision"], _ptr(center_offsets), _ptr(centers), v["radius"], v["step"], int(bool(v["normalize"])),
+            *args, _ptr(v["windows"]), v["mem_space"]))
+
     def input_batch_noisy(self, wave, wave_dtype, offsets, coefs, B, Cn, lpf, cutoff, precision, center_offsets, centers, radius,
                           step, normalize, snr_db, level_of, first_utterance, seed, windows, mem_space):
         """input_batch on the batch as noise_pick leaves it, the noisy waveform never leaving the device; see
         f2_input_batch_noisy."""
-        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
-        center_offsets = np.ascontiguousarray(center_offsets, dtype=np.int64)
-        centers = np.ascontiguousarray(centers, dtype=np.int64)
-        snr, lev = _noise_levels(snr_db, level_of)
-        self.check(self.lib.f2_input_batch_noisy(self.handle, _ptr(wave), wave_dtype, _ptr(offsets), _ptr(coefs), int(B), Cn,
-                                                 int(bool(lpf)), float(cutoff), precision, _ptr(center_offsets), _ptr(centers),
-                                                 radius, step, int(bool(normalize)), _ptr(snr) if len(snr) else None, len(snr),
-                                                 _ptr(lev), int(first_utterance), int(seed) & (2 ** 64 - 1), _ptr(windows), mem_space))
+        self._input_batch_staged("noisy", locals())
 
     def reverb_pick(self, wave, wave_dtype, offsets, B, rirs, room_of, wet, mem_space):
         """The batch with one room per utterance (see f2_reverb_pick): utterance b convolved with rirs[room_of[b]] (a sequence of
@@ -418,16 +420,7 @@ class Context:
                         normalize, rirs, room_of, snr_db, level_of, first_utterance, seed, windows, mem_space):
         """input_batch on the batch as reverb_pick, then noise_pick leave it, neither waveform leaving the device; see
         f2_input_batch_wet."""
-        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
-        center_offsets = np.ascontiguousarray(center_offsets, dtype=np.int64)
-        centers = np.ascontiguousarray(centers, dtype=np.int64)
-        snr, lev = _noise_levels(snr_db, level_of)
-        taps, rir_offsets, room = _rooms(rirs, room_of)
-        self.check(self.lib.f2_input_batch_wet(self.handle, _ptr(wave), wave_dtype, _ptr(offsets), _ptr(coefs), int(B), Cn,
-                                               int(bool(lpf)), float(cutoff), precision, _ptr(center_offsets), _ptr(centers), radius,
-                                               step, int(bool(normalize)), _ptr(taps) if len(taps) else None, _ptr(rir_offsets),
-                                               len(rir_offsets) - 1, _ptr(room), _ptr(snr) if len(snr) else None, len(snr), _ptr(lev),
-                                               int(first_utterance), int(seed) & (2 ** 64 - 1), _ptr(windows), mem_space))
+        self._input_batch_staged("wet", locals())
 
     def shaped_noise_pick(self, wave, wave_dtype, offsets, B, snr_db, firs, level_of, first_utterance, seed, noisy, mem_space,
                           sigma=None):
@@ -449,19 +442,7 @@ class Context:
                              step, normalize, rirs, room_of, snr_db, firs, level_of, first_utterance, seed, windows, mem_space):
         """input_batch on the batch as reverb_pick, then shaped_noise_pick leave it, neither waveform leaving the device; firs None:
         input_batch_wet. See f2_input_batch_coloured."""
-        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
-        center_offsets = np.ascontiguousarray(center_offsets, dtype=np.int64)
-        centers = np.ascontiguousarray(centers, dtype=np.int64)
-        snr, lev = _noise_levels(snr_db, level_of)
-        fir_taps, fir_offsets = _colours(firs, len(snr))
-        taps, rir_offsets, room = _rooms(rirs, room_of)
-        self.check(self.lib.f2_input_batch_coloured(self.handle, _ptr(wave), wave_dtype, _ptr(offsets), _ptr(coefs), int(B), Cn,
-                                                    int(bool(lpf)), float(cutoff), precision, _ptr(center_offsets), _ptr(centers),
-                                                    radius, step, int(bool(normalize)), _ptr(taps) if len(taps) else None,
-                                                    _ptr(rir_offsets), len(rir_offsets) - 1, _ptr(room),
-                                                    _ptr(snr) if len(snr) else None, _ptr(fir_taps), _ptr(fir_offsets), len(snr),
-                                                    _ptr(lev), int(first_utterance), int(seed) & (2 ** 64 - 1), _ptr(windows),
-                                                    mem_space))
+        self._input_batch_staged("coloured", locals())
 
     def gather_windows_mixed(self, env, offsets, B, Cn, center_offsets, centers, radius, step, normalize, mixes, mix_of, windows,
                              mem_space):
@@ -483,20 +464,7 @@ class Context:
                             mem_space):
         """input_batch_coloured whose gather is gather_windows_mixed: room, noise, envelopes, then the windows of utterance b
         through mixes[mix_of[b]], nothing leaving the device; mixes None: input_batch_coloured. See f2_input_batch_smeared."""
-        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
-        center_offsets = np.ascontiguousarray(center_offsets, dtype=np.int64)
-        centers = np.ascontiguousarray(centers, dtype=np.int64)
-        snr, lev = _noise_levels(snr_db, level_of)
-        fir_taps, fir_offsets = _colours(firs, len(snr))
-        taps, rir_offsets, room = _rooms(rirs, room_of)
-        mix, mlev = _smears(mixes, mix_of, Cn)
-        self.check(self.lib.f2_input_batch_smeared(self.handle, _ptr(wave), wave_dtype, _ptr(offsets), _ptr(coefs), int(B), Cn,
-                                                   int(bool(lpf)), float(cutoff), precision, _ptr(center_offsets), _ptr(centers),
-                                                   radius, step, int(bool(normalize)), _ptr(taps) if len(taps) else None,
-                                                   _ptr(rir_offsets), len(rir_offsets) - 1, _ptr(room),
-                                                   _ptr(snr) if len(snr) else None, _ptr(fir_taps), _ptr(fir_offsets), len(snr),
-                                                   _ptr(lev), int(first_utterance), int(seed) & (2 ** 64 - 1),
-                                                   _ptr(mix) if len(mix) else None, len(mix), _ptr(mlev), _ptr(windows), mem_space))
+        self._input_batch_staged("smeared", locals())
 
     def cnn_create(self, tensors, rows, channels):
         """tensors: 12 contiguous float32 arrays in Keras layouts (see include/f2cnn_hip.h). Returns a handle."""
@@ -903,45 +871,30 @@ class Context:
                                                  int(bool(lpf)), float(cutoff), precision, _ptr(center_offsets), _ptr(centers),
                                                  _ptr(signs), radius, step, int(group)))
 
+    def _trainer_render_staged(self, name, v):
+        """f2_trainer_render (name "noisy") / f2_trainer_render_<name> from the arguments `v` of its method; no first_utterance: a render counts"""
+        args, alive = _stage_args([k for k in _STAGE_KEYS[name] if k != "first_utterance"], v)
+        self.check(getattr(self.lib, "f2_trainer_render" + ("" if name == "noisy" else "_" + name))(self.handle, v["handle"], *args))
+
     def trainer_render(self, handle, snr_db=(), level_of=None, seed=0):
         """The training windows from the stored waves, utterance b at snr_db[level_of[b]] (see f2_trainer_render)"""
-        snr, lev = _noise_levels(snr_db, level_of)
-        self.check(self.lib.f2_trainer_render(self.handle, handle, _ptr(snr) if len(snr) else None, len(snr), _ptr(lev),
-                                              int(seed) & (2 ** 64 - 1)))
+        self._trainer_render_staged("noisy", locals())
 
     def trainer_render_wet(self, handle, rirs=(), room_of=None, snr_db=(), level_of=None, seed=0):
         """The training windows from the stored waves, utterance b in room rirs[room_of[b]] and at snr_db[level_of[b]] (see
         f2_trainer_render_wet)"""
-        snr, lev = _noise_levels(snr_db, level_of)
-        taps, rir_offsets, room = _rooms(rirs, room_of)
-        self.check(self.lib.f2_trainer_render_wet(self.handle, handle, _ptr(taps) if len(taps) else None, _ptr(rir_offsets),
-                                                  len(rir_offsets) - 1, _ptr(room), _ptr(snr) if len(snr) else None, len(snr),
-                                                  _ptr(lev), int(seed) & (2 ** 64 - 1)))
+        self._trainer_render_staged("wet", locals())
 
     def trainer_render_coloured(self, handle, rirs=(), room_of=None, snr_db=(), firs=None, level_of=None, seed=0):
         """The training windows from the stored waves, utterance b in room rirs[room_of[b]] and under noise of the colour
         firs[level_of[b]] at snr_db[level_of[b]]; firs None: trainer_render_wet (see f2_trainer_render_coloured)"""
-        snr, lev = _noise_levels(snr_db, level_of)
-        fir_taps, fir_offsets = _colours(firs, len(snr))
-        taps, rir_offsets, room = _rooms(rirs, room_of)
-        self.check(self.lib.f2_trainer_render_coloured(self.handle, handle, _ptr(taps) if len(taps) else None, _ptr(rir_offsets),
-                                                       len(rir_offsets) - 1, _ptr(room), _ptr(snr) if len(snr) else None,
-                                                       _ptr(fir_taps), _ptr(fir_offsets), len(snr), _ptr(lev),
-                                                       int(seed) & (2 ** 64 - 1)))
+        self._trainer_render_staged("coloured", locals())
 
     def trainer_render_smeared(self, handle, rirs=(), room_of=None, snr_db=(), firs=None, level_of=None, seed=0, mixes=None,
                                mix_of=None, channels=None):
         """trainer_render_coloured with the windows of utterance b mixed across their channels by mixes[mix_of[b]] ((K, C, C)
         float64), sharp where mix_of[b] == K; mixes None: trainer_render_coloured (see f2_trainer_render_smeared)"""
-        snr, lev = _noise_levels(snr_db, level_of)
-        fir_taps, fir_offsets = _colours(firs, len(snr))
-        taps, rir_offsets, room = _rooms(rirs, room_of)
-        mix, mlev = _smears(mixes, mix_of, channels)
-        self.check(self.lib.f2_trainer_render_smeared(self.handle, handle, _ptr(taps) if len(taps) else None, _ptr(rir_offsets),
-                                                      len(rir_offsets) - 1, _ptr(room), _ptr(snr) if len(snr) else None,
-                                                      _ptr(fir_taps), _ptr(fir_offsets), len(snr), _ptr(lev),
-                                                      int(seed) & (2 ** 64 - 1), _ptr(mix) if len(mix) else None, len(mix),
-                                                      _ptr(mlev)))
+        self._trainer_render_staged("smeared", locals())
 
     def trainer_get_windows(self, handle, first, count, shape):
         """Rows first .. first + count - 1 of the training set: (count, *shape) float32 windows and (count) uint8 labels"""
@@ -1095,6 +1048,31 @@ def _smears(mixes, mix_of, Cn):
     mix = _pack_mix(mixes, Cn)
     lev = None if mix_of is None else np.ascontiguousarray(mix_of, dtype=np.int32).reshape(-1)
     return mix, lev
+
+
+# the stage arguments of f2_input_batch_<name>, in the order of the C declaration (f2_trainer_render<_name>: without first_utterance)
+_STAGE_KEYS = {"noisy": "snr_db K level_of first_utterance seed".split()}
+_STAGE_KEYS["wet"] = "rir rir_offsets Kr room_of".split() + _STAGE_KEYS["noisy"]
+_STAGE_KEYS["coloured"] = "rir rir_offsets Kr room_of snr_db fir fir_offsets K level_of first_utterance seed".split()
+_STAGE_KEYS["smeared"] = _STAGE_KEYS["coloured"] + "mix Km mix_of".split()
+
+
+def _stage_args(keys, v):
+    """([the C arguments named by `keys`], what holds their arrays until the call returns) from the Python arguments `v` of a call with
+    augmentation stages: noise levels, colours, rooms, spectral resolutions, marshalled in that order and only where the symbol has
+    them. Arrays become their addresses; counts, first_utterance and seed are plain ints, which _ptr hands through as they are"""
+    snr, lev = _noise_levels(v["snr_db"], v["level_of"])
+    a = dict(snr_db=snr if len(snr) else None, K=len(snr), level_of=lev, first_utterance=int(v.get("first_utterance", 0)),
+             seed=int(v["seed"]) & (2 ** 64 - 1))
+    if "fir" in keys:
+        a["fir"], a["fir_offsets"] = _colours(v["firs"], len(snr))
+    if "rir" in keys:
+        taps, a["rir_offsets"], a["room_of"] = _rooms(v["rirs"], v["room_of"])
+        a.update(rir=taps if len(taps) else None, Kr=len(a["rir_offsets"]) - 1)
+    if "mix" in keys:
+        mix, a["mix_of"] = _smears(v["mixes"], v["mix_of"], v.get("Cn", v.get("channels")))
+        a.update(mix=mix if len(mix) else None, Km=len(mix))
+    return [_ptr(a[k]) for k in keys], a
 
 
 def resampled_length(n, up, down):

@@ -895,43 +895,40 @@ int f2_trainer_set_waves(f2_ctx* ctx, f2_trainer* t, const void* wave, int wave_
     return F2_OK;
 }
 
+// [offsets | taps] of the K filters of a stage into `area`, enqueued once for every group of the render in flight
+static int upload_taps(f2_ctx* ctx, f2_scratch& area, const int64_t* offsets, const double* taps, int K, const int64_t** d_offsets,
+                       const double** d_taps) {
+    const size_t obytes = sizeof(int64_t) * ((size_t)K + 1), tbytes = sizeof(double) * (size_t)offsets[K];
+    F2_TRY(f2_reserve(ctx, area, obytes + tbytes));
+    F2_TRY(f2_upload_async(ctx, area.ptr, offsets, obytes));
+    F2_TRY(f2_upload_async(ctx, (char*)area.ptr + obytes, taps, tbytes));
+    *d_offsets = (const int64_t*)area.ptr, *d_taps = (const double*)((const char*)area.ptr + obytes);
+    return F2_OK;
+}
+
 int f2_trainer_render_smeared(f2_ctx* ctx, f2_trainer* t, const double* rir, const int64_t* rir_offsets, int Kr, const int32_t* room_of,
                               const double* snr_db, const double* fir, const int64_t* fir_offsets, int K, const int32_t* level_of,
                               uint64_t seed, const double* mix, int Km, const int32_t* mix_of) {
     F2_TRY(f2_check_ctx(ctx));
     F2_TRY(check_trainer(ctx, t));
     F2_CHECK(ctx, t->have_waves, F2_ERR_INVALID, "the trainer has no waves to render from (f2_trainer_set_waves)");
-    f2_noise_pick_args Nall = {snr_db, K, level_of, 0, seed, fir, fir_offsets};
-    F2_TRY(f2_check_noise_pick(ctx, t->B, Nall));
-    F2_TRY(f2_check_noise_colours(ctx, t->B, &Nall, false));
-    f2_reverb_pick_args R = {rir, rir_offsets, Kr, room_of, nullptr, nullptr};
-    F2_TRY(f2_check_reverb_pick(ctx, t->B, R));
-    f2_mix_gather_args S;
-    S.mix = mix, S.K = Km, S.mix_of = mix_of;
-    F2_TRY(f2_check_mix_gather(ctx, t->B, t->channels, t->radius, &S));
+    f2_augment_args A = f2_augment_args::of(rir, rir_offsets, Kr, room_of, snr_db, fir, fir_offsets, K, level_of, 0, seed, mix, Km, mix_of);
+    F2_TRY(f2_check_noise_pick(ctx, t->B, A.noise));
+    F2_TRY(A.check(ctx, t->B, t->channels, t->radius));
     if (t->n == 0) return F2_OK;
     const size_t xs = (size_t)t->rows * t->channels, ws = t->wave_dtype == F2_WAVE_I16 ? 2 : 8;
     const int64_t* d_centers = (const int64_t*)t->centers.ptr;
     const int* d_win_utt = (const int*)((const char*)t->centers.ptr + sizeof(int64_t) * (size_t)t->n);
-    if (!R.dry()) {   // the taps and their offsets go up once, for every group
-        const size_t obytes = sizeof(int64_t) * ((size_t)Kr + 1);
-        F2_TRY(f2_reserve(ctx, t->rir, obytes + sizeof(double) * (size_t)rir_offsets[Kr]));
-        F2_TRY(f2_upload_async(ctx, t->rir.ptr, rir_offsets, obytes));
-        F2_TRY(f2_upload_async(ctx, (char*)t->rir.ptr + obytes, rir, sizeof(double) * (size_t)rir_offsets[Kr]));
-        R.d_rir_off = (const int64_t*)t->rir.ptr, R.d_rir = (const double*)((const char*)t->rir.ptr + obytes);
+    // what every group reads goes up once: the rooms' taps, the filters of the noise (a group whose utterances are all clean keeps
+    // the colours: its tiles copy), and the mixing matrices as the image the gather reads (a group whose utterances are all sharp
+    // takes the mixing gather's sharp path)
+    if (!A.rooms.dry()) F2_TRY(upload_taps(ctx, t->rir, rir_offsets, rir, Kr, &A.rooms.d_rir_off, &A.rooms.d_rir));
+    if (A.noise.coloured()) F2_TRY(upload_taps(ctx, t->fir, fir_offsets, fir, K, &A.noise.d_fir_off, &A.noise.d_fir));
+    if (!A.smear.sharp() && !A.smear.all_sharp) {
+        F2_TRY(f2_reserve(ctx, t->mix, f2_mix_image_bytes(*A.smear.plan)));
+        F2_TRY(f2_upload_mix_image(ctx, *A.smear.plan, t->mix.ptr, &A.smear.d_spans, &A.smear.d_wT));
     }
-    if (Nall.coloured()) {   // ... and so do the filters of the noise
-        const size_t obytes = sizeof(int64_t) * ((size_t)K + 1);
-        F2_TRY(f2_reserve(ctx, t->fir, obytes + sizeof(double) * (size_t)fir_offsets[K]));
-        F2_TRY(f2_upload_async(ctx, t->fir.ptr, fir_offsets, obytes));
-        F2_TRY(f2_upload_async(ctx, (char*)t->fir.ptr + obytes, fir, sizeof(double) * (size_t)fir_offsets[K]));
-        Nall.d_fir_off = (const int64_t*)t->fir.ptr, Nall.d_fir = (const double*)((const char*)t->fir.ptr + obytes);
-    }
-    if (!S.sharp() && !S.all_sharp) {   // ... and the mixing matrices, as the image the gather reads
-        F2_TRY(f2_reserve(ctx, t->mix, f2_mix_image_bytes(S.plan)));
-        F2_TRY(f2_upload_mix_image(ctx, S.plan, t->mix.ptr, &S.d_spans, &S.d_wT));
-    }
-    F2_HIP(ctx, hipMemsetAsync(ctx->flags.ptr, 0, sizeof(int), ctx->stream));
+    F2_TRY(f2_reset_flag(ctx));
     std::vector<int64_t> off;
     // group after group onto the stream, each into its rows of x; one wait at the end
     for (int b0 = 0; b0 < t->B; b0 += std::min(t->group, t->B - b0)) {
@@ -940,19 +937,12 @@ int f2_trainer_render_smeared(f2_ctx* ctx, f2_trainer* t, const double* rir, con
         if (nw == 0) continue;
         off.resize((size_t)nb + 1);
         for (int b = 0; b <= nb; ++b) off[(size_t)b] = t->offsets[(size_t)b0 + b] - t->offsets[(size_t)b0];
-        f2_noise_pick_args N = Nall;   // (a group whose utterances are all clean keeps the colours: its tiles copy)
-        N.level_of = level_of ? level_of + b0 : nullptr, N.first_utterance = (uint32_t)b0;
-        f2_reverb_pick_args Rg = R;
-        if (!R.dry()) Rg.room_of = room_of + b0;
-        if (!S.sharp()) S.mix_of = mix_of + b0;   // (a group whose utterances are all sharp takes the mixing gather's sharp path)
-        F2_TRY(f2_launch_noisy_windows(ctx, (const char*)t->wave.ptr + ws * (size_t)t->offsets[(size_t)b0], t->wave_dtype, off.data(),
-                                       t->coefs.data(), nb, t->channels, t->lpf, t->cutoff_hz, t->fft_precision, d_centers + w0, d_win_utt + w0,
-                                       true, nw, t->radius, t->step, 1, N, (float*)t->x.ptr + xs * (size_t)w0, &Rg, &S));
+        const f2_batch X = {(const char*)t->wave.ptr + ws * (size_t)t->offsets[(size_t)b0], t->wave_dtype, off.data(), t->coefs.data(), nb,
+                            t->channels, t->lpf, t->cutoff_hz, t->fft_precision, F2_MEM_DEVICE};
+        const f2_window_list W = {d_centers + w0, d_win_utt + w0, true, nw, t->radius, t->step, 1};
+        F2_TRY(f2_launch_noisy_windows(ctx, X, W, A.slice(b0), (float*)t->x.ptr + xs * (size_t)w0));
     }
-    F2_HIP(ctx, hipMemcpyAsync(ctx->host_flags, ctx->flags.ptr, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    F2_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    F2_CHECK(ctx, !ctx->host_flags[0], F2_ERR_NONPOSITIVE, "values must all be positive (normalizeInput)");
-    return F2_OK;
+    return f2_finish_positive(ctx);
 }
 
 // the render at full resolution: the same code, whose last call is then the plain gather

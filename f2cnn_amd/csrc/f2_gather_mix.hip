@@ -144,7 +144,8 @@ int f2_check_mix_gather(f2_ctx* ctx, int B, int C, int radius, f2_mix_gather_arg
     F2_CHECK(ctx, S->K >= 0, F2_ERR_INVALID, "negative number of mixing matrices (K=%d)", S->K);
     S->all_sharp = true;
     if (S->sharp()) return F2_OK;
-    F2_TRY(f2_check_mix(ctx, S->mix, S->K, C, &S->plan));
+    S->plan = std::make_shared<f2_smear_plan>();
+    F2_TRY(f2_check_mix(ctx, S->mix, S->K, C, S->plan.get()));
     for (int b = 0; b < B; ++b) {
         F2_CHECK(ctx, S->mix_of[b] >= 0 && S->mix_of[b] <= S->K, F2_ERR_INVALID, "utterance %d: mixing level %d is outside [0, %d]", b,
                  (int)S->mix_of[b], S->K);

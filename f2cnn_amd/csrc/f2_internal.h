@@ -7,6 +7,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <utility>
@@ -593,17 +594,10 @@ int f2_launch_noise_pick(f2_ctx* ctx, const void* d_wave, int wave_dtype, const 
 // ... and its first launch alone (k_noise_pick_sigma), for a stage whose second kernel is another (k_shaped_noise_pick)
 int f2_launch_noise_pick_sigma(f2_ctx* ctx, const void* d_wave, int wave_dtype, const int64_t* d_offsets, const double* d_lin,
                                const int32_t* d_level, int B, int K, double* d_sigma);
-// f2_pipeline.hip, the driver f2_input_batch_noisy and f2_trainer_render share: the B utterances at d_wave (device, offsets from 0
-// on the host) through the noise kernels into ctx->levels, then f2_input_batch's envelopes and gather on that float64 buffer, the
-// windows written to d_windows (device). The centres and the utterance of every window (counted inside this batch) are either on
-// the device already (lists_on_device) or host arrays that go up behind the envelope launches, as in f2_input_batch. Enqueues only; the gather ORs into word 0 of ctx->flags, which the caller resets before and reads after. The arguments
-// have passed f2_check_noise_pick and f2_input_batch's checks. With `rooms` (passed f2_check_reverb_pick) that are not dry, the
-// utterances go through f2_launch_reverb_pick into ctx->wet first and the noise kernels read that float64 buffer.
-// A coloured stage (fir != NULL, passed f2_check_noise_colours) filters the deviates of level l with the taps fir + fir_offsets[l]
-// (host, K + 1 offsets) through k_shaped_noise_pick instead of k_noise_pick; sigma is k_noise_pick_sigma's in both.
-// d_fir / d_fir_off: device copies that are up already (a render uploads them once for all its groups), or NULL.
-// With `smear` (passed f2_check_mix_gather) that mixes anything, the last call is f2_launch_gather_mixed instead of
-// f2_launch_gather_ragged; its image goes into ctx->mix unless smear->d_wT says it is up already.
+// The noise stage of a window call or a render (f2_augment_args below). A coloured stage (fir != NULL, passed
+// f2_check_noise_colours) filters the deviates of level l with the taps fir + fir_offsets[l] (host, K + 1 offsets) through
+// k_shaped_noise_pick instead of k_noise_pick; sigma is k_noise_pick_sigma's in both. d_fir / d_fir_off: device copies that are up
+// already (a render uploads them once for all its groups), or NULL.
 struct f2_noise_pick_args {
     const double* snr_db;
     int K;
@@ -644,10 +638,6 @@ int f2_check_input_batch(f2_ctx* ctx, const void* wave, int wave_dtype, const in
 // the call's data pointers are all non-NULL (tested only where there are windows)
 int f2_check_window_lists(f2_ctx* ctx, const int64_t* offsets, int B, const int64_t* center_offsets, const int64_t* centers, int radius,
                           int step, bool data_given, int64_t* n_windows, std::vector<int>* win_utt);
-int f2_launch_noisy_windows(f2_ctx* ctx, const void* d_wave, int wave_dtype, const int64_t* offsets, const double* coefs, int B, int C,
-                            int lpf, double cutoff_hz, int fft_precision, const int64_t* centers, const int* win_utt,
-                            bool lists_on_device, int64_t n_windows, int radius, int step, int normalize, const f2_noise_pick_args& N, float* d_windows,
-                            const struct f2_reverb_pick_args* rooms = nullptr, const struct f2_mix_gather_args* smear = nullptr);
 // d_stats ((K + 1) * B pairs, zeroed by the caller) += {windows labelled rising, windows labelled as the clean level labels them}
 // per utterance of the (K + 1) * B batch whose window offsets are d_window_offsets; max_windows: the most any utterance has
 int f2_launch_label_tally(f2_ctx* ctx, const uint8_t* d_labels, const int64_t* d_window_offsets, int B, int K, int64_t max_windows,
@@ -765,7 +755,7 @@ struct f2_mix_gather_args {
     const double* mix = nullptr;
     int K = 0;
     const int32_t* mix_of = nullptr;
-    f2_smear_plan plan;
+    std::shared_ptr<f2_smear_plan> plan;   // (shared by the slices of a render)
     bool all_sharp = true;
     const int64_t* d_spans = nullptr;
     const double* d_wT = nullptr;
@@ -778,6 +768,58 @@ int f2_upload_mix_image(f2_ctx* ctx, const f2_smear_plan& P, void* d_image, cons
 int f2_launch_gather_mixed(f2_ctx* ctx, const double* d_env, int C, const int64_t* d_offsets, const int64_t* d_centers, const int* d_win_utt,
                            int64_t n_windows, int radius, int step, int normalize, const f2_smear_plan& P, const int64_t* d_spans,
                            const double* d_wT, const int32_t* d_mix_of, float* d_out, int* d_flag);
+// The augmentation stages of a window call (f2_input_batch_smeared and the entries that telescope into it) or of a render
+// (f2_trainer_render_smeared likewise), in the order they run: rooms (f2_launch_reverb_pick into ctx->wet, skipped where dry()),
+// noise (k_noise_pick or k_shaped_noise_pick into ctx->levels, reading ctx->wet behind rooms; converts alone where clean()), the
+// envelopes, and smear (f2_launch_gather_mixed instead of f2_launch_gather_ragged unless sharp() or all_sharp; its image goes into
+// ctx->mix unless smear.d_wT says it is up already). A further stage is a further record here: of() fills it from the C arguments
+// (a render passes first_utterance 0), check() checks it, slice() advances it and f2_launch_noisy_windows runs it.
+struct f2_augment_args {
+    f2_reverb_pick_args rooms;
+    f2_noise_pick_args noise;
+    f2_mix_gather_args smear;
+    static f2_augment_args of(const double* rir, const int64_t* rir_offsets, int Kr, const int32_t* room_of, const double* snr_db,
+                              const double* fir, const int64_t* fir_offsets, int K, const int32_t* level_of, uint32_t first_utterance,
+                              uint64_t seed, const double* mix, int Km, const int32_t* mix_of) {
+        f2_augment_args A = {{rir, rir_offsets, Kr, room_of, nullptr, nullptr}, {snr_db, K, level_of, first_utterance, seed, fir, fir_offsets}, {}};
+        A.smear.mix = mix, A.smear.K = Km, A.smear.mix_of = mix_of;
+        return A;
+    }
+    // colours, rooms, mix, before anything is launched (builds smear.plan): the checks behind f2_check_noise_pick, which every caller
+    // places itself - a window call runs it before its window lists
+    int check(f2_ctx* ctx, int B, int C, int radius) {
+        F2_TRY(f2_check_noise_colours(ctx, B, &noise, false));
+        F2_TRY(f2_check_reverb_pick(ctx, B, rooms));
+        return f2_check_mix_gather(ctx, B, C, radius, &smear);
+    }
+    // the stages of utterances b0 .. of the checked batch: their rows of the per-utterance tables, numbered on from b0 for the
+    // generator; the taps, the plan and what is up on the device stay
+    f2_augment_args slice(int b0) const {
+        f2_augment_args G = *this;
+        if (!rooms.dry()) G.rooms.room_of += b0;
+        if (noise.level_of) G.noise.level_of += b0;
+        if (!smear.sharp()) G.smear.mix_of += b0;
+        G.noise.first_utterance += (uint32_t)b0;
+        return G;
+    }
+};
+// The windows of a call: centres and the utterance of every window (counted inside the batch), on the device already (on_device) or
+// host arrays that go up behind the envelope launches, as in f2_input_batch
+struct f2_window_list {
+    const int64_t* centers;
+    const int* win_utt;
+    bool on_device;
+    int64_t n_windows;
+    int radius, step, normalize;
+};
+// f2_pipeline.hip, the driver f2_input_batch_smeared and f2_trainer_render_smeared share: the utterances of X (wave on the device,
+// offsets from 0 on the host) through the stages of A (which passed f2_check_noise_pick and A.check) into ctx->levels, then
+// f2_input_batch's envelopes and gather on that float64 buffer, the windows of W written to d_windows (device). Enqueues only; the
+// gather ORs into word 0 of ctx->flags, which the caller clears before (f2_reset_flag) and reads after (f2_finish_positive: waits
+// for the stream, F2_ERR_NONPOSITIVE for a window with a value <= 0 under normalisation).
+int f2_launch_noisy_windows(f2_ctx* ctx, const f2_batch& X, const f2_window_list& W, const f2_augment_args& A, float* d_windows);
+int f2_reset_flag(f2_ctx* ctx);
+int f2_finish_positive(f2_ctx* ctx);
 // f2_accuracy.hip, the kernel of f2_label_accuracy. d_counts (4 per utterance, zeroed by the caller)[4 u + 2 ref + pred] += rows
 // of utterance u (rows d_window_offsets[u] .. [u + 1] of d_labels, row j at sample origin + j * hop) that the rule of the header
 // counts against reference set u % R (d_ref_offsets: R + 1; timepoints strictly increasing inside a set, signs 0 / 1);

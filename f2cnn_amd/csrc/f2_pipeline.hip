@@ -5,28 +5,39 @@
 #include <algorithm>
 #include <cmath>
 
-namespace {
-
-constexpr int64_t CNN_CHUNK = 16384;  // windows per CNN launch group (activation workspace 1.75 GB, windows 92 MB)
-constexpr int64_t DENSE_GROUP = 8 * CNN_CHUNK;   // windows per dense1 / dense2 launch of f2_eval_batch (conv4 + dense1 outputs: 1.3 GB)
-
-int reset_flag(f2_ctx* ctx) {
+int f2_reset_flag(f2_ctx* ctx) {
     F2_HIP(ctx, hipMemsetAsync(ctx->flags.ptr, 0, sizeof(int), ctx->stream));
     return F2_OK;
 }
 
-// waits for the stream; the error of a window with a value <= 0 under normalisation (the gather kernels set the flag)
-int finish_positive(f2_ctx* ctx) {
+int f2_finish_positive(f2_ctx* ctx) {
     F2_HIP(ctx, hipMemcpyAsync(ctx->host_flags, ctx->flags.ptr, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     F2_HIP(ctx, hipStreamSynchronize(ctx->stream));
     F2_CHECK(ctx, !ctx->host_flags[0], F2_ERR_NONPOSITIVE, "values must all be positive (normalizeInput)");
     return F2_OK;
 }
 
-// the end of a call that gathers windows: their copy to a host caller; a host call and a normalising one wait (finish_positive)
+namespace {
+
+constexpr int64_t CNN_CHUNK = 16384;  // windows per CNN launch group (activation workspace 1.75 GB, windows 92 MB)
+constexpr int64_t DENSE_GROUP = 8 * CNN_CHUNK;   // windows per dense1 / dense2 launch of f2_eval_batch (conv4 + dense1 outputs: 1.3 GB)
+
+// the end of a call that gathers windows: their copy to a host caller; a host call and a normalising one wait (f2_finish_positive)
 int finish_windows(f2_ctx* ctx, const f2_output& win, int normalize) {
     F2_TRY(f2_copy_back(ctx, win));
-    return normalize || win.host ? finish_positive(ctx) : F2_OK;
+    return normalize || win.host ? f2_finish_positive(ctx) : F2_OK;
+}
+
+// The tail of a window call, behind its checks, stagings and uploads: the n_windows windows of 2 * radius + 1 rows and C channels
+// are placed (ctx->xbuf, or the caller's device buffer), the flag is reset, gather(d_windows) enqueues what writes them, and the
+// call ends as finish_windows says
+template <class Gather>
+int window_tail(f2_ctx* ctx, float* windows, int64_t n_windows, int radius, int C, int normalize, int mem_space, Gather gather) {
+    f2_output win;
+    F2_TRY(f2_place(ctx, ctx->xbuf, windows, sizeof(float) * (size_t)n_windows * (2 * radius + 1) * (size_t)C, mem_space, true, &win));
+    F2_TRY(f2_reset_flag(ctx));
+    F2_TRY(gather(win.as<float>()));
+    return finish_windows(ctx, win, normalize);
 }
 
 // Input range of f2_cnn_forward: ctx->flags words RANGE_WORD .. + 2 = bit pattern of max |x| over the finite values, inf / NaN
@@ -137,7 +148,7 @@ int f2_gather_windows(f2_ctx* ctx, const double* env, int C, int64_t N, const in
     F2_TRY(f2_place(ctx, ctx->stage_out, out, sizeof(float) * (size_t)n_windows * R * (size_t)C, mem_space, true, &win));
     const void* d_env;
     F2_TRY(f2_stage_input(ctx, env, sizeof(double) * (size_t)C * (size_t)N, mem_space, &d_env));
-    F2_TRY(reset_flag(ctx));
+    F2_TRY(f2_reset_flag(ctx));
     F2_TRY(f2_launch_gather(ctx, (const double*)d_env, C, N, d_centers, reach, n_windows, radius, step, normalize, win.as<float>(),
                             (int*)ctx->flags.ptr));
     return finish_windows(ctx, win, normalize);
@@ -303,7 +314,7 @@ int eval_cnn_begin(f2_ctx* ctx, const f2_cnn* cnn, eval_call* E, int64_t chunk, 
     F2_TRY(f2_cnn_scale_set(ctx, cnn, 0, &E->S1));   // K3's normalised windows lie in [0, 1] by construction: no range pass
     E->route = f2_cnn_call_route(ctx, cnn, E->S1 != nullptr);
     E->g0 = E->gn = 0;
-    return reset_flag(ctx);
+    return f2_reset_flag(ctx);
 }
 
 int eval_dense_flush(f2_ctx* ctx, const f2_cnn* cnn, eval_call* E) {
@@ -334,7 +345,7 @@ int eval_cnn_end(f2_ctx* ctx, const f2_cnn* cnn, eval_call* E) {
     F2_TRY(eval_dense_flush(ctx, cnn, E));
     F2_TRY(f2_copy_back(ctx, E->out.scores));
     F2_TRY(f2_copy_back(ctx, E->out.labels));
-    return finish_positive(ctx);
+    return f2_finish_positive(ctx);
 }
 
 }  // namespace
@@ -846,7 +857,7 @@ int f2_cnn_score_windows(f2_ctx* ctx, const f2_cnn* cnn, const float* windows, i
 
     F2_HIP(ctx, hipMemsetAsync(d_counts, 0, 8 * 5 * (size_t)G, ctx->stream));
     F2_HIP(ctx, hipMemsetAsync((int*)ctx->flags.ptr + SCORE_WORD, 0, sizeof(int), ctx->stream));
-    F2_TRY(reset_flag(ctx));
+    F2_TRY(f2_reset_flag(ctx));
     for (int64_t s = 0; s < n; s += chunk) {
         const int64_t m = n - s < chunk ? n - s : chunk;
         // The windows (up to 92 MB a chunk) go up straight from the caller's memory, as in f2_cnn_forward: the pinned buffers
@@ -885,7 +896,7 @@ int f2_cnn_score_windows(f2_ctx* ctx, const f2_cnn* cnn, const float* windows, i
     F2_HIP(ctx, hipMemcpyAsync(loss_sum, d_loss, sizeof(double) * (size_t)G, hipMemcpyDeviceToHost, ctx->stream));
     F2_HIP(ctx, hipMemcpyAsync(ctx->host_flags + SCORE_WORD, (int*)ctx->flags.ptr + SCORE_WORD, sizeof(int), hipMemcpyDeviceToHost,
                                ctx->stream));
-    F2_TRY(finish_positive(ctx));
+    F2_TRY(f2_finish_positive(ctx));
     const int wrong = ctx->host_flags[SCORE_WORD];
     F2_CHECK(ctx, !(wrong & 1), F2_ERR_INVALID, "a sign is neither 0 nor 1");
     F2_CHECK(ctx, !(wrong & 2), F2_ERR_INVALID, "a group lies outside [0, %d)", G);
@@ -926,31 +937,30 @@ struct noise_pick_meta {
     }
 };
 
-// The gather that ends a window call with a smear stage (S NULL, sharp or all_sharp: the plain ragged gather and nothing else). carve
+// The gather that ends a window call with a smear stage (sharp or all_sharp: the plain ragged gather and nothing else). carve
 // names the levels of the utterances in the call's f2_meta_carve; reserve sizes ctx->mix for the image unless it is up already
 // (before the call's first launch); launch uploads what is not up and gathers from d_env with the offsets in ctx->offsets, ORing into
 // word 0 of ctx->flags.
 struct mix_gather_meta {
     const f2_mix_gather_args* S = nullptr;
     int64_t* d_mix_of = nullptr;   // B int32 values in 8-byte slots
-    void carve(f2_meta_carve* meta, int B, const f2_mix_gather_args* smear) {
-        if (!smear || smear->sharp() || smear->all_sharp) return;
-        S = smear;
+    void carve(f2_meta_carve* meta, int B, const f2_mix_gather_args& smear) {
+        if (smear.sharp() || smear.all_sharp) return;
+        S = &smear;
         meta->add(&d_mix_of, ((size_t)B + 1) / 2);
     }
-    int reserve(f2_ctx* ctx) const { return S && !S->d_wT ? f2_reserve(ctx, ctx->mix, f2_mix_image_bytes(S->plan)) : F2_OK; }
-    int launch(f2_ctx* ctx, const double* d_env, int B, int C, const int64_t* d_centers, const int* d_win_utt, int64_t n_windows, int radius,
-               int step, int normalize, float* d_windows) const {
+    int reserve(f2_ctx* ctx) const { return S && !S->d_wT ? f2_reserve(ctx, ctx->mix, f2_mix_image_bytes(*S->plan)) : F2_OK; }
+    int launch(f2_ctx* ctx, const double* d_env, int B, int C, const f2_window_list& W, float* d_windows) const {   // (W on the device)
         const int64_t* d_offsets = (const int64_t*)ctx->offsets.ptr;
         if (!S)
-            return f2_launch_gather_ragged(ctx, d_env, C, d_offsets, d_centers, d_win_utt, n_windows, radius, step, normalize, d_windows,
+            return f2_launch_gather_ragged(ctx, d_env, C, d_offsets, W.centers, W.win_utt, W.n_windows, W.radius, W.step, W.normalize, d_windows,
                                            (int*)ctx->flags.ptr);
         const int64_t* d_spans = S->d_spans;
         const double* d_wT = S->d_wT;
-        if (!d_wT) F2_TRY(f2_upload_mix_image(ctx, S->plan, ctx->mix.ptr, &d_spans, &d_wT));
+        if (!d_wT) F2_TRY(f2_upload_mix_image(ctx, *S->plan, ctx->mix.ptr, &d_spans, &d_wT));
         F2_TRY(f2_upload_async(ctx, d_mix_of, S->mix_of, sizeof(int32_t) * (size_t)B));
-        return f2_launch_gather_mixed(ctx, d_env, C, d_offsets, d_centers, d_win_utt, n_windows, radius, step, normalize, S->plan, d_spans, d_wT,
-                                      (const int32_t*)d_mix_of, d_windows, (int*)ctx->flags.ptr);
+        return f2_launch_gather_mixed(ctx, d_env, C, d_offsets, W.centers, W.win_utt, W.n_windows, W.radius, W.step, W.normalize, *S->plan,
+                                      d_spans, d_wT, (const int32_t*)d_mix_of, d_windows, (int*)ctx->flags.ptr);
     }
 };
 
@@ -1009,38 +1019,39 @@ int f2_check_noise_pick(f2_ctx* ctx, int B, const f2_noise_pick_args& N) {
     return F2_OK;
 }
 
-int f2_launch_noisy_windows(f2_ctx* ctx, const void* d_wave, int wave_dtype, const int64_t* offsets, const double* coefs, int B, int C,
-                            int lpf, double cutoff_hz, int fft_precision, const int64_t* centers, const int* win_utt,
-                            bool lists_on_device, int64_t n_windows, int radius, int step, int normalize, const f2_noise_pick_args& N,
-                            float* d_windows, const f2_reverb_pick_args* rooms, const f2_mix_gather_args* smear) {
-    const int64_t total = offsets[B];
-    const bool wet = rooms && !rooms->dry();
+int f2_launch_noisy_windows(f2_ctx* ctx, const f2_batch& X, const f2_window_list& W, const f2_augment_args& A, float* d_windows) {
+    const int B = X.B;
+    const int64_t* offsets = X.offsets;
+    const int64_t total = X.total();
+    const bool wet = !A.rooms.dry();
     mix_gather_meta G;
     // the small arrays and the waveforms first: nothing the envelopes reserve is one of these areas
     noise_pick_meta M;
-    f2_reverb_pick_arrays A;
+    f2_reverb_pick_arrays R;
     f2_meta_carve meta;
-    M.carve(&meta, B, offsets, N);
-    if (wet) f2_reverb_pick_meta(&meta, B, offsets, *rooms, &A);
-    G.carve(&meta, B, smear);
+    M.carve(&meta, B, offsets, A.noise);
+    if (wet) f2_reverb_pick_meta(&meta, B, offsets, A.rooms, &R);
+    G.carve(&meta, B, A.smear);
     F2_TRY(meta.reserve(ctx));
     F2_TRY(G.reserve(ctx));
     F2_TRY(f2_reserve(ctx, ctx->levels, sizeof(double) * (size_t)total));
     if (wet) F2_TRY(f2_reserve(ctx, ctx->wet, sizeof(double) * (size_t)total));
     F2_TRY(f2_upload_offsets(ctx, offsets, B));
+    const void* d_wave = X.wave;
+    int wave_dtype = X.wave_dtype;
     if (wet) {   // f2_reverb_pick into ctx->wet, then f2_noise_pick(F2_WAVE_F64) from there: sigma is the reverberant signal's
-        F2_TRY(f2_launch_reverb_pick(ctx, d_wave, wave_dtype, (const int64_t*)ctx->offsets.ptr, offsets, B, *rooms, A, (double*)ctx->wet.ptr));
+        F2_TRY(f2_launch_reverb_pick(ctx, d_wave, wave_dtype, (const int64_t*)ctx->offsets.ptr, offsets, B, A.rooms, R, (double*)ctx->wet.ptr));
         d_wave = ctx->wet.ptr, wave_dtype = F2_WAVE_F64;
     }
-    F2_TRY(M.launch(ctx, d_wave, wave_dtype, (const int64_t*)ctx->offsets.ptr, offsets, B, total, N, (double*)ctx->levels.ptr));
+    F2_TRY(M.launch(ctx, d_wave, wave_dtype, (const int64_t*)ctx->offsets.ptr, offsets, B, total, A.noise, (double*)ctx->levels.ptr));
     // f2_input_batch from here on, as a device call on the float64 buffer
-    const f2_batch X = {ctx->levels.ptr, F2_WAVE_F64, offsets, coefs, B, C, lpf, cutoff_hz, fft_precision, F2_MEM_DEVICE};
+    f2_batch E = X;
+    E.wave = ctx->levels.ptr, E.wave_dtype = F2_WAVE_F64, E.mem_space = F2_MEM_DEVICE;
     double* d_env;
-    F2_TRY(f2_batch_envelopes(ctx, X, nullptr, nullptr, true, &d_env));
-    const int64_t* d_centers = centers;
-    const int* d_win_utt = win_utt;
-    if (!lists_on_device) F2_TRY(f2_upload_windows(ctx, centers, win_utt, n_windows, &d_centers, &d_win_utt));
-    return G.launch(ctx, d_env, B, C, d_centers, d_win_utt, n_windows, radius, step, normalize, d_windows);
+    F2_TRY(f2_batch_envelopes(ctx, E, nullptr, nullptr, true, &d_env));
+    f2_window_list D = W;
+    if (!W.on_device) F2_TRY(f2_upload_windows(ctx, W.centers, W.win_utt, W.n_windows, &D.centers, &D.win_utt));
+    return G.launch(ctx, d_env, B, X.C, D, d_windows);
 }
 
 extern "C" {
@@ -1053,7 +1064,6 @@ int f2_input_batch(f2_ctx* ctx, const void* wave, int wave_dtype, const int64_t*
     F2_TRY(f2_check_input_batch(ctx, wave, wave_dtype, offsets, coefs, B, C, lpf, cutoff_hz, fft_precision, center_offsets, centers, radius,
                              step, windows, mem_space, nullptr, &n_windows, &win_utt));
     if (n_windows == 0) return F2_OK;
-    const int R = 2 * radius + 1;
 
     // envelopes of the whole batch, by the routes of f2_filterbank_envelope_fused (gfb_or_null = NULL), into a scratch buffer
     const f2_batch X = {wave, wave_dtype, offsets, coefs, B, C, lpf, cutoff_hz, fft_precision, mem_space};
@@ -1064,12 +1074,10 @@ int f2_input_batch(f2_ctx* ctx, const void* wave, int wave_dtype, const int64_t*
     const int64_t* d_centers;
     const int* d_win_utt;
     F2_TRY(f2_upload_windows(ctx, centers, win_utt.data(), n_windows, &d_centers, &d_win_utt));
-    f2_output win;
-    F2_TRY(f2_place(ctx, ctx->xbuf, windows, sizeof(float) * (size_t)n_windows * R * (size_t)C, mem_space, true, &win));
-    F2_TRY(reset_flag(ctx));
-    F2_TRY(f2_launch_gather_ragged(ctx, d_env, C, (const int64_t*)ctx->offsets.ptr, d_centers, d_win_utt, n_windows, radius, step,
-                                   normalize, win.as<float>(), (int*)ctx->flags.ptr));
-    return finish_windows(ctx, win, normalize);
+    return window_tail(ctx, windows, n_windows, radius, C, normalize, mem_space, [&](float* d_windows) {
+        return f2_launch_gather_ragged(ctx, d_env, C, (const int64_t*)ctx->offsets.ptr, d_centers, d_win_utt, n_windows, radius, step, normalize,
+                                       d_windows, (int*)ctx->flags.ptr);
+    });
 }
 
 // f2_noise_pick / f2_shaped_noise_pick: the clean samples go up (host calls), the sigma kernel and k_noise_pick or k_shaped_noise_pick
@@ -1130,20 +1138,16 @@ int f2_gather_windows_mixed(f2_ctx* ctx, const double* env, const int64_t* offse
     if (n_windows == 0) return F2_OK;
     mix_gather_meta G;
     f2_meta_carve meta;
-    G.carve(&meta, B, &S);
+    G.carve(&meta, B, S);
     F2_TRY(meta.reserve(ctx));
     F2_TRY(G.reserve(ctx));
     const void* d_env;
     F2_TRY(f2_stage_input(ctx, env, sizeof(double) * (size_t)C * (size_t)offsets[B], mem_space, &d_env));
     F2_TRY(f2_upload_offsets(ctx, offsets, B));
-    const int64_t* d_centers;
-    const int* d_win_utt;
-    F2_TRY(f2_upload_windows(ctx, centers, win_utt.data(), n_windows, &d_centers, &d_win_utt));
-    f2_output win;
-    F2_TRY(f2_place(ctx, ctx->xbuf, windows, sizeof(float) * (size_t)n_windows * (2 * radius + 1) * (size_t)C, mem_space, true, &win));
-    F2_TRY(reset_flag(ctx));
-    F2_TRY(G.launch(ctx, (const double*)d_env, B, C, d_centers, d_win_utt, n_windows, radius, step, normalize, win.as<float>()));
-    return finish_windows(ctx, win, normalize);
+    f2_window_list W = {nullptr, nullptr, true, n_windows, radius, step, normalize};
+    F2_TRY(f2_upload_windows(ctx, centers, win_utt.data(), n_windows, &W.centers, &W.win_utt));
+    return window_tail(ctx, windows, n_windows, radius, C, normalize, mem_space,
+                       [&](float* d_windows) { return G.launch(ctx, (const double*)d_env, B, C, W, d_windows); });
 }
 
 // The one window path behind a noise stage: f2_input_batch_smeared, and without matrices f2_input_batch_coloured, and with
@@ -1153,26 +1157,19 @@ int f2_input_batch_smeared(f2_ctx* ctx, const void* wave, int wave_dtype, const 
                            int normalize, const double* rir, const int64_t* rir_offsets, int Kr, const int32_t* room_of, const double* snr_db,
                            const double* fir, const int64_t* fir_offsets, int K, const int32_t* level_of, uint32_t first_utterance,
                            uint64_t seed, const double* mix, int Km, const int32_t* mix_of, float* windows, int mem_space) {
-    f2_noise_pick_args N = {snr_db, K, level_of, first_utterance, seed, fir, fir_offsets};
-    const f2_reverb_pick_args R = {rir, rir_offsets, Kr, room_of, nullptr, nullptr};
-    f2_mix_gather_args S;
-    S.mix = mix, S.K = Km, S.mix_of = mix_of;
+    f2_augment_args A = f2_augment_args::of(rir, rir_offsets, Kr, room_of, snr_db, fir, fir_offsets, K, level_of, first_utterance, seed, mix, Km,
+                                            mix_of);
     int64_t n_windows;
     std::vector<int> win_utt;
     F2_TRY(f2_check_input_batch(ctx, wave, wave_dtype, offsets, coefs, B, C, lpf, cutoff_hz, fft_precision, center_offsets, centers, radius,
-                             step, windows, mem_space, &N, &n_windows, &win_utt));
-    F2_TRY(f2_check_noise_colours(ctx, B, &N, false));
-    F2_TRY(f2_check_reverb_pick(ctx, B, R));
-    F2_TRY(f2_check_mix_gather(ctx, B, C, radius, &S));
+                             step, windows, mem_space, &A.noise, &n_windows, &win_utt));
+    F2_TRY(A.check(ctx, B, C, radius));
     if (n_windows == 0) return F2_OK;
-    const void* d_wave;
-    F2_TRY(f2_stage_wave(ctx, wave, wave_dtype, offsets[B], mem_space, &d_wave));
-    f2_output win;
-    F2_TRY(f2_place(ctx, ctx->xbuf, windows, sizeof(float) * (size_t)n_windows * (2 * radius + 1) * (size_t)C, mem_space, true, &win));
-    F2_TRY(reset_flag(ctx));
-    F2_TRY(f2_launch_noisy_windows(ctx, d_wave, wave_dtype, offsets, coefs, B, C, lpf, cutoff_hz, fft_precision, centers, win_utt.data(),
-                                   false, n_windows, radius, step, normalize, N, win.as<float>(), &R, &S));
-    return finish_windows(ctx, win, normalize);
+    f2_batch X = {nullptr, wave_dtype, offsets, coefs, B, C, lpf, cutoff_hz, fft_precision, F2_MEM_DEVICE};
+    F2_TRY(f2_stage_wave(ctx, wave, wave_dtype, offsets[B], mem_space, &X.wave));
+    const f2_window_list W = {centers, win_utt.data(), false, n_windows, radius, step, normalize};
+    return window_tail(ctx, windows, n_windows, radius, C, normalize, mem_space,
+                       [&](float* d_windows) { return f2_launch_noisy_windows(ctx, X, W, A, d_windows); });
 }
 
 int f2_input_batch_coloured(f2_ctx* ctx, const void* wave, int wave_dtype, const int64_t* offsets, const double* coefs, int B, int C, int lpf,

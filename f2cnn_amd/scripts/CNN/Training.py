@@ -381,27 +381,18 @@ def _render_windows(ctx, waves, centers, coefs, cfg, LPF, CUTOFF, precision, snr
         if n == 0:
             continue
         level_of = None if level is None else numpy.full(len(ws), level, numpy.int32)
+        front = (flat, _lib.WAVE_F64 if f64 else _lib.WAVE_I16, offsets, coefs, len(ws), Cn, bool(LPF), float(CUTOFF) if LPF else 0.0,
+                 precision, center_offsets, numpy.concatenate(cs), cfg.radius, cfg.step, True)
+        rooms = (rirs if room is not None else (), None if room is None else numpy.full(len(ws), room, numpy.int32))
+        back = (level_of, g, seed, out[row:row + n], _lib.MEM_HOST)
         if mix is not None:
-            ctx.input_batch_smeared(flat, _lib.WAVE_F64 if f64 else _lib.WAVE_I16, offsets, coefs, len(ws), Cn, bool(LPF),
-                                    float(CUTOFF) if LPF else 0.0, precision, center_offsets, numpy.concatenate(cs), cfg.radius,
-                                    cfg.step, True, rirs if room is not None else (),
-                                    None if room is None else numpy.full(len(ws), room, numpy.int32), snrs, firs, level_of, g, seed,
-                                    mix[None], numpy.zeros(len(ws), numpy.int32), out[row:row + n], _lib.MEM_HOST)
+            ctx.input_batch_smeared(*front, *rooms, snrs, firs, *back[:3], mix[None], numpy.zeros(len(ws), numpy.int32), *back[3:])
         elif firs is not None:
-            ctx.input_batch_coloured(flat, _lib.WAVE_F64 if f64 else _lib.WAVE_I16, offsets, coefs, len(ws), Cn, bool(LPF),
-                                     float(CUTOFF) if LPF else 0.0, precision, center_offsets, numpy.concatenate(cs), cfg.radius,
-                                     cfg.step, True, rirs if room is not None else (),
-                                     None if room is None else numpy.full(len(ws), room, numpy.int32), snrs, firs, level_of, g, seed,
-                                     out[row:row + n], _lib.MEM_HOST)
+            ctx.input_batch_coloured(*front, *rooms, snrs, firs, *back)
         elif room is None:
-            ctx.input_batch_noisy(flat, _lib.WAVE_F64 if f64 else _lib.WAVE_I16, offsets, coefs, len(ws), Cn, bool(LPF),
-                                  float(CUTOFF) if LPF else 0.0, precision, center_offsets, numpy.concatenate(cs), cfg.radius, cfg.step,
-                                  True, snrs, level_of, g, seed, out[row:row + n], _lib.MEM_HOST)
+            ctx.input_batch_noisy(*front, snrs, *back)
         else:
-            ctx.input_batch_wet(flat, _lib.WAVE_F64 if f64 else _lib.WAVE_I16, offsets, coefs, len(ws), Cn, bool(LPF),
-                                float(CUTOFF) if LPF else 0.0, precision, center_offsets, numpy.concatenate(cs), cfg.radius, cfg.step,
-                                True, rirs, numpy.full(len(ws), room, numpy.int32), snrs, level_of, g, seed, out[row:row + n],
-                                _lib.MEM_HOST)
+            ctx.input_batch_wet(*front, *rooms, snrs, *back)
         row += n
     return out
 

@@ -1,8 +1,8 @@
 """f2_input_batch_smeared: the windows of a batch with a room, a coloured-noise level and a spectral resolution per utterance in one
 call, against the four stateless calls it is made of - f2_reverb_pick, f2_shaped_noise_pick(F2_WAVE_F64) on its output,
 f2_filterbank_envelope_fused(F2_WAVE_F64, gfb NULL) on that, f2_gather_windows_mixed on those envelopes - on raw bytes; against
-f2_input_batch_coloured without matrices; and the errors of each stage, which come before any launch. Three utterances of 0.2 to
-0.4 s, 32 channels, windows of 11 x 32."""
+f2_input_batch_coloured without matrices; the whole ladder of entries on one small batch; and the errors of each stage, which come
+before any launch. Three utterances of 0.2 to 0.4 s, 32 channels, windows of 11 x 32."""
 import numpy as np
 import pytest
 
@@ -123,6 +123,39 @@ def test_without_matrices_it_is_input_batch_coloured(ctx, coefs, dt):
     alone = np.full_like(got, np.nan)
     ctx.gather_windows_mixed(env, OFFSETS, B, C, coff, cen, RADIUS, STEP, True, mix, MIX_OF, alone, _lib.MEM_HOST)
     assert bits(got).tobytes() == bits(alone).tobytes()
+
+
+@pytest.mark.parametrize("dt", (_lib.WAVE_I16, _lib.WAVE_F64))
+def test_the_whole_ladder_gives_the_same_bytes(ctx, dt):
+    """A configuration a lower entry can express gives the same bytes through every higher one: f2_input_batch_noisy through _wet,
+    _coloured and _smeared, _wet through _coloured and _smeared, _coloured through _smeared (the other tests compare neighbours
+    only). 8 channels, utterances of 1761, 2500 and 1000 samples - the last without room for a window."""
+    lens, Cs = (1761, 2500, 1000), 8
+    offs = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+    flat = np.concatenate([orc.synth_utterance(90 + i, n) for i, n in enumerate(lens)]).astype(np.int16)
+    flat = flat if dt == _lib.WAVE_I16 else flat.astype(np.float64) * 0.37
+    small = orc.make_erb_filters(16000, orc.centre_freqs(16000, Cs, 100))
+    cs = [np.array([REACH, n // 2, n - 1 - REACH], np.int64) if n > 2 * REACH else np.zeros(0, np.int64) for n in lens]
+    cen, coff = np.concatenate(cs), np.concatenate([[0], np.cumsum([len(c) for c in cs])]).astype(np.int64)
+    entries = ("noisy", "wet", "coloured", "smeared")
+
+    def through(entry, rooms, firs):
+        noise = (LEVEL_OF, FIRST, SEED)
+        stages = {"noisy": (SNR, *noise), "wet": (*rooms, SNR, *noise), "coloured": (*rooms, SNR, firs, *noise),
+                  "smeared": (*rooms, SNR, firs, *noise, None, None)}[entry]
+        out = np.full((int(coff[-1]), R, Cs), np.nan, np.float32)
+        getattr(ctx, "input_batch_" + entry)(flat, dt, offs, small, len(lens), Cs, True, 50.0, _lib.FFT_F32, coff, cen, RADIUS, STEP, True,
+                                             *stages, out, _lib.MEM_HOST)
+        assert len(out) == 6 and np.isfinite(out).all()
+        return out
+    seen = []
+    for lowest, rooms, firs in (("noisy", ((), None), None), ("wet", (RIRS, ROOM_OF), None), ("coloured", (RIRS, ROOM_OF), FIRS)):
+        want = through(lowest, rooms, firs)
+        for higher in entries[entries.index(lowest) + 1:]:
+            assert bits(through(higher, rooms, firs)).tobytes() == bits(want).tobytes(), (lowest, higher)
+        seen.append(want)
+    # ... and the three configurations are three: a room and a colour each change the windows of utterance 0
+    assert not np.array_equal(seen[0][:3], seen[1][:3]) and not np.array_equal(seen[1][:3], seen[2][:3])
 
 
 def test_errors_of_each_stage_come_before_any_launch(ctx, coefs):

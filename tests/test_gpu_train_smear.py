@@ -109,6 +109,47 @@ def test_render_with_matrices_is_input_batch_smeared_group_by_group(ctx, corpus,
     t.close()
 
 
+def test_the_groups_of_a_render_share_nothing_they_change(ctx):
+    """Rooms, coloured noise and matrices at once on a trainer in groups of two over five utterances (radius 5, step 160, windows of
+    11 x 10: the narrowest network with a dense1 input; 1761, 2500, 1000 - no room for a window -, 2100 and 1900 samples): the middle
+    group entirely dry, clean and sharp between two that are not, the last one partial. Rendered twice with the same arguments the
+    bytes are the same, and each group is f2_input_batch_smeared on its utterances with first_utterance = the group's first."""
+    Cs, rad, stp, lens = 10, 5, 160, (1761, 2500, 1000, 2100, 1900)
+    reach, rows = rad * stp, 2 * rad + 1
+    waves = [orc.synth_utterance(70 + i, n).astype(np.int16) for i, n in enumerate(lens)]
+    offsets = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+    cs = [np.array([reach, n // 2, n - 1 - reach], np.int64) if n > 2 * reach else np.zeros(0, np.int64) for n in lens]
+    signs = [(np.arange(len(c)) % 2).astype(np.uint8) for c in cs]
+    coefs = orc.make_erb_filters(16000, orc.centre_freqs(16000, Cs, 100))
+    freqs = orc.centre_freqs(16000, Cs, 100)
+    mix = np.stack([smear.SmearMatrix(freqs, 1.0), smear.BandMatrix(Cs, 3), smear.SmearMatrix(freqs, 3.0)])
+    K, KR = len(SNR), len(RIRS)
+    room, lev, mof = np.array((1, 0, KR, KR, 1), np.int32), np.array((0, 2, K, K, 1), np.int32), np.array((2, 0, KM, KM, 1), np.int32)
+    t = Trainer(F2CNNModel.glorot(7, rows, Cs, zero_bias=False), lr=1e-3, rho=0.9, eps=1e-7, decay=0.5, drop=tr.DROP, seed=5, ctx=ctx)
+    t.set_waves(waves, cs, signs, coefs, rad, stp, lpf=True, cutoff=50.0, group=GROUP)
+    t.render_wet(RIRS, room, SNR, lev, SEED, firs=FIRS, mixes=mix, mix_of=mof)
+    x, y = t.windows()
+    assert np.array_equal(y, np.concatenate(signs)) and len(x) == 12 and np.isfinite(x).all()
+    t.render_wet(RIRS, room, SNR, lev, SEED, firs=FIRS, mixes=mix, mix_of=mof)
+    assert bits(t.windows()[0]).tobytes() == bits(x).tobytes()
+    flat, row = np.concatenate(waves), 0
+    for g in range(0, len(lens), GROUP):
+        e = min(g + GROUP, len(lens))
+        coff = np.concatenate([[0], np.cumsum([len(c) for c in cs[g:e]])]).astype(np.int64)
+        want = np.full((int(coff[-1]), rows, Cs), np.nan, np.float32)
+        ctx.input_batch_smeared(flat[int(offsets[g]):int(offsets[e])], _lib.WAVE_I16, offsets[g:e + 1] - offsets[g], coefs, e - g, Cs, True, 50.0,
+                                _lib.FFT_F32, coff, np.concatenate(cs[g:e]), rad, stp, True, RIRS, room[g:e], SNR, FIRS, lev[g:e], g, SEED, mix,
+                                mof[g:e], want, _lib.MEM_HOST)
+        assert len(want) == 3 * sum(n > 2 * reach for n in lens[g:e])
+        assert bits(x[row:row + len(want)]).tobytes() == bits(want).tobytes(), g
+        row += len(want)
+    assert row == len(x)
+    # the middle group is the plain render's: its windows carry no room, no noise and no mixing
+    t.render()
+    assert bits(t.windows()[0][6:9]).tobytes() == bits(x[6:9]).tobytes() and not np.array_equal(t.windows()[0][:6], x[:6])
+    t.close()
+
+
 def test_without_matrices_it_is_the_render_it_was(ctx, corpus):
     waves, cs, signs = corpus
     mix = matrices()

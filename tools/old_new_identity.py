@@ -2,7 +2,7 @@
     python tools/old_new_identity.py run LIB OUT.json [KEEP_DIR] [--only=GROUP,...]    digests of every case's outputs with that
                                           library; with KEEP_DIR the outputs of the low-pass cases themselves are kept there (float64,
                                           ~1.3 GB); --only: the named groups alone (cnn_cases, entry_cases, sweep_cases, grad_cases,
-                                          figure_cases, stage_cases)
+                                          figure_cases, stage_cases, window_cases)
     python tools/old_new_identity.py compare OLD.json NEW.json [OLD_KEEP_DIR NEW_KEEP_DIR]    the table "case: identical /
                                           differs"; with the kept outputs, for a case that differs, the largest difference
                                           relative to the row maximum (envelopes: per utterance and channel; scores and windows:
@@ -38,7 +38,14 @@ of 0, 1, 1023, 1024, 1025 and 3000 samples, int16 and float64, host and device m
 2, 1025 and 2048 taps (noise filters), sigma given and left out, all-dry / all-clean stages and a batch without samples;
 f2_input_batch_wet and a render_wet of the trainer with one pass of steps behind it; and per call the status and message of a
 fixed list of invalid calls - those of tests/test_gpu_reverb_levels.py, tests/test_gpu_reverb_pick.py, tests/test_gpu_noise_pick.py
-and ERROR_CASES of tests/test_gpu_shaped_noise.py, and calls with two things wrong at once (which one is named)."""
+and ERROR_CASES of tests/test_gpu_shaped_noise.py, and calls with two things wrong at once (which one is named). The window calls with
+augmentation stages (profiles/r42_a_old_new_identity.txt; radius 5, step 160, 8 channels, utterances of 1761, 2500 and 1000 samples,
+int16 and float64, host and device memory): f2_input_batch_noisy / _wet / _coloured / _smeared with every stage active and with
+each stage all-dry / all-clean / all-sharp in turn, f2_gather_windows_mixed; a trainer with group 2 over five utterances (10
+channels) through render, render_wet, render(firs=) and render_wet(mixes=), the rendered windows and one pass of steps behind the
+last; and per call the status and message of the invalid calls of the test_errors_* functions of
+tests/test_gpu_input_batch_wet.py, _coloured.py, _smeared.py and tests/test_gpu_trainer_render.py, and one call per pair of adjacent
+checks with both things wrong at once."""
 import hashlib, json, os, sys
 import numpy as np
 
@@ -540,6 +547,188 @@ def stage_cases(ctx, res):
     print("stage cases done", flush=True)
 
 
+def window_cases(ctx, res):
+    """the window calls with augmentation stages and the trainer's renders (profiles/r42_a_old_new_identity.txt): outputs with every
+    stage active and with each stage idle in turn, the renders of a trainer in groups with one pass of steps behind the last, and
+    the status and message of invalid calls - those of the test_errors_* functions of tests/test_gpu_input_batch_wet.py,
+    test_gpu_input_batch_coloured.py, test_gpu_input_batch_smeared.py and test_gpu_trainer_render.py, and one call per pair of
+    adjacent checks with both things wrong at once"""
+    from f2cnn_amd import _lib
+    from f2cnn_amd.gammatone import filters
+    from f2cnn_amd.model import F2CNNModel
+    from f2cnn_amd.trainer import Trainer
+    import f2cnn_oracle as orc
+    MEMS = (("host", _lib.MEM_HOST), ("device", _lib.MEM_DEVICE))
+    INV = _lib.F2_ERR_INVALID
+    lens, CW, CT = [1761, 2500, 1000], 8, 10       # (1000 samples: no room for a window; an 11 x 8 network has no dense1 input, so
+    B = len(lens)                                  # the trainer renders 10 channels)
+    offs = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+    i16 = np.concatenate([orc.synth_utterance(4200 + i, n) for i, n in enumerate(lens)]).astype(np.int16)
+    coefs = {c: np.ascontiguousarray(filters.make_erb_filters(16000, filters.centre_freqs(16000, c, 100))) for c in (CW, CT)}
+    reach = RADIUS * STEP
+    cs = [np.array([reach, n // 2, n - 1 - reach], np.int64) if n > 2 * reach else np.zeros(0, np.int64) for n in lens]
+    cen, coffs = np.concatenate(cs), np.concatenate([[0], np.cumsum([len(c) for c in cs])]).astype(np.int64)
+    n = int(coffs[-1])
+    rng = np.random.default_rng(42)
+    rirs = [rng.standard_normal(t) * np.exp(-np.arange(t) / (t / 5.0 + 1)) for t in (7, 1025)]
+    firs = [h / np.sqrt(h @ h) for h in (rng.standard_normal(t) for t in (5, 1025))]
+    snr, seed, first = np.array([20.0, 3.0]), 0x1234_5678_9ABC, 7
+    KR, K, KM = len(rirs), len(snr), 3
+
+    def mixes(c):
+        return rng.random((KM, c, c)) * (np.abs(np.subtract.outer(np.arange(c), np.arange(c))) < 3)   # (weights >= 0: the windows are normalised)
+    mix = mixes(CW)
+    room_of, level_of, mix_of = np.array([1, 2, 0], np.int32), np.array([0, 2, 1], np.int32), np.array([1, 3, 0], np.int32)
+    idle = {"all dry": dict(room_of=np.full(B, KR, np.int32)), "all clean": dict(level_of=np.full(B, K, np.int32)),
+            "all sharp": dict(mix_of=np.full(B, KM, np.int32))}
+    entries = {     # the stages an entry has, and its call
+        "noisy": ("all clean",), "wet": ("all dry", "all clean"), "coloured": ("all dry", "all clean"),
+        "smeared": ("all dry", "all clean", "all sharp")}
+
+    def stage_args(entry, room_of=room_of, level_of=level_of, mix_of=mix_of):
+        return {"noisy": (snr, level_of, first, seed), "wet": (rirs, room_of, snr, level_of, first, seed),
+                "coloured": (rirs, room_of, snr, firs, level_of, first, seed),
+                "smeared": (rirs, room_of, snr, firs, level_of, first, seed, mix, mix_of)}[entry]
+
+    def both(name, inp, size, call):
+        for mname, mem in MEMS:
+            o = np.zeros(size, np.float32)
+            if mem == _lib.MEM_HOST:
+                call(mem, inp, o)
+            else:
+                on_device(ctx, [inp, o], lambda di, do: call(mem, di, do))
+            res[f"{name}, {mname} memory"] = digest(o)
+
+    for dname, dt, wave in (("int16", _lib.WAVE_I16, i16), ("float64", _lib.WAVE_F64, i16.astype(np.float64) * 0.37)):
+        for entry, idles in entries.items():
+            for vname in ("every stage active",) + idles:
+                args = stage_args(entry, **idle.get(vname, {}))
+                both(f"f2_input_batch_{entry}: {dname}, {vname}", wave, n * R * CW, lambda mem, w, o: getattr(ctx, "input_batch_" + entry)(
+                    w, dt, offs, coefs[CW], B, CW, True, 50.0, _lib.FFT_F32, coffs, cen, RADIUS, STEP, True, *args, o, mem))
+    env = np.zeros(CW * int(offs[-1]))
+    ctx.filterbank_envelope_fused(i16, _lib.WAVE_I16, offs, coefs[CW], B, CW, True, 50.0, _lib.FFT_F32, env, None, _lib.MEM_HOST)
+    for vname, mof in (("every utterance mixed or sharp by its level", mix_of), ("all sharp", idle["all sharp"]["mix_of"]), ("no levels", None)):
+        for norm in (True, False):
+            both(f"f2_gather_windows_mixed: {vname}, normalize {int(norm)}", env, n * R * CW, lambda mem, e, o: ctx.gather_windows_mixed(
+                e, offs, B, CW, coffs, cen, RADIUS, STEP, norm, mix, mof, o, mem))
+    print("window outputs done", flush=True)
+
+    # a trainer in groups of two over five utterances (the middle group: one utterance without windows), each render and one pass of
+    # steps behind the last
+    lens5 = lens + [2100, 1900]
+    w5 = [orc.synth_utterance(4300 + i, m).astype(np.int16) for i, m in enumerate(lens5)]
+    cs5 = [np.array([reach, m - 1 - reach], np.int64) if m > 2 * reach else np.zeros(0, np.int64) for m in lens5]
+    sg5 = [(np.arange(len(c)) % 2).astype(np.uint8) for c in cs5]
+    room5, lev5, mof5 = np.array([1, 2, 0, 2, 0], np.int32), np.array([0, 2, 1, 2, 1], np.int32), np.array([2, 0, 1, 3, 1], np.int32)
+    mix5 = mixes(CT)
+    tr = Trainer(F2CNNModel.glorot(7, R, CT, zero_bias=False), lr=1e-3, decay=1e-6, drop=(0.25, 0.25, 0.5), seed=5, ctx=ctx)
+    tr.set_waves(w5, cs5, sg5, coefs[CT], RADIUS, STEP, lpf=True, group=2)
+    renders = [("render", lambda: tr.render(snr, lev5, seed)), ("render_wet", lambda: tr.render_wet(rirs, room5, snr, lev5, seed)),
+               ("render(firs=)", lambda: tr.render(snr, lev5, seed, firs=firs)),
+               ("render_wet(mixes=)", lambda: tr.render_wet(rirs, room5, snr, lev5, seed, firs=firs, mixes=mix5, mix_of=mof5))]
+    for rname, render in renders:
+        render()
+        res[f"f2_trainer_{rname}: five utterances in groups of two, the rendered windows"] = digest(*tr.windows())
+    nw = len(tr.windows()[1])
+    loss, hits = tr.steps(np.random.default_rng(5).permutation(nw), 4)
+    res["f2_trainer_steps behind render_wet(mixes=): weights, accumulators, gradient, loss, hits"] = digest(
+        *tr.weights().values(), *tr.accumulators().values(), *tr.gradient().values(), np.float64(loss), np.int64(hits), np.int64(tr.iterations))
+    print("renders done", flush=True)
+
+    # invalid calls: status and message
+    p = lambda a: None if a is None else a.ctypes.data
+    rir, ro = _lib._pack_rirs(rirs)
+    fir, fo = _lib._pack_rirs(firs)
+    out = np.zeros(n * R * CW, np.float32)
+    dec, far = offs.copy(), cen.copy()
+    dec[2], far[0] = dec[1] - 1, 0
+    bad_room, bad_level, bad_mof = room_of.copy(), level_of.copy(), mix_of.copy()
+    bad_room[2], bad_level[1], bad_mof[2] = KR + 1, K + 1, KM + 1
+    nan_rir, nan_fir, nan_mix, nan_snr, fo_long = rir.copy(), fir.copy(), mix.copy(), snr.copy(), fo.copy()
+    nan_rir[5], nan_fir[2], nan_mix[1, 4, 5], nan_snr[1], fo_long[2] = np.nan, np.nan, np.nan, np.nan, fo[1] + 2049
+
+    def invalid(name, call, cases):
+        rows = []
+        for cname, kw in cases:
+            rc = call(**kw)
+            rows.append(f"{cname}: {rc} {ctx.lib.f2_last_error(ctx.handle).decode()}")
+            assert rc != _lib.F2_OK, (name, cname)
+        res[f"{name}: {len(cases)} invalid calls, status and message"] = digest(np.frombuffer("\n".join(rows).encode(), np.uint8))
+
+    def smeared(symbol):
+        """the call of f2_input_batch_<symbol> with the arguments that symbol has"""
+        def call(wave=i16, dt=_lib.WAVE_I16, off=offs, c=CW, cutoff=50.0, centres=cen, rir=rir, ro=ro, kr=KR, room=room_of, s=snr, fir=fir, fo=fo,
+                 k=K, level=level_of, mix=mix, km=KM, mof=mix_of, out=out, mem=_lib.MEM_HOST):
+            rooms, noise = (p(rir), p(ro), kr, p(room)), (k, p(level), first, seed)      # (the order of include/f2cnn_hip.h, written out)
+            stages = {"noisy": (p(s), *noise), "wet": (*rooms, p(s), *noise), "coloured": (*rooms, p(s), p(fir), p(fo), *noise),
+                      "smeared": (*rooms, p(s), p(fir), p(fo), *noise, p(mix), km, p(mof))}[symbol]
+            return getattr(ctx.lib, "f2_input_batch_" + symbol)(
+                ctx.handle, p(wave), dt, p(off), p(coefs[CW]), B, c, 1, cutoff, _lib.FFT_F32, p(coffs), p(centres), RADIUS, STEP, 1,
+                *stages, p(out), mem)
+        return call
+    noise_cases = [("level high", dict(level=bad_level)), ("K<0", dict(k=-1)), ("snr NULL", dict(s=None)), ("snr nan", dict(s=nan_snr)),
+                   ("window outside", dict(centres=far)), ("offsets decreasing", dict(off=dec)), ("wave NULL", dict(wave=None)),
+                   ("windows NULL", dict(out=None)), ("wave_dtype", dict(dt=7)), ("mem_space", dict(mem=9)), ("C=0", dict(c=0)),
+                   ("cutoff", dict(cutoff=9000.0)),
+                   # two things wrong at once, in the order of the checks: which one the call names
+                   ("mem_space and wave_dtype", dict(mem=9, dt=7)), ("wave_dtype and C=0", dict(dt=7, c=0)), ("C=0 and K<0", dict(c=0, k=-1)),
+                   ("level high and offsets decreasing", dict(level=bad_level, off=dec)),
+                   ("offsets decreasing and window outside", dict(off=dec, centres=far))]
+    room_cases = [("room high", dict(room=bad_room)), ("rir NULL", dict(rir=None)), ("Kr<0", dict(kr=-1)), ("rir tap nan", dict(rir=nan_rir)),
+                  ("rir_offsets NULL", dict(ro=None)), ("window outside and room high", dict(centres=far, room=bad_room)),
+                  ("level high and room high", dict(level=bad_level, room=bad_room))]
+    colour_cases = [("fir_offsets NULL", dict(fo=None)), ("fir tap nan", dict(fir=nan_fir)),
+                    ("2049 taps", dict(fir=np.ones(int(fo_long[2])), fo=fo_long)), ("window outside and fir tap nan", dict(centres=far, fir=nan_fir)),
+                    ("fir tap nan and room high", dict(fir=nan_fir, room=bad_room)), ("fir tap nan and rir NULL", dict(fir=nan_fir, rir=None))]
+    mix_cases = [("mix NULL", dict(mix=None)), ("weight nan", dict(mix=nan_mix)), ("mix level high", dict(mof=bad_mof)), ("Km<0", dict(km=-1)),
+                 ("Km=65", dict(mix=np.resize(mix, (65, CW, CW)), km=65)), ("room high and weight nan", dict(room=bad_room, mix=nan_mix)),
+                 ("rir tap nan and Km<0", dict(rir=nan_rir, km=-1)), ("weight nan and mix level high", dict(mix=nan_mix, mof=bad_mof))]
+    invalid("f2_input_batch_noisy", smeared("noisy"), noise_cases)
+    invalid("f2_input_batch_wet", smeared("wet"), noise_cases + room_cases)
+    invalid("f2_input_batch_coloured", smeared("coloured"), noise_cases + room_cases + colour_cases)
+    invalid("f2_input_batch_smeared", smeared("smeared"), noise_cases + room_cases + colour_cases + mix_cases)
+
+    def gather(env=env, off=offs, c=CW, centres=cen, mix=mix, km=KM, mof=mix_of, out=out, mem=_lib.MEM_HOST, nb=B):
+        return ctx.lib.f2_gather_windows_mixed(ctx.handle, p(env), p(off), nb, c, p(coffs), p(centres), RADIUS, STEP, 1, p(mix), km, p(mof),
+                                               p(out), mem)
+    invalid("f2_gather_windows_mixed", gather, [
+        ("mem_space", dict(mem=9)), ("C=0", dict(c=0)), ("B<0", dict(nb=-1)), ("Km<0", dict(km=-1)), ("mix NULL", dict(mix=None)),
+        ("weight nan", dict(mix=nan_mix)), ("mix level high", dict(mof=bad_mof)), ("offsets decreasing", dict(off=dec)),
+        ("window outside", dict(centres=far)), ("env NULL", dict(env=None)), ("windows NULL", dict(out=None)),
+        ("mem_space and C=0", dict(mem=9, c=0)), ("C=0 and Km<0", dict(c=0, km=-1)), ("mix level high and offsets decreasing", dict(mof=bad_mof, off=dec)),
+        ("offsets decreasing and window outside", dict(off=dec, centres=far))])
+
+    bad_room5, bad_lev5, bad_mof5, nan_mix5 = room5.copy(), lev5.copy(), mof5.copy(), mix5.copy()
+    bad_room5[4], bad_lev5[3], bad_mof5[3], nan_mix5[1, 2, 3] = KR + 1, K + 1, KM + 1, np.nan
+
+    bare = Trainer(F2CNNModel.glorot(7, R, CT, zero_bias=False), ctx=ctx)      # (no set_waves)
+
+    def render(symbol):
+        def call(rir=rir, ro=ro, kr=KR, room=room5, s=snr, fir=fir, fo=fo, k=K, level=lev5, mix=mix5, km=KM, mof=mof5, t=tr.handle):
+            rooms, noise = (p(rir), p(ro), kr, p(room)), (k, p(level), seed)
+            stages = {"": (p(s), *noise), "_wet": (*rooms, p(s), *noise), "_coloured": (*rooms, p(s), p(fir), p(fo), *noise),
+                      "_smeared": (*rooms, p(s), p(fir), p(fo), *noise, p(mix), km, p(mof))}[symbol]
+            return getattr(ctx.lib, "f2_trainer_render" + symbol)(ctx.handle, t, *stages)
+        return call
+    r_noise = [("level high", dict(level=bad_lev5)), ("snr nan", dict(s=nan_snr)), ("snr NULL", dict(s=None)), ("K<0", dict(k=-1, level=None)),
+               ("trainer NULL", dict(t=None)), ("trainer NULL and K<0", dict(t=None, k=-1)), ("trainer without waves", dict(t=bare.handle)),
+               ("trainer without waves and K<0", dict(t=bare.handle, k=-1, level=None))]
+    r_room = [("room high", dict(room=bad_room5)), ("rir NULL", dict(rir=None)), ("Kr<0", dict(kr=-1)), ("rir tap nan", dict(rir=nan_rir)),
+              ("level high and room high", dict(level=bad_lev5, room=bad_room5))]
+    r_colour = [("fir_offsets NULL", dict(fo=None)), ("fir tap nan", dict(fir=nan_fir)), ("level high and fir tap nan", dict(level=bad_lev5, fir=nan_fir)),
+                ("fir tap nan and room high", dict(fir=nan_fir, room=bad_room5))]
+    r_mix = [("mix level high", dict(mof=bad_mof5)), ("weight nan", dict(mix=nan_mix5)), ("mix NULL", dict(mix=None)), ("Km<0", dict(km=-1)),
+             ("room high and weight nan", dict(room=bad_room5, mix=nan_mix5)), ("weight nan and mix level high", dict(mix=nan_mix5, mof=bad_mof5))]
+    invalid("f2_trainer_render", render(""), r_noise)
+    invalid("f2_trainer_render_wet", render("_wet"), r_noise + r_room)
+    invalid("f2_trainer_render_coloured", render("_coloured"), r_noise + r_room + r_colour)
+    invalid("f2_trainer_render_smeared", render("_smeared"), r_noise + r_room + r_colour + r_mix)
+    res["f2_trainer_render_*: the windows after the invalid calls"] = digest(*tr.windows())
+    tr.close()
+    bare.close()
+    print("window cases done", flush=True)
+
+
 def keep_arrays(keep, key, arrays, lens=None, C=None, envelopes=()):
     """the outputs of one case under KEEP_DIR: a<i>.npy each; `envelopes` = the indices of the arrays laid out
     [utterance][channel][sample] for utterances of `lens` samples and C channels"""
@@ -622,7 +811,7 @@ def run(lib, out, keep=None, only=None):
             if lpf:
                 keep_arrays(keep, f"f2_input_batch: {tag}", [win])
             print(tag, "done", flush=True)
-    for group in (cnn_cases, entry_cases, sweep_cases, grad_cases, figure_cases, stage_cases):
+    for group in (cnn_cases, entry_cases, sweep_cases, grad_cases, figure_cases, stage_cases, window_cases):
         if not only or group.__name__ in only.split(","):
             group(ctx, res)
     ctx.close()
