@@ -9,7 +9,12 @@
 // of pass-1 outputs k = 0..3, the high lane k = 4..7), and the exchange pass 1 -> pass 2 (16 ds_write_b64 + 16 ds_read_b64
 // per thread, two barriers) is gone. Same arithmetic, same twiddle tables, same result bits as fft_pass<1> + fft_pass<2>.
 // Measured bound (a build that simply skips that exchange, results wrong): -5 % on the kernel.
-template <int NT, int PTV>
+// PAD (f2_fft_lds.h): every address is one base plus compile-time offsets under both policies - the reads step by 1024 points,
+// the stores by 16 k + 128 k2 from a position whose bit 4 is 0 (pos0 = q + 64 hl + 512 plo, q < 16), so neither carries into
+// the pad count. Pad32: each 32-lane group of the reads takes 32 consecutive, 32-aligned points (b = (l & 31) + 32 ...), each
+// 16-lane group of the stores 16 consecutive points inside one aligned 16: no bank conflict; the twiddle reads of a 32-lane
+// group touch two addresses (p = b >> 4), which broadcast.
+template <int NT, int PTV, typename PAD = Pad16>
 __device__ __forceinline__ void fft13_pass12_merged(cpx<float>* lds, const cpx<float>* twl, int tid, cpx<float> (&v)[PTV]) {
     constexpr int LOG2H = 13;
     static_assert(NT == 512 && PTV >= 16 && plan_npass(LOG2H) == 4 && plan_bits(LOG2H, 1) == 3 && plan_bits(LOG2H, 2) == 2 &&
@@ -20,9 +25,9 @@ __device__ __forceinline__ void fft13_pass12_merged(cpx<float>* lds, const cpx<f
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
         const int b = base8 + 256 * (i + 2 * hl);
-        const cpx<float>* src = lds + cpad(b);
+        const cpx<float>* src = lds + PAD::pad(b);
 #pragma unroll
-        for (int j = 0; j < 8; ++j) v[i * 8 + j] = src[j * (1024 + 64)];   // cpad(b + 1024 j)
+        for (int j = 0; j < 8; ++j) v[i * 8 + j] = lds_read<PAD>(src + j * PAD::step(1024));   // pad(b + 1024 j)
     }
     __syncthreads();
 #pragma unroll
@@ -30,7 +35,7 @@ __device__ __forceinline__ void fft13_pass12_merged(cpx<float>* lds, const cpx<f
         dft<8>(&v[i * 8]);                                  // X[k] in v[8 i + brev<8>(k)]
         const cpx<float>* t1 = twl + (((base8 >> 4) + 16 * (i + 2 * hl)));   // p = b >> 4
 #pragma unroll
-        for (int k = 1; k < 8; ++k) v[i * 8 + brev<8>(k)] = cmul(v[i * 8 + brev<8>(k)], t1[(k - 1) * 64]);
+        for (int k = 1; k < 8; ++k) v[i * 8 + brev<8>(k)] = cmul(v[i * 8 + brev<8>(k)], lds_read<PAD>(t1 + (k - 1) * 64));
     }
     // lane pair exchange: A = (i, k), B = (i, k + 4), k < 4. Afterwards, in both lanes, A holds the value of p_hi = i and
     // B that of p_hi = i + 2 for the pass-1 output kk = k + 4 (lane >> 5)
@@ -62,14 +67,17 @@ __device__ __forceinline__ void fft13_pass12_merged(cpx<float>* lds, const cpx<f
     }
     const int q = base8 & 15, plo = base8 >> 4;
     const cpx<float>* t2 = twl + OFF2 + plo;
+    cpx<float> w2[4];                                       // (read once: a single read is not merged with a repeat of itself either)
+#pragma unroll
+    for (int k2 = 1; k2 < 4; ++k2) w2[k2] = lds_read<PAD>(t2 + (k2 - 1) * 16);
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         cpx<float> t[4] = {v[brev<8>(k)], v[8 + brev<8>(k)], v[brev<8>(k + 4)], v[8 + brev<8>(k + 4)]};   // p_hi = 0..3
         dft<4>(t);                                          // X[k2] in t[brev<4>(k2)]
-        const int pos = q + 16 * (k + 4 * hl) + 512 * plo;
-        lds[cpad(pos)] = t[0];
+        cpx<float>* dst = lds + PAD::pad(q + 64 * hl + 512 * plo) + PAD::step(16 * k);   // pos = q + 16 (k + 4 hl) + 512 plo
+        lds_write<PAD>(dst, t[0]);
 #pragma unroll
-        for (int k2 = 1; k2 < 4; ++k2) lds[cpad(pos + 128 * k2)] = cmul(t[brev<4>(k2)], t2[(k2 - 1) * 16]);
+        for (int k2 = 1; k2 < 4; ++k2) lds_write<PAD>(dst + PAD::step(128 * k2), cmul(t[brev<4>(k2)], w2[k2]));
     }
     __syncthreads();
 }
@@ -165,6 +173,20 @@ __device__ __forceinline__ void fft_pass0_pair(const cpx<float>* __restrict__ tw
     }
 }
 
+// Which first-pass butterfly a thread takes. Pad16: its own number. Pad32 (512 threads): dealt by parity inside each half wave,
+//     t = 64 wv + 32 (l >> 5) + 2 (l & 15) + ((l >> 4) & 1),
+// so that the sixteen lanes the LDS serves a ds_write_b64 for together hold t = t0 + 2 i: the pass stores point 16 t + k at slot
+// 16 t + (t >> 1) + k, and t >> 1 then takes sixteen consecutive values - sixteen distinct slots mod 16, the offsets + k stay
+// immediates (with t = consecutive lanes t >> 1 takes eight values: the 2-way conflict of DESIGN.md section 6a). A permutation
+// inside each 32-lane group that keeps thread 0 on butterfly 0 (the Nyquist bin); a wave's table loads cover the same bins.
+// Only the first pass (bins loaded, phase factor, pass-0 twiddles, store base) goes by t; the merged pass and everything
+// behind it go by the thread's own number, so the register layout the transforms leave does not move.
+template <typename PAD>
+__device__ __forceinline__ int pass0_deal(int tid) {
+    if constexpr (PAD::LOG2PER == 5) return (tid & ~31) | ((tid & 15) << 1) | ((tid >> 4) & 1);
+    else return tid;
+}
+
 // the rest of an 8192-point transform whose first pass (fft13_pass0_pair) left its outputs in v: exchange, merged passes
 // 1 + 2, last pass; results in v as fft_regs_to_regs leaves them
 template <int LOG2H, int PTV, int NT, bool T0REGS, int PASS = 1>
@@ -176,15 +198,23 @@ __device__ __forceinline__ void fft_remaining_passes(cpx<float>* lds, const cpx<
         fft_remaining_passes<LOG2H, PTV, NT, T0REGS, PASS + 1>(lds, tw, twl, tid, v);
     }
 }
-template <int LOG2H, int PTV, int NT, bool T0REGS>
-__device__ __forceinline__ void fft_from_pass0(cpx<float>* lds, const cpx<float>* __restrict__ tw, const cpx<float>* twl, int tid,
+// (t0: the first-pass butterfly whose outputs v holds, pass0_deal<PAD>(tid))
+template <int LOG2H, int PTV, int NT, bool T0REGS, typename PAD = Pad16>
+__device__ __forceinline__ void fft_from_pass0(cpx<float>* lds, const cpx<float>* __restrict__ tw, const cpx<float>* twl, int tid, int t0,
                                                cpx<float> (&v)[PTV]) {
+    static_assert(PAD::LOG2PER == 4 || LOG2H == 13, "Pad32: the 16-8-4-16 plan only");
+    if constexpr (PAD::LOG2PER == 4) {
 #pragma unroll
-    for (int k = 0; k < 16; ++k) lds[cpad(tid * 16 + k)] = v[brev<16>(k)];     // pass 0 has stride 1: outputs 16 t + k
+        for (int k = 0; k < 16; ++k) lds[cpad(t0 * 16 + k)] = v[brev<16>(k)];     // pass 0 has stride 1: outputs 16 t + k
+    } else {
+        cpx<float>* dst = lds + PAD::pad(t0 * 16);                                 // pad(16 t + k) = pad(16 t) + k, k < 16
+#pragma unroll
+        for (int k = 0; k < 16; ++k) dst[k] = v[brev<16>(k)];
+    }
     __syncthreads();
     if constexpr (LOG2H == 13) {
-        fft13_pass12_merged<NT, PTV>(lds, twl, tid, v);
-        fft_pass<float, 13, 3, false, true, PTV, NT, false, T0REGS>(lds, tw, twl, tid, v);
+        fft13_pass12_merged<NT, PTV, PAD>(lds, twl, tid, v);
+        fft_pass<float, 13, 3, false, true, PTV, NT, false, T0REGS, 4, PAD>(lds, tw, twl, tid, v);
     } else if constexpr (LOG2H == 14) {
         fft14_pass12_merged<NT, PTV>(lds, twl, tid, v);
         fft_pass<float, 14, 3, false, true, PTV, NT, false, T0REGS>(lds, tw, twl, tid, v);

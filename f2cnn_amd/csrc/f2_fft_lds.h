@@ -86,6 +86,51 @@ constexpr int plan_tw_lds_count(int h, int p13 = 4) { return plan_npass(h, p13) 
 __device__ __forceinline__ int cpad(int i) { return i + (i >> 4); }
 constexpr int cpad_size(int h) { return h + (h >> 4) + 1; }
 
+// Padding as a policy of the transforms (trailing template parameter PAD, default Pad16 = cpad above). LOG2PER: one extra slot
+// per 2^LOG2PER points; pad(i + s) = pad(i) + step(s) wherever the low LOG2PER bits of i and s do not carry into each other.
+// SINGLE_READS: the 8-byte reads of the exchanges (lds_read) and the stores of the merged pass (lds_write) are spelled so that
+// the compiler does not pair them into ds_read2 / ds_write2 forms (a ds_read2_b64 costs the LDS array 8 cycles, two single
+// ds_read_b64 2 + 2).
+struct Pad16 {
+    static constexpr int LOG2PER = 4;
+    static constexpr bool SINGLE_READS = false;
+    static __device__ __forceinline__ int pad(int i) { return cpad(i); }
+    static constexpr int step(int s) { return s + (s >> 4); }
+    static constexpr int size(int h) { return cpad_size(h); }
+};
+// One pad per 32 points: a 32-lane group of ds_read_b64 that reads 32 consecutive, 32-aligned points sees one pad offset and
+// 32 distinct slots (with one pad per 16 every such group crosses a pad: 2-way conflict). The stores of a pass with stride 1
+// are conflict-free under it only with the butterflies dealt by parity (pass0_deal, f2_fft13_merged.h). H = 8192 of KS only.
+struct Pad32 {
+    static constexpr int LOG2PER = 5;
+    static constexpr bool SINGLE_READS = true;
+    static __device__ __forceinline__ int pad(int i) { return i + (i >> 5); }
+    static constexpr int step(int s) { return s + (s >> 5); }
+    static constexpr int size(int h) { return h + (h >> 5) + 1; }
+};
+// an 8-byte LDS read of an exchange under the policy (volatile: not merged with a neighbour; the compiler still places the waits)
+template <typename PAD, typename F>
+__device__ __forceinline__ cpx<F> lds_read(const cpx<F>* p) {
+    if constexpr (PAD::SINGLE_READS && sizeof(cpx<F>) == 8) {
+        // (read as one 64-bit integer in the LDS address space: a volatile access through a generic pointer stays a flat load,
+        // and a float vector would invite packed arithmetic on the pair)
+        const unsigned long long r = *(const volatile __attribute__((address_space(3))) unsigned long long*)p;
+        return __builtin_bit_cast(cpx<F>, r);
+    } else {
+        return *p;
+    }
+}
+// ... and an 8-byte store that stays a ds_write_b64: off one base with immediate offsets the compiler pairs neighbours into
+// ds_write2_b64 (measured on the merged pass's stores of the 1 s rows: 4.438 ms per step paired, 4.420 ms single)
+template <typename PAD, typename F>
+__device__ __forceinline__ void lds_write(cpx<F>* p, cpx<F> x) {
+    if constexpr (PAD::SINGLE_READS && sizeof(cpx<F>) == 8) {
+        *(volatile __attribute__((address_space(3))) unsigned long long*)p = __builtin_bit_cast(unsigned long long, x);
+    } else {
+        *p = x;
+    }
+}
+
 // One Stockham pass. SRC_REGS: inputs are already in v (first pass, loaded from global memory);
 // DST_REGS: outputs stay in v (last pass of the inverse transform). v is indexed [i*R + j] with
 // butterfly bf = tid + i*NT and point bf + j*NB.
@@ -94,7 +139,7 @@ constexpr int cpad_size(int h) { return h + (h >> 4) + 1; }
 //   W[m] = i sin(t_m) Z[m] + cos(t_m) conj(Z[H-m]),  t_m = 2 pi m / M,  W[0] = 0
 // so the spectrum never makes a separate trip through LDS.
 template <typename F, int LOG2H, int PASS, bool SRC_REGS, bool DST_REGS, int PTV, int NT, bool HILBERT = false,
-          bool T0REGS = false, int P13 = 4>
+          bool T0REGS = false, int P13 = 4, typename PAD = Pad16>
 __device__ __forceinline__ void fft_pass(cpx<F>* lds, const cpx<F>* __restrict__ tw, const cpx<F>* twl, int tid,
                                          cpx<F> (&v)[PTV]) {
     constexpr int H = 1 << LOG2H;
@@ -105,6 +150,8 @@ __device__ __forceinline__ void fft_pass(cpx<F>* lds, const cpx<F>* __restrict__
     constexpr int ITER = (NB + NT - 1) / NT;
     constexpr bool LAST = (S * R == H);
     static_assert(ITER * R <= PTV, "register array too small");
+    // (another padding than the default: for the reads of a pass whose outputs stay in registers, H = 8192 of KS)
+    static_assert(PAD::LOG2PER == 4 || (!SRC_REGS && DST_REGS && !HILBERT && NB % (1 << PAD::LOG2PER) == 0), "padding policy");
     constexpr bool FULL = NB % NT == 0;   // every thread owns ITER whole butterflies: no guards
     const cpx<F>* __restrict__ twp = tw + plan_tw_offset(LOG2H, PASS, P13);
     if constexpr (!SRC_REGS) {
@@ -113,7 +160,12 @@ __device__ __forceinline__ void fft_pass(cpx<F>* lds, const cpx<F>* __restrict__
             const int bf = tid + i * NT;
             if (FULL || bf < NB) {
                 // cpad(bf + j*NB) = cpad(bf) + j*(NB + NB/16) when 16 | NB: one base + immediate offsets
-                if constexpr (NB % 16 == 0) {
+                if constexpr (PAD::LOG2PER != 4) {
+                    // pad(bf + j*NB) = pad(bf) + j*step(NB): the policy's points per pad slot divide NB (asserted above)
+                    const cpx<F>* src = lds + PAD::pad(bf);
+#pragma unroll
+                    for (int j = 0; j < R; ++j) v[i * R + j] = lds_read<PAD>(src + j * PAD::step(NB));
+                } else if constexpr (NB % 16 == 0) {
                     const cpx<F>* src = lds + cpad(bf);
 #pragma unroll
                     for (int j = 0; j < R; ++j) v[i * R + j] = src[j * (NB + NB / 16)];

@@ -52,6 +52,7 @@
 #include <cmath>
 #include <complex>
 #include <thread>
+#include <type_traits>
 
 #include "f2_fft_lds.h"
 
@@ -478,7 +479,9 @@ __global__ __launch_bounds__((threads_for<float, LOG2H>()), (min_waves_for<float
     constexpr int NT = threads_for<float, LOG2H>();
     constexpr int H = 1 << LOG2H;
     constexpr int M = 2 * H;
-    constexpr int CS = cpad_size(H);
+    // 8192-point rows: one pad per 32 points, first-pass butterflies dealt by parity, single LDS reads
+    using PAD = std::conditional_t<LOG2H == 13, Pad32, Pad16>;
+    constexpr int CS = PAD::size(H);
     constexpr int R0 = 1 << plan_bits(LOG2H, 0);
     constexpr int NB0 = H / R0;
     static_assert(NB0 % NT == 0, "every thread owns whole butterflies of the first pass");
@@ -495,6 +498,7 @@ __global__ __launch_bounds__((threads_for<float, LOG2H>()), (min_waves_for<float
     cpx<float>* lds = reinterpret_cast<cpx<float>*>(smem);
 
     const int tid = threadIdx.x;
+    const int t0 = pass0_deal<PAD>(tid);   // this thread's first-pass butterfly: its bins are k = t0 + j NB0
     int u, c;
     row_decode<KS_CGROUP>(P, u, c);
     const int row_id = u * P.C + c;
@@ -507,7 +511,7 @@ __global__ __launch_bounds__((threads_for<float, LOG2H>()), (min_waves_for<float
     if (tid < 4) guard[tid] = 0u;
 
     // 1. spectrum of the front-padded row at this thread's bins k = tid + j NB0 (first-pass register layout). Per bin two
-    //    loads (utterance spectrum, channel table); the phase factor follows from one load: w_k = w_tid e^{-2 pi i j / 32}
+    //    loads (utterance spectrum, channel table); the phase factor follows from one load: w_k = w_t0 e^{-2 pi i j / 32}
     //    (compile-time constants). No load of this phase needs the row's length (the end of the scalar chain ulist -> offsets).
     //    The bins go in groups of GB with the next group's loads in flight - all 32 loads at once would need 96 registers.
     static_assert(ITER0 == 1 && R0 == 16, "one radix-16 butterfly per thread in the first pass");
@@ -516,7 +520,7 @@ __global__ __launch_bounds__((threads_for<float, LOG2H>()), (min_waves_for<float
     // rows whose first pass is one radix-16 butterfly per thread (all three length classes served): the two transforms share it
     static_assert(NB0 == NT && plan_npass(LOG2H) >= 3, "fft_pass0_pair + fft_from_pass0");
     cpx<float> vo[PT];   // conj(A_o) / M = conj(A) w_k / M, formed while the bin's phase factor is at hand
-    cpx<float> w0 = E[tid];
+    cpx<float> w0 = E[t0];
     // Every vector load a row starts with is issued before the first wait for one. The twiddles of the later passes go to LDS:
     // each thread loads its entries here, without a branch (threads beyond the table take its last entry), and writes them
     // below, behind the issue of the table loads - `twl` is first read after the first barrier of the transforms.
@@ -550,7 +554,7 @@ __global__ __launch_bounds__((threads_for<float, LOG2H>()), (min_waves_for<float
     // It is an unsigned BYTE offset (8 bytes per bin of X; HU, 16 bytes per bin, takes twice that, formed where a group's loads
     // are issued: one register carried from group to group). The row of X and the channel's table are scalar buffer descriptors
     // (their 64-bit bases stay in scalar arithmetic), the bin's distance a scalar offset: no vector instruction forms an address.
-    unsigned kb8 = (unsigned)tid * (unsigned)sizeof(cpx<float>);
+    unsigned kb8 = (unsigned)t0 * (unsigned)sizeof(cpx<float>);
     asm volatile("" : "+v"(kb8));
     const __amdgpu_buffer_rsrc_t Xb = table_buffer(Xu, (H + 1) * (int)sizeof(cpx<float>)), HUb = table_buffer(HUc, (H + 1) * (int)sizeof(f2_f4));
     // Issued in the order the bins are consumed in - the first and the last bin of the group come first, the laundering below
@@ -644,15 +648,16 @@ __global__ __launch_bounds__((threads_for<float, LOG2H>()), (min_waves_for<float
         F2_STAMP(st, 4);
         int tid_e = tid;
         asm volatile("" : "+v"(tid_e), "+v"(v[0].re), "+v"(vo[PT - 1].im));
-        fft_pass0_pair<LOG2H, NT, PT>(tw, tid_e, v, vo);
-        fft_from_pass0<LOG2H, PT, NT, T0R>(lds, tw, twl, tid_e, v);
+        const int t0_e = pass0_deal<PAD>(tid_e);   // (formed again from the laundered thread number: not held over the bin loop)
+        fft_pass0_pair<LOG2H, NT, PT>(tw, t0_e, v, vo);
+        fft_from_pass0<LOG2H, PT, NT, T0R, PAD>(lds, tw, twl, tid_e, t0_e, v);
         gout = pad_residual<R0, NT, PADFIRST>(v, np, tid, 0, gout);
 #pragma unroll
         for (int j = 0; j < R0; ++j) {
             const cpx<float> a = v[brev<R0>(j)];
             er[j] = fsqrt(a.re * a.re + a.im * a.im);
         }
-        fft_from_pass0<LOG2H, PT, NT, T0R>(lds, tw, twl, tid_e, vo);
+        fft_from_pass0<LOG2H, PT, NT, T0R, PAD>(lds, tw, twl, tid_e, t0_e, vo);
         F2_STAMP(st, 5);
         gout = pad_residual<R0, NT, PADFIRST>(vo, np, tid, 1, gout);
 #pragma unroll
@@ -819,8 +824,8 @@ __global__ __launch_bounds__(1024, 4) void k_spectral_envelope_long(
 #pragma unroll
         for (int half = 0; half < 2; ++half) {
             // conj a[4 m + r], m = tid + j NT in (half ? vo : v)[brev(j)], r = p + 2 half
-            if (half == 0) fft_from_pass0<LOG2Q, PT, NT, T0R>(lds, tw, twl, tid_e, v);
-            else fft_from_pass0<LOG2Q, PT, NT, T0R>(lds, tw, twl, tid_e, vo);
+            if (half == 0) fft_from_pass0<LOG2Q, PT, NT, T0R>(lds, tw, twl, tid_e, tid_e, v);
+            else fft_from_pass0<LOG2Q, PT, NT, T0R>(lds, tw, twl, tid_e, tid_e, vo);
             const int r = p + 2 * half;
             const __amdgpu_buffer_rsrc_t yb = row_buffer_uniform(y, n);
             // (one lane offset per bank; the block j adds a compile-time 4096 bytes)
