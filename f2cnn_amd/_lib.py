@@ -29,6 +29,9 @@ SMEAR_TILE_SAMPLES, SMEAR_TILE_CHANNELS, SMEAR_MAX_CHANNELS, SMEAR_MAX_LEVELS = 
 # tile constant of k_shaped_noise_levels (csrc/f2_internal.h: F2_SHAPED_BLOCK outputs per workgroup) and the longest filter and the most
 # levels f2_shaped_noise_levels takes (F2_SHAPED_MAX_TAPS, F2_SHAPED_MAX_LEVELS)
 SHAPED_BLOCK, SHAPED_MAX_TAPS, SHAPED_MAX_LEVELS = 1024, 2048, 64
+# the decoding kernels of f2_decision_path (include/f2cnn_hip.h): F2_PATH_TILE rows per workgroup, F2_PATH_SCAN_CHUNK tile products per
+# step of the per-utterance scans; the largest logit_scale and penalty the call takes
+PATH_TILE, PATH_SCAN_CHUNK, PATH_MAX_SCALE, PATH_MAX_PENALTY = 1024, 256, float(1 << 20), 1 << 40
 
 _vp, _i, _i64, _d = C.c_void_p, C.c_int, C.c_int64, C.c_double
 _P = C.POINTER
@@ -128,6 +131,11 @@ SIGNATURES = {
     "f2_input_batch_smeared": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i, _i, _d, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp,
                                     _i, _vp, C.c_uint32, C.c_uint64, _vp, _i, _vp, _vp, _i]),
     "f2_trainer_render_smeared": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, C.c_uint64, _vp, _i, _vp]),
+    "f2_decision_path": (_i, [_vp, _vp, _vp, _i, _d, _i64, _vp, _vp, _vp, _i]),
+    "f2_decision_runs": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _i64, _i]),
+    "f2_interval_tally": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i64, _i, _vp, _i]),
+    "f2_eval_segments_batch": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _d, _i, _i, _i, _i, _d, _i64, _vp, _vp, _i, _vp, _vp, _vp,
+                                    _vp, _vp, _vp, _vp, _vp, _vp, _i]),
 }
 TRAINER_WHAT = {"weights": 0, "accumulators": 1, "gradient": 2}   # F2_TRAINER_* of f2_trainer_get
 
@@ -199,6 +207,12 @@ def _ptr(a):
     if isinstance(a, np.ndarray):
         return a.ctypes.data
     return a  # int device pointer
+
+
+def _want_array(a, dtype, size, name):
+    """A numpy output (device pointers and None pass): contiguous, of this dtype, with room for `size` elements."""
+    if isinstance(a, np.ndarray) and (a.dtype != dtype or a.size < size or not a.flags["C_CONTIGUOUS"]):
+        raise ValueError(f"{name} must be contiguous {np.dtype(dtype).name} with room for {size} elements")
 
 
 class _PinnedOwner:
@@ -671,6 +685,86 @@ class Context:
                                               _ptr(counts), mem_space))
         return counts.reshape(U, 2, 2)
 
+
+    def decision_path(self, scores, window_offsets, logit_scale, penalty, path, mem_space, emissions=None, value=None):
+        """The smoothed decision per row (see f2_decision_path): the most probable two-state sequence of every utterance under a
+        switching penalty, on the integer emissions q = rint(logit_scale * log-odds). scores (n, 2) float32, path (n) uint8 and
+        emissions (n) int32 or None: numpy arrays or device pointers, by mem_space. Returns value (U,) int64, the optimum of every
+        utterance (written into `value` when given)."""
+        window_offsets = np.ascontiguousarray(window_offsets, dtype=np.int64)
+        U = len(window_offsets) - 1
+        if isinstance(scores, np.ndarray):
+            scores = np.ascontiguousarray(scores, dtype=np.float32)
+        _want_array(path, np.uint8, int(window_offsets[-1]), "path")
+        _want_array(emissions, np.int32, int(window_offsets[-1]), "emissions")
+        if value is None:
+            value = np.zeros(U, np.int64)
+        _want_array(value, np.int64, U, "value")
+        self.check(self.lib.f2_decision_path(self.handle, _ptr(scores), _ptr(window_offsets), U, float(logit_scale), int(penalty),
+                                             _ptr(path), _ptr(emissions), _ptr(value), mem_space))
+        return value
+
+    def decision_runs(self, labels, emissions, window_offsets, runs, capacity, mem_space, run_offsets=None):
+        """Maximal runs of equal decisions (see f2_decision_runs). labels (n) uint8 - a path or raw labels - and emissions (n)
+        int32 or None: numpy arrays or device pointers, by mem_space; runs (capacity, 4) int64 likewise, or None to count only:
+        {first row within the utterance, rows, label, sum of the emissions}. Returns run_offsets (U + 1,) int64."""
+        window_offsets = np.ascontiguousarray(window_offsets, dtype=np.int64)
+        U = len(window_offsets) - 1
+        if isinstance(labels, np.ndarray):
+            labels = np.ascontiguousarray(labels, dtype=np.uint8)
+        if isinstance(emissions, np.ndarray):
+            emissions = np.ascontiguousarray(emissions, dtype=np.int32)
+        _want_array(runs, np.int64, 4 * max(int(capacity), 0), "runs")
+        if run_offsets is None:
+            run_offsets = np.zeros(U + 1, np.int64)
+        _want_array(run_offsets, np.int64, U + 1, "run_offsets")
+        self.check(self.lib.f2_decision_runs(self.handle, _ptr(labels), _ptr(emissions), _ptr(window_offsets), U, _ptr(run_offsets),
+                                             _ptr(runs), int(capacity), mem_space))
+        return run_offsets
+
+    def interval_tally(self, labels, path, emissions, window_offsets, iv_offsets, iv_bounds, origin, hop, tally, mem_space):
+        """Decisions per labelled interval (see f2_interval_tally): utterance u is tallied against interval set u % R, sample
+        intervals [a, b) between iv_offsets[r] and iv_offsets[r + 1] of iv_bounds (total, 2). labels / path (uint8, path may be
+        None) / emissions (int32 or None) / tally ((U / R) * total, 4) int64 - {rows, rising labels, rising path, sum of the
+        emissions} -: numpy arrays or device pointers, by mem_space. Returns `tally`."""
+        window_offsets = np.ascontiguousarray(window_offsets, dtype=np.int64)
+        iv_offsets = np.ascontiguousarray(iv_offsets, dtype=np.int64)
+        iv_bounds = np.ascontiguousarray(iv_bounds, dtype=np.int64)
+        U, R = len(window_offsets) - 1, len(iv_offsets) - 1
+        if isinstance(labels, np.ndarray):
+            labels = np.ascontiguousarray(labels, dtype=np.uint8)
+        if isinstance(path, np.ndarray):
+            path = np.ascontiguousarray(path, dtype=np.uint8)
+        if isinstance(emissions, np.ndarray):
+            emissions = np.ascontiguousarray(emissions, dtype=np.int32)
+        if R >= 1 and U % R == 0:
+            _want_array(tally, np.int64, 4 * (U // R) * int(iv_offsets[-1]), "tally")
+        self.check(self.lib.f2_interval_tally(self.handle, _ptr(labels), _ptr(path), _ptr(emissions), _ptr(window_offsets), U,
+                                              _ptr(iv_offsets), _ptr(iv_bounds), R, int(origin), int(hop), _ptr(tally), mem_space))
+        return tally
+
+    def eval_segments_batch(self, handle, wave, wave_dtype, offsets, coefs, B, Cn, lpf, cutoff, precision, radius, step, hop,
+                            logit_scale, penalty, iv_offsets, iv_bounds, scores, labels, path, emissions, runs, tally, mem_space,
+                            want_value=True, want_runs=True):
+        """f2_eval_batch_strided, then the path, its runs and the interval tally on the device's scores (see
+        f2_eval_segments_batch). iv_offsets / iv_bounds: the interval sets or None (no tally). scores / labels / path / emissions /
+        runs ((rows, 4) int64, room for every row) / tally: numpy arrays or device pointers, by mem_space, each may be None.
+        Returns (window_offsets (B + 1), value (B) or None, run_offsets (B + 1) or None)."""
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        R = 0
+        if iv_offsets is not None:
+            iv_offsets = np.ascontiguousarray(iv_offsets, dtype=np.int64)
+            iv_bounds = np.ascontiguousarray(iv_bounds, dtype=np.int64)
+            R = len(iv_offsets) - 1
+        window_offsets = np.zeros(max(int(B), 0) + 1, np.int64)
+        value = np.zeros(max(int(B), 0), np.int64) if want_value else None
+        run_offsets = np.zeros(max(int(B), 0) + 1, np.int64) if want_runs else None
+        self.check(self.lib.f2_eval_segments_batch(self.handle, handle, _ptr(wave), wave_dtype, _ptr(offsets), _ptr(coefs), int(B), Cn,
+                                                   int(bool(lpf)), float(cutoff), precision, radius, step, int(hop), float(logit_scale),
+                                                   int(penalty), _ptr(iv_offsets), _ptr(iv_bounds), R, _ptr(scores), _ptr(labels),
+                                                   _ptr(window_offsets), _ptr(path), _ptr(emissions), _ptr(value), _ptr(run_offsets),
+                                                   _ptr(runs), _ptr(tally), mem_space))
+        return window_offsets, value, run_offsets
 
     def cnn_score_windows(self, handle, windows, n, normalize, signs, groups, n_groups, scores, labels, mem_space, counts=None,
                           loss_sum=None):

@@ -110,6 +110,12 @@ package implements:
      reversed), graphs/Saliency/<basename>.png with the G x map under the gammatonegram, --figure-width columns wide, and
      saliency_map, saliency_summary, saliency_span in the .npz; scores and labels stay those without the flag; one map per run,
      so not together with --occlusion, and not on the sweeps; not in the reference)
+    (eval / evalnoise / evalrand also take --segments [--dwell MS] [--segments-weight auto|X]: the decisions smoothed into
+     transitions - the most probable rising / falling sequence of a two-state chain whose states last MS on average (default
+     three label frames, 30 ms at 16 kHz: a default, not a tuned value), decoded on the device in the same pass; one table line
+     per run (start, end, duration, decision, mean log-odds, the phonemes it overlaps), with the file's .PHN a second table per
+     phoneme (rows, % rising raw and smoothed, mean log-odds), and segments_* keys in the .npz; with --accuracy a second accuracy
+     line for the smoothed decisions; scores and labels stay those without the flag; not on the sweeps; not in the reference)
     python -m f2cnn_amd plot gtg [--file/-f WAV | --all] [--width W] [--pool mean|max] [--cutoff HZ] [--formant N] [--start S --end E] [--out PNG]
                                                             (gammatonegram pictures, pooled to W columns and log-normalised on the
                                                              device, written as graphs/gtg/<basename>.png without matplotlib; the
@@ -402,6 +408,14 @@ def build_parser():
                    help="eval / evalnoise / evalrand: the saliency map - the gradient of P(rising) at every cell of every window, one "
                         "backward pass on the device; a table per band of channels, saliency_* keys in the .npz and "
                         "graphs/Saliency/<basename>.png, --figure-width columns wide; not together with --occlusion")
+    c.add_argument('--segments', action='store_true', default=argparse.SUPPRESS, dest='segments',
+                   help="eval / evalnoise / evalrand: the decisions smoothed into transitions by a two-state decoder on the device; a "
+                        "table of runs, with the file's .PHN a table per phoneme, and segments_* keys in the .npz")
+    c.add_argument('--dwell', type=float, default=argparse.SUPPRESS, dest='dwell', metavar='MS',
+                   help="--segments: the expected time in a state, in ms (default three label frames, 30 ms at 16 kHz; a default, not a "
+                        "tuned value)")
+    c.add_argument('--segments-weight', type=segments_weight, default=argparse.SUPPRESS, dest='segments_weight', metavar='auto|X',
+                   help="--segments: the weight of a row's log-odds (default auto: min(1, hop / STEP), a heuristic for overlapping rows)")
     c.add_argument('--saliency-bands', type=int, default=argparse.SUPPRESS, dest='saliency_bands', metavar='N',
                    help="--saliency: channels per line of the table (default 8)")
     g = sub.add_parser('plot', help='plotting commands')
@@ -563,10 +577,26 @@ def augment_smear_refusal(args):
     return None
 
 
+def segments_weight(text):
+    """--segments-weight: 'auto' or a number in (0, 16]"""
+    if text == 'auto':
+        return text
+    try:
+        value = float(text)
+    except ValueError:
+        value = 0.0
+    if not 0.0 < value <= 16.0:
+        raise argparse.ArgumentTypeError("--segments-weight takes 'auto' or a number in (0, 16], not {!r}".format(text))
+    return value
+
+
+NO_SWEEP_SEGMENTS = "the sweeps print no transitions; the decoding entry points take their batches as they are"
+
+
 def sweep_refusal(args, no_lpf, instead):
     """says which option the sweep does not take, if one was given (an option that was not given is absent, None or False)"""
     for attr, option, why in (('CUTOFF', '--lpf', no_lpf), ('figure', '--figure', instead), ('occlusion', '--occlusion', instead),
-                              ('saliency', '--saliency', instead)):
+                              ('saliency', '--saliency', instead), ('segments', '--segments', NO_SWEEP_SEGMENTS)):
         if why and getattr(args, attr, None) not in (None, False):
             print("{} is not supported by {} ({})".format(option, args.cnn_command, why.format(option)))
             return True
@@ -698,6 +728,17 @@ def main(argv=None):
                 kwargs['figure_width'] = args.figure_width
         elif 'saliency_bands' in args:
             print("--saliency-bands belongs to --saliency")
+            return 1
+        if 'segments' in args:
+            if sweep:
+                print("--segments is not supported by {} ({})".format(args.cnn_command, NO_SWEEP_SEGMENTS))
+                return 1
+            if getattr(args, 'dwell', 1.0) <= 0.0:
+                print("--dwell must be a positive time in ms")
+                return 1
+            kwargs['segments'] = dict(dwell_ms=getattr(args, 'dwell', None), weight=getattr(args, 'segments_weight', 'auto'))
+        elif 'dwell' in args or 'segments_weight' in args:
+            print("--dwell and --segments-weight belong to --segments")
             return 1
         if args.cnn_command == 'evalrand':                     # needs no --file (unreachable in the reference CLI)
             if args.count is not None:

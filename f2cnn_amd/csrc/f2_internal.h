@@ -82,6 +82,9 @@ struct f2_ctx {
     //    nested call reserves it;
     //  - every reader and every upload goes through ctx->stream, so the next call's reuse is ordered behind them.
     f2_scratch meta;
+    // f2_decision_path, f2_decision_runs, f2_interval_tally, f2_eval_segments_batch: every device array of the call in flight that is
+    // not the caller's (f2_seg_plan, f2_segments.hip), reserved once per call before its first launch
+    f2_scratch seg_ws;
     f2_scratch rs_tab;     // f2_resample_batch: the polyphase table of the last (up, down, half_len, taps)
     int64_t rs_up = 0, rs_down = 0, rs_half_len = -1;
     std::vector<double> rs_taps_host;   // the taps rs_tab was built from (skip the rebuild and the upload when equal)
@@ -827,6 +830,49 @@ int f2_finish_positive(f2_ctx* ctx);
 int f2_launch_label_accuracy(f2_ctx* ctx, const uint8_t* d_labels, const int64_t* d_window_offsets, int U, const int64_t* d_ref_offsets,
                              const int64_t* d_ref_timepoints, const uint8_t* d_ref_signs, int R, int64_t origin, int hop, int step,
                              int64_t max_rows, int64_t* d_counts);
+// f2_segments.hip, the kernels of f2_decision_path / f2_decision_runs / f2_interval_tally / f2_eval_segments_batch. The plan of a
+// call: set() takes the rows (host window_offsets, which must outlive the plan) and builds the tile table of F2_PATH_TILE rows;
+// name_arrays() names the device arrays of the stages the call runs, name_bytes() whatever else the call keeps on the device (staged
+// inputs, a host caller's outputs), reserve() places all of them in ctx->seg_ws, upload_tables() sends d_wo and d_first up.
+struct f2_seg_plan {
+    int U = 0;
+    const int64_t* wo = nullptr;
+    int64_t n_rows = 0, tiles = 0, max_rows = 0;
+    std::vector<int64_t> first;   // U + 1 running sums of the utterances' tiles
+    struct slot_at {
+        void* slot;   // the T* to set
+        size_t at;
+    };
+    std::vector<slot_at> slots;
+    size_t bytes = 0;
+    int64_t *d_wo = nullptr, *d_first = nullptr;
+    int64_t *d_tprod = nullptr, *d_vin = nullptr, *d_value = nullptr;          // tile products (4 each), entering vectors (2 each), optima (U)
+    uint8_t *d_tmap = nullptr, *d_xin = nullptr, *d_xlast = nullptr;           // tile maps, state of each tile's last row, of each utterance's
+    int64_t *d_tcount = nullptr, *d_tqsum = nullptr, *d_ro = nullptr;          // tiles + 1 prefix sums of flags and of q, U + 1 run offsets
+    int64_t *d_rstart = nullptr, *d_rsum = nullptr;                            // per run: first row in the batch, sum of q before it
+    int64_t *d_ivo = nullptr, *d_ivb = nullptr;                                // R + 1 interval offsets, the bounds
+    void set(const int64_t* window_offsets, int U);
+    void name_arrays(bool want_path, bool want_runs, int64_t intervals, int R);
+    void name_bytes(char** slot, size_t bytes);
+    int reserve(f2_ctx* ctx);
+    int upload_tables(f2_ctx* ctx) const;
+};
+// the argument errors of the three stages that do not depend on pointers: scale and penalty; the row count; the interval sets
+// (*out_rows: the rows of the tally, (U / R) * iv_offsets[R])
+int f2_check_decision_path(f2_ctx* ctx, double logit_scale, int64_t penalty);
+int f2_check_segment_rows(f2_ctx* ctx, int64_t n_rows);
+int f2_check_intervals(f2_ctx* ctx, int U, const int64_t* iv_offsets, const int64_t* iv_bounds, int R, int64_t origin, int hop,
+                       int64_t max_rows, int64_t* out_rows);
+// The launches, device pointers only, behind reserve() and upload_tables(). Path: d_q (n_rows) and S.d_value are written too.
+// Runs: count fills S.d_ro; scatter writes at most most_runs rows of d_runs (the caller knows S.d_ro[U] <= most_runs). Tally: uploads
+// the interval sets (host) and writes out_rows x 4.
+int f2_launch_decision_path(f2_ctx* ctx, const f2_seg_plan& S, const float* d_scores, double logit_scale, int64_t penalty, uint8_t* d_path,
+                            int32_t* d_q);
+int f2_launch_runs_count(f2_ctx* ctx, const f2_seg_plan& S, const uint8_t* d_labels, const int32_t* d_q);
+int f2_launch_runs_scatter(f2_ctx* ctx, const f2_seg_plan& S, const uint8_t* d_labels, const int32_t* d_q, int64_t most_runs, int64_t* d_runs);
+int f2_launch_interval_tally(f2_ctx* ctx, const f2_seg_plan& S, const uint8_t* d_labels, const uint8_t* d_path, const int32_t* d_q,
+                             const int64_t* iv_offsets, const int64_t* iv_bounds, int R, int64_t origin, int hop, int64_t out_rows,
+                             int64_t* d_tally);
 // f2_score.hip, the kernels of f2_cnn_score_windows. k_normalize_windows: n windows of `total` contiguous float32 values each,
 // normalised with K3's arithmetic into d_out (may not alias d_in); a window with a value <= 0 or a NaN becomes zeros and ORs 1
 // into *d_flag.

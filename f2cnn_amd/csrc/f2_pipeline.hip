@@ -499,6 +499,104 @@ int f2_eval_batch_strided(f2_ctx* ctx, const f2_cnn* cnn, const void* wave, int 
     return eval_cnn_end(ctx, cnn, &E);
 }
 
+// f2_eval_segments_batch: the strided call with its scores and labels kept on the device, then the launches of f2_decision_path,
+// f2_decision_runs and f2_interval_tally (f2_segments.hip) on them. One block of ctx->seg_ws for everything the stages keep, placed
+// before the first launch; the small results (value, run_offsets) come down in front of the wait of eval_cnn_end.
+int f2_eval_segments_batch(f2_ctx* ctx, const f2_cnn* cnn, const void* wave, int wave_dtype, const int64_t* offsets, const double* coefs,
+                           int B, int C, int lpf, double cutoff_hz, int fft_precision, int radius, int step, int hop, double logit_scale,
+                           int64_t penalty, const int64_t* iv_offsets_or_null, const int64_t* iv_bounds, int R, float* scores_or_null,
+                           uint8_t* labels_or_null, int64_t* window_offsets_or_null, uint8_t* path_or_null, int32_t* emissions_or_null,
+                           int64_t* value_or_null, int64_t* run_offsets_or_null, int64_t* runs_or_null, int64_t* tally_or_null,
+                           int mem_space) {
+    const f2_batch X = {wave, wave_dtype, offsets, coefs, B, C, lpf, cutoff_hz, fft_precision, mem_space};
+    eval_call E;
+    F2_TRY(eval_check(ctx, cnn, X, radius, step, &E));
+    F2_CHECK(ctx, hop >= 1, F2_ERR_INVALID, "hop must be at least 1 sample (got %d)", hop);
+    F2_CHECK(ctx, X.wave || X.total() == 0, F2_ERR_INVALID, "null wave");
+    std::vector<int64_t> nbh((size_t)B), wo((size_t)B + 1, 0);
+    for (int b = 0; b < B; ++b) {
+        nbh[(size_t)b] = strided_windows(offsets[b + 1] - offsets[b], E.R, step, hop);
+        wo[(size_t)b + 1] = wo[(size_t)b] + nbh[(size_t)b];
+    }
+    const int64_t n_total = wo[(size_t)B];
+    f2_seg_plan S;
+    S.set(wo.data(), B);
+    const bool want_runs = run_offsets_or_null || runs_or_null, want_tally = tally_or_null != nullptr;
+    const bool want_path = path_or_null || emissions_or_null || value_or_null || want_runs || want_tally;
+    int64_t tally_rows = 0;
+    F2_TRY(f2_check_decision_path(ctx, logit_scale, penalty));
+    F2_TRY(f2_check_segment_rows(ctx, n_total));
+    F2_CHECK(ctx, !want_tally || iv_offsets_or_null, F2_ERR_INVALID, "a tally needs iv_offsets");
+    if (want_tally) F2_TRY(f2_check_intervals(ctx, B, iv_offsets_or_null, iv_bounds, R, (int64_t)radius * step, hop, S.max_rows, &tally_rows));
+    if (window_offsets_or_null) memcpy(window_offsets_or_null, wo.data(), sizeof(int64_t) * wo.size());
+    if (X.total() == 0 || n_total == 0) {
+        if (value_or_null) std::fill(value_or_null, value_or_null + B, (int64_t)0);
+        if (run_offsets_or_null) std::fill(run_offsets_or_null, run_offsets_or_null + B + 1, (int64_t)0);
+    }
+    if (X.total() == 0) return F2_OK;
+
+    const bool host = mem_space != F2_MEM_DEVICE;
+    const size_t n = (size_t)n_total, tally_bytes = sizeof(int64_t) * 4 * (size_t)tally_rows;
+    char *s_path = nullptr, *s_q = nullptr, *s_runs = nullptr, *s_tally = nullptr;
+    if (n_total > 0 && want_path) {
+        S.name_arrays(true, want_runs, want_tally ? iv_offsets_or_null[R] : 0, want_tally ? R : 0);
+        if (host || !path_or_null) S.name_bytes(&s_path, n);
+        if (host || !emissions_or_null) S.name_bytes(&s_q, sizeof(int32_t) * n);
+        if (runs_or_null && host) S.name_bytes(&s_runs, sizeof(int64_t) * 4 * n);
+        if (want_tally && host) S.name_bytes(&s_tally, tally_bytes);
+        F2_TRY(S.reserve(ctx));
+    }
+    F2_TRY(eval_envelopes(ctx, &E, X, nullptr, n_total));
+    if (n_total == 0) {
+        // (intervals of utterances without rows own no row)
+        if (want_tally && tally_rows > 0) {
+            if (host) memset(tally_or_null, 0, tally_bytes);
+            else F2_HIP(ctx, hipMemsetAsync(tally_or_null, 0, tally_bytes, ctx->stream));
+        }
+        return F2_OK;
+    }
+    const int64_t chunk = n_total < CNN_CHUNK ? n_total : CNN_CHUNK;
+    F2_TRY(eval_cnn_begin(ctx, cnn, &E, chunk, n_total, C, scores_or_null, labels_or_null, mem_space, want_path));
+    F2_TRY(strided_window_loop(ctx, cnn, &E, X, nbh, chunk, radius, step, hop, (float*)ctx->xbuf.ptr));
+    std::vector<int64_t> ro((size_t)B + 1, 0);
+    uint8_t* d_runs_src = nullptr;
+    if (want_path) {
+        F2_TRY(eval_dense_flush(ctx, cnn, &E));
+        uint8_t* d_path = host || !path_or_null ? (uint8_t*)s_path : path_or_null;
+        int32_t* d_q = host || !emissions_or_null ? (int32_t*)s_q : emissions_or_null;
+        const uint8_t* d_labels = E.out.labels.as<uint8_t>();
+        F2_TRY(S.upload_tables(ctx));
+        F2_TRY(f2_launch_decision_path(ctx, S, E.out.scores.as<float>(), logit_scale, penalty, d_path, d_q));
+        if (host && path_or_null) F2_HIP(ctx, hipMemcpyAsync(path_or_null, d_path, n, hipMemcpyDeviceToHost, ctx->stream));
+        if (host && emissions_or_null)
+            F2_HIP(ctx, hipMemcpyAsync(emissions_or_null, d_q, sizeof(int32_t) * n, hipMemcpyDeviceToHost, ctx->stream));
+        if (value_or_null)
+            F2_HIP(ctx, hipMemcpyAsync(value_or_null, S.d_value, sizeof(int64_t) * (size_t)B, hipMemcpyDeviceToHost, ctx->stream));
+        if (want_runs) {
+            F2_TRY(f2_launch_runs_count(ctx, S, d_path, d_q));
+            F2_HIP(ctx, hipMemcpyAsync(ro.data(), S.d_ro, sizeof(int64_t) * ro.size(), hipMemcpyDeviceToHost, ctx->stream));
+            if (runs_or_null) {
+                d_runs_src = host ? (uint8_t*)s_runs : (uint8_t*)runs_or_null;
+                F2_TRY(f2_launch_runs_scatter(ctx, S, d_path, d_q, n_total, (int64_t*)d_runs_src));
+            }
+        }
+        if (want_tally && tally_rows > 0) {
+            int64_t* d_tally = host ? (int64_t*)s_tally : tally_or_null;
+            F2_TRY(f2_launch_interval_tally(ctx, S, d_labels, d_path, d_q, iv_offsets_or_null, iv_bounds, R, (int64_t)radius * step, hop,
+                                            tally_rows, d_tally));
+            if (host) F2_HIP(ctx, hipMemcpyAsync(tally_or_null, d_tally, tally_bytes, hipMemcpyDeviceToHost, ctx->stream));
+        }
+    }
+    const int rc = eval_cnn_end(ctx, cnn, &E);   // (waits for the stream)
+    if (rc != F2_OK && rc != F2_ERR_NONPOSITIVE) return rc;
+    if (run_offsets_or_null) memcpy(run_offsets_or_null, ro.data(), sizeof(int64_t) * ro.size());
+    if (host && runs_or_null && ro[(size_t)B] > 0) {
+        F2_HIP(ctx, hipMemcpyAsync(runs_or_null, d_runs_src, sizeof(int64_t) * 4 * (size_t)ro[(size_t)B], hipMemcpyDeviceToHost, ctx->stream));
+        F2_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    return rc;
+}
+
 }  // extern "C"
 
 // ---- the robustness sweeps: K levels of one axis (noise, room, envelope cutoff, spectral resolution) and the unchanged level of a ragged batch as ONE

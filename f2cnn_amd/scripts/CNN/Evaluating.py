@@ -72,6 +72,7 @@ from ... import _lib
 from ...config import F2Config
 from ...gammatone import filters
 from ...model import F2CNNModel, load_model
+from ...segments import CombinePhonemeTally, PhonemeIntervals, PhonemeTable, Quantise, RunsTable
 from ..processing.EnvelopeExtraction import FFT_PRECISION
 from ..processing.GammatoneFiltering import GetArrayFromWAV, GetArraysFromWAVsResampled
 
@@ -178,8 +179,8 @@ def _print_accuracy(what, confusion, accuracy):
         what, accuracy, float(_accuracy_of(confusion)), int(numpy.trace(confusion)), int(confusion.sum())))
 
 
-def _file_accuracy(file, labels, accuracy, hop, framerate, ctx=None):
-    """The accuracy keys of one file's labels against the labels of `file`'s side files ({} without them), printed."""
+def _file_accuracy(file, labels, accuracy, hop, framerate, ctx=None, what=None):
+    """The accuracy keys of one file's labels against the labels of `file`'s side files ({} without them), printed (as `what`)."""
     _accuracy_origin(accuracy, 0, 0)      # (the mode is checked before anything is read)
     ref = ReferenceLabels(file)
     if ref is None:
@@ -187,7 +188,7 @@ def _file_accuracy(file, labels, accuracy, hop, framerate, ctx=None):
         return {}
     confusion = _confusions(ctx or _lib.default_context(), labels, [0, len(labels)], [ref], accuracy, hop,
                             _step(framerate, F2Config()))[0]
-    _print_accuracy(file, confusion, accuracy)
+    _print_accuracy(what or file, confusion, accuracy)
     return _accuracy_keys(confusion, accuracy)
 
 
@@ -201,6 +202,71 @@ def _scored_extra(file, labels, accuracy, hop, framerate, source, resample):
         extra = _file_accuracy(file, labels, accuracy, hop, framerate)
     extra = dict(extra, **_rate_keys(resample, framerate, source))
     return extra or None
+
+
+# ---- transitions: the decisions smoothed by the two-state decoder (segments.py; not in the reference) -----------------------
+def _segments_spec(segments):
+    """segments= as the callers give it (True, or a dict with dwell_ms / weight / intervals) with every key present"""
+    given = {} if segments is True else dict(segments)
+    return dict(dwell_ms=given.get('dwell_ms'), weight=given.get('weight', 'auto'), intervals=given.get('intervals'))
+
+
+def _segments_sets(intervals, B):
+    """(iv_offsets (B + 1), iv_bounds (total, 2)): one interval set per utterance, empty where it has none"""
+    sets = [numpy.zeros((0, 2), numpy.int64) if iv is None else numpy.asarray(iv, numpy.int64).reshape(-1, 2)
+            for iv in (intervals if intervals is not None else [None] * B)]
+    if len(sets) != B:
+        raise ValueError("segments: one interval set (or None) per utterance")
+    offsets = numpy.zeros(B + 1, numpy.int64)
+    offsets[1:] = numpy.cumsum([len(iv) for iv in sets])
+    return offsets, numpy.concatenate(sets).reshape(-1, 2)
+
+
+def PhonemeIntervalsOf(wavFile):
+    """(names, bounds (k, 2) int64) of the file's .PHN, or None without it"""
+    from ..processing.PHNFileReader import ExtractPhonemes
+    phn = os.path.splitext(wavFile)[0] + '.PHN'
+    if not os.path.exists(phn):
+        return None
+    names, bounds = PhonemeIntervals(ExtractPhonemes(phn))
+    return (names, bounds) if names else None
+
+
+def _file_segments(segments, file, source, framerate):
+    """segments= of one file for EvaluateWavArrays and the names of its phonemes (None: no .PHN, or a resampled file, whose .PHN
+    counts source samples)"""
+    phonemes = PhonemeIntervalsOf(file) if source == framerate else None
+    if source != framerate:
+        print("\t\t{}\tresampled from {} Hz to {} Hz, its .PHN counts source samples: no phoneme table".format(file, source, framerate))
+    spec = _segments_spec(segments)
+    return dict(spec, intervals=[None if phonemes is None else phonemes[1]]), None if phonemes is None else phonemes[0]
+
+
+def _write_segments(what, seg, framerate, names):
+    """Prints the runs table and, with the names of the file's phonemes, the phoneme table; returns the segments_* keys of the .npz.
+    seg: an entry's dict of EvaluateWavArrays(segments=)."""
+    cfg = F2Config()
+    origin = cfg.radius * _step(framerate, cfg)
+    bounds = seg['intervals']
+    for line in RunsTable(what, seg['runs'], origin, seg['hop'], framerate, seg['logit_scale'], names, bounds):
+        print(line)
+    keys = dict(segments_path=seg['path'], segments_runs=seg['runs'], segments_run_offsets=numpy.array([0, len(seg['runs'])], numpy.int64),
+                segments_value=numpy.int64(seg['value']), segments_logit_scale=numpy.float64(seg['logit_scale']),
+                segments_penalty=numpy.int64(seg['penalty']), segments_hop=numpy.int64(seg['hop']))
+    if names is not None:
+        for line in PhonemeTable(what, names, seg['tally'], seg['logit_scale']):
+            print(line)
+        order, rows = CombinePhonemeTally(names, seg['tally'])
+        keys.update(segments_phoneme_names=numpy.array(order), segments_phoneme_tally=rows)
+    return keys
+
+
+def _smoothed_accuracy(file, seg, accuracy, framerate, source):
+    """the second accuracy line of accuracy= with segments=: f2_label_accuracy on the path; its keys ({}: nothing to score)"""
+    if accuracy is None or source != framerate:
+        return {}
+    keys = _file_accuracy(file, seg['path'], accuracy, seg['hop'], framerate, what=file + " (smoothed)")
+    return {'segments_' + k: v for k, v in keys.items() if k != 'accuracy_mode'}
 
 
 # ---- the figure (reference scripts/CNN/Evaluating.py:109-113, scripts/plotting/PlottingCNN.py) ------------------------------
@@ -482,8 +548,10 @@ def EvaluateOneWavArray(wavArray, framerate, wavFileName=None, model='last_train
 
 def EvaluateOneWavFile(file, LPF=False, CUTOFF=50, model='last_trained_model', CENTER_FREQUENCIES=None,
                        FILTERBANK_COEFFICIENTS=None, hop=None, accuracy=None, resample=False, figure=False,
-                       figure_width=FIGURE_WIDTH, occlusion=None, saliency=None):
-    """`cnn eval --file X.WAV [--hop N] [--accuracy [MODE]] [--resample] [--figure] [--occlusion | --saliency]`: writes <base>.F2CNN.npz
+                       figure_width=FIGURE_WIDTH, occlusion=None, saliency=None, segments=None):
+    """(with segments= - True or dict(dwell_ms=, weight=) - also the runs table, with the file's .PHN the phoneme table, with
+    accuracy= a second accuracy line for the smoothed decisions, and the segments_* keys of _write_segments)
+    `cnn eval --file X.WAV [--hop N] [--accuracy [MODE]] [--resample] [--figure] [--occlusion | --saliency]`: writes <base>.F2CNN.npz
     (scores, labels; with a hop also hop, timepoints; with accuracy= and the file's .FB / .PHN also accuracy, confusion,
     accuracy_mode; with resample= framerate, source_framerate; with figure= figure_track, figure_span, and
     graphs/FallingOrRising/<basename>.png; with occlusion= the occlusion_* keys of _write_occlusion, its table, and
@@ -492,13 +560,17 @@ def EvaluateOneWavFile(file, LPF=False, CUTOFF=50, model='last_trained_model', C
     print('Using model', model if not isinstance(model, F2CNNModel) else '<in-memory model>')
     print("File:\t\t{}".format(file))
     source, framerate, wavArray = _load([file], resample)[0]
-    occ = sal = None
-    if figure or occlusion is not None or saliency is not None:
+    occ = sal = seg = None
+    if segments is not None:
+        segments, phoneme_names = _file_segments(segments, file, source, framerate)
+    if figure or occlusion is not None or saliency is not None or segments is not None:
         result = EvaluateWavArrays([wavArray], framerate, model=model, LPF=LPF, CUTOFF=CUTOFF,
                                    FILTERBANK_COEFFICIENTS=FILTERBANK_COEFFICIENTS, hop=hop,
                                    figure_width=figure_width if figure else None, occlusion=occlusion, occlusion_width=figure_width,
-                                   saliency=saliency, saliency_width=figure_width)[0]
+                                   saliency=saliency, saliency_width=figure_width, segments=segments)[0]
         scores, labels = result[:2]
+        if segments is not None:
+            seg, result = result[-1], result[:-1]
         if figure:
             levels, track = result[2:4]
         if occlusion is not None:
@@ -520,6 +592,9 @@ def EvaluateOneWavFile(file, LPF=False, CUTOFF=50, model='last_trained_model', C
     if sal is not None:
         extra = dict(extra or {}, **_write_saliency(file, os.path.splitext(os.path.basename(file))[0], sal, len(wavArray), framerate,
                                                     source))
+    if seg is not None:
+        extra = dict(extra or {}, **_smoothed_accuracy(file, seg, accuracy, framerate, source))
+        extra = dict(extra, **_write_segments(file, seg, framerate, phoneme_names))
     _save(out, scores, labels, hop, len(wavArray), framerate, extra)
     rising = int(labels.sum())
     print("\t\t{}\tdone ! {} windows: {} rising, {} falling -> {}".format(file, len(labels), rising,
@@ -530,7 +605,7 @@ def EvaluateOneWavFile(file, LPF=False, CUTOFF=50, model='last_trained_model', C
 # ---- batch / noise evaluation (reference scripts/CNN/Evaluating.py:138-221) -------------
 def EvaluateWavArrays(wavArrays, framerate, model='last_trained_model', LPF=False, CUTOFF=100,
                       FILTERBANK_COEFFICIENTS=None, ctx=None, hop=None, figure_width=None, occlusion=None,
-                      occlusion_width=None, saliency=None, saliency_width=None):
+                      occlusion_width=None, saliency=None, saliency_width=None, segments=None):
     """EvaluateOneWavArray for a list of utterances of one sample type in one device pass (f2_eval_batch): the
     filterbank and envelope kernels see the whole batch, windows and CNN run utterance by utterance. With a hop
     (f2_eval_batch_strided) every hop-th window, and the window stage and the CNN see the batch as well.
@@ -544,7 +619,12 @@ def EvaluateWavArrays(wavArrays, framerate, model='last_trained_model', LPF=Fals
     With saliency= (True, or the channels per line of the table: _saliency_bands) the pass is f2_eval_saliency_batch (hop=None: hop
     1): scores and labels are those without it, the same bits, and every entry ends in a dict - bands, summary (C, 3), map
     (C, W, 3) and levels (C, W), W = saliency_width (default: figure_width, else FIGURE_WIDTH); with figure_width as well the track
-    is f2_score_track of the scores. One map per pass: not together with occlusion=."""
+    is f2_score_track of the scores. One map per pass: not together with occlusion=.
+    With segments= (True, or a dict: dwell_ms, weight, intervals - one (k, 2) array of sample intervals or None per utterance) the
+    decisions are smoothed by the two-state decoder (hop=None: hop 1) and every entry ends in a dict - path, emissions, runs (n, 4),
+    value, tally (k, 4), intervals, logit_scale, penalty, hop. Alone the pass is f2_eval_segments_batch; together with a figure or
+    a map it is f2_decision_path, f2_decision_runs and f2_interval_tally on the scores that pass returns. Scores and labels are
+    those without it, the same bits."""
     if occlusion is not None and saliency is not None:
         raise ValueError("one map per pass: occlusion= or saliency=, not both")
     ctx = ctx or _lib.default_context()
@@ -570,7 +650,15 @@ def EvaluateWavArrays(wavArrays, framerate, model='last_trained_model', LPF=Fals
         nbs = [_lib.strided_window_count(w.shape[0], cfg.radius, STEP, hop) for w in waves]
     scores = numpy.empty((sum(nbs), 2), numpy.float32)
     labels = numpy.empty(sum(nbs), numpy.uint8)
-    levels = track = occ = sal = None
+    levels = track = occ = sal = seg = None
+    if segments is not None:
+        spec = _segments_spec(segments)
+        seg_hop = 1 if hop is None else hop
+        seg_scale, seg_penalty = Quantise(seg_hop, STEP, framerate, spec['dwell_ms'], spec['weight'])
+        ivo, ivb = _segments_sets(spec['intervals'], len(waves))
+        seg = dict(path=numpy.empty(sum(nbs), numpy.uint8), emissions=numpy.empty(sum(nbs), numpy.int32),
+                   runs=numpy.empty((sum(nbs), 4), numpy.int64), tally=numpy.zeros((int(ivo[-1]), 4), numpy.int64))
+        seg_wo = numpy.concatenate([[0], numpy.cumsum(nbs)]).astype(numpy.int64)
     try:
         if saliency is not None:
             B = len(waves)
@@ -613,6 +701,12 @@ def EvaluateWavArrays(wavArrays, framerate, model='last_trained_model', LPF=Fals
                                            CUTOFF if LPF else 0.0, FFT_PRECISION, cfg.radius, STEP, 1 if hop is None else hop,
                                            None, int(figure_width), 0, levels, track, scores, labels, _lib.MEM_HOST)
             assert list(numpy.diff(got)) == nbs
+        elif seg is not None:
+            got, seg['value'], seg['run_offsets'] = ctx.eval_segments_batch(
+                model.handle(ctx), flat, dts[0], offsets, coefs, len(waves), Cn, bool(LPF), CUTOFF if LPF else 0.0, FFT_PRECISION,
+                cfg.radius, STEP, seg_hop, seg_scale, seg_penalty, ivo, ivb, scores, labels, seg['path'], seg['emissions'], seg['runs'],
+                seg['tally'], _lib.MEM_HOST)
+            assert list(numpy.diff(got)) == nbs
         elif hop is not None:
             got = ctx.eval_batch_strided(model.handle(ctx), flat, dts[0], offsets, coefs, len(waves), Cn, bool(LPF),
                                          CUTOFF if LPF else 0.0, FFT_PRECISION, cfg.radius, STEP, hop, scores, labels,
@@ -621,6 +715,11 @@ def EvaluateWavArrays(wavArrays, framerate, model='last_trained_model', LPF=Fals
         else:
             ctx.eval_batch(model.handle(ctx), flat, dts[0], offsets, coefs, len(waves), Cn, bool(LPF), CUTOFF if LPF else 0.0,
                            FFT_PRECISION, cfg.radius, STEP, scores, labels, _lib.MEM_HOST)
+        if seg is not None and 'value' not in seg:     # beside a figure or a map: the three stage calls on its scores
+            seg['value'] = ctx.decision_path(scores, seg_wo, seg_scale, seg_penalty, seg['path'], _lib.MEM_HOST, emissions=seg['emissions'])
+            seg['run_offsets'] = ctx.decision_runs(seg['path'], seg['emissions'], seg_wo, seg['runs'], len(seg['runs']), _lib.MEM_HOST)
+            ctx.interval_tally(labels, seg['path'], seg['emissions'], seg_wo, ivo, ivb, cfg.radius * STEP, seg_hop, seg['tally'],
+                               _lib.MEM_HOST)
     except _lib.F2Error as e:
         if e.code == _lib.F2_ERR_NONPOSITIVE:
             raise ValueError("values must all be positive")
@@ -633,14 +732,21 @@ def EvaluateWavArrays(wavArrays, framerate, model='last_trained_model', LPF=Fals
                            map=occ['map'][b], levels=occ['levels'][b]),)
         if sal is not None:
             entry += (dict(bands=sal['bands'], summary=sal['summary'][b], map=sal['map'][b], levels=sal['levels'][b]),)
+        if seg is not None:
+            ro = seg['run_offsets']
+            entry += (dict(path=seg['path'][pos:pos + nb], emissions=seg['emissions'][pos:pos + nb], runs=seg['runs'][ro[b]:ro[b + 1]],
+                           value=seg['value'][b], tally=seg['tally'][ivo[b]:ivo[b + 1]], intervals=ivb[ivo[b]:ivo[b + 1]],
+                           logit_scale=seg_scale, penalty=seg_penalty, hop=seg_hop),)
         out.append(entry)
         pos += nb
     return out
 
 
 def EvaluateRandom(count=None, LPF=False, CUTOFF=50, model='last_trained_model', hop=None, accuracy=None, resample=False,
-                   figure=False, figure_width=FIGURE_WIDTH, occlusion=None, saliency=None):
-    """`cnn evalrand`: evaluate the WAV files under resources/f2cnn/*/ in random order (all of them, or `count`
+                   figure=False, figure_width=FIGURE_WIDTH, occlusion=None, saliency=None, segments=None):
+    """(with segments= every file's transitions as EvaluateOneWavFile prints and stores them, a group of files decoded in the
+    group's device pass)
+    `cnn evalrand`: evaluate the WAV files under resources/f2cnn/*/ in random order (all of them, or `count`
     drawn with replacement like numpy.random.choice in the reference). The filterbank is designed once and the model
     is uploaded once (the reference reloads the Keras model for every file). With a hop each group of files is one
     strided call. With accuracy= every file that has its .FB / .PHN is scored against them - a group in one device pass - and
@@ -680,17 +786,22 @@ def EvaluateRandom(count=None, LPF=False, CUTOFF=50, model='last_trained_model',
         group = wavFiles[s0:s0 + BATCH]
         sources, loaded = zip(*[(source, (fr, w)) for source, fr, w in _load(group, resample)])
         rates = {fr for fr, _ in loaded}
+        file_segments = [(None, None)] * len(group)
+        if segments is not None:
+            file_segments = [_file_segments(segments, file, source, fr) for file, source, (fr, _) in zip(group, sources, loaded)]
+        group_segments = None if segments is None else dict(file_segments[0][0], intervals=[fs['intervals'][0] for fs, _ in file_segments])
         if len(rates) == 1 and len({numpy.asarray(w).dtype for _, w in loaded}) == 1:
             outs = EvaluateWavArrays([w for _, w in loaded], loaded[0][0], model=model, LPF=LPF, CUTOFF=CUTOFF,
                                      FILTERBANK_COEFFICIENTS=FILTERBANK_COEFFICIENTS, hop=hop,
                                      figure_width=figure_width if figure else None, occlusion=occlusion,
-                                     occlusion_width=figure_width, saliency=saliency, saliency_width=figure_width)
-        elif figure or occlusion is not None or saliency is not None:     # mixed files: one at a time
+                                     occlusion_width=figure_width, saliency=saliency, saliency_width=figure_width,
+                                     segments=group_segments)
+        elif figure or occlusion is not None or saliency is not None or segments is not None:     # mixed files: one at a time
             outs = [EvaluateWavArrays([w], fr, model=model, LPF=LPF, CUTOFF=CUTOFF,
                                       FILTERBANK_COEFFICIENTS=FILTERBANK_COEFFICIENTS if fr == cfg.framerate else None, hop=hop,
                                       figure_width=figure_width if figure else None, occlusion=occlusion,
-                                      occlusion_width=figure_width, saliency=saliency, saliency_width=figure_width)[0]
-                    for fr, w in loaded]
+                                      occlusion_width=figure_width, saliency=saliency, saliency_width=figure_width, segments=fs)[0]
+                    for (fr, w), (fs, _) in zip(loaded, file_segments)]
         else:                                     # mixed files: one at a time
             outs = [EvaluateOneWavArray(w, fr, file, model=model, LPF=LPF, CUTOFF=CUTOFF,
                                         FILTERBANK_COEFFICIENTS=FILTERBANK_COEFFICIENTS if fr == cfg.framerate else None,
@@ -714,9 +825,13 @@ def EvaluateRandom(count=None, LPF=False, CUTOFF=50, model='last_trained_model',
                     _print_accuracy(group[i], confusion, accuracy)
                     extras[i] = _accuracy_keys(confusion, accuracy)
                     corpus += confusion
-        for file, source, (fr, w), result, extra in zip(group, sources, loaded, outs, extras):
+        for file, source, (fr, w), result, extra, (_, phoneme_names) in zip(group, sources, loaded, outs, extras, file_segments):
             scores, labels = result[:2]
             out = os.path.splitext(file)[0] + '.F2CNN.npz'
+            if segments is not None:
+                seg, result = result[-1], result[:-1]
+                extra = dict(extra or {}, **_smoothed_accuracy(file, seg, accuracy, fr, source))
+                extra = dict(extra, **_write_segments(file, seg, fr, phoneme_names))
             if figure:
                 extra = dict(extra or {}, **_write_figure(file, os.path.splitext(os.path.basename(file))[0], result[2], result[3],
                                                           len(w), fr, source, extra))
@@ -779,8 +894,9 @@ def add_gaussian_noise(wave, SNRdB, rng=None):
 
 def EvaluateWithNoise(file, LPF=False, CUTOFF=100, model='last_trained_model', CENTER_FREQUENCIES=None,
                       FILTERBANK_COEFFICIENTS=None, SNRdB=-3, rng=None, hop=None, accuracy=None, resample=False, figure=False,
-                      figure_width=FIGURE_WIDTH, occlusion=None, saliency=None):
-    """`cnn evalnoise` (reference: scripts/CNN/Evaluating.py:193-221): the file plus Gaussian noise at the requested level is
+                      figure_width=FIGURE_WIDTH, occlusion=None, saliency=None, segments=None):
+    """(with segments= the noisy run's transitions as EvaluateOneWavFile prints and stores them, its phonemes those of the clean file)
+    `cnn evalnoise` (reference: scripts/CNN/Evaluating.py:193-221): the file plus Gaussian noise at the requested level is
     written next to copies of its annotation files under OutputWavFiles/addedNoise/ and the float64 waveform is evaluated by
     the device pipeline. Returns (scores, labels) and also leaves them in <target>.F2CNN.npz; `rng` (a numpy Generator or
     RandomState) makes the noise reproducible - the reference draws from the global numpy state. With accuracy= the noisy
@@ -803,13 +919,17 @@ def EvaluateWithNoise(file, LPF=False, CUTOFF=100, model='last_trained_model', C
         if os.path.exists(source + ext):
             shutil.copyfile(source + ext, target + ext)
     print('New noisy WAVE file saved as', target + '.WAV')
-    occ = sal = None
-    if figure or occlusion is not None or saliency is not None:
+    occ = sal = seg = None
+    if segments is not None:
+        segments, phoneme_names = _file_segments(segments, file, source_rate, framerate)
+    if figure or occlusion is not None or saliency is not None or segments is not None:
         result = EvaluateWavArrays([noisy], framerate, model=model, LPF=LPF, CUTOFF=CUTOFF,
                                    FILTERBANK_COEFFICIENTS=FILTERBANK_COEFFICIENTS, hop=hop,
                                    figure_width=figure_width if figure else None, occlusion=occlusion, occlusion_width=figure_width,
-                                   saliency=saliency, saliency_width=figure_width)[0]
+                                   saliency=saliency, saliency_width=figure_width, segments=segments)[0]
         scores, labels = result[:2]
+        if segments is not None:
+            seg, result = result[-1], result[:-1]
         if figure:
             levels, track = result[2:4]
         if occlusion is not None:
@@ -828,6 +948,9 @@ def EvaluateWithNoise(file, LPF=False, CUTOFF=100, model='last_trained_model', C
         extra = dict(extra or {}, **_write_occlusion(file, os.path.basename(target), occ, len(noisy), framerate, source_rate))
     if sal is not None:
         extra = dict(extra or {}, **_write_saliency(file, os.path.basename(target), sal, len(noisy), framerate, source_rate))
+    if seg is not None:
+        extra = dict(extra or {}, **_smoothed_accuracy(file, seg, accuracy, framerate, source_rate))
+        extra = dict(extra, **_write_segments(target + '.WAV', seg, framerate, phoneme_names))
     _save(target + '.F2CNN.npz', scores, labels, hop, len(noisy), framerate, extra)
     print("\t\t{}\tdone !".format(file))
     return scores, labels

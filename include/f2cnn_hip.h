@@ -1273,6 +1273,92 @@ int f2_trainer_render_smeared(f2_ctx* ctx, f2_trainer* trainer, const double* ri
                               const double* mix /* host, (Km, C, C), or NULL: sharp */, int Km,
                               const int32_t* mix_of /* host, B, or NULL */);
 
+/* ---- `cnn eval --segments`: decisions smoothed into transitions ---------------------------------------------------------------
+ * The reference stops at a rising / falling label per row (Evaluating.py:73-90); where the network is unsure the labels flicker,
+ * and a run-length reading of them is mostly noise. Here: the most probable two-state sequence under a switching penalty, its
+ * maximal runs, and the rows of every labelled interval (a phoneme) counted, all on the device. (f2_version stays 115 with these
+ * four entries: look the symbols up to find out whether a build has them.)
+ * Rows are those of f2_score_track / f2_label_accuracy: utterance u owns rows window_offsets[u] .. window_offsets[u+1] - 1, row j
+ * stands at sample t = origin + j*hop, scores[j][1] is P(rising). mem_space is F2_MEM_HOST or F2_MEM_DEVICE; device pointers need
+ * element alignment only; the small host arrays go up through the context's page-locked staging.
+ *
+ * f2_decision_path: the smoothed decision per row.
+ *   emission    q_j = (int32) rint(logit_scale * (ln c(scores[j][1]) - ln c(scores[j][0]))), c(p) = min(max((double)p, 1e-7), 1.0)
+ *               (f2_cnn_score_windows' clip), float64 throughout, rint to nearest with ties to even; a NaN in either score: q_j = 0.
+ *   objective   over x in {0,1}^n: maximise sum_j x_j q_j - penalty * #{j >= 1 : x_j != x_{j-1}}, in int64.
+ *   path        the one the sequential definition gives, ties included: V_0 = (0, q_0); V_j(s) = max(V_{j-1}(s), V_{j-1}(1-s) -
+ *               penalty) + (s ? q_j : 0); bp_j(s) = s if V_{j-1}(s) >= V_{j-1}(1-s) - penalty (a tie stays), else 1-s;
+ *               x_{n-1} = 1 iff V_{n-1}(1) > V_{n-1}(0) (a tie is falling); x_{j-1} = bp_j(x_j). With penalty = 0: x_j = (q_j > 0)
+ *               wherever q_j != 0, a row with q_j = 0 takes the state of the row after it, and the last row is falling.
+ *   outputs     path (window_offsets[U]) uint8 in mem_space; emissions_or_null int32, same shape and memory space;
+ *               value_or_null (host, U) int64, the optimum. An utterance without rows has value 0 and writes nothing.
+ *   kernels     the recurrence is a product of 2 x 2 matrices over (max, +) on int64, which is exactly associative: a product per
+ *               tile of F2_PATH_TILE rows, a scan of the tile products per utterance (F2_PATH_SCAN_CHUNK tiles per step), each
+ *               tile redone from the vector that enters it; then the same three steps from the right for the back pointers, which
+ *               are maps {0,1} -> {0,1} under composition. Any order of an exact associative product gives the same V, hence the
+ *               same path: the same bytes on every call, in both memory spaces, alone or inside a batch. No kernel waits for
+ *               another workgroup.
+ *   The call waits for the stream when it hands back value (whatever mem_space is) or serves host memory.
+ *   F2_ERR_INVALID, before anything is launched or written: a NULL ctx / window_offsets; NULL scores or path with rows; U < 0;
+ *   offsets that do not start at 0 or decrease; logit_scale not finite or <= 0; penalty < 0; a bad mem_space. F2_ERR_UNSUPPORTED,
+ *   likewise: logit_scale > 2^20, penalty > 2^40, 2^31 rows or more (inside these limits |V| < 2^62).
+ *
+ * f2_decision_runs: maximal runs of equal decisions. labels: a path or raw labels, nonzero = rising.
+ *   run_offsets (host, U+1)   utterance u owns runs run_offsets[u] .. run_offsets[u+1] - 1; always filled when the arguments pass.
+ *   runs (capacity, 4) int64 in mem_space, or NULL to count only: {first row j0 within the utterance, rows, label 0 / 1,
+ *               sum of q_j over the run (0 without emissions)}, utterance-major, ascending j0; a run never crosses an utterance
+ *               boundary. capacity = window_offsets[U] always suffices.
+ *   Boundary flags, integer prefix sums of the flags and of q, scatter: exact, the same bytes on every call and in both memory
+ *   spaces. The call waits for the stream once to hand back run_offsets (and a second time behind the runs of a host caller).
+ *   F2_ERR_INVALID: a NULL ctx / window_offsets / run_offsets; NULL labels with rows; U < 0; bad offsets; capacity < 0 with runs;
+ *   a bad mem_space. F2_ERR_UNSUPPORTED: 2^31 rows or more; a non-NULL runs with capacity < run_offsets[U] - then run_offsets is
+ *   filled and runs untouched.
+ *
+ * f2_interval_tally: decisions per labelled interval, the device side of a per-phoneme table.
+ *   iv_offsets (host, R+1), iv_bounds (host, 2 * iv_offsets[R]) int64 pairs [a_k, b_k)   R interval sets, utterance u uses set
+ *               u % R (a sweep passes U = (K+1)*B and R = B); within a set 0 <= a_k <= b_k <= a_{k+1}. Interval k owns the rows
+ *               with a_k <= t_j < b_k.
+ *   tally       (sum over u of the intervals of set u % R, 4) int64 in mem_space, utterance-major: {rows, rows with labels != 0,
+ *               rows with path != 0 (0 if path is NULL), sum of q (0 if emissions is NULL)}.
+ *   F2_ERR_INVALID, before anything is launched or written: a NULL ctx / tally / window_offsets / iv_offsets; NULL labels with
+ *   rows; NULL iv_bounds with intervals; U < 0; R < 1 or U % R != 0 when U > 0 (R < 0 always); hop < 1 or origin < 0; bad offsets;
+ *   bounds that are negative, reversed or overlap the interval before; a bad mem_space. F2_ERR_UNSUPPORTED: 2^31 rows or tally rows
+ *   or more; the timepoint of an utterance's last row does not fit int64.
+ *
+ * f2_eval_segments_batch: f2_eval_batch_strided, then the three stages on the device's scores; nothing comes down in between.
+ *   scores, labels, window_offsets   bit for bit what f2_eval_batch_strided returns for the same wave ... hop and mem_space
+ *   path, emissions, value           f2_decision_path of those scores
+ *   run_offsets, runs                f2_decision_runs of that path and those emissions; runs has room for window_offsets[B]
+ *                                    rows (f2_eval_batch_strided's window count)
+ *   tally                            f2_interval_tally of labels, path, emissions with origin = radius*step; NULL iv_offsets: none
+ *   Every output is optional (NULL) and bit for bit what the separate call gives on those scores; path and emissions are made
+ *   whenever runs or tally need them. One wait at the end (a host caller's runs come down behind it, once their number is known).
+ *   Errors: everything f2_eval_batch_strided rejects, by the same checks and first; then those of the three stages in their order,
+ *   all before anything is launched or written.
+ */
+#define F2_PATH_TILE 1024       /* rows per workgroup of the decoding kernels */
+#define F2_PATH_SCAN_CHUNK 256  /* tiles per step of the per-utterance scans of the tile products */
+int f2_decision_path(f2_ctx* ctx, const float* scores /* (window_offsets[U], 2), mem_space */,
+                     const int64_t* window_offsets /* host, U+1 */, int U, double logit_scale, int64_t penalty,
+                     uint8_t* path /* (window_offsets[U]), mem_space */, int32_t* emissions_or_null /* likewise */,
+                     int64_t* value_or_null /* host, U */, int mem_space);
+int f2_decision_runs(f2_ctx* ctx, const uint8_t* labels /* (window_offsets[U]), mem_space */,
+                     const int32_t* emissions_or_null /* likewise */, const int64_t* window_offsets /* host, U+1 */, int U,
+                     int64_t* run_offsets /* host, U+1 */, int64_t* runs_or_null /* (capacity, 4), mem_space */, int64_t capacity,
+                     int mem_space);
+int f2_interval_tally(f2_ctx* ctx, const uint8_t* labels /* mem_space */, const uint8_t* path_or_null /* mem_space */,
+                      const int32_t* emissions_or_null /* mem_space */, const int64_t* window_offsets /* host, U+1 */, int U,
+                      const int64_t* iv_offsets /* host, R+1 */, const int64_t* iv_bounds /* host, 2 * iv_offsets[R] */, int R,
+                      int64_t origin, int hop, int64_t* tally /* (rows, 4), mem_space */, int mem_space);
+int f2_eval_segments_batch(f2_ctx* ctx, const f2_cnn* cnn, const void* wave, int wave_dtype, const int64_t* offsets,
+                           const double* coefs, int B, int C, int lpf, double cutoff_hz, int fft_precision, int radius, int step,
+                           int hop, double logit_scale, int64_t penalty, const int64_t* iv_offsets_or_null /* host, R+1 */,
+                           const int64_t* iv_bounds /* host */, int R, float* scores_or_null, uint8_t* labels_or_null,
+                           int64_t* window_offsets_or_null /* host, B+1 */, uint8_t* path_or_null, int32_t* emissions_or_null,
+                           int64_t* value_or_null /* host, B */, int64_t* run_offsets_or_null /* host, B+1 */,
+                           int64_t* runs_or_null /* (window_offsets[B], 4), mem_space */, int64_t* tally_or_null /* mem_space */,
+                           int mem_space);
+
 #ifdef __cplusplus
 }
 #endif
