@@ -701,8 +701,6 @@ def main(argv=None):
             return 1
         if getattr(args, 'figure', False):
             kwargs['figure'] = True
-            if getattr(args, 'figure_width', None) is not None:
-                kwargs['figure_width'] = args.figure_width
         if 'occlusion' in args:
             fill = getattr(args, 'occlusion_fill', 0.0)
             if not 0.0 <= fill <= 1.0:
@@ -710,8 +708,6 @@ def main(argv=None):
                 return 1
             rows = getattr(args, 'occlusion_rows', (None, None))
             kwargs['occlusion'] = dict(band=args.occlusion[0], stride=args.occlusion[1], row_band=rows[0], row_stride=rows[1], fill=fill)
-            if getattr(args, 'figure_width', None) is not None:
-                kwargs['figure_width'] = args.figure_width
         elif 'occlusion_rows' in args or 'occlusion_fill' in args:
             print("--occlusion-rows and --occlusion-fill belong to --occlusion")
             return 1
@@ -724,11 +720,11 @@ def main(argv=None):
                 print("--saliency-bands must be at least 1 channel")
                 return 1
             kwargs['saliency'] = bands
-            if getattr(args, 'figure_width', None) is not None:
-                kwargs['figure_width'] = args.figure_width
         elif 'saliency_bands' in args:
             print("--saliency-bands belongs to --saliency")
             return 1
+        if getattr(args, 'figure_width', None) is not None and (kwargs.get('figure') or 'occlusion' in kwargs or 'saliency' in kwargs):
+            kwargs['figure_width'] = args.figure_width          # (the one width of the figure and of a map)
         if 'segments' in args:
             if sweep:
                 print("--segments is not supported by {} ({})".format(args.cnn_command, NO_SWEEP_SEGMENTS))

@@ -34,6 +34,16 @@ on the device (``f2_eval_saliency_batch``; only sum_r G x and sum_r |G| per wind
 One map per run: not together with ``occlusion=``. Scores and labels are bit for bit those without the flag; ``saliency=None``
 changes nothing.
 
+``segments=True | dict(dwell_ms=, weight=)`` (``cnn eval|evalnoise|evalrand --segments [--dwell MS] [--segments-weight auto|X]``;
+not in the reference) smooths the decisions into transitions with the two-state decoder of ``segments.py``, on the device
+(``f2_eval_segments_batch``; beside a figure or a map the three stage calls on that pass's scores). The runs table is printed,
+with the file's ``.PHN`` (for ``evalnoise`` the clean file's; not for a file whose rate differed under ``resample=``) the phoneme
+table as well, with ``accuracy=`` a second accuracy line for the smoothed decisions, and the ``.npz`` gains the ``segments_*`` keys
+of ``_write_segments``. Scores and labels are bit for bit those without it; ``segments=None`` changes nothing.
+
+The three commands share the request (``_Request``), the evaluation of a group of files (``_evaluate_group``: an ``_Evaluated`` per
+file) and the end of a file (``_finish_file``); a file's blocks come in the order of the paragraphs above.
+
 ``accuracy='reference'|'centre'`` (``cnn eval|evalnoise|evalrand|noisesweep --accuracy [MODE]``) is the end of the reference's
 ``EvaluateOneWavArray`` (:38-40, :92-108): the decisions held against the labels ``LabelDataGenerator.ExtractLabel`` derives
 from the SOURCE file's ``.FB`` / ``.PHN``, counted on the device (``f2_label_accuracy``, where the rule is written out). A row
@@ -193,15 +203,14 @@ def _file_accuracy(file, labels, accuracy, hop, framerate, ctx=None, what=None):
 
 
 def _scored_extra(file, labels, accuracy, hop, framerate, source, resample):
-    """the keys a per-file .npz gains from accuracy= and resample= (None: none)"""
+    """the keys a per-file .npz gains from accuracy= and resample="""
     extra = {}
     if accuracy is not None and source != framerate:
         _accuracy_origin(accuracy, 0, 0)
         _no_rate_accuracy(file, source, framerate)
     elif accuracy is not None:
         extra = _file_accuracy(file, labels, accuracy, hop, framerate)
-    extra = dict(extra, **_rate_keys(resample, framerate, source))
-    return extra or None
+    return dict(extra, **_rate_keys(resample, framerate, source))
 
 
 # ---- transitions: the decisions smoothed by the two-state decoder (segments.py; not in the reference) -----------------------
@@ -232,14 +241,12 @@ def PhonemeIntervalsOf(wavFile):
     return (names, bounds) if names else None
 
 
-def _file_segments(segments, file, source, framerate):
-    """segments= of one file for EvaluateWavArrays and the names of its phonemes (None: no .PHN, or a resampled file, whose .PHN
-    counts source samples)"""
-    phonemes = PhonemeIntervalsOf(file) if source == framerate else None
+def _file_phonemes(file, source, framerate):
+    """PhonemeIntervalsOf the file for its segments (None: no .PHN, or a resampled file, whose .PHN counts source samples)"""
     if source != framerate:
         print("\t\t{}\tresampled from {} Hz to {} Hz, its .PHN counts source samples: no phoneme table".format(file, source, framerate))
-    spec = _segments_spec(segments)
-    return dict(spec, intervals=[None if phonemes is None else phonemes[1]]), None if phonemes is None else phonemes[0]
+        return None
+    return PhonemeIntervalsOf(file)
 
 
 def _write_segments(what, seg, framerate, names):
@@ -546,63 +553,136 @@ def EvaluateOneWavArray(wavArray, framerate, wavFileName=None, model='last_train
     return (scores, labels, env) if return_envelopes else (scores, labels)
 
 
-def EvaluateOneWavFile(file, LPF=False, CUTOFF=50, model='last_trained_model', CENTER_FREQUENCIES=None,
-                       FILTERBANK_COEFFICIENTS=None, hop=None, accuracy=None, resample=False, figure=False,
-                       figure_width=FIGURE_WIDTH, occlusion=None, saliency=None, segments=None):
-    """(with segments= - True or dict(dwell_ms=, weight=) - also the runs table, with the file's .PHN the phoneme table, with
-    accuracy= a second accuracy line for the smoothed decisions, and the segments_* keys of _write_segments)
-    `cnn eval --file X.WAV [--hop N] [--accuracy [MODE]] [--resample] [--figure] [--occlusion | --saliency]`: writes <base>.F2CNN.npz
-    (scores, labels; with a hop also hop, timepoints; with accuracy= and the file's .FB / .PHN also accuracy, confusion,
-    accuracy_mode; with resample= framerate, source_framerate; with figure= figure_track, figure_span, and
-    graphs/FallingOrRising/<basename>.png; with occlusion= the occlusion_* keys of _write_occlusion, its table, and
-    graphs/Occlusion/<basename>.png; with saliency= the saliency_* keys of _write_saliency, its table, and
-    graphs/Saliency/<basename>.png) and returns (scores, labels)."""
-    print('Using model', model if not isinstance(model, F2CNNModel) else '<in-memory model>')
-    print("File:\t\t{}".format(file))
-    source, framerate, wavArray = _load([file], resample)[0]
-    occ = sal = seg = None
-    if segments is not None:
-        segments, phoneme_names = _file_segments(segments, file, source, framerate)
-    if figure or occlusion is not None or saliency is not None or segments is not None:
-        result = EvaluateWavArrays([wavArray], framerate, model=model, LPF=LPF, CUTOFF=CUTOFF,
-                                   FILTERBANK_COEFFICIENTS=FILTERBANK_COEFFICIENTS, hop=hop,
-                                   figure_width=figure_width if figure else None, occlusion=occlusion, occlusion_width=figure_width,
-                                   saliency=saliency, saliency_width=figure_width, segments=segments)[0]
-        scores, labels = result[:2]
-        if segments is not None:
-            seg, result = result[-1], result[:-1]
-        if figure:
-            levels, track = result[2:4]
-        if occlusion is not None:
-            occ = result[-1]
-        if saliency is not None:
-            sal = result[-1]
-    else:
-        scores, labels = EvaluateOneWavArray(wavArray, framerate, file, model=model, LPF=LPF, CUTOFF=CUTOFF,
-                                             CENTER_FREQUENCIES=CENTER_FREQUENCIES,
-                                             FILTERBANK_COEFFICIENTS=FILTERBANK_COEFFICIENTS, hop=hop)
-    out = os.path.splitext(file)[0] + '.F2CNN.npz'
-    extra = _scored_extra(file, labels, accuracy, hop, framerate, source, resample)
-    if figure:
-        extra = dict(extra or {}, **_write_figure(file, os.path.splitext(os.path.basename(file))[0], levels, track, len(wavArray),
-                                                  framerate, source, extra))
-    if occ is not None:
-        extra = dict(extra or {}, **_write_occlusion(file, os.path.splitext(os.path.basename(file))[0], occ, len(wavArray), framerate,
-                                                     source))
-    if sal is not None:
-        extra = dict(extra or {}, **_write_saliency(file, os.path.splitext(os.path.basename(file))[0], sal, len(wavArray), framerate,
-                                                    source))
-    if seg is not None:
-        extra = dict(extra or {}, **_smoothed_accuracy(file, seg, accuracy, framerate, source))
-        extra = dict(extra, **_write_segments(file, seg, framerate, phoneme_names))
-    _save(out, scores, labels, hop, len(wavArray), framerate, extra)
-    rising = int(labels.sum())
-    print("\t\t{}\tdone ! {} windows: {} rising, {} falling -> {}".format(file, len(labels), rising,
-                                                                          len(labels) - rising, out))
-    return scores, labels
-
-
 # ---- batch / noise evaluation (reference scripts/CNN/Evaluating.py:138-221; SURVEY section 8f row n2) -------------
+class _Request(collections.namedtuple('_Request', 'hop device_hop figure_width map_width occlusion saliency segments')):
+    """What a run asks of the evaluation beyond scores and labels, settled once from the keywords: the hop as given and as the
+    device sees it (1 for None), the figure's width (None: no figure), the width of a map, and the occlusion spec
+    (_occlusion_spec), the saliency bands (_saliency_bands) and the segments spec (_segments_spec), None where not asked for."""
+    __slots__ = ()
+
+    @classmethod
+    def of(cls, hop=None, figure_width=None, map_width=None, occlusion=None, saliency=None, segments=None):
+        if occlusion is not None and saliency is not None:
+            raise ValueError("one map per pass: occlusion= or saliency=, not both")
+        return cls(hop, 1 if hop is None else hop, None if figure_width is None else int(figure_width),
+                   int(map_width or figure_width or FIGURE_WIDTH), None if occlusion is None else _occlusion_spec(occlusion),
+                   None if saliency is None else _saliency_bands(saliency), None if segments is None else _segments_spec(segments))
+
+    @classmethod
+    def of_command(cls, hop, figure, figure_width, occlusion, saliency, segments):
+        """the request of cnn eval / evalnoise / evalrand: one width for the figure and the maps"""
+        return cls.of(hop, figure_width if figure else None, figure_width, occlusion, saliency, segments)
+
+    @property
+    def needs_pass(self):
+        """something only the batch pass (_evaluate_arrays) makes"""
+        return any(x is not None for x in (self.figure_width, self.occlusion, self.saliency, self.segments))
+
+
+# one utterance of _evaluate_arrays; what was not asked for is None. levels, track: the figure's; occlusion, saliency, segments:
+# the dicts EvaluateWavArrays documents
+_Evaluated = collections.namedtuple('_Evaluated', 'scores labels levels track occlusion saliency segments')
+
+
+def _evaluate_arrays(wavArrays, framerate, req, model, LPF, CUTOFF, FILTERBANK_COEFFICIENTS, ctx=None):
+    """EvaluateWavArrays' device pass for the request `req`: an _Evaluated per utterance"""
+    ctx = ctx or _lib.default_context()
+    cfg = F2Config()
+    if FILTERBANK_COEFFICIENTS is None:
+        FILTERBANK_COEFFICIENTS = filters.make_erb_filters(framerate, filters.centre_freqs(framerate, cfg.nchannels,
+                                                                                           cfg.low_freq))
+    coefs = numpy.ascontiguousarray(FILTERBANK_COEFFICIENTS, dtype=numpy.float64)
+    Cn = coefs.shape[0]
+    if not isinstance(model, F2CNNModel):
+        model = load_model(model)
+    if not len(wavArrays):
+        return []
+    waves, dts = zip(*[filters._wave_args(w) for w in wavArrays])
+    if len(set(dts)) != 1:
+        raise ValueError("the utterances of one batch must share a sample type (int16 or float64)")
+    B = len(waves)
+    offsets = numpy.zeros(B + 1, numpy.int64)
+    offsets[1:] = numpy.cumsum([w.shape[0] for w in waves])
+    flat = numpy.concatenate(waves)
+    STEP = _step(framerate, cfg)
+    nbs = [max(int(w.shape[0] - cfg.dots_per_input * STEP), 0) for w in waves]
+    if req.hop is not None:
+        nbs = [_lib.strided_window_count(w.shape[0], cfg.radius, STEP, req.hop) for w in waves]
+    n, W, H = sum(nbs), req.map_width, _lib.MEM_HOST
+    scores = numpy.empty((n, 2), numpy.float32)
+    labels = numpy.empty(n, numpy.uint8)
+    levels = track = occ = sal = seg = got = None
+    if req.segments is not None:
+        seg_scale, seg_penalty = Quantise(req.device_hop, STEP, framerate, req.segments['dwell_ms'], req.segments['weight'])
+        ivo, ivb = _segments_sets(req.segments['intervals'], B)
+        seg = dict(path=numpy.empty(n, numpy.uint8), emissions=numpy.empty(n, numpy.int32), runs=numpy.empty((n, 4), numpy.int64),
+                   tally=numpy.zeros((int(ivo[-1]), 4), numpy.int64))
+        seg_wo = numpy.concatenate([[0], numpy.cumsum(nbs)]).astype(numpy.int64)
+    try:
+        front = (model.handle(ctx), flat, dts[0], offsets, coefs, B, Cn, bool(LPF), CUTOFF if LPF else 0.0, FFT_PRECISION, cfg.radius, STEP)
+        if req.saliency is not None or req.occlusion is not None:
+            if req.saliency is not None:
+                sal = dict(bands=req.saliency, map=numpy.empty((B, Cn, W, 3), numpy.float64), summary=numpy.empty((B, Cn, 3), numpy.float64),
+                           levels=numpy.zeros((B, Cn, W), numpy.uint8))
+                got, _ = ctx.eval_saliency_batch(*front, req.device_hop, None, W, 0, sal['levels'], sal['map'], sal['summary'], scores,
+                                                 labels, H)
+            else:
+                spec = req.occlusion
+                patches = OcclusionPatches(cfg.dots_per_input, Cn, spec['band'], spec['stride'], spec['row_band'], spec['row_stride'])
+                K = len(patches)
+                occ = dict(patches=patches, fill=numpy.float32(spec['fill']), scores=numpy.empty((n, K + 1, 2), numpy.float32),
+                           labels=numpy.empty((n, K + 1), numpy.uint8), map=numpy.empty((B, K, W, 4), numpy.float64),
+                           summary=numpy.empty((B, K, 4), numpy.float64), levels=numpy.zeros((B, Cn, W), numpy.uint8))
+                got, _ = ctx.eval_occlusion_batch(*front, req.device_hop, patches, occ['fill'], None, W, 0, occ['levels'], occ['map'],
+                                                  occ['summary'], occ['scores'], occ['labels'], H)
+                scores[...], labels[...] = occ['scores'][:, 0], occ['labels'][:, 0]
+            if req.figure_width is not None:       # the figure beside a map: the map call's levels, the track of its scores
+                levels = (sal or occ)['levels']
+                whole = numpy.stack([offsets[:-1] * 0, numpy.diff(offsets)], axis=1)
+                track = ctx.score_track(scores, labels, got, whole, cfg.radius * STEP, req.device_hop, W,
+                                        numpy.empty((B, W, 5), numpy.float64), H)
+        elif req.figure_width is not None:
+            levels = numpy.zeros((B, Cn, req.figure_width), numpy.uint8)
+            track = numpy.empty((B, req.figure_width, 5), numpy.float64)
+            got, _ = ctx.eval_figure_batch(*front, req.device_hop, None, req.figure_width, 0, levels, track, scores, labels, H)
+        elif seg is not None:
+            got, seg['value'], seg['run_offsets'] = ctx.eval_segments_batch(
+                *front, req.device_hop, seg_scale, seg_penalty, ivo, ivb, scores, labels, seg['path'], seg['emissions'], seg['runs'],
+                seg['tally'], H)
+        elif req.hop is not None:
+            got = ctx.eval_batch_strided(*front, req.hop, scores, labels, H)
+        else:
+            ctx.eval_batch(*front, scores, labels, H)
+        assert got is None or list(numpy.diff(got)) == nbs
+        if seg is not None and 'value' not in seg:     # beside a figure or a map: the three stage calls on its scores
+            seg['value'] = ctx.decision_path(scores, seg_wo, seg_scale, seg_penalty, seg['path'], H, emissions=seg['emissions'])
+            seg['run_offsets'] = ctx.decision_runs(seg['path'], seg['emissions'], seg_wo, seg['runs'], len(seg['runs']), H)
+            ctx.interval_tally(labels, seg['path'], seg['emissions'], seg_wo, ivo, ivb, cfg.radius * STEP, req.device_hop, seg['tally'], H)
+    except _lib.F2Error as e:
+        if e.code == _lib.F2_ERR_NONPOSITIVE:
+            raise ValueError("values must all be positive")
+        raise
+    out, pos = [], 0
+    for b, nb in enumerate(nbs):
+        rows = slice(pos, pos + nb)
+        one = _Evaluated(scores[rows], labels[rows], None if levels is None else levels[b], None if track is None else track[b],
+                         None, None, None)
+        if occ is not None:
+            one = one._replace(occlusion=dict(patches=occ['patches'], fill=occ['fill'], scores=occ['scores'][rows],
+                                              summary=occ['summary'][b], map=occ['map'][b], levels=occ['levels'][b]))
+        if sal is not None:
+            one = one._replace(saliency=dict(bands=sal['bands'], summary=sal['summary'][b], map=sal['map'][b], levels=sal['levels'][b]))
+        if seg is not None:
+            ro = seg['run_offsets']
+            one = one._replace(segments=dict(
+                path=seg['path'][rows], emissions=seg['emissions'][rows], runs=seg['runs'][ro[b]:ro[b + 1]], value=seg['value'][b],
+                tally=seg['tally'][ivo[b]:ivo[b + 1]], intervals=ivb[ivo[b]:ivo[b + 1]], logit_scale=seg_scale, penalty=seg_penalty,
+                hop=req.device_hop))
+        out.append(one)
+        pos += nb
+    return out
+
+
 def EvaluateWavArrays(wavArrays, framerate, model='last_trained_model', LPF=False, CUTOFF=100,
                       FILTERBANK_COEFFICIENTS=None, ctx=None, hop=None, figure_width=None, occlusion=None,
                       occlusion_width=None, saliency=None, saliency_width=None, segments=None):
@@ -625,138 +705,97 @@ def EvaluateWavArrays(wavArrays, framerate, model='last_trained_model', LPF=Fals
     value, tally (k, 4), intervals, logit_scale, penalty, hop. Alone the pass is f2_eval_segments_batch; together with a figure or
     a map it is f2_decision_path, f2_decision_runs and f2_interval_tally on the scores that pass returns. Scores and labels are
     those without it, the same bits."""
-    if occlusion is not None and saliency is not None:
-        raise ValueError("one map per pass: occlusion= or saliency=, not both")
-    ctx = ctx or _lib.default_context()
-    cfg = F2Config()
-    if FILTERBANK_COEFFICIENTS is None:
-        FILTERBANK_COEFFICIENTS = filters.make_erb_filters(framerate, filters.centre_freqs(framerate, cfg.nchannels,
-                                                                                           cfg.low_freq))
-    coefs = numpy.ascontiguousarray(FILTERBANK_COEFFICIENTS, dtype=numpy.float64)
-    Cn = coefs.shape[0]
-    if not isinstance(model, F2CNNModel):
-        model = load_model(model)
-    if not len(wavArrays):
-        return []
-    waves, dts = zip(*[filters._wave_args(w) for w in wavArrays])
-    if len(set(dts)) != 1:
-        raise ValueError("the utterances of one batch must share a sample type (int16 or float64)")
-    offsets = numpy.zeros(len(waves) + 1, numpy.int64)
-    offsets[1:] = numpy.cumsum([w.shape[0] for w in waves])
-    flat = numpy.concatenate(waves)
-    STEP = _step(framerate, cfg)
-    nbs = [max(int(w.shape[0] - cfg.dots_per_input * STEP), 0) for w in waves]
-    if hop is not None:
-        nbs = [_lib.strided_window_count(w.shape[0], cfg.radius, STEP, hop) for w in waves]
-    scores = numpy.empty((sum(nbs), 2), numpy.float32)
-    labels = numpy.empty(sum(nbs), numpy.uint8)
-    levels = track = occ = sal = seg = None
-    if segments is not None:
-        spec = _segments_spec(segments)
-        seg_hop = 1 if hop is None else hop
-        seg_scale, seg_penalty = Quantise(seg_hop, STEP, framerate, spec['dwell_ms'], spec['weight'])
-        ivo, ivb = _segments_sets(spec['intervals'], len(waves))
-        seg = dict(path=numpy.empty(sum(nbs), numpy.uint8), emissions=numpy.empty(sum(nbs), numpy.int32),
-                   runs=numpy.empty((sum(nbs), 4), numpy.int64), tally=numpy.zeros((int(ivo[-1]), 4), numpy.int64))
-        seg_wo = numpy.concatenate([[0], numpy.cumsum(nbs)]).astype(numpy.int64)
-    try:
-        if saliency is not None:
-            B = len(waves)
-            W = int(saliency_width or figure_width or FIGURE_WIDTH)
-            step_hop = 1 if hop is None else hop
-            sal = dict(bands=_saliency_bands(saliency), map=numpy.empty((B, Cn, W, 3), numpy.float64),
-                       summary=numpy.empty((B, Cn, 3), numpy.float64), levels=numpy.zeros((B, Cn, W), numpy.uint8))
-            got, _ = ctx.eval_saliency_batch(model.handle(ctx), flat, dts[0], offsets, coefs, B, Cn, bool(LPF), CUTOFF if LPF else 0.0,
-                                             FFT_PRECISION, cfg.radius, STEP, step_hop, None, W, 0, sal['levels'], sal['map'],
-                                             sal['summary'], scores, labels, _lib.MEM_HOST)
-            assert list(numpy.diff(got)) == nbs
-            if figure_width is not None:
-                levels = sal['levels']
-                whole = numpy.stack([offsets[:-1] * 0, numpy.diff(offsets)], axis=1)
-                track = ctx.score_track(scores, labels, got, whole, cfg.radius * STEP, step_hop, W, numpy.empty((B, W, 5), numpy.float64),
-                                        _lib.MEM_HOST)
-        elif occlusion is not None:
-            spec = _occlusion_spec(occlusion)
-            patches = OcclusionPatches(cfg.dots_per_input, Cn, spec['band'], spec['stride'], spec['row_band'], spec['row_stride'])
-            K, B = len(patches), len(waves)
-            W = int(occlusion_width or figure_width or FIGURE_WIDTH)
-            step_hop = 1 if hop is None else hop
-            occ = dict(patches=patches, fill=numpy.float32(spec['fill']), scores=numpy.empty((sum(nbs), K + 1, 2), numpy.float32),
-                       labels=numpy.empty((sum(nbs), K + 1), numpy.uint8), map=numpy.empty((B, K, W, 4), numpy.float64),
-                       summary=numpy.empty((B, K, 4), numpy.float64), levels=numpy.zeros((B, Cn, W), numpy.uint8))
-            got, _ = ctx.eval_occlusion_batch(model.handle(ctx), flat, dts[0], offsets, coefs, B, Cn, bool(LPF), CUTOFF if LPF else 0.0,
-                                              FFT_PRECISION, cfg.radius, STEP, step_hop, patches, occ['fill'], None, W, 0, occ['levels'],
-                                              occ['map'], occ['summary'], occ['scores'], occ['labels'], _lib.MEM_HOST)
-            assert list(numpy.diff(got)) == nbs
-            scores[...], labels[...] = occ['scores'][:, 0], occ['labels'][:, 0]
-            if figure_width is not None:
-                levels = occ['levels']
-                whole = numpy.stack([offsets[:-1] * 0, numpy.diff(offsets)], axis=1)
-                track = ctx.score_track(scores, labels, got, whole, cfg.radius * STEP, step_hop, W, numpy.empty((B, W, 5), numpy.float64),
-                                        _lib.MEM_HOST)
-        elif figure_width is not None:
-            levels = numpy.zeros((len(waves), Cn, int(figure_width)), numpy.uint8)
-            track = numpy.empty((len(waves), int(figure_width), 5), numpy.float64)
-            got, _ = ctx.eval_figure_batch(model.handle(ctx), flat, dts[0], offsets, coefs, len(waves), Cn, bool(LPF),
-                                           CUTOFF if LPF else 0.0, FFT_PRECISION, cfg.radius, STEP, 1 if hop is None else hop,
-                                           None, int(figure_width), 0, levels, track, scores, labels, _lib.MEM_HOST)
-            assert list(numpy.diff(got)) == nbs
-        elif seg is not None:
-            got, seg['value'], seg['run_offsets'] = ctx.eval_segments_batch(
-                model.handle(ctx), flat, dts[0], offsets, coefs, len(waves), Cn, bool(LPF), CUTOFF if LPF else 0.0, FFT_PRECISION,
-                cfg.radius, STEP, seg_hop, seg_scale, seg_penalty, ivo, ivb, scores, labels, seg['path'], seg['emissions'], seg['runs'],
-                seg['tally'], _lib.MEM_HOST)
-            assert list(numpy.diff(got)) == nbs
-        elif hop is not None:
-            got = ctx.eval_batch_strided(model.handle(ctx), flat, dts[0], offsets, coefs, len(waves), Cn, bool(LPF),
-                                         CUTOFF if LPF else 0.0, FFT_PRECISION, cfg.radius, STEP, hop, scores, labels,
-                                         _lib.MEM_HOST)
-            assert list(numpy.diff(got)) == nbs
+    req = _Request.of(hop, figure_width, saliency_width if occlusion is None else occlusion_width, occlusion, saliency, segments)
+    return [(e.scores, e.labels) + (() if e.levels is None else (e.levels, e.track))
+            + tuple(d for d in (e.occlusion, e.saliency, e.segments) if d is not None)
+            for e in _evaluate_arrays(wavArrays, framerate, req, model, LPF, CUTOFF, FILTERBANK_COEFFICIENTS, ctx)]
+
+
+def _evaluate_group(files, loaded, req, model, LPF, CUTOFF, coefs, verbose=False):
+    """The files of a group - loaded: their (source rate, rate, samples) - evaluated for `req`: (an _Evaluated per file, the names
+    of its phonemes per file - None unless segments are asked for and its .PHN gives some). Files of one rate and one sample type
+    are one batch pass with `coefs`, the filterbank of the configured rate (None: designed for the files' rate); mixed files go
+    one at a time, with `coefs` where the rate is the configured one. A file on its own goes through the batch pass, silently, where
+    req.needs_pass and through EvaluateOneWavArray, with the reference's prints, where not; `verbose` (cnn eval, evalnoise) sends
+    every file without options that way."""
+    rates = [fr for _, fr, _ in loaded]
+    waves = [w for _, _, w in loaded]
+    phonemes = [None] * len(files)
+    if req.segments is not None:
+        phonemes = [_file_phonemes(file, source, fr) for file, (source, fr, _) in zip(files, loaded)]
+    names = [None if p is None else p[0] for p in phonemes]
+
+    def batch_pass(members, c):
+        mine = req
+        if req.segments is not None:
+            mine = req._replace(segments=dict(req.segments, intervals=[None if phonemes[i] is None else phonemes[i][1] for i in members]))
+        return _evaluate_arrays([waves[i] for i in members], rates[members[0]], mine, model, LPF, CUTOFF, c)
+
+    uniform = len(set(rates)) == 1 and len({numpy.asarray(w).dtype for w in waves}) == 1
+    if uniform and (req.needs_pass or not verbose):
+        return batch_pass(list(range(len(files))), coefs), names
+    configured = F2Config().framerate
+    out = []
+    for i, (file, fr, w) in enumerate(zip(files, rates, waves)):
+        c = coefs if uniform or fr == configured else None
+        if req.needs_pass:
+            out += batch_pass([i], c)
         else:
-            ctx.eval_batch(model.handle(ctx), flat, dts[0], offsets, coefs, len(waves), Cn, bool(LPF), CUTOFF if LPF else 0.0,
-                           FFT_PRECISION, cfg.radius, STEP, scores, labels, _lib.MEM_HOST)
-        if seg is not None and 'value' not in seg:     # beside a figure or a map: the three stage calls on its scores
-            seg['value'] = ctx.decision_path(scores, seg_wo, seg_scale, seg_penalty, seg['path'], _lib.MEM_HOST, emissions=seg['emissions'])
-            seg['run_offsets'] = ctx.decision_runs(seg['path'], seg['emissions'], seg_wo, seg['runs'], len(seg['runs']), _lib.MEM_HOST)
-            ctx.interval_tally(labels, seg['path'], seg['emissions'], seg_wo, ivo, ivb, cfg.radius * STEP, seg_hop, seg['tally'],
-                               _lib.MEM_HOST)
-    except _lib.F2Error as e:
-        if e.code == _lib.F2_ERR_NONPOSITIVE:
-            raise ValueError("values must all be positive")
-        raise
-    out, pos = [], 0
-    for b, nb in enumerate(nbs):
-        entry = (scores[pos:pos + nb], labels[pos:pos + nb]) + ((levels[b], track[b]) if figure_width is not None else ())
-        if occ is not None:
-            entry += (dict(patches=occ['patches'], fill=occ['fill'], scores=occ['scores'][pos:pos + nb], summary=occ['summary'][b],
-                           map=occ['map'][b], levels=occ['levels'][b]),)
-        if sal is not None:
-            entry += (dict(bands=sal['bands'], summary=sal['summary'][b], map=sal['map'][b], levels=sal['levels'][b]),)
-        if seg is not None:
-            ro = seg['run_offsets']
-            entry += (dict(path=seg['path'][pos:pos + nb], emissions=seg['emissions'][pos:pos + nb], runs=seg['runs'][ro[b]:ro[b + 1]],
-                           value=seg['value'][b], tally=seg['tally'][ivo[b]:ivo[b + 1]], intervals=ivb[ivo[b]:ivo[b + 1]],
-                           logit_scale=seg_scale, penalty=seg_penalty, hop=seg_hop),)
-        out.append(entry)
-        pos += nb
-    return out
+            out.append(_Evaluated(*EvaluateOneWavArray(w, fr, file, model=model, LPF=LPF, CUTOFF=CUTOFF, FILTERBANK_COEFFICIENTS=c,
+                                                       hop=req.hop), None, None, None, None, None))
+    return out, names
+
+
+def _finish_file(one, file, stem, what, out, N, framerate, source, req, accuracy, resample, keys, names):
+    """The end of a file in cnn eval / evalnoise / evalrand: figure, occlusion map, saliency map, the smoothed decisions' accuracy and
+    the segment tables of its _Evaluated `one`, each where `req` asks for it, then `out`, the .F2CNN.npz. file: whose .FB / .PHN label
+    it (evalnoise: the clean file); stem: of the pictures; what: its name in the segment tables; keys: what the .npz holds already -
+    the accuracy keys, in cnn eval / evalnoise the rate keys too, which then stay in front. Returns every key the .npz gained."""
+    keys = dict(keys)
+    if req.figure_width is not None:
+        keys.update(_write_figure(file, stem, one.levels, one.track, N, framerate, source, keys))
+    if one.occlusion is not None:
+        keys.update(_write_occlusion(file, stem, one.occlusion, N, framerate, source))
+    if one.saliency is not None:
+        keys.update(_write_saliency(file, stem, one.saliency, N, framerate, source))
+    if one.segments is not None:
+        keys.update(_smoothed_accuracy(file, one.segments, accuracy, framerate, source))
+        keys.update(_write_segments(what, one.segments, framerate, names))
+    keys.update(_rate_keys(resample, framerate, source))
+    _save(out, one.scores, one.labels, req.hop, N, framerate, keys)
+    return keys
+
+
+def EvaluateOneWavFile(file, LPF=False, CUTOFF=50, model='last_trained_model', CENTER_FREQUENCIES=None,
+                       FILTERBANK_COEFFICIENTS=None, hop=None, accuracy=None, resample=False, figure=False,
+                       figure_width=FIGURE_WIDTH, occlusion=None, saliency=None, segments=None):
+    """`cnn eval --file X.WAV`: evaluates the file, writes <base>.F2CNN.npz - scores and labels, and what the options of the
+    module's docstring add - and returns (scores, labels)."""
+    print('Using model', model if not isinstance(model, F2CNNModel) else '<in-memory model>')
+    print("File:\t\t{}".format(file))
+    source, framerate, wavArray = _load([file], resample)[0]
+    req = _Request.of_command(hop, figure, figure_width, occlusion, saliency, segments)
+    (one,), (names,) = _evaluate_group([file], [(source, framerate, wavArray)], req, model, LPF, CUTOFF, FILTERBANK_COEFFICIENTS,
+                                       verbose=True)
+    out = os.path.splitext(file)[0] + '.F2CNN.npz'
+    keys = _scored_extra(file, one.labels, accuracy, hop, framerate, source, resample)
+    _finish_file(one, file, os.path.splitext(os.path.basename(file))[0], file, out, len(wavArray), framerate, source, req, accuracy,
+                 resample, keys, names)
+    rising = int(one.labels.sum())
+    print("\t\t{}\tdone ! {} windows: {} rising, {} falling -> {}".format(file, len(one.labels), rising,
+                                                                          len(one.labels) - rising, out))
+    return one.scores, one.labels
 
 
 def EvaluateRandom(count=None, LPF=False, CUTOFF=50, model='last_trained_model', hop=None, accuracy=None, resample=False,
                    figure=False, figure_width=FIGURE_WIDTH, occlusion=None, saliency=None, segments=None):
-    """(with segments= every file's transitions as EvaluateOneWavFile prints and stores them, a group of files decoded in the
-    group's device pass)
-    `cnn evalrand`: evaluate the WAV files under resources/f2cnn/*/ in random order (all of them, or `count`
+    """`cnn evalrand`: evaluate the WAV files under resources/f2cnn/*/ in random order (all of them, or `count`
     drawn with replacement like numpy.random.choice in the reference). The filterbank is designed once and the model
-    is uploaded once (the reference reloads the Keras model for every file). With a hop each group of files is one
-    strided call. With accuracy= every file that has its .FB / .PHN is scored against them - a group in one device pass - and
-    the corpus total is printed from the summed confusion matrices. With resample= a group of files is brought to the
-    configured framerate first (a file whose rate differed is left out of the accuracy). With figure= each group of files is
-    one f2_eval_figure_batch call and every file gets its figure, as EvaluateOneWavFile writes it. With occlusion= each group
-    is one f2_eval_occlusion_batch call, every file gets its table, map and .npz keys, and the corpus table is printed at the
-    end: counts summed, means weighted by rows (CombineOcclusionSummaries). With saliency= each group is one
-    f2_eval_saliency_batch call, every file gets its table, map and .npz keys, and the corpus table is printed at the end
-    (CombineSaliencySummaries)."""
+    is uploaded once (the reference reloads the Keras model for every file). Files go to the device in groups of 16, a group of
+    one rate and one sample type in one pass (_evaluate_group); every file gets what EvaluateOneWavFile writes and prints for it
+    under the options of the module's docstring. With accuracy= a group is scored in one device pass per rate and the corpus total
+    is printed from the summed confusion matrices; with occlusion= / saliency= the table of the corpus is printed at the end,
+    counts summed and means weighted by rows (CombineOcclusionSummaries, CombineSaliencySummaries)."""
     import glob
     import time
     TotalTime = time.time()
@@ -782,75 +821,44 @@ def EvaluateRandom(count=None, LPF=False, CUTOFF=50, model='last_trained_model',
     occlusion_corpus = []                         # (patches, hz, summary) per file
     saliency_corpus = []                          # (framerate, summary) per file
     BATCH = 16                                    # files per device pass
+    req = _Request.of_command(hop, figure, figure_width, occlusion, saliency, segments)
     for s0 in range(0, len(wavFiles), BATCH):
         group = wavFiles[s0:s0 + BATCH]
-        sources, loaded = zip(*[(source, (fr, w)) for source, fr, w in _load(group, resample)])
-        rates = {fr for fr, _ in loaded}
-        file_segments = [(None, None)] * len(group)
-        if segments is not None:
-            file_segments = [_file_segments(segments, file, source, fr) for file, source, (fr, _) in zip(group, sources, loaded)]
-        group_segments = None if segments is None else dict(file_segments[0][0], intervals=[fs['intervals'][0] for fs, _ in file_segments])
-        if len(rates) == 1 and len({numpy.asarray(w).dtype for _, w in loaded}) == 1:
-            outs = EvaluateWavArrays([w for _, w in loaded], loaded[0][0], model=model, LPF=LPF, CUTOFF=CUTOFF,
-                                     FILTERBANK_COEFFICIENTS=FILTERBANK_COEFFICIENTS, hop=hop,
-                                     figure_width=figure_width if figure else None, occlusion=occlusion,
-                                     occlusion_width=figure_width, saliency=saliency, saliency_width=figure_width,
-                                     segments=group_segments)
-        elif figure or occlusion is not None or saliency is not None or segments is not None:     # mixed files: one at a time
-            outs = [EvaluateWavArrays([w], fr, model=model, LPF=LPF, CUTOFF=CUTOFF,
-                                      FILTERBANK_COEFFICIENTS=FILTERBANK_COEFFICIENTS if fr == cfg.framerate else None, hop=hop,
-                                      figure_width=figure_width if figure else None, occlusion=occlusion,
-                                      occlusion_width=figure_width, saliency=saliency, saliency_width=figure_width, segments=fs)[0]
-                    for (fr, w), (fs, _) in zip(loaded, file_segments)]
-        else:                                     # mixed files: one at a time
-            outs = [EvaluateOneWavArray(w, fr, file, model=model, LPF=LPF, CUTOFF=CUTOFF,
-                                        FILTERBANK_COEFFICIENTS=FILTERBANK_COEFFICIENTS if fr == cfg.framerate else None,
-                                        hop=hop)
-                    for file, (fr, w) in zip(group, loaded)]
-        extras = [None] * len(group)
+        loaded = _load(group, resample)
+        outs, phoneme_names = _evaluate_group(group, loaded, req, model, LPF, CUTOFF, FILTERBANK_COEFFICIENTS)
+        extras = [{} for _ in group]
         if accuracy is not None:
-            refs = [ReferenceLabels(file) if source == fr else None for file, source, (fr, _) in zip(group, sources, loaded)]
-            for file, ref, source, (fr, _) in zip(group, refs, sources, loaded):
+            refs = [ReferenceLabels(file) if source == fr else None for file, (source, fr, _) in zip(group, loaded)]
+            for file, ref, (source, fr, _) in zip(group, refs, loaded):
                 if source != fr:
                     _no_rate_accuracy(file, source, fr)
                 elif ref is None:
                     _no_side_files(file)
             # one pass per framerate of the group (the step is in samples of the file)
-            for rate in sorted({fr for (fr, _), ref in zip(loaded, refs) if ref is not None}):
-                members = [i for i, ((fr, _), ref) in enumerate(zip(loaded, refs)) if fr == rate and ref is not None]
-                wo = numpy.concatenate([[0], numpy.cumsum([len(outs[i][1]) for i in members])]).astype(numpy.int64)
-                confusions = _confusions(_lib.default_context(), numpy.concatenate([outs[i][1] for i in members]), wo,
+            for rate in sorted({fr for (_, fr, _), ref in zip(loaded, refs) if ref is not None}):
+                members = [i for i, ((_, fr, _), ref) in enumerate(zip(loaded, refs)) if fr == rate and ref is not None]
+                wo = numpy.concatenate([[0], numpy.cumsum([len(outs[i].labels) for i in members])]).astype(numpy.int64)
+                confusions = _confusions(_lib.default_context(), numpy.concatenate([outs[i].labels for i in members]), wo,
                                          [refs[i] for i in members], accuracy, hop, _step(rate, cfg))
                 for i, confusion in zip(members, confusions):
                     _print_accuracy(group[i], confusion, accuracy)
                     extras[i] = _accuracy_keys(confusion, accuracy)
                     corpus += confusion
-        for file, source, (fr, w), result, extra, (_, phoneme_names) in zip(group, sources, loaded, outs, extras, file_segments):
-            scores, labels = result[:2]
+        for file, (source, fr, w), one, extra, names in zip(group, loaded, outs, extras, phoneme_names):
             out = os.path.splitext(file)[0] + '.F2CNN.npz'
-            if segments is not None:
-                seg, result = result[-1], result[:-1]
-                extra = dict(extra or {}, **_smoothed_accuracy(file, seg, accuracy, fr, source))
-                extra = dict(extra, **_write_segments(file, seg, fr, phoneme_names))
-            if figure:
-                extra = dict(extra or {}, **_write_figure(file, os.path.splitext(os.path.basename(file))[0], result[2], result[3],
-                                                          len(w), fr, source, extra))
+            keys = _finish_file(one, file, os.path.splitext(os.path.basename(file))[0], file, out, len(w), fr, source, req, accuracy,
+                                resample, extra, names)
             if occlusion is not None:
-                extra = dict(extra or {}, **_write_occlusion(file, os.path.splitext(os.path.basename(file))[0], result[-1], len(w), fr,
-                                                             source))
-                if occlusion_corpus and not numpy.array_equal(occlusion_corpus[0][0], extra['occlusion_patches']):
+                if occlusion_corpus and not numpy.array_equal(occlusion_corpus[0][0], keys['occlusion_patches']):
                     occlusion_corpus = None       # (files of another channel count: no common table)
                 if occlusion_corpus is not None:
-                    occlusion_corpus.append((extra['occlusion_patches'], extra['occlusion_hz'], extra['occlusion_summary']))
+                    occlusion_corpus.append((keys['occlusion_patches'], keys['occlusion_hz'], keys['occlusion_summary']))
             if saliency is not None:
-                extra = dict(extra or {}, **_write_saliency(file, os.path.splitext(os.path.basename(file))[0], result[-1], len(w), fr,
-                                                            source))
-                saliency_corpus.append((fr, extra['saliency_summary']))
-            _save(out, scores, labels, hop, len(w), fr, dict(extra or {}, **_rate_keys(resample, fr, source)) or None)
-            rising = int(labels.sum())
-            print("\t\t{}\tdone ! {} windows: {} rising, {} falling -> {}".format(file, len(labels), rising,
-                                                                                  len(labels) - rising, out))
-            results[file] = (scores, labels)
+                saliency_corpus.append((fr, keys['saliency_summary']))
+            rising = int(one.labels.sum())
+            print("\t\t{}\tdone ! {} windows: {} rising, {} falling -> {}".format(file, len(one.labels), rising,
+                                                                                  len(one.labels) - rising, out))
+            results[file] = (one.scores, one.labels)
     print("Evaluating network on all files.")
     if accuracy is not None:
         _print_accuracy("all files", corpus, accuracy)
@@ -860,8 +868,7 @@ def EvaluateRandom(count=None, LPF=False, CUTOFF=50, model='last_trained_model',
             print(line)
     if saliency is not None and saliency_corpus and len({(fr, len(summary)) for fr, summary in saliency_corpus}) == 1:
         cf = numpy.asarray(filters.centre_freqs(saliency_corpus[0][0], len(saliency_corpus[0][1]), cfg.low_freq), numpy.float64)
-        for line in SaliencyTable("all files", cf, CombineSaliencySummaries([summary for _, summary in saliency_corpus]),
-                                  _saliency_bands(saliency)):
+        for line in SaliencyTable("all files", cf, CombineSaliencySummaries([summary for _, summary in saliency_corpus]), req.saliency):
             print(line)
     print('              Total time:', time.time() - TotalTime)
     print('')
@@ -895,16 +902,13 @@ def add_gaussian_noise(wave, SNRdB, rng=None):
 def EvaluateWithNoise(file, LPF=False, CUTOFF=100, model='last_trained_model', CENTER_FREQUENCIES=None,
                       FILTERBANK_COEFFICIENTS=None, SNRdB=-3, rng=None, hop=None, accuracy=None, resample=False, figure=False,
                       figure_width=FIGURE_WIDTH, occlusion=None, saliency=None, segments=None):
-    """(with segments= the noisy run's transitions as EvaluateOneWavFile prints and stores them, its phonemes those of the clean file)
-    `cnn evalnoise` (reference: scripts/CNN/Evaluating.py:193-221): the file plus Gaussian noise at the requested level is
+    """`cnn evalnoise` (reference: scripts/CNN/Evaluating.py:193-221): the file plus Gaussian noise at the requested level is
     written next to copies of its annotation files under OutputWavFiles/addedNoise/ and the float64 waveform is evaluated by
     the device pipeline. Returns (scores, labels) and also leaves them in <target>.F2CNN.npz; `rng` (a numpy Generator or
-    RandomState) makes the noise reproducible - the reference draws from the global numpy state. With accuracy= the noisy
-    run is scored against the labels of the clean file's .FB / .PHN (what the copies under addedNoise/ are there for). With
-    resample= the noise is added to the resampled, one-channel signal and the noisy WAV is written at the configured framerate.
-    With figure= the noisy run's figure goes to graphs/FallingOrRising/<noisy stem>.png, its overlays from the clean file's
-    side files. With occlusion= the noisy run's occlusion table, .npz keys and graphs/Occlusion/<noisy stem>.png; with saliency=
-    its saliency table, .npz keys and graphs/Saliency/<noisy stem>.png."""
+    RandomState) makes the noise reproducible - the reference draws from the global numpy state. With resample= the noise is
+    added to the resampled, one-channel signal and the noisy WAV is written at the configured framerate. The options of the
+    module's docstring apply to the noisy run: pictures and tables carry the noisy file's name, and labels, formant, slope and
+    phonemes are those of the clean file's .FB / .PHN (what the copies under addedNoise/ are there for)."""
     import shutil
     from scipy.io import wavfile
     print("File:\t\t{}".format(file))
@@ -919,41 +923,14 @@ def EvaluateWithNoise(file, LPF=False, CUTOFF=100, model='last_trained_model', C
         if os.path.exists(source + ext):
             shutil.copyfile(source + ext, target + ext)
     print('New noisy WAVE file saved as', target + '.WAV')
-    occ = sal = seg = None
-    if segments is not None:
-        segments, phoneme_names = _file_segments(segments, file, source_rate, framerate)
-    if figure or occlusion is not None or saliency is not None or segments is not None:
-        result = EvaluateWavArrays([noisy], framerate, model=model, LPF=LPF, CUTOFF=CUTOFF,
-                                   FILTERBANK_COEFFICIENTS=FILTERBANK_COEFFICIENTS, hop=hop,
-                                   figure_width=figure_width if figure else None, occlusion=occlusion, occlusion_width=figure_width,
-                                   saliency=saliency, saliency_width=figure_width, segments=segments)[0]
-        scores, labels = result[:2]
-        if segments is not None:
-            seg, result = result[-1], result[:-1]
-        if figure:
-            levels, track = result[2:4]
-        if occlusion is not None:
-            occ = result[-1]
-        if saliency is not None:
-            sal = result[-1]
-    else:
-        scores, labels = EvaluateOneWavArray(noisy, framerate, target + '.WAV', model=model, LPF=LPF, CUTOFF=CUTOFF,
-                                             CENTER_FREQUENCIES=CENTER_FREQUENCIES,
-                                             FILTERBANK_COEFFICIENTS=FILTERBANK_COEFFICIENTS, hop=hop)
-    extra = _scored_extra(file, labels, accuracy, hop, framerate, source_rate, resample)
-    if figure:
-        extra = dict(extra or {}, **_write_figure(file, os.path.basename(target), levels, track, len(noisy), framerate, source_rate,
-                                                  extra))
-    if occ is not None:
-        extra = dict(extra or {}, **_write_occlusion(file, os.path.basename(target), occ, len(noisy), framerate, source_rate))
-    if sal is not None:
-        extra = dict(extra or {}, **_write_saliency(file, os.path.basename(target), sal, len(noisy), framerate, source_rate))
-    if seg is not None:
-        extra = dict(extra or {}, **_smoothed_accuracy(file, seg, accuracy, framerate, source_rate))
-        extra = dict(extra, **_write_segments(target + '.WAV', seg, framerate, phoneme_names))
-    _save(target + '.F2CNN.npz', scores, labels, hop, len(noisy), framerate, extra)
+    req = _Request.of_command(hop, figure, figure_width, occlusion, saliency, segments)
+    (one,), (names,) = _evaluate_group([file], [(source_rate, framerate, noisy)], req, model, LPF, CUTOFF, FILTERBANK_COEFFICIENTS,
+                                       verbose=True)
+    keys = _scored_extra(file, one.labels, accuracy, hop, framerate, source_rate, resample)
+    _finish_file(one, file, os.path.basename(target), target + '.WAV', target + '.F2CNN.npz', len(noisy), framerate, source_rate, req,
+                 accuracy, resample, keys, names)
     print("\t\t{}\tdone !".format(file))
-    return scores, labels
+    return one.scores, one.labels
 
 
 # ---- the robustness sweeps: a file at K levels of one axis (noise, envelope cutoff, room) and at the unchanged level, the

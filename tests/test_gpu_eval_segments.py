@@ -228,3 +228,32 @@ def test_evalnoise_and_evalrand_take_segments(corpus, monkeypatch, capsys):
         if k.startswith("segments_"):
             assert again[k].tobytes() == single[k].tobytes(), k
     assert "segments_confusion" in again
+
+
+def test_evalrand_mixed_group_with_options_equals_eval(tmp_path, monkeypatch, capsys):
+    """a group of two rates goes through the batch pass file by file: with segments and a figure every file's .npz is, byte for byte,
+    the one `cnn eval` writes for it alone. 4000 samples at 16 kHz and 2000 at 8 kHz (STEP 80): 14 and 7 rows at the hop."""
+    from scipy.io import wavfile
+    from f2cnn_amd import config, wavio
+    from f2cnn_amd.scripts.CNN import Evaluating
+    monkeypatch.chdir(tmp_path)
+    config.write_default(str(tmp_path / "configF2CNN.conf"))
+    folder = tmp_path / "resources" / "f2cnn" / "TEST"
+    os.makedirs(folder)
+    files = [os.path.join("resources", "f2cnn", "TEST", name) for name in ("WIDE.WAV", "NARROW.WAV")]
+    wavio.write_sphere(files[0], 16000, orc.synth_utterance(31, 4000))
+    wavfile.write(files[1], 8000, orc.synth_utterance(32, 2000).astype(np.int16))
+    model = F2CNNModel(orc.glorot_weights(7))
+    keywords = dict(model=model, hop=160, segments=True, figure=True, figure_width=64)
+    alone = {}
+    for file in files:
+        Evaluating.EvaluateOneWavFile(file, **keywords)
+        alone[file] = dict(np.load(os.path.splitext(file)[0] + ".F2CNN.npz"))
+        os.remove(os.path.splitext(file)[0] + ".F2CNN.npz")
+    results = Evaluating.EvaluateRandom(**keywords)
+    assert sorted(results) == sorted(files)
+    for file, rows in zip(files, (14, 7)):
+        grouped = dict(np.load(os.path.splitext(file)[0] + ".F2CNN.npz"))
+        assert set(grouped) == set(alone[file]) and len(grouped["labels"]) == rows and "segments_path" in grouped and "figure_track" in grouped
+        for key, value in alone[file].items():
+            assert grouped[key].dtype == value.dtype and grouped[key].tobytes() == value.tobytes(), (file, key)
