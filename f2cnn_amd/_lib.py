@@ -29,6 +29,9 @@ SMEAR_TILE_SAMPLES, SMEAR_TILE_CHANNELS, SMEAR_MAX_CHANNELS, SMEAR_MAX_LEVELS = 
 # tile constant of k_shaped_noise_levels (csrc/f2_internal.h: F2_SHAPED_BLOCK outputs per workgroup) and the longest filter and the most
 # levels f2_shaped_noise_levels takes (F2_SHAPED_MAX_TAPS, F2_SHAPED_MAX_LEVELS)
 SHAPED_BLOCK, SHAPED_MAX_TAPS, SHAPED_MAX_LEVELS = 1024, 2048, 64
+# the most recordings and levels the masker calls take and the longest recording (csrc/f2_internal.h: F2_MASKER_MAX_RECORDINGS,
+# F2_MASKER_MAX_LEVELS, F2_MASKER_MAX_SAMPLES), the threads of their fixed-order sum, and the second counter word of the segment draw
+MASKER_MAX_RECORDINGS, MASKER_MAX_LEVELS, MASKER_MAX_SAMPLES, MASKER_SUM_THREADS, MASKER_STREAM = 64, 64, 1 << 26, 1024, 0x4D41534B
 # the decoding kernels of f2_decision_path (include/f2cnn_hip.h): F2_PATH_TILE rows per workgroup, F2_PATH_SCAN_CHUNK tile products per
 # step of the per-utterance scans; the largest logit_scale and penalty the call takes
 PATH_TILE, PATH_SCAN_CHUNK, PATH_MAX_SCALE, PATH_MAX_PENALTY = 1024, 256, float(1 << 20), 1 << 40
@@ -131,6 +134,14 @@ SIGNATURES = {
     "f2_input_batch_smeared": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i, _i, _d, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp,
                                     _i, _vp, C.c_uint32, C.c_uint64, _vp, _i, _vp, _vp, _i]),
     "f2_trainer_render_smeared": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, C.c_uint64, _vp, _i, _vp]),
+    "f2_masker_levels": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _i, _vp, _i, C.c_uint64, _vp, _vp, _vp, _vp, _i]),
+    "f2_eval_masker_sweep": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _d, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _i, C.c_uint64, _vp,
+                                  _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i]),
+    "f2_masker_pick": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _i, _vp, _i, _vp, C.c_uint32, C.c_uint64, _vp, _vp, _vp, _vp, _i]),
+    "f2_input_batch_masked": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i, _i, _d, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp,
+                                   _i, _vp, C.c_uint32, C.c_uint64, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _i]),
+    "f2_trainer_render_masked": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, C.c_uint64, _vp, _i, _vp, _vp, _vp, _vp, _i,
+                                      _vp, _i, _vp]),
     "f2_decision_path": (_i, [_vp, _vp, _vp, _i, _d, _i64, _vp, _vp, _vp, _i]),
     "f2_decision_runs": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _i64, _i]),
     "f2_interval_tally": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i64, _i, _vp, _i]),
@@ -479,6 +490,62 @@ class Context:
         """input_batch_coloured whose gather is gather_windows_mixed: room, noise, envelopes, then the windows of utterance b
         through mixes[mix_of[b]], nothing leaving the device; mixes None: input_batch_coloured. See f2_input_batch_smeared."""
         self._input_batch_staged("smeared", locals())
+
+    def input_batch_masked(self, wave, wave_dtype, offsets, coefs, B, Cn, lpf, cutoff, precision, center_offsets, centers, radius,
+                           step, normalize, rirs, room_of, snr_db, firs, level_of, first_utterance, seed, mixes, mix_of, maskers,
+                           masker_of, masker_snrs, masker_level_of, windows, mem_space):
+        """input_batch_smeared with a recorded masker per utterance between the room and the noise: utterance b under the recording
+        maskers[masker_of[l]] at masker_snrs[l], l = masker_level_of[b], or none where l == len(masker_snrs); maskers None:
+        input_batch_smeared. See f2_input_batch_masked."""
+        self._input_batch_staged("masked", locals())
+
+    def masker_pick(self, wave, wave_dtype, offsets, B, snr_db, maskers, masker_of, level_of, first_utterance, seed, noisy, mem_space,
+                    small=False):
+        """The batch with one masker level per utterance (see f2_masker_pick): utterance b under the recording maskers[masker_of[l]]
+        (a sequence of 1-D float64 arrays, always host arrays) at snr_db[l], l = level_of[b], or clean where l == len(snr_db);
+        level_of None: all clean. wave / noisy are numpy arrays or device pointers, by mem_space. small: also return (sigma, gain,
+        start), B values each."""
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        snr, lev = _noise_levels(snr_db, level_of)
+        samples, moff, mof = _maskers(maskers, masker_of, len(snr))
+        out = (np.zeros(int(B), np.float64), np.zeros(int(B), np.float64), np.zeros(int(B), np.int64)) if small else (None, None, None)
+        self.check(self.lib.f2_masker_pick(self.handle, _ptr(wave), wave_dtype, _ptr(offsets), int(B), _ptr(snr) if len(snr) else None,
+                                           _ptr(samples), _ptr(moff), len(moff) - 1 if moff is not None else 0, _ptr(mof), len(snr),
+                                           _ptr(lev), int(first_utterance), int(seed) & (2 ** 64 - 1), _ptr(noisy), _ptr(out[0]),
+                                           _ptr(out[1]), _ptr(out[2]), mem_space))
+        return out if small else None
+
+    def masker_levels(self, wave, wave_dtype, offsets, B, snr_db, maskers, masker_of, seed, noisy, mem_space):
+        """The batch under recorded maskers at every level and clean, in one device pass (see f2_masker_levels): level l is the
+        recording maskers[masker_of[l]] at snr_db[l]. noisy receives (K+1) * offsets[B] float64, level-major, the clean level last.
+        Returns (sigma, gain, start), (K+1)*B values each, level-major."""
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        snr = np.ascontiguousarray(snr_db, dtype=np.float64).reshape(-1)
+        samples, moff, mof = _maskers(maskers, masker_of, len(snr))
+        U = (len(snr) + 1) * int(B)
+        sigma, gain, start = np.zeros(U, np.float64), np.zeros(U, np.float64), np.zeros(U, np.int64)
+        self.check(self.lib.f2_masker_levels(self.handle, _ptr(wave), wave_dtype, _ptr(offsets), int(B), _ptr(snr) if len(snr) else None,
+                                             _ptr(samples), _ptr(moff), len(moff) - 1, _ptr(mof), len(snr), int(seed) & (2 ** 64 - 1),
+                                             _ptr(noisy), _ptr(sigma), _ptr(gain), _ptr(start), mem_space))
+        return sigma, gain, start
+
+    def eval_masker_sweep(self, handle, wave, wave_dtype, offsets, coefs, B, Cn, lpf, cutoff, precision, radius, step, hop, snr_db,
+                          maskers, masker_of, seed, noisy, scores, labels, mem_space, window_offsets=None, sigma=None, stats=None):
+        """eval_noise_sweep with a recorded masker per level (see f2_eval_masker_sweep): level l is the batch under the recording
+        maskers[masker_of[l]] at snr_db[l], the clean level last. Returns (window_offsets, sigma, stats, gain, start): the first
+        three as eval_noise_sweep does, gain (float64) and start (int64) of (K+1)*B, level-major."""
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        snr = np.ascontiguousarray(snr_db, dtype=np.float64).reshape(-1)
+        samples, moff, mof = _maskers(maskers, masker_of, len(snr))
+        U = (len(snr) + 1) * int(B)
+        window_offsets, stats, sigma = _sweep_outputs(U, window_offsets, stats, sigma, True)
+        gain, start = np.zeros(U, np.float64), np.zeros(U, np.int64)
+        self.check(self.lib.f2_eval_masker_sweep(self.handle, handle, _ptr(wave), wave_dtype, _ptr(offsets), _ptr(coefs), int(B), Cn,
+                                                 int(bool(lpf)), float(cutoff), precision, radius, step, int(hop),
+                                                 _ptr(snr) if len(snr) else None, _ptr(samples), _ptr(moff), len(moff) - 1, _ptr(mof),
+                                                 len(snr), int(seed) & (2 ** 64 - 1), _ptr(noisy), _ptr(scores), _ptr(labels),
+                                                 _ptr(window_offsets), _ptr(sigma), _ptr(gain), _ptr(start), _ptr(stats), mem_space))
+        return window_offsets, sigma, stats, gain, start
 
     def cnn_create(self, tensors, rows, channels):
         """tensors: 12 contiguous float32 arrays in Keras layouts (see include/f2cnn_hip.h). Returns a handle."""
@@ -990,6 +1057,12 @@ class Context:
         float64), sharp where mix_of[b] == K; mixes None: trainer_render_coloured (see f2_trainer_render_smeared)"""
         self._trainer_render_staged("smeared", locals())
 
+    def trainer_render_masked(self, handle, rirs=(), room_of=None, snr_db=(), firs=None, level_of=None, seed=0, mixes=None,
+                              mix_of=None, channels=None, maskers=None, masker_of=None, masker_snrs=(), masker_level_of=None):
+        """trainer_render_smeared with utterance b under the recording maskers[masker_of[l]] at masker_snrs[l], l =
+        masker_level_of[b], between its room and its noise; maskers None: trainer_render_smeared (see f2_trainer_render_masked)"""
+        self._trainer_render_staged("masked", locals())
+
     def trainer_get_windows(self, handle, first, count, shape):
         """Rows first .. first + count - 1 of the training set: (count, *shape) float32 windows and (count) uint8 labels"""
         x = np.empty((int(count),) + tuple(shape), np.float32)
@@ -1112,6 +1185,18 @@ def _colours(firs, K):
     return (taps if len(taps) else None), fir_offsets
 
 
+def _maskers(maskers, masker_of, K):
+    """(samples, masker_offsets, masker_of as int32) of the masker calls: the recordings one after the other as float64 with their
+    R + 1 offsets, and the recording of each of the K levels; (None, None, None) without recordings"""
+    if maskers is None:
+        return None, None, None
+    samples, masker_offsets = _pack_rirs(maskers)
+    mof = np.ascontiguousarray(masker_of if masker_of is not None else (), dtype=np.int32).reshape(-1)
+    if len(mof) != K:
+        raise ValueError("{} recordings named for {} masker levels (one per level is needed)".format(len(mof), K))
+    return (samples if len(samples) else None), masker_offsets, mof
+
+
 def _rooms(rirs, room_of):
     """(taps, rir_offsets, room_of as int32 or None) for the calls that give every utterance a room of its own"""
     taps, rir_offsets = _pack_rirs(rirs if rirs is not None else ())
@@ -1149,11 +1234,12 @@ _STAGE_KEYS = {"noisy": "snr_db K level_of first_utterance seed".split()}
 _STAGE_KEYS["wet"] = "rir rir_offsets Kr room_of".split() + _STAGE_KEYS["noisy"]
 _STAGE_KEYS["coloured"] = "rir rir_offsets Kr room_of snr_db fir fir_offsets K level_of first_utterance seed".split()
 _STAGE_KEYS["smeared"] = _STAGE_KEYS["coloured"] + "mix Km mix_of".split()
+_STAGE_KEYS["masked"] = _STAGE_KEYS["smeared"] + "masker_snr_db masker masker_offsets R masker_of Kk masker_level_of".split()
 
 
 def _stage_args(keys, v):
     """([the C arguments named by `keys`], what holds their arrays until the call returns) from the Python arguments `v` of a call with
-    augmentation stages: noise levels, colours, rooms, spectral resolutions, marshalled in that order and only where the symbol has
+    augmentation stages: noise levels, colours, rooms, spectral resolutions, maskers, marshalled in that order and only where the symbol has
     them. Arrays become their addresses; counts, first_utterance and seed are plain ints, which _ptr hands through as they are"""
     snr, lev = _noise_levels(v["snr_db"], v["level_of"])
     a = dict(snr_db=snr if len(snr) else None, K=len(snr), level_of=lev, first_utterance=int(v.get("first_utterance", 0)),
@@ -1166,6 +1252,10 @@ def _stage_args(keys, v):
     if "mix" in keys:
         mix, a["mix_of"] = _smears(v["mixes"], v["mix_of"], v.get("Cn", v.get("channels")))
         a.update(mix=mix if len(mix) else None, Km=len(mix))
+    if "masker" in keys:
+        msnr, a["masker_level_of"] = _noise_levels(v["masker_snrs"], v["masker_level_of"])
+        a["masker"], a["masker_offsets"], a["masker_of"] = _maskers(v["maskers"], v["masker_of"], len(msnr))
+        a.update(masker_snr_db=msnr if len(msnr) else None, Kk=len(msnr), R=len(a["masker_offsets"]) - 1 if a["masker_offsets"] is not None else 0)
     return [_ptr(a[k]) for k in keys], a
 
 

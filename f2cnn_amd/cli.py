@@ -43,6 +43,13 @@ package implements:
                                                              before they are normalised; the TEST files are also validated once
                                                              per resolution; combines with every other --augment option; not in
                                                              the reference)
+    python -m f2cnn_amd cnn train --engine hip --from-wav --augment-maskers babble.wav,cafe.wav --augment-masker-snrs 20,10,5 [--augment-snrs ...] [--seed S]
+                                                            (a masker level is a pair (recording, SNR), masker-major over the SNRs
+                                                             as in noisesweep --maskers, at most 64: every epoch each TRAIN file is
+                                                             rendered under a segment of one of the recordings or without, mixed
+                                                             on the device behind the room and before the Gaussian noise; the
+                                                             TEST files are validated once per pair; combines with every other
+                                                             --augment option; not in the reference)
     python -m f2cnn_amd cnn test [--input/-i NPY] [--label/-l CSV] [--model/-m NPZ] [--by set|region|speaker|phoneme] [--rows test|train|all]
                                                             (loss, accuracy and the 2 x 2 counts of a saved model on the labelled
                                                              windows, per value of a label column, in one device pass; writes
@@ -63,6 +70,15 @@ package implements:
                                                              written to OutputWavFiles/addedNoise/<stem>.coloursweep.npz; --colours
                                                              and --noise-taps are refused on every other command; not in the
                                                              reference)
+    python -m f2cnn_amd cnn noisesweep --file/-f WAV --snrs 20,10,0 --maskers babble.wav,cafe.wav [--seed N] [--hop N|frame] [--lpf HZ] [--accuracy [MODE]] [--resample] [--save-wavs]
+                                                            (the same under recorded maskers: a cyclic segment of every recording,
+                                                             drawn per file from the seed, scaled to every level and mixed in on
+                                                             the device - the recording itself with its own modulations, not a
+                                                             Gaussian noise of its spectrum; masker-major, at most 64 levels named
+                                                             like `babble 10dB`, written to
+                                                             OutputWavFiles/addedNoise/<stem>.maskersweep.npz; a recording at
+                                                             another rate needs --resample; not together with --colours; not in
+                                                             the reference)
     python -m f2cnn_amd cnn lpfsweep --file/-f WAV --cutoffs 5,10,20,50,100 [--hop N|frame] [--accuracy [MODE]] [--resample] [--model/-m NPZ]
                                                             (the file at every envelope cutoff and unfiltered in one device pass -
                                                              filterbank and Hilbert envelope run once - agreement with the
@@ -252,6 +268,7 @@ def drr_argument(text):
 NOISE_COLOURS = ('white', 'pink', 'brown', 'speech')     # noise.COLOURS (kept here so that parsing imports nothing)
 NOISE_LEVELS_MAX = 64
 SMEAR_LEVELS_MAX = 64                                    # F2_SMEAR_MAX_LEVELS (likewise)
+MASKER_RECORDINGS_MAX = 64                               # F2_MASKER_MAX_RECORDINGS (likewise; the levels: NOISE_LEVELS_MAX)
 
 
 def colours_argument(text):
@@ -291,6 +308,29 @@ def augment_noise_taps_argument(text):
         return noise_taps_argument(text)
     except argparse.ArgumentTypeError:
         raise argparse.ArgumentTypeError("--augment-noise-taps takes an odd, positive number of taps, not {!r}".format(text))
+
+
+def maskers_argument(text, option='--maskers'):
+    """--maskers: a comma-separated list of at least one recording (RIFF files; read where they are used)"""
+    maskers = text.split(',')
+    if not all(maskers):
+        raise argparse.ArgumentTypeError("{} takes a comma-separated list of recordings, not {!r}".format(option, text))
+    if len(maskers) > MASKER_RECORDINGS_MAX:
+        raise argparse.ArgumentTypeError("{} takes at most {} recordings, not {}".format(option, MASKER_RECORDINGS_MAX, len(maskers)))
+    return maskers
+
+
+def augment_maskers_argument(text):
+    """--augment-maskers: as --maskers"""
+    return maskers_argument(text, '--augment-maskers')
+
+
+def augment_masker_snrs_argument(text):
+    """--augment-masker-snrs: as --augment-snrs"""
+    try:
+        return augment_snrs_argument(text)
+    except argparse.ArgumentTypeError:
+        raise argparse.ArgumentTypeError("--augment-masker-snrs takes a comma-separated list of SNRs in dB, not {!r}".format(text))
 
 
 def build_parser():
@@ -372,6 +412,14 @@ def build_parser():
                         "spectrum of a mono recording at the file's rate), fir:<taps.npy> - every one at every level of --snrs")
     c.add_argument('--noise-taps', action='store', type=noise_taps_argument, dest='noise_taps', default=argparse.SUPPRESS,
                    help="noisesweep --colours: taps of the designed noise filters, odd (default 1025, at most 2047)")
+    c.add_argument('--maskers', action='store', type=maskers_argument, dest='maskers', default=argparse.SUPPRESS,
+                   help="noisesweep: comma-separated recordings (babble, a cafeteria, music; any RIFF at the file's rate, any rate with "
+                        "--resample) mixed in themselves, not as Gaussian noise - every one at every level of --snrs")
+    c.add_argument('--augment-maskers', action='store', type=augment_maskers_argument, dest='augment_maskers', default=argparse.SUPPRESS,
+                   help="train --engine hip --from-wav --augment-masker-snrs: comma-separated recordings, as noisesweep's --maskers; "
+                        "every epoch each file is rendered under a segment of one of them at one of the SNRs, or without")
+    c.add_argument('--augment-masker-snrs', action='store', type=augment_masker_snrs_argument, dest='augment_masker_snrs',
+                   default=argparse.SUPPRESS, help="train --augment-maskers: comma-separated SNRs in dB of the maskers")
     c.add_argument('--seed', action='store', type=int, dest='seed',
                    help="noisesweep: seed of the noise (default 0); train --from-wav: seed of the weights, the order and the noise")
     c.add_argument('--save-wavs', action='store_true', dest='save_wavs',
@@ -495,7 +543,46 @@ def colour_keywords(args):
         kw['colours'] = args.colours
         if 'noise_taps' in args:
             kw['noise_taps'] = args.noise_taps
+    if 'maskers' in args:
+        kw['maskers'] = args.maskers
     return kw
+
+
+def maskers_refusal(args):
+    """What is wrong with --maskers on this command line, or None. Looks at the arguments alone."""
+    if 'maskers' not in args:
+        return None
+    if args.cnn_command != 'noisesweep':
+        if args.cnn_command in SWEEPS:
+            return "--maskers is not supported by {} (the maskers belong to noisesweep)".format(args.cnn_command)
+        return "--maskers only applies to 'cnn noisesweep'"
+    if 'colours' in args or 'noise_taps' in args:
+        return "--maskers and --colours each make the levels of a sweep: give one of them"
+    if args.snrs is not None and len(args.maskers) * len(args.snrs) > NOISE_LEVELS_MAX:
+        return "a noise sweep takes at most {} levels, not {} maskers x {} SNRs = {}".format(
+            NOISE_LEVELS_MAX, len(args.maskers), len(args.snrs), len(args.maskers) * len(args.snrs))
+    return None
+
+
+def augment_maskers_refusal(args):
+    """The same for --augment-maskers / --augment-masker-snrs, asked once from_wav_refusal has nothing to say"""
+    given = [opt for attr, opt in (('augment_maskers', '--augment-maskers'), ('augment_masker_snrs', '--augment-masker-snrs')) if attr in args]
+    if not given:
+        return None
+    if args.cnn_command != 'train':
+        return "{} only applies to 'cnn train'".format(given[0])
+    if getattr(args, 'engine', 'torch') != 'hip':
+        return "{} needs --engine hip: only the library's own training step renders windows from the waves".format(given[0])
+    if 'from_wav' not in args:
+        return "{} needs --from-wav: stored windows cannot be rendered again under a masker".format(given[0])
+    if 'augment_maskers' not in args:
+        return "--augment-masker-snrs belongs to --augment-maskers"
+    if 'augment_masker_snrs' not in args:
+        return "--augment-maskers needs --augment-masker-snrs: a masker is drawn together with the SNR it is mixed in at"
+    if len(args.augment_maskers) * len(args.augment_masker_snrs) > NOISE_LEVELS_MAX:
+        return "training takes at most {} masker levels, not {} maskers x {} SNRs = {}".format(
+            NOISE_LEVELS_MAX, len(args.augment_maskers), len(args.augment_masker_snrs), len(args.augment_maskers) * len(args.augment_masker_snrs))
+    return None
 
 
 def colours_refusal(args):
@@ -639,7 +726,7 @@ def main(argv=None):
             return report.exit_status
     elif 'cnn_command' in args:
         refusal = (from_wav_refusal(args) or rooms_refusal(args) or augment_colours_refusal(args) or augment_smear_refusal(args) or
-                   colours_refusal(args))
+                   augment_maskers_refusal(args) or colours_refusal(args) or maskers_refusal(args))
         if refusal:
             print(refusal)
             return 1
@@ -660,6 +747,8 @@ def main(argv=None):
                     rooms['noise_taps'] = args.augment_noise_taps
             if 'augment_spreads' in args or 'augment_bands' in args:
                 rooms.update(spreads=tuple(getattr(args, 'augment_spreads', ())), bands=tuple(getattr(args, 'augment_bands', ())))
+            if 'augment_maskers' in args:                      # (likewise)
+                rooms.update(maskers=tuple(args.augment_maskers), masker_snrs=tuple(args.augment_masker_snrs))
             TrainFromWav(labelFile=labelFile, LPF=args.CUTOFF is not None, CUTOFF=args.CUTOFF, snrs=tuple(getattr(args, 'augment_snrs', ())),
                          seed=args.seed, **rooms)
             return 0

@@ -69,6 +69,11 @@ struct f2_ctx {
     // f2_reverb_pick / f2_launch_noisy_windows with rooms: the reverberant float64 batch, which the noise kernels read while they
     // write `levels` (a span of its own: k_noise_pick's pointers are __restrict__)
     f2_scratch wet;
+    // f2_masker_levels, f2_masker_pick, f2_eval_masker_sweep, f2_launch_noisy_windows with maskers: [masker_offsets | samples] of the
+    // recordings of the call in flight (up to 64 x 2^26 float64 samples: too much for `meta`), uploaded once per call
+    f2_scratch masker;
+    // f2_launch_noisy_windows with maskers: the masked float64 batch, which the noise kernels read while they write `levels`
+    f2_scratch masked;
     // f2_channel_mix_levels, f2_eval_smear_sweep: tile sums, tile spans and the transposed mixing matrices of the call in flight (up to
     // 134 MB at 64 levels of 512 channels: too much for `meta`). Reserved once per call, before its first launch.
     f2_scratch mix;
@@ -329,7 +334,7 @@ struct f2_meta_carve {
         void* slot;      // the T* to set
         size_t bytes;
         bool wide;
-    } items[12];
+    } items[16];
     int n = 0;
     template <class T>
     void add(T** p, size_t count) {
@@ -630,6 +635,62 @@ void f2_shaped_pick_meta(f2_meta_carve* meta, int B, const int64_t* h_offsets, c
 int f2_launch_shaped_noise_pick(f2_ctx* ctx, const void* d_wave, int wave_dtype, const int64_t* d_offsets, const int64_t* h_offsets, int B,
                                 const f2_noise_pick_args& N, const f2_shaped_pick_arrays& A, const int32_t* d_level,
                                 const double* d_sigma, double* d_out);
+// f2_masker.hip, the kernels of f2_masker_levels / f2_eval_masker_sweep / f2_masker_pick and of the masker stage of a window call or
+// a render. A level l < K is the recording masker_of[l] at snr_db[l]; the recordings are host float64 samples, packed, with R + 1
+// masker_offsets.
+// f2_check_maskers: masker / masker_offsets / masker_of non-NULL and R >= 1 (F2_ERR_INVALID), R <= F2_MASKER_MAX_RECORDINGS and
+// K <= F2_MASKER_MAX_LEVELS (F2_ERR_UNSUPPORTED), masker_offsets from 0 and non-decreasing, no empty recording (F2_ERR_INVALID), none
+// above F2_MASKER_MAX_SAMPLES (F2_ERR_UNSUPPORTED), every sample finite and every masker_of entry in [0, R) (F2_ERR_INVALID), tested
+// in that order; the messages name the recording or the level. f2_check_masker_levels: the white sweep's checks of K and snr_db
+// before them. f2_upload_maskers: [masker_offsets | samples] into `area` (ctx->masker, or a buffer a trainer owns), enqueued.
+// f2_masker_meta names the small device arrays of a launch in the call's f2_meta_carve (before its reserve()): [sigma | gain | start]
+// as one run of 3 (K + 1) B values, level-major each, 10^(snr_db / 10) and masker_of. The launch uploads them and the recordings,
+// runs f2_launch_noise_sigma and the two masker kernels, and writes (K + 1) * h_offsets[B] doubles, level-major, level K the clean
+// samples.
+#define F2_MASKER_MAX_RECORDINGS 64
+#define F2_MASKER_MAX_LEVELS 64
+#define F2_MASKER_MAX_SAMPLES (int64_t(1) << 26)
+struct f2_masker_arrays {
+    double *d_sigma = nullptr, *d_gain = nullptr, *d_lin = nullptr;
+    int64_t *d_start = nullptr, *d_masker_of = nullptr;   // (masker_of: K int32 values in 8-byte slots)
+};
+int f2_check_maskers(f2_ctx* ctx, const double* masker, const int64_t* masker_offsets, int R, const int32_t* masker_of, int K);
+int f2_check_masker_levels(f2_ctx* ctx, const double* snr_db, const double* masker, const int64_t* masker_offsets, int R,
+                           const int32_t* masker_of, int K);
+int f2_upload_maskers(f2_ctx* ctx, f2_scratch& area, const double* masker, const int64_t* masker_offsets, int R, const int64_t** d_moff,
+                      const double** d_masker);
+void f2_masker_meta(f2_meta_carve* meta, int B, int K, f2_masker_arrays* A);
+int f2_launch_masker_levels(f2_ctx* ctx, const void* d_wave, int wave_dtype, const int64_t* d_offsets, const int64_t* h_offsets, int B,
+                            const double* snr_db, const double* masker, const int64_t* masker_offsets, int R, const int32_t* masker_of,
+                            int K, uint64_t seed, f2_masker_arrays& A, double* d_out);
+// The masker stage of a window call or a render (f2_augment_args below) and the arguments of f2_masker_pick: utterance b at level
+// level_of[b] in [0, K] (K: no masker), utterance first_utterance + b of its corpus. f2_check_masker_pick: f2_check_noise_pick's
+// checks of K, snr_db, level_of and first_utterance; where every utterance is clean (silent(), or every level_of entry is K) nothing
+// reads a recording and the stage becomes silent(); otherwise f2_check_maskers. d_masker / d_moff: device copies that are up already
+// (a render uploads them once for all its groups), or NULL: the launch uploads them into ctx->masker. The launch runs
+// k_noise_pick_sigma and the two pick kernels into d_out (total doubles); a silent stage converts alone.
+struct f2_masker_pick_args {
+    const double* snr_db = nullptr;
+    const double* masker = nullptr;
+    const int64_t* masker_offsets = nullptr;
+    int R = 0;
+    const int32_t* masker_of = nullptr;
+    int K = 0;
+    const int32_t* level_of = nullptr;
+    uint32_t first_utterance = 0;
+    uint64_t seed = 0;
+    const double* d_masker = nullptr;
+    const int64_t* d_moff = nullptr;
+    bool silent() const { return K == 0 || !level_of; }
+};
+struct f2_masker_pick_arrays {
+    double *d_sigma = nullptr, *d_gain = nullptr, *d_lin = nullptr;   // [sigma | gain | start] as one run of 3 B values
+    int64_t *d_start = nullptr, *d_level = nullptr, *d_masker_of = nullptr;   // (level, masker_of: int32 values in 8-byte slots)
+};
+int f2_check_masker_pick(f2_ctx* ctx, int B, f2_masker_pick_args* M);
+void f2_masker_pick_meta(f2_meta_carve* meta, int B, const f2_masker_pick_args& M, f2_masker_pick_arrays* A);
+int f2_launch_masker_pick(f2_ctx* ctx, const void* d_wave, int wave_dtype, const int64_t* d_offsets, int B, int64_t total,
+                          const f2_masker_pick_args& M, f2_masker_pick_arrays& A, double* d_out);
 // The argument checks of f2_input_batch, and behind them f2_check_noise_pick when the call has a noise stage (noise != NULL), all
 // before anything is launched. `windows`: where the windows go (only tested for NULL). *n_windows == 0 on F2_OK: an empty call.
 // win_utt: the utterance of every window.
@@ -771,9 +832,10 @@ int f2_upload_mix_image(f2_ctx* ctx, const f2_smear_plan& P, void* d_image, cons
 int f2_launch_gather_mixed(f2_ctx* ctx, const double* d_env, int C, const int64_t* d_offsets, const int64_t* d_centers, const int* d_win_utt,
                            int64_t n_windows, int radius, int step, int normalize, const f2_smear_plan& P, const int64_t* d_spans,
                            const double* d_wT, const int32_t* d_mix_of, float* d_out, int* d_flag);
-// The augmentation stages of a window call (f2_input_batch_smeared and the entries that telescope into it) or of a render
-// (f2_trainer_render_smeared likewise), in the order they run: rooms (f2_launch_reverb_pick into ctx->wet, skipped where dry()),
-// noise (k_noise_pick or k_shaped_noise_pick into ctx->levels, reading ctx->wet behind rooms; converts alone where clean()), the
+// The augmentation stages of a window call (f2_input_batch_masked and the entries that telescope into it) or of a render
+// (f2_trainer_render_masked likewise), in the order they run: rooms (f2_launch_reverb_pick into ctx->wet, skipped where dry()),
+// maskers (f2_launch_masker_pick into ctx->masked, reading ctx->wet behind rooms; skipped where silent()), noise (k_noise_pick or
+// k_shaped_noise_pick into ctx->levels, reading the last buffer written before it; converts alone where clean()), the
 // envelopes, and smear (f2_launch_gather_mixed instead of f2_launch_gather_ragged unless sharp() or all_sharp; its image goes into
 // ctx->mix unless smear.d_wT says it is up already). A further stage is a further record here: of() fills it from the C arguments
 // (a render passes first_utterance 0), check() checks it, slice() advances it and f2_launch_noisy_windows runs it.
@@ -781,6 +843,7 @@ struct f2_augment_args {
     f2_reverb_pick_args rooms;
     f2_noise_pick_args noise;
     f2_mix_gather_args smear;
+    f2_masker_pick_args maskers;   // (behind smear: the entries that have none leave it silent)
     static f2_augment_args of(const double* rir, const int64_t* rir_offsets, int Kr, const int32_t* room_of, const double* snr_db,
                               const double* fir, const int64_t* fir_offsets, int K, const int32_t* level_of, uint32_t first_utterance,
                               uint64_t seed, const double* mix, int Km, const int32_t* mix_of) {
@@ -788,12 +851,19 @@ struct f2_augment_args {
         A.smear.mix = mix, A.smear.K = Km, A.smear.mix_of = mix_of;
         return A;
     }
-    // colours, rooms, mix, before anything is launched (builds smear.plan): the checks behind f2_check_noise_pick, which every caller
+    // ... and the masker stage of the entries that have one, drawn with the noise stage's seed and utterance numbers
+    f2_augment_args& with_maskers(const double* snr_db, const double* masker, const int64_t* masker_offsets, int R, const int32_t* masker_of,
+                                  int K, const int32_t* level_of) {
+        maskers = {snr_db, masker, masker_offsets, R, masker_of, K, level_of, noise.first_utterance, noise.seed, nullptr, nullptr};
+        return *this;
+    }
+    // colours, rooms, mix, maskers, before anything is launched (builds smear.plan): the checks behind f2_check_noise_pick, which every caller
     // places itself - a window call runs it before its window lists
     int check(f2_ctx* ctx, int B, int C, int radius) {
         F2_TRY(f2_check_noise_colours(ctx, B, &noise, false));
         F2_TRY(f2_check_reverb_pick(ctx, B, rooms));
-        return f2_check_mix_gather(ctx, B, C, radius, &smear);
+        F2_TRY(f2_check_mix_gather(ctx, B, C, radius, &smear));
+        return f2_check_masker_pick(ctx, B, &maskers);
     }
     // the stages of utterances b0 .. of the checked batch: their rows of the per-utterance tables, numbered on from b0 for the
     // generator; the taps, the plan and what is up on the device stay
@@ -802,7 +872,8 @@ struct f2_augment_args {
         if (!rooms.dry()) G.rooms.room_of += b0;
         if (noise.level_of) G.noise.level_of += b0;
         if (!smear.sharp()) G.smear.mix_of += b0;
-        G.noise.first_utterance += (uint32_t)b0;
+        if (!maskers.silent()) G.maskers.level_of += b0;
+        G.noise.first_utterance += (uint32_t)b0, G.maskers.first_utterance += (uint32_t)b0;
         return G;
     }
 };

@@ -5,6 +5,7 @@
 //   k_label_tally  per (level, utterance): windows labelled rising, windows whose label is the clean level's
 // gfx950, wave64. Everything that reaches memory is written by plain C++ stores or vector integer atomics.
 #include "f2_internal.h"
+#include "f2_block_sum.h"
 #include "f2_philox.h"
 
 #include <type_traits>
@@ -13,24 +14,7 @@ namespace {
 
 constexpr int SIGMA_THREADS = 1024, NOISE_THREADS = 256, TALLY_THREADS = 256;
 
-template <typename T>
-__device__ inline T wave_sum(T v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_down(v, d, 64);
-    return v;   // lane 0 holds the sum; the tree is the same on every call
-}
-
-// sum over the workgroup, valid in thread 0: lanes by shuffles, waves through LDS in wave order
-template <typename T, int THREADS>
-__device__ inline T block_sum(T v, T* lds) {
-    v = wave_sum(v);
-    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
-    __syncthreads();
-    T total = 0;
-    if (threadIdx.x == 0)
-        for (int w = 0; w < THREADS / 64; ++w) total += lds[w];
-    return total;
-}
+// (wave_sum, block_sum and utterance_of live in f2_block_sum.h: the masker kernels of f2_masker.hip sum with the same tree)
 
 // RMS of row b of the clean batch, valid in thread 0. int16: the squares are summed in int64 (exact, so the order does not matter),
 // then sqrt((double)sum / n). float64: thread t adds samples t, t + THREADS, ... in that order, then the fixed tree of block_sum.
@@ -81,16 +65,6 @@ __global__ __launch_bounds__(SIGMA_THREADS) void k_noise_pick_sigma(const T* __r
 
 // (noise_deviate, the standard normal deviate of (seed, level, utterance, sample), lives in f2_philox.h: k_shaped_noise_levels of
 // f2_noise_shaped.hip draws from the same function)
-
-// utterance of sample p of the batch: the last b with offsets[b] <= p (empty utterances are stepped over)
-__device__ inline int utterance_of(const int64_t* __restrict__ offsets, int B, int64_t p) {
-    int lo = 0, hi = B;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (offsets[mid] <= p) lo = mid; else hi = mid;
-    }
-    return lo;
-}
 
 // One thread per sample of one level (blockIdx.y strides over the levels): out[l * total + p] = clean[p] + sigma[l * B + b] * z,
 // product and sum rounded separately; where sigma is 0 (the clean level, an all-zero row) the sample itself, exactly.

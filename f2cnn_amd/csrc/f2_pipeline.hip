@@ -821,6 +821,39 @@ int f2_eval_shaped_noise_sweep(f2_ctx* ctx, const f2_cnn* cnn, const void* wave,
         noisy_or_null, scores_or_null, labels_or_null, window_offsets_or_null, stats_or_null, sigma_or_null, &A.d_sigma);
 }
 
+// f2_eval_masker_sweep: a wave sweep whose levels come from k_noise_sigma and the two masker kernels (f2_masker.hip). Only the clean
+// samples and the recordings go up; sigma, gain, start, stats and what the caller asked for come back behind one wait.
+int f2_eval_masker_sweep(f2_ctx* ctx, const f2_cnn* cnn, const void* wave, int wave_dtype, const int64_t* offsets, const double* coefs,
+                         int B, int C, int lpf, double cutoff_hz, int fft_precision, int radius, int step, int hop, const double* snr_db,
+                         const double* masker, const int64_t* masker_offsets, int R, const int32_t* masker_of, int K, uint64_t seed,
+                         double* noisy_or_null, float* scores_or_null, uint8_t* labels_or_null, int64_t* window_offsets_or_null,
+                         double* sigma_or_null, double* gain_or_null, int64_t* start_or_null, int64_t* stats_or_null, int mem_space) {
+    const f2_batch X = {wave, wave_dtype, offsets, coefs, B, C, lpf, cutoff_hz, fft_precision, mem_space};
+    f2_masker_arrays A;
+    bool ran = false;
+    const int rc = wave_sweep(
+        ctx, cnn, X, radius, step, hop, K, [&] { return f2_check_masker_levels(ctx, snr_db, masker, masker_offsets, R, masker_of, K); },
+        [&](f2_meta_carve* meta, size_t) { f2_masker_meta(meta, B, K, &A); },
+        [&](const int64_t* d_offsets, int64_t, double* d_noisy) -> int {
+            const void* d_wave;
+            F2_TRY(f2_stage_wave(ctx, wave, wave_dtype, offsets[B], mem_space, &d_wave));
+            F2_TRY(f2_launch_masker_levels(ctx, d_wave, wave_dtype, d_offsets, offsets, B, snr_db, masker, masker_offsets, R, masker_of, K, seed,
+                                           A, d_noisy));
+            const size_t bytes = sizeof(double) * ((size_t)K + 1) * (size_t)B;   // (read behind the sweep's one wait)
+            if (gain_or_null) F2_HIP(ctx, hipMemcpyAsync(gain_or_null, A.d_gain, bytes, hipMemcpyDeviceToHost, ctx->stream));
+            if (start_or_null) F2_HIP(ctx, hipMemcpyAsync(start_or_null, A.d_start, bytes, hipMemcpyDeviceToHost, ctx->stream));
+            ran = true;
+            return F2_OK;
+        },
+        noisy_or_null, scores_or_null, labels_or_null, window_offsets_or_null, stats_or_null, sigma_or_null, &A.d_sigma);
+    if (rc == F2_OK && !ran) {   // a batch without samples: nothing was launched
+        const size_t U = ((size_t)K + 1) * (size_t)(B > 0 ? B : 0);
+        if (gain_or_null) std::fill(gain_or_null, gain_or_null + U, 0.0);
+        if (start_or_null) std::fill(start_or_null, start_or_null + U, (int64_t)0);
+    }
+    return rc;
+}
+
 // f2_eval_cutoff_sweep: an envelope sweep whose levels come from k_lowpass_levels (f2_lowpass.hip), on the unfiltered envelopes. Only
 // the samples and the K coefficient pairs go up; one wait at the end.
 int f2_eval_cutoff_sweep(f2_ctx* ctx, const f2_cnn* cnn, const void* wave, int wave_dtype, const int64_t* offsets,
@@ -1121,25 +1154,32 @@ int f2_launch_noisy_windows(f2_ctx* ctx, const f2_batch& X, const f2_window_list
     const int B = X.B;
     const int64_t* offsets = X.offsets;
     const int64_t total = X.total();
-    const bool wet = !A.rooms.dry();
+    const bool wet = !A.rooms.dry(), masked = !A.maskers.silent();
     mix_gather_meta G;
     // the small arrays and the waveforms first: nothing the envelopes reserve is one of these areas
     noise_pick_meta M;
     f2_reverb_pick_arrays R;
+    f2_masker_pick_arrays K;
     f2_meta_carve meta;
     M.carve(&meta, B, offsets, A.noise);
     if (wet) f2_reverb_pick_meta(&meta, B, offsets, A.rooms, &R);
+    if (masked) f2_masker_pick_meta(&meta, B, A.maskers, &K);
     G.carve(&meta, B, A.smear);
     F2_TRY(meta.reserve(ctx));
     F2_TRY(G.reserve(ctx));
     F2_TRY(f2_reserve(ctx, ctx->levels, sizeof(double) * (size_t)total));
     if (wet) F2_TRY(f2_reserve(ctx, ctx->wet, sizeof(double) * (size_t)total));
+    if (masked) F2_TRY(f2_reserve(ctx, ctx->masked, sizeof(double) * (size_t)total));
     F2_TRY(f2_upload_offsets(ctx, offsets, B));
     const void* d_wave = X.wave;
     int wave_dtype = X.wave_dtype;
     if (wet) {   // f2_reverb_pick into ctx->wet, then f2_noise_pick(F2_WAVE_F64) from there: sigma is the reverberant signal's
         F2_TRY(f2_launch_reverb_pick(ctx, d_wave, wave_dtype, (const int64_t*)ctx->offsets.ptr, offsets, B, A.rooms, R, (double*)ctx->wet.ptr));
         d_wave = ctx->wet.ptr, wave_dtype = F2_WAVE_F64;
+    }
+    if (masked) {   // f2_masker_pick into ctx->masked, then the noise from there: its sigma is the masked signal's
+        F2_TRY(f2_launch_masker_pick(ctx, d_wave, wave_dtype, (const int64_t*)ctx->offsets.ptr, B, total, A.maskers, K, (double*)ctx->masked.ptr));
+        d_wave = ctx->masked.ptr, wave_dtype = F2_WAVE_F64;
     }
     F2_TRY(M.launch(ctx, d_wave, wave_dtype, (const int64_t*)ctx->offsets.ptr, offsets, B, total, A.noise, (double*)ctx->levels.ptr));
     // f2_input_batch from here on, as a device call on the float64 buffer
@@ -1248,15 +1288,18 @@ int f2_gather_windows_mixed(f2_ctx* ctx, const double* env, const int64_t* offse
                        [&](float* d_windows) { return G.launch(ctx, (const double*)d_env, B, C, W, d_windows); });
 }
 
-// The one window path behind a noise stage: f2_input_batch_smeared, and without matrices f2_input_batch_coloured, and with
-// fir == NULL f2_input_batch_wet, and without rooms f2_input_batch_noisy.
-int f2_input_batch_smeared(f2_ctx* ctx, const void* wave, int wave_dtype, const int64_t* offsets, const double* coefs, int B, int C, int lpf,
-                           double cutoff_hz, int fft_precision, const int64_t* center_offsets, const int64_t* centers, int radius, int step,
-                           int normalize, const double* rir, const int64_t* rir_offsets, int Kr, const int32_t* room_of, const double* snr_db,
-                           const double* fir, const int64_t* fir_offsets, int K, const int32_t* level_of, uint32_t first_utterance,
-                           uint64_t seed, const double* mix, int Km, const int32_t* mix_of, float* windows, int mem_space) {
+// The one window path behind a noise stage: f2_input_batch_masked, and without maskers f2_input_batch_smeared, and without matrices
+// f2_input_batch_coloured, and with fir == NULL f2_input_batch_wet, and without rooms f2_input_batch_noisy.
+int f2_input_batch_masked(f2_ctx* ctx, const void* wave, int wave_dtype, const int64_t* offsets, const double* coefs, int B, int C, int lpf,
+                          double cutoff_hz, int fft_precision, const int64_t* center_offsets, const int64_t* centers, int radius, int step,
+                          int normalize, const double* rir, const int64_t* rir_offsets, int Kr, const int32_t* room_of, const double* snr_db,
+                          const double* fir, const int64_t* fir_offsets, int K, const int32_t* level_of, uint32_t first_utterance,
+                          uint64_t seed, const double* mix, int Km, const int32_t* mix_of, const double* masker_snr_db, const double* masker,
+                          const int64_t* masker_offsets, int R, const int32_t* masker_of, int Kk, const int32_t* masker_level_of,
+                          float* windows, int mem_space) {
     f2_augment_args A = f2_augment_args::of(rir, rir_offsets, Kr, room_of, snr_db, fir, fir_offsets, K, level_of, first_utterance, seed, mix, Km,
-                                            mix_of);
+                                            mix_of)
+                            .with_maskers(masker_snr_db, masker, masker_offsets, R, masker_of, Kk, masker_level_of);
     int64_t n_windows;
     std::vector<int> win_utt;
     F2_TRY(f2_check_input_batch(ctx, wave, wave_dtype, offsets, coefs, B, C, lpf, cutoff_hz, fft_precision, center_offsets, centers, radius,
@@ -1268,6 +1311,16 @@ int f2_input_batch_smeared(f2_ctx* ctx, const void* wave, int wave_dtype, const 
     const f2_window_list W = {centers, win_utt.data(), false, n_windows, radius, step, normalize};
     return window_tail(ctx, windows, n_windows, radius, C, normalize, mem_space,
                        [&](float* d_windows) { return f2_launch_noisy_windows(ctx, X, W, A, d_windows); });
+}
+
+int f2_input_batch_smeared(f2_ctx* ctx, const void* wave, int wave_dtype, const int64_t* offsets, const double* coefs, int B, int C, int lpf,
+                           double cutoff_hz, int fft_precision, const int64_t* center_offsets, const int64_t* centers, int radius, int step,
+                           int normalize, const double* rir, const int64_t* rir_offsets, int Kr, const int32_t* room_of, const double* snr_db,
+                           const double* fir, const int64_t* fir_offsets, int K, const int32_t* level_of, uint32_t first_utterance,
+                           uint64_t seed, const double* mix, int Km, const int32_t* mix_of, float* windows, int mem_space) {
+    return f2_input_batch_masked(ctx, wave, wave_dtype, offsets, coefs, B, C, lpf, cutoff_hz, fft_precision, center_offsets, centers, radius,
+                                 step, normalize, rir, rir_offsets, Kr, room_of, snr_db, fir, fir_offsets, K, level_of, first_utterance, seed,
+                                 mix, Km, mix_of, nullptr, nullptr, nullptr, 0, nullptr, 0, nullptr, windows, mem_space);
 }
 
 int f2_input_batch_coloured(f2_ctx* ctx, const void* wave, int wave_dtype, const int64_t* offsets, const double* coefs, int B, int C, int lpf,

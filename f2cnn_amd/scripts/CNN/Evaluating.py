@@ -1059,7 +1059,7 @@ def _run_sweep(axis, files, hop, model, ctx, accuracy, resample):
 
 
 def EvaluateNoiseSweep(files, SNRdBs, seed=0, hop=None, LPF=False, CUTOFF=50, model='last_trained_model', save_wavs=False,
-                       ctx=None, accuracy=None, resample=False, colours=None, noise_taps=1025):
+                       ctx=None, accuracy=None, resample=False, maskers=None, colours=None, noise_taps=1025):
     """`cnn noisesweep` (not in the reference, whose EvaluateWithNoise :193-221 takes one file at one level): every file at
     every level of SNRdBs and clean in one device pass per group of files (f2_eval_noise_sweep: the noise is drawn on the device
     from (seed, level, file's place in its group, sample), so a sweep repeats bit for bit), with the clean run of the same
@@ -1080,12 +1080,22 @@ def EvaluateNoiseSweep(files, SNRdBs, seed=0, hop=None, LPF=False, CUTOFF=50, mo
     are colour-major over SNRdBs, at most 64, named like 'pink 10dB'; the file is <stem>.coloursweep.npz - a white sweep's
     .sweep.npz is never overwritten - with the keys above, snr_db per level, and colours (a string per level), fir and fir_offsets
     (the taps of all levels and where each level's start); save_wavs writes <stem>_<colour>_<SNR>dB.WAV. colours=None is the
-    white sweep as it was, to the byte."""
+    white sweep as it was, to the byte.
+    With maskers= (`--maskers`: recordings, read by masker.LoadMasker at the files' framerate, with resample= at any rate) a level
+    is a recording at an SNR and nothing is Gaussian: per file a cyclic segment of the recording, drawn from (seed, recording,
+    file's place in its group), is scaled to sigma and mixed in (f2_eval_masker_sweep). The levels are masker-major over SNRdBs
+    (masker.MaskerLevels), at most 64, named like 'babble 10dB'; the file is <stem>.maskersweep.npz with snr_db, maskers (a
+    name per level), masker_files, sigma, gain and start per level, then the keys above; save_wavs writes
+    <stem>_<masker>_<SNR>dB.WAV. Not together with colours=."""
     if isinstance(files, (str, bytes, os.PathLike)):
         files = [files]
     snr = numpy.asarray(SNRdBs, dtype=numpy.float64).reshape(-1)
     if not len(snr) or not numpy.isfinite(snr).all():
         raise ValueError("a noise sweep needs at least one finite SNR in dB")
+    if maskers is not None:
+        if colours is not None:
+            raise ValueError("a noise sweep has colours or maskers, not both")
+        return _EvaluateMaskerSweep(files, snr, maskers, seed, hop, LPF, CUTOFF, model, save_wavs, ctx, accuracy, resample)
     if colours is not None:
         return _EvaluateColourSweep(files, snr, colours, noise_taps, seed, hop, LPF, CUTOFF, model, save_wavs, ctx, accuracy, resample)
     K = len(snr)
@@ -1169,6 +1179,47 @@ def _EvaluateColourSweep(files, snr, colours, noise_taps, seed, hop, LPF, CUTOFF
                       limit=float('inf'), call=call, own=own,
                       order=('snr_db', 'colours', 'sigma', 'windows', 'rising', 'agree', 'agreement', 'seed', 'hop'),
                       out=lambda file: os.path.join(outdir, stem(file) + '.coloursweep.npz'), outdir=outdir,
+                      wav_target=lambda file, l: os.path.join(outdir, '{}_{}_{}dB'.format(stem(file), grid[l][1], _level_text(grid[l][2]))))
+    return _run_sweep(axis, files, hop, model, ctx, accuracy, resample)
+
+
+def _EvaluateMaskerSweep(files, snr, maskers, seed, hop, LPF, CUTOFF, model, save_wavs, ctx, accuracy, resample):
+    """EvaluateNoiseSweep with maskers: the grid is checked before any file is read, a recording is read once per framerate"""
+    from ... import masker
+    if isinstance(maskers, str):
+        maskers = maskers.split(',')
+    maskers = [str(m) for m in maskers]
+    grid = masker.MaskerLevels(maskers, snr)
+    K = len(grid)
+    level_snr = numpy.array([v for _, _, v in grid], numpy.float64)
+    level_name = numpy.array([name for _, name, _ in grid], dtype=str)
+    masker_of = numpy.array([r for r, _, _ in grid], numpy.int32)
+    recordings_at = {}
+
+    def recordings(framerate):
+        if framerate not in recordings_at:
+            recordings_at[framerate] = [masker.LoadMasker(m, framerate, resample=bool(resample)) for m in maskers]
+        return recordings_at[framerate]
+
+    def call(ctx, handle, flat, dt, offsets, coefs, B, Cn, radius, STEP, hop, framerate, labels):
+        noisy = numpy.empty((K + 1) * int(offsets[-1]), numpy.float64) if save_wavs else None
+        wo, sigma, stats, gain, start = ctx.eval_masker_sweep(handle, flat, dt, offsets, coefs, B, Cn, bool(LPF), CUTOFF if LPF else 0.0,
+                                                              FFT_PRECISION, radius, STEP, hop, level_snr, recordings(framerate), masker_of,
+                                                              seed, noisy, None, labels, _lib.MEM_HOST)
+        return wo, stats, noisy, (sigma, gain, start)
+
+    def own(got, rows, wo, n, radius, STEP, hop, framerate):
+        sigma, gain, start = got
+        return dict(snr_db=level_snr.copy(), maskers=level_name.copy(), masker_files=numpy.array(maskers, dtype=str), sigma=sigma[rows].copy(),
+                    gain=gain[rows].copy(), start=start[rows].copy(), seed=numpy.uint64(int(seed) & (2 ** 64 - 1)))
+
+    outdir = os.path.join('OutputWavFiles', 'addedNoise')
+    stem = lambda file: os.path.basename(os.path.splitext(file)[0])
+    axis = _SweepAxis(names=['{} {}dB'.format(name, _level_text(v)) for _, name, v in grid], referee='clean', label="{:>16}",
+                      limit=float('inf'), call=call, own=own,
+                      order=('snr_db', 'maskers', 'masker_files', 'sigma', 'gain', 'start', 'windows', 'rising', 'agree', 'agreement', 'seed',
+                             'hop'),
+                      out=lambda file: os.path.join(outdir, stem(file) + '.maskersweep.npz'), outdir=outdir,
                       wav_target=lambda file, l: os.path.join(outdir, '{}_{}_{}dB'.format(stem(file), grid[l][1], _level_text(grid[l][2]))))
     return _run_sweep(axis, files, hop, model, ctx, accuracy, resample)
 

@@ -11,7 +11,7 @@ produces weights; every forward pass used for evaluation is HIP kernel K4 (the t
 ``TrainFromWav`` (`cnn train --engine hip --from-wav`, not in the reference) trains on windows the device renders from the WAV files,
 again before every epoch under fresh noise (``--augment-snrs``), of a colour drawn per file (``--augment-colours``), and in a
 freshly drawn room per file (``--augment-t60``, ``--augment-rirs``) and at a spectral resolution drawn per file
-(``--augment-spreads``, ``--augment-bands``) when asked.
+(``--augment-spreads``, ``--augment-bands``) and under a recorded masker drawn per file (``--augment-maskers``) when asked.
 
 ``TestModel`` (`cnn test`, not in the reference) is ``model.evaluate(x_test, y_test)`` (:136) for a saved model, broken down
 by a column of the label CSV: one ``f2_cnn_score_windows`` call on the stored windows.
@@ -324,6 +324,7 @@ VALIDATION_NOISE_SEED = 0x76616C69    # 'vali': the noisy validation sets are re
 ROOM_STREAM = 0x726F6F6D        # 'room': the generator of the epochs' rooms is default_rng([seed, ROOM_STREAM])
 VALIDATION_ROOM_SEED = 0x76726F6D     # 'vrom': the synthetic responses of the reverberant validation sets are built once, from this seed
 SMEAR_STREAM = 0x736D6561       # 'smea': the generator of the epochs' spectral resolutions is default_rng([seed, SMEAR_STREAM])
+MASKER_STREAM = 0x6D61736B      # 'mask': the generator of the epochs' maskers is default_rng([seed, MASKER_STREAM])
 RENDER_GROUP = 64               # files per envelope pass, as `prepare input --from-wav`
 
 
@@ -342,6 +343,12 @@ def draw_epoch_rooms(rng, Kr, B):
 def draw_epoch_smear(rng, Km, B):
     """mix_of (B) int32 in [0, Km] of one epoch, drawn from rng; Km is the sharp one (the mixing is deterministic: no seed)"""
     return rng.integers(0, Km + 1, B).astype(numpy.int32)
+
+
+def draw_epoch_maskers(rng, Kk, B):
+    """(masker_level_of (B) int32 in [0, Kk], masker seed) of one epoch, drawn from rng in that order; Kk is the one without a masker"""
+    masker_level_of = rng.integers(0, Kk + 1, B).astype(numpy.int32)
+    return masker_level_of, int(rng.integers(0, 2 ** 63))
 
 
 def build_smear_levels(spreads, bands, centre_freqs):
@@ -364,10 +371,11 @@ def build_rooms(t60s, measured, framerate, drr_db, room_seed):
 
 
 def _render_windows(ctx, waves, centers, coefs, cfg, LPF, CUTOFF, precision, snrs=(), level=None, seed=0, rirs=(), room=None, firs=None,
-                    mix=None):
+                    mix=None, masker=None):
     """Normalised windows of some files through f2_input_batch_noisy, RENDER_GROUP files per call, every file at snrs[level]
     (level None: clean); with `room`, through f2_input_batch_wet with every file in rirs[room]; with `firs` (a filter per level),
-    through f2_input_batch_coloured; with `mix` (a (C, C) matrix), through f2_input_batch_smeared with every file mixed by it"""
+    through f2_input_batch_coloured; with `mix` (a (C, C) matrix), through f2_input_batch_smeared with every file mixed by it; with
+    `masker` (recordings, masker_of, masker_snrs, level), through f2_input_batch_masked with every file at that masker level"""
     Cn = coefs.shape[0]
     out = numpy.empty((int(sum(len(c) for c in centers)), cfg.dots_per_input, Cn), numpy.float32)
     row = 0
@@ -385,7 +393,10 @@ def _render_windows(ctx, waves, centers, coefs, cfg, LPF, CUTOFF, precision, snr
                  precision, center_offsets, numpy.concatenate(cs), cfg.radius, cfg.step, True)
         rooms = (rirs if room is not None else (), None if room is None else numpy.full(len(ws), room, numpy.int32))
         back = (level_of, g, seed, out[row:row + n], _lib.MEM_HOST)
-        if mix is not None:
+        if masker is not None:
+            ctx.input_batch_masked(*front, *rooms, snrs, firs, *back[:3], None, None, masker[0], masker[1], masker[2],
+                                   numpy.full(len(ws), masker[3], numpy.int32), *back[3:])
+        elif mix is not None:
             ctx.input_batch_smeared(*front, *rooms, snrs, firs, *back[:3], mix[None], numpy.zeros(len(ws), numpy.int32), *back[3:])
         elif firs is not None:
             ctx.input_batch_coloured(*front, *rooms, snrs, firs, *back)
@@ -398,7 +409,7 @@ def _render_windows(ctx, waves, centers, coefs, cfg, LPF, CUTOFF, precision, snr
 
 
 def TrainFromWav(labelFile=None, LPF=False, CUTOFF=100, snrs=(), seed=None, ctx=None, verbose=1, on_epoch=None, t60s=(), rirs=(),
-                 drr_db=0.0, colours=(), noise_taps=1025, spreads=(), bands=()):
+                 drr_db=0.0, colours=(), noise_taps=1025, spreads=(), bands=(), maskers=(), masker_snrs=()):
     """`cnn train --engine hip --from-wav`: trains on windows rendered on the device from the WAV files of the label CSV.
 
     The TRAIN files go to the trainer once (Trainer.set_waves); the TEST files become normalised windows once, clean - the
@@ -433,6 +444,16 @@ def TrainFromWav(labelFile=None, LPF=False, CUTOFF=100, snrs=(), seed=None, ctx=
     read (a bad spread raises smear.py's ValueError there). The noise and room generators are drawn exactly as without them. The
     TEST files are validated sharp as before and once more per resolution, clean and dry (f2_input_batch_smeared): the history
     gains 'val_acc_smear' / 'val_loss_smear' and augment gains spreads, bands and smear_levels (a name per level).
+    With `maskers` (recordings, masker.LoadMasker at the corpus' rate; needs `masker_snrs`) a masker level is a pair (recording,
+    SNR): the levels are masker.MaskerLevels(maskers, masker_snrs), masker-major over the SNRs and at most 64 - the level numbers
+    of `cnn noisesweep --maskers` - and the recordings are read once, before any other file (a recording at another rate raises
+    masker.py's ValueError there). Every epoch also draws, from numpy.random.default_rng([seed, MASKER_STREAM]), a masker level
+    in [0, Kk] per TRAIN file (Kk: none) and a masker seed (draw_epoch_maskers) and renders through Trainer.render /
+    render_wet(maskers=...): behind the room and before the Gaussian noise a cyclic segment of the recording is mixed in at that
+    SNR (f2_trainer_render_masked). The segments are drawn with the epoch's noise seed, or with the masker seed where there is no
+    noise. The other generators are drawn exactly as without maskers. The TEST files are also validated once per masker level
+    (f2_input_batch_masked, VALIDATION_NOISE_SEED): the history gains 'val_acc_masker' / 'val_loss_masker' and augment gains
+    maskers (the files), masker_snrs, masker_levels (a name per level) and masker_seed per epoch.
     on_epoch(iterations, trainer), if given, is called after each epoch's render, before its steps (for tests and for looking at
     what the network is about to see).
     BATCH_SIZE and EPOCHS come from configF2CNN.conf. Returns (F2CNNModel, history)."""
@@ -464,6 +485,21 @@ def TrainFromWav(labelFile=None, LPF=False, CUTOFF=100, snrs=(), seed=None, ctx=
         level_snrs = tuple(v for _, _, v in grid)
         level_names = ['{} {}dB'.format(name, _level_text(v)) for _, name, v in grid]
     K = len(level_snrs)
+    # (the maskers likewise: a recording that cannot be used is refused here, with masker.py's message)
+    maskers = tuple(maskers.split(',')) if isinstance(maskers, str) else tuple(maskers)
+    masker_snrs = tuple(float(v) for v in masker_snrs)
+    recordings, masker_of, masker_level_snrs, masker_names = None, None, (), []
+    if maskers:
+        from ... import masker as _masker
+        from .Evaluating import _level_text
+        if not masker_snrs:
+            raise ValueError("maskers need the SNRs they are mixed in at (masker_snrs)")
+        masker_grid = _masker.MaskerLevels(maskers, masker_snrs)
+        recordings = [_masker.LoadMasker(m, cfg.framerate) for m in maskers]
+        masker_of = numpy.array([r for r, _, _ in masker_grid], numpy.int32)
+        masker_level_snrs = tuple(v for _, _, v in masker_grid)
+        masker_names = ['{} {}dB'.format(name, _level_text(v)) for _, name, v in masker_grid]
+    Kk = len(masker_names)
     # (the mixing matrices likewise: a bad spread or number of bands is refused here, with smear.py's message)
     spreads, bands = tuple(float(v) for v in spreads), tuple(bands)
     centre_freqs, coefs = filterbank_from_config(cfg)
@@ -496,6 +532,8 @@ def TrainFromWav(labelFile=None, LPF=False, CUTOFF=100, snrs=(), seed=None, ctx=
         print('rooms: t60 (s)', list(t60s) or 'none', '| measured', list(rir_files) or 'none', '| drr (dB) {:g}'.format(float(drr_db)))
     if Km:
         print('spectral resolutions:', ', '.join(smear_names))
+    if Kk:
+        print('maskers:', ', '.join(masker_names))
     coefs = numpy.ascontiguousarray(coefs, dtype=numpy.float64)
     ctx = ctx or _lib.default_context()
     try:
@@ -510,6 +548,9 @@ def TrainFromWav(labelFile=None, LPF=False, CUTOFF=100, snrs=(), seed=None, ctx=
         for m in range(Km if len(y_test) else 0):
             val.append(_render_windows(ctx, [waves[k] for k in test], [lw.centers[k] for k in test], coefs, cfg, LPF, CUTOFF,
                                        FFT_PRECISION, mix=mixes[m]))
+        for k in range(Kk if len(y_test) else 0):
+            val.append(_render_windows(ctx, [waves[j] for j in test], [lw.centers[j] for j in test], coefs, cfg, LPF, CUTOFF,
+                                       FFT_PRECISION, seed=VALIDATION_NOISE_SEED, masker=(recordings, masker_of, masker_level_snrs, k)))
         x_val, y_val = numpy.concatenate(val), numpy.tile(y_test, len(val))
         groups = numpy.repeat(numpy.arange(len(val), dtype=numpy.int32), len(y_test))
         trainer, rng = _hip_trainer(cfg.dots_per_input, coefs.shape[0], seed, 1e-4, 1e-6, ctx)
@@ -521,7 +562,9 @@ def TrainFromWav(labelFile=None, LPF=False, CUTOFF=100, snrs=(), seed=None, ctx=
         room_seeds, val_room = [], {"val_acc_room": [[] for _ in range(Kr)], "val_loss_room": [[] for _ in range(Kr)]}
         smear_rng = numpy.random.default_rng([seed, SMEAR_STREAM])
         val_smear = {"val_acc_smear": [[] for _ in range(Km)], "val_loss_smear": [[] for _ in range(Km)]}
-        if not K and not Kr and not Km:
+        masker_rng = numpy.random.default_rng([seed, MASKER_STREAM])
+        masker_seeds, val_masker = [], {"val_acc_masker": [[] for _ in range(Kk)], "val_loss_masker": [[] for _ in range(Kk)]}
+        if not K and not Kr and not Km and not Kk:
             trainer.render()
 
         def run_epoch():
@@ -530,20 +573,27 @@ def TrainFromWav(labelFile=None, LPF=False, CUTOFF=100, snrs=(), seed=None, ctx=
             if K:
                 level_of, noise_seed = draw_epoch_noise(noise_rng, K, len(train))
                 noise_seeds.append(noise_seed)
+            masking = {}                                       # (only when asked for: the render without maskers is the one it was)
+            if Kk:
+                masker_level_of, masker_seed = draw_epoch_maskers(masker_rng, Kk, len(train))
+                masker_seeds.append(masker_seed)
+                masking = dict(maskers=recordings, masker_of=masker_of, masker_snrs=masker_level_snrs, masker_level_of=masker_level_of)
+                if not K:                                      # (the one seed of a render draws the segments too)
+                    noise_seed = masker_seed
             if Kr:
                 room_of, room_seed = draw_epoch_rooms(room_rng, Kr, len(train))
                 room_seeds.append(room_seed)
                 trainer.render_wet(build_rooms(t60s, measured, cfg.framerate, drr_db, room_seed), room_of, level_snrs, level_of, noise_seed,
-                                   firs=firs, mixes=mixes, mix_of=mix_of)
-            elif K or Km:
-                trainer.render(level_snrs, level_of, noise_seed, firs=firs, mixes=mixes, mix_of=mix_of)
+                                   firs=firs, mixes=mixes, mix_of=mix_of, **masking)
+            elif K or Km or Kk:
+                trainer.render(level_snrs, level_of, noise_seed, firs=firs, mixes=mixes, mix_of=mix_of, **masking)
             if on_epoch:
                 on_epoch(trainer.iterations, trainer)
             return trainer.steps(rng.permutation(len(y_train)), batch_size)
 
         def validate():
             if not len(y_test):
-                for per in (val_snr, val_room, val_smear):
+                for per in (val_snr, val_room, val_smear, val_masker):
                     for k in per:
                         for per_level in per[k]:
                             per_level.append(float("nan"))
@@ -560,10 +610,14 @@ def TrainFromWav(labelFile=None, LPF=False, CUTOFF=100, snrs=(), seed=None, ctx=
             for m in range(Km):
                 val_smear["val_acc_smear"][m].append(float(acc[K + Kr + 1 + m]))
                 val_smear["val_loss_smear"][m].append(float(loss[K + Kr + 1 + m]))
-            if verbose and (K or Kr or Km):
+            for k in range(Kk):
+                val_masker["val_acc_masker"][k].append(float(acc[K + Kr + Km + 1 + k]))
+                val_masker["val_loss_masker"][k].append(float(loss[K + Kr + Km + 1 + k]))
+            if verbose and (K or Kr or Km or Kk):
                 print("    val_acc clean {:.4f}".format(acc[0]) + "".join(" | {} {:.4f}".format(s, a) for s, a in zip(level_names, acc[1:])) +
                       "".join(" | room {} {:.4f}".format(r, a) for r, a in enumerate(acc[K + 1:K + Kr + 1])) +
-                      "".join(" | {} {:.4f}".format(s, a) for s, a in zip(smear_names, acc[K + Kr + 1:])))
+                      "".join(" | {} {:.4f}".format(s, a) for s, a in zip(smear_names, acc[K + Kr + 1:])) +
+                      "".join(" | {} {:.4f}".format(s, a) for s, a in zip(masker_names, acc[K + Kr + Km + 1:])))
             return float(loss[0]), float(acc[0])
 
         model, history = fit_epochs(run_epoch, validate, trainer.model, len(y_train), epochs, verbose)
@@ -577,13 +631,15 @@ def TrainFromWav(labelFile=None, LPF=False, CUTOFF=100, snrs=(), seed=None, ctx=
         history.update(val_room)
     if Km:
         history.update(val_smear)
+    if Kk:
+        history.update(val_masker)
     model.save('last_trained_model')
     print("Model saved as 'last_trained_model'.")
     if len(y_test):
         print('Test loss:', history["val_loss"][-1])
         print('Test accuracy:', history["val_acc"][-1])
     results = dict(history)
-    if K or Kr or Km:
+    if K or Kr or Km or Kk:
         results["augment"] = {"snrs": list(snrs), "seed": int(seed), "noise_seed": noise_seeds}
     if colours:
         results["augment"].update({"colours": [name for _, name, _ in grid], "level_snr_db": list(level_snrs), "noise_taps": int(noise_taps)})
@@ -591,6 +647,9 @@ def TrainFromWav(labelFile=None, LPF=False, CUTOFF=100, snrs=(), seed=None, ctx=
         results["augment"].update({"t60": list(t60s), "rirs": list(rir_files), "drr": float(drr_db), "room_seed": room_seeds})
     if Km:
         results["augment"].update({"spreads": list(spreads), "bands": [int(v) for v in bands], "smear_levels": list(smear_names)})
+    if Kk:
+        results["augment"].update({"maskers": list(maskers), "masker_snrs": list(masker_snrs), "masker_levels": list(masker_names),
+                                   "masker_seed": masker_seeds})
     with open('last_trained_model_results.json', 'w') as fp:
         json.dump(results, fp)
     print("History saved as 'last_trained_model_results.json'")

@@ -1273,6 +1273,109 @@ int f2_trainer_render_smeared(f2_ctx* ctx, f2_trainer* trainer, const double* ri
                               const double* mix /* host, (Km, C, C), or NULL: sharp */, int Km,
                               const int32_t* mix_of /* host, B, or NULL */);
 
+/* ---- Recorded maskers: `cnn noisesweep --maskers` and `cnn train --augment-maskers` ----------------------------------------------
+ * Every other noise of this library is Gaussian. A recorded masker (babble, a cafeteria, music) keeps the envelope modulations of
+ * its own that `like:` removes: the recording itself is mixed in, not a noise with its spectrum. (f2_version stays 115 with these
+ * entries: look the symbols up to find out whether a build has them.)
+ *
+ * The maskers are R recordings of float64 samples, packed in `masker` with R + 1 `masker_offsets`; recording r has
+ * M_r = masker_offsets[r+1] - masker_offsets[r] samples. A level l < K is a pair (recording r = masker_of[l], snr_db[l]); level K
+ * is clean. For utterance number utt (b in f2_masker_levels and the sweep, first_utterance + b in f2_masker_pick, a window call or
+ * a render) of n samples at level l:
+ *   segment   start = ((w1 << 32) | w0) mod M_r as unsigned 64-bit integers, (w0, w1, w2, w3) = Philox4x32-10 with counter
+ *             (r, 0x4D41534B, 0, utt) and key (seed & 0xffffffff, seed >> 32), by the generator's own device function. No deviate
+ *             has 0x4D41534B as its second counter word (theirs is 0 or 0xffffffff for rows of at most 2^22 samples): the streams
+ *             are disjoint. The start depends on (seed, r, utt) alone, so two levels of one recording mix the same segment and
+ *             differ in their SNR only. The segment is cyclic, m[i] = masker_r[(start + i) mod M_r], i < n: a recording shorter
+ *             than the utterance wraps.
+ *   sigma     RMS(clean) / 10^(snr_db[l] / 10), the white sweep's rule and its kernels: the same bits as f2_eval_noise_sweep /
+ *             f2_noise_pick return for that SNR, so that "10 dB" means the same on the white, coloured and masker axes.
+ *   gain      P = sum over i < n of m[i]^2 in float64 in a fixed order: one workgroup of 1024 threads per (utterance, level),
+ *             thread t adds i = t, t + 1024, ... in that order, then the tree of the sigma kernel (lanes by shuffles, waves in
+ *             order). No atomics: the same bits on every call. gain = sigma / sqrt(P / n), and 0 where n = 0, sigma = 0 or P = 0
+ *             (a silent segment); no infinity or NaN is formed.
+ *   mix       noisy[i] = clean[i] + gain * m[i], product and sum rounded separately. Where gain is 0, and at level K, the clean
+ *             sample converted to float64 exactly.
+ * A sample depends on (seed, r, snr, utt, i), its clean utterance and the recording - not on B, K, the other utterances or levels,
+ * the launch shape, the memory space or the input dtype of equal values.
+ *   kernels   the mix is one thread per sample, consecutive lanes on consecutive float64 values of the wave, the recording (up to
+ *             the wrap) and the output, as k_noise_levels; the index is reduced once per thread and corrected by compare and
+ *             subtract. One device function for the start and the sum in both gain kernels, one for the segment and the mix in both
+ *             mix kernels. Plain vector stores.
+ * Limits: 1 <= R <= 64, 1 <= K <= 64 (K = 0 allowed where a level per utterance is picked), every recording 1 .. 2^26 samples.
+ * Beyond them: F2_ERR_UNSUPPORTED. F2_ERR_INVALID: a NULL masker, masker_offsets or masker_of; masker_offsets that do not start at 0
+ * or that decrease; an empty recording; a sample that is not finite; a masker_of entry outside [0, R); and what the white sweep
+ * rejects of K and snr_db. All before anything is launched or written; the messages name the level or the recording.
+ * masker, masker_offsets, masker_of and snr_db are always host pointers; the recordings go up once per call (once per render, into
+ * a buffer the trainer owns).
+ *
+ * f2_masker_levels: the (K+1) * offsets[B] float64 samples of all levels, level-major, utterance u = l*B + b of a (K+1)*B batch
+ * whose offsets are the clean ones tiled, as f2_shaped_noise_levels. sigma_or_null, gain_or_null (float64) and start_or_null
+ * (int64) are host arrays of (K+1)*B, level-major; the clean level holds 0 in all three. wave and noisy are in mem_space (device
+ * pointers need element alignment only). F2_MEM_DEVICE: the call enqueues and waits only to hand back sigma / gain / start.
+ * Errors: f2_shaped_noise_levels' of the batch, then the maskers'. B == 0 or offsets[B] == 0: F2_OK, the three filled with zeros.
+ *
+ * f2_eval_masker_sweep: f2_eval_shaped_noise_sweep with the levels made by f2_masker_levels' kernels. Only the clean samples and
+ * the recordings go up; one wait at the end; every output is optional. noisy is bit for bit f2_masker_levels; scores, labels and
+ * window_offsets are bit for bit what f2_eval_batch_strided(F2_WAVE_F64) returns on it; stats come from the white sweep's tally
+ * kernel. Errors in the sweeps' order, the maskers' last.
+ *
+ * f2_masker_pick: utterance b at level level_of[b] in [0, K] as utterance number first_utterance + b, the output in the layout of
+ * the waves; sigma / gain / start of B. With first_utterance == 0 bit for bit that level of that utterance of f2_masker_levels.
+ * level_of == NULL or K == 0, or every entry K: the conversion to float64 alone, and masker may be NULL. Errors: f2_noise_pick's of
+ * the batch, K, snr_db, level_of and first_utterance, then the maskers'.
+ *
+ * f2_input_batch_masked: f2_input_batch_smeared's arguments plus the masker stage behind mix_of (its SNRs, the recordings, the
+ * levels and a level per utterance); the stage draws with the call's seed and first_utterance. The stages run in the order room,
+ * masker, noise, envelopes, mixing gather: the Gaussian noise is added to the masked signal, and its sigma is that float64
+ * signal's. Bit for bit f2_input_batch_smeared(F2_WAVE_F64, no rooms) on f2_masker_pick(F2_WAVE_F64) on f2_reverb_pick; nothing
+ * leaves the device in between. Kk == 0 or masker_level_of == NULL: bit for bit f2_input_batch_smeared (it is that call). Errors:
+ * those of f2_input_batch_smeared, then the masker stage's, all before a launch.
+ *
+ * f2_trainer_render_masked: f2_trainer_render_smeared's arguments plus the same stage. Group g is bit for bit f2_input_batch_masked
+ * on its utterances with first_utterance = g group; the recordings go up once per call. f2_trainer_render_smeared is this call
+ * without maskers, bit for bit.
+ */
+int f2_masker_levels(f2_ctx* ctx, const void* wave, int wave_dtype, const int64_t* offsets /* host, B+1 */, int B,
+                     const double* snr_db /* host, K */, const double* masker /* host, masker_offsets[R] samples */,
+                     const int64_t* masker_offsets /* host, R+1 */, int R, const int32_t* masker_of /* host, K, each in [0, R) */,
+                     int K, uint64_t seed, double* noisy /* (K+1) * offsets[B], level-major, mem_space */,
+                     double* sigma_or_null /* host, (K+1)*B */, double* gain_or_null /* host, (K+1)*B */,
+                     int64_t* start_or_null /* host, (K+1)*B */, int mem_space);
+int f2_eval_masker_sweep(f2_ctx* ctx, const f2_cnn* cnn, const void* wave, int wave_dtype, const int64_t* offsets,
+                         const double* coefs, int B, int C, int lpf, double cutoff_hz, int fft_precision, int radius, int step,
+                         int hop, const double* snr_db /* host, K */, const double* masker, const int64_t* masker_offsets /* host, R+1 */,
+                         int R, const int32_t* masker_of /* host, K */, int K, uint64_t seed,
+                         double* noisy_or_null /* (K+1) * offsets[B], mem_space */, float* scores_or_null, uint8_t* labels_or_null,
+                         int64_t* window_offsets_or_null /* host, (K+1)*B + 1 */, double* sigma_or_null /* host, (K+1)*B */,
+                         double* gain_or_null /* host, (K+1)*B */, int64_t* start_or_null /* host, (K+1)*B */,
+                         int64_t* stats_or_null /* host, (K+1)*B*2 */, int mem_space);
+int f2_masker_pick(f2_ctx* ctx, const void* wave, int wave_dtype, const int64_t* offsets /* host, B+1 */, int B,
+                   const double* snr_db /* host, K */, const double* masker, const int64_t* masker_offsets /* host, R+1 */, int R,
+                   const int32_t* masker_of /* host, K */, int K, const int32_t* level_of /* host, B, each in [0, K], or NULL */,
+                   uint32_t first_utterance, uint64_t seed, double* noisy /* offsets[B], mem_space */,
+                   double* sigma_or_null /* host, B */, double* gain_or_null /* host, B */, int64_t* start_or_null /* host, B */,
+                   int mem_space);
+int f2_input_batch_masked(f2_ctx* ctx, const void* wave, int wave_dtype, const int64_t* offsets, const double* coefs, int B, int C,
+                          int lpf, double cutoff_hz, int fft_precision, const int64_t* center_offsets, const int64_t* centers,
+                          int radius, int step, int normalize, const double* rir, const int64_t* rir_offsets, int Kr,
+                          const int32_t* room_of, const double* snr_db, const double* fir /* or NULL: white */,
+                          const int64_t* fir_offsets, int K, const int32_t* level_of, uint32_t first_utterance, uint64_t seed,
+                          const double* mix /* host, (Km, C, C), or NULL: sharp */, int Km,
+                          const int32_t* mix_of /* host, B, each in [0, Km], or NULL */, const double* masker_snr_db /* host, Kk */,
+                          const double* masker /* host, or NULL: no maskers */, const int64_t* masker_offsets /* host, R+1 */, int R,
+                          const int32_t* masker_of /* host, Kk */, int Kk,
+                          const int32_t* masker_level_of /* host, B, each in [0, Kk], or NULL */, float* windows, int mem_space);
+int f2_trainer_render_masked(f2_ctx* ctx, f2_trainer* trainer, const double* rir, const int64_t* rir_offsets, int Kr,
+                             const int32_t* room_of /* host, B, or NULL */, const double* snr_db,
+                             const double* fir /* or NULL: white */, const int64_t* fir_offsets, int K,
+                             const int32_t* level_of /* host, B, or NULL */, uint64_t seed,
+                             const double* mix /* host, (Km, C, C), or NULL: sharp */, int Km,
+                             const int32_t* mix_of /* host, B, or NULL */, const double* masker_snr_db /* host, Kk */,
+                             const double* masker /* host, or NULL: no maskers */, const int64_t* masker_offsets /* host, R+1 */,
+                             int R, const int32_t* masker_of /* host, Kk */, int Kk,
+                             const int32_t* masker_level_of /* host, B, or NULL */);
+
 /* ---- `cnn eval --segments`: decisions smoothed into transitions ---------------------------------------------------------------
  * The reference stops at a rising / falling label per row (Evaluating.py:73-90); where the network is unsure the labels flicker,
  * and a run-length reading of them is mostly noise. Here: the most probable two-state sequence under a switching penalty, its
