@@ -142,6 +142,12 @@ SIGNATURES = {
                                    _i, _vp, C.c_uint32, C.c_uint64, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _i]),
     "f2_trainer_render_masked": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, C.c_uint64, _vp, _i, _vp, _vp, _vp, _vp, _i,
                                       _vp, _i, _vp]),
+    "f2_lowpass_pick": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _vp, _vp, _i]),
+    "f2_input_batch_filtered": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i, _i, _d, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp,
+                                     _i, _vp, C.c_uint32, C.c_uint64, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _vp,
+                                     _i]),
+    "f2_trainer_render_filtered": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, C.c_uint64, _vp, _i, _vp, _vp, _vp, _vp, _i,
+                                        _vp, _i, _vp, _vp, _i, _vp]),
     "f2_decision_path": (_i, [_vp, _vp, _vp, _i, _d, _i64, _vp, _vp, _vp, _i]),
     "f2_decision_runs": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _i64, _i]),
     "f2_interval_tally": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i64, _i, _vp, _i]),
@@ -498,6 +504,24 @@ class Context:
         maskers[masker_of[l]] at masker_snrs[l], l = masker_level_of[b], or none where l == len(masker_snrs); maskers None:
         input_batch_smeared. See f2_input_batch_masked."""
         self._input_batch_staged("masked", locals())
+
+    def input_batch_filtered(self, wave, wave_dtype, offsets, coefs, B, Cn, lpf, cutoff, precision, center_offsets, centers, radius,
+                             step, normalize, rirs, room_of, snr_db, firs, level_of, first_utterance, seed, mixes, mix_of, maskers,
+                             masker_of, masker_snrs, masker_level_of, cutoffs, cutoff_of, windows, mem_space):
+        """input_batch_masked with an envelope cutoff per utterance between the envelopes and the gather: the unfiltered envelopes
+        of utterance b low-passed at cutoffs[cutoff_of[b]] Hz, or left as they are where cutoff_of[b] == len(cutoffs); cutoffs
+        empty or cutoff_of None: input_batch_masked. The stage excludes lpf. See f2_input_batch_filtered."""
+        self._input_batch_staged("filtered", locals())
+
+    def lowpass_pick(self, env, offsets, B, Cn, cutoffs, cutoff_of, filtered, mem_space):
+        """Envelopes that are already in memory with one cutoff per utterance (see f2_lowpass_pick): utterance b low-passed at
+        cutoffs[cutoff_of[b]] Hz, or copied where cutoff_of[b] == len(cutoffs); cutoff_of None: all copied. filtered receives
+        Cn * offsets[B] float64 in the layout of env (numpy arrays or device pointers, by mem_space); in device memory it may be
+        env itself."""
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        cut, lev = _cutoff_levels(cutoffs, cutoff_of)
+        self.check(self.lib.f2_lowpass_pick(self.handle, _ptr(env), _ptr(offsets), int(B), int(Cn), _ptr(cut) if len(cut) else None,
+                                            len(cut), _ptr(lev), _ptr(filtered), mem_space))
 
     def masker_pick(self, wave, wave_dtype, offsets, B, snr_db, maskers, masker_of, level_of, first_utterance, seed, noisy, mem_space,
                     small=False):
@@ -1063,6 +1087,14 @@ class Context:
         masker_level_of[b], between its room and its noise; maskers None: trainer_render_smeared (see f2_trainer_render_masked)"""
         self._trainer_render_staged("masked", locals())
 
+    def trainer_render_filtered(self, handle, rirs=(), room_of=None, snr_db=(), firs=None, level_of=None, seed=0, mixes=None,
+                                mix_of=None, channels=None, maskers=None, masker_of=None, masker_snrs=(), masker_level_of=None,
+                                cutoffs=(), cutoff_of=None):
+        """trainer_render_masked with the unfiltered envelopes of utterance b low-passed at cutoffs[cutoff_of[b]] Hz before the
+        gather, left as they are where cutoff_of[b] == len(cutoffs); cutoff_of None: trainer_render_masked (see
+        f2_trainer_render_filtered)"""
+        self._trainer_render_staged("filtered", locals())
+
     def trainer_get_windows(self, handle, first, count, shape):
         """Rows first .. first + count - 1 of the training set: (count, *shape) float32 windows and (count) uint8 labels"""
         x = np.empty((int(count),) + tuple(shape), np.float32)
@@ -1197,6 +1229,13 @@ def _maskers(maskers, masker_of, K):
     return (samples if len(samples) else None), masker_offsets, mof
 
 
+def _cutoff_levels(cutoffs, cutoff_of):
+    """(cutoffs as float64, cutoff_of as int32 or None) for the calls that give every utterance an envelope cutoff of its own"""
+    cut = np.ascontiguousarray(cutoffs if cutoffs is not None else (), dtype=np.float64).reshape(-1)
+    lev = None if cutoff_of is None else np.ascontiguousarray(cutoff_of, dtype=np.int32).reshape(-1)
+    return cut, lev
+
+
 def _rooms(rirs, room_of):
     """(taps, rir_offsets, room_of as int32 or None) for the calls that give every utterance a room of its own"""
     taps, rir_offsets = _pack_rirs(rirs if rirs is not None else ())
@@ -1235,11 +1274,12 @@ _STAGE_KEYS["wet"] = "rir rir_offsets Kr room_of".split() + _STAGE_KEYS["noisy"]
 _STAGE_KEYS["coloured"] = "rir rir_offsets Kr room_of snr_db fir fir_offsets K level_of first_utterance seed".split()
 _STAGE_KEYS["smeared"] = _STAGE_KEYS["coloured"] + "mix Km mix_of".split()
 _STAGE_KEYS["masked"] = _STAGE_KEYS["smeared"] + "masker_snr_db masker masker_offsets R masker_of Kk masker_level_of".split()
+_STAGE_KEYS["filtered"] = _STAGE_KEYS["masked"] + "cutoff_levels_hz Kc cutoff_of".split()
 
 
 def _stage_args(keys, v):
     """([the C arguments named by `keys`], what holds their arrays until the call returns) from the Python arguments `v` of a call with
-    augmentation stages: noise levels, colours, rooms, spectral resolutions, maskers, marshalled in that order and only where the symbol has
+    augmentation stages: noise levels, colours, rooms, spectral resolutions, maskers, cutoffs, marshalled in that order and only where the symbol has
     them. Arrays become their addresses; counts, first_utterance and seed are plain ints, which _ptr hands through as they are"""
     snr, lev = _noise_levels(v["snr_db"], v["level_of"])
     a = dict(snr_db=snr if len(snr) else None, K=len(snr), level_of=lev, first_utterance=int(v.get("first_utterance", 0)),
@@ -1256,6 +1296,9 @@ def _stage_args(keys, v):
         msnr, a["masker_level_of"] = _noise_levels(v["masker_snrs"], v["masker_level_of"])
         a["masker"], a["masker_offsets"], a["masker_of"] = _maskers(v["maskers"], v["masker_of"], len(msnr))
         a.update(masker_snr_db=msnr if len(msnr) else None, Kk=len(msnr), R=len(a["masker_offsets"]) - 1 if a["masker_offsets"] is not None else 0)
+    if "cutoff_of" in keys:
+        cut, a["cutoff_of"] = _cutoff_levels(v["cutoffs"], v["cutoff_of"])
+        a.update(cutoff_levels_hz=cut if len(cut) else None, Kc=len(cut))
     return [_ptr(a[k]) for k in keys], a
 
 

@@ -50,6 +50,13 @@ package implements:
                                                              on the device behind the room and before the Gaussian noise; the
                                                              TEST files are validated once per pair; combines with every other
                                                              --augment option; not in the reference)
+    python -m f2cnn_amd cnn train --engine hip --from-wav --augment-cutoffs 5,10,20,50 [--augment-snrs ...] [--augment-t60 ...] [--seed S]
+                                                            (every epoch the envelopes of each TRAIN file are low-passed at a
+                                                             cutoff drawn from the levels of lpfsweep, at most 64, or left
+                                                             unfiltered: filtered on the device between the envelopes and the
+                                                             gather; the TEST files are also validated once per cutoff; not with
+                                                             --lpf; combines with every other --augment option; not in the
+                                                             reference)
     python -m f2cnn_amd cnn test [--input/-i NPY] [--label/-l CSV] [--model/-m NPZ] [--by set|region|speaker|phoneme] [--rows test|train|all]
                                                             (loss, accuracy and the 2 x 2 counts of a saved model on the labelled
                                                              windows, per value of a label column, in one device pass; writes
@@ -207,6 +214,17 @@ def cutoffs_argument(text):
         cutoffs = []
     if not cutoffs or not all(math.isfinite(v) and 0 < v < 8000 for v in cutoffs):
         raise argparse.ArgumentTypeError("--cutoffs takes a comma-separated list of cutoffs in Hz inside (0, 8000), not {!r}".format(text))
+    return cutoffs
+
+
+def augment_cutoffs_argument(text):
+    """--augment-cutoffs: as --cutoffs, at most NOISE_LEVELS_MAX"""
+    try:
+        cutoffs = cutoffs_argument(text)
+    except argparse.ArgumentTypeError as e:
+        raise argparse.ArgumentTypeError(str(e).replace('--cutoffs', '--augment-cutoffs'))
+    if len(cutoffs) > NOISE_LEVELS_MAX:
+        raise argparse.ArgumentTypeError("--augment-cutoffs takes at most {} cutoffs, not {}".format(NOISE_LEVELS_MAX, len(cutoffs)))
     return cutoffs
 
 
@@ -420,6 +438,9 @@ def build_parser():
                         "every epoch each file is rendered under a segment of one of them at one of the SNRs, or without")
     c.add_argument('--augment-masker-snrs', action='store', type=augment_masker_snrs_argument, dest='augment_masker_snrs',
                    default=argparse.SUPPRESS, help="train --augment-maskers: comma-separated SNRs in dB of the maskers")
+    c.add_argument('--augment-cutoffs', action='store', type=augment_cutoffs_argument, dest='augment_cutoffs', default=argparse.SUPPRESS,
+                   help="train --engine hip --from-wav: comma-separated envelope cutoffs in Hz, as lpfsweep's --cutoffs; every epoch "
+                        "the envelopes of each file are low-passed at one of them, or left unfiltered (not with --lpf)")
     c.add_argument('--seed', action='store', type=int, dest='seed',
                    help="noisesweep: seed of the noise (default 0); train --from-wav: seed of the weights, the order and the noise")
     c.add_argument('--save-wavs', action='store_true', dest='save_wavs',
@@ -585,6 +606,21 @@ def augment_maskers_refusal(args):
     return None
 
 
+def augment_cutoffs_refusal(args):
+    """The same for --augment-cutoffs, asked once from_wav_refusal has nothing to say"""
+    if 'augment_cutoffs' not in args:
+        return None
+    if args.cnn_command != 'train':
+        return "--augment-cutoffs only applies to 'cnn train'"
+    if getattr(args, 'engine', 'torch') != 'hip':
+        return "--augment-cutoffs needs --engine hip: only the library's own training step renders windows from the waves"
+    if 'from_wav' not in args:
+        return "--augment-cutoffs needs --from-wav: stored windows cannot be rendered again at another envelope cutoff"
+    if args.CUTOFF is not None:
+        return "--augment-cutoffs and --lpf exclude each other: the cutoffs filter unfiltered envelopes, one cutoff per file"
+    return None
+
+
 def colours_refusal(args):
     """What is wrong with --colours / --noise-taps on this command line, or None. Looks at the arguments alone."""
     given = [opt for attr, opt in (('colours', '--colours'), ('noise_taps', '--noise-taps')) if attr in args]
@@ -726,7 +762,7 @@ def main(argv=None):
             return report.exit_status
     elif 'cnn_command' in args:
         refusal = (from_wav_refusal(args) or rooms_refusal(args) or augment_colours_refusal(args) or augment_smear_refusal(args) or
-                   augment_maskers_refusal(args) or colours_refusal(args) or maskers_refusal(args))
+                   augment_maskers_refusal(args) or augment_cutoffs_refusal(args) or colours_refusal(args) or maskers_refusal(args))
         if refusal:
             print(refusal)
             return 1
@@ -749,6 +785,8 @@ def main(argv=None):
                 rooms.update(spreads=tuple(getattr(args, 'augment_spreads', ())), bands=tuple(getattr(args, 'augment_bands', ())))
             if 'augment_maskers' in args:                      # (likewise)
                 rooms.update(maskers=tuple(args.augment_maskers), masker_snrs=tuple(args.augment_masker_snrs))
+            if 'augment_cutoffs' in args:                      # (likewise)
+                rooms.update(cutoffs=tuple(args.augment_cutoffs))
             TrainFromWav(labelFile=labelFile, LPF=args.CUTOFF is not None, CUTOFF=args.CUTOFF, snrs=tuple(getattr(args, 'augment_snrs', ())),
                          seed=args.seed, **rooms)
             return 0

@@ -711,6 +711,7 @@ struct f2_trainer {
     f2_scratch fir;             // f2_trainer_render_coloured: [fir_offsets | taps] of the render in flight, likewise
     f2_scratch mix;             // f2_trainer_render_smeared: [tile spans | transposed mixing matrices] of the render in flight, likewise
     f2_scratch masker;          // f2_trainer_render_masked: [masker_offsets | samples] of the recordings of the render in flight, likewise
+    f2_scratch lp_coef;         // f2_trainer_render_filtered: the {b0, a1} pairs of the cutoffs of the render in flight, likewise
     std::vector<int64_t> offsets, center_offsets;
     std::vector<double> coefs;
     int wave_dtype = 0, B = 0, lpf = 0, fft_precision = 0, radius = 0, step = 0, group = 1;
@@ -907,25 +908,26 @@ static int upload_taps(f2_ctx* ctx, f2_scratch& area, const int64_t* offsets, co
     return F2_OK;
 }
 
-int f2_trainer_render_masked(f2_ctx* ctx, f2_trainer* t, const double* rir, const int64_t* rir_offsets, int Kr, const int32_t* room_of,
-                             const double* snr_db, const double* fir, const int64_t* fir_offsets, int K, const int32_t* level_of,
-                             uint64_t seed, const double* mix, int Km, const int32_t* mix_of, const double* masker_snr_db,
-                             const double* masker, const int64_t* masker_offsets, int R, const int32_t* masker_of, int Kk,
-                             const int32_t* masker_level_of) {
+int f2_trainer_render_filtered(f2_ctx* ctx, f2_trainer* t, const double* rir, const int64_t* rir_offsets, int Kr, const int32_t* room_of,
+                               const double* snr_db, const double* fir, const int64_t* fir_offsets, int K, const int32_t* level_of,
+                               uint64_t seed, const double* mix, int Km, const int32_t* mix_of, const double* masker_snr_db,
+                               const double* masker, const int64_t* masker_offsets, int R, const int32_t* masker_of, int Kk,
+                               const int32_t* masker_level_of, const double* cutoff_levels_hz, int Kc, const int32_t* cutoff_of) {
     F2_TRY(f2_check_ctx(ctx));
     F2_TRY(check_trainer(ctx, t));
     F2_CHECK(ctx, t->have_waves, F2_ERR_INVALID, "the trainer has no waves to render from (f2_trainer_set_waves)");
     f2_augment_args A = f2_augment_args::of(rir, rir_offsets, Kr, room_of, snr_db, fir, fir_offsets, K, level_of, 0, seed, mix, Km, mix_of)
-                            .with_maskers(masker_snr_db, masker, masker_offsets, R, masker_of, Kk, masker_level_of);
+                            .with_maskers(masker_snr_db, masker, masker_offsets, R, masker_of, Kk, masker_level_of)
+                            .with_cutoffs(cutoff_levels_hz, Kc, cutoff_of);
     F2_TRY(f2_check_noise_pick(ctx, t->B, A.noise));
-    F2_TRY(A.check(ctx, t->B, t->channels, t->radius));
+    F2_TRY(A.check(ctx, t->B, t->channels, t->radius, t->lpf));   // (a trainer set with lpf = 1 refuses a cutoff stage)
     if (t->n == 0) return F2_OK;
     const size_t xs = (size_t)t->rows * t->channels, ws = t->wave_dtype == F2_WAVE_I16 ? 2 : 8;
     const int64_t* d_centers = (const int64_t*)t->centers.ptr;
     const int* d_win_utt = (const int*)((const char*)t->centers.ptr + sizeof(int64_t) * (size_t)t->n);
     // what every group reads goes up once: the rooms' taps, the filters of the noise (a group whose utterances are all clean keeps
     // the colours: its tiles copy), the mixing matrices as the image the gather reads (a group whose utterances are all sharp
-    // takes the mixing gather's sharp path), and the recordings of the maskers
+    // takes the mixing gather's sharp path), the recordings of the maskers, and the filter coefficients of the cutoffs
     if (!A.rooms.dry()) F2_TRY(upload_taps(ctx, t->rir, rir_offsets, rir, Kr, &A.rooms.d_rir_off, &A.rooms.d_rir));
     if (A.noise.coloured()) F2_TRY(upload_taps(ctx, t->fir, fir_offsets, fir, K, &A.noise.d_fir_off, &A.noise.d_fir));
     if (!A.smear.sharp() && !A.smear.all_sharp) {
@@ -933,6 +935,11 @@ int f2_trainer_render_masked(f2_ctx* ctx, f2_trainer* t, const double* rir, cons
         F2_TRY(f2_upload_mix_image(ctx, *A.smear.plan, t->mix.ptr, &A.smear.d_spans, &A.smear.d_wT));
     }
     if (!A.maskers.silent()) F2_TRY(f2_upload_maskers(ctx, t->masker, masker, masker_offsets, R, &A.maskers.d_moff, &A.maskers.d_masker));
+    if (!A.cutoffs.unfiltered()) {
+        F2_TRY(f2_reserve(ctx, t->lp_coef, sizeof(double) * 2 * (size_t)Kc));
+        F2_TRY(f2_upload_lowpass_coefs(ctx, cutoff_levels_hz, Kc, (double*)t->lp_coef.ptr));
+        A.cutoffs.d_coef = (const double*)t->lp_coef.ptr;
+    }
     F2_TRY(f2_reset_flag(ctx));
     std::vector<int64_t> off;
     // group after group onto the stream, each into its rows of x; one wait at the end
@@ -948,6 +955,16 @@ int f2_trainer_render_masked(f2_ctx* ctx, f2_trainer* t, const double* rir, cons
         F2_TRY(f2_launch_noisy_windows(ctx, X, W, A.slice(b0), (float*)t->x.ptr + xs * (size_t)w0));
     }
     return f2_finish_positive(ctx);
+}
+
+// the render without cutoffs: the same code, whose envelopes are then the trainer's own (lpf as it was set) and go to the gather as they are
+int f2_trainer_render_masked(f2_ctx* ctx, f2_trainer* t, const double* rir, const int64_t* rir_offsets, int Kr, const int32_t* room_of,
+                             const double* snr_db, const double* fir, const int64_t* fir_offsets, int K, const int32_t* level_of,
+                             uint64_t seed, const double* mix, int Km, const int32_t* mix_of, const double* masker_snr_db,
+                             const double* masker, const int64_t* masker_offsets, int R, const int32_t* masker_of, int Kk,
+                             const int32_t* masker_level_of) {
+    return f2_trainer_render_filtered(ctx, t, rir, rir_offsets, Kr, room_of, snr_db, fir, fir_offsets, K, level_of, seed, mix, Km, mix_of,
+                                      masker_snr_db, masker, masker_offsets, R, masker_of, Kk, masker_level_of, nullptr, 0, nullptr);
 }
 
 // the render without maskers: the same code, whose masker stage is then skipped altogether

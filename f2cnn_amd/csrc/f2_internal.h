@@ -334,7 +334,7 @@ struct f2_meta_carve {
         void* slot;      // the T* to set
         size_t bytes;
         bool wide;
-    } items[16];
+    } items[20];   // (a window call with every stage names 17)
     int n = 0;
     template <class T>
     void add(T** p, size_t count) {
@@ -715,6 +715,28 @@ int f2_check_cutoffs(f2_ctx* ctx, const double* cutoff_hz, int K);
 int f2_upload_lowpass_coefs(f2_ctx* ctx, const double* cutoff_hz, int K, double* d_coef);
 int f2_launch_lowpass_levels(f2_ctx* ctx, const double* d_env, const int64_t* d_offsets, int B, int C, int64_t total,
                              const double* d_coef, int K, double* d_levels);
+// The cutoff stage of a window call or a render (f2_augment_args below) and the arguments of f2_lowpass_pick: utterance b at cutoff
+// cutoff_of[b] in [0, K] (K: unfiltered). f2_check_lowpass_pick: K >= 0; unless the stage is unfiltered(), a non-NULL cutoff_hz,
+// f2_check_cutoffs, every cutoff_of entry in [0, K] (F2_ERR_INVALID, the message names the utterance) and B * C rows that fit a grid
+// (F2_ERR_UNSUPPORTED). d_coef: the K x {b0, a1} table on the device already (a render uploads it once for all its groups), or NULL:
+// the launch uploads it into the array f2_lowpass_pick_meta named. The launch reads the (C, n_b) blocks of d_src and writes them to
+// d_dst in the same layout; d_dst == d_src filters in place and touches nothing of an unfiltered utterance; an unfiltered() stage
+// copies (nothing in place).
+struct f2_lowpass_pick_args {
+    const double* cutoff_hz = nullptr;
+    int K = 0;
+    const int32_t* cutoff_of = nullptr;
+    const double* d_coef = nullptr;
+    bool unfiltered() const { return K == 0 || !cutoff_of; }
+};
+struct f2_lowpass_pick_arrays {
+    double* d_coef = nullptr;          // 2 K
+    int64_t* d_cutoff_of = nullptr;    // B int32 values in 8-byte slots
+};
+int f2_check_lowpass_pick(f2_ctx* ctx, int B, int C, const f2_lowpass_pick_args& P);
+void f2_lowpass_pick_meta(f2_meta_carve* meta, int B, const f2_lowpass_pick_args& P, f2_lowpass_pick_arrays* A);
+int f2_launch_lowpass_pick(f2_ctx* ctx, const double* d_src, const int64_t* d_offsets, int B, int C, int64_t total,
+                           const f2_lowpass_pick_args& P, const f2_lowpass_pick_arrays& A, double* d_dst);
 // f2_reverb.hip, the kernel of f2_reverb_levels / f2_eval_reverb_sweep. A workgroup of k_reverb_levels makes F2_REVERB_BLOCK
 // consecutive outputs of one utterance at one level and walks the taps in chunks of F2_REVERB_TAP_CHUNK (the input span of a chunk,
 // F2_REVERB_BLOCK + F2_REVERB_TAP_CHUNK float64 samples, is what it stages in LDS).
@@ -837,13 +859,16 @@ int f2_launch_gather_mixed(f2_ctx* ctx, const double* d_env, int C, const int64_
 // maskers (f2_launch_masker_pick into ctx->masked, reading ctx->wet behind rooms; skipped where silent()), noise (k_noise_pick or
 // k_shaped_noise_pick into ctx->levels, reading the last buffer written before it; converts alone where clean()), the
 // envelopes, and smear (f2_launch_gather_mixed instead of f2_launch_gather_ragged unless sharp() or all_sharp; its image goes into
-// ctx->mix unless smear.d_wT says it is up already). A further stage is a further record here: of() fills it from the C arguments
+// ctx->mix unless smear.d_wT says it is up already). Cutoffs (f2_launch_lowpass_pick, in place on the envelopes, between them and the
+// gather; skipped where unfiltered()) make the envelopes of the call unfiltered ones: lpf = 0, whatever X says - and a call with the
+// stage and lpf = 1 does not pass check(). A further stage is a further record here: of() fills it from the C arguments
 // (a render passes first_utterance 0), check() checks it, slice() advances it and f2_launch_noisy_windows runs it.
 struct f2_augment_args {
     f2_reverb_pick_args rooms;
     f2_noise_pick_args noise;
     f2_mix_gather_args smear;
     f2_masker_pick_args maskers;   // (behind smear: the entries that have none leave it silent)
+    f2_lowpass_pick_args cutoffs;  // (likewise: unfiltered)
     static f2_augment_args of(const double* rir, const int64_t* rir_offsets, int Kr, const int32_t* room_of, const double* snr_db,
                               const double* fir, const int64_t* fir_offsets, int K, const int32_t* level_of, uint32_t first_utterance,
                               uint64_t seed, const double* mix, int Km, const int32_t* mix_of) {
@@ -857,13 +882,24 @@ struct f2_augment_args {
         maskers = {snr_db, masker, masker_offsets, R, masker_of, K, level_of, noise.first_utterance, noise.seed, nullptr, nullptr};
         return *this;
     }
-    // colours, rooms, mix, maskers, before anything is launched (builds smear.plan): the checks behind f2_check_noise_pick, which every caller
-    // places itself - a window call runs it before its window lists
-    int check(f2_ctx* ctx, int B, int C, int radius) {
+    // ... and the cutoff stage of the entries that have one
+    f2_augment_args& with_cutoffs(const double* cutoff_hz, int K, const int32_t* cutoff_of) {
+        cutoffs.cutoff_hz = cutoff_hz, cutoffs.K = K, cutoffs.cutoff_of = cutoff_of;
+        return *this;
+    }
+    // colours, rooms, mix, maskers, cutoffs, before anything is launched (builds smear.plan): the checks behind f2_check_noise_pick, which
+    // every caller places itself - a window call runs it before its window lists. lpf: the call's own low-pass switch, which a cutoff
+    // stage excludes
+    int check(f2_ctx* ctx, int B, int C, int radius, int lpf) {
         F2_TRY(f2_check_noise_colours(ctx, B, &noise, false));
         F2_TRY(f2_check_reverb_pick(ctx, B, rooms));
         F2_TRY(f2_check_mix_gather(ctx, B, C, radius, &smear));
-        return f2_check_masker_pick(ctx, B, &maskers);
+        F2_TRY(f2_check_masker_pick(ctx, B, &maskers));
+        F2_TRY(f2_check_lowpass_pick(ctx, B, C, cutoffs));
+        F2_CHECK(ctx, cutoffs.unfiltered() || !lpf, F2_ERR_INVALID,
+                 "a cutoff stage (cutoff_of with K=%d cutoffs) and lpf = 1 exclude each other: the stage filters unfiltered envelopes",
+                 cutoffs.K);
+        return F2_OK;
     }
     // the stages of utterances b0 .. of the checked batch: their rows of the per-utterance tables, numbered on from b0 for the
     // generator; the taps, the plan and what is up on the device stay
@@ -873,6 +909,7 @@ struct f2_augment_args {
         if (noise.level_of) G.noise.level_of += b0;
         if (!smear.sharp()) G.smear.mix_of += b0;
         if (!maskers.silent()) G.maskers.level_of += b0;
+        if (!cutoffs.unfiltered()) G.cutoffs.cutoff_of += b0;
         G.noise.first_utterance += (uint32_t)b0, G.maskers.first_utterance += (uint32_t)b0;
         return G;
     }

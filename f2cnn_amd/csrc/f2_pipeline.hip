@@ -1154,16 +1154,18 @@ int f2_launch_noisy_windows(f2_ctx* ctx, const f2_batch& X, const f2_window_list
     const int B = X.B;
     const int64_t* offsets = X.offsets;
     const int64_t total = X.total();
-    const bool wet = !A.rooms.dry(), masked = !A.maskers.silent();
+    const bool wet = !A.rooms.dry(), masked = !A.maskers.silent(), filtered = !A.cutoffs.unfiltered();
     mix_gather_meta G;
     // the small arrays and the waveforms first: nothing the envelopes reserve is one of these areas
     noise_pick_meta M;
     f2_reverb_pick_arrays R;
     f2_masker_pick_arrays K;
+    f2_lowpass_pick_arrays L;
     f2_meta_carve meta;
     M.carve(&meta, B, offsets, A.noise);
     if (wet) f2_reverb_pick_meta(&meta, B, offsets, A.rooms, &R);
     if (masked) f2_masker_pick_meta(&meta, B, A.maskers, &K);
+    if (filtered) f2_lowpass_pick_meta(&meta, B, A.cutoffs, &L);
     G.carve(&meta, B, A.smear);
     F2_TRY(meta.reserve(ctx));
     F2_TRY(G.reserve(ctx));
@@ -1185,8 +1187,11 @@ int f2_launch_noisy_windows(f2_ctx* ctx, const f2_batch& X, const f2_window_list
     // f2_input_batch from here on, as a device call on the float64 buffer
     f2_batch E = X;
     E.wave = ctx->levels.ptr, E.wave_dtype = F2_WAVE_F64, E.mem_space = F2_MEM_DEVICE;
+    if (filtered) E.lpf = 0;   // the stage filters unfiltered envelopes (A.check refused lpf = 1 beside it)
     double* d_env;
     F2_TRY(f2_batch_envelopes(ctx, E, nullptr, nullptr, true, &d_env));
+    // f2_lowpass_pick on the envelope scratch, in place: the rows of an unfiltered utterance are neither read nor written
+    if (filtered) F2_TRY(f2_launch_lowpass_pick(ctx, d_env, (const int64_t*)ctx->offsets.ptr, B, X.C, total, A.cutoffs, L, d_env));
     f2_window_list D = W;
     if (!W.on_device) F2_TRY(f2_upload_windows(ctx, W.centers, W.win_utt, W.n_windows, &D.centers, &D.win_utt));
     return G.launch(ctx, d_env, B, X.C, D, d_windows);
@@ -1288,8 +1293,33 @@ int f2_gather_windows_mixed(f2_ctx* ctx, const double* env, const int64_t* offse
                        [&](float* d_windows) { return G.launch(ctx, (const double*)d_env, B, C, W, d_windows); });
 }
 
-// The one window path behind a noise stage: f2_input_batch_masked, and without maskers f2_input_batch_smeared, and without matrices
-// f2_input_batch_coloured, and with fir == NULL f2_input_batch_wet, and without rooms f2_input_batch_noisy.
+// The one window path behind a noise stage: f2_input_batch_filtered, and without cutoffs f2_input_batch_masked, and without maskers
+// f2_input_batch_smeared, and without matrices f2_input_batch_coloured, and with fir == NULL f2_input_batch_wet, and without rooms
+// f2_input_batch_noisy.
+int f2_input_batch_filtered(f2_ctx* ctx, const void* wave, int wave_dtype, const int64_t* offsets, const double* coefs, int B, int C, int lpf,
+                          double cutoff_hz, int fft_precision, const int64_t* center_offsets, const int64_t* centers, int radius, int step,
+                          int normalize, const double* rir, const int64_t* rir_offsets, int Kr, const int32_t* room_of, const double* snr_db,
+                          const double* fir, const int64_t* fir_offsets, int K, const int32_t* level_of, uint32_t first_utterance,
+                          uint64_t seed, const double* mix, int Km, const int32_t* mix_of, const double* masker_snr_db, const double* masker,
+                          const int64_t* masker_offsets, int R, const int32_t* masker_of, int Kk, const int32_t* masker_level_of,
+                          const double* cutoff_levels_hz, int Kc, const int32_t* cutoff_of, float* windows, int mem_space) {
+    f2_augment_args A = f2_augment_args::of(rir, rir_offsets, Kr, room_of, snr_db, fir, fir_offsets, K, level_of, first_utterance, seed, mix, Km,
+                                            mix_of)
+                            .with_maskers(masker_snr_db, masker, masker_offsets, R, masker_of, Kk, masker_level_of)
+                            .with_cutoffs(cutoff_levels_hz, Kc, cutoff_of);
+    int64_t n_windows;
+    std::vector<int> win_utt;
+    F2_TRY(f2_check_input_batch(ctx, wave, wave_dtype, offsets, coefs, B, C, lpf, cutoff_hz, fft_precision, center_offsets, centers, radius,
+                             step, windows, mem_space, &A.noise, &n_windows, &win_utt));
+    F2_TRY(A.check(ctx, B, C, radius, lpf));
+    if (n_windows == 0) return F2_OK;
+    f2_batch X = {nullptr, wave_dtype, offsets, coefs, B, C, lpf, cutoff_hz, fft_precision, F2_MEM_DEVICE};
+    F2_TRY(f2_stage_wave(ctx, wave, wave_dtype, offsets[B], mem_space, &X.wave));
+    const f2_window_list W = {centers, win_utt.data(), false, n_windows, radius, step, normalize};
+    return window_tail(ctx, windows, n_windows, radius, C, normalize, mem_space,
+                       [&](float* d_windows) { return f2_launch_noisy_windows(ctx, X, W, A, d_windows); });
+}
+
 int f2_input_batch_masked(f2_ctx* ctx, const void* wave, int wave_dtype, const int64_t* offsets, const double* coefs, int B, int C, int lpf,
                           double cutoff_hz, int fft_precision, const int64_t* center_offsets, const int64_t* centers, int radius, int step,
                           int normalize, const double* rir, const int64_t* rir_offsets, int Kr, const int32_t* room_of, const double* snr_db,
@@ -1297,20 +1327,10 @@ int f2_input_batch_masked(f2_ctx* ctx, const void* wave, int wave_dtype, const i
                           uint64_t seed, const double* mix, int Km, const int32_t* mix_of, const double* masker_snr_db, const double* masker,
                           const int64_t* masker_offsets, int R, const int32_t* masker_of, int Kk, const int32_t* masker_level_of,
                           float* windows, int mem_space) {
-    f2_augment_args A = f2_augment_args::of(rir, rir_offsets, Kr, room_of, snr_db, fir, fir_offsets, K, level_of, first_utterance, seed, mix, Km,
-                                            mix_of)
-                            .with_maskers(masker_snr_db, masker, masker_offsets, R, masker_of, Kk, masker_level_of);
-    int64_t n_windows;
-    std::vector<int> win_utt;
-    F2_TRY(f2_check_input_batch(ctx, wave, wave_dtype, offsets, coefs, B, C, lpf, cutoff_hz, fft_precision, center_offsets, centers, radius,
-                             step, windows, mem_space, &A.noise, &n_windows, &win_utt));
-    F2_TRY(A.check(ctx, B, C, radius));
-    if (n_windows == 0) return F2_OK;
-    f2_batch X = {nullptr, wave_dtype, offsets, coefs, B, C, lpf, cutoff_hz, fft_precision, F2_MEM_DEVICE};
-    F2_TRY(f2_stage_wave(ctx, wave, wave_dtype, offsets[B], mem_space, &X.wave));
-    const f2_window_list W = {centers, win_utt.data(), false, n_windows, radius, step, normalize};
-    return window_tail(ctx, windows, n_windows, radius, C, normalize, mem_space,
-                       [&](float* d_windows) { return f2_launch_noisy_windows(ctx, X, W, A, d_windows); });
+    return f2_input_batch_filtered(ctx, wave, wave_dtype, offsets, coefs, B, C, lpf, cutoff_hz, fft_precision, center_offsets, centers, radius,
+                                   step, normalize, rir, rir_offsets, Kr, room_of, snr_db, fir, fir_offsets, K, level_of, first_utterance, seed,
+                                   mix, Km, mix_of, masker_snr_db, masker, masker_offsets, R, masker_of, Kk, masker_level_of, nullptr, 0,
+                                   nullptr, windows, mem_space);
 }
 
 int f2_input_batch_smeared(f2_ctx* ctx, const void* wave, int wave_dtype, const int64_t* offsets, const double* coefs, int B, int C, int lpf,

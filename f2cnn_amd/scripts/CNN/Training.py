@@ -11,7 +11,8 @@ produces weights; every forward pass used for evaluation is HIP kernel K4 (the t
 ``TrainFromWav`` (`cnn train --engine hip --from-wav`, not in the reference) trains on windows the device renders from the WAV files,
 again before every epoch under fresh noise (``--augment-snrs``), of a colour drawn per file (``--augment-colours``), and in a
 freshly drawn room per file (``--augment-t60``, ``--augment-rirs``) and at a spectral resolution drawn per file
-(``--augment-spreads``, ``--augment-bands``) and under a recorded masker drawn per file (``--augment-maskers``) when asked.
+(``--augment-spreads``, ``--augment-bands``) and under a recorded masker drawn per file (``--augment-maskers``) and with the
+envelopes low-passed at a cutoff drawn per file (``--augment-cutoffs``) when asked.
 
 ``TestModel`` (`cnn test`, not in the reference) is ``model.evaluate(x_test, y_test)`` (:136) for a saved model, broken down
 by a column of the label CSV: one ``f2_cnn_score_windows`` call on the stored windows.
@@ -325,6 +326,8 @@ ROOM_STREAM = 0x726F6F6D        # 'room': the generator of the epochs' rooms is 
 VALIDATION_ROOM_SEED = 0x76726F6D     # 'vrom': the synthetic responses of the reverberant validation sets are built once, from this seed
 SMEAR_STREAM = 0x736D6561       # 'smea': the generator of the epochs' spectral resolutions is default_rng([seed, SMEAR_STREAM])
 MASKER_STREAM = 0x6D61736B      # 'mask': the generator of the epochs' maskers is default_rng([seed, MASKER_STREAM])
+CUTOFF_STREAM = 0x6375746F      # 'cuto': the generator of the epochs' envelope cutoffs is default_rng([seed, CUTOFF_STREAM])
+MAX_CUTOFFS = 64                # csrc/f2_internal.h: F2_LOWPASS_MAX_CUTOFFS
 RENDER_GROUP = 64               # files per envelope pass, as `prepare input --from-wav`
 
 
@@ -351,6 +354,23 @@ def draw_epoch_maskers(rng, Kk, B):
     return masker_level_of, int(rng.integers(0, 2 ** 63))
 
 
+def draw_epoch_cutoffs(rng, Kc, B):
+    """cutoff_of (B) int32 in [0, Kc] of one epoch, drawn from rng; Kc is the unfiltered one (the filter is deterministic: no seed)"""
+    return rng.integers(0, Kc + 1, B).astype(numpy.int32)
+
+
+def check_cutoffs(cutoffs):
+    """The envelope cutoffs (Hz) of a training run as a tuple of floats, by the rules of f2_lowpass_levels: at most MAX_CUTOFFS,
+    every one finite and inside (0, 8000); ValueError otherwise"""
+    cutoffs = tuple(float(v) for v in cutoffs)
+    if len(cutoffs) > MAX_CUTOFFS:
+        raise ValueError("{} envelope cutoffs (at most {})".format(len(cutoffs), MAX_CUTOFFS))
+    for v in cutoffs:
+        if not (numpy.isfinite(v) and 0.0 < v < 8000.0):
+            raise ValueError("envelope cutoff {:g} Hz outside (0, 8000)".format(v))
+    return cutoffs
+
+
 def build_smear_levels(spreads, bands, centre_freqs):
     """((Km, C, C) float64 matrices, names) of the spectral resolutions of a training run, ordered and named as
     Evaluating.EvaluateSmearSweep orders and names them: the spreads (smear.SmearMatrix on the centre frequencies), then the
@@ -371,11 +391,13 @@ def build_rooms(t60s, measured, framerate, drr_db, room_seed):
 
 
 def _render_windows(ctx, waves, centers, coefs, cfg, LPF, CUTOFF, precision, snrs=(), level=None, seed=0, rirs=(), room=None, firs=None,
-                    mix=None, masker=None):
+                    mix=None, masker=None, cutoff=None):
     """Normalised windows of some files through f2_input_batch_noisy, RENDER_GROUP files per call, every file at snrs[level]
     (level None: clean); with `room`, through f2_input_batch_wet with every file in rirs[room]; with `firs` (a filter per level),
     through f2_input_batch_coloured; with `mix` (a (C, C) matrix), through f2_input_batch_smeared with every file mixed by it; with
-    `masker` (recordings, masker_of, masker_snrs, level), through f2_input_batch_masked with every file at that masker level"""
+    `masker` (recordings, masker_of, masker_snrs, level), through f2_input_batch_masked with every file at that masker level; with
+    `cutoff` (cutoffs, level), through f2_input_batch_filtered with the envelopes of every file low-passed at cutoffs[level] (LPF
+    must be off)"""
     Cn = coefs.shape[0]
     out = numpy.empty((int(sum(len(c) for c in centers)), cfg.dots_per_input, Cn), numpy.float32)
     row = 0
@@ -393,7 +415,12 @@ def _render_windows(ctx, waves, centers, coefs, cfg, LPF, CUTOFF, precision, snr
                  precision, center_offsets, numpy.concatenate(cs), cfg.radius, cfg.step, True)
         rooms = (rirs if room is not None else (), None if room is None else numpy.full(len(ws), room, numpy.int32))
         back = (level_of, g, seed, out[row:row + n], _lib.MEM_HOST)
-        if masker is not None:
+        if cutoff is not None:
+            mk = (None, None, (), None) if masker is None else (masker[0], masker[1], masker[2], numpy.full(len(ws), masker[3], numpy.int32))
+            ctx.input_batch_filtered(*front, *rooms, snrs, firs, *back[:3], None if mix is None else mix[None],
+                                     None if mix is None else numpy.zeros(len(ws), numpy.int32), *mk, cutoff[0],
+                                     numpy.full(len(ws), cutoff[1], numpy.int32), *back[3:])
+        elif masker is not None:
             ctx.input_batch_masked(*front, *rooms, snrs, firs, *back[:3], None, None, masker[0], masker[1], masker[2],
                                    numpy.full(len(ws), masker[3], numpy.int32), *back[3:])
         elif mix is not None:
@@ -409,7 +436,7 @@ def _render_windows(ctx, waves, centers, coefs, cfg, LPF, CUTOFF, precision, snr
 
 
 def TrainFromWav(labelFile=None, LPF=False, CUTOFF=100, snrs=(), seed=None, ctx=None, verbose=1, on_epoch=None, t60s=(), rirs=(),
-                 drr_db=0.0, colours=(), noise_taps=1025, spreads=(), bands=(), maskers=(), masker_snrs=()):
+                 drr_db=0.0, colours=(), noise_taps=1025, spreads=(), bands=(), maskers=(), masker_snrs=(), cutoffs=()):
     """`cnn train --engine hip --from-wav`: trains on windows rendered on the device from the WAV files of the label CSV.
 
     The TRAIN files go to the trainer once (Trainer.set_waves); the TEST files become normalised windows once, clean - the
@@ -454,6 +481,13 @@ def TrainFromWav(labelFile=None, LPF=False, CUTOFF=100, snrs=(), seed=None, ctx=
     noise. The other generators are drawn exactly as without maskers. The TEST files are also validated once per masker level
     (f2_input_batch_masked, VALIDATION_NOISE_SEED): the history gains 'val_acc_masker' / 'val_loss_masker' and augment gains
     maskers (the files), masker_snrs, masker_levels (a name per level) and masker_seed per epoch.
+    With `cutoffs` (Hz; the levels of `cnn lpfsweep`, at most 64, every one inside (0, 8000); not together with LPF) every epoch
+    also draws, from numpy.random.default_rng([seed, CUTOFF_STREAM]), an envelope cutoff in [0, Kc] per TRAIN file (Kc: unfiltered;
+    draw_epoch_cutoffs) and renders through Trainer.render / render_wet(cutoffs=..., cutoff_of=...): the unfiltered envelopes of the
+    file are low-passed at that cutoff before its windows are gathered (f2_trainer_render_filtered). Bad cutoffs raise ValueError
+    before any file is read. The other generators are drawn exactly as without cutoffs. The TEST files are validated unfiltered as
+    before and once more per cutoff, clean, dry and sharp (f2_input_batch_filtered): the history gains 'val_acc_cutoff' /
+    'val_loss_cutoff' and augment gains cutoffs.
     on_epoch(iterations, trainer), if given, is called after each epoch's render, before its steps (for tests and for looking at
     what the network is about to see).
     BATCH_SIZE and EPOCHS come from configF2CNN.conf. Returns (F2CNNModel, history)."""
@@ -500,6 +534,12 @@ def TrainFromWav(labelFile=None, LPF=False, CUTOFF=100, snrs=(), seed=None, ctx=
         masker_level_snrs = tuple(v for _, _, v in masker_grid)
         masker_names = ['{} {}dB'.format(name, _level_text(v)) for _, name, v in masker_grid]
     Kk = len(masker_names)
+    # (the envelope cutoffs likewise)
+    cutoffs = check_cutoffs(cutoffs)
+    Kc = len(cutoffs)
+    if Kc and LPF:
+        raise ValueError("envelope cutoffs per file (cutoffs) and LPF exclude each other: the cutoffs filter unfiltered envelopes")
+    cutoff_names = ['{:g} Hz'.format(v) for v in cutoffs]
     # (the mixing matrices likewise: a bad spread or number of bands is refused here, with smear.py's message)
     spreads, bands = tuple(float(v) for v in spreads), tuple(bands)
     centre_freqs, coefs = filterbank_from_config(cfg)
@@ -534,6 +574,8 @@ def TrainFromWav(labelFile=None, LPF=False, CUTOFF=100, snrs=(), seed=None, ctx=
         print('spectral resolutions:', ', '.join(smear_names))
     if Kk:
         print('maskers:', ', '.join(masker_names))
+    if Kc:
+        print('envelope cutoffs:', ', '.join(cutoff_names))
     coefs = numpy.ascontiguousarray(coefs, dtype=numpy.float64)
     ctx = ctx or _lib.default_context()
     try:
@@ -551,6 +593,9 @@ def TrainFromWav(labelFile=None, LPF=False, CUTOFF=100, snrs=(), seed=None, ctx=
         for k in range(Kk if len(y_test) else 0):
             val.append(_render_windows(ctx, [waves[j] for j in test], [lw.centers[j] for j in test], coefs, cfg, LPF, CUTOFF,
                                        FFT_PRECISION, seed=VALIDATION_NOISE_SEED, masker=(recordings, masker_of, masker_level_snrs, k)))
+        for c in range(Kc if len(y_test) else 0):
+            val.append(_render_windows(ctx, [waves[j] for j in test], [lw.centers[j] for j in test], coefs, cfg, LPF, CUTOFF,
+                                       FFT_PRECISION, cutoff=(cutoffs, c)))
         x_val, y_val = numpy.concatenate(val), numpy.tile(y_test, len(val))
         groups = numpy.repeat(numpy.arange(len(val), dtype=numpy.int32), len(y_test))
         trainer, rng = _hip_trainer(cfg.dots_per_input, coefs.shape[0], seed, 1e-4, 1e-6, ctx)
@@ -564,7 +609,9 @@ def TrainFromWav(labelFile=None, LPF=False, CUTOFF=100, snrs=(), seed=None, ctx=
         val_smear = {"val_acc_smear": [[] for _ in range(Km)], "val_loss_smear": [[] for _ in range(Km)]}
         masker_rng = numpy.random.default_rng([seed, MASKER_STREAM])
         masker_seeds, val_masker = [], {"val_acc_masker": [[] for _ in range(Kk)], "val_loss_masker": [[] for _ in range(Kk)]}
-        if not K and not Kr and not Km and not Kk:
+        cutoff_rng = numpy.random.default_rng([seed, CUTOFF_STREAM])
+        val_cutoff = {"val_acc_cutoff": [[] for _ in range(Kc)], "val_loss_cutoff": [[] for _ in range(Kc)]}
+        if not K and not Kr and not Km and not Kk and not Kc:
             trainer.render()
 
         def run_epoch():
@@ -580,12 +627,14 @@ def TrainFromWav(labelFile=None, LPF=False, CUTOFF=100, snrs=(), seed=None, ctx=
                 masking = dict(maskers=recordings, masker_of=masker_of, masker_snrs=masker_level_snrs, masker_level_of=masker_level_of)
                 if not K:                                      # (the one seed of a render draws the segments too)
                     noise_seed = masker_seed
+            if Kc:                                             # (likewise only when asked for)
+                masking.update(cutoffs=cutoffs, cutoff_of=draw_epoch_cutoffs(cutoff_rng, Kc, len(train)))
             if Kr:
                 room_of, room_seed = draw_epoch_rooms(room_rng, Kr, len(train))
                 room_seeds.append(room_seed)
                 trainer.render_wet(build_rooms(t60s, measured, cfg.framerate, drr_db, room_seed), room_of, level_snrs, level_of, noise_seed,
                                    firs=firs, mixes=mixes, mix_of=mix_of, **masking)
-            elif K or Km or Kk:
+            elif K or Km or Kk or Kc:
                 trainer.render(level_snrs, level_of, noise_seed, firs=firs, mixes=mixes, mix_of=mix_of, **masking)
             if on_epoch:
                 on_epoch(trainer.iterations, trainer)
@@ -593,7 +642,7 @@ def TrainFromWav(labelFile=None, LPF=False, CUTOFF=100, snrs=(), seed=None, ctx=
 
         def validate():
             if not len(y_test):
-                for per in (val_snr, val_room, val_smear, val_masker):
+                for per in (val_snr, val_room, val_smear, val_masker, val_cutoff):
                     for k in per:
                         for per_level in per[k]:
                             per_level.append(float("nan"))
@@ -613,11 +662,15 @@ def TrainFromWav(labelFile=None, LPF=False, CUTOFF=100, snrs=(), seed=None, ctx=
             for k in range(Kk):
                 val_masker["val_acc_masker"][k].append(float(acc[K + Kr + Km + 1 + k]))
                 val_masker["val_loss_masker"][k].append(float(loss[K + Kr + Km + 1 + k]))
-            if verbose and (K or Kr or Km or Kk):
+            for c in range(Kc):
+                val_cutoff["val_acc_cutoff"][c].append(float(acc[K + Kr + Km + Kk + 1 + c]))
+                val_cutoff["val_loss_cutoff"][c].append(float(loss[K + Kr + Km + Kk + 1 + c]))
+            if verbose and (K or Kr or Km or Kk or Kc):
                 print("    val_acc clean {:.4f}".format(acc[0]) + "".join(" | {} {:.4f}".format(s, a) for s, a in zip(level_names, acc[1:])) +
                       "".join(" | room {} {:.4f}".format(r, a) for r, a in enumerate(acc[K + 1:K + Kr + 1])) +
                       "".join(" | {} {:.4f}".format(s, a) for s, a in zip(smear_names, acc[K + Kr + 1:])) +
-                      "".join(" | {} {:.4f}".format(s, a) for s, a in zip(masker_names, acc[K + Kr + Km + 1:])))
+                      "".join(" | {} {:.4f}".format(s, a) for s, a in zip(masker_names, acc[K + Kr + Km + 1:])) +
+                      "".join(" | lpf {} {:.4f}".format(s, a) for s, a in zip(cutoff_names, acc[K + Kr + Km + Kk + 1:])))
             return float(loss[0]), float(acc[0])
 
         model, history = fit_epochs(run_epoch, validate, trainer.model, len(y_train), epochs, verbose)
@@ -633,13 +686,15 @@ def TrainFromWav(labelFile=None, LPF=False, CUTOFF=100, snrs=(), seed=None, ctx=
         history.update(val_smear)
     if Kk:
         history.update(val_masker)
+    if Kc:
+        history.update(val_cutoff)
     model.save('last_trained_model')
     print("Model saved as 'last_trained_model'.")
     if len(y_test):
         print('Test loss:', history["val_loss"][-1])
         print('Test accuracy:', history["val_acc"][-1])
     results = dict(history)
-    if K or Kr or Km or Kk:
+    if K or Kr or Km or Kk or Kc:
         results["augment"] = {"snrs": list(snrs), "seed": int(seed), "noise_seed": noise_seeds}
     if colours:
         results["augment"].update({"colours": [name for _, name, _ in grid], "level_snr_db": list(level_snrs), "noise_taps": int(noise_taps)})
@@ -650,6 +705,8 @@ def TrainFromWav(labelFile=None, LPF=False, CUTOFF=100, snrs=(), seed=None, ctx=
     if Kk:
         results["augment"].update({"maskers": list(maskers), "masker_snrs": list(masker_snrs), "masker_levels": list(masker_names),
                                    "masker_seed": masker_seeds})
+    if Kc:
+        results["augment"].update({"cutoffs": list(cutoffs)})
     with open('last_trained_model_results.json', 'w') as fp:
         json.dump(results, fp)
     print("History saved as 'last_trained_model_results.json'")

@@ -13,6 +13,7 @@ A trainer can own the waves instead of the windows and rebuild the windows under
     t.render(snrs=(20, 10), level_of=levels, seed=s)                # utterance b at snrs[levels[b]], len(snrs) = clean
     t.render_wet(rirs=[h0, h1], room_of=rooms, snrs=(20, 10), level_of=levels, seed=s)   # ... in room rirs[rooms[b]] first
     t.render(snrs=(20, 10), level_of=levels, seed=s, firs=[pink, speech])   # ... under noise of the colour firs[levels[b]]
+    t.render(snrs=(20, 10), level_of=levels, seed=s, cutoffs=(5, 50), cutoff_of=cut)   # ... envelopes low-passed at cutoffs[cut[b]] Hz
     x, y = t.windows()                                              # what the network is about to see
 """
 import numpy as np
@@ -77,9 +78,12 @@ class Trainer:
                                    y.astype(np.uint8), int(radius), int(step), group)
 
     def _render(self, wet, rirs, room_of, snrs, level_of, seed, firs, mixes, mix_of, maskers=None, masker_of=None, masker_snrs=(),
-                masker_level_of=None):
+                masker_level_of=None, cutoffs=None, cutoff_of=None):
         """the entry of render (wet False: no rooms) / render_wet: the lowest that has every stage asked for"""
-        if maskers is not None:
+        if cutoffs is not None:
+            self.ctx.trainer_render_filtered(self.handle, rirs, room_of, snrs, firs, level_of, seed, mixes, mix_of, self.channels, maskers,
+                                             masker_of, masker_snrs, masker_level_of, cutoffs, cutoff_of)
+        elif maskers is not None:
             self.ctx.trainer_render_masked(self.handle, rirs, room_of, snrs, firs, level_of, seed, mixes, mix_of, self.channels, maskers,
                                            masker_of, masker_snrs, masker_level_of)
         elif mixes is not None:
@@ -92,7 +96,7 @@ class Trainer:
             self.ctx.trainer_render(self.handle, snrs, level_of, seed)
 
     def render(self, snrs=(), level_of=None, seed=0, firs=None, mixes=None, mix_of=None, maskers=None, masker_of=None, masker_snrs=(),
-               masker_level_of=None):
+               masker_level_of=None, cutoffs=None, cutoff_of=None):
         """Rebuild the training windows from the stored waves: utterance b at snrs[level_of[b]] dB, clean where level_of[b] ==
         len(snrs) or level_of is None; the noise of an utterance depends on (seed, its level, its number) alone. firs (one 1-D
         float64 filter per level): the noise of level l is filtered with firs[l] (f2_trainer_render_coloured); None: white.
@@ -100,15 +104,20 @@ class Trainer:
         before they are normalised, sharp where mix_of[b] == K (f2_trainer_render_smeared); None: the render without them.
         maskers (1-D float64 recordings), masker_of (the recording of each masker level), masker_snrs (its SNR) and masker_level_of:
         utterance b is mixed with a segment of maskers[masker_of[l]] at masker_snrs[l] dB, l = masker_level_of[b], before the noise;
-        no masker where l == len(masker_snrs) (f2_trainer_render_masked); None: the render without them."""
-        self._render(False, (), None, snrs, level_of, seed, firs, mixes, mix_of, maskers, masker_of, masker_snrs, masker_level_of)
+        no masker where l == len(masker_snrs) (f2_trainer_render_masked); None: the render without them.
+        cutoffs (Hz) and cutoff_of: the unfiltered envelopes of utterance b are low-passed at cutoffs[cutoff_of[b]] before the
+        windows are gathered, left unfiltered where cutoff_of[b] == len(cutoffs) (f2_trainer_render_filtered); the waves must have
+        been set with lpf=False. None: the render without them."""
+        self._render(False, (), None, snrs, level_of, seed, firs, mixes, mix_of, maskers, masker_of, masker_snrs, masker_level_of, cutoffs,
+                     cutoff_of)
 
     def render_wet(self, rirs=(), room_of=None, snrs=(), level_of=None, seed=0, firs=None, mixes=None, mix_of=None, maskers=None,
-                   masker_of=None, masker_snrs=(), masker_level_of=None):
+                   masker_of=None, masker_snrs=(), masker_level_of=None, cutoffs=None, cutoff_of=None):
         """render() with a room per utterance: utterance b is convolved with rirs[room_of[b]] (float64 arrays), dry where
         room_of[b] == len(rirs) or room_of is None, and then noised at snrs[level_of[b]] dB of the reverberant signal. Without
-        rooms it is render(), bit for bit. firs, mixes, mix_of and the maskers (which stay dry): as in render()."""
-        self._render(True, rirs, room_of, snrs, level_of, seed, firs, mixes, mix_of, maskers, masker_of, masker_snrs, masker_level_of)
+        rooms it is render(), bit for bit. firs, mixes, mix_of, the maskers (which stay dry), cutoffs and cutoff_of: as in render()."""
+        self._render(True, rirs, room_of, snrs, level_of, seed, firs, mixes, mix_of, maskers, masker_of, masker_snrs, masker_level_of,
+                     cutoffs, cutoff_of)
 
     def windows(self, first=0, count=None):
         """(x, y): rows first .. first + count - 1 of the training set as it stands on the device (count None: to the end)"""

@@ -1376,6 +1376,62 @@ int f2_trainer_render_masked(f2_ctx* ctx, f2_trainer* trainer, const double* rir
                              int R, const int32_t* masker_of /* host, Kk */, int Kk,
                              const int32_t* masker_level_of /* host, B, or NULL */);
 
+/* ---- `cnn train --augment-cutoffs`: an envelope cutoff per utterance ------------------------------------------------------------
+ * f2_lowpass_levels makes every utterance at every cutoff; training needs one cutoff per utterance, new every epoch. (f2_version
+ * stays 115 with these three entries: look the symbols up to find out whether a build has them.)
+ * A cutoff level l < K is cutoff_hz[l] in Hz; level K is unfiltered, as in f2_lowpass_levels. cutoff_hz and cutoff_of are always
+ * host pointers. Limits and errors of cutoff_hz and K are f2_lowpass_levels' (K <= 64: beyond, F2_ERR_UNSUPPORTED; every cutoff
+ * finite and inside (0, 8000): F2_ERR_INVALID, the message names the cutoff) except that K == 0 is allowed; a cutoff_of entry
+ * outside [0, K]: F2_ERR_INVALID, the message names the utterance. All before anything is launched or written.
+ *   kernel    k_lowpass_pick: one workgroup per row (utterance, channel) walks the segments of k_lowpass_levels with the same loads,
+ *             the same filter call and the same carried state, through one device function the two kernels share, with the pair
+ *             {b0, a1} of the row's level. Plain vector stores.
+ *
+ * f2_lowpass_pick: utterance b of env at level cutoff_of[b], in the layout of env (C * offsets[B] doubles). Bit for bit block
+ * cutoff_of[b] of f2_lowpass_levels for that utterance - whatever the batch around it, K or the other cutoffs - and at level K bit
+ * for bit the input. filtered == env is allowed for F2_MEM_DEVICE and filters in place: nothing of an unfiltered utterance is then
+ * read or written. cutoff_of == NULL or K == 0: a copy (nothing at all in place), and cutoff_hz may be NULL. Errors:
+ * f2_lowpass_levels' of the batch, then the stage's. B == 0 or offsets[B] == 0: F2_OK.
+ *
+ * f2_input_batch_filtered: f2_input_batch_masked's arguments plus the cutoff stage behind masker_level_of. The stages run in the
+ * order room, masker, noise, envelopes, cutoff, (mixing) gather. With the stage (Kc > 0 and cutoff_of != NULL) the envelopes of
+ * the call are computed with lpf = 0 and filtered in place by k_lowpass_pick before the gather: the windows of utterance b are bit
+ * for bit f2_gather_windows / f2_gather_windows_mixed on f2_lowpass_pick on the unfiltered envelopes of the stages before. A call
+ * with the stage and lpf = 1 is F2_ERR_INVALID (the message names both). Without the stage: bit for bit f2_input_batch_masked (it
+ * is that call), lpf = 1 included. Errors: those of f2_input_batch_masked, then the cutoff stage's, all before a launch.
+ *
+ * f2_trainer_render_filtered: f2_trainer_render_masked's arguments plus the same stage. Group g is bit for bit
+ * f2_input_batch_filtered on its utterances; the filter coefficients go up once per call. A trainer whose waves were set with
+ * lpf = 1 refuses the stage (F2_ERR_INVALID). f2_trainer_render_masked is this call without cutoffs, bit for bit.
+ */
+int f2_lowpass_pick(f2_ctx* ctx, const double* env /* C * offsets[B], mem_space */, const int64_t* offsets /* host, B+1 */, int B,
+                    int C, const double* cutoff_hz /* host, K */, int K,
+                    const int32_t* cutoff_of /* host, B, each in [0, K], or NULL */,
+                    double* filtered /* C * offsets[B], mem_space; may be env in device memory */, int mem_space);
+int f2_input_batch_filtered(f2_ctx* ctx, const void* wave, int wave_dtype, const int64_t* offsets, const double* coefs, int B, int C,
+                            int lpf, double cutoff_hz, int fft_precision, const int64_t* center_offsets, const int64_t* centers,
+                            int radius, int step, int normalize, const double* rir, const int64_t* rir_offsets, int Kr,
+                            const int32_t* room_of, const double* snr_db, const double* fir /* or NULL: white */,
+                            const int64_t* fir_offsets, int K, const int32_t* level_of, uint32_t first_utterance, uint64_t seed,
+                            const double* mix /* host, (Km, C, C), or NULL: sharp */, int Km,
+                            const int32_t* mix_of /* host, B, each in [0, Km], or NULL */, const double* masker_snr_db /* host, Kk */,
+                            const double* masker /* host, or NULL: no maskers */, const int64_t* masker_offsets /* host, R+1 */, int R,
+                            const int32_t* masker_of /* host, Kk */, int Kk,
+                            const int32_t* masker_level_of /* host, B, each in [0, Kk], or NULL */,
+                            const double* cutoff_levels_hz /* host, Kc, or NULL: no cutoffs */, int Kc,
+                            const int32_t* cutoff_of /* host, B, each in [0, Kc], or NULL */, float* windows, int mem_space);
+int f2_trainer_render_filtered(f2_ctx* ctx, f2_trainer* trainer, const double* rir, const int64_t* rir_offsets, int Kr,
+                               const int32_t* room_of /* host, B, or NULL */, const double* snr_db,
+                               const double* fir /* or NULL: white */, const int64_t* fir_offsets, int K,
+                               const int32_t* level_of /* host, B, or NULL */, uint64_t seed,
+                               const double* mix /* host, (Km, C, C), or NULL: sharp */, int Km,
+                               const int32_t* mix_of /* host, B, or NULL */, const double* masker_snr_db /* host, Kk */,
+                               const double* masker /* host, or NULL: no maskers */, const int64_t* masker_offsets /* host, R+1 */,
+                               int R, const int32_t* masker_of /* host, Kk */, int Kk,
+                               const int32_t* masker_level_of /* host, B, or NULL */,
+                               const double* cutoff_levels_hz /* host, Kc, or NULL: no cutoffs */, int Kc,
+                               const int32_t* cutoff_of /* host, B, or NULL */);
+
 /* ---- `cnn eval --segments`: decisions smoothed into transitions ---------------------------------------------------------------
  * The reference stops at a rising / falling label per row (Evaluating.py:73-90); where the network is unsure the labels flicker,
  * and a run-length reading of them is mostly noise. Here: the most probable two-state sequence under a switching penalty, its
